@@ -21,13 +21,16 @@ Workloads (BASELINE.json configs):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement), including
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times --steps steps and reports
+metric / value / unit / higher_is_better / dtype / ms_per_step; --dump-outputs DIR also writes what the last timed step computed
+(see dump_batch_outputs / dump_consumer_outputs).  --full adds everything else, with extra runs of its own:
   roofline      for the dominant kernel: algorithmic bytes per launch / mean launch time (HIP events on the launch stream over the
-                timed region) vs the 8 TB/s HBM peak
+                timed region) vs the 8 TB/s HBM peak; the per-stage table from a few extra steps with every stage timed
   cpu_baseline  the CPU oracle (oracle/, kind "port": the reference itself cannot be built here) on the same frames and the same
                 call sequence: 1 thread (median / mean ms per frame, per-call ms) and one stream per host core
   parity_checked_frames  frames of the last timed step (or of the consumer's run) compared bit for bit with the oracle; the run
-                FAILS (exit 1) on a mismatch.
+                FAILS (exit 1) on a mismatch (0 without --full)
+  like_for_like, previous_rounds_scene, mean_segments (lines): 6144 frames per launch, the 'struct' scene, LSD segment counts.
 """
 import argparse
 import json
@@ -166,6 +169,49 @@ def depth_f32(depth_u16):
     return np.ascontiguousarray(depth_u16).astype(np.float32) * (np.float32(1.0) / np.float32(5000.0))   # u16 -> f32 is exact, one f32 product
 
 
+# ---- --dump-outputs: what a caller of the timed path receives, written as float arrays so that two builds compare output for output
+DUMP_FRAMES, DUMP_SEED = 64, 2024   # the fixed, seeded sample of a batch's frames (lines: about 20 MB in all)
+
+
+def write_dump(outdir, frames):
+    """frames: one dict name -> array (or count) per dumped frame.  DIR/<name>.npy holds the frames' arrays one after the other along
+    the first axis, DIR/<name>_rows.npy how many rows each frame has.  Records become one float64 column per field, u8 arrays
+    float32 and everything else float64: every value is exact."""
+    os.makedirs(outdir, exist_ok=True)
+    for name in frames[0]:
+        parts = []
+        for fr in frames:
+            a = np.asarray(fr[name])
+            if a.dtype.names:
+                a = np.stack([a[k].astype(np.float64) for k in a.dtype.names], -1).reshape(len(a), len(a.dtype.names))
+            parts.append(a.astype(np.float32 if a.dtype == np.uint8 else np.float64))
+        if parts[0].ndim == 0:
+            np.save(os.path.join(outdir, name + ".npy"), np.stack(parts))
+        else:
+            np.save(os.path.join(outdir, name + ".npy"), np.concatenate(parts, 0))
+            np.save(os.path.join(outdir, name + "_rows.npy"), np.array([len(p) for p in parts], np.float64))
+
+
+def dump_batch_outputs(pipe, P, torch, dev, B, outdir):
+    """The per-frame results of the last step (BatchPipeline.fetch_frame) for DUMP_FRAMES frames of the batch.  Point and line matches
+    are cut to their queries: one entry per key point / key line of the predecessor frame (f - 1, cyclic in the batch)."""
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(B, min(B, DUMP_FRAMES), replace=False))
+    nq = pipe.nq.cpu().numpy()
+    nkl = None
+    if pipe.lines:
+        d_nkl = pipe.le.results_device()[3]
+        nkl = torch.as_tensor(P._DevArray(d_nkl, (B,), "<i4"), device=dev).cpu().numpy()
+    frames = []
+    for f in sample:
+        got = pipe.fetch_frame(int(f))
+        got["match"] = got["match"][:nq[f]]
+        if nkl is not None:
+            got["lmatch"] = got["lmatch"][:nkl[(f - 1) % B]]
+        frames.append(got)
+    write_dump(outdir, frames)
+    return len(sample)
+
+
 class stdout_to_stderr:
     """RCCL prints a version banner on STDOUT when a communicator is created; the contract is one JSON line there."""
 
@@ -199,28 +245,26 @@ def run_consumer(args):
     scene = args.scene or "struct"
     gray, depth = D.synth_stream(w, h, nframes, scene, seed_for(0))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = CB.run(gray, depth, nf, nl, True, budget_s=20.0, min_frames=min(200, max(16, nframes - 10)), warm=min(10, nframes // 4))
     tmp = tempfile.mkdtemp()
     fpath = os.path.join(tmp, "frames.bin")
     D.write_frames(fpath, gray, depth)
-    ncheck = min(8, nframes)
-    rpath = os.path.join(tmp, "results.bin")
-    cpath = os.path.join(tmp, "check.bin")
-    D.write_frames(cpath, gray[:ncheck], depth[:ncheck])
-    D.run(cpath, nf, nl, 0, results_path=rpath, lookahead=K)        # untimed: the results the parity check reads
-    got = D.read_results(rpath, ncheck)
-    ref = D.oracle_sequence(gray[:ncheck], depth[:ncheck], nf, nl)
-    for t in range(ncheck):
-        D.compare(got[t], ref[t], f"frame {t}: ")
-    r = D.run(fpath, nf, nl, args.warmup, lookahead=K)               # the timed run: host clock around every frame, copies included
-    rs = D.run(fpath, nf, nl, args.warmup, stages=True, lookahead=K)  # same again with the library's per-kernel HIP-event timers on
-    stages = rs.get("gpu_stage_ms_per_frame", {})
-    dom = max(stages, key=lambda s: stages[s]) if stages else "line.lsd_grow"
-    scale_bytes = (w * h) / float(W * H)
-    dom_bytes = int(STAGE_BYTES_PER_FRAME.get(dom, 0) * scale_bytes)
-    dom_ms = stages.get(dom, 0.0)
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    ncheck = min(8, nframes) if args.full else 0
+    if ncheck:
+        rpath = os.path.join(tmp, "results.bin")
+        cpath = os.path.join(tmp, "check.bin")
+        D.write_frames(cpath, gray[:ncheck], depth[:ncheck])
+        D.run(cpath, nf, nl, 0, results_path=rpath, lookahead=K)        # untimed: the results the parity check reads
+        got = D.read_results(rpath, ncheck)
+        ref = D.oracle_sequence(gray[:ncheck], depth[:ncheck], nf, nl)
+        for t in range(ncheck):
+            D.compare(got[t], ref[t], f"frame {t}: ")
+    # the timed run: host clock around every frame, copies included (dropin_main writes a frame's results after its clock stops)
+    dpath = os.path.join(tmp, "timed_results.bin") if args.dump_outputs else None
+    r = D.run(fpath, nf, nl, args.warmup, results_path=dpath, lookahead=K)
+    if dpath is not None:   # the last frame the consumer tracked
+        write_dump(args.dump_outputs, D.read_results(dpath, nframes)[-1:])
     out = {
         "metric": ("frames/sec ORB+line extract+match, single-frame drop-in (B = 1), host buffers in / host results out" if K == 1 else
                    f"frames/sec ORB+line extract+match, Tracking loop with a look-ahead of {K} frames (FramePrefetcher), host buffers in / host results out"),
@@ -238,14 +282,23 @@ def run_consumer(args):
                    "frames_per_step_per_gpu": 1, "lookahead": K, "scene": scene, "mean_keypoints": r["mean_keypoints"], "mean_keylines": r["mean_keylines"],
                    "mean_matches": r["mean_matches"], "mean_line_matches": r["mean_line_matches"], "lsd_refine": "LSD_REFINE_ADV"},
         "latency_ms_per_frame": r["ms_per_frame"], "frame_ctor_ms": r["frame_ctor_ms"], "track_ms": r["track_ms"],
-        "calls_ms_mean": r["calls_ms_mean"], "gpu_stage_ms_per_frame": stages,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 7), "traffic": None, "algorithmic_bytes_per_launch": dom_bytes,
-                     "ms_per_launch": round(dom_ms, 4),
-                     "note": ("one frame per launch: a serial chain on one wave, latency-bound (DESIGN.md §5)" if K == 1 else
-                              f"{K} frames per launch; time and bytes are per frame (launch / {K})")},
+        "calls_ms_mean": r["calls_ms_mean"],
         "parity_checked_frames": ncheck,
     }
+    if args.full:
+        rs = D.run(fpath, nf, nl, args.warmup, stages=True, lookahead=K)  # the timed run again with the library's per-kernel HIP-event timers on
+        stages = rs.get("gpu_stage_ms_per_frame", {})
+        dom = max(stages, key=lambda s: stages[s]) if stages else "line.lsd_grow"
+        scale_bytes = (w * h) / float(W * H)
+        dom_bytes = int(STAGE_BYTES_PER_FRAME.get(dom, 0) * scale_bytes)
+        dom_ms = stages.get(dom, 0.0)
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        out["gpu_stage_ms_per_frame"] = stages
+        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 7), "traffic": None, "algorithmic_bytes_per_launch": dom_bytes,
+                           "ms_per_launch": round(dom_ms, 4),
+                           "note": ("one frame per launch: a serial chain on one wave, latency-bound (DESIGN.md §5)" if K == 1 else
+                                    f"{K} frames per launch; time and bytes are per frame (launch / {K})")}
     if cpu is not None:
         out["cpu_baseline"] = cpu
     print(json.dumps(out), flush=True)
@@ -258,10 +311,11 @@ def under_profiler():
 
 
 def build_once():
-    """libpslfe.so is built by ONE process (the others wait on a file lock and find it up to date)."""
+    """libpslfe.so is built by ONE process (the others wait on a file lock and find it up to date).  The lock is the tree's own
+    build script, opened for reading: a fixed path in the shared temporary directory would belong to whoever created it first."""
     import fcntl
     import psl_slam_amd as P
-    with open(os.path.join(tempfile.gettempdir(), "pslfe_build.lock"), "w") as lk:
+    with open(os.path.join(ROOT, "psl-slam_amd", "build.py")) as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         try:
             P.build()
@@ -391,6 +445,12 @@ def main():
     ap.add_argument("--no-like-for-like", action="store_true", help="skip the extra steps at 6144 frames per launch after the timed region")
     ap.add_argument("--lookahead", type=int, default=1, help="dropin / tracking: frames extracted per launch by the FramePrefetcher (1 = one frame at a time)")
     ap.add_argument("--parity-frames", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: CPU baseline, parity with the oracle, per-stage table and roofline, like-for-like and "
+                         "previous-scene steps (--no-cpu-baseline / --no-like-for-like / --parity-frames 0 leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64): the per-frame "
+                         "results of a fixed sample of DUMP_FRAMES frames of the batch (lines / orb), or of the last frame (dropin / tracking)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--prepare-inputs", action="store_true", help="generate (and cache in /tmp) the input frames of the workload, then exit: run before profiler passes")
     args = ap.parse_args()
@@ -433,11 +493,11 @@ def main():
     gray256, depth8 = distinct_frames(W, H, scene, seed_for(rank), serial=profiled)
     # continuity with rounds 1 - 2, whose headline ran on the 'struct' scene (29 keylines per frame): a few steps on it after the timed region
     gray_prev = None
-    if LINES and scene == "sticks" and world == 1 and not args.host_io and not args.no_like_for_like and not profiled:
+    if args.full and LINES and scene == "sticks" and world == 1 and not args.host_io and not args.no_like_for_like and not profiled:
         gray_prev, _ = distinct_frames(W, H, "struct", seed_for(rank))
     ND = len(gray256)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not profiled:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not profiled:
         import cpu_baseline as CB
         d32 = depth_f32(depth8[0])
         cpu = CB.run(gray256[:64], np.broadcast_to(d32, (64,) + d32.shape), NFEATURES, 200, LINES, budget_s=20.0, min_frames=200, warm=10)
@@ -560,7 +620,7 @@ def main():
                 host_io.setdefault("ev_d2h", [None, None])[k] = ev
 
     for c in pipe.contexts():
-        c.profile(True)
+        c.profile(args.full)
     step()  # first call allocates buffers / builds tables (not one of the W warm-up steps)
     torch.cuda.synchronize(dev)
     if world > 1 or args.host_io:
@@ -600,19 +660,21 @@ def main():
                     out[s] = {"ms_per_launch": ms / n, "launches": n, "steps": nsteps}
         return out
 
-    # Warm-up, with every stage timed: finds the dominant stage.  Each timed stage puts two HIP event records between
+    # --full: warm-up with every stage timed finds the dominant stage.  Each timed stage puts two HIP event records between
     # kernels (~10 us of idle GPU per stage boundary), so inside the timed region only the dominant stage is timed.
-    if args.warmup > 0:
+    if args.full and args.warmup > 0:
         for c in pipe.contexts():
             c.profile_reset()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    warm = read_stages(max(1, args.warmup))
-    dom = max(warm, key=lambda s: warm[s]["ms_per_launch"])
-    for c in pipe.contexts():
-        c.profile_reset()
-        c.profile_only(dom)
+    dom = None
+    if args.full:
+        warm = read_stages(max(1, args.warmup))
+        dom = max(warm, key=lambda s: warm[s]["ms_per_launch"])
+        for c in pipe.contexts():
+            c.profile_reset()
+            c.profile_only(dom)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -630,11 +692,13 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    dom_stage = read_stages(args.steps)[dom]  # the dominant kernel over exactly the timed steps
+    dom_stage = read_stages(args.steps)[dom] if args.full else None  # the dominant kernel over exactly the timed steps
+    if rank == 0 and args.dump_outputs:
+        dump_batch_outputs(pipe, P, torch, dev, B, args.dump_outputs)
 
     # ---- parity: frames of the LAST TIMED STEP against the oracle (bit for bit); a mismatch fails the run
     nchk = 0
-    if rank == 0 and args.parity_frames > 0:
+    if args.full and rank == 0 and args.parity_frames > 0:
         cand = sorted(set(int(v) for v in np.linspace(0, B - 1, args.parity_frames)) | {0, min(B - 1, 32), B - 1})[:max(args.parity_frames, 3)]
         cache = {}
         cam = pipe.cam
@@ -668,25 +732,28 @@ def main():
                      "mean_lbd_pixels_per_line": round(float((npx.sum() / max(1, int(nkl.sum().item()))).item()), 1),
                      "lbd_sample_bytes_per_frame": int(round(float(npx.mean().item()) * 63 * 4))}
 
-    # per-stage table: a few extra steps after the timed region, every stage timed
-    for c in pipe.contexts():
-        c.profile_reset()
-        c.profile_only(None)
-    for _ in range(min(args.steps, 5)):
-        step()
-    if gather is not None:
-        gather.wait()
-    torch.cuda.synchronize(dev)
-    stages = read_stages(min(args.steps, 5))
-    stages[dom] = dom_stage
     counts = torch.as_tensor(P.orb_results_as_arrays(pipe.orb, B)[2], device=dev)
     mean_kp = float(counts.float().mean().item())
     mean_matches = float(pipe.nmatches.float().mean().item())
     mean_lm = float(pipe.lnm.float().mean().item()) if LINES else 0.0
 
+    # per-stage table: a few extra steps after the timed region, every stage timed
+    stages = None
+    if args.full:
+        for c in pipe.contexts():
+            c.profile_reset()
+            c.profile_only(None)
+        for _ in range(min(args.steps, 5)):
+            step()
+        if gather is not None:
+            gather.wait()
+        torch.cuda.synchronize(dev)
+        stages = read_stages(min(args.steps, 5))
+        stages[dom] = dom_stage
+
     # like for like with rounds 1 - 2 and with runs that do not get 12288 frames into memory: 6144 frames per launch, 5 steps, untimed stages
     lfl = None
-    if LINES and B > 6144 and not args.no_like_for_like and stream_l is None:
+    if args.full and LINES and B > 6144 and not args.no_like_for_like and stream_l is None:
         for c in pipe.contexts():
             c.profile(False)
         nB[0] = 6144
@@ -727,7 +794,7 @@ def main():
                       "note": "the scene the headline of rounds 1 - 2 was measured on (overlapping polygons: ~29 keylines per frame), same pipeline object and "
                               "batch; BENCH_r02: 52 495.5 frames/s"}
     segs = None
-    if LINES and rank == 0 and not profiled:   # LSD segments in front of the merging, on 16 of the distinct frames (single-frame entry point; not under
+    if args.full and LINES and rank == 0 and not profiled:   # LSD segments in front of the merging, on 16 of the distinct frames (single-frame entry point; not under
         # a profiler: its single-frame launches would dilute the per-kernel averages of the trace)
         le1 = P.LINEextractor(1, 1.2, 200, 0.0, ctx=ctx)
         segs = round(float(np.mean([len(le1.lsd_detect(gray256[i])) for i in range(0, ND, max(1, ND // 16))])), 1)
@@ -742,10 +809,6 @@ def main():
         if line_load is not None:   # the LBD's gathers from the MEASURED sum of numOfPixels x 63 rows x 4 B instead of NL = 200, L = 100
             stage_bytes["line.lbd"] = line_load["lbd_sample_bytes_per_frame"] + 100 * int(round(line_load["mean_keylines"]))
             line_bytes = LINE_BYTES_PER_FRAME - (5040000 + 20000) + stage_bytes["line.lbd"]
-        dom_bytes = stage_bytes[dom] * B
-        dom_s = stages[dom]["ms_per_launch"] * 1e-3
-        achieved = dom_bytes / dom_s / 1e9
-        traffic, traffic_src = pmc_traffic(args.workload + ("" if scene in ("sticks", "desk") else "_" + scene), dom, B)
         per_frame = ORB_BYTES_PER_FRAME + MATCH_BYTES_PER_FRAME + (line_bytes if LINES else 0)
         io = ("host gray + depth(u16) in, host result records out inside the timed region (one H2D and one D2H per step on a copy stream: the next batch comes in "
               "and the previous records go out while a batch is computed)" if args.host_io else "frames resident in HBM")
@@ -770,21 +833,25 @@ def main():
                        "multi_gpu": ("independent stream per rank, no data-path collective; per-frame result records (counts, keypoints, descriptors, point "
                                      "matches, keylines, LBD descriptors, line equations, line matches, fans, planes) packed on the device and gathered "
                                      f"per batch: {gather_info['kind']}") if world > 1 else "single GPU"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": dom_bytes, "ms_per_launch": round(stages[dom]["ms_per_launch"], 4)},
             "pipeline_roofline": {"bytes_per_frame": per_frame,
                                   "achieved_GBs": round(fps / world * per_frame / 1e9, 2),
                                   "frac_of_8TBs": round(fps / world * per_frame / 1e9 / HBM_PEAK_GBS, 5),
                                   "note": "SURVEY.md §8(d)'s accounting with the LBD term taken from the measured keylines of this workload"},
-            "stages_ms_per_launch": {k: round(v["ms_per_launch"], 4) for k, v in stages.items()},
-            "stages_ms_per_step": {k: round(v["ms_per_launch"] * v["launches"] / max(1, v["steps"]), 4) for k, v in stages.items()},
-            # algorithmic bytes of a stage (per launch for the NFA stages, whose table entry is per launch; per step otherwise) / its time
-            "stages_frac_of_hbm_peak": {k: round(stage_bytes[k] * B / ((v["ms_per_launch"] if k in PER_LAUNCH_STAGES else
-                                                                        v["ms_per_launch"] * v["launches"] / max(1, v["steps"])) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                        for k, v in stages.items() if k in stage_bytes and v["ms_per_launch"] > 0},
             "parity_checked_frames": nchk,
         }
+        if stages is not None:
+            dom_bytes = stage_bytes[dom] * B
+            achieved = dom_bytes / (stages[dom]["ms_per_launch"] * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(args.workload + ("" if scene in ("sticks", "desk") else "_" + scene), dom, B)
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": dom_bytes, "ms_per_launch": round(stages[dom]["ms_per_launch"], 4)}
+            out["stages_ms_per_launch"] = {k: round(v["ms_per_launch"], 4) for k, v in stages.items()}
+            out["stages_ms_per_step"] = {k: round(v["ms_per_launch"] * v["launches"] / max(1, v["steps"]), 4) for k, v in stages.items()}
+            # algorithmic bytes of a stage (per launch for the NFA stages, whose table entry is per launch; per step otherwise) / its time
+            out["stages_frac_of_hbm_peak"] = {k: round(stage_bytes[k] * B / ((v["ms_per_launch"] if k in PER_LAUNCH_STAGES else
+                                                                             v["ms_per_launch"] * v["launches"] / max(1, v["steps"])) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                             for k, v in stages.items() if k in stage_bytes and v["ms_per_launch"] > 0}
         if gather_info is not None:
             out["gather"] = gather_info
         if prev_scene is not None:

@@ -77,8 +77,54 @@ def glue():
     print("glue", int((np.abs(r["lines3d"]).sum(1) > 0).sum()), len(r["pair"]), len(r["planes"]))
 
 
+def ref():
+    """ref_pins.npz: the outputs of the reference's standalone files (oracle/_ref, `make -C oracle _ref REF=<reference tree>`) on the
+    inputs of tests/test_oracle_ref_cpu.py, which pins the oracle against them without a reference tree.  Outputs and input CRCs only."""
+    import ctypes as C
+    import test_oracle_ref_cpu as T
+    rdir = os.path.join(ROOT, "oracle", "_ref")
+    out = {}
+    # the line grid walk (add_src/lineIterator.cpp): cells per walk and their CRC
+    li = C.CDLL(os.path.join(rdir, "libref_lineiterator.so"))
+    li.ref_line_iterator_walk.argtypes = [C.c_double] * 4 + [C.c_void_p, C.c_int]
+    cases = T.walk_cases()
+    a = np.zeros((4096, 2), np.int32)
+    counts, crcs = [], []
+    for c in cases:
+        n = li.ref_line_iterator_walk(*[float(v) for v in c], a.ctypes.data, 4096)
+        counts.append(n)
+        crcs.append(T.crc(a[:n]))
+    out.update(walk_cases_crc=T.crc(cases), walk_counts=np.array(counts, np.int32), walk_crc=np.array(crcs, np.uint32))
+    # nfa() / log_gamma() (Thirdparty/line_descriptor/src/ED_Lib/NFA.cpp)
+    nfa = C.CDLL(os.path.join(rdir, "libref_nfa.so"))
+    nfa.ref_log_gamma.argtypes, nfa.ref_log_gamma.restype = [C.c_double], C.c_double
+    nfa.ref_nfa.argtypes, nfa.ref_nfa.restype = [C.c_int, C.c_int, C.c_double, C.c_double], C.c_double
+    xs, nk = T.log_gamma_args(), T.nfa_cases()
+    out.update(nfa_inputs_crc=T.crc(xs, nk), lgamma_ref=np.array([nfa.ref_log_gamma(float(x)) for x in xs]),
+               nfa_ref=np.array([nfa.ref_nfa(*T.nfa_args(i, n, k)) for i, (n, k) in enumerate(nk)]),
+               nfa_exact_ref=np.array([nfa.ref_nfa(n, k, p, T.LOGNTS[0]) for n, k, p in T.NFA_EXACT]))
+    # BowVector / FeatureVector accumulation (Thirdparty/DBoW2), fed the oracle's (word, weight, node) stream
+    db = C.CDLL(os.path.join(rdir, "libref_dbow2.so"))
+    db.ref_bow_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
+    for case, (o, n) in enumerate(T.bow_inputs()):
+        m = max(n, 1)
+        bow_id, bow_val = np.zeros(m, np.int32), np.zeros(m, np.float64)
+        fv_node, fv_start, fv_idx = np.zeros(m, np.int32), np.zeros(m + 1, np.int32), np.zeros(m, np.int32)
+        nf = C.c_int()
+        w, wt, nid = (np.ascontiguousarray(o[key]) for key in ("word", "weight", "nid"))
+        nb = db.ref_bow_accumulate(w.ctypes.data, wt.ctypes.data, nid.ctypes.data, n, bow_id.ctypes.data, bow_val.ctypes.data, fv_node.ctypes.data,
+                                   fv_start.ctypes.data, fv_idx.ctypes.data, C.byref(nf))
+        nf = nf.value
+        out.update({f"bow{case}_in_crc": T.crc(w, wt, nid), f"bow{case}_id": bow_id[:nb], f"bow{case}_val": bow_val[:nb],
+                    f"bow{case}_fv_node": fv_node[:nf], f"bow{case}_fv_start": fv_start[:nf + 1], f"bow{case}_fv_idx": fv_idx[:fv_start[nf]]})
+    np.savez_compressed(os.path.join(HERE, "ref_pins.npz"), **out)
+    print("ref", len(cases), int(out["walk_counts"].sum()), len(xs), len(nk))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["lines", "main", "glue"]
+    if "ref" in which:
+        ref()
     if "lines" in which:
         lines()
     if "main" in which:

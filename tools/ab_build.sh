@@ -6,7 +6,7 @@ for rep in 1 2; do
 for f in "$@"; do
   PSLFE_EXTRA_FLAGS="$f" python psl-slam_amd/build.py --force > /dev/null 2>&1 || exit 1
   echo "== $f (run $rep)"
-  timeout -k 10 400 python bench.py $args 2>/dev/null | python -c "
+  timeout -k 10 400 python bench.py --full $args 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), d['ms_per_step'], {k: round(v, 2) for k, v in d.get('stages_ms_per_step', {}).items() if k in ('orb.fast', 'orb.blur', 'orb.describe')})" || exit 1
