@@ -353,6 +353,93 @@ int pslfe_orb_search_by_projection_last_device(pslfe_frame* cur, int slot0, int 
                                                const uint8_t* d_qdesc, const int32_t* d_nq, int qstride,
                                                int check_orientation, int32_t* d_match, int32_t* d_nmatches);
 
+/* ---- Projection of 3-D points into a frame: the part of both SearchByProjection variants before the window search.
+ *
+ * Arithmetic conventions (cv::Mat arithmetic is not in the reference tree):
+ *   - a float 3x3 * 3x1 (+ 3x1) product (Rcw*x3Dw+tcw, -Rcw.t()*tcw, Rlw*twc+tlw, mRwc*x3Dc+mOw): every row is the double sum,
+ *     in index order, of the exact double products (then + the double of the translation), rounded once to float;
+ *   - cv::norm and Mat::dot of float 3-vectors: double sums in index order (norm: sqrt in double, rounded to float);
+ *     viewCos = dot / dist in double, rounded to float;
+ *   - PredictScale: ceil(psl_log((double)ratio) / (double)mfLogScaleFactor) with ratio = mfMaxDistance / dist in float, clamped to
+ *     [0, nlevels-1] (ratio 0 or NaN -> 0, infinite -> nlevels-1); psl_log is the double log of psl-slam_amd/csrc/psl_f64math.h;
+ *   - a point with camera depth z <= 0 (z == 0 included, where the reference goes on with inf and reaches undefined behaviour in
+ *     GetFeaturesInArea), a NaN depth or a NaN pixel coordinate is not emitted.
+ * Every other operation is the reference's float operation, in its order.
+ *
+ * Emitted rows are compacted in point order (the reference's loop order, so the matchers' first-come-first-served order is the
+ * reference's); owner[q] is the point of row q.  A count larger than the row capacity is reported, never truncated silently:
+ * the device forms write the first qstride rows and the full count (the window searches read at most qstride rows); the host
+ * forms return PSLFE_E_CAPACITY with *nq set. */
+typedef struct PslPose {
+    float R[9];  /* rows 0..2, columns 0..2 of Frame::mTcw, row-major */
+    float t[3];  /* rows 0..2 of column 3 */
+} PslPose;
+/* LastFrame.mvpMapPoints[i]: state 0 = none, 1 = a map point with Observations()==0, 2 = with Observations()>0; | 8 = mvbOutlier[i].
+ * x, y, z = its GetWorldPos(). */
+typedef struct PslLastPoint {
+    float x, y, z;
+    int32_t state;
+} PslLastPoint;
+/* A local map point: mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance (the 0.8f / 1.2f factors of
+ * GetMin/MaxDistanceInvariance are applied inside). */
+typedef struct PslMapPointGeom {
+    float x, y, z, nx, ny, nz, min_dist, max_dist;
+} PslMapPointGeom;
+
+/* == ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) src/ORBmatcher.cc:1338-1390 up to the window search, for
+ *    npairs pairs: pair p's last frame is slot last_slot0 + p of `last` (mvKeysUn, mvDepth, descriptors: pslfe_frame_set_rgbd /
+ *    _set_from_orb_rgbd), its poses d_Tlw[p] (LastFrame.mTcw) and d_Tcw[p] (CurrentFrame.mTcw).  twc, tlc, bForward / bBackward
+ *    against mb = bf/fx and bMono = mono; every existing, non-outlier point is projected (invzc = 1.0/z in double, rounded to
+ *    float) and a row u, v, radius = th*mvScaleFactors[octave], ur = u - mbf*invzc, the level band of the three
+ *    GetFeaturesInArea calls (:1385-1390), angle = mvKeysUn[i].angle, blocks = Observations()>0 is emitted when u, v lie in
+ *    [min_x, max_x] x [min_y, max_y].  d_points: [npairs][last->cap] or NULL (no map points); d_mpdesc: [npairs][cap][32] the map
+ *    points' descriptors or NULL (= the slot's keypoint descriptors).  Outputs at p*qstride: d_queries, d_qdesc (32 B per row),
+ *    d_owner (may be NULL) = last-frame keypoint of the row; d_nq[p] = the row count.  qstride <= last->cap (PSLFE_E_CAPACITY).
+ *    vo != 0: first the "visual odometry" points of Tracking::UpdateLastFrame src/Tracking.cc:1052-1104 (localisation mode): of
+ *    the keypoints with mvDepth > 0 sorted by (z, i), the first min(n_valid, max(n_close + 1, 101)) are visited
+ *    (n_close = #{0 < z <= th_depth}); those with state 0 or 1 get a new point Frame::UnprojectStereo src/Frame.cc:1365-1379
+ *    (invfx = 1.0f/fx) whose descriptor is the keypoint's and which has no observations; state-2 points are kept.  VO on a slot
+ *    without depth is PSLFE_E_STATE.  scale_factors: host array of nlevels (<= PSLFE_MAX_LEVELS) floats; cam: host.
+ *    Asynchronous on the context's stream. */
+int pslfe_orb_project_last_device(pslfe_frame* last, int last_slot0, int npairs, const PslPose* d_Tlw, const PslPose* d_Tcw,
+                                  const PslLastPoint* d_points, const uint8_t* d_mpdesc, const PslCamera* cam,
+                                  const float* scale_factors, int nlevels, float th, float th_depth, int mono, int vo, float min_x,
+                                  float min_y, float max_x, float max_y, PslProjQuery* d_queries, uint8_t* d_qdesc,
+                                  int32_t* d_owner, int32_t* d_nq, int qstride);
+/* Same for one slot, host arrays: points / mpdesc hold the slot's N entries (or NULL); queries / qdesc / owner (may be NULL)
+ * have room for qcap rows; *nq = row count. */
+int pslfe_orb_project_last(pslfe_frame* last, int slot, const PslPose* Tlw, const PslPose* Tcw, const PslLastPoint* points,
+                           const uint8_t* mpdesc, const PslCamera* cam, const float* scale_factors, int nlevels, float th,
+                           float th_depth, int mono, int vo, float min_x, float min_y, float max_x, float max_y,
+                           PslProjQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap);
+
+/* == Frame::isInFrustum(pMP, view_cos_limit) src/Frame.cc:927-983 + PredictScale src/MapPoint.cc:402-416 for every local map
+ *    point, and the query rows of ORBmatcher::SearchByProjection(F, vpMapPoints, th) src/ORBmatcher.cc:45-70 for those in view:
+ *    gates z, image bounds (invz = 1.0f/z), 0.8f*min_dist <= |P - Ow| <= 1.2f*max_dist, viewCos >= view_cos_limit; radius
+ *    = RadiusByViewingCos (2.5 if (double)viewCos > 0.998 else 4.0, :131-137) * th when th != 1, * mvScaleFactors[level];
+ *    levels level-1 .. level; ur = mTrackProjXR = u - mbf*invz; angle 0; blocks 1.  Frame f: d_nmp[f] map points at
+ *    d_mp + f*mpstride (descriptors d_mpdesc + f*mpstride*32), pose d_Tcw[f]; rows at f*qstride, d_nq[f] = number of map points
+ *    in view (nToMatch of Tracking::SearchLocalPoints src/Tracking.cc:1725-1741; rows beyond qstride are not written).
+ *    Per map point (each may be NULL): d_inview (mbTrackInView), d_level (mnTrackScaleLevel, -1 when not in view), d_viewcos
+ *    (mTrackViewCos, 0 when not in view).  Asynchronous on the context's stream. */
+int pslfe_orb_project_frustum_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw, const PslMapPointGeom* d_mp,
+                                     const uint8_t* d_mpdesc, const int32_t* d_nmp, int mpstride, const PslCamera* cam,
+                                     const float* scale_factors, int nlevels, float log_scale_factor, float view_cos_limit,
+                                     float th, float min_x, float min_y, float max_x, float max_y, PslProjQuery* d_queries,
+                                     uint8_t* d_qdesc, int32_t* d_owner, int32_t* d_nq, int qstride, uint8_t* d_inview,
+                                     int32_t* d_level, float* d_viewcos);
+/* Same for one frame, host arrays: mp / mpdesc / inview / level / viewcos have nmp entries (the last three may be NULL). */
+int pslfe_orb_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapPointGeom* mp, const uint8_t* mpdesc, int nmp,
+                              const PslCamera* cam, const float* scale_factors, int nlevels, float log_scale_factor,
+                              float view_cos_limit, float th, float min_x, float min_y, float max_x, float max_y,
+                              PslProjQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap, uint8_t* inview,
+                              int32_t* level, float* viewcos);
+/* Batched, HBM-resident form of pslfe_orb_search_by_projection_map, laid out as pslfe_orb_search_by_projection_last_device;
+ * d_taken: [npairs][cur->cap] or NULL. */
+int pslfe_orb_search_by_projection_map_device(pslfe_frame* cur, int slot0, int npairs, const PslProjQuery* d_queries,
+                                              const uint8_t* d_qdesc, const int32_t* d_nq, int qstride, const uint8_t* d_taken,
+                                              float nnratio, int32_t* d_match, int32_t* d_nmatches);
+
 /* == LSDmatcher::matchNNR add_src/LSDmatcher.cpp:354-376 (and LSDmatcher::match :378-413, whose
  *    live branch is matchNNR): matches12[i] = best train row if d0 < d1 * nnr (float compare on
  *    DMatch.distance) else -1; *nmatches = return value.  n2 < 2 is UB in the reference

@@ -29,6 +29,20 @@ PROJQUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("ur"
 BOWQUERY_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("angle", "<f4")])
 CAMERA_DTYPE = np.dtype([(k, "<f4") for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf")])
 assert KEYPOINT_DTYPE.itemsize == 28 and KEYLINE_DTYPE.itemsize == 68 and PROJQUERY_DTYPE.itemsize == 32
+# projection of 3-D points (include/pslfe.h: PslPose, PslLastPoint, PslMapPointGeom)
+POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,))])
+LASTPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("state", "<i4")])
+MAPPOINT_DTYPE = np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz", "min_dist", "max_dist")])
+assert POSE_DTYPE.itemsize == 48 and LASTPOINT_DTYPE.itemsize == 16 and MAPPOINT_DTYPE.itemsize == 32
+LASTPOINT_NONE, LASTPOINT_NO_OBS, LASTPOINT_OBS, LASTPOINT_OUTLIER = 0, 1, 2, 8
+
+
+def pose(Tcw):
+    """A 4x4 (or 3x4) Frame::mTcw -> one POSE_DTYPE record."""
+    T = np.asarray(Tcw, np.float32)
+    p = np.zeros((), POSE_DTYPE)
+    p["R"], p["t"] = T[:3, :3].reshape(9), T[:3, 3]
+    return p
 
 
 class PslfeError(RuntimeError):
@@ -343,6 +357,36 @@ class FrameGrid:
         self.n[slot] = n.value
         return kps[:n.value], dep[:n.value], ur[:n.value]
 
+    def project_last(self, slot, Tlw, Tcw, points, mpdesc, cam, scale_factors, th, th_depth, mono, vo, bounds):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) src/ORBmatcher.cc:1338-1390 up to the window search, slot `slot` as
+        the last frame (vo: with UpdateLastFrame's visual-odometry points).  points: LASTPOINT_DTYPE[N] or None, mpdesc: [N, 32]
+        or None.  -> (queries PROJQUERY_DTYPE, qdesc [nq, 32], owner [nq])."""
+        Tl, Tc = np.ascontiguousarray(Tlw, POSE_DTYPE).reshape(1), np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
+        pts = None if points is None else np.ascontiguousarray(points, LASTPOINT_DTYPE)
+        md = None if mpdesc is None else np.ascontiguousarray(mpdesc, np.uint8)
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        sc = np.ascontiguousarray(scale_factors, np.float32)
+        q = np.zeros(self.cap, PROJQUERY_DTYPE)
+        qd = np.zeros((self.cap, 32), np.uint8)
+        ow = np.zeros(self.cap, np.int32)
+        nq = C.c_int()
+        _check(lib().pslfe_orb_project_last(self._h, C.c_int(slot), _ptr(Tl), _ptr(Tc), _ptr(pts), _ptr(md), _ptr(cam), _ptr(sc),
+                                            C.c_int(len(sc)), C.c_float(th), C.c_float(th_depth), C.c_int(1 if mono else 0),
+                                            C.c_int(1 if vo else 0), *[C.c_float(b) for b in bounds], _ptr(q), _ptr(qd), _ptr(ow),
+                                            C.byref(nq), C.c_int(self.cap)), "pslfe_orb_project_last")
+        return q[:nq.value], qd[:nq.value], ow[:nq.value]
+
+    def project_last_device(self, slot0, npairs, d_Tlw, d_Tcw, d_points, d_mpdesc, cam, scale_factors, th, th_depth, mono, vo, bounds,
+                            d_queries, d_qdesc, d_owner, d_nq, qstride):
+        """Batched, HBM-resident project_last: all d_* are device addresses (ints; d_points / d_mpdesc / d_owner may be 0)."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        sc = np.ascontiguousarray(scale_factors, np.float32)
+        _check(lib().pslfe_orb_project_last_device(
+            self._h, C.c_int(slot0), C.c_int(npairs), C.c_void_p(d_Tlw), C.c_void_p(d_Tcw), C.c_void_p(d_points or None),
+            C.c_void_p(d_mpdesc or None), _ptr(cam), _ptr(sc), C.c_int(len(sc)), C.c_float(th), C.c_float(th_depth),
+            C.c_int(1 if mono else 0), C.c_int(1 if vo else 0), *[C.c_float(b) for b in bounds], C.c_void_p(d_queries),
+            C.c_void_p(d_qdesc), C.c_void_p(d_owner or None), C.c_void_p(d_nq), C.c_int(qstride)), "pslfe_orb_project_last_device")
+
     def debug_grid(self, slot):
         start = np.zeros(64 * 48 + 1, np.int32)
         idx = np.zeros(self.cap, np.int32)
@@ -483,6 +527,53 @@ def search_by_projection_last_device(frame, slot0, npairs, d_queries, d_qdesc, d
         frame._h, C.c_int(slot0), C.c_int(npairs), C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_nq),
         C.c_int(qstride), C.c_int(1 if check_orientation else 0), C.c_void_p(d_match), C.c_void_p(d_nmatches)),
         "pslfe_orb_search_by_projection_last_device")
+
+
+def project_frustum(Tcw, mp, mpdesc, cam, scale_factors, log_scale_factor, view_cos_limit, th, bounds, ctx=None):
+    """Frame::isInFrustum src/Frame.cc:927-983 for every map point (MAPPOINT_DTYPE[M], descriptors [M, 32]) and the query rows of
+    SearchByProjection(F, vpMapPoints, th) src/ORBmatcher.cc:45-70 for those in view.
+    -> (queries, qdesc, owner, inview [M] u8, level [M] i32, viewcos [M] f32)."""
+    ctx = ctx or default_context()
+    T = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
+    mp = np.ascontiguousarray(mp, MAPPOINT_DTYPE)
+    md = np.ascontiguousarray(mpdesc, np.uint8).reshape(-1, 32)
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    sc = np.ascontiguousarray(scale_factors, np.float32)
+    M = len(mp)
+    q = np.zeros(max(M, 1), PROJQUERY_DTYPE)
+    qd = np.zeros((max(M, 1), 32), np.uint8)
+    ow = np.zeros(max(M, 1), np.int32)
+    inview, level, vc = np.zeros(max(M, 1), np.uint8), np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.float32)
+    nq = C.c_int()
+    _check(lib().pslfe_orb_project_frustum(ctx._h, _ptr(T), _ptr(mp), _ptr(md), C.c_int(M), _ptr(cam), _ptr(sc), C.c_int(len(sc)),
+                                           C.c_float(log_scale_factor), C.c_float(view_cos_limit), C.c_float(th),
+                                           *[C.c_float(b) for b in bounds], _ptr(q), _ptr(qd), _ptr(ow), C.byref(nq), C.c_int(M),
+                                           _ptr(inview), _ptr(level), _ptr(vc)), "pslfe_orb_project_frustum")
+    n = nq.value
+    return q[:n], qd[:n], ow[:n], inview[:M], level[:M], vc[:M]
+
+
+def project_frustum_device(nframes, d_Tcw, d_mp, d_mpdesc, d_nmp, mpstride, cam, scale_factors, log_scale_factor, view_cos_limit, th,
+                           bounds, d_queries, d_qdesc, d_owner, d_nq, qstride, d_inview=0, d_level=0, d_viewcos=0, ctx=None):
+    """Batched, HBM-resident project_frustum; all d_* are device addresses (ints; d_owner / d_inview / d_level / d_viewcos may be 0).
+    d_nq[f] > qstride: more map points in view than rows (the first qstride are written)."""
+    ctx = ctx or default_context()
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    sc = np.ascontiguousarray(scale_factors, np.float32)
+    _check(lib().pslfe_orb_project_frustum_device(
+        ctx._h, C.c_int(nframes), C.c_void_p(d_Tcw), C.c_void_p(d_mp), C.c_void_p(d_mpdesc), C.c_void_p(d_nmp), C.c_int(mpstride),
+        _ptr(cam), _ptr(sc), C.c_int(len(sc)), C.c_float(log_scale_factor), C.c_float(view_cos_limit), C.c_float(th),
+        *[C.c_float(b) for b in bounds], C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_owner or None), C.c_void_p(d_nq),
+        C.c_int(qstride), C.c_void_p(d_inview or None), C.c_void_p(d_level or None), C.c_void_p(d_viewcos or None)),
+        "pslfe_orb_project_frustum_device")
+
+
+def search_by_projection_map_device(frame, slot0, npairs, d_queries, d_qdesc, d_nq, qstride, d_taken, nnratio, d_match, d_nmatches):
+    """Batched HBM-resident SearchByProjection(F, vpMapPoints); all d_* are device addresses (ints; d_taken may be 0)."""
+    _check(lib().pslfe_orb_search_by_projection_map_device(
+        frame._h, C.c_int(slot0), C.c_int(npairs), C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_nq), C.c_int(qstride),
+        C.c_void_p(d_taken or None), C.c_float(nnratio), C.c_void_p(d_match), C.c_void_p(d_nmatches)),
+        "pslfe_orb_search_by_projection_map_device")
 
 
 class LINEextractor:

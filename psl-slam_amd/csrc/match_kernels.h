@@ -224,6 +224,7 @@ struct pslfe_frame {
     float* d_depth = nullptr;    // [max_frames][cap] mvDepth (RGB-D post-processing)
     float* d_bounds = nullptr;   // [4] scratch for k_image_bounds
     std::vector<char> slot_set;
+    std::vector<char> slot_depth;  // the slot's mvDepth was set (pslfe_frame_set_rgbd / _set_from_orb_rgbd)
 };
 
 #endif

@@ -610,6 +610,37 @@ int host_search(pslfe_frame* f, int slot, const PslProjQuery* queries, const uin
     PSL_HIP(hipStreamSynchronize(st));
     return PSLFE_OK;
 }
+
+// Batched, HBM-resident window search: mode 0 = SearchByProjection(cur,last), mode 1 = SearchByProjection(F,MPs).
+int device_search(pslfe_frame* cur, int slot0, int npairs, const PslProjQuery* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq,
+                  int qstride, const uint8_t* d_taken, int mode, int check_orientation, float nnratio, int32_t* d_match,
+                  int32_t* d_nmatches, const char* what) {
+    PSL_REQUIRE(cur && d_queries && d_qdesc && d_nq && d_match && d_nmatches, PSLFE_E_INVALID, "%s: NULL argument", what);
+    PSL_REQUIRE(npairs >= 1 && slot0 >= 0 && slot0 + npairs <= cur->max_frames && qstride >= 1, PSLFE_E_INVALID,
+                "%s: slots %d..%d of %d", what, slot0, slot0 + npairs - 1, cur->max_frames);
+    for (int s = slot0; s < slot0 + npairs; ++s)
+        PSL_REQUIRE(cur->slot_set[s], PSLFE_E_STATE, "%s: slot %d not set", what, s);
+    PSL_HIP(hipSetDevice(cur->ctx->device));
+    MatchArgs A;
+    A.S = cur->S; A.slot0 = slot0; A.q = d_queries; A.qdesc = d_qdesc; A.nq_arr = d_nq; A.nq_single = 0; A.qstride = qstride;
+    A.taken = d_taken; A.check_ori = check_orientation; A.nnratio = nnratio; A.match = d_match; A.assigned = nullptr; A.nmatches = d_nmatches;
+    A.th = PSL_TH_HIGH; A.no_stereo = 0; A.fidx = nullptr;
+    PSL_REQUIRE(qstride <= cur->cap && npairs <= cur->max_frames, PSLFE_E_CAPACITY, "%s: qstride %d > capacity %d", what, qstride, cur->cap);
+    A.topk = cur->d_topk; A.more = cur->d_more;
+    {
+        PSL_STAGE_BEGIN(cur->ctx, "match.window");
+        if (cur->cap <= PSL_WS_CAP && npairs >= 64)   // many frames of at most 1280 keypoints: the frame staged in LDS, one workgroup per frame
+            k_window_eval_staged<<<npairs, 1024, 0, cur->ctx->stream>>>(A);
+        else
+            k_window_eval<<<dim3((std::min(qstride, PSL_QMAX) + 3) / 4, npairs), 256, 0, cur->ctx->stream>>>(A);
+        // one 1024-thread workgroup per frame: measured faster than 512-thread workgroups at 256 and at 4096 frames
+        if (mode == 0) k_window_resolve<0, PSL_QMAX, 1024><<<npairs, 1024, 0, cur->ctx->stream>>>(A);
+        else k_window_resolve<1, PSL_QMAX, 1024><<<npairs, 1024, 0, cur->ctx->stream>>>(A);
+        PSL_STAGE_END(cur->ctx, "match.window");
+    }
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -623,6 +654,7 @@ int pslfe_frame_create(pslfe_ctx* ctx, int max_keypoints, int max_frames, pslfe_
     pslfe_frame* f = new pslfe_frame();
     f->ctx = ctx; f->cap = max_keypoints; f->max_frames = max_frames;
     f->slot_set.assign(max_frames, 0);
+    f->slot_depth.assign(max_frames, 0);
     const size_t F = (size_t)max_frames, K = (size_t)max_keypoints;
     f->S.cap = max_keypoints;
     hipError_t e = hipSuccess;
@@ -697,6 +729,7 @@ int pslfe_frame_set(pslfe_frame* f, int slot, const PslKeyPoint* kps, const uint
     }
     PSL_HIP(hipGetLastError());
     f->slot_set[slot] = 1;
+    f->slot_depth[slot] = 0;
     return PSLFE_OK;
 }
 
@@ -719,7 +752,7 @@ int pslfe_frame_set_from_orb(pslfe_frame* f, pslfe_orb* orb, float min_x, float 
         PSL_STAGE_END(f->ctx, "match.grid");
     }
     PSL_HIP(hipGetLastError());
-    for (int s = 0; s < nframes; ++s) f->slot_set[s] = 1;
+    for (int s = 0; s < nframes; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 0;
     return PSLFE_OK;
 }
 
@@ -748,7 +781,7 @@ static int frame_post_rgbd(pslfe_frame* f, int slot0, int nslots, const float* d
         PSL_STAGE_END(f->ctx, "match.grid");
     }
     PSL_HIP(hipGetLastError());
-    for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1;
+    for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1;
     return PSLFE_OK;
 }
 
@@ -881,30 +914,15 @@ int pslfe_orb_search_by_bow(pslfe_frame* f, int slot, const int32_t* fidx, int n
 int pslfe_orb_search_by_projection_last_device(pslfe_frame* cur, int slot0, int npairs, const PslProjQuery* d_queries,
                                                const uint8_t* d_qdesc, const int32_t* d_nq, int qstride, int check_orientation,
                                                int32_t* d_match, int32_t* d_nmatches) {
-    PSL_REQUIRE(cur && d_queries && d_qdesc && d_nq && d_match && d_nmatches, PSLFE_E_INVALID, "search_by_projection_last_device: NULL argument");
-    PSL_REQUIRE(npairs >= 1 && slot0 >= 0 && slot0 + npairs <= cur->max_frames && qstride >= 1, PSLFE_E_INVALID,
-                "search_by_projection_last_device: slots %d..%d of %d", slot0, slot0 + npairs - 1, cur->max_frames);
-    for (int s = slot0; s < slot0 + npairs; ++s)
-        PSL_REQUIRE(cur->slot_set[s], PSLFE_E_STATE, "search_by_projection_last_device: slot %d not set", s);
-    PSL_HIP(hipSetDevice(cur->ctx->device));
-    MatchArgs A;
-    A.S = cur->S; A.slot0 = slot0; A.q = d_queries; A.qdesc = d_qdesc; A.nq_arr = d_nq; A.nq_single = 0; A.qstride = qstride;
-    A.taken = nullptr; A.check_ori = check_orientation; A.nnratio = 0.f; A.match = d_match; A.assigned = nullptr; A.nmatches = d_nmatches;
-    A.th = PSL_TH_HIGH; A.no_stereo = 0; A.fidx = nullptr;
-    PSL_REQUIRE(qstride <= cur->cap && npairs <= cur->max_frames, PSLFE_E_CAPACITY, "search_by_projection_last_device: qstride %d > capacity %d", qstride, cur->cap);
-    A.topk = cur->d_topk; A.more = cur->d_more;
-    {
-        PSL_STAGE_BEGIN(cur->ctx, "match.window");
-        if (cur->cap <= PSL_WS_CAP && npairs >= 64)   // many frames of at most 1280 keypoints: the frame staged in LDS, one workgroup per frame
-            k_window_eval_staged<<<npairs, 1024, 0, cur->ctx->stream>>>(A);
-        else
-            k_window_eval<<<dim3((std::min(qstride, PSL_QMAX) + 3) / 4, npairs), 256, 0, cur->ctx->stream>>>(A);
-        // one 1024-thread workgroup per frame: measured faster than 512-thread workgroups at 256 and at 4096 frames
-        k_window_resolve<0, PSL_QMAX, 1024><<<npairs, 1024, 0, cur->ctx->stream>>>(A);
-        PSL_STAGE_END(cur->ctx, "match.window");
-    }
-    PSL_HIP(hipGetLastError());
-    return PSLFE_OK;
+    return device_search(cur, slot0, npairs, d_queries, d_qdesc, d_nq, qstride, nullptr, 0, check_orientation, 0.f, d_match, d_nmatches,
+                         "search_by_projection_last_device");
+}
+
+int pslfe_orb_search_by_projection_map_device(pslfe_frame* cur, int slot0, int npairs, const PslProjQuery* d_queries,
+                                              const uint8_t* d_qdesc, const int32_t* d_nq, int qstride, const uint8_t* d_taken,
+                                              float nnratio, int32_t* d_match, int32_t* d_nmatches) {
+    return device_search(cur, slot0, npairs, d_queries, d_qdesc, d_nq, qstride, d_taken, 1, 0, nnratio, d_match, d_nmatches,
+                         "search_by_projection_map_device");
 }
 
 int pslfe_hamming_knn2_device(pslfe_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int32_t* d_idx, int32_t* d_dist) {

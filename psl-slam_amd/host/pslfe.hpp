@@ -120,6 +120,22 @@ public:
     void imageBounds(const PslCamera& cam, int cols, int rows, float bounds[4]) {
         check(pslfe_image_bounds(h_, &cam, cols, rows, bounds), "pslfe_image_bounds");
     }
+    // SearchByProjection(CurrentFrame, LastFrame, th, bMono), src/ORBmatcher.cc:1338-1390, up to the window search: slot `slot` is
+    // the last frame; points / mpdesc: LastFrame.mvpMapPoints as PslLastPoint[N] / [N][32] (either may be NULL); vo: first the
+    // visual-odometry points of Tracking::UpdateLastFrame (src/Tracking.cc:1052-1104).  Fills the queries SearchByProjection takes;
+    // owner[q] = last-frame keypoint of query q.
+    void ProjectLast(int slot, const PslPose& Tlw, const PslPose& Tcw, const PslLastPoint* points, const uint8_t* mpdesc, const PslCamera& cam,
+                     const std::vector<float>& scaleFactors, float th, float thDepth, bool bMono, bool vo, float mnMinX, float mnMinY,
+                     float mnMaxX, float mnMaxY, int capacity, std::vector<PslProjQuery>& queries, std::vector<uint8_t>& qdesc,
+                     std::vector<int32_t>& owner) {
+        queries.resize(capacity); qdesc.resize((size_t)capacity * 32); owner.resize(capacity);
+        int n = 0;
+        check(pslfe_orb_project_last(h_, slot, &Tlw, &Tcw, points, mpdesc, &cam, scaleFactors.data(), (int)scaleFactors.size(), th, thDepth,
+                                     bMono ? 1 : 0, vo ? 1 : 0, mnMinX, mnMinY, mnMaxX, mnMaxY, queries.data(), qdesc.data(), owner.data(),
+                                     &n, capacity),
+              "pslfe_orb_project_last");
+        queries.resize(n); qdesc.resize((size_t)n * 32); owner.resize(n);
+    }
     pslfe_frame* get() const { return h_; }
 private:
     pslfe_frame* h_ = nullptr;
@@ -172,6 +188,31 @@ public:
                                       mfNNratio, mbCheckOrientation ? 1 : 0, match.data(), assigned ? assigned->data() : nullptr, &nm),
               "pslfe_orb_search_by_bow");
         return nm;
+    }
+    // Frame::isInFrustum(pMP, viewCosLimit) (src/Frame.cc:927-983) for every local map point, and the queries of
+    // SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:45-70) for those in view, in map-point order; inView / level /
+    // viewCos per map point (mbTrackInView, mnTrackScaleLevel, mTrackViewCos).  Returns nToMatch.
+    static int ProjectFrustum(Context& ctx, const PslPose& Tcw, const std::vector<PslMapPointGeom>& mps, const std::vector<uint8_t>& mpdesc,
+                              const PslCamera& cam, const std::vector<float>& scaleFactors, float mfLogScaleFactor, float viewCosLimit, float th,
+                              float mnMinX, float mnMinY, float mnMaxX, float mnMaxY, std::vector<PslProjQuery>& queries,
+                              std::vector<uint8_t>& qdesc, std::vector<int32_t>& owner, std::vector<uint8_t>& inView,
+                              std::vector<int32_t>& level, std::vector<float>& viewCos) {
+        const size_t M = mps.size();
+        queries.resize(M); qdesc.resize(M * 32); owner.resize(M); inView.resize(M); level.resize(M); viewCos.resize(M);
+        int n = 0;
+        check(pslfe_orb_project_frustum(ctx.get(), &Tcw, mps.data(), mpdesc.data(), (int)M, &cam, scaleFactors.data(), (int)scaleFactors.size(),
+                                        mfLogScaleFactor, viewCosLimit, th, mnMinX, mnMinY, mnMaxX, mnMaxY, queries.data(), qdesc.data(),
+                                        owner.data(), &n, (int)M, inView.data(), level.data(), viewCos.data()),
+              "pslfe_orb_project_frustum");
+        queries.resize(n); qdesc.resize((size_t)n * 32); owner.resize(n);
+        return n;
+    }
+    // Batched, HBM-resident SearchByProjection(F, vpMapPoints, th) over slots slot0.. of `cur` (pointers are device memory).
+    void SearchByProjectionMapDevice(FrameGrid& cur, int slot0, int npairs, const PslProjQuery* d_queries, const uint8_t* d_qdesc,
+                                     const int32_t* d_nq, int qstride, const uint8_t* d_taken, int32_t* d_match, int32_t* d_nmatches) {
+        check(pslfe_orb_search_by_projection_map_device(cur.get(), slot0, npairs, d_queries, d_qdesc, d_nq, qstride, d_taken, mfNNratio,
+                                                        d_match, d_nmatches),
+              "pslfe_orb_search_by_projection_map_device");
     }
     // DescriptorDistance, src/ORBmatcher.cc:1647-1663 (host helper, same SWAR popcount)
     static int DescriptorDistance(const uint8_t* a, const uint8_t* b) {
