@@ -494,6 +494,87 @@ int pslfe_line_search_by_projection(pslfe_ctx* ctx, const PslKeyLine* kls, const
                                     const PslLineQuery* queries, const uint8_t* qdesc, int nq, const uint8_t* taken, int mode,
                                     float nnratio, int32_t* match, int32_t* assigned, int* nmatches, int32_t* grid_start,
                                     int32_t* grid_idx, int grid_cap, int* grid_n);
+/* Batched, HBM-resident form of pslfe_line_search_by_projection (modes 0 and 1) for npairs pairs; every pair's results equal the
+ *    one-frame entry point's on the same inputs.  Pair p: the current frame's keylines / LBD rows (32 B) / line equations at
+ *    p*kl_stride (the views of pslfe_line_results_device, offset by a frame to pick "current = f+1"), d_nkl[p] lines;
+ *    mode 1: d_lines3d [npairs][lines3d_stride][6] f64 = mvLines3D as pslfe_glue_lines3d_device holds it (lines3d_stride must equal
+ *    kl_stride; the kernel forms first - second itself); queries / descriptors at p*qstride, min(d_nq[p], qstride) of them read;
+ *    d_taken [npairs][kl_stride] or NULL.  Outputs: d_match at p*qstride, d_assigned [npairs][kl_stride] (may be NULL),
+ *    d_nmatches[p].  kl_stride <= 1024.  The 64x48 grid of a pair is built in LDS with 16-bit entries; a pair with more than
+ *    8192 (line, cell) entries runs in a second launch whose grid holds every entry of 1024 lines; d_nfallback (may be NULL) = the
+ *    number of such pairs.  Asynchronous on the context's stream. */
+int pslfe_line_search_by_projection_device(pslfe_ctx* ctx, int npairs, const PslKeyLine* d_kls, const uint8_t* d_desc,
+                                           const double* d_lineEq, const int32_t* d_nkl, int kl_stride, const double* d_lines3d,
+                                           int lines3d_stride, float min_x, float min_y, float max_x, float max_y,
+                                           const PslLineQuery* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq, int qstride,
+                                           const uint8_t* d_taken, int mode, float nnratio, int32_t* d_match, int32_t* d_assigned,
+                                           int32_t* d_nmatches, int32_t* d_nfallback);
+
+/* ---- Projection of map lines into a frame: the part of both LSDmatcher::SearchByProjection variants before the window search.
+ *
+ * Conventions: those of the point projections above, and
+ *   - SP / EP = MapLine::GetWorldPos() rounded to float; OM = 0.5*(SP+EP) - mOw is, per component, the float sum of the exact
+ *     halves 0.5f*SP + 0.5f*EP (one rounding: cv::addWeighted with weights 0.5, whether it sums in float or in double), then the
+ *     float difference with mOw.  OpenCV is not in the reference tree, so this is pinned against the in-repo restatement only;
+ *   - an endpoint with camera depth z == 0 or NaN, a NaN pixel coordinate, dist or viewCos: the line is not in view (the reference
+ *     tests z < 0 only and goes on dividing by zero; dist == 0 gives viewCos = 0/0 and is therefore not in view either);
+ *   - MapLine::PredictScale (add_src/MapLine.cpp:381-390) is unclamped float arithmetic: ceil(logf(ratio) / logScaleFactor)
+ *     (`using namespace std` makes log(float) std::log(float)).  logf here is the correctly rounded float log, (float)psl_log of the
+ *     ratio; the quotient and ceil are the reference's float operations.  A ratio of +inf gives INT32_MAX, 0 gives INT32_MIN, NaN 0;
+ *     a finite level is outside [0, nlevels) whenever the ratio is (no clamp, as in the reference).
+ *   - RadiusByViewingCos (add_src/LSDmatcher.cpp:986-992): 5.0 if (double)viewCos > 0.998 else 8.0, times th when th != 1. */
+typedef struct PslMapLineGeom {
+    double sp[3], ep[3];      /* MapLine::GetWorldPos() (Vector6d)                                              */
+    double normal[3];         /* GetNormal(): float in isInFrustum, double in the mode-1 gate (LSDmatcher.cpp:293) */
+    float min_dist, max_dist; /* mfMinDistance, mfMaxDistance (the 0.8f / 1.2f factors are applied inside)      */
+} PslMapLineGeom;
+/* LastFrame.mvpMapLines[i]: state 0 = none, 1 = a map line with Observations()==0, 2 = with Observations()>0; | 8 = mvbLineOutlier[i]. */
+typedef struct PslLastLine {
+    double sp[3], ep[3], normal[3];
+    float min_dist, max_dist;
+    int32_t state;
+    int32_t reserved;
+} PslLastLine;
+#ifdef __cplusplus
+static_assert(sizeof(PslMapLineGeom) == 80 && sizeof(PslLastLine) == 88 && sizeof(PslLineQuery) == 64, "line projection PODs");
+#endif
+
+/* == Frame::isInFrustum(pML, view_cos_limit) src/Frame.cc:828-904 + MapLine::PredictScale for every map line of a frame, and the
+ *    query rows of LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) add_src/LSDmatcher.cpp:260-289 for those in view.
+ *    The caller passes the lines SearchLocalLines would test (src/Tracking.cc:1792-1808: not bad, mnLastFrameSeen != mnId).
+ *    Gates in the reference's order: both camera z >= 0, endpoint 1 in [min_x, max_x] x [min_y, max_y], then endpoint 2,
+ *    0.8f*min_dist <= |OM| <= 1.2f*max_dist, viewCos >= view_cos_limit.  Row: x1..y2 = mTrackProj{X,Y}{1,2}, radius =
+ *    RadiusByViewingCos(viewCos) (* th when th != 1), th_cos = 0.998f (GetFeaturesInAreaForLine's default TH), wdir = normal,
+ *    blocks = 1, vx = vy = length = 0.  Frame f: d_nml[f] map lines at d_ml + f*mlstride (descriptors d_mldesc + f*mlstride*32),
+ *    pose d_Tcw[f]; rows at f*qstride compacted in map-line order, d_owner (may be NULL) = map line of the row, d_nq[f] = lines in
+ *    view (nToMatch; rows beyond qstride are not written).  Per map line (each may be NULL): d_inview, d_level
+ *    (mnTrackScaleLevel, -1 when not in view), d_viewcos (mTrackViewCos, 0 when not in view).  Asynchronous. */
+int pslfe_line_project_frustum_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw, const PslMapLineGeom* d_ml,
+                                      const uint8_t* d_mldesc, const int32_t* d_nml, int mlstride, const PslCamera* cam,
+                                      float log_scale_factor, float view_cos_limit, float th, float min_x, float min_y, float max_x,
+                                      float max_y, PslLineQuery* d_queries, uint8_t* d_qdesc, int32_t* d_owner, int32_t* d_nq,
+                                      int qstride, uint8_t* d_inview, int32_t* d_level, float* d_viewcos);
+/* Same for one frame, host arrays: ml / mldesc / inview / level / viewcos have nml entries (the last three may be NULL); rows for
+ * qcap; more lines in view than qcap is PSLFE_E_CAPACITY with *nq set. */
+int pslfe_line_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapLineGeom* ml, const uint8_t* mldesc, int nml,
+                               const PslCamera* cam, float log_scale_factor, float view_cos_limit, float th, float min_x, float min_y,
+                               float max_x, float max_y, PslLineQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap,
+                               uint8_t* inview, int32_t* level, float* viewcos);
+/* == LSDmatcher::SearchByProjection(CurrentFrame, LastFrame, th) add_src/LSDmatcher.cpp:112-155 up to GetFeaturesInAreaForLine,
+ *    for npairs pairs.  Pair p: the last frame's keylines (mvKeylinesUn) and LBD rows at p*kl_stride, d_nkl_last[p] of them,
+ *    its PslLastLine rows d_lines + p*kl_stride, the current pose d_Tcw[p].  Every line with state & 3 != 0 and no outlier bit
+ *    that passes isInFrustum(pML, 0.5) against the current pose gives a row: x1..y2, radius = th, th_cos = 0.96f, vx, vy = the
+ *    last keyline's ePointInOctave - sPointInOctave, length = its lineLength, blocks = (state & 3) == 2, wdir = 0.  Query
+ *    descriptor: d_mldesc + (p*kl_stride + i)*32 (GetDescriptor()) or, when d_mldesc is NULL, the last frame's own LBD row.
+ *    Rows at p*qstride in line order, d_owner (may be NULL) = last-frame line, d_nq[p] = the row count.  Asynchronous. */
+int pslfe_line_project_last_device(pslfe_ctx* ctx, int npairs, const PslKeyLine* d_kls_last, const uint8_t* d_ldesc_last,
+                                   const int32_t* d_nkl_last, int kl_stride, const PslLastLine* d_lines, const uint8_t* d_mldesc,
+                                   const PslPose* d_Tcw, const PslCamera* cam, float th, float min_x, float min_y, float max_x,
+                                   float max_y, PslLineQuery* d_queries, uint8_t* d_qdesc, int32_t* d_owner, int32_t* d_nq, int qstride);
+/* Same for one pair, host arrays of n lines (mldesc may be NULL). */
+int pslfe_line_project_last(pslfe_ctx* ctx, const PslKeyLine* kls_last, const uint8_t* ldesc_last, int n, const PslLastLine* lines,
+                            const uint8_t* mldesc, const PslPose* Tcw, const PslCamera* cam, float th, float min_x, float min_y,
+                            float max_x, float max_y, PslLineQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap);
 
 /* ---- Frame::ComputeBoW ------------------------------------------------------------- */
 typedef struct pslfe_vocab pslfe_vocab;
@@ -652,6 +733,8 @@ typedef struct PslRecordSources {
 /* Packs the records of nframes frames into d_records ([nframes][layout.bytes]), asynchronously on the context's stream. */
 int pslfe_record_pack_device(pslfe_ctx* ctx, const PslRecordCaps* caps, const PslRecordSources* src, int nframes, void* d_records);
 /* mvPlanes / mvPlaneLineNo / their counts of the last pslfe_glue_run_batch_device, HBM resident ([nframes][plane_stride][..]). */
+/* Device view of the last batch's mvLines3D: [max_batch][stride][6] f64 (start, end), stride = max_lines. */
+int pslfe_glue_lines3d_device(pslfe_glue* g, const double** d_lines3d, int* stride);
 int pslfe_glue_planes_device(pslfe_glue* g, const float** d_planes, const int32_t** d_plane_lines, const int32_t** d_plane_counts,
                              int* plane_stride);
 

@@ -822,6 +822,96 @@ def _lsd_search_by_projection(self, kls, desc, lineEq, bounds, queries, qdesc, m
 
 LSDmatcher.SearchByProjection = _lsd_search_by_projection
 
+MAPLINE_DTYPE = np.dtype([("sp", "<f8", (3,)), ("ep", "<f8", (3,)), ("normal", "<f8", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4")])
+LASTLINE_DTYPE = np.dtype([("sp", "<f8", (3,)), ("ep", "<f8", (3,)), ("normal", "<f8", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"),
+                           ("state", "<i4"), ("reserved", "<i4")])
+assert MAPLINE_DTYPE.itemsize == 80 and LASTLINE_DTYPE.itemsize == 88
+
+
+def line_project_frustum(Tcw, ml, mldesc, cam, log_scale_factor, view_cos_limit, th, bounds, ctx=None):
+    """Frame::isInFrustum(MapLine*) src/Frame.cc:828-904 for every map line (MAPLINE_DTYPE[M], descriptors [M, 32]) and the query rows of
+    LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) add_src/LSDmatcher.cpp:260-289 for those in view.
+    bounds = (mnMinX, mnMinY, mnMaxX, mnMaxY) -> (queries LINEQUERY_DTYPE, qdesc, owner, inview [M] u8, level [M] i32, viewcos [M] f32)."""
+    ctx = ctx or default_context()
+    T = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
+    ml = np.ascontiguousarray(ml, MAPLINE_DTYPE)
+    md = np.ascontiguousarray(mldesc, np.uint8).reshape(-1, 32)
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    M = len(ml)
+    q = np.zeros(max(M, 1), LINEQUERY_DTYPE)
+    qd = np.zeros((max(M, 1), 32), np.uint8)
+    ow = np.zeros(max(M, 1), np.int32)
+    inview, level, vc = np.zeros(max(M, 1), np.uint8), np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.float32)
+    nq = C.c_int()
+    _check(lib().pslfe_line_project_frustum(ctx._h, _ptr(T), _ptr(ml), _ptr(md), C.c_int(M), _ptr(cam), C.c_float(log_scale_factor),
+                                            C.c_float(view_cos_limit), C.c_float(th), *[C.c_float(b) for b in bounds], _ptr(q), _ptr(qd),
+                                            _ptr(ow), C.byref(nq), C.c_int(M), _ptr(inview), _ptr(level), _ptr(vc)),
+           "pslfe_line_project_frustum")
+    n = nq.value
+    return q[:n], qd[:n], ow[:n], inview[:M], level[:M], vc[:M]
+
+
+def line_project_frustum_device(nframes, d_Tcw, d_ml, d_mldesc, d_nml, mlstride, cam, log_scale_factor, view_cos_limit, th, bounds,
+                                d_queries, d_qdesc, d_owner, d_nq, qstride, d_inview=0, d_level=0, d_viewcos=0, ctx=None):
+    """Batched, HBM-resident line_project_frustum; all d_* are device addresses (ints; d_owner / d_inview / d_level / d_viewcos may be
+    0).  d_nq[f] > qstride: more map lines in view than rows (the first qstride are written)."""
+    ctx = ctx or default_context()
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    _check(lib().pslfe_line_project_frustum_device(
+        ctx._h, C.c_int(nframes), C.c_void_p(d_Tcw), C.c_void_p(d_ml), C.c_void_p(d_mldesc), C.c_void_p(d_nml), C.c_int(mlstride),
+        _ptr(cam), C.c_float(log_scale_factor), C.c_float(view_cos_limit), C.c_float(th), *[C.c_float(b) for b in bounds],
+        C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_owner or None), C.c_void_p(d_nq), C.c_int(qstride),
+        C.c_void_p(d_inview or None), C.c_void_p(d_level or None), C.c_void_p(d_viewcos or None)), "pslfe_line_project_frustum_device")
+
+
+def line_project_last(kls_last, ldesc_last, lines, mldesc, Tcw, cam, th, bounds, ctx=None):
+    """LSDmatcher::SearchByProjection(CurrentFrame, LastFrame, th) add_src/LSDmatcher.cpp:112-155 up to the window search: the last
+    frame's keylines / LBD rows and LASTLINE_DTYPE[n] (mvpMapLines, outliers), mldesc [n, 32] or None.
+    -> (queries LINEQUERY_DTYPE, qdesc, owner)."""
+    ctx = ctx or default_context()
+    k = np.ascontiguousarray(kls_last, KEYLINE_DTYPE)
+    d = np.ascontiguousarray(ldesc_last, np.uint8).reshape(-1, 32)
+    L = np.ascontiguousarray(lines, LASTLINE_DTYPE)
+    md = None if mldesc is None else np.ascontiguousarray(mldesc, np.uint8).reshape(-1, 32)
+    T = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    n = len(k)
+    q = np.zeros(max(n, 1), LINEQUERY_DTYPE)
+    qd = np.zeros((max(n, 1), 32), np.uint8)
+    ow = np.zeros(max(n, 1), np.int32)
+    nq = C.c_int()
+    _check(lib().pslfe_line_project_last(ctx._h, _ptr(k), _ptr(d), C.c_int(n), _ptr(L), _ptr(md), _ptr(T), _ptr(cam), C.c_float(th),
+                                         *[C.c_float(b) for b in bounds], _ptr(q), _ptr(qd), _ptr(ow), C.byref(nq), C.c_int(n)),
+           "pslfe_line_project_last")
+    m = nq.value
+    return q[:m], qd[:m], ow[:m]
+
+
+def line_project_last_device(npairs, d_kls_last, d_ldesc_last, d_nkl_last, kl_stride, d_lines, d_mldesc, d_Tcw, cam, th, bounds,
+                             d_queries, d_qdesc, d_owner, d_nq, qstride, ctx=None):
+    """Batched, HBM-resident line_project_last; all d_* are device addresses (ints; d_mldesc / d_owner may be 0)."""
+    ctx = ctx or default_context()
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    _check(lib().pslfe_line_project_last_device(
+        ctx._h, C.c_int(npairs), C.c_void_p(d_kls_last), C.c_void_p(d_ldesc_last), C.c_void_p(d_nkl_last), C.c_int(kl_stride),
+        C.c_void_p(d_lines), C.c_void_p(d_mldesc or None), C.c_void_p(d_Tcw), _ptr(cam), C.c_float(th), *[C.c_float(b) for b in bounds],
+        C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_owner or None), C.c_void_p(d_nq), C.c_int(qstride)),
+        "pslfe_line_project_last_device")
+
+
+def line_search_by_projection_device(npairs, d_kls, d_desc, d_lineEq, d_nkl, kl_stride, d_lines3d, lines3d_stride, bounds, d_queries,
+                                     d_qdesc, d_nq, qstride, d_taken, mode, nnratio, d_match, d_assigned, d_nmatches, d_nfallback=0,
+                                     ctx=None):
+    """Batched, HBM-resident LSDmatcher::SearchByProjection (mode 0 / 1) on pairs of HBM-resident frames; all d_* are device addresses
+    (ints; d_lines3d in mode 0, d_taken, d_assigned and d_nfallback may be 0).  bounds = (mnMinX, mnMinY, mnMaxX, mnMaxY)."""
+    ctx = ctx or default_context()
+    _check(lib().pslfe_line_search_by_projection_device(
+        ctx._h, C.c_int(npairs), C.c_void_p(d_kls), C.c_void_p(d_desc), C.c_void_p(d_lineEq), C.c_void_p(d_nkl), C.c_int(kl_stride),
+        C.c_void_p(d_lines3d or None), C.c_int(lines3d_stride), *[C.c_float(b) for b in bounds], C.c_void_p(d_queries),
+        C.c_void_p(d_qdesc), C.c_void_p(d_nq), C.c_int(qstride), C.c_void_p(d_taken or None), C.c_int(mode), C.c_float(nnratio),
+        C.c_void_p(d_match), C.c_void_p(d_assigned or None), C.c_void_p(d_nmatches), C.c_void_p(d_nfallback or None)),
+        "pslfe_line_search_by_projection_device")
+
 
 class FrameGlue:
     """== the part of Frame::ExtractLSD after the extractor (src/Frame.cc:490-660): isLineGood (3-D RANSAC per keyline),
@@ -851,6 +941,12 @@ class FrameGlue:
                                                  C.c_void_p(int(d_nkl)), C.c_void_p(int(d_fans)), C.c_int(fan_stride),
                                                  C.c_void_p(int(d_nfans)), C.c_void_p(int(d_depth)), C.c_int(width), C.c_int(height),
                                                  _ptr(cam), C.c_uint32(seed0)), "pslfe_glue_run_batch_device")
+
+    def lines3d_device(self):
+        """(device address of mvLines3D [max_batch][stride][6] f64, stride = max_lines) of the last batch."""
+        d, st = C.c_void_p(), C.c_int()
+        _check(lib().pslfe_glue_lines3d_device(self._h, C.byref(d), C.byref(st)), "pslfe_glue_lines3d_device")
+        return d.value, st.value
 
     def fetch(self, frame, nlines):
         """dict with mvLines3D, mvLineEq, the crossings (pair, xy, cross, le_l) and the planes."""

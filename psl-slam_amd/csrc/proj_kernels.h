@@ -1,0 +1,52 @@
+// Shared by pslfe_project.hip and pslfe_project_line.hip: the cv::Mat pose algebra of the projection conventions (include/pslfe.h,
+// DESIGN.md §3) and the workgroup compaction that keeps emitted rows in input order.  Product code.
+#ifndef PSL_PROJ_KERNELS_H
+#define PSL_PROJ_KERNELS_H
+
+#include "pslfe_internal.h"
+#include "psl_device_math.h"
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PSL_DDIV(a, b) __ddiv_rn((a), (b))
+#define PSL_DSQRT(a) __dsqrt_rn(a)
+#else
+#define PSL_DDIV(a, b) ((a) / (b))
+#define PSL_DSQRT(a) __builtin_sqrt(a)
+#endif
+
+// row r of M * x + t: double products (exact for float operands), summed in index order, one rounding
+__device__ __forceinline__ float psl_affine_row(float m0, float m1, float m2, float x0, float x1, float x2, float t) {
+    double a = PSL_DMUL((double)m0, (double)x0);
+    a = PSL_DADD(a, PSL_DMUL((double)m1, (double)x1));
+    a = PSL_DADD(a, PSL_DMUL((double)m2, (double)x2));
+    a = PSL_DADD(a, (double)t);
+    return (float)a;
+}
+
+// -R^T * t (camera centre twc / mOw of Frame::UpdatePoseMatrices)
+__device__ __forceinline__ void psl_centre(const PslPose& T, float* c) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) c[r] = -psl_affine_row(T.R[r], T.R[3 + r], T.R[6 + r], T.t[0], T.t[1], T.t[2], 0.f);
+}
+
+// Exclusive position of this thread's flag among the workgroup's set flags, and the workgroup's count.  All BS threads call it;
+// s_wave holds BS / 64 ints of LDS.
+template <int BS>
+__device__ __forceinline__ int psl_wg_compact(bool flag, int* s_wave, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t b = __ballot(flag);
+    const uint64_t below = lane ? (b & (~0ull >> (64 - lane))) : 0ull;
+    if (lane == 0) s_wave[wave] = __popcll(b);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < BS / 64; ++w) {
+        const int c = s_wave[w];
+        off += w < wave ? c : 0;
+        tot += c;
+    }
+    __syncthreads();  // s_wave is reused by the next round
+    *total = tot;
+    return off + __popcll(below);
+}
+
+#endif

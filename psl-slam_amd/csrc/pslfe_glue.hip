@@ -853,6 +853,14 @@ int pslfe_glue_fetch(pslfe_glue* g, int frame, int nlines, double* lines3d, floa
     return PSLFE_OK;
 }
 
+int pslfe_glue_lines3d_device(pslfe_glue* g, const double** d_lines3d, int* stride) {
+    PSL_REQUIRE(g, PSLFE_E_INVALID, "pslfe_glue_lines3d_device: glue is NULL");
+    PSL_REQUIRE(g->last_nframes > 0, PSLFE_E_STATE, "pslfe_glue_lines3d_device: no batch processed yet");
+    if (d_lines3d) *d_lines3d = g->d_lines3d;
+    if (stride) *stride = g->max_lines;
+    return PSLFE_OK;
+}
+
 int pslfe_glue_planes_device(pslfe_glue* g, const float** d_planes, const int32_t** d_plane_lines, const int32_t** d_plane_counts, int* plane_stride) {
     PSL_REQUIRE(g, PSLFE_E_INVALID, "pslfe_glue_planes_device: glue is NULL");
     PSL_REQUIRE(g->last_nframes > 0, PSLFE_E_STATE, "pslfe_glue_planes_device: no batch processed yet");

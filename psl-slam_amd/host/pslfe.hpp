@@ -323,6 +323,50 @@ public:
               "pslfe_line_search_by_projection");
         return n;
     }
+    // Batched, HBM-resident SearchByProjection (mode 0 / 1) over npairs pairs of device-resident frames (pointers are device memory;
+    // layout in include/pslfe.h).  Asynchronous on the context's stream.
+    void SearchByProjectionDevice(int npairs, const PslKeyLine* d_kls, const uint8_t* d_ldesc, const double* d_lineEq, const int32_t* d_nkl,
+                                  int klStride, const double* d_lines3d, int lines3dStride, float mnMinX, float mnMinY, float mnMaxX,
+                                  float mnMaxY, const PslLineQuery* d_queries, const uint8_t* d_qdesc, const int32_t* d_nq, int qstride,
+                                  const uint8_t* d_taken, int mode, int32_t* d_match, int32_t* d_assigned, int32_t* d_nmatches,
+                                  int32_t* d_nfallback = nullptr) {
+        check(pslfe_line_search_by_projection_device(ctx_.get(), npairs, d_kls, d_ldesc, d_lineEq, d_nkl, klStride, d_lines3d, lines3dStride,
+                                                     mnMinX, mnMinY, mnMaxX, mnMaxY, d_queries, d_qdesc, d_nq, qstride, d_taken, mode,
+                                                     mfNNratio, d_match, d_assigned, d_nmatches, d_nfallback),
+              "pslfe_line_search_by_projection_device");
+    }
+    // Frame::isInFrustum(MapLine*, viewCosLimit) src/Frame.cc:828-904 for every map line and the query rows of
+    // SearchByProjection(F, vpMapLines, eval_orient, th) :260-289 for those in view, in map-line order; inView / level / viewCos per line.
+    void ProjectMapLines(const PslPose& Tcw, const std::vector<PslMapLineGeom>& mls, const std::vector<uint8_t>& mldesc, const PslCamera& cam,
+                         float logScaleFactor, float viewCosLimit, float th, float mnMinX, float mnMinY, float mnMaxX, float mnMaxY,
+                         std::vector<PslLineQuery>& queries, std::vector<uint8_t>& qdesc, std::vector<int32_t>& owner,
+                         std::vector<uint8_t>* inView = nullptr, std::vector<int32_t>* level = nullptr, std::vector<float>* viewCos = nullptr) {
+        const size_t M = mls.size();
+        queries.resize(M); qdesc.resize(M * 32); owner.resize(M);
+        if (inView) inView->resize(M);
+        if (level) level->resize(M);
+        if (viewCos) viewCos->resize(M);
+        int nq = 0;
+        check(pslfe_line_project_frustum(ctx_.get(), &Tcw, mls.data(), mldesc.data(), (int)M, &cam, logScaleFactor, viewCosLimit, th, mnMinX,
+                                         mnMinY, mnMaxX, mnMaxY, queries.data(), qdesc.data(), owner.data(), &nq, (int)M,
+                                         inView ? inView->data() : nullptr, level ? level->data() : nullptr, viewCos ? viewCos->data() : nullptr),
+              "pslfe_line_project_frustum");
+        queries.resize(nq); qdesc.resize((size_t)nq * 32); owner.resize(nq);
+    }
+    // SearchByProjection(CurrentFrame, LastFrame, th) :112-155 up to the window search: the last frame's keylines / LBD rows and
+    // mvpMapLines as PslLastLine records (mldesc: the map lines' descriptors, or empty for the last frame's own rows).
+    void ProjectLastFrameLines(const std::vector<PslKeyLine>& klsLast, const std::vector<uint8_t>& ldescLast, const std::vector<PslLastLine>& lines,
+                               const std::vector<uint8_t>& mldesc, const PslPose& Tcw, const PslCamera& cam, float th, float mnMinX,
+                               float mnMinY, float mnMaxX, float mnMaxY, std::vector<PslLineQuery>& queries, std::vector<uint8_t>& qdesc,
+                               std::vector<int32_t>& owner) {
+        const size_t n = klsLast.size();
+        queries.resize(n); qdesc.resize(n * 32); owner.resize(n);
+        int nq = 0;
+        check(pslfe_line_project_last(ctx_.get(), klsLast.data(), ldescLast.data(), (int)n, lines.data(), mldesc.empty() ? nullptr : mldesc.data(),
+                                      &Tcw, &cam, th, mnMinX, mnMinY, mnMaxX, mnMaxY, queries.data(), qdesc.data(), owner.data(), &nq, (int)n),
+              "pslfe_line_project_last");
+        queries.resize(nq); qdesc.resize((size_t)nq * 32); owner.resize(nq);
+    }
 private:
     Context& ctx_;
 public:
@@ -377,6 +421,12 @@ public:
         return r;
     }
     pslfe_glue* get() const { return h_; }
+    // device view of the last batch's mvLines3D: [maxBatch][stride][6] doubles, stride = maxLines
+    const double* lines3dDevice(int* stride) const {
+        const double* d = nullptr;
+        check(pslfe_glue_lines3d_device(h_, &d, stride), "pslfe_glue_lines3d_device");
+        return d;
+    }
 private:
     pslfe_glue* h_ = nullptr;
     int maxFans_;
