@@ -205,6 +205,9 @@ int pslfe_line_results_device(pslfe_line* line, const PslKeyLine** d_kls, const 
 /* Copy one frame of the last batch to the host. *status (may be NULL): 0, or bit 1 = more raw segments
  * than the merge stage holds, bit 2 = cluster list overflow, bit 4 = more merged lines than cap. */
 int pslfe_line_fetch(pslfe_line* line, int frame, PslKeyLine* kls, uint8_t* desc, double* lineEq, int cap, int* n, int* status);
+/* The LSD segment list (x1, y1, x2, y2 rows, what pslfe_lsd_detect returns for one image) of one frame of the last batch:
+ * *n = its length, at most cap rows copied (PSLFE_E_CAPACITY beyond). */
+int pslfe_line_segments_fetch(pslfe_line* line, int frame, float* segments, int cap, int* n);
 
 /* == optimizeAndMergeLines_lsd(keylines, img) add_src/uselongline.cpp:449-485 on a segment list
  *    (MergeLines 0.05/5/15 -> drop < 30 px -> MergeLines 0.03/3/30 -> drop < 50 px -> KeyLines). */

@@ -668,6 +668,14 @@ def _line_fetch(self, frame, cap=1024):
     return kls[:n.value].copy(), desc[:n.value].copy(), eq[:n.value].copy(), st.value
 
 
+def _line_segments_fetch(self, frame, cap=8192):
+    """The LSD segment list of one frame of the last batch -> (n, 4) float32 (what lsd_detect returns for that image)."""
+    seg = np.zeros((cap, 4), np.float32)
+    n = C.c_int()
+    _check(lib().pslfe_line_segments_fetch(self._h, C.c_int(frame), _ptr(seg), C.c_int(cap), C.byref(n)), "pslfe_line_segments_fetch")
+    return seg[:n.value].copy()
+
+
 def _line_results_device(self):
     k, d, e, c, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
     _check(lib().pslfe_line_results_device(self._h, C.byref(k), C.byref(d), C.byref(e), C.byref(c), C.byref(cap)), "pslfe_line_results_device")
@@ -730,6 +738,7 @@ LINEextractor.match_batch_device = _line_match_batch_device
 LINEextractor.__call__ = _line_call
 LINEextractor.extract_batch_device = _line_extract_batch_device
 LINEextractor.fetch = _line_fetch
+LINEextractor.segments_fetch = _line_segments_fetch
 LINEextractor.results_device = _line_results_device
 LINEextractor.optimize_and_merge = _line_optimize_and_merge
 LINEextractor.lbd_compute = _line_lbd

@@ -534,6 +534,7 @@ __global__ __launch_bounds__(256, PSL_NFA_COUNT_WAVES) void k_lsd_nfa_count(Line
 // float ABOVE the threshold (never below FLT_MIN): a larger threshold only stops later.  `pad`: the length class, 0xffff = no series.
 struct LsdnSeries { double term, p_term; int n, i; float stop; uint16_t slot, pad; };
 static_assert(sizeof(LsdnSeries) == 32, "LsdnSeries is 32 bytes");
+static_assert(PSL_MERGE_NMAX * 5 <= 65535, "LsdnSeries.slot (uint16_t) indexes the 5 trials of up to maxseg = PSL_MERGE_NMAX rectangles");
 #define PSL_NFA_NCLS 12   // length classes of the series: class c holds predicted lengths in [2^c, 2^(c+1)) (c = 11: all longer ones)
 #ifndef PSL_NFA_FG
 #define PSL_NFA_FG 16     // frames whose series of one class are summed by one workgroup (8: nfa_eval 29.0 ms per 12288 dense frames, 16: 27.3, 32: 42.6, 64: 50.2 - profiles/r03z_ab_nfa_fg.log)

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "line_kernels2.h"
@@ -22,6 +23,23 @@
 #ifndef PSL_GROW_HELPER_FRAMES
 #define PSL_GROW_HELPER_FRAMES 64   // launches of at most this many frames run k_lsd_grow4 with helper waves (measured: tools/helper_sweep.sh)
 #endif
+
+// hipFuncSetAttribute acts on the function on the current device, not on an extractor object: the dynamic LDS k_lsd_grow4<3, 1> has
+// been allowed is kept per device and only ever raised (an extractor of a smaller geometry must not lower what another one relies on)
+#define PSL_GROW_LDS_DEVICES 64
+static std::mutex g_grow_lds_mu;
+static size_t g_grow_lds_attr[PSL_GROW_LDS_DEVICES];   // 0: the default 64 KB
+
+static hipError_t psl_grow_lds_allow(int device, size_t bytes) {
+    if (bytes <= 64u * 1024u) return hipSuccess;
+    if (device < 0 || device >= PSL_GROW_LDS_DEVICES) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lock(g_grow_lds_mu);
+    if (bytes <= g_grow_lds_attr[device]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsd_grow4<3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) g_grow_lds_attr[device] = bytes;
+    return e;
+}
+
 struct pslfe_line {
     pslfe_ctx* ctx = nullptr;
     int numOctaves = 1, nfeatures = 200, max_batch = 1;
@@ -46,7 +64,6 @@ struct pslfe_line {
     uint32_t* d_reg = nullptr;
     LsdnTables NT = {};           // LSD_REFINE_ADV: log_gamma / log(p) tables of nfa() (NT.lg in HBM)
     double* d_lgamma = nullptr;
-    size_t lds_used_attr = 64u * 1024u;   // dynamic LDS k_lsd_grow4<3, 1> has been allowed so far
     double* d_sctab = nullptr;    // psl_sincostab.inc
     double* d_rects = nullptr;    // LSD_REFINE_ADV: rectangles of k_lsd_grow4 for k_lsd_nfa
     int* d_nrect = nullptr;
@@ -291,10 +308,7 @@ struct pslfe_line {
             if (F <= PSL_GROW_HELPER_FRAMES) {  // few workgroups per XCD: three more waves each keep that XCD's L2 warm in front of the chain (line_kernels.h)
                 const size_t ubytes = (((size_t)P.W * P.H + 31) >> 5) * 4;   // the `used` bits of the frame in LDS (24 KB at 640x480, 96 KB at 1280x960)
                 if (PSL_GROW_LDS_USED && ubytes <= PSL_GROW_LDS_USED_MAX) {
-                    if (ubytes > lds_used_attr) {   // more than the default 64 KB of dynamic LDS needs the attribute (once per size)
-                        PSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsd_grow4<3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ubytes));
-                        lds_used_attr = ubytes;
-                    }
+                    PSL_HIP(psl_grow_lds_allow(ctx->device, ubytes));   // more than the default 64 KB of dynamic LDS needs the attribute
                     k_lsd_grow4<3, 1><<<F, 256, ubytes, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F, nullptr);
                 } else {
                     k_lsd_grow4<3, 0><<<F, 256, 0, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F, nullptr);
@@ -303,6 +317,7 @@ struct pslfe_line {
                 k_lsd_grow4<0, 0><<<F, 64, 0, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F,
                                                  PSL_FRAME_ORDER ? d_order : nullptr);
             PSL_STAGE_END(ctx, "line.lsd_grow");
+            PSL_HIP(hipGetLastError());   // a refused grow launch (e.g. its dynamic LDS) must not hide behind the NFA launches
         }
         if (refine >= 2) {
             // rect_improve + NFA: per phase a pixel-scan launch (16 lanes = rectangle x trial), two nfa() launches (thread = evaluation:
@@ -528,6 +543,24 @@ int pslfe_line_fetch(pslfe_line* line, int frame, PslKeyLine* kls, uint8_t* desc
         if (kls) PSL_HIP(hipMemcpyAsync(kls, line->d_kls + o, (size_t)cnt * sizeof(PslKeyLine), hipMemcpyDeviceToHost, st));
         if (desc) PSL_HIP(hipMemcpyAsync(desc, line->d_ldesc + o * 32, (size_t)cnt * 32, hipMemcpyDeviceToHost, st));
         if (lineEq) PSL_HIP(hipMemcpyAsync(lineEq, line->d_lineEq + o * 3, (size_t)cnt * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        PSL_HIP(hipStreamSynchronize(st));
+    }
+    return PSLFE_OK;
+}
+
+int pslfe_line_segments_fetch(pslfe_line* line, int frame, float* segments, int cap, int* n) {
+    PSL_REQUIRE(line && n, PSLFE_E_INVALID, "pslfe_line_segments_fetch: NULL argument");
+    PSL_REQUIRE(line->last_nframes > 0 && frame >= 0 && frame < line->last_nframes, PSLFE_E_STATE, "pslfe_line_segments_fetch: frame %d", frame);
+    PSL_HIP(hipSetDevice(line->ctx->device));
+    hipStream_t st = line->ctx->stream;
+    int cnt = 0;
+    PSL_HIP(hipMemcpyAsync(&cnt, line->d_nseg + frame, sizeof(int), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    *n = cnt;
+    PSL_REQUIRE(cnt <= cap && cnt <= line->P.maxseg, PSLFE_E_CAPACITY, "pslfe_line_segments_fetch: %d segments, capacity %d (list %d)", cnt, cap,
+                line->P.maxseg);
+    if (cnt > 0 && segments) {
+        PSL_HIP(hipMemcpyAsync(segments, line->d_seg + (size_t)frame * line->P.maxseg * 4, (size_t)cnt * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
         PSL_HIP(hipStreamSynchronize(st));
     }
     return PSLFE_OK;

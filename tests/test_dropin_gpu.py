@@ -13,8 +13,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("w,h,nfeatures,nlines,style,nframes", [(640, 480, 1000, 200, "struct", 5), (640, 480, 1000, 200, "desk", 3),
-                                                                (1280, 960, 2000, 200, "struct", 3)],
-                         ids=["configs2-struct", "configs2-desk", "configs4-1280x960"])
+                                                                (1280, 960, 2000, 200, "struct", 3), (640, 480, 1000, 200, "sticks", 4)],
+                         ids=["configs2-struct", "configs2-desk", "configs4-1280x960", "configs2-sticks"])
 def test_cpp_consumer_frame_and_tracking_sequence_equals_oracle(tmp_path, w, h, nfeatures, nlines, style, nframes):
     gray, depth = D.synth_stream(w, h, nframes, style, seed=77)
     frames, results = str(tmp_path / "frames.bin"), str(tmp_path / "results.bin")
@@ -34,8 +34,8 @@ def test_cpp_consumer_frame_and_tracking_sequence_equals_oracle(tmp_path, w, h, 
 
 
 @pytest.mark.parametrize("w,h,nfeatures,nlines,style,nframes,K", [(640, 480, 1000, 200, "struct", 7, 3), (640, 480, 1000, 200, "desk", 5, 8),
-                                                                  (1280, 960, 2000, 200, "struct", 4, 4)],
-                         ids=["configs2-struct-K3", "configs2-desk-K8", "configs4-1280x960-K4"])
+                                                                  (1280, 960, 2000, 200, "struct", 4, 4), (640, 480, 1000, 200, "sticks", 9, 8)],
+                         ids=["configs2-struct-K3", "configs2-desk-K8", "configs4-1280x960-K4", "configs2-sticks-K8"])
 def test_cpp_consumer_with_lookahead_prefetcher_equals_oracle(tmp_path, w, h, nfeatures, nlines, style, nframes, K):
     """pslfe::FramePrefetcher (host/pslfe.hpp): K frames pushed ahead and extracted by ONE batched launch (a last batch that is
     shorter included), every frame then tracked as before - the same arrays as the one-frame-at-a-time path and as the oracle."""

@@ -127,17 +127,26 @@ def test_lsd_large_regions_exercise_queue_overflow():
         assert len(ref) >= (4 if mode == STD else 2) and exact
 
 
+RAMP_CASES = [(40, 40, 0.3, 0), (40, 40, 0.3, 9), (40, 40, 0.3, 14), (40, 40, 0.45, 5), (40, 40, 0.6, 2), (40, 40, 0.6, 3), (40, 40, 0.8, 6),
+              (36, 36, 0.6, 21), (36, 36, 0.8, 17)]   # (w, h, noise, seed)
+
+
+def ramp_image(w, h, noise, seed):
+    """A noisy diagonal ramp: one LSD region is most of the image (test_lsd_reduce_region_radius_on_a_queue_of_most_of_the_image)."""
+    yy, xx = np.mgrid[0:h, 0:w]
+    return np.clip(254.0 / (w + h - 2) * (xx + yy) + np.random.default_rng(seed).normal(0, noise, (h, w)), 0, 255).astype(np.uint8)
+
+
 def test_lsd_reduce_region_radius_on_a_queue_of_most_of_the_image():
     """A noisy diagonal ramp on a small image: one region is most of the image and its rectangle, turned by 45 degrees, is twice its size - the
     density test fails, the refinement regrows it, and reduce_region_radius starts on a list of ~80 % of the pixels.  lsdw_refine's compaction by rank
     keeps a scratch list behind the queue; here list + removed pixels exceed the image (checked on the oracle's counts), so these steps take the walk that
     remains for that case, and the later, shorter ones the rank passes - segments bit for bit, both refine modes."""
     import oracle_lib
-    cases = [(40, 40, 0.3, 0), (40, 40, 0.3, 9), (40, 40, 0.3, 14), (40, 40, 0.45, 5), (40, 40, 0.6, 2), (40, 40, 0.6, 3), (40, 40, 0.8, 6), (36, 36, 0.6, 21), (36, 36, 0.8, 17)]
+    cases = RAMP_CASES
     over = steps = 0
     for w, h, noise, seed in cases:
-        yy, xx = np.mgrid[0:h, 0:w]
-        img = np.clip(254.0 / (w + h - 2) * (xx + yy) + np.random.default_rng(seed).normal(0, noise, (h, w)), 0, 255).astype(np.uint8)
+        img = ramp_image(w, h, noise, seed)
         st = oracle_lib.lsd_refine_stats(img)
         over += int(st[8] > st[9])
         steps += int(st[5])
@@ -162,6 +171,24 @@ def test_lsd_one_large_frame_on_both_sides_of_the_lds_map_limit(w, h):
     ref = oracle_lib.lsd_detect(img)
     got = _extractor(ADV).lsd_detect(img)
     assert len(ref) > 100 and got.shape == ref.shape and (got.view(np.uint32) == ref.view(np.uint32)).all()
+
+
+def test_lds_map_attribute_is_kept_per_device_across_extractors():
+    """The dynamic-LDS attribute of k_lsd_grow4<3, 1> belongs to the function on a device, not to an extractor: A at 1536x1152 (~138 KB of
+    `used` bits) raises it, B at 1280x960 (~96 KB) must not lower it, and A's next frame must still launch and equal its first result and
+    the oracle."""
+    import oracle_lib
+    img_a = _scene("struct", 23, 1, 1536, 1152)
+    img_b = _scene("struct", 41, 0, 1280, 960)
+    ref_a = oracle_lib.line_extract(img_a, 200)
+    a, b = _extractor(ADV, 1, 1.2, 200, 0.0), _extractor(ADV, 1, 1.2, 200, 0.0)
+    first = a(img_a)
+    _assert_extract_equal(first, ref_a, "extractor A, first frame")
+    _assert_extract_equal(b(img_b), oracle_lib.line_extract(img_b, 200), "extractor B")
+    again = a(img_a)
+    _assert_extract_equal(again, first, "extractor A after B")
+    _assert_extract_equal(again, ref_a, "extractor A after B vs oracle")
+    assert len(ref_a[0]) > 20
 
 
 def _adversarial_images():
