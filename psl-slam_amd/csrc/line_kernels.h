@@ -210,9 +210,6 @@ __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uin
 // Also tabulates, per pixel with a defined angle a = (double)deg * DEG_TO_RADS, the four values the
 // region-growing chain needs: cosf((float)a), sinf((float)a) (every pixel that joins a region) and
 // (float)cos(a), (float)sin(a) (the seed pixel), so that the serial chain contains no trigonometry.
-#ifndef PSL_LSD_SINGLES
-#define PSL_LSD_SINGLES 1   // 0: no static-singleton flags (A/B, tools/ab_build.sh)
-#endif
 #define PSL_GRAD_TH 16  // tile height of k_lsd_grad (64 x 16 pixels per workgroup, 4 per thread)
 // squared gradient magnitude of pixel (x, y); false where the reference leaves the angle undefined by construction
 __device__ __forceinline__ bool psl_lsd_norm(const LineParams& P, const double* __restrict__ img, int x, int y, double* q) {
@@ -348,7 +345,7 @@ __global__ __launch_bounds__(256, PSL_GRAD_WAVES) void k_lsd_grad(LineParams P, 
     // long as its heaviest frames) and pay 0.3 ms here: P.singles is set for launches of at most 64 frames.  (It can still be absorbed by a neighbour's region
     // before the scan reaches it: the test there is against the REGION's angle.)  Only pixels whose neighbours all lie in the tile
     // are examined; the others go the ordinary way.
-    for (int k = tid; PSL_LSD_SINGLES && P.singles && k < n; k += 256) {
+    for (int k = tid; P.singles && k < n; k += 256) {
         const int px = s_px[k], r = px >> 6, c = px & 63;
         if (r < 1 || r > PSL_GRAD_TH - 2 || c < 1 || c > 62) continue;
         const double ap = PSL_DMUL((double)s_deg[px], PSL_DEG2RAD);
@@ -384,9 +381,6 @@ __global__ __launch_bounds__(256, PSL_GRAD_WAVES) void k_lsd_grad(LineParams P, 
 // inside a class is whatever the atomics give: it only affects the schedule, never a result).
 #ifndef PSL_LSD_SUBBATCH
 #define PSL_LSD_SUBBATCH 2048   // frames whose f64 working image is resident between k_lsd_scale_tiled and k_lsd_grad (pslfe_line.hip: run_lsd)
-#endif
-#ifndef PSL_FRAME_ORDER
-#define PSL_FRAME_ORDER 1   // 0: frames in index order (A/B, tools/ab_build.sh)
 #endif
 #define PSL_ORDER_CLASSES 1024
 __global__ __launch_bounds__(1024) void k_frame_order(const int* __restrict__ weight, int nframes, int wmax, int* __restrict__ order) {
@@ -462,9 +456,6 @@ __device__ __forceinline__ double psl_lsd_density(int reg_size, const LsdRect& r
                             // -DPSL_LSD_RING=128 and running tests/test_line_gpu.py (its "band" image reaches a lag of 85)
 #endif
 #define PSL_LSD_HALF (PSL_LSD_RING / 2)
-#ifndef PSL_REDUCE_SERIAL
-#define PSL_REDUCE_SERIAL 0   // 1: reduce_region_radius walked entry by entry as the reference writes it (A/B, tools/ab_build.sh)
-#endif
 
 struct LsdW {
     int W, H, lane;
@@ -544,17 +535,16 @@ __device__ __forceinline__ int lsdw_pix(const LsdW& F, int x, int y) { return __
 //    (vector-memory operations complete in issue order), so the `used` word needs no wait of its own.
 // ---------------------------------------------------------------------------------------------
 #define PSL_G4_MARGIN 2.0e-3f
-#ifdef PSL_GROW_STATS   // diagnostic build only (PSLFE_EXTRA_FLAGS=-DPSL_GROW_STATS): loop trip counts of frame 0, printed by the kernel
-__device__ unsigned long long g_gstats[16];
-#define GS(k) (++gs[k])
-#else
-#define GS(k)
-#endif
 // a wave-uniform 64-bit value the compiler no longer knows to be uniform (after inline asm / volatile reloads): back into SGPRs
 __device__ __forceinline__ unsigned long long lsdg_uniform64(unsigned long long v) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
     return ((unsigned long long)hi << 32) | lo;
 }
+// The thresholds of lsdg_pops2's sure decisions, packed as th2 = (t_hi, t_lo): |cr| < t_hi dot => joins, |cr| >= t_lo dot => does not
+// (cr = S x u, dot = S . u).  No max(dot, 0) is needed: for dot <= 0 the first is false (t_hi >= 0) and the second true, as they
+// would be against max(dot, 0).  "Never": t_hi = 0 (|cr| < +-0 is false) below the margin, t_lo = NaN (every comparison false) once
+// prec + m reaches 1.5 rad.  Only th2 is read; the unpacked fields stay in the struct because removing them changes the instruction
+// schedule of k_lsd_grow4.
 struct LsdgFast { float t_hi, t_lo; int ok; unsigned long long th2; };
 __device__ __forceinline__ unsigned long long lsdg_pack2(float lo, float hi) {
     return ((unsigned long long)__float_as_uint(hi) << 32) | (unsigned long long)__float_as_uint(lo);
@@ -565,167 +555,32 @@ __device__ __forceinline__ LsdgFast lsdg_fast_setup(double prec) {
     LsdgFast f;
     const float p = (float)prec;
     f.ok = p + PSL_G4_MARGIN < 1.5f;
-    // cr < t_hi max(dot, 0) => joins, cr >= t_lo max(dot, 0) => does not; -1 / +inf: never true (inf * 0 = NaN compares false)
     f.t_hi = f.ok && p - PSL_G4_MARGIN > 0.f ? psl_tanf(p - PSL_G4_MARGIN) * (1.f - 1e-5f) : -1.f;
     f.t_lo = f.ok ? psl_tanf(p + PSL_G4_MARGIN) * (1.f + 1e-5f) : __builtin_inff();
-    // lsdg_pops2 compares with t dot instead of t max(dot, 0): |cr| < t_hi dot is false for dot <= 0 as it is (t_hi >= 0), |cr| >= t_lo dot true;
-    // "never": t_hi = 0 (|cr| < +-0 is false), t_lo = NaN (every comparison false)
     f.th2 = lsdg_pack2(f.t_hi > 0.f ? f.t_hi : 0.f, f.ok ? f.t_lo : __builtin_nanf(""));
     return f;
 }
 // The marks of the last round that ran (of this region or of the one before): possibly still on their way to memory.
 struct LsdgPend { unsigned long long PA; int pox, poy; };
 
-// The decision loop over the candidates of one popped entry, hand-scheduled: hipcc spends ~31 scalar instructions per accepted pixel on
-// this wave-uniform mask logic (every uniform bool becomes a 64-bit mask, a compare and a branch); written out it is 15.  `cand`:
-// candidates still to decide (absolute lane positions, ascending = visiting order).  Per iteration: masks of sure joins / sure
-// rejects against the current sums unless still valid (`fresh`), skip the sure rejects in front, take the first other candidate c:
-// a sure join is added (sums in order, its queue index, `live`), anything else ends the block with c returned (it is removed from
-// cand; the caller runs the reference's arithmetic for it).  Returns -1 when all candidates are decided.
-// gfx950 wait states observed: an SGPR written by a VALU instruction (v_readlane) is read by a VALU instruction no sooner than the third
-// instruction after it.
-__device__ __forceinline__ int lsdg_decide(unsigned long long& cand, unsigned long long& live, unsigned long long& RA, unsigned long long& RN, int& fresh,
-                                           int& reg_size, float& sumdx, float& sumdy, int& seq, float cs, float sn, float t_hi, float t_lo) {
-    int cx, c, sa, sb;
-    float t0, t1, t2;
-    unsigned long long tm;
-    asm volatile(
-        "s_mov_b32 %[cx], -1\n\t"
-        ".Ltop%=:\n\t"
-        "s_cmp_lg_u32 %[fresh], 0\n\t"
-        "s_cbranch_scc1 .Lhave%=\n\t"
-        "v_mul_f32 %[t0], %[sy], %[sn]\n\t"
-        "v_mul_f32 %[t1], %[sy], %[cs]\n\t"
-        "v_fmac_f32 %[t0], %[sx], %[cs]\n\t"
-        "v_fma_f32 %[t1], %[sx], %[sn], -%[t1]\n\t"
-        "v_max_f32 %[t0], 0, %[t0]\n\t"
-        "v_mul_f32 %[t2], %[thi], %[t0]\n\t"
-        "v_mul_f32 %[t0], %[tlo], %[t0]\n\t"
-        "v_cmp_lt_f32 %[RA], |%[t1]|, %[t2]\n\t"
-        "v_cmp_ge_f32 %[RN], |%[t1]|, %[t0]\n\t"
-        "s_mov_b32 %[fresh], 1\n\t"
-        ".Lhave%=:\n\t"
-        "s_andn2_b64 %[tm], %[cand], %[RN]\n\t"
-        "s_cbranch_scc0 .Lnone%=\n\t"
-        "s_ff1_i32_b64 %[c], %[tm]\n\t"
-        "s_lshl_b64 %[tm], -2, %[c]\n\t"
-        "s_and_b64 %[cand], %[cand], %[tm]\n\t"
-        "s_bitcmp1_b64 %[RA], %[c]\n\t"
-        "s_cbranch_scc0 .Lamb%=\n\t"
-        "s_mov_b32 m0, %[c]\n\t"
-        "v_readlane_b32 %[sa], %[cs], %[c]\n\t"
-        "v_readlane_b32 %[sb], %[sn], %[c]\n\t"
-        "v_writelane_b32 %[seq], %[rs], m0\n\t"
-        "s_nop 0\n\t"
-        "v_add_f32 %[sx], %[sa], %[sx]\n\t"
-        "v_add_f32 %[sy], %[sb], %[sy]\n\t"
-        "s_bitset0_b64 %[live], %[c]\n\t"
-        "s_add_i32 %[rs], %[rs], 1\n\t"
-        "s_mov_b32 %[fresh], 0\n\t"
-        "s_cmp_lg_u64 %[cand], 0\n\t"
-        "s_cbranch_scc1 .Ltop%=\n\t"
-        "s_branch .Ldone%=\n\t"
-        ".Lamb%=:\n\t"
-        "s_mov_b32 %[cx], %[c]\n\t"
-        "s_branch .Ldone%=\n\t"
-        ".Lnone%=:\n\t"
-        "s_mov_b64 %[cand], 0\n\t"
-        ".Ldone%=:\n\t"
-        : [cand] "+s"(cand), [live] "+s"(live), [RA] "+s"(RA), [RN] "+s"(RN), [fresh] "+s"(fresh), [rs] "+s"(reg_size), [sx] "+v"(sumdx), [sy] "+v"(sumdy),
-          [seq] "+v"(seq), [cx] "=&s"(cx), [c] "=&s"(c), [sa] "=&s"(sa), [sb] "=&s"(sb), [tm] "=&s"(tm), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
-        : [cs] "v"(cs), [sn] "v"(sn), [thi] "v"(t_hi), [tlo] "v"(t_lo)
-        : "scc", "m0");
-    return cx;
-}
-
-#ifndef PSL_GROW_ASM_POPS
-#define PSL_GROW_ASM_POPS 2   // 2: lsdg_pops2, 1: lsdg_pops, 0: the pop loop as compiled C++ around lsdg_decide (A/B, tools/ab_build.sh)
-#endif
-// lsdg_decide with the loop over the popped entries around it (round 3): per popped entry the compiler spent ~23 scalar instructions on
-// "which lane holds entry i, is it in the window's interior, which of its neighbours are live" (every uniform bool a 64-bit mask, a
-// compare, a select and a branch); written out it is 9.  Runs pops and decisions until no lane of the window's interior holds entry i
-// (returns -1: the round is over) or a candidate c falls inside the decision margin (returns c with the popped entry's remaining
-// candidates in `cand`: the caller runs the reference's arithmetic for c and calls again, which resumes with `cand`).
-__device__ __forceinline__ int lsdg_pops(unsigned long long& cand, unsigned long long& live, unsigned long long& RA, unsigned long long& RN, int& fresh,
-                                         int& reg_size, int& i, float& sumdx, float& sumdy, int& seq, float cs, float sn, float t_hi, float t_lo,
-                                         unsigned long long interior) {
-    int cx, c, sa, sb;
-    float t0, t1, t2;
-    unsigned long long tm;
-    const unsigned long long k3x3 = 0x070707ull;
-    asm volatile(
-        "s_mov_b32 %[cx], -1\n\t"
-        "s_cmp_lg_u64 %[cand], 0\n\t"
-        "s_cbranch_scc1 .Ltop%=\n\t"
-        ".Lpop%=:\n\t"
-        "v_cmp_eq_u32 vcc, %[i], %[seq]\n\t"
-        "s_and_b64 %[tm], vcc, %[inter]\n\t"
-        "s_cbranch_scc0 .Ldone%=\n\t"
-        "s_ff1_i32_b64 %[c], %[tm]\n\t"
-        "s_add_i32 %[c], %[c], -9\n\t"
-        "s_lshl_b64 %[tm], %[k3], %[c]\n\t"
-        "s_add_i32 %[i], %[i], 1\n\t"
-        "s_and_b64 %[cand], %[tm], %[live]\n\t"
-        "s_cbranch_scc0 .Lpop%=\n\t"
-        ".Ltop%=:\n\t"
-        "s_cmp_lg_u32 %[fresh], 0\n\t"
-        "s_cbranch_scc1 .Lhave%=\n\t"
-        "v_mul_f32 %[t0], %[sy], %[sn]\n\t"
-        "v_mul_f32 %[t1], %[sy], %[cs]\n\t"
-        "v_fmac_f32 %[t0], %[sx], %[cs]\n\t"
-        "v_fma_f32 %[t1], %[sx], %[sn], -%[t1]\n\t"
-        "v_max_f32 %[t0], 0, %[t0]\n\t"
-        "v_mul_f32 %[t2], %[thi], %[t0]\n\t"
-        "v_mul_f32 %[t0], %[tlo], %[t0]\n\t"
-        "v_cmp_lt_f32 %[RA], |%[t1]|, %[t2]\n\t"
-        "v_cmp_ge_f32 %[RN], |%[t1]|, %[t0]\n\t"
-        "s_mov_b32 %[fresh], 1\n\t"
-        ".Lhave%=:\n\t"
-        "s_andn2_b64 %[tm], %[cand], %[RN]\n\t"
-        "s_cbranch_scc0 .Lnone%=\n\t"
-        "s_ff1_i32_b64 %[c], %[tm]\n\t"
-        "s_lshl_b64 %[tm], -2, %[c]\n\t"
-        "s_and_b64 %[cand], %[cand], %[tm]\n\t"
-        "s_bitcmp1_b64 %[RA], %[c]\n\t"
-        "s_cbranch_scc0 .Lamb%=\n\t"
-        "s_mov_b32 m0, %[c]\n\t"
-        "v_readlane_b32 %[sa], %[cs], %[c]\n\t"
-        "v_readlane_b32 %[sb], %[sn], %[c]\n\t"
-        "v_writelane_b32 %[seq], %[rs], m0\n\t"
-        "s_nop 0\n\t"
-        "v_add_f32 %[sx], %[sa], %[sx]\n\t"
-        "v_add_f32 %[sy], %[sb], %[sy]\n\t"
-        "s_bitset0_b64 %[live], %[c]\n\t"
-        "s_add_i32 %[rs], %[rs], 1\n\t"
-        "s_mov_b32 %[fresh], 0\n\t"
-        "s_cmp_lg_u64 %[cand], 0\n\t"
-        "s_cbranch_scc1 .Ltop%=\n\t"
-        "s_branch .Lpop%=\n\t"
-        ".Lamb%=:\n\t"
-        "s_mov_b32 %[cx], %[c]\n\t"
-        "s_branch .Ldone%=\n\t"
-        ".Lnone%=:\n\t"
-        "s_mov_b64 %[cand], 0\n\t"
-        "s_branch .Lpop%=\n\t"
-        ".Ldone%=:\n\t"
-        : [cand] "+s"(cand), [live] "+s"(live), [RA] "+s"(RA), [RN] "+s"(RN), [fresh] "+s"(fresh), [rs] "+s"(reg_size), [i] "+s"(i), [sx] "+v"(sumdx),
-          [sy] "+v"(sumdy), [seq] "+v"(seq), [cx] "=&s"(cx), [c] "=&s"(c), [sa] "=&s"(sa), [sb] "=&s"(sb), [tm] "=&s"(tm), [t0] "=&v"(t0), [t1] "=&v"(t1),
-          [t2] "=&v"(t2)
-        : [cs] "v"(cs), [sn] "v"(sn), [thi] "v"(t_hi), [tlo] "v"(t_lo), [inter] "s"(interior), [k3] "s"(k3x3)
-        : "scc", "m0", "vcc");
-    return cx;
-}
-
-// lsdg_pops with packed f32 arithmetic and without the `fresh` flag (round 3, second pass; PSL_GROW_ASM_POPS == 2).  The kernel's time is its
-// instruction count (7 waves per SIMD take as long as 8: profiles/r03t_ab_waves.log), and an accepted pixel cost 15 vector + 25 scalar
-// instructions.  Now: the sums live in one register pair S = (sum dx, sum dy), the pixel's vector in U = (cos, sin), the thresholds in
-// TH = (t_hi, t_lo);   (S.x U.x, S.x U.y)  ->  (S.y U.y + S.x U.x, -S.y U.x + S.x U.y) = (dot, cross)  ->  (t_hi dot, t_lo dot)  is three
-// packed instructions, the two compares make five (nine before; max(dot, 0) is not needed: see lsdg_fast_setup), the sums take one
-// packed add.  Whether the masks belong to the current sums is known from the place in the code (two copies of the pop sequence) instead of
-// a flag that is set, reset and tested.  10 vector + ~21 scalar instructions per accepted pixel.  D, PT, U and the pair the accepted
-// vector is read into are bound to registers by name: v_cmp / v_readlane take halves of those pairs, which an operand cannot express.
-// Rounding differs from the three-operation form (one fused step); the decision is only taken outside the margin, which is 2e-3 rad
-// against errors of ~1e-7 |S|.  Re-entry after the caller's exact test recomputes the masks.
+// The pop loop of a window round, hand-scheduled.  Pops queue entries for as long as a lane of the window's 6 x 6 interior holds entry i;
+// a popped entry's candidates (`cand`: its live 3 x 3 neighbours, absolute lane positions, ascending = visiting order) are decided
+// against the current sums: sure rejects are skipped, a sure join is added (sums in order, its queue index, `live`).  Returns -1 when
+// no lane of the interior holds entry i (the round is over), or the first candidate c inside the decision margin, with the popped
+// entry's remaining candidates in `cand`: the caller runs the reference's arithmetic for c and calls again, which resumes with `cand`
+// and recomputes the masks.
+// Why assembly: the kernel's time is its instruction count (7 waves per SIMD take as long as 8: profiles/r03t_ab_waves.log).  Compiled
+// from C++, this wave-uniform logic cost ~23 scalar instructions per popped entry and ~31 per accepted pixel (every uniform bool a
+// 64-bit mask, a compare, a select and a branch); written out with one f32 operation per instruction, an accepted pixel cost 15 vector
+// + 25 scalar instructions.  Here the sums live in one register pair S = (sum dx, sum dy), the pixel's vector in U = (cos, sin), the
+// thresholds in TH = (t_hi, t_lo);   (S.x U.x, S.x U.y)  ->  (S.y U.y + S.x U.x, -S.y U.x + S.x U.y) = (dot, cross)  ->  (t_hi dot,
+// t_lo dot)  is three packed instructions, the two compares make five (nine in unpacked form; max(dot, 0) is not needed: see
+// lsdg_fast_setup), the sums take one packed add.  Whether the masks belong to the current sums is known from the place in the code (two
+// copies of the pop sequence) instead of a flag that is set, reset and tested.  10 vector + ~21 scalar instructions per accepted pixel.
+// D, PT, U and the pair the accepted vector is read into are bound to registers by name: v_cmp / v_readlane take halves of those pairs,
+// which an operand cannot express.  Rounding differs from computing dot and cross with a separate multiply and add each (here one step
+// is fused); the decision is only taken outside the margin, which is 2e-3 rad against errors of ~1e-7 |S|.  gfx950 wait states observed:
+// an SGPR written by a VALU instruction (v_readlane) is read by a VALU instruction no sooner than the third instruction after it.
 __device__ __forceinline__ int lsdg_pops2(unsigned long long& cand, unsigned long long& live, int& reg_size, int& i, unsigned long long& S, int& seq,
                                           unsigned long long U, unsigned long long TH, unsigned long long interior) {
     int cx, c;
@@ -817,17 +672,12 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
     const float2 t0 = F.seedt[addr0];
     float sumdx = t0.x, sumdy = t0.y;
     unsigned long long tch = 0ull;
-#ifdef PSL_GROW_STATS
-    unsigned gs[16] = {0};
-#endif
-    GS(0);
     int rs_angle = 1;  // the region size reg_deg belongs to (the seed's own angle at 1)
     unsigned long long PA = pd.PA;
     int pox = pd.pox, poy = pd.poy;
     int i = 0;
     while (i < reg_size) {
         const int rs0 = reg_size;
-        GS(1);
         const int qi = i + lane;
         uint32_t q = 0xffffffffu;
         if (reg_size - i > PSL_LSD_HALF) {  // uniform: the frontier lags more than half a ring behind the queue's end: the entries in front of
@@ -845,9 +695,6 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
         const int x = ox + lx, y = oy + ly;
         const bool inside = (unsigned)x < (unsigned)F.W && (unsigned)y < (unsigned)F.H;
         const int cidx = inside ? lsdw_pix(F, x, y) : addr0;
-#ifdef PSL_GROW_STATS
-        const unsigned long long st_l0 = __builtin_amdgcn_s_memtime();
-#endif
         const float2 t = F.trig[cidx];
         const bool ub = lsdg_used<LU>(F, cidx);
         // queue entry -> lane of the window (while the load is in flight)
@@ -860,42 +707,9 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
         const int px = x - pox, py = y - poy;
         const bool pa = LU ? false : ((unsigned)px < 8u && (unsigned)py < 8u && ((PA >> (py * 8 + px)) & 1ull) != 0ull);   // (marks in LDS are never "on their way")
         const uint32_t xy = (uint32_t)x | ((uint32_t)y << 16);
-#ifdef PSL_GROW_STATS
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // [8]: cycles from the window's loads to their data (with the LDS map work in their shadow)
-        if (blockIdx.x == 0 && lane == 0) g_gstats[8] += __builtin_amdgcn_s_memtime() - st_l0;
-#endif
         const float cs = t.x, sn = t.y;
         // a lane that holds a queue entry is a pixel of the region (the seed among them: its mark is not in memory yet)
         unsigned long long live = __ballot((int)inside & ((int)(cs != 0.f) | (int)(sn != 0.f)) & (int)!ub & (int)!pa & (int)(seq < 0));   // (no short circuit: one straight run of compares)
-        unsigned long long RA = 0ull, RN = 0ull;  // valid while the sums are the ones they were computed from (`fresh`)
-        int fresh = 0;
-#if defined(PSL_GROW_STATS) || !PSL_GROW_ASM_POPS   // the same loop as the compiler writes it (diagnostic counters; A/B)
-        for (;;) {
-            const unsigned long long m = __ballot(seq == i) & F.interior;  // in the window, and in its 6 x 6 interior
-            if (!m) break;  // (also when i == reg_size: no lane holds an index that does not exist yet)
-            const int sh = __ffsll((long long)m) - 10;
-            unsigned long long cand = (0x070707ull << sh) & live;  // the 3 x 3 neighbours, ascending bit = visiting order
-            ++i;
-            GS(2);
-            if (cand) GS(3);
-            while (cand) {
-                GS(4);
-                const int c = lsdg_decide(cand, live, RA, RN, fresh, reg_size, sumdx, sumdy, seq, cs, sn, fc.t_hi, fc.t_lo);
-                if (c < 0) break;
-                // lane c is within the margin of the threshold: the reference's arithmetic
-                GS(6);
-                if (rs_angle != reg_size) { reg_deg = psl_fast_atan2(sumdy, sumdx); rs_angle = reg_size; }
-                const double ad = PSL_DMUL((double)F.ang[cidx], PSL_DEG2RAD), th = PSL_DMUL((double)reg_deg, PSL_DEG2RAD);
-                if (!((__ballot(lsdg_aligned(ad, th, prec)) >> c) & 1ull)) continue;
-                sumdx = PSL_FADD(sumdx, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), c)));
-                sumdy = PSL_FADD(sumdy, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), c)));
-                if (lane == c) seq = reg_size;
-                live &= ~(1ull << c);
-                ++reg_size;
-                fresh = 0;
-            }
-        }
-#elif PSL_GROW_ASM_POPS == 2
         unsigned long long cand = 0ull;
         unsigned long long S = lsdg_pack2(sumdx, sumdy);
         const unsigned long long U = lsdg_pack2(cs, sn);
@@ -913,24 +727,6 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
             ++reg_size;
         }
         sumdx = lsdg_lo(S); sumdy = lsdg_hi(S);
-        (void)RA; (void)RN; (void)fresh;
-#else
-        unsigned long long cand = 0ull;
-        for (;;) {
-            const int c = lsdg_pops(cand, live, RA, RN, fresh, reg_size, i, sumdx, sumdy, seq, cs, sn, fc.t_hi, fc.t_lo, F.interior);
-            if (c < 0) break;   // no lane of the window's interior holds entry i: the round is over
-            // lane c is within the margin of the threshold: the reference's arithmetic
-            if (rs_angle != reg_size) { reg_deg = psl_fast_atan2(sumdy, sumdx); rs_angle = reg_size; }
-            const double ad = PSL_DMUL((double)F.ang[cidx], PSL_DEG2RAD), th = PSL_DMUL((double)reg_deg, PSL_DEG2RAD);
-            if (!((__ballot(lsdg_aligned(ad, th, prec)) >> c) & 1ull)) continue;
-            sumdx = PSL_FADD(sumdx, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), c)));
-            sumdy = PSL_FADD(sumdy, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), c)));
-            if (lane == c) seq = reg_size;
-            live &= ~(1ull << c);
-            ++reg_size;
-            fresh = 0;
-        }
-#endif
         // the round's pixels: queue entries and marks, one store instruction each
         const bool mine = seq >= rs0;
         const unsigned long long acc_round = __ballot(mine);
@@ -950,9 +746,6 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
     if (tch) touched = true;
     pd.PA = PA; pd.pox = pox; pd.poy = poy;
     if (rs_angle != reg_size) reg_deg = psl_fast_atan2(sumdy, sumdx);
-#ifdef PSL_GROW_STATS
-    if (blockIdx.x == 0 && lane == 0) for (int k = 0; k < 16; ++k) g_gstats[k] += gs[k];
-#endif
     *reg_angle_out = PSL_DMUL((double)reg_deg, PSL_DEG2RAD);
     return reg_size;
 }
@@ -995,10 +788,6 @@ __device__ __forceinline__ double lsdw_lane_f64(double v, int lane) {
 }
 
 __device__ void lsdw_region2rect(const LsdW& F, int reg_size, double reg_angle, double prec, LsdRect* rec) {
-#if PSL_GROW_DIAG == 4 || PSL_GROW_DIAG == 5
-  for (int diag_rep = 0; diag_rep < (PSL_GROW_DIAG == 4 ? 2 : 1); ++diag_rep) {
-    asm volatile("" ::: "memory");
-#endif
     double acc = 0;  // lane 0: sum x w, lane 1: sum y w, lane 2: sum w
     for (int base = 0; base < reg_size; base += 64) {
         const int j = base + F.lane, cnt = min(64, reg_size - base);
@@ -1060,9 +849,6 @@ __device__ void lsdw_region2rect(const LsdW& F, int reg_size, double reg_angle, 
     rec->width = PSL_DSUB(w_max, w_min);
     if (rec->width < 1.0) rec->width = 1.0;
     rec->theta = theta; rec->dx = dx; rec->dy = dy;  // read by the NFA validation (LSD_REFINE_ADV) only
-#if PSL_GROW_DIAG == 4 || PSL_GROW_DIAG == 5
-  }
-#endif
 }
 
 template <int LU>
@@ -1076,11 +862,6 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
     const double ang_c = PSL_DMUL((double)F.ang[x0 + y0 * F.W], PSL_DEG2RAD);
     double acc = 0;  // lane 0: sum of the angle differences, lane 1: sum of their squares (pixels outside the radius stage +0.0)
     int n = 0;
-#if PSL_GROW_DIAG == 5
-  for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-    asm volatile("" ::: "memory");
-    acc = 0; n = 0;
-#endif
     for (int base = 0; base < reg_size; base += 64) {
         const int j = base + F.lane, cnt = min(64, reg_size - base);
         double ang_d = 0;
@@ -1101,9 +882,6 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
         acc = lsdw_sum_rows(F, acc, cnt);
         __builtin_amdgcn_wave_barrier();
     }
-#if PSL_GROW_DIAG == 5
-  }
-#endif
     const double sum = lsdw_lane_f64(acc, 0), s_sum = lsdw_lane_f64(acc, 1);
     const double mean_angle = sum / (double)n;
     const double tau = PSL_DMUL(2.0, __dsqrt_rn(PSL_DADD(PSL_DSUB(s_sum, PSL_DMUL(PSL_DMUL(2.0, mean_angle), sum)) / (double)n, PSL_DMUL(mean_angle, mean_angle))));
@@ -1129,13 +907,7 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
     while (density < density_th) {
         radSq = PSL_DMUL(radSq, 0.75 * 0.75);
         const int n = reg_size;
-#if !PSL_REDUCE_SERIAL
         int m = 0;
-#if PSL_GROW_DIAG == 5
-      for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-        asm volatile("" ::: "memory");
-        m = 0;
-#endif
         for (int base = 0; base < n; base += 64) {
             const int j = base + F.lane;
             bool in = false;
@@ -1147,18 +919,10 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
             }
             m += __popcll(__ballot(in));
         }
-#if PSL_GROW_DIAG == 5
-      }
-#endif
         if (m == n) continue;
         if (m >= 2 && (size_t)n + (size_t)(n - m) <= (size_t)F.W * F.H) {
             uint32_t* S = F.reg + n;   // scratch: the stayers behind m, last first (at most n - m of them)
             int fr = 0;
-#if PSL_GROW_DIAG == 5
-          for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-            asm volatile("" ::: "memory");
-            fr = 0;
-#endif
             for (int e = n; e > m; e -= 64) {
                 const int q = e - 1 - F.lane;
                 bool in = false;
@@ -1171,9 +935,6 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
                 if (in) S[fr + __popcll(b & lt)] = rp;
                 fr += __popcll(b);
             }
-#if PSL_GROW_DIAG == 5
-          }
-#endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             int hr = 0;
             for (int base = 0; base < m; base += 64) {
@@ -1190,9 +951,7 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
             reg_size = m;
         } else if (m < 2) {
             reg_size = m;   // (the marks are released; what the list holds no longer matters)
-        } else
-#endif
-        {   // the walk as written (no room for the scratch list behind a queue of more than two thirds of the image; or -DPSL_REDUCE_SERIAL=1)
+        } else {   // the walk as written (no room for the scratch list behind a queue of more than two thirds of the image)
             for (int i = 0; i < reg_size; ++i) {
                 const uint32_t rp = F.reg[i];
                 const int px = (int)(rp & 0xffff), py = (int)(rp >> 16);
@@ -1245,13 +1004,10 @@ __device__ __forceinline__ void psl_lsd_store_segment(const LineParams& P, doubl
     out[0] = e[0]; out[1] = e[1]; out[2] = e[2]; out[3] = e[3];
 }
 
-#ifndef PSL_GROW_DIAG
-#define PSL_GROW_DIAG 0
-#endif
 #ifndef PSL_GROW_WAVES
 #define PSL_GROW_WAVES 8   // waves per SIMD.  Round 2 (1024-entry ring, 12288 struct frames, tools/occ_sweep.sh): 5: 60.5 ms, 6: 52.1 ms, 7: 53.4 ms - but 5.9 KB of
                            // LDS per wave capped the CU at 27 waves, so 7 and 8 never ran.  Round 3, 512-entry ring (3.8 KB per wave, 32 waves per CU), 12288 frames of
-                           // the dense scene, A/B in one session (tools/ab_round3.sh, profiles/r03c_ab_waves.log): 6: 261.3 ms, 7: 246.3 ms, 8: 242.8 ms (64 VGPRs, 36
+                           // the dense scene, A/B in one session (profiles/r03c_ab_waves.log): 6: 261.3 ms, 7: 246.3 ms, 8: 242.8 ms (64 VGPRs, 36
                            // spilled to scratch, 133 SGPR spills: the kernel is bound by instruction issue, not by the waves in flight; -7 %).
                            // Without a bound the kernel takes 105 VGPRs (4 waves): 63.1 ms on the struct scene
 #endif
@@ -1312,9 +1068,6 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
     const LsdgFast fcP = lsdg_fast_setup(P.prec);
     LsdgPend pd;
     pd.PA = 0ull; pd.pox = 0; pd.poy = 0;
-#ifdef PSL_GROW_STATS
-    const unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // (the used flags start at 0: k_lsd_grad has just written the records)
     (void)words;
     float* out = seg + (size_t)frame * P.maxseg * 4;
@@ -1376,12 +1129,7 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
                 mask &= mask - 1;
                 int x = trip_x + q * 64 + s, y = trip_y;
                 while (x >= P.W) { x -= P.W; ++y; }
-#if PSL_GROW_DIAG == 3   // diagnostic timing builds only (tools/ab_round3e.sh): 3 = no growth at all (every seed a singleton), 1 = no rectangle / refinement, 2 = no refinement;
-                         // 4 = every region2rect twice, 5 = the refinement's statistics loop and the count / scratch passes of its radius steps twice (same results: their cost = the time added)
-                if (true) {
-#else
                 if ((smq >> s) & 1ull) {
-#endif
                     // a static singleton: the region it would grow is itself.  Its mark joins the pending ones if it lies in their window;
                     // otherwise those are waited for and it opens a window of its own.
                     if (!LU) {
@@ -1398,33 +1146,12 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
                 }
                 double reg_angle;
                 bool touched = false;
-#ifdef PSL_GROW_STATS
-                const unsigned long long st_g0 = __builtin_amdgcn_s_memtime();
-#endif
                 int reg_size = lsdg_region_grow4<LU>(F, x, y, &reg_angle, P.prec, fcP, pd, false, trip_end, touched);
-#ifdef PSL_GROW_STATS
-                if (frame == 0 && lane == 0) g_gstats[11] += __builtin_amdgcn_s_memtime() - st_g0;
-                const unsigned long long st_r1 = __builtin_amdgcn_s_memtime();
-#endif
                 if (touched) { stale = true; dirty = true; }
                 if (reg_size < P.min_reg_size) continue;
-#if PSL_GROW_DIAG == 1
-                continue;
-#endif
                 LsdRect rec;
                 lsdw_region2rect(F, reg_size, reg_angle, P.prec, &rec);
-#ifdef PSL_GROW_STATS
-                const unsigned long long st_r2 = __builtin_amdgcn_s_memtime();
-                if (frame == 0 && lane == 0) g_gstats[9] += st_r2 - st_r1;
-#endif
-#if PSL_GROW_DIAG == 2
-                const int kept = reg_size;
-#else
                 const int kept = lsdw_refine<LU>(F, reg_size, reg_angle, P.prec, &rec, 0.7, pd, trip_end, touched);
-#endif
-#ifdef PSL_GROW_STATS
-                if (frame == 0 && lane == 0) g_gstats[10] += __builtin_amdgcn_s_memtime() - st_r2;
-#endif
                 if (touched) { stale = true; dirty = true; }
                 if (!kept) continue;
                 if (count < P.maxseg && lane == 0) {
@@ -1441,17 +1168,6 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
     }
     if (HELPERS && lane == 0) *(volatile int*)&s_scan_unit = (int)(npx >> 6);  // the helpers' exit condition
     if (lane == 0) nseg[frame] = count < P.maxseg ? count : P.maxseg;
-#ifdef PSL_GROW_STATS
-    if (frame == 0 && lane == 0) {
-        const unsigned long long dc = __builtin_amdgcn_s_memtime() - st_c0, dr = __builtin_amdgcn_s_memrealtime() - st_r0;
-        printf("grow clock: %llu shader cycles in %llu ticks of 100 MHz = %.0f MHz\n", dc, dr, (double)dc / (double)dr * 100.0);
-        printf("grow stats: regions %llu rounds %llu pops %llu pops_with_candidates %llu decision_blocks %llu exact_tests %llu\n", g_gstats[0], g_gstats[1],
-               g_gstats[2], g_gstats[3], g_gstats[4], g_gstats[6]);
-        printf("grow cycles: growth of the scan's regions %llu (of which waiting for the window loads of ALL growths incl. the refinement's %llu), region2rect %llu, refinement %llu\n",
-               g_gstats[11], g_gstats[8], g_gstats[9], g_gstats[10]);
-        for (int k = 0; k < 16; ++k) g_gstats[k] = 0;
-    }
-#endif
 }
 
 #endif

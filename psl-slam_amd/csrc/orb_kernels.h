@@ -226,40 +226,17 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
 //     test scores below minTh - and both only for the rare pixel where both pass;
 //   * NMS and the raster-ordered output are driven by the compacted list (a few % of the pixels): survivors
 //     set a bit in a per-row mask, row prefix sums give the raster positions.
-#ifndef PSL_FAST_DIAG
-#define PSL_FAST_DIAG 0   // timing builds only (tools/ab_round3x.sh): 1 = the quick test twice, 2 = the scores twice, 3 = NMS + output twice, 4 = tile load + clears twice (same results)
-#endif
 #define PSL_FAST4_TP 76   // tile pitch (bytes): 1 + (64 + 6) + slack, multiple of 4
 #define PSL_FAST4_SP 72   // score pitch (bytes): interior x at byte 4 + x
 __device__ __forceinline__ uint32_t psl_alignbyte(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbyte(hi, lo, sh); }
 
-// max over the 16 arcs of 9 contiguous ring pixels of min(sgn * (v - ring)), minus 1: the cornerScore of one polarity
-__device__ __forceinline__ int psl_fast_score_pol(const uint8_t* c, const int tp, const int sgn) {
-    const int sv = sgn * (int)c[0];
-    int e[16];
-    e[0] = sv - sgn * c[3 * tp];       e[1] = sv - sgn * c[3 * tp + 1];   e[2] = sv - sgn * c[2 * tp + 2];   e[3] = sv - sgn * c[tp + 3];
-    e[4] = sv - sgn * c[3];            e[5] = sv - sgn * c[-tp + 3];      e[6] = sv - sgn * c[-2 * tp + 2];  e[7] = sv - sgn * c[-3 * tp + 1];
-    e[8] = sv - sgn * c[-3 * tp];      e[9] = sv - sgn * c[-3 * tp - 1];  e[10] = sv - sgn * c[-2 * tp - 2]; e[11] = sv - sgn * c[-tp - 3];
-    e[12] = sv - sgn * c[-3];          e[13] = sv - sgn * c[tp - 3];      e[14] = sv - sgn * c[2 * tp - 2];  e[15] = sv - sgn * c[3 * tp - 1];
-    int lo2[16], lo4[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) lo2[k] = min(e[k], e[(k + 1) & 15]);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) lo4[k] = min(lo2[k], lo2[(k + 2) & 15]);
-    int A = -256;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) A = max(A, min(min(lo4[k], lo4[(k + 4) & 15]), e[(k + 8) & 15]));
-    return A - 1;
-}
-
-#ifndef PSL_FAST_SCORE_PK
-#define PSL_FAST_SCORE_PK 1   // 0: psl_fast_score_pol, one ring difference per instruction (A/B, tools/ab_build.sh)
-#endif
-// The same score with TWO ring positions per instruction (packed signed 16-bit: the differences lie in [-255, 255]).  The scores are 36 % of the kernel
-// (12.9 of 35.4 ms per 12288 dense frames, profiles/r03g_fast_parts_twice.log) and the kernel is bound by vector issue.  E[j] = (e[2j], e[2j+1]),
-// O[j] = (e[2j+1], e[2j+2]) (one v_alignbit of two E's); then min over a pair of neighbours, over four, over the nine of an arc, and the maximum
-// over the arcs, all on pairs: 41 packed instructions instead of 80, and e = sgn v - sgn ring is one packed multiply-add per pair.
-// Measured: 35.15 -> 34.63 ms (profiles/r03g_ab_fast_score_pk.log) - far less than the instruction count promised: the 16 byte reads of the ring from LDS, not the
+// The cornerScore of one polarity: the maximum over the 16 arcs of 9 contiguous ring pixels of min(e) over the arc, minus 1, where
+// e[k] = sgn v - sgn ring[k] (v the centre, ring[k] the k-th pixel of the radius-3 circle, r[] below).  Two ring positions per instruction
+// (packed signed 16-bit: the differences lie in [-255, 255]).  The scores are 36 % of the kernel (12.9 of 35.4 ms per 12288 dense frames,
+// profiles/r03g_fast_parts_twice.log) and the kernel is bound by vector issue.  E[j] = (e[2j], e[2j+1]), O[j] = (e[2j+1], e[2j+2]) (one
+// v_alignbit of two E's); then min over a pair of neighbours, over four, over the nine of an arc, and the maximum over the arcs, all on
+// pairs: 41 packed instructions instead of 80 with one ring position per instruction, and e is one packed multiply-add per pair.
+// Measured against that form: 35.15 -> 34.63 ms (profiles/r03g_ab_fast_score_pk.log) - far less than the instruction count promised: the 16 byte reads of the ring from LDS, not the
 // min / max tree, are what a score costs.
 typedef short psl_i16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int psl_fast_score_pol_pk(const uint8_t* c, const int tp, const int sgn) {
@@ -323,10 +300,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     // LDS tile byte (1 + x) of row y = image pixel (iniX + x, iniY + y); dword d of a row = image bytes
     // iniX - 1 + 4d .. + 3, assembled from the two aligned global dwords that hold them
     const bool aligned4 = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)pitch) & 3) == 0 && iniX >= 4 && maxX + 8 <= pitch;
-#if PSL_FAST_DIAG == 4
-  for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-    asm volatile("" ::: "memory");
-#endif
     const int ndw = (tw + 4) >> 2;  // <= 18
     if (aligned4) {
         const int gx0 = (iniX - 1) & ~3;
@@ -347,9 +320,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     (&s_rowmask[0][0][0])[tid] = 0;  // 2 * 64 * 2 words
     if (tid == 0) s_nlist = 0;
     __syncthreads();
-#if PSL_FAST_DIAG == 4
-  }
-#endif
 
     const int ng = (iw + 3) >> 2;            // groups of 4 pixels per row, <= 16
     const int nitems = ng * ih;              // <= 1024
@@ -364,10 +334,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
         const int idx = p * 256 + tid;
         uint32_t m4 = 0, pol = 0;  // pol: 2 bits per pixel
         int y = 0, g = 0;
-#if PSL_FAST_DIAG == 1
-      for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-        asm volatile("" ::: "memory");
-#endif
         if (idx < nitems) {
             y = (int)(((uint32_t)idx * magic) >> 20);
             g = idx - y * ng;
@@ -409,10 +375,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
             if (nin < 4) pol &= (1u << (2 * nin)) - 1u;
             m4 = ((pol | (pol >> 1)) & 0x1u) | (((pol | (pol >> 1)) >> 1) & 0x2u) | (((pol | (pol >> 1)) >> 2) & 0x4u) | (((pol | (pol >> 1)) >> 3) & 0x8u);
         }
-#if PSL_FAST_DIAG == 1
-        asm volatile("" : "+v"(m4), "+v"(pol));
-      }
-#endif
         // order inside s_list is irrelevant: one slot range per (wave, jj)
         const unsigned long long b0 = __ballot(m4 & 1), b1 = __ballot(m4 & 2), b2 = __ballot(m4 & 4), b3 = __ballot(m4 & 8);
         const int n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2), n3 = __popcll(b3);
@@ -430,34 +392,17 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     }
     __syncthreads();
     const int nlist = s_nlist;
-#if PSL_FAST_DIAG == 2
-  for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-    asm volatile("" ::: "memory");
-#endif
     for (int k = tid; k < nlist; k += 256) {
         const int e = s_list[k];
         const int y = (e >> 6) & 63, x = e & 63, pl = e >> 12;
         const uint8_t* c = &s_tile[(y + 3) * PSL_FAST4_TP + x + 4];
         // polarity bit 0: ring brighter than the centre (ring - v), bit 1: ring darker (v - ring)
-#if PSL_FAST_SCORE_PK
         int s = psl_fast_score_pol_pk(c, PSL_FAST4_TP, (pl & 1) ? -1 : 1);
         if (pl == 3) s = max(s, psl_fast_score_pol_pk(c, PSL_FAST4_TP, 1));
-#else
-        int s = psl_fast_score_pol(c, PSL_FAST4_TP, (pl & 1) ? -1 : 1);
-        if (pl == 3) s = max(s, psl_fast_score_pol(c, PSL_FAST4_TP, 1));
-#endif
         s = s < minTh ? 0 : (s > 255 ? 255 : s);
         s_score[(y + 1) * PSL_FAST4_SP + x + 4] = (uint8_t)s;
     }
-#if PSL_FAST_DIAG == 2
-  }
-#endif
     __syncthreads();
-#if PSL_FAST_DIAG == 3
-  for (int diag_rep = 0; diag_rep < 2; ++diag_rep) {
-    asm volatile("" ::: "memory");
-    __syncthreads();
-#endif
     // cv::FAST's NMS: strictly greater than the 8 neighbours (scores outside the interior are 0)
     for (int k = tid; k < nlist; k += 256) {
         const int e = s_list[k];
@@ -503,13 +448,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
                 out[pos] = (uint32_t)(x + 3 + j * L.wCell) | ((uint32_t)(y + 3 + i * L.hCell) << 12) | (sc << 24);
         }
     }
-#if PSL_FAST_DIAG == 3
-    if (diag_rep == 1)
-#endif
     if (tid == 0) *out_cnt = total < P.cellcap ? total : P.cellcap;
-#if PSL_FAST_DIAG == 3
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------

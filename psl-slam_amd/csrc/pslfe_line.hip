@@ -16,10 +16,10 @@
 #define PSL_NFA_COUNT_WGS 4   // workgroups (16 scan groups each) per frame of a many-frames k_lsd_nfa_count launch: 12288 dense frames, 8 waves per SIMD: 1: 38.2 ms, 2: 37.3, 3: 36.9,
                               // 4: 36.7; at 4 waves per SIMD 4: 38.1, 8: 39.9 (the default until round 3), 16: 45.2, 32: 59.1 (profiles/r03z_ab_nfa_grid.log)
 #endif
-#ifndef PSL_GROW_LDS_USED
-#define PSL_GROW_LDS_USED 1                  // launches with helper waves keep the `used` bits in LDS (0: in memory, as the many-frames launches do; A/B)
-#endif
-#define PSL_GROW_LDS_USED_MAX (144u * 1024u)   // of the CU's 160 KB (the kernel's own arrays take 4 KB): scaled images up to ~1.18 M pixels
+// Launches with helper waves keep the `used` bits of their frames in LDS when those fit in this many bytes of the CU's 160 KB (the
+// kernel's own arrays take 4 KB): scaled images up to ~1.18 M pixels.  Larger frames keep them in the `used` map in memory, as the
+// many-frames launches do.
+#define PSL_GROW_LDS_USED_MAX (144u * 1024u)
 #ifndef PSL_GROW_HELPER_FRAMES
 #define PSL_GROW_HELPER_FRAMES 64   // launches of at most this many frames run k_lsd_grow4 with helper waves (measured: tools/helper_sweep.sh)
 #endif
@@ -278,7 +278,7 @@ struct pslfe_line {
             PSL_HIP(hipMemsetAsync(d_used, 0, (size_t)P.W * P.H * F, st));  // the `used` map: 1 byte per scaled pixel
             P.singles = F <= PSL_GROW_HELPER_FRAMES;
             P.full_grad = nframes == 1;  // pslfe_line_debug_gradient reads the whole magnitude image of a single-frame call
-            const bool ordered = PSL_FRAME_ORDER && F > PSL_GROW_HELPER_FRAMES;   // many-frames launches: k_lsd_grow4 takes the heaviest frames first
+            const bool ordered = F > PSL_GROW_HELPER_FRAMES;   // many-frames launches: k_lsd_grow4 takes the heaviest frames first
             if (ordered) PSL_HIP(hipMemsetAsync(d_weight, 0, (size_t)F * sizeof(int), st));
             const unsigned tx = (P.W + 63) / 64, ty = (P.H + 15) / 16, gy = (P.H + PSL_GRAD_TH - 1) / PSL_GRAD_TH;
             const size_t npx = (size_t)P.W * P.H;
@@ -307,7 +307,7 @@ struct pslfe_line {
             // LSD_REFINE_ADV: the kernel leaves rectangles (d_rects / d_nrect) for the NFA validation below
             if (F <= PSL_GROW_HELPER_FRAMES) {  // few workgroups per XCD: three more waves each keep that XCD's L2 warm in front of the chain (line_kernels.h)
                 const size_t ubytes = (((size_t)P.W * P.H + 31) >> 5) * 4;   // the `used` bits of the frame in LDS (24 KB at 640x480, 96 KB at 1280x960)
-                if (PSL_GROW_LDS_USED && ubytes <= PSL_GROW_LDS_USED_MAX) {
+                if (ubytes <= PSL_GROW_LDS_USED_MAX) {
                     PSL_HIP(psl_grow_lds_allow(ctx->device, ubytes));   // more than the default 64 KB of dynamic LDS needs the attribute
                     k_lsd_grow4<3, 1><<<F, 256, ubytes, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F, nullptr);
                 } else {
@@ -315,7 +315,7 @@ struct pslfe_line {
                 }
             } else
                 k_lsd_grow4<0, 0><<<F, 64, 0, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F,
-                                                 PSL_FRAME_ORDER ? d_order : nullptr);
+                                                 d_order);
             PSL_STAGE_END(ctx, "line.lsd_grow");
             PSL_HIP(hipGetLastError());   // a refused grow launch (e.g. its dynamic LDS) must not hide behind the NFA launches
         }

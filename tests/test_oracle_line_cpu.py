@@ -154,7 +154,7 @@ def test_restated_atanf_atan2f_equal_libm(tmp_path):
 
 def test_cross_dot_test_of_the_window_rounds_never_contradicts_the_reference_decision():
     """k_lsd_grow4 decides a neighbour from the running sum S and the pixel's unit vector u: |S x u| < tan(prec - m) max(S.u, 0) => joins,
-    |S x u| >= tan(prec + m) max(S.u, 0) => does not (m = 2e-3 rad, line_kernels.h lsdg_fast_setup / lsdg_decide); everything in between
+    |S x u| >= tan(prec + m) max(S.u, 0) => does not (m = 2e-3 rad, line_kernels.h lsdg_fast_setup / lsdg_pops2); everything in between
     takes the reference's arithmetic.  Here the rule is evaluated in float32 on vectors of every direction, of the magnitudes a region's
     sum can have, with the pixel angle placed around the threshold, for the detector's tolerance and for refinement tolerances, and
     compared with the reference's decision fold(|fastAtan2(S) - a|) <= prec: a sure answer must never differ from it."""
