@@ -32,6 +32,7 @@ extern "C" {
 #define PSLFE_E_STATE (-5)     /* call order (e.g. fetch before extract)                      */
 
 #define PSLFE_MAX_LEVELS 16
+#define PSLFE_FAN_CAP 4096   /* fans rows per frame of the line pairing (pslfe_line_fans_device's fan_stride) */
 
 /* == cv::KeyPoint as filled by ORBextractor (src/ORBextractor.cc:837-847, 1095-1103). */
 typedef struct PslKeyPoint {

@@ -13,7 +13,7 @@
 
 #define PSL_MERGE_NMAX 4096    // most segments MergeLines handles per frame
 #define PSL_MERGE_CLMAX 65536  // capacity of the concatenated (sub-)cluster lists
-#define PSL_FAN_CAP 4096       // rows of the fans matrix before de-duplication, per frame
+#define PSL_FAN_CAP PSLFE_FAN_CAP  // rows of the fans matrix before de-duplication, per frame
 
 struct MergeScratch {  // base pointers; frame f uses base + f * (per-frame size)
     float* lines0;     // [NMAX][4]

@@ -223,6 +223,7 @@ struct pslfe_frame {
     int* d_fidx = nullptr;       // [cap] the frame's FeatureVector (SearchByBoW, host-pointer entry point)
     float* d_depth = nullptr;    // [max_frames][cap] mvDepth (RGB-D post-processing)
     float* d_bounds = nullptr;   // [4] scratch for k_image_bounds
+    PslDeviceBuffers mem;        // owns every device buffer above
     std::vector<char> slot_set;
     std::vector<char> slot_depth;  // the slot's mvDepth was set (pslfe_frame_set_rgbd / _set_from_orb_rgbd)
 };

@@ -118,15 +118,6 @@ __global__ void k_associate_planes(const float* __restrict__ planes, const doubl
     *nmatches = nm;
 }
 
-namespace {
-struct DevBuf {  // the host-pointer entry points' device buffers: carved from the context's scratch arena (no hipMalloc / hipFree per call)
-    pslfe_ctx* ctx;
-    explicit DevBuf(pslfe_ctx* c) : ctx(c) {}
-    template <typename T>
-    T* up(const T* host, size_t count, hipStream_t st, hipError_t* e) { return psl_scratch_up(ctx, host, count, st, e); }
-};
-}  // namespace
-
 extern "C" {
 
 int pslfe_line_search_by_geom_appearance(pslfe_ctx* ctx, const PslKeyLine* kl_last, const uint8_t* desc_last, int n1, const PslKeyLine* kl_cur,
@@ -141,18 +132,17 @@ int pslfe_line_search_by_geom_appearance(pslfe_ctx* ctx, const PslKeyLine* kl_la
     PSL_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     { const int rc_ = psl_scratch_begin(ctx); if (rc_) return rc_; }
-    DevBuf B(ctx);
     hipError_t e = hipSuccess;
-    PslKeyLine* dl = B.up(kl_last, n1, st, &e);
-    PslKeyLine* dc = B.up(kl_cur, n2, st, &e);
-    uint8_t* dd1 = B.up(desc_last, (size_t)n1 * 32, st, &e);
-    uint8_t* dd2 = B.up(desc_cur, (size_t)n2 * 32, st, &e);
-    uint8_t* dh = B.up(has_mapline, n1, st, &e);
-    int* didx = B.up((const int*)nullptr, (size_t)n1 * 2, st, &e);
-    int* ddist = B.up((const int*)nullptr, (size_t)n1 * 2, st, &e);
-    int* dm = B.up((const int*)nullptr, n1, st, &e);
-    int* da = B.up((const int*)nullptr, n2, st, &e);
-    int* dn = B.up((const int*)nullptr, 1, st, &e);
+    PslKeyLine* dl = psl_scratch_up(ctx, kl_last, n1, st, &e);
+    PslKeyLine* dc = psl_scratch_up(ctx, kl_cur, n2, st, &e);
+    uint8_t* dd1 = psl_scratch_up(ctx, desc_last, (size_t)n1 * 32, st, &e);
+    uint8_t* dd2 = psl_scratch_up(ctx, desc_cur, (size_t)n2 * 32, st, &e);
+    uint8_t* dh = psl_scratch_up(ctx, has_mapline, n1, st, &e);
+    int* didx = psl_scratch_up(ctx, (const int*)nullptr, (size_t)n1 * 2, st, &e);
+    int* ddist = psl_scratch_up(ctx, (const int*)nullptr, (size_t)n1 * 2, st, &e);
+    int* dm = psl_scratch_up(ctx, (const int*)nullptr, n1, st, &e);
+    int* da = psl_scratch_up(ctx, (const int*)nullptr, n2, st, &e);
+    int* dn = psl_scratch_up(ctx, (const int*)nullptr, 1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_line_search_by_geom_appearance: %s", hipGetErrorString(e));
     int rc = pslfe_hamming_knn2_device(ctx, dd1, n1, dd2, n2, didx, ddist);
     if (rc) return rc;
@@ -176,14 +166,13 @@ int pslfe_line_frame_bf_match(pslfe_ctx* ctx, const uint8_t* desc1, int n1, cons
     PSL_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     { const int rc_ = psl_scratch_begin(ctx); if (rc_) return rc_; }
-    DevBuf B(ctx);
     hipError_t e = hipSuccess;
-    uint8_t* dd1 = B.up(desc1, (size_t)n1 * 32, st, &e);
-    uint8_t* dd2 = B.up(desc2, (size_t)n2 * 32, st, &e);
-    int* didx = B.up((const int*)nullptr, (size_t)n1 * 2, st, &e);
-    int* ddist = B.up((const int*)nullptr, (size_t)n1 * 2, st, &e);
-    float* ds = B.up((const float*)nullptr, (size_t)n1 * 2, st, &e);
-    int* dm = B.up((const int*)nullptr, n1, st, &e);
+    uint8_t* dd1 = psl_scratch_up(ctx, desc1, (size_t)n1 * 32, st, &e);
+    uint8_t* dd2 = psl_scratch_up(ctx, desc2, (size_t)n2 * 32, st, &e);
+    int* didx = psl_scratch_up(ctx, (const int*)nullptr, (size_t)n1 * 2, st, &e);
+    int* ddist = psl_scratch_up(ctx, (const int*)nullptr, (size_t)n1 * 2, st, &e);
+    float* ds = psl_scratch_up(ctx, (const float*)nullptr, (size_t)n1 * 2, st, &e);
+    int* dm = psl_scratch_up(ctx, (const int*)nullptr, n1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_line_frame_bf_match: %s", hipGetErrorString(e));
     int rc = pslfe_hamming_knn2_device(ctx, dd1, n1, dd2, n2, didx, ddist);
     if (rc) return rc;
@@ -204,14 +193,13 @@ int pslfe_associate_planes(pslfe_ctx* ctx, const float* planes, const double* po
     PSL_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     { const int rc_ = psl_scratch_begin(ctx); if (rc_) return rc_; }
-    DevBuf B(ctx);
     hipError_t e = hipSuccess;
-    float* dp = B.up(planes, (size_t)nplanes * 4, st, &e);
-    double* dq = B.up(points, (size_t)nplanes * 15, st, &e);
-    float* dw = B.up(map_planes, (size_t)nmap * 4, st, &e);
-    uint8_t* db = map_bad ? B.up(map_bad, nmap, st, &e) : nullptr;
-    int* da = B.up((const int*)nullptr, nplanes, st, &e);
-    int* dn = B.up((const int*)nullptr, 1, st, &e);
+    float* dp = psl_scratch_up(ctx, planes, (size_t)nplanes * 4, st, &e);
+    double* dq = psl_scratch_up(ctx, points, (size_t)nplanes * 15, st, &e);
+    float* dw = psl_scratch_up(ctx, map_planes, (size_t)nmap * 4, st, &e);
+    uint8_t* db = map_bad ? psl_scratch_up(ctx, map_bad, nmap, st, &e) : nullptr;
+    int* da = psl_scratch_up(ctx, (const int*)nullptr, nplanes, st, &e);
+    int* dn = psl_scratch_up(ctx, (const int*)nullptr, 1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_associate_planes: %s", hipGetErrorString(e));
     k_associate_planes<<<1, 64, 0, st>>>(dp, dq, nplanes, dw, db, nmap, dTh, aTh, live, da, dn);
     PSL_HIP(hipGetLastError());

@@ -174,17 +174,16 @@ __global__ __launch_bounds__(256) void k_bow_vectors(const int32_t* __restrict__
 struct pslfe_vocab {
     pslfe_ctx* ctx = nullptr;
     VocabDev V = {};
-    void* bufs[6] = {};
+    PslDeviceBuffers mem;   // owns the tree arrays of V
 };
 
 extern "C" {
 
 void pslfe_vocab_destroy(pslfe_vocab* v) {
     if (!v) return;
-    hipSetDevice(v->ctx->device);
-    hipStreamSynchronize(v->ctx->stream);
-    for (void* b : v->bufs) hipFree(b);
-    delete v;
+    (void)hipSetDevice(v->ctx->device);
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;   // its buffers go with it
 }
 
 int pslfe_vocab_create(pslfe_ctx* ctx, int nnodes, const int32_t* child_begin, const int32_t* child_count, const int32_t* child_ids, int nchild,
@@ -218,20 +217,23 @@ int pslfe_vocab_create(pslfe_ctx* ctx, int nnodes, const int32_t* child_begin, c
     PSL_HIP(hipSetDevice(ctx->device));
     pslfe_vocab* v = new pslfe_vocab();
     v->ctx = ctx;
-    const size_t sizes[6] = {(size_t)nnodes * 4, (size_t)nnodes * 4, (size_t)nchild * 4, (size_t)nnodes * 32, (size_t)nnodes * 8, (size_t)nnodes * 4};
-    const void* srcs[6] = {child_begin, child_count, child_ids, node_desc, node_weight, node_word};
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 6 && e == hipSuccess; ++k) {
-        e = hipMalloc(&v->bufs[k], sizes[k]);
-        if (e == hipSuccess) e = hipMemcpy(v->bufs[k], srcs[k], sizes[k], hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        pslfe_set_error("pslfe_vocab_create: %s", hipGetErrorString(e));
+    auto up = [&](auto*& slot, const void* src, size_t count, const char* what) {   // one tree array: allocated, then copied
+        v->mem.alloc(slot, count, what);
+        if (slot && e == hipSuccess) e = hipMemcpy((void*)slot, src, count * sizeof(*slot), hipMemcpyHostToDevice);
+    };
+    up(v->V.child_begin, child_begin, nnodes, "child_begin");
+    up(v->V.child_count, child_count, nnodes, "child_count");
+    up(v->V.child_ids, child_ids, nchild, "child_ids");
+    up(v->V.node_desc, node_desc, (size_t)nnodes * 8, "node_desc");
+    up(v->V.node_weight, node_weight, nnodes, "node_weight");
+    up(v->V.node_word, node_word, nnodes, "node_word");
+    int rc = v->mem.check("pslfe_vocab_create");
+    if (!rc && e != hipSuccess) { pslfe_set_error("pslfe_vocab_create: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
+    if (rc) {
         pslfe_vocab_destroy(v);
-        return PSLFE_E_HIP;
+        return rc;
     }
-    v->V.child_begin = (const int32_t*)v->bufs[0]; v->V.child_count = (const int32_t*)v->bufs[1]; v->V.child_ids = (const int32_t*)v->bufs[2];
-    v->V.node_desc = (const uint32_t*)v->bufs[3]; v->V.node_weight = (const double*)v->bufs[4]; v->V.node_word = (const int32_t*)v->bufs[5];
     v->V.nnodes = nnodes; v->V.L = L;
     *out = v;
     return PSLFE_OK;
@@ -272,7 +274,7 @@ int pslfe_compute_bow(pslfe_vocab* v, const uint8_t* desc, int n, int levelsup, 
     // one allocation: desc | fword | fnid | bow_id | bow_start | fv_node | fv_start | fv_idx | counters | fweight | bow_val
     const size_t N = (size_t)n, i4 = 4, need = N * 32 + (N * 5 + 2 * (N + 1) + 4) * i4 + 16 + N * 16;
     { const int rc_ = psl_scratch_begin(v->ctx); if (rc_) return rc_; }
-    uint8_t* base = static_cast<uint8_t*>(psl_scratch(v->ctx, need));   // the context's scratch arena (no hipMalloc / hipFree per call)
+    uint8_t* base = static_cast<uint8_t*>(psl_scratch(v->ctx, need));   // the context's scratch arena
     PSL_REQUIRE(base, PSLFE_E_HIP, "pslfe_compute_bow: out of device memory");
     uint8_t* p = base;
     uint8_t* d_desc = p; p += N * 32;
@@ -309,8 +311,7 @@ int pslfe_compute_bow(pslfe_vocab* v, const uint8_t* desc, int n, int levelsup, 
         D(fv_idx, d_fv_idx, (size_t)kept * 4);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { pslfe_set_error("pslfe_compute_bow: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    hipStreamSynchronize(st);
+    if (e != hipSuccess) { pslfe_set_error("pslfe_compute_bow: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; (void)hipStreamSynchronize(st); }
     *nbow = cnt[0]; *nfv = cnt[1];
     return rc;
 }

@@ -35,8 +35,8 @@ int pslfe_ctx::resolve_pending() {
         StageTimer& t = stages[p.stage];
         t.ms += ms;
         t.launches += 1;
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
+        PSL_HIP(hipEventDestroy(p.a));
+        PSL_HIP(hipEventDestroy(p.b));
     }
     pending.clear();
     return PSLFE_OK;
@@ -44,7 +44,10 @@ int pslfe_ctx::resolve_pending() {
 
 char* psl_host_stage(pslfe_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->hstage_cap) return ctx->hstage;
-    if (ctx->hstage) { hipHostFree(ctx->hstage); ctx->hstage = nullptr; ctx->hstage_cap = 0; }
+    if (ctx->hstage) {
+        if (hipHostFree(ctx->hstage) != hipSuccess) return nullptr;
+        ctx->hstage = nullptr; ctx->hstage_cap = 0;
+    }
     const size_t want = psl_align_up(bytes + bytes / 2, (size_t)1 << 16);
     void* q = nullptr;
     if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) return nullptr;
@@ -55,13 +58,15 @@ char* psl_host_stage(pslfe_ctx* ctx, size_t bytes) {
 int psl_scratch_begin(pslfe_ctx* ctx) {
     if (!ctx->arena_extra.empty()) {   // the previous call outgrew the arena: its fall-back blocks go, and the arena grows
         PSL_HIP(hipStreamSynchronize(ctx->stream));
-        for (void* q : ctx->arena_extra) hipFree(q);
-        ctx->arena_extra.clear();
+        std::vector<void*> extra;
+        extra.swap(ctx->arena_extra);
+        for (void* q : extra) PSL_HIP(hipFree(q));
     }
     if (ctx->arena_want > ctx->arena_cap) {
         PSL_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->arena) hipFree(ctx->arena);
+        char* old = ctx->arena;
         ctx->arena = nullptr; ctx->arena_cap = 0;
+        if (old) PSL_HIP(hipFree(old));
         const size_t want = psl_align_up(ctx->arena_want + ctx->arena_want / 2, 1 << 20);
         PSL_HIP(hipMalloc((void**)&ctx->arena, want));
         ctx->arena_cap = want;
@@ -135,17 +140,17 @@ int pslfe_ctx_create(int device, pslfe_ctx** out) {
 
 void pslfe_ctx_destroy(pslfe_ctx* ctx) {
     if (!ctx) return;
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    for (void* q : ctx->arena_extra) hipFree(q);
-    if (ctx->arena) hipFree(ctx->arena);
-    if (ctx->hstage) hipHostFree(ctx->hstage);
-    if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
-    ctx->resolve_pending();
-    if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    if (ctx->aux_stream) hipStreamDestroy(ctx->aux_stream);
-    if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void* q : ctx->arena_extra) (void)hipFree(q);
+    if (ctx->arena) (void)hipFree(ctx->arena);
+    if (ctx->hstage) (void)hipHostFree(ctx->hstage);
+    if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
+    (void)ctx->resolve_pending();
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
+    if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
+    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
 

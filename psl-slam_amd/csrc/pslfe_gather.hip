@@ -218,13 +218,13 @@ int pslfe_gather_create(pslfe_ctx* ctx, int rank, int world, const uint8_t id[12
 
 void pslfe_gather_destroy(pslfe_gather* g) {
     if (!g) return;
-    hipSetDevice(g->ctx->device);
-    if (g->stream) hipStreamSynchronize(g->stream);
+    (void)hipSetDevice(g->ctx->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
     Rccl* R = rccl();
     if (R && g->comm) R->destroy(g->comm);
-    if (g->ev_ready) hipEventDestroy(g->ev_ready);
-    if (g->ev_done) hipEventDestroy(g->ev_done);
-    if (g->stream) hipStreamDestroy(g->stream);
+    if (g->ev_ready) (void)hipEventDestroy(g->ev_ready);
+    if (g->ev_done) (void)hipEventDestroy(g->ev_done);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
 

@@ -697,6 +697,7 @@ struct pslfe_glue {
     float* d_fans = nullptr;
     float* d_depth = nullptr;
     size_t depth_cap = 0;
+    PslDeviceBuffers mem;   // owns every device buffer above
 };
 
 static int glue_run(pslfe_glue* g, int nframes, const PslKeyLine* d_kls, int kl_stride, const int32_t* d_nkl, int nkl_single,
@@ -725,12 +726,9 @@ extern "C" {
 
 void pslfe_glue_destroy(pslfe_glue* g) {
     if (!g) return;
-    hipSetDevice(g->ctx->device);
-    hipStreamSynchronize(g->ctx->stream);
-    hipFree(g->d_lines3d); hipFree(g->d_lineEq); hipFree(g->d_pair); hipFree(g->d_xy); hipFree(g->d_cross); hipFree(g->d_le_l);
-    hipFree(g->d_nint); hipFree(g->d_planes); hipFree(g->d_normals); hipFree(g->d_lineNo); hipFree(g->d_cross3d); hipFree(g->d_cross2d);
-    hipFree(g->d_nplanes); hipFree(g->d_kls); hipFree(g->d_fans); hipFree(g->d_depth);
-    delete g;
+    (void)hipSetDevice(g->ctx->device);
+    (void)hipStreamSynchronize(g->ctx->stream);
+    delete g;   // its buffers go with it
 }
 
 int pslfe_glue_create(pslfe_ctx* ctx, int max_lines, int max_fans, int max_batch, pslfe_glue** out) {
@@ -743,27 +741,25 @@ int pslfe_glue_create(pslfe_ctx* ctx, int max_lines, int max_fans, int max_batch
     g->ctx = ctx; g->max_lines = max_lines; g->max_fans = max_fans; g->max_batch = max_batch;
     g->int_cap = max_fans; g->plane_cap = max_fans;
     const size_t F = (size_t)max_batch, L = (size_t)max_lines, I = (size_t)g->int_cap, Pn = (size_t)g->plane_cap;
-    hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 1); };
-    A((void**)&g->d_lines3d, F * L * 6 * sizeof(double));
-    A((void**)&g->d_lineEq, F * L * 3 * sizeof(float));
-    A((void**)&g->d_pair, F * I * 2 * sizeof(int32_t));
-    A((void**)&g->d_xy, F * I * 2 * sizeof(float));
-    A((void**)&g->d_cross, F * I * 3 * sizeof(double));
-    A((void**)&g->d_le_l, F * I * 6 * sizeof(double));
-    A((void**)&g->d_nint, F * sizeof(int32_t));
-    A((void**)&g->d_planes, F * Pn * 4 * sizeof(float));
-    A((void**)&g->d_normals, F * Pn * 3 * sizeof(double));
-    A((void**)&g->d_lineNo, F * Pn * 2 * sizeof(int32_t));
-    A((void**)&g->d_cross3d, F * Pn * 3 * sizeof(double));
-    A((void**)&g->d_cross2d, F * Pn * 2 * sizeof(double));
-    A((void**)&g->d_nplanes, F * sizeof(int32_t));
-    A((void**)&g->d_kls, L * sizeof(PslKeyLine));
-    A((void**)&g->d_fans, (size_t)max_fans * 4 * sizeof(float));
-    if (e != hipSuccess) {
-        pslfe_set_error("pslfe_glue_create: hipMalloc failed: %s", hipGetErrorString(e));
+    PslDeviceBuffers& m = g->mem;
+    m.alloc(g->d_lines3d, F * L * 6, "d_lines3d");
+    m.alloc(g->d_lineEq, F * L * 3, "d_lineEq");
+    m.alloc(g->d_pair, F * I * 2, "d_pair");
+    m.alloc(g->d_xy, F * I * 2, "d_xy");
+    m.alloc(g->d_cross, F * I * 3, "d_cross");
+    m.alloc(g->d_le_l, F * I * 6, "d_le_l");
+    m.alloc(g->d_nint, F, "d_nint");
+    m.alloc(g->d_planes, F * Pn * 4, "d_planes");
+    m.alloc(g->d_normals, F * Pn * 3, "d_normals");
+    m.alloc(g->d_lineNo, F * Pn * 2, "d_lineNo");
+    m.alloc(g->d_cross3d, F * Pn * 3, "d_cross3d");
+    m.alloc(g->d_cross2d, F * Pn * 2, "d_cross2d");
+    m.alloc(g->d_nplanes, F, "d_nplanes");
+    m.alloc(g->d_kls, L, "d_kls");
+    m.alloc(g->d_fans, (size_t)max_fans * 4, "d_fans");
+    if (int rc = m.check("pslfe_glue_create")) {
         pslfe_glue_destroy(g);
-        return PSLFE_E_HIP;
+        return rc;
     }
     *out = g;
     return PSLFE_OK;
@@ -783,8 +779,9 @@ int pslfe_glue_run(pslfe_glue* g, const PslKeyLine* kls, int nlines, const float
     const size_t need = (size_t)height * depth_stride;
     if (need > g->depth_cap) {
         PSL_HIP(hipStreamSynchronize(st));
-        hipFree(g->d_depth); g->d_depth = nullptr; g->depth_cap = 0;
-        PSL_HIP(hipMalloc((void**)&g->d_depth, need * sizeof(float)));
+        g->mem.release(g->d_depth); g->depth_cap = 0;
+        g->mem.alloc(g->d_depth, need, "d_depth");
+        if (int rc = g->mem.check("pslfe_glue_run")) return rc;
         g->depth_cap = need;
     }
     PSL_HIP(hipMemcpyAsync(g->d_depth, depth, need * sizeof(float), hipMemcpyHostToDevice, st));

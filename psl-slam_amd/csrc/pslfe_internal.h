@@ -96,6 +96,53 @@ struct pslfe_ctx {
 
 static inline size_t psl_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The device buffers of one object (extractor, frame store, glue, vocabulary): one hipMalloc per buffer, each recorded with the member
+// pointer that holds it.  The members stay plain pointers (kernels and MergeScratch take them by value); release() frees every buffer
+// and sets every recorded member back to nullptr, and the destructor calls it.  After a failed allocation nothing more is allocated
+// until check() has reported it.
+class PslDeviceBuffers {
+public:
+    PslDeviceBuffers() = default;
+    PslDeviceBuffers(const PslDeviceBuffers&) = delete;
+    PslDeviceBuffers& operator=(const PslDeviceBuffers&) = delete;
+    ~PslDeviceBuffers() { release(); }
+
+    // `count` elements (at least one byte) into `slot`; a failure is kept, named by `what`, for check()
+    template <class T>
+    void alloc(T*& slot, size_t count, const char* what) {
+        if (err_ != hipSuccess) return;
+        void* p = nullptr;
+        err_ = hipMalloc(&p, count ? count * sizeof(T) : 1);
+        if (err_ != hipSuccess) { failed_ = what; return; }
+        slot = static_cast<T*>(p);
+        slots_.push_back((void**)&slot);
+    }
+    // frees the buffer held by `slot` alone (a buffer that grows)
+    template <class T>
+    void release(T*& slot) {
+        for (size_t i = 0; i < slots_.size(); ++i)
+            if (slots_[i] == (void**)&slot) { (void)hipFree((void*)slot); slot = nullptr; slots_.erase(slots_.begin() + i); return; }
+    }
+    // frees every buffer (the caller has synchronised the streams that use them)
+    void release() {
+        for (void** s : slots_) { (void)hipFree(*s); *s = nullptr; }
+        slots_.clear();
+    }
+    // PSLFE_OK, or: the failed allocation named in pslfe_last_error(), the failure cleared here and in HIP's last error, PSLFE_E_HIP
+    int check(const char* who) {
+        if (err_ == hipSuccess) return PSLFE_OK;
+        pslfe_set_error("%s: allocating %s failed: %s", who, failed_, hipGetErrorString(err_));
+        err_ = hipSuccess; failed_ = nullptr;
+        (void)hipGetLastError();   // a failed hipMalloc must not surface in a later hipGetLastError()
+        return PSLFE_E_HIP;
+    }
+
+private:
+    std::vector<void**> slots_;
+    hipError_t err_ = hipSuccess;
+    const char* failed_ = nullptr;
+};
+
 // at least `bytes` of pinned host memory owned by the context (valid until the next call that asks for more); nullptr on failure
 char* psl_host_stage(pslfe_ctx* ctx, size_t bytes);
 // start of a call: releases the previous call's fall-back blocks and grows the arena to what that call wanted (calls on a context are serialised)

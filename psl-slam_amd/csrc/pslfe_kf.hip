@@ -325,34 +325,11 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-struct pslfe_kf {
+struct pslfe_kf {   // the per-call buffers come from the context's scratch arena
     pslfe_ctx* ctx = nullptr;
-    char* arena = nullptr;
-    size_t arena_cap = 0, arena_top = 0;
-
-    int reserve(size_t bytes) {
-        arena_top = 0;
-        if (bytes <= arena_cap) return PSLFE_OK;
-        PSL_HIP(hipStreamSynchronize(ctx->stream));
-        if (arena) PSL_HIP(hipFree(arena));
-        arena = nullptr;
-        arena_cap = 0;
-        const size_t want = psl_align_up(bytes + bytes / 2, 1 << 16);
-        PSL_HIP(hipMalloc(&arena, want));
-        arena_cap = want;
-        return PSLFE_OK;
-    }
-    template <typename T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(arena + arena_top);
-        arena_top += psl_align_up(count * sizeof(T) + 1, 256);
-        return p;
-    }
 };
 
 namespace {
-size_t padded(size_t bytes) { return psl_align_up(bytes + 1, 256); }
-
 int check_slot(pslfe_frame* f, int slot, const char* who) {
     PSL_REQUIRE(f, PSLFE_E_INVALID, "%s: NULL frame", who);
     PSL_REQUIRE(slot >= 0 && slot < f->max_frames && f->slot_set[slot], PSLFE_E_STATE, "%s: slot %d not set", who, slot);
@@ -382,12 +359,6 @@ int pslfe_kf_create(pslfe_ctx* ctx, pslfe_kf** out) {
 }
 
 void pslfe_kf_destroy(pslfe_kf* k) {
-    if (!k) return;
-    if (k->arena) {
-        (void)hipSetDevice(k->ctx->device);
-        (void)hipStreamSynchronize(k->ctx->stream);
-        (void)hipFree(k->arena);
-    }
     delete k;
 }
 
@@ -401,13 +372,13 @@ int pslfe_kf_window_best(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQue
     if (nq == 0) return PSLFE_OK;
     PSL_HIP(hipSetDevice(k->ctx->device));
     hipStream_t st = k->ctx->stream;
-    if (int rc = k->reserve(padded((size_t)nq * sizeof(PslProjQuery)) + padded((size_t)nq * 32) + 2 * padded((size_t)nq * 4))) return rc;
-    PslProjQuery* d_q = k->take<PslProjQuery>(nq);
-    uint8_t* d_qd = k->take<uint8_t>((size_t)nq * 32);
-    int* d_i = k->take<int>(nq);
-    int* d_d = k->take<int>(nq);
-    PSL_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * sizeof(PslProjQuery), hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_qd, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, st));
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
+    PslProjQuery* d_q = psl_scratch_up(k->ctx, queries, nq, st, &e);
+    uint8_t* d_qd = psl_scratch_up(k->ctx, qdesc, (size_t)nq * 32, st, &e);
+    int* d_i = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    int* d_d = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_window_best: %s", hipGetErrorString(e));
     {
         PSL_STAGE_BEGIN(k->ctx, "kf.window_best");
         if (int rc = launch_window_best(k, f, slot, d_q, d_qd, nq, chi2, inv_level_sigma2, nlevels, d_i, d_d)) return rc;
@@ -432,25 +403,19 @@ int pslfe_kf_search_by_sim3(pslfe_kf* k, pslfe_frame* f1, int slot1, pslfe_frame
     PSL_HIP(hipSetDevice(k->ctx->device));
     hipStream_t st = k->ctx->stream;
     const size_t m1 = (size_t)n1, m2 = (size_t)(n2 > 0 ? n2 : 1);
-    if (int rc = k->reserve(padded(m1 * sizeof(PslProjQuery)) + padded(m1 * 32) + padded(m2 * sizeof(PslProjQuery)) + padded(m2 * 32) +
-                            3 * padded(m1 * 4) + 2 * padded(m2 * 4) + padded(4)))
-        return rc;
-    PslProjQuery* d_q1 = k->take<PslProjQuery>(m1);
-    uint8_t* d_qd1 = k->take<uint8_t>(m1 * 32);
-    PslProjQuery* d_q2 = k->take<PslProjQuery>(m2);
-    uint8_t* d_qd2 = k->take<uint8_t>(m2 * 32);
-    int* d_b1 = k->take<int>(m1);
-    int* d_d1 = k->take<int>(m1);
-    int* d_m = k->take<int>(m1);
-    int* d_b2 = k->take<int>(m2);
-    int* d_d2 = k->take<int>(m2);
-    int* d_nf = k->take<int>(1);
-    PSL_HIP(hipMemcpyAsync(d_q1, q12, m1 * sizeof(PslProjQuery), hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_qd1, qdesc1, m1 * 32, hipMemcpyHostToDevice, st));
-    if (n2 > 0) {
-        PSL_HIP(hipMemcpyAsync(d_q2, q21, m2 * sizeof(PslProjQuery), hipMemcpyHostToDevice, st));
-        PSL_HIP(hipMemcpyAsync(d_qd2, qdesc2, m2 * 32, hipMemcpyHostToDevice, st));
-    }
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
+    PslProjQuery* d_q1 = psl_scratch_up(k->ctx, q12, m1, st, &e);
+    uint8_t* d_qd1 = psl_scratch_up(k->ctx, qdesc1, m1 * 32, st, &e);
+    PslProjQuery* d_q2 = psl_scratch_up(k->ctx, n2 > 0 ? q21 : nullptr, m2, st, &e);
+    uint8_t* d_qd2 = psl_scratch_up(k->ctx, n2 > 0 ? qdesc2 : nullptr, m2 * 32, st, &e);
+    int* d_b1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_d1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_m = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_b2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
+    int* d_d2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
+    int* d_nf = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_search_by_sim3: %s", hipGetErrorString(e));
     PSL_HIP(hipMemsetAsync(d_nf, 0, 4, st));
     {
         PSL_STAGE_BEGIN(k->ctx, "kf.sim3");
@@ -487,20 +452,17 @@ int pslfe_kf_search_for_triangulation(pslfe_kf* k, pslfe_frame* f2, int slot2, c
     PSL_HIP(hipMemcpyAsync(&m, f2->S.meta + slot2, sizeof(m), hipMemcpyDeviceToHost, st));
     PSL_HIP(hipStreamSynchronize(st));
     const size_t nf = (size_t)(nfidx2 > 0 ? nfidx2 : 1), nk = (size_t)(m.n > 0 ? m.n : 1);
-    if (int rc = k->reserve(padded((size_t)nq * sizeof(PslTriQuery)) + padded((size_t)nq * 32) + padded(nf * 4) + padded(nk) +
-                            2 * padded((size_t)nq * 4) + padded(4)))
-        return rc;
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
     TriArgs A;
-    PslTriQuery* d_q = k->take<PslTriQuery>(nq);
-    uint8_t* d_qd = k->take<uint8_t>((size_t)nq * 32);
-    int* d_fidx = k->take<int>(nf);
-    uint8_t* d_taken = k->take<uint8_t>(nk);
-    A.choice = k->take<int>(nq);
-    A.match = k->take<int>(nq);
-    A.nmatches = k->take<int>(1);
-    PSL_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * sizeof(PslTriQuery), hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_qd, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, st));
-    if (nfidx2 > 0) PSL_HIP(hipMemcpyAsync(d_fidx, fidx2, (size_t)nfidx2 * 4, hipMemcpyHostToDevice, st));
+    PslTriQuery* d_q = psl_scratch_up(k->ctx, queries, nq, st, &e);
+    uint8_t* d_qd = psl_scratch_up(k->ctx, qdesc, (size_t)nq * 32, st, &e);
+    int* d_fidx = psl_scratch_up(k->ctx, nfidx2 > 0 ? fidx2 : nullptr, nf, st, &e);
+    uint8_t* d_taken = psl_scratch_up(k->ctx, (const uint8_t*)nullptr, nk, st, &e);
+    A.choice = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    A.match = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    A.nmatches = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_search_for_triangulation: %s", hipGetErrorString(e));
     if (m.n > 0 && taken2) PSL_HIP(hipMemcpyAsync(d_taken, taken2, (size_t)m.n, hipMemcpyHostToDevice, st));
     else PSL_HIP(hipMemsetAsync(d_taken, 0, nk, st));
     A.S = f2->S; A.slot = slot2; A.fidx = d_fidx; A.nfidx = nfidx2; A.taken = d_taken; A.q = d_q; A.qdesc = d_qd; A.nq = nq;
@@ -529,19 +491,15 @@ int pslfe_kf_line_fuse_best(pslfe_kf* k, const PslKeyLine* kls, int n, const uin
     PSL_HIP(hipSetDevice(k->ctx->device));
     hipStream_t st = k->ctx->stream;
     const size_t nn = (size_t)(n > 0 ? n : 1), nd = (size_t)(ndesc > 0 ? ndesc : 1);
-    if (int rc = k->reserve(padded(nn * sizeof(PslKeyLine)) + padded(nd * 32) + padded((size_t)nq * sizeof(PslLineFuseQuery)) +
-                            padded((size_t)nq * 32) + 2 * padded((size_t)nq * 4)))
-        return rc;
-    PslKeyLine* d_kl = k->take<PslKeyLine>(nn);
-    uint8_t* d_desc = k->take<uint8_t>(nd * 32);
-    PslLineFuseQuery* d_q = k->take<PslLineFuseQuery>(nq);
-    uint8_t* d_qd = k->take<uint8_t>((size_t)nq * 32);
-    int* d_i = k->take<int>(nq);
-    int* d_d = k->take<int>(nq);
-    if (n > 0) PSL_HIP(hipMemcpyAsync(d_kl, kls, (size_t)n * sizeof(PslKeyLine), hipMemcpyHostToDevice, st));
-    if (ndesc > 0) PSL_HIP(hipMemcpyAsync(d_desc, desc, (size_t)ndesc * 32, hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * sizeof(PslLineFuseQuery), hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_qd, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, st));
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
+    PslKeyLine* d_kl = psl_scratch_up(k->ctx, n > 0 ? kls : nullptr, nn, st, &e);
+    uint8_t* d_desc = psl_scratch_up(k->ctx, ndesc > 0 ? desc : nullptr, nd * 32, st, &e);
+    PslLineFuseQuery* d_q = psl_scratch_up(k->ctx, queries, nq, st, &e);
+    uint8_t* d_qd = psl_scratch_up(k->ctx, qdesc, (size_t)nq * 32, st, &e);
+    int* d_i = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    int* d_d = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_line_fuse_best: %s", hipGetErrorString(e));
     {
         PSL_STAGE_BEGIN(k->ctx, "kf.line_fuse");
         k_line_fuse_best<<<(nq + 3) / 4, 256, 0, st>>>(d_kl, n, d_desc, ndesc, d_q, d_qd, nq, d_i, d_d);
@@ -569,12 +527,12 @@ int pslfe_kf_distinctive_descriptors(pslfe_kf* k, const uint8_t* desc, const int
     PSL_REQUIRE(total == 0 || desc, PSLFE_E_INVALID, "pslfe_kf_distinctive_descriptors: NULL descriptors");
     PSL_HIP(hipSetDevice(k->ctx->device));
     hipStream_t st = k->ctx->stream;
-    if (int rc = k->reserve(padded((total ? total : 1) * 32) + padded((size_t)(npts + 1) * 4) + padded((size_t)npts * 4))) return rc;
-    uint8_t* d_desc = k->take<uint8_t>((total ? total : 1) * 32);
-    int* d_off = k->take<int>(npts + 1);
-    int* d_best = k->take<int>(npts);
-    if (total) PSL_HIP(hipMemcpyAsync(d_desc, desc, total * 32, hipMemcpyHostToDevice, st));
-    PSL_HIP(hipMemcpyAsync(d_off, offsets, (size_t)(npts + 1) * 4, hipMemcpyHostToDevice, st));
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
+    uint8_t* d_desc = psl_scratch_up(k->ctx, total ? desc : nullptr, (total ? total : 1) * 32, st, &e);
+    int* d_off = psl_scratch_up(k->ctx, offsets, (size_t)npts + 1, st, &e);
+    int* d_best = psl_scratch_up(k->ctx, (const int*)nullptr, npts, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_distinctive_descriptors: %s", hipGetErrorString(e));
     {
         PSL_STAGE_BEGIN(k->ctx, "kf.distinctive");
         k_distinctive<<<npts, 64, 0, st>>>(d_desc, d_off, npts, d_best);

@@ -92,35 +92,12 @@ struct pslfe_line {
     int* d_nfans = nullptr;
     float* d_tmplines = nullptr;  // [NMAX][4] staging for the host-pointer pairing entry point
 
+    PslDeviceBuffers mem;         // owns every d_* buffer above and those of M
+
     void release() {
-        hipFree(M.lines0); hipFree(M.lines1); hipFree(M.merged); hipFree(M.angles); hipFree(M.length); hipFree(M.order); hipFree(M.pos);
-        hipFree(M.adj); hipFree(M.code); hipFree(M.clist); hipFree(M.coff); hipFree(M.work); hipFree(M.bits); hipFree(M.stage);
-        M = MergeScratch{};
-        hipFree(d_kls); hipFree(d_ldesc); hipFree(d_fdesc); hipFree(d_lineEq); hipFree(d_nkl); hipFree(d_status); hipFree(d_dxy);
-        hipFree(d_rawfans); hipFree(d_fans); hipFree(d_nfans); hipFree(d_tmplines);
-        d_kls = nullptr; d_ldesc = nullptr; d_fdesc = nullptr; d_lineEq = nullptr; d_nkl = nullptr; d_status = nullptr; d_dxy = nullptr;
-        d_rawfans = nullptr; d_fans = nullptr; d_nfans = nullptr; d_tmplines = nullptr;
-        hipFree(d_trig); d_trig = nullptr;
-        hipFree(d_seedt); d_seedt = nullptr;
-        hipFree(d_used); d_used = nullptr;
-        hipFree(d_in); hipFree(d_scaled); hipFree(d_angdeg); hipFree(d_modgrad); hipFree(d_reg);
-        hipFree(d_seg); hipFree(d_nseg); hipFree(d_rects); hipFree(d_nrect); hipFree(d_weight); hipFree(d_order); hipFree(d_segtmp); hipFree(d_keep); hipFree(d_lgamma); hipFree(d_sctab);
-        d_sctab = nullptr; hipFree(d_counts); hipFree(d_vals); hipFree(d_sstate); hipFree(d_slist); hipFree(d_stmp); hipFree(d_lcount);
-        d_counts = nullptr; d_vals = nullptr; d_sstate = nullptr; d_slist = nullptr; d_stmp = nullptr; d_lcount = nullptr;
-        d_lgamma = nullptr;
-        d_in = nullptr; d_scaled = nullptr; d_angdeg = nullptr; d_modgrad = nullptr; d_reg = nullptr;
-        d_seg = nullptr; d_nseg = nullptr; d_rects = nullptr; d_nrect = nullptr; d_weight = nullptr; d_order = nullptr; d_segtmp = nullptr; d_keep = nullptr;
+        mem.release();
         gw = gh = 0;   // no geometry is prepared any more: the next call allocates again (or fails again) instead of
         last_nframes = 0;  // launching on freed memory
-    }
-
-    // allocation failure inside prepare(): leave the object empty, not half-built (the early return `w == gw && h == gh` of the
-    // next call must not see the old geometry with freed or undersized buffers)
-    int fail_prepare(hipError_t e, const char* what) {
-        release();
-        (void)hipGetLastError();
-        pslfe_set_error("line: allocating %s for %d frames failed: %s", what, max_batch, hipGetErrorString(e));
-        return PSLFE_E_HIP;
     }
 
     int prepare(int w, int h) {
@@ -175,94 +152,85 @@ struct pslfe_line {
         PSL_HIP(hipSetDevice(ctx->device));
         PSL_HIP(hipStreamSynchronize(ctx->stream));
         release();  // also forgets the old geometry: a failure below leaves an empty object, never a half-built one
-#define PSL_ALLOC(ptr, bytes)                                                   \
-    do {                                                                        \
-        const hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));               \
-        if (e_ != hipSuccess) return fail_prepare(e_, #ptr);                    \
-    } while (0)
-        const size_t F = (size_t)max_batch, npx = (size_t)Q.W * Q.H;
-        in_pitch = (int)psl_align_up(w, 16);
-        in_fstride = psl_align_up((size_t)in_pitch * h, 256);
-        PSL_ALLOC(d_in, in_fstride * F);
-        PSL_ALLOC(d_scaled, npx * std::min<size_t>(F, PSL_LSD_SUBBATCH) * sizeof(double));   // one sub-batch of the f64 working image (run_lsd)
-        PSL_ALLOC(d_angdeg, npx * F * sizeof(float));
-        PSL_ALLOC(d_modgrad, npx * F * sizeof(double));
-        PSL_ALLOC(d_trig, npx * F * sizeof(float2));
-        PSL_ALLOC(d_seedt, npx * F * sizeof(float2));
-        PSL_ALLOC(d_used, npx * F);
-        PSL_ALLOC(d_reg, npx * F * sizeof(uint32_t));
-        PSL_ALLOC(d_seg, (size_t)Q.maxseg * 4 * sizeof(float) * F);
-        PSL_ALLOC(d_nseg, F * sizeof(int));
-        PSL_ALLOC(d_rects, (size_t)Q.maxseg * PSL_LSD_RECT_F64 * sizeof(double) * F);
-        PSL_ALLOC(d_nrect, F * sizeof(int));
-        PSL_ALLOC(d_weight, F * sizeof(int));
-        PSL_ALLOC(d_order, F * sizeof(int));
-        PSL_ALLOC(d_segtmp, (size_t)Q.maxseg * 4 * sizeof(float) * F);
-        PSL_ALLOC(d_keep, (size_t)Q.maxseg * F);
-        PSL_ALLOC(d_counts, (size_t)Q.maxseg * 5 * sizeof(int2) * F);
-        PSL_ALLOC(d_vals, (size_t)Q.maxseg * 5 * sizeof(double) * F);
-        PSL_ALLOC(d_sstate, (size_t)Q.maxseg * 5 * sizeof(double2) * F);
-        PSL_ALLOC(d_slist, (size_t)Q.maxseg * 5 * sizeof(LsdnSeries) * F);
-        PSL_ALLOC(d_stmp, (size_t)Q.maxseg * 5 * sizeof(LsdnSeries) * F);
-        PSL_ALLOC(d_lcount, F * (PSL_NFA_NCLS + 1) * sizeof(int));
-        {
-            static const double sctab[444] = {
-#include "psl_sincostab.inc"
-            };
-            PSL_ALLOC(d_sctab, sizeof(sctab));
-            const hipError_t e_ = hipMemcpy(d_sctab, sctab, sizeof(sctab), hipMemcpyHostToDevice);
-            if (e_ != hipSuccess) return fail_prepare(e_, "d_sctab (upload)");
-            Q.sctab = d_sctab;
-        }
-        {   // nfa() tables: the same functions the device would evaluate, here on the host (bit-identical: single IEEE operations)
-            const int lgn = 1 << 16;
-            std::vector<double> lg((size_t)lgn, 0.0);
-            for (int i = 1; i < lgn; ++i) lg[i] = lsdn_log_gamma((double)i);
-            double pj = Q.p;
-            for (int j = 0; j < PSL_NFA_NP; ++j, pj = pj / 2) {
-                lg.push_back(0);  // placeholders, filled below: the three log tables follow the log_gamma table in the same allocation
-            }
-            lg.resize((size_t)lgn + 3 * PSL_NFA_NP + PSL_RATIO_BMAX);
-            for (int i = 1; i < PSL_RATIO_BMAX; ++i) lg[(size_t)lgn + 3 * PSL_NFA_NP + i] = 1.0 / (double)i;   // psl_ratio_inv's table (k_lsd_nfa_series)
-            pj = Q.p;
-            for (int j = 0; j < PSL_NFA_NP; ++j, pj = pj / 2) {
-                lg[(size_t)lgn + j] = psl_log(pj); lg[(size_t)lgn + PSL_NFA_NP + j] = psl_log(1.0 - pj); lg[(size_t)lgn + 2 * PSL_NFA_NP + j] = psl_log10(pj);
-            }
-            PSL_ALLOC(d_lgamma, lg.size() * sizeof(double));
-            const hipError_t e_ = hipMemcpy(d_lgamma, lg.data(), lg.size() * sizeof(double), hipMemcpyHostToDevice);
-            if (e_ != hipSuccess) return fail_prepare(e_, "d_lgamma (upload)");
-            NT.lg = d_lgamma; NT.logs = d_lgamma + lgn; NT.lg_n = lgn; NT.p0 = Q.p; NT.log_nt = Q.log_nt; NT.inv = d_lgamma + lgn + 3 * PSL_NFA_NP;
-        }
-        const size_t N = PSL_MERGE_NMAX;
-        PSL_ALLOC(M.lines0, F * N * 4 * sizeof(float));
-        PSL_ALLOC(M.lines1, F * N * 4 * sizeof(float));
-        PSL_ALLOC(M.merged, F * N * 4 * sizeof(float));
-        PSL_ALLOC(M.angles, F * N * sizeof(float));
-        PSL_ALLOC(M.length, F * N * sizeof(float));
-        PSL_ALLOC(M.order, F * N * sizeof(int));
-        PSL_ALLOC(M.pos, F * N * sizeof(int));
-        PSL_ALLOC(M.adj, F * N * (N / 32) * sizeof(uint32_t));
-        PSL_ALLOC(M.code, F * N * sizeof(int));
-        PSL_ALLOC(M.clist, F * PSL_MERGE_CLMAX * sizeof(int));
-        PSL_ALLOC(M.coff, F * (2 * N + 2) * sizeof(int));
-        PSL_ALLOC(M.work, F * 4 * N * sizeof(int));
-        PSL_ALLOC(M.bits, F * (N / 32) * sizeof(uint32_t));
-        PSL_ALLOC(M.stage, F * N * sizeof(PslKeyLine));
-        PSL_ALLOC(d_kls, F * Q.maxkl * sizeof(PslKeyLine));
-        PSL_ALLOC(d_ldesc, F * Q.maxkl * 32);
-        PSL_ALLOC(d_fdesc, F * Q.maxkl * 72 * sizeof(float));
-        PSL_ALLOC(d_lineEq, F * Q.maxkl * 3 * sizeof(double));
-        PSL_ALLOC(d_nkl, F * sizeof(int));
-        PSL_ALLOC(d_status, F * sizeof(int));
-        PSL_ALLOC(d_dxy, F * (size_t)w * h * sizeof(short2));
-        PSL_ALLOC(d_rawfans, F * PSL_FAN_CAP * 4 * sizeof(float));
-        PSL_ALLOC(d_fans, F * PSL_FAN_CAP * 4 * sizeof(float));
-        PSL_ALLOC(d_nfans, F * sizeof(int));
-        PSL_ALLOC(d_tmplines, N * 4 * sizeof(float));
-#undef PSL_ALLOC
+        if (int rc = allocate(Q, w, h)) { release(); return rc; }
         P = Q;
         gw = w; gh = h;
         last_nframes = 0;
+        return PSLFE_OK;
+    }
+
+    // the buffers of prepare() for max_batch frames of w x h, and the nfa() / sincos tables; Q.sctab set
+    int allocate(LineParams& Q, int w, int h) {
+        const size_t F = (size_t)max_batch, npx = (size_t)Q.W * Q.H, N = PSL_MERGE_NMAX;
+        in_pitch = (int)psl_align_up(w, 16);
+        in_fstride = psl_align_up((size_t)in_pitch * h, 256);
+        static const double sctab[444] = {
+#include "psl_sincostab.inc"
+        };
+        // nfa() tables: the same functions the device would evaluate, here on the host (bit-identical: single IEEE operations)
+        const int lgn = 1 << 16;
+        std::vector<double> lg((size_t)lgn, 0.0);
+        for (int i = 1; i < lgn; ++i) lg[i] = lsdn_log_gamma((double)i);
+        lg.resize((size_t)lgn + 3 * PSL_NFA_NP + PSL_RATIO_BMAX);   // the three log tables and 1 / i follow the log_gamma table in the same allocation
+        for (int i = 1; i < PSL_RATIO_BMAX; ++i) lg[(size_t)lgn + 3 * PSL_NFA_NP + i] = 1.0 / (double)i;   // psl_ratio_inv's table (k_lsd_nfa_series)
+        double pj = Q.p;
+        for (int j = 0; j < PSL_NFA_NP; ++j, pj = pj / 2) {
+            lg[(size_t)lgn + j] = psl_log(pj); lg[(size_t)lgn + PSL_NFA_NP + j] = psl_log(1.0 - pj); lg[(size_t)lgn + 2 * PSL_NFA_NP + j] = psl_log10(pj);
+        }
+        mem.alloc(d_in, in_fstride * F, "d_in");
+        mem.alloc(d_scaled, npx * std::min<size_t>(F, PSL_LSD_SUBBATCH), "d_scaled");   // one sub-batch of the f64 working image (run_lsd)
+        mem.alloc(d_angdeg, npx * F, "d_angdeg");
+        mem.alloc(d_modgrad, npx * F, "d_modgrad");
+        mem.alloc(d_trig, npx * F, "d_trig");
+        mem.alloc(d_seedt, npx * F, "d_seedt");
+        mem.alloc(d_used, npx * F, "d_used");
+        mem.alloc(d_reg, npx * F, "d_reg");
+        mem.alloc(d_seg, (size_t)Q.maxseg * 4 * F, "d_seg");
+        mem.alloc(d_nseg, F, "d_nseg");
+        mem.alloc(d_rects, (size_t)Q.maxseg * PSL_LSD_RECT_F64 * F, "d_rects");
+        mem.alloc(d_nrect, F, "d_nrect");
+        mem.alloc(d_weight, F, "d_weight");
+        mem.alloc(d_order, F, "d_order");
+        mem.alloc(d_segtmp, (size_t)Q.maxseg * 4 * F, "d_segtmp");
+        mem.alloc(d_keep, (size_t)Q.maxseg * F, "d_keep");
+        mem.alloc(d_counts, (size_t)Q.maxseg * 5 * F, "d_counts");
+        mem.alloc(d_vals, (size_t)Q.maxseg * 5 * F, "d_vals");
+        mem.alloc(d_sstate, (size_t)Q.maxseg * 5 * F, "d_sstate");
+        mem.alloc(d_slist, (size_t)Q.maxseg * 5 * F, "d_slist");
+        mem.alloc(d_stmp, (size_t)Q.maxseg * 5 * F, "d_stmp");
+        mem.alloc(d_lcount, F * (PSL_NFA_NCLS + 1), "d_lcount");
+        mem.alloc(d_sctab, sizeof(sctab) / sizeof(double), "d_sctab");
+        mem.alloc(d_lgamma, lg.size(), "d_lgamma");
+        mem.alloc(M.lines0, F * N * 4, "M.lines0");
+        mem.alloc(M.lines1, F * N * 4, "M.lines1");
+        mem.alloc(M.merged, F * N * 4, "M.merged");
+        mem.alloc(M.angles, F * N, "M.angles");
+        mem.alloc(M.length, F * N, "M.length");
+        mem.alloc(M.order, F * N, "M.order");
+        mem.alloc(M.pos, F * N, "M.pos");
+        mem.alloc(M.adj, F * N * (N / 32), "M.adj");
+        mem.alloc(M.code, F * N, "M.code");
+        mem.alloc(M.clist, F * PSL_MERGE_CLMAX, "M.clist");
+        mem.alloc(M.coff, F * (2 * N + 2), "M.coff");
+        mem.alloc(M.work, F * 4 * N, "M.work");
+        mem.alloc(M.bits, F * (N / 32), "M.bits");
+        mem.alloc(M.stage, F * N, "M.stage");
+        mem.alloc(d_kls, F * Q.maxkl, "d_kls");
+        mem.alloc(d_ldesc, F * Q.maxkl * 32, "d_ldesc");
+        mem.alloc(d_fdesc, F * Q.maxkl * 72, "d_fdesc");
+        mem.alloc(d_lineEq, F * Q.maxkl * 3, "d_lineEq");
+        mem.alloc(d_nkl, F, "d_nkl");
+        mem.alloc(d_status, F, "d_status");
+        mem.alloc(d_dxy, F * (size_t)w * h, "d_dxy");
+        mem.alloc(d_rawfans, F * PSL_FAN_CAP * 4, "d_rawfans");
+        mem.alloc(d_fans, F * PSL_FAN_CAP * 4, "d_fans");
+        mem.alloc(d_nfans, F, "d_nfans");
+        mem.alloc(d_tmplines, N * 4, "d_tmplines");
+        if (int rc = mem.check("line")) return rc;
+        PSL_HIP(hipMemcpy(d_sctab, sctab, sizeof(sctab), hipMemcpyHostToDevice));
+        Q.sctab = d_sctab;
+        PSL_HIP(hipMemcpy(d_lgamma, lg.data(), lg.size() * sizeof(double), hipMemcpyHostToDevice));
+        NT.lg = d_lgamma; NT.logs = d_lgamma + lgn; NT.lg_n = lgn; NT.p0 = Q.p; NT.log_nt = Q.log_nt; NT.inv = d_lgamma + lgn + 3 * PSL_NFA_NP;
         return PSLFE_OK;
     }
 
@@ -438,10 +406,9 @@ int pslfe_line_create(pslfe_ctx* ctx, int numOctaves, float scale, int nLSDFeatu
 
 void pslfe_line_destroy(pslfe_line* line) {
     if (!line) return;
-    hipSetDevice(line->ctx->device);
-    hipStreamSynchronize(line->ctx->stream);
-    line->release();
-    delete line;
+    (void)hipSetDevice(line->ctx->device);
+    (void)hipStreamSynchronize(line->ctx->stream);
+    delete line;   // its buffers go with it
 }
 
 int pslfe_line_set_refine(pslfe_line* line, int refine) {

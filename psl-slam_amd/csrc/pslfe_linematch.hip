@@ -377,15 +377,6 @@ __global__ __launch_bounds__(64) void k_line_proj_match_batch_big(LineBatchArgs 
     if (blockIdx.x == 0 && threadIdx.x == 0 && A.nfallback) *A.nfallback = cnt;
 }
 
-namespace {
-struct DevBufs {  // device buffers of the host-pointer entry point: carved from the context's scratch arena
-    pslfe_ctx* ctx;
-    explicit DevBufs(pslfe_ctx* c) : ctx(c) {}
-    template <typename T>
-    T* up(const T* host, size_t count, hipStream_t st, hipError_t* e) { return psl_scratch_up(ctx, host, count, st, e); }
-};
-}  // namespace
-
 extern "C" {
 
 int pslfe_line_search_by_projection(pslfe_ctx* ctx, const PslKeyLine* kls, const uint8_t* desc, const double* lineEq, const double* dir3d, int n,
@@ -404,30 +395,29 @@ int pslfe_line_search_by_projection(pslfe_ctx* ctx, const PslKeyLine* kls, const
     PSL_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     { const int rc_ = psl_scratch_begin(ctx); if (rc_) return rc_; }
-    DevBufs B(ctx);
     hipError_t e = hipSuccess;
     LineMatchArgs A;
     memset(&A, 0, sizeof(A));
-    A.kls = B.up(kls, n, st, &e);
-    A.desc = B.up(desc, (size_t)n * 32, st, &e);
-    A.eq = B.up(lineEq, (size_t)n * 3, st, &e);
-    A.dir3d = dir3d ? B.up(dir3d, (size_t)n * 3, st, &e) : nullptr;
+    A.kls = psl_scratch_up(ctx, kls, n, st, &e);
+    A.desc = psl_scratch_up(ctx, desc, (size_t)n * 32, st, &e);
+    A.eq = psl_scratch_up(ctx, lineEq, (size_t)n * 3, st, &e);
+    A.dir3d = dir3d ? psl_scratch_up(ctx, dir3d, (size_t)n * 3, st, &e) : nullptr;
     A.n = n;
     A.minX = min_x; A.minY = min_y;
     A.invW = (float)PSL_LG_COLS / (float)(max_x - min_x);
     A.invH = (float)PSL_LG_ROWS / (float)(max_y - min_y);
-    A.q = B.up(queries, nq, st, &e);
-    A.qdesc = B.up(qdesc, (size_t)nq * 32, st, &e);
+    A.q = psl_scratch_up(ctx, queries, nq, st, &e);
+    A.qdesc = psl_scratch_up(ctx, qdesc, (size_t)nq * 32, st, &e);
     A.nq = nq;
-    A.taken = taken ? B.up(taken, n, st, &e) : nullptr;
+    A.taken = taken ? psl_scratch_up(ctx, taken, n, st, &e) : nullptr;
     A.nnratio = nnratio;
     A.cos_gate = mode == 0 ? cos(10.0 / 180.0 * M_PI) : cos(15.0 / 180.0 * M_PI);
     A.gcap = n * (PSL_LG_COLS + PSL_LG_ROWS);  // a Bresenham walk visits at most max(cols, rows) + 1 cells
-    A.gstart = B.up((const int*)nullptr, PSL_LG_CELLS + 1, st, &e);
-    A.gidx = B.up((const int*)nullptr, A.gcap, st, &e);
-    A.match = B.up((const int*)nullptr, nq ? nq : 1, st, &e);
-    A.assigned = B.up((const int*)nullptr, n, st, &e);
-    A.nmatches = B.up((const int*)nullptr, 1, st, &e);
+    A.gstart = psl_scratch_up(ctx, (const int*)nullptr, PSL_LG_CELLS + 1, st, &e);
+    A.gidx = psl_scratch_up(ctx, (const int*)nullptr, A.gcap, st, &e);
+    A.match = psl_scratch_up(ctx, (const int*)nullptr, nq ? nq : 1, st, &e);
+    A.assigned = psl_scratch_up(ctx, (const int*)nullptr, n, st, &e);
+    A.nmatches = psl_scratch_up(ctx, (const int*)nullptr, 1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_line_search_by_projection: %s", hipGetErrorString(e));
     {
         PSL_STAGE_BEGIN(ctx, "line.proj_match");

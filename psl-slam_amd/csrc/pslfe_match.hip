@@ -657,48 +657,45 @@ int pslfe_frame_create(pslfe_ctx* ctx, int max_keypoints, int max_frames, pslfe_
     f->slot_depth.assign(max_frames, 0);
     const size_t F = (size_t)max_frames, K = (size_t)max_keypoints;
     f->S.cap = max_keypoints;
-    hipError_t e = hipSuccess;
-    auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 1); };
-    A((void**)&f->S.kps, F * K * sizeof(PslKeyPoint));
-    A((void**)&f->S.desc, F * K * 32);
-    A((void**)&f->S.uright, F * K * sizeof(float));
-    A((void**)&f->S.cellof, F * K * sizeof(uint16_t));
-    A((void**)&f->S.gstart, F * (PSL_GRID_CELLS + 1) * sizeof(int));
-    A((void**)&f->S.gidx, F * K * sizeof(int));
-    A((void**)&f->S.meta, F * sizeof(FrameMeta));
-    A((void**)&f->d_q, PSL_QMAX * sizeof(PslProjQuery));
-    A((void**)&f->d_qdesc, PSL_QMAX * 32);
-    A((void**)&f->d_taken, K);
-    A((void**)&f->d_match, PSL_QMAX * sizeof(int));
-    A((void**)&f->d_assigned, K * sizeof(int));
-    A((void**)&f->d_nm, sizeof(int));
-    A((void**)&f->d_topk, F * K * PSL_TOPK * sizeof(uint32_t));
-    A((void**)&f->d_more, F * K);
-    A((void**)&f->d_topk1, (size_t)PSL_QMAX * PSL_TOPK * sizeof(uint32_t));
-    A((void**)&f->d_more1, PSL_QMAX);
-    A((void**)&f->d_fidx, K * sizeof(int));
-    A((void**)&f->d_depth, F * K * sizeof(float));
-    A((void**)&f->d_bounds, 4 * sizeof(float));
-    if (e != hipSuccess) {
-        pslfe_set_error("pslfe_frame_create: hipMalloc failed: %s", hipGetErrorString(e));
-        pslfe_frame_destroy(f);
-        return PSLFE_E_HIP;
+    PslDeviceBuffers& m = f->mem;
+    m.alloc(f->S.kps, F * K, "S.kps");
+    m.alloc(f->S.desc, F * K * 32, "S.desc");
+    m.alloc(f->S.uright, F * K, "S.uright");
+    m.alloc(f->S.cellof, F * K, "S.cellof");
+    m.alloc(f->S.gstart, F * (PSL_GRID_CELLS + 1), "S.gstart");
+    m.alloc(f->S.gidx, F * K, "S.gidx");
+    m.alloc(f->S.meta, F, "S.meta");
+    m.alloc(f->d_q, PSL_QMAX, "d_q");
+    m.alloc(f->d_qdesc, PSL_QMAX * 32, "d_qdesc");
+    m.alloc(f->d_taken, K, "d_taken");
+    m.alloc(f->d_match, PSL_QMAX, "d_match");
+    m.alloc(f->d_assigned, K, "d_assigned");
+    m.alloc(f->d_nm, 1, "d_nm");
+    m.alloc(f->d_topk, F * K * PSL_TOPK, "d_topk");
+    m.alloc(f->d_more, F * K, "d_more");
+    m.alloc(f->d_topk1, (size_t)PSL_QMAX * PSL_TOPK, "d_topk1");
+    m.alloc(f->d_more1, PSL_QMAX, "d_more1");
+    m.alloc(f->d_fidx, K, "d_fidx");
+    m.alloc(f->d_depth, F * K, "d_depth");
+    m.alloc(f->d_bounds, 4, "d_bounds");
+    int rc = m.check("pslfe_frame_create");
+    if (!rc && hipMemset(f->S.meta, 0, F * sizeof(FrameMeta)) != hipSuccess) {
+        pslfe_set_error("pslfe_frame_create: clearing the frame records failed");
+        rc = PSLFE_E_HIP;
     }
-    e = hipMemset(f->S.meta, 0, F * sizeof(FrameMeta));
+    if (rc) {
+        pslfe_frame_destroy(f);
+        return rc;
+    }
     *out = f;
     return PSLFE_OK;
 }
 
 void pslfe_frame_destroy(pslfe_frame* f) {
     if (!f) return;
-    hipSetDevice(f->ctx->device);
-    hipStreamSynchronize(f->ctx->stream);
-    hipFree(f->S.kps); hipFree(f->S.desc); hipFree(f->S.uright); hipFree(f->S.cellof); hipFree(f->S.gstart);
-    hipFree(f->S.gidx); hipFree(f->S.meta); hipFree(f->d_q); hipFree(f->d_qdesc); hipFree(f->d_taken);
-    hipFree(f->d_match); hipFree(f->d_assigned); hipFree(f->d_nm);
-    hipFree(f->d_topk); hipFree(f->d_more); hipFree(f->d_topk1); hipFree(f->d_more1);
-    hipFree(f->d_depth); hipFree(f->d_bounds); hipFree(f->d_fidx);
-    delete f;
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipStreamSynchronize(f->ctx->stream);
+    delete f;   // its buffers go with it
 }
 
 int pslfe_frame_set(pslfe_frame* f, int slot, const PslKeyPoint* kps, const uint8_t* desc, const float* uright, int n,
@@ -795,7 +792,7 @@ int pslfe_frame_set_rgbd(pslfe_frame* f, int slot, const PslKeyPoint* kps, const
     hipStream_t st = f->ctx->stream;
     const size_t o = (size_t)slot * f->cap;
     { const int rc_ = psl_scratch_begin(f->ctx); if (rc_) return rc_; }
-    float* d_img = static_cast<float*>(psl_scratch(f->ctx, (size_t)height * depth_stride * sizeof(float)));   // the context's scratch arena: no hipMalloc / hipFree per frame
+    float* d_img = static_cast<float*>(psl_scratch(f->ctx, (size_t)height * depth_stride * sizeof(float)));   // the context's scratch arena
     PSL_REQUIRE(d_img, PSLFE_E_HIP, "pslfe_frame_set_rgbd: out of device memory");
     hipError_t e = hipMemcpyAsync(d_img, depth, (size_t)height * depth_stride * sizeof(float), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(f->S.kps + o, kps, (size_t)n * sizeof(PslKeyPoint), hipMemcpyHostToDevice, st);
@@ -807,8 +804,9 @@ int pslfe_frame_set_rgbd(pslfe_frame* f, int slot, const PslKeyPoint* kps, const
     int rc = PSLFE_OK;
     if (e != hipSuccess) { pslfe_set_error("pslfe_frame_set_rgbd: H2D: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
     if (!rc) rc = frame_post_rgbd(f, slot, 1, d_img, width, height, depth_stride, 0, cam);
-    hipStreamSynchronize(st);
-    return rc;
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // failing already: drain the queued copies, report the first error
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
 }
 
 int pslfe_frame_set_from_orb_rgbd(pslfe_frame* f, pslfe_orb* orb, const float* d_depth, int width, int height, const PslCamera* cam) {
@@ -947,28 +945,18 @@ int pslfe_hamming_knn2(pslfe_ctx* ctx, const uint8_t* q, int nq, const uint8_t* 
     PSL_REQUIRE(q && (nt == 0 || t), PSLFE_E_INVALID, "pslfe_hamming_knn2: NULL descriptors");
     PSL_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    uint8_t *dq = nullptr, *dt = nullptr;
-    int *di = nullptr, *dd = nullptr;
-    hipError_t e = hipMalloc((void**)&dq, (size_t)nq * 32);
-    if (e == hipSuccess) e = hipMalloc((void**)&dt, nt ? (size_t)nt * 32 : 1);
-    if (e == hipSuccess) e = hipMalloc((void**)&di, (size_t)nq * 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&dd, (size_t)nq * 2 * sizeof(int));
-    int rc = PSLFE_OK;
-    if (e != hipSuccess) { pslfe_set_error("pslfe_hamming_knn2: hipMalloc: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    if (!rc) {
-        e = hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && nt) e = hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { pslfe_set_error("pslfe_hamming_knn2: H2D: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    }
-    if (!rc) rc = pslfe_hamming_knn2_device(ctx, dq, nq, dt, nt, di, dd);
-    if (!rc) {
-        e = hipMemcpyAsync(idx, di, (size_t)nq * 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dist, dd, (size_t)nq * 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { pslfe_set_error("pslfe_hamming_knn2: D2H: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    }
-    hipFree(dq); hipFree(dt); hipFree(di); hipFree(dd);
-    return rc;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    hipError_t e = hipSuccess;
+    uint8_t* dq = psl_scratch_up(ctx, q, (size_t)nq * 32, st, &e);
+    uint8_t* dt = psl_scratch_up(ctx, nt ? t : nullptr, (size_t)nt * 32, st, &e);
+    int* di = psl_scratch_up(ctx, (const int*)nullptr, (size_t)nq * 2, st, &e);
+    int* dd = psl_scratch_up(ctx, (const int*)nullptr, (size_t)nq * 2, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_hamming_knn2: %s", hipGetErrorString(e));
+    if (int rc = pslfe_hamming_knn2_device(ctx, dq, nq, dt, nt, di, dd)) return rc;
+    PSL_HIP(hipMemcpyAsync(idx, di, (size_t)nq * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(dist, dd, (size_t)nq * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
 }
 
 int pslfe_line_match_nnr(pslfe_ctx* ctx, const uint8_t* desc1, int n1, const uint8_t* desc2, int n2, float nnr,

@@ -53,14 +53,6 @@ void build_gauss_q8(int ksize, double sigma, int* K) {
     }
 }
 
-template <typename T>
-int dev_alloc(T** p, size_t count) {
-    if (*p) { hipFree(*p); *p = nullptr; }
-    if (count == 0) count = 1;
-    PSL_HIP(hipMalloc((void**)p, count * sizeof(T)));
-    return PSLFE_OK;
-}
-
 }  // namespace
 
 struct pslfe_orb {
@@ -99,20 +91,7 @@ struct pslfe_orb {
     int last_nframes = 0;
     FrameSrc last_src = {};
 
-    void release() {
-        hipFree(d_pyr); hipFree(d_blur); hipFree(d_cellcnt); hipFree(d_celloff); hipFree(d_cellcand);
-        hipFree(d_cand); hipFree(d_knode); hipFree(d_lvlkp); hipFree(d_lvlcnt); hipFree(d_kps);
-        hipFree(d_desc); hipFree(d_counts); hipFree(d_in); hipFree(d_celltab);
-        d_celltab = nullptr;
-        d_pyr = d_blur = d_desc = d_in = nullptr;
-        d_cellcnt = d_celloff = d_lvlcnt = d_counts = nullptr;
-        d_cellcand = d_cand = d_lvlkp = nullptr;
-        d_knode = nullptr; d_kps = nullptr;
-        for (int l = 0; l < PSLFE_MAX_LEVELS; ++l) {
-            hipFree(d_xofs[l]); hipFree(d_alpha[l]); hipFree(d_yofs[l]); hipFree(d_beta[l]);
-            d_xofs[l] = d_yofs[l] = nullptr; d_alpha[l] = d_beta[l] = nullptr;
-        }
-    }
+    PslDeviceBuffers mem;   // owns every d_* buffer above
 
     // Derives every size the kernels need for a w x h input (src/ORBextractor.cc:765-787, 541-545,
     // 1107-1115) and (re)allocates the HBM buffers for max_batch frames.
@@ -185,12 +164,12 @@ struct pslfe_orb {
 
         PSL_HIP(hipSetDevice(ctx->device));
         PSL_HIP(hipStreamSynchronize(ctx->stream));
-        // From here on buffers are freed and re-allocated one by one: forget the old geometry first, so that a failure below
-        // (dev_alloc returns early) cannot leave `w == gw && h == gh` true over freed or undersized buffers.
+        // Forget the old geometry with the old buffers, so that a failure below cannot leave `w == gw && h == gh` true over freed or
+        // undersized buffers.
         gw = gh = 0;
         last_nframes = 0;
-        const int rc_alloc = allocate(Q, w, h, pyr_off, blur_off, cellcap);
-        if (rc_alloc) { release(); (void)hipGetLastError(); return rc_alloc; }  // the failed hipMalloc must not surface in a later hipGetLastError()
+        mem.release();
+        if (int rc = allocate(Q, w, h, pyr_off, blur_off, cellcap)) { mem.release(); return rc; }
         P = Q;
         gw = w; gh = h;
         return PSLFE_OK;
@@ -200,28 +179,28 @@ struct pslfe_orb {
         const size_t F = (size_t)max_batch;
         pyr_fstride = psl_align_up(pyr_off, 256);
         blur_fstride = psl_align_up(blur_off, 256);
-        int rc;
-        if ((rc = dev_alloc(&d_pyr, pyr_fstride * F))) return rc;
-        if ((rc = dev_alloc(&d_blur, blur_fstride * F))) return rc;
-        if ((rc = dev_alloc(&d_cellcnt, (size_t)Q.ncells * F))) return rc;
-        if ((rc = dev_alloc(&d_celloff, (size_t)Q.ncells * F))) return rc;
-        if ((rc = dev_alloc(&d_cellcand, (size_t)Q.ncells * cellcap * F))) return rc;
-        if ((rc = dev_alloc(&d_cand, (size_t)Q.cand_total * F))) return rc;
-        if ((rc = dev_alloc(&d_knode, (size_t)Q.cand_total * F))) return rc;
-        if ((rc = dev_alloc(&d_lvlkp, (size_t)Q.kp_total * F))) return rc;
-        if ((rc = dev_alloc(&d_lvlcnt, (size_t)nlevels * F))) return rc;
-        if ((rc = dev_alloc(&d_kps, (size_t)Q.out_cap * F))) return rc;
-        if ((rc = dev_alloc(&d_desc, (size_t)Q.out_cap * 32 * F))) return rc;
-        if ((rc = dev_alloc(&d_counts, F))) return rc;
         in_pitch = (int)psl_align_up(w, 16);
         in_fstride = psl_align_up((size_t)in_pitch * h, 256);
-        if ((rc = dev_alloc(&d_in, in_fstride * F))) return rc;
+        mem.alloc(d_pyr, pyr_fstride * F, "d_pyr");
+        mem.alloc(d_blur, blur_fstride * F, "d_blur");
+        mem.alloc(d_cellcnt, (size_t)Q.ncells * F, "d_cellcnt");
+        mem.alloc(d_celloff, (size_t)Q.ncells * F, "d_celloff");
+        mem.alloc(d_cellcand, (size_t)Q.ncells * cellcap * F, "d_cellcand");
+        mem.alloc(d_cand, (size_t)Q.cand_total * F, "d_cand");
+        mem.alloc(d_knode, (size_t)Q.cand_total * F, "d_knode");
+        mem.alloc(d_lvlkp, (size_t)Q.kp_total * F, "d_lvlkp");
+        mem.alloc(d_lvlcnt, (size_t)nlevels * F, "d_lvlcnt");
+        mem.alloc(d_kps, (size_t)Q.out_cap * F, "d_kps");
+        mem.alloc(d_desc, (size_t)Q.out_cap * 32 * F, "d_desc");
+        mem.alloc(d_counts, F, "d_counts");
+        mem.alloc(d_in, in_fstride * F, "d_in");
         {
             std::vector<uint32_t> tab((size_t)Q.ncells);
             for (int l = 0; l < nlevels; ++l)
                 for (int c = 0; c < Q.lv[l].nCols * Q.lv[l].nRows; ++c)
                     tab[(size_t)Q.lv[l].cell_off + c] = (uint32_t)l | ((uint32_t)(c / Q.lv[l].nCols) << 8) | ((uint32_t)(c % Q.lv[l].nCols) << 20);
-            if ((rc = dev_alloc(&d_celltab, tab.size()))) return rc;
+            mem.alloc(d_celltab, tab.size(), "d_celltab");
+            if (int rc = mem.check("orb")) return rc;
             PSL_HIP(hipMemcpy(d_celltab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         for (int l = 1; l < nlevels; ++l) {
@@ -229,10 +208,11 @@ struct pslfe_orb {
             std::vector<short> al, be;
             build_linear_table(Q.lv[l - 1].w, Q.lv[l].w, true, xo, al);
             build_linear_table(Q.lv[l - 1].h, Q.lv[l].h, false, yo, be);
-            if ((rc = dev_alloc(&d_xofs[l], xo.size()))) return rc;
-            if ((rc = dev_alloc(&d_alpha[l], xo.size()))) return rc;
-            if ((rc = dev_alloc(&d_yofs[l], yo.size()))) return rc;
-            if ((rc = dev_alloc(&d_beta[l], yo.size()))) return rc;
+            mem.alloc(d_xofs[l], xo.size(), "d_xofs");
+            mem.alloc(d_alpha[l], xo.size(), "d_alpha");
+            mem.alloc(d_yofs[l], yo.size(), "d_yofs");
+            mem.alloc(d_beta[l], yo.size(), "d_beta");
+            if (int rc = mem.check("orb")) return rc;
             PSL_HIP(hipMemcpy(d_xofs[l], xo.data(), xo.size() * sizeof(int), hipMemcpyHostToDevice));
             PSL_HIP(hipMemcpy(d_alpha[l], al.data(), al.size() * sizeof(short), hipMemcpyHostToDevice));
             PSL_HIP(hipMemcpy(d_yofs[l], yo.data(), yo.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -347,9 +327,8 @@ int pslfe_orb_create(pslfe_ctx* ctx, int nfeatures, float scaleFactor, int nleve
 
 void pslfe_orb_destroy(pslfe_orb* orb) {
     if (!orb) return;
-    hipSetDevice(orb->ctx->device);
-    hipStreamSynchronize(orb->ctx->stream);
-    orb->release();
+    (void)hipSetDevice(orb->ctx->device);
+    (void)hipStreamSynchronize(orb->ctx->stream);
     delete orb;
 }
 

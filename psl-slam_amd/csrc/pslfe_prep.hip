@@ -89,43 +89,31 @@ int pslfe_rgb_to_gray(pslfe_ctx* ctx, const uint8_t* rgb, int w, int h, int stri
     PSL_REQUIRE(ctx && rgb && gray, PSLFE_E_INVALID, "pslfe_rgb_to_gray: NULL argument");
     PSL_REQUIRE(w > 0 && h > 0 && stride >= 3 * w, PSLFE_E_INVALID, "pslfe_rgb_to_gray: %dx%d stride %d", w, h, stride);
     PSL_HIP(hipSetDevice(ctx->device));
-    uint8_t *d_in = nullptr, *d_out = nullptr;
     const size_t bytes = (size_t)stride * h;
-    PSL_HIP(hipMalloc((void**)&d_in, bytes));
-    hipError_t e = hipMalloc((void**)&d_out, (size_t)w * h);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, rgb, (size_t)stride * (h - 1) + 3 * (size_t)w, hipMemcpyHostToDevice, ctx->stream);
-    int rc = PSLFE_OK;
-    if (e != hipSuccess) { pslfe_set_error("pslfe_rgb_to_gray: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    if (!rc) rc = pslfe_rgb_to_gray_device(ctx, d_in, 1, w, h, stride, bytes, is_rgb, d_out);
-    if (!rc) {
-        e = hipMemcpyAsync(gray, d_out, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pslfe_set_error("pslfe_rgb_to_gray: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    }
-    hipStreamSynchronize(ctx->stream);
-    hipFree(d_in); hipFree(d_out);
-    return rc;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    uint8_t* d_in = static_cast<uint8_t*>(psl_scratch(ctx, bytes));
+    uint8_t* d_out = static_cast<uint8_t*>(psl_scratch(ctx, (size_t)w * h));
+    PSL_REQUIRE(d_in && d_out, PSLFE_E_HIP, "pslfe_rgb_to_gray: out of device memory");
+    PSL_HIP(hipMemcpyAsync(d_in, rgb, (size_t)stride * (h - 1) + 3 * (size_t)w, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = pslfe_rgb_to_gray_device(ctx, d_in, 1, w, h, stride, bytes, is_rgb, d_out)) return rc;
+    PSL_HIP(hipMemcpyAsync(gray, d_out, (size_t)w * h, hipMemcpyDeviceToHost, ctx->stream));
+    PSL_HIP(hipStreamSynchronize(ctx->stream));
+    return PSLFE_OK;
 }
 
 int pslfe_depth_to_float(pslfe_ctx* ctx, const uint16_t* depth, size_t n, float factor, float* out) {
     PSL_REQUIRE(ctx && (n == 0 || (depth && out)), PSLFE_E_INVALID, "pslfe_depth_to_float: NULL argument");
     if (n == 0) return PSLFE_OK;
     PSL_HIP(hipSetDevice(ctx->device));
-    uint16_t* d_in = nullptr; float* d_out = nullptr;
-    PSL_HIP(hipMalloc((void**)&d_in, n * 2 + 4));
-    hipError_t e = hipMalloc((void**)&d_out, n * 4 + 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, depth, n * 2, hipMemcpyHostToDevice, ctx->stream);
-    int rc = PSLFE_OK;
-    if (e != hipSuccess) { pslfe_set_error("pslfe_depth_to_float: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    if (!rc) rc = pslfe_depth_to_float_device(ctx, d_in, n, factor, d_out);
-    if (!rc) {
-        e = hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pslfe_set_error("pslfe_depth_to_float: %s", hipGetErrorString(e)); rc = PSLFE_E_HIP; }
-    }
-    hipStreamSynchronize(ctx->stream);
-    hipFree(d_in); hipFree(d_out);
-    return rc;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    uint16_t* d_in = static_cast<uint16_t*>(psl_scratch(ctx, n * 2 + 4));
+    float* d_out = static_cast<float*>(psl_scratch(ctx, n * 4 + 8));
+    PSL_REQUIRE(d_in && d_out, PSLFE_E_HIP, "pslfe_depth_to_float: out of device memory");
+    PSL_HIP(hipMemcpyAsync(d_in, depth, n * 2, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = pslfe_depth_to_float_device(ctx, d_in, n, factor, d_out)) return rc;
+    PSL_HIP(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PSL_HIP(hipStreamSynchronize(ctx->stream));
+    return PSLFE_OK;
 }
 
 }  // extern "C"

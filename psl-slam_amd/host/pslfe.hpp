@@ -13,8 +13,10 @@
 #include <cstdint>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pslfe.h"
@@ -467,29 +469,19 @@ public:
         : w_(cols), h_(rows), K_(lookahead < 1 ? 1 : lookahead), cam_(cam), radius_(pairRadius), fanThr_(fanThr) {
         for (int l = 0; l < 2; ++l) {
             Lane& L = lane_[l];
-            L.own = new Context(ctx.device());   // a context (= a stream) of its own per lane: the caller's context stays free for the per-frame
-            L.ctx = L.own;                       // calls of the tracker (LSDmatcher, plane association ...) while a lane extracts
-            L.orb = new ORBextractor(*L.ctx, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, K_);
-            L.lsd = new LINEextractor(*L.ctx, 1, 1.2f, (unsigned)nLSDFeature, 0.0, K_);
+            L.ctx = std::make_unique<Context>(ctx.device());   // a context (= a stream) of its own per lane: the caller's context stays free for
+                                                             // the per-frame calls of the tracker (LSDmatcher, plane association ...) while a lane extracts
+            L.orb = std::make_unique<ORBextractor>(*L.ctx, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, K_);
+            L.lsd = std::make_unique<LINEextractor>(*L.ctx, 1, 1.2f, (unsigned)nLSDFeature, 0.0, K_);
             kpCap_ = pslfe_orb_max_keypoints(L.orb->get(), cols, rows);
             if (kpCap_ < 0) throw Error(kpCap_, "pslfe_orb_max_keypoints");
-            L.grid = new FrameGrid(*L.ctx, kpCap_ > 0 ? kpCap_ : 1, K_);
-            check(pslfe_device_alloc(L.ctx->get(), (size_t)K_ * w_ * h_, &L.d_gray), "pslfe_device_alloc");
-            check(pslfe_device_alloc(L.ctx->get(), (size_t)K_ * w_ * h_ * sizeof(float), &L.d_depth), "pslfe_device_alloc");
-            caps_.kp_cap = kpCap_; caps_.kl_cap = nLSDFeature; caps_.fan_cap = 4096; caps_.plane_cap = 0;
+            L.grid = std::make_unique<FrameGrid>(*L.ctx, kpCap_ > 0 ? kpCap_ : 1, K_);
+            L.d_gray = DeviceBuffer(*L.ctx, (size_t)K_ * w_ * h_);
+            L.d_depth = DeviceBuffer(*L.ctx, (size_t)K_ * w_ * h_ * sizeof(float));
+            caps_.kp_cap = kpCap_; caps_.kl_cap = nLSDFeature; caps_.fan_cap = PSLFE_FAN_CAP; caps_.plane_cap = 0;
             check(pslfe_record_layout(&caps_, &lay_), "pslfe_record_layout");
-            check(pslfe_device_alloc(L.ctx->get(), (size_t)K_ * lay_.bytes, &L.d_rec), "pslfe_device_alloc");
+            L.d_rec = DeviceBuffer(*L.ctx, (size_t)K_ * lay_.bytes);
             L.rec.resize((size_t)K_ * lay_.bytes);
-        }
-    }
-    ~FramePrefetcher() {
-        for (int l = 0; l < 2; ++l) {
-            Lane& L = lane_[l];
-            if (L.ctx) {
-                pslfe_ctx_synchronize(L.ctx->get());
-                pslfe_device_free(L.ctx->get(), L.d_gray); pslfe_device_free(L.ctx->get(), L.d_depth); pslfe_device_free(L.ctx->get(), L.d_rec);
-            }
-            delete L.glue; delete L.grid; delete L.lsd; delete L.orb; delete L.own;
         }
     }
     FramePrefetcher(const FramePrefetcher&) = delete;
@@ -518,8 +510,8 @@ public:
             if (!(L.collected && L.next == L.staged)) return false;   // still being popped (or not popped at all)
             L.launched = L.collected = false; L.staged = L.next = 0;   // every frame of this lane has been handed out: it takes the next batch
         }
-        uint8_t* dg = static_cast<uint8_t*>(L.d_gray) + (size_t)L.staged * w_ * h_;
-        float* dd = static_cast<float*>(L.d_depth) + (size_t)L.staged * w_ * h_;
+        uint8_t* dg = static_cast<uint8_t*>(L.d_gray.get()) + (size_t)L.staged * w_ * h_;
+        float* dd = static_cast<float*>(L.d_depth.get()) + (size_t)L.staged * w_ * h_;
         if (grayStep != w_) {   // rows with padding: packed on the host first, one copy either way
             tmp8_.resize((size_t)w_ * h_);
             for (int y = 0; y < h_; ++y) memcpy(tmp8_.data() + (size_t)y * w_, gray + (size_t)y * grayStep, (size_t)w_);
@@ -553,16 +545,17 @@ public:
             if (stage_ == cur_) stage_ ^= 1;
         }
         if (!L.collected) {   // the batch's packed records, one copy (waits for the lane's stream)
-            check(pslfe_device_download(L.ctx->get(), L.rec.data(), L.d_rec, (size_t)L.staged * lay_.bytes), "pslfe_device_download");
+            check(pslfe_device_download(L.ctx->get(), L.rec.data(), L.d_rec.get(), (size_t)L.staged * lay_.bytes), "pslfe_device_download");
             L.collected = true;
         }
-        const int k = L.next++;
+        const int k = L.next;
         const uint8_t* r = L.rec.data() + (size_t)k * lay_.bytes;
         int32_t hd[8];
         memcpy(hd, r, sizeof(hd));
         const int nkp = hd[0], nkl = hd[2], nfan = hd[4];
         if ((hd[6] & 7) != 0) throw Error(PSLFE_E_CAPACITY, "FramePrefetcher: a frame's results exceed the record capacities");
-        out.index = L.index0 + (uint64_t)k; out.slot = k; out.grid = L.grid;
+        ++L.next;   // only once the record is known to be whole: after a throw above, a retry sees the same frame
+        out.index = L.index0 + (uint64_t)k; out.slot = k; out.grid = L.grid.get();
         out.mvKeys.resize(nkp); out.mDescriptors.resize((size_t)nkp * 32);
         out.mvKeylinesUn.resize(nkl); out.mLdesc.resize((size_t)nkl * 32); out.mvKeyLineFunctions.resize((size_t)nkl * 3);
         out.fans.resize((size_t)nfan * 4);
@@ -582,14 +575,31 @@ public:
     }
 
 private:
+    // One pslfe_device_alloc block of a lane, freed once the lane's context has finished with it.
+    class DeviceBuffer {
+    public:
+        DeviceBuffer() = default;
+        DeviceBuffer(Context& ctx, size_t bytes) : ctx_(&ctx) { check(pslfe_device_alloc(ctx.get(), bytes, &p_), "pslfe_device_alloc"); }
+        DeviceBuffer(DeviceBuffer&& o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+        DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { std::swap(ctx_, o.ctx_); std::swap(p_, o.p_); return *this; }
+        ~DeviceBuffer() {
+            if (!p_) return;
+            pslfe_ctx_synchronize(ctx_->get());
+            pslfe_device_free(ctx_->get(), p_);
+        }
+        void* get() const { return p_; }
+    private:
+        Context* ctx_ = nullptr;
+        void* p_ = nullptr;
+    };
+    // members are destroyed in reverse order: the buffers and extractors before the lane's context
     struct Lane {
-        Context* own = nullptr;
-        Context* ctx = nullptr;
-        ORBextractor* orb = nullptr;
-        LINEextractor* lsd = nullptr;
-        FrameGrid* grid = nullptr;
-        FrameGlue* glue = nullptr;   // created after the first batch: its row stride is the line extractor's (pslfe_line_results_device)
-        void* d_gray = nullptr; void* d_depth = nullptr; void* d_rec = nullptr;
+        std::unique_ptr<Context> ctx;
+        std::unique_ptr<ORBextractor> orb;
+        std::unique_ptr<LINEextractor> lsd;
+        std::unique_ptr<FrameGrid> grid;
+        std::unique_ptr<FrameGlue> glue;   // created after the first batch: its row stride is the line extractor's (pslfe_line_results_device)
+        DeviceBuffer d_gray, d_depth, d_rec;
         std::vector<uint8_t> rec;
         int staged = 0, next = 0;            // frames staged in this lane / handed out
         bool launched = false, collected = false;
@@ -600,8 +610,8 @@ private:
     void launch(int l) {
         Lane& L = lane_[l];
         const int F = L.staged;
-        const uint8_t* dg = static_cast<const uint8_t*>(L.d_gray);
-        const float* dd = static_cast<const float*>(L.d_depth);
+        const uint8_t* dg = static_cast<const uint8_t*>(L.d_gray.get());
+        const float* dd = static_cast<const float*>(L.d_depth.get());
         check(pslfe_orb_extract_batch_device(L.orb->get(), dg, F, w_, h_, w_, (size_t)w_ * h_), "pslfe_orb_extract_batch_device");       // ExtractORB
         check(pslfe_line_extract_batch_device(L.lsd->get(), dg, F, w_, h_, w_, (size_t)w_ * h_), "pslfe_line_extract_batch_device");   // ExtractLSD: extractor
         check(pslfe_line_pair_batch_device(L.lsd->get(), radius_, fanThr_), "pslfe_line_pair_batch_device");                              // src/Frame.cc:505
@@ -610,11 +620,11 @@ private:
         check(pslfe_orb_results_device(L.orb->get(), &S.d_kps, &S.d_desc, &S.d_kp_counts, &S.kp_stride), "pslfe_orb_results_device");
         check(pslfe_line_results_device(L.lsd->get(), &S.d_kls, &S.d_ldesc, &S.d_lineEq, &S.d_kl_counts, &S.kl_stride), "pslfe_line_results_device");
         check(pslfe_line_fans_device(L.lsd->get(), &S.d_fans, &S.d_fan_counts, &S.fan_stride), "pslfe_line_fans_device");
-        if (!L.glue) L.glue = new FrameGlue(*L.ctx, S.kl_stride, S.fan_stride, K_);
+        if (!L.glue) L.glue = std::make_unique<FrameGlue>(*L.ctx, S.kl_stride, S.fan_stride, K_);
         check(pslfe_glue_run_batch_device(L.glue->get(), F, S.d_kls, S.kl_stride, S.d_kl_counts, S.d_fans, S.fan_stride, S.d_fan_counts, dd, w_, h_, &cam_,
                                           (uint32_t)(1u + next_index_)), "pslfe_glue_run_batch_device");                               // isLineGood, fans, planes
         check(pslfe_frame_set_from_orb_rgbd(L.grid->get(), L.orb->get(), dd, w_, h_, &cam_), "pslfe_frame_set_from_orb_rgbd");          // Undistort .. AssignFeaturesToGrid
-        check(pslfe_record_pack_device(L.ctx->get(), &caps_, &S, F, L.d_rec), "pslfe_record_pack_device");
+        check(pslfe_record_pack_device(L.ctx->get(), &caps_, &S, F, L.d_rec.get()), "pslfe_record_pack_device");
         L.index0 = next_index_;
         next_index_ += (uint64_t)F;
         L.launched = true; L.collected = false; L.next = 0;
