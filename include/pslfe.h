@@ -300,6 +300,40 @@ int pslfe_frame_set_rgbd(pslfe_frame* f, int slot, const PslKeyPoint* kps, const
  * d_depth: [nframes][height][width] float in HBM. */
 int pslfe_frame_set_from_orb_rgbd(pslfe_frame* f, pslfe_orb* orb, const float* d_depth, int width, int height,
                                   const PslCamera* cam);
+/* == The stereo Frame constructor src/Frame.cc:75-131 for nframes rectified pairs: Frame::ComputeStereoMatches :1165-1340 on
+ *    the DISTORTED keypoints (mvKeys / mvKeysRight), then UndistortKeyPoints, ComputeImageBounds and AssignFeaturesToGrid exactly
+ *    as pslfe_frame_set_from_orb_rgbd does.  Left frame left0+p of `left`'s last batch and right frame right0+p of `right`'s last
+ *    batch -> slot slot0+p; the slot then holds mvKeysUn, mvuRight (DISTORTED coordinates, as in the reference) and mvDepth.
+ *    left == right is allowed (one extraction launch of 2N frames).  Both handles: f's context, the same image size and nlevels,
+ *    bitwise-equal scale factors, capacity <= f's.  Asynchronous on the context's stream.  Level 0 of a batch extracted with
+ *    pslfe_orb_extract_batch_device is the caller's input buffer: it must stay unchanged until this call's work has run on the
+ *    stream (the host entry points copy the image into the handle, so they need no such rule).
+ *    Reproduced exactly (integer SAD, float steps rounded as the reference rounds them, no contraction):
+ *    - row band :1182-1192: right keypoint iR is a candidate of left keypoint iL when (int)vL (vRowIndices[vL], truncation) lies
+ *      in [floor(y - r), ceil(y + r)], r = 2.0f*mvScaleFactors[octave_R]; octave_R within +-1 of octave_L (:1232);
+ *      uR in [uL - maxD, uL - minD] (:1237), minD = 0, maxD = mbf/minZ; maxU < 0 skips the keypoint (:1218);
+ *    - descriptor choice :1221-1248: the first strict minimum below TH_HIGH = 100 in ascending iR == the least (dist, iR);
+ *      the SAD step only when bestDist < thOrbDist = 75 (:1251);
+ *    - SAD windows :1253-1291: both pyramids at the LEFT keypoint's octave, positions round(x*invScale) in float, w = L = 5;
+ *      skipped when iniu < 0 || endu >= cols with iniu = scaleduR0+L-w (the reference's +L); metric
+ *      sum |(IL - IL(w,w)) - (IR - IR(w,w))| over 11x11 (exact in integers); first minimum over incR = -5..5; bestincR == +-L
+ *      rejected (:1293);
+ *    - parabola and rescale :1297-1324: deltaR = (d1-d3)/(2.0f*(d1+d3-2.0f*d2)), |deltaR| > 1 rejected,
+ *      bestuR = mvScaleFactors[octave]*((float)scaleduR0+(float)bestincR+deltaR), disparity = uL - bestuR accepted in
+ *      [0, maxD); disparity <= 0 -> disparity = 0.01f, bestuR = (float)((double)uL - 0.01); mvDepth = mbf/disparity;
+ *    - median filter :1325-1339 (the inner bestDist shadows the Hamming one: the SAD minimum is filtered): median = the
+ *      size/2-th smallest SAD of the accepted keypoints, thDist = 1.5f*1.4f*median, every accepted keypoint with SAD >= thDist
+ *      gets mvuRight = mvDepth = -1.
+ *    Conventions where the reference is undefined: minZ = mb = mbf/fx in float (the reference reads mb before
+ *    :128 assigns it); no accepted keypoint -> nothing is filtered (the reference indexes an empty vector); a row band or a
+ *    left row outside the image, and SAD windows outside the level image (where cv::Mat::rowRange/colRange would throw), give
+ *    no match - none of them occurs for keypoints of the extractor. */
+int pslfe_frame_set_from_orb_stereo(pslfe_frame* f, int slot0, pslfe_orb* left, int left0, pslfe_orb* right, int right0,
+                                    int nframes, const PslCamera* cam);
+/* Tap per left keypoint of a stereo slot: idx_right = right keypoint chosen by the descriptor stage (-1: none below
+ * thOrbDist), sad = the SAD minimum of the window sweep (-1: skipped or rejected before the median filter).  *n = the slot's
+ * keypoint count; either array may be NULL.  PSLFE_E_STATE if the slot was not set by pslfe_frame_set_from_orb_stereo. */
+int pslfe_frame_debug_stereo(pslfe_frame* f, int slot, int32_t* idx_right, int32_t* sad, int cap, int* n);
 /* mvKeysUn, mvDepth, mvuRight of a slot (any pointer may be NULL). */
 int pslfe_frame_fetch(pslfe_frame* f, int slot, PslKeyPoint* kps_un, float* depth, float* uright, int cap, int* n);
 

@@ -346,6 +346,23 @@ class FrameGrid:
         _check(lib().pslfe_frame_set_from_orb_rgbd(self._h, orb._h, C.c_void_p(int(d_depth)), C.c_int(width), C.c_int(height),
                                                    _ptr(cam)), "pslfe_frame_set_from_orb_rgbd")
 
+    def set_from_orb_stereo(self, slot0, left, left0, right, right0, nframes, cam):
+        """The stereo Frame constructor (src/Frame.cc:75-131: ComputeStereoMatches, UndistortKeyPoints, AssignFeaturesToGrid) for
+        nframes rectified pairs, HBM to HBM: frame left0+p of `left`'s last batch and frame right0+p of `right`'s -> slot slot0+p.
+        `left` and `right` may be the same extractor.  Asynchronous."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_frame_set_from_orb_stereo(self._h, C.c_int(slot0), left._h, C.c_int(left0), right._h, C.c_int(right0),
+                                                     C.c_int(nframes), _ptr(cam)), "pslfe_frame_set_from_orb_stereo")
+
+    def debug_stereo(self, slot):
+        """Taps of a stereo slot: (right index of the descriptor stage or -1, SAD minimum of an accepted keypoint or -1)."""
+        idx = np.zeros(self.cap, np.int32)
+        sad = np.zeros(self.cap, np.int32)
+        n = C.c_int()
+        _check(lib().pslfe_frame_debug_stereo(self._h, C.c_int(slot), _ptr(idx), _ptr(sad), C.c_int(self.cap), C.byref(n)),
+               "pslfe_frame_debug_stereo")
+        return idx[:n.value], sad[:n.value]
+
     def fetch(self, slot):
         """(mvKeysUn, mvDepth, mvuRight) of a slot."""
         kps = np.zeros(self.cap, KEYPOINT_DTYPE)

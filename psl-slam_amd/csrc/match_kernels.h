@@ -223,9 +223,22 @@ struct pslfe_frame {
     int* d_fidx = nullptr;       // [cap] the frame's FeatureVector (SearchByBoW, host-pointer entry point)
     float* d_depth = nullptr;    // [max_frames][cap] mvDepth (RGB-D post-processing)
     float* d_bounds = nullptr;   // [4] scratch for k_image_bounds
+    // stereo (pslfe_stereo.hip), allocated on the first stereo call: taps [max_frames][cap], right keypoints binned by row
+    int32_t* d_st_idx = nullptr;
+    int32_t* d_st_sad = nullptr;
+    int* d_st_rowstart = nullptr;     // [pairs][rows + 1]
+    uint16_t* d_st_rowidx = nullptr;  // [pairs][right capacity]
+    size_t st_rowstart_cap = 0, st_rowidx_cap = 0;
     PslDeviceBuffers mem;        // owns every device buffer above
     std::vector<char> slot_set;
-    std::vector<char> slot_depth;  // the slot's mvDepth was set (pslfe_frame_set_rgbd / _set_from_orb_rgbd)
+    std::vector<char> slot_depth;  // the slot's mvDepth was set (pslfe_frame_set_rgbd / _set_from_orb_rgbd / _set_from_orb_stereo)
+    std::vector<char> slot_stereo; // the slot was set by pslfe_frame_set_from_orb_stereo (its taps are valid)
 };
+
+// pslfe_match.hip, for pslfe_stereo.hip: frames of an extractor's result arrays (pointers at the first frame) -> slots
+// slot0.., and the constructor's tail on those slots (bounds of a cols x rows image, UndistortKeyPoints, grid)
+extern "C" int psl_frame_import(pslfe_frame* f, int slot0, const PslKeyPoint* okps, const uint8_t* odesc, const int* ocounts, int ocap,
+                                int nframes);
+extern "C" int psl_frame_finish_stereo(pslfe_frame* f, int slot0, int nslots, int cols, int rows, const PslCamera* cam);
 
 #endif

@@ -143,6 +143,26 @@ private:
     const char* failed_ = nullptr;
 };
 
+// The image pyramid (mvImagePyramid) of an extractor's last batch, for pslfe_stereo.hip: level 0 of frame f at
+// img0 + f*fstride0 (the caller's input for a device batch, the handle's staging copy for the host entry points), level l >= 1
+// at pyr + f*pyr_fstride + off[l]; rows pitch[l] bytes apart (pitch[0] = stride0).
+struct PslOrbPyramid {
+    pslfe_ctx* ctx;
+    int nlevels, nframes, cap;          // cap: keypoint rows per frame of the result arrays
+    const PslKeyPoint* kps;
+    const uint8_t* desc;
+    const int* counts;
+    const uint8_t* img0;
+    size_t fstride0;
+    const uint8_t* pyr;
+    size_t pyr_fstride;
+    int w[PSLFE_MAX_LEVELS], h[PSLFE_MAX_LEVELS], pitch[PSLFE_MAX_LEVELS];
+    size_t off[PSLFE_MAX_LEVELS];
+    float scale[PSLFE_MAX_LEVELS], inv_scale[PSLFE_MAX_LEVELS];
+};
+// PSLFE_E_STATE before the first batch
+int pslfe_orb_internal_pyramid(pslfe_orb* orb, PslOrbPyramid* out);
+
 // at least `bytes` of pinned host memory owned by the context (valid until the next call that asks for more); nullptr on failure
 char* psl_host_stage(pslfe_ctx* ctx, size_t bytes);
 // start of a call: releases the previous call's fall-back blocks and grows the arena to what that call wanted (calls on a context are serialised)

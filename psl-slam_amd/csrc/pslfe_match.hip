@@ -23,16 +23,18 @@
 #include "match_kernels.h"
 
 // ---------------------------------------------------------------------------------------------
+// block b: frame b of (okps, odesc, ocounts) -> slot slot0 + b
 __global__ __launch_bounds__(256) void k_frame_import(FrameStore S, const PslKeyPoint* __restrict__ okps,
                                                        const uint8_t* __restrict__ odesc, const int* __restrict__ ocounts,
-                                                       int ocap, float minX, float minY, float invW, float invH) {
-    const int slot = blockIdx.x;
-    int n = ocounts[slot];
+                                                       int ocap, float minX, float minY, float invW, float invH, int slot0) {
+    const int slot = slot0 + blockIdx.x;
+    okps += (size_t)blockIdx.x * ocap; odesc += (size_t)blockIdx.x * ocap * 32; ocounts += blockIdx.x;
+    int n = ocounts[0];
     n = n < S.cap ? n : S.cap;
-    const uint32_t* sk = reinterpret_cast<const uint32_t*>(okps + (size_t)slot * ocap);
+    const uint32_t* sk = reinterpret_cast<const uint32_t*>(okps);
     uint32_t* dk = reinterpret_cast<uint32_t*>(S.kps + (size_t)slot * S.cap);
     for (int i = threadIdx.x; i < n * 7; i += 256) dk[i] = sk[i];
-    const uint32_t* sd = reinterpret_cast<const uint32_t*>(odesc + (size_t)slot * ocap * 32);
+    const uint32_t* sd = reinterpret_cast<const uint32_t*>(odesc);
     uint32_t* dd = reinterpret_cast<uint32_t*>(S.desc + (size_t)slot * S.cap * 32);
     for (int i = threadIdx.x; i < n * 8; i += 256) dd[i] = sd[i];
     float* ur = S.uright + (size_t)slot * S.cap;
@@ -105,6 +107,17 @@ __global__ __launch_bounds__(256) void k_frame_post_rgbd(FrameStore S, float* __
     kp->x = xu; kp->y = yu;
     mvDepth[(size_t)slot * S.cap + i] = dep;
     S.uright[(size_t)slot * S.cap + i] = ur;
+}
+
+// Frame::UndistortKeyPoints alone (the stereo constructor: mvuRight / mvDepth come from ComputeStereoMatches on the distorted
+// keypoints).  grid (ceil(cap/256), nframes).
+__global__ __launch_bounds__(256) void k_frame_undistort(FrameStore S, int slot0, PslCamera C) {
+    const int slot = slot0 + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S.meta[slot].n || C.k1 == 0.0f) return;
+    PslKeyPoint* kp = S.kps + (size_t)slot * S.cap + i;
+    float xu, yu;
+    psl_undistort_point((double)kp->x, (double)kp->y, C, &xu, &yu);
+    kp->x = xu; kp->y = yu;
 }
 
 // meta of slots slot0..slot0+nslots-1 <- grid geometry from the device-side bounds (src/Frame.cc:163-164)
@@ -655,6 +668,7 @@ int pslfe_frame_create(pslfe_ctx* ctx, int max_keypoints, int max_frames, pslfe_
     f->ctx = ctx; f->cap = max_keypoints; f->max_frames = max_frames;
     f->slot_set.assign(max_frames, 0);
     f->slot_depth.assign(max_frames, 0);
+    f->slot_stereo.assign(max_frames, 0);
     const size_t F = (size_t)max_frames, K = (size_t)max_keypoints;
     f->S.cap = max_keypoints;
     PslDeviceBuffers& m = f->mem;
@@ -727,6 +741,7 @@ int pslfe_frame_set(pslfe_frame* f, int slot, const PslKeyPoint* kps, const uint
     PSL_HIP(hipGetLastError());
     f->slot_set[slot] = 1;
     f->slot_depth[slot] = 0;
+    f->slot_stereo[slot] = 0;
     return PSLFE_OK;
 }
 
@@ -744,12 +759,12 @@ int pslfe_frame_set_from_orb(pslfe_frame* f, pslfe_orb* orb, float min_x, float 
     const float invW = (float)PSL_GRID_COLS / (float)(max_x - min_x), invH = (float)PSL_GRID_ROWS / (float)(max_y - min_y);
     {
         PSL_STAGE_BEGIN(f->ctx, "match.grid");
-        k_frame_import<<<nframes, 256, 0, st>>>(f->S, okps, odesc, ocnt, ocap, min_x, min_y, invW, invH);
+        k_frame_import<<<nframes, 256, 0, st>>>(f->S, okps, odesc, ocnt, ocap, min_x, min_y, invW, invH, 0);
         k_build_grid<<<nframes, 1024, 0, st>>>(f->S, 0);
         PSL_STAGE_END(f->ctx, "match.grid");
     }
     PSL_HIP(hipGetLastError());
-    for (int s = 0; s < nframes; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 0;
+    for (int s = 0; s < nframes; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 0, f->slot_stereo[s] = 0;
     return PSLFE_OK;
 }
 
@@ -778,7 +793,35 @@ static int frame_post_rgbd(pslfe_frame* f, int slot0, int nslots, const float* d
         PSL_STAGE_END(f->ctx, "match.grid");
     }
     PSL_HIP(hipGetLastError());
-    for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1;
+    for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1, f->slot_stereo[s] = 0;
+    return PSLFE_OK;
+}
+
+// The stereo constructor's frame part, for pslfe_stereo.hip (kernels cannot be launched across translation units).
+int psl_frame_import(pslfe_frame* f, int slot0, const PslKeyPoint* okps, const uint8_t* odesc, const int* ocounts, int ocap, int nframes) {
+    PSL_STAGE_BEGIN(f->ctx, "match.grid");
+    k_frame_import<<<nframes, 256, 0, f->ctx->stream>>>(f->S, okps, odesc, ocounts, ocap, 0.f, 0.f, 1.f, 1.f, slot0);
+    PSL_STAGE_END(f->ctx, "match.grid");
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+
+int psl_frame_finish_stereo(pslfe_frame* f, int slot0, int nslots, int cols, int rows, const PslCamera* cam) {
+    hipStream_t st = f->ctx->stream;
+    {
+        PSL_STAGE_BEGIN(f->ctx, "frame.stereo");
+        k_image_bounds<<<1, 64, 0, st>>>(*cam, cols, rows, f->d_bounds);
+        k_frame_meta_bounds<<<(nslots + 255) / 256, 256, 0, st>>>(f->S, slot0, nslots, f->d_bounds);
+        k_frame_undistort<<<dim3((f->cap + 255) / 256, nslots), 256, 0, st>>>(f->S, slot0, *cam);
+        PSL_STAGE_END(f->ctx, "frame.stereo");
+    }
+    {
+        PSL_STAGE_BEGIN(f->ctx, "match.grid");
+        k_build_grid<<<nslots, 1024, 0, st>>>(f->S, slot0);
+        PSL_STAGE_END(f->ctx, "match.grid");
+    }
+    PSL_HIP(hipGetLastError());
+    for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1, f->slot_stereo[s] = 1;
     return PSLFE_OK;
 }
 
@@ -821,7 +864,7 @@ int pslfe_frame_set_from_orb_rgbd(pslfe_frame* f, pslfe_orb* orb, const float* d
     PSL_HIP(hipSetDevice(f->ctx->device));
     {
         PSL_STAGE_BEGIN(f->ctx, "match.grid");
-        k_frame_import<<<nframes, 256, 0, f->ctx->stream>>>(f->S, okps, odesc, ocnt, ocap, 0.f, 0.f, 1.f, 1.f);
+        k_frame_import<<<nframes, 256, 0, f->ctx->stream>>>(f->S, okps, odesc, ocnt, ocap, 0.f, 0.f, 1.f, 1.f, 0);
         PSL_STAGE_END(f->ctx, "match.grid");
     }
     return frame_post_rgbd(f, 0, nframes, d_depth, width, height, width, (size_t)width * height, cam);

@@ -280,6 +280,22 @@ int pslfe_orb_internal_last(pslfe_orb* orb, const PslKeyPoint** kps, const uint8
     return PSLFE_OK;
 }
 
+int pslfe_orb_internal_pyramid(pslfe_orb* orb, PslOrbPyramid* out) {
+    PSL_REQUIRE(orb->last_nframes > 0, PSLFE_E_STATE, "no batch extracted yet");
+    memset(out, 0, sizeof(*out));
+    out->ctx = orb->ctx; out->nlevels = orb->nlevels; out->nframes = orb->last_nframes; out->cap = orb->P.out_cap;
+    out->kps = orb->d_kps; out->desc = orb->d_desc; out->counts = orb->d_counts;
+    out->img0 = orb->last_src.img0; out->fstride0 = orb->last_src.fstride0;
+    out->pyr = orb->last_src.pyr; out->pyr_fstride = orb->last_src.pyr_fstride;
+    for (int l = 0; l < orb->nlevels; ++l) {
+        out->w[l] = orb->P.lv[l].w; out->h[l] = orb->P.lv[l].h;
+        out->pitch[l] = l == 0 ? orb->last_src.stride0 : orb->P.lv[l].pitch;
+        out->off[l] = l == 0 ? 0 : orb->P.lv[l].img_off;
+        out->scale[l] = orb->scale[l]; out->inv_scale[l] = orb->invScale[l];
+    }
+    return PSLFE_OK;
+}
+
 extern "C" {
 
 int pslfe_orb_create(pslfe_ctx* ctx, int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST,

@@ -111,6 +111,19 @@ public:
         check(pslfe_frame_set_rgbd(h_, slot, keys.data(), descriptors.data(), (int)keys.size(), depth, cols, rows, strideFloats, &cam),
               "pslfe_frame_set_rgbd");
     }
+    // The stereo Frame constructor (src/Frame.cc:75-131: ComputeStereoMatches, UndistortKeyPoints, ComputeImageBounds,
+    // AssignFeaturesToGrid) for one rectified pair, after left(imLeft, ...) and right(imRight, ...) have run: the last frame of
+    // each extractor -> `slot`.  The two extractors are built with the same settings (src/Tracking.cc:128-129).
+    void setStereo(int slot, ORBextractor& left, ORBextractor& right, const PslCamera& cam) {
+        check(pslfe_frame_set_from_orb_stereo(h_, slot, left.get(), 0, right.get(), 0, 1, &cam), "pslfe_frame_set_from_orb_stereo");
+    }
+    // The same for nframes pairs of device batches: frame left0+p of `left`'s last batch and frame right0+p of `right`'s -> slot
+    // slot0+p (left and right may be one extractor that extracted both images of every pair).  Asynchronous; a device batch's input
+    // images must stay unchanged until the work has run (include/pslfe.h).
+    void setStereoDevice(int slot0, ORBextractor& left, int left0, ORBextractor& right, int right0, int nframes, const PslCamera& cam) {
+        check(pslfe_frame_set_from_orb_stereo(h_, slot0, left.get(), left0, right.get(), right0, nframes, &cam),
+              "pslfe_frame_set_from_orb_stereo");
+    }
     // mvKeysUn, mvDepth, mvuRight of a slot
     void fetch(int slot, std::vector<PslKeyPoint>& keysUn, std::vector<float>& depth, std::vector<float>& uRight, int capacity) {
         keysUn.resize(capacity); depth.resize(capacity); uRight.resize(capacity);

@@ -1,0 +1,130 @@
+// Sequential C++ restatement of Frame::ComputeStereoMatches (src/Frame.cc:1165-1340) under the conventions stated at
+// pslfe_frame_set_from_orb_stereo in include/pslfe.h (psl-slam_amd/csrc/stereo_kernels.h).  Test infrastructure: the tests build
+// it with g++ -O2 -ffp-contract=off into a shared library and compare the HIP kernels with it bit for bit.
+//
+// Inputs: the distorted left / right keypoints and descriptors, the two pyramids as one pointer, pitch, width and height per level,
+// the extractor's scale factors and the camera (mbf, fx).  Outputs per left keypoint: mvuRight, mvDepth and the two taps
+// (right index of the descriptor stage or -1, SAD minimum of an accepted keypoint or -1).
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "../include/pslfe.h"
+
+static int hamming(const uint8_t* a, const uint8_t* b) {
+    int d = 0;
+    for (int k = 0; k < 32; ++k) d += __builtin_popcount((unsigned)(a[k] ^ b[k]));
+    return d;
+}
+
+extern "C" int sr_stereo(const PslKeyPoint* kL, const uint8_t* dL, int nL, const PslKeyPoint* kR, const uint8_t* dR, int nR,
+                         const uint8_t* const* imL, const int* pitchL, const uint8_t* const* imR, const int* pitchR, const int* lw,
+                         const int* lh, const float* scale, const float* inv_scale, int nlevels, float bf, float fx, float* uright,
+                         float* depth, int32_t* tap_idx, int32_t* tap_sad) {
+    for (int i = 0; i < nL; ++i) uright[i] = -1.0f, depth[i] = -1.0f, tap_idx[i] = -1, tap_sad[i] = -1;
+    const int thOrbDist = (100 + 50) / 2;
+    const int nRows = lh[0];
+    std::vector<std::vector<int>> vRowIndices(nRows);
+    for (int iR = 0; iR < nR; ++iR) {
+        const PslKeyPoint& kp = kR[iR];
+        if (kp.octave < 0 || kp.octave >= nlevels) continue;
+        const float kpY = kp.y;
+        const float r = 2.0f * scale[kp.octave];
+        const int maxr = (int)ceilf(kpY + r);
+        const int minr = (int)floorf(kpY - r);
+        for (int yi = minr; yi <= maxr; ++yi)
+            if (yi >= 0 && yi < nRows) vRowIndices[yi].push_back(iR);   // rows outside the image dropped (convention)
+    }
+    const float mb = bf / fx;            // convention: minZ = mb = mbf/fx
+    const float minZ = mb;
+    const float minD = 0;
+    const float maxD = bf / minZ;
+    std::vector<std::pair<int, int>> vDistIdx;
+    for (int iL = 0; iL < nL; ++iL) {
+        const PslKeyPoint& kpL = kL[iL];
+        const int levelL = kpL.octave;
+        const float vL = kpL.y, uL = kpL.x;
+        if (!(vL >= 0.f && vL < (float)nRows) || levelL < 0 || levelL >= nlevels) continue;   // convention: no row, no candidates
+        const std::vector<int>& vCandidates = vRowIndices[(int)vL];
+        if (vCandidates.empty()) continue;
+        const float minU = uL - maxD;
+        const float maxU = uL - minD;
+        if (maxU < 0) continue;
+        int bestDist = 100;
+        int bestIdxR = 0;
+        for (size_t iC = 0; iC < vCandidates.size(); ++iC) {
+            const int iR = vCandidates[iC];
+            const PslKeyPoint& kpR = kR[iR];
+            if (kpR.octave < levelL - 1 || kpR.octave > levelL + 1) continue;
+            const float uR = kpR.x;
+            if (uR >= minU && uR <= maxU) {
+                const int dist = hamming(dL + (size_t)iL * 32, dR + (size_t)iR * 32);
+                if (dist < bestDist) { bestDist = dist; bestIdxR = iR; }
+            }
+        }
+        if (bestDist >= thOrbDist) continue;
+        tap_idx[iL] = bestIdxR;
+        const float uR0 = kR[bestIdxR].x;
+        const float scaleFactor = inv_scale[levelL];
+        const float scaleduL = roundf(kpL.x * scaleFactor);
+        const float scaledvL = roundf(kpL.y * scaleFactor);
+        const float scaleduR0 = roundf(uR0 * scaleFactor);
+        const int w = 5, L = 5;
+        const float iniu = scaleduR0 + L - w;
+        const float endu = scaleduR0 + L + w + 1;
+        const int cols = lw[levelL], rows = lh[levelL];
+        if (iniu < 0 || endu >= cols) continue;
+        // convention: both windows inside the level image
+        if (!(scaledvL >= 5.f && scaledvL + 5.f < (float)rows && scaleduL >= 5.f && scaleduL + 5.f < (float)cols && scaleduR0 >= 10.f &&
+              scaleduR0 + 10.f < (float)cols))
+            continue;
+        const int y0 = (int)scaledvL, xl = (int)scaleduL, xr = (int)scaleduR0;
+        const uint8_t* IL = imL[levelL];
+        const uint8_t* IR = imR[levelL];
+        const int pl = pitchL[levelL], pr = pitchR[levelL];
+        const int cL = IL[(size_t)y0 * pl + xl];
+        int bestSad = INT_MAX, bestincR = 0;
+        int vDists[2 * 5 + 1];
+        for (int incR = -L; incR <= L; ++incR) {
+            const int cR = IR[(size_t)y0 * pr + xr + incR];
+            int dist = 0;
+            for (int dy = -w; dy <= w; ++dy)
+                for (int dx = -w; dx <= w; ++dx)
+                    dist += abs(((int)IL[(size_t)(y0 + dy) * pl + xl + dx] - cL) - ((int)IR[(size_t)(y0 + dy) * pr + xr + incR + dx] - cR));
+            if (dist < bestSad) { bestSad = dist; bestincR = incR; }
+            vDists[L + incR] = dist;
+        }
+        if (bestincR == -L || bestincR == L) continue;
+        const float dist1 = (float)vDists[L + bestincR - 1];
+        const float dist2 = (float)vDists[L + bestincR];
+        const float dist3 = (float)vDists[L + bestincR + 1];
+        const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
+        if (deltaR < -1 || deltaR > 1) continue;
+        float bestuR = scale[levelL] * ((float)scaleduR0 + (float)bestincR + deltaR);
+        float disparity = (uL - bestuR);
+        if (disparity >= minD && disparity < maxD) {
+            if (disparity <= 0) {
+                disparity = 0.01;
+                bestuR = uL - 0.01;
+            }
+            depth[iL] = bf / disparity;
+            uright[iL] = bestuR;
+            tap_sad[iL] = bestSad;
+            vDistIdx.push_back(std::make_pair(bestSad, iL));
+        }
+    }
+    if (vDistIdx.empty()) return 0;   // convention: nothing accepted, nothing filtered
+    std::sort(vDistIdx.begin(), vDistIdx.end());
+    const float median = vDistIdx[vDistIdx.size() / 2].first;
+    const float thDist = 1.5f * 1.4f * median;
+    for (int i = (int)vDistIdx.size() - 1; i >= 0; --i) {
+        if (vDistIdx[i].first < thDist) break;
+        uright[vDistIdx[i].second] = -1;
+        depth[vDistIdx[i].second] = -1;
+    }
+    return (int)vDistIdx.size();
+}
