@@ -330,6 +330,14 @@ int pslfe_frame_set_from_orb_rgbd(pslfe_frame* f, pslfe_orb* orb, const float* d
  *    no match - none of them occurs for keypoints of the extractor. */
 int pslfe_frame_set_from_orb_stereo(pslfe_frame* f, int slot0, pslfe_orb* left, int left0, pslfe_orb* right, int right0,
                                     int nframes, const PslCamera* cam);
+/* == The monocular Frame constructor src/Frame.cc:213-267 for frames first..first+nframes-1 of orb's last batch -> slots
+ *    slot0..slot0+nframes-1: UndistortKeyPoints :1062-1092 (skipped when k1 == 0, as the reference does), mvuRight = mvDepth = -1
+ *    (:241-243), ComputeImageBounds :1135-1168 (first-frame statics, as the RGB-D and stereo paths keep them: they depend on the
+ *    camera and the image size only, so a frame without keypoints - for which the reference returns before both - changes
+ *    nothing) and AssignFeaturesToGrid :269-284 on the undistorted points.  A frame with 0 keypoints gives a slot with n = 0 and an
+ *    empty grid.  The slot then holds mvKeysUn / mvDepth / mvuRight (pslfe_frame_fetch).  Extractor capacity <= f's
+ *    (PSLFE_E_CAPACITY).  Asynchronous on f's context stream. */
+int pslfe_frame_set_from_orb_mono(pslfe_frame* f, int slot0, pslfe_orb* orb, int first, int nframes, const PslCamera* cam);
 /* Tap per left keypoint of a stereo slot: idx_right = right keypoint chosen by the descriptor stage (-1: none below
  * thOrbDist), sad = the SAD minimum of the window sweep (-1: skipped or rejected before the median filter).  *n = the slot's
  * keypoint count; either array may be NULL.  PSLFE_E_STATE if the slot was not set by pslfe_frame_set_from_orb_stereo. */
@@ -390,6 +398,35 @@ int pslfe_orb_search_by_bow(pslfe_frame* f, int slot, const int32_t* fidx, int n
 int pslfe_orb_search_by_projection_last_device(pslfe_frame* cur, int slot0, int npairs, const PslProjQuery* d_queries,
                                                const uint8_t* d_qdesc, const int32_t* d_nq, int qstride,
                                                int check_orientation, int32_t* d_match, int32_t* d_nmatches);
+
+/* == ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) src/ORBmatcher.cc:405-520 with
+ *    mfNNratio = nnratio, mbCheckOrientation = check_orientation (Tracking::MonocularInitialization: ORBmatcher(0.9, true),
+ *    windowSize 100, src/Tracking.cc:696).  F1 = slot slot1 of f1, F2 = slot slot2 of f2 (f1 == f2 allowed; one context).
+ *    Reproduced exactly:
+ *    - queries: the F1 keypoints of octave 0 (:421-423), in ascending index order;
+ *    - candidates: F2.GetFeaturesInArea(prev[i1].x, prev[i1].y, (float)window, 0, 0) src/Frame.cc:985-1038 (window centred at
+ *      prev, octave exactly 0, |dx| < r and |dy| < r on mvKeysUn, cells ix outer / iy inner, indices ascending; a cell range
+ *      outside the grid is empty);
+ *    - a candidate whose vMatchedDistance is <= its distance is skipped (:442-443), for the best and the second best alike;
+ *      best = the first strict minimum in visiting order, bestDist2 = the second smallest surviving distance (ties included,
+ *      INT_MAX with one survivor); accepted when bestDist <= TH_LOW (50) and bestDist < (float)bestDist2 * nnratio (float
+ *      multiply, no contraction);
+ *    - an accepted query takes its keypoint from an earlier query for good (:462-466): the earlier one gets -1 and is never
+ *      searched again, but its rotHist entry stays and counts in ComputeThreeMaxima :1601-1645;
+ *    - rotation histogram (:470-508): rot = angle1 - angle2 (+360 if negative), bin = round(rot * (1.0f/30)); only still
+ *      matched queries in non-maximum bins are cleared.
+ *    Outputs: matches12[i] for every F1 keypoint (-1: none), *nmatches = the return value, prev_matched[i] = F2 mvKeysUn of
+ *    matches12[i] where it is >= 0; every other prev row keeps its value.  prev_matched: host [n1][2], in/out; matches12: host
+ *    [n1].  Synchronous. */
+int pslfe_orb_search_for_initialization(pslfe_frame* f1, int slot1, pslfe_frame* f2, int slot2, float* prev_matched, int window,
+                                        float nnratio, int check_orientation, int32_t* matches12, int* nmatches);
+/* Batched, HBM-resident form: pair p has F1 = f1 slot slot1[p], F2 = f2 slot slot2[p] (host int arrays), its own prev rows
+ * d_prev + p*prev_stride*2 (float, in/out) and matches d_matches12 + p*prev_stride; d_nmatches[p].  prev_stride >= f1's capacity
+ * (PSLFE_E_INVALID).  Pairs are independent.  Returns once the slot tables have been copied; the matching is queued on the
+ * context's stream. */
+int pslfe_orb_search_for_initialization_device(pslfe_frame* f1, const int32_t* slot1, pslfe_frame* f2, const int32_t* slot2, int npairs,
+                                               float* d_prev, int prev_stride, int window, float nnratio, int check_orientation,
+                                               int32_t* d_matches12, int32_t* d_nmatches);
 
 /* ---- Projection of 3-D points into a frame: the part of both SearchByProjection variants before the window search.
  *

@@ -354,6 +354,13 @@ class FrameGrid:
         _check(lib().pslfe_frame_set_from_orb_stereo(self._h, C.c_int(slot0), left._h, C.c_int(left0), right._h, C.c_int(right0),
                                                      C.c_int(nframes), _ptr(cam)), "pslfe_frame_set_from_orb_stereo")
 
+    def set_from_orb_mono(self, slot0, orb, first, nframes, cam):
+        """The monocular Frame constructor (src/Frame.cc:213-267: UndistortKeyPoints, mvuRight = mvDepth = -1, ComputeImageBounds,
+        AssignFeaturesToGrid) for frames first..first+nframes-1 of `orb`'s last batch -> slots slot0.., HBM to HBM.  Asynchronous."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_frame_set_from_orb_mono(self._h, C.c_int(slot0), orb._h, C.c_int(first), C.c_int(nframes), _ptr(cam)),
+               "pslfe_frame_set_from_orb_mono")
+
     def debug_stereo(self, slot):
         """Taps of a stereo slot: (right index of the descriptor stage or -1, SAD minimum of an accepted keypoint or -1)."""
         idx = np.zeros(self.cap, np.int32)
@@ -486,6 +493,19 @@ class ORBmatcher:
         return self._run(lib().pslfe_orb_search_by_projection_map, frame, slot, queries, qdesc, taken,
                          C.c_float(self.mfNNratio))
 
+    def SearchForInitialization(self, f1, slot1, f2, slot2, prev_matched, window=100):
+        """SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) src/ORBmatcher.cc:405: F1 = slot1 of f1, F2 =
+        slot2 of f2.  prev_matched: float32 [n1, 2] (n1 = F1's keypoint count), updated in place.  -> (nmatches, matches12)."""
+        if not (isinstance(prev_matched, np.ndarray) and prev_matched.dtype == np.float32 and prev_matched.flags.c_contiguous):
+            raise TypeError("prev_matched must be a C-contiguous float32 array [n1, 2] (it is updated in place)")
+        n1 = prev_matched.size // 2
+        m12 = np.full(max(n1, 1), -1, np.int32)
+        nm = C.c_int()
+        _check(lib().pslfe_orb_search_for_initialization(f1._h, C.c_int(slot1), f2._h, C.c_int(slot2), _ptr(prev_matched), C.c_int(window),
+                                                         C.c_float(self.mfNNratio), C.c_int(1 if self.mbCheckOrientation else 0),
+                                                         _ptr(m12), C.byref(nm)), "pslfe_orb_search_for_initialization")
+        return nm.value, m12[:n1]
+
 
 def hamming_knn2(q, t, ctx=None):
     """cv::BFMatcher(NORM_HAMMING).knnMatch(q, t, 2) -> (idx[nq,2], dist[nq,2])."""
@@ -544,6 +564,20 @@ def search_by_projection_last_device(frame, slot0, npairs, d_queries, d_qdesc, d
         frame._h, C.c_int(slot0), C.c_int(npairs), C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_nq),
         C.c_int(qstride), C.c_int(1 if check_orientation else 0), C.c_void_p(d_match), C.c_void_p(d_nmatches)),
         "pslfe_orb_search_by_projection_last_device")
+
+
+def search_for_initialization_device(f1, slot1, f2, slot2, d_prev, prev_stride, d_matches12, d_nmatches, window=100, nnratio=0.9,
+                                     check_orientation=True):
+    """Batched HBM-resident SearchForInitialization: pair p = (f1 slot slot1[p], f2 slot slot2[p]) with prev rows
+    d_prev + p*prev_stride*2 (float32, in/out), matches d_matches12 + p*prev_stride and d_nmatches[p]; d_* are device addresses."""
+    s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1)
+    s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+    if len(s1) != len(s2):
+        raise ValueError("slot1 and slot2 differ in length")
+    _check(lib().pslfe_orb_search_for_initialization_device(
+        f1._h, _ptr(s1), f2._h, _ptr(s2), C.c_int(len(s1)), C.c_void_p(d_prev), C.c_int(prev_stride), C.c_int(window),
+        C.c_float(nnratio), C.c_int(1 if check_orientation else 0), C.c_void_p(d_matches12), C.c_void_p(d_nmatches)),
+        "pslfe_orb_search_for_initialization_device")
 
 
 def project_frustum(Tcw, mp, mpdesc, cam, scale_factors, log_scale_factor, view_cos_limit, th, bounds, ctx=None):

@@ -120,6 +120,19 @@ __global__ __launch_bounds__(256) void k_frame_undistort(FrameStore S, int slot0
     kp->x = xu; kp->y = yu;
 }
 
+// The monocular constructor's tail (src/Frame.cc:238-245): UndistortKeyPoints, mvuRight = mvDepth = -1 (k_frame_import has
+// set mvuRight).  grid (ceil(cap/256), nframes).
+__global__ __launch_bounds__(256) void k_frame_post_mono(FrameStore S, float* __restrict__ mvDepth, int slot0, PslCamera C) {
+    const int slot = slot0 + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S.meta[slot].n) return;
+    mvDepth[(size_t)slot * S.cap + i] = -1.f;
+    if (C.k1 == 0.0f) return;
+    PslKeyPoint* kp = S.kps + (size_t)slot * S.cap + i;
+    float xu, yu;
+    psl_undistort_point((double)kp->x, (double)kp->y, C, &xu, &yu);
+    kp->x = xu; kp->y = yu;
+}
+
 // meta of slots slot0..slot0+nslots-1 <- grid geometry from the device-side bounds (src/Frame.cc:163-164)
 __global__ void k_frame_meta_bounds(FrameStore S, int slot0, int nslots, const float* __restrict__ bounds) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -822,6 +835,41 @@ int psl_frame_finish_stereo(pslfe_frame* f, int slot0, int nslots, int cols, int
     }
     PSL_HIP(hipGetLastError());
     for (int s = slot0; s < slot0 + nslots; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1, f->slot_stereo[s] = 1;
+    return PSLFE_OK;
+}
+
+int pslfe_frame_set_from_orb_mono(pslfe_frame* f, int slot0, pslfe_orb* orb, int first, int nframes, const PslCamera* cam) {
+    const char* who = "pslfe_frame_set_from_orb_mono";
+    PSL_REQUIRE(f && orb && cam, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PslOrbPyramid P;
+    int rc = pslfe_orb_internal_pyramid(orb, &P);
+    if (rc) return rc;
+    PSL_REQUIRE(P.ctx == f->ctx, PSLFE_E_INVALID, "%s: handles belong to different contexts", who);
+    PSL_REQUIRE(nframes >= 1 && first >= 0 && first + nframes <= P.nframes, PSLFE_E_INVALID, "%s: frames %d..%d of %d", who, first,
+                first + nframes - 1, P.nframes);
+    PSL_REQUIRE(slot0 >= 0, PSLFE_E_INVALID, "%s: slot %d", who, slot0);
+    PSL_REQUIRE(slot0 + nframes <= f->max_frames, PSLFE_E_CAPACITY, "%s: slots %d..%d, %d slots", who, slot0, slot0 + nframes - 1, f->max_frames);
+    PSL_REQUIRE(P.cap <= f->cap, PSLFE_E_CAPACITY, "%s: extractor capacity %d > frame capacity %d", who, P.cap, f->cap);
+    PSL_HIP(hipSetDevice(f->ctx->device));
+    if ((rc = psl_frame_import(f, slot0, P.kps + (size_t)first * P.cap, P.desc + (size_t)first * P.cap * 32, P.counts + first, P.cap, nframes)))
+        return rc;
+    hipStream_t st = f->ctx->stream;
+    {
+        // ComputeImageBounds depends on the camera and the image size only, so every slot of the call gets the first non-empty
+        // frame's bounds; a slot without keypoints keeps them too and has an empty grid
+        PSL_STAGE_BEGIN(f->ctx, "frame.mono");
+        k_image_bounds<<<1, 64, 0, st>>>(*cam, P.w[0], P.h[0], f->d_bounds);
+        k_frame_meta_bounds<<<(nframes + 255) / 256, 256, 0, st>>>(f->S, slot0, nframes, f->d_bounds);
+        k_frame_post_mono<<<dim3((f->cap + 255) / 256, nframes), 256, 0, st>>>(f->S, f->d_depth, slot0, *cam);
+        PSL_STAGE_END(f->ctx, "frame.mono");
+    }
+    {
+        PSL_STAGE_BEGIN(f->ctx, "match.grid");
+        k_build_grid<<<nframes, 1024, 0, st>>>(f->S, slot0);
+        PSL_STAGE_END(f->ctx, "match.grid");
+    }
+    PSL_HIP(hipGetLastError());
+    for (int s = slot0; s < slot0 + nframes; ++s) f->slot_set[s] = 1, f->slot_depth[s] = 1, f->slot_stereo[s] = 0;
     return PSLFE_OK;
 }
 

@@ -124,6 +124,11 @@ public:
         check(pslfe_frame_set_from_orb_stereo(h_, slot0, left.get(), left0, right.get(), right0, nframes, &cam),
               "pslfe_frame_set_from_orb_stereo");
     }
+    // The monocular Frame constructor (src/Frame.cc:213-267: UndistortKeyPoints, mvuRight = mvDepth = -1, ComputeImageBounds,
+    // AssignFeaturesToGrid) for frames first..first+nframes-1 of `orb`'s last batch -> slots slot0..  Asynchronous.
+    void setMono(int slot0, ORBextractor& orb, int first, int nframes, const PslCamera& cam) {
+        check(pslfe_frame_set_from_orb_mono(h_, slot0, orb.get(), first, nframes, &cam), "pslfe_frame_set_from_orb_mono");
+    }
     // mvKeysUn, mvDepth, mvuRight of a slot
     void fetch(int slot, std::vector<PslKeyPoint>& keysUn, std::vector<float>& depth, std::vector<float>& uRight, int capacity) {
         keysUn.resize(capacity); depth.resize(capacity); uRight.resize(capacity);
@@ -228,6 +233,26 @@ public:
         check(pslfe_orb_search_by_projection_map_device(cur.get(), slot0, npairs, d_queries, d_qdesc, d_nq, qstride, d_taken, mfNNratio,
                                                         d_match, d_nmatches),
               "pslfe_orb_search_by_projection_map_device");
+    }
+    // SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize), src/ORBmatcher.cc:405: F1 = slot1 of f1, F2 = slot2
+    // of f2; vbPrevMatched as [n1][2] floats (updated in place), n1 = F1's keypoint count.  Returns nmatches.
+    int SearchForInitialization(FrameGrid& f1, int slot1, FrameGrid& f2, int slot2, std::vector<float>& vbPrevMatched,
+                                std::vector<int32_t>& vnMatches12, int windowSize = 10) {
+        vnMatches12.assign(vbPrevMatched.size() / 2, -1);
+        int nm = 0;
+        check(pslfe_orb_search_for_initialization(f1.get(), slot1, f2.get(), slot2, vbPrevMatched.data(), windowSize, mfNNratio,
+                                                  mbCheckOrientation ? 1 : 0, vnMatches12.data(), &nm),
+              "pslfe_orb_search_for_initialization");
+        return nm;
+    }
+    // Batched, HBM-resident SearchForInitialization: pair p = (f1 slot slot1[p], f2 slot slot2[p]) with prev rows
+    // d_prev + p*prevStride*2, matches d_matches12 + p*prevStride, count d_nmatches[p] (device memory).
+    void SearchForInitializationDevice(FrameGrid& f1, const std::vector<int32_t>& slot1, FrameGrid& f2, const std::vector<int32_t>& slot2,
+                                       float* d_prev, int prevStride, int windowSize, int32_t* d_matches12, int32_t* d_nmatches) {
+        check(slot1.size() == slot2.size() ? PSLFE_OK : PSLFE_E_INVALID, "SearchForInitializationDevice: slot tables differ in length");
+        check(pslfe_orb_search_for_initialization_device(f1.get(), slot1.data(), f2.get(), slot2.data(), (int)slot1.size(), d_prev, prevStride,
+                                                         windowSize, mfNNratio, mbCheckOrientation ? 1 : 0, d_matches12, d_nmatches),
+              "pslfe_orb_search_for_initialization_device");
     }
     // DescriptorDistance, src/ORBmatcher.cc:1647-1663 (host helper, same SWAR popcount)
     static int DescriptorDistance(const uint8_t* a, const uint8_t* b) {
