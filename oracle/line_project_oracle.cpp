@@ -2,7 +2,7 @@
 // written from the reference's code (src/Frame.cc:828-904; add_src/LSDmatcher.cpp:112-155, 260-289, 986-992;
 // add_src/MapLine.cpp:369-390) and the conventions stated in include/pslfe.h: float 3x3 * 3x1 products as double sums rounded
 // once, OM = 0.5f*SP + 0.5f*EP - mOw in float, cv::norm / dot in double, the correctly rounded logf of PredictScale, and
-// "not in view" for z == 0 and NaN.  Test infrastructure: the tests build it with g++ -ffp-contract=off into a shared library.
+// "not in view" for z == 0 and NaN.  Test infrastructure: part of the oracle library.
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
@@ -11,23 +11,13 @@
 #include "../include/pslfe.h"
 #define PSL_F64_QUAL static inline
 #include "../psl-slam_amd/csrc/psl_f64math.h"
-
-static float affine_row(float m0, float m1, float m2, float x0, float x1, float x2, float t) {
-    double a = (double)m0 * (double)x0;
-    a += (double)m1 * (double)x1;
-    a += (double)m2 * (double)x2;
-    a += (double)t;
-    return (float)a;
-}
+#include "psl_oracle.h"
+#include "psl_oracle_internal.h"
 
 // mRcw * x + mtcw
-static void affine(const PslPose& T, const float* x, float* out) {
-    for (int r = 0; r < 3; ++r) out[r] = affine_row(T.R[3 * r], T.R[3 * r + 1], T.R[3 * r + 2], x[0], x[1], x[2], T.t[r]);
-}
+static void affine(const PslPose& T, const float* x, float* out) { pso::affine(T.R, x, T.t, out); }
 // mOw = -mRcw.t() * mtcw
-static void centre(const PslPose& T, float* c) {
-    for (int r = 0; r < 3; ++r) c[r] = -affine_row(T.R[r], T.R[3 + r], T.R[6 + r], T.t[0], T.t[1], T.t[2], 0.f);
-}
+static void centre(const PslPose& T, float* c) { pso::centre(T.R, T.t, c); }
 
 // MapLine::PredictScale: ceil(log(ratio) / logScaleFactor), float.  how: 0 = the library's logf ((float)psl_log), 1 = the host's
 // logf, 2 = the point projections' double path ceil(psl_log(ratio) / (double)lsf).

@@ -15,24 +15,15 @@
 #include <vector>
 
 #include "psl_oracle.h"
+#include "psl_oracle_internal.h"
 
 namespace {
 
+using pso::descriptor_distance;
+using pso::three_maxima;
+
 const int GRID_COLS = 64, GRID_ROWS = 48;  // include/Frame.h:45-46
 const int TH_HIGH = 100, HISTO_LENGTH = 30;
-
-int descriptor_distance(const uint8_t* a, const uint8_t* b) {
-    const int32_t* pa = (const int32_t*)a;
-    const int32_t* pb = (const int32_t*)b;
-    int dist = 0;
-    for (int i = 0; i < 8; i++, pa++, pb++) {
-        unsigned int v = *pa ^ *pb;
-        v = v - ((v >> 1) & 0x55555555);
-        v = (v & 0x33333333) + ((v >> 2) & 0x33333333);
-        dist += (((v + (v >> 4)) & 0xF0F0F0F) * 0x1010101) >> 24;
-    }
-    return dist;
-}
 
 struct Grid {
     float minX, minY, maxX, maxY, invW, invH;
@@ -77,18 +68,6 @@ struct Grid {
         return out;
     }
 };
-
-void three_maxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < L; i++) {
-        const int s = (int)histo[i].size();
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
 
 }  // namespace
 

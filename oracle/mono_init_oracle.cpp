@@ -1,7 +1,7 @@
 // Sequential restatement of the monocular initialiser's matcher, in this project's words: the frame grid of the frame store
 // (64 x 48 cells, CSR in the order the window search visits them) and SearchForInitialization on it, one query after the
-// other.  Test infrastructure for tests/test_mono_init_*.py and tools/bench_mono_init.py; build with -ffp-contract=off so
-// every float operation is rounded on its own, as on the device.
+// other.  Test infrastructure for tests/test_mono_init_*.py and tools/bench_mono_init.py, part of the oracle library: built with
+// -ffp-contract=off so every float operation is rounded on its own, as on the device.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,11 +10,10 @@
 #include <climits>
 #include <vector>
 
+#include "psl_oracle.h"
+#include "psl_oracle_internal.h"
+
 namespace {
-struct Kp {
-    float x, y, size, angle, response;
-    int32_t octave, class_id;
-};
 
 constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows, kHisto = 30, kThLow = 50;
 
@@ -23,27 +22,19 @@ struct Grid {
     std::vector<int> start, idx;   // CSR, cell = ix * 48 + iy
 };
 
-Grid make_grid(const Kp* k, int n, const float* b) {
+Grid make_grid(const PsoKeyPoint* k, int n, const float* b) {
     Grid g;
     g.minX = b[0]; g.minY = b[1];
     g.invW = (float)kCols / (b[2] - b[0]);
     g.invH = (float)kRows / (b[3] - b[1]);
-    std::vector<std::vector<int>> cell(kCells);
-    for (int i = 0; i < n; ++i) {
-        const int px = (int)roundf((k[i].x - g.minX) * g.invW), py = (int)roundf((k[i].y - g.minY) * g.invH);
-        if (px < 0 || px >= kCols || py < 0 || py >= kRows) continue;
-        cell[px * kRows + py].push_back(i);
-    }
     g.start.assign(kCells + 1, 0);
-    for (int c = 0; c < kCells; ++c) {
-        g.start[c + 1] = g.start[c] + (int)cell[c].size();
-        g.idx.insert(g.idx.end(), cell[c].begin(), cell[c].end());
-    }
+    g.idx.resize(n > 0 ? n : 1);
+    g.idx.resize(pso_grid_build(k, n, b[0], b[1], b[2], b[3], g.start.data(), g.idx.data()));
     return g;
 }
 
 // the octave-0 keypoints of the window of radius r around (x, y), in visiting order
-void window0(const Grid& g, const Kp* k, float x, float y, float r, std::vector<int>& out) {
+void window0(const Grid& g, const PsoKeyPoint* k, float x, float y, float r, std::vector<int>& out) {
     out.clear();
     const int x0 = std::max(0, (int)floorf((x - g.minX - r) * g.invW));
     const int x1 = std::min(kCols - 1, (int)ceilf((x - g.minX + r) * g.invW));
@@ -53,35 +44,24 @@ void window0(const Grid& g, const Kp* k, float x, float y, float r, std::vector<
     for (int ix = x0; ix <= x1; ++ix)
         for (int iy = y0; iy <= y1; ++iy)
             for (int p = g.start[ix * kRows + iy]; p < g.start[ix * kRows + iy + 1]; ++p) {
-                const Kp& c = k[g.idx[p]];
+                const PsoKeyPoint& c = k[g.idx[p]];
                 if (c.octave != 0) continue;
                 if (fabsf(c.x - x) < r && fabsf(c.y - y) < r) out.push_back(g.idx[p]);
             }
-}
-
-int hamming(const uint8_t* a, const uint8_t* b) {
-    int d = 0;
-    for (int i = 0; i < 32; ++i) d += __builtin_popcount((unsigned)(a[i] ^ b[i]));
-    return d;
 }
 }  // namespace
 
 extern "C" {
 
 // CSR of the grid of n keypoints with bounds {minX, minY, maxX, maxY}: start[64*48+1], idx[n]; returns the entry count
-int mr_grid(const void* kps, int n, const float* bounds, int32_t* start, int32_t* idx) {
-    const Grid g = make_grid(static_cast<const Kp*>(kps), n, bounds);
-    memcpy(start, g.start.data(), sizeof(int) * (kCells + 1));
-    if (!g.idx.empty()) memcpy(idx, g.idx.data(), sizeof(int) * g.idx.size());
-    return (int)g.idx.size();
+int mr_grid(const PsoKeyPoint* kps, int n, const float* bounds, int32_t* start, int32_t* idx) {
+    return pso_grid_build(kps, n, bounds[0], bounds[1], bounds[2], bounds[3], start, idx);
 }
 
 // SearchForInitialization.  prev: [n1][2] in/out; m12: [n1] out; accepted: [n1] out or NULL (the keypoint a query accepted,
 // also when a later query took it; -1 if it never accepted); returns the match count.
-int mr_search(const void* kps1, const uint8_t* desc1, int n1, const void* kps2, const uint8_t* desc2, int n2, const float* bounds2,
-              float* prev, int window, float nnratio, int check_ori, int32_t* m12, int32_t* accepted) {
-    const Kp* k1 = static_cast<const Kp*>(kps1);
-    const Kp* k2 = static_cast<const Kp*>(kps2);
+int mr_search(const PsoKeyPoint* k1, const uint8_t* desc1, int n1, const PsoKeyPoint* k2, const uint8_t* desc2, int n2,
+              const float* bounds2, float* prev, int window, float nnratio, int check_ori, int32_t* m12, int32_t* accepted) {
     const Grid g = make_grid(k2, n2, bounds2);
     const float r = (float)window;
     std::vector<int> best_of(n2, INT_MAX), owner(n2, -1), took(n1, -1), bin(n1, -1), cand;
@@ -92,7 +72,7 @@ int mr_search(const void* kps1, const uint8_t* desc1, int n1, const void* kps2, 
         window0(g, k2, prev[2 * q], prev[2 * q + 1], r, cand);
         int d1 = INT_MAX, d2 = INT_MAX, pick = -1;
         for (int c : cand) {
-            const int d = hamming(desc1 + 32 * (size_t)q, desc2 + 32 * (size_t)c);
+            const int d = pso::descriptor_distance(desc1 + 32 * (size_t)q, desc2 + 32 * (size_t)c);
             if (best_of[c] <= d) continue;            // a better match holds c already
             if (d < d1) { d2 = d1; d1 = d; pick = c; }
             else if (d < d2) d2 = d;
@@ -113,15 +93,8 @@ int mr_search(const void* kps1, const uint8_t* desc1, int n1, const void* kps2, 
         }
     }
     if (check_ori) {
-        int m1 = 0, m2 = 0, m3 = 0, b1 = -1, b2 = -1, b3 = -1;
-        for (int b = 0; b < kHisto; ++b) {
-            const int s = hist[b];
-            if (s > m1) { m3 = m2; m2 = m1; m1 = s; b3 = b2; b2 = b1; b1 = b; }
-            else if (s > m2) { m3 = m2; m2 = s; b3 = b2; b2 = b; }
-            else if (s > m3) { m3 = s; b3 = b; }
-        }
-        if (m2 < 0.1f * (float)m1) b2 = b3 = -1;
-        else if (m3 < 0.1f * (float)m1) b3 = -1;
+        int b1 = -1, b2 = -1, b3 = -1;
+        pso::three_maxima(hist.data(), kHisto, b1, b2, b3);
         for (int q = 0; q < n1; ++q)
             if (m12[q] >= 0 && bin[q] != b1 && bin[q] != b2 && bin[q] != b3) m12[q] = -1;
     }

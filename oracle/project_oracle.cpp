@@ -1,7 +1,7 @@
 // Sequential C++ restatement of the projection entry points of include/pslfe.h (psl-slam_amd/csrc/pslfe_project.hip), written
 // from the reference's loops (src/ORBmatcher.cc:45-70, 1338-1390; src/Frame.cc:927-983, 1365-1379; src/Tracking.cc:1052-1104;
-// src/MapPoint.cc:402-416) and the arithmetic conventions stated in include/pslfe.h.  Test infrastructure: the tests build it
-// with g++ -ffp-contract=off into a shared library and compare the HIP kernels with it field by field.
+// src/MapPoint.cc:402-416) and the arithmetic conventions stated in include/pslfe.h.  Test infrastructure: part of the oracle
+// library; the tests compare the HIP kernels with it field by field.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -13,23 +13,12 @@
 #include "../include/pslfe.h"
 #define PSL_F64_QUAL static inline
 #include "../psl-slam_amd/csrc/psl_f64math.h"
+#include "psl_oracle.h"
+#include "psl_oracle_internal.h"
 
-static float affine_row(float m0, float m1, float m2, float x0, float x1, float x2, float t) {
-    double a = (double)m0 * (double)x0;
-    a += (double)m1 * (double)x1;
-    a += (double)m2 * (double)x2;
-    a += (double)t;
-    return (float)a;
-}
-
-// cv::Mat(R) * x + t
-static void affine(const float* R, const float* x, const float* t, float* out) {
-    for (int r = 0; r < 3; ++r) out[r] = affine_row(R[3 * r], R[3 * r + 1], R[3 * r + 2], x[0], x[1], x[2], t[r]);
-}
+using pso::affine;
 // -R.t() * t
-static void centre(const PslPose& T, float* c) {
-    for (int r = 0; r < 3; ++r) c[r] = -affine_row(T.R[r], T.R[3 + r], T.R[6 + r], T.t[0], T.t[1], T.t[2], 0.f);
-}
+static void centre(const PslPose& T, float* c) { pso::centre(T.R, T.t, c); }
 
 static int predict_level(float ratio, float log_scale_factor, int nlevels, int host_log) {
     if (!(ratio > 0.f)) return 0;

@@ -155,6 +155,49 @@ int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const doub
                           double* le_l, int cap);
 int pso_glibc_rand(uint32_t seed, int n, int32_t* out);
 
+/* The sequential checkers of the device projections, the stereo constructor and the monocular initialiser.  Their PODs are the
+   product's own (include/pslfe.h); only the sources that define these entry points include that header. */
+struct PslKeyPoint; struct PslKeyLine; struct PslCamera; struct PslPose; struct PslLastPoint; struct PslMapPointGeom;
+struct PslProjQuery; struct PslMapLineGeom; struct PslLastLine; struct PslLineQuery;
+
+/* project_oracle.cpp: pslfe_orb_project_last / _frustum */
+void pr_sizes(int32_t* out);
+int pr_vo_select(const float* depth, int n, float th_depth, uint8_t* sel);
+long pr_level_sweep(float lo, float hi, float log_scale_factor, int nlevels, long* nsamples);
+int pr_predict_level(float ratio, float log_scale_factor, int nlevels);
+int pr_project_last(const struct PslKeyPoint* kps, const uint8_t* desc, const float* depth, int n, const struct PslPose* Tlw,
+                    const struct PslPose* Tcw, const struct PslLastPoint* points, const uint8_t* mpdesc, const struct PslCamera* cam,
+                    const float* scale, int nlevels, float th, float th_depth, int mono, int vo, const float* bounds,
+                    struct PslProjQuery* q, uint8_t* qdesc, int32_t* owner);
+int pr_project_frustum(const struct PslPose* Tcw, const struct PslMapPointGeom* mp, const uint8_t* mpdesc, int nmp,
+                       const struct PslCamera* cam, const float* scale, int nlevels, float log_scale_factor, float view_cos_limit, float th,
+                       const float* bounds, struct PslProjQuery* q, uint8_t* qdesc, int32_t* owner, uint8_t* inview, int32_t* level,
+                       float* viewcos);
+
+/* line_project_oracle.cpp: pslfe_line_project_frustum / _last */
+void lr_sizes(int32_t* out);
+int lr_level(float ratio, float lsf, int how);
+long lr_level_sweep(float lo, float hi, float lsf, long* flips);
+int lr_in_frustum(const struct PslMapLineGeom* G, const struct PslPose* T, const struct PslCamera* C, const float* bounds, float limit,
+                  float lsf, float* out, int32_t* level);
+int lr_project_frustum(const struct PslPose* Tcw, const struct PslMapLineGeom* ml, const uint8_t* mldesc, int nml,
+                       const struct PslCamera* cam, float log_scale_factor, float view_cos_limit, float th, const float* bounds,
+                       struct PslLineQuery* q, uint8_t* qdesc, int32_t* owner, uint8_t* inview, int32_t* level, float* viewcos);
+int lr_project_last(const struct PslKeyLine* kls, const uint8_t* ldesc, int n, const struct PslLastLine* lines, const uint8_t* mldesc,
+                    const struct PslPose* Tcw, const struct PslCamera* cam, float th, const float* bounds, struct PslLineQuery* q,
+                    uint8_t* qdesc, int32_t* owner);
+
+/* stereo_oracle.cpp: pslfe_frame_set_from_orb_stereo */
+int sr_stereo(const struct PslKeyPoint* kL, const uint8_t* dL, int nL, const struct PslKeyPoint* kR, const uint8_t* dR, int nR,
+              const uint8_t* const* imL, const int* pitchL, const uint8_t* const* imR, const int* pitchR, const int* lw, const int* lh,
+              const float* scale, const float* inv_scale, int nlevels, float bf, float fx, float* uright, float* depth, int32_t* tap_idx,
+              int32_t* tap_sad);
+
+/* mono_init_oracle.cpp: the frame grid and pslfe_orb_search_for_initialization */
+int mr_grid(const PsoKeyPoint* kps, int n, const float* bounds, int32_t* start, int32_t* idx);
+int mr_search(const PsoKeyPoint* kps1, const uint8_t* desc1, int n1, const PsoKeyPoint* kps2, const uint8_t* desc2, int n2,
+              const float* bounds2, float* prev, int window, float nnratio, int check_ori, int32_t* m12, int32_t* accepted);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // Sequential C++ restatement of Frame::ComputeStereoMatches (src/Frame.cc:1165-1340) under the conventions stated at
-// pslfe_frame_set_from_orb_stereo in include/pslfe.h (psl-slam_amd/csrc/stereo_kernels.h).  Test infrastructure: the tests build
-// it with g++ -O2 -ffp-contract=off into a shared library and compare the HIP kernels with it bit for bit.
+// pslfe_frame_set_from_orb_stereo in include/pslfe.h (psl-slam_amd/csrc/stereo_kernels.h).  Test infrastructure: part of the
+// oracle library; the tests compare the HIP kernels with it bit for bit.
 //
 // Inputs: the distorted left / right keypoints and descriptors, the two pyramids as one pointer, pitch, width and height per level,
 // the extractor's scale factors and the camera (mbf, fx).  Outputs per left keypoint: mvuRight, mvDepth and the two taps
@@ -14,12 +14,8 @@
 #include <vector>
 
 #include "../include/pslfe.h"
-
-static int hamming(const uint8_t* a, const uint8_t* b) {
-    int d = 0;
-    for (int k = 0; k < 32; ++k) d += __builtin_popcount((unsigned)(a[k] ^ b[k]));
-    return d;
-}
+#include "psl_oracle.h"
+#include "psl_oracle_internal.h"
 
 extern "C" int sr_stereo(const PslKeyPoint* kL, const uint8_t* dL, int nL, const PslKeyPoint* kR, const uint8_t* dR, int nR,
                          const uint8_t* const* imL, const int* pitchL, const uint8_t* const* imR, const int* pitchR, const int* lw,
@@ -62,7 +58,7 @@ extern "C" int sr_stereo(const PslKeyPoint* kL, const uint8_t* dL, int nL, const
             if (kpR.octave < levelL - 1 || kpR.octave > levelL + 1) continue;
             const float uR = kpR.x;
             if (uR >= minU && uR <= maxU) {
-                const int dist = hamming(dL + (size_t)iL * 32, dR + (size_t)iR * 32);
+                const int dist = pso::descriptor_distance(dL + (size_t)iL * 32, dR + (size_t)iR * 32);
                 if (dist < bestDist) { bestDist = dist; bestIdxR = iR; }
             }
         }

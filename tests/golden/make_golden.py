@@ -81,7 +81,7 @@ def ref():
     """ref_pins.npz: the outputs of the reference's standalone files (oracle/_ref, `make -C oracle _ref REF=<reference tree>`) on the
     inputs of tests/test_oracle_ref_cpu.py, which pins the oracle against them without a reference tree.  Outputs and input CRCs only."""
     import ctypes as C
-    import test_oracle_ref_cpu as T
+    import ref_cases as T
     rdir = os.path.join(ROOT, "oracle", "_ref")
     out = {}
     # the line grid walk (add_src/lineIterator.cpp): cells per walk and their CRC

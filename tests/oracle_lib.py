@@ -585,3 +585,195 @@ def lsd_rects(img, cap=20000):
     L.pso_lsd_rects.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     n = L.pso_lsd_rects(_p(img), w, h, img.strides[0], _p(r), cap)
     return r[:n].copy()
+
+
+# ---- sequential checkers of the device projections (oracle/project_oracle.cpp, oracle/line_project_oracle.cpp) ------
+# Poses, cameras, map points and map lines are passed as the records of psl_slam_amd (POSE_DTYPE, CAMERA_DTYPE, ...).
+def _c(a):
+    return None if a is None else np.ascontiguousarray(a)
+
+
+def _sizes(name, n):
+    fn = getattr(load(), name)
+    sz = np.zeros(n, np.int32)
+    fn.argtypes = [C.c_void_p]
+    fn(_p(sz))
+    return sz
+
+
+def pr_sizes():
+    """sizeof(PslPose), PslLastPoint, PslMapPointGeom, PslProjQuery as the checker's compiler sees them."""
+    return _sizes("pr_sizes", 4)
+
+
+def pr_vo_select(depth, th_depth):
+    """UpdateLastFrame's selection: (number of keypoints visited, sel[i] = 1 for the visited ones)."""
+    L = load()
+    depth = np.ascontiguousarray(depth, np.float32)
+    sel = np.zeros(max(len(depth), 1), np.uint8)
+    L.pr_vo_select.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    n = L.pr_vo_select(_p(depth), len(depth), float(th_depth), _p(sel))
+    return n, sel[:len(depth)]
+
+
+def pr_predict_level(ratio, log_scale_factor, nlevels):
+    L = load()
+    L.pr_predict_level.argtypes = [C.c_float, C.c_float, C.c_int]
+    return L.pr_predict_level(float(ratio), float(log_scale_factor), nlevels)
+
+
+def pr_level_sweep(lo, hi, log_scale_factor, nlevels):
+    """Every float ratio in [lo, hi]: (levels that differ between psl_log and the host's log, ratios visited)."""
+    L = load()
+    n = C.c_long()
+    L.pr_level_sweep.restype = C.c_long
+    L.pr_level_sweep.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_long)]
+    bad = L.pr_level_sweep(float(lo), float(hi), float(log_scale_factor), nlevels, C.byref(n))
+    return bad, n.value
+
+
+def pr_project_last(kps, desc, depth, Tlw, Tcw, points, mpdesc, cam, scale, th, th_depth, mono, vo, bounds):
+    """The query rows of SearchByProjection(CurrentFrame, LastFrame): (queries, qdesc, owner)."""
+    L = load()
+    kps, desc, depth, Tlw, Tcw, points, mpdesc, cam = (_c(a) for a in (kps, desc, depth, Tlw, Tcw, points, mpdesc, cam))
+    scale, b = np.ascontiguousarray(scale, np.float32), np.asarray(bounds, np.float32)
+    n = len(kps)
+    q = np.zeros(max(n, 1), PROJQUERY_DTYPE)
+    qd = np.zeros((max(n, 1), 32), np.uint8)
+    ow = np.zeros(max(n, 1), np.int32)
+    L.pr_project_last.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + \
+        [C.c_void_p] * 4
+    nq = L.pr_project_last(_p(kps), _p(desc), _p(depth), n, _p(Tlw), _p(Tcw), _p(points), _p(mpdesc), _p(cam), _p(scale), len(scale), th,
+                           th_depth, int(mono), int(vo), _p(b), _p(q), _p(qd), _p(ow))
+    return q[:nq], qd[:nq], ow[:nq]
+
+
+def pr_project_frustum(Tcw, mp, mpdesc, cam, scale, log_scale_factor, view_cos_limit, th, bounds):
+    """isInFrustum + the query rows of SearchByProjection(F, vpMapPoints): (queries, qdesc, owner, inview, level, viewcos)."""
+    L = load()
+    Tcw, mp, mpdesc, cam = (_c(a) for a in (Tcw, mp, mpdesc, cam))
+    scale, b = np.ascontiguousarray(scale, np.float32), np.asarray(bounds, np.float32)
+    n = len(mp)
+    m = max(n, 1)
+    q, qd = np.zeros(m, PROJQUERY_DTYPE), np.zeros((m, 32), np.uint8)
+    ow, iv, lv, vc = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros(m, np.float32)
+    L.pr_project_frustum.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_float, C.c_float, C.c_float] + \
+        [C.c_void_p] * 7
+    nq = L.pr_project_frustum(_p(Tcw), _p(mp), _p(mpdesc), n, _p(cam), _p(scale), len(scale), log_scale_factor, view_cos_limit, th, _p(b),
+                              _p(q), _p(qd), _p(ow), _p(iv), _p(lv), _p(vc))
+    return q[:nq], qd[:nq], ow[:nq], iv[:n], lv[:n], vc[:n]
+
+
+def lr_sizes():
+    """sizeof(PslMapLineGeom), PslLastLine, PslLineQuery as the checker's compiler sees them."""
+    return _sizes("lr_sizes", 3)
+
+
+def lr_level(ratio, lsf, how):
+    """MapLine::PredictScale; how: 0 = the library's logf, 1 = the host's logf, 2 = the point projections' double path."""
+    L = load()
+    L.lr_level.argtypes = [C.c_float, C.c_float, C.c_int]
+    return L.lr_level(float(ratio), float(lsf), how)
+
+
+def lr_level_sweep(lo, hi, lsf):
+    """Every float ratio in [lo, hi]: (ratios visited, [levels that differ from the host's logf, from the double path])."""
+    L = load()
+    flips = np.zeros(2, np.int64)
+    L.lr_level_sweep.restype = C.c_long
+    L.lr_level_sweep.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
+    n = L.lr_level_sweep(float(lo), float(hi), float(lsf), _p(flips))
+    return n, flips
+
+
+def lr_in_frustum(G, T, cam, bounds, limit, lsf):
+    """Frame::isInFrustum of one map line: (in view, [u1, v1, u2, v2, viewCos], level)."""
+    L = load()
+    G, T, cam, b = _c(G), _c(T), _c(cam), np.asarray(bounds, np.float32)
+    out = np.zeros(5, np.float32)
+    lvl = C.c_int32()
+    L.lr_in_frustum.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    got = L.lr_in_frustum(_p(G), _p(T), _p(cam), _p(b), float(limit), float(lsf), _p(out), C.byref(lvl))
+    return got, out, lvl.value
+
+
+def lr_project_frustum(Tcw, ml, mldesc, cam, log_scale_factor, view_cos_limit, th, bounds):
+    """isInFrustum + the query rows of SearchByProjection(F, vpMapLines): (queries, qdesc, owner, inview, level, viewcos)."""
+    L = load()
+    Tcw, ml, mldesc, cam, b = _c(Tcw), _c(ml), np.ascontiguousarray(mldesc, np.uint8), _c(cam), np.asarray(bounds, np.float32)
+    n = len(ml)
+    m = max(n, 1)
+    q, qd = np.zeros(m, LINEQUERY_DTYPE), np.zeros((m, 32), np.uint8)
+    ow, iv, lv, vc = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros(m, np.float32)
+    L.lr_project_frustum.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 7
+    nq = L.lr_project_frustum(_p(Tcw), _p(ml), _p(mldesc), n, _p(cam), log_scale_factor, view_cos_limit, th, _p(b), _p(q), _p(qd), _p(ow),
+                              _p(iv), _p(lv), _p(vc))
+    return q[:nq], qd[:nq], ow[:nq], iv[:n], lv[:n], vc[:n]
+
+
+def lr_project_last(kls, ldesc, lines, mldesc, Tcw, cam, th, bounds):
+    """The query rows of SearchByProjection(CurrentFrame, LastFrame) of the last frame's lines: (queries, qdesc, owner)."""
+    L = load()
+    kls, ldesc, lines, Tcw, cam, b = _c(kls), _c(ldesc), _c(lines), _c(Tcw), _c(cam), np.asarray(bounds, np.float32)
+    md = None if mldesc is None else np.ascontiguousarray(mldesc, np.uint8)
+    n = len(kls)
+    q, qd, ow = np.zeros(max(n, 1), LINEQUERY_DTYPE), np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.int32)
+    L.lr_project_last.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4
+    nq = L.lr_project_last(_p(kls), _p(ldesc), n, _p(lines), _p(md), _p(Tcw), _p(cam), th, _p(b), _p(q), _p(qd), _p(ow))
+    return q[:nq], qd[:nq], ow[:nq]
+
+
+# ---- sequential checkers of the stereo constructor and the monocular initialiser (oracle/stereo_oracle.cpp, mono_init_oracle.cpp)
+def restate_stereo(kL, dL, kR, dR, levL, levR, scale, inv_scale, bf, fx):
+    """(uright, depth, idx_right, sad) of the restatement.  levL / levR: level images (2-D uint8 arrays of any row pitch)."""
+    L = load()
+    kL, kR = np.ascontiguousarray(kL, KEYPOINT_DTYPE), np.ascontiguousarray(kR, KEYPOINT_DTYPE)
+    dL = np.ascontiguousarray(dL, np.uint8).reshape(-1, 32)
+    dR = np.ascontiguousarray(dR, np.uint8).reshape(-1, 32)
+    nl = len(levL)
+    ptr = lambda levs: (C.c_void_p * nl)(*[lv.ctypes.data for lv in levs])
+    pit = lambda levs: np.array([lv.strides[0] for lv in levs], np.int32)
+    for a, b in zip(levL, levR):
+        assert a.shape == b.shape and a.strides[1] == 1 and b.strides[1] == 1
+    lw = np.array([lv.shape[1] for lv in levL], np.int32)
+    lh = np.array([lv.shape[0] for lv in levL], np.int32)
+    pL, pR, sL, sR = ptr(levL), ptr(levR), pit(levL), pit(levR)
+    sc, isc = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(inv_scale, np.float32)
+    n = len(kL)
+    ur, dep = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+    idx, sad = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    L.sr_stereo.argtypes = [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_float, C.c_float] + \
+        [C.c_void_p] * 4
+    L.sr_stereo(_p(kL), _p(dL), n, _p(kR), _p(dR), len(kR), C.cast(pL, C.c_void_p), _p(sL), C.cast(pR, C.c_void_p), _p(sR), _p(lw), _p(lh),
+                _p(sc), _p(isc), nl, float(bf), float(fx), _p(ur), _p(dep), _p(idx), _p(sad))
+    return ur[:n], dep[:n], idx[:n], sad[:n]
+
+
+def restate_grid(kps, bounds):
+    """CSR of the frame grid as the monocular checker builds it: (start[64 * 48 + 1], idx)."""
+    L = load()
+    kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    b = np.asarray(bounds, np.float32)
+    start = np.zeros(64 * 48 + 1, np.int32)
+    idx = np.zeros(max(len(kps), 1), np.int32)
+    L.mr_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    n = L.mr_grid(_p(kps), len(kps), _p(b), _p(start), _p(idx))
+    return start, idx[:n]
+
+
+def restate_search(k1, d1, k2, d2, bounds2, prev, window=100, nnratio=0.9, check_ori=True):
+    """(nmatches, matches12, prev after the call, accepted) of the restatement; `prev` itself is not modified."""
+    L = load()
+    k1, k2 = np.ascontiguousarray(k1, KEYPOINT_DTYPE), np.ascontiguousarray(k2, KEYPOINT_DTYPE)
+    d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 32)
+    d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 32)
+    b = np.asarray(bounds2, np.float32)
+    pv = np.array(prev, np.float32).reshape(-1, 2).copy()
+    n1 = len(k1)
+    m12 = np.zeros(max(n1, 1), np.int32)
+    acc = np.zeros(max(n1, 1), np.int32)
+    L.mr_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                            C.c_int, C.c_void_p, C.c_void_p]
+    nm = L.mr_search(_p(k1), _p(d1), n1, _p(k2), _p(d2), len(k2), _p(b), _p(pv), int(window), float(nnratio), int(bool(check_ori)), _p(m12),
+                     _p(acc))
+    return nm, m12[:n1], pv, acc[:n1]

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import synth_frames as sf
-from test_line_gpu import ADV, STD, RAMP_CASES, _adversarial_images, _assert_extract_equal, ramp_image
+from line_cases import ADV, STD, RAMP_CASES, adversarial_images, assert_extract_equal, ramp_image
 
 try:   # PyTorch's HIP runtime before libpslfe's in a process that uses both (tests/test_gather_gpu.py; test 1d runs the torch pipeline)
     import torch
@@ -105,7 +105,7 @@ def _run_batch(le, frames):
 
 
 def _equal(got, ref, what):
-    _assert_extract_equal(got[:3], ref[:3], what)
+    assert_extract_equal(got[:3], ref[:3], what)
     assert got[3].tobytes() == ref[3].tobytes(), f"{what}: fans differ ({len(got[3])} vs {len(ref[3])} rows)"
 
 
@@ -173,7 +173,7 @@ def test_adversarial_inputs_through_the_many_frames_grow_kernel(mode):
     one occurrence of every image equals the oracle: its LSD segment list (the ramps give segments but no keylines) and its keylines,
     LBD rows, line equations and fans."""
     groups = {}
-    for name, img in _adversarial_images().items():
+    for name, img in adversarial_images().items():
         groups.setdefault(img.shape, []).append((name, np.ascontiguousarray(img)))
     for w, h, noise, seed in RAMP_CASES:
         groups.setdefault((h, w), []).append((f"ramp {w}x{h} {noise} {seed}", ramp_image(w, h, noise, seed)))

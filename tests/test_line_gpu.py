@@ -11,13 +11,11 @@ import numpy as np
 import pytest
 
 import synth_frames as sf
+from line_cases import ADV, STD, RAMP_CASES, adversarial_images, assert_extract_equal, kl_equal, ramp_image
 
 pytestmark = pytest.mark.gpu
 
 DEG2RAD = np.pi / 180
-
-
-ADV, STD = 2, 1
 
 
 def _scene(style, seed, t=0, w=640, h=480):
@@ -94,9 +92,9 @@ def test_line_stages_at_1280x960(refine_mode):
     np.testing.assert_array_equal(scaled, rs)
     gang = np.where(angdeg == -1024.0, -1024.0, angdeg.astype(np.float64) * DEG2RAD)
     np.testing.assert_array_equal(gang, ra)
-    _kl_equal(le.optimize_and_merge(ref_seg, 1280, 960, cap=4096), oracle_lib.optimize_and_merge(ref_seg, 1280, 960, cap=4096), "merge 1280x960")
+    kl_equal(le.optimize_and_merge(ref_seg, 1280, 960, cap=4096), oracle_lib.optimize_and_merge(ref_seg, 1280, 960, cap=4096), "merge 1280x960")
     ref = oracle_lib.line_extract(img, 200)
-    _assert_extract_equal(le(img), ref, "line extract 1280x960")
+    assert_extract_equal(le(img), ref, "line extract 1280x960")
     L = np.stack([ref[0][n] for n in ("startPointX", "startPointY", "endPointX", "endPointY")], 1).astype(np.float32)
     np.testing.assert_array_equal(le.pair(L, 20.0, np.float32(np.pi / 4), 1280, 960).view(np.uint32),
                                   oracle_lib.lil_pair(L, 20.0, np.float32(np.pi / 4), 1280, 960).view(np.uint32))
@@ -125,16 +123,6 @@ def test_lsd_large_regions_exercise_queue_overflow():
         exact = got.shape == ref.shape and (got.view(np.uint32) == ref.view(np.uint32)).all()
         print(f"LSD ramps refine {mode}: {len(got)} vs oracle {len(ref)} segments, bit-identical {exact}")
         assert len(ref) >= (4 if mode == STD else 2) and exact
-
-
-RAMP_CASES = [(40, 40, 0.3, 0), (40, 40, 0.3, 9), (40, 40, 0.3, 14), (40, 40, 0.45, 5), (40, 40, 0.6, 2), (40, 40, 0.6, 3), (40, 40, 0.8, 6),
-              (36, 36, 0.6, 21), (36, 36, 0.8, 17)]   # (w, h, noise, seed)
-
-
-def ramp_image(w, h, noise, seed):
-    """A noisy diagonal ramp: one LSD region is most of the image (test_lsd_reduce_region_radius_on_a_queue_of_most_of_the_image)."""
-    yy, xx = np.mgrid[0:h, 0:w]
-    return np.clip(254.0 / (w + h - 2) * (xx + yy) + np.random.default_rng(seed).normal(0, noise, (h, w)), 0, 255).astype(np.uint8)
 
 
 def test_lsd_reduce_region_radius_on_a_queue_of_most_of_the_image():
@@ -183,48 +171,18 @@ def test_lds_map_attribute_is_kept_per_device_across_extractors():
     ref_a = oracle_lib.line_extract(img_a, 200)
     a, b = _extractor(ADV, 1, 1.2, 200, 0.0), _extractor(ADV, 1, 1.2, 200, 0.0)
     first = a(img_a)
-    _assert_extract_equal(first, ref_a, "extractor A, first frame")
-    _assert_extract_equal(b(img_b), oracle_lib.line_extract(img_b, 200), "extractor B")
+    assert_extract_equal(first, ref_a, "extractor A, first frame")
+    assert_extract_equal(b(img_b), oracle_lib.line_extract(img_b, 200), "extractor B")
     again = a(img_a)
-    _assert_extract_equal(again, first, "extractor A after B")
-    _assert_extract_equal(again, ref_a, "extractor A after B vs oracle")
+    assert_extract_equal(again, first, "extractor A after B")
+    assert_extract_equal(again, ref_a, "extractor A after B vs oracle")
     assert len(ref_a[0]) > 20
-
-
-def _adversarial_images():
-    """Inputs that stress the queue order of the region growing rather than look like a room: rings (regions that turn and close on
-    themselves), stripes of every thickness in both diagonals (frontiers several entries wide, growth up and to the left of the seed),
-    smoothed noise (blobs, many tiny regions), a checker board (corners everywhere), raw noise, and a frame that touches all four
-    borders."""
-    import synth_frames as sf
-    h, w = 300, 400
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
-    out = {}
-    r = np.hypot(xx - 190.3, yy - 140.7)
-    out["rings"] = np.clip(128 + 100 * np.sin(r / 3.1), 0, 255).astype(np.uint8)
-    st = np.zeros((h, w))
-    for k, (t, s) in enumerate([(1, 1), (2, -1), (3, 1), (5, -1), (8, 1), (13, -1)]):
-        d = (xx + s * yy * (0.35 + 0.2 * k)) - (40 + 55 * k) - (0 if s > 0 else -120)
-        st += 170.0 * (np.abs(d) < t)
-    out["stripes"] = np.clip(30 + st, 0, 255).astype(np.uint8)
-    out["blobs"] = sf.random_gray(w, h, 12, "blobs")
-    out["checker"] = sf.random_gray(w, h, 13, "checker")
-    out["noise"] = sf.random_gray(w, h, 14, "noise")
-    fr = np.full((h, w), 60, np.uint8)
-    fr[:3] = 250; fr[-3:] = 250; fr[:, :3] = 250; fr[:, -3:] = 250
-    fr[40:44, :] = 200; fr[:, 100:103] = 10
-    out["frame"] = fr
-    # one region of 22 000 pixels whose breadth-first frontier is 85 entries behind the queue's end (tools/grow_stats.py): the queue's
-    # LDS ring wraps 20 times; in a build with -DPSL_LSD_RING=128 the frontier is mapped from the HBM copy of the queue
-    by, bx = np.mgrid[0:200, 0:640].astype(np.float64)
-    out["band"] = np.rint(np.clip(4.4 * (by - 40 + 0.05 * np.abs(bx - 320)), 0, 255)).astype(np.uint8)
-    return out
 
 
 @pytest.mark.parametrize("refine_mode", [ADV, STD], indirect=True)
 def test_lsd_adversarial_queue_orders(refine_mode):
     import oracle_lib
-    for name, img in _adversarial_images().items():
+    for name, img in adversarial_images().items():
         img = np.ascontiguousarray(img)
         ref = oracle_lib.lsd_detect(img)
         got = _extractor(refine_mode).lsd_detect(img)
@@ -236,16 +194,6 @@ def test_lsd_adversarial_queue_orders(refine_mode):
 def test_lsd_flat_image_gives_no_segments():
     import psl_slam_amd as P
     assert len(P.LINEextractor().lsd_detect(np.full((480, 640), 128, np.uint8))) == 0
-
-
-def _kl_equal(a, b, what, skip=()):
-    assert len(a) == len(b), f"{what}: {len(a)} vs {len(b)} keylines"
-    for name in a.dtype.names:
-        if name in skip:
-            continue
-        x, y = a[name], b[name]
-        bad = np.flatnonzero(x.view(np.uint32) != y.view(np.uint32)) if x.dtype.kind == "f" else np.flatnonzero(x != y)
-        assert bad.size == 0, f"{what}: field {name} differs at {bad[:5]}: {x[bad[:5]]} vs {y[bad[:5]]}"
 
 
 @pytest.mark.parametrize("style,seed", [("struct", 3), ("desk", 4), ("struct", 8)])
@@ -263,7 +211,7 @@ def test_merge_stage_on_oracle_segments(style, seed):
     ref = oracle_lib.optimize_and_merge(seg, 640, 480)
     got = P.LINEextractor().optimize_and_merge(seg, 640, 480)
     assert len(ref) > 10
-    _kl_equal(got, ref, f"merge {style}/{seed}")
+    kl_equal(got, ref, f"merge {style}/{seed}")
     print(f"merge {style}/{seed}: {len(seg)} segments -> {len(got)} keylines, bit-identical")
 
 
@@ -323,14 +271,6 @@ def test_pairing_on_oracle_lines(style, seed):
     assert len(P.LINEextractor().pair(lines[:1], 20.0, 0.785, 640, 480)) == 0
 
 
-def _assert_extract_equal(got, ref, what):
-    gk, gd, ge = got
-    rk, rd, re_ = ref
-    _kl_equal(gk, rk, what)
-    np.testing.assert_array_equal(gd, rd, err_msg=what)
-    np.testing.assert_array_equal(ge.view(np.uint64), re_.view(np.uint64), err_msg=what)
-
-
 @pytest.mark.parametrize("refine_mode", [ADV, STD], indirect=True)
 @pytest.mark.parametrize("style,seed,t", [("struct", 3, 0), ("desk", 4, 0), ("struct", 8, 0), ("struct", 5, 0), ("desk", 7, 7), ("struct", 9, 15),
                                           ("desk", 11, 23), ("sticks", 13, 0), ("sticks", 14, 5)])
@@ -344,7 +284,7 @@ def test_full_line_extractor(style, seed, t, refine_mode):
     ref = oracle_lib.line_extract(img, 200)
     got = _extractor(refine_mode, 1, 1.2, 200, 0.0)(img)
     assert len(ref[0]) > (20 if refine_mode == STD else 8)
-    _assert_extract_equal(got, ref, f"line extract {style}/{seed}/{t} refine {refine_mode}")
+    assert_extract_equal(got, ref, f"line extract {style}/{seed}/{t} refine {refine_mode}")
 
 
 def test_line_extractor_batch_and_pairing_device():
@@ -471,7 +411,7 @@ def test_merge_stage_more_segments_than_the_small_lds_instance(nscenes):
     ref = oracle_lib.optimize_and_merge(seg, 640, 480, cap=4096)
     got = P.LINEextractor().optimize_and_merge(seg, 640, 480, cap=4096)
     assert len(ref) > 100
-    _kl_equal(got, ref, f"merge of {len(seg)} segments")
+    kl_equal(got, ref, f"merge of {len(seg)} segments")
 
 
 @pytest.mark.parametrize("refine_mode", [ADV, STD], indirect=True)
@@ -526,7 +466,7 @@ def test_full_size_line_batch_properties():
     for f in np.linspace(0, n - 1, 16).astype(int):
         f = int(f)
         k, dsc, eq, _ = le.fetch(f)
-        _assert_extract_equal((k, dsc, eq), oracle_lib.line_extract(batch[f], 200), f"batch frame {f}")
+        assert_extract_equal((k, dsc, eq), oracle_lib.line_extract(batch[f], 200), f"batch frame {f}")
         L = np.stack([k[m] for m in ("startPointX", "startPointY", "endPointX", "endPointY")], 1).astype(np.float32)
         np.testing.assert_array_equal(le.fans_fetch(f).view(np.uint32), oracle_lib.lil_pair(L, 20.0, np.float32(np.pi / 4), 640, 480).view(np.uint32))
     le.ctx.device_free(d_ptr)
@@ -547,7 +487,7 @@ def test_line_extractor_many_random_scenes_in_one_batch():
     for f in range(len(frames)):
         k, dsc, eq, st = le.fetch(f)
         assert st == 0
-        _assert_extract_equal((k, dsc, eq), oracle_lib.line_extract(frames[f], 200), f"scene {f}")
+        assert_extract_equal((k, dsc, eq), oracle_lib.line_extract(frames[f], 200), f"scene {f}")
         L = np.stack([k[m] for m in ("startPointX", "startPointY", "endPointX", "endPointY")], 1).astype(np.float32) if len(k) else np.zeros((0, 4), np.float32)
         np.testing.assert_array_equal(le.fans_fetch(f).view(np.uint32), oracle_lib.lil_pair(L, 20.0, np.float32(np.pi / 4), 640, 480).view(np.uint32))
         nkl += len(k)

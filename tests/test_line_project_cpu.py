@@ -1,40 +1,17 @@
 """CPU checks of the map-line projection entry points (include/pslfe.h: pslfe_line_project_frustum[_device],
 pslfe_line_project_last[_device], pslfe_line_search_by_projection_device, pslfe_glue_lines3d_device): the restatement the GPU tests
-compare with (tests/line_proj_restate.cpp) against a literal Python transcription of Frame::isInFrustum(MapLine*), the log of
+compare with (oracle/line_project_oracle.cpp) against a literal Python transcription of Frame::isInFrustum(MapLine*), the log of
 MapLine::PredictScale swept over every float ratio the gates admit, the POD layouts, and the argument checks, which need no GPU."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import oracle_lib
+
 TUM1 = (517.306408, 516.469215, 318.643040, 255.313989, 0, 0, 0, 0, 0, 40.0)
 BOUNDS = (0.0, 0.0, 640.0, 480.0)
 F32 = np.float32
-
-
-def build_line_restatement(out_dir):
-    """g++ -ffp-contract=off build of tests/line_proj_restate.cpp -> ctypes handle."""
-    so = os.path.join(str(out_dir), "libline_proj_restate.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(ROOT, "tests", "line_proj_restate.cpp"),
-                    "-o", so], check=True)
-    L = C.CDLL(so)
-    L.lr_sizes.argtypes = [C.c_void_p]
-    L.lr_level.argtypes = [C.c_float, C.c_float, C.c_int]
-    L.lr_level_sweep.restype = C.c_long
-    L.lr_level_sweep.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
-    L.lr_in_frustum.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    L.lr_project_frustum.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 7
-    L.lr_project_last.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4
-    return L
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_line_restatement(tmp_path_factory.mktemp("line_proj_restate"))
 
 
 def camera():
@@ -107,11 +84,10 @@ def random_lines(rng, T, n):
     return G
 
 
-def test_restatement_equals_transcription(restate):
+def test_restatement_equals_transcription():
     import psl_slam_amd as P
     rng = np.random.default_rng(11)
     cam = np.ascontiguousarray(camera()).reshape(1)
-    b = np.asarray(BOUNDS, np.float32)
     lsf = F32(np.log(F32(1.2)))
     n_in = n_all = 0
     for trial in range(40):
@@ -121,17 +97,13 @@ def test_restatement_equals_transcription(restate):
         G = random_lines(rng, T[0], 200)
         G[:5]["sp"][:, 2] = np.nan if trial % 3 == 0 else G[:5]["sp"][:, 2]
         for j in range(len(G)):
-            g = np.ascontiguousarray(G[j:j + 1])
-            out = np.zeros(5, np.float32)
-            lvl = C.c_int32()
-            got = restate.lr_in_frustum(g.ctypes.data, T.ctypes.data, cam.ctypes.data, b.ctypes.data, C.c_float(0.5), lsf, out.ctypes.data,
-                                        C.byref(lvl))
+            got, out, lvl = oracle_lib.lr_in_frustum(G[j:j + 1], T, cam, BOUNDS, 0.5, lsf)
             want = is_in_frustum(G[j], T[0], cam[0], BOUNDS, 0.5, lsf)
             n_all += 1
             assert bool(got) == (want is not None), (trial, j)
             if want is not None:
                 n_in += 1
-                assert out.tobytes() == np.asarray(want[:5], np.float32).tobytes() and lvl.value == want[5], (trial, j)
+                assert out.tobytes() == np.asarray(want[:5], np.float32).tobytes() and lvl == want[5], (trial, j)
     assert n_in > 100 and n_all - n_in > 1000
 
 
@@ -139,31 +111,29 @@ def test_restatement_equals_transcription(restate):
 DOUBLE_PATH_FLIPS = 2
 
 
-def test_predict_scale_log_sweep(restate):
+def test_predict_scale_log_sweep():
     """MapLine::PredictScale for every float ratio isInFrustum lets through (mfMaxDistance / dist with 0.8 * min <= dist <= 1.2 * max,
     max / min = 1.2^7 as MapLine::UpdateAverageDir sets it): the library's level (correctly rounded logf of psl_log, float quotient and
     ceil) against the host's logf and against the double path of the point projections."""
     lsf = F32(np.log(F32(1.2)))
     lo = F32(1.0) / F32(1.2)
     hi = F32(F32(1.2) ** 7) / F32(0.8)
-    flips = np.zeros(2, np.int64)
-    n = restate.lr_level_sweep(lo, hi, lsf, flips.ctypes.data)
+    n, flips = oracle_lib.lr_level_sweep(lo, hi, lsf)
     assert n > 20_000_000
     assert flips[0] == 0, f"{flips[0]} ratios of {n} give another level with the host's logf"
     # the double path differs where logf(ratio) / lsf rounds onto an integer: the reason the float path is restated
     assert flips[1] == DOUBLE_PATH_FLIPS, flips[1]
     # unclamped levels and the defined edge cases
-    assert restate.lr_level(C.c_float(0.5), lsf, 0) == -3
-    assert restate.lr_level(C.c_float(1000.0), lsf, 0) == 38
-    assert restate.lr_level(C.c_float(np.inf), lsf, 0) == 2**31 - 1
-    assert restate.lr_level(C.c_float(0.0), lsf, 0) == -2**31
-    assert restate.lr_level(C.c_float(np.nan), lsf, 0) == 0
+    assert oracle_lib.lr_level(0.5, lsf, 0) == -3
+    assert oracle_lib.lr_level(1000.0, lsf, 0) == 38
+    assert oracle_lib.lr_level(np.inf, lsf, 0) == 2**31 - 1
+    assert oracle_lib.lr_level(0.0, lsf, 0) == -2**31
+    assert oracle_lib.lr_level(np.nan, lsf, 0) == 0
 
 
-def test_line_projection_dtypes_match_header(restate):
+def test_line_projection_dtypes_match_header():
     import psl_slam_amd as P
-    sz = np.zeros(3, np.int32)
-    restate.lr_sizes(sz.ctypes.data)
+    sz = oracle_lib.lr_sizes()
     assert list(sz) == [P.MAPLINE_DTYPE.itemsize, P.LASTLINE_DTYPE.itemsize, P.LINEQUERY_DTYPE.itemsize] == [80, 88, 64]
     assert P.LASTLINE_DTYPE.fields["state"][1] == 80 and P.MAPLINE_DTYPE.fields["min_dist"][1] == 72
 

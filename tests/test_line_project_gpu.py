@@ -1,5 +1,5 @@
 """GPU parity of the map-line projections (pslfe_line_project_frustum[_device], pslfe_line_project_last[_device]) with the sequential
-restatement tests/line_proj_restate.cpp, bit for bit; of the batched line window search (pslfe_line_search_by_projection_device, both
+restatement oracle/line_project_oracle.cpp, bit for bit; of the batched line window search (pslfe_line_search_by_projection_device, both
 modes) with the one-frame entry point and the oracle; and of the device chain line extraction -> pairing -> glue -> projections ->
 batched search with a host chain that fetches each frame, projects with the restatement and searches with the oracle."""
 import ctypes as C
@@ -7,8 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import oracle_lib
 import synth_frames as sf
-from test_line_project_cpu import build_line_restatement
+from project_cases import T4, rot
 
 pytestmark = pytest.mark.gpu
 
@@ -21,29 +22,12 @@ NNR = 0.95
 E_CAPACITY = -4
 
 
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_line_restatement(tmp_path_factory.mktemp("line_proj_restate_gpu"))
-
-
 def camera():
     import psl_slam_amd as P
     cam = np.zeros((), P.CAMERA_DTYPE)
     for k, v in zip(P.CAMERA_DTYPE.names, TUM1_NODIST):
         cam[k] = F32(v)
     return cam
-
-
-def T4(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
-
-
-def rot(ax, ay, az):
-    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
-    return np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @ \
-        np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
 
 
 class Batch:
@@ -160,36 +144,15 @@ def line_dist(sp, ep, T):
     return F32(np.sqrt(sum(float(o) * float(o) for o in OM)))
 
 
-def restated_frustum(restate, T, G, gd, cam, limit, th):
+def restated_frustum(T, G, gd, cam, limit, th):
     import psl_slam_amd as P
-    M = len(G)
-    ml = np.ascontiguousarray(G[list(P.MAPLINE_DTYPE.names)].astype(P.MAPLINE_DTYPE))
-    md = np.ascontiguousarray(gd, np.uint8)
-    q = np.zeros(max(M, 1), P.LINEQUERY_DTYPE)
-    qd = np.zeros((max(M, 1), 32), np.uint8)
-    ow, iv, lv, vc = np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.uint8), np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.float32)
-    Tp = np.ascontiguousarray(P.pose(T)).reshape(1)
-    c = np.ascontiguousarray(cam).reshape(1)
-    b = np.asarray(BOUNDS, np.float32)
-    n = restate.lr_project_frustum(Tp.ctypes.data, ml.ctypes.data, md.ctypes.data, M, c.ctypes.data, LSF, limit, th, b.ctypes.data,
-                                   q.ctypes.data, qd.ctypes.data, ow.ctypes.data, iv.ctypes.data, lv.ctypes.data, vc.ctypes.data)
-    return q[:n], qd[:n], ow[:n], iv[:M], lv[:M], vc[:M]
+    ml = G[list(P.MAPLINE_DTYPE.names)].astype(P.MAPLINE_DTYPE)
+    return oracle_lib.lr_project_frustum(P.pose(T).reshape(1), ml, gd, np.ascontiguousarray(cam).reshape(1), LSF, limit, th, BOUNDS)
 
 
-def restated_last(restate, kls, ldesc, L, mldesc, T, cam, th):
+def restated_last(kls, ldesc, L, mldesc, T, cam, th):
     import psl_slam_amd as P
-    n = len(kls)
-    k, d, Ls = (np.ascontiguousarray(a) for a in (kls, ldesc, L))
-    md = None if mldesc is None else np.ascontiguousarray(mldesc, np.uint8)
-    q = np.zeros(max(n, 1), P.LINEQUERY_DTYPE)
-    qd = np.zeros((max(n, 1), 32), np.uint8)
-    ow = np.zeros(max(n, 1), np.int32)
-    Tp = np.ascontiguousarray(P.pose(T)).reshape(1)
-    c = np.ascontiguousarray(cam).reshape(1)
-    b = np.asarray(BOUNDS, np.float32)
-    m = restate.lr_project_last(k.ctypes.data, d.ctypes.data, n, Ls.ctypes.data, None if md is None else md.ctypes.data, Tp.ctypes.data,
-                                c.ctypes.data, th, b.ctypes.data, q.ctypes.data, qd.ctypes.data, ow.ctypes.data)
-    return q[:m], qd[:m], ow[:m]
+    return oracle_lib.lr_project_last(kls, ldesc, L, mldesc, P.pose(T).reshape(1), np.ascontiguousarray(cam).reshape(1), th, BOUNDS)
 
 
 def _t(a, dev):
@@ -212,7 +175,7 @@ def batches():
 
 @pytest.mark.parametrize("style", ["sticks", "struct"])
 @pytest.mark.parametrize("th", [1.0, 3.0])
-def test_line_projections_equal_restatement(restate, batches, style, th):
+def test_line_projections_equal_restatement(batches, style, th):
     """Both projections, device and host forms, against the restatement: every row byte, owner, count, in-view flag, level and
     viewCos, on map lines from real frames plus the adversarial ones; qstride smaller than the count is reported."""
     import psl_slam_amd as P
@@ -258,7 +221,7 @@ def test_line_projections_equal_restatement(restate, batches, style, th):
         small = 0
         for p in range(npairs):
             n = nml[p]
-            rq, rqd, row, riv, rlv, rvc = restated_frustum(restate, Ts[p], Gs[p, :n], Gd[p, :n], cam, 0.5, th)
+            rq, rqd, row, riv, rlv, rvc = restated_frustum(Ts[p], Gs[p, :n], Gd[p, :n], cam, 0.5, th)
             m = min(len(rq), qstride)
             small += len(rq) > qstride
             assert NQ[p] == len(rq) and Q[p, :m].tobytes() == rq[:m].tobytes(), f"pair {p}: frustum rows differ"
@@ -271,7 +234,7 @@ def test_line_projections_equal_restatement(restate, batches, style, th):
                 assert len(rq) > 10 and len(set(rlv[riv == 1].tolist())) >= 3
         assert qstride == stride or small > 0
     # the adversarial lines: levels outside [0, 8) and the infinite ratio occur
-    _, _, _, riv, rlv, _ = restated_frustum(restate, Ts[0], Gs[0, :nml[0]], Gd[0, :nml[0]], cam, 0.5, th)
+    _, _, _, riv, rlv, _ = restated_frustum(Ts[0], Gs[0, :nml[0]], Gd[0, :nml[0]], cam, 0.5, th)
     assert (rlv[riv == 1] >= 8).any() and (riv == 0).any()
     with pytest.raises(P.PslfeError):  # the host form reports a count above its capacity
         _check_capacity(ctx, Ts[0], Gs[0, :nml[0]], Gd[0, :nml[0]], cam)
@@ -293,7 +256,7 @@ def test_line_projections_equal_restatement(restate, batches, style, th):
                 k, d, L, _ = data[p]
                 n = nk[p]
                 md = MD[p, :n] if use_md else None
-                rq, rqd, row = restated_last(restate, k, d, Ls[p, :n], md, Ts[p], cam, 10.0 * th)
+                rq, rqd, row = restated_last(k, d, Ls[p, :n], md, Ts[p], cam, 10.0 * th)
                 m = min(len(rq), qstride)
                 assert NQ[p] == len(rq) and Q[p, :m].tobytes() == rq[:m].tobytes(), f"pair {p}: last-frame rows differ"
                 assert (QD[p, :m] == rqd[:m]).all() and (OW[p, :m] == row[:m]).all()
@@ -345,7 +308,6 @@ def test_line_search_device_equals_one_frame_and_oracle(batches, style, mode, wi
     little: every match, assignment and count equals the one-frame entry point and the oracle; one pair has long lines enough to take
     the second launch."""
     import psl_slam_amd as P
-    import oracle_lib
     ctx, bs = batches
     b = bs[style]
     dev = b.dev
@@ -414,13 +376,12 @@ def test_line_search_device_equals_one_frame_and_oracle(batches, style, mode, wi
     assert total > npairs
 
 
-def test_line_device_chain_equals_host_chain(restate):
+def test_line_device_chain_equals_host_chain():
     """line_extract_batch_device -> pair_batch_device -> glue_run_batch_device -> line_project_last_device / line_project_frustum_device
     -> line_search_by_projection_device (mode 0 on the last-frame rows, mode 1 on the frustum rows) on 257 'sticks' frames with no
     host round trip, against a host chain on sampled pairs: fetch, restated projections, oracle searches."""
     import torch
     import psl_slam_amd as P
-    import oracle_lib
     ctx = P.Context(0, torch.cuda.current_stream(torch.device("cuda", 0)).cuda_stream)
     B = 257
     b = Batch("sticks", B, 5, ctx)
@@ -481,11 +442,11 @@ def test_line_device_chain_equals_host_chain(restate):
         k, d, e, _ = b.frame(p)
         k1, d1, e1, l31 = b.frame(p + 1)
         n = len(k)
-        rq, rqd, _ = restated_last(restate, k, d, LAST[p, :n], None, Tc[p], cam, 20.0)
+        rq, rqd, _ = restated_last(k, d, LAST[p, :n], None, Tc[p], cam, 20.0)
         rn, rm, _ = oracle_lib.line_search_by_projection(k1, d1, e1, BOUNDS, rq, rqd, 0, None, None, NNR)
         assert NQ0[p] == len(rq) and NM0[p] == rn and (M0[p, :len(rq)] == rm).all(), f"pair {p}: mode-0 chain differs"
         G = LAST[p, :n]
-        fq, fqd, _, _, _, _ = restated_frustum(restate, Tc[p], G, d, cam, 0.5, 1.0)
+        fq, fqd, _, _, _, _ = restated_frustum(Tc[p], G, d, cam, 0.5, 1.0)
         fn, fm, _ = oracle_lib.line_search_by_projection(k1, d1, e1, BOUNDS, fq, fqd, 1, l31[:, :3] - l31[:, 3:], None, NNR)
         assert NQ1[p] == len(fq) and NM1[p] == fn and (M1[p, :len(fq)] == fm).all(), f"pair {p}: mode-1 chain differs"
         tot0 += rn

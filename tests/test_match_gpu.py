@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import synth_frames as sf
+from match_cases import make_queries
 
 pytestmark = pytest.mark.gpu
 
@@ -17,22 +18,6 @@ def _frames():
     orc = oracle_lib.OracleORB()
     sc = sf.Scene(640, 480, "desk", seed=11)
     return [orc(sc.gray(t)) for t in range(2)], sc
-
-
-def make_queries(kps, desc, rng, th=15.0, jitter=2.0, p_block=0.7, with_ur=False):
-    import psl_slam_amd as P
-    scale = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
-    scale = sf.orb_scale_factors()
-    q = np.zeros(len(kps), P.PROJQUERY_DTYPE)
-    q["u"] = kps["x"] + rng.uniform(-jitter, jitter, len(kps)).astype(np.float32)
-    q["v"] = kps["y"] + rng.uniform(-jitter, jitter, len(kps)).astype(np.float32)
-    q["radius"] = np.float32(th) * scale[kps["octave"]]
-    q["min_level"] = kps["octave"] - 1
-    q["max_level"] = kps["octave"] + 1
-    q["angle"] = kps["angle"]
-    q["blocks"] = (rng.random(len(kps)) < p_block).astype(np.int32)
-    q["ur"] = q["u"] - np.float32(40.0) / np.float32(2.0) if with_ur else 0
-    return q, desc.copy()
 
 
 def test_grid_matches_reference_order():

@@ -1,64 +1,18 @@
 """CPU checks of the monocular initialiser's matcher (include/pslfe.h: pslfe_orb_search_for_initialization): the sequential
-restatement the GPU tests compare with (tests/mono_init_restate.cpp) against a literal numpy-float32 transcription of
+restatement the GPU tests compare with (oracle/mono_init_oracle.cpp) against a literal numpy-float32 transcription of
 ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405-520), GetFeaturesInArea (src/Frame.cc:985-1038),
 AssignFeaturesToGrid / PosInGrid and ComputeThreeMaxima, on random keypoint sets and constructed cases; and the argument checks
 of the library, which need no GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from mono_init_cases import BOUNDS, Case, constructed, one_tenth, random_pair, stolen_decides
+from oracle_lib import KEYPOINT_DTYPE, restate_grid, restate_search
+
 F32 = np.float32
 INT_MAX = 2**31 - 1
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                           ("octave", "<i4"), ("class_id", "<i4")])
-BOUNDS = (0.0, 0.0, 640.0, 480.0)
-
-
-def build_restatement(out_dir):
-    """g++ -ffp-contract=off build of tests/mono_init_restate.cpp -> ctypes handle."""
-    so = os.path.join(str(out_dir), "libmono_init_restate.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                    os.path.join(ROOT, "tests", "mono_init_restate.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    L.mr_grid.restype = C.c_int
-    L.mr_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mr_search.restype = C.c_int
-    L.mr_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
-                            C.c_int, C.c_void_p, C.c_void_p]
-    return L
-
-
-def restate_grid(L, kps, bounds):
-    kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
-    b = np.asarray(bounds, F32)
-    start = np.zeros(64 * 48 + 1, np.int32)
-    idx = np.zeros(max(len(kps), 1), np.int32)
-    n = L.mr_grid(kps.ctypes.data, len(kps), b.ctypes.data, start.ctypes.data, idx.ctypes.data)
-    return start, idx[:n]
-
-
-def restate_search(L, k1, d1, k2, d2, bounds2, prev, window=100, nnratio=0.9, check_ori=True):
-    """(nmatches, matches12, prev after the call, accepted) of the restatement; `prev` itself is not modified."""
-    k1, k2 = np.ascontiguousarray(k1, KEYPOINT_DTYPE), np.ascontiguousarray(k2, KEYPOINT_DTYPE)
-    d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 32)
-    d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 32)
-    b = np.asarray(bounds2, F32)
-    pv = np.array(prev, F32).reshape(-1, 2).copy()
-    n1 = len(k1)
-    m12 = np.zeros(max(n1, 1), np.int32)
-    acc = np.zeros(max(n1, 1), np.int32)
-    nm = L.mr_search(k1.ctypes.data, d1.ctypes.data, n1, k2.ctypes.data, d2.ctypes.data, len(k2), b.ctypes.data, pv.ctypes.data,
-                     int(window), float(nnratio), int(bool(check_ori)), m12.ctypes.data, acc.ctypes.data)
-    return nm, m12[:n1], pv, acc[:n1]
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_restatement(tmp_path_factory.mktemp("mono_init_restate"))
 
 
 def _round(x):
@@ -194,150 +148,15 @@ def assert_same(got, want, what):
     assert np.asarray(pv, F32).tobytes() == np.asarray(wpv, F32).tobytes(), f"{what}: prev differs"
 
 
-# ---- constructed cases: keypoints at chosen places, descriptors at controlled Hamming distances ------------------------------
-
-class Case:
-    """F1 / F2 keypoints and descriptors built up piece by piece (shared with tests/test_mono_init_gpu.py)."""
-
-    def __init__(self):
-        self.k1, self.d1, self.k2, self.d2, self.prev = [], [], [], [], []
-
-    @staticmethod
-    def _kp(x, y, angle, octave):
-        k = np.zeros((), KEYPOINT_DTYPE)
-        k["x"], k["y"], k["angle"], k["octave"], k["size"] = x, y, angle, octave, 31.0
-        return k
-
-    def f2(self, x, y, desc, angle=0.0, octave=0):
-        self.k2.append(self._kp(x, y, angle, octave))
-        self.d2.append(np.asarray(desc, np.uint8))
-        return len(self.k2) - 1
-
-    def f1(self, x, y, desc, angle=0.0, octave=0, prev=None):
-        self.k1.append(self._kp(x, y, angle, octave))
-        self.d1.append(np.asarray(desc, np.uint8))
-        self.prev.append((x, y) if prev is None else prev)
-        return len(self.k1) - 1
-
-    def arrays(self):
-        k1 = np.array(self.k1, KEYPOINT_DTYPE) if self.k1 else np.zeros(0, KEYPOINT_DTYPE)
-        k2 = np.array(self.k2, KEYPOINT_DTYPE) if self.k2 else np.zeros(0, KEYPOINT_DTYPE)
-        d1 = np.array(self.d1, np.uint8).reshape(-1, 32)
-        d2 = np.array(self.d2, np.uint8).reshape(-1, 32)
-        prev = np.array(self.prev, F32).reshape(-1, 2)
-        return k1, d1, k2, d2, prev
-
-
-def random_desc(rng):
-    return rng.integers(0, 256, 32, dtype=np.uint8)
-
-
-def flip(desc, rng, k):
-    """desc with k distinct bits flipped."""
-    b = np.unpackbits(desc)
-    b[rng.choice(256, k, replace=False)] ^= 1
-    return np.packbits(b)
-
-
-def constructed(c, rng):
-    """The edge cases of the matcher on one frame pair (window 20): returns the ids the assertions need."""
-    ids = {}
-    # steal chain: three queries compete for one F2 keypoint with distances 40, 30, 20; each takes it from the one before
-    base = random_desc(rng)
-    k = c.f2(100, 100, base)
-    ids["chain"] = (k, [c.f1(101, 100, flip(base, rng, d)) for d in (40, 30, 20)])
-    # tie: two F2 keypoints at the same distance; the first in visiting order (lower grid column) has the higher index
-    base = random_desc(rng)
-    right = c.f2(312, 100, base)
-    left = c.f2(288, 100, base)
-    ids["tie"] = (c.f1(300, 100, flip(base, rng, 10)), left, right)
-    # the filter removes the best and changes the second best: an earlier query holds X at 10; the later query sees X at 12
-    # (filtered), Y at 20, Z at 22
-    base = random_desc(rng)
-    X = c.f2(500, 100, base)
-    c.f1(500, 100, flip(base, rng, 10))
-    qd = flip(base, rng, 12)
-    Y = c.f2(505, 100, flip(qd, rng, 20))
-    Z = c.f2(495, 100, flip(qd, rng, 22))
-    ids["filt"] = (c.f1(501, 101, qd), X, Y, Z)
-    # a single survivor: bestDist2 stays INT_MAX
-    base = random_desc(rng)
-    k = c.f2(100, 300, base)
-    ids["single"] = (c.f1(100, 300, flip(base, rng, 45)), k)
-    # octave > 0: the query is skipped, and an F2 keypoint of octave 2 is no candidate
-    base = random_desc(rng)
-    k = c.f2(300, 300, base)
-    q = c.f1(300, 300, base, octave=1)
-    k_hi = c.f2(303, 300, base, octave=2)
-    ids["skip"] = (q, c.f1(303, 300, flip(base, rng, 60)), k, k_hi)
-    # prev outside the grid: an empty window
-    base = random_desc(rng)
-    c.f2(500, 300, base)
-    ids["out"] = c.f1(500, 300, flip(base, rng, 5), prev=(-500.0, 2000.0))
-    return ids
-
-
-def stolen_decides(c, rng):
-    """24 plain matches in bin 0; a query A matched in bin 6, later taken over by B (bin 0); two more matches C, D in bin 6.
-    Bin 6 holds 3 entries against 25 in bin 0 (3 >= 2.5): C and D survive only because A's entry still counts.  Window 10."""
-    for j in range(24):
-        base = random_desc(rng)
-        c.f2(20 + 25 * j, 400, base, angle=100.0)
-        c.f1(20 + 25 * j, 400, flip(base, rng, 5), angle=100.0)
-    base = random_desc(rng)
-    kA = c.f2(100, 100, base, angle=10.0)
-    A = c.f1(100, 100, flip(base, rng, 30), angle=190.0)      # rot 180 -> bin 6
-    CD = []
-    for j in range(2):
-        b = random_desc(rng)
-        c.f2(300 + 40 * j, 200, b, angle=20.0)
-        CD.append(c.f1(300 + 40 * j, 200, flip(b, rng, 8), angle=200.0))
-    B = c.f1(101, 100, flip(base, rng, 10), angle=10.0)       # bin 0, takes kA
-    return A, B, kA, CD
-
-
-def one_tenth(c, rng):
-    """max2 == max3 == 0.1 * max1 exactly (0.1f * 10.0f rounds to 1.0f): both bins are kept, a fourth is cleared.  Window 10."""
-    for j in range(10):
-        b = random_desc(rng)
-        c.f2(20 + 25 * j, 50, b)
-        c.f1(20 + 25 * j, 50, flip(b, rng, 5))
-    out = []
-    for j, rot in enumerate((150.0, 240.0, 300.0)):
-        b = random_desc(rng)
-        c.f2(100 + 60 * j, 300, b)
-        out.append(c.f1(100 + 60 * j, 300, flip(b, rng, 5), angle=rot))
-    return out
-
-
-def random_pair(rng, n1, n2, w=640, h=480, p0=0.5):
-    k2 = np.zeros(n2, KEYPOINT_DTYPE)
-    k2["x"], k2["y"] = rng.uniform(-5, w + 5, n2), rng.uniform(-5, h + 5, n2)
-    k2["octave"] = np.where(rng.random(n2) < p0, 0, rng.integers(1, 8, n2))
-    k2["angle"] = rng.uniform(0, 360, n2)
-    d2 = rng.integers(0, 256, (n2, 32), dtype=np.uint8)
-    k1 = np.zeros(n1, KEYPOINT_DTYPE)
-    if n2:
-        src = rng.integers(0, n2, n1)
-        k1["x"] = k2["x"][src] + rng.normal(0, 30, n1)
-        k1["y"] = k2["y"][src] + rng.normal(0, 30, n1)
-        k1["angle"] = np.mod(k2["angle"][src] + np.where(rng.random(n1) < 0.7, rng.normal(0, 5, n1), rng.uniform(0, 360, n1)), 360)
-        d1 = np.stack([flip(d2[s], rng, int(rng.integers(0, 70))) for s in src]) if n1 else np.zeros((0, 32), np.uint8)
-    else:
-        d1 = rng.integers(0, 256, (n1, 32), dtype=np.uint8)
-    k1["octave"] = np.where(rng.random(n1) < 0.6, 0, rng.integers(1, 8, n1))
-    prev = np.stack([k1["x"], k1["y"]], 1).astype(F32)
-    return k1, d1, k2, d2, prev
-
 
 @pytest.mark.parametrize("check_ori", [True, False])
-def test_restatement_equals_transcription_random(restate, check_ori):
+def test_restatement_equals_transcription_random(check_ori):
     rng = np.random.default_rng(11 if check_ori else 12)
     for rep in range(8):
         n1, n2 = (300, 300) if rep == 0 else (int(rng.integers(0, 400)), int(rng.integers(0, 400)))
         k1, d1, k2, d2, prev = random_pair(rng, n1, n2)
         window = 100 if rep == 0 else int(rng.choice([10, 50, 100]))
-        got = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, window, 0.9, check_ori)
+        got = restate_search(k1, d1, k2, d2, BOUNDS, prev, window, 0.9, check_ori)
         want = transcription(k1, d1, k2, d2, BOUNDS, prev, window, 0.9, check_ori)
         assert_same(got, want, f"rep {rep}")
         if rep == 0:
@@ -345,14 +164,14 @@ def test_restatement_equals_transcription_random(restate, check_ori):
 
 
 @pytest.mark.parametrize("check_ori", [True, False])
-def test_constructed_cases(restate, check_ori):
+def test_constructed_cases(check_ori):
     rng = np.random.default_rng(3)
     c = Case()
     ids = constructed(c, rng)
     k1, d1, k2, d2, prev = c.arrays()
-    got = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, 20, 0.9, check_ori)
+    got = restate_search(k1, d1, k2, d2, BOUNDS, prev, 20, 0.9, check_ori)
     assert_same(got, transcription(k1, d1, k2, d2, BOUNDS, prev, 20, 0.9, check_ori), "constructed")
-    loose = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, 20, 1.5, check_ori)
+    loose = restate_search(k1, d1, k2, d2, BOUNDS, prev, 20, 1.5, check_ori)
     assert_same(loose, transcription(k1, d1, k2, d2, BOUNDS, prev, 20, 1.5, check_ori), "constructed, nnratio 1.5")
     nm, m12, pv, acc = got
     k, qs = ids["chain"]
@@ -368,36 +187,36 @@ def test_constructed_cases(restate, check_ori):
     assert acc[ids["out"]] == -1 and pv[ids["out"]].tolist() == [-500.0, 2000.0]
 
 
-def test_stolen_entry_decides_the_maxima(restate):
+def test_stolen_entry_decides_the_maxima():
     rng = np.random.default_rng(8)
     c = Case()
     A, B, kA, CD = stolen_decides(c, rng)
     k1, d1, k2, d2, prev = c.arrays()
-    got = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True)
+    got = restate_search(k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True)
     assert_same(got, transcription(k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True), "stolen entry")
     nm, m12, _, acc = got
     assert acc[A] == kA and m12[A] == -1 and m12[B] == kA
     assert all(m12[q] >= 0 for q in CD) and nm == 24 + 1 + 2
 
 
-def test_three_maxima_at_one_tenth(restate):
+def test_three_maxima_at_one_tenth():
     rng = np.random.default_rng(9)
     c = Case()
     q5, q8, q10 = one_tenth(c, rng)
     k1, d1, k2, d2, prev = c.arrays()
-    got = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True)
+    got = restate_search(k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True)
     assert_same(got, transcription(k1, d1, k2, d2, BOUNDS, prev, 10, 0.9, True), "one tenth")
     nm, m12 = got[0], got[1]
     assert m12[q5] >= 0 and m12[q8] >= 0 and m12[q10] == -1 and nm == 12
 
 
-def test_grid_equals_transcription(restate):
+def test_grid_equals_transcription():
     rng = np.random.default_rng(4)
     n = 500
     k = np.zeros(n, KEYPOINT_DTYPE)
     k["x"], k["y"] = rng.uniform(-10, 650, n), rng.uniform(-10, 490, n)
     bounds = (-3.5, -2.25, 641.0, 482.5)
-    start, idx = restate_grid(restate, k, bounds)
+    start, idx = restate_grid(k, bounds)
     mnMinX, mnMinY, mnMaxX, mnMaxY = (F32(b) for b in bounds)
     invW, invH = F32(F32(64) / F32(mnMaxX - mnMinX)), F32(F32(48) / F32(mnMaxY - mnMinY))
     cells = [[] for _ in range(64 * 48)]

@@ -1,6 +1,6 @@
 """GPU parity of the monocular Frame constructor (pslfe_frame_set_from_orb_mono) and ORBmatcher::SearchForInitialization
 (pslfe_orb_search_for_initialization / _device) against the CPU oracle's undistortion and the sequential restatement
-tests/mono_init_restate.cpp (itself checked against a numpy transcription of the reference in tests/test_mono_init_cpu.py)."""
+oracle/mono_init_oracle.cpp (itself checked against a numpy transcription of the reference in tests/test_mono_init_cpu.py)."""
 import ctypes as C
 import json
 import os
@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import synth_frames as sf
-from test_mono_init_cpu import (BOUNDS, Case, build_restatement, constructed, one_tenth, random_pair, restate_grid, restate_search,
-                                stolen_decides)
+from mono_init_cases import BOUNDS, Case, constructed, one_tenth, random_pair, stolen_decides
+from oracle_lib import restate_grid, restate_search
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +21,6 @@ E_INVALID, E_CAPACITY, E_STATE = -1, -4, -5
 TUM1 = (517.306408, 516.469215, 318.643040, 255.313989, 0.262383, -0.953104, -0.005358, 0.002628, 1.163314, 40.0)
 PLAIN = (517.306408, 516.469215, 318.643040, 255.313989, 0, 0, 0, 0, 0, 40.0)
 KITTI = (718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 0, 386.1448)
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_restatement(tmp_path_factory.mktemp("mono_init_restate_gpu"))
 
 
 def camera(vals):
@@ -46,7 +41,7 @@ def xy(k):
 
 
 @pytest.mark.parametrize("cam_vals", [TUM1, PLAIN], ids=["tum1", "plain"])
-def test_constructor_equals_rgbd_undistortion_and_grid(restate, cam_vals):
+def test_constructor_equals_rgbd_undistortion_and_grid(cam_vals):
     """mvKeysUn equal to the RGB-D path's undistortion, mvDepth = mvuRight = -1, the grid equal to the restatement's; empty frames
     (first and in the middle) give n = 0 and an empty grid."""
     import psl_slam_amd as P
@@ -73,13 +68,13 @@ def test_constructor_equals_rgbd_undistortion_and_grid(restate, cam_vals):
         want, _, _ = oracle_lib.frame_post_rgbd(k, np.zeros((h, w), np.float32), cam)
         assert kun.tobytes() == want.tobytes(), f"frame {t}: mvKeysUn differs"
         assert (dep == -1).all() and (ur == -1).all()
-        rs, ri = restate_grid(restate, want, bounds)
+        rs, ri = restate_grid(want, bounds)
         assert start.tobytes() == rs.tobytes() and gidx.tobytes() == ri.tobytes(), f"frame {t}: grid differs"
         if cam_vals is TUM1:
             assert kun.tobytes() != k.tobytes()
 
 
-def _chain(restate, g, f1_slot, k1un, d1, frames, bounds, set_f2):
+def _chain(g, f1_slot, k1un, d1, frames, bounds, set_f2):
     """prev chained over the frames against one initial frame: the library's host path vs the restatement."""
     import psl_slam_amd as P
     m = P.ORBmatcher(0.9, True)
@@ -88,14 +83,14 @@ def _chain(restate, g, f1_slot, k1un, d1, frames, bounds, set_f2):
     for t, fr in enumerate(frames):
         k2un, d2 = set_f2(fr)
         nm, m12 = m.SearchForInitialization(g, f1_slot, g, 1, prev, 100)
-        rnm, rm12, rprev, _ = restate_search(restate, k1un, d1, k2un, d2, bounds, rprev, 100, 0.9, True)
+        rnm, rm12, rprev, _ = restate_search(k1un, d1, k2un, d2, bounds, rprev, 100, 0.9, True)
         assert nm == rnm and (m12 == rm12).all(), f"frame {t}: matches differ ({nm} vs {rnm})"
         assert prev.tobytes() == rprev.tobytes(), f"frame {t}: prev differs"
         counts.append(nm)
     return counts
 
 
-def test_single_pair_chain_tum(restate):
+def test_single_pair_chain_tum():
     """TUM1 640x480, the initialiser's 2000 features, prev chained over 6 frames against frame 0."""
     import psl_slam_amd as P
     import oracle_lib
@@ -112,11 +107,11 @@ def test_single_pair_chain_tum(restate):
         _, d2 = orb(img)
         g.set_from_orb_mono(1, orb, 0, 1, cam)
         return g.fetch(1)[0], d2
-    counts = _chain(restate, g, 0, k1un, d1, imgs[1:], oracle_lib.image_bounds(cam, w, h), set_f2)
+    counts = _chain(g, 0, k1un, d1, imgs[1:], oracle_lib.image_bounds(cam, w, h), set_f2)
     assert counts[0] > 100, counts
 
 
-def test_single_pair_chain_kitti_4000(restate):
+def test_single_pair_chain_kitti_4000():
     """KITTI 1241x376 with 4000 initialiser features: the device extractor refuses them (a level quota above its 512-node octree,
     PSLFE_E_INVALID), so the keypoints come from the CPU oracle of the extractor through pslfe_frame_set."""
     import psl_slam_amd as P
@@ -136,18 +131,18 @@ def test_single_pair_chain_kitti_4000(restate):
         k2, d2 = orc(img)
         g.set(1, k2, d2, bounds)
         return k2, d2
-    counts = _chain(restate, g, 0, k1, d1, imgs[1:], bounds, set_f2)
+    counts = _chain(g, 0, k1, d1, imgs[1:], bounds, set_f2)
     assert counts[0] > 100, counts
 
 
-def _host_case(restate, k1, d1, k2, d2, prev, window, nnratio=0.9, check_ori=True, cap=None):
+def _host_case(k1, d1, k2, d2, prev, window, nnratio=0.9, check_ori=True, cap=None):
     import psl_slam_amd as P
     g = P.FrameGrid(cap or max(len(k1), len(k2), 1), 2)
     g.set(0, k1, d1, BOUNDS)
     g.set(1, k2, d2, BOUNDS)
     pv = np.ascontiguousarray(prev, np.float32).copy()
     nm, m12 = P.ORBmatcher(nnratio, check_ori).SearchForInitialization(g, 0, g, 1, pv, window)
-    want = restate_search(restate, k1, d1, k2, d2, BOUNDS, prev, window, nnratio, check_ori)
+    want = restate_search(k1, d1, k2, d2, BOUNDS, prev, window, nnratio, check_ori)
     assert nm == want[0] and (m12 == want[1]).all() and pv.tobytes() == want[2].tobytes()
     return want
 
@@ -169,40 +164,40 @@ def rewalk(c):
 
 
 @pytest.mark.parametrize("check_ori", [True, False])
-def test_adversarial_pairs(restate, check_ori):
+def test_adversarial_pairs(check_ori):
     rng = np.random.default_rng(21)
     c = Case()
     constructed(c, rng)
     k1, d1, k2, d2, prev = c.arrays()
     for nnratio in (0.9, 1.5):
-        _host_case(restate, k1, d1, k2, d2, prev, 20, nnratio, check_ori)
+        _host_case(k1, d1, k2, d2, prev, 20, nnratio, check_ori)
     c = Case()
     q, ks = rewalk(c)
-    want = _host_case(restate, *c.arrays(), 20, 0.9, check_ori)
+    want = _host_case(*c.arrays(), 20, 0.9, check_ori)
     assert want[1][q] == ks[9] and want[0] == 10
     c = Case()
     A, B, kA, CD = stolen_decides(c, rng)
-    want = _host_case(restate, *c.arrays(), 10, 0.9, check_ori)
+    want = _host_case(*c.arrays(), 10, 0.9, check_ori)
     if check_ori:
         assert want[1][A] == -1 and want[1][B] == kA and all(want[1][q] >= 0 for q in CD)
     c = Case()
     one_tenth(c, rng)
-    _host_case(restate, *c.arrays(), 10, 0.9, check_ori)
+    _host_case(*c.arrays(), 10, 0.9, check_ori)
 
 
-def test_full_capacity_and_empty_f2(restate):
+def test_full_capacity_and_empty_f2():
     """4096 octave-0 keypoints in F2 (the frame store's capacity, 16-bit candidate positions at their limit), and an empty F2."""
     rng = np.random.default_rng(5)
     k1, d1, k2, d2, prev = random_pair(rng, 4096, 4096, p0=1.0)
-    want = _host_case(restate, k1, d1, k2, d2, prev, 100, cap=4096)
+    want = _host_case(k1, d1, k2, d2, prev, 100, cap=4096)
     assert want[0] > 100
     k1, d1, _, _, prev = random_pair(rng, 300, 300)
     e = np.zeros(0, k1.dtype)
-    want = _host_case(restate, k1, d1, e, np.zeros((0, 32), np.uint8), prev, 100)
+    want = _host_case(k1, d1, e, np.zeros((0, 32), np.uint8), prev, 100)
     assert want[0] == 0 and (want[1] == -1).all() and want[2].tobytes() == prev.tobytes()
 
 
-def test_batch_equals_per_pair_calls(restate):
+def test_batch_equals_per_pair_calls():
     """257 pairs in one device call, F1 and F2 in one store (f1 == f2) and in two stores, against the per-pair host calls and the
     restatement; then a device-resident chain (batch extraction -> set_from_orb_mono -> _device search) against the host path."""
     import torch
@@ -245,7 +240,7 @@ def test_batch_equals_per_pair_calls(restate):
         nm, m12 = m.SearchForInitialization(G, 0, G, int(s2[p]), pv, 100)
         assert nm == NM1[p] and (m12 == M1[p, :n1]).all() and pv.tobytes() == PV1[p, :n1].tobytes(), f"pair {p}: batch vs host"
         k2un = G.fetch(int(s2[p]))[0]
-        rnm, rm12, rpv, _ = restate_search(restate, k1un, res[0][1], k2un, res[int(s2[p])][1], bounds, base[p, :n1], 100, 0.9, True)
+        rnm, rm12, rpv, _ = restate_search(k1un, res[0][1], k2un, res[int(s2[p])][1], bounds, base[p, :n1], 100, 0.9, True)
         assert rnm == nm and (rm12 == m12).all() and rpv.tobytes() == pv.tobytes(), f"pair {p}: batch vs restatement"
     assert NM1.min() > 50
 

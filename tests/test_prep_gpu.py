@@ -82,7 +82,7 @@ def test_frame_rgbd_feeds_matcher():
     """mvuRight produced on the device takes part in SearchByProjection exactly as a host-provided one."""
     import psl_slam_amd as P
     import oracle_lib
-    from test_match_gpu import make_queries
+    from match_cases import make_queries
     cam = _cam(P, TUM1)
     sc = sf.Scene(640, 480, "desk", seed=11)
     kps, desc = oracle_lib.OracleORB()(sc.gray(0))

@@ -1,34 +1,12 @@
 """CPU checks of the projection entry points (include/pslfe.h: pslfe_orb_project_last[_device], pslfe_orb_project_frustum[_device],
-pslfe_orb_search_by_projection_map_device): the restatement the GPU tests compare with (tests/proj_restate.cpp) against a literal
+pslfe_orb_search_by_projection_map_device): the restatement the GPU tests compare with (oracle/project_oracle.cpp) against a literal
 transcription of Tracking::UpdateLastFrame's loop, the double log of PredictScale against the host's libm, the POD layouts, and the
 argument checks of the library, which need no GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_restatement(out_dir):
-    """g++ -ffp-contract=off build of tests/proj_restate.cpp -> ctypes handle."""
-    so = os.path.join(str(out_dir), "libproj_restate.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(ROOT, "tests", "proj_restate.cpp"),
-                    "-o", so], check=True)
-    L = C.CDLL(so)
-    L.pr_level_sweep.restype = C.c_long
-    L.pr_level_sweep.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_long)]
-    L.pr_vo_select.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p]
-    L.pr_predict_level.argtypes = [C.c_float, C.c_float, C.c_int]
-    L.pr_sizes.argtypes = [C.c_void_p]
-    return L
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_restatement(tmp_path_factory.mktemp("proj_restate"))
+import oracle_lib
 
 
 def update_last_frame_loop(depth, th_depth):
@@ -66,42 +44,39 @@ def depth_cases(rng):
         yield d, np.float32(rng.choice([0.0, 1.0, 3.0, 100.0]))
 
 
-def test_vo_selection_equals_update_last_frame_loop(restate):
+def test_vo_selection_equals_update_last_frame_loop():
     rng = np.random.default_rng(5)
     ncases = 0
     for d, th in depth_cases(rng):
         d = np.ascontiguousarray(d, np.float32)
-        sel = np.zeros(max(len(d), 1), np.uint8)
-        L = restate.pr_vo_select(d.ctypes.data, len(d), C.c_float(th), sel.ctypes.data)
+        L, sel = oracle_lib.pr_vo_select(d, th)
         want = update_last_frame_loop(d, float(th))
-        got = set(np.flatnonzero(sel[:len(d)]).tolist())
+        got = set(np.flatnonzero(sel).tolist())
         assert got == want and L == len(want), (len(d), float(th), L, len(want))
         ncases += 1
     assert ncases > 300
 
 
-def test_predicted_level_psl_log_equals_host_log(restate):
+def test_predicted_level_psl_log_equals_host_log():
     """PredictScale's level with the library's double log (psl_log) and with the host's log agree for every float ratio of the range
     isInFrustum lets through: mfMaxDistance / dist with 0.8 * min <= dist <= 1.2 * max, max / min up to 1.2^7 (8 levels)."""
     scale, nlevels = np.float32(1.2), 8
     lsf = np.float32(np.log(scale))
     lo = np.float32(1.0) / np.float32(1.2)
     hi = np.float32(scale ** (nlevels - 1)) / np.float32(0.8)
-    n = C.c_long()
-    bad = restate.pr_level_sweep(lo, hi, lsf, nlevels, C.byref(n))
-    assert n.value > 20_000_000 and bad == 0, (n.value, bad)
+    bad, n = oracle_lib.pr_level_sweep(lo, hi, lsf, nlevels)
+    assert n > 20_000_000 and bad == 0, (n, bad)
     # the clamps of src/MapPoint.cc:409-412 and the defined edge cases
-    assert restate.pr_predict_level(C.c_float(0.5), lsf, nlevels) == 0
-    assert restate.pr_predict_level(C.c_float(1000.0), lsf, nlevels) == nlevels - 1
-    assert restate.pr_predict_level(C.c_float(np.inf), lsf, nlevels) == nlevels - 1
-    assert restate.pr_predict_level(C.c_float(0.0), lsf, nlevels) == 0
-    assert restate.pr_predict_level(C.c_float(np.nan), lsf, nlevels) == 0
+    assert oracle_lib.pr_predict_level(0.5, lsf, nlevels) == 0
+    assert oracle_lib.pr_predict_level(1000.0, lsf, nlevels) == nlevels - 1
+    assert oracle_lib.pr_predict_level(np.inf, lsf, nlevels) == nlevels - 1
+    assert oracle_lib.pr_predict_level(0.0, lsf, nlevels) == 0
+    assert oracle_lib.pr_predict_level(np.nan, lsf, nlevels) == 0
 
 
-def test_projection_dtypes_match_header(restate):
+def test_projection_dtypes_match_header():
     import psl_slam_amd as P
-    sz = np.zeros(4, np.int32)
-    restate.pr_sizes(sz.ctypes.data)
+    sz = oracle_lib.pr_sizes()
     assert list(sz) == [P.POSE_DTYPE.itemsize, P.LASTPOINT_DTYPE.itemsize, P.MAPPOINT_DTYPE.itemsize, P.PROJQUERY_DTYPE.itemsize]
     assert list(sz) == [48, 16, 32, 32]
     T = np.eye(4, dtype=np.float32)

@@ -1,5 +1,5 @@
 """GPU parity of the projection entry points (pslfe_orb_project_last[_device], pslfe_orb_project_frustum[_device]) with the
-sequential restatement tests/proj_restate.cpp, field by field and bit for bit, and of the device chain
+sequential restatement oracle/project_oracle.cpp, field by field and bit for bit, and of the device chain
 set_from_orb_rgbd -> project_last_device -> search_by_projection_last_device (and project_frustum_device ->
 search_by_projection_map_device) with the sequential matcher oracle run on the restated queries."""
 import ctypes as C
@@ -8,8 +8,9 @@ import zlib
 import numpy as np
 import pytest
 
+import oracle_lib
 import synth_frames as sf
-from test_project_cpu import build_restatement
+from project_cases import T4, moved, restated_last, rot
 
 pytestmark = pytest.mark.gpu
 
@@ -18,16 +19,6 @@ TUM1 = (517.306408, 516.469215, 318.643040, 255.313989, 0.262383, -0.953104, -0.
 TUM1_NODIST = TUM1[:4] + (0, 0, 0, 0, 0) + TUM1[9:]
 NLEVELS, SCALE = 8, 1.2
 E_STATE, E_CAPACITY = -5, -4
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    L = build_restatement(tmp_path_factory.mktemp("proj_restate_gpu"))
-    L.pr_project_last.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + \
-        [C.c_void_p] * 4
-    L.pr_project_frustum.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_float, C.c_float, C.c_float] + \
-        [C.c_void_p] * 7
-    return L
 
 
 def camera(vals):
@@ -40,25 +31,6 @@ def camera(vals):
 
 def depth_image(t):
     return (sf.Scene(W, H, "desk", seed=3).depth_u16(t).astype(np.float32) / np.float32(5000.0))
-
-
-def rot(ax, ay, az):
-    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
-    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    return Rz @ Ry @ Rx
-
-
-def T4(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
-
-
-def moved(Tlw, d, R=np.eye(3)):
-    """Tcw of a camera displaced by d (and turned by R) in the last camera's coordinates: tlc == d."""
-    return T4(R, -R @ np.asarray(d, np.float64)) @ Tlw
 
 
 @pytest.fixture(scope="module")
@@ -79,26 +51,6 @@ def slots():
         bounds = tuple(float(b) for b in g.image_bounds(cam, W, H))
         out[name] = (g, cam, bounds, [g.fetch(s) + (frames[s][1],) for s in range(2)])
     return out, orb.GetScaleFactors().astype(np.float32)
-
-
-def restated_last(restate, slot_data, Tlw, Tcw, points, mpdesc, cam, scale, th, th_depth, mono, vo, bounds):
-    import psl_slam_amd as P
-    kun, dep, _, desc = slot_data
-    n = len(kun)
-    q = np.zeros(max(n, 1), P.PROJQUERY_DTYPE)
-    qd = np.zeros((max(n, 1), 32), np.uint8)
-    ow = np.zeros(max(n, 1), np.int32)
-    Tl, Tc = P.pose(Tlw).reshape(1), P.pose(Tcw).reshape(1)
-    b = np.asarray(bounds, np.float32)
-    kun, dep, desc = np.ascontiguousarray(kun), np.ascontiguousarray(dep), np.ascontiguousarray(desc)
-    cam1 = np.ascontiguousarray(cam).reshape(1)
-    pts = None if points is None else np.ascontiguousarray(points, P.LASTPOINT_DTYPE)
-    md = None if mpdesc is None else np.ascontiguousarray(mpdesc, np.uint8)
-    nq = restate.pr_project_last(kun.ctypes.data, desc.ctypes.data, dep.ctypes.data, n, Tl.ctypes.data, Tc.ctypes.data,
-                                 None if pts is None else pts.ctypes.data, None if md is None else md.ctypes.data, cam1.ctypes.data,
-                                 scale.ctypes.data, len(scale), th, th_depth, int(mono), int(vo), b.ctypes.data, q.ctypes.data,
-                                 qd.ctypes.data, ow.ctypes.data)
-    return q[:nq], qd[:nq], ow[:nq]
 
 
 def caller_points(rng, slot_data, cam, Tlw):
@@ -133,7 +85,7 @@ POSES = {   # displacement of the current camera in the last camera's coordinate
 @pytest.mark.parametrize("camname", ["tum1", "nodist"])
 @pytest.mark.parametrize("case", list(POSES))
 @pytest.mark.parametrize("vo", [0, 1])
-def test_project_last_equals_restatement(restate, slots, camname, case, vo):
+def test_project_last_equals_restatement(slots, camname, case, vo):
     out, scale = slots
     g, cam, bounds, data = out[camname]
     rng = np.random.default_rng(zlib.crc32(f"{camname} {case} {vo}".encode()))
@@ -147,7 +99,7 @@ def test_project_last_equals_restatement(restate, slots, camname, case, vo):
             if not with_points and not vo:
                 continue
             q, qd, ow = g.project_last(0, Tlw_p(Tlw), Tlw_p(Tcw), p_, m_, cam, scale, th, 3.0, mono, vo, bounds)
-            rq, rqd, row = restated_last(restate, data[0], Tlw, Tcw, p_, m_, cam, scale, th, 3.0, mono, vo, bounds)
+            rq, rqd, row = restated_last(data[0], Tlw, Tcw, p_, m_, cam, scale, th, 3.0, mono, vo, bounds)
             assert len(q) == len(rq) and len(q) > 50
             assert q.tobytes() == rq.tobytes(), "query rows differ from the restatement"
             np.testing.assert_array_equal(qd, rqd)
@@ -166,7 +118,7 @@ def Tlw_p(T):
     return P.pose(T)
 
 
-def test_project_last_depth_zero_and_bounds(restate, slots):
+def test_project_last_depth_zero_and_bounds(slots):
     """Points exactly at z == 0 of the current camera, just behind it and at the image border are not emitted (or emitted) exactly as
     the restatement says; VO with a depth cut of 0 visits the 101 closest keypoints."""
     import psl_slam_amd as P
@@ -181,12 +133,12 @@ def test_project_last_depth_zero_and_bounds(restate, slots):
     pts["z"] = rng.choice(np.float32([1.0, 0.999, 1.001, 3.0, -2.0]), n)       # z == 1: camera depth exactly 0
     pts["state"] = 2
     q, qd, ow = g.project_last(0, P.pose(Tlw), P.pose(Tcw), pts, None, cam, scale, 10.0, 3.0, False, False, bounds)
-    rq, rqd, row = restated_last(restate, data[0], Tlw, Tcw, pts, None, cam, scale, 10.0, 3.0, False, False, bounds)
+    rq, rqd, row = restated_last(data[0], Tlw, Tcw, pts, None, cam, scale, 10.0, 3.0, False, False, bounds)
     assert q.tobytes() == rq.tobytes() and (ow == row).all() and (qd == rqd).all()
     assert not np.isin(ow, np.flatnonzero(pts["z"] == np.float32(1.0))).any()
     assert np.isin(ow, np.flatnonzero(pts["z"] == np.float32(3.0))).any()
     q, qd, ow = g.project_last(0, P.pose(Tlw), P.pose(Tlw), None, None, cam, scale, 10.0, 0.0, False, True, bounds)
-    rq, rqd, row = restated_last(restate, data[0], Tlw, Tlw, None, None, cam, scale, 10.0, 0.0, False, True, bounds)
+    rq, rqd, row = restated_last(data[0], Tlw, Tlw, None, None, cam, scale, 10.0, 0.0, False, True, bounds)
     assert q.tobytes() == rq.tobytes() and (ow == row).all()
     assert 90 <= len(q) <= 101
 
@@ -253,23 +205,13 @@ def map_points(rng, n, Tcw):
     return mp, rng.integers(0, 256, (n, 32), dtype=np.uint8)
 
 
-def restated_frustum(restate, Tcw, mp, mpd, cam, scale, lsf, limit, th, bounds):
+def restated_frustum(Tcw, mp, mpd, cam, scale, lsf, limit, th, bounds):
     import psl_slam_amd as P
-    n = len(mp)
-    q = np.zeros(max(n, 1), P.PROJQUERY_DTYPE)
-    qd = np.zeros((max(n, 1), 32), np.uint8)
-    ow, iv, lv, vc = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
-    T = P.pose(Tcw).reshape(1)
-    b = np.asarray(bounds, np.float32)
-    mp, mpd, cam1 = np.ascontiguousarray(mp), np.ascontiguousarray(mpd), np.ascontiguousarray(cam).reshape(1)
-    nq = restate.pr_project_frustum(T.ctypes.data, mp.ctypes.data, mpd.ctypes.data, n, cam1.ctypes.data, scale.ctypes.data, len(scale),
-                                    lsf, limit, th, b.ctypes.data, q.ctypes.data, qd.ctypes.data, ow.ctypes.data, iv.ctypes.data,
-                                    lv.ctypes.data, vc.ctypes.data)
-    return q[:nq], qd[:nq], ow[:nq], iv[:n], lv[:n], vc[:n]
+    return oracle_lib.pr_project_frustum(P.pose(Tcw).reshape(1), mp, mpd, np.ascontiguousarray(cam).reshape(1), scale, lsf, limit, th, bounds)
 
 
 @pytest.mark.parametrize("th", [1.0, 3.0, 5.0])
-def test_project_frustum_equals_restatement(restate, slots, th):
+def test_project_frustum_equals_restatement(slots, th):
     import psl_slam_amd as P
     out, scale = slots
     _, cam, bounds, _ = out["tum1"]
@@ -278,7 +220,7 @@ def test_project_frustum_equals_restatement(restate, slots, th):
     Tcw = T4(rot(0.3, -0.1, 0.2), (0.5, 0.2, -1.0))
     mp, mpd = map_points(rng, 6000, Tcw)
     got = P.project_frustum(P.pose(Tcw), mp, mpd, cam, scale, lsf, 0.5, th, bounds)
-    ref = restated_frustum(restate, Tcw, mp, mpd, cam, scale, lsf, 0.5, th, bounds)
+    ref = restated_frustum(Tcw, mp, mpd, cam, scale, lsf, 0.5, th, bounds)
     for a, b, name in zip(got, ref, ("queries", "qdesc", "owner", "inview", "level", "viewcos")):
         assert len(a) == len(b) and a.tobytes() == b.tobytes(), f"{name} differ from the restatement"
     q, _, ow, iv, lv, vc = got
@@ -323,12 +265,11 @@ def test_project_frustum_capacity_is_reported(slots):
     assert rc == E_CAPACITY and nq.value == k
 
 
-def _chain(restate, style, B, seed):
+def _chain(style, B, seed):
     """extract_batch_device -> set_from_orb_rgbd -> project_last_device (VO, pair p: slot p -> slot p + 1) ->
     search_by_projection_last_device, and project_frustum_device -> search_by_projection_map_device, all on the device."""
     import torch
     import psl_slam_amd as P
-    import oracle_lib
     dev = torch.device("cuda", 0)
     sc = sf.Scene(W, H, style, seed)
     gray = np.ascontiguousarray(np.stack([sc.gray(t) for t in range(B)], 0))
@@ -405,14 +346,14 @@ def _chain(restate, style, B, seed):
     FQD, FNQ, FMATCH, FNM = fqd.cpu().numpy(), fnq.cpu().numpy(), fmatch.cpu().numpy(), fnm.cpu().numpy()
     checked = 0
     for p in sorted(k for k in data if k < npairs and nmp[k] > 0):
-        rq, rqd, row = restated_last(restate, data[p], Tl[p], Tc[p], None, None, cam, scale, 15.0, 3.0, False, True, bounds)
+        rq, rqd, row = restated_last(data[p], Tl[p], Tc[p], None, None, cam, scale, 15.0, 3.0, False, True, bounds)
         n = NQ[p]
         assert n == len(rq) and Q[p, :n].tobytes() == rq.tobytes(), f"pair {p}: query rows differ"
         assert (QD[p, :n] == rqd).all() and (OW[p, :n] == row).all()
         kun1, _, ur1, desc1 = data[p + 1]
         rnm, rmatch, _ = oracle_lib.search_by_projection_last(kun1, desc1, ur1, bounds, rq, rqd, None, True)
         assert NM[p] == rnm and (MATCH[p, :n] == rmatch).all(), f"pair {p}: matches differ from the oracle"
-        fr = restated_frustum(restate, Tc[p], mps[p, :nmp[p]], mpd[p, :nmp[p]], cam, scale, np.float32(lsf), 0.5, 1.0, bounds)
+        fr = restated_frustum(Tc[p], mps[p, :nmp[p]], mpd[p, :nmp[p]], cam, scale, np.float32(lsf), 0.5, 1.0, bounds)
         m = FNQ[p]
         assert m == len(fr[0]) and m <= cap and FQ[p, :m].tobytes() == fr[0].tobytes() and (FQD[p, :m] == fr[1]).all()
         fnm_, fm_, _ = oracle_lib.search_by_projection_map(kun1, desc1, ur1, bounds, fr[0], fr[1], None, 0.8)
@@ -425,5 +366,5 @@ def _chain(restate, style, B, seed):
 
 @pytest.mark.parametrize("style", ["desk", "sticks"])
 @pytest.mark.parametrize("B", [32, 97])
-def test_device_chain_equals_oracle(restate, style, B):
-    _chain(restate, style, B, seed=40 + B)
+def test_device_chain_equals_oracle(style, B):
+    _chain(style, B, seed=40 + B)

@@ -1,61 +1,17 @@
 """CPU checks of the stereo constructor (include/pslfe.h: pslfe_frame_set_from_orb_stereo): the sequential restatement the GPU
-tests compare with (tests/stereo_restate.cpp) against a literal numpy-float32 transcription of Frame::ComputeStereoMatches
+tests compare with (oracle/stereo_oracle.cpp) against a literal numpy-float32 transcription of Frame::ComputeStereoMatches
 (src/Frame.cc:1165-1340) on random keypoint sets, level images and edge cases; the depth it recovers on a constant-disparity
 pair; and the argument checks of the library, which need no GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import synth_frames as sf
 import stereo_scene as ss
+from oracle_lib import KEYPOINT_DTYPE, restate_stereo
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                           ("octave", "<i4"), ("class_id", "<i4")])
-
-
-def build_restatement(out_dir):
-    """g++ -ffp-contract=off build of tests/stereo_restate.cpp -> ctypes handle."""
-    so = os.path.join(str(out_dir), "libstereo_restate.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(ROOT, "tests", "stereo_restate.cpp"),
-                    "-o", so], check=True)
-    L = C.CDLL(so)
-    L.sr_stereo.restype = C.c_int
-    L.sr_stereo.argtypes = [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_float, C.c_float] + \
-        [C.c_void_p] * 4
-    return L
-
-
-def restate_stereo(L, kL, dL, kR, dR, levL, levR, scale, inv_scale, bf, fx):
-    """(uright, depth, idx_right, sad) of the restatement.  levL / levR: level images (2-D uint8 arrays of any row pitch)."""
-    kL, kR = np.ascontiguousarray(kL, KEYPOINT_DTYPE), np.ascontiguousarray(kR, KEYPOINT_DTYPE)
-    dL = np.ascontiguousarray(dL, np.uint8).reshape(-1, 32)
-    dR = np.ascontiguousarray(dR, np.uint8).reshape(-1, 32)
-    nl = len(levL)
-    ptr = lambda levs: (C.c_void_p * nl)(*[lv.ctypes.data for lv in levs])
-    pit = lambda levs: np.array([lv.strides[0] for lv in levs], np.int32)
-    for a, b in zip(levL, levR):
-        assert a.shape == b.shape and a.strides[1] == 1 and b.strides[1] == 1
-    lw = np.array([lv.shape[1] for lv in levL], np.int32)
-    lh = np.array([lv.shape[0] for lv in levL], np.int32)
-    pL, pR, sL, sR = ptr(levL), ptr(levR), pit(levL), pit(levR)
-    sc, isc = np.ascontiguousarray(scale, F32), np.ascontiguousarray(inv_scale, F32)
-    n = len(kL)
-    ur, dep = np.zeros(max(n, 1), F32), np.zeros(max(n, 1), F32)
-    idx, sad = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-    L.sr_stereo(kL.ctypes.data, dL.ctypes.data, n, kR.ctypes.data, dR.ctypes.data, len(kR), C.cast(pL, C.c_void_p), sL.ctypes.data,
-                C.cast(pR, C.c_void_p), sR.ctypes.data, lw.ctypes.data, lh.ctypes.data, sc.ctypes.data, isc.ctypes.data, nl, float(bf),
-                float(fx), ur.ctypes.data, dep.ctypes.data, idx.ctypes.data, sad.ctypes.data)
-    return ur[:n], dep[:n], idx[:n], sad[:n]
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_restatement(tmp_path_factory.mktemp("stereo_restate"))
 
 
 def _round(x):
@@ -231,13 +187,13 @@ CAMS = [(40.0, 517.3), (47.906, 435.2), (386.1448, 718.856), (0.5, 500.0)]
 
 
 @pytest.mark.parametrize("kind", KINDS)
-def test_restatement_equals_transcription(restate, kind):
+def test_restatement_equals_transcription(kind):
     rng = np.random.default_rng(zlib_seed(kind))
     seen = dict(sad=0, filtered=0, edge=0, empty=0)
     for rep in range(30):
         kL, dL, kR, dR, levL, levR, scale, inv = random_case(rng, kind)
         bf, fx = CAMS[rep % len(CAMS)]
-        got = restate_stereo(restate, kL, dL, kR, dR, levL, levR, scale, inv, bf, fx)
+        got = restate_stereo(kL, dL, kR, dR, levL, levR, scale, inv, bf, fx)
         want = transcription(kL, dL, kR, dR, levL, levR, scale, inv, bf, fx)
         for g, x, name in zip(got, want, ("uright", "depth", "idx", "sad")):
             assert g.tobytes() == x.tobytes(), f"{kind} #{rep}: {name} differs"
@@ -256,7 +212,7 @@ def zlib_seed(s):
     return zlib.crc32(s.encode())
 
 
-def test_restatement_bestinc_edges_and_median(restate):
+def test_restatement_bestinc_edges_and_median():
     """A window sweep whose minimum sits at incR = +-5 is rejected; the median filter drops the worst SADs."""
     rng = np.random.default_rng(5)
     scale = sf.orb_scale_factors(8, 1.2)
@@ -276,7 +232,7 @@ def test_restatement_bestinc_edges_and_median(restate):
     kR["x"][:10] += F32(5.0)       # right keypoint 5 px off: the minimum at incR = -5 -> rejected
     kR["x"][10:20] += F32(3.0)
     dL = rng.integers(0, 256, (n, 32), dtype=np.uint8)
-    ur, dep, idx, sad = restate_stereo(restate, kL, dL, kR, dL.copy(), levL, levR, scale, inv, 40.0, 500.0)
+    ur, dep, idx, sad = restate_stereo(kL, dL, kR, dL.copy(), levL, levR, scale, inv, 40.0, 500.0)
     want = transcription(kL, dL, kR, dL.copy(), levL, levR, scale, inv, 40.0, 500.0)
     assert all(a.tobytes() == b.tobytes() for a, b in zip((ur, dep, idx, sad), want))
     assert (idx == np.arange(n)).all()
@@ -284,7 +240,7 @@ def test_restatement_bestinc_edges_and_median(restate):
     assert (dep[10:] > 0).any()
 
 
-def test_constant_disparity_depth(restate):
+def test_constant_disparity_depth():
     """On a pair shifted by a constant disparity the recovered depth is bf/d within 1 % for most accepted keypoints (sanity,
     not parity).  Keypoints and pyramids from the CPU oracle of the extractor."""
     import oracle_lib
@@ -298,7 +254,7 @@ def test_constant_disparity_depth(restate):
     levR = [oR.level_image(l) for l in range(8)]
     scale = sf.orb_scale_factors(8, 1.2)
     inv = (F32(1.0) / scale).astype(F32)
-    ur, dep, idx, sad = restate_stereo(restate, kL, dL, kR, dR, levL, levR, scale, inv, bf, 517.3)
+    ur, dep, idx, sad = restate_stereo(kL, dL, kR, dR, levL, levR, scale, inv, bf, 517.3)
     ok = dep > 0
     assert ok.sum() >= 100, ok.sum()
     rel = np.abs(dep[ok] / (bf / d) - 1.0)

@@ -1,5 +1,5 @@
 """GPU parity of the stereo constructor (pslfe_frame_set_from_orb_stereo): mvuRight, mvDepth, the taps, mvKeysUn and the grid CSR
-equal, bit for bit, the sequential restatement tests/stereo_restate.cpp fed with the extractor's keypoints and pyramid (and with
+equal, bit for bit, the sequential restatement oracle/stereo_oracle.cpp fed with the extractor's keypoints and pyramid (and with
 the CPU oracle's), plus the oracle's undistortion and grid; at the TUM1 (distorted), EuRoC and KITTI geometries, for one-pair
 calls, 257-pair batches through one or two extractors, the edge cases of tests/stereo_scene.py, the device chain into
 SearchByProjection, the argument checks and the compiled C++ consumer of host/pslfe.hpp."""
@@ -12,19 +12,14 @@ import numpy as np
 import pytest
 
 import stereo_scene as ss
-from test_project_cpu import build_restatement as build_proj_restatement
-from test_stereo_cpu import build_restatement, restate_stereo
+from oracle_lib import restate_stereo
+from project_cases import T4, moved, restated_last, rot
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NLEVELS, SCALE = 8, 1.2
 E_INVALID, E_CAPACITY, E_STATE = -1, -4, -5
-
-
-@pytest.fixture(scope="module")
-def restate(tmp_path_factory):
-    return build_restatement(tmp_path_factory.mktemp("stereo_restate_gpu"))
 
 
 def camera(vals):
@@ -35,10 +30,10 @@ def camera(vals):
     return cam
 
 
-def expected(restate, kL, dL, kR, dR, levL, levR, scale, inv, cam, w, h):
+def expected(kL, dL, kR, dR, levL, levR, scale, inv, cam, w, h):
     """The restatement's mvuRight / mvDepth / taps, the oracle's UndistortKeyPoints, ComputeImageBounds and grid."""
     import oracle_lib
-    ur, dep, idx, sad = restate_stereo(restate, kL, dL, kR, dR, levL, levR, scale, inv, float(cam["bf"]), float(cam["fx"]))
+    ur, dep, idx, sad = restate_stereo(kL, dL, kR, dR, levL, levR, scale, inv, float(cam["bf"]), float(cam["fx"]))
     un, _, _ = oracle_lib.frame_post_rgbd(kL, np.zeros((h, w), np.float32), cam)
     start, gidx = oracle_lib.grid_build(un, oracle_lib.image_bounds(cam, w, h))
     return dict(uright=ur, depth=dep, idx=idx, sad=sad, kun=un, start=start, gidx=gidx)
@@ -79,7 +74,7 @@ def factors(orb):
 
 
 @pytest.mark.parametrize("geom", list(ss.GEOMETRIES))
-def test_one_pair_equals_restatement_and_oracle(restate, geom):
+def test_one_pair_equals_restatement_and_oracle(geom):
     import oracle_lib
     G = ss.GEOMETRIES[geom]
     w, h, cam = G["w"], G["h"], camera(G["cam"])
@@ -87,7 +82,7 @@ def test_one_pair_equals_restatement_and_oracle(restate, geom):
     g, oL, oR, (kL, dL, kR, dR) = host_pair(left, right, G["nfeatures"], cam)
     got = slot_outputs(g, 0)
     scale, inv = factors(oL)
-    want = expected(restate, kL, dL, kR, dR, levels(oL, 0), levels(oR, 0), scale, inv, cam, w, h)
+    want = expected(kL, dL, kR, dR, levels(oL, 0), levels(oR, 0), scale, inv, cam, w, h)
     assert_same(got, want, f"{geom}: device keypoints and pyramids")
     acc = (got["sad"] >= 0).sum()
     assert len(kL) > 0.5 * G["nfeatures"] and acc > 0.3 * len(kL) and (got["depth"] > 0).sum() > 0.2 * len(kL), (len(kL), acc)
@@ -97,20 +92,20 @@ def test_one_pair_equals_restatement_and_oracle(restate, geom):
     xL, xR = oracle_lib.OracleORB(G["nfeatures"], SCALE, NLEVELS, 20, 7), oracle_lib.OracleORB(G["nfeatures"], SCALE, NLEVELS, 20, 7)
     okL, odL = xL(left)
     okR, odR = xR(right)
-    want_o = expected(restate, okL, odL, okR, odR, [xL.level_image(l) for l in range(NLEVELS)], [xR.level_image(l) for l in range(NLEVELS)],
+    want_o = expected(okL, odL, okR, odR, [xL.level_image(l) for l in range(NLEVELS)], [xR.level_image(l) for l in range(NLEVELS)],
                       scale, inv, cam, w, h)
     assert_same(got, want_o, f"{geom}: oracle keypoints and pyramids")
 
 
 @pytest.mark.parametrize("geom", list(ss.GEOMETRIES))
-def test_edge_cases_equal_restatement(restate, geom):
+def test_edge_cases_equal_restatement(geom):
     G = ss.GEOMETRIES[geom]
     w, h, cam = G["w"], G["h"], camera(G["cam"])
     for name, (left, right) in ss.edge_cases(w, h).items():
         g, oL, oR, (kL, dL, kR, dR) = host_pair(left, right, G["nfeatures"], cam)
         got = slot_outputs(g, 0)
         scale, inv = factors(oL)
-        want = expected(restate, kL, dL, kR, dR, levels(oL, 0), levels(oR, 0), scale, inv, cam, w, h)
+        want = expected(kL, dL, kR, dR, levels(oL, 0), levels(oR, 0), scale, inv, cam, w, h)
         assert_same(got, want, f"{geom}/{name}")
         if name == "flat_right":
             assert len(kR) == 0 and (got["idx"] == -1).all() and (got["uright"] == -1).all()
@@ -128,7 +123,7 @@ def _batch_images(w, h, bf, zscale, npairs, ndistinct=12):
 
 
 @pytest.mark.parametrize("geom", list(ss.GEOMETRIES))
-def test_batch_one_and_two_handles_equal_per_pair_calls(restate, geom):
+def test_batch_one_and_two_handles_equal_per_pair_calls(geom):
     import torch
     import psl_slam_amd as P
     G = ss.GEOMETRIES[geom]
@@ -161,7 +156,7 @@ def test_batch_one_and_two_handles_equal_per_pair_calls(restate, geom):
         if p in samples:
             kL, dLp = oa.fetch(p, w, h)
             kR, dRp = ob.fetch(p, w, h)
-            want = expected(restate, kL, dLp, kR, dRp, levels(oa, p), levels(ob, p), scale, inv, cam, w, h)
+            want = expected(kL, dLp, kR, dRp, levels(oa, p), levels(ob, p), scale, inv, cam, w, h)
             assert_same(a, want, f"{geom} pair {p}: batch vs restatement")
             gs, _, _, _ = host_pair(Ls[p], Rs[p], nf, cam, ctx=ctx)
             assert_same(a, slot_outputs(gs, 0), f"{geom} pair {p}: batch vs one-pair call")
@@ -169,16 +164,12 @@ def test_batch_one_and_two_handles_equal_per_pair_calls(restate, geom):
     ctx.synchronize()
 
 
-def test_device_chain_into_search_by_projection(restate, tmp_path):
+def test_device_chain_into_search_by_projection():
     """Stereo slots -> project_last_device (visual-odometry points from the stereo mvDepth) -> search_by_projection_last_device,
-    against tests/proj_restate.cpp fed with the stereo restatement's mvKeysUn / mvDepth / mvuRight and the sequential matcher oracle."""
+    against oracle/project_oracle.cpp fed with the stereo restatement's mvKeysUn / mvDepth / mvuRight and the sequential matcher oracle."""
     import torch
     import psl_slam_amd as P
     import oracle_lib
-    from test_project_gpu import T4, moved, restated_last, rot
-    pr = build_proj_restatement(tmp_path)
-    pr.pr_project_last.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + \
-        [C.c_void_p] * 4
     G = ss.GEOMETRIES["euroc"]
     w, h, cam, nf = G["w"], G["h"], camera(G["cam"]), G["nfeatures"]
     B = 6
@@ -216,11 +207,11 @@ def test_device_chain_into_search_by_projection(restate, tmp_path):
     for t in range(B):
         kL, dL = orb.fetch(t, w, h)
         kR, dR = orb.fetch(B + t, w, h)
-        e = expected(restate, kL, dL, kR, dR, levels(orb, t), levels(orb, B + t), scale, inv, cam, w, h)
+        e = expected(kL, dL, kR, dR, levels(orb, t), levels(orb, B + t), scale, inv, cam, w, h)
         assert_same(slot_outputs(g, t), e, f"chain frame {t}")
         restated.append((e["kun"], e["depth"], e["uright"], dL))
     for p in range(npairs):
-        rq, rqd, row = restated_last(pr, restated[p], Tl[p], Tc[p], None, None, cam, scale, 15.0,
+        rq, rqd, row = restated_last(restated[p], Tl[p], Tc[p], None, None, cam, scale, 15.0,
                                      np.float32(35.0 * float(cam["bf"]) / float(cam["fx"])), False, True, bounds)
         n = NQ[p]
         assert n == len(rq) and n > 50 and Q[p, :n].tobytes() == rq.tobytes(), f"pair {p}: query rows differ"

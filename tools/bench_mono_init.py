@@ -1,7 +1,7 @@
 """Measurement of the monocular initialiser's matcher (pslfe_orb_search_for_initialization_device) beside the ORB extraction of
 the second frames it matches, at TUM1 640x480 with the initialiser's 2000 features and KITTI 1241x376 with 4000: for N pairs per
 launch it reports the event-timed `match.mono_init` stage next to the `orb.*` stages (and `frame.mono`, `match.grid`) of the N
-F2 frames extracted as one batch, the one-pair latency through the host path, and the restatement tests/mono_init_restate.cpp
+F2 frames extracted as one batch, the one-pair latency through the host path, and the restatement oracle/mono_init_oracle.cpp
 timed on one host core.  The device extractor refuses 4000 features (a level quota above its 512-node octree), so at KITTI the
 frames come from the CPU oracle of the extractor (8 distinct F2 frames, pair p matching frame 1 + p % 8) and the ORB column is
 the 2000-feature extraction of the same N frames, for scale.  Prints one JSON line (and writes it with --out).  Also meant to run
@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -124,10 +123,9 @@ def one_pair(P, ctx, G, cam, frames, oracle_frames, reps):
 
 
 def restatement_ms(P, ctx, G, cam, frames, oracle_frames, reps):
-    import test_mono_init_cpu as T
+    import oracle_lib
     w, h = G["w"], G["h"]
     if oracle_frames is None:
-        import oracle_lib
         orb = P.ORBextractor(G["nfeatures"], 1.2, 8, 20, 7, ctx=ctx)
         g = P.FrameGrid(orb.max_keypoints(w, h), 2, ctx=ctx)
         kd = []
@@ -139,13 +137,12 @@ def restatement_ms(P, ctx, G, cam, frames, oracle_frames, reps):
     else:
         kd, bounds = oracle_frames[:2], (0.0, 0.0, float(w), float(h))
     prev = np.stack([kd[0][0]["x"], kd[0][0]["y"]], 1).astype(np.float32)
-    with tempfile.TemporaryDirectory() as d:
-        R = T.build_restatement(d)
-        ts = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            T.restate_search(R, kd[0][0], kd[0][1], kd[1][0], kd[1][1], bounds, prev, 100, 0.9, True)
-            ts.append((time.perf_counter() - t0) * 1e3)
+    oracle_lib.load()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        oracle_lib.restate_search(kd[0][0], kd[0][1], kd[1][0], kd[1][1], bounds, prev, 100, 0.9, True)
+        ts.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ts))
 
 

@@ -2,7 +2,7 @@
 640x480, EuRoC 752x480 and KITTI 1241x376 geometries (tests/stereo_scene.py): for N pairs extracted as ONE batch of 2N frames
 (lefts, then rights) it reports the event-timed `orb.*` stages and `frame.stereo` per launch, pairs/s, the one-pair latency
 through the host path (two extractors + the stereo call + fetch, and the part the stereo call adds), and the restatement
-tests/stereo_restate.cpp timed on one host core.  Prints one JSON line (and writes it with --out).  Also meant to run under
+oracle/stereo_oracle.cpp timed on one host core.  Prints one JSON line (and writes it with --out).  Also meant to run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_stereo.py --quick`.
 
 Usage: python tools/bench_stereo.py [--pairs 1,32,12288] [--kitti-max 6144] [--reps 3] [--quick] [--out FILE]
@@ -11,7 +11,6 @@ import argparse
 import json
 import os
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -90,7 +89,7 @@ def one_pair(P, ctx, G, cam, pair, reps):
 
 
 def restatement_ms(P, ctx, G, cam, pair, reps):
-    import test_stereo_cpu as T
+    import oracle_lib
     w, h, nf = G["w"], G["h"], G["nfeatures"]
     oL, oR = P.ORBextractor(nf, 1.2, 8, 20, 7, ctx=ctx), P.ORBextractor(nf, 1.2, 8, 20, 7, ctx=ctx)
     kL, dL = oL(pair[0])
@@ -98,13 +97,12 @@ def restatement_ms(P, ctx, G, cam, pair, reps):
     levL = [oL.debug_level_image(0, l) for l in range(8)]
     levR = [oR.debug_level_image(0, l) for l in range(8)]
     sc, inv = oL.GetScaleFactors().astype(np.float32), oL.GetInverseScaleFactors().astype(np.float32)
-    with tempfile.TemporaryDirectory() as d:
-        R = T.build_restatement(d)
-        ts = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            T.restate_stereo(R, kL, dL, kR, dR, levL, levR, sc, inv, float(cam["bf"]), float(cam["fx"]))
-            ts.append((time.perf_counter() - t0) * 1e3)
+    oracle_lib.load()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        oracle_lib.restate_stereo(kL, dL, kR, dR, levL, levR, sc, inv, float(cam["bf"]), float(cam["fx"]))
+        ts.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ts))
 
 
