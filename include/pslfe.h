@@ -702,6 +702,49 @@ int pslfe_kf_window_best(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQue
 int pslfe_kf_search_by_sim3(pslfe_kf* k, pslfe_frame* f1, int slot1, pslfe_frame* f2, int slot2, const PslProjQuery* q12,
                             const uint8_t* qdesc1, int n1, const PslProjQuery* q21, const uint8_t* qdesc2, int n2,
                             int32_t* match12, int* nfound);
+/* == ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) src/ORBmatcher.cc:522-655 (LoopClosing::ComputeSim3, src/LoopClosing.cc:265),
+ *    from the point where the two FeatureVectors are walked.  Slot `slot2` of f2 holds KF2 (mvKeysUn, descriptors).
+ *    - fidx2: pKF2->mFeatVec flattened in node order, keeping only the features whose map point exists and is not bad - the
+ *      caller applies `!pMP2` :576 and `pMP2->isBad()` :579 by leaving the others out.  A feature appears at most once and the
+ *      runs of two nodes do not overlap (PSLFE_E_INVALID otherwise): that is what a FeatureVector is, and what lets nodes run
+ *      side by side;
+ *    - one query per KF1 feature whose map point exists and is not bad (:558-562), in the reference's iteration order (common
+ *      nodes ascending :550-632, f1it->second order :554): [start, start+len) = the run of fidx2 that is the shared node's index
+ *      list in KF2, angle = pKF1->mvKeysUn[idx1].angle, qdesc = Descriptors1.row(idx1); the queries of one node are consecutive;
+ *    - :566-596: bestDist1 = the first strict minimum in run order, bestDist2 = the second smallest distance (256 when there is
+ *      none), a KF2 feature taken by an earlier query is skipped (vbMatched2 :576, set at :603);
+ *    - :598-600: accepted when bestDist1 < TH_LOW = 50, STRICTLY (pslfe_orb_search_by_bow, the (pKF, F) overload, has <= :228),
+ *      and (float)bestDist1 < nnratio*(float)bestDist2 (float multiply, no contraction);
+ *    - :605-615, :634-652: rot = angle1 - angle2 (+360 when negative), bin = round(rot*(1.0f/30)), bin 30 -> 0,
+ *      ComputeThreeMaxima :1601-1645; a match in a non-maximum bin is cleared but its KF2 feature stays marked (vbMatched2 is
+ *      only read inside the candidate loop).
+ *    match[i] = KF2 feature of query i or -1 (vpMatches12[idx1] = vpMapPoints2[match[i]]); *nmatches = the return value. */
+int pslfe_kf_search_by_bow(pslfe_kf* k, pslfe_frame* f2, int slot2, const int32_t* fidx2, int nfidx2, const PslBowQuery* queries,
+                           const uint8_t* qdesc, int nq, float nnratio, int check_orientation, int32_t* match, int* nmatches);
+/* The candidate loop of LoopClosing::ComputeSim3 src/LoopClosing.cc:252-284 in one call: candidate c is slot slots2[c] of f2, its
+ * flattened FeatureVector fidx2[fidx2_off[c] .. fidx2_off[c+1]), its queries (those of the CURRENT keyframe against this candidate;
+ * start is relative to fidx2_off[c]) queries / qdesc [q_off[c] .. q_off[c+1]); both offset arrays have ncand+1 ascending entries
+ * starting at 0.  Candidates are independent: match rows q_off[c].. and nmatches[c] equal what pslfe_kf_search_by_bow gives for
+ * candidate c alone.  One upload, one launch chain sized by the queries and node runs of all candidates, one synchronisation. */
+int pslfe_kf_search_by_bow_candidates(pslfe_kf* k, pslfe_frame* f2, const int32_t* slots2, int ncand, const int32_t* fidx2,
+                                      const int32_t* fidx2_off, const PslBowQuery* queries, const uint8_t* qdesc,
+                                      const int32_t* q_off, float nnratio, int check_orientation, int32_t* match,
+                                      int32_t* nmatches);
+/* == ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290-403 (src/LoopClosing.cc:375) after
+ *    the projection.  The host decomposes Scw :299-303, projects and applies the gates of :316-357 (isBad, spAlreadyFound, depth,
+ *    IsInImage, distance range, viewing angle, PredictScale) and passes, per map point of vpPoints in order: u, v, radius =
+ *    th*mvScaleFactors[nPredictedLevel] :360, max_level = nPredictedLevel (min_level, ur, angle, blocks are ignored), its
+ *    descriptor; radius < 0 for a point dropped before the search - exactly the queries of pslfe_kf_window_best.
+ *    - :362 KeyFrame::GetFeaturesInArea(u, v, radius) src/KeyFrame.cc:685-724 on the grid of slot `slot`, same visiting order as
+ *      pslfe_kf_window_best;
+ *    - :375 a keypoint with vpMatched[idx] != NULL is skipped: taken[idx] != 0 on entry (taken: n bytes, NULL = none), or given
+ *      to an earlier map point of this call at :396 - the first-come rule, reproduced exactly;
+ *    - :380 octaves max_level-1 .. max_level; :387 the smallest distance, first visited on ties;
+ *    - :394 accepted when bestDist <= TH_LOW = 50; the keypoint is then occupied :396.
+ *    match[i] = keypoint of map point i or -1; assigned[c] (n entries, may be NULL) = the map point now in vpMatched[c] or -1
+ *    (entry marks excluded: vpMatched[c] = vpPoints[assigned[c]] where assigned[c] >= 0); *nmatches = the return value. */
+int pslfe_kf_search_by_projection_sim3(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const uint8_t* qdesc,
+                                       int nq, const uint8_t* taken, int32_t* match, int32_t* assigned, int* nmatches);
 /* One feature of KF1 in ORBmatcher::SearchForTriangulation, in the reference's iteration order (common vocabulary nodes
  * ascending, f1it->second order; features that have a map point and, under bOnlyStereo, those without a right coordinate
  * are dropped by the caller, :699-711). */

@@ -1093,7 +1093,8 @@ assert TRIQUERY_DTYPE.itemsize == 24 and LINEFUSEQUERY_DTYPE.itemsize == 24
 
 class KeyFrameMatcher:
     """The KeyFrame-rate searches of LocalMapping / LoopClosing (pslfe_kf): ORBmatcher::Fuse (both), SearchBySim3,
-    SearchForTriangulation (src/ORBmatcher.cc:657-1326), LSDmatcher::Fuse / SearchForTriangulation
+    SearchForTriangulation (src/ORBmatcher.cc:657-1326), SearchByBoW(pKF1, pKF2) and SearchByProjection(pKF, Scw, ...) of
+    LoopClosing::ComputeSim3 (src/ORBmatcher.cc:290-403, 522-655), LSDmatcher::Fuse / SearchForTriangulation
     (add_src/LSDmatcher.cpp:705-984) and Map{Point,Line}::ComputeDistinctiveDescriptors, from the point where the host has
     projected its map points.  Give each host thread its own Context + KeyFrameMatcher."""
 
@@ -1157,6 +1158,64 @@ class KeyFrameMatcher:
                                                        C.c_int(1 if bOnlyStereo else 0), C.c_int(1 if checkOri else 0), _ptr(sf), _ptr(s2),
                                                        C.c_int(len(sf)), _ptr(match), C.byref(nm)), "pslfe_kf_search_for_triangulation")
         return nm.value, match[:len(q)]
+
+    @staticmethod
+    def _bow_queries(runs, qangle, qdesc):
+        q = np.zeros(len(runs), BOWQUERY_DTYPE)
+        if len(runs):
+            r = np.asarray(runs, np.int32).reshape(-1, 2)
+            q["start"], q["len"], q["angle"] = r[:, 0], r[:, 1], np.asarray(qangle, np.float32)
+        return q, np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+
+    def SearchByBoW(self, frame, slot2, fidx2, runs, qangle, qdesc, nnratio=0.75, check_ori=True):
+        """SearchByBoW(pKF1, pKF2, vpMatches12) src/ORBmatcher.cc:522: slot2 holds KF2; fidx2 = its FeatureVector flattened in node
+        order, features without a good map point left out; runs[i] = (start, len) of query i's node in fidx2; qangle / qdesc per
+        KF1 feature with a good map point.  -> (nmatches, match per query)."""
+        fidx = np.ascontiguousarray(fidx2, np.int32)
+        q, qd = self._bow_queries(runs, qangle, qdesc)
+        match = np.full(max(len(q), 1), -1, np.int32)
+        nm = C.c_int()
+        _check(lib().pslfe_kf_search_by_bow(self._h, frame._h, C.c_int(slot2), _ptr(fidx), C.c_int(len(fidx)), _ptr(q), _ptr(qd),
+                                            C.c_int(len(q)), C.c_float(nnratio), C.c_int(1 if check_ori else 0), _ptr(match),
+                                            C.byref(nm)), "pslfe_kf_search_by_bow")
+        return nm.value, match[:len(q)]
+
+    def SearchByBoWCandidates(self, frame, slots2, fidx2, runs, qangle, qdesc, nnratio=0.75, check_ori=True):
+        """The candidate loop of LoopClosing::ComputeSim3 src/LoopClosing.cc:252-284: one list entry per candidate in every argument
+        (slots2[c], fidx2[c], runs[c], qangle[c], qdesc[c] as SearchByBoW takes them).  -> (nmatches[c], [match of candidate c])."""
+        nc = len(slots2)
+        slots = np.ascontiguousarray(slots2, np.int32)
+        fl = [np.ascontiguousarray(f, np.int32).reshape(-1) for f in fidx2]
+        ql = [self._bow_queries(runs[c], qangle[c], qdesc[c]) for c in range(nc)]
+        foff = np.zeros(nc + 1, np.int32)
+        qoff = np.zeros(nc + 1, np.int32)
+        foff[1:] = np.cumsum([len(f) for f in fl])
+        qoff[1:] = np.cumsum([len(q) for q, _ in ql])
+        fidx = np.concatenate(fl) if nc else np.zeros(0, np.int32)
+        q = np.concatenate([q for q, _ in ql]) if nc else np.zeros(0, BOWQUERY_DTYPE)
+        qd = np.concatenate([d for _, d in ql]) if nc else np.zeros((0, 32), np.uint8)
+        match = np.full(max(len(q), 1), -1, np.int32)
+        nm = np.zeros(max(nc, 1), np.int32)
+        _check(lib().pslfe_kf_search_by_bow_candidates(self._h, frame._h, _ptr(slots), C.c_int(nc), _ptr(fidx), _ptr(foff), _ptr(q), _ptr(qd),
+                                                       _ptr(qoff), C.c_float(nnratio), C.c_int(1 if check_ori else 0), _ptr(match), _ptr(nm)),
+               "pslfe_kf_search_by_bow_candidates")
+        return nm[:nc], [match[qoff[c]:qoff[c + 1]] for c in range(nc)]
+
+    def SearchByProjectionSim3(self, frame, slot, queries, qdesc, taken=None):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290 after the projection: queries as for
+        FuseSim3, taken[idx] = vpMatched[idx] != NULL on entry.  -> (nmatches, match per map point, assigned per keypoint)."""
+        q = np.ascontiguousarray(queries, PROJQUERY_DTYPE)
+        qd = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+        n = frame.n[slot]
+        tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        if tk is not None and len(tk) != n:
+            raise PslfeError(f"SearchByProjectionSim3: taken has {len(tk)} entries, the keyframe {n} keypoints")
+        match = np.full(max(len(q), 1), -1, np.int32)
+        assigned = np.full(max(n, 1), -1, np.int32)
+        nm = C.c_int()
+        _check(lib().pslfe_kf_search_by_projection_sim3(self._h, frame._h, C.c_int(slot), _ptr(q), _ptr(qd), C.c_int(len(q)), _ptr(tk),
+                                                        _ptr(match), _ptr(assigned), C.byref(nm)), "pslfe_kf_search_by_projection_sim3")
+        return nm.value, match[:len(q)], assigned[:n]
 
     def LineFuse(self, keylines, desc, queries, qdesc):
         """Search of LSDmatcher::Fuse add_src/LSDmatcher.cpp:933-958 -> (bestIdx, bestDist)."""

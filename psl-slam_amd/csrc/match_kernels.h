@@ -235,6 +235,10 @@ struct pslfe_frame {
     std::vector<char> slot_stereo; // the slot was set by pslfe_frame_set_from_orb_stereo (its taps are valid)
 };
 
+struct pslfe_kf {   // pslfe_kf.hip, pslfe_loop.hip: the per-call buffers come from the context's scratch arena
+    pslfe_ctx* ctx = nullptr;
+};
+
 // pslfe_match.hip, for pslfe_stereo.hip: frames of an extractor's result arrays (pointers at the first frame) -> slots
 // slot0.., and the constructor's tail on those slots (bounds of a cols x rows image, UndistortKeyPoints, grid)
 extern "C" int psl_frame_import(pslfe_frame* f, int slot0, const PslKeyPoint* okps, const uint8_t* odesc, const int* ocounts, int ocap,

@@ -325,10 +325,6 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-struct pslfe_kf {   // the per-call buffers come from the context's scratch arena
-    pslfe_ctx* ctx = nullptr;
-};
-
 namespace {
 int check_slot(pslfe_frame* f, int slot, const char* who) {
     PSL_REQUIRE(f, PSLFE_E_INVALID, "%s: NULL frame", who);

@@ -755,6 +755,45 @@ public:
                                                 (int)scaleFactors.size(), match.data(), &nm), "pslfe_kf_search_for_triangulation");
         return nm;
     }
+    // SearchByBoW(pKF1, pKF2, vpMatches12) src/ORBmatcher.cc:522: fidx2 = KF2's FeatureVector flattened in node order without the
+    // features that have no good map point; one query per KF1 feature with a good map point.  Returns nmatches.
+    int SearchByBoW(FrameGrid& kf2, int slot2, const std::vector<int32_t>& fidx2, const std::vector<PslBowQuery>& q,
+                    const std::vector<uint8_t>& qdesc, std::vector<int32_t>& match, float nnratio = 0.75f, bool checkOrientation = true) {
+        match.assign(q.size(), -1);
+        int nm = 0;
+        check(pslfe_kf_search_by_bow(h_, kf2.get(), slot2, fidx2.data(), (int)fidx2.size(), q.data(), qdesc.data(), (int)q.size(), nnratio,
+                                     checkOrientation, match.data(), &nm), "pslfe_kf_search_by_bow");
+        return nm;
+    }
+    // the candidate loop of LoopClosing::ComputeSim3 src/LoopClosing.cc:252-284: candidate c = slot slots2[c], fidx2 / q / qdesc
+    // concatenated over the candidates with fidx2Off / qOff (ncand + 1 entries from 0); nmatches[c] per candidate
+    void SearchByBoWCandidates(FrameGrid& kf2, const std::vector<int32_t>& slots2, const std::vector<int32_t>& fidx2,
+                               const std::vector<int32_t>& fidx2Off, const std::vector<PslBowQuery>& q, const std::vector<uint8_t>& qdesc,
+                               const std::vector<int32_t>& qOff, std::vector<int32_t>& match, std::vector<int32_t>& nmatches,
+                               float nnratio = 0.75f, bool checkOrientation = true) {
+        if (fidx2Off.size() != slots2.size() + 1 || qOff.size() != slots2.size() + 1)
+            throw Error(PSLFE_E_INVALID, "SearchByBoWCandidates: the offset arrays need one entry more than there are candidates");
+        match.assign(q.size(), -1);
+        nmatches.assign(slots2.size(), 0);
+        check(pslfe_kf_search_by_bow_candidates(h_, kf2.get(), slots2.data(), (int)slots2.size(), fidx2.data(), fidx2Off.data(), q.data(),
+                                                qdesc.data(), qOff.data(), nnratio, checkOrientation, match.data(), nmatches.data()),
+              "pslfe_kf_search_by_bow_candidates");
+    }
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290 after the projection; taken: vpMatched[idx] != NULL
+    // on entry, one byte per keypoint of the slot (empty = none).  assigned[c] = the map point now in vpMatched[c] or -1, sized here
+    // by the slot's own keypoint count.  Returns nmatches.
+    int SearchByProjectionSim3(FrameGrid& kf, int slot, const std::vector<PslProjQuery>& q, const std::vector<uint8_t>& qdesc,
+                               const std::vector<uint8_t>& taken, std::vector<int32_t>& match, std::vector<int32_t>& assigned) {
+        int n = 0;
+        check(pslfe_frame_fetch(kf.get(), slot, nullptr, nullptr, nullptr, 0x7fffffff, &n), "pslfe_frame_fetch");
+        if (!taken.empty() && (int)taken.size() != n) throw Error(PSLFE_E_INVALID, "SearchByProjectionSim3: taken needs one entry per keypoint of the slot");
+        match.assign(q.size(), -1);
+        assigned.assign(n, -1);
+        int nm = 0;
+        check(pslfe_kf_search_by_projection_sim3(h_, kf.get(), slot, q.data(), qdesc.data(), (int)q.size(), taken.empty() ? nullptr : taken.data(),
+                                                 match.data(), assigned.data(), &nm), "pslfe_kf_search_by_projection_sim3");
+        return nm;
+    }
     void LineFuse(const std::vector<PslKeyLine>& kls, const std::vector<uint8_t>& desc, const std::vector<PslLineFuseQuery>& q,
                   const std::vector<uint8_t>& qdesc, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
         bestIdx.assign(q.size(), -1); bestDist.assign(q.size(), 256);
