@@ -1,5 +1,15 @@
-// Shared by pslfe_match.hip and pslfe_kf.hip: the frame store (keypoints bucketed on the 64x48 grid of include/Frame.h:45-46),
-// the GetFeaturesInArea window as CSR runs, candidate keys and wave helpers.  Product code.
+// The matcher primitives of every ORB search on the device.  Product code.
+// Users: pslfe_match.hip (Tracking searches, SearchByBoW), pslfe_kf.hip (Fuse, SearchBySim3, SearchForTriangulation),
+// pslfe_mono.hip (SearchForInitialization), pslfe_loop.hip (loop-closing searches), pslfe_stereo.hip / stereo_kernels.h
+// (ComputeStereoMatches), pslfe_project.hip (frame store only), pslfe_bow.hip and pslfe_linematch.hip (Hamming and wave helpers).
+// What it offers:
+//   frame store       FrameMeta / FrameStore / FrameView: keypoints bucketed on the 64x48 grid of include/Frame.h:45-46 as CSR runs
+//   wave helpers      psl_wave_min_u32, psl_wave_sum, psl_merge2 / psl_wave_min2 (two smallest keys), psl_wave_sort, psl_topk_merge
+//   Hamming           psl_hamming256: query in registers against two uint4 halves, or against a pointer
+//   rotation check    psl_rot_bin, psl_three_maxima (ComputeThreeMaxima), psl_rot_keep
+//   window            psl_grid_cols / psl_window_cols (GetFeaturesInArea as column runs), psl_window_pos
+//   candidate key     psl_window_key over a candidate accessor (FrameCands here; a kernel with a staged frame brings its own)
+// A new search starts from these and keeps for itself only what is its own: its gates and its histogram fill loop.
 #ifndef PSL_MATCH_KERNELS_H
 #define PSL_MATCH_KERNELS_H
 #include <vector>
@@ -12,6 +22,7 @@
 #define PSL_GRID_CELLS (PSL_GRID_COLS * PSL_GRID_ROWS)
 #define PSL_QMAX 4096      // most queries / keypoints one workgroup handles
 #define PSL_TH_HIGH 100    // ORBmatcher::TH_HIGH src/ORBmatcher.cc:37
+#define PSL_TH_LOW 50      // ORBmatcher::TH_LOW :38, LSDmatcher::TH_LOW
 #define PSL_HISTO 30       // ORBmatcher::HISTO_LENGTH :39
 
 struct FrameMeta {
@@ -31,18 +42,65 @@ struct FrameStore {  // slot s lives at [s * cap] of every array
 };
 
 
-__device__ __forceinline__ int psl_hamming256(const uint32_t* q, const uint32_t* __restrict__ d) {
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += __popc(q[k] ^ d[k]);
-    return s;
+// 256-bit Hamming distance of a query held in registers and a candidate given as its two 128-bit halves
+__device__ __forceinline__ int psl_hamming256(const uint32_t (&q)[8], const uint4 d0, const uint4 d1) {
+    return __popc(q[0] ^ d0.x) + __popc(q[1] ^ d0.y) + __popc(q[2] ^ d0.z) + __popc(q[3] ^ d0.w) + __popc(q[4] ^ d1.x) +
+           __popc(q[5] ^ d1.y) + __popc(q[6] ^ d1.z) + __popc(q[7] ^ d1.w);
 }
 
+__device__ __forceinline__ int psl_hamming256(const uint32_t (&q)[8], const uint32_t* __restrict__ d) {  // d: 16-byte aligned
+    return psl_hamming256(q, *reinterpret_cast<const uint4*>(d), *reinterpret_cast<const uint4*>(d + 4));
+}
+
+__device__ __forceinline__ uint32_t psl_wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+
+__device__ __forceinline__ int psl_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// (k1, k2) <- the two smallest of {k1, k2, o1, o2}, given k1 <= k2 and o1 <= o2
 __device__ __forceinline__ void psl_merge2(uint32_t& k1, uint32_t& k2, uint32_t o1, uint32_t o2) {
     const uint32_t lo = min(k1, o1), hi = max(k1, o1);
     k2 = min(hi, min(k2, o2));
     k1 = lo;
 }
+
+// every lane's two smallest keys (k1 <= k2) -> the two smallest of the wave, in all lanes
+__device__ __forceinline__ void psl_wave_min2(uint32_t& k1, uint32_t& k2) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) psl_merge2(k1, k2, __shfl_xor(k1, o), __shfl_xor(k2, o));
+}
+
+// Rotation consistency of the ORBmatcher searches: bin of angle1 - angle2 in the HISTO_LENGTH histogram (src/ORBmatcher.cc:607-612)
+__device__ __forceinline__ int psl_rot_bin(float a1, float a2) {
+    float rot = PSL_FSUB(a1, a2);
+    if (rot < 0.0f) rot = PSL_FADD(rot, 360.0f);
+    int bin = (int)__builtin_roundf(PSL_FMUL(rot, 1.0f / PSL_HISTO));
+    if (bin == PSL_HISTO) bin = 0;
+    return bin < 0 ? 0 : (bin >= PSL_HISTO ? PSL_HISTO - 1 : bin);
+}
+
+// ORBmatcher::ComputeThreeMaxima (:1601-1645) of hist[PSL_HISTO] into ind[3]; one thread, on LDS
+__device__ __forceinline__ void psl_three_maxima(const int* hist, int* ind) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < PSL_HISTO; ++i) {
+        const int sz = hist[i];
+        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
+        else if (sz > max3) { max3 = sz; ind3 = i; }
+    }
+    if ((float)max2 < PSL_FMUL(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < PSL_FMUL(0.1f, (float)max1)) { ind3 = -1; }
+    ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
+}
+
+__device__ __forceinline__ bool psl_rot_keep(int bin, const int* ind) { return bin == ind[0] || bin == ind[1] || bin == ind[2]; }
 
 struct MatchArgs {
     FrameStore S;
@@ -108,9 +166,35 @@ struct WindowCols {
     bool checkLevels;
 };
 
-__device__ __forceinline__ WindowCols psl_window_cols(const FrameView& V, const PslProjQuery& q, const int* fidx) {
+// The window of (u, v, r) on the CSR grid `gstart` (a frame's, a reduced one, or a copy in LDS).  Called by all 64 lanes.
+__device__ __forceinline__ WindowCols psl_grid_cols(const int* gstart, const FrameMeta& M, float u, float v, float r) {
     const int lane = threadIdx.x & 63;
+    const int minCX = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(u, M.minX), r), M.invW)));
+    const int maxCX = min(PSL_GRID_COLS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(u, M.minX), r), M.invW)));
+    const int minCY = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(v, M.minY), r), M.invH)));
+    const int maxCY = min(PSL_GRID_ROWS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(v, M.minY), r), M.invH)));
+    const bool window = minCX < PSL_GRID_COLS && maxCX >= 0 && minCY < PSL_GRID_ROWS && maxCY >= 0;
+    WindowCols W;
+    W.start = 0;
+    int len = 0;
+    if (window && minCX + lane <= maxCX) {
+        const int ix = minCX + lane;
+        W.start = gstart[ix * PSL_GRID_ROWS + minCY];
+        len = gstart[ix * PSL_GRID_ROWS + maxCY + 1] - W.start;
+    }
+    int incl = len;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    W.incl = incl;
+    W.excl = incl - len;
+    W.T = __shfl(incl, 63);
+    W.checkLevels = false;
+    return W;
+}
+
+__device__ __forceinline__ WindowCols psl_window_cols(const FrameView& V, const PslProjQuery& q, const int* fidx) {
     if (fidx) {  // one run: the frame's features under the query's vocabulary node
+        const int lane = threadIdx.x & 63;
         WindowCols W;
         W.start = lane == 0 ? q.min_level : 0;
         const int len = lane == 0 ? (q.max_level > 0 ? q.max_level : 0) : 0;
@@ -121,27 +205,7 @@ __device__ __forceinline__ WindowCols psl_window_cols(const FrameView& V, const 
         W.checkLevels = false;
         return W;
     }
-    const FrameMeta& M = V.M;
-    const float r = q.radius;
-    const int minCX = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(q.u, M.minX), r), M.invW)));
-    const int maxCX = min(PSL_GRID_COLS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(q.u, M.minX), r), M.invW)));
-    const int minCY = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(q.v, M.minY), r), M.invH)));
-    const int maxCY = min(PSL_GRID_ROWS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(q.v, M.minY), r), M.invH)));
-    const bool window = minCX < PSL_GRID_COLS && maxCX >= 0 && minCY < PSL_GRID_ROWS && maxCY >= 0;
-    WindowCols W;
-    W.start = 0;
-    int len = 0;
-    if (window && minCX + lane <= maxCX) {
-        const int ix = minCX + lane;
-        W.start = V.gstart[ix * PSL_GRID_ROWS + minCY];
-        len = V.gstart[ix * PSL_GRID_ROWS + maxCY + 1] - W.start;
-    }
-    int incl = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-    W.incl = incl;
-    W.excl = incl - len;
-    W.T = __shfl(incl, 63);
+    WindowCols W = psl_grid_cols(V.gstart, V.M, q.u, q.v, q.radius);
     W.checkLevels = (q.min_level > 0) || (q.max_level >= 0);
     return W;
 }
@@ -159,31 +223,45 @@ __device__ __forceinline__ int psl_window_pos(const WindowCols& W, int j) {
     return j < W.T ? cs + (j - ce) : -1;
 }
 
+// What a window search fetches of the candidate at CSR position p, from the frame store: the keypoint index and, by index, the
+// keypoint's fields.  `windowed` is false where the candidates are a feature-vector run (fidx) and not a grid window.
+struct FrameCands {
+    const FrameView& V;
+    const int* fidx;
+    __device__ bool windowed() const { return !fidx; }
+    __device__ int index(int p) const { return fidx ? fidx[p] : V.gidx[p]; }
+    __device__ bool inside(int i2) const { return i2 >= 0 && i2 < V.n; }
+    __device__ float2 xy(int i2) const { return *reinterpret_cast<const float2*>(&V.kps[i2].x); }
+    __device__ int octave(int i2) const { return V.kps[i2].octave; }
+    __device__ float uright(int i2) const { return V.uright[i2]; }
+    __device__ uint4 desc0(int i2) const { return *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8); }
+    __device__ uint4 desc1(int i2) const { return *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8 + 4); }
+};
+
 // Key (distance << 16 | CSR position) of candidate number j, PSL_KEY_INF if j >= T or a gate rejects it: level band,
 // window, stereo (:1405-1411), taken initially (:1401-1403), taken by an earlier query of this call (blocker != NULL).
 // Called by all 64 lanes (shuffles inside).
-__device__ __forceinline__ uint32_t psl_window_key(const FrameView& V, const PslProjQuery& q, const uint32_t* qd, const uint8_t* taken,
-                                                   const int* blocker, int qi, const WindowCols& W, int j, const int* fidx, int no_stereo) {
+template <typename Cands>
+__device__ __forceinline__ uint32_t psl_window_key(const Cands& C, const PslProjQuery& q, const uint32_t (&qd)[8], const uint8_t* taken,
+                                                   const int* blocker, int qi, const WindowCols& W, int j, int no_stereo) {
     const int p = psl_window_pos(W, j);
     uint32_t key = PSL_KEY_INF;
     if (p >= 0) {
         const float r = q.radius;
-        const int i2 = fidx ? fidx[p] : V.gidx[p];
-        const float2 xy = *reinterpret_cast<const float2*>(&V.kps[i2].x);
-        const int octave = V.kps[i2].octave;
-        const float ur = V.uright[i2];
-        const uint4 d0 = *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8);
-        const uint4 d1 = *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8 + 4);
-        bool ok = i2 >= 0 && i2 < V.n;
-        if (!fidx) {
+        const int i2 = C.index(p);
+        const float2 xy = C.xy(i2);
+        const int octave = C.octave(i2);
+        const float ur = C.uright(i2);
+        const uint4 d0 = C.desc0(i2), d1 = C.desc1(i2);
+        bool ok = C.inside(i2);
+        if (C.windowed()) {
             if (W.checkLevels) ok = ok && !(octave < q.min_level) && !(q.max_level >= 0 && octave > q.max_level);
             ok = ok && (__builtin_fabsf(PSL_FSUB(xy.x, q.u)) < r && __builtin_fabsf(PSL_FSUB(xy.y, q.v)) < r);
         }
         if (taken) ok = ok && !taken[i2];
         if (blocker) ok = ok && !(blocker[i2] < qi);
         if (!no_stereo) ok = ok && !(ur > 0 && __builtin_fabsf(PSL_FSUB(q.ur, ur)) > r);
-        const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                         __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+        const int dist = psl_hamming256(qd, d0, d1);
         if (ok) key = ((uint32_t)dist << 16) | (uint32_t)p;
     }
     return key;
@@ -204,6 +282,18 @@ __device__ __forceinline__ uint32_t psl_wave_sort(uint32_t v) {
     return v;
 }
 
+// One round of the running top-K of pass 1.  `best`: the K smallest keys so far in lanes 0..K-1, ascending (unused in the first
+// round); `key`: this round's key of every lane.  Returns the new running list, again in lanes 0..K-1.
+template <int K>
+__device__ __forceinline__ uint32_t psl_topk_merge(uint32_t best, uint32_t key, bool first_round) {
+    const int lane = threadIdx.x & 63;
+    key = psl_wave_sort(key);
+    if (!first_round) {  // merge this round's smallest with the running ones
+        const uint32_t o = __shfl(key, (lane - K) & 63);
+        key = psl_wave_sort(lane < K ? best : (lane < 2 * K ? o : PSL_KEY_INF));
+    }
+    return key;
+}
 
 struct pslfe_frame {
     pslfe_ctx* ctx = nullptr;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "pslfe_internal.h"
+#include "match_kernels.h"
 
 #define PSL_BOW_NMAX 4096
 
@@ -48,15 +49,11 @@ __global__ __launch_bounds__(256) void k_bow_descend(VocabDev V, const uint8_t* 
         uint32_t best = 0xffffffffu;
         for (int c = lane; c < cc; c += 64) {
             const int id = V.child_ids[cb + c];
-            const uint4 d0 = *reinterpret_cast<const uint4*>(V.node_desc + (size_t)id * 8);
-            const uint4 d1 = *reinterpret_cast<const uint4*>(V.node_desc + (size_t)id * 8 + 4);
-            const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                             __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+            const int dist = psl_hamming256(qd, V.node_desc + (size_t)id * 8);
             const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)min(c, 0xffff);
             best = key < best ? key : best;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(best, o); best = u < best ? u : best; }
+        best = psl_wave_min_u32(best);
         node = V.child_ids[cb + (int)(best & 0xffff)];
         if (level == nid_level) nid = node;
     }

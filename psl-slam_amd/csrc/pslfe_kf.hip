@@ -15,22 +15,8 @@
 
 #include "match_kernels.h"
 
-#define PSL_TH_LOW 50         // ORBmatcher::TH_LOW src/ORBmatcher.cc:38, LSDmatcher::TH_LOW
 #define PSL_KF_LEVELS 16
 #define PSL_DISTINCT_MAX 1024  // observations of one map point handled (36 KB of descriptors in LDS)
-
-__device__ __forceinline__ uint32_t psl_wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-
-__device__ __forceinline__ int psl_hamming_regs(const uint32_t (&qd)[8], const uint32_t* __restrict__ d) {
-    const uint4 d0 = *reinterpret_cast<const uint4*>(d);
-    const uint4 d1 = *reinterpret_cast<const uint4*>(d + 4);
-    return __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) + __popc(qd[4] ^ d1.x) +
-           __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
-}
 
 struct BestArgs {
     FrameStore S;
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(256) void k_window_best(BestArgs A) {
             }
         }
         if (!ok) continue;
-        const int dist = psl_hamming_regs(qd, V.desc + (size_t)i2 * 8);
+        const int dist = psl_hamming256(qd, V.desc + (size_t)i2 * 8);
         best = min(best, ((uint32_t)dist << 16) | (uint32_t)p);
     }
     best = psl_wave_min_u32(best);
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(256) void k_triangulation(TriArgs A) {
         if (A.taken[idx2]) continue;
         const bool stereo2 = V.uright[idx2] >= 0;
         if (A.only_stereo && !stereo2) continue;
-        const int dist = psl_hamming_regs(qd, V.desc + (size_t)idx2 * 8);
+        const int dist = psl_hamming256(qd, V.desc + (size_t)idx2 * 8);
         if (dist > PSL_TH_LOW) continue;
         const float2 xy = *reinterpret_cast<const float2*>(&V.kps[idx2].x);
         const int octave = V.kps[idx2].octave & (PSL_KF_LEVELS - 1);
@@ -185,43 +171,26 @@ __global__ __launch_bounds__(1024) void k_triangulation_finish(TriArgs A) {
     if (tid == 0) { s_ind[0] = s_ind[1] = s_ind[2] = -1; s_nm = 0; }
     __syncthreads();
     if (A.check_ori) {
-        const float factor = 1.0f / PSL_HISTO;
         for (int qi = tid; qi < A.nq; qi += 1024) {
             const int c2 = A.choice[qi];
             if (c2 < 0) continue;
-            float rot = PSL_FSUB(A.q[qi].angle, V.kps[c2].angle);
-            if (rot < 0.0f) rot = PSL_FADD(rot, 360.0f);
-            int bin = (int)__builtin_roundf(PSL_FMUL(rot, factor));
-            if (bin == PSL_HISTO) bin = 0;
-            bin = bin < 0 ? 0 : (bin >= PSL_HISTO ? PSL_HISTO - 1 : bin);
+            const int bin = psl_rot_bin(A.q[qi].angle, V.kps[c2].angle);
             s_bin[qi] = (uint8_t)bin;
             atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < PSL_HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if ((float)max2 < PSL_FMUL(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < PSL_FMUL(0.1f, (float)max1)) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (tid == 0) psl_three_maxima(s_hist, s_ind);
         __syncthreads();
     }
     int local = 0;
     for (int qi = tid; qi < A.nq; qi += 1024) {
         const int c2 = A.choice[qi];
         bool good = c2 >= 0;
-        if (good && A.check_ori) { const int bn = s_bin[qi]; good = (bn == s_ind[0] || bn == s_ind[1] || bn == s_ind[2]); }
+        if (good && A.check_ori) good = psl_rot_keep(s_bin[qi], s_ind);
         A.match[qi] = good ? c2 : -1;
         local += good;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+    local = psl_wave_sum(local);
     if ((tid & 63) == 0 && local) atomicAdd(&s_nm, local);
     __syncthreads();
     if (tid == 0) *A.nmatches = s_nm;
@@ -262,7 +231,7 @@ __global__ __launch_bounds__(256) void k_line_fuse_best(const PslKeyLine* __rest
         if (cs < 0.998f) continue;
         if (kl.octave < q.level - 1 || kl.octave > q.level) continue;
         if (k >= ndesc) continue;
-        const int dist = psl_hamming_regs(qd, reinterpret_cast<const uint32_t*>(desc) + (size_t)k * 8);
+        const int dist = psl_hamming256(qd, reinterpret_cast<const uint32_t*>(desc) + (size_t)k * 8);
         best = min(best, ((uint32_t)dist << 16) | (uint32_t)k);
     }
     best = psl_wave_min_u32(best);
@@ -316,7 +285,7 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
             for (int t = 0; t < PER; ++t)
                 if (t * 64 < N) cnt += d[t] <= mid;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);  // not psl_wave_sum: the call changes this kernel's registers (77 -> 62 VGPRs, +65 instructions)
             if (cnt >= k + 1) hi = mid; else lo = mid + 1;
         }
         bestKey = min(bestKey, ((uint32_t)lo << 16) | (uint32_t)i);

@@ -17,6 +17,7 @@
 
 #include "pslfe_internal.h"
 #include "psl_device_math.h"
+#include "match_kernels.h"
 
 #define PSL_LG_COLS 64
 #define PSL_LG_ROWS 48
@@ -152,17 +153,11 @@ __device__ int line_pick(const PslKeyLine* kls, const uint8_t* desc, const doubl
         const uint32_t* D = reinterpret_cast<const uint32_t*>(desc) + (size_t)i2 * 8;
         int d = 0;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) d += __popc(qd[k] ^ D[k]);
+        for (int k = 0; k < 8; ++k) d += __popc(qd[k] ^ D[k]);   // rows of a caller's array: no 16-byte alignment assumed
         const uint32_t key = ((uint32_t)d << 16) | (uint32_t)ci;
         if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t o1 = __shfl_xor(k1, o), o2 = __shfl_xor(k2, o);
-        const uint32_t lo = min(k1, o1), hi = max(k1, o1);
-        k2 = min(hi, min(k2, o2));
-        k1 = lo;
-    }
+    psl_wave_min2(k1, k2);
     int pick = -1;
     if (k1 != 0xffffffffu && (int)(k1 >> 16) <= PSL_LINE_TH) {
         pick = s_cand[k1 & 0xffff];

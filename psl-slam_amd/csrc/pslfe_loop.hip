@@ -22,7 +22,6 @@
 
 #include "match_kernels.h"
 
-#define PSL_TH_LOW 50          // ORBmatcher::TH_LOW src/ORBmatcher.cc:38
 #define PSL_LOOP_TOPK 8
 #define PSL_BOW_ROW_WORDS 9    // odd stride: lanes on consecutive rows hit different banks
 
@@ -44,12 +43,6 @@ struct BowKfArgs {
     int* match;
     int* nmatches;
 };
-
-__device__ __forceinline__ uint32_t psl_loop_wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
 
 // the candidate loop :554-619 for one (candidate, node): one wave
 __global__ __launch_bounds__(64) void k_bow_kf_walk(BowKfArgs A) {
@@ -87,15 +80,10 @@ __global__ __launch_bounds__(64) void k_bow_kf_walk(BowKfArgs A) {
         for (int j = lane; j < G.len; j += 64) {
             const uint32_t* r = s_row + j * PSL_BOW_ROW_WORDS;
             if (r[8]) continue;   // vbMatched2[idx2] :576
-            const int dist = __popc(qd[0] ^ r[0]) + __popc(qd[1] ^ r[1]) + __popc(qd[2] ^ r[2]) + __popc(qd[3] ^ r[3]) +
-                             __popc(qd[4] ^ r[4]) + __popc(qd[5] ^ r[5]) + __popc(qd[6] ^ r[6]) + __popc(qd[7] ^ r[7]);
+            const int dist = psl_hamming256(qd, make_uint4(r[0], r[1], r[2], r[3]), make_uint4(r[4], r[5], r[6], r[7]));   // odd stride: scalar reads
             psl_merge2(k1, k2, ((uint32_t)dist << 16) | (uint32_t)j, PSL_KEY_INF);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t o1 = (uint32_t)__shfl_xor((int)k1, o), o2 = (uint32_t)__shfl_xor((int)k2, o);
-            psl_merge2(k1, k2, o1, o2);
-        }
+        psl_wave_min2(k1, k2);
         const int bestDist1 = k1 == PSL_KEY_INF ? 256 : (int)(k1 >> 16), bestDist2 = k2 == PSL_KEY_INF ? 256 : (int)(k2 >> 16);
         const bool acc = bestDist1 < PSL_TH_LOW && (float)bestDist1 < PSL_FMUL(A.nnratio, (float)bestDist2);   // :598-600
         const int pos = (int)(k1 & 0xffffu);
@@ -105,14 +93,6 @@ __global__ __launch_bounds__(64) void k_bow_kf_walk(BowKfArgs A) {
         }
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ int psl_loop_rot_bin(float a1, float a2) {   // :607-612
-    float rot = PSL_FSUB(a1, a2);
-    if (rot < 0.0f) rot = PSL_FADD(rot, 360.0f);
-    int bin = (int)__builtin_roundf(PSL_FMUL(rot, 1.0f / PSL_HISTO));
-    if (bin == PSL_HISTO) bin = 0;
-    return bin < 0 ? 0 : (bin >= PSL_HISTO ? PSL_HISTO - 1 : bin);
 }
 
 // rotation histogram + ComputeThreeMaxima + outputs (:605-615, :634-652) of one candidate
@@ -129,36 +109,21 @@ __global__ __launch_bounds__(256) void k_bow_kf_finish(BowKfArgs A) {
     if (A.check_ori) {
         for (int qi = q0 + tid; qi < q1; qi += 256) {
             const int c2 = A.choice[qi];
-            if (c2 >= 0) atomicAdd(&s_hist[psl_loop_rot_bin(A.q[qi].angle, V.kps[c2].angle)], 1);
+            if (c2 >= 0) atomicAdd(&s_hist[psl_rot_bin(A.q[qi].angle, V.kps[c2].angle)], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < PSL_HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if ((float)max2 < PSL_FMUL(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < PSL_FMUL(0.1f, (float)max1)) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (tid == 0) psl_three_maxima(s_hist, s_ind);
         __syncthreads();
     }
     int local = 0;
     for (int qi = q0 + tid; qi < q1; qi += 256) {
         const int c2 = A.choice[qi];
         bool good = c2 >= 0;
-        if (good && A.check_ori) {
-            const int bn = psl_loop_rot_bin(A.q[qi].angle, V.kps[c2].angle);
-            good = (bn == s_ind[0] || bn == s_ind[1] || bn == s_ind[2]);
-        }
+        if (good && A.check_ori) good = psl_rot_keep(psl_rot_bin(A.q[qi].angle, V.kps[c2].angle), s_ind);
         A.match[qi] = good ? c2 : -1;
         local += good;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+    local = psl_wave_sum(local);
     if ((tid & 63) == 0 && local) atomicAdd(&s_nm, local);
     __syncthreads();
     if (tid == 0) A.nmatches[c] = s_nm;
@@ -191,10 +156,7 @@ __device__ __forceinline__ uint32_t psl_loop_key(const FrameView& V, const PslPr
     if (!(__builtin_fabsf(PSL_FSUB(xy.x, q.u)) < r && __builtin_fabsf(PSL_FSUB(xy.y, q.v)) < r)) return PSL_KEY_INF;
     if (octave < q.max_level - 1 || octave > q.max_level) return PSL_KEY_INF;
     if (busy(i2)) return PSL_KEY_INF;
-    const uint4 d0 = *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8);
-    const uint4 d1 = *reinterpret_cast<const uint4*>(V.desc + (size_t)i2 * 8 + 4);
-    const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) + __popc(qd[4] ^ d1.x) +
-                     __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+    const int dist = psl_hamming256(qd, V.desc + (size_t)i2 * 8);
     return dist <= PSL_TH_LOW ? (((uint32_t)dist << 16) | (uint32_t)p) : PSL_KEY_INF;
 }
 
@@ -228,15 +190,13 @@ __global__ __launch_bounds__(256) void k_loop_proj_lists(LoopProjArgs A) {
     int popped = 0, nout = 0, mine = -1;
     for (int k = 0; k < PSL_LOOP_TOPK; ++k) {
         if (__any(popped == 4 && cnt > 4)) break;   // a lane has keys this wave no longer sees: the list ends here, `more` is set
-        const uint32_t m = psl_loop_wave_min(t[0]);
+        const uint32_t m = psl_wave_min_u32(t[0]);
         if (m == PSL_KEY_INF) break;
         if (t[0] == m) { t[0] = t[1]; t[1] = t[2]; t[2] = t[3]; t[3] = PSL_KEY_INF; ++popped; }   // positions are distinct: one owner
         if (lane == k) mine = V.gidx[m & 0xffffu];
         ++nout;
     }
-    int total = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+    const int total = psl_wave_sum(cnt);
     if (lane < PSL_LOOP_TOPK) out[lane] = lane < nout ? mine : -1;
     if (lane == 0) A.more[qi] = total > nout;
 }
@@ -308,7 +268,7 @@ __global__ __launch_bounds__(64) void k_loop_proj_resolve(LoopProjArgs A) {
                     const int p = psl_window_pos(W, b0 + lane);
                     best = min(best, psl_loop_key(V, q, qd, p, [&](int i2) { return s_busy[i2] != 0; }));
                 }
-                best = psl_loop_wave_min(best);
+                best = psl_wave_min_u32(best);
                 const int kp = best == PSL_KEY_INF ? -1 : V.gidx[best & 0xffffu];
                 if (lane == done) {
                     result = kp;
@@ -323,8 +283,7 @@ __global__ __launch_bounds__(64) void k_loop_proj_resolve(LoopProjArgs A) {
             nm += result >= 0;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nm += __shfl_xor(nm, o);
+    nm = psl_wave_sum(nm);
     if (lane == 0) *A.nmatches = nm;
 }
 

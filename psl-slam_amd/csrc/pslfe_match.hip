@@ -223,17 +223,13 @@ __global__ __launch_bounds__(256) void k_window_eval(MatchArgs A) {
     for (int k = 0; k < 8; ++k) qd[k] = QD[k];
     const uint8_t* taken = A.taken ? A.taken + (size_t)pair * A.S.cap : nullptr;
     const WindowCols W = psl_window_cols(V, q, A.fidx);
+    const FrameCands C = {V, A.fidx};
     uint32_t best = PSL_KEY_INF;  // lanes 0..PSL_TOPK-1: running smallest keys, ascending
     int cnt = 0;
     for (int base = 0; base < W.T; base += 64) {
-        uint32_t key = psl_window_key(V, q, qd, taken, nullptr, qi, W, base + lane, A.fidx, A.no_stereo);
+        const uint32_t key = psl_window_key(C, q, qd, taken, nullptr, qi, W, base + lane, A.no_stereo);
         cnt += __popcll(__ballot(key != PSL_KEY_INF));
-        key = psl_wave_sort(key);
-        if (base > 0) {  // merge this round's smallest with the running ones
-            const uint32_t o = __shfl(key, (lane - PSL_TOPK) & 63);
-            key = psl_wave_sort(lane < PSL_TOPK ? best : (lane < 2 * PSL_TOPK ? o : PSL_KEY_INF));
-        }
-        best = key;
+        best = psl_topk_merge<PSL_TOPK>(best, key, base == 0);
     }
     if (lane < PSL_TOPK) A.topk[((size_t)pair * A.qstride + qi) * PSL_TOPK + lane] = best;
     if (lane == 0) A.more[(size_t)pair * A.qstride + qi] = cnt > PSL_TOPK;
@@ -246,6 +242,22 @@ __global__ __launch_bounds__(256) void k_window_eval(MatchArgs A) {
 // keypoint + descriptor) from 12 M independent waves per launch: 8.7 GB fetched for 0.9 GB of frames, two thirds of a wave's life
 // spent waiting (profiles/r03e_*).  Same arithmetic, same keys, same order.
 #define PSL_WS_CAP 1280
+struct StagedCands {  // psl_window_key's candidate accessor on the staged frame
+    const uint16_t* gidx;
+    const float2* kxy;
+    const uint8_t* oct;
+    const float* ur;
+    const uint4* desc;
+    int n;
+    __device__ bool windowed() const { return true; }
+    __device__ int index(int p) const { return gidx[p]; }
+    __device__ bool inside(int i2) const { return i2 < n; }
+    __device__ float2 xy(int i2) const { return kxy[i2]; }
+    __device__ int octave(int i2) const { return oct[i2]; }
+    __device__ float uright(int i2) const { return ur[i2]; }
+    __device__ uint4 desc0(int i2) const { return desc[2 * i2]; }
+    __device__ uint4 desc1(int i2) const { return desc[2 * i2 + 1]; }
+};
 __global__ __launch_bounds__(1024, 8) void k_window_eval_staged(MatchArgs A) {   // 64 VGPRs: two workgroups (72 KB of LDS each) per CU
     __shared__ int s_gstart[PSL_GRID_CELLS + 1];
     __shared__ uint16_t s_gidx[PSL_WS_CAP];
@@ -267,7 +279,7 @@ __global__ __launch_bounds__(1024, 8) void k_window_eval_staged(MatchArgs A) {  
     for (int i = tid; i < 2 * n; i += 1024) s_desc[i] = reinterpret_cast<const uint4*>(V.desc)[i];
     for (int c = tid; c <= PSL_GRID_CELLS; c += 1024) s_gstart[c] = V.gstart[c];
     __syncthreads();
-    const FrameMeta& M = V.M;
+    const StagedCands C = {s_gidx, s_xy, s_oct, s_ur, s_desc, n};
     const PslProjQuery* Q = A.q + (size_t)pair * A.qstride;
     const uint4* QD = reinterpret_cast<const uint4*>(A.qdesc + (size_t)pair * A.qstride * 32);
     const uint8_t* taken = A.taken ? A.taken + (size_t)pair * A.S.cap : nullptr;
@@ -280,56 +292,14 @@ __global__ __launch_bounds__(1024, 8) void k_window_eval_staged(MatchArgs A) {  
         const PslProjQuery q = qn;
         const uint32_t qd[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
         if (qi + 16 < nq) { qn = Q[qi + 16]; qa = QD[2 * (size_t)(qi + 16)]; qb = QD[2 * (size_t)(qi + 16) + 1]; }
-        // psl_window_cols on the staged grid
-        const float r = q.radius;
-        const int minCX = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(q.u, M.minX), r), M.invW)));
-        const int maxCX = min(PSL_GRID_COLS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(q.u, M.minX), r), M.invW)));
-        const int minCY = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(q.v, M.minY), r), M.invH)));
-        const int maxCY = min(PSL_GRID_ROWS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(q.v, M.minY), r), M.invH)));
-        const bool window = minCX < PSL_GRID_COLS && maxCX >= 0 && minCY < PSL_GRID_ROWS && maxCY >= 0;
-        WindowCols W;
-        W.start = 0;
-        int len = 0;
-        if (window && minCX + lane <= maxCX) {
-            const int ix = minCX + lane;
-            W.start = s_gstart[ix * PSL_GRID_ROWS + minCY];
-            len = s_gstart[ix * PSL_GRID_ROWS + maxCY + 1] - W.start;
-        }
-        int incl = len;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-        W.incl = incl;
-        W.excl = incl - len;
-        W.T = __shfl(incl, 63);
+        WindowCols W = psl_grid_cols(s_gstart, V.M, q.u, q.v, q.radius);
         W.checkLevels = (q.min_level > 0) || (q.max_level >= 0);
         uint32_t best = PSL_KEY_INF;  // lanes 0..PSL_TOPK-1: running smallest keys, ascending
         int cnt = 0;
         for (int base = 0; base < W.T; base += 64) {
-            // psl_window_key on the staged frame
-            const int p = psl_window_pos(W, base + lane);
-            uint32_t key = PSL_KEY_INF;
-            if (p >= 0) {
-                const int i2 = s_gidx[p];
-                const float2 xy = s_xy[i2];
-                const int octave = s_oct[i2];
-                const float ur = s_ur[i2];
-                const uint4 d0 = s_desc[2 * i2], d1 = s_desc[2 * i2 + 1];
-                bool ok = i2 < n;
-                if (W.checkLevels) ok = ok && !(octave < q.min_level) && !(q.max_level >= 0 && octave > q.max_level);
-                ok = ok && (__builtin_fabsf(PSL_FSUB(xy.x, q.u)) < r && __builtin_fabsf(PSL_FSUB(xy.y, q.v)) < r);
-                if (taken) ok = ok && !taken[i2];
-                if (!A.no_stereo) ok = ok && !(ur > 0 && __builtin_fabsf(PSL_FSUB(q.ur, ur)) > r);
-                const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                                 __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
-                if (ok) key = ((uint32_t)dist << 16) | (uint32_t)p;
-            }
+            const uint32_t key = psl_window_key(C, q, qd, taken, nullptr, qi, W, base + lane, A.no_stereo);
             cnt += __popcll(__ballot(key != PSL_KEY_INF));
-            key = psl_wave_sort(key);
-            if (base > 0) {  // merge this round's smallest with the running ones
-                const uint32_t o = __shfl(key, (lane - PSL_TOPK) & 63);
-                key = psl_wave_sort(lane < PSL_TOPK ? best : (lane < 2 * PSL_TOPK ? o : PSL_KEY_INF));
-            }
-            best = key;
+            best = psl_topk_merge<PSL_TOPK>(best, key, base == 0);
         }
         if (lane < PSL_TOPK) A.topk[((size_t)pair * A.qstride + qi) * PSL_TOPK + lane] = best;
         if (lane == 0) A.more[(size_t)pair * A.qstride + qi] = cnt > PSL_TOPK;
@@ -462,18 +432,13 @@ __global__ __launch_bounds__(BS) void k_window_resolve(MatchArgs A) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) qd[k] = QD[(size_t)qi * 8 + k];
                 const WindowCols W = psl_window_cols(V, q, A.fidx);
+                const FrameCands C = {V, A.fidx};
                 uint32_t t0 = PSL_KEY_INF, t1 = PSL_KEY_INF;  // two smallest keys
                 for (int base = 0; base < W.T; base += 64) {
-                    const uint32_t key = psl_window_key(V, q, qd, taken, blk, qi, W, base + lane, A.fidx, A.no_stereo);
+                    const uint32_t key = psl_window_key(C, q, qd, taken, blk, qi, W, base + lane, A.no_stereo);
                     if (key < t0) { t1 = t0; t0 = key; } else if (key < t1) t1 = key;
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const uint32_t a0 = __shfl_xor(t0, o), a1 = __shfl_xor(t1, o);
-                    const uint32_t lo = min(t0, a0), hi = max(t0, a0);
-                    t1 = min(hi, min(t1, a1));
-                    t0 = lo;
-                }
+                psl_wave_min2(t0, t1);
                 uint32_t c1 = 0, c2 = 0;
                 if (t0 != PSL_KEY_INF) { c1 = posmap[t0 & 0xffff]; if (MODE == 1) c1 |= (uint32_t)V.kps[c1].octave << 12; }
                 if (t1 != PSL_KEY_INF) { c2 = posmap[t1 & 0xffff]; if (MODE == 1) c2 |= (uint32_t)V.kps[c2].octave << 12; }
@@ -503,31 +468,15 @@ __global__ __launch_bounds__(BS) void k_window_resolve(MatchArgs A) {
     __syncthreads();
     const bool ori = (MODE == 0 || MODE == 2) && A.check_ori;
     if (ori) {
-        const float factor = 1.0f / PSL_HISTO;
         for (int qi = tid; qi < nq; qi += BS) {
             const int c = s_choice[qi];
             if (c < 0) continue;
-            float rot = PSL_FSUB(Q[qi].angle, V.kps[c].angle);
-            if (rot < 0.0f) rot = PSL_FADD(rot, 360.0f);
-            int bin = (int)__builtin_roundf(PSL_FMUL(rot, factor));
-            if (bin == PSL_HISTO) bin = 0;
-            bin = bin < 0 ? 0 : (bin >= PSL_HISTO ? PSL_HISTO - 1 : bin);
+            const int bin = psl_rot_bin(Q[qi].angle, V.kps[c].angle);
             s_bin[qi] = (uint8_t)bin;
             atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (:1601-1645)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < PSL_HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if ((float)max2 < PSL_FMUL(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < PSL_FMUL(0.1f, (float)max1)) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (tid == 0) psl_three_maxima(s_hist, s_ind);
         __syncthreads();
     }
     // owners: the last query that assigned a keypoint, unless one of its assignments was filtered
@@ -539,7 +488,7 @@ __global__ __launch_bounds__(BS) void k_window_resolve(MatchArgs A) {
         const int c = s_choice[qi];
         bool good = c >= 0;
         if (good) atomicMax(&s_blocker[c], qi);
-        if (good && ori) { const int b = s_bin[qi]; good = (b == s_ind[0] || b == s_ind[1] || b == s_ind[2]); }
+        if (good && ori) good = psl_rot_keep(s_bin[qi], s_ind);
         match[qi] = good ? c : -1;
         local += good;
     }
@@ -548,11 +497,9 @@ __global__ __launch_bounds__(BS) void k_window_resolve(MatchArgs A) {
         for (int qi = tid; qi < nq; qi += BS) {
             const int c = s_choice[qi];
             if (c < 0) continue;
-            const int b = s_bin[qi];
-            if (!(b == s_ind[0] || b == s_ind[1] || b == s_ind[2])) s_blocker[c] = -1;
+            if (!psl_rot_keep(s_bin[qi], s_ind)) s_blocker[c] = -1;
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+    local = psl_wave_sum(local);
     if (lane == 0 && local) atomicAdd(&s_nm, local);
     __syncthreads();
     if (A.assigned) {
@@ -577,8 +524,7 @@ __global__ __launch_bounds__(256) void k_hamming_knn2(const uint8_t* __restrict_
         const uint32_t key = ((uint32_t)psl_hamming256(qd, T + (size_t)j * 8) << 20) | (uint32_t)j;  // nt < 2^20
         if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) psl_merge2(k1, k2, __shfl_xor(k1, o), __shfl_xor(k2, o));
+    psl_wave_min2(k1, k2);
     if (lane == 0) {
         idx[2 * qi] = k1 == 0xffffffffu ? -1 : (int)(k1 & 0xfffff);
         dist[2 * qi] = k1 == 0xffffffffu ? 0x7fffffff : (int)(k1 >> 20);

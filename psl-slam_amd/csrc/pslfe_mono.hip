@@ -28,7 +28,6 @@
 #include "match_kernels.h"
 
 #define PSL_MI_K 8       // cached candidates per query
-#define PSL_TH_LOW 50    // ORBmatcher::TH_LOW src/ORBmatcher.cc:38
 #define PSL_MD_NONE 255  // vMatchedDistance == INT_MAX (every stored distance is <= TH_LOW)
 
 struct MonoArgs {
@@ -63,47 +62,17 @@ __device__ __forceinline__ MonoF2 psl_mono_f2(const MonoArgs& A, int pair) {
     return F;
 }
 
-// GetFeaturesInArea(x, y, r, 0, 0) on the octave-0 grid: psl_window_cols with the reduced CSR.  Called by all 64 lanes.
-__device__ __forceinline__ WindowCols psl_mono_cols(const MonoF2& F, float x, float y, float r) {
-    const int lane = threadIdx.x & 63;
-    const FrameMeta& M = F.V.M;
-    const int minCX = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(x, M.minX), r), M.invW)));
-    const int maxCX = min(PSL_GRID_COLS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(x, M.minX), r), M.invW)));
-    const int minCY = max(0, (int)__builtin_floorf(PSL_FMUL(PSL_FSUB(PSL_FSUB(y, M.minY), r), M.invH)));
-    const int maxCY = min(PSL_GRID_ROWS - 1, (int)__builtin_ceilf(PSL_FMUL(PSL_FADD(PSL_FSUB(y, M.minY), r), M.invH)));
-    const bool window = minCX < PSL_GRID_COLS && maxCX >= 0 && minCY < PSL_GRID_ROWS && maxCY >= 0;
-    WindowCols W;
-    W.start = 0;
-    int len = 0;
-    if (window && minCX + lane <= maxCX) {
-        const int ix = minCX + lane;
-        W.start = F.gstart0[ix * PSL_GRID_ROWS + minCY];
-        len = F.gstart0[ix * PSL_GRID_ROWS + maxCY + 1] - W.start;
-    }
-    int incl = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-    W.incl = incl;
-    W.excl = incl - len;
-    W.T = __shfl(incl, 63);
-    W.checkLevels = false;
-    return W;
-}
-
 // Key (dist << 16 | position) of window candidate j, PSL_KEY_INF past the end, outside |dx| < r, |dy| < r, or - md != NULL -
 // filtered by vMatchedDistance (:442-443).  Called by all 64 lanes.
-__device__ __forceinline__ uint32_t psl_mono_key(const MonoF2& F, float x, float y, float r, const uint32_t* qd, const WindowCols& W, int j,
+__device__ __forceinline__ uint32_t psl_mono_key(const MonoF2& F, float x, float y, float r, const uint32_t (&qd)[8], const WindowCols& W, int j,
                                                  const uint8_t* md) {
     const int p = psl_window_pos(W, j);
     uint32_t key = PSL_KEY_INF;
     if (p >= 0) {
         const int i2 = F.gidx0[p];
         const float2 xy = *reinterpret_cast<const float2*>(&F.V.kps[i2].x);
-        const uint4 d0 = *reinterpret_cast<const uint4*>(F.V.desc + (size_t)i2 * 8);
-        const uint4 d1 = *reinterpret_cast<const uint4*>(F.V.desc + (size_t)i2 * 8 + 4);
         bool ok = __builtin_fabsf(PSL_FSUB(xy.x, x)) < r && __builtin_fabsf(PSL_FSUB(xy.y, y)) < r;
-        const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                         __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+        const int dist = psl_hamming256(qd, F.V.desc + (size_t)i2 * 8);
         if (md) {
             const int m = md[i2];
             ok = ok && !(m != PSL_MD_NONE && m <= dist);
@@ -169,16 +138,12 @@ __global__ __launch_bounds__(256) void k_mono_eval(MonoArgs A) {
         uint32_t qd[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) qd[k] = V1.desc[(size_t)qi * 8 + k];
-        const WindowCols W = psl_mono_cols(F, x, y, A.r);
+        // GetFeaturesInArea(x, y, r, 0, 0): the octave-0 grid makes the level band exact, checkLevels stays off
+        const WindowCols W = psl_grid_cols(F.gstart0, F.V.M, x, y, A.r);
         for (int base = 0; base < W.T; base += 64) {
-            uint32_t key = psl_mono_key(F, x, y, A.r, qd, W, base + lane, nullptr);
+            const uint32_t key = psl_mono_key(F, x, y, A.r, qd, W, base + lane, nullptr);
             cnt += __popcll(__ballot(key != PSL_KEY_INF));
-            key = psl_wave_sort(key);
-            if (base > 0) {
-                const uint32_t u = __shfl(key, (lane - PSL_MI_K) & 63);
-                key = psl_wave_sort(lane < PSL_MI_K ? best : (lane < 2 * PSL_MI_K ? u : PSL_KEY_INF));
-            }
-            best = key;
+            best = psl_topk_merge<PSL_MI_K>(best, key, base == 0);
         }
     }
     if (lane < PSL_MI_K) {  // the position becomes the keypoint; the list keeps the (dist, position) order
@@ -238,14 +203,13 @@ __global__ __launch_bounds__(64) void k_mono_resolve(MonoArgs A) {
                 uint32_t qd[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) qd[k] = V1.desc[(size_t)qi * 8 + k];
-                const WindowCols W = psl_mono_cols(F, x, y, A.r);
+                const WindowCols W = psl_grid_cols(F.gstart0, F.V.M, x, y, A.r);
                 uint32_t t0 = PSL_KEY_INF, t1 = PSL_KEY_INF;
                 for (int b = 0; b < W.T; b += 64) {
                     const uint32_t key = psl_mono_key(F, x, y, A.r, qd, W, b + lane, s_md);
                     if (key < t0) { t1 = t0; t0 = key; } else if (key < t1) t1 = key;
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) psl_merge2(t0, t1, __shfl_xor(t0, o), __shfl_xor(t1, o));
+                psl_wave_min2(t0, t1);
                 if (t0 != PSL_KEY_INF) { bestDist = (int)(t0 >> 16); bestIdx2 = F.gidx0[t0 & 0xffff]; }
                 if (t1 != PSL_KEY_INF) bestDist2 = (int)(t1 >> 16);
             }
@@ -266,31 +230,15 @@ __global__ __launch_bounds__(64) void k_mono_resolve(MonoArgs A) {
     // rotation histogram (:470-481, :485-508): every accepted query counts, also one whose keypoint was taken later
     const bool ori = A.check_ori != 0;
     if (ori) {
-        const float factor = 1.0f / PSL_HISTO;
         for (int qi = lane; qi < n1; qi += 64) {
             const int a = s_acc[qi];
             if (a < 0) continue;
-            float rot = PSL_FSUB(V1.kps[qi].angle, F.V.kps[a & 0xfff].angle);
-            if (rot < 0.0f) rot = PSL_FADD(rot, 360.0f);
-            int bin = (int)__builtin_roundf(PSL_FMUL(rot, factor));
-            if (bin == PSL_HISTO) bin = 0;
-            bin = bin < 0 ? 0 : (bin >= PSL_HISTO ? PSL_HISTO - 1 : bin);
+            const int bin = psl_rot_bin(V1.kps[qi].angle, F.V.kps[a & 0xfff].angle);
             s_bin[qi] = (uint8_t)bin;
             atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (lane == 0) {  // ComputeThreeMaxima (:1601-1645)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < PSL_HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if ((float)max2 < PSL_FMUL(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < PSL_FMUL(0.1f, (float)max1)) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (lane == 0) psl_three_maxima(s_hist, s_ind);
         __syncthreads();
     }
     // vnMatches12 and vbPrevMatched (:512-516)
@@ -300,10 +248,7 @@ __global__ __launch_bounds__(64) void k_mono_resolve(MonoArgs A) {
     for (int qi = lane; qi < n1; qi += 64) {
         const int a = s_acc[qi];
         int m = (a >= 0 && !(a & 0x4000)) ? a : -1;
-        if (m >= 0 && ori) {
-            const int b = s_bin[qi];
-            if (!(b == s_ind[0] || b == s_ind[1] || b == s_ind[2])) m = -1;
-        }
+        if (m >= 0 && ori && !psl_rot_keep(s_bin[qi], s_ind)) m = -1;
         m12[qi] = m;
         if (m >= 0) {
             const float2 xy = *reinterpret_cast<const float2*>(&F.V.kps[m].x);
@@ -311,8 +256,7 @@ __global__ __launch_bounds__(64) void k_mono_resolve(MonoArgs A) {
             ++local;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+    local = psl_wave_sum(local);
     if (lane == 0) A.nmatches[pair] = local;
 }
 

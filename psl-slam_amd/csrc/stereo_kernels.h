@@ -68,12 +68,6 @@ __device__ __forceinline__ int psl_st_bin(float y, int rows) {
     return y >= 0.f ? (y < (float)rows ? (int)y : rows - 1) : 0;
 }
 
-__device__ __forceinline__ uint32_t psl_st_wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_stereo_rows(StereoArgs A) {
     __shared__ int s_cnt[PSL_ST_MAX_ROWS];
@@ -153,14 +147,11 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs A) {
                 if (row < minr || row > maxr) continue;
                 if (R.octave < oL - 1 || R.octave > oL + 1) continue;                      // :1232
                 if (!(R.x >= minU && R.x <= maxU)) continue;                               // :1237
-                const uint4 a = *reinterpret_cast<const uint4*>(dR + (size_t)iR * 8);
-                const uint4 b = *reinterpret_cast<const uint4*>(dR + (size_t)iR * 8 + 4);
-                const uint32_t dist = __popc(qd[0] ^ a.x) + __popc(qd[1] ^ a.y) + __popc(qd[2] ^ a.z) + __popc(qd[3] ^ a.w) +
-                                      __popc(qd[4] ^ b.x) + __popc(qd[5] ^ b.y) + __popc(qd[6] ^ b.z) + __popc(qd[7] ^ b.w);
+                const uint32_t dist = (uint32_t)psl_hamming256(qd, dR + (size_t)iR * 8);
                 if (dist < PSL_ST_TH_HIGH) best = min(best, (dist << 16) | (uint32_t)iR);
             }
         }
-        best = psl_st_wave_min(best);
+        best = psl_wave_min_u32(best);
         if (go && best != 0xffffffffu && (int)(best >> 16) < PSL_ST_TH_ORB) {
             const int iR = (int)(best & 0xffffu);
             out_idx = iR;
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs A) {
                     const int a = __shfl(part[0], t & 63), b = __shfl(part[1], (t - 64) & 63);
                     D += t < 64 ? a : b;
                 }
-                const uint32_t m = psl_st_wave_min(lane < 11 ? ((uint32_t)D << 4) | (uint32_t)lane : 0xffffffffu);   // first minimum
+                const uint32_t m = psl_wave_min_u32(lane < 11 ? ((uint32_t)D << 4) | (uint32_t)lane : 0xffffffffu);   // first minimum
                 const int binc = (int)(m & 15u), d2i = (int)(m >> 4);
                 const int d1i = __shfl(D, max(binc - 1, 0)), d3i = __shfl(D, min(binc + 1, 10));
                 if (binc != 0 && binc != 2 * PSL_ST_W) {                                     // bestincR == +-L (:1293)
