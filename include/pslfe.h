@@ -691,12 +691,13 @@ void pslfe_kf_destroy(pslfe_kf* k);
  * vpReplacePoint) :968-1100 (chi2 = 0) and one direction of SearchBySim3 :1165-1232: KeyFrame::GetFeaturesInArea(u, v,
  * radius) src/KeyFrame.cc:685-724 on the grid of slot `slot`, octaves max_level-1 .. max_level (max_level =
  * nPredictedLevel; min_level, angle, blocks are ignored), the smallest DescriptorDistance, first visited on ties.
- * The host projects (it owns the map points); a query with radius < 0 is one the reference dropped before the search.
+ * The caller passes projected rows (pslfe_kf_project makes them on the device; pslfe_kf_fuse_keyframes does both for a set
+ * of keyframes); a query with radius < 0 is one the reference dropped before the search.
  * best_idx[i] = keypoint or -1, best_dist[i] = its distance or INT_MAX: the caller applies bestDist <= TH_LOW and
  * mutates the map (:950-964).  inv_level_sigma2: pKF->mvInvLevelSigma2 (nlevels <= 16 entries; chi2 = 1 only). */
 int pslfe_kf_window_best(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const uint8_t* qdesc, int nq,
                          int chi2, const float* inv_level_sigma2, int nlevels, int32_t* best_idx, int32_t* best_dist);
-/* == ORBmatcher::SearchBySim3 src/ORBmatcher.cc:1102-1326 after the projections: q12[i1] = map point i1 of KF1 in KF2's
+/* == ORBmatcher::SearchBySim3 src/ORBmatcher.cc:1102-1326 after the projections (pslfe_kf_search_by_sim3_poses projects too): q12[i1] = map point i1 of KF1 in KF2's
  *    image (radius < 0: none / already matched / bad / a gate failed), qdesc1 its descriptor, n1 = N1; q21 / qdesc2 / n2
  *    likewise.  Both directions, TH_HIGH, then the agreement check :1307-1323: match12[i1] = idx2 or -1. */
 int pslfe_kf_search_by_sim3(pslfe_kf* k, pslfe_frame* f1, int slot1, pslfe_frame* f2, int slot2, const PslProjQuery* q12,
@@ -731,7 +732,7 @@ int pslfe_kf_search_by_bow_candidates(pslfe_kf* k, pslfe_frame* f2, const int32_
                                       const int32_t* q_off, float nnratio, int check_orientation, int32_t* match,
                                       int32_t* nmatches);
 /* == ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290-403 (src/LoopClosing.cc:375) after
- *    the projection.  The host decomposes Scw :299-303, projects and applies the gates of :316-357 (isBad, spAlreadyFound, depth,
+ *    the projection (pslfe_kf_search_by_projection_sim3_pose projects too).  The host decomposes Scw :299-303, projects and applies the gates of :316-357 (isBad, spAlreadyFound, depth,
  *    IsInImage, distance range, viewing angle, PredictScale) and passes, per map point of vpPoints in order: u, v, radius =
  *    th*mvScaleFactors[nPredictedLevel] :360, max_level = nPredictedLevel (min_level, ur, angle, blocks are ignored), its
  *    descriptor; radius < 0 for a point dropped before the search - exactly the queries of pslfe_kf_window_best.
@@ -745,6 +746,67 @@ int pslfe_kf_search_by_bow_candidates(pslfe_kf* k, pslfe_frame* f2, const int32_
  *    (entry marks excluded: vpMatched[c] = vpPoints[assigned[c]] where assigned[c] >= 0); *nmatches = the return value. */
 int pslfe_kf_search_by_projection_sim3(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const uint8_t* qdesc,
                                        int nq, const uint8_t* taken, int32_t* match, int32_t* assigned, int* nmatches);
+/* ---- Projection of map points into keyframes: the part of Fuse (both), SearchByProjection(pKF, Scw, ...) and SearchBySim3 before
+ * the window search, for K keyframes x M map points in one call.  Conventions: those stated above PslPose (affine products, norm and
+ * dot as double sums, PredictScale with psl_log and its clamps, z <= 0 or NaN dropped); the view gate is compared in double
+ * (PO.dot(Pn) < 0.5 * (double)dist drops); every other float operation is the reference's, in its order, without contraction:
+ * x = X*invz, u = fx*x + cx (Frame::isInFrustum multiplies fx*X first), and KeyFrame::IsInImage src/KeyFrame.cc:726-729 has a
+ * STRICT upper bound (u >= min_x && u < max_x).
+ *   PSLFE_KF_PROJ_FUSE  Fuse(pKF, vpMapPoints, th) src/ORBmatcher.cc:842-890: p3Dc = Rcw*p3Dw + tcw, invz = 1/z in float, ur =
+ *                       u - bf*invz, PO = p3Dw - Ow with Ow = -Rcw.t()*tcw (KeyFrame::SetPose src/KeyFrame.cc:132-145 computes the same product),
+ *                       0.8f*min_dist <= |PO| <= 1.2f*max_dist, view gate, MapPoint::PredictScale(dist, pKF) src/MapPoint.cc:385-400,
+ *                       radius = th*mvScaleFactors[level];
+ *   PSLFE_KF_PROJ_SCW   Fuse(pKF, Scw, ...) :1000-1050 and SearchByProjection(pKF, Scw, ...) :312-360 with the Rcw, tcw the caller
+ *                       decomposed from Scw (:299-303, :984-988): the same with invz = 1.0/z rounded to float (:1019; 1/z in :331 is
+ *                       the same value); ur is written as in mode 0 and those searches ignore it;
+ *   PSLFE_KF_PROJ_SIM3  one direction of SearchBySim3 :1148-1189 / :1228-1269: p3Dc1 = R1w*p3Dw + t1w rounded to float, p3Dc2 =
+ *                       sR21*p3Dc1 + t21, invz = 1.0/z, dist = |p3Dc2|, distance gate, NO view gate, PredictScale, radius.  The
+ *                       caller forms sR12 = s12*R12, sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12 (:1119-1121). */
+#define PSLFE_KF_PROJ_FUSE 0
+#define PSLFE_KF_PROJ_SCW 1
+#define PSLFE_KF_PROJ_SIM3 2
+typedef struct PslKfView {
+    PslPose Tcw;   /* world -> camera of this keyframe (modes 0, 1); R1w, t1w of the SOURCE keyframe (mode 2) */
+    PslPose T21;   /* mode 2: sR21, t21 (camera 1 -> camera 2); ignored otherwise */
+    int32_t slot;  /* slot of the keyframe whose image is searched */
+} PslKfView;
+/* Row k*M + i of `queries` = map point mp[i] in keyframe views[k] (rows are NOT compacted: the searches index by map point):
+ * u, v, ur, radius, min_level = level-1, max_level = level, angle = 0, blocks = 0; a point that a gate drops, or whose
+ * skip[k*M + i] != 0 (isBad, IsInKeyFrame, spAlreadyFound, vbAlreadyMatched, NULL: the map stays with the caller; skip == NULL = none),
+ * has radius = -1 and every other field 0.  level[k*M + i] (may be NULL) = nPredictedLevel or -1.  mp holds mfMinDistance /
+ * mfMaxDistance; the 0.8f / 1.2f factors are applied inside.  `slot` is not read here.  K == 0 or M == 0: PSLFE_OK, nothing written. */
+int pslfe_kf_project(pslfe_kf* k, int mode, const PslKfView* views, int K, const PslMapPointGeom* mp, const uint8_t* skip, int M,
+                     const PslCamera* cam, float min_x, float min_y, float max_x, float max_y, const float* scale_factors, int nlevels,
+                     float log_scale_factor, float th, PslProjQuery* queries, int32_t* level);
+/* == ORBmatcher::Fuse(pKF, vpMapPoints, th) src/ORBmatcher.cc:825-948 (mode 0, reprojection gates :907-934 on) or
+ *    ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) :968-1085 (mode 1, gates off) up to bestDist, for the K keyframes
+ *    views[k].slot of one frame store against the same M map points: LocalMapping::SearchInNeighbors src/LocalMapping.cc:790-797 and
+ *    LoopClosing::SearchAndFuse src/LoopClosing.cc:587-600 in one call.  pslfe_kf_project, then the candidate loop of
+ *    pslfe_kf_window_best with mpdesc[i] (M x 32 bytes, shared by all keyframes) as the descriptor of row k*M + i: one upload each of
+ *    views, mp, mpdesc and skip, one launch chain, one synchronisation.  best_idx / best_dist [K*M] as pslfe_kf_window_best gives them
+ *    for keyframe k alone; queries (K*M rows, may be NULL) = the rows of pslfe_kf_project, for the host tail (:950-964).
+ *    inv_level_sigma2: mvInvLevelSigma2 (nlevels entries), required in mode 0. */
+int pslfe_kf_fuse_keyframes(pslfe_kf* k, pslfe_frame* f, int mode, const PslKfView* views, int K, const PslMapPointGeom* mp,
+                            const uint8_t* mpdesc, const uint8_t* skip, int M, const PslCamera* cam, float min_x, float min_y, float max_x,
+                            float max_y, const float* scale_factors, const float* inv_level_sigma2, int nlevels, float log_scale_factor,
+                            float th, int32_t* best_idx, int32_t* best_dist, PslProjQuery* queries);
+/* == ORBmatcher::SearchBySim3 src/ORBmatcher.cc:1102-1326 with both projections on the device.  view12: Tcw = R1w, t1w, T21 = sR21,
+ *    t21, slot = KF2's slot in f2; mp1 / desc1 / skip1: the n1 = N1 entries of pKF1->GetMapPointMatches() (skip1[i1] != 0: NULL,
+ *    vbAlreadyMatched1, isBad).  view21: Tcw = R2w, t2w, T21 = sR12, t12, slot = KF1's slot in f1; mp2 / desc2 / skip2 likewise.
+ *    Both mode-2 projections, then exactly pslfe_kf_search_by_sim3.  q12 / q21 (n1 / n2 rows, may be NULL): the projected rows. */
+int pslfe_kf_search_by_sim3_poses(pslfe_kf* k, pslfe_frame* f1, pslfe_frame* f2, const PslKfView* view12, const PslMapPointGeom* mp1,
+                                  const uint8_t* desc1, const uint8_t* skip1, int n1, const PslKfView* view21, const PslMapPointGeom* mp2,
+                                  const uint8_t* desc2, const uint8_t* skip2, int n2, const PslCamera* cam, float min_x, float min_y,
+                                  float max_x, float max_y, const float* scale_factors, int nlevels, float log_scale_factor, float th,
+                                  int32_t* match12, int* nfound, PslProjQuery* q12, PslProjQuery* q21);
+/* == ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290-403 from :312 on: the mode-1 projection of
+ *    the M map points into view->slot of f, then exactly pslfe_kf_search_by_projection_sim3 (taken, match, assigned, *nmatches as
+ *    there).  queries (M rows, may be NULL): the projected rows. */
+int pslfe_kf_search_by_projection_sim3_pose(pslfe_kf* k, pslfe_frame* f, const PslKfView* view, const PslMapPointGeom* mp,
+                                            const uint8_t* mpdesc, const uint8_t* skip, int M, const PslCamera* cam, float min_x,
+                                            float min_y, float max_x, float max_y, const float* scale_factors, int nlevels,
+                                            float log_scale_factor, float th, const uint8_t* taken, int32_t* match, int32_t* assigned,
+                                            int* nmatches, PslProjQuery* queries);
 /* One feature of KF1 in ORBmatcher::SearchForTriangulation, in the reference's iteration order (common vocabulary nodes
  * ascending, f1it->second order; features that have a map point and, under bOnlyStereo, those without a right coordinate
  * are dropped by the caller, :699-711). */

@@ -1089,6 +1089,17 @@ class ORBVocabulary:
 TRIQUERY_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("stereo", "<i4")])
 LINEFUSEQUERY_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("radius", "<f4"), ("level", "<i4")])
 assert TRIQUERY_DTYPE.itemsize == 24 and LINEFUSEQUERY_DTYPE.itemsize == 24
+# PslKfView: a keyframe as the device projection of map points sees it (include/pslfe.h)
+KFVIEW_DTYPE = np.dtype([("Tcw", POSE_DTYPE), ("T21", POSE_DTYPE), ("slot", "<i4")])
+assert KFVIEW_DTYPE.itemsize == 100
+KF_PROJ_FUSE, KF_PROJ_SCW, KF_PROJ_SIM3 = 0, 1, 2
+
+
+def _proj_args(cam, bounds, scale_factors, log_scale_factor, th):
+    """cam, bounds, scale_factors, nlevels, log_scale_factor, th as the pslfe_kf_* projections take them (keeps the arrays alive)"""
+    cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    sf = np.ascontiguousarray(scale_factors, np.float32)
+    return cam, sf, (_ptr(cam), *[C.c_float(b) for b in bounds], _ptr(sf)), (C.c_int(len(sf)), C.c_float(log_scale_factor), C.c_float(th))
 
 
 class KeyFrameMatcher:
@@ -1216,6 +1227,85 @@ class KeyFrameMatcher:
         _check(lib().pslfe_kf_search_by_projection_sim3(self._h, frame._h, C.c_int(slot), _ptr(q), _ptr(qd), C.c_int(len(q)), _ptr(tk),
                                                         _ptr(match), _ptr(assigned), C.byref(nm)), "pslfe_kf_search_by_projection_sim3")
         return nm.value, match[:len(q)], assigned[:n]
+
+    def project(self, mode, views, mp, cam, bounds, scale_factors, log_scale_factor, th, skip=None):
+        """pslfe_kf_project: the per-point arithmetic of Fuse (mode KF_PROJ_FUSE), Fuse / SearchByProjection with a decomposed Scw
+        (KF_PROJ_SCW) or one direction of SearchBySim3 (KF_PROJ_SIM3) for K keyframes (KFVIEW_DTYPE[K]) x M map points
+        (MAPPOINT_DTYPE[M]); skip [K, M] bytes or None.  -> (rows PROJQUERY_DTYPE [K, M], level [K, M])."""
+        v = np.ascontiguousarray(views, KFVIEW_DTYPE).reshape(-1)
+        g = np.ascontiguousarray(mp, MAPPOINT_DTYPE).reshape(-1)
+        K, M = len(v), len(g)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors, log_scale_factor, th)
+        q = np.zeros((K, M), PROJQUERY_DTYPE)
+        lvl = np.full((K, M), -1, np.int32)
+        _check(lib().pslfe_kf_project(self._h, C.c_int(mode), _ptr(v), C.c_int(K), _ptr(g), _ptr(sk), C.c_int(M), *a, *b, _ptr(q), _ptr(lvl)),
+               "pslfe_kf_project")
+        return q, lvl
+
+    def FuseKeyFrames(self, frame, mode, views, mp, mpdesc, cam, bounds, scale_factors, log_scale_factor, th, inv_level_sigma2=None,
+                      skip=None):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (mode KF_PROJ_FUSE, needs inv_level_sigma2) or Fuse(pKF, Scw, ...) (KF_PROJ_SCW) up to
+        bestDist for the K keyframes views[k]["slot"] of `frame` against the same M map points, projection included.
+        -> (bestIdx [K, M], bestDist [K, M], rows [K, M]); fused = bestDist <= TH_LOW, the caller mutates the map."""
+        v = np.ascontiguousarray(views, KFVIEW_DTYPE).reshape(-1)
+        g = np.ascontiguousarray(mp, MAPPOINT_DTYPE).reshape(-1)
+        K, M = len(v), len(g)
+        d = np.ascontiguousarray(mpdesc, np.uint8).reshape(M, 32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+        s2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors, log_scale_factor, th)
+        if s2 is not None and len(s2) != len(sf):
+            raise PslfeError(f"FuseKeyFrames: {len(s2)} inverse sigmas for {len(sf)} levels")
+        bi = np.full((K, M), -1, np.int32)
+        bd = np.full((K, M), 0x7fffffff, np.int32)
+        q = np.zeros((K, M), PROJQUERY_DTYPE)
+        _check(lib().pslfe_kf_fuse_keyframes(self._h, frame._h, C.c_int(mode), _ptr(v), C.c_int(K), _ptr(g), _ptr(d), _ptr(sk), C.c_int(M), *a,
+                                             _ptr(s2), *b, _ptr(bi), _ptr(bd), _ptr(q)), "pslfe_kf_fuse_keyframes")
+        return bi, bd, q
+
+    def SearchBySim3Poses(self, frame1, frame2, view12, mp1, desc1, skip1, view21, mp2, desc2, skip2, cam, bounds, scale_factors,
+                          log_scale_factor, th):
+        """ORBmatcher::SearchBySim3 src/ORBmatcher.cc:1102 with both projections on the device.  view12: R1w, t1w / sR21, t21 / KF2's slot
+        in frame2; view21: R2w, t2w / sR12, t12 / KF1's slot in frame1; mp / desc / skip per entry of GetMapPointMatches().
+        -> (nFound, match12, rows12, rows21)."""
+        v12 = np.ascontiguousarray(view12, KFVIEW_DTYPE).reshape(1)
+        v21 = np.ascontiguousarray(view21, KFVIEW_DTYPE).reshape(1)
+        g1, g2 = np.ascontiguousarray(mp1, MAPPOINT_DTYPE).reshape(-1), np.ascontiguousarray(mp2, MAPPOINT_DTYPE).reshape(-1)
+        n1, n2 = len(g1), len(g2)
+        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(n1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(n2, 32)
+        s1 = None if skip1 is None else np.ascontiguousarray(skip1, np.uint8).reshape(n1)
+        s2 = None if skip2 is None else np.ascontiguousarray(skip2, np.uint8).reshape(n2)
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors, log_scale_factor, th)
+        m = np.full(max(n1, 1), -1, np.int32)
+        q12, q21 = np.zeros(max(n1, 1), PROJQUERY_DTYPE), np.zeros(max(n2, 1), PROJQUERY_DTYPE)
+        nf = C.c_int()
+        _check(lib().pslfe_kf_search_by_sim3_poses(self._h, frame1._h, frame2._h, _ptr(v12), _ptr(g1), _ptr(d1), _ptr(s1), C.c_int(n1), _ptr(v21),
+                                                   _ptr(g2), _ptr(d2), _ptr(s2), C.c_int(n2), *a, *b, _ptr(m), C.byref(nf), _ptr(q12), _ptr(q21)),
+               "pslfe_kf_search_by_sim3_poses")
+        return nf.value, m[:n1], q12[:n1], q21[:n2]
+
+    def SearchByProjectionSim3Pose(self, frame, view, mp, mpdesc, cam, bounds, scale_factors, log_scale_factor, th, skip=None, taken=None):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) src/ORBmatcher.cc:290 from :312 on, projection included: view = the
+        decomposed Scw and the keyframe's slot.  -> (nmatches, match per map point, assigned per keypoint, rows)."""
+        v = np.ascontiguousarray(view, KFVIEW_DTYPE).reshape(1)
+        g = np.ascontiguousarray(mp, MAPPOINT_DTYPE).reshape(-1)
+        M = len(g)
+        d = np.ascontiguousarray(mpdesc, np.uint8).reshape(M, 32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(M)
+        n = frame.n[int(v["slot"][0])]
+        tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        if tk is not None and len(tk) != n:
+            raise PslfeError(f"SearchByProjectionSim3Pose: taken has {len(tk)} entries, the keyframe {n} keypoints")
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors, log_scale_factor, th)
+        match = np.full(max(M, 1), -1, np.int32)
+        assigned = np.full(max(n, 1), -1, np.int32)
+        q = np.zeros(max(M, 1), PROJQUERY_DTYPE)
+        nm = C.c_int()
+        _check(lib().pslfe_kf_search_by_projection_sim3_pose(self._h, frame._h, _ptr(v), _ptr(g), _ptr(d), _ptr(sk), C.c_int(M), *a, *b, _ptr(tk),
+                                                             _ptr(match), _ptr(assigned), C.byref(nm), _ptr(q)),
+               "pslfe_kf_search_by_projection_sim3_pose")
+        return nm.value, match[:M], assigned[:n], q[:M]
 
     def LineFuse(self, keylines, desc, queries, qdesc):
         """Search of LSDmatcher::Fuse add_src/LSDmatcher.cpp:933-958 -> (bestIdx, bestDist)."""

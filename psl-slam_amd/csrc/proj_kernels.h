@@ -1,10 +1,14 @@
-// Shared by pslfe_project.hip and pslfe_project_line.hip: the cv::Mat pose algebra of the projection conventions (include/pslfe.h,
+// Shared by pslfe_project.hip, pslfe_project_line.hip and pslfe_kf_project.hip: the cv::Mat pose algebra of the projection conventions (include/pslfe.h,
 // DESIGN.md §3) and the workgroup compaction that keeps emitted rows in input order.  Product code.
 #ifndef PSL_PROJ_KERNELS_H
 #define PSL_PROJ_KERNELS_H
 
 #include "pslfe_internal.h"
 #include "psl_device_math.h"
+#ifndef PSL_F64_QUAL
+#define PSL_F64_QUAL __host__ __device__ static inline
+#endif
+#include "psl_f64math.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PSL_DDIV(a, b) __ddiv_rn((a), (b))
@@ -27,6 +31,31 @@ __device__ __forceinline__ float psl_affine_row(float m0, float m1, float m2, fl
 __device__ __forceinline__ void psl_centre(const PslPose& T, float* c) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) c[r] = -psl_affine_row(T.R[r], T.R[3 + r], T.R[6 + r], T.t[0], T.t[1], T.t[2], 0.f);
+}
+
+// cv::norm of a float 3-vector: the double sum of squares in index order, sqrt in double, rounded to float
+__device__ __forceinline__ float psl_norm3(float p0, float p1, float p2) {
+    double s = PSL_DMUL((double)p0, (double)p0);
+    s = PSL_DADD(s, PSL_DMUL((double)p1, (double)p1));
+    s = PSL_DADD(s, PSL_DMUL((double)p2, (double)p2));
+    return (float)PSL_DSQRT(s);
+}
+
+// Mat::dot of two float 3-vectors: the double sum in index order
+__device__ __forceinline__ double psl_dot3(float p0, float p1, float p2, float n0, float n1, float n2) {
+    double dot = PSL_DMUL((double)p0, (double)n0);
+    dot = PSL_DADD(dot, PSL_DMUL((double)p1, (double)n1));
+    dot = PSL_DADD(dot, PSL_DMUL((double)p2, (double)n2));
+    return dot;
+}
+
+// MapPoint::PredictScale (src/MapPoint.cc:385-416, both overloads): ceil(log(mfMaxDistance / dist) / mfLogScaleFactor), clamped
+__device__ __forceinline__ int psl_predict_level(float max_dist, float dist, float log_scale_factor, int nlevels) {
+    const float ratio = PSL_FDIV(max_dist, dist);
+    // psl_log needs a positive finite argument: log(0) = -inf -> level 0, log(inf) = inf -> the last level
+    double ls = ratio > 0.f ? 1e300 : -1.0;
+    if (ratio > 0.f && ratio < __builtin_huge_valf()) ls = __builtin_ceil(PSL_DDIV(psl_log((double)ratio), (double)log_scale_factor));
+    return ls > 0.0 ? (ls < (double)nlevels ? (int)ls : nlevels - 1) : 0;
 }
 
 // Exclusive position of this thread's flag among the workgroup's set flags, and the workgroup's count.  All BS threads call it;

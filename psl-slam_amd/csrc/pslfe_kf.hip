@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "match_kernels.h"
+#include "kf_project.h"
 
 #define PSL_KF_LEVELS 16
 #define PSL_DISTINCT_MAX 1024  // observations of one map point handled (36 KB of descriptors in LDS)
@@ -29,17 +30,16 @@ struct BestArgs {
     int* best_dist;
 };
 
-// Fuse / SearchBySim3 candidate loop: one wave per projected map point.
-__global__ __launch_bounds__(256) void k_window_best(BestArgs A) {
-    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (qi >= A.nq) return;
+// Fuse / SearchBySim3 candidate loop of one projected map point against slot `slot`, by one wave: row qi of the queries, descriptor
+// row di; lane 0 writes best_idx[qi] / best_dist[qi].
+__device__ __forceinline__ void psl_window_best_row(const BestArgs& A, int slot, int qi, int di, int lane) {
     const PslProjQuery q = A.q[qi];
     if (!(q.radius >= 0)) {
         if (lane == 0) { A.best_idx[qi] = -1; A.best_dist[qi] = INT_MAX; }
         return;
     }
-    const FrameView V = psl_frame_view(A.S, A.slot);
-    const uint32_t* QD = reinterpret_cast<const uint32_t*>(A.qdesc + (size_t)qi * 32);
+    const FrameView V = psl_frame_view(A.S, slot);
+    const uint32_t* QD = reinterpret_cast<const uint32_t*>(A.qdesc + (size_t)di * 32);
     uint32_t qd[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) qd[k] = QD[k];
@@ -78,6 +78,21 @@ __global__ __launch_bounds__(256) void k_window_best(BestArgs A) {
         A.best_idx[qi] = best == PSL_KEY_INF ? -1 : V.gidx[best & 0xffffu];
         A.best_dist[qi] = best == PSL_KEY_INF ? INT_MAX : (int)(best >> 16);
     }
+}
+
+// one keyframe: one wave per projected map point
+__global__ __launch_bounds__(256) void k_window_best(BestArgs A) {
+    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (qi >= A.nq) return;
+    psl_window_best_row(A, A.slot, qi, qi, lane);
+}
+
+// K keyframes x M map points (pslfe_kf_fuse_keyframes): one wave per row k*M + i of pslfe_kf_project, searched in slot views[k].slot
+// with the descriptor of map point i.  Keyframes on blockIdx.y: the waves of a workgroup read one keyframe's grid.
+__global__ __launch_bounds__(256) void k_window_best_set(BestArgs A, const PslKfView* __restrict__ views) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, k = blockIdx.y;
+    if (i >= A.nq) return;   // nq = M
+    psl_window_best_row(A, views[k].slot, k * A.nq + i, i, lane);
 }
 
 // SearchBySim3 agreement check (src/ORBmatcher.cc:1225-1232, 1296-1323)
@@ -311,6 +326,37 @@ int launch_window_best(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery
     PSL_HIP(hipGetLastError());
     return PSLFE_OK;
 }
+
+// a slot a PslKfView names: PSLFE_E_INVALID outside the store, PSLFE_E_STATE when it was never set
+int check_view_slot(pslfe_frame* f, int slot, const char* who) {
+    PSL_REQUIRE(slot >= 0 && slot < f->max_frames, PSLFE_E_INVALID, "%s: slot %d outside the store (0..%d)", who, slot, f->max_frames - 1);
+    PSL_REQUIRE(f->slot_set[slot], PSLFE_E_STATE, "%s: slot %d not set", who, slot);
+    return PSLFE_OK;
+}
+
+// both directions and the agreement check of SearchBySim3 on device rows; d_m [n1], d_nf [1]
+int launch_sim3(pslfe_kf* k, pslfe_frame* f1, int slot1, pslfe_frame* f2, int slot2, const PslProjQuery* d_q1, const uint8_t* d_qd1, int n1,
+                const PslProjQuery* d_q2, const uint8_t* d_qd2, int n2, int* d_m, int* d_nf) {
+    hipStream_t st = k->ctx->stream;
+    const size_t m1 = (size_t)n1, m2 = (size_t)(n2 > 0 ? n2 : 1);
+    hipError_t e = hipSuccess;
+    int* d_b1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_d1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_b2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
+    int* d_d2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "SearchBySim3: %s", hipGetErrorString(e));
+    PSL_HIP(hipMemsetAsync(d_nf, 0, 4, st));
+    {
+        PSL_STAGE_BEGIN(k->ctx, "kf.sim3");
+        if (int rc = launch_window_best(k, f2, slot2, d_q1, d_qd1, n1, 0, nullptr, 0, d_b1, d_d1)) return rc;
+        if (n2 > 0)
+            if (int rc = launch_window_best(k, f1, slot1, d_q2, d_qd2, n2, 0, nullptr, 0, d_b2, d_d2)) return rc;
+        k_sim3_agree<<<(n1 + 255) / 256, 256, 0, st>>>(d_b1, d_d1, n1, d_b2, d_d2, n2, d_m, d_nf);
+        PSL_STAGE_END(k->ctx, "kf.sim3");
+    }
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -374,25 +420,97 @@ int pslfe_kf_search_by_sim3(pslfe_kf* k, pslfe_frame* f1, int slot1, pslfe_frame
     uint8_t* d_qd1 = psl_scratch_up(k->ctx, qdesc1, m1 * 32, st, &e);
     PslProjQuery* d_q2 = psl_scratch_up(k->ctx, n2 > 0 ? q21 : nullptr, m2, st, &e);
     uint8_t* d_qd2 = psl_scratch_up(k->ctx, n2 > 0 ? qdesc2 : nullptr, m2 * 32, st, &e);
-    int* d_b1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
-    int* d_d1 = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
     int* d_m = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
-    int* d_b2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
-    int* d_d2 = psl_scratch_up(k->ctx, (const int*)nullptr, m2, st, &e);
     int* d_nf = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "pslfe_kf_search_by_sim3: %s", hipGetErrorString(e));
-    PSL_HIP(hipMemsetAsync(d_nf, 0, 4, st));
-    {
-        PSL_STAGE_BEGIN(k->ctx, "kf.sim3");
-        if (int rc = launch_window_best(k, f2, slot2, d_q1, d_qd1, n1, 0, nullptr, 0, d_b1, d_d1)) return rc;
-        if (n2 > 0)
-            if (int rc = launch_window_best(k, f1, slot1, d_q2, d_qd2, n2, 0, nullptr, 0, d_b2, d_d2)) return rc;
-        k_sim3_agree<<<(n1 + 255) / 256, 256, 0, st>>>(d_b1, d_d1, n1, d_b2, d_d2, n2, d_m, d_nf);
-        PSL_STAGE_END(k->ctx, "kf.sim3");
-    }
-    PSL_HIP(hipGetLastError());
+    if (int rc = launch_sim3(k, f1, slot1, f2, slot2, d_q1, d_qd1, n1, d_q2, d_qd2, n2, d_m, d_nf)) return rc;
     PSL_HIP(hipMemcpyAsync(match12, d_m, m1 * 4, hipMemcpyDeviceToHost, st));
     PSL_HIP(hipMemcpyAsync(nfound, d_nf, 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
+}
+
+int pslfe_kf_fuse_keyframes(pslfe_kf* k, pslfe_frame* f, int mode, const PslKfView* views, int K, const PslMapPointGeom* mp,
+                            const uint8_t* mpdesc, const uint8_t* skip, int M, const PslCamera* cam, float min_x, float min_y, float max_x,
+                            float max_y, const float* scale_factors, const float* inv_level_sigma2, int nlevels, float log_scale_factor,
+                            float th, int32_t* best_idx, int32_t* best_dist, PslProjQuery* queries) {
+    static const char* who = "pslfe_kf_fuse_keyframes";
+    PSL_REQUIRE(k && f, PSLFE_E_INVALID, "%s: NULL handle", who);
+    PSL_REQUIRE(K >= 0 && M >= 0 && (double)K * (double)M <= (double)INT_MAX && K <= 65535, PSLFE_E_INVALID, "%s: K = %d, M = %d", who, K, M);
+    PSL_REQUIRE(mode == PSLFE_KF_PROJ_FUSE || mode == PSLFE_KF_PROJ_SCW, PSLFE_E_INVALID, "%s: mode %d (0: Fuse(pKF, ...), 1: Fuse(pKF, Scw, ...))",
+                who, mode);
+    const int chi2 = mode == PSLFE_KF_PROJ_FUSE;
+    PSL_REQUIRE(!chi2 || inv_level_sigma2, PSLFE_E_INVALID, "%s: the chi2 gates of mode 0 need mvInvLevelSigma2", who);
+    KfProjParams P;
+    if (int rc = psl_kf_proj_params(&P, mode, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who)) return rc;
+    if (K == 0 || M == 0) return PSLFE_OK;
+    PSL_REQUIRE(views && mp && mpdesc && best_idx && best_dist, PSLFE_E_INVALID, "%s: NULL argument", who);
+    for (int i = 0; i < K; ++i)
+        if (int rc = check_view_slot(f, views[i].slot, who)) return rc;
+    PSL_HIP(hipSetDevice(k->ctx->device));
+    hipStream_t st = k->ctx->stream;
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    const size_t rows = (size_t)K * M;
+    KfProjBuffers B;
+    if (int rc = psl_kf_project_upload(k->ctx, P, views, K, mp, skip, M, false, &B, who)) return rc;
+    hipError_t e = hipSuccess;
+    BestArgs A;
+    A.S = f->S; A.slot = 0; A.q = B.q; A.nq = M; A.chi2 = chi2;
+    A.qdesc = psl_scratch_up(k->ctx, mpdesc, (size_t)M * 32, st, &e);
+    A.best_idx = psl_scratch_up(k->ctx, (const int*)nullptr, rows, st, &e);
+    A.best_dist = psl_scratch_up(k->ctx, (const int*)nullptr, rows, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    for (int i = 0; i < PSL_KF_LEVELS; ++i) A.inv_sigma2[i] = (chi2 && i < nlevels) ? inv_level_sigma2[i] : 0.f;
+    {
+        PSL_STAGE_BEGIN(k->ctx, "kf.window_best_set");
+        k_window_best_set<<<dim3((M + 3) / 4, K), 256, 0, st>>>(A, B.views);
+        PSL_STAGE_END(k->ctx, "kf.window_best_set");
+    }
+    PSL_HIP(hipGetLastError());
+    PSL_HIP(hipMemcpyAsync(best_idx, A.best_idx, rows * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(best_dist, A.best_dist, rows * 4, hipMemcpyDeviceToHost, st));
+    if (queries) PSL_HIP(hipMemcpyAsync(queries, B.q, rows * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
+}
+
+int pslfe_kf_search_by_sim3_poses(pslfe_kf* k, pslfe_frame* f1, pslfe_frame* f2, const PslKfView* view12, const PslMapPointGeom* mp1,
+                                  const uint8_t* desc1, const uint8_t* skip1, int n1, const PslKfView* view21, const PslMapPointGeom* mp2,
+                                  const uint8_t* desc2, const uint8_t* skip2, int n2, const PslCamera* cam, float min_x, float min_y,
+                                  float max_x, float max_y, const float* scale_factors, int nlevels, float log_scale_factor, float th,
+                                  int32_t* match12, int* nfound, PslProjQuery* q12, PslProjQuery* q21) {
+    static const char* who = "pslfe_kf_search_by_sim3_poses";
+    PSL_REQUIRE(k && f1 && f2, PSLFE_E_INVALID, "%s: NULL handle", who);
+    PSL_REQUIRE(nfound && view12 && view21, PSLFE_E_INVALID, "%s: NULL view or output", who);
+    PSL_REQUIRE(n1 >= 0 && n2 >= 0, PSLFE_E_INVALID, "%s: negative count", who);
+    PSL_REQUIRE((n1 == 0 || (mp1 && desc1 && match12)) && (n2 == 0 || (mp2 && desc2)), PSLFE_E_INVALID, "%s: NULL argument", who);
+    KfProjParams P;
+    if (int rc = psl_kf_proj_params(&P, PSLFE_KF_PROJ_SIM3, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
+        return rc;
+    if (int rc = check_view_slot(f2, view12->slot, who)) return rc;   // map points of KF1 are searched in KF2's image
+    if (int rc = check_view_slot(f1, view21->slot, who)) return rc;
+    *nfound = 0;
+    if (n1 == 0) return PSLFE_OK;
+    PSL_HIP(hipSetDevice(k->ctx->device));
+    hipStream_t st = k->ctx->stream;
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    KfProjBuffers B1, B2;
+    B2.q = nullptr;
+    if (int rc = psl_kf_project_upload(k->ctx, P, view12, 1, mp1, skip1, n1, false, &B1, who)) return rc;
+    if (n2 > 0)
+        if (int rc = psl_kf_project_upload(k->ctx, P, view21, 1, mp2, skip2, n2, false, &B2, who)) return rc;
+    const size_t m1 = (size_t)n1, m2 = (size_t)(n2 > 0 ? n2 : 1);
+    hipError_t e = hipSuccess;
+    uint8_t* d_qd1 = psl_scratch_up(k->ctx, desc1, m1 * 32, st, &e);
+    uint8_t* d_qd2 = psl_scratch_up(k->ctx, n2 > 0 ? desc2 : nullptr, m2 * 32, st, &e);
+    int* d_m = psl_scratch_up(k->ctx, (const int*)nullptr, m1, st, &e);
+    int* d_nf = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int rc = launch_sim3(k, f1, view21->slot, f2, view12->slot, B1.q, d_qd1, n1, B2.q, d_qd2, n2, d_m, d_nf)) return rc;
+    PSL_HIP(hipMemcpyAsync(match12, d_m, m1 * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(nfound, d_nf, 4, hipMemcpyDeviceToHost, st));
+    if (q12) PSL_HIP(hipMemcpyAsync(q12, B1.q, m1 * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
+    if (q21 && n2 > 0) PSL_HIP(hipMemcpyAsync(q21, B2.q, (size_t)n2 * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
     PSL_HIP(hipStreamSynchronize(st));
     return PSLFE_OK;
 }

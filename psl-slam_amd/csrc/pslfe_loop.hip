@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "match_kernels.h"
+#include "kf_project.h"
 
 #define PSL_LOOP_TOPK 8
 #define PSL_BOW_ROW_WORDS 9    // odd stride: lanes on consecutive rows hit different banks
@@ -293,6 +294,57 @@ int loop_check_slot(pslfe_frame* f, int slot, const char* who) {
     PSL_REQUIRE(slot >= 0 && slot < f->max_frames && f->slot_set[slot], PSLFE_E_STATE, "%s: slot %d not set", who, slot);
     return PSLFE_OK;
 }
+
+// SearchByProjection(pKF, Scw, ...) from :362 on.  The rows are the caller's (`queries`, host) or, with P != NULL, projected here from
+// view / mp / skip (pslfe_kf_project, mode 1) and copied to queries_out when that is not NULL.
+int loop_proj_search(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const KfProjParams* P, const PslKfView* view,
+                     const PslMapPointGeom* mp, const uint8_t* skip, const uint8_t* qdesc, int nq, const uint8_t* taken, int32_t* match,
+                     int32_t* assigned, int* nmatches, PslProjQuery* queries_out, const char* who) {
+    *nmatches = 0;
+    PSL_HIP(hipSetDevice(k->ctx->device));
+    hipStream_t st = k->ctx->stream;
+    FrameMeta m;
+    PSL_HIP(hipMemcpyAsync(&m, f->S.meta + slot, sizeof(m), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    const int n = std::min(std::max(m.n, 0), PSL_QMAX);
+    if (assigned)
+        for (int i = 0; i < n; ++i) assigned[i] = -1;
+    if (nq == 0) return PSLFE_OK;
+    const size_t nk = (size_t)(n > 0 ? n : 1);
+    if (int rc = psl_scratch_begin(k->ctx)) return rc;
+    hipError_t e = hipSuccess;
+    LoopProjArgs A;
+    A.S = f->S; A.slot = slot; A.nq = nq;
+    if (P) {
+        KfProjBuffers B;
+        if (int rc = psl_kf_project_upload(k->ctx, *P, view, 1, mp, skip, nq, false, &B, who)) return rc;
+        A.q = B.q;
+    } else {
+        A.q = psl_scratch_up(k->ctx, queries, nq, st, &e);
+    }
+    A.qdesc = psl_scratch_up(k->ctx, qdesc, (size_t)nq * 32, st, &e);
+    A.taken = (taken && n > 0) ? psl_scratch_up(k->ctx, taken, nk, st, &e) : nullptr;
+    A.topk = psl_scratch_up(k->ctx, (const int*)nullptr, (size_t)nq * PSL_LOOP_TOPK, st, &e);
+    A.more = psl_scratch_up(k->ctx, (const uint8_t*)nullptr, nq, st, &e);
+    A.match = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
+    A.assigned = psl_scratch_up(k->ctx, (const int*)nullptr, nk, st, &e);
+    A.nmatches = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    PSL_HIP(hipMemsetAsync(A.assigned, 0xff, nk * 4, st));
+    {
+        PSL_STAGE_BEGIN(k->ctx, "kf.projection_sim3");
+        k_loop_proj_lists<<<(nq + 3) / 4, 256, 0, st>>>(A);
+        k_loop_proj_resolve<<<1, 64, 0, st>>>(A);
+        PSL_STAGE_END(k->ctx, "kf.projection_sim3");
+    }
+    PSL_HIP(hipGetLastError());
+    PSL_HIP(hipMemcpyAsync(match, A.match, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    if (assigned && n > 0) PSL_HIP(hipMemcpyAsync(assigned, A.assigned, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost, st));
+    if (P && queries_out) PSL_HIP(hipMemcpyAsync(queries_out, A.q, (size_t)nq * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -398,43 +450,25 @@ int pslfe_kf_search_by_projection_sim3(pslfe_kf* k, pslfe_frame* f, int slot, co
     PSL_REQUIRE(k && f && nmatches && (nq == 0 || (queries && qdesc && match)), PSLFE_E_INVALID, "%s: NULL argument", who);
     PSL_REQUIRE(nq >= 0, PSLFE_E_INVALID, "%s: nq = %d", who, nq);
     if (int rc = loop_check_slot(f, slot, who)) return rc;
-    *nmatches = 0;
-    PSL_HIP(hipSetDevice(k->ctx->device));
-    hipStream_t st = k->ctx->stream;
-    FrameMeta m;
-    PSL_HIP(hipMemcpyAsync(&m, f->S.meta + slot, sizeof(m), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    const int n = std::min(std::max(m.n, 0), PSL_QMAX);
-    if (assigned)
-        for (int i = 0; i < n; ++i) assigned[i] = -1;
-    if (nq == 0) return PSLFE_OK;
-    const size_t nk = (size_t)(n > 0 ? n : 1);
-    if (int rc = psl_scratch_begin(k->ctx)) return rc;
-    hipError_t e = hipSuccess;
-    LoopProjArgs A;
-    A.S = f->S; A.slot = slot; A.nq = nq;
-    A.q = psl_scratch_up(k->ctx, queries, nq, st, &e);
-    A.qdesc = psl_scratch_up(k->ctx, qdesc, (size_t)nq * 32, st, &e);
-    A.taken = (taken && n > 0) ? psl_scratch_up(k->ctx, taken, nk, st, &e) : nullptr;
-    A.topk = psl_scratch_up(k->ctx, (const int*)nullptr, (size_t)nq * PSL_LOOP_TOPK, st, &e);
-    A.more = psl_scratch_up(k->ctx, (const uint8_t*)nullptr, nq, st, &e);
-    A.match = psl_scratch_up(k->ctx, (const int*)nullptr, nq, st, &e);
-    A.assigned = psl_scratch_up(k->ctx, (const int*)nullptr, nk, st, &e);
-    A.nmatches = psl_scratch_up(k->ctx, (const int*)nullptr, 1, st, &e);
-    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    PSL_HIP(hipMemsetAsync(A.assigned, 0xff, nk * 4, st));
-    {
-        PSL_STAGE_BEGIN(k->ctx, "kf.projection_sim3");
-        k_loop_proj_lists<<<(nq + 3) / 4, 256, 0, st>>>(A);
-        k_loop_proj_resolve<<<1, 64, 0, st>>>(A);
-        PSL_STAGE_END(k->ctx, "kf.projection_sim3");
-    }
-    PSL_HIP(hipGetLastError());
-    PSL_HIP(hipMemcpyAsync(match, A.match, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    if (assigned && n > 0) PSL_HIP(hipMemcpyAsync(assigned, A.assigned, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipMemcpyAsync(nmatches, A.nmatches, 4, hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    return PSLFE_OK;
+    return loop_proj_search(k, f, slot, queries, nullptr, nullptr, nullptr, nullptr, qdesc, nq, taken, match, assigned, nmatches, nullptr, who);
+}
+
+int pslfe_kf_search_by_projection_sim3_pose(pslfe_kf* k, pslfe_frame* f, const PslKfView* view, const PslMapPointGeom* mp,
+                                            const uint8_t* mpdesc, const uint8_t* skip, int M, const PslCamera* cam, float min_x,
+                                            float min_y, float max_x, float max_y, const float* scale_factors, int nlevels,
+                                            float log_scale_factor, float th, const uint8_t* taken, int32_t* match, int32_t* assigned,
+                                            int* nmatches, PslProjQuery* queries) {
+    static const char* who = "pslfe_kf_search_by_projection_sim3_pose";
+    PSL_REQUIRE(k && f, PSLFE_E_INVALID, "%s: NULL handle", who);
+    PSL_REQUIRE(view && nmatches && (M == 0 || (mp && mpdesc && match)), PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE(M >= 0, PSLFE_E_INVALID, "%s: M = %d", who, M);
+    KfProjParams P;
+    if (int rc = psl_kf_proj_params(&P, PSLFE_KF_PROJ_SCW, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
+        return rc;
+    PSL_REQUIRE(view->slot >= 0 && view->slot < f->max_frames, PSLFE_E_INVALID, "%s: slot %d outside the store (0..%d)", who, view->slot,
+                f->max_frames - 1);
+    if (int rc = loop_check_slot(f, view->slot, who)) return rc;
+    return loop_proj_search(k, f, view->slot, nullptr, &P, view, mp, skip, mpdesc, M, taken, match, assigned, nmatches, queries, who);
 }
 
 }  // extern "C"

@@ -20,8 +20,6 @@
 
 #include "pslfe_internal.h"
 #include "psl_device_math.h"
-#define PSL_F64_QUAL __host__ __device__ static inline
-#include "psl_f64math.h"
 
 #include "match_kernels.h"
 #include "proj_kernels.h"
@@ -254,22 +252,12 @@ __global__ __launch_bounds__(PSL_PROJ_BS) void k_project_frustum(FrustumArgs A, 
                 if (u >= P.minX && u <= P.maxX && v >= P.minY && v <= P.maxY) {
                     const float maxD = PSL_FMUL(1.2f, G.max_dist), minD = PSL_FMUL(0.8f, G.min_dist);
                     const float p0 = PSL_FSUB(G.x, Ow[0]), p1 = PSL_FSUB(G.y, Ow[1]), p2 = PSL_FSUB(G.z, Ow[2]);
-                    double s = PSL_DMUL((double)p0, (double)p0);
-                    s = PSL_DADD(s, PSL_DMUL((double)p1, (double)p1));
-                    s = PSL_DADD(s, PSL_DMUL((double)p2, (double)p2));
-                    const float dist = (float)PSL_DSQRT(s);
+                    const float dist = psl_norm3(p0, p1, p2);
                     if (!(dist < minD || dist > maxD)) {
-                        double dot = PSL_DMUL((double)p0, (double)G.nx);
-                        dot = PSL_DADD(dot, PSL_DMUL((double)p1, (double)G.ny));
-                        dot = PSL_DADD(dot, PSL_DMUL((double)p2, (double)G.nz));
+                        const double dot = psl_dot3(p0, p1, p2, G.nx, G.ny, G.nz);
                         const float viewCos = (float)PSL_DDIV(dot, (double)dist);
                         if (!(viewCos < P.view_cos_limit)) {
-                            const float ratio = PSL_FDIV(G.max_dist, dist);
-                            // psl_log needs a positive finite argument: log(0) = -inf -> level 0, log(inf) = inf -> the last level
-                            double ls = ratio > 0.f ? 1e300 : -1.0;
-                            if (ratio > 0.f && ratio < __builtin_huge_valf())
-                                ls = __builtin_ceil(PSL_DDIV(psl_log((double)ratio), (double)P.log_scale_factor));
-                            lvl = ls > 0.0 ? (ls < (double)P.nlevels ? (int)ls : P.nlevels - 1) : 0;
+                            lvl = psl_predict_level(G.max_dist, dist, P.log_scale_factor, P.nlevels);
                             vc = viewCos;
                             float r = (double)viewCos > 0.998 ? 2.5f : 4.0f;
                             if (P.th != 1.0f) r = PSL_FMUL(r, P.th);

@@ -794,6 +794,83 @@ public:
                                                  match.data(), assigned.data(), &nm), "pslfe_kf_search_by_projection_sim3");
         return nm;
     }
+    // pslfe_kf_project: rows k*M + i = map point i in keyframe views[k] (mode PSLFE_KF_PROJ_FUSE / _SCW / _SIM3); skip: K*M bytes or
+    // empty; bounds = {mnMinX, mnMinY, mnMaxX, mnMaxY}; level (may be nullptr) = nPredictedLevel or -1
+    void Project(int mode, const std::vector<PslKfView>& views, const std::vector<PslMapPointGeom>& mp, const std::vector<uint8_t>& skip,
+                 const PslCamera& cam, const float bounds[4], const std::vector<float>& scaleFactors, float logScaleFactor, float th,
+                 std::vector<PslProjQuery>& rows, std::vector<int32_t>* level = nullptr) {
+        const size_t n = views.size() * mp.size();
+        checkSkip(skip, n, "Project");
+        rows.assign(n, PslProjQuery{});
+        if (level) level->assign(n, -1);
+        check(pslfe_kf_project(h_, mode, views.data(), (int)views.size(), mp.data(), skip.empty() ? nullptr : skip.data(), (int)mp.size(), &cam,
+                               bounds[0], bounds[1], bounds[2], bounds[3], scaleFactors.data(), (int)scaleFactors.size(), logScaleFactor, th,
+                               rows.data(), level ? level->data() : nullptr), "pslfe_kf_project");
+    }
+    // Fuse(pKF, vpMapPoints, th) (PSLFE_KF_PROJ_FUSE, invLevelSigma2 required) or Fuse(pKF, Scw, ...) (PSLFE_KF_PROJ_SCW) up to bestDist for
+    // the keyframes views[k].slot of `kf` against the same map points, projection included; rows (may be nullptr) for the host tail
+    void FuseKeyFrames(FrameGrid& kf, int mode, const std::vector<PslKfView>& views, const std::vector<PslMapPointGeom>& mp,
+                       const std::vector<uint8_t>& mpdesc, const std::vector<uint8_t>& skip, const PslCamera& cam, const float bounds[4],
+                       const std::vector<float>& scaleFactors, const std::vector<float>* invLevelSigma2, float logScaleFactor, float th,
+                       std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist, std::vector<PslProjQuery>* rows = nullptr) {
+        const size_t n = views.size() * mp.size();
+        checkSkip(skip, n, "FuseKeyFrames");
+        if (mpdesc.size() != mp.size() * 32) throw Error(PSLFE_E_INVALID, "FuseKeyFrames: mpdesc needs 32 bytes per map point");
+        if (invLevelSigma2 && invLevelSigma2->size() != scaleFactors.size())
+            throw Error(PSLFE_E_INVALID, "FuseKeyFrames: invLevelSigma2 needs one entry per level");
+        bestIdx.assign(n, -1); bestDist.assign(n, 0x7fffffff);
+        if (rows) rows->assign(n, PslProjQuery{});
+        check(pslfe_kf_fuse_keyframes(h_, kf.get(), mode, views.data(), (int)views.size(), mp.data(), mpdesc.data(),
+                                      skip.empty() ? nullptr : skip.data(), (int)mp.size(), &cam, bounds[0], bounds[1], bounds[2], bounds[3],
+                                      scaleFactors.data(), invLevelSigma2 ? invLevelSigma2->data() : nullptr, (int)scaleFactors.size(),
+                                      logScaleFactor, th, bestIdx.data(), bestDist.data(), rows ? rows->data() : nullptr),
+              "pslfe_kf_fuse_keyframes");
+    }
+    // SearchBySim3 with both projections on the device: view12 = {R1w t1w, sR21 t21, KF2's slot in kf2}, view21 = {R2w t2w, sR12 t12,
+    // KF1's slot in kf1}; mp / desc / skip per entry of GetMapPointMatches() (skip may be empty).  Returns nFound.
+    int SearchBySim3Poses(FrameGrid& kf1, FrameGrid& kf2, const PslKfView& view12, const std::vector<PslMapPointGeom>& mp1,
+                          const std::vector<uint8_t>& desc1, const std::vector<uint8_t>& skip1, const PslKfView& view21,
+                          const std::vector<PslMapPointGeom>& mp2, const std::vector<uint8_t>& desc2, const std::vector<uint8_t>& skip2,
+                          const PslCamera& cam, const float bounds[4], const std::vector<float>& scaleFactors, float logScaleFactor, float th,
+                          std::vector<int32_t>& match12, std::vector<PslProjQuery>* rows12 = nullptr, std::vector<PslProjQuery>* rows21 = nullptr) {
+        checkSkip(skip1, mp1.size(), "SearchBySim3Poses");
+        checkSkip(skip2, mp2.size(), "SearchBySim3Poses");
+        if (desc1.size() != mp1.size() * 32 || desc2.size() != mp2.size() * 32)
+            throw Error(PSLFE_E_INVALID, "SearchBySim3Poses: descriptors need 32 bytes per map point");
+        match12.assign(mp1.size(), -1);
+        if (rows12) rows12->assign(mp1.size(), PslProjQuery{});
+        if (rows21) rows21->assign(mp2.size(), PslProjQuery{});
+        int nf = 0;
+        check(pslfe_kf_search_by_sim3_poses(h_, kf1.get(), kf2.get(), &view12, mp1.data(), desc1.data(), skip1.empty() ? nullptr : skip1.data(),
+                                            (int)mp1.size(), &view21, mp2.data(), desc2.data(), skip2.empty() ? nullptr : skip2.data(),
+                                            (int)mp2.size(), &cam, bounds[0], bounds[1], bounds[2], bounds[3], scaleFactors.data(),
+                                            (int)scaleFactors.size(), logScaleFactor, th, match12.data(), &nf, rows12 ? rows12->data() : nullptr,
+                                            rows21 ? rows21->data() : nullptr), "pslfe_kf_search_by_sim3_poses");
+        return nf;
+    }
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) from :312 on, projection included: view = {the decomposed Scw, -, the
+    // keyframe's slot}; taken / match / assigned as SearchByProjectionSim3.  Returns nmatches.
+    int SearchByProjectionSim3Pose(FrameGrid& kf, const PslKfView& view, const std::vector<PslMapPointGeom>& mp, const std::vector<uint8_t>& mpdesc,
+                                   const std::vector<uint8_t>& skip, const PslCamera& cam, const float bounds[4],
+                                   const std::vector<float>& scaleFactors, float logScaleFactor, float th, const std::vector<uint8_t>& taken,
+                                   std::vector<int32_t>& match, std::vector<int32_t>& assigned, std::vector<PslProjQuery>* rows = nullptr) {
+        checkSkip(skip, mp.size(), "SearchByProjectionSim3Pose");
+        if (mpdesc.size() != mp.size() * 32) throw Error(PSLFE_E_INVALID, "SearchByProjectionSim3Pose: mpdesc needs 32 bytes per map point");
+        int n = 0;
+        check(pslfe_frame_fetch(kf.get(), view.slot, nullptr, nullptr, nullptr, 0x7fffffff, &n), "pslfe_frame_fetch");
+        if (!taken.empty() && (int)taken.size() != n)
+            throw Error(PSLFE_E_INVALID, "SearchByProjectionSim3Pose: taken needs one entry per keypoint of the slot");
+        match.assign(mp.size(), -1);
+        assigned.assign(n, -1);
+        if (rows) rows->assign(mp.size(), PslProjQuery{});
+        int nm = 0;
+        check(pslfe_kf_search_by_projection_sim3_pose(h_, kf.get(), &view, mp.data(), mpdesc.data(), skip.empty() ? nullptr : skip.data(),
+                                                      (int)mp.size(), &cam, bounds[0], bounds[1], bounds[2], bounds[3], scaleFactors.data(),
+                                                      (int)scaleFactors.size(), logScaleFactor, th, taken.empty() ? nullptr : taken.data(),
+                                                      match.data(), assigned.data(), &nm, rows ? rows->data() : nullptr),
+              "pslfe_kf_search_by_projection_sim3_pose");
+        return nm;
+    }
     void LineFuse(const std::vector<PslKeyLine>& kls, const std::vector<uint8_t>& desc, const std::vector<PslLineFuseQuery>& q,
                   const std::vector<uint8_t>& qdesc, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
         bestIdx.assign(q.size(), -1); bestDist.assign(q.size(), 256);
@@ -807,6 +884,9 @@ public:
         return best;
     }
 private:
+    static void checkSkip(const std::vector<uint8_t>& skip, size_t n, const char* who) {
+        if (!skip.empty() && skip.size() != n) throw Error(PSLFE_E_INVALID, std::string(who) + ": skip needs one byte per (keyframe, map point)");
+    }
     pslfe_kf* h_ = nullptr;
 };
 
