@@ -417,9 +417,10 @@ __device__ __forceinline__ void lsdn_shrink(LsdnRect& r, int phase) {
 // rect_improve() is: first test; then five phases (finer precision; narrower; one side; the other side; finer precision again),
 // each of five trial rectangles, returning as soon as a phase ends with log_nfa > 0.  The trials of a phase do not depend on
 // each other's outcome (r changes cumulatively, rec only receives copies), and the two halves of a trial parallelise in
-// opposite ways, so every phase is TWO launches over all rectangles that are still undecided:
-//   k_lsd_nfa_count<PH>  16 lanes = (rectangle, trial): the pixel scan (for the finer-precision phases 16 lanes = rectangle, one
-//                        scan for all five tolerances) -> (n, k) per trial;
+// opposite ways, so every phase is TWO groups of launches over the rectangles that are still undecided:
+//   k_lsd_nfa_count<PH>  16 lanes = rectangle: ONE pixel scan for the five trials of the phase -> (n, k) per trial.  The first test and
+//                        the first finer-precision phase scan the same pixels (the first test changes neither the geometry nor p), so
+//                        k_lsd_nfa_count<PSL_NFA_FIRST> counts all six tolerances in its one pass and phase -1 has no count launch;
 //   k_lsd_nfa_setup<PH> / k_lsd_nfa_series<PH>  THREAD = (rectangle, trial): nfa(n, k, p) is scalar code - thousands of
 //                        independent evaluations per launch instead of one per wave; the series are drawn from a shared
 //                        counter, because their lengths differ widely;
@@ -427,6 +428,10 @@ __device__ __forceinline__ void lsdn_shrink(LsdnRect& r, int phase) {
 //                        chosen trial rebuilt by replaying its steps, accept / keep going / reject.
 // State per rectangle: PSL_LSD_RECT_F64 doubles in `rects` (x1 y1 x2 y2 width theta dx dy | prec p log_nfa) and one byte in
 // `keep`: 0 = rejected, 1 = accepted, 2 = undecided.  PH: -2 first test, -1 finer, 0 narrower, 1 / 2 one side, 3 finer again.
+// The undecided rectangles of a frame are a LIST: k_lsd_nfa_select<PH> appends the index of every rectangle it leaves undecided to
+// the list the launches of the next phase walk (`ulist` [F][maxseg] uint16_t and `ucount` [F] per phase, the counters zeroed on the
+// stream; two lists, read and written alternately).  The order of a list is whatever the appends give: the rectangles are
+// independent and every result is stored by rectangle index, so it only affects the schedule.
 #define PSL_NFA_FIRST (-2)
 
 __device__ __forceinline__ void lsdn_load(const double* __restrict__ r, LsdnRect* rec) {
@@ -439,33 +444,46 @@ __device__ __forceinline__ void lsdn_load(const double* __restrict__ r, LsdnRect
 #endif
 
 #ifndef PSL_NFA_COUNT_WAVES
-#define PSL_NFA_COUNT_WAVES 8   // register bound: 64 VGPRs (78 at 4): 39.9 -> 38.4 ms per 12288 dense frames (profiles/r03z_ab_nfa_grid.log)
+#define PSL_NFA_COUNT_WAVES 8   // register bound: 64 VGPRs (78 at 4): 39.9 -> 38.4 ms per 12288 dense frames (profiles/r03z_ab_nfa_grid.log); the first test's pass with its six
+                                // tolerances spills 50 registers under it and none at 6 waves (80 VGPRs): the same time within the spread (profiles/nfa_list_ab.log)
 #endif
 template <int PH>
 __global__ __launch_bounds__(256, PSL_NFA_COUNT_WAVES) void k_lsd_nfa_count(LineParams P, const float* __restrict__ angdeg, double* __restrict__ rects,
-                                                          const int* __restrict__ nrect, const uint8_t* __restrict__ keep, int2* __restrict__ counts) {
-    constexpr int TR = 1;                               // scans per rectangle: the five trials of a phase share ONE pass (lsdn_count_trials / lsdn_count<5>)
+                                                          const int* __restrict__ nrect, const uint16_t* __restrict__ ulist, const int* __restrict__ ucount,
+                                                          int2* __restrict__ counts, int2* __restrict__ count0) {
+    static_assert(PH == PSL_NFA_FIRST || (PH >= 0 && PH <= 3), "phase -1 is counted by the first test's pass");
     constexpr int GPB = 256 / PSL_NFA_GL;               // scans in flight per workgroup
     __shared__ int s_geo[GPB * 45];                     // per scan group: five trial geometries (LsdnGeomI)
     const int frame = blockIdx.y, lane = threadIdx.x & (PSL_NFA_GL - 1);
-    const int cnt = nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg;
+    // the first test scans every rectangle of the frame, a phase the frame's undecided ones (at most maxseg: a rectangle is listed once)
+    const int cnt = PH == PSL_NFA_FIRST ? (nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg) : ucount[frame];
+    const uint16_t* ul = ulist + (size_t)frame * P.maxseg;
     const float* ang = angdeg + (size_t)frame * P.W * P.H;
     // every lane runs its own trip count (its group's items); nothing inside the loop crosses groups
-    for (int item = (int)blockIdx.x * GPB + (int)(threadIdx.x / PSL_NFA_GL); item < cnt * TR; item += (int)gridDim.x * GPB) {
-        const int idx = item / TR, j = item - idx * TR;
+    for (int item = (int)blockIdx.x * GPB + (int)(threadIdx.x / PSL_NFA_GL); item < cnt; item += (int)gridDim.x * GPB) {
+        const int idx = PH == PSL_NFA_FIRST ? item : (int)ul[item];
         const size_t o = (size_t)frame * P.maxseg + idx;
-        if (PH != PSL_NFA_FIRST && keep[o] != 2) continue;
         double* rs = rects + o * PSL_LSD_RECT_F64;
         LsdnRect rec;
         lsdn_load(rs, &rec);
-        if (PH == PSL_NFA_FIRST) {
-            rec.prec = P.prec; rec.p = P.p;
-            if (lane == 0) { rs[8] = rec.prec; rs[9] = rec.p; }
-        }
         LsdnGeom G;
         int2* out = counts + o * 5;
-        if (PH == -1 || PH == 3) {       // five tolerances p / 2^(j+1), one geometry, ONE pass over the pixels
-            if (PH == 3 && !(PSL_DSUB(rec.width, 0.5) >= 0.5)) {   // the guard holds for all five trials or for none
+        if (PH == PSL_NFA_FIRST) {       // the first test's tolerance and the five of phase -1, p / 2^(t+1): one geometry, ONE pass over the pixels
+            if (lane == 0) { rs[8] = P.prec; rs[9] = P.p; }
+            double pr[6], pp = P.p;
+            pr[0] = P.prec;
+#pragma unroll
+            for (int t = 0; t < 5; ++t) { pp = pp / 2; pr[t + 1] = PSL_DMUL(pp, PSL_PI); }
+            int tot, kk[6];
+            lsdn_geom(rec, P.H, &G);
+            lsdn_count<6, PSL_NFA_GL>(ang, P.W, G, rec.theta, pr, lane, &tot, kk);
+            if (lane == 0) {
+                count0[o] = make_int2(tot, kk[0]);
+#pragma unroll
+                for (int t = 0; t < 5; ++t) out[t] = make_int2(tot, kk[t + 1]);
+            }
+        } else if (PH == 3) {            // five tolerances p / 2^(t+1), one geometry, ONE pass over the pixels
+            if (!(PSL_DSUB(rec.width, 0.5) >= 0.5)) {   // the guard holds for all five trials or for none
                 if (lane < 5) out[lane] = make_int2(-1, 0);
                 continue;
             }
@@ -479,7 +497,7 @@ __global__ __launch_bounds__(256, PSL_NFA_COUNT_WAVES) void k_lsd_nfa_count(Line
 #pragma unroll
                 for (int t = 0; t < 5; ++t) out[t] = make_int2(tot, kk[t]);
             }
-        } else if (PH >= 0) {            // trial t = t + 1 cumulative steps, each under the width guard (it only ever turns false)
+        } else {                         // trial t = t + 1 cumulative steps, each under the width guard (it only ever turns false)
             int* geo = &s_geo[(threadIdx.x / PSL_NFA_GL) * 45];
             if (lane < 5) {              // lane t builds trial t's geometry
                 LsdnRect r = rec;
@@ -507,11 +525,6 @@ __global__ __launch_bounds__(256, PSL_NFA_COUNT_WAVES) void k_lsd_nfa_count(Line
                 for (int t = 0; t < 5; ++t) out[t] = geo[9 * t + 1] == -2 ? make_int2(-1, 0) : make_int2(nn[t], kk[t]);
             }
             __builtin_amdgcn_wave_barrier();   // the group's geometries are rewritten by its next item
-        } else {                         // the first test: one scan
-            int nn = -1, kk = 0;
-            lsdn_geom(rec, P.H, &G);
-            lsdn_count<1, PSL_NFA_GL>(ang, P.W, G, rec.theta, &rec.prec, lane, &nn, &kk);
-            if (lane == 0) out[j] = make_int2(nn, kk);
         }
     }
 }
@@ -551,15 +564,18 @@ __device__ __forceinline__ int lsdn_series_class(int n, int k, double p) {
 }
 
 // workgroup = frame (all items of the frame, so that its series can be bucketed by predicted length in LDS without global
-// atomics).  list: [F][maxseg * 5] entries, class-major; coff: [F][PSL_NFA_NCLS + 1] offsets of the classes
+// atomics).  list: [F][maxseg * 5] entries, class-major; coff: [F][PSL_NFA_NCLS + 1] offsets of the classes.  The items of a phase
+// are (position in the frame's list of undecided rectangles, trial); the first test's are the frame's rectangles, its (n, k) in count0
 template <int PH>
 __global__ __launch_bounds__(256) void k_lsd_nfa_setup(LineParams P, LsdnTables T, const double* __restrict__ rects, const int* __restrict__ nrect,
-                                                       const uint8_t* __restrict__ keep, const int2* __restrict__ counts, double* __restrict__ vals,
+                                                       const uint16_t* __restrict__ ulist, const int* __restrict__ ucount, const int2* __restrict__ counts,
+                                                       const int2* __restrict__ count0, double* __restrict__ vals,
                                                        double2* __restrict__ sstate, LsdnSeries* __restrict__ tmp, LsdnSeries* __restrict__ list,
                                                        int* __restrict__ coff) {
     __shared__ int s_hist[PSL_NFA_NCLS], s_cur[PSL_NFA_NCLS];
     const int frame = blockIdx.x, tid = threadIdx.x;
-    const int cnt = nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg;
+    const int cnt = PH == PSL_NFA_FIRST ? (nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg) : ucount[frame];
+    const uint16_t* ul = ulist + (size_t)frame * P.maxseg;
     constexpr int TR = PH == PSL_NFA_FIRST ? 1 : 5;
     const double log_nt = T.log_nt;
     const int lcap = P.maxseg * 5;
@@ -568,14 +584,14 @@ __global__ __launch_bounds__(256) void k_lsd_nfa_setup(LineParams P, LsdnTables 
     if (tid < PSL_NFA_NCLS) s_hist[tid] = 0;
     __syncthreads();
     for (int item = tid; item < cnt * TR; item += 256) {
-        const int idx = item / TR, j = item - idx * TR;
-        const size_t o = (size_t)frame * P.maxseg + idx;
+        const int pos = item / TR, j = item - pos * TR;
+        const size_t o = (size_t)frame * P.maxseg + (PH == PSL_NFA_FIRST ? pos : (int)ul[pos]);
         LsdnSeries e = {};
         e.pad = 0xffffu;   // no series
-        if (PH == PSL_NFA_FIRST || keep[o] == 2) {
+        {
             const size_t slot = o * 5 + j;
             double v = 0, term = 0, p_term = 0;
-            const int2 c = counts[slot];
+            const int2 c = PH == PSL_NFA_FIRST ? count0[o] : counts[slot];
             if (c.x < 0) v = -__builtin_inf();
             else {
                 double p = rects[o * PSL_LSD_RECT_F64 + 9];
@@ -736,52 +752,74 @@ __global__ __launch_bounds__(256, PSL_NFA_SERIES_WAVES) void k_lsd_nfa_series(Li
 }
 
 // thread = rectangle: the reference's selection over the trials of the phase, in trial order - `if (v > log_nfa) { log_nfa = v;
-// rec = r; }` - the chosen trial rebuilt by replaying its steps, and the verdict if there is one
+// rec = r; }` - the chosen trial rebuilt by replaying its steps, and the verdict if there is one.  A rectangle that stays undecided
+// is appended to the list of the next phase (ulist_out / ucount_out; one atomic per wave and trip)
 template <int PH>
 __global__ __launch_bounds__(256) void k_lsd_nfa_select(LineParams P, double log_nt, double* __restrict__ rects, const int* __restrict__ nrect,
-                                                        uint8_t* __restrict__ keep, const double* __restrict__ vals, const double2* __restrict__ sstate,
-                                                        float* __restrict__ segtmp) {
-    const int frame = blockIdx.y;
-    const int cnt = nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg;
-    for (int idx = (int)(blockIdx.x * 256 + threadIdx.x); idx < cnt; idx += (int)gridDim.x * 256) {
-        const size_t o = (size_t)frame * P.maxseg + idx;
-        if (PH != PSL_NFA_FIRST && keep[o] != 2) continue;
-        double* rs = rects + o * PSL_LSD_RECT_F64;
-        LsdnRect rec;
-        lsdn_load(rs, &rec);
-        double logn;
-        int best = -1;
-        // nfa() of trial t: the value k_lsd_nfa_setup left, or -log10(binomial tail) - logNT of its series
-        auto value = [&](int t) {
-            const double bt = sstate[o * 5 + t].x;
-            if (bt == __builtin_inf()) return -__builtin_inf();   // a series that ended at its `stop`: the trial cannot be selected
-            return bt != 0 ? PSL_DSUB(-psl_log10(bt), log_nt) : vals[o * 5 + t];
-        };
-        if (PH == PSL_NFA_FIRST) logn = value(0);
-        else {
-            logn = rs[10];
+                                                        const uint16_t* __restrict__ ulist, const int* __restrict__ ucount, uint8_t* __restrict__ keep,
+                                                        const double* __restrict__ vals, const double2* __restrict__ sstate, float* __restrict__ segtmp,
+                                                        uint16_t* __restrict__ ulist_out, int* __restrict__ ucount_out) {
+    const int frame = blockIdx.y, lane = threadIdx.x & 63;
+    const int cnt = PH == PSL_NFA_FIRST ? (nrect[frame] < P.maxseg ? nrect[frame] : P.maxseg) : ucount[frame];
+    const uint16_t* ul = ulist + (size_t)frame * P.maxseg;
+    // the trip count is the workgroup's, so that the waves are whole at the append
+    for (int base = (int)blockIdx.x * 256; base < cnt; base += (int)gridDim.x * 256) {
+        const int item = base + (int)threadIdx.x;
+        int idx = 0;
+        bool undecided = false;
+        if (item < cnt) {
+            idx = PH == PSL_NFA_FIRST ? item : (int)ul[item];
+            const size_t o = (size_t)frame * P.maxseg + idx;
+            double* rs = rects + o * PSL_LSD_RECT_F64;
+            LsdnRect rec;
+            lsdn_load(rs, &rec);
+            double logn;
+            int best = -1;
+            // nfa() of trial t: the value k_lsd_nfa_setup left, or -log10(binomial tail) - logNT of its series
+            auto value = [&](int t) {
+                const double bt = sstate[o * 5 + t].x;
+                if (bt == __builtin_inf()) return -__builtin_inf();   // a series that ended at its `stop`: the trial cannot be selected
+                return bt != 0 ? PSL_DSUB(-psl_log10(bt), log_nt) : vals[o * 5 + t];
+            };
+            if (PH == PSL_NFA_FIRST) logn = value(0);
+            else {
+                logn = rs[10];
 #pragma unroll 1
-            for (int t = 0; t < 5; ++t) {
-                const double vt = value(t);
-                if (vt > logn) { logn = vt; best = t; }
+                for (int t = 0; t < 5; ++t) {
+                    const double vt = value(t);
+                    if (vt > logn) { logn = vt; best = t; }
+                }
+            }
+            if (best >= 0) {
+                if (PH == -1 || PH == 3) {
+                    double pp = rec.p;
+                    for (int t = 0; t <= best; ++t) pp = pp / 2;
+                    rec.p = pp; rec.prec = PSL_DMUL(pp, PSL_PI);
+                    rs[8] = rec.prec; rs[9] = rec.p;
+                } else if (PH >= 0) {
+                    for (int t = 0; t <= best; ++t) lsdn_shrink(rec, PH);
+                    rs[0] = rec.x1; rs[1] = rec.y1; rs[2] = rec.x2; rs[3] = rec.y2; rs[4] = rec.width;
+                }
+            }
+            rs[10] = logn;
+            if (logn > 0) {   // LOG_EPS = 0: accepted, with the rectangle as it stands now
+                keep[o] = 1;
+                psl_lsd_store_segment(P, rec.x1, rec.y1, rec.x2, rec.y2, segtmp + 4 * o);
+            } else {
+                keep[o] = PH == 3 ? 0 : 2;
+                undecided = PH != 3;
             }
         }
-        if (best >= 0) {
-            if (PH == -1 || PH == 3) {
-                double pp = rec.p;
-                for (int t = 0; t <= best; ++t) pp = pp / 2;
-                rec.p = pp; rec.prec = PSL_DMUL(pp, PSL_PI);
-                rs[8] = rec.prec; rs[9] = rec.p;
-            } else if (PH >= 0) {
-                for (int t = 0; t <= best; ++t) lsdn_shrink(rec, PH);
-                rs[0] = rec.x1; rs[1] = rec.y1; rs[2] = rec.x2; rs[3] = rec.y2; rs[4] = rec.width;
+        if (PH != 3) {
+            const unsigned long long m = __ballot(undecided);
+            if (m) {
+                const int first = __ffsll((long long)m) - 1;
+                int at = 0;
+                if (lane == first) at = atomicAdd(&ucount_out[frame], __popcll(m));
+                at = __shfl(at, first);
+                if (undecided) ulist_out[(size_t)frame * P.maxseg + at + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)idx;
             }
         }
-        rs[10] = logn;
-        if (logn > 0) {   // LOG_EPS = 0: accepted, with the rectangle as it stands now
-            keep[o] = 1;
-            psl_lsd_store_segment(P, rec.x1, rec.y1, rec.x2, rec.y2, segtmp + 4 * o);
-        } else keep[o] = PH == 3 ? 0 : 2;
     }
 }
 

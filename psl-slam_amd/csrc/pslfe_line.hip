@@ -72,6 +72,9 @@ struct pslfe_line {
     float* d_segtmp = nullptr;
     uint8_t* d_keep = nullptr;
     int2* d_counts = nullptr;     // (n, k) of the five trial rectangles of a rect_improve phase
+    int2* d_count0 = nullptr;     // (n, k) of the first test, whose pixel pass also counts phase -1's five trials into d_counts
+    uint16_t* d_ulist = nullptr;  // [2][F][maxseg] the undecided rectangles of a frame, as left by the selection of the phase before (read / written alternately)
+    int* d_ucount = nullptr;      // [5][F] their number: after the first test and after phases -1 .. 2
     double* d_vals = nullptr;     // their nfa() values
     double2* d_sstate = nullptr;  // (first term, p / (1 - p)) of the binomial tails that have to be summed
     LsdnSeries* d_slist = nullptr;  // ... as one list per frame, by predicted length (d_stmp: in item order, before the bucketing)
@@ -194,6 +197,9 @@ struct pslfe_line {
         mem.alloc(d_segtmp, (size_t)Q.maxseg * 4 * F, "d_segtmp");
         mem.alloc(d_keep, (size_t)Q.maxseg * F, "d_keep");
         mem.alloc(d_counts, (size_t)Q.maxseg * 5 * F, "d_counts");
+        mem.alloc(d_count0, (size_t)Q.maxseg * F, "d_count0");
+        mem.alloc(d_ulist, (size_t)Q.maxseg * 2 * F, "d_ulist");
+        mem.alloc(d_ucount, 5 * F, "d_ucount");
         mem.alloc(d_vals, (size_t)Q.maxseg * 5 * F, "d_vals");
         mem.alloc(d_sstate, (size_t)Q.maxseg * 5 * F, "d_sstate");
         mem.alloc(d_slist, (size_t)Q.maxseg * 5 * F, "d_slist");
@@ -288,31 +294,44 @@ struct pslfe_line {
             PSL_HIP(hipGetLastError());   // a refused grow launch (e.g. its dynamic LDS) must not hide behind the NFA launches
         }
         if (refine >= 2) {
-            // rect_improve + NFA: per phase a pixel-scan launch (16 lanes = rectangle x trial), two nfa() launches (thread = evaluation:
+            // rect_improve + NFA: per phase a pixel-scan launch (16 lanes = rectangle), two nfa() launches (thread = evaluation:
             // set-up, then the binomial tails drawn from a shared counter) and a selection launch (thread = rectangle), line_kernels3.h.  A few hundred rectangles per frame: a many-frames launch fills
             // the chip by frames, a single frame by chunks.  (The stage timers record the launches of a phase as they are issued;
             // with profiling on, every stage costs two event records.)
+            // List k holds the rectangles still undecided after the first test (k = 0) and after phases -1 .. 2 (k = 1 .. 4): phase PH
+            // walks list PH + 1 and fills list PH + 2.  Phase -1 has no pixel scan of its own: the first test's pass counts its trials.
             const dim3 gc(F >= 64 ? PSL_NFA_COUNT_WGS : 128, F), gs(F >= 64 ? 1 : 4, F);
-#define PSL_NFA_PHASE(PH)                                                                                                \
+            PSL_HIP(hipMemsetAsync(d_ucount, 0, (size_t)5 * F * sizeof(int), st));
+            auto ul = [&](int k) { return k >= 0 ? d_ulist + (size_t)(k & 1) * P.maxseg * F : nullptr; };
+            auto uc = [&](int k) { return k >= 0 && k < 5 ? d_ucount + (size_t)k * F : nullptr; };
+#define PSL_NFA_COUNT(PH)                                                                                                \
     {                                                                                                                    \
         PSL_STAGE_BEGIN(ctx, "line.nfa_count");                                                                          \
-        k_lsd_nfa_count<PH><<<gc, 256, 0, st>>>(P, d_angdeg, d_rects, d_nrect, d_keep, d_counts);                       \
+        k_lsd_nfa_count<PH><<<gc, 256, 0, st>>>(P, d_angdeg, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_counts, d_count0); \
         PSL_STAGE_END(ctx, "line.nfa_count");                                                                            \
-    }                                                                                                                    \
+    }
+#define PSL_NFA_EVAL(PH)                                                                                                 \
     {                                                                                                                    \
         PSL_STAGE_BEGIN(ctx, "line.nfa_eval");                                                                           \
-        k_lsd_nfa_setup<PH><<<F, 256, 0, st>>>(P, NT, d_rects, d_nrect, d_keep, d_counts, d_vals, d_sstate, d_stmp, d_slist, d_lcount); \
+        k_lsd_nfa_setup<PH><<<F, 256, 0, st>>>(P, NT, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_counts, d_count0, d_vals, d_sstate, d_stmp, d_slist, d_lcount); \
         k_lsd_nfa_series<PH><<<dim3(PSL_NFA_NCLS, (F + PSL_NFA_FG - 1) / PSL_NFA_FG), 256, 0, st>>>(P, NT, (int)F, d_slist, d_lcount, d_sstate); \
-        k_lsd_nfa_select<PH><<<gs, 256, 0, st>>>(P, NT.log_nt, d_rects, d_nrect, d_keep, d_vals, d_sstate, d_segtmp);           \
+        k_lsd_nfa_select<PH><<<gs, 256, 0, st>>>(P, NT.log_nt, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_keep, d_vals, d_sstate, d_segtmp, \
+                                                 PH < 3 ? ul(PH + 2) : nullptr, uc(PH + 2));                             \
         PSL_STAGE_END(ctx, "line.nfa_eval");                                                                             \
     }
-            PSL_NFA_PHASE(PSL_NFA_FIRST)
-            PSL_NFA_PHASE(-1)
-            PSL_NFA_PHASE(0)
-            PSL_NFA_PHASE(1)
-            PSL_NFA_PHASE(2)
-            PSL_NFA_PHASE(3)
-#undef PSL_NFA_PHASE
+            PSL_NFA_COUNT(PSL_NFA_FIRST)
+            PSL_NFA_EVAL(PSL_NFA_FIRST)
+            PSL_NFA_EVAL(-1)
+            PSL_NFA_COUNT(0)
+            PSL_NFA_EVAL(0)
+            PSL_NFA_COUNT(1)
+            PSL_NFA_EVAL(1)
+            PSL_NFA_COUNT(2)
+            PSL_NFA_EVAL(2)
+            PSL_NFA_COUNT(3)
+            PSL_NFA_EVAL(3)
+#undef PSL_NFA_COUNT
+#undef PSL_NFA_EVAL
             k_lsd_emit<<<F, 256, 0, st>>>(P, d_nrect, d_segtmp, d_keep, d_seg, d_nseg);
         }
         PSL_HIP(hipGetLastError());
