@@ -840,6 +840,62 @@ typedef struct PslLineFuseQuery {
 int pslfe_kf_line_fuse_best(pslfe_kf* k, const PslKeyLine* kls, int n, const uint8_t* desc, int ndesc,
                             const PslLineFuseQuery* queries, const uint8_t* qdesc, int nq, int32_t* best_idx,
                             int32_t* best_dist);
+/* ---- LSDmatcher::Fuse for K keyframes x M map lines: the line half of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:839-872),
+ * which calls Fuse(pKFi, vpMapLineMatches) once per target keyframe with the same list.  Per (keyframe k, map line i), following
+ * add_src/LSDmatcher.cpp:865-931 with the conventions stated above pslfe_kf_project (affine products, cv::norm and Mat::dot as double
+ * sums, every other step one float operation in the reference's order, never contracted):
+ *   - skip[k*M + i] != 0 (NULL, isBad(), IsInKeyFrame(pKF) :869-873; the map stays with the caller; skip == NULL = none): dropped,
+ *     tested before anything else;
+ *   - sp, ep, normal of PslMapLineGeom rounded to float (:877-878, :919); SPc = Rcw*SP + tcw, EPc likewise;
+ *   - SPc.z < 0.0f || EPc.z < 0.0f: the reference executes `return false` (:890-891) and leaves the WHOLE function.  stop[k] = the
+ *     smallest such i among the lines not skipped, or M when there is none; every row i >= stop[k] of keyframe k is dropped.  The
+ *     host tail applies the rows i < stop[k] and returns 0 (false) when stop[k] < M.  A depth of exactly +0, -0 (the comparison is a
+ *     float compare, not a sign test) or NaN is no stop: it goes on and fails IsInImage;
+ *   - invz = 1.0f/z, u = (fx*X)*invz + cx, v likewise (this product order differs from the point Fuse); KeyFrame::IsInImage
+ *     src/KeyFrame.cc:726-729 (>= min && < max) for the first end point, then for the second;
+ *   - OM = 0.5*(SP+EP) - Ow: a float sum, an exact halving, a float difference, Ow = -Rcw.t()*tcw; dist = cv::norm(OM); dropped when
+ *     dist < 0.8f*min_dist || dist > 1.2f*max_dist; dropped when OM.dot(pn) < 0.5*(double)dist;
+ *   - level = MapLine::PredictScale(dist, log_scale_factor_line) as pslfe_line_project_frustum computes it (unclamped float arithmetic
+ *     on max_dist/dist with the correctly rounded logf).  A level outside [0, nlevels) is where the reference indexes
+ *     mvScaleFactorsLine out of range (undefined behaviour); THE LIBRARY DROPS THE ROW;
+ *   - row k*M + i = {u1, v1, u2, v2, radius = th*scale_factors_line[level], level}; a dropped row is radius = -1 and every other
+ *     field 0.  Rows are NOT compacted: the host tail indexes by map line.  level[k*M + i] (may be NULL) = the unclamped level of every
+ *     row that reached PredictScale, INT32_MIN otherwise.
+ * Negative counts or more than 65535 keyframes: PSLFE_E_INVALID.  Otherwise K == 0 or M == 0: PSLFE_OK, nothing written and no other
+ * argument looked at.  Otherwise nlevels outside 1..16 or a NULL array or handle: PSLFE_E_INVALID, before any device is touched.
+ * Difference from K sequential Fuse calls: keyframe k+1 of the reference sees the IsInKeyFrame / isBad state that the replacements of
+ * keyframe k left (:961-981); here every keyframe sees the state the caller put into `skip`.  A caller that needs that order fills
+ * skip per keyframe and calls with K = 1. */
+int pslfe_kf_line_project(pslfe_kf* k, const PslPose* Tcw, int K, const PslMapLineGeom* ml, const uint8_t* skip, int M,
+                          const PslCamera* cam, float min_x, float min_y, float max_x, float max_y, const float* scale_factors_line,
+                          int nlevels, float log_scale_factor_line, float th, PslLineFuseQuery* queries, int32_t* level, int32_t* stop);
+/* == LSDmatcher::Fuse(pKF, vpMapLines, th) add_src/LSDmatcher.cpp:847-958 up to bestDist for K keyframes against the same M map lines:
+ *    pslfe_kf_line_project, then for keyframe k exactly the search of pslfe_kf_line_fuse_best on rows k*M .. with the keylines
+ *    kls[kl_off[k] .. kl_off[k+1]) and the descriptor rows desc[desc_off[k] .. desc_off[k+1]) (the matrix the reference indexes with the
+ *    line index, :948; a keyline without a row is skipped) and mldesc[i] (M x 32 bytes) as the descriptor of map line i.  One upload,
+ *    one launch chain, one synchronisation whatever K is.  best_idx[k*M + i] = index among keyframe k's own keylines or -1, best_dist =
+ *    256 when none: the caller applies bestDist <= TH_LOW and mutates the map (:961-981) for the rows i < stop[k].  queries (K*M rows,
+ *    may be NULL) = the rows of pslfe_kf_line_project.  Both offset arrays have K+1 ascending entries (PSLFE_E_INVALID otherwise); a
+ *    keyframe with more than 65535 keylines is PSLFE_E_INVALID, the limit of pslfe_kf_line_fuse_best.  The difference from K
+ *    sequential Fuse calls is the one stated above. */
+int pslfe_kf_line_fuse_keyframes(pslfe_kf* k, const PslPose* Tcw, int K, const PslKeyLine* kls, const int32_t* kl_off, const uint8_t* desc,
+                                 const int32_t* desc_off, const PslMapLineGeom* ml, const uint8_t* mldesc, const uint8_t* skip, int M,
+                                 const PslCamera* cam, float min_x, float min_y, float max_x, float max_y,
+                                 const float* scale_factors_line, int nlevels, float log_scale_factor_line, float th, int32_t* best_idx,
+                                 int32_t* best_dist, PslLineFuseQuery* queries, int32_t* stop);
+/* == LSDmatcher::SearchForTriangulation add_src/LSDmatcher.cpp:705-781 of one keyframe against K neighbours (CreateNewMapLines2,
+ *    src/LocalMapping.cc:554-580): the pair-list overload :705-743 is TH = TH_LOW, mutual = 1; the vector<int> overload :745-781 is TH =
+ *    TH_HIGH, mutual = isDouble.  desc1: the n1 LBD rows of KF1; neighbour k: rows desc2[off2[k] .. off2[k+1]) (off2: K+1 ascending
+ *    entries from 0); has_mapline1[i] / has_mapline2[off2[k] + j] != 0 <=> GetMapLine(i) / GetMapLine(j) != NULL (NULL = none).  Per
+ *    neighbour: pslfe_line_frame_bf_match both ways (the reverse way only when mutual), the mutual test, the GetMapLine(i) ||
+ *    GetMapLine(j) filter.  match[k*n1 + i] = line of neighbour k or -1; nmatches[k] = the return value.  n1 == 0 or an empty neighbour:
+ *    0 matches and a row of -1 (:715-716).  All 2K directions run in one launch chain with one synchronisation.
+ *    K == 0: PSLFE_OK, nothing written and no other argument looked at.
+ *    Caveat: CreateNewMapLines2 gives lines of KF1 map lines between two neighbours; has_mapline1 is the state at the call, so the
+ *    caller checks GetMapLine(i) again when it consumes the pairs of neighbour k. */
+int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t* desc1, int n1, const uint8_t* has_mapline1,
+                                                     const uint8_t* desc2, const int32_t* off2, const uint8_t* has_mapline2, int K,
+                                                     float nnratio, float TH, int mutual, int32_t* match, int32_t* nmatches);
 /* == MapPoint::ComputeDistinctiveDescriptors src/MapPoint.cc:242-304 and MapLine::ComputeDistinctiveDescriptors
  *    add_src/MapLine.cpp:250-310 for npts map points / lines at once: the observed descriptors of point p are rows
  *    offsets[p] .. offsets[p+1] of desc (at most 1024 per point); best[p] = the row (relative to offsets[p]) with the

@@ -1319,6 +1319,73 @@ class KeyFrameMatcher:
                                              _ptr(bi), _ptr(bd)), "pslfe_kf_line_fuse_best")
         return bi[:len(q)], bd[:len(q)]
 
+    def line_project(self, poses, ml, cam, bounds, scale_factors_line, log_scale_factor_line, th, skip=None):
+        """pslfe_kf_line_project: the per-line arithmetic of LSDmatcher::Fuse add_src/LSDmatcher.cpp:865-931 for K keyframe poses
+        (POSE_DTYPE[K]) x M map lines (MAPLINE_DTYPE[M]); skip [K, M] bytes or None.
+        -> (rows LINEFUSEQUERY_DTYPE [K, M], level [K, M], stop [K]): rows i >= stop[k] are dropped, the reference returned there."""
+        T = np.ascontiguousarray(poses, POSE_DTYPE).reshape(-1)
+        g = np.ascontiguousarray(ml, MAPLINE_DTYPE).reshape(-1)
+        K, M = len(T), len(g)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors_line, log_scale_factor_line, th)
+        q = np.zeros((K, M), LINEFUSEQUERY_DTYPE)
+        lvl = np.full((K, M), -2**31, np.int32)
+        stop = np.full(K, M, np.int32)
+        _check(lib().pslfe_kf_line_project(self._h, _ptr(T), C.c_int(K), _ptr(g), _ptr(sk), C.c_int(M), *a, *b, _ptr(q), _ptr(lvl), _ptr(stop)),
+               "pslfe_kf_line_project")
+        return q, lvl, stop
+
+    def LineFuseKeyFrames(self, poses, keylines, descs, ml, mldesc, cam, bounds, scale_factors_line, log_scale_factor_line, th, skip=None):
+        """LSDmatcher::Fuse(pKF, vpMapLines, th) add_src/LSDmatcher.cpp:847-958 up to bestDist for K keyframes against the same M map
+        lines, projection included: keylines[k] (KEYLINE_DTYPE) and descs[k] (rows x 32, the matrix the reference indexes with the line
+        index) per keyframe.  -> (bestIdx [K, M], bestDist [K, M], rows [K, M], stop [K]); fused = bestDist <= TH_LOW for the rows
+        i < stop[k], the caller mutates the map and returns 0 for a keyframe with stop[k] < M."""
+        T = np.ascontiguousarray(poses, POSE_DTYPE).reshape(-1)
+        g = np.ascontiguousarray(ml, MAPLINE_DTYPE).reshape(-1)
+        K, M = len(T), len(g)
+        if len(keylines) != K or len(descs) != K:
+            raise PslfeError(f"LineFuseKeyFrames: {len(keylines)} keyline lists and {len(descs)} descriptor matrices for {K} keyframes")
+        kl = [np.ascontiguousarray(x, KEYLINE_DTYPE).reshape(-1) for x in keylines]
+        dd = [np.ascontiguousarray(x, np.uint8).reshape(-1, 32) for x in descs]
+        koff, doff = np.zeros(K + 1, np.int32), np.zeros(K + 1, np.int32)
+        koff[1:], doff[1:] = np.cumsum([len(x) for x in kl]), np.cumsum([len(x) for x in dd])
+        kls = np.concatenate(kl) if K else np.zeros(0, KEYLINE_DTYPE)
+        desc = np.concatenate(dd) if K else np.zeros((0, 32), np.uint8)
+        d = np.ascontiguousarray(mldesc, np.uint8).reshape(M, 32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+        cam, sf, a, b = _proj_args(cam, bounds, scale_factors_line, log_scale_factor_line, th)
+        bi = np.full((K, M), -1, np.int32)
+        bd = np.full((K, M), 256, np.int32)
+        q = np.zeros((K, M), LINEFUSEQUERY_DTYPE)
+        stop = np.full(K, M, np.int32)
+        _check(lib().pslfe_kf_line_fuse_keyframes(self._h, _ptr(T), C.c_int(K), _ptr(kls), _ptr(koff), _ptr(desc), _ptr(doff), _ptr(g), _ptr(d),
+                                                  _ptr(sk), C.c_int(M), *a, *b, _ptr(bi), _ptr(bd), _ptr(q), _ptr(stop)),
+               "pslfe_kf_line_fuse_keyframes")
+        return bi, bd, q, stop
+
+    def LineSearchForTriangulationKeyFrames(self, ldesc1, ldescs2, has_mapline1, has_maplines2, nnratio, TH, mutual=True):
+        """pslfe_kf_line_search_for_triangulation_keyframes (LSDmatcher.SearchForTriangulationKeyFrames is the reference-shaped call)
+        -> (nmatches [K], match [K, n1])."""
+        d1 = np.ascontiguousarray(ldesc1, np.uint8).reshape(-1, 32)
+        K, n1 = len(ldescs2), len(d1)
+        dd = [np.ascontiguousarray(x, np.uint8).reshape(-1, 32) for x in ldescs2]
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in dd])
+        d2 = np.concatenate(dd) if K else np.zeros((0, 32), np.uint8)
+        h1 = None if has_mapline1 is None else np.ascontiguousarray(has_mapline1, np.uint8).reshape(n1)
+        h2 = None
+        if has_maplines2 is not None:
+            h2 = np.concatenate([np.ascontiguousarray(x, np.uint8).reshape(-1) for x in has_maplines2]) if K else np.zeros(0, np.uint8)
+            if len(h2) != off[K]:
+                raise PslfeError(f"SearchForTriangulationKeyFrames: {len(h2)} GetMapLine bytes for {off[K]} neighbour lines")
+        match = np.full((K, n1), -1, np.int32)
+        nm = np.zeros(max(K, 1), np.int32)
+        _check(lib().pslfe_kf_line_search_for_triangulation_keyframes(self._h, _ptr(d1), C.c_int(n1), _ptr(h1), _ptr(d2), _ptr(off), _ptr(h2),
+                                                                      C.c_int(K), C.c_float(nnratio), C.c_float(TH), C.c_int(1 if mutual else 0),
+                                                                      _ptr(match), _ptr(nm)),
+               "pslfe_kf_line_search_for_triangulation_keyframes")
+        return nm[:K], match
+
     def ComputeDistinctiveDescriptors(self, desc, offsets):
         """src/MapPoint.cc:242-304 for many map points / lines at once -> best row per point (relative to its run)."""
         d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
@@ -1362,4 +1429,16 @@ def _lsd_search_for_triangulation(self, ldesc1, ldesc2, has_mapline1, has_maplin
     return n, out
 
 
+def _lsd_search_for_triangulation_keyframes(self, ldesc1, ldescs2, has_mapline1, has_maplines2, TH=None, isDouble=True):
+    """LSDmatcher::SearchForTriangulation add_src/LSDmatcher.cpp:705-781 of one keyframe against the K neighbours of CreateNewMapLines2
+    (src/LocalMapping.cc:554-580) in one call: ldescs2[k] / has_maplines2[k] per neighbour, TH and isDouble as SearchForTriangulation.
+    -> (nmatches [K], vMatchedPairs [K, n1]).  has_mapline1 is the state at the call: a caller that gives KF1's lines map lines between
+    neighbours checks GetMapLine(i) again when it consumes neighbour k's pairs."""
+    if getattr(self, "_kf", None) is None:
+        self._kf = KeyFrameMatcher(self.ctx)
+    return self._kf.LineSearchForTriangulationKeyFrames(ldesc1, ldescs2, has_mapline1, has_maplines2, self.mfNNratio,
+                                                        self.TH_LOW if TH is None else TH, isDouble)
+
+
 LSDmatcher.SearchForTriangulation = _lsd_search_for_triangulation
+LSDmatcher.SearchForTriangulationKeyFrames = _lsd_search_for_triangulation_keyframes

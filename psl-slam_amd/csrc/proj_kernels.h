@@ -1,7 +1,10 @@
-// Shared by pslfe_project.hip, pslfe_project_line.hip and pslfe_kf_project.hip: the cv::Mat pose algebra of the projection conventions (include/pslfe.h,
-// DESIGN.md §3) and the workgroup compaction that keeps emitted rows in input order.  Product code.
+// Shared by pslfe_project.hip, pslfe_project_line.hip, pslfe_kf_project.hip and pslfe_kf_line.hip: the cv::Mat pose algebra of the
+// projection conventions (include/pslfe.h), both PredictScale variants and the workgroup compaction that keeps emitted
+// rows in input order.  Product code.
 #ifndef PSL_PROJ_KERNELS_H
 #define PSL_PROJ_KERNELS_H
+
+#include <limits.h>
 
 #include "pslfe_internal.h"
 #include "psl_device_math.h"
@@ -56,6 +59,20 @@ __device__ __forceinline__ int psl_predict_level(float max_dist, float dist, flo
     double ls = ratio > 0.f ? 1e300 : -1.0;
     if (ratio > 0.f && ratio < __builtin_huge_valf()) ls = __builtin_ceil(PSL_DDIV(psl_log((double)ratio), (double)log_scale_factor));
     return ls > 0.0 ? (ls < (double)nlevels ? (int)ls : nlevels - 1) : 0;
+}
+
+// ceil(logf(ratio) / lsf) of MapLine::PredictScale (add_src/MapLine.cpp:381-390), unclamped; logf = the correctly rounded float log;
+// +inf -> INT_MAX, 0 -> INT_MIN, NaN -> 0
+__device__ __forceinline__ int psl_line_level(float ratio, float lsf) {
+    float lf;
+    if (ratio != ratio) return 0;
+    if (ratio > 0.f && ratio < __builtin_huge_valf()) lf = (float)psl_log((double)ratio);
+    else lf = ratio > 0.f ? __builtin_huge_valf() : -__builtin_huge_valf();
+    const float c = __builtin_ceilf(PSL_FDIV(lf, lsf));
+    if (c != c) return 0;
+    if (c >= 2147483648.f) return INT_MAX;
+    if (c < -2147483648.f) return INT_MIN;
+    return (int)c;
 }
 
 // Exclusive position of this thread's flag among the workgroup's set flags, and the workgroup's count.  All BS threads call it;

@@ -11,6 +11,7 @@
 
 #include "pslfe_internal.h"
 #include "psl_device_math.h"
+#include "kf_line_kernels.h"
 
 // gates of SearchByGeomNApearance after matchNNR (:56-106)
 __global__ __launch_bounds__(256) void k_line_geom_gate(const PslKeyLine* __restrict__ kl_last, int n1, const PslKeyLine* __restrict__ kl_cur, int n2,
@@ -55,33 +56,7 @@ __global__ __launch_bounds__(256) void k_line_geom_gate(const PslKeyLine* __rest
 __global__ __launch_bounds__(256) void k_frame_bf_gate(const int* __restrict__ knn_idx, const int* __restrict__ knn_dist, int n1, float nnratio,
                                                         float TH, float* __restrict__ scratch, int* __restrict__ lineMatches) {
     __shared__ float s_med;
-    float* d12 = scratch;        // [n1]
-    float* dev = scratch + n1;   // [n1]
-    const int tid = threadIdx.x;
-    for (int i = tid; i < n1; i += 256) d12[i] = PSL_FSUB((float)knn_dist[2 * i + 1], (float)knn_dist[2 * i]);
-    __syncthreads();
-    for (int i = tid; i < n1; i += 256) {  // the element of rank n1/2 of the sorted values
-        const float v = d12[i];
-        int r = 0;
-        for (int j = 0; j < n1; ++j) { const float u = d12[j]; r += (u < v) || (u == v && j < i); }
-        if (r == n1 / 2) s_med = v;
-    }
-    __syncthreads();
-    const double med = (double)s_med;
-    for (int i = tid; i < n1; i += 256) dev[i] = __builtin_fabsf((float)PSL_DSUB((double)d12[i], med));
-    __syncthreads();
-    for (int i = tid; i < n1; i += 256) {
-        const float v = dev[i];
-        int r = 0;
-        for (int j = 0; j < n1; ++j) { const float u = dev[j]; r += (u < v) || (u == v && j < i); }
-        if (r == n1 / 2) s_med = v;
-    }
-    __syncthreads();
-    const double nn12_th = PSL_DMUL(PSL_DMUL(1.4826, (double)s_med), 0.5);
-    for (int i = tid; i < n1; i += 256) {
-        const float a = (float)knn_dist[2 * i], b = (float)knn_dist[2 * i + 1];
-        lineMatches[i] = ((double)PSL_FSUB(b, a) > nn12_th && a < TH && a < PSL_FMUL(nnratio, b)) ? knn_idx[2 * i] : -1;
-    }
+    psl_frame_bf_gate(knn_idx, knn_dist, n1, nnratio, TH, scratch, lineMatches, &s_med);
 }
 
 // plane association: sequential by definition (running threshold), tiny -> one thread

@@ -15,6 +15,7 @@
 
 #include "match_kernels.h"
 #include "kf_project.h"
+#include "kf_line_kernels.h"
 
 #define PSL_KF_LEVELS 16
 #define PSL_DISTINCT_MAX 1024  // observations of one map point handled (36 KB of descriptors in LDS)
@@ -217,43 +218,8 @@ __global__ __launch_bounds__(256) void k_line_fuse_best(const PslKeyLine* __rest
                                                          int* __restrict__ best_idx, int* __restrict__ best_dist) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (qi >= nq) return;
-    const PslLineFuseQuery q = Q[qi];
-    if (!(q.radius >= 0)) {
-        if (lane == 0) { best_idx[qi] = -1; best_dist[qi] = 256; }
-        return;
-    }
-    const uint32_t* QD = reinterpret_cast<const uint32_t*>(qdesc + (size_t)qi * 32);
-    uint32_t qd[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) qd[k] = QD[k];
-    float d1x = PSL_FSUB(q.x1, q.x2), d1y = PSL_FSUB(q.y1, q.y2);
-    const float n1 = sqrtf(PSL_FADD(PSL_FMUL(d1x, d1x), PSL_FMUL(d1y, d1y)));
-    d1x = PSL_FDIV(d1x, n1);
-    d1y = PSL_FDIV(d1y, n1);
-    const double mx = PSL_DMUL(0.5, (double)PSL_FADD(q.x1, q.x2)), my = PSL_DMUL(0.5, (double)PSL_FADD(q.y1, q.y2));
-    const float rr = PSL_FMUL(q.radius, q.radius);
-    uint32_t best = PSL_KEY_INF;
-    for (int k = lane; k < n; k += 64) {
-        const PslKeyLine kl = kls[k];
-        const double ddx = PSL_DSUB(mx, (double)kl.pt_x), ddy = PSL_DSUB(my, (double)kl.pt_y);
-        const float distance = (float)PSL_DADD(PSL_DMUL(ddx, ddx), PSL_DMUL(ddy, ddy));
-        if (distance > rr) continue;
-        float d2x = PSL_FSUB(kl.startPointX, kl.endPointX), d2y = PSL_FSUB(kl.startPointY, kl.endPointY);
-        const float n2 = sqrtf(PSL_FADD(PSL_FMUL(d2x, d2x), PSL_FMUL(d2y, d2y)));
-        d2x = PSL_FDIV(d2x, n2);
-        d2y = PSL_FDIV(d2y, n2);
-        const float cs = __builtin_fabsf(PSL_FADD(PSL_FMUL(d1x, d2x), PSL_FMUL(d1y, d2y)));
-        if (cs < 0.998f) continue;
-        if (kl.octave < q.level - 1 || kl.octave > q.level) continue;
-        if (k >= ndesc) continue;
-        const int dist = psl_hamming256(qd, reinterpret_cast<const uint32_t*>(desc) + (size_t)k * 8);
-        best = min(best, ((uint32_t)dist << 16) | (uint32_t)k);
-    }
-    best = psl_wave_min_u32(best);
-    if (lane == 0) {
-        best_idx[qi] = best == PSL_KEY_INF ? -1 : (int)(best & 0xffffu);
-        best_dist[qi] = best == PSL_KEY_INF ? 256 : (int)(best >> 16);
-    }
+    const LineFuseGlobal S = {kls, reinterpret_cast<const uint32_t*>(desc)};
+    psl_line_fuse_row(S, n, ndesc, Q[qi], qdesc + (size_t)qi * 32, lane, best_idx + qi, best_dist + qi);
 }
 
 // ComputeDistinctiveDescriptors: one wave per map point.  Row i of the distance matrix lives in the lanes' registers

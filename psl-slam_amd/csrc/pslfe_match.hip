@@ -21,6 +21,7 @@
 #include "psl_device_math.h"
 
 #include "match_kernels.h"
+#include "kf_line_kernels.h"
 
 // ---------------------------------------------------------------------------------------------
 // block b: frame b of (okps, odesc, ocounts) -> slot slot0 + b
@@ -514,23 +515,7 @@ __global__ __launch_bounds__(256) void k_hamming_knn2(const uint8_t* __restrict_
                                                        int* __restrict__ idx, int* __restrict__ dist) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (qi >= nq) return;
-    uint32_t qd[8];
-    const uint32_t* Q = reinterpret_cast<const uint32_t*>(q) + (size_t)qi * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) qd[k] = Q[k];
-    const uint32_t* T = reinterpret_cast<const uint32_t*>(t);
-    uint32_t k1 = 0xffffffffu, k2 = 0xffffffffu;
-    for (int j = lane; j < nt; j += 64) {
-        const uint32_t key = ((uint32_t)psl_hamming256(qd, T + (size_t)j * 8) << 20) | (uint32_t)j;  // nt < 2^20
-        if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
-    }
-    psl_wave_min2(k1, k2);
-    if (lane == 0) {
-        idx[2 * qi] = k1 == 0xffffffffu ? -1 : (int)(k1 & 0xfffff);
-        dist[2 * qi] = k1 == 0xffffffffu ? 0x7fffffff : (int)(k1 >> 20);
-        idx[2 * qi + 1] = k2 == 0xffffffffu ? -1 : (int)(k2 & 0xfffff);
-        dist[2 * qi + 1] = k2 == 0xffffffffu ? 0x7fffffff : (int)(k2 >> 20);
-    }
+    psl_knn2_row(q + (size_t)qi * 32, t, nt, lane, idx + 2 * qi, dist + 2 * qi);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -30,19 +30,6 @@ struct LineProjParams {
     float minX, minY, maxX, maxY;
 };
 
-// ceil(logf(ratio) / lsf) of MapLine::PredictScale, logf = the correctly rounded float log; +inf -> INT_MAX, 0 -> INT_MIN, NaN -> 0
-__device__ __forceinline__ int psl_line_level(float ratio, float lsf) {
-    float lf;
-    if (ratio != ratio) return 0;
-    if (ratio > 0.f && ratio < __builtin_huge_valf()) lf = (float)psl_log((double)ratio);
-    else lf = ratio > 0.f ? __builtin_huge_valf() : -__builtin_huge_valf();
-    const float c = __builtin_ceilf(PSL_FDIV(lf, lsf));
-    if (c != c) return 0;
-    if (c >= 2147483648.f) return INT_MAX;
-    if (c < -2147483648.f) return INT_MIN;
-    return (int)c;
-}
-
 struct LineView {
     float u1, v1, u2, v2, viewCos;
     int level;

@@ -877,6 +877,63 @@ public:
         check(pslfe_kf_line_fuse_best(h_, kls.data(), (int)kls.size(), desc.data(), (int)desc.size() / 32, q.data(), qdesc.data(), (int)q.size(),
                                       bestIdx.data(), bestDist.data()), "pslfe_kf_line_fuse_best");
     }
+    // pslfe_kf_line_project: rows k*M + i = map line i in the keyframe with pose Tcw[k] (LSDmatcher::Fuse add_src/LSDmatcher.cpp:865-931);
+    // skip: K*M bytes or empty; stop[k] = the line at which the reference returned, or M; level (may be nullptr) unclamped or INT32_MIN
+    void LineProject(const std::vector<PslPose>& Tcw, const std::vector<PslMapLineGeom>& ml, const std::vector<uint8_t>& skip,
+                     const PslCamera& cam, const float bounds[4], const std::vector<float>& scaleFactorsLine, float logScaleFactorLine, float th,
+                     std::vector<PslLineFuseQuery>& rows, std::vector<int32_t>& stop, std::vector<int32_t>* level = nullptr) {
+        const size_t n = Tcw.size() * ml.size();
+        checkSkip(skip, n, "LineProject");
+        rows.assign(n, PslLineFuseQuery{});
+        stop.assign(Tcw.size(), (int32_t)ml.size());
+        if (level) level->assign(n, INT32_MIN);
+        check(pslfe_kf_line_project(h_, Tcw.data(), (int)Tcw.size(), ml.data(), skip.empty() ? nullptr : skip.data(), (int)ml.size(), &cam,
+                                    bounds[0], bounds[1], bounds[2], bounds[3], scaleFactorsLine.data(), (int)scaleFactorsLine.size(),
+                                    logScaleFactorLine, th, rows.data(), level ? level->data() : nullptr, stop.data()), "pslfe_kf_line_project");
+    }
+    // LSDmatcher::Fuse(pKF, vpMapLines, th) up to bestDist for the keyframes Tcw[k] against the same map lines, projection included:
+    // keyframe k owns kls[klOff[k] .. klOff[k+1]) and the descriptor rows desc[descOff[k] .. descOff[k+1]); rows (may be nullptr) and
+    // stop for the host tail, which applies the rows i < stop[k]
+    void LineFuseKeyFrames(const std::vector<PslPose>& Tcw, const std::vector<PslKeyLine>& kls, const std::vector<int32_t>& klOff,
+                           const std::vector<uint8_t>& desc, const std::vector<int32_t>& descOff, const std::vector<PslMapLineGeom>& ml,
+                           const std::vector<uint8_t>& mldesc, const std::vector<uint8_t>& skip, const PslCamera& cam, const float bounds[4],
+                           const std::vector<float>& scaleFactorsLine, float logScaleFactorLine, float th, std::vector<int32_t>& bestIdx,
+                           std::vector<int32_t>& bestDist, std::vector<int32_t>& stop, std::vector<PslLineFuseQuery>* rows = nullptr) {
+        const size_t n = Tcw.size() * ml.size();
+        checkSkip(skip, n, "LineFuseKeyFrames");
+        if (klOff.size() != Tcw.size() + 1 || descOff.size() != Tcw.size() + 1)
+            throw Error(PSLFE_E_INVALID, "LineFuseKeyFrames: the offset arrays need one entry more than there are keyframes");
+        if ((size_t)klOff.back() > kls.size() || (size_t)descOff.back() * 32 > desc.size())
+            throw Error(PSLFE_E_INVALID, "LineFuseKeyFrames: the offsets run past the keylines or descriptors");
+        if (mldesc.size() != ml.size() * 32) throw Error(PSLFE_E_INVALID, "LineFuseKeyFrames: mldesc needs 32 bytes per map line");
+        bestIdx.assign(n, -1); bestDist.assign(n, 256);
+        stop.assign(Tcw.size(), (int32_t)ml.size());
+        if (rows) rows->assign(n, PslLineFuseQuery{});
+        check(pslfe_kf_line_fuse_keyframes(h_, Tcw.data(), (int)Tcw.size(), kls.data(), klOff.data(), desc.data(), descOff.data(), ml.data(),
+                                           mldesc.data(), skip.empty() ? nullptr : skip.data(), (int)ml.size(), &cam, bounds[0], bounds[1],
+                                           bounds[2], bounds[3], scaleFactorsLine.data(), (int)scaleFactorsLine.size(), logScaleFactorLine, th,
+                                           bestIdx.data(), bestDist.data(), rows ? rows->data() : nullptr, stop.data()),
+              "pslfe_kf_line_fuse_keyframes");
+    }
+    // LSDmatcher::SearchForTriangulation of one keyframe against K neighbours (CreateNewMapLines2): neighbour k owns the LBD rows
+    // ldesc2[off2[k] .. off2[k+1]); hasMapLine1 / hasMapLine2 (may be empty = none) one byte per line; TH_LOW + mutual for the pair-list
+    // overload, TH_HIGH + isDouble for the vector<int> one.  match[k*n1 + i] = line of neighbour k or -1, nmatches[k] the return value
+    void LineSearchForTriangulationKeyFrames(const std::vector<uint8_t>& ldesc1, const std::vector<uint8_t>& hasMapLine1,
+                                             const std::vector<uint8_t>& ldesc2, const std::vector<int32_t>& off2,
+                                             const std::vector<uint8_t>& hasMapLine2, float nnratio, float TH, bool mutual,
+                                             std::vector<int32_t>& match, std::vector<int32_t>& nmatches) {
+        if (off2.empty()) throw Error(PSLFE_E_INVALID, "LineSearchForTriangulationKeyFrames: off2 needs K + 1 entries");
+        const size_t K = off2.size() - 1, n1 = ldesc1.size() / 32;
+        if ((size_t)off2.back() * 32 > ldesc2.size() || (!hasMapLine1.empty() && hasMapLine1.size() != n1) ||
+            (!hasMapLine2.empty() && hasMapLine2.size() != (size_t)off2.back()))
+            throw Error(PSLFE_E_INVALID, "LineSearchForTriangulationKeyFrames: descriptor or GetMapLine arrays do not fit the offsets");
+        match.assign(K * n1, -1);
+        nmatches.assign(K, 0);
+        check(pslfe_kf_line_search_for_triangulation_keyframes(h_, ldesc1.data(), (int)n1, hasMapLine1.empty() ? nullptr : hasMapLine1.data(),
+                                                               ldesc2.data(), off2.data(), hasMapLine2.empty() ? nullptr : hasMapLine2.data(),
+                                                               (int)K, nnratio, TH, mutual, match.data(), nmatches.data()),
+              "pslfe_kf_line_search_for_triangulation_keyframes");
+    }
     // offsets: npts + 1 entries; returns the best row of every point relative to its run
     std::vector<int32_t> ComputeDistinctiveDescriptors(const std::vector<uint8_t>& desc, const std::vector<int32_t>& offsets) {
         std::vector<int32_t> best(offsets.empty() ? 0 : offsets.size() - 1, -1);

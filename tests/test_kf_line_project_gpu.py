@@ -1,0 +1,202 @@
+"""GPU parity of the line half of LocalMapping at keyframe rate, through the C ABI: pslfe_kf_line_project rows, levels and stops == the
+numpy restatement of tests/kf_line_project_cases.py byte for byte; pslfe_kf_line_fuse_keyframes == the oracle's Fuse search on the
+restated rows and == pslfe_kf_line_fuse_best fed with those rows; pslfe_kf_line_search_for_triangulation_keyframes == the existing
+per-neighbour composition and == the oracle's FrameBFMatch plus the reference's loop.  Every comparison is exact."""
+import functools
+
+import numpy as np
+import pytest
+
+import kf_line_project_cases as lc
+import kf_project_cases as kc
+import kf_scene as ks
+
+pytestmark = pytest.mark.gpu
+
+TH = 3.0
+VIEWS3 = [0, 11, 23]
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(M):
+    views = kc.views()[VIEWS3]
+    ml, desc = lc.map_lines(M, views, nbehind=2 if M >= 5 else 0)
+    return views, ml, desc
+
+
+def _args():
+    return kc.camera(), lc.BOUNDS, lc.SCALE_LINE, lc.LOG_SCALE, TH
+
+
+@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("M", [1, 5, 257, 600])
+@pytest.mark.parametrize("with_skip", [False, True])
+def test_line_project_equals_restatement(K, M, with_skip):
+    """M = 257 is one line past a 256-thread workgroup; 600 has workgroups in which some waves have no line"""
+    import psl_slam_amd as P
+    views, ml, _ = _scene(M)
+    views = views[:K] if K > 1 else views[1:2]
+    skip = None
+    if with_skip:
+        skip = lc.skip_bytes(K, M)
+        if M >= 5:
+            skip[:, M - 2:] = 0
+            skip[0, M - 2:] = 1                               # keyframe 0 skips the lines behind it: it does not stop
+    cam = kc.camera()
+    want, wlevel, wstop, why = lc.restate_line_project(views, ml, cam, lc.BOUNDS, lc.SCALE_LINE, TH, skip)
+    if M >= 600:
+        assert (why == lc.KEPT).mean() > 0.3
+        if K == 3:
+            assert set(np.unique(why).tolist()) == set(range(len(lc.REASONS))) - (set() if with_skip else {lc.SKIP})
+    if M >= 5:
+        assert wstop.tolist() == [M if (with_skip and k == 0) else M - 2 for k in range(K)]
+    kf = P.KeyFrameMatcher()
+    rows, level, stop = kf.line_project(views["Tcw"], ml, *_args(), skip)
+    assert rows.shape == (K, M)
+    np.testing.assert_array_equal(stop, wstop)
+    np.testing.assert_array_equal(level, wlevel)
+    assert rows.tobytes() == want.tobytes()
+    rows2, level2, stop2 = kf.line_project(views["Tcw"], ml, *_args(), skip)
+    assert rows2.tobytes() == rows.tobytes() and level2.tobytes() == level.tobytes() and stop2.tobytes() == stop.tobytes()
+
+
+def test_line_project_limit_cases():
+    import psl_slam_amd as P
+    poses, ml, names = lc.limit_cases()
+    n = len(ml)
+    cam = kc.limit_camera()
+    kf = P.KeyFrameMatcher()
+    scenarios = {
+        "the line behind the camera is skipped: no stop": (np.arange(n), True),
+        "behind the camera at index 0: everything is dropped": (np.roll(np.arange(n), 1), False),
+        "behind the camera at index M - 1": (np.arange(n), False),
+    }
+    for title, (order, skip_last) in scenarios.items():
+        skip = np.zeros((len(poses), n), np.uint8)
+        if skip_last:
+            skip[:, np.nonzero(order == n - 1)[0][0]] = 1
+        g = ml[order]
+        want, wlevel, wstop, why = lc.restate_line_project(poses, g, cam, lc.BOUNDS, lc.SCALE_LINE, TH, skip)
+        rows, level, stop = kf.line_project(poses, g, cam, lc.BOUNDS, lc.SCALE_LINE, lc.LOG_SCALE, TH, skip)
+        np.testing.assert_array_equal(stop, wstop, err_msg=title)
+        for i, j in enumerate(order):
+            assert rows[0, i].tobytes() == want[0, i].tobytes() and level[0, i] == wlevel[0, i], (title, names[j][0], rows[0, i], want[0, i])
+        assert rows.tobytes() == want.tobytes()
+    assert wstop.tolist() == [n - 1] * len(poses)
+
+
+def test_a_stop_in_one_keyframe_leaves_the_others_untouched():
+    import psl_slam_amd as P
+    M = 600
+    views, ml, _ = _scene(M)
+    skip = np.zeros((3, M), np.uint8)
+    skip[0, M - 2:] = skip[2, M - 2:] = 1                      # only keyframe 1 meets the lines behind the cameras
+    behind = np.zeros((), ml.dtype)
+    behind[()] = ml[M - 1]
+    g = ml.copy()
+    g[300] = behind                                           # ... and meets one early
+    skip[0, 300] = skip[2, 300] = 1
+    cam = kc.camera()
+    want, wlevel, wstop, why = lc.restate_line_project(views, g, cam, lc.BOUNDS, lc.SCALE_LINE, TH, skip)
+    assert wstop.tolist() == [M, 300, M]
+    assert (why[1, 300:] == lc.STOP).all() and (why[0, 301:M - 2] == lc.KEPT).sum() > 50 and (why[2, 301:M - 2] == lc.KEPT).sum() > 50
+    rows, level, stop = P.KeyFrameMatcher().line_project(views["Tcw"], g, *_args(), skip)
+    np.testing.assert_array_equal(stop, wstop)
+    np.testing.assert_array_equal(level, wlevel)
+    assert rows.tobytes() == want.tobytes()
+
+
+def _fuse_scene(ns, short, seed):
+    """K = len(ns) keyframes of ns[k] keylines; keyframe `short` has fewer descriptor rows than keylines; M = 300 map lines, a third of
+    them laid onto keylines of the two largest keyframes, half each"""
+    rng = np.random.default_rng(seed)
+    views = kc.views()[VIEWS3][:len(ns)]
+    cam = kc.camera()
+    kls = [lc.keylines(n, rng) for n in ns]
+    descs = [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in ns]
+    descs[short] = descs[short][:max(ns[short] - 7, 0)]
+    M = 300
+    ml, mld = lc.map_lines(M, views, seed=seed + 1)
+    big = [int(k) for k in np.argsort(ns)[::-1][:2]]
+    for h, k in enumerate(big):
+        take = rng.integers(0, ns[k], 50)
+        onto, ontod = lc.lines_onto(kls[k][take], descs[k][np.minimum(take, len(descs[k]) - 1)], views[k]["Tcw"], cam, rng)
+        ml[3 * h:300:6][:50], mld[3 * h:300:6][:50] = onto, ontod
+    return views, kls, descs, ml, mld, big
+
+
+@pytest.mark.parametrize("ns,short", [((0, 63, 200), 2), ((1, 64, 65), 1), ((512, 513, 40), 1)])
+def test_line_fuse_keyframes(ns, short):
+    """(512, 513, 40): both sides of the number of keylines that is staged in LDS"""
+    import oracle_lib
+    import psl_slam_amd as P
+    views, kls, descs, ml, mld, big = _fuse_scene(ns, short, seed=31 + sum(ns))
+    K, M = len(ns), len(ml)
+    skip = lc.skip_bytes(K, M)
+    skip[:, M - 2:] = 1
+    skip[1, M - 2:] = 0                                        # keyframe 1 stops two lines before the end
+    cam = kc.camera()
+    want, wlevel, wstop, why = lc.restate_line_project(views, ml, cam, lc.BOUNDS, lc.SCALE_LINE, TH, skip)
+    assert wstop.tolist() == [M, M - 2, M]
+    kf = P.KeyFrameMatcher()
+    bi, bd, rows, stop = kf.LineFuseKeyFrames(views["Tcw"], kls, descs, ml, mld, *_args(), skip)
+    np.testing.assert_array_equal(stop, wstop)
+    assert rows.tobytes() == want.tobytes()
+    prow, _, pstop = kf.line_project(views["Tcw"], ml, *_args(), skip)
+    assert rows.tobytes() == prow.tobytes() and (pstop == stop).all()
+    for k in range(K):
+        rbi, rbd = oracle_lib.line_fuse_best(kls[k], descs[k], want[k], mld)
+        np.testing.assert_array_equal(bi[k], rbi, err_msg=f"keyframe {k}")
+        np.testing.assert_array_equal(bd[k], rbd, err_msg=f"keyframe {k}")
+        obi, obd = kf.LineFuse(kls[k], descs[k], want[k], mld)
+        np.testing.assert_array_equal(bi[k], obi)
+        np.testing.assert_array_equal(bd[k], obd)
+        assert (bi[k] < max(len(descs[k]), 1)).all()
+    for k in big:
+        fused = (bd[k] <= kf.TH_LOW) & (bi[k] >= 0)
+        assert fused.sum() >= 15, (k, fused.sum())            # the planted lines really fuse
+    assert (bi[np.array(ns) == 0] == -1).all() and (bd[np.array(ns) == 0] == 256).all()
+
+
+def _tri_scene(n1, seed=41):
+    rng = np.random.default_rng(seed)
+    base = rng.integers(0, 256, (170, 32), dtype=np.uint8)
+    d1 = base[:n1]
+    neigh = [np.zeros((0, 32), np.uint8),
+             np.concatenate([ks.noisy_desc(base[:50], rng, flips=16)[rng.permutation(50)], rng.integers(0, 256, (15, 32), dtype=np.uint8)]),
+             np.concatenate([ks.noisy_desc(base[:150], rng, flips=16)[rng.permutation(150)], rng.integers(0, 256, (20, 32), dtype=np.uint8)])]
+    has1 = (rng.random(n1) < 0.2).astype(np.uint8)
+    has2 = [(rng.random(len(d)) < 0.2).astype(np.uint8) for d in neigh]
+    return d1, neigh, has1, has2
+
+
+@pytest.mark.parametrize("n1", [0, 1, 2, 64, 170])
+@pytest.mark.parametrize("mutual", [True, False])
+@pytest.mark.parametrize("th", ["low", "high"])
+def test_line_search_for_triangulation_keyframes(n1, mutual, th):
+    """neighbours of 0, 65 and 170 lines; n1 = 1 has no second neighbour for the reverse kNN, n1 = 0 returns at once"""
+    import oracle_lib
+    import psl_slam_amd as P
+    d1, neigh, has1, has2 = _tri_scene(n1)
+    lm = P.LSDmatcher(0.95, True)
+    TH_ = lm.TH_LOW if th == "low" else lm.TH_HIGH
+    nm, match = lm.SearchForTriangulationKeyFrames(d1, neigh, has1, has2, TH_, mutual)
+    assert match.shape == (3, n1) and len(nm) == 3
+    for k, d2 in enumerate(neigh):
+        n, pairs = lm.SearchForTriangulation(d1, d2, has1, has2[k], TH_, mutual)          # the per-neighbour composition
+        np.testing.assert_array_equal(match[k], pairs, err_msg=f"neighbour {k}")
+        assert nm[k] == n
+        ref = np.full(n1, -1, np.int32)
+        if n1 and len(d2):
+            m12 = oracle_lib.frame_bf_match(d1, d2, 0.95, TH_)
+            m21 = oracle_lib.frame_bf_match(d2, d1, 0.95, TH_)
+            for i, j in enumerate(m12):
+                if j >= 0 and (not mutual or m21[j] == i) and not has1[i] and not has2[k][j]:
+                    ref[i] = j
+        np.testing.assert_array_equal(match[k], ref, err_msg=f"neighbour {k}")
+        assert nm[k] == (ref >= 0).sum()
+    assert nm[0] == 0
+    if n1 == 170:
+        assert nm[2] > 50 and nm[1] > 10
+    nm0, match0 = lm.SearchForTriangulationKeyFrames(d1, neigh, None, None, TH_, mutual)   # no GetMapLine bytes: nothing filtered
+    assert (nm0 >= nm).all() and ((match0 == match) | (match == -1)).all()
