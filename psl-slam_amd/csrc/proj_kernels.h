@@ -1,6 +1,7 @@
 // Shared by pslfe_project.hip, pslfe_project_line.hip, pslfe_kf_project.hip and pslfe_kf_line.hip: the cv::Mat pose algebra of the
-// projection conventions (include/pslfe.h), both PredictScale variants and the workgroup compaction that keeps emitted
-// rows in input order.  Product code.
+// projection conventions (include/pslfe.h) - the pose products, the camera centre, cv::norm, Mat::dot - both
+// PredictScale variants, the descriptor copy and the workgroup compaction that keeps emitted rows in input order.  Which form of the
+// reference uses which arithmetic on top of these is the table of DESIGN.md §5.0h.  Product code.
 #ifndef PSL_PROJ_KERNELS_H
 #define PSL_PROJ_KERNELS_H
 
@@ -30,10 +31,23 @@ __device__ __forceinline__ float psl_affine_row(float m0, float m1, float m2, fl
     return (float)a;
 }
 
+// The pose products.  y = M*x + t, M row-major: world to camera with a PslPose's (R, t), camera 1 to camera 2 with Sim3's (sR21, t21).
+__device__ __forceinline__ void psl_pose_mul(const float* M, const float* t, float x0, float x1, float x2, float* y) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) y[r] = psl_affine_row(M[3 * r], M[3 * r + 1], M[3 * r + 2], x0, x1, x2, t[r]);
+}
+// y = M^T*x + t: camera to world with (Rcw, Ow) (Frame::UnprojectStereo)
+__device__ __forceinline__ void psl_pose_mul_t(const float* M, const float* t, float x0, float x1, float x2, float* y) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) y[r] = psl_affine_row(M[r], M[3 + r], M[6 + r], x0, x1, x2, t[r]);
+}
+
 // -R^T * t (camera centre twc / mOw of Frame::UpdatePoseMatrices)
 __device__ __forceinline__ void psl_centre(const PslPose& T, float* c) {
+    const float zero[3] = {0.f, 0.f, 0.f};
+    psl_pose_mul_t(T.R, zero, T.t[0], T.t[1], T.t[2], c);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) c[r] = -psl_affine_row(T.R[r], T.R[3 + r], T.R[6 + r], T.t[0], T.t[1], T.t[2], 0.f);
+    for (int r = 0; r < 3; ++r) c[r] = -c[r];
 }
 
 // cv::norm of a float 3-vector: the double sum of squares in index order, sqrt in double, rounded to float
@@ -73,6 +87,14 @@ __device__ __forceinline__ int psl_line_level(float ratio, float lsf) {
     if (c >= 2147483648.f) return INT_MAX;
     if (c < -2147483648.f) return INT_MIN;
     return (int)c;
+}
+
+// one 32-byte descriptor row
+__device__ __forceinline__ void psl_copy_desc(uint8_t* dst, const uint8_t* src) {
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = s[0];
+    d[1] = s[1];
 }
 
 // Exclusive position of this thread's flag among the workgroup's set flags, and the workgroup's count.  All BS threads call it;

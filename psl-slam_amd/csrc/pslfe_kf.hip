@@ -407,8 +407,8 @@ int pslfe_kf_fuse_keyframes(pslfe_kf* k, pslfe_frame* f, int mode, const PslKfVi
                 who, mode);
     const int chi2 = mode == PSLFE_KF_PROJ_FUSE;
     PSL_REQUIRE(!chi2 || inv_level_sigma2, PSLFE_E_INVALID, "%s: the chi2 gates of mode 0 need mvInvLevelSigma2", who);
-    KfProjParams P;
-    if (int rc = psl_kf_proj_params(&P, mode, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who)) return rc;
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, mode, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who)) return rc;
     if (K == 0 || M == 0) return PSLFE_OK;
     PSL_REQUIRE(views && mp && mpdesc && best_idx && best_dist, PSLFE_E_INVALID, "%s: NULL argument", who);
     for (int i = 0; i < K; ++i)
@@ -450,8 +450,8 @@ int pslfe_kf_search_by_sim3_poses(pslfe_kf* k, pslfe_frame* f1, pslfe_frame* f2,
     PSL_REQUIRE(nfound && view12 && view21, PSLFE_E_INVALID, "%s: NULL view or output", who);
     PSL_REQUIRE(n1 >= 0 && n2 >= 0, PSLFE_E_INVALID, "%s: negative count", who);
     PSL_REQUIRE((n1 == 0 || (mp1 && desc1 && match12)) && (n2 == 0 || (mp2 && desc2)), PSLFE_E_INVALID, "%s: NULL argument", who);
-    KfProjParams P;
-    if (int rc = psl_kf_proj_params(&P, PSLFE_KF_PROJ_SIM3, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, PSLFE_KF_PROJ_SIM3, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
         return rc;
     if (int rc = check_view_slot(f2, view12->slot, who)) return rc;   // map points of KF1 are searched in KF2's image
     if (int rc = check_view_slot(f1, view21->slot, who)) return rc;

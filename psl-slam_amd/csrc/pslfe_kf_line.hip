@@ -6,7 +6,8 @@
 //   KeyFrame::GetLinesInArea                                         src/KeyFrame.cc:857-891
 //   LSDmatcher::SearchForTriangulation, both live overloads          add_src/LSDmatcher.cpp:705-781   (one keyframe x K neighbours)
 //   LSDmatcher::FrameBFMatch + lineDescriptorMAD                     add_src/LSDmatcher.cpp:492-516, 660-685
-// Conventions: include/pslfe.h above pslfe_kf_line_project; the helpers are those of proj_kernels.h and kf_line_kernels.h.
+// Conventions: include/pslfe.h above pslfe_kf_line_project; helpers: proj_kernels.h, kf_line_kernels.h; differences from the frame
+// line forms: DESIGN.md §5.0h.
 //
 // Projection: one thread per (keyframe, map line), keyframes on blockIdx.y, rows not compacted (the host tail indexes by map line).
 // A thread reads 80 B of geometry as five 16-byte loads and one skip byte and writes 24 B.  The reference leaves Fuse at the first
@@ -24,6 +25,7 @@
 
 #include "match_kernels.h"
 #include "proj_kernels.h"
+#include "kf_project.h"
 #include "kf_line_kernels.h"
 
 #define PSL_KLP_BS 256
@@ -31,14 +33,6 @@
 #define PSL_KLF_CHUNK 16      // map lines per workgroup of the search: 4 per wave
 
 static_assert(sizeof(PslPose) == 48 && sizeof(PslMapLineGeom) == 80 && sizeof(PslLineFuseQuery) == 24, "keyframe line projection PODs");
-
-struct KfLineProjParams {
-    PslCamera cam;
-    float scale[PSLFE_MAX_LEVELS];
-    int nlevels;
-    float th, log_scale_factor;
-    float minX, minY, maxX, maxY;
-};
 
 struct KfLineProjArgs {
     const PslPose* Tcw;
@@ -51,23 +45,13 @@ struct KfLineProjArgs {
     int32_t* stop;        // [K]
 };
 
-// Ow = -Rcw.t()*tcw of every keyframe (KeyFrame::GetCameraCenter, :858) and stop[k] = M
-__global__ __launch_bounds__(64) void k_kf_line_centres(KfLineProjArgs A, int K) {
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= K) return;
-    float c[3];
-    psl_centre(A.Tcw[k], c);
-    A.ow[3 * k] = c[0]; A.ow[3 * k + 1] = c[1]; A.ow[3 * k + 2] = c[2];
-    A.stop[k] = A.M;
-}
-
 __device__ __forceinline__ void psl_line_fuse_row_store(uint2* q, size_t row, float u1, float v1, float u2, float v2, float radius, int level) {
     q[3 * row] = make_uint2(__float_as_uint(u1), __float_as_uint(v1));
     q[3 * row + 1] = make_uint2(__float_as_uint(u2), __float_as_uint(v2));
     q[3 * row + 2] = make_uint2(__float_as_uint(radius), (uint32_t)level);
 }
 
-__global__ __launch_bounds__(PSL_KLP_BS) void k_kf_line_project(KfLineProjArgs A, KfLineProjParams P) {
+__global__ __launch_bounds__(PSL_KLP_BS) void k_kf_line_project(KfLineProjArgs A, ProjParams P) {
     __shared__ float s_pose[12 + 3 + PSLFE_MAX_LEVELS];
     __shared__ int s_stop;
     const int k = blockIdx.y, tid = threadIdx.x;
@@ -273,20 +257,6 @@ int line_counts(int K, int M, const char* who) {
     return PSLFE_OK;
 }
 
-int line_proj_params(KfLineProjParams* P, const PslCamera* cam, float min_x, float min_y, float max_x, float max_y, const float* scale,
-                     int nlevels, float log_scale_factor, float th, const char* who) {
-    PSL_REQUIRE(cam && scale, PSLFE_E_INVALID, "%s: NULL camera or scale factors", who);
-    PSL_REQUIRE(nlevels >= 1 && nlevels <= PSLFE_MAX_LEVELS, PSLFE_E_INVALID, "%s: nlevels %d (1..%d)", who, nlevels, PSLFE_MAX_LEVELS);
-    memset(P, 0, sizeof(*P));
-    P->cam = *cam;
-    memcpy(P->scale, scale, (size_t)nlevels * sizeof(float));
-    P->nlevels = nlevels;
-    P->th = th;
-    P->log_scale_factor = log_scale_factor;
-    P->minX = min_x; P->minY = min_y; P->maxX = max_x; P->maxY = max_y;
-    return PSLFE_OK;
-}
-
 // K + 1 ascending, non-negative entries
 int check_offsets(const int32_t* off, int K, const char* what, const char* who) {
     PSL_REQUIRE(off, PSLFE_E_INVALID, "%s: NULL %s", who, what);
@@ -296,7 +266,7 @@ int check_offsets(const int32_t* off, int K, const char* what, const char* who) 
 }
 
 // after psl_scratch_begin: uploads poses, map lines and skip, takes the outputs from the arena and launches centres, projection, mask
-int line_project_upload(pslfe_ctx* ctx, const KfLineProjParams& P, const PslPose* Tcw, int K, const PslMapLineGeom* ml, const uint8_t* skip, int M,
+int line_project_upload(pslfe_ctx* ctx, const ProjParams& P, const PslPose* Tcw, int K, const PslMapLineGeom* ml, const uint8_t* skip, int M,
                         bool want_level, KfLineProjArgs* A, const char* who) {
     hipStream_t st = ctx->stream;
     const size_t rows = (size_t)K * M;
@@ -313,7 +283,7 @@ int line_project_upload(pslfe_ctx* ctx, const KfLineProjParams& P, const PslPose
     const dim3 grid((M + PSL_KLP_BS - 1) / PSL_KLP_BS, K);
     {
         PSL_STAGE_BEGIN(ctx, "kf.line_project");
-        k_kf_line_centres<<<(K + 63) / 64, 64, 0, st>>>(*A, K);
+        psl_proj_centres_launch(st, A->Tcw, sizeof(PslPose), K, A->ow, A->stop, M);
         k_kf_line_project<<<grid, PSL_KLP_BS, 0, st>>>(*A, P);
         k_kf_line_mask<<<grid, PSL_KLP_BS, 0, st>>>(*A);
         PSL_STAGE_END(ctx, "kf.line_project");
@@ -332,8 +302,9 @@ int pslfe_kf_line_project(pslfe_kf* k, const PslPose* Tcw, int K, const PslMapLi
     static const char* who = "pslfe_kf_line_project";
     if (int rc = line_counts(K, M, who)) return rc;
     if (K == 0 || M == 0) return PSLFE_OK;
-    KfLineProjParams P;
-    if (int rc = line_proj_params(&P, cam, min_x, min_y, max_x, max_y, scale_factors_line, nlevels, log_scale_factor_line, th, who)) return rc;
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors_line, nlevels, log_scale_factor_line, th, who))
+        return rc;
     PSL_REQUIRE(Tcw && ml && queries && stop, PSLFE_E_INVALID, "%s: NULL poses, map lines or output", who);
     PSL_REQUIRE(k, PSLFE_E_INVALID, "%s: NULL handle", who);
     pslfe_ctx* ctx = k->ctx;
@@ -358,8 +329,9 @@ int pslfe_kf_line_fuse_keyframes(pslfe_kf* k, const PslPose* Tcw, int K, const P
     static const char* who = "pslfe_kf_line_fuse_keyframes";
     if (int rc = line_counts(K, M, who)) return rc;
     if (K == 0 || M == 0) return PSLFE_OK;
-    KfLineProjParams P;
-    if (int rc = line_proj_params(&P, cam, min_x, min_y, max_x, max_y, scale_factors_line, nlevels, log_scale_factor_line, th, who)) return rc;
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors_line, nlevels, log_scale_factor_line, th, who))
+        return rc;
     PSL_REQUIRE(Tcw && ml && mldesc && best_idx && best_dist && stop, PSLFE_E_INVALID, "%s: NULL argument", who);
     if (int rc = check_offsets(kl_off, K, "kl_off", who)) return rc;
     if (int rc = check_offsets(desc_off, K, "desc_off", who)) return rc;

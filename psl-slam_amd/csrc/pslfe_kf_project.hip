@@ -7,11 +7,12 @@
 //   ORBmatcher::SearchBySim3, one direction                         src/ORBmatcher.cc:1148-1189, 1228-1269 (PSLFE_KF_PROJ_SIM3)
 //   KeyFrame::IsInImage                                             src/KeyFrame.cc:726-729
 //   MapPoint::PredictScale(dist, KeyFrame*)                         src/MapPoint.cc:385-400
-// Conventions: include/pslfe.h above PslPose and above PslKfView; the helpers are those of proj_kernels.h.
+// Conventions: include/pslfe.h above PslPose and above PslKfView; helpers: proj_kernels.h; differences from the frame forms: DESIGN.md §5.0h.
 //
 // K keyframes x M map points, one thread per pair (keyframes on blockIdx.y).  Rows are not compacted - the searches index by map
 // point - so there is no scan: a thread reads 32 B of geometry and one skip byte and writes 32 B.  k_kf_centres gives every
 // keyframe its camera centre once; a workgroup stages its keyframe's view and centre in LDS.
+#include <stddef.h>
 #include <string.h>
 
 #include "pslfe_internal.h"
@@ -24,15 +25,22 @@
 #define PSL_KFP_BS 256
 #define PSL_KFP_VIEW_WORDS (sizeof(PslKfView) / 4)
 
-static_assert(sizeof(PslKfView) == 100 && sizeof(PslMapPointGeom) == 32 && sizeof(PslProjQuery) == 32, "keyframe projection PODs");
+static_assert(offsetof(PslKfView, Tcw) == 0 && sizeof(PslKfView) == 100 && sizeof(PslMapPointGeom) == 32 && sizeof(PslProjQuery) == 32, "keyframe projection PODs");
 
-// Ow = -Rcw.t()*tcw of every keyframe (KeyFrame::SetPose src/KeyFrame.cc:132-145; src/ORBmatcher.cc:303, :988 for a decomposed Scw)
-__global__ __launch_bounds__(64) void k_kf_centres(const PslKfView* __restrict__ views, int K, float* __restrict__ ow) {
+// Ow = -Rcw.t()*tcw of every pose (KeyFrame::SetPose src/KeyFrame.cc:132-145; src/ORBmatcher.cc:303, :988 for a decomposed Scw;
+// KeyFrame::GetCameraCenter for the line Fuse, which also starts from stop[k] = M)
+__global__ __launch_bounds__(64) void k_kf_centres(const uint8_t* __restrict__ poses, int stride, int K, float* __restrict__ ow,
+                                                   int32_t* __restrict__ stop, int M) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= K) return;
     float c[3];
-    psl_centre(views[k].Tcw, c);
+    psl_centre(*reinterpret_cast<const PslPose*>(poses + (size_t)k * stride), c);
     ow[3 * k] = c[0]; ow[3 * k + 1] = c[1]; ow[3 * k + 2] = c[2];
+    if (stop) stop[k] = M;
+}
+
+void psl_proj_centres_launch(hipStream_t st, const void* d_poses, int stride, int K, float* d_ow, int32_t* d_stop, int M) {
+    k_kf_centres<<<(K + 63) / 64, 64, 0, st>>>(static_cast<const uint8_t*>(d_poses), stride, K, d_ow, d_stop, M);
 }
 
 struct KfProjArgs {
@@ -46,7 +54,7 @@ struct KfProjArgs {
 };
 
 template <int MODE>
-__global__ __launch_bounds__(PSL_KFP_BS) void k_kf_project(KfProjArgs A, KfProjParams P) {
+__global__ __launch_bounds__(PSL_KFP_BS) void k_kf_project(KfProjArgs A, ProjParams P) {
     __shared__ float s_view[PSL_KFP_VIEW_WORDS + 3];
     const int k = blockIdx.y, tid = threadIdx.x;
     if (tid < (int)PSL_KFP_VIEW_WORDS) s_view[tid] = reinterpret_cast<const float*>(A.views + k)[tid];
@@ -66,15 +74,10 @@ __global__ __launch_bounds__(PSL_KFP_BS) void k_kf_project(KfProjArgs A, KfProjP
     float u = 0.f, v = 0.f, ur = 0.f, radius = -1.0f;
     if (!(A.skip && A.skip[row])) {
         const float4 g0 = A.mp[2 * (size_t)i], g1 = A.mp[2 * (size_t)i + 1];  // x y z nx | ny nz min_dist max_dist
-        float X = psl_affine_row(R[0], R[1], R[2], g0.x, g0.y, g0.z, t[0]);
-        float Y = psl_affine_row(R[3], R[4], R[5], g0.x, g0.y, g0.z, t[1]);
-        float Z = psl_affine_row(R[6], R[7], R[8], g0.x, g0.y, g0.z, t[2]);
-        if (MODE == PSLFE_KF_PROJ_SIM3) {  // p3Dc2 = sR21*p3Dc1 + t21 (:1160)
-            const float x1 = X, y1 = Y, z1 = Z;
-            X = psl_affine_row(R2[0], R2[1], R2[2], x1, y1, z1, t2[0]);
-            Y = psl_affine_row(R2[3], R2[4], R2[5], x1, y1, z1, t2[1]);
-            Z = psl_affine_row(R2[6], R2[7], R2[8], x1, y1, z1, t2[2]);
-        }
+        float Xc[3];
+        psl_pose_mul(R, t, g0.x, g0.y, g0.z, Xc);
+        if (MODE == PSLFE_KF_PROJ_SIM3) psl_pose_mul(R2, t2, Xc[0], Xc[1], Xc[2], Xc);  // p3Dc2 = sR21*p3Dc1 + t21 (:1160)
+        const float X = Xc[0], Y = Xc[1], Z = Xc[2];
         if (Z > 0.f) {
             // `1/p3Dc.at<float>(2)` (:859) is a float division, `1.0/...` (:1019, :1166) a double one rounded to float
             const float invz = MODE == PSLFE_KF_PROJ_FUSE ? PSL_FDIV(1.0f, Z) : (float)PSL_DDIV(1.0, (double)Z);
@@ -110,9 +113,8 @@ __global__ __launch_bounds__(PSL_KFP_BS) void k_kf_project(KfProjArgs A, KfProjP
     if (A.level) A.level[row] = lvl;
 }
 
-int psl_kf_proj_params(KfProjParams* P, int mode, const PslCamera* cam, float min_x, float min_y, float max_x, float max_y,
-                       const float* scale_factors, int nlevels, float log_scale_factor, float th, const char* who) {
-    PSL_REQUIRE(mode >= PSLFE_KF_PROJ_FUSE && mode <= PSLFE_KF_PROJ_SIM3, PSLFE_E_INVALID, "%s: mode %d (0..2)", who, mode);
+int psl_proj_params(ProjParams* P, int mode, const PslCamera* cam, float min_x, float min_y, float max_x, float max_y,
+                    const float* scale_factors, int nlevels, float log_scale_factor, float th, const char* who) {
     PSL_REQUIRE(cam && scale_factors, PSLFE_E_INVALID, "%s: NULL camera or scale factors", who);
     PSL_REQUIRE(nlevels >= 1 && nlevels <= PSLFE_MAX_LEVELS, PSLFE_E_INVALID, "%s: nlevels %d (1..%d)", who, nlevels, PSLFE_MAX_LEVELS);
     memset(P, 0, sizeof(*P));
@@ -126,7 +128,7 @@ int psl_kf_proj_params(KfProjParams* P, int mode, const PslCamera* cam, float mi
     return PSLFE_OK;
 }
 
-int psl_kf_project_launch(pslfe_ctx* ctx, const KfProjParams& P, const PslKfView* d_views, int K, const PslMapPointGeom* d_mp,
+int psl_kf_project_launch(pslfe_ctx* ctx, const ProjParams& P, const PslKfView* d_views, int K, const PslMapPointGeom* d_mp,
                           const uint8_t* d_skip, int M, float* d_ow, PslProjQuery* d_q, int32_t* d_level) {
     hipStream_t st = ctx->stream;
     KfProjArgs A;
@@ -138,7 +140,7 @@ int psl_kf_project_launch(pslfe_ctx* ctx, const KfProjParams& P, const PslKfView
         if (P.mode == PSLFE_KF_PROJ_SIM3) {
             k_kf_project<PSLFE_KF_PROJ_SIM3><<<grid, PSL_KFP_BS, 0, st>>>(A, P);
         } else {
-            k_kf_centres<<<(K + 63) / 64, 64, 0, st>>>(d_views, K, d_ow);
+            psl_proj_centres_launch(st, d_views, sizeof(PslKfView), K, d_ow, nullptr, 0);
             if (P.mode == PSLFE_KF_PROJ_FUSE) k_kf_project<PSLFE_KF_PROJ_FUSE><<<grid, PSL_KFP_BS, 0, st>>>(A, P);
             else k_kf_project<PSLFE_KF_PROJ_SCW><<<grid, PSL_KFP_BS, 0, st>>>(A, P);
         }
@@ -148,7 +150,7 @@ int psl_kf_project_launch(pslfe_ctx* ctx, const KfProjParams& P, const PslKfView
     return PSLFE_OK;
 }
 
-int psl_kf_project_upload(pslfe_ctx* ctx, const KfProjParams& P, const PslKfView* views, int K, const PslMapPointGeom* mp, const uint8_t* skip,
+int psl_kf_project_upload(pslfe_ctx* ctx, const ProjParams& P, const PslKfView* views, int K, const PslMapPointGeom* mp, const uint8_t* skip,
                           int M, bool want_level, KfProjBuffers* B, const char* who) {
     hipStream_t st = ctx->stream;
     const size_t rows = (size_t)K * M;
@@ -171,8 +173,9 @@ int pslfe_kf_project(pslfe_kf* k, int mode, const PslKfView* views, int K, const
     static const char* who = "pslfe_kf_project";
     PSL_REQUIRE(k, PSLFE_E_INVALID, "%s: NULL handle", who);
     PSL_REQUIRE(K >= 0 && M >= 0, PSLFE_E_INVALID, "%s: K = %d, M = %d", who, K, M);
-    KfProjParams P;
-    if (int rc = psl_kf_proj_params(&P, mode, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who)) return rc;
+    PSL_REQUIRE(mode >= PSLFE_KF_PROJ_FUSE && mode <= PSLFE_KF_PROJ_SIM3, PSLFE_E_INVALID, "%s: mode %d (0..2)", who, mode);
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, mode, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who)) return rc;
     if (K == 0 || M == 0) return PSLFE_OK;
     PSL_REQUIRE(views && mp && queries, PSLFE_E_INVALID, "%s: NULL views, map points or output", who);
     pslfe_ctx* ctx = k->ctx;

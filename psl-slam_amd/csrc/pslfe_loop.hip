@@ -297,7 +297,7 @@ int loop_check_slot(pslfe_frame* f, int slot, const char* who) {
 
 // SearchByProjection(pKF, Scw, ...) from :362 on.  The rows are the caller's (`queries`, host) or, with P != NULL, projected here from
 // view / mp / skip (pslfe_kf_project, mode 1) and copied to queries_out when that is not NULL.
-int loop_proj_search(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const KfProjParams* P, const PslKfView* view,
+int loop_proj_search(pslfe_kf* k, pslfe_frame* f, int slot, const PslProjQuery* queries, const ProjParams* P, const PslKfView* view,
                      const PslMapPointGeom* mp, const uint8_t* skip, const uint8_t* qdesc, int nq, const uint8_t* taken, int32_t* match,
                      int32_t* assigned, int* nmatches, PslProjQuery* queries_out, const char* who) {
     *nmatches = 0;
@@ -462,8 +462,8 @@ int pslfe_kf_search_by_projection_sim3_pose(pslfe_kf* k, pslfe_frame* f, const P
     PSL_REQUIRE(k && f, PSLFE_E_INVALID, "%s: NULL handle", who);
     PSL_REQUIRE(view && nmatches && (M == 0 || (mp && mpdesc && match)), PSLFE_E_INVALID, "%s: NULL argument", who);
     PSL_REQUIRE(M >= 0, PSLFE_E_INVALID, "%s: M = %d", who, M);
-    KfProjParams P;
-    if (int rc = psl_kf_proj_params(&P, PSLFE_KF_PROJ_SCW, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
+    ProjParams P;
+    if (int rc = psl_proj_params(&P, PSLFE_KF_PROJ_SCW, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, who))
         return rc;
     PSL_REQUIRE(view->slot >= 0 && view->slot < f->max_frames, PSLFE_E_INVALID, "%s: slot %d outside the store (0..%d)", who, view->slot,
                 f->max_frames - 1);

@@ -6,11 +6,8 @@
 //   Frame::isInFrustum + MapPoint::PredictScale                          src/Frame.cc:927-983, src/MapPoint.cc:402-416
 //   ORBmatcher::SearchByProjection(F,MPs) up to GetFeaturesInArea        src/ORBmatcher.cc:45-70, RadiusByViewingCos :131-137
 //
-// cv::Mat arithmetic is not in the reference tree; the conventions used here (include/pslfe.h):
-//   3x3 * 3x1 (+ 3x1) products: double accumulation in index order, one rounding to float (psl_affine_row);
-//   cv::norm / Mat::dot: double sums in index order, viewCos = dot / dist in double, rounded once;
-//   PredictScale: psl_log (double) of the float ratio / (double)mfLogScaleFactor, ceil, clamped;
-//   z == 0, negative or NaN depth and NaN pixel coordinates: not emitted.
+// cv::Mat arithmetic is not in the reference tree; its conventions are include/pslfe.h and DESIGN.md §3, the helpers proj_kernels.h,
+// and what these frame forms do differently from the keyframe forms is the table of DESIGN.md §5.0h.
 //
 // One workgroup per frame (frames on blockIdx.y): thread t handles points t, t + 1024, ... and the emitted rows are compacted
 // in point order by a workgroup scan, so the matchers' first-come-first-served order is the reference's loop order.
@@ -23,19 +20,11 @@
 
 #include "match_kernels.h"
 #include "proj_kernels.h"
+#include "kf_project.h"
 
 #define PSL_PROJ_BS 1024
 
 namespace {
-
-struct ProjParams {
-    PslCamera cam;
-    float scale[PSLFE_MAX_LEVELS];
-    int nlevels;
-    float th, th_depth, log_scale_factor, view_cos_limit;
-    int mono;
-    float minX, minY, maxX, maxY;
-};
 
 // UpdateLastFrame's selection (src/Tracking.cc:1065-1103): over the keypoints with mvDepth > 0 sorted by (z, i), the loop
 // visits the first L = min(n_valid, max(n_close + 1, 101)) (n_close = #{z <= th_depth}; the break follows the increment).
@@ -197,10 +186,7 @@ __global__ __launch_bounds__(PSL_PROJ_BS) void k_project_last(LastArgs A, ProjPa
         if (emit && q < A.qstride) {
             const size_t r = (size_t)pair * A.qstride + q;
             A.q[r] = row;
-            const uint4* s = reinterpret_cast<const uint4*>(dsrc);
-            uint4* d = reinterpret_cast<uint4*>(A.qdesc + r * 32);
-            d[0] = s[0];
-            d[1] = s[1];
+            psl_copy_desc(A.qdesc + r * 32, dsrc);
             if (A.owner) A.owner[r] = i;
         }
         written += total;
@@ -242,9 +228,9 @@ __global__ __launch_bounds__(PSL_PROJ_BS) void k_project_frustum(FrustumArgs A, 
         float vc = 0.f;
         if (j < n) {
             const PslMapPointGeom G = A.mp[base + j];
-            const float X = psl_affine_row(T.R[0], T.R[1], T.R[2], G.x, G.y, G.z, T.t[0]);
-            const float Y = psl_affine_row(T.R[3], T.R[4], T.R[5], G.x, G.y, G.z, T.t[1]);
-            const float Z = psl_affine_row(T.R[6], T.R[7], T.R[8], G.x, G.y, G.z, T.t[2]);
+            float Xc[3];
+            psl_pose_mul(T.R, T.t, G.x, G.y, G.z, Xc);
+            const float X = Xc[0], Y = Xc[1], Z = Xc[2];
             if (Z > 0.f) {
                 const float invz = PSL_FDIV(1.0f, Z);
                 const float u = PSL_FADD(PSL_FMUL(PSL_FMUL(C.fx, X), invz), C.cx);
@@ -283,29 +269,12 @@ __global__ __launch_bounds__(PSL_PROJ_BS) void k_project_frustum(FrustumArgs A, 
         if (emit && q < A.qstride) {
             const size_t r = (size_t)f * A.qstride + q;
             A.q[r] = row;
-            const uint4* s = reinterpret_cast<const uint4*>(A.mpdesc + (base + j) * 32);
-            uint4* d = reinterpret_cast<uint4*>(A.qdesc + r * 32);
-            d[0] = s[0];
-            d[1] = s[1];
+            psl_copy_desc(A.qdesc + r * 32, A.mpdesc + (base + j) * 32);
             if (A.owner) A.owner[r] = j;
         }
         written += total;
     }
     if (tid == 0) A.nq[f] = written;
-}
-
-int make_params(ProjParams* P, const PslCamera* cam, const float* scale_factors, int nlevels, float th, float min_x, float min_y,
-                float max_x, float max_y, const char* what) {
-    PSL_REQUIRE(cam && scale_factors, PSLFE_E_INVALID, "%s: NULL argument", what);
-    PSL_REQUIRE(nlevels >= 1 && nlevels <= PSLFE_MAX_LEVELS, PSLFE_E_INVALID, "%s: nlevels %d (1..%d)", what, nlevels, PSLFE_MAX_LEVELS);
-    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
-    memset(P, 0, sizeof(*P));
-    P->cam = *cam;
-    memcpy(P->scale, scale_factors, (size_t)nlevels * sizeof(float));
-    P->nlevels = nlevels;
-    P->th = th;
-    P->minX = min_x; P->minY = min_y; P->maxX = max_x; P->maxY = max_y;
-    return PSLFE_OK;
 }
 
 int launch_project_last(pslfe_frame* last, int slot0, int npairs, const PslPose* d_Tlw, const PslPose* d_Tcw, const PslLastPoint* d_points,
@@ -361,10 +330,11 @@ int pslfe_orb_project_last_device(pslfe_frame* last, int last_slot0, int npairs,
                                   int nlevels, float th, float th_depth, int mono, int vo, float min_x, float min_y, float max_x,
                                   float max_y, PslProjQuery* d_queries, uint8_t* d_qdesc, int32_t* d_owner, int32_t* d_nq, int qstride) {
     static const char* what = "pslfe_orb_project_last_device";
-    PSL_REQUIRE(last && d_Tlw && d_Tcw && d_queries && d_qdesc && d_nq, PSLFE_E_INVALID, "%s: NULL argument", what);
+    PSL_REQUIRE(last && d_Tlw && d_Tcw && d_queries && d_qdesc && d_nq && cam && scale_factors, PSLFE_E_INVALID, "%s: NULL argument", what);
     ProjParams P;
-    int rc = make_params(&P, cam, scale_factors, nlevels, th, min_x, min_y, max_x, max_y, what);
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, 0.f, th, what);
     if (rc) return rc;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
     P.th_depth = th_depth; P.mono = mono;
     rc = check_last(last, last_slot0, npairs, vo, th_depth, qstride, what);
     if (rc) return rc;
@@ -377,10 +347,11 @@ int pslfe_orb_project_last(pslfe_frame* last, int slot, const PslPose* Tlw, cons
                            int mono, int vo, float min_x, float min_y, float max_x, float max_y, PslProjQuery* queries, uint8_t* qdesc,
                            int32_t* owner, int* nq, int qcap) {
     static const char* what = "pslfe_orb_project_last";
-    PSL_REQUIRE(last && Tlw && Tcw && nq && qcap >= 0 && (qcap == 0 || (queries && qdesc)), PSLFE_E_INVALID, "%s: NULL argument", what);
+    PSL_REQUIRE(last && Tlw && Tcw && nq && qcap >= 0 && (qcap == 0 || (queries && qdesc)) && cam && scale_factors, PSLFE_E_INVALID, "%s: NULL argument", what);
     ProjParams P;
-    int rc = make_params(&P, cam, scale_factors, nlevels, th, min_x, min_y, max_x, max_y, what);
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, 0.f, th, what);
     if (rc) return rc;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
     P.th_depth = th_depth; P.mono = mono;
     rc = check_last(last, slot, 1, vo, th_depth, last->cap, what);
     if (rc) return rc;
@@ -406,18 +377,7 @@ int pslfe_orb_project_last(pslfe_frame* last, int slot, const PslPose* Tlw, cons
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", what, hipGetErrorString(e));
     rc = launch_project_last(last, slot, 1, dTl, dTc, dp, dd, P, vo, dq, dqd, dow, dnq, (int)K);
     if (rc) return rc;
-    int cnt = 0;
-    PSL_HIP(hipMemcpyAsync(&cnt, dnq, sizeof(int), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    *nq = cnt;
-    PSL_REQUIRE(cnt <= qcap, PSLFE_E_CAPACITY, "%s: %d rows, capacity %d", what, cnt, qcap);
-    if (cnt > 0) {
-        PSL_HIP(hipMemcpyAsync(queries, dq, (size_t)cnt * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipMemcpyAsync(qdesc, dqd, (size_t)cnt * 32, hipMemcpyDeviceToHost, st));
-        if (owner) PSL_HIP(hipMemcpyAsync(owner, dow, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipStreamSynchronize(st));
-    }
-    return PSLFE_OK;
+    return psl_fetch_rows(ctx, dnq, dq, dqd, dow, queries, qdesc, owner, nq, qcap, what, "rows");
 }
 
 int pslfe_orb_project_frustum_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw, const PslMapPointGeom* d_mp, const uint8_t* d_mpdesc,
@@ -429,10 +389,12 @@ int pslfe_orb_project_frustum_device(pslfe_ctx* ctx, int nframes, const PslPose*
     PSL_REQUIRE(ctx && d_Tcw && d_mp && d_mpdesc && d_nmp && d_queries && d_qdesc && d_nq, PSLFE_E_INVALID, "%s: NULL argument", what);
     PSL_REQUIRE(nframes >= 1 && mpstride >= 1 && qstride >= 1, PSLFE_E_INVALID, "%s: nframes %d mpstride %d qstride %d", what, nframes,
                 mpstride, qstride);
+    PSL_REQUIRE(cam && scale_factors, PSLFE_E_INVALID, "%s: NULL argument", what);
     ProjParams P;
-    int rc = make_params(&P, cam, scale_factors, nlevels, th, min_x, min_y, max_x, max_y, what);
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, what);
     if (rc) return rc;
-    P.log_scale_factor = log_scale_factor; P.view_cos_limit = view_cos_limit;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
+    P.view_cos_limit = view_cos_limit;
     PSL_HIP(hipSetDevice(ctx->device));
     return launch_project_frustum(ctx, nframes, d_Tcw, d_mp, d_mpdesc, d_nmp, mpstride, P, d_queries, d_qdesc, d_owner, d_nq, qstride,
                                   d_inview, d_level, d_viewcos);
@@ -443,12 +405,13 @@ int pslfe_orb_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapPo
                               float th, float min_x, float min_y, float max_x, float max_y, PslProjQuery* queries, uint8_t* qdesc,
                               int32_t* owner, int* nq, int qcap, uint8_t* inview, int32_t* level, float* viewcos) {
     static const char* what = "pslfe_orb_project_frustum";
-    PSL_REQUIRE(ctx && Tcw && nq && nmp >= 0 && qcap >= 0 && (nmp == 0 || (mp && mpdesc)) && (qcap == 0 || (queries && qdesc)),
-                PSLFE_E_INVALID, "%s: NULL argument", what);
+    PSL_REQUIRE(ctx && Tcw && nq && nmp >= 0 && qcap >= 0 && (nmp == 0 || (mp && mpdesc)) && (qcap == 0 || (queries && qdesc)) && cam &&
+                scale_factors, PSLFE_E_INVALID, "%s: NULL argument", what);
     ProjParams P;
-    int rc = make_params(&P, cam, scale_factors, nlevels, th, min_x, min_y, max_x, max_y, what);
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, scale_factors, nlevels, log_scale_factor, th, what);
     if (rc) return rc;
-    P.log_scale_factor = log_scale_factor; P.view_cos_limit = view_cos_limit;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
+    P.view_cos_limit = view_cos_limit;
     *nq = 0;
     if (nmp == 0) return PSLFE_OK;
     PSL_HIP(hipSetDevice(ctx->device));
@@ -471,21 +434,10 @@ int pslfe_orb_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapPo
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", what, hipGetErrorString(e));
     rc = launch_project_frustum(ctx, 1, dT, dmp, dmd, dn, nmp, P, dq, dqd, dow, dnq, nmp, div, dlv, dvc);
     if (rc) return rc;
-    int cnt = 0;
-    PSL_HIP(hipMemcpyAsync(&cnt, dnq, sizeof(int), hipMemcpyDeviceToHost, st));
     if (inview) PSL_HIP(hipMemcpyAsync(inview, div, M, hipMemcpyDeviceToHost, st));
     if (level) PSL_HIP(hipMemcpyAsync(level, dlv, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (viewcos) PSL_HIP(hipMemcpyAsync(viewcos, dvc, M * sizeof(float), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    *nq = cnt;
-    PSL_REQUIRE(cnt <= qcap, PSLFE_E_CAPACITY, "%s: %d map points in view, capacity %d", what, cnt, qcap);
-    if (cnt > 0) {
-        PSL_HIP(hipMemcpyAsync(queries, dq, (size_t)cnt * sizeof(PslProjQuery), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipMemcpyAsync(qdesc, dqd, (size_t)cnt * 32, hipMemcpyDeviceToHost, st));
-        if (owner) PSL_HIP(hipMemcpyAsync(owner, dow, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipStreamSynchronize(st));
-    }
-    return PSLFE_OK;
+    return psl_fetch_rows(ctx, dnq, dq, dqd, dow, queries, qdesc, owner, nq, qcap, what, "map points in view");
 }
 
 }  // extern "C"

@@ -5,8 +5,7 @@
 //   LSDmatcher::SearchByProjection(cur,last,th) up to the window search   add_src/LSDmatcher.cpp:112-155
 //   LSDmatcher::SearchByProjection(F,MLs,..,th) up to the window search   add_src/LSDmatcher.cpp:260-289, RadiusByViewingCos :986-992
 //
-// The cv::Mat conventions are those of the point projections (include/pslfe.h) plus OM = 0.5*(SP+EP) - mOw as the
-// float sum of exact halves, then a float subtraction; PredictScale unclamped in float with the correctly rounded logf.
+// The cv::Mat conventions are those of the point projections; the frame column of DESIGN.md §5.0h lists what differs from the line Fuse.
 //
 // One workgroup per frame or pair (blockIdx.y): thread t handles lines t, t + 256, ... and the emitted rows are compacted in line
 // order by a workgroup scan, so the matcher's first-come-first-served order is the reference's loop order.
@@ -19,16 +18,11 @@
 #include "psl_f64math.h"
 
 #include "proj_kernels.h"
+#include "kf_project.h"
 
 #define PSL_LPROJ_BS 256
 
 namespace {
-
-struct LineProjParams {
-    PslCamera cam;
-    float th, log_scale_factor, view_cos_limit;
-    float minX, minY, maxX, maxY;
-};
 
 struct LineView {
     float u1, v1, u2, v2, viewCos;
@@ -37,16 +31,14 @@ struct LineView {
 
 // Frame::isInFrustum(pML, limit) src/Frame.cc:828-904 against pose T with camera centre Ow.
 __device__ bool psl_line_in_frustum(const double* sp, const double* ep, const double* nrm, float min_dist, float max_dist, const PslPose& T,
-                                    const float* Ow, const LineProjParams& P, float limit, LineView* out) {
+                                    const float* Ow, const ProjParams& P, float limit, LineView* out) {
     const PslCamera& C = P.cam;
     const float SP[3] = {(float)sp[0], (float)sp[1], (float)sp[2]};
     const float EP[3] = {(float)ep[0], (float)ep[1], (float)ep[2]};
-    const float SPcX = psl_affine_row(T.R[0], T.R[1], T.R[2], SP[0], SP[1], SP[2], T.t[0]);
-    const float SPcY = psl_affine_row(T.R[3], T.R[4], T.R[5], SP[0], SP[1], SP[2], T.t[1]);
-    const float SPcZ = psl_affine_row(T.R[6], T.R[7], T.R[8], SP[0], SP[1], SP[2], T.t[2]);
-    const float EPcX = psl_affine_row(T.R[0], T.R[1], T.R[2], EP[0], EP[1], EP[2], T.t[0]);
-    const float EPcY = psl_affine_row(T.R[3], T.R[4], T.R[5], EP[0], EP[1], EP[2], T.t[1]);
-    const float EPcZ = psl_affine_row(T.R[6], T.R[7], T.R[8], EP[0], EP[1], EP[2], T.t[2]);
+    float SPc[3], EPc[3];
+    psl_pose_mul(T.R, T.t, SP[0], SP[1], SP[2], SPc);
+    psl_pose_mul(T.R, T.t, EP[0], EP[1], EP[2], EPc);
+    const float SPcX = SPc[0], SPcY = SPc[1], SPcZ = SPc[2], EPcX = EPc[0], EPcY = EPc[1], EPcZ = EPc[2];
     if (SPcZ < 0.0f || EPcZ < 0.0f) return false;
     if (!(SPcZ > 0.0f) || !(EPcZ > 0.0f)) return false;  // z == 0 or NaN: stated outcome, not in view
     const float invz1 = PSL_FDIV(1.0f, SPcZ);
@@ -63,28 +55,15 @@ __device__ bool psl_line_in_frustum(const double* sp, const double* ep, const do
     float OM[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) OM[k] = PSL_FSUB(PSL_FADD(PSL_FMUL(0.5f, SP[k]), PSL_FMUL(0.5f, EP[k])), Ow[k]);
-    double s = PSL_DMUL((double)OM[0], (double)OM[0]);
-    s = PSL_DADD(s, PSL_DMUL((double)OM[1], (double)OM[1]));
-    s = PSL_DADD(s, PSL_DMUL((double)OM[2], (double)OM[2]));
-    const float dist = (float)PSL_DSQRT(s);
+    const float dist = psl_norm3(OM[0], OM[1], OM[2]);
     if (!(dist >= minD && dist <= maxD)) return false;
-    const float pn[3] = {(float)nrm[0], (float)nrm[1], (float)nrm[2]};
-    double dot = PSL_DMUL((double)OM[0], (double)pn[0]);
-    dot = PSL_DADD(dot, PSL_DMUL((double)OM[1], (double)pn[1]));
-    dot = PSL_DADD(dot, PSL_DMUL((double)OM[2], (double)pn[2]));
+    const double dot = psl_dot3(OM[0], OM[1], OM[2], (float)nrm[0], (float)nrm[1], (float)nrm[2]);
     const float viewCos = (float)PSL_DDIV(dot, (double)dist);
     if (!(viewCos >= limit)) return false;
     out->u1 = u1; out->v1 = v1; out->u2 = u2; out->v2 = v2;
     out->viewCos = viewCos;
     out->level = psl_line_level(PSL_FDIV(max_dist, dist), P.log_scale_factor);
     return true;
-}
-
-__device__ __forceinline__ void psl_copy_desc(uint8_t* dst, const uint8_t* src) {
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    d[0] = s[0];
-    d[1] = s[1];
 }
 
 struct LineFrustumArgs {
@@ -103,7 +82,7 @@ struct LineFrustumArgs {
     float* viewcos;
 };
 
-__global__ __launch_bounds__(PSL_LPROJ_BS) void k_line_project_frustum(LineFrustumArgs A, LineProjParams P) {
+__global__ __launch_bounds__(PSL_LPROJ_BS) void k_line_project_frustum(LineFrustumArgs A, ProjParams P) {
     __shared__ int s_wave[PSL_LPROJ_BS / 64];
     const int f = blockIdx.y, tid = threadIdx.x;
     const size_t base = (size_t)f * A.mlstride;
@@ -162,7 +141,7 @@ struct LineLastArgs {
     int qstride;
 };
 
-__global__ __launch_bounds__(PSL_LPROJ_BS) void k_line_project_last(LineLastArgs A, LineProjParams P) {
+__global__ __launch_bounds__(PSL_LPROJ_BS) void k_line_project_last(LineLastArgs A, ProjParams P) {
     __shared__ int s_wave[PSL_LPROJ_BS / 64];
     const int p = blockIdx.y, tid = threadIdx.x;
     const size_t base = (size_t)p * A.kl_stride;
@@ -205,17 +184,9 @@ __global__ __launch_bounds__(PSL_LPROJ_BS) void k_line_project_last(LineLastArgs
     if (tid == 0) A.nq[p] = written;
 }
 
-int make_line_params(LineProjParams* P, const PslCamera* cam, float th, float min_x, float min_y, float max_x, float max_y, const char* what) {
-    PSL_REQUIRE(cam, PSLFE_E_INVALID, "%s: NULL argument", what);
-    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
-    memset(P, 0, sizeof(*P));
-    P->cam = *cam;
-    P->th = th;
-    P->minX = min_x; P->minY = min_y; P->maxX = max_x; P->maxY = max_y;
-    return PSLFE_OK;
-}
+const float kNoScale[1] = {1.0f};   // the frame line forms read no scale table: one level of 1 for the builder
 
-int launch_line_frustum(pslfe_ctx* ctx, int nframes, const LineFrustumArgs& A, const LineProjParams& P) {
+int launch_line_frustum(pslfe_ctx* ctx, int nframes, const LineFrustumArgs& A, const ProjParams& P) {
     {
         PSL_STAGE_BEGIN(ctx, "line.project_frustum");
         k_line_project_frustum<<<dim3(1, nframes), PSL_LPROJ_BS, 0, ctx->stream>>>(A, P);
@@ -225,31 +196,13 @@ int launch_line_frustum(pslfe_ctx* ctx, int nframes, const LineFrustumArgs& A, c
     return PSLFE_OK;
 }
 
-int launch_line_last(pslfe_ctx* ctx, int npairs, const LineLastArgs& A, const LineProjParams& P) {
+int launch_line_last(pslfe_ctx* ctx, int npairs, const LineLastArgs& A, const ProjParams& P) {
     {
         PSL_STAGE_BEGIN(ctx, "line.project_last");
         k_line_project_last<<<dim3(1, npairs), PSL_LPROJ_BS, 0, ctx->stream>>>(A, P);
         PSL_STAGE_END(ctx, "line.project_last");
     }
     PSL_HIP(hipGetLastError());
-    return PSLFE_OK;
-}
-
-// rows of a host-form call: count, then (when it fits) the rows, descriptors and owners
-int fetch_rows(pslfe_ctx* ctx, const int32_t* dnq, const PslLineQuery* dq, const uint8_t* dqd, const int32_t* dow, PslLineQuery* queries,
-               uint8_t* qdesc, int32_t* owner, int* nq, int qcap, const char* what) {
-    hipStream_t st = ctx->stream;
-    int cnt = 0;
-    PSL_HIP(hipMemcpyAsync(&cnt, dnq, sizeof(int), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    *nq = cnt;
-    PSL_REQUIRE(cnt <= qcap, PSLFE_E_CAPACITY, "%s: %d lines in view, capacity %d", what, cnt, qcap);
-    if (cnt > 0) {
-        PSL_HIP(hipMemcpyAsync(queries, dq, (size_t)cnt * sizeof(PslLineQuery), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipMemcpyAsync(qdesc, dqd, (size_t)cnt * 32, hipMemcpyDeviceToHost, st));
-        if (owner) PSL_HIP(hipMemcpyAsync(owner, dow, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        PSL_HIP(hipStreamSynchronize(st));
-    }
     return PSLFE_OK;
 }
 
@@ -265,10 +218,12 @@ int pslfe_line_project_frustum_device(pslfe_ctx* ctx, int nframes, const PslPose
     PSL_REQUIRE(ctx && d_Tcw && d_ml && d_mldesc && d_nml && d_queries && d_qdesc && d_nq, PSLFE_E_INVALID, "%s: NULL argument", what);
     PSL_REQUIRE(nframes >= 1 && mlstride >= 1 && qstride >= 1, PSLFE_E_INVALID, "%s: nframes %d mlstride %d qstride %d", what, nframes,
                 mlstride, qstride);
-    LineProjParams P;
-    int rc = make_line_params(&P, cam, th, min_x, min_y, max_x, max_y, what);
+    PSL_REQUIRE(cam, PSLFE_E_INVALID, "%s: NULL argument", what);
+    ProjParams P;
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, kNoScale, 1, log_scale_factor, th, what);
     if (rc) return rc;
-    P.log_scale_factor = log_scale_factor; P.view_cos_limit = view_cos_limit;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
+    P.view_cos_limit = view_cos_limit;
     LineFrustumArgs A = {d_Tcw, d_ml, d_mldesc, d_nml, mlstride, d_queries, d_qdesc, d_owner, d_nq, qstride, d_inview, d_level, d_viewcos};
     PSL_HIP(hipSetDevice(ctx->device));
     return launch_line_frustum(ctx, nframes, A, P);
@@ -279,12 +234,13 @@ int pslfe_line_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapL
                                PslLineQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap, uint8_t* inview, int32_t* level,
                                float* viewcos) {
     static const char* what = "pslfe_line_project_frustum";
-    PSL_REQUIRE(ctx && Tcw && nq && nml >= 0 && qcap >= 0 && (nml == 0 || (ml && mldesc)) && (qcap == 0 || (queries && qdesc)),
+    PSL_REQUIRE(ctx && Tcw && nq && nml >= 0 && qcap >= 0 && (nml == 0 || (ml && mldesc)) && (qcap == 0 || (queries && qdesc)) && cam,
                 PSLFE_E_INVALID, "%s: NULL argument", what);
-    LineProjParams P;
-    int rc = make_line_params(&P, cam, th, min_x, min_y, max_x, max_y, what);
+    ProjParams P;
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, kNoScale, 1, log_scale_factor, th, what);
     if (rc) return rc;
-    P.log_scale_factor = log_scale_factor; P.view_cos_limit = view_cos_limit;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
+    P.view_cos_limit = view_cos_limit;
     *nq = 0;
     if (nml == 0) return PSLFE_OK;
     PSL_HIP(hipSetDevice(ctx->device));
@@ -313,7 +269,7 @@ int pslfe_line_project_frustum(pslfe_ctx* ctx, const PslPose* Tcw, const PslMapL
     if (inview) PSL_HIP(hipMemcpyAsync(inview, A.inview, M, hipMemcpyDeviceToHost, st));
     if (level) PSL_HIP(hipMemcpyAsync(level, A.level, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (viewcos) PSL_HIP(hipMemcpyAsync(viewcos, A.viewcos, M * sizeof(float), hipMemcpyDeviceToHost, st));
-    return fetch_rows(ctx, A.nq, A.q, A.qdesc, A.owner, queries, qdesc, owner, nq, qcap, what);
+    return psl_fetch_rows(ctx, A.nq, A.q, A.qdesc, A.owner, queries, qdesc, owner, nq, qcap, what, "lines in view");
 }
 
 int pslfe_line_project_last_device(pslfe_ctx* ctx, int npairs, const PslKeyLine* d_kls_last, const uint8_t* d_ldesc_last,
@@ -325,9 +281,11 @@ int pslfe_line_project_last_device(pslfe_ctx* ctx, int npairs, const PslKeyLine*
                 "%s: NULL argument", what);
     PSL_REQUIRE(npairs >= 1 && kl_stride >= 1 && qstride >= 1, PSLFE_E_INVALID, "%s: npairs %d kl_stride %d qstride %d", what, npairs,
                 kl_stride, qstride);
-    LineProjParams P;
-    int rc = make_line_params(&P, cam, th, min_x, min_y, max_x, max_y, what);
+    PSL_REQUIRE(cam, PSLFE_E_INVALID, "%s: NULL argument", what);
+    ProjParams P;
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, kNoScale, 1, 0.f, th, what);
     if (rc) return rc;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
     LineLastArgs A = {d_kls_last, d_ldesc_last, d_nkl_last, kl_stride, d_lines, d_mldesc, d_Tcw, d_queries, d_qdesc, d_owner, d_nq, qstride};
     PSL_HIP(hipSetDevice(ctx->device));
     return launch_line_last(ctx, npairs, A, P);
@@ -337,11 +295,12 @@ int pslfe_line_project_last(pslfe_ctx* ctx, const PslKeyLine* kls_last, const ui
                             const uint8_t* mldesc, const PslPose* Tcw, const PslCamera* cam, float th, float min_x, float min_y, float max_x,
                             float max_y, PslLineQuery* queries, uint8_t* qdesc, int32_t* owner, int* nq, int qcap) {
     static const char* what = "pslfe_line_project_last";
-    PSL_REQUIRE(ctx && Tcw && nq && n >= 0 && qcap >= 0 && (n == 0 || (kls_last && ldesc_last && lines)) && (qcap == 0 || (queries && qdesc)),
-                PSLFE_E_INVALID, "%s: NULL argument", what);
-    LineProjParams P;
-    int rc = make_line_params(&P, cam, th, min_x, min_y, max_x, max_y, what);
+    PSL_REQUIRE(ctx && Tcw && nq && n >= 0 && qcap >= 0 && (n == 0 || (kls_last && ldesc_last && lines)) && (qcap == 0 || (queries && qdesc)) &&
+                cam, PSLFE_E_INVALID, "%s: NULL argument", what);
+    ProjParams P;
+    int rc = psl_proj_params(&P, PSL_PROJ_NO_MODE, cam, min_x, min_y, max_x, max_y, kNoScale, 1, 0.f, th, what);
     if (rc) return rc;
+    PSL_REQUIRE(max_x > min_x && max_y > min_y, PSLFE_E_INVALID, "%s: empty image bounds", what);
     *nq = 0;
     if (n == 0) return PSLFE_OK;
     PSL_HIP(hipSetDevice(ctx->device));
@@ -366,7 +325,7 @@ int pslfe_line_project_last(pslfe_ctx* ctx, const PslKeyLine* kls_last, const ui
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", what, hipGetErrorString(e));
     rc = launch_line_last(ctx, 1, A, P);
     if (rc) return rc;
-    return fetch_rows(ctx, A.nq, A.q, A.qdesc, A.owner, queries, qdesc, owner, nq, qcap, what);
+    return psl_fetch_rows(ctx, A.nq, A.q, A.qdesc, A.owner, queries, qdesc, owner, nq, qcap, what, "lines in view");
 }
 
 }  // extern "C"

@@ -60,9 +60,18 @@ def test_line_project_equals_restatement(K, M, with_skip):
     assert rows2.tobytes() == rows.tobytes() and level2.tobytes() == level.tobytes() and stop2.tobytes() == stop.tobytes()
 
 
+def _limit_cases():
+    """lc.limit_cases() plus, in front of the line behind the camera, a line on the optical axis at 2.5e38: SP + EP is +inf in float,
+    so dist is inf, the ratio 0 and the level the sentinel (0.5f*SP + 0.5f*EP, the frame projections' form, stays finite and keeps it)"""
+    poses, ml, names = lc.limit_cases()
+    far = np.zeros(1, ml.dtype)
+    far[0] = ((0.0, 0.0, 2.5e38), (0.0, 0.0, 2.5e38), (0.0, 0.0, 1.0), 1.0, 3e38)
+    return poses, np.concatenate([ml[:-1], far, ml[-1:]]), names[:-1] + [("SP + EP overflows: dropped", lc.LEVEL, None)] + names[-1:]
+
+
 def test_line_project_limit_cases():
     import psl_slam_amd as P
-    poses, ml, names = lc.limit_cases()
+    poses, ml, names = _limit_cases()
     n = len(ml)
     cam = kc.limit_camera()
     kf = P.KeyFrameMatcher()
@@ -77,6 +86,9 @@ def test_line_project_limit_cases():
             skip[:, np.nonzero(order == n - 1)[0][0]] = 1
         g = ml[order]
         want, wlevel, wstop, why = lc.restate_line_project(poses, g, cam, lc.BOUNDS, lc.SCALE_LINE, TH, skip)
+        if order[0] == 0:                                     # nothing stops in front of the overflowing line
+            i = np.nonzero(order == n - 2)[0][0]
+            assert (why[:, i] == lc.LEVEL).all() and (wlevel[:, i] == lc.INT32_MIN).all() and (want["radius"][:, i] == -1.0).all()
         rows, level, stop = kf.line_project(poses, g, cam, lc.BOUNDS, lc.SCALE_LINE, lc.LOG_SCALE, TH, skip)
         np.testing.assert_array_equal(stop, wstop, err_msg=title)
         for i, j in enumerate(order):

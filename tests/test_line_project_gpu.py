@@ -130,6 +130,8 @@ def adversarial_lines(T, cam, lsf):
     add([-0.1, 0.0, 2.0], [0.1, 0.0, 2.0], mn=0.0, mx=1e30)
     add([-0.1, 0.0, 2.0], [0.1, 0.0, 2.0], mn=0.0, mx=0.0)                  # ratio 0
     add(Twc[:3, 3], Twc[:3, 3], mn=0.0, mx=3.0, nrm=[0.0, 0.0, 1.0], cam_coords=False)   # both endpoints at the camera centre
+    # on the optical axis at 2.5e38: 0.5f*SP + 0.5f*EP stays finite (in view, a finite level), SP + EP would be +inf
+    add([0, 0, 2.5e38], [0, 0, 2.5e38], mn=1.0, mx=3e38, nrm=Twc[:3, :3] @ np.array([0.0, 0.0, 1.0]))
     G = np.stack(out)
     G[1]["state"], G[2]["state"], G[3]["state"] = 1, 9, 2   # state and outlier bits
     return G
@@ -197,8 +199,9 @@ def test_line_projections_equal_restatement(batches, style, th):
         Tcw = T4(rot(*rng.normal(0, 0.01, 3)), rng.normal(0, 0.02, 3)) @ Tlw
         L = world_lines(rng, l3, np.linalg.inv(Tlw))
         A = adversarial_lines(Tcw, cam, LSF)
-        G = np.concatenate([L, A])
+        G = np.concatenate([L, A[:-1]])
         G = G[rng.permutation(len(G))] if p % 2 else G
+        G = np.concatenate([G, A[-1:]])   # the overflow line after the permutation: the draws stay those the scene checks below were written on
         n = min(len(G), stride)
         Gs[p, :n] = G[:n][list(P.MAPLINE_DTYPE.names)].astype(P.MAPLINE_DTYPE)
         nml[p] = n
@@ -232,6 +235,7 @@ def test_line_projections_equal_restatement(batches, style, th):
                 assert hq.tobytes() == rq.tobytes() and (hqd == rqd).all() and (how == row).all()
                 assert (hiv == riv).all() and (hlv == rlv).all() and hvc.tobytes() == rvc.tobytes()
                 assert len(rq) > 10 and len(set(rlv[riv == 1].tolist())) >= 3
+                assert riv[-1] == 1 and rlv[-1] >= 0   # the overflow line, last of every pair: in view under 0.5f*SP + 0.5f*EP
         assert qstride == stride or small > 0
     # the adversarial lines: levels outside [0, 8) and the infinite ratio occur
     _, _, _, riv, rlv, _ = restated_frustum(Ts[0], Gs[0, :nml[0]], Gd[0, :nml[0]], cam, 0.5, th)
