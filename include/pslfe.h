@@ -677,6 +677,58 @@ int pslfe_compute_bow_device(pslfe_vocab* v, const uint8_t* d_desc, const int32_
                              double* d_bow_val, int32_t* d_bow_start, int32_t* d_nbow, int32_t* d_fv_node,
                              int32_t* d_fv_start, int32_t* d_fv_idx, int32_t* d_nfv);
 
+/* ---- KeyFrameDatabase: BoW scores and the candidate queries of loop closing and relocalisation ------------------ */
+/* The step between Frame::ComputeBoW and the searches that follow a candidate list.  The reference keeps an inverted file
+ * (word -> list of keyframes, src/KeyFrameDatabase.cc:33-73) and scores what a walk over the query's words reaches; here the
+ * BowVectors are resident in HBM, one row of at most max_words ascending (word id, f64 value) pairs per slot (a slot is the
+ * caller's name for a keyframe, 0 .. max_keyframes-1), and a query visits every live row.  Per slot it gives what the walk of
+ * DetectLoopCandidates :86-104 / DetectRelocalizationCandidates :207-222 leaves behind:
+ *   words       the number of word ids common to the query and the row (mnLoopWords / mnRelocWords); 0 for a slot that is
+ *               dead, excluded or shares no word;
+ *   first_word  the smallest common word id, or -1: lKFsSharingWords holds the slots with words > 0 in ascending
+ *               (first_word, order of their add) - the order in which the walk meets them;
+ *   score       mpVoc->score(query, row) == DBoW2::L1Scoring::score Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68 as f64, the
+ *               same additions in the same order (bit-identical); 0.0 where words == 0.  The reference scores only the keyframes
+ *               with words > minCommonWords (:129, :246); the others' scores are there to be ignored;
+ *   max_common  the maximum of words (maxCommonWords :113-118, :228-233).
+ * The covisibility tails (:141-196, :255-308) walk the caller's map graph and stay with the caller; the mirrors
+ * (KeyFrameDatabase in psl-slam_amd/host/pslfe.hpp and the Python package) hold them as written.  Everything is allocated by
+ * pslfe_kfdb_create.  All calls on one handle come from one thread at a time and run on the context's stream. */
+typedef struct pslfe_kfdb pslfe_kfdb;
+/* max_keyframes 1 .. 2^24 slots of max_words 1 .. 4096 (the longest BowVector pslfe_compute_bow writes) entries: 12 bytes each */
+int pslfe_kfdb_create(pslfe_ctx* ctx, int max_keyframes, int max_words, pslfe_kfdb** out);
+void pslfe_kfdb_destroy(pslfe_kfdb* db);
+/* == KeyFrameDatabase::add src/KeyFrameDatabase.cc:40-46 of the keyframe in `slot` with mBowVec = n ascending (bow_id, bow_val)
+ *    pairs (host arrays; n <= max_words, ids >= 0 and strictly ascending, PSLFE_E_INVALID otherwise).  A live slot is
+ *    PSLFE_E_INVALID: erase it first.  Every add takes the next add-sequence number.  Synchronous. */
+int pslfe_kfdb_add(pslfe_kfdb* db, int slot, const int32_t* bow_id, const double* bow_val, int n);
+/* The same for the nframes BowVectors of a pslfe_compute_bow_device result, device to device: frame f goes to slot0 + f, the
+ * sequence numbers follow f.  stride <= max_words (PSLFE_E_INVALID otherwise: a row must fit whatever its count).  Asynchronous. */
+int pslfe_kfdb_add_device(pslfe_kfdb* db, int slot0, const int32_t* d_bow_id, const double* d_bow_val, const int32_t* d_nbow,
+                          int nframes, int stride);
+/* == KeyFrameDatabase::erase :48-67; a slot that is not live is left alone, as the reference's walk finds nothing to erase. */
+int pslfe_kfdb_erase(pslfe_kfdb* db, int slot);
+/* == KeyFrameDatabase::clear :69-73 */
+int pslfe_kfdb_clear(pslfe_kfdb* db);
+/* Slot state (either array may be NULL): live[max_keyframes], seq[max_keyframes] = the add-sequence number, -1 for a dead slot. */
+int pslfe_kfdb_state(const pslfe_kfdb* db, uint8_t* live, int64_t* seq);
+/* One query on host arrays (n <= max_words, ids as for add); exclude: NULL or max_keyframes bytes, non-zero = the slot is left out
+ * (spConnectedKeyFrames :78, :96) and does not count for max_common.  words, first_word, score: max_keyframes entries each.
+ * n == 0 or an empty database: zeros, first_word -1, *max_common = 0.  Synchronous. */
+int pslfe_kfdb_query(pslfe_kfdb* db, const int32_t* bow_id, const double* bow_val, int n, const uint8_t* exclude, int32_t* words,
+                     int32_t* first_word, double* score, int* max_common);
+/* nq queries in one launch, read where pslfe_compute_bow_device wrote them: query q = d_nbow[q] pairs at d_bow_id / d_bow_val +
+ * q*stride (stride <= 4096).  d_exclude: NULL or [nq][max_keyframes]; outputs [nq][max_keyframes], d_max_common [nq].
+ * Asynchronous on the context's stream. */
+int pslfe_kfdb_query_device(pslfe_kfdb* db, const int32_t* d_bow_id, const double* d_bow_val, const int32_t* d_nbow, int nq,
+                            int stride, const uint8_t* d_exclude, int32_t* d_words, int32_t* d_first_word, double* d_score,
+                            int32_t* d_max_common);
+/* == mpORBVocabulary->score(CurrentBowVec, pKF->mBowVec) of the minScore loop of LoopClosing::DetectLoop src/LoopClosing.cc:124-138
+ *    for the keyframes in slots[nslots] (host arrays): score[j] as f64; the caller narrows to float as the reference does.  A slot
+ *    that is out of range or not live is PSLFE_E_INVALID.  Synchronous. */
+int pslfe_kfdb_score(pslfe_kfdb* db, const int32_t* bow_id, const double* bow_val, int n, const int32_t* slots, int nslots,
+                     double* score);
+
 /* ---- KeyFrame-rate matchers of LocalMapping / LoopClosing ------------------------------ */
 /* These run on other threads than Tracking in the reference (src/LocalMapping.cc:336, 580, 796-872,
  * src/LoopClosing.cc:599, 245-330): give them their own pslfe_ctx (own stream) and one pslfe_kf handle per thread.  A frame

@@ -1086,6 +1086,171 @@ class ORBVocabulary:
             pass
 
 
+class KeyFrameDatabase:
+    """== KeyFrameDatabase (src/KeyFrameDatabase.cc) on resident BowVectors (pslfe_kfdb).  A keyframe is a slot
+    0 .. max_keyframes-1; a BowVector is a pair (bow_id ascending int32, bow_val float64), e.g. ORBVocabulary.transform's.  The
+    device gives words / first_word / score per slot; the covisibility tails of the reference run here as written, on the
+    caller's graph: connected_slots = pKF->GetConnectedKeyFrames(), neighbours[slot] = that keyframe's
+    GetBestCovisibilityKeyFrames(10) as slots (a dict or a sequence; a missing entry is an empty list).
+    mLoopScore / mRelocScore are kept per slot between queries, written only when the slot is scored; they are 0.0f after add
+    (the reference leaves them uninitialised, src/KeyFrame.cc:35)."""
+
+    def __init__(self, max_keyframes, max_words=4096, ctx=None):
+        self.ctx = ctx or default_context()
+        self.max_keyframes, self.max_words = int(max_keyframes), int(max_words)
+        self._h = C.c_void_p()
+        _check(lib().pslfe_kfdb_create(self.ctx._h, C.c_int(max_keyframes), C.c_int(max_words), C.byref(self._h)), "pslfe_kfdb_create")
+        self.mLoopScore = np.zeros(self.max_keyframes, np.float32)
+        self.mRelocScore = np.zeros(self.max_keyframes, np.float32)
+
+    @staticmethod
+    def _bow(bow):
+        ids, vals = np.ascontiguousarray(bow[0], np.int32), np.ascontiguousarray(bow[1], np.float64)
+        if ids.ndim != 1 or ids.shape != vals.shape:
+            raise PslfeError("KeyFrameDatabase: a BowVector is a pair of equally long 1-D arrays (ids, values)")
+        return ids, vals
+
+    def add(self, slot, bow):
+        ids, vals = self._bow(bow)
+        _check(lib().pslfe_kfdb_add(self._h, C.c_int(slot), _ptr(ids), _ptr(vals), C.c_int(len(ids))), "pslfe_kfdb_add")
+        self.mLoopScore[slot] = self.mRelocScore[slot] = 0.0
+
+    def add_device(self, slot0, d_bow_id, d_bow_val, d_nbow, nframes, stride):
+        """the BowVectors of a pslfe_compute_bow_device result (device addresses) -> slots slot0 .. slot0 + nframes - 1"""
+        _check(lib().pslfe_kfdb_add_device(self._h, C.c_int(slot0), C.c_void_p(d_bow_id), C.c_void_p(d_bow_val), C.c_void_p(d_nbow), C.c_int(nframes),
+                                           C.c_int(stride)), "pslfe_kfdb_add_device")
+        self.mLoopScore[slot0:slot0 + nframes] = 0.0
+        self.mRelocScore[slot0:slot0 + nframes] = 0.0
+
+    def erase(self, slot):
+        _check(lib().pslfe_kfdb_erase(self._h, C.c_int(slot)), "pslfe_kfdb_erase")
+
+    def clear(self):
+        _check(lib().pslfe_kfdb_clear(self._h), "pslfe_kfdb_clear")
+
+    def state(self):
+        """-> live (u8 per slot), seq (add-sequence number per slot, -1 for a dead one)"""
+        live, seq = np.zeros(self.max_keyframes, np.uint8), np.zeros(self.max_keyframes, np.int64)
+        _check(lib().pslfe_kfdb_state(self._h, _ptr(live), _ptr(seq)), "pslfe_kfdb_state")
+        return live, seq
+
+    def query(self, bow, exclude=None):
+        """-> words, first_word, score (per slot), max_common; exclude: None or one byte per slot"""
+        ids, vals = self._bow(bow)
+        if exclude is not None:
+            exclude = np.ascontiguousarray(exclude, np.uint8)
+            if exclude.shape != (self.max_keyframes,):
+                raise PslfeError("KeyFrameDatabase.query: exclude needs one byte per slot")
+        K = self.max_keyframes
+        words, first, score, maxc = np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.float64), C.c_int()
+        _check(lib().pslfe_kfdb_query(self._h, _ptr(ids), _ptr(vals), C.c_int(len(ids)), _ptr(exclude), _ptr(words), _ptr(first), _ptr(score),
+                                      C.byref(maxc)), "pslfe_kfdb_query")
+        return words, first, score, maxc.value
+
+    def query_device(self, d_bow_id, d_bow_val, d_nbow, nq, stride, d_exclude, d_words, d_first_word, d_score, d_max_common):
+        """nq queries in one launch on device addresses (d_exclude may be None); asynchronous"""
+        _check(lib().pslfe_kfdb_query_device(self._h, C.c_void_p(d_bow_id), C.c_void_p(d_bow_val), C.c_void_p(d_nbow), C.c_int(nq), C.c_int(stride),
+                                             C.c_void_p(d_exclude), C.c_void_p(d_words), C.c_void_p(d_first_word), C.c_void_p(d_score),
+                                             C.c_void_p(d_max_common)), "pslfe_kfdb_query_device")
+
+    def Score(self, bow, slots):
+        """mpORBVocabulary->score(bow, mBowVec of each slot) -> float64 (the minScore loop of LoopClosing::DetectLoop narrows to float)"""
+        ids, vals = self._bow(bow)
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros(len(slots), np.float64)
+        _check(lib().pslfe_kfdb_score(self._h, _ptr(ids), _ptr(vals), C.c_int(len(ids)), _ptr(slots), C.c_int(len(slots)), _ptr(out)),
+               "pslfe_kfdb_score")
+        return out
+
+    def _sharing(self, bow, exclude):
+        """the query, lKFsSharingWords as slots in the reference's order, and minCommonWords"""
+        words, first, score, maxc = self.query(bow, exclude)
+        _, seq = self.state()
+        sharing = np.flatnonzero(words > 0)
+        sharing = sharing[np.lexsort((seq[sharing], first[sharing]))]
+        return words, score, [int(s) for s in sharing], int(np.float32(maxc) * np.float32(0.8))
+
+    @staticmethod
+    def _neigh(neighbours, slot):
+        if isinstance(neighbours, dict):
+            return neighbours.get(slot, ())
+        return neighbours[slot] if slot < len(neighbours) else ()
+
+    @staticmethod
+    def _retain(acc, best_acc):
+        keep = np.float32(np.float32(0.75) * best_acc)
+        out, added = [], set()
+        for a, s in acc:
+            if a > keep and s not in added:
+                out.append(s)
+                added.add(s)
+        return out
+
+    def DetectLoopCandidates(self, bow, connected_slots, min_score, neighbours):
+        """== KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) src/KeyFrameDatabase.cc:76-197 -> candidate slots, in its order"""
+        exclude = np.zeros(self.max_keyframes, np.uint8)
+        exclude[np.asarray(list(connected_slots), np.int64)] = 1
+        min_score = np.float32(min_score)
+        words, score, sharing, min_common = self._sharing(bow, exclude)
+        scored = []
+        for s in sharing:
+            if words[s] > min_common:
+                si = np.float32(score[s])
+                self.mLoopScore[s] = si
+                if si >= min_score:
+                    scored.append((si, s))
+        if not scored:
+            return []
+        acc, best_acc = [], min_score
+        for si, s in scored:
+            best_score, acc_score, best = si, si, s
+            for s2 in self._neigh(neighbours, s):
+                if words[s2] > 0 and words[s2] > min_common:   # reached by this query (never a connected one) and scored
+                    acc_score = np.float32(acc_score + self.mLoopScore[s2])
+                    if self.mLoopScore[s2] > best_score:
+                        best, best_score = int(s2), self.mLoopScore[s2]
+            acc.append((acc_score, best))
+            if acc_score > best_acc:
+                best_acc = acc_score
+        return self._retain(acc, best_acc)
+
+    def DetectRelocalizationCandidates(self, bow, neighbours):
+        """== KeyFrameDatabase::DetectRelocalizationCandidates(F) src/KeyFrameDatabase.cc:199-309 -> candidate slots, in its order"""
+        words, score, sharing, min_common = self._sharing(bow, None)
+        scored = []
+        for s in sharing:
+            if words[s] > min_common:
+                si = np.float32(score[s])
+                self.mRelocScore[s] = si
+                scored.append((si, s))
+        if not scored:
+            return []
+        acc, best_acc = [], np.float32(0)
+        for si, s in scored:
+            best_score, acc_score, best = si, si, s
+            for s2 in self._neigh(neighbours, s):
+                if words[s2] <= 0:   # mnRelocQuery != F->mnId; no minCommonWords test here (:273-281): mRelocScore may be an earlier query's
+                    continue
+                acc_score = np.float32(acc_score + self.mRelocScore[s2])
+                if self.mRelocScore[s2] > best_score:
+                    best, best_score = int(s2), self.mRelocScore[s2]
+            acc.append((acc_score, best))
+            if acc_score > best_acc:
+                best_acc = acc_score
+        return self._retain(acc, best_acc)
+
+    def close(self):
+        if self._h:
+            lib().pslfe_kfdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 TRIQUERY_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("stereo", "<i4")])
 LINEFUSEQUERY_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("radius", "<f4"), ("level", "<i4")])
 assert TRIQUERY_DTYPE.itemsize == 24 and LINEFUSEQUERY_DTYPE.itemsize == 24

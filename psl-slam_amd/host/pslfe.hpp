@@ -10,6 +10,7 @@
 #ifndef PSLFE_HPP
 #define PSLFE_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <deque>
@@ -714,6 +715,147 @@ public:
     }
 private:
     pslfe_vocab* h_ = nullptr;
+};
+
+// == KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) on resident BowVectors (pslfe_kfdb).  A keyframe is a
+//    slot 0 .. maxKeyFrames-1; a BowVector is ascending word ids with their values (ORBVocabulary::Result::bowId / bowVal).  The
+//    device gives the common words, the first common word and the L1 score of every slot; the covisibility tails run here as the
+//    reference writes them, on the caller's graph: connected = pKF->GetConnectedKeyFrames(), neighbours[slot] = that keyframe's
+//    GetBestCovisibilityKeyFrames(10), both as slots (neighbours may be shorter than the database: a missing entry is empty).
+//    mLoopScore / mRelocScore live per slot between queries and are written only when the slot is scored; add sets them to 0.0f
+//    (the reference leaves them uninitialised, src/KeyFrame.cc:35).
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(Context& ctx, int maxKeyFrames, int maxWords = 4096)
+        : K_(maxKeyFrames > 0 ? maxKeyFrames : 0), mLoopScore_(K_, 0.0f), mRelocScore_(K_, 0.0f) {
+        check(pslfe_kfdb_create(ctx.get(), maxKeyFrames, maxWords, &h_), "pslfe_kfdb_create");
+    }
+    ~KeyFrameDatabase() { pslfe_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+    pslfe_kfdb* get() const { return h_; }
+
+    void add(int slot, const std::vector<int32_t>& bowId, const std::vector<double>& bowVal) {
+        sameLength(bowId, bowVal, "KeyFrameDatabase::add");
+        check(pslfe_kfdb_add(h_, slot, bowId.data(), bowVal.data(), (int)bowId.size()), "pslfe_kfdb_add");
+        mLoopScore_[slot] = mRelocScore_[slot] = 0.0f;
+    }
+    // the BowVectors of a pslfe_compute_bow_device result -> slots slot0 .. slot0 + nframes - 1
+    void addDevice(int slot0, const int32_t* d_bowId, const double* d_bowVal, const int32_t* d_nbow, int nframes, int stride) {
+        check(pslfe_kfdb_add_device(h_, slot0, d_bowId, d_bowVal, d_nbow, nframes, stride), "pslfe_kfdb_add_device");
+        std::fill(mLoopScore_.begin() + slot0, mLoopScore_.begin() + slot0 + nframes, 0.0f);
+        std::fill(mRelocScore_.begin() + slot0, mRelocScore_.begin() + slot0 + nframes, 0.0f);
+    }
+    void erase(int slot) { check(pslfe_kfdb_erase(h_, slot), "pslfe_kfdb_erase"); }
+    void clear() { check(pslfe_kfdb_clear(h_), "pslfe_kfdb_clear"); }
+
+    // mpORBVocabulary->score(bow, mBowVec of each slot), the minScore loop of LoopClosing::DetectLoop (src/LoopClosing.cc:124-138)
+    std::vector<double> Score(const std::vector<int32_t>& bowId, const std::vector<double>& bowVal, const std::vector<int32_t>& slots) {
+        sameLength(bowId, bowVal, "KeyFrameDatabase::Score");
+        std::vector<double> s(slots.size(), 0.0);
+        check(pslfe_kfdb_score(h_, bowId.data(), bowVal.data(), (int)bowId.size(), slots.data(), (int)slots.size(), s.data()), "pslfe_kfdb_score");
+        return s;
+    }
+    // == DetectLoopCandidates(pKF, minScore) src/KeyFrameDatabase.cc:76-197: the candidate slots in the reference's order
+    std::vector<int32_t> DetectLoopCandidates(const std::vector<int32_t>& bowId, const std::vector<double>& bowVal, const std::vector<int32_t>& connected,
+                                              float minScore, const std::vector<std::vector<int32_t>>& neighbours) {
+        std::vector<uint8_t> exclude(K_, 0);
+        for (int32_t s : connected) {
+            if (s < 0 || (size_t)s >= K_) throw Error(PSLFE_E_INVALID, "KeyFrameDatabase::DetectLoopCandidates: connected slot out of range");
+            exclude[s] = 1;
+        }
+        const int minCommonWords = sharing(bowId, bowVal, exclude.data(), "KeyFrameDatabase::DetectLoopCandidates");
+        std::vector<std::pair<float, int32_t>> lScoreAndMatch, lAccScoreAndMatch;
+        for (int32_t s : sharing_) {
+            if (words_[s] > minCommonWords) {
+                const float si = (float)score_[s];
+                mLoopScore_[s] = si;
+                if (si >= minScore) lScoreAndMatch.push_back(std::make_pair(si, s));
+            }
+        }
+        if (lScoreAndMatch.empty()) return std::vector<int32_t>();
+        float bestAccScore = minScore;
+        for (const auto& it : lScoreAndMatch) {
+            float bestScore = it.first, accScore = it.first;
+            int32_t best = it.second;
+            for (int32_t s2 : neigh(neighbours, it.second)) {
+                if (words_[s2] > 0 && words_[s2] > minCommonWords) {   // reached by this query (never a connected one) and scored
+                    accScore += mLoopScore_[s2];
+                    if (mLoopScore_[s2] > bestScore) { best = s2; bestScore = mLoopScore_[s2]; }
+                }
+            }
+            lAccScoreAndMatch.push_back(std::make_pair(accScore, best));
+            if (accScore > bestAccScore) bestAccScore = accScore;
+        }
+        return retain(lAccScoreAndMatch, 0.75f * bestAccScore);
+    }
+    // == DetectRelocalizationCandidates(F) src/KeyFrameDatabase.cc:199-309
+    std::vector<int32_t> DetectRelocalizationCandidates(const std::vector<int32_t>& bowId, const std::vector<double>& bowVal,
+                                                        const std::vector<std::vector<int32_t>>& neighbours) {
+        const int minCommonWords = sharing(bowId, bowVal, nullptr, "KeyFrameDatabase::DetectRelocalizationCandidates");
+        std::vector<std::pair<float, int32_t>> lScoreAndMatch, lAccScoreAndMatch;
+        for (int32_t s : sharing_) {
+            if (words_[s] > minCommonWords) {
+                const float si = (float)score_[s];
+                mRelocScore_[s] = si;
+                lScoreAndMatch.push_back(std::make_pair(si, s));
+            }
+        }
+        if (lScoreAndMatch.empty()) return std::vector<int32_t>();
+        float bestAccScore = 0;
+        for (const auto& it : lScoreAndMatch) {
+            float bestScore = it.first, accScore = bestScore;
+            int32_t best = it.second;
+            for (int32_t s2 : neigh(neighbours, it.second)) {
+                if (words_[s2] <= 0) continue;   // mnRelocQuery != F->mnId; no minCommonWords test (:273-281): the score may be an earlier query's
+                accScore += mRelocScore_[s2];
+                if (mRelocScore_[s2] > bestScore) { best = s2; bestScore = mRelocScore_[s2]; }
+            }
+            lAccScoreAndMatch.push_back(std::make_pair(accScore, best));
+            if (accScore > bestAccScore) bestAccScore = accScore;
+        }
+        return retain(lAccScoreAndMatch, 0.75f * bestAccScore);
+    }
+
+private:
+    static void sameLength(const std::vector<int32_t>& id, const std::vector<double>& val, const char* who) {
+        if (id.size() != val.size()) throw Error(PSLFE_E_INVALID, std::string(who) + ": word ids and values differ in length");
+    }
+    // the query; sharing_ = lKFsSharingWords as slots: words > 0 in ascending (first common word, order of the adds); returns minCommonWords
+    int sharing(const std::vector<int32_t>& bowId, const std::vector<double>& bowVal, const uint8_t* exclude, const char* who) {
+        sameLength(bowId, bowVal, who);
+        words_.resize(K_); first_.resize(K_); score_.resize(K_); seq_.resize(K_);
+        int maxCommonWords = 0;
+        check(pslfe_kfdb_query(h_, bowId.data(), bowVal.data(), (int)bowId.size(), exclude, words_.data(), first_.data(), score_.data(), &maxCommonWords),
+              "pslfe_kfdb_query");
+        check(pslfe_kfdb_state(h_, nullptr, seq_.data()), "pslfe_kfdb_state");
+        sharing_.clear();
+        for (size_t s = 0; s < K_; ++s)
+            if (words_[s] > 0) sharing_.push_back((int32_t)s);
+        std::sort(sharing_.begin(), sharing_.end(), [this](int32_t a, int32_t b) {
+            return first_[a] != first_[b] ? first_[a] < first_[b] : seq_[a] < seq_[b];
+        });
+        return (int)(maxCommonWords * 0.8f);
+    }
+    const std::vector<int32_t>& neigh(const std::vector<std::vector<int32_t>>& neighbours, int32_t slot) const {
+        static const std::vector<int32_t> none;
+        if ((size_t)slot >= neighbours.size()) return none;
+        for (int32_t s2 : neighbours[slot])
+            if (s2 < 0 || (size_t)s2 >= K_) throw Error(PSLFE_E_INVALID, "KeyFrameDatabase: neighbour slot out of range");
+        return neighbours[slot];
+    }
+    static std::vector<int32_t> retain(const std::vector<std::pair<float, int32_t>>& lAccScoreAndMatch, float minScoreToRetain) {
+        std::vector<int32_t> out;
+        for (const auto& it : lAccScoreAndMatch)
+            if (it.first > minScoreToRetain && std::find(out.begin(), out.end(), it.second) == out.end()) out.push_back(it.second);
+        return out;
+    }
+    pslfe_kfdb* h_ = nullptr;
+    size_t K_ = 0;
+    std::vector<float> mLoopScore_, mRelocScore_;
+    std::vector<int32_t> words_, first_, sharing_;
+    std::vector<double> score_;
+    std::vector<int64_t> seq_;
 };
 
 // == the KeyFrame-rate searches of LocalMapping / LoopClosing (pslfe_kf): ORBmatcher::Fuse (both overloads), SearchBySim3,
