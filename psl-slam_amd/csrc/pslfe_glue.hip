@@ -9,10 +9,12 @@
 // per frame: convention H7), OpenCV's one-sided Jacobi SVD (f64), Cramer's rule for the 2x2 system.
 //
 // Work decomposition: the RANSAC of isLineGood consumes rand() values in line order and the number consumed depends on
-// the outcome, so the lines of a frame form a serial chain: one wave per frame, lines in order.  Inside a line the <= 21
-// depth samples are the lanes: back-projection, the 3x3 covariance SVD and every Mahalanobis distance run in parallel;
-// inlier sets are ballots; arg-min/arg-max with the reference's first-occurrence rule are wave reductions; only the
-// order-sensitive sums (mean, Jacobi sweeps of the n x 3 matrix) run on one lane.  Frames fill the GPU.
+// the outcome, so the lines of a frame form a serial chain: lines in order.  Inside a line the <= 21 depth samples are the
+// lanes: back-projection, the 3x3 covariance SVD and every Mahalanobis distance run in parallel; inlier sets are ballots;
+// arg-min/arg-max with the reference's first-occurrence rule are lane reductions; only the order-sensitive sums (mean,
+// Jacobi sweeps of the n x 3 matrix) run on one lane per sum.  21 lanes are a third of a wave and frames are independent
+// (srand(seed0 + frame) each), so a wave carries PSL_GOOD_GROUPS = 3 frames, one per group of 21 lanes, each with its own
+// LDS state, rand() ring and loop predicates: one instruction stream serves three frames.  Frames fill the GPU.
 #include <string.h>
 
 #include <vector>
@@ -174,74 +176,173 @@ __device__ __forceinline__ GlueP3 psl_proj_pt_ln(const GlueP3& P, const GlueP3& 
     return A + AB * (gdot(AB, AP) / gdot(AB, AB));
 }
 
-// First index (lowest lane) holding the minimum / maximum of v over the lanes of `mask`, with the reference's start values:
-// "if (v < minv) ..." from minv = 100 and "if (v > maxv) ..." from maxv = -100, index 0 of the LIST (= the lowest lane of the
-// mask) when nothing beats the start value.
-__device__ int psl_first_arg(double v, unsigned long long mask, bool want_min) {
+// ---- lane groups -------------------------------------------------------------------------------------------------------------
+// A wave of k_line_good carries PSL_GOOD_GROUPS frames, one per group of PSL_GOOD_LW consecutive lanes.  Everything that was
+// wave-uniform with one frame per wave (masks, counts, indices, loop predicates) is group-uniform here: a ballot is cut to the
+// group's bits and shifted down, so a mask is indexed with the lane's position INSIDE its group (`rl`), and a reduction never
+// crosses a group boundary.  With three groups lane 63 rides along as a 22nd lane of the last group that is in no set.
+#ifndef PSL_GOOD_WAVES
+#define PSL_GOOD_WAVES 4
+#endif
+#ifndef PSL_GOOD_GROUPS
+#define PSL_GOOD_GROUPS 3
+#endif
+#if PSL_GOOD_GROUPS == 1
+#define PSL_GOOD_LW 64
+#define PSL_GOOD_XOR0 32
+typedef unsigned long long glue_mask_t;
+#elif PSL_GOOD_GROUPS == 2
+#define PSL_GOOD_LW 32
+#define PSL_GOOD_XOR0 16
+typedef uint32_t glue_mask_t;
+#elif PSL_GOOD_GROUPS == 3
+#define PSL_GOOD_LW 21
+#define PSL_GOOD_XOR0 16
+typedef uint32_t glue_mask_t;
+#else
+#error "PSL_GOOD_GROUPS must be 1, 2 or 3"
+#endif
+static_assert(PSL_GOOD_LW >= PSL_GLUE_MAXPTS, "a group holds one lane per depth sample");
+
+struct GlueLane { int g, rl, base; };   // group, lane inside the group, first lane of the group
+__device__ __forceinline__ GlueLane glue_lane() {
     const int lane = threadIdx.x & 63;
-    const bool in = (mask >> lane) & 1ull;
+#if PSL_GOOD_GROUPS == 1
+    return {0, lane, 0};
+#else
+    const int g = min(lane / PSL_GOOD_LW, PSL_GOOD_GROUPS - 1);
+    return {g, lane - g * PSL_GOOD_LW, g * PSL_GOOD_LW};
+#endif
+}
+__device__ __forceinline__ int glue_popc(unsigned long long m) { return __popcll(m); }
+__device__ __forceinline__ int glue_popc(uint32_t m) { return __popc(m); }
+__device__ __forceinline__ int glue_ffs(unsigned long long m) { return (int)__ffsll((long long)m); }
+__device__ __forceinline__ int glue_ffs(uint32_t m) { return (int)__ffs((int)m); }
+// the group's part of a ballot, bit k = lane k of the group
+__device__ __forceinline__ glue_mask_t glue_ballot(bool p, const GlueLane& ln) {
+    const unsigned long long b = __ballot(p);
+#if PSL_GOOD_GROUPS == 1
+    return b;
+#else
+    return (glue_mask_t)(b >> ln.base) & (glue_mask_t)((1ull << PSL_GOOD_LW) - 1ull);
+#endif
+}
+__device__ __forceinline__ bool glue_any(bool p) { return __ballot(p) != 0ull; }   // over the whole wave: loop control
+// One butterfly step inside the group: the value of the lane whose position in the group is rl ^ o.  Groups of 32 or 64 lanes
+// are closed under it.  A group of 21 is not: *ok is false where the partner would lie outside, and the caller lets such a
+// step contribute nothing.  Run from the highest bit down, the first lane of the group (rl = 0) still receives every lane of
+// the group - a value travels from rl = x to 0 over positions (high bits already cleared, low bits of x) <= x, all inside the
+// group - so the group takes the result from there (glue_from_first).
+template <class T>
+__device__ __forceinline__ T glue_shfl_xor(T v, int o, const GlueLane& ln, bool* ok) {
+#if PSL_GOOD_GROUPS == 3
+    const int prl = ln.rl ^ o;
+    *ok = prl < PSL_GOOD_LW;
+    return __shfl(v, ln.base + (*ok ? prl : ln.rl));
+#else
+    *ok = true;
+    return __shfl_xor(v, o);
+#endif
+}
+__device__ __forceinline__ int glue_from_first(int v, const GlueLane& ln) {
+#if PSL_GOOD_GROUPS == 3
+    return __shfl(v, ln.base);
+#else
+    return v;
+#endif
+}
+
+// First index (lowest lane of the group) holding the minimum / maximum of v over the lanes of `mask`, with the reference's start
+// values: "if (v < minv) ..." from minv = 100 and "if (v > maxv) ..." from maxv = -100, index 0 of the LIST (= the lowest lane of
+// the mask) when nothing beats the start value.  (value, index) pairs are totally ordered, so the order of the butterfly is free.
+__device__ __forceinline__ int psl_first_arg(double v, glue_mask_t mask, bool want_min, const GlueLane& ln) {
+    const bool in = (mask >> ln.rl) & 1;
     double best = in ? v : (want_min ? 1e300 : -1e300);
-    int idx = in ? lane : 64;
+    int idx = in ? ln.rl : 64;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(idx, o);
-        const bool take = want_min ? (ob < best || (ob == best && oi < idx)) : (ob > best || (ob == best && oi < idx));
+    for (int o = PSL_GOOD_XOR0; o > 0; o >>= 1) {
+        bool ok;
+        const double ob = glue_shfl_xor(best, o, ln, &ok);
+        const int oi = glue_shfl_xor(idx, o, ln, &ok);
+        const bool take = ok && (want_min ? (ob < best || (ob == best && oi < idx)) : (ob > best || (ob == best && oi < idx)));
         if (take) { best = ob; idx = oi; }
     }
     const bool beats = want_min ? best < 100 : best > -100;
-    return beats ? idx : (int)__ffsll((long long)mask) - 1;
+    return glue_from_first(beats ? idx : glue_ffs(mask) - 1, ln);
 }
 
-struct GlueLds {
+struct GlueLds {   // one per group
     double pos[PSL_GLUE_MAXPTS][3];
     double DU[PSL_GLUE_MAXPTS][9];
     uint32_t ring[34];
     int idx[PSL_GLUE_MAXPTS + 3];   // the RANSAC shuffle (`indexes`)
     int rank[PSL_GLUE_MAXPTS + 3];  // rank -> point of an inlier set
     double term[3][24];             // psl_ordered_sum3: the terms of three ordered sums, one row each
+    double bc[3];                   // three values of the group's first three lanes, for every lane of the group
 };
 
 __device__ __forceinline__ GlueP3 glue_pos(const GlueLds& S, int i) { return {S.pos[i][0], S.pos[i][1], S.pos[i][2]}; }
 
-// verify3dLine (:95-161) on the points of `mask`
-__device__ bool psl_verify_line(const GlueLds& S, unsigned long long mask, const GlueP3& A, const GlueP3& B, int np) {
-    const int lane = threadIdx.x & 63;
-    const GlueP3 me = lane < np ? glue_pos(S, lane) : GlueP3{0, 0, 0};
+// The values x of the group's lanes 0, 1, 2, in every lane of the group
+__device__ __forceinline__ void glue_bcast3(GlueLds& S, double x, const GlueLane& ln, double* s0, double* s1, double* s2) {
+#if PSL_GOOD_GROUPS == 1
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    *s0 = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+    *s1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 1), __builtin_amdgcn_readlane(lo, 1));
+    *s2 = __hiloint2double(__builtin_amdgcn_readlane(hi, 2), __builtin_amdgcn_readlane(lo, 2));
+#else
+    if (ln.rl < 3) S.bc[ln.rl] = x;
+    __builtin_amdgcn_wave_barrier();
+    *s0 = S.bc[0]; *s1 = S.bc[1]; *s2 = S.bc[2];
+    __builtin_amdgcn_wave_barrier();   // rewritten by the next call
+#endif
+}
+
+// verify3dLine (:95-161) on the points of `mask`; every group evaluates it, the caller keeps the answer of those that asked
+__device__ __forceinline__ bool psl_verify_line(const GlueLds& S, glue_mask_t mask, const GlueP3& A, const GlueP3& B, int np, const GlueLane& ln) {
+    const int rl = ln.rl;
+    const GlueP3 me = rl < np ? glue_pos(S, rl) : GlueP3{0, 0, 0};
     const double v = gdot(me - A, B - A);
-    const int i1 = psl_first_arg(v, mask, true), i2 = psl_first_arg(v, mask, false);
+    const int i1 = max(psl_first_arg(v, mask, true, ln), 0), i2 = max(psl_first_arg(v, mask, false, ln), 0);   // -1: a group that did not ask
     const GlueP3 C = psl_proj_pt_ln(glue_pos(S, i1), (A + B) * 0.5, B - A);
     const GlueP3 D = psl_proj_pt_ln(glue_pos(S, i2), (A + B) * 0.5, B - A);
     const double cd = gnorm(D - C);
-    if (cd < 0.0000000001) return false;
     uint32_t bit = 0;
-    if ((mask >> lane) & 1ull) {
+    if ((mask >> rl) & 1) {
         double lambda = gdot(me - C, D - C) / cd / cd;
         lambda = lambda < 0 ? -lambda : lambda;
         bit = lambda >= 1 ? (1u << 9) : (1u << (unsigned int)floor(lambda * 10));
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bit |= __shfl_xor(bit, o);
+    for (int o = PSL_GOOD_XOR0; o > 0; o >>= 1) {
+        bool ok;
+        const uint32_t ob = (uint32_t)glue_shfl_xor((int)bit, o, ln, &ok);
+        bit |= ok ? ob : 0u;
+    }
+    bit = (uint32_t)glue_from_first((int)bit, ln);
     const double sum = (double)__popc(bit);
-    return sum / 10 > 0.7;
+    return !(cd < 0.0000000001) && sum / 10 > 0.7;
 }
 
-// Sum of `term` over lanes 0..m-1 in lane order (the reference's sequential accumulation), the same value in every lane.
-// THREE sums over the first m lanes' terms, each added strictly in lane order starting from +0.0 (the reference's `s += x[k]` loops:
-// the rounding depends on the order), at the price of one: "terms in parallel, additions in series" - the terms are staged in three
-// LDS rows, lane r (r = 0, 1, 2) adds row r, so ONE chain of m dependent f64 adds serves the three sums (one readlane pair + add
-// per term and sum before: the n x 3 Jacobi SVD of isLineGood's refinement spent three quarters of its instructions there).  Rows
-// are padded with +0.0 to the batch of 8: x + (+0.0) == x for every value such a running sum can hold (it is never -0.0).
-__device__ __forceinline__ void psl_ordered_sum3(GlueLds& S, double t0, double t1, double t2, int m, double* s0, double* s1, double* s2) {
-    const int lane = threadIdx.x & 63;
-    if (lane < 24) {
-        const bool in = lane < m;
-        S.term[0][lane] = in ? t0 : 0.0; S.term[1][lane] = in ? t1 : 0.0; S.term[2][lane] = in ? t2 : 0.0;
+// THREE sums per group over the terms of the group's first m lanes, each added strictly in lane order starting from +0.0 (the
+// reference's `s += x[k]` loops: the rounding depends on the order), the same values in every lane of the group, at the price of
+// one: "terms in parallel, additions in series" - the terms are staged in three LDS rows of the group, lane r of the group
+// (r = 0, 1, 2) adds row r, so ONE chain of dependent f64 adds serves the three sums of every group.  The chain is as long as the
+// largest m in the wave, rounded up to the batch of 8 (m = 0 for a group that does not ask).  Rows are padded with +0.0 (the
+// entries past the group's lanes are zeroed once, at kernel start): x + (+0.0) == x for every value such a running sum can hold
+// (it starts from +0.0 and is never -0.0), so a group with a smaller m gets bit-identical sums.
+__device__ __forceinline__ void psl_ordered_sum3(GlueLds& S, double t0, double t1, double t2, int m, const GlueLane& ln, double* s0, double* s1,
+                                                 double* s2) {
+    const int rl = ln.rl;
+    if (rl < 24) {
+        const bool in = rl < m;
+        S.term[0][rl] = in ? t0 : 0.0; S.term[1][rl] = in ? t1 : 0.0; S.term[2][rl] = in ? t2 : 0.0;
     }
     __builtin_amdgcn_wave_barrier();
-    const double* my = S.term[lane < 3 ? lane : 0];
+    const double* my = S.term[rl < 3 ? rl : 0];
+    const int mm = glue_any(m > 16) ? 24 : (glue_any(m > 8) ? 16 : (glue_any(m > 0) ? 8 : 0));
     double acc = 0;
-    for (int t = 0; t < m; t += 8) {   // m <= 21 (uniform)
+    for (int t = 0; t < mm; t += 8) {   // m <= 21
         double v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = my[t + k];
@@ -249,45 +350,54 @@ __device__ __forceinline__ void psl_ordered_sum3(GlueLds& S, double t0, double t
         for (int k = 0; k < 8; ++k) acc += v[k];
     }
     __builtin_amdgcn_wave_barrier();   // the rows are rewritten by the next call
-    const int lo = __double2loint(acc), hi = __double2hiint(acc);
-    *s0 = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
-    *s1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 1), __builtin_amdgcn_readlane(lo, 1));
-    *s2 = __hiloint2double(__builtin_amdgcn_readlane(hi, 2), __builtin_amdgcn_readlane(lo, 2));
+    glue_bcast3(S, acc, ln, s0, s1, s2);
 }
 
-// OpenCV's JacobiSVDImpl_<double> on a matrix whose n <= 3 rows of length m <= 21 are spread over the lanes (lane k holds column k:
-// a[0..2]).  The reference's sweep order (0,1), (0,2), (1,2) and every sum's order are kept; a rotation's two new row norms and the
-// NEXT pair's scalar product - it is formed from the rows as the rotation leaves them, and nothing changes them before that pair is
-// looked at - share one psl_ordered_sum3.
-__device__ void psl_jacobi_wave(GlueLds& S, double a[3], int m, int n, double W[3], double Vt[9]) {
+__device__ __forceinline__ double glue_get3(const double* v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : v[2]); }
+__device__ __forceinline__ void glue_put3(double* v, int i, double x) { v[0] = i == 0 ? x : v[0]; v[1] = i == 1 ? x : v[1]; v[2] = i == 2 ? x : v[2]; }
+
+// OpenCV's JacobiSVDImpl_<double> on a matrix whose n <= 3 rows of length m <= 21 are spread over the lanes of a group (lane k
+// holds column k: a[0..2]); m, n and `on` (the group wants this SVD at all) are group-uniform, and the groups of a wave sweep side
+// by side: a step runs while any group needs it and changes the state of those groups only.  The reference's sweep order (0,1),
+// (0,2), (1,2) and every sum's order are kept; a rotation's two new row norms and the NEXT pair's scalar product - it is formed
+// from the rows as the rotation leaves them, and nothing changes them before that pair is looked at - share one psl_ordered_sum3.
+__device__ __forceinline__ void psl_jacobi_wave(GlueLds& S, double a[3], int m, int n, bool on, const GlueLane& ln, double Vt[9]) {
     const double eps = 2.220446049250313e-16 * 10;
-    const int max_iter = m > 30 ? m : 30;
+    const int max_iter = 30;   // max(m, 30), m <= 21
     double Wd[3] = {0, 0, 0};
-    auto get = [&](const double* v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : v[2]); };
-    auto put = [&](double* v, int i, double x) { v[0] = i == 0 ? x : v[0]; v[1] = i == 1 ? x : v[1]; v[2] = i == 2 ? x : v[2]; };
+    m = on ? m : 0;
+    n = on ? n : 0;
     {
         double s0, s1, s2;   // rows i >= n hold zeros: their sums are the +0.0 Wd starts with
-        psl_ordered_sum3(S, a[0] * a[0], a[1] * a[1], a[2] * a[2], m, &s0, &s1, &s2);
+        psl_ordered_sum3(S, a[0] * a[0], a[1] * a[1], a[2] * a[2], m, ln, &s0, &s1, &s2);
         Wd[0] = s0; Wd[1] = n > 1 ? s1 : 0.0; Wd[2] = n > 2 ? s2 : 0.0;
     }
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < n; ++k) Vt[i * 3 + k] = 0;
-        Vt[i * 3 + i] = 1;
-    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Vt[i * 3 + k] = i == k ? 1 : 0;   // the rows and columns >= n are never looked at
     const int npairs = n == 3 ? 3 : (n == 2 ? 1 : 0);
-    bool have_p = false;
+    bool have_p = false, run = on;
     double p_next = 0;
     for (int iter = 0; iter < max_iter; ++iter) {
+        if (!glue_any(run)) break;
         bool changed = false;
-        for (int pr = 0; pr < npairs; ++pr) {
+#pragma unroll
+        for (int pr = 0; pr < 3; ++pr) {
             const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
-            const double ai = get(a, i), aj = get(a, j);
-            const double aa = get(Wd, i), bb = get(Wd, j);
-            double p;
-            if (have_p) p = p_next;
-            else { double d1, d2; psl_ordered_sum3(S, ai * aj, 0.0, 0.0, m, &p, &d1, &d2); }
-            have_p = false;
-            if (fabs(p) <= eps * __dsqrt_rn(aa * bb)) continue;
+            const bool pact = run && pr < npairs;
+            const double ai = a[i], aj = a[j];
+            const double aa = Wd[i], bb = Wd[j];
+            double p = p_next;
+            const bool need = pact && !have_p;
+            if (glue_any(need)) {
+                double pc, d1, d2;
+                psl_ordered_sum3(S, ai * aj, 0.0, 0.0, need ? m : 0, ln, &pc, &d1, &d2);
+                p = need ? pc : p;
+            }
+            have_p = pact ? false : have_p;
+            const bool rot = pact && !(fabs(p) <= eps * __dsqrt_rn(aa * bb));
+            if (!glue_any(rot)) continue;
             p *= 2;
             const double beta = aa - bb, gamma = __dsqrt_rn(p * p + beta * beta);
             double c, sn;
@@ -301,91 +411,103 @@ __device__ void psl_jacobi_wave(GlueLds& S, double a[3], int m, int n, double W[
             }
             const double t0 = c * ai + sn * aj;
             const double t1 = -sn * ai + c * aj;
-            put(a, i, t0); put(a, j, t1);
+            if (rot) { a[i] = t0; a[j] = t1; }
             // the pair the sweep looks at next (the first pair of the next sweep after the last one), on the rows as they are now
-            const int npr = pr + 1 < npairs ? pr + 1 : 0;
-            const int ni = npr == 2 ? 1 : 0, nj = npr == 0 ? 1 : 2;
-            double w0, w1;
-            psl_ordered_sum3(S, t0 * t0, t1 * t1, get(a, ni) * get(a, nj), m, &w0, &w1, &p_next);
-            put(Wd, i, w0); put(Wd, j, w1);
-            have_p = true;
-            changed = true;
-            for (int k = 0; k < n; ++k) {
-                const double v0 = c * Vt[i * 3 + k] + sn * Vt[j * 3 + k];
-                const double v1 = -sn * Vt[i * 3 + k] + c * Vt[j * 3 + k];
-                Vt[i * 3 + k] = v0; Vt[j * 3 + k] = v1;
+            const int nps = pr == 2 ? 0 : pr + 1, nis = nps == 2 ? 1 : 0, njs = nps == 0 ? 1 : 2;
+            const double nprod = npairs == 3 ? a[nis] * a[njs] : a[0] * a[1];
+            double w0, w1, pn;
+            psl_ordered_sum3(S, t0 * t0, t1 * t1, nprod, rot ? m : 0, ln, &w0, &w1, &pn);
+            if (rot) {
+                Wd[i] = w0; Wd[j] = w1;
+                p_next = pn;
+                have_p = true;
+                changed = true;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double v0 = c * Vt[i * 3 + k] + sn * Vt[j * 3 + k];
+                    const double v1 = -sn * Vt[i * 3 + k] + c * Vt[j * 3 + k];
+                    Vt[i * 3 + k] = v0; Vt[j * 3 + k] = v1;
+                }
             }
         }
-        if (!changed) break;
+        run = run && changed;
     }
     {
         double s0, s1, s2;
-        psl_ordered_sum3(S, a[0] * a[0], a[1] * a[1], a[2] * a[2], m, &s0, &s1, &s2);
+        psl_ordered_sum3(S, a[0] * a[0], a[1] * a[1], a[2] * a[2], m, ln, &s0, &s1, &s2);
         Wd[0] = __dsqrt_rn(s0);
         if (n > 1) Wd[1] = __dsqrt_rn(s1);
         if (n > 2) Wd[2] = __dsqrt_rn(s2);
     }
-    for (int i = 0; i < n - 1; ++i) {
-        int j = i;
-        for (int k = i + 1; k < n; ++k)
-            if (Wd[j] < Wd[k]) j = k;
-        if (i != j) {
-            const double t = Wd[i]; Wd[i] = Wd[j]; Wd[j] = t;
-            const double u = a[i]; a[i] = a[j]; a[j] = u;
-            for (int k = 0; k < n; ++k) { const double v = Vt[i * 3 + k]; Vt[i * 3 + k] = Vt[j * 3 + k]; Vt[j * 3 + k] = v; }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (i < n - 1) {
+            int j = i;
+#pragma unroll
+            for (int k = i + 1; k < 3; ++k)
+                if (k < n && glue_get3(Wd, j) < Wd[k]) j = k;
+            if (i != j) {
+                const double t = Wd[i]; Wd[i] = glue_get3(Wd, j); glue_put3(Wd, j, t);
+                const double u = a[i]; a[i] = glue_get3(a, j); glue_put3(a, j, u);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double v = Vt[i * 3 + k];
+                    const double w = j == 1 ? Vt[3 + k] : Vt[6 + k];   // j > i >= 0
+                    Vt[i * 3 + k] = w;
+                    if (j == 1) Vt[3 + k] = v; else Vt[6 + k] = v;
+                }
+            }
         }
     }
-    for (int i = 0; i < n; ++i) {
-        W[i] = Wd[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
         const double sc = Wd[i] > 2.2250738585072014e-308 ? 1 / Wd[i] : 0.;
-        a[i] *= sc;
+        if (i < n) a[i] *= sc;
     }
 }
 
-// computeLine3d_svd (:163-185) on the points of `mask` (lane = point index); returns mean and direction in every lane
-__device__ void psl_line_svd(GlueLds& S, unsigned long long mask, const GlueP3& me, GlueP3* mean_out, GlueP3* drct_out) {
-    const int lane = threadIdx.x & 63;
-    const int n = __popcll(mask);
+// computeLine3d_svd (:163-185) on the points of `mask` (lane of the group = point index) for the groups that are `on`; returns mean
+// and direction in every lane of the group
+__device__ __forceinline__ void psl_line_svd(GlueLds& S, glue_mask_t mask, bool on, const GlueLane& ln, GlueP3* mean_out, GlueP3* drct_out) {
+    const int rl = ln.rl;
+    mask = on ? mask : (glue_mask_t)0;
+    const int n = glue_popc(mask);
     // rank r of an inlier = its column / row in the matrix
-    if ((mask >> lane) & 1ull) S.rank[__popcll(mask & ((1ull << lane) - 1ull))] = lane;
+    if ((mask >> rl) & 1) S.rank[glue_popc(mask & (((glue_mask_t)1 << rl) - (glue_mask_t)1))] = rl;
     __builtin_amdgcn_wave_barrier();
     GlueP3 mean = {0, 0, 0};
     {   // mean = mean + pts[idx[i]].pos, in index order (= rank order): the three coordinate sums in one pass
-        const GlueP3 q = lane < n ? glue_pos(S, S.rank[lane]) : GlueP3{0, 0, 0};
-        psl_ordered_sum3(S, q.x, q.y, q.z, n, &mean.x, &mean.y, &mean.z);
+        const GlueP3 q = rl < n ? glue_pos(S, S.rank[rl]) : GlueP3{0, 0, 0};
+        psl_ordered_sum3(S, q.x, q.y, q.z, n, ln, &mean.x, &mean.y, &mean.z);
     }
     mean = mean * (1.0 / n);
-    double W[3], Vt[9], a[3] = {0, 0, 0};
-    GlueP3 drct;
-    if (n >= 3) {  // cv::SVD(P.t()), P.t() n x 3: A^T has 3 rows of length n, vt = V^T
-        if (lane < n) {
-            const GlueP3 p = glue_pos(S, S.rank[lane]);
+    double Vt[9], a[3] = {0, 0, 0};
+    const bool tall = n >= 3;
+    if (tall) {   // cv::SVD(P.t()), P.t() n x 3: A^T has 3 rows of length n, vt = V^T
+        if (rl < n) {
+            const GlueP3 p = glue_pos(S, S.rank[rl]);
             a[0] = p.x - mean.x; a[1] = p.y - mean.y; a[2] = p.z - mean.z;
         }
-        psl_jacobi_wave(S, a, n, 3, W, Vt);
-        drct = {Vt[0], Vt[1], Vt[2]};
-    } else {       // fewer rows than columns: the rows of P.t() themselves (n rows of length 3), vt = their normalised rotations
-        if (lane < 3) {
-            for (int r = 0; r < n; ++r) {
+    } else if (rl < 3) {   // fewer rows than columns: the rows of P.t() themselves (n rows of length 3), vt = their normalised rotations
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            if (r < n) {
                 const GlueP3 p = glue_pos(S, S.rank[r]);
-                a[r] = lane == 0 ? p.x - mean.x : (lane == 1 ? p.y - mean.y : p.z - mean.z);
+                a[r] = rl == 0 ? p.x - mean.x : (rl == 1 ? p.y - mean.y : p.z - mean.z);
             }
-        }
-        psl_jacobi_wave(S, a, 3, n, W, Vt);
-        const double r0 = a[0];
-        drct.x = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r0), 0), __builtin_amdgcn_readlane(__double2loint(r0), 0));
-        drct.y = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r0), 1), __builtin_amdgcn_readlane(__double2loint(r0), 1));
-        drct.z = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r0), 2), __builtin_amdgcn_readlane(__double2loint(r0), 2));
     }
+    psl_jacobi_wave(S, a, tall ? n : 3, tall ? 3 : n, on, ln, Vt);
+    GlueP3 wide;
+    glue_bcast3(S, a[0], ln, &wide.x, &wide.y, &wide.z);
+    const GlueP3 drct = tall ? GlueP3{Vt[0], Vt[1], Vt[2]} : wide;
     __builtin_amdgcn_wave_barrier();  // S.rank is rewritten by the next call
-    (void)me;
     *mean_out = mean;
     *drct_out = drct;
 }
 
-// glibc rand(): TYPE_3 ring in LDS, advanced by lane 0; *k is the (uniform) stream position
-__device__ void psl_glibc_srand(GlueLds& S, uint32_t seed, int* k) {
-    if ((threadIdx.x & 63) == 0) {
+// glibc rand(): TYPE_3 ring in LDS, one per group, advanced by the group's first lane; *k is the group's stream position
+__device__ void psl_glibc_srand(GlueLds& S, uint32_t seed, int* k, bool first_lane) {
+    if (first_lane) {
         int32_t s[34];
         s[0] = seed == 0 ? 1 : (int32_t)seed;
         for (int i = 1; i < 31; ++i) {
@@ -401,46 +523,56 @@ __device__ void psl_glibc_srand(GlueLds& S, uint32_t seed, int* k) {
     *k = 34 + 310;
     __builtin_amdgcn_wave_barrier();
 }
-__device__ __forceinline__ int psl_glibc_rand_lane0(GlueLds& S, int k) {  // lane 0 only
+__device__ __forceinline__ int psl_glibc_rand_first(GlueLds& S, int k) {  // the group's first lane only
     const uint32_t v = S.ring[(k - 31) % 34] + S.ring[(k - 3) % 34];
     S.ring[k % 34] = v;
     return (int)(v >> 1);
 }
 
-#ifndef PSL_GOOD_WAVES
-#define PSL_GOOD_WAVES 4
-#endif
+// Group g of block b works on frame G * b + g (neighbouring frames of a batch or a recording carry similar line counts, which
+// keeps the groups' loops in step); a group whose frame does not exist is switched off for the whole kernel.  Every `continue` and
+// `break` of the reference's loops is a predicate of the group: a loop runs while any group of the wave is in it, and a group
+// that is done waits for the others.
 __global__ __launch_bounds__(64, PSL_GOOD_WAVES) void k_line_good(const PslKeyLine* __restrict__ kls, int kl_stride, const int32_t* __restrict__ nkl,
-                                                   int nkl_single, const float* __restrict__ depth, int cols, int rows, int dstride,
+                                                   int nkl_single, int nframes, const float* __restrict__ depth, int cols, int rows, int dstride,
                                                    size_t dframe, PslCamera cam, uint32_t seed0, double* __restrict__ lines3d,
                                                    float* __restrict__ lineEq) {
-    __shared__ GlueLds S;
-    const int frame = blockIdx.x, lane = threadIdx.x;
-    const int n = min(nkl ? nkl[frame] : nkl_single, kl_stride);
+    __shared__ GlueLds SS[PSL_GOOD_GROUPS];
+    const GlueLane ln = glue_lane();
+    const int rl = ln.rl;
+    GlueLds& S = SS[ln.g];
+    const bool live = blockIdx.x * PSL_GOOD_GROUPS + ln.g < nframes;
+    const int frame = live ? blockIdx.x * PSL_GOOD_GROUPS + ln.g : 0;
+    const int n = live ? min(nkl ? nkl[frame] : nkl_single, kl_stride) : 0;
     const PslKeyLine* K = kls + (size_t)frame * kl_stride;
     const float* D = depth + (size_t)frame * dframe;
     double* L3 = lines3d + (size_t)frame * kl_stride * 6;
     float* LE = lineEq + (size_t)frame * kl_stride * 3;
     const float cx = cam.cx, cy = cam.cy;
     const float invfx = 1.0f / cam.fx, invfy = 1.0f / cam.fy;
-    for (int i = lane; i < n * 6; i += 64) L3[i] = 0.0;
-    for (int i = lane; i < n * 3; i += 64) LE[i] = -1.0f;
+    if (rl < PSL_GOOD_LW) {
+        for (int i = rl; i < n * 6; i += PSL_GOOD_LW) L3[i] = 0.0;
+        for (int i = rl; i < n * 3; i += PSL_GOOD_LW) LE[i] = -1.0f;
+        for (int i = rl; i < 3 * 24; i += PSL_GOOD_LW) (&S.term[0][0])[i] = 0.0;   // the padding of psl_ordered_sum3's rows
+    }
     int rk;
-    psl_glibc_srand(S, seed0 + (uint32_t)frame, &rk);
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    psl_glibc_srand(S, seed0 + (uint32_t)frame, &rk, rl == 0 && live);
+    const glue_mask_t lt = ((glue_mask_t)1 << rl) - (glue_mask_t)1;
 
-    for (int i = 0; i < n; ++i) {
-        const float spx = K[i].startPointX, spy = K[i].startPointY, epx = K[i].endPointX, epy = K[i].endPointY;
+    for (int i = 0; glue_any(i < n); ++i) {
+        bool act = i < n;   // the group still works on this line
+        float spx = 0, spy = 0, epx = 0, epy = 0;
+        if (act) { spx = K[i].startPointX; spy = K[i].startPointY; epx = K[i].endPointX; epy = K[i].endPointY; }
         const float dxf = spx - epx, dyf = spy - epy;
         const double len = __dsqrt_rn((double)dxf * dxf + (double)dyf * dyf);
         const int ilen = (int)len;
         const double numSmp = (double)(ilen < 20 ? ilen : 20);
-        if (numSmp == 0) continue;  // convention: 0/0 upstream
-        // ---- depth samples (:674-716), lane = j
+        act = act && !(numSmp == 0);  // convention: 0/0 upstream
+        // ---- depth samples (:674-716), lane of the group = j
         bool valid = false;
         GlueP3 p = {0, 0, 0};
-        if (lane <= (int)numSmp) {
-            const int j = lane;
+        if (act && rl <= (int)numSmp) {
+            const int j = rl;
             const double w1 = 1 - j / numSmp, w2 = j / numSmp;
             const float ax = (float)(spx * w1), ay = (float)(spy * w1), bx = (float)(epx * w2), by = (float)(epy * w2);
             const double ptx = (double)(ax + bx), pty = (double)(ay + by);
@@ -462,67 +594,77 @@ __global__ __launch_bounds__(64, PSL_GOOD_WAVES) void k_line_good(const PslKeyLi
                 }
             }
         }
-        const unsigned long long vmask = __ballot(valid);
-        const int np = __popcll(vmask);
-        if (np < 5) continue;
-        if (valid) {
-            const int r = __popcll(vmask & lt);
+        const glue_mask_t vmask = glue_ballot(valid, ln);
+        const int np = glue_popc(vmask);
+        act = act && !(np < 5);
+        if (!glue_any(act)) continue;
+        if (valid && act) {
+            const int r = glue_popc(vmask & lt);
             S.pos[r][0] = p.x; S.pos[r][1] = p.y; S.pos[r][2] = p.z;
             double DU[9];
             psl_comp_du(p, (double)cam.fx, DU);
 #pragma unroll
             for (int c = 0; c < 9; ++c) S.DU[r][c] = DU[c];
         }
-        if (lane < np) S.idx[lane] = lane;
+        if (act && rl < np) S.idx[rl] = rl;
         __builtin_amdgcn_wave_barrier();
         // ---- extract3dline_mahdist (:216-322)
-        const GlueP3 me = lane < np ? glue_pos(S, lane) : GlueP3{0, 0, 0};
+        const bool mine = act && rl < np;
+        const GlueP3 me = mine ? glue_pos(S, rl) : GlueP3{0, 0, 0};
         double myDU[9];
 #pragma unroll
-        for (int c = 0; c < 9; ++c) myDU[c] = lane < np ? S.DU[lane][c] : 0.0;
-        const int maxIterNo = min(10, (int)(np * (np - 1) * 0.5));
+        for (int c = 0; c < 9; ++c) myDU[c] = mine ? S.DU[rl][c] : 0.0;
+        const int maxIterNo = act ? min(10, (int)(np * (np - 1) * 0.5)) : 0;
         const double distThresh = 3.0;
-        unsigned long long maxMask = 0;
+        glue_mask_t maxMask = 0;
         int maxCnt = 0, bestA = 0, bestB = 0;
-        for (int iter = 0; iter < maxIterNo; ++iter) {
-            if (lane == 0) {  // random_unique(indexes.begin(), indexes.end(), 2)
+        bool run = act;
+        for (int iter = 0;; ++iter) {
+            run = run && iter < maxIterNo;
+            if (!glue_any(run)) break;
+            if (run && rl == 0) {  // random_unique(indexes.begin(), indexes.end(), 2)
                 int left = np, begin = 0;
                 for (int num = 0; num < 2; ++num) {
-                    const int r = begin + psl_glibc_rand_lane0(S, rk + num) % left;
+                    const int r = begin + psl_glibc_rand_first(S, rk + num) % left;
                     const int t = S.idx[begin]; S.idx[begin] = S.idx[r]; S.idx[r] = t;
                     ++begin; --left;
                 }
             }
-            rk += 2;
+            rk += run ? 2 : 0;
             __builtin_amdgcn_wave_barrier();
-            const int ia = S.idx[0], ib = S.idx[1];
+            const int ia = run ? S.idx[0] : 0, ib = run ? S.idx[1] : 0;
             const GlueP3 A = glue_pos(S, ia), B = glue_pos(S, ib);
-            if (gnorm(B - A) < 0.0000000001) continue;
-            const bool in = lane < np && psl_mah_dist(myDU, me, A, B) < distThresh;
-            const unsigned long long inMask = __ballot(in);
-            const int cnt = __popcll(inMask);
-            if (cnt > maxCnt) {
-                if (psl_verify_line(S, inMask, A, B, np)) { maxMask = inMask; maxCnt = cnt; bestA = ia; bestB = ib; }
+            const bool go = run && !(gnorm(B - A) < 0.0000000001);
+            const bool in = go && mine && psl_mah_dist(myDU, me, A, B) < distThresh;
+            const glue_mask_t inMask = glue_ballot(in, ln);
+            const int cnt = glue_popc(inMask);
+            const bool ask = go && cnt > maxCnt;
+            if (glue_any(ask)) {
+                const bool okl = psl_verify_line(S, ask ? inMask : (glue_mask_t)0, A, B, ask ? np : 0, ln);
+                if (ask && okl) { maxMask = inMask; maxCnt = cnt; bestA = ia; bestB = ib; }
             }
-            if (maxCnt > np * 0.6) break;
+            run = run && !(go && maxCnt > np * 0.6);
         }
         GlueP3 outA = {0, 0, 0}, outB = {0, 0, 0};
-        if (maxCnt >= 2) {
+        const bool fit = act && maxCnt >= 2;
+        if (glue_any(fit)) {
             GlueP3 m = (glue_pos(S, bestA) + glue_pos(S, bestB)) * 0.5, d = glue_pos(S, bestB) - glue_pos(S, bestA);
-            while (true) {
+            bool ref = fit;
+            while (glue_any(ref)) {
                 GlueP3 tm, td;
-                psl_line_svd(S, maxMask, me, &tm, &td);
-                const bool in = lane < np && psl_mah_dist(myDU, me, tm, tm + td) < distThresh;
-                const unsigned long long tmask = __ballot(in);
-                if (__popcll(tmask) > maxCnt) { maxMask = tmask; maxCnt = __popcll(tmask); m = tm; d = td; }
-                else break;
+                psl_line_svd(S, maxMask, ref, ln, &tm, &td);
+                const bool in = ref && mine && psl_mah_dist(myDU, me, tm, tm + td) < distThresh;
+                const glue_mask_t tmask = glue_ballot(in, ln);
+                const bool more = ref && glue_popc(tmask) > maxCnt;
+                if (more) { maxMask = tmask; maxCnt = glue_popc(tmask); m = tm; d = td; }
+                ref = more;
             }
             const double dp = gdot(me - m, d);
-            const int e1 = psl_first_arg(dp, maxMask, true), e2 = psl_first_arg(dp, maxMask, false);
-            outA = glue_pos(S, e1);
-            outB = glue_pos(S, e2);
+            const glue_mask_t emask = fit ? maxMask : (glue_mask_t)0;
+            const int e1 = max(psl_first_arg(dp, emask, true, ln), 0), e2 = max(psl_first_arg(dp, emask, false, ln), 0);
+            if (fit) { outA = glue_pos(S, e1); outB = glue_pos(S, e2); }
         }
-        if (gnorm(outA - outB) > 0.02 && lane == 0) {  // (:731-748)
+        if (fit && gnorm(outA - outB) > 0.02 && rl == 0) {  // (:731-748)
             const float e0 = (float)(outB.x - outA.x), e1f = (float)(outB.y - outA.y), e2f = (float)(outB.z - outA.z);
             const float magn = sqrtf(e0 * e0 + e1f * e1f + e2f * e2f);
             L3[6 * i] = outA.x; L3[6 * i + 1] = outA.y; L3[6 * i + 2] = outA.z;
@@ -706,8 +848,9 @@ static int glue_run(pslfe_glue* g, int nframes, const PslKeyLine* d_kls, int kl_
     hipStream_t st = g->ctx->stream;
     {
         PSL_STAGE_BEGIN(g->ctx, "line.good");
-        k_line_good<<<nframes, 64, 0, st>>>(d_kls, kl_stride, d_nkl, nkl_single, d_depth, w, h, dstride, dframe, *cam, seed0, g->d_lines3d,
-                                           g->d_lineEq);
+        const int nblocks = (nframes + PSL_GOOD_GROUPS - 1) / PSL_GOOD_GROUPS;   // PSL_GOOD_GROUPS frames per wave
+        k_line_good<<<nblocks, 64, 0, st>>>(d_kls, kl_stride, d_nkl, nkl_single, nframes, d_depth, w, h, dstride, dframe, *cam, seed0,
+                                           g->d_lines3d, g->d_lineEq);
         PSL_STAGE_END(g->ctx, "line.good");
     }
     {
