@@ -187,6 +187,52 @@ int pslfe_lsd_detect(pslfe_line* line, const uint8_t* gray, int w, int h, int st
 /* Tap for parity tests: LSD working image (f64), level-line angle in degrees (f32, -1024 = NOTDEF;
  * the reference's double angle is exactly (double)deg * CV_PI/180) and gradient norm (f64). */
 int pslfe_line_debug_gradient(pslfe_line* line, int frame, int* W, int* H, double* scaled, float* angle_deg, double* modgrad);
+/* Tap for parity tests: the kernels' restated libm, evaluated on the device.  One thread per element computes function `fn` of
+ * a[i] (and b[i] for the two-argument functions) into out0[i] (and out1[i] for the two-output ones); all four are HOST arrays of
+ * n elements.  The file is built with the flags of every kernel file, so the result is what a product kernel computes for that
+ * argument.  f32 in -> f32 out unless noted; f64 in -> f64 out unless noted.  Unknown fn, a NULL ctx or a NULL array the function
+ * uses: PSLFE_E_INVALID.  n == 0: PSLFE_OK.  Synchronous. */
+#define PSLFE_MATH_ATANF 0            /* psl_atanf(a)                                          */
+#define PSLFE_MATH_TANF 1             /* psl_tanf(a)                                           */
+#define PSLFE_MATH_SINCOSF 2          /* psl_sincosf(a): out0 = sin, out1 = cos                */
+#define PSLFE_MATH_FAST_ATAN2 3       /* psl_fast_atan2(y = a, x = b)                          */
+#define PSLFE_MATH_ATAN2F 4           /* psl_atan2f(y = a, x = b)                              */
+#define PSLFE_MATH_FDIV 5             /* PSL_FDIV(a, b)                                        */
+#define PSLFE_MATH_SQRTF 6            /* __builtin_sqrtf(a)                                    */
+#define PSLFE_MATH_CVROUND_F 7        /* psl_cvround_f(a): out0 int32                          */
+#define PSLFE_MATH_LOG 8              /* psl_log(a)                                            */
+#define PSLFE_MATH_EXP 9              /* psl_exp(a)                                            */
+#define PSLFE_MATH_LOG10 10           /* psl_log10(a)                                          */
+#define PSLFE_MATH_POW_POS 11         /* psl_pow_pos(a, b)                                     */
+#define PSLFE_MATH_SINH_SMALL 12      /* psl_sinh_small(a)                                     */
+#define PSLFE_MATH_LOG_GAMMA 13       /* lsdn_log_gamma(a)                                     */
+#define PSLFE_MATH_GLIBC_SIN 14       /* psl_glibc_sin(a, table)                               */
+#define PSLFE_MATH_GLIBC_COS 15       /* psl_glibc_cos(a, table)                               */
+#define PSLFE_MATH_COS_SIN_F64 16     /* psl_cos_sin_f64(a): out0 = cos, out1 = sin            */
+#define PSLFE_MATH_COS_SIN_2PI_F32 17 /* psl_cos_sin_2pi_f32(a): out0 = cos, out1 = sin, float */
+#define PSLFE_MATH_RATIO_INV 18       /* psl_ratio_inv(a, b, 1.0 / b)                          */
+#define PSLFE_MATH_DDIV 19            /* a / b                                                 */
+#define PSLFE_MATH_DSQRT 20           /* sqrt(a)                                               */
+#define PSLFE_MATH_CVROUND_D 21       /* psl_cvround_d(a): out0 int32                          */
+#define PSLFE_MATH_COUNT 22
+int pslfe_debug_math(pslfe_ctx* ctx, int fn, size_t n, const void* a, const void* b, void* out0, void* out1);
+/* Tap for parity tests: nfa(n, k, p) of LSD_REFINE_ADV exactly as an extraction evaluates it - the product's k_lsd_nfa_setup<phase>
+ * and k_lsd_nfa_series<phase>, with run_lsd's grids, on caller-supplied trials instead of rectangles counted in an image.
+ *   w, h       frame size: the geometry is prepared as an extraction of w x h frames prepares it (logNT, the tables);
+ *   phase      PSLFE_NFA_FIRST (the first test: one trial per rectangle) or -1 .. 3 (five trials per rectangle; in phases -1 and 3
+ *              trial t is evaluated at p / 2^(t+1));
+ *   nframes    1 .. max_batch; nrect[f] = rectangles of frame f, 0 .. rect_cap (rect_cap <= the extractor's segment capacity, 4096);
+ *   p_lognfa   [nframes][rect_cap][2]: per rectangle its p and the log_nfa it brings into the phase;
+ *   nk         [nframes][rect_cap][5][2] int32: (n, k) per trial (the first test reads trial 0 only); n < 0 = a trial the width
+ *              guard excludes;
+ *   vals, tail [nframes][rect_cap][5] doubles: the value k_lsd_nfa_setup left and sstate[].x after k_lsd_nfa_series - the binomial
+ *              tail, 0 where no series was summed (the value is then in vals), +inf where the series ended at its `stop`;
+ *   log_nt     the logNT used (may be NULL).
+ * Rows beyond nrect[f] and, for the first test, trials 1 .. 4 are not written.  OVERWRITES the rectangle and NFA buffers of the
+ * last extraction: fetch its results first.  Synchronous. */
+#define PSLFE_NFA_FIRST (-2)
+int pslfe_line_debug_nfa(pslfe_line* line, int w, int h, int phase, int nframes, const int32_t* nrect, int rect_cap,
+                         const double* p_lognfa, const int32_t* nk, double* vals, double* tail, double* log_nt);
 
 /* == LINEextractor::operator()(image, mask, keylines, descriptors, lineVec2d)
  *    add_inc/LineExtractor.h:167, add_src/LineExtractor.cpp:325-366; called from Frame::ExtractLSD

@@ -332,7 +332,9 @@ struct Lsd {
         if (abs_max < 2.2250738585072014e-308) abs_max = 2.2250738585072014e-308;  // DBL_MIN
         return (abs_diff / abs_max) <= (100.0 * 2.2204460492503131e-16);            // RELATIVE_ERROR_FACTOR * DBL_EPSILON
     }
-    double nfa(int n, int k, double p) const {
+    // *tail (if asked for) = the binomial tail the value was taken from, 0 when no series was summed
+    double nfa(int n, int k, double p, double* tail = nullptr) const {
+        if (tail) *tail = 0;
         if (n == 0 || k == 0) return -LOG_NT;
         if (n == k) return -LOG_NT - double(n) * m_log10(p);
         const double p_term = p / (1 - p);
@@ -355,6 +357,7 @@ struct Lsd {
                 if (err < tolerance * std::fabs(-m_log10(bin_tail) - LOG_NT) * bin_tail) break;
             }
         }
+        if (tail) *tail = bin_tail;
         return -m_log10(bin_tail) - LOG_NT;
     }
     // The rectangle scan of OpenCV 3.x as it behaves: corners truncated to int, slopes by INTEGER division, the second
@@ -881,6 +884,18 @@ double pso_lsd_nfa_lognt(int n, int k, double p, double logNT) {
     Lsd l;
     l.LOG_NT = logNT;
     return l.nfa(n, k, p);
+}
+// ... and the binomial tail it was taken from (0: a trivial case or an underflowed first term, no series summed)
+double pso_lsd_nfa_lognt_tail(int n, int k, double p, double logNT, double* tail) {
+    Lsd l;
+    l.LOG_NT = logNT;
+    return l.nfa(n, k, p, tail);
+}
+// many at once: n, k, p [count] -> v, tail [count]
+void pso_lsd_nfa_lognt_tail_n(int count, const int32_t* n, const int32_t* k, const double* p, double logNT, double* v, double* tail) {
+    Lsd l;
+    l.LOG_NT = logNT;
+    for (int i = 0; i < count; ++i) v[i] = l.nfa(n[i], k[i], p[i], &tail[i]);
 }
 double pso_lsd_log_gamma(double x) { return Lsd::log_gamma(x); }
 // rectangles that reach rect_improve (12 doubles each: x1 y1 x2 y2 width x y theta dx dy prec p); returns their number

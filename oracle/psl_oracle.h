@@ -103,6 +103,12 @@ int pso_line_match_nnr(const uint8_t* d1, int n1, const uint8_t* d2, int n2, flo
 int pso_set_lsd_refine(int mode);   /* 1 = LSD_REFINE_STD, 2 = LSD_REFINE_ADV (default) */
 int pso_set_nfa_math(int restated); /* 0 = host libm (default), 1 = psl_f64math.h */
 double pso_lsd_nfa(int n, int k, double p, int W, int H);
+double pso_lsd_nfa_lognt(int n, int k, double p, double logNT);
+double pso_lsd_nfa_lognt_tail(int n, int k, double p, double logNT, double* tail); /* *tail: the binomial tail, 0 = no series summed */
+void pso_lsd_nfa_lognt_tail_n(int count, const int32_t* n, const int32_t* k, const double* p, double logNT, double* v, double* tail);
+double pso_lsd_log_gamma(double x);
+/* host twins of pslfe_debug_math (math_oracle.cpp): function ids PSLFE_MATH_* of include/pslfe.h */
+int pso_math_eval(int fn, size_t n, const void* a, const void* b, void* out0, void* out1);
 int pso_lsd_rects(const uint8_t* gray, int w, int h, int stride, double* rects, int cap);
 int pso_lsd_detect(const uint8_t* gray, int w, int h, int stride, float* lines, int cap);
 int pso_lsd_gradient(const uint8_t* gray, int w, int h, int stride, double* scaled, double* angles, double* modgrad, int* W, int* H);

@@ -806,6 +806,71 @@ LINEextractor.fans_fetch = _line_fans_fetch
 LINEextractor.fans_device = _line_fans_device
 
 
+# ---- pslfe_debug_math: the kernels' restated libm on the device (include/pslfe.h: PSLFE_MATH_*) ----
+MATH_FUNCTIONS = ("atanf", "tanf", "sincosf", "fast_atan2", "atan2f", "fdiv", "sqrtf", "cvround_f", "log", "exp", "log10", "pow_pos",
+                  "sinh_small", "log_gamma", "glibc_sin", "glibc_cos", "cos_sin_f64", "cos_sin_2pi_f32", "ratio_inv", "ddiv", "dsqrt",
+                  "cvround_d")
+_F4, _F8, _I4 = np.dtype("<f4"), np.dtype("<f8"), np.dtype("<i4")
+# name -> (input dtype, takes b, out0 dtype, out1 dtype or None)
+MATH_SIGNATURES = {
+    "atanf": (_F4, False, _F4, None), "tanf": (_F4, False, _F4, None), "sincosf": (_F4, False, _F4, _F4),
+    "fast_atan2": (_F4, True, _F4, None), "atan2f": (_F4, True, _F4, None), "fdiv": (_F4, True, _F4, None),
+    "sqrtf": (_F4, False, _F4, None), "cvround_f": (_F4, False, _I4, None),
+    "log": (_F8, False, _F8, None), "exp": (_F8, False, _F8, None), "log10": (_F8, False, _F8, None), "pow_pos": (_F8, True, _F8, None),
+    "sinh_small": (_F8, False, _F8, None), "log_gamma": (_F8, False, _F8, None), "glibc_sin": (_F8, False, _F8, None),
+    "glibc_cos": (_F8, False, _F8, None), "cos_sin_f64": (_F8, False, _F8, _F8), "cos_sin_2pi_f32": (_F8, False, _F4, _F4),
+    "ratio_inv": (_F8, True, _F8, None), "ddiv": (_F8, True, _F8, None), "dsqrt": (_F8, False, _F8, None),
+    "cvround_d": (_F8, False, _I4, None),
+}
+
+
+def math_arrays(fn, a, b=None):
+    """(id, a, b, out0, out1) for function `fn` (a name of MATH_FUNCTIONS): the arguments as contiguous arrays of the function's
+    input type and zeroed outputs of its output types.  Shared by debug_math and the oracle's twin (tests/oracle_lib.py)."""
+    ti, binary, t0, t1 = MATH_SIGNATURES[fn]
+    a = np.ascontiguousarray(a, ti).ravel()
+    if binary:
+        b = np.ascontiguousarray(b, ti).ravel()
+        assert b.shape == a.shape, "a and b differ in length"
+    else:
+        assert b is None, f"{fn} takes one argument"
+    return MATH_FUNCTIONS.index(fn), a, b, np.zeros(len(a), t0), None if t1 is None else np.zeros(len(a), t1)
+
+
+def debug_math(fn, a, b=None, ctx=None):
+    """pslfe_debug_math: function `fn` of the kernels' restated libm evaluated on the device, one thread per element -> out0, or
+    (out0, out1) for sincosf (sin, cos), cos_sin_f64 and cos_sin_2pi_f32 (cos, sin)."""
+    ctx = ctx or default_context()
+    i, a, b, o0, o1 = math_arrays(fn, a, b)
+    _check(lib().pslfe_debug_math(ctx._h, C.c_int(i), C.c_size_t(len(a)), _ptr(a), _ptr(b), _ptr(o0), _ptr(o1)), "pslfe_debug_math")
+    return o0 if o1 is None else (o0, o1)
+
+
+NFA_FIRST = -2
+
+
+def _line_debug_nfa(self, w, h, phase, nrect, p_lognfa, nk):
+    """pslfe_line_debug_nfa: k_lsd_nfa_setup<phase> + k_lsd_nfa_series<phase> on caller-supplied trials.  nrect: [F] rectangles per
+    frame; p_lognfa: [F, R, 2] (p, incoming log_nfa); nk: [F, R, 5, 2] int32 (n, k) per trial, n < 0 = excluded by the width guard.
+    -> (vals [F, R, 5], tail [F, R, 5], logNT).  Entries beyond nrect[f] (and trials 1 .. 4 of NFA_FIRST) are NaN.  Overwrites the
+    rectangle and NFA buffers of the last extraction."""
+    nrect = np.ascontiguousarray(nrect, np.int32).ravel()
+    F = len(nrect)
+    pl = np.ascontiguousarray(p_lognfa, np.float64)
+    nk = np.ascontiguousarray(nk, np.int32)
+    R = pl.shape[1]
+    assert pl.shape == (F, R, 2) and nk.shape == (F, R, 5, 2), (pl.shape, nk.shape)
+    vals = np.full((F, R, 5), np.nan)
+    tail = np.full((F, R, 5), np.nan)
+    lognt = C.c_double()
+    _check(lib().pslfe_line_debug_nfa(self._h, C.c_int(w), C.c_int(h), C.c_int(phase), C.c_int(F), _ptr(nrect), C.c_int(R), _ptr(pl), _ptr(nk),
+                                      _ptr(vals), _ptr(tail), C.byref(lognt)), "pslfe_line_debug_nfa")
+    return vals, tail, lognt.value
+
+
+LINEextractor.debug_nfa = _line_debug_nfa
+
+
 def _lsd_search_by_geom_appearance(self, kl_last, desc_last, kl_cur, desc_cur, has_mapline, desc_th, bounds):
     """LSDmatcher::SearchByGeomNApearance(CurrentFrame, LastFrame, desc_th) -> (lmatches, matches12, assigned).
     bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY)."""

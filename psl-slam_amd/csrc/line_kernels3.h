@@ -18,6 +18,7 @@
 #define PSL_LINE_KERNELS3_H
 
 #include "line_kernels.h"
+#include "psl_log_gamma.h"   // lsdn_log_gamma
 
 struct LsdnRect { double x1, y1, x2, y2, width, theta, dx, dy, prec, p; };
 struct LsdnGeom {
@@ -285,26 +286,6 @@ __device__ __forceinline__ void lsdn_count_trials(const float* __restrict__ ang,
 }
 
 // ---- nfa() ------------------------------------------------------------------------------------------------------------
-// pow(x, n) for the integer-valued arguments log_gamma sees: exact products where libm's pow is exact as well (x <= 15,
-// n <= 6); x^6 = (x^3)^2 with x^3 exact, i.e. one rounding - what a pow with < 1 ulp of error returns - for the Windschitl term
-__host__ __device__ static inline double lsdn_log_gamma(double x) {
-    if (x > 15.0) {
-        const double c = PSL_DMUL(PSL_DMUL(x, x), x), x6 = PSL_DMUL(c, c);
-        const double inner = PSL_DADD(PSL_DMUL(x, psl_sinh_small(1 / x)), 1 / PSL_DMUL(810.0, x6));
-        return PSL_DADD(PSL_DSUB(PSL_DADD(0.918938533204673, PSL_DMUL(PSL_DSUB(x, 0.5), psl_log(x))), x), PSL_DMUL(PSL_DMUL(0.5, x), psl_log(inner)));
-    }
-    const double q[7] = {75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424, 2.50662827511};
-    double a = PSL_DSUB(PSL_DMUL(PSL_DADD(x, 0.5), psl_log(PSL_DADD(x, 5.5))), PSL_DADD(x, 5.5));
-    double b = 0, xn = 1;
-#pragma unroll
-    for (int n = 0; n < 7; ++n) {
-        a = PSL_DSUB(a, psl_log(PSL_DADD(x, (double)n)));
-        b = PSL_DADD(b, PSL_DMUL(q[n], xn));
-        xn = PSL_DMUL(xn, x);
-    }
-    return PSL_DADD(a, psl_log(b));
-}
-
 __device__ __forceinline__ bool lsdn_double_equal0(double a) {  // double_equal(a, 0)
     if (a == 0.0) return true;
     const double aa = fabs(a);
@@ -362,42 +343,6 @@ __device__ __forceinline__ int lsdn_tail_test_fast(double term, double bin_tail,
     if (errE * 1.001 + slack < tb * (lo > 0 ? lo : 0.0)) return 1;
     if (errE * 0.999 - slack >= tb * hi) return 0;
     return -1;
-}
-
-__device__ __forceinline__ double lsdn_nfa(const LsdnTables& T, int n, int k, double p) {
-    const double log_nt = T.log_nt;
-    if (n == 0 || k == 0) return -log_nt;
-    // p = p0 / 2^j: the table row, or -1 (a probability rect_improve cannot produce: evaluated directly)
-    int j = (int)((__double_as_longlong(T.p0) >> 52) & 0x7ff) - (int)((__double_as_longlong(p) >> 52) & 0x7ff);
-    if (j < 0 || j >= PSL_NFA_NP || __longlong_as_double(__double_as_longlong(T.p0) - ((long long)j << 52)) != p) j = -1;
-    if (n == k) return PSL_DSUB(-log_nt, PSL_DMUL((double)n, j >= 0 ? T.logs[2 * PSL_NFA_NP + j] : psl_log10(p)));
-    const double p_term = p / PSL_DSUB(1.0, p);
-    double log1term = PSL_DSUB(PSL_DSUB(lsdn_lg(T, n + 1), lsdn_lg(T, k + 1)), lsdn_lg(T, n - k + 1));
-    log1term = PSL_DADD(PSL_DADD(log1term, PSL_DMUL((double)k, j >= 0 ? T.logs[j] : psl_log(p))),
-                        PSL_DMUL((double)(n - k), j >= 0 ? T.logs[PSL_NFA_NP + j] : psl_log(PSL_DSUB(1.0, p))));
-    double term = psl_exp(log1term);
-    if (lsdn_double_equal0(term)) {
-        if ((double)k > PSL_DMUL((double)n, p)) return PSL_DSUB(-log1term / 2.30258509299404568402, log_nt);
-        return -log_nt;
-    }
-    double bin_tail = term;
-    for (int i = k + 1; i <= n; ++i) {
-        const double bin_term = (double)(n - i + 1) / (double)i;
-        const double mult_term = PSL_DMUL(bin_term, p_term);
-        term = PSL_DMUL(term, mult_term);
-        bin_tail = PSL_DADD(bin_tail, term);
-        if (bin_term < 1) {
-            const int q = n - i + 1;
-            int stop = lsdn_tail_test_fast(term, bin_tail, mult_term, q, log_nt);
-            if (stop < 0) {
-                const double pw = q == 1 ? mult_term : psl_pow_pos(mult_term, (double)q);  // pow(x, 1) is exact in any libm
-                const double err = PSL_DMUL(term, PSL_DSUB(PSL_DSUB(1.0, pw) / PSL_DSUB(1.0, mult_term), 1.0));
-                stop = err < PSL_DMUL(PSL_DMUL(0.1, fabs(PSL_DSUB(-psl_log10(bin_tail), log_nt))), bin_tail) ? 1 : 0;
-            }
-            if (stop) break;
-        }
-    }
-    return PSL_DSUB(-psl_log10(bin_tail), log_nt);
 }
 
 // one step of the cumulative change a rect_improve phase applies to its trial rectangle (phase 0: narrower, 1 / 2: one side)

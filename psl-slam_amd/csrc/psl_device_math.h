@@ -12,7 +12,16 @@
 #ifndef PSL_DEVICE_MATH_H
 #define PSL_DEVICE_MATH_H
 
+#if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
+#else   // a plain host compiler (oracle/math_oracle.cpp, the host twin of pslfe_debug_math): only the host half below is compiled
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 #include <stdint.h>
 
 #pragma clang fp contract(off)
@@ -37,10 +46,14 @@
 
 #define PSL_HD __host__ __device__ static inline
 
+// Out of int's range the device conversion saturates (NaN: 0); the host cast would be undefined there, so the host half says the same
+// in words (tests/test_debug_math_gpu.py: cvround_*_limits).  No caller gets there: the arguments are pixel coordinates and bin indices.
 PSL_HD int psl_cvround_f(float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __float2int_rn(v);
 #else
+    if (!(v < 2147483648.0f)) return v != v ? 0 : 2147483647;
+    if (v < -2147483648.0f) return -2147483647 - 1;
     return (int)__builtin_nearbyintf(v);
 #endif
 }
@@ -49,6 +62,8 @@ PSL_HD int psl_cvround_d(double v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __double2int_rn(v);
 #else
+    if (!(v < 2147483647.5)) return v != v ? 0 : 2147483647;    // 2147483647.5 rounds (to even) to 2^31
+    if (v < -2147483648.5) return -2147483647 - 1;              // -2147483648.5 rounds (to even) to -2^31
     return (int)__builtin_nearbyint(v);
 #endif
 }

@@ -6,7 +6,8 @@
 // Product code.  Plain-C text so that the CPU suite can compile it for the host (tests/test_f64math_cpu.py builds
 // oracle/f64math_check.c around it): set PSL_F64_QUAL to the function qualifiers first.  Every operation is a single
 // IEEE operation - the library and the check program are both built with -ffp-contract=off - so host and device results
-// are bit-identical by construction.
+// are bit-identical: pslfe_debug_math runs these functions on the device and tests/test_debug_math_gpu.py compares them with the
+// host compile (oracle/math_oracle.cpp) on argument grids around every branch threshold below.
 //
 // psl_tanf is glibc's float tanf (sysdeps/ieee754/flt-32/s_tanf.c, k_tanf.c: the fdlibm kernel in plain f32 arithmetic, with
 // glibc >= 2.28's double-precision argument reduction) restated for |x| < 120; the check program compares it with the host's libm for EVERY float in

@@ -489,6 +489,89 @@ int pslfe_line_debug_gradient(pslfe_line* line, int frame, int* W, int* H, doubl
 }
 
 
+// nfa() on caller-supplied trials: the launches PSL_NFA_EVAL(PH) of run_lsd without the selection, on state written here instead of
+// counted in an image.  Runs no kernel of its own.
+int pslfe_line_debug_nfa(pslfe_line* line, int w, int h, int phase, int nframes, const int32_t* nrect, int rect_cap, const double* p_lognfa,
+                         const int32_t* nk, double* vals, double* tail, double* log_nt) {
+    PSL_REQUIRE(line && nrect && p_lognfa && nk && vals && tail, PSLFE_E_INVALID, "pslfe_line_debug_nfa: NULL argument");
+    PSL_REQUIRE(phase == PSL_NFA_FIRST || (phase >= -1 && phase <= 3), PSLFE_E_INVALID, "pslfe_line_debug_nfa: phase %d", phase);
+    PSL_REQUIRE(nframes >= 1 && nframes <= line->max_batch, PSLFE_E_INVALID, "pslfe_line_debug_nfa: nframes %d (max_batch %d)", nframes, line->max_batch);
+    PSL_REQUIRE(rect_cap >= 1 && rect_cap <= PSL_MERGE_NMAX, PSLFE_E_INVALID, "pslfe_line_debug_nfa: rect_cap %d (at most %d)", rect_cap, PSL_MERGE_NMAX);
+    const int TR = phase == PSL_NFA_FIRST ? 1 : 5;
+    for (int f = 0; f < nframes; ++f) {
+        PSL_REQUIRE(nrect[f] >= 0 && nrect[f] <= rect_cap, PSLFE_E_INVALID, "pslfe_line_debug_nfa: frame %d has %d rectangles (rect_cap %d)", f, nrect[f], rect_cap);
+        for (int r = 0; r < nrect[f]; ++r) {
+            const double p = p_lognfa[((size_t)f * rect_cap + r) * 2];
+            PSL_REQUIRE(p > 0.0 && p < 1.0, PSLFE_E_INVALID, "pslfe_line_debug_nfa: frame %d rectangle %d: p %g", f, r, p);
+            for (int t = 0; t < TR; ++t) {
+                const int32_t* c = nk + (((size_t)f * rect_cap + r) * 5 + t) * 2;
+                PSL_REQUIRE(c[0] < 0 || (c[1] >= 0 && c[1] <= c[0] && c[0] <= (1 << 24)), PSLFE_E_INVALID,
+                            "pslfe_line_debug_nfa: frame %d rectangle %d trial %d: (n, k) = (%d, %d)", f, r, t, c[0], c[1]);
+            }
+        }
+    }
+    int rc = line->prepare(w, h);
+    if (rc) return rc;
+    PSL_HIP(hipSetDevice(line->ctx->device));
+    hipStream_t st = line->ctx->stream;
+    const LineParams& P = line->P;
+    const size_t F = (size_t)nframes, N = (size_t)P.maxseg;
+    // the state the count and select launches of an extraction leave for this phase: rectangles (p, log_nfa), their (n, k), and the list
+    // of undecided rectangles the phase walks (every rectangle, in descending order: results are stored by rectangle index)
+    std::vector<double> rects(F * N * PSL_LSD_RECT_F64, 0.0);
+    std::vector<int2> cnt(F * N * TR, make_int2(-1, 0));
+    std::vector<uint16_t> ulist(F * N, 0);
+    for (size_t f = 0; f < F; ++f)
+        for (int r = 0; r < nrect[f]; ++r) {
+            const size_t o = f * N + r, s = f * rect_cap + r;
+            rects[o * PSL_LSD_RECT_F64 + 9] = p_lognfa[s * 2];
+            rects[o * PSL_LSD_RECT_F64 + 10] = p_lognfa[s * 2 + 1];
+            for (int t = 0; t < TR; ++t) cnt[o * TR + t] = make_int2(nk[(s * 5 + t) * 2], nk[(s * 5 + t) * 2 + 1]);
+            ulist[f * N + r] = (uint16_t)(nrect[f] - 1 - r);
+        }
+    PSL_HIP(hipMemcpyAsync(line->d_rects, rects.data(), rects.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    PSL_HIP(hipMemcpyAsync(line->d_nrect, nrect, F * sizeof(int), hipMemcpyHostToDevice, st));
+    PSL_HIP(hipMemcpyAsync(phase == PSL_NFA_FIRST ? line->d_count0 : line->d_counts, cnt.data(), cnt.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+    uint16_t* d_ul = nullptr;
+    int* d_uc = nullptr;
+    if (phase != PSL_NFA_FIRST) {   // list phase + 1 of run_lsd, at the place a launch of `nframes` frames keeps it
+        d_ul = line->d_ulist + (size_t)((phase + 1) & 1) * N * F;
+        d_uc = line->d_ucount + (size_t)(phase + 1) * F;
+        PSL_HIP(hipMemcpyAsync(d_ul, ulist.data(), ulist.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        PSL_HIP(hipMemcpyAsync(d_uc, nrect, F * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+#define PSL_NFA_DEBUG_EVAL(PH)                                                                                                                  \
+    case PH:                                                                                                                                    \
+        k_lsd_nfa_setup<PH><<<F, 256, 0, st>>>(P, line->NT, line->d_rects, line->d_nrect, d_ul, d_uc, line->d_counts, line->d_count0, line->d_vals, \
+                                               line->d_sstate, line->d_stmp, line->d_slist, line->d_lcount);                                    \
+        k_lsd_nfa_series<PH><<<dim3(PSL_NFA_NCLS, (F + PSL_NFA_FG - 1) / PSL_NFA_FG), 256, 0, st>>>(P, line->NT, (int)F, line->d_slist, line->d_lcount, \
+                                                                                                    line->d_sstate);                            \
+        break;
+    switch (phase) {
+        PSL_NFA_DEBUG_EVAL(PSL_NFA_FIRST)
+        PSL_NFA_DEBUG_EVAL(-1)
+        PSL_NFA_DEBUG_EVAL(0)
+        PSL_NFA_DEBUG_EVAL(1)
+        PSL_NFA_DEBUG_EVAL(2)
+        PSL_NFA_DEBUG_EVAL(3)
+    }
+#undef PSL_NFA_DEBUG_EVAL
+    PSL_HIP(hipGetLastError());
+    std::vector<double> v(F * N * 5);
+    std::vector<double2> ss(F * N * 5);
+    PSL_HIP(hipMemcpyAsync(v.data(), line->d_vals, v.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(ss.data(), line->d_sstate, ss.size() * sizeof(double2), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    for (size_t f = 0; f < F; ++f)
+        for (int r = 0; r < nrect[f]; ++r)
+            for (int t = 0; t < TR; ++t) {
+                vals[((size_t)f * rect_cap + r) * 5 + t] = v[(f * N + r) * 5 + t];
+                tail[((size_t)f * rect_cap + r) * 5 + t] = ss[(f * N + r) * 5 + t].x;
+            }
+    if (log_nt) *log_nt = line->NT.log_nt;
+    return PSLFE_OK;
+}
+
 // ---- full extractor ------------------------------------------------------------------------------
 int pslfe_line_extract_batch_device(pslfe_line* line, const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
     PSL_REQUIRE(line && d_gray, PSLFE_E_INVALID, "pslfe_line_extract_batch_device: NULL argument");

@@ -573,6 +573,39 @@ def lsd_nfa(n, k, p, W, H):
     return L.pso_lsd_nfa(n, k, p, W, H)
 
 
+def lsd_nfa_lognt_tail(n, k, p, log_nt):
+    """nfa(n, k, p) with log(NT) given, and the binomial tail it was taken from (0 = no series was summed), for arrays of trials."""
+    L = load()
+    n = np.ascontiguousarray(n, np.int32).ravel()
+    k = np.ascontiguousarray(k, np.int32).ravel()
+    p = np.ascontiguousarray(p, np.float64).ravel()
+    assert len(n) == len(k) == len(p)
+    v, tail = np.zeros(len(n)), np.zeros(len(n))
+    L.pso_lsd_nfa_lognt_tail_n.restype = None
+    L.pso_lsd_nfa_lognt_tail_n.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.pso_lsd_nfa_lognt_tail_n(len(n), _p(n), _p(k), _p(p), float(log_nt), _p(v), _p(tail))
+    return v, tail
+
+
+def lsd_log_gamma(x):
+    """log_gamma() of the oracle's nfa() for an array of arguments (host libm, or the restated functions under set_nfa_math(1))."""
+    L = load()
+    L.pso_lsd_log_gamma.restype = C.c_double
+    L.pso_lsd_log_gamma.argtypes = [C.c_double]
+    return np.array([L.pso_lsd_log_gamma(float(v)) for v in np.asarray(x).ravel()], np.float64)
+
+
+def math_eval(fn, a, b=None):
+    """Host twin of psl_slam_amd.debug_math (oracle/math_oracle.cpp): the host compile of the product's math headers."""
+    import psl_slam_amd as P
+    L = load()
+    i, a, b, o0, o1 = P.math_arrays(fn, a, b)
+    L.pso_math_eval.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.pso_math_eval(i, len(a), _p(a), None if b is None else _p(b), _p(o0), None if o1 is None else _p(o1))
+    assert rc == 0, f"pso_math_eval({fn}) -> {rc}"
+    return o0 if o1 is None else (o0, o1)
+
+
 LSD_RECT_FIELDS = ("x1", "y1", "x2", "y2", "width", "x", "y", "theta", "dx", "dy", "prec", "p")
 
 

@@ -58,6 +58,14 @@ def test_null_arguments_return_error_codes():
     assert lib.pslfe_frame_create(None, 10, 1, None) == -1
     n = C.c_int(5)
     assert lib.pslfe_hamming_knn2(None, None, 0, None, 0, None, None) == -1
+    # the debug taps of the restated libm and of the NFA evaluation
+    a, o = np.ones(4, np.float32), np.zeros(4, np.float32)
+    pa, po = C.c_void_p(a.ctypes.data), C.c_void_p(o.ctypes.data)
+    assert lib.pslfe_debug_math(None, 0, C.c_size_t(4), pa, None, po, None) == -1
+    assert lib.pslfe_debug_math(None, 999, C.c_size_t(4), pa, None, po, None) == -1
+    assert lib.pslfe_debug_math(None, 0, C.c_size_t(4), None, None, None, None) == -1
+    assert lib.pslfe_line_debug_nfa(None, 640, 480, 0, 1, None, 1, None, None, None, None, None) == -1
+    assert b"pslfe_line_debug_nfa" in lib.pslfe_last_error()
     lib.pslfe_orb_destroy(None)
     lib.pslfe_frame_destroy(None)
     lib.pslfe_ctx_destroy(None)
