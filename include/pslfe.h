@@ -1000,6 +1000,79 @@ int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t*
  *    least median Hamming distance to the others (median = sorted[0.5*(N-1)], first on ties), -1 for an empty run. */
 int pslfe_kf_distinctive_descriptors(pslfe_kf* k, const uint8_t* desc, const int32_t* offsets, int npts, int32_t* best);
 
+/* ---- Map upkeep: the geometry half of the refresh whose descriptor half is pslfe_kf_distinctive_descriptors.  These make the rows
+ * (PslMapPointGeom, PslMapLineGeom) that every projection above reads.  The reference calls them wherever the map changes:
+ * LocalMapping::ProcessNewKeyFrame src/LocalMapping.cc:160, :183; after both Fuse passes of SearchInNeighbors :834, :884; after
+ * triangulation :512, :750; for the local points after local BA src/Optimizer.cc:1950; for EVERY map point after a loop correction or
+ * a global BA src/LoopClosing.cc:500, src/Optimizer.cc:227, :2797.
+ *
+ * Row i has the observation run obs_kf[obs_off[i] .. obs_off[i+1]): indices into centres (nkf x 3 floats, KeyFrame::GetCameraCenter())
+ * in the order in which the caller's mObservations iterates.  The reference's std::map<KeyFrame*, size_t> iterates in pointer order and
+ * the sums below depend on the order: it belongs to the caller and is kept.  ref_kf[i] = the index of mpRefKF, ref_level[i] = the octave
+ * of the observation in mpRefKF (mvKeysUn[observations[pRefKF]].octave / mvKeyLines[...].octave).  A row with an empty run or
+ * skip[i] != 0 (mbBad; skip == NULL = none) keeps every byte: the reference's early returns.  Of the other rows the normal, min_dist and
+ * max_dist are written in place; the position (x, y, z / sp, ep) is only read.
+ *
+ * Arithmetic (the conventions above PslPose; OpenCV and Eigen are not in the reference tree, so this is pinned against the in-repo
+ * restatement tests/map_upkeep_cases.py only):
+ *   points  normali = P - Ow_j, a float subtraction per component; nrm = cv::norm(normali) as the double it returns, the double sqrt of
+ *           the double sum in index order of the exact squares, NOT rounded to float; normali/nrm is Mat / double as OpenCV 3.2's
+ *           MatExpr evaluates it, a scaling by the reciprocal in the Mat's float: t = (float)(1.0 / nrm), term[c] = normali[c] * t;
+ *           normal[c] += term[c] is a float add, sequential in run order; after the run normal[c] * (float)(1.0 / (double)n);
+ *           dist = the float-rounded norm of P - centres[ref_kf[i]]; max_dist = dist * scale_factors[ref_level[i]]; min_dist =
+ *           max_dist / scale_factors[nlevels-1]; float operations, never contracted.
+ *   lines   mid = 0.5*(sp+ep) in double (a sum, then the exact halving); normali = mid - (double)Ow_j; norm = sqrt(x*x + y*y + z*z), the
+ *           double sum in index order without contraction; normal += normali / norm, a true double division per component, sequential in
+ *           run order; after the run normal / (double)n.  dist: SP, EP = sp, ep rounded to float, MP = the one-rounding half-sum stated
+ *           above PslMapLineGeom, CM = MP - Ow_ref in float, dist = the float-rounded double norm of CM; min_dist, max_dist as for
+ *           points.  scale_factors is the table the reference reads there, pRefKF->mvScaleFactors: the POINT table, not
+ *           mvScaleFactorsLine (add_src/MapLine.cpp:358, :364).
+ * There is no special case for a zero distance: the IEEE results (inf, NaN) are the reference's.
+ *
+ * Checks, before any device is touched: negative M or nkf is PSLFE_E_INVALID; then M == 0 is PSLFE_OK, nothing written and nothing else
+ * looked at; then a NULL array (obs_kf may be NULL when there is no observation, centres when nkf == 0, in the host forms) or nlevels
+ * outside 1..16 is PSLFE_E_INVALID.  The host forms also refuse, with PSLFE_E_INVALID, offsets that do not ascend from 0, an obs_kf
+ * outside [0, nkf) and, for a row that is refreshed, a ref_kf outside [0, nkf) or a ref_level outside [0, nlevels).  The device forms
+ * cannot see their arrays: such a row is a caller error there (the kernel reads outside the tables).  In every form obs_kf must be in
+ * range for EVERY run, those of skipped rows included: the tiled layout forms the terms of a skipped row before it drops them, so a
+ * stale index behind a bad point is read there, while ref_kf and ref_level of a row that is not refreshed are never read.  The device
+ * row arrays (d_mp, d_ml) must be 16-byte aligned, as hipMalloc returns them and as any whole-row offset into them keeps them: the
+ * kernels read and write rows in 16-byte pieces. */
+/* == MapPoint::UpdateNormalAndDepth src/MapPoint.cc:330-371 for M map points.  Host arrays; returns after mp has been updated. */
+int pslfe_kf_update_normal_and_depth(pslfe_kf* k, PslMapPointGeom* mp, int M, const int32_t* obs_off, const int32_t* obs_kf,
+                                     const float* centres, int nkf, const int32_t* ref_kf, const int32_t* ref_level, const uint8_t* skip,
+                                     const float* scale_factors, int nlevels);
+/* The same on device arrays (scale_factors stays a host array of nlevels floats): queued on the context's stream, no synchronisation.
+ * d_mp is the array that pslfe_orb_project_frustum_device reads and that the pslfe_kf_* entry points upload a copy of. */
+int pslfe_kf_update_normal_and_depth_device(pslfe_kf* k, PslMapPointGeom* d_mp, int M, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                            const float* d_centres, int nkf, const int32_t* d_ref_kf, const int32_t* d_ref_level,
+                                            const uint8_t* d_skip, const float* scale_factors, int nlevels);
+/* == MapLine::UpdateAverageDir add_src/MapLine.cpp:320-367 for M map lines.  Host arrays; returns after ml has been updated. */
+int pslfe_kf_line_update_average_dir(pslfe_kf* k, PslMapLineGeom* ml, int M, const int32_t* obs_off, const int32_t* obs_kf,
+                                     const float* centres, int nkf, const int32_t* ref_kf, const int32_t* ref_level, const uint8_t* skip,
+                                     const float* scale_factors, int nlevels);
+/* The same on device arrays, as pslfe_kf_update_normal_and_depth_device; d_ml is the array pslfe_line_project_frustum_device reads. */
+int pslfe_kf_line_update_average_dir_device(pslfe_kf* k, PslMapLineGeom* d_ml, int M, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                            const float* d_centres, int nkf, const int32_t* d_ref_kf, const int32_t* d_ref_level,
+                                            const uint8_t* d_skip, const float* scale_factors, int nlevels);
+/* The layout of the run-order sums of the four refresh entry points on this handle.  Both give the same bytes.  The default is
+ * PSLFE_UPKEEP_SUM_WALK; the two have not been measured against each other, the choice is open and
+ * tools/bench_map_upkeep.py is what settles it.
+ *   PSLFE_UPKEEP_SUM_WALK   one thread per row walks its run;
+ *   PSLFE_UPKEEP_SUM_TILED  one lane per observation forms the terms of a tile in LDS, the row's thread adds them in run order. */
+#define PSLFE_UPKEEP_SUM_WALK 0
+#define PSLFE_UPKEEP_SUM_TILED 1
+int pslfe_kf_set_upkeep_sum(pslfe_kf* k, int layout);
+/* == KeyFrame::ComputeSceneMedianDepth(q) src/KeyFrame.cc:749-779 for K keyframes (the monocular CreateNewMapPoints / CreateNewMapLines2
+ *    call it once per neighbour, src/LocalMapping.cc:324, :569).  Keyframe j has the world positions x[off[j] .. off[j+1]) (float
+ *    triples: GetWorldPos() of its non-NULL mvpMapPoints, in index order) and the pose Tcw[j]; off: K+1 entries ascending from 0
+ *    (PSLFE_E_INVALID otherwise).  z = Rcw2.dot(x3Dw) + zcw: the double sum in index order of the exact products, + the double of
+ *    tcw[2], rounded once to float; depth[j] = sorted[(n-1)/q] with integer division.  n == 0: depth[j] = -1.0f (the reference indexes
+ *    an empty vector there).  A NaN depth is a precondition violation (std::sort's order is then undefined); of +0 and -0, which sort
+ *    may leave in either order, the library ranks -0 first.  K < 0, q < 1 or a NULL array: PSLFE_E_INVALID; K == 0: PSLFE_OK, nothing
+ *    written.  Host arrays; returns after depth has arrived. */
+int pslfe_kf_scene_median_depth(pslfe_kf* k, const PslPose* Tcw, int K, const float* x, const int32_t* off, int q, float* depth);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

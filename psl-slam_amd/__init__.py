@@ -1323,6 +1323,7 @@ assert TRIQUERY_DTYPE.itemsize == 24 and LINEFUSEQUERY_DTYPE.itemsize == 24
 KFVIEW_DTYPE = np.dtype([("Tcw", POSE_DTYPE), ("T21", POSE_DTYPE), ("slot", "<i4")])
 assert KFVIEW_DTYPE.itemsize == 100
 KF_PROJ_FUSE, KF_PROJ_SCW, KF_PROJ_SIM3 = 0, 1, 2
+UPKEEP_SUM_WALK, UPKEEP_SUM_TILED = 0, 1   # PSLFE_UPKEEP_SUM_*: KeyFrameMatcher.set_upkeep_sum
 
 
 def _proj_args(cam, bounds, scale_factors, log_scale_factor, th):
@@ -1625,6 +1626,74 @@ class KeyFrameMatcher:
         _check(lib().pslfe_kf_distinctive_descriptors(self._h, _ptr(d), _ptr(off), C.c_int(npts), _ptr(best)),
                "pslfe_kf_distinctive_descriptors")
         return best[:npts]
+
+    def set_upkeep_sum(self, layout):
+        """The layout of the run-order sums of the refresh methods below: UPKEEP_SUM_WALK or UPKEEP_SUM_TILED (same bytes)."""
+        _check(lib().pslfe_kf_set_upkeep_sum(self._h, C.c_int(layout)), "pslfe_kf_set_upkeep_sum")
+
+    @staticmethod
+    def _upkeep_args(n, obs_off, obs_kf, centres, ref_kf, ref_level, scale_factors, skip, who):
+        off = np.ascontiguousarray(obs_off, np.int32).reshape(-1)
+        okf = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+        ow = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+        rk, rl = np.ascontiguousarray(ref_kf, np.int32).reshape(-1), np.ascontiguousarray(ref_level, np.int32).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(-1)
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        if len(off) != n + 1 or len(rk) != n or len(rl) != n or (sk is not None and len(sk) != n) or (n and len(okf) < off[-1]):
+            raise PslfeError(f"{who}: the offsets, references or skip bytes do not fit {n} rows")
+        keep = (off, okf, ow, rk, rl, sk, sf)
+        return keep, (_ptr(off), _ptr(okf), _ptr(ow), C.c_int(len(ow)), _ptr(rk), _ptr(rl), _ptr(sk), _ptr(sf), C.c_int(len(sf)))
+
+    def UpdateNormalAndDepth(self, mp, obs_off, obs_kf, centres, ref_kf, ref_level, scale_factors, skip=None):
+        """MapPoint::UpdateNormalAndDepth src/MapPoint.cc:330-371 for every row of mp (MAPPOINT_DTYPE[M]): row i is observed from the
+        camera centres centres[obs_kf[obs_off[i]:obs_off[i+1]]] in the caller's mObservations order; ref_kf / ref_level = mpRefKF and
+        the octave of its observation; scale_factors = mvScaleFactors.  -> a copy of mp with nx..max_dist refreshed; rows with an empty
+        run or a skip byte unchanged."""
+        g = np.array(mp, MAPPOINT_DTYPE).reshape(-1)
+        keep, a = self._upkeep_args(len(g), obs_off, obs_kf, centres, ref_kf, ref_level, scale_factors, skip, "UpdateNormalAndDepth")
+        _check(lib().pslfe_kf_update_normal_and_depth(self._h, _ptr(g), C.c_int(len(g)), *a), "pslfe_kf_update_normal_and_depth")
+        return g
+
+    def update_normal_and_depth_device(self, d_mp, M, d_obs_off, d_obs_kf, d_centres, nkf, d_ref_kf, d_ref_level, d_skip, scale_factors):
+        """The same on device addresses (d_skip 0 = none), in place, queued on the context's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        v = lambda d: C.c_void_p(d) if d else None
+        _check(lib().pslfe_kf_update_normal_and_depth_device(self._h, v(d_mp), C.c_int(M), v(d_obs_off), v(d_obs_kf), v(d_centres), C.c_int(nkf),
+                                                             v(d_ref_kf), v(d_ref_level), v(d_skip), _ptr(sf), C.c_int(len(sf))),
+               "pslfe_kf_update_normal_and_depth_device")
+
+    def LineUpdateAverageDir(self, ml, obs_off, obs_kf, centres, ref_kf, ref_level, scale_factors, skip=None):
+        """MapLine::UpdateAverageDir add_src/MapLine.cpp:320-367 for every row of ml (MAPLINE_DTYPE[M]), arguments as
+        UpdateNormalAndDepth; scale_factors = pRefKF->mvScaleFactors (the point table, as the reference reads it).
+        -> a copy of ml with normal, min_dist, max_dist refreshed."""
+        g = np.array(ml, MAPLINE_DTYPE).reshape(-1)
+        keep, a = self._upkeep_args(len(g), obs_off, obs_kf, centres, ref_kf, ref_level, scale_factors, skip, "LineUpdateAverageDir")
+        _check(lib().pslfe_kf_line_update_average_dir(self._h, _ptr(g), C.c_int(len(g)), *a), "pslfe_kf_line_update_average_dir")
+        return g
+
+    def line_update_average_dir_device(self, d_ml, M, d_obs_off, d_obs_kf, d_centres, nkf, d_ref_kf, d_ref_level, d_skip, scale_factors):
+        """The same on device addresses, in place, queued on the context's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        v = lambda d: C.c_void_p(d) if d else None
+        _check(lib().pslfe_kf_line_update_average_dir_device(self._h, v(d_ml), C.c_int(M), v(d_obs_off), v(d_obs_kf), v(d_centres), C.c_int(nkf),
+                                                             v(d_ref_kf), v(d_ref_level), v(d_skip), _ptr(sf), C.c_int(len(sf))),
+               "pslfe_kf_line_update_average_dir_device")
+
+    def ComputeSceneMedianDepth(self, poses, positions, q):
+        """KeyFrame::ComputeSceneMedianDepth(q) src/KeyFrame.cc:749-779 for K keyframes: poses POSE_DTYPE[K], positions[k] = the world
+        positions (n_k x 3) of keyframe k's map points.  -> depth float32[K]; -1 for a keyframe without map points."""
+        T = np.ascontiguousarray(poses, POSE_DTYPE).reshape(-1)
+        K = len(T)
+        if len(positions) != K:
+            raise PslfeError(f"ComputeSceneMedianDepth: {len(positions)} position lists for {K} keyframes")
+        xs = [np.ascontiguousarray(p, np.float32).reshape(-1, 3) for p in positions]
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(p) for p in xs])
+        x = np.concatenate(xs) if K else np.zeros((0, 3), np.float32)
+        depth = np.zeros(max(K, 1), np.float32)
+        _check(lib().pslfe_kf_scene_median_depth(self._h, _ptr(T), C.c_int(K), _ptr(x), _ptr(off), C.c_int(q), _ptr(depth)),
+               "pslfe_kf_scene_median_depth")
+        return depth[:K]
 
     def close(self):
         if self._h:

@@ -327,6 +327,7 @@ struct pslfe_frame {
 
 struct pslfe_kf {   // pslfe_kf.hip, pslfe_loop.hip: the per-call buffers come from the context's scratch arena
     pslfe_ctx* ctx = nullptr;
+    int upkeep_sum = PSLFE_UPKEEP_SUM_WALK;   // pslfe_map_upkeep.hip: the layout of the run-order sums (pslfe_kf_set_upkeep_sum)
 };
 
 // pslfe_match.hip, for pslfe_stereo.hip: frames of an extractor's result arrays (pointers at the first frame) -> slots

@@ -50,13 +50,18 @@ __device__ __forceinline__ void psl_centre(const PslPose& T, float* c) {
     for (int r = 0; r < 3; ++r) c[r] = -c[r];
 }
 
-// cv::norm of a float 3-vector: the double sum of squares in index order, sqrt in double, rounded to float
-__device__ __forceinline__ float psl_norm3(float p0, float p1, float p2) {
+// cv::norm of a float 3-vector as the double it returns: the double sum of the exact squares in index order, sqrt in double
+__device__ __forceinline__ double psl_norm3_d(float p0, float p1, float p2) {
     double s = PSL_DMUL((double)p0, (double)p0);
     s = PSL_DADD(s, PSL_DMUL((double)p1, (double)p1));
     s = PSL_DADD(s, PSL_DMUL((double)p2, (double)p2));
-    return (float)PSL_DSQRT(s);
+    return PSL_DSQRT(s);
 }
+// ... assigned to a float (`const float dist = cv::norm(PO)`)
+__device__ __forceinline__ float psl_norm3(float p0, float p1, float p2) { return (float)psl_norm3_d(p0, p1, p2); }
+
+// one component of 0.5*(SP+EP) on float Mats: the float sum of the exact halves, one rounding (include/pslfe.h above PslMapLineGeom)
+__device__ __forceinline__ float psl_half_sum(float a, float b) { return PSL_FADD(PSL_FMUL(0.5f, a), PSL_FMUL(0.5f, b)); }
 
 // Mat::dot of two float 3-vectors: the double sum in index order
 __device__ __forceinline__ double psl_dot3(float p0, float p1, float p2, float n0, float n1, float n2) {

@@ -54,7 +54,7 @@ __device__ bool psl_line_in_frustum(const double* sp, const double* ep, const do
     const float maxD = PSL_FMUL(1.2f, max_dist), minD = PSL_FMUL(0.8f, min_dist);
     float OM[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) OM[k] = PSL_FSUB(PSL_FADD(PSL_FMUL(0.5f, SP[k]), PSL_FMUL(0.5f, EP[k])), Ow[k]);
+    for (int k = 0; k < 3; ++k) OM[k] = PSL_FSUB(psl_half_sum(SP[k], EP[k]), Ow[k]);
     const float dist = psl_norm3(OM[0], OM[1], OM[2]);
     if (!(dist >= minD && dist <= maxD)) return false;
     const double dot = psl_dot3(OM[0], OM[1], OM[2], (float)nrm[0], (float)nrm[1], (float)nrm[2]);

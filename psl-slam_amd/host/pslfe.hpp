@@ -1082,7 +1082,59 @@ public:
         check(pslfe_kf_distinctive_descriptors(h_, desc.data(), offsets.data(), (int)best.size(), best.data()), "pslfe_kf_distinctive_descriptors");
         return best;
     }
+    // MapPoint::UpdateNormalAndDepth src/MapPoint.cc:330-371 for every row of mp, in place: row i is observed from the camera centres
+    // centres[3*obsKf[j]..] (KeyFrame::GetCameraCenter()), j in [obsOff[i], obsOff[i+1]), in the order in which mObservations iterates;
+    // refKf / refLevel = mpRefKF and the octave of its observation; scaleFactors = mvScaleFactors; skip (mbBad): one byte per row or
+    // empty.  Rows with an empty run or a skip byte keep every byte.
+    void UpdateNormalAndDepth(std::vector<PslMapPointGeom>& mp, const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKf,
+                              const std::vector<float>& centres, const std::vector<int32_t>& refKf, const std::vector<int32_t>& refLevel,
+                              const std::vector<uint8_t>& skip, const std::vector<float>& scaleFactors) {
+        checkUpkeep(mp.size(), obsOff, obsKf, refKf, refLevel, skip, "UpdateNormalAndDepth");
+        check(pslfe_kf_update_normal_and_depth(h_, mp.data(), (int)mp.size(), obsOff.data(), obsKf.data(), centres.data(), (int)centres.size() / 3,
+                                               refKf.data(), refLevel.data(), skip.empty() ? nullptr : skip.data(), scaleFactors.data(),
+                                               (int)scaleFactors.size()), "pslfe_kf_update_normal_and_depth");
+    }
+    // the same on device arrays, queued on the context's stream: the rows pslfe_orb_project_frustum_device reads, refreshed where they are
+    void UpdateNormalAndDepthDevice(PslMapPointGeom* d_mp, int M, const int32_t* d_obsOff, const int32_t* d_obsKf, const float* d_centres, int nkf,
+                                    const int32_t* d_refKf, const int32_t* d_refLevel, const uint8_t* d_skip,
+                                    const std::vector<float>& scaleFactors) {
+        check(pslfe_kf_update_normal_and_depth_device(h_, d_mp, M, d_obsOff, d_obsKf, d_centres, nkf, d_refKf, d_refLevel, d_skip,
+                                                      scaleFactors.data(), (int)scaleFactors.size()), "pslfe_kf_update_normal_and_depth_device");
+    }
+    // MapLine::UpdateAverageDir add_src/MapLine.cpp:320-367, arguments as UpdateNormalAndDepth; scaleFactors = pRefKF->mvScaleFactors,
+    // the point table, as the reference reads it
+    void LineUpdateAverageDir(std::vector<PslMapLineGeom>& ml, const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKf,
+                              const std::vector<float>& centres, const std::vector<int32_t>& refKf, const std::vector<int32_t>& refLevel,
+                              const std::vector<uint8_t>& skip, const std::vector<float>& scaleFactors) {
+        checkUpkeep(ml.size(), obsOff, obsKf, refKf, refLevel, skip, "LineUpdateAverageDir");
+        check(pslfe_kf_line_update_average_dir(h_, ml.data(), (int)ml.size(), obsOff.data(), obsKf.data(), centres.data(), (int)centres.size() / 3,
+                                               refKf.data(), refLevel.data(), skip.empty() ? nullptr : skip.data(), scaleFactors.data(),
+                                               (int)scaleFactors.size()), "pslfe_kf_line_update_average_dir");
+    }
+    void LineUpdateAverageDirDevice(PslMapLineGeom* d_ml, int M, const int32_t* d_obsOff, const int32_t* d_obsKf, const float* d_centres, int nkf,
+                                    const int32_t* d_refKf, const int32_t* d_refLevel, const uint8_t* d_skip,
+                                    const std::vector<float>& scaleFactors) {
+        check(pslfe_kf_line_update_average_dir_device(h_, d_ml, M, d_obsOff, d_obsKf, d_centres, nkf, d_refKf, d_refLevel, d_skip,
+                                                      scaleFactors.data(), (int)scaleFactors.size()), "pslfe_kf_line_update_average_dir_device");
+    }
+    // the layout of the run-order sums of the four refresh calls: PSLFE_UPKEEP_SUM_WALK or PSLFE_UPKEEP_SUM_TILED (same results)
+    void SetUpkeepSum(int layout) { check(pslfe_kf_set_upkeep_sum(h_, layout), "pslfe_kf_set_upkeep_sum"); }
+    // KeyFrame::ComputeSceneMedianDepth(q) src/KeyFrame.cc:749-779 for the keyframes Tcw[k]: keyframe k owns the world positions
+    // x[3*off[k] .. 3*off[k+1]) of its map points (off: K + 1 entries from 0); -1 for a keyframe without map points
+    std::vector<float> ComputeSceneMedianDepth(const std::vector<PslPose>& Tcw, const std::vector<float>& x, const std::vector<int32_t>& off, int q) {
+        if (off.size() != Tcw.size() + 1 || (size_t)off.back() * 3 > x.size())
+            throw Error(PSLFE_E_INVALID, "ComputeSceneMedianDepth: off needs K + 1 entries that stay inside x");
+        std::vector<float> depth(Tcw.size(), 0.f);
+        check(pslfe_kf_scene_median_depth(h_, Tcw.data(), (int)Tcw.size(), x.data(), off.data(), q, depth.data()), "pslfe_kf_scene_median_depth");
+        return depth;
+    }
 private:
+    static void checkUpkeep(size_t n, const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKf, const std::vector<int32_t>& refKf,
+                            const std::vector<int32_t>& refLevel, const std::vector<uint8_t>& skip, const char* who) {
+        if (obsOff.size() != n + 1 || refKf.size() != n || refLevel.size() != n || (!skip.empty() && skip.size() != n) ||
+            (size_t)obsOff.back() > obsKf.size())
+            throw Error(PSLFE_E_INVALID, std::string(who) + ": the offsets, references or skip bytes do not fit the rows");
+    }
     static void checkSkip(const std::vector<uint8_t>& skip, size_t n, const char* who) {
         if (!skip.empty() && skip.size() != n) throw Error(PSLFE_E_INVALID, std::string(who) + ": skip needs one byte per (keyframe, map point)");
     }
