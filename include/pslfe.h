@@ -1073,6 +1073,77 @@ int pslfe_kf_set_upkeep_sum(pslfe_kf* k, int layout);
  *    written.  Host arrays; returns after depth has arrived. */
 int pslfe_kf_scene_median_depth(pslfe_kf* k, const PslPose* Tcw, int K, const float* x, const int32_t* off, int q, float* depth);
 
+/* ---- Pose optimisation: the point edges of Optimizer::PoseOptimization (src/Optimizer.cc:239-1023) ----------------------------
+ * Called by TrackReferenceKeyFrame src/Tracking.cc:968, TrackWithMotionModel :1214, TrackLocalMap :1331 and, once per candidate,
+ * Relocalization :2130-2161.
+ *
+ * Scope: the monocular edges (EdgeSE3ProjectXYZOnlyPose) and the stereo edges (EdgeStereoSE3ProjectXYZOnlyPose).  The LIL edges
+ * (EdgeLILSE3ProjectXYZ with VertexLIL, src/Optimizer.cc:619-694, :973-1008) are not built and stay host code: the result is the
+ * reference's only for a frame whose mvpMapInsecs holds no live entry.
+ *
+ * Parity: g2o and Eigen cannot be built offline, so this stage is "HIP == restatement", parity with g2o unpinned.
+ * The restatement (tests/pose_opt_cases.py) follows g2o's algorithm in double, in the reference's order of decisions: the pose
+ * enters as Converter::toSE3Quat(mTcw) and leaves as Converter::toCvMat; information invSigma2 * I; Huber deltas (float)sqrt(5.991)
+ * and (float)sqrt(7.815); four rounds of up to 10 Levenberg iterations, each from the input pose (:719), each ended early by
+ * Terminate; tau = 1e-5, at most 10 trials after a failure, rho = (chi - chi_new) / (sum x_j (lambda x_j + b_j) + 1e-3), the factor
+ * 1 - (2 rho - 1)^3 clamped to [1/3, 2/3] or lambda *= ni, ni *= 2; Terminate after 10 failed trials, rho == 0, or three iterations
+ * in a row with (iniChi - chi) * 1e3 < iniChi; a non-finite trial chi2 rejects the step; after every round the plain chi2 of EVERY
+ * edge at the round's pose, as a float, against 5.991f / 7.815f sets the flag and the level of the next round; no robust kernel
+ * after round index 2; no further round when the frame has fewer than 10 edges (:1011).  A point behind the camera is not guarded
+ * in the reference and is not guarded here.  The 6x6 system is solved by LDLt without pivoting; a pivot that is not a finite positive
+ * number is "the solve failed": the trial's chi2 is DBL_MAX and the step is rejected.  The order of the sums over the edges is fixed
+ * by the edge index and the edge count alone (psl-slam_amd/csrc/pslfe_pose.hip), never by the batch. */
+/* One edge, in the order the reference creates them (keypoint order, :282-363). */
+typedef struct PslPoseEdge {
+    float u, v;         /* mvKeysUn[i].pt (:294, :329)                                                   */
+    float ur;           /* mvuRight[i]; < 0: a monocular edge (:288)                                     */
+    float inv_sigma2;   /* mvInvLevelSigma2[mvKeysUn[i].octave] (:301, :337)                             */
+    float x, y, z;      /* pMP->GetWorldPos() (:312-315, :350-353)                                       */
+} PslPoseEdge;
+/* What the optimisation of a frame did: rounds run (0..4) and the iterations of each (optimize()'s return value; 0 for a round
+ * that had no active edge or was not run). */
+typedef struct PslPoseInfo {
+    int32_t rounds;
+    int32_t iterations[4];
+} PslPoseInfo;
+/* == Optimizer::PoseOptimization src/Optimizer.cc:239-1023 (point edges) for nframes independent frames in one launch.  Frame f: pose
+ *    d_Tcw_in[f] (pFrame->mTcw), d_nedges[f] edges at d_edges + f*estride.  Outputs: d_Tcw_out[f] (the pose :1020 sets; d_Tcw_out
+ *    may alias d_Tcw_in), d_outlier [nframes][estride] bytes (mvbOutlier of the edge's keypoint, :739-775), d_ngood[f] (the return
+ *    value nInitialCorrespondences - nBad of the last executed round, :1022), d_info[f] (may be NULL).
+ *    Fewer than 3 edges (:696): d_ngood[f] = 0, d_Tcw_out[f] = d_Tcw_in[f], the outlier bytes are not written (the reference
+ *    clears mvbOutlier of those keypoints during the set-up, :291; a caller that needs this clears them).
+ *    d_nedges[f] > estride (an overflow that pslfe_pose_edges_from_matches_device reported): nothing is optimised on a truncated
+ *    set; d_ngood[f] = PSLFE_E_CAPACITY, d_Tcw_out[f] = d_Tcw_in[f].
+ *    nframes < 0, estride < 0, a NULL array with a non-zero count: PSLFE_E_INVALID; nframes == 0: PSLFE_OK, nothing is done.
+ *    A trial step whose rotation angle |omega| is not below 105414350 (the range of the restated sin / cos; NaN included) counts as a
+ *    failed solve.  cam: host (fx, fy, cx, cy, bf are read).  Asynchronous on the context's stream. */
+int pslfe_pose_optimize_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw_in, const PslPoseEdge* d_edges, const int32_t* d_nedges,
+                               int estride, const PslCamera* cam, PslPose* d_Tcw_out, uint8_t* d_outlier, int32_t* d_ngood,
+                               PslPoseInfo* d_info);
+/* Same for one frame, host arrays: outlier has room for nedges bytes and is an output only (never read; not written for fewer than
+ * 3 edges); returns after the results have arrived.  Tcw_out may be Tcw. */
+int pslfe_pose_optimize(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* edges, int nedges, const PslCamera* cam, PslPose* Tcw_out,
+                        uint8_t* outlier, int* ngood);
+/* == F.mvpMapPoints[bestIdx] = pMP of ORBmatcher::SearchByProjection(F, vpMapPoints, th) src/ORBmatcher.cc:127 for nframes frames, HBM to
+ *    HBM: the rows of pslfe_orb_project_frustum_device (d_owner[f][q] = the map point of row q, d_nq[f] rows) and the matches of
+ *    pslfe_orb_search_by_projection_map_device (d_match[f][q] = the keypoint row q took, or -1), both with row stride qstride, become
+ *    d_mp_index [nframes][frame's keypoint capacity]: the map point of every keypoint, -1 for a keypoint without one.  Where two rows
+ *    took one keypoint the later row stays, as the reference's assignment overwrites.  This is the array
+ *    pslfe_pose_edges_from_matches_device reads.  nframes < 0, qstride < 0 or a NULL array: PSLFE_E_INVALID; nframes == 0: PSLFE_OK.
+ *    Asynchronous on the frame's context stream. */
+int pslfe_pose_mp_index_from_matches_device(pslfe_frame* frame, int nframes, const int32_t* d_match, const int32_t* d_owner, const int32_t* d_nq,
+                                            int qstride, int32_t* d_mp_index);
+/* == The edge set-up loop src/Optimizer.cc:282-363 from the matches of nframes frames, HBM to HBM: d_mp_index[f][i] (row stride
+ *    frame's keypoint capacity) is the row in frame f's PslMapPointGeom array (d_mp + f*mpstride) of keypoint i's map point
+ *    (pFrame->mvpMapPoints[i]), or -1; an index outside [0, mpstride) counts as -1.  mvKeysUn, mvuRight and the octave come from slot
+ *    slot0 + f; inv_level_sigma2: host array of nlevels (mvInvLevelSigma2).  The edges are compacted in keypoint order at
+ *    d_edges + f*estride, d_edge_kp (may be NULL) gets the keypoint of each edge.  d_nedges[f] is the full count: a count above
+ *    estride is reported, never truncated silently (the first estride rows are written).  Asynchronous on the frame's context
+ *    stream.  With it the chain projection -> search -> pose -> next projection needs no host copy. */
+int pslfe_pose_edges_from_matches_device(pslfe_frame* frame, int slot0, int nframes, const int32_t* d_mp_index, const PslMapPointGeom* d_mp,
+                                         int mpstride, const float* inv_level_sigma2, int nlevels, PslPoseEdge* d_edges, int32_t* d_edge_kp,
+                                         int32_t* d_nedges, int estride);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

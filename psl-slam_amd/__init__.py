@@ -35,6 +35,10 @@ LASTPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("state", 
 MAPPOINT_DTYPE = np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz", "min_dist", "max_dist")])
 assert POSE_DTYPE.itemsize == 48 and LASTPOINT_DTYPE.itemsize == 16 and MAPPOINT_DTYPE.itemsize == 32
 LASTPOINT_NONE, LASTPOINT_NO_OBS, LASTPOINT_OBS, LASTPOINT_OUTLIER = 0, 1, 2, 8
+# pose optimisation (include/pslfe.h: PslPoseEdge, PslPoseInfo)
+POSEEDGE_DTYPE = np.dtype([(k, "<f4") for k in ("u", "v", "ur", "inv_sigma2", "x", "y", "z")])
+POSEINFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (4,))])
+assert POSEEDGE_DTYPE.itemsize == 28 and POSEINFO_DTYPE.itemsize == 20
 
 
 def pose(Tcw):
@@ -625,6 +629,57 @@ def search_by_projection_map_device(frame, slot0, npairs, d_queries, d_qdesc, d_
         frame._h, C.c_int(slot0), C.c_int(npairs), C.c_void_p(d_queries), C.c_void_p(d_qdesc), C.c_void_p(d_nq), C.c_int(qstride),
         C.c_void_p(d_taken or None), C.c_float(nnratio), C.c_void_p(d_match), C.c_void_p(d_nmatches)),
         "pslfe_orb_search_by_projection_map_device")
+
+
+class Optimizer:
+    """Optimizer::PoseOptimization src/Optimizer.cc:239-1023, the point edges (EdgeSE3ProjectXYZOnlyPose and
+    EdgeStereoSE3ProjectXYZOnlyPose).  The LIL edges (:619-694, :973-1008) stay host code: the result is the reference's only for a
+    frame whose mvpMapInsecs holds no live entry.  Parity with g2o itself is unpinned."""
+
+    @staticmethod
+    def PoseOptimization(Tcw, edges, cam, ctx=None):
+        """One frame, host arrays: Tcw a POSE_DTYPE record (pFrame->mTcw), edges POSEEDGE_DTYPE[n] in keypoint order.
+        -> (ngood = the return value, Tcw_out, outlier u8 [n] = mvbOutlier of each edge's keypoint).  Fewer than 3 edges: (0, Tcw,
+        zeros), as the reference leaves them (:291, :696)."""
+        ctx = ctx or default_context()
+        T = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
+        e = np.ascontiguousarray(edges, POSEEDGE_DTYPE)
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        out = np.zeros(1, POSE_DTYPE)
+        outlier = np.zeros(max(len(e), 1), np.uint8)
+        ng = C.c_int()
+        _check(lib().pslfe_pose_optimize(ctx._h, _ptr(T), _ptr(e) if len(e) else None, C.c_int(len(e)), _ptr(cam), _ptr(out),
+                                         _ptr(outlier) if len(e) else None, C.byref(ng)), "pslfe_pose_optimize")
+        return ng.value, out[0], outlier[:len(e)]
+
+    @staticmethod
+    def PoseOptimizationDevice(nframes, d_Tcw_in, d_edges, d_nedges, estride, cam, d_Tcw_out, d_outlier, d_ngood, d_info=0, ctx=None):
+        """nframes independent frames in one launch, HBM to HBM, asynchronous; all d_* are device addresses (ints; d_info may be 0,
+        d_Tcw_out may be d_Tcw_in).  d_ngood[f] = PSLFE_E_CAPACITY (-4) for a frame whose count exceeds estride."""
+        ctx = ctx or default_context()
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_pose_optimize_device(ctx._h, C.c_int(nframes), C.c_void_p(d_Tcw_in or None), C.c_void_p(d_edges or None),
+                                                C.c_void_p(d_nedges or None), C.c_int(estride), _ptr(cam), C.c_void_p(d_Tcw_out or None),
+                                                C.c_void_p(d_outlier or None), C.c_void_p(d_ngood or None), C.c_void_p(d_info or None)),
+               "pslfe_pose_optimize_device")
+
+    @staticmethod
+    def MapPointIndexFromMatchesDevice(frame, nframes, d_match, d_owner, d_nq, qstride, d_mp_index):
+        """F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:127) on the device: the owner rows of project_frustum_device and the matches
+        of search_by_projection_map_device -> d_mp_index [nframes][frame capacity], the array EdgesFromMatchesDevice reads."""
+        _check(lib().pslfe_pose_mp_index_from_matches_device(frame._h, C.c_int(nframes), C.c_void_p(d_match or None), C.c_void_p(d_owner or None),
+                                                             C.c_void_p(d_nq or None), C.c_int(qstride), C.c_void_p(d_mp_index or None)),
+               "pslfe_pose_mp_index_from_matches_device")
+
+    @staticmethod
+    def EdgesFromMatchesDevice(frame, slot0, nframes, d_mp_index, d_mp, mpstride, inv_level_sigma2, d_edges, d_edge_kp, d_nedges, estride):
+        """The edge set-up loop :282-363 on the device: d_mp_index [nframes][frame capacity] = the PslMapPointGeom row of each
+        keypoint's map point or -1; edges compacted in keypoint order; d_nedges[f] = the full count, also above estride."""
+        s2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        _check(lib().pslfe_pose_edges_from_matches_device(
+            frame._h, C.c_int(slot0), C.c_int(nframes), C.c_void_p(d_mp_index or None), C.c_void_p(d_mp or None), C.c_int(mpstride), _ptr(s2),
+            C.c_int(len(s2)), C.c_void_p(d_edges or None), C.c_void_p(d_edge_kp or None), C.c_void_p(d_nedges or None), C.c_int(estride)),
+            "pslfe_pose_edges_from_matches_device")
 
 
 class LINEextractor:

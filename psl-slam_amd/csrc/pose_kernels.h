@@ -1,0 +1,338 @@
+// The per-edge arithmetic, the 6x6 solve and the SE3 update of the pose optimisation (pslfe_pose.hip), as functions of one thread.
+// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp for its host loop, so both
+// run the same single IEEE operations (build with -ffp-contract=off).  Restated from the reference's g2o:
+//   edge errors / Jacobians   Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp} (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose)
+//   SE3Quat, exp, product     Thirdparty/g2o/g2o/types/se3quat.h, se3_ops.hpp
+//   quadratic form, Huber     Thirdparty/g2o/g2o/core/base_unary_edge.hpp, robust_kernel_impl.cpp
+// Eigen is not in the reference tree, so where g2o hands a step to Eigen (quaternion <-> matrix, quaternion * vector, the products
+// of small matrices) the order written here is this library's: sums run in index order, left to right.  DESIGN.md §3, §5.0k.
+#ifndef PSL_POSE_KERNELS_H
+#define PSL_POSE_KERNELS_H
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define PSL_PO_HD __host__ __device__ static inline
+#else
+#define PSL_PO_HD static inline
+#endif
+#include <stdint.h>
+
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+
+#ifndef PSL_SC64_QUAL
+#define PSL_SC64_QUAL PSL_PO_HD
+#endif
+#include "psl_sincos_glibc.h"
+
+// division and square root: the correctly rounded device intrinsics, as csrc/proj_kernels.h takes them
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PSL_PO_DIV(a, b) __ddiv_rn((a), (b))
+#define PSL_PO_SQRT(a) __dsqrt_rn(a)
+#else
+#define PSL_PO_DIV(a, b) ((a) / (b))
+#define PSL_PO_SQRT(a) __builtin_sqrt(a)
+#endif
+
+#define PSL_POSE_NTERMS 28   // per edge: the 21 upper-triangle values of H row by row, the 6 of b (before the sign), the robust chi2
+#define PSL_POSE_LANES 256   // partial sums of the ordered reduction (the header of pslfe_pose.hip)
+#define PSL_POSE_GROUP 64    // partial sums of one butterfly
+
+struct PslSE3 {
+    double q[4];   // x y z w
+    double t[3];
+};
+
+struct PslPoseCamD {
+    double fx, fy, cx, cy, bf;
+};
+
+// Huber deltas as Optimizer.cc:274-275 holds them: `const float deltaMono = sqrt(5.991)`, a double root rounded to float
+#define PSL_POSE_DELTA_MONO 2.4476518630981445   /* (float)sqrt(5.991) */
+#define PSL_POSE_DELTA_STEREO 2.7955322265625     /* (float)sqrt(7.815) */
+
+PSL_PO_HD void psl_po_cross(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// SE3Quat::normalizeRotation (se3quat.h:284-289)
+PSL_PO_HD void psl_po_normalize(double* q) {
+    if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
+    const double n = PSL_PO_SQRT(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    q[0] = PSL_PO_DIV(q[0], n); q[1] = PSL_PO_DIV(q[1], n); q[2] = PSL_PO_DIV(q[2], n); q[3] = PSL_PO_DIV(q[3], n);
+}
+
+// Quaterniond(R): the branch on the trace and the largest diagonal entry
+PSL_PO_HD void psl_po_quat_from_R(const double* R, double* q) {
+    double t = (R[0] + R[4]) + R[8];
+    if (t > 0) {
+        t = PSL_PO_SQRT(t + 1.0);
+        q[3] = 0.5 * t;
+        t = PSL_PO_DIV(0.5, t);
+        q[0] = (R[7] - R[5]) * t;
+        q[1] = (R[2] - R[6]) * t;
+        q[2] = (R[3] - R[1]) * t;
+    } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > (i ? R[4] : R[0])) i = 2;
+        // i, j = (i + 1) % 3, k = (j + 1) % 3: q[i] = t / 2, w = (R(k,j) - R(j,k)) t', q[j] = (R(j,i) + R(i,j)) t', q[k] = (R(k,i) + R(i,k)) t'
+        if (i == 0) {
+            t = PSL_PO_SQRT(((R[0] - R[4]) - R[8]) + 1.0);
+            q[0] = 0.5 * t; t = PSL_PO_DIV(0.5, t);
+            q[3] = (R[7] - R[5]) * t; q[1] = (R[3] + R[1]) * t; q[2] = (R[6] + R[2]) * t;
+        } else if (i == 1) {
+            t = PSL_PO_SQRT(((R[4] - R[8]) - R[0]) + 1.0);
+            q[1] = 0.5 * t; t = PSL_PO_DIV(0.5, t);
+            q[3] = (R[2] - R[6]) * t; q[2] = (R[7] + R[5]) * t; q[0] = (R[1] + R[3]) * t;
+        } else {
+            t = PSL_PO_SQRT(((R[8] - R[0]) - R[4]) + 1.0);
+            q[2] = 0.5 * t; t = PSL_PO_DIV(0.5, t);
+            q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
+        }
+    }
+}
+
+// Quaterniond::toRotationMatrix
+PSL_PO_HD void psl_po_quat_to_R(const double* q, double* R) {
+    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
+    R[3] = txy + twz;         R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
+}
+
+// Quaterniond * Vector3d: uv = 2 (q.vec x v); v + w uv + q.vec x uv
+PSL_PO_HD void psl_po_rotate(const double* q, const double* v, double* o) {
+    double uv[3], c[3];
+    psl_po_cross(q, v, uv);
+    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
+    psl_po_cross(q, uv, c);
+    o[0] = (v[0] + q[3] * uv[0]) + c[0];
+    o[1] = (v[1] + q[3] * uv[1]) + c[1];
+    o[2] = (v[2] + q[3] * uv[2]) + c[2];
+}
+
+// Converter::toSE3Quat(mTcw): float -> double, SE3Quat(R, t) (se3quat.h:58-60)
+PSL_PO_HD void psl_po_from_pose(const float* R9, const float* t3, PslSE3* T) {
+    double R[9];
+    for (int i = 0; i < 9; ++i) R[i] = (double)R9[i];
+    psl_po_quat_from_R(R, T->q);
+    psl_po_normalize(T->q);
+    for (int i = 0; i < 3; ++i) T->t[i] = (double)t3[i];
+}
+
+// Converter::toCvMat(SE3Quat): to_homogeneous_matrix, double -> float
+PSL_PO_HD void psl_po_to_pose(const PslSE3* T, float* R9, float* t3) {
+    double R[9];
+    psl_po_quat_to_R(T->q, R);
+    for (int i = 0; i < 9; ++i) R9[i] = (float)R[i];
+    for (int i = 0; i < 3; ++i) t3[i] = (float)T->t[i];
+}
+
+// a 3x3 product, every entry (a0 b0 + a1 b1) + a2 b2
+PSL_PO_HD void psl_po_mat3mul(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) C[3 * i + k] = (A[3 * i] * B[k] + A[3 * i + 1] * B[3 + k]) + A[3 * i + 2] * B[6 + k];
+}
+
+// SE3Quat::exp (se3quat.h:227-261): x = (omega, upsilon); tab: the table of psl_sincos_glibc.h
+PSL_PO_HD void psl_po_exp(const double* x, PslSE3* T, const double* tab) {
+    const double theta = PSL_PO_SQRT((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    const double O[9] = {0.0, -x[2], x[1], x[2], 0.0, -x[0], -x[1], x[0], 0.0};
+    double O2[9], R[9], V[9];
+    psl_po_mat3mul(O, O, O2);
+    if (theta < 0.00001) {
+        for (int i = 0; i < 9; ++i) {
+            R[i] = (((i % 4) == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
+            V[i] = R[i];
+        }
+    } else {
+        const double s = psl_glibc_sin(theta, tab), c = psl_glibc_cos(theta, tab);
+        const double th2 = theta * theta;
+        const double a = PSL_PO_DIV(s, theta), b = PSL_PO_DIV(1.0 - c, th2), g = PSL_PO_DIV(theta - s, th2 * theta);
+        for (int i = 0; i < 9; ++i) {
+            const double I = (i % 4) == 0 ? 1.0 : 0.0;
+            R[i] = (I + a * O[i]) + b * O2[i];
+            V[i] = (I + b * O[i]) + g * O2[i];
+        }
+    }
+    psl_po_quat_from_R(R, T->q);
+    psl_po_normalize(T->q);
+    for (int i = 0; i < 3; ++i) T->t[i] = (V[3 * i] * x[3] + V[3 * i + 1] * x[4]) + V[3 * i + 2] * x[5];
+}
+
+// SE3Quat::operator* (se3quat.h:104-110): A * B
+PSL_PO_HD void psl_po_mul(const PslSE3* A, const PslSE3* B, PslSE3* C) {
+    double r[3];
+    psl_po_rotate(A->q, B->t, r);
+    const double *a = A->q, *b = B->q;
+    double q[4];
+    q[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
+    q[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
+    q[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
+    q[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+    psl_po_normalize(q);
+    for (int i = 0; i < 4; ++i) C->q[i] = q[i];
+    for (int i = 0; i < 3; ++i) C->t[i] = A->t[i] + r[i];
+}
+
+// computeError of both edges at pose T: e (e[2] = 0 for a monocular edge), the camera point Pc; returns 1 for a monocular edge.
+// E: u v ur inv_sigma2 x y z.  The stereo projection keeps its `const float invz` (types_six_dof_expmap.cpp:300).
+PSL_PO_HD int psl_po_error(const float* E, const PslSE3* T, const PslPoseCamD* K, double* e, double* Pc) {
+    const double Xw[3] = {(double)E[4], (double)E[5], (double)E[6]};
+    double r[3];
+    psl_po_rotate(T->q, Xw, r);
+    Pc[0] = r[0] + T->t[0]; Pc[1] = r[1] + T->t[1]; Pc[2] = r[2] + T->t[2];
+    const int mono = E[2] < 0.f;
+    if (mono) {
+        e[0] = (double)E[0] - (PSL_PO_DIV(Pc[0], Pc[2]) * K->fx + K->cx);
+        e[1] = (double)E[1] - (PSL_PO_DIV(Pc[1], Pc[2]) * K->fy + K->cy);
+        e[2] = 0.0;
+    } else {
+        const double invz = (double)(float)PSL_PO_DIV(1.0, Pc[2]);
+        const double r0 = (Pc[0] * invz) * K->fx + K->cx;
+        e[0] = (double)E[0] - r0;
+        e[1] = (double)E[1] - ((Pc[1] * invz) * K->fy + K->cy);
+        e[2] = (double)E[2] - (r0 - K->bf * invz);
+    }
+    return mono;
+}
+
+// chi2 = e . (invSigma2 I) e
+PSL_PO_HD double psl_po_chi2(const double* e, double is2, int mono) {
+    const double c = e[0] * (is2 * e[0]) + e[1] * (is2 * e[1]);
+    return mono ? c : c + e[2] * (is2 * e[2]);
+}
+
+// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-92): rho(chi2) and rho'(chi2)
+PSL_PO_HD void psl_po_huber(double chi2, int mono, double* rho0, double* rho1) {
+    const double delta = mono ? PSL_POSE_DELTA_MONO : PSL_POSE_DELTA_STEREO;
+    const double dsqr = delta * delta;
+    if (chi2 <= dsqr) { *rho0 = chi2; *rho1 = 1.0; }
+    else {
+        const double sq = PSL_PO_SQRT(chi2);
+        *rho0 = (2.0 * sq) * delta - dsqr;
+        *rho1 = PSL_PO_DIV(delta, sq);
+    }
+}
+
+// linearizeOplus (types_six_dof_expmap.cpp:266-288, :335-364) and constructQuadraticForm (base_unary_edge.hpp:43-72) of one edge:
+// adds its 28 terms to acc.  w = rho' * invSigma2 weighs both H and b.
+PSL_PO_HD void psl_po_add_terms(const double* e, const double* Pc, int mono, double is2, double rho0, double rho1, const PslPoseCamD* K,
+                                double* acc) {
+    const double x = Pc[0], y = Pc[1], invz = PSL_PO_DIV(1.0, Pc[2]), invz2 = invz * invz;
+    double J[3][6];
+    J[0][0] = ((x * y) * invz2) * K->fx;
+    J[0][1] = (-(1.0 + (x * x) * invz2)) * K->fx;
+    J[0][2] = (y * invz) * K->fx;
+    J[0][3] = (-invz) * K->fx;
+    J[0][4] = 0.0;
+    J[0][5] = (x * invz2) * K->fx;
+    J[1][0] = (1.0 + (y * y) * invz2) * K->fy;
+    J[1][1] = (((-x) * y) * invz2) * K->fy;
+    J[1][2] = ((-x) * invz) * K->fy;
+    J[1][3] = 0.0;
+    J[1][4] = (-invz) * K->fy;
+    J[1][5] = (y * invz2) * K->fy;
+    J[2][0] = J[0][0] - (K->bf * y) * invz2;
+    J[2][1] = J[0][1] + (K->bf * x) * invz2;
+    J[2][2] = J[0][2];
+    J[2][3] = J[0][3];
+    J[2][4] = 0.0;
+    J[2][5] = J[0][5] - K->bf * invz2;
+    const double w = rho1 * is2;
+    int h = 0;
+    for (int j = 0; j < 6; ++j) {
+        const double w0 = w * J[0][j], w1 = w * J[1][j], w2 = w * J[2][j];
+        for (int k = j; k < 6; ++k, ++h) {
+            const double s = w0 * J[0][k] + w1 * J[1][k];
+            acc[h] = acc[h] + (mono ? s : s + w2 * J[2][k]);
+        }
+        const double s = w0 * e[0] + w1 * e[1];
+        acc[21 + j] = acc[21 + j] + (mono ? s : s + w2 * e[2]);
+    }
+    acc[27] = acc[27] + rho0;
+}
+
+// (H + lambda I) x = b by LDLt without pivoting; H: the 21 upper-triangle values row by row.  Returns 0 - "the solve failed" - when a
+// pivot is not a finite positive number (the matrix is then not positive definite to working precision); x is not written then.
+PSL_PO_HD int psl_po_solve6(const double* H, double lambda, const double* b, double* x) {
+    double A[6][6], L[6][6], D[6], y[6];
+    int h = 0;
+    for (int j = 0; j < 6; ++j)
+        for (int k = j; k < 6; ++k, ++h) { A[j][k] = H[h]; A[k][j] = H[h]; }
+    for (int j = 0; j < 6; ++j) A[j][j] = A[j][j] + lambda;
+    int ok = 1;
+    for (int j = 0; j < 6; ++j) {
+        double d = A[j][j];
+        for (int k = 0; k < j; ++k) d = d - L[j][k] * (L[j][k] * D[k]);
+        if (!(d > 0.0) || !(d <= 1.79769313486231570815e+308)) ok = 0;
+        D[j] = d;
+        for (int i = j + 1; i < 6; ++i) {
+            double s = A[i][j];
+            for (int k = 0; k < j; ++k) s = s - L[i][k] * (L[j][k] * D[k]);
+            L[i][j] = PSL_PO_DIV(s, d);
+        }
+    }
+    if (!ok) return 0;
+    for (int i = 0; i < 6; ++i) {
+        double s = b[i];
+        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+        y[i] = s;
+    }
+    for (int i = 5; i >= 0; --i) {
+        double s = PSL_PO_DIV(y[i], D[i]);
+        for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
+        x[i] = s;
+    }
+    return 1;
+}
+
+// The rotation angle of a step, |omega|, must lie inside the range of psl_glibc_sin / psl_glibc_cos (their table index is not
+// clamped).  A step outside it - or a NaN one - only comes from non-physical data and counts as "the solve failed".
+#define PSL_POSE_THETA_MAX 105414350.0
+PSL_PO_HD int psl_po_step_ok(const double* x) {
+    const double theta = PSL_PO_SQRT((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    return theta < PSL_POSE_THETA_MAX;
+}
+
+// The state of OptimizationAlgorithmLevenberg between two solves of a round (optimization_algorithm_levenberg.cpp)
+struct PslPoseLM {
+    double lambda, ni;
+    int nbad;
+};
+
+// computeLambdaInit (:166-180): tau * max |H_jj|
+PSL_PO_HD double psl_po_lambda_init(const double* H) {
+    double m = 0.0;
+    int h = 0;
+    for (int j = 0; j < 6; h += 6 - j, ++j) {
+        const double a = __builtin_fabs(H[h]);
+        m = a < m ? m : a;   // std::max(fabs(h), m)
+    }
+    return 1e-5 * m;
+}
+
+// rho of one trial (:129-132): (chi - chi_new) / (sum x_j (lambda x_j + b_j) + 1e-3)
+PSL_PO_HD double psl_po_rho(double chi, double chi_new, const double* x, const double* b, double lambda) {
+    double scale = 0.0;
+    for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lambda * x[j] + b[j]);
+    scale = scale + 1e-3;
+    return PSL_PO_DIV(chi - chi_new, scale);
+}
+
+// the lambda factor of an accepted step (:135-139): 1 - (2 rho - 1)^3 clamped to [1/3, 2/3]; the cube is two products
+PSL_PO_HD double psl_po_good_scale(double rho) {
+    const double t = 2.0 * rho - 1.0;
+    double alpha = 1.0 - (t * t) * t;
+    alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;    // std::min(alpha, upper)
+    return (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);     // std::max(lower, alpha)
+}
+
+#endif

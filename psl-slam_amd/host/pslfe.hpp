@@ -1141,5 +1141,43 @@ private:
     pslfe_kf* h_ = nullptr;
 };
 
+// == Optimizer (include/Optimizer.h:58): the point edges of PoseOptimization, src/Optimizer.cc:239-1023.  The LIL edges (:619-694,
+//    :973-1008) are not built: the result is the reference's only for a frame whose mvpMapInsecs holds no live entry, and a caller
+//    with live entries keeps the host g2o call.  Parity with g2o itself is unpinned.
+class Optimizer {
+public:
+    // int Optimizer::PoseOptimization(Frame* pFrame): edges = one PslPoseEdge per non-NULL pFrame->mvpMapPoints[i] in keypoint order
+    // (:282-363); Tcw = pFrame->mTcw, replaced by the pose :1020 sets; outlier[e] = mvbOutlier of the edge's keypoint; returns
+    // nInitialCorrespondences - nBad.  Fewer than 3 edges: returns 0, Tcw unchanged, outlier all false (:291, :696).
+    static int PoseOptimization(Context& ctx, PslPose& Tcw, const std::vector<PslPoseEdge>& edges, const PslCamera& cam,
+                                std::vector<uint8_t>& outlier) {
+        outlier.assign(edges.size(), 0);
+        int ngood = 0;
+        check(pslfe_pose_optimize(ctx.get(), &Tcw, edges.data(), (int)edges.size(), &cam, &Tcw, outlier.data(), &ngood), "pslfe_pose_optimize");
+        return ngood;
+    }
+    // K frames in one launch, HBM to HBM, asynchronous on the context's stream (the many-frames mode): pslfe_pose_optimize_device
+    static void PoseOptimizationDevice(Context& ctx, int nframes, const PslPose* d_TcwIn, const PslPoseEdge* d_edges, const int32_t* d_nedges,
+                                       int estride, const PslCamera& cam, PslPose* d_TcwOut, uint8_t* d_outlier, int32_t* d_ngood,
+                                       PslPoseInfo* d_info = nullptr) {
+        check(pslfe_pose_optimize_device(ctx.get(), nframes, d_TcwIn, d_edges, d_nedges, estride, &cam, d_TcwOut, d_outlier, d_ngood, d_info),
+              "pslfe_pose_optimize_device");
+    }
+    // F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:127) for nframes frames, HBM to HBM: pslfe_pose_mp_index_from_matches_device
+    static void MapPointIndexFromMatchesDevice(FrameGrid& frame, int nframes, const int32_t* d_match, const int32_t* d_owner, const int32_t* d_nq,
+                                               int qstride, int32_t* d_mpIndex) {
+        check(pslfe_pose_mp_index_from_matches_device(frame.get(), nframes, d_match, d_owner, d_nq, qstride, d_mpIndex),
+              "pslfe_pose_mp_index_from_matches_device");
+    }
+    // the edge set-up loop :282-363 from the matches of nframes frames, HBM to HBM: pslfe_pose_edges_from_matches_device
+    static void EdgesFromMatchesDevice(FrameGrid& frame, int slot0, int nframes, const int32_t* d_mpIndex, const PslMapPointGeom* d_mp, int mpStride,
+                                       const std::vector<float>& invLevelSigma2, PslPoseEdge* d_edges, int32_t* d_edgeKp, int32_t* d_nedges,
+                                       int estride) {
+        check(pslfe_pose_edges_from_matches_device(frame.get(), slot0, nframes, d_mpIndex, d_mp, mpStride, invLevelSigma2.data(),
+                                                   (int)invLevelSigma2.size(), d_edges, d_edgeKp, d_nedges, estride),
+              "pslfe_pose_edges_from_matches_device");
+    }
+};
+
 }  // namespace pslfe
 #endif
