@@ -1073,13 +1073,14 @@ int pslfe_kf_set_upkeep_sum(pslfe_kf* k, int layout);
  *    written.  Host arrays; returns after depth has arrived. */
 int pslfe_kf_scene_median_depth(pslfe_kf* k, const PslPose* Tcw, int K, const float* x, const int32_t* off, int q, float* depth);
 
-/* ---- Pose optimisation: the point edges of Optimizer::PoseOptimization (src/Optimizer.cc:239-1023) ----------------------------
+/* ---- Pose optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:239-1023), point edges and LIL edges ------------------
  * Called by TrackReferenceKeyFrame src/Tracking.cc:968, TrackWithMotionModel :1214, TrackLocalMap :1331 and, once per candidate,
  * Relocalization :2130-2161.
  *
- * Scope: the monocular edges (EdgeSE3ProjectXYZOnlyPose) and the stereo edges (EdgeStereoSE3ProjectXYZOnlyPose).  The LIL edges
- * (EdgeLILSE3ProjectXYZ with VertexLIL, src/Optimizer.cc:619-694, :973-1008) are not built and stay host code: the result is the
- * reference's only for a frame whose mvpMapInsecs holds no live entry.
+ * Scope: the monocular edges (EdgeSE3ProjectXYZOnlyPose), the stereo edges (EdgeStereoSE3ProjectXYZOnlyPose) and the LIL edges
+ * (EdgeLILSE3ProjectXYZ with its fixed VertexLIL, add_inc/EdgeLIL.h:210-439, src/Optimizer.cc:619-694, :973-1008): every edge the
+ * function creates.  pslfe_pose_optimize[_device] take point edges only and are the reference's for a frame without live
+ * mvpMapInsecs entries; pslfe_pose_optimize_lil[_device] take both kinds.
  *
  * Parity: g2o and Eigen cannot be built offline, so this stage is "HIP == restatement", parity with g2o unpinned.
  * The restatement (tests/pose_opt_cases.py) follows g2o's algorithm in double, in the reference's order of decisions: the pose
@@ -1143,6 +1144,61 @@ int pslfe_pose_mp_index_from_matches_device(pslfe_frame* frame, int nframes, con
 int pslfe_pose_edges_from_matches_device(pslfe_frame* frame, int slot0, int nframes, const int32_t* d_mp_index, const PslMapPointGeom* d_mp,
                                          int mpstride, const float* inv_level_sigma2, int nlevels, PslPoseEdge* d_edges, int32_t* d_edge_kp,
                                          int32_t* d_nedges, int estride);
+/* One LIL edge (EdgeLILSE3ProjectXYZ with its fixed VertexLIL, add_inc/EdgeLIL.h:210-439), in the order the reference creates them
+ * (plane order, src/Optimizer.cc:631-693).  All double, as the reference holds them. */
+typedef struct PslPoseLilEdge {
+    double line1[6];    /* pLIL->line1: start, end (:639-640, :679-680)                                  */
+    double line2[6];    /* pLIL->line2: start, end (:641-642, :681-682)                                  */
+    double cross[3];    /* pLIL->crosspoint (:643, :683)                                                 */
+    double obs1[3];     /* pFrame->mvle_l[i].first (:658, :685)                                          */
+    double obs2[3];     /* pFrame->mvle_l[i].second (:659, :686)                                         */
+    double obs_ins[2];  /* pFrame->CrossPoint_2D[i] (:660)                                               */
+} PslPoseLilEdge;
+/* A map LIL (InsectLine) as the set-up loop reads it: line1, line2, crosspoint (15 doubles, :639-643) and mbBad (:634). */
+typedef struct PslMapLil {
+    double w[15];
+    uint8_t bad;
+    uint8_t pad[7];
+} PslMapLil;
+#ifdef __cplusplus
+static_assert(sizeof(PslPoseLilEdge) == 184 && sizeof(PslMapLil) == 128, "LIL PODs");
+#else
+_Static_assert(sizeof(PslPoseLilEdge) == 184 && sizeof(PslMapLil) == 128, "LIL PODs");
+#endif
+/* == Optimizer::PoseOptimization src/Optimizer.cc:239-1023 whole: the point edges as in pslfe_pose_optimize_device plus the LIL
+ *    edges (:619-694, the classification :973-1008).  Frame f has d_nlil[f] LIL edges at d_lil + f*lstride; LIL edge j has the edge
+ *    index d_nedges[f] + j (g2o adds them after the point edges), which fixes its place in the order of the sums.
+ *    d_outlier_lil [nframes][lstride] bytes: mvbOutlier_Insec of the edge's plane ((float)chi2 > 11.07f, :993-1004).  Error
+ *    (EdgeLIL.h:220-256), Jacobian (_jacobianOplusXj :339-379; row 2 is evaluated at line 2's END point, :273-275, as the
+ *    reference does), information 1.0 (:241, :668), Huber delta (float)sqrt(11.07) (:628), no robust kernel after round index 2 (:1006).
+ *    The `< 3` early return (:696) and the `< 10` rule (:1011) count point and LIL edges together.  d_ngood[f] =
+ *    nInitialCorrespondences - nBad (:1022): the LIL edges are in the first number, nBad counts point edges only, so an outlying LIL
+ *    edge counts as good.  Fewer than 3 edges in total: d_ngood[f] = 0, the pose is copied, no outlier byte of either kind is
+ *    written.  d_nedges[f] > estride or d_nlil[f] > lstride: d_ngood[f] = PSLFE_E_CAPACITY, the pose is copied, nothing is optimised.
+ *    A negative d_nedges[f] or d_nlil[f] (an error code that pslfe_pose_lil_edges_device left there, for instance): d_ngood[f] =
+ *    PSLFE_E_INVALID, the pose is copied, nothing is optimised.
+ *    lstride == 0: d_lil and d_outlier_lil may be NULL; with every d_nlil[f] == 0 the results are the bits of
+ *    pslfe_pose_optimize_device.  The other rules and d_info are those of pslfe_pose_optimize_device. */
+int pslfe_pose_optimize_lil_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw_in, const PslPoseEdge* d_edges, const int32_t* d_nedges,
+                                   int estride, const PslPoseLilEdge* d_lil, const int32_t* d_nlil, int lstride, const PslCamera* cam,
+                                   PslPose* d_Tcw_out, uint8_t* d_outlier, uint8_t* d_outlier_lil, int32_t* d_ngood, PslPoseInfo* d_info);
+/* Same for one frame, host arrays (outlier: nedges bytes, outlier_lil: nlil bytes; outputs only, not written below 3 edges in total). */
+int pslfe_pose_optimize_lil(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* edges, int nedges, const PslPoseLilEdge* lil, int nlil,
+                            const PslCamera* cam, PslPose* Tcw_out, uint8_t* outlier, uint8_t* outlier_lil, int* ngood);
+/* == The LIL set-up loop src/Optimizer.cc:631-693 for nframes frames, HBM to HBM.  Frame f has d_nplanes[f] planes (N_LJL =
+ *    mvPlanes.size()); d_lil_index[f][i] (row stride plane_stride) is the row of plane i's map LIL (pFrame->mvpMapInsecs[i]) in
+ *    d_map (nmap rows, shared by the frames), or -1; an index outside [0, nmap) counts as -1; a row with bad != 0 gives no edge
+ *    (:634).  The observation of plane i is row i of d_le_l (mvle_l, one row per CROSSING, src/Frame.cc:528, row stride le_stride)
+ *    and row i of d_cross2d (CrossPoint_2D, one row per PLANE, :643, row stride plane_stride): i is a plane index, so the two rows
+ *    need not belong to the same crossing - the reference indexes them so (:658-660) and this is kept.  The edges are compacted in
+ *    plane order at d_lil + f*lstride, d_edge_plane (may be NULL) gets the plane of each edge, d_nlil[f] the full count: a count
+ *    above lstride is reported, never truncated silently (the first lstride rows are written).  d_nplanes[f] above plane_stride or
+ *    above le_stride (rows the arrays cannot hold; impossible with the glue's own buffers): d_nlil[f] = PSLFE_E_CAPACITY and no edge
+ *    of that frame is written; pslfe_pose_optimize_lil_device answers such a count with PSLFE_E_INVALID.  pslfe_glue_lil_obs_device gives the
+ *    observation arrays.  Asynchronous on the context's stream. */
+int pslfe_pose_lil_edges_device(pslfe_ctx* ctx, int nframes, const double* d_le_l, int le_stride, const double* d_cross2d, int plane_stride,
+                                const int32_t* d_nplanes, const int32_t* d_lil_index, const PslMapLil* d_map, int nmap, PslPoseLilEdge* d_lil,
+                                int32_t* d_edge_plane, int32_t* d_nlil, int lstride);
 
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
@@ -1215,6 +1271,11 @@ int pslfe_record_pack_device(pslfe_ctx* ctx, const PslRecordCaps* caps, const Ps
 int pslfe_glue_lines3d_device(pslfe_glue* g, const double** d_lines3d, int* stride);
 int pslfe_glue_planes_device(pslfe_glue* g, const float** d_planes, const int32_t** d_plane_lines, const int32_t** d_plane_counts,
                              int* plane_stride);
+/* Device view of the last batch's mvle_l ([max_batch][le_stride][6] f64, one row per crossing, src/Frame.cc:517-528; d_ncross = the
+ * crossings of each frame) and CrossPoint_2D ([max_batch][plane_stride][2] f64, one row per plane, :643; d_plane_counts as above):
+ * what pslfe_pose_lil_edges_device reads (src/Optimizer.cc:658-660).  Any pointer may be NULL. */
+int pslfe_glue_lil_obs_device(pslfe_glue* g, const double** d_le_l, int* le_stride, const int32_t** d_ncross, const double** d_cross2d,
+                              int* plane_stride, const int32_t** d_plane_counts);
 
 /* RCCL gather of the records, one communicator per context.  RCCL is loaded at run time (librccl.so.1).
  *   pslfe_gather_unique_id  rank 0 obtains the 128-byte ncclUniqueId and hands it to the other ranks by whatever channel the

@@ -39,6 +39,11 @@ LASTPOINT_NONE, LASTPOINT_NO_OBS, LASTPOINT_OBS, LASTPOINT_OUTLIER = 0, 1, 2, 8
 POSEEDGE_DTYPE = np.dtype([(k, "<f4") for k in ("u", "v", "ur", "inv_sigma2", "x", "y", "z")])
 POSEINFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (4,))])
 assert POSEEDGE_DTYPE.itemsize == 28 and POSEINFO_DTYPE.itemsize == 20
+# the LIL edge and the map LIL it is made from (include/pslfe.h: PslPoseLilEdge, PslMapLil)
+POSELIL_DTYPE = np.dtype([("line1", "<f8", (6,)), ("line2", "<f8", (6,)), ("cross", "<f8", (3,)), ("obs1", "<f8", (3,)), ("obs2", "<f8", (3,)),
+                          ("obs_ins", "<f8", (2,))])
+MAPLIL_DTYPE = np.dtype([("w", "<f8", (15,)), ("bad", "u1"), ("pad", "u1", (7,))])
+assert POSELIL_DTYPE.itemsize == 184 and MAPLIL_DTYPE.itemsize == 128
 
 
 def pose(Tcw):
@@ -632,15 +637,17 @@ def search_by_projection_map_device(frame, slot0, npairs, d_queries, d_qdesc, d_
 
 
 class Optimizer:
-    """Optimizer::PoseOptimization src/Optimizer.cc:239-1023, the point edges (EdgeSE3ProjectXYZOnlyPose and
-    EdgeStereoSE3ProjectXYZOnlyPose).  The LIL edges (:619-694, :973-1008) stay host code: the result is the reference's only for a
-    frame whose mvpMapInsecs holds no live entry.  Parity with g2o itself is unpinned."""
+    """Optimizer::PoseOptimization src/Optimizer.cc:239-1023: the point edges (EdgeSE3ProjectXYZOnlyPose and
+    EdgeStereoSE3ProjectXYZOnlyPose) and the LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the `lil` argument and the *Lil*
+    methods).  Parity with g2o itself is unpinned."""
 
     @staticmethod
-    def PoseOptimization(Tcw, edges, cam, ctx=None):
+    def PoseOptimization(Tcw, edges, cam, ctx=None, lil=None):
         """One frame, host arrays: Tcw a POSE_DTYPE record (pFrame->mTcw), edges POSEEDGE_DTYPE[n] in keypoint order.
         -> (ngood = the return value, Tcw_out, outlier u8 [n] = mvbOutlier of each edge's keypoint).  Fewer than 3 edges: (0, Tcw,
-        zeros), as the reference leaves them (:291, :696)."""
+        zeros), as the reference leaves them (:291, :696).
+        lil: POSELIL_DTYPE[m] in plane order (:631-693) -> (ngood, Tcw_out, outlier, outlier_lil u8 [m] = mvbOutlier_Insec of each
+        edge's plane); ngood counts every LIL edge as good (:1022) and "fewer than 3" counts both kinds."""
         ctx = ctx or default_context()
         T = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(1)
         e = np.ascontiguousarray(edges, POSEEDGE_DTYPE)
@@ -648,6 +655,13 @@ class Optimizer:
         out = np.zeros(1, POSE_DTYPE)
         outlier = np.zeros(max(len(e), 1), np.uint8)
         ng = C.c_int()
+        if lil is not None:
+            l = np.ascontiguousarray(lil, POSELIL_DTYPE)
+            outlier_lil = np.zeros(max(len(l), 1), np.uint8)
+            _check(lib().pslfe_pose_optimize_lil(ctx._h, _ptr(T), _ptr(e) if len(e) else None, C.c_int(len(e)), _ptr(l) if len(l) else None,
+                                                 C.c_int(len(l)), _ptr(cam), _ptr(out), _ptr(outlier) if len(e) else None,
+                                                 _ptr(outlier_lil) if len(l) else None, C.byref(ng)), "pslfe_pose_optimize_lil")
+            return ng.value, out[0], outlier[:len(e)], outlier_lil[:len(l)]
         _check(lib().pslfe_pose_optimize(ctx._h, _ptr(T), _ptr(e) if len(e) else None, C.c_int(len(e)), _ptr(cam), _ptr(out),
                                          _ptr(outlier) if len(e) else None, C.byref(ng)), "pslfe_pose_optimize")
         return ng.value, out[0], outlier[:len(e)]
@@ -662,6 +676,31 @@ class Optimizer:
                                                 C.c_void_p(d_nedges or None), C.c_int(estride), _ptr(cam), C.c_void_p(d_Tcw_out or None),
                                                 C.c_void_p(d_outlier or None), C.c_void_p(d_ngood or None), C.c_void_p(d_info or None)),
                "pslfe_pose_optimize_device")
+
+    @staticmethod
+    def PoseOptimizationLilDevice(nframes, d_Tcw_in, d_edges, d_nedges, estride, d_lil, d_nlil, lstride, cam, d_Tcw_out, d_outlier,
+                                  d_outlier_lil, d_ngood, d_info=0, ctx=None):
+        """PoseOptimizationDevice with the LIL edges of every frame: d_lil POSELIL_DTYPE [nframes][lstride], d_nlil [nframes],
+        d_outlier_lil [nframes][lstride] bytes.  LIL edge j of a frame has the edge index d_nedges[f] + j."""
+        ctx = ctx or default_context()
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_pose_optimize_lil_device(
+            ctx._h, C.c_int(nframes), C.c_void_p(d_Tcw_in or None), C.c_void_p(d_edges or None), C.c_void_p(d_nedges or None), C.c_int(estride),
+            C.c_void_p(d_lil or None), C.c_void_p(d_nlil or None), C.c_int(lstride), _ptr(cam), C.c_void_p(d_Tcw_out or None),
+            C.c_void_p(d_outlier or None), C.c_void_p(d_outlier_lil or None), C.c_void_p(d_ngood or None), C.c_void_p(d_info or None)),
+            "pslfe_pose_optimize_lil_device")
+
+    @staticmethod
+    def LilEdgesDevice(nframes, d_le_l, le_stride, d_cross2d, plane_stride, d_nplanes, d_lil_index, d_map, nmap, d_lil, d_edge_plane, d_nlil,
+                       lstride, ctx=None):
+        """The LIL set-up loop :631-693 on the device: d_lil_index [nframes][plane_stride] = the MAPLIL_DTYPE row of each plane's map
+        LIL or -1; plane i takes row i of mvle_l and row i of CrossPoint_2D (FrameGlue.lil_obs_device), as the reference does; edges
+        compacted in plane order; d_nlil[f] = the full count, also above lstride."""
+        ctx = ctx or default_context()
+        _check(lib().pslfe_pose_lil_edges_device(
+            ctx._h, C.c_int(nframes), C.c_void_p(d_le_l or None), C.c_int(le_stride), C.c_void_p(d_cross2d or None), C.c_int(plane_stride),
+            C.c_void_p(d_nplanes or None), C.c_void_p(d_lil_index or None), C.c_void_p(d_map or None), C.c_int(nmap), C.c_void_p(d_lil or None),
+            C.c_void_p(d_edge_plane or None), C.c_void_p(d_nlil or None), C.c_int(lstride)), "pslfe_pose_lil_edges_device")
 
     @staticmethod
     def MapPointIndexFromMatchesDevice(frame, nframes, d_match, d_owner, d_nq, qstride, d_mp_index):
@@ -1127,6 +1166,14 @@ class FrameGlue:
         d, st = C.c_void_p(), C.c_int()
         _check(lib().pslfe_glue_lines3d_device(self._h, C.byref(d), C.byref(st)), "pslfe_glue_lines3d_device")
         return d.value, st.value
+
+    def lil_obs_device(self):
+        """Device view of the last batch's mvle_l and CrossPoint_2D -> dict(le_l, le_stride, ncross, cross2d, plane_stride, nplanes):
+        le_l [max_batch][le_stride][6] f64 (one row per crossing), cross2d [max_batch][plane_stride][2] f64 (one row per plane)."""
+        le, c2, nc, npl, ls, ps = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        _check(lib().pslfe_glue_lil_obs_device(self._h, C.byref(le), C.byref(ls), C.byref(nc), C.byref(c2), C.byref(ps), C.byref(npl)),
+               "pslfe_glue_lil_obs_device")
+        return dict(le_l=le.value, le_stride=ls.value, ncross=nc.value, cross2d=c2.value, plane_stride=ps.value, nplanes=npl.value)
 
     def fetch(self, frame, nlines):
         """dict with mvLines3D, mvLineEq, the crossings (pair, xy, cross, le_l) and the planes."""

@@ -1,5 +1,5 @@
 // The per-edge arithmetic, the 6x6 solve and the SE3 update of the pose optimisation (pslfe_pose.hip), as functions of one thread.
-// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp for its host loop, so both
+// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp / pose_lil_main.cpp for their host loops, so both
 // run the same single IEEE operations (build with -ffp-contract=off).  Restated from the reference's g2o:
 //   edge errors / Jacobians   Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp} (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose)
 //   SE3Quat, exp, product     Thirdparty/g2o/g2o/types/se3quat.h, se3_ops.hpp
@@ -256,6 +256,123 @@ PSL_PO_HD void psl_po_add_terms(const double* e, const double* Pc, int mono, dou
         }
         const double s = w0 * e[0] + w1 * e[1];
         acc[21 + j] = acc[21 + j] + (mono ? s : s + w2 * e[2]);
+    }
+    acc[27] = acc[27] + rho0;
+}
+
+// ---- the LIL edge: EdgeLILSE3ProjectXYZ with its fixed VertexLIL (add_inc/EdgeLIL.h:210-439, src/Optimizer.cc:619-694) ---------------
+// One row L of 23 doubles (PslPoseLilEdge): the world data X1s X1e X2s X2e Xins (L[0..14]: line1 start / end, line2 start / end,
+// crosspoint) and the observation l1 l2 ins (L[15..22]: mvle_l[i].first, .second, CrossPoint_2D[i]).  Information: the identity
+// (invSigma = 1, src/Optimizer.cc:241, :668).  The vertex is fixed, so only _jacobianOplusXj (:339-379) enters H and b.
+#define PSL_POSE_LIL_DOUBLES 23
+#define PSL_POSE_DELTA_LIL 3.3271608352661133   /* float deltaLJL = sqrt(11.07) (src/Optimizer.cc:628) */
+
+// T.map(X) and cam_project of it (EdgeLIL.h:415-430: project2d divides, then * fx + cx)
+PSL_PO_HD void psl_po_lil_map(const double* X, const PslSE3* T, double* Pc) {
+    double r[3];
+    psl_po_rotate(T->q, X, r);
+    Pc[0] = r[0] + T->t[0]; Pc[1] = r[1] + T->t[1]; Pc[2] = r[2] + T->t[2];
+}
+PSL_PO_HD void psl_po_lil_project(const double* X, const PslSE3* T, const PslPoseCamD* K, double* uv) {
+    double Pc[3];
+    psl_po_lil_map(X, T, Pc);
+    uv[0] = PSL_PO_DIV(Pc[0], Pc[2]) * K->fx + K->cx;
+    uv[1] = PSL_PO_DIV(Pc[1], Pc[2]) * K->fy + K->cy;
+}
+
+// computeError (EdgeLIL.h:220-256): e0, e1 = (u, v, 1) . l1 at X1s, X1e; e2, e3 = (u, v, 1) . l2 at X2s, X2e; (e4, e5) = ins - P(Xins).
+// The products of the 2x3 matrix with the line run in index order; 1.0 * l[2] is l[2].
+PSL_PO_HD void psl_po_lil_error(const double* L, const PslSE3* T, const PslPoseCamD* K, double* e) {
+    double uv[2];
+    for (int r = 0; r < 4; ++r) {
+        const double* l = L + 15 + 3 * (r >> 1);
+        psl_po_lil_project(L + 3 * r, T, K, uv);
+        e[r] = (uv[0] * l[0] + uv[1] * l[1]) + l[2];
+    }
+    psl_po_lil_project(L + 12, T, K, uv);
+    e[4] = L[21] - uv[0];
+    e[5] = L[22] - uv[1];
+}
+
+// chi2 = e . (1.0 I) e, the six products summed in ascending order
+PSL_PO_HD double psl_po_lil_chi2(const double* e) {
+    double c = e[0] * e[0];
+    for (int r = 1; r < 6; ++r) c = c + e[r] * e[r];
+    return c;
+}
+
+// RobustKernelHuber::robustify with the LIL delta
+PSL_PO_HD void psl_po_lil_huber(double chi2, double* rho0, double* rho1) {
+    const double delta = PSL_POSE_DELTA_LIL;
+    const double dsqr = delta * delta;
+    if (chi2 <= dsqr) { *rho0 = chi2; *rho1 = 1.0; }
+    else {
+        const double sq = PSL_PO_SQRT(chi2);
+        *rho0 = (2.0 * sq) * delta - dsqr;
+        *rho1 = PSL_PO_DIV(delta, sq);
+    }
+}
+
+// a line row of _jacobianOplusXj (EdgeLIL.h:339-365) at the camera point Pc with the line (l0, l1), every entry in the header's order
+PSL_PO_HD void psl_po_lil_row_line(const double* Pc, double l0, double l1, const PslPoseCamD* K, double* J) {
+    const double x = Pc[0], y = Pc[1], invz = PSL_PO_DIV(1.0, Pc[2]), invz2 = invz * invz;
+    const double fx = K->fx, fy = K->fy;
+    J[0] = ((((-fx) * x) * y) * invz2) * l0 - (fy * (1.0 + (y * y) * invz2)) * l1;
+    J[1] = (fx * (1.0 + (x * x) * invz2)) * l0 + (((fy * x) * y) * invz2) * l1;
+    J[2] = (((-fx) * y) * invz) * l0 + ((fy * x) * invz) * l1;
+    J[3] = (fx * invz) * l0;
+    J[4] = (fy * invz) * l1;
+    J[5] = (((-fx) * x) * l0 - (fy * y) * l1) * invz2;
+}
+
+// rows 4 and 5 (EdgeLIL.h:367-379): the monocular point edge's rows at Xins, in this header's order
+PSL_PO_HD void psl_po_lil_row_ins(const double* Pc, int second, const PslPoseCamD* K, double* J) {
+    const double x = Pc[0], y = Pc[1], invz = PSL_PO_DIV(1.0, Pc[2]), invz2 = invz * invz;
+    const double fx = K->fx, fy = K->fy;
+    if (!second) {
+        J[0] = ((x * y) * invz2) * fx;
+        J[1] = (-(1.0 + (x * x) * invz2)) * fx;
+        J[2] = (y * invz) * fx;
+        J[3] = (-fx) * invz;
+        J[4] = 0.0;
+        J[5] = (x * invz2) * fx;
+    } else {
+        J[0] = (1.0 + (y * y) * invz2) * fy;
+        J[1] = (((-fy) * x) * y) * invz2;
+        J[2] = ((-fy) * x) * invz;
+        J[3] = 0.0;
+        J[4] = (-fy) * invz;
+        J[5] = (fy * y) * invz2;
+    }
+}
+
+// the rank-one contribution of one Jacobian row J with its error er: acc_H[jk] += (w J_j) J_k, acc_b[j] += (w J_j) er
+PSL_PO_HD void psl_po_lil_add_row(const double* J, double er, double w, double* acc) {
+    int h = 0;
+    for (int j = 0; j < 6; ++j) {
+        const double wj = w * J[j];
+        for (int k = j; k < 6; ++k, ++h) acc[h] = acc[h] + wj * J[k];
+        acc[21 + j] = acc[21 + j] + wj * er;
+    }
+}
+
+// linearizeOplus (EdgeLIL.h:264-381) and constructQuadraticForm of one LIL edge: adds its 28 terms to acc row by row - row 0, its
+// rank-one contribution, row 1, ... row 5, then rho - so that no 6x6 Jacobian is ever live.  w = rho' (the information is 1.0).
+// linearizeOplus reads segment<3>(9) for xyz2_s AND xyz2_e (:273-275): row 2 of the Jacobian is evaluated at the END point of line 2
+// while e[2] is the error at its START point.  That is the reference's behaviour and is kept.
+PSL_PO_HD void psl_po_lil_add_terms(const double* L, const double* e, const PslSE3* T, double rho0, double rho1, const PslPoseCamD* K,
+                                    double* acc) {
+    double Pc[3], J[6];
+    for (int r = 0; r < 4; ++r) {
+        const double* l = L + 15 + 3 * (r >> 1);
+        psl_po_lil_map(L + (r == 2 ? 9 : 3 * r), T, Pc);
+        psl_po_lil_row_line(Pc, l[0], l[1], K, J);
+        psl_po_lil_add_row(J, e[r], rho1, acc);
+    }
+    psl_po_lil_map(L + 12, T, Pc);
+    for (int r = 4; r < 6; ++r) {
+        psl_po_lil_row_ins(Pc, r - 4, K, J);
+        psl_po_lil_add_row(J, e[r], rho1, acc);
     }
     acc[27] = acc[27] + rho0;
 }

@@ -1011,4 +1011,17 @@ int pslfe_glue_planes_device(pslfe_glue* g, const float** d_planes, const int32_
     return PSLFE_OK;
 }
 
+int pslfe_glue_lil_obs_device(pslfe_glue* g, const double** d_le_l, int* le_stride, const int32_t** d_ncross, const double** d_cross2d,
+                              int* plane_stride, const int32_t** d_plane_counts) {
+    PSL_REQUIRE(g, PSLFE_E_INVALID, "pslfe_glue_lil_obs_device: glue is NULL");
+    PSL_REQUIRE(g->last_nframes > 0, PSLFE_E_STATE, "pslfe_glue_lil_obs_device: no batch processed yet");
+    if (d_le_l) *d_le_l = g->d_le_l;
+    if (le_stride) *le_stride = g->int_cap;
+    if (d_ncross) *d_ncross = g->d_nint;
+    if (d_cross2d) *d_cross2d = g->d_cross2d;
+    if (plane_stride) *plane_stride = g->plane_cap;
+    if (d_plane_counts) *d_plane_counts = g->d_nplanes;
+    return PSLFE_OK;
+}
+
 }  // extern "C"

@@ -1,10 +1,18 @@
-// libpslfe: the point edges of Optimizer::PoseOptimization (src/Optimizer.cc:239-1023) for K frames in one launch.  Product code.
+// libpslfe: Optimizer::PoseOptimization (src/Optimizer.cc:239-1023), its point edges and its LIL edges, for K frames in one launch.
+// Product code.
 // Reference behaviour restated (in double, in the reference's order of decisions; the arithmetic is in pose_kernels.h):
 //   edge set-up, the four rounds, the classification after a round   src/Optimizer.cc:282-363, :696-780, :1011-1022
 //   one iteration: lambda, trials, rho, Terminate                    Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189
 //   the iteration loop of a round                                    Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419
-// Scope: the monocular and stereo point edges only.  The LIL edges (EdgeLILSE3ProjectXYZ with VertexLIL, src/Optimizer.cc:619-694,
-// :973-1008) are host code; the result is the reference's only for a frame whose mvpMapInsecs holds no live entry.
+//   the LIL edges: set-up, error / Jacobian, classification            src/Optimizer.cc:619-694, add_inc/EdgeLIL.h:210-439, :973-1008
+// Scope: the monocular and stereo point edges (k_pose_optimize<false>, what pslfe_pose_optimize[_device] launch) and, in
+// k_pose_optimize<true> (pslfe_pose_optimize_lil[_device]), the LIL edges (EdgeLILSE3ProjectXYZ with its fixed VertexLIL) as well.
+// The LIL edges of a frame extend its edge index space: LIL edge j has the index n + j (g2o adds them after the point edges), so
+// ownership (index mod 256) and the order of the sums stay a function of the edge index and the counts alone.  Their rows (23
+// doubles) are read from HBM; a LIL edge adds its 28 terms row by row (psl_po_lil_add_terms), so that no 6x6 Jacobian is live next
+// to the accumulators (no scratch in either instantiation: profiles/pose_lil_codegen.txt).  The `< 3` and `< 10` rules count both
+// kinds; the return value counts an outlying LIL edge as good (:1022).  Two oddities of the reference are kept:
+// the Jacobian's row 2 at line 2's end point (EdgeLIL.h:273-275) and mvle_l[i] indexed by the plane (src/Optimizer.cc:658).
 // Conventions: include/pslfe.h above pslfe_pose_optimize_device.
 //
 // Layout.  One workgroup of 256 threads per frame, resident through every round, iteration and trial; there is no launch per
@@ -42,6 +50,7 @@
 #define PSL_POSE_BS PSL_POSE_LANES
 #define PSL_POSE_LDS_EDGES 2048   // 56 KB of edge rows
 
+static_assert(sizeof(PslPoseLilEdge) == PSL_POSE_LIL_DOUBLES * sizeof(double), "a LIL row is 23 doubles");
 static_assert(sizeof(PslPoseEdge) == 28 && sizeof(PslPoseInfo) == 20 && sizeof(PslPose) == 48, "pose PODs");
 static_assert(PSL_POSE_BS == 4 * PSL_POSE_GROUP, "four waves of 64");
 
@@ -59,6 +68,13 @@ struct PoseArgs {
     uint8_t* outlier;
     int32_t* ngood;
     PslPoseInfo* info;
+};
+// the LIL edges of the frames (k_pose_optimize<true> only): rows of 23 doubles read from HBM, LIL edge j has the edge index n + j
+struct PoseLilArgs {
+    const PslPoseLilEdge* lil;
+    const int32_t* nlil;
+    int lstride;
+    uint8_t* outlier;
 };
 
 // steps 2 and 3 of the order of the sums for N values per thread; `flip` alternates the LDS buffer
@@ -86,18 +102,25 @@ __device__ __forceinline__ void psl_pose_reduce(double* acc, double* s_red, int&
 
 extern __shared__ float s_pose_edges[];
 
-__global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
+// LIL: the frames have LIL edges (B); without them B is not read and the kernel is the point-edge kernel.  n: the point edges, m: the
+// LIL edges, nt = n + m: the edges (the `< 3` and `< 10` rules and the order of the sums see one index space, points first).
+template <bool LIL>
+__global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseLilArgs B) {
     __shared__ double s_red[2 * 4 * PSL_POSE_NTERMS];
     const int f = blockIdx.x, tid = threadIdx.x;
     const int n = A.nedges[f];
+    const int m = LIL ? B.nlil[f] : 0;
+    const int nt = n + m;
     const float* Tin = reinterpret_cast<const float*>(A.Tin + f);
     float* Tout = reinterpret_cast<float*>(A.Tout + f);
-    if (n < 3 || n > A.estride) {   // uniform: fewer than 3 edges (src/Optimizer.cc:696), or a count the rows cannot hold
+    const bool over = n > A.estride || (LIL && m > B.lstride);
+    const bool negative = LIL && (n < 0 || m < 0);   // a negative count, such as an error code pslfe_pose_lil_edges_device left in d_nlil
+    if (nt < 3 || over || negative) {   // uniform: fewer than 3 edges (src/Optimizer.cc:696), or a count the rows cannot hold
         if (tid == 0) {
             float P[12];
             for (int i = 0; i < 12; ++i) P[i] = Tin[i];
             for (int i = 0; i < 12; ++i) Tout[i] = P[i];
-            A.ngood[f] = n > A.estride ? PSLFE_E_CAPACITY : 0;
+            A.ngood[f] = negative ? PSLFE_E_INVALID : over ? PSLFE_E_CAPACITY : 0;
             if (A.info) {
                 PslPoseInfo I = {0, {0, 0, 0, 0}};
                 A.info[f] = I;
@@ -112,6 +135,10 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
         __syncthreads();
     }
     uint8_t* out = A.outlier + (size_t)f * A.estride;
+    // the first LIL edge of this thread: the smallest j with (n + j) mod 256 == tid
+    const int j0 = LIL ? ((tid - n % PSL_POSE_BS) + PSL_POSE_BS) % PSL_POSE_BS : 0;
+    const double* Lrows = LIL ? reinterpret_cast<const double*>(B.lil + (size_t)f * B.lstride) : nullptr;
+    uint8_t* out_lil = LIL ? B.outlier + (size_t)f * B.lstride : nullptr;
     const PslPoseCamD K = A.K;
     PslSE3 T0;
     {
@@ -123,13 +150,13 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
         PslPoseInfo I = {0, {0, 0, 0, 0}};
         A.info[f] = I;
     }
-    int flip = 0, nbad = 0;
+    int flip = 0, nbad = 0, nbad_lil = 0;
     PslSE3 T = T0;
     for (int r = 0; r < 4; ++r) {
         T = T0;                       // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) (:719)
         const bool robust = r < 3;    // e->setRobustKernel(0) after round index 2 (:749)
         int its = 0;
-        if (n - nbad > 0) {           // without an active edge g2o has no vertex to optimise and optimize() returns at once
+        if (nt - nbad - nbad_lil > 0) {   // without an active edge g2o has no vertex to optimise and optimize() returns at once
             double lambda = 0.0, ni = 2.0;
             int lm_bad = 0;
             for (int it = 0; it < 10; ++it) {
@@ -145,6 +172,18 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
                     rho0 = c;
                     if (robust) psl_po_huber(c, mono, &rho0, &rho1);
                     psl_po_add_terms(e, Pc, mono, is2, rho0, rho1, &K, acc);
+                }
+                if constexpr (LIL) {
+                    for (int j = j0; j < m; j += PSL_POSE_BS) {
+                        if (r > 0 && out_lil[j]) continue;
+                        const double* L = Lrows + (size_t)j * PSL_POSE_LIL_DOUBLES;
+                        double e[6], rho0, rho1 = 1.0;
+                        psl_po_lil_error(L, &T, &K, e);
+                        const double c = psl_po_lil_chi2(e);
+                        rho0 = c;
+                        if (robust) psl_po_lil_huber(c, &rho0, &rho1);
+                        psl_po_lil_add_terms(L, e, &T, rho0, rho1, &K, acc);
+                    }
                 }
                 psl_pose_reduce<PSL_POSE_NTERMS>(acc, s_red, flip);
                 double b[6];
@@ -179,6 +218,17 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
                             if (robust) psl_po_huber(c, mono, &rho0, &rho1);
                             cs[0] = cs[0] + rho0;
                         }
+                        if constexpr (LIL) {
+                            for (int j = j0; j < m; j += PSL_POSE_BS) {
+                                if (r > 0 && out_lil[j]) continue;
+                                double e[6], rho0, rho1 = 1.0;
+                                psl_po_lil_error(Lrows + (size_t)j * PSL_POSE_LIL_DOUBLES, &Tn, &K, e);
+                                const double c = psl_po_lil_chi2(e);
+                                rho0 = c;
+                                if (robust) psl_po_lil_huber(c, &rho0, &rho1);
+                                cs[0] = cs[0] + rho0;
+                            }
+                        }
                         psl_pose_reduce<1>(cs, s_red, flip);
                         temp_chi = cs[0];
                     }
@@ -201,7 +251,8 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
             }
         }
         // the plain chi2 of every edge at the round's pose, as a float, against 5.991f / 7.815f (:724-780)
-        double cnt[1] = {0.0};
+        // and of every LIL edge against 11.07f (:977-1008); nBad counts the point edges only
+        double cnt[LIL ? 2 : 1] = {0.0};
         for (int i = tid; i < n; i += PSL_POSE_BS) {
             double e[3], Pc[3];
             const int mono = psl_po_error(E + 7 * i, &T, &K, e, Pc);
@@ -210,19 +261,29 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A) {
             out[i] = bad ? 1 : 0;
             cnt[0] = cnt[0] + (bad ? 1.0 : 0.0);
         }
-        psl_pose_reduce<1>(cnt, s_red, flip);   // a count: exact in any order
+        if constexpr (LIL) {
+            for (int j = j0; j < m; j += PSL_POSE_BS) {
+                double e[6];
+                psl_po_lil_error(Lrows + (size_t)j * PSL_POSE_LIL_DOUBLES, &T, &K, e);
+                const bool bad = (float)psl_po_lil_chi2(e) > 11.07f;
+                out_lil[j] = bad ? 1 : 0;
+                cnt[1] = cnt[1] + (bad ? 1.0 : 0.0);
+            }
+        }
+        psl_pose_reduce<LIL ? 2 : 1>(cnt, s_red, flip);   // counts: exact in any order
         nbad = (int)cnt[0];
+        if constexpr (LIL) nbad_lil = (int)cnt[1];
         if (tid == 0 && A.info) {
             A.info[f].rounds = r + 1;
             A.info[f].iterations[r] = its;
         }
-        if (n < 10) break;   // optimizer.edges().size() < 10: all edges, not the active ones (:1011)
+        if (nt < 10) break;   // optimizer.edges().size() < 10: all edges, not the active ones (:1011)
     }
     if (tid == 0) {
         float P[12];
         psl_po_to_pose(&T, P, P + 9);
         for (int i = 0; i < 12; ++i) Tout[i] = P[i];
-        A.ngood[f] = n - nbad;
+        A.ngood[f] = nt - nbad;   // nInitialCorrespondences - nBad (:1022): an outlying LIL edge still counts as good
     }
 }
 
@@ -311,10 +372,76 @@ __global__ __launch_bounds__(256) void k_pose_mp_index(const int32_t* __restrict
     }
 }
 
+// ---- the LIL edges of a frame from its planes: the set-up loop src/Optimizer.cc:631-693 ---------------------------------------------------
+struct PoseLilEdgeArgs {
+    const double* le_l;        // [nframes][le_stride][6]     mvle_l, one row per crossing
+    const double* cross2d;     // [nframes][plane_stride][2]  CrossPoint_2D, one row per plane
+    const int32_t* nplanes;    // [nframes]
+    const int32_t* lil_index;  // [nframes][plane_stride]
+    const PslMapLil* map;
+    int le_stride, plane_stride, nmap;
+    PslPoseLilEdge* lil;
+    int32_t* edge_plane;
+    int32_t* nlil;
+    int lstride;
+};
+
+// one workgroup per frame: the planes in chunks of 256, compacted in plane order as k_pose_edges compacts the keypoints.  Plane i
+// takes row i of mvle_l and row i of CrossPoint_2D, as the reference does (:658-660).
+__global__ __launch_bounds__(256) void k_pose_lil_edges(PoseLilEdgeArgs A) {
+    __shared__ int s_cnt[4];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (A.nplanes[f] > min(A.plane_stride, A.le_stride)) {   // uniform: planes the rows cannot hold are reported, not dropped
+        if (tid == 0) A.nlil[f] = PSLFE_E_CAPACITY;
+        return;
+    }
+    const int n = A.nplanes[f];
+    const double* le = A.le_l + (size_t)f * A.le_stride * 6;
+    const double* c2 = A.cross2d + (size_t)f * A.plane_stride * 2;
+    const int32_t* idx = A.lil_index + (size_t)f * A.plane_stride;
+    PslPoseLilEdge* lil = A.lil + (size_t)f * A.lstride;
+    int32_t* edge_plane = A.edge_plane ? A.edge_plane + (size_t)f * A.lstride : nullptr;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {   // uniform
+        const int i = i0 + tid;
+        int q = -1;
+        if (i < n) {
+            q = idx[i];
+            if (q < 0 || q >= A.nmap) q = -1;          // mvpMapInsecs[i] == NULL
+            else if (A.map[q].bad) q = -1;             // mbBad (:634)
+        }
+        const unsigned long long bal = __ballot(q >= 0);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) s_cnt[w] = __popcll(bal);
+        __syncthreads();
+        int wbase = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < w) wbase += s_cnt[k];
+            total += s_cnt[k];
+        }
+        const int pos = base + wbase + before;
+        if (q >= 0 && pos < A.lstride) {
+            PslPoseLilEdge e;
+            const double* W = A.map[q].w;
+            for (int k = 0; k < 6; ++k) { e.line1[k] = W[k]; e.line2[k] = W[6 + k]; }
+            for (int k = 0; k < 3; ++k) { e.cross[k] = W[12 + k]; e.obs1[k] = le[6 * (size_t)i + k]; e.obs2[k] = le[6 * (size_t)i + 3 + k]; }
+            e.obs_ins[0] = c2[2 * (size_t)i]; e.obs_ins[1] = c2[2 * (size_t)i + 1];
+            lil[pos] = e;
+            if (edge_plane) edge_plane[pos] = i;
+        }
+        base += total;
+        __syncthreads();   // s_cnt is rewritten by the next chunk
+    }
+    if (tid == 0) A.nlil[f] = base;
+}
+
 namespace {
 
+template <bool LIL>
 int pose_launch(pslfe_ctx* ctx, int nframes, const PslPose* d_Tin, const PslPoseEdge* d_edges, const int32_t* d_nedges, int estride,
-                const PslCamera* cam, PslPose* d_Tout, uint8_t* d_outlier, int32_t* d_ngood, PslPoseInfo* d_info) {
+                const PslCamera* cam, PslPose* d_Tout, uint8_t* d_outlier, int32_t* d_ngood, PslPoseInfo* d_info,
+                const PoseLilArgs& B = PoseLilArgs{nullptr, nullptr, 0, nullptr}) {
     PoseArgs A;
     A.Tin = d_Tin; A.edges = d_edges; A.nedges = d_nedges; A.estride = estride;
     A.lds_edges = estride < PSL_POSE_LDS_EDGES ? estride : PSL_POSE_LDS_EDGES;
@@ -323,7 +450,7 @@ int pose_launch(pslfe_ctx* ctx, int nframes, const PslPose* d_Tin, const PslPose
     const size_t lds = (size_t)A.lds_edges * sizeof(PslPoseEdge);
     {
         PSL_STAGE_BEGIN(ctx, "pose.optimize");
-        k_pose_optimize<<<nframes, PSL_POSE_BS, lds, ctx->stream>>>(A);
+        k_pose_optimize<LIL><<<nframes, PSL_POSE_BS, lds, ctx->stream>>>(A, B);
         PSL_STAGE_END(ctx, "pose.optimize");
     }
     PSL_HIP(hipGetLastError());
@@ -344,7 +471,7 @@ int pslfe_pose_optimize_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw
     PSL_REQUIRE(d_Tcw_in && d_nedges && d_Tcw_out && d_ngood, PSLFE_E_INVALID, "%s: NULL array", who);
     PSL_REQUIRE(estride == 0 || (d_edges && d_outlier), PSLFE_E_INVALID, "%s: NULL edges or outlier bytes with estride = %d", who, estride);
     PSL_HIP(hipSetDevice(ctx->device));
-    return pose_launch(ctx, nframes, d_Tcw_in, d_edges, d_nedges, estride, cam, d_Tcw_out, d_outlier, d_ngood, d_info);
+    return pose_launch<false>(ctx, nframes, d_Tcw_in, d_edges, d_nedges, estride, cam, d_Tcw_out, d_outlier, d_ngood, d_info);
 }
 
 int pslfe_pose_optimize(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* edges, int nedges, const PslCamera* cam, PslPose* Tcw_out,
@@ -364,13 +491,90 @@ int pslfe_pose_optimize(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* e
     uint8_t* d_out = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);   // an output: not read, not written below 3 edges
     int32_t* d_ng = psl_scratch_up(ctx, (const int32_t*)nullptr, 1, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
-    if (int rc = pose_launch(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr)) return rc;
+    if (int rc = pose_launch<false>(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr)) return rc;
     int32_t ng = 0;
     PSL_HIP(hipMemcpyAsync(Tcw_out, d_T, sizeof(PslPose), hipMemcpyDeviceToHost, st));
     if (nedges >= 3) PSL_HIP(hipMemcpyAsync(outlier, d_out, (size_t)nedges, hipMemcpyDeviceToHost, st));
     PSL_HIP(hipMemcpyAsync(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost, st));
     PSL_HIP(hipStreamSynchronize(st));
     *ngood = ng;
+    return PSLFE_OK;
+}
+
+int pslfe_pose_optimize_lil_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw_in, const PslPoseEdge* d_edges, const int32_t* d_nedges,
+                                   int estride, const PslPoseLilEdge* d_lil, const int32_t* d_nlil, int lstride, const PslCamera* cam,
+                                   PslPose* d_Tcw_out, uint8_t* d_outlier, uint8_t* d_outlier_lil, int32_t* d_ngood, PslPoseInfo* d_info) {
+    static const char* who = "pslfe_pose_optimize_lil_device";
+    PSL_REQUIRE(nframes >= 0 && estride >= 0 && lstride >= 0, PSLFE_E_INVALID, "%s: nframes = %d, estride = %d, lstride = %d", who, nframes,
+                estride, lstride);
+    if (nframes == 0) return PSLFE_OK;
+    PSL_REQUIRE(ctx && cam, PSLFE_E_INVALID, "%s: NULL context or camera", who);
+    PSL_REQUIRE(d_Tcw_in && d_nedges && d_nlil && d_Tcw_out && d_ngood, PSLFE_E_INVALID, "%s: NULL array", who);
+    PSL_REQUIRE(estride == 0 || (d_edges && d_outlier), PSLFE_E_INVALID, "%s: NULL edges or outlier bytes with estride = %d", who, estride);
+    PSL_REQUIRE(lstride == 0 || (d_lil && d_outlier_lil), PSLFE_E_INVALID, "%s: NULL LIL edges or outlier bytes with lstride = %d", who, lstride);
+    PSL_HIP(hipSetDevice(ctx->device));
+    const PoseLilArgs B = {d_lil, d_nlil, lstride, d_outlier_lil};
+    return pose_launch<true>(ctx, nframes, d_Tcw_in, d_edges, d_nedges, estride, cam, d_Tcw_out, d_outlier, d_ngood, d_info, B);
+}
+
+int pslfe_pose_optimize_lil(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* edges, int nedges, const PslPoseLilEdge* lil, int nlil,
+                            const PslCamera* cam, PslPose* Tcw_out, uint8_t* outlier, uint8_t* outlier_lil, int* ngood) {
+    static const char* who = "pslfe_pose_optimize_lil";
+    PSL_REQUIRE(nedges >= 0 && nlil >= 0, PSLFE_E_INVALID, "%s: nedges = %d, nlil = %d", who, nedges, nlil);
+    PSL_REQUIRE(ctx && cam && Tcw && Tcw_out && ngood, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE(nedges == 0 || (edges && outlier), PSLFE_E_INVALID, "%s: NULL edges or outlier bytes with nedges = %d", who, nedges);
+    PSL_REQUIRE(nlil == 0 || (lil && outlier_lil), PSLFE_E_INVALID, "%s: NULL LIL edges or outlier bytes with nlil = %d", who, nlil);
+    PSL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    hipError_t e = hipSuccess;
+    const int32_t n32 = nedges, m32 = nlil;
+    PslPose* d_T = psl_scratch_up(ctx, Tcw, 1, st, &e);
+    const PslPoseEdge* d_edges = psl_scratch_up(ctx, nedges ? edges : nullptr, (size_t)nedges, st, &e);
+    const PslPoseLilEdge* d_lil = psl_scratch_up(ctx, nlil ? lil : nullptr, (size_t)nlil, st, &e);
+    const int32_t* d_n = psl_scratch_up(ctx, &n32, 1, st, &e);
+    const int32_t* d_m = psl_scratch_up(ctx, &m32, 1, st, &e);
+    uint8_t* d_out = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);   // outputs: not read, not written below 3 edges
+    uint8_t* d_outl = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nlil, st, &e);
+    int32_t* d_ng = psl_scratch_up(ctx, (const int32_t*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
+    const PoseLilArgs B = {d_lil, d_m, nlil, d_outl};
+    if (int rc = pose_launch<true>(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr, B)) return rc;
+    int32_t ng = 0;
+    PSL_HIP(hipMemcpyAsync(Tcw_out, d_T, sizeof(PslPose), hipMemcpyDeviceToHost, st));
+    if (nedges + nlil >= 3) {
+        if (nedges) PSL_HIP(hipMemcpyAsync(outlier, d_out, (size_t)nedges, hipMemcpyDeviceToHost, st));
+        if (nlil) PSL_HIP(hipMemcpyAsync(outlier_lil, d_outl, (size_t)nlil, hipMemcpyDeviceToHost, st));
+    }
+    PSL_HIP(hipMemcpyAsync(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    *ngood = ng;
+    return PSLFE_OK;
+}
+
+int pslfe_pose_lil_edges_device(pslfe_ctx* ctx, int nframes, const double* d_le_l, int le_stride, const double* d_cross2d, int plane_stride,
+                                const int32_t* d_nplanes, const int32_t* d_lil_index, const PslMapLil* d_map, int nmap, PslPoseLilEdge* d_lil,
+                                int32_t* d_edge_plane, int32_t* d_nlil, int lstride) {
+    static const char* who = "pslfe_pose_lil_edges_device";
+    PSL_REQUIRE(nframes >= 0 && le_stride >= 0 && plane_stride >= 0 && nmap >= 0 && lstride >= 0, PSLFE_E_INVALID,
+                "%s: nframes = %d, le_stride = %d, plane_stride = %d, nmap = %d, lstride = %d", who, nframes, le_stride, plane_stride, nmap, lstride);
+    if (nframes == 0) return PSLFE_OK;
+    PSL_REQUIRE(ctx && d_nplanes && d_nlil, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE(plane_stride == 0 || (d_cross2d && d_lil_index), PSLFE_E_INVALID, "%s: NULL planes with plane_stride = %d", who, plane_stride);
+    PSL_REQUIRE(le_stride == 0 || d_le_l, PSLFE_E_INVALID, "%s: NULL mvle_l rows with le_stride = %d", who, le_stride);
+    PSL_REQUIRE(nmap == 0 || d_map, PSLFE_E_INVALID, "%s: NULL map LILs with nmap = %d", who, nmap);
+    PSL_REQUIRE(lstride == 0 || d_lil, PSLFE_E_INVALID, "%s: NULL edges with lstride = %d", who, lstride);
+    PSL_HIP(hipSetDevice(ctx->device));
+    PoseLilEdgeArgs A;
+    A.le_l = d_le_l; A.cross2d = d_cross2d; A.nplanes = d_nplanes; A.lil_index = d_lil_index; A.map = d_map;
+    A.le_stride = le_stride; A.plane_stride = plane_stride; A.nmap = nmap;
+    A.lil = d_lil; A.edge_plane = d_edge_plane; A.nlil = d_nlil; A.lstride = lstride;
+    {
+        PSL_STAGE_BEGIN(ctx, "pose.lil_edges");
+        k_pose_lil_edges<<<nframes, 256, 0, ctx->stream>>>(A);
+        PSL_STAGE_END(ctx, "pose.lil_edges");
+    }
+    PSL_HIP(hipGetLastError());
     return PSLFE_OK;
 }
 

@@ -468,6 +468,20 @@ public:
         check(pslfe_glue_lines3d_device(h_, &d, stride), "pslfe_glue_lines3d_device");
         return d;
     }
+    // device view of the last batch's mvle_l ([maxBatch][leStride][6]) and CrossPoint_2D ([maxBatch][planeStride][2]) with their counts
+    struct LilObs {
+        const double* d_leL = nullptr;
+        const double* d_cross2d = nullptr;
+        const int32_t* d_ncross = nullptr;
+        const int32_t* d_nplanes = nullptr;
+        int leStride = 0, planeStride = 0;
+    };
+    LilObs lilObsDevice() const {
+        LilObs o;
+        check(pslfe_glue_lil_obs_device(h_, &o.d_leL, &o.leStride, &o.d_ncross, &o.d_cross2d, &o.planeStride, &o.d_nplanes),
+              "pslfe_glue_lil_obs_device");
+        return o;
+    }
 private:
     pslfe_glue* h_ = nullptr;
     int maxFans_;
@@ -1141,9 +1155,9 @@ private:
     pslfe_kf* h_ = nullptr;
 };
 
-// == Optimizer (include/Optimizer.h:58): the point edges of PoseOptimization, src/Optimizer.cc:239-1023.  The LIL edges (:619-694,
-//    :973-1008) are not built: the result is the reference's only for a frame whose mvpMapInsecs holds no live entry, and a caller
-//    with live entries keeps the host g2o call.  Parity with g2o itself is unpinned.
+// == Optimizer (include/Optimizer.h:58): PoseOptimization, src/Optimizer.cc:239-1023: the monocular and stereo point edges and the
+//    LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the overloads and methods that take PslPoseLilEdge rows).  Parity with g2o
+//    itself is unpinned.
 class Optimizer {
 public:
     // int Optimizer::PoseOptimization(Frame* pFrame): edges = one PslPoseEdge per non-NULL pFrame->mvpMapPoints[i] in keypoint order
@@ -1156,12 +1170,39 @@ public:
         check(pslfe_pose_optimize(ctx.get(), &Tcw, edges.data(), (int)edges.size(), &cam, &Tcw, outlier.data(), &ngood), "pslfe_pose_optimize");
         return ngood;
     }
+    // The same with the frame's LIL edges: lil = one PslPoseLilEdge per live, not bad pFrame->mvpMapInsecs[i] in plane order (:631-693);
+    // outlierLil[e] = mvbOutlier_Insec of the edge's plane.  The return value counts every LIL edge as good (:1022).
+    static int PoseOptimization(Context& ctx, PslPose& Tcw, const std::vector<PslPoseEdge>& edges, const std::vector<PslPoseLilEdge>& lil,
+                                const PslCamera& cam, std::vector<uint8_t>& outlier, std::vector<uint8_t>& outlierLil) {
+        outlier.assign(edges.size(), 0);
+        outlierLil.assign(lil.size(), 0);
+        int ngood = 0;
+        check(pslfe_pose_optimize_lil(ctx.get(), &Tcw, edges.data(), (int)edges.size(), lil.data(), (int)lil.size(), &cam, &Tcw, outlier.data(),
+                                      outlierLil.data(), &ngood), "pslfe_pose_optimize_lil");
+        return ngood;
+    }
     // K frames in one launch, HBM to HBM, asynchronous on the context's stream (the many-frames mode): pslfe_pose_optimize_device
     static void PoseOptimizationDevice(Context& ctx, int nframes, const PslPose* d_TcwIn, const PslPoseEdge* d_edges, const int32_t* d_nedges,
                                        int estride, const PslCamera& cam, PslPose* d_TcwOut, uint8_t* d_outlier, int32_t* d_ngood,
                                        PslPoseInfo* d_info = nullptr) {
         check(pslfe_pose_optimize_device(ctx.get(), nframes, d_TcwIn, d_edges, d_nedges, estride, &cam, d_TcwOut, d_outlier, d_ngood, d_info),
               "pslfe_pose_optimize_device");
+    }
+    // the same with LIL edges: pslfe_pose_optimize_lil_device
+    static void PoseOptimizationLilDevice(Context& ctx, int nframes, const PslPose* d_TcwIn, const PslPoseEdge* d_edges, const int32_t* d_nedges,
+                                          int estride, const PslPoseLilEdge* d_lil, const int32_t* d_nlil, int lstride, const PslCamera& cam,
+                                          PslPose* d_TcwOut, uint8_t* d_outlier, uint8_t* d_outlierLil, int32_t* d_ngood,
+                                          PslPoseInfo* d_info = nullptr) {
+        check(pslfe_pose_optimize_lil_device(ctx.get(), nframes, d_TcwIn, d_edges, d_nedges, estride, d_lil, d_nlil, lstride, &cam, d_TcwOut,
+                                             d_outlier, d_outlierLil, d_ngood, d_info), "pslfe_pose_optimize_lil_device");
+    }
+    // the LIL set-up loop :631-693 for nframes frames, HBM to HBM: pslfe_pose_lil_edges_device (the observation arrays are those of
+    // FrameGlue::lilObsDevice)
+    static void LilEdgesDevice(Context& ctx, int nframes, const double* d_leL, int leStride, const double* d_cross2d, int planeStride,
+                               const int32_t* d_nplanes, const int32_t* d_lilIndex, const PslMapLil* d_map, int nmap, PslPoseLilEdge* d_lil,
+                               int32_t* d_edgePlane, int32_t* d_nlil, int lstride) {
+        check(pslfe_pose_lil_edges_device(ctx.get(), nframes, d_leL, leStride, d_cross2d, planeStride, d_nplanes, d_lilIndex, d_map, nmap, d_lil,
+                                          d_edgePlane, d_nlil, lstride), "pslfe_pose_lil_edges_device");
     }
     // F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:127) for nframes frames, HBM to HBM: pslfe_pose_mp_index_from_matches_device
     static void MapPointIndexFromMatchesDevice(FrameGrid& frame, int nframes, const int32_t* d_match, const int32_t* d_owner, const int32_t* d_nq,
