@@ -1,9 +1,15 @@
-// The per-edge arithmetic, the 6x6 solve and the SE3 update of the pose optimisation (pslfe_pose.hip), as functions of one thread.
-// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp / pose_lil_main.cpp for their host loops, so both
-// run the same single IEEE operations (build with -ffp-contract=off).  Restated from the reference's g2o:
+// The pose optimisation (pslfe_pose.hip) as functions of one thread: the per-edge arithmetic, the 6x6 solve, the SE3 update and the
+// Levenberg driver (psl_po_rounds: the four rounds, the iterations and trials of a round, every decision g2o makes between two sums).
+// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp for its host loop, so both run
+// the same single IEEE operations (build with -ffp-contract=off).  The driver asks its `Sums` argument for everything that is summed
+// over the edges; the order of those sums is not here but in the `Sums`.  The host loop instantiates the driver; k_pose_optimize
+// holds the same loop written out (the header of pslfe_pose.hip says why), so the two are changed together.  Restated from the
+// reference's g2o:
 //   edge errors / Jacobians   Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp} (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose)
 //   SE3Quat, exp, product     Thirdparty/g2o/g2o/types/se3quat.h, se3_ops.hpp
 //   quadratic form, Huber     Thirdparty/g2o/g2o/core/base_unary_edge.hpp, robust_kernel_impl.cpp
+//   the rounds                src/Optimizer.cc:696-780, :1011-1022
+//   one iteration, the loop   Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189, sparse_optimizer.cpp:354-419
 // Eigen is not in the reference tree, so where g2o hands a step to Eigen (quaternion <-> matrix, quaternion * vector, the products
 // of small matrices) the order written here is this library's: sums run in index order, left to right.  DESIGN.md §3, §5.0k.
 #ifndef PSL_POSE_KERNELS_H
@@ -422,7 +428,7 @@ PSL_PO_HD int psl_po_step_ok(const double* x) {
 // The state of OptimizationAlgorithmLevenberg between two solves of a round (optimization_algorithm_levenberg.cpp)
 struct PslPoseLM {
     double lambda, ni;
-    int nbad;
+    int nbad;   // _nBad: iterations in a row that gained less than 1e-3 of their chi2
 };
 
 // computeLambdaInit (:166-180): tau * max |H_jj|
@@ -450,6 +456,80 @@ PSL_PO_HD double psl_po_good_scale(double rho) {
     double alpha = 1.0 - (t * t) * t;
     alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;    // std::min(alpha, upper)
     return (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);     // std::max(lower, alpha)
+}
+
+// The four rounds of PoseOptimization on one vertex, each up to ten Levenberg iterations of up to ten trials.  Sums supplies what is
+// summed over the edges (in its own, fixed order) and takes the results of a round:
+//   int round                          the round index, set here; from round 1 on an edge whose outlier byte is set is not active
+//   system(T, robust, acc)             the 28 sums (PSL_POSE_NTERMS) of the active edges at T
+//   chi(T, robust)                     the robust chi2 of the active edges at T
+//   classify(T, &nbad, &nbad_lil)      the outlier bytes of ALL edges at T and the count of either kind
+//   round_done(r, its)                 round r has run its iterations (PslPoseInfo)
+// nt: the edges of both kinds, at least 3.  sctab: the table of psl_sincos_glibc.h.  T_out: the pose of the last round; nbad_out:
+// its outlying POINT edges - nInitialCorrespondences - nBad (:1022) counts an outlying LIL edge as good.
+#define PSL_POSE_DBL_MAX 1.79769313486231570815e+308
+template <class Sums>
+PSL_PO_HD void psl_po_rounds(Sums& S, const PslSE3& T0, int nt, const double* sctab, PslSE3* T_out, int* nbad_out) {
+    int nbad = 0, nbad_lil = 0;
+    PslSE3 T = T0;
+    for (int r = 0; r < 4; ++r) {
+        S.round = r;
+        T = T0;                       // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) (:719)
+        const bool robust = r < 3;    // e->setRobustKernel(0) after round index 2 (:749)
+        int its = 0;
+        if (nt - nbad - nbad_lil > 0) {   // without an active edge g2o has no vertex to optimise and optimize() returns at once
+            PslPoseLM lm = {0.0, 2.0, 0};
+            for (int it = 0; it < 10; ++it) {
+                double acc[PSL_POSE_NTERMS];
+                S.system(T, robust, acc);
+                double b[6];
+                for (int j = 0; j < 6; ++j) b[j] = -acc[21 + j];
+                double chi = acc[27];
+                const double ini_chi = chi;
+                if (it == 0) { lm.lambda = psl_po_lambda_init(acc); lm.ni = 2.0; lm.nbad = 0; }
+                double rho = 0.0;
+                int qmax = 0;
+                do {
+                    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                    int ok = psl_po_solve6(acc, lm.lambda, b, x);
+                    if (ok && !psl_po_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
+                        ok = 0;
+                        for (int j = 0; j < 6; ++j) x[j] = 0.0;
+                    }
+                    double temp_chi = PSL_POSE_DBL_MAX;   // a failed solve (:120)
+                    PslSE3 Tn = T;
+                    if (ok) {
+                        PslSE3 dT;
+                        psl_po_exp(x, &dT, sctab);
+                        psl_po_mul(&dT, &T, &Tn);          // oplusImpl: exp(update) * estimate
+                        temp_chi = S.chi(Tn, robust);
+                    }
+                    rho = psl_po_rho(chi, temp_chi, x, b, lm.lambda);
+                    if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_POSE_DBL_MAX) {
+                        lm.lambda = lm.lambda * psl_po_good_scale(rho);
+                        lm.ni = 2.0;
+                        chi = temp_chi;
+                        T = Tn;
+                    } else {
+                        lm.lambda = lm.lambda * lm.ni;
+                        lm.ni = lm.ni * 2.0;
+                    }
+                    ++qmax;
+                } while (rho < 0 && qmax < 10);
+                ++its;
+                if (qmax == 10 || rho == 0) break;                                    // Terminate
+                if ((ini_chi - chi) * 1e3 < ini_chi) ++lm.nbad; else lm.nbad = 0;     // the _nBad rule
+                if (lm.nbad >= 3) break;
+            }
+        }
+        // the plain chi2 of every edge at the round's pose, as a float, against 5.991f / 7.815f (:724-780) and of every LIL edge
+        // against 11.07f (:977-1008)
+        S.classify(T, &nbad, &nbad_lil);
+        S.round_done(r, its);
+        if (nt < 10) break;   // optimizer.edges().size() < 10: all edges, not the active ones (:1011)
+    }
+    *T_out = T;
+    *nbad_out = nbad;
 }
 
 #endif

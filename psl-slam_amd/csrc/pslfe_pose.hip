@@ -1,10 +1,17 @@
 // libpslfe: Optimizer::PoseOptimization (src/Optimizer.cc:239-1023), its point edges and its LIL edges, for K frames in one launch.
 // Product code.
-// Reference behaviour restated (in double, in the reference's order of decisions; the arithmetic is in pose_kernels.h):
+// Reference behaviour restated (in double, in the reference's order of decisions):
 //   edge set-up, the four rounds, the classification after a round   src/Optimizer.cc:282-363, :696-780, :1011-1022
 //   one iteration: lambda, trials, rho, Terminate                    Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189
 //   the iteration loop of a round                                    Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419
 //   the LIL edges: set-up, error / Jacobian, classification            src/Optimizer.cc:619-694, add_inc/EdgeLIL.h:210-439, :973-1008
+// Who owns what.  pose_kernels.h holds the arithmetic of an edge, the solve and the update, which the kernel and the host loop of
+// tools/dropin/pose_main.cpp share, and the Levenberg driver psl_po_rounds (the rounds, iterations and trials with every decision
+// between two sums), which that host loop instantiates.  k_pose_optimize keeps the same loop written out in its body: instantiating
+// the driver here gave the same registers, LDS and scratch and the same per-edge and reduction code, but launches 0.6 to 1.9 % slower
+// than this form on an MI355X (profiles/pose_driver_ab.json).  A change to the driver is a change to the loop below
+// and the reverse; tests/test_pose_*_gpu.py compare both with the numpy restatement bit for bit.  The device's own: which thread
+// owns which edge, the order of the sums (psl_pose_reduce), the LDS copy of the rows, the early return, the edge set-up kernels.
 // Scope: the monocular and stereo point edges (k_pose_optimize<false>, what pslfe_pose_optimize[_device] launch) and, in
 // k_pose_optimize<true> (pslfe_pose_optimize_lil[_device]), the LIL edges (EdgeLILSE3ProjectXYZ with its fixed VertexLIL) as well.
 // The LIL edges of a frame extend its edge index space: LIL edge j has the index n + j (g2o adds them after the point edges), so
@@ -287,6 +294,27 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
     }
 }
 
+// Ordered compaction of one chunk of 256 items of a workgroup of 256 threads: the position of this thread's item among the kept ones
+// (base + the kept items of the threads before it: a ballot inside the wave, a scan of the four wave counts through s_cnt) and base
+// moved past the chunk.  Every thread calls it (two barriers; the second lets the next chunk rewrite s_cnt).
+__device__ __forceinline__ int psl_pose_compact(bool keep, int* s_cnt, int& base) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[w] = __popcll(bal);
+    __syncthreads();
+    int wbase = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < w) wbase += s_cnt[k];
+        total += s_cnt[k];
+    }
+    const int pos = base + wbase + before;
+    base += total;
+    __syncthreads();
+    return pos;
+}
+
 // ---- the edges of a frame from its matches ------------------------------------------------------------------------------------------
 struct PoseEdgeArgs {
     FrameStore S;
@@ -306,7 +334,7 @@ struct PoseEdgeArgs {
 // four wave counts
 __global__ __launch_bounds__(256) void k_pose_edges(PoseEdgeArgs A) {
     __shared__ int s_cnt[4];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int f = blockIdx.x, tid = threadIdx.x;
     const int slot = A.slot0 + f;
     const int n = min(A.S.meta[slot].n, A.S.cap);
     const PslKeyPoint* kps = A.S.kps + (size_t)slot * A.S.cap;
@@ -323,17 +351,7 @@ __global__ __launch_bounds__(256) void k_pose_edges(PoseEdgeArgs A) {
             m = idx[i];
             if (m < 0 || m >= A.mpstride) m = -1;
         }
-        const unsigned long long bal = __ballot(m >= 0);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cnt[w] = __popcll(bal);
-        __syncthreads();
-        int wbase = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < w) wbase += s_cnt[k];
-            total += s_cnt[k];
-        }
-        const int pos = base + wbase + before;
+        const int pos = psl_pose_compact(m >= 0, s_cnt, base);
         if (m >= 0 && pos < A.estride) {
             const PslKeyPoint kp = kps[i];
             const int oct = min(max(kp.octave, 0), A.nlevels - 1);
@@ -343,8 +361,6 @@ __global__ __launch_bounds__(256) void k_pose_edges(PoseEdgeArgs A) {
             edges[pos] = e;
             if (edge_kp) edge_kp[pos] = i;
         }
-        base += total;
-        __syncthreads();   // s_cnt is rewritten by the next chunk
     }
     if (tid == 0) A.nedges[f] = base;
 }
@@ -390,7 +406,7 @@ struct PoseLilEdgeArgs {
 // takes row i of mvle_l and row i of CrossPoint_2D, as the reference does (:658-660).
 __global__ __launch_bounds__(256) void k_pose_lil_edges(PoseLilEdgeArgs A) {
     __shared__ int s_cnt[4];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int f = blockIdx.x, tid = threadIdx.x;
     if (A.nplanes[f] > min(A.plane_stride, A.le_stride)) {   // uniform: planes the rows cannot hold are reported, not dropped
         if (tid == 0) A.nlil[f] = PSLFE_E_CAPACITY;
         return;
@@ -410,17 +426,7 @@ __global__ __launch_bounds__(256) void k_pose_lil_edges(PoseLilEdgeArgs A) {
             if (q < 0 || q >= A.nmap) q = -1;          // mvpMapInsecs[i] == NULL
             else if (A.map[q].bad) q = -1;             // mbBad (:634)
         }
-        const unsigned long long bal = __ballot(q >= 0);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cnt[w] = __popcll(bal);
-        __syncthreads();
-        int wbase = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < w) wbase += s_cnt[k];
-            total += s_cnt[k];
-        }
-        const int pos = base + wbase + before;
+        const int pos = psl_pose_compact(q >= 0, s_cnt, base);
         if (q >= 0 && pos < A.lstride) {
             PslPoseLilEdge e;
             const double* W = A.map[q].w;
@@ -430,8 +436,6 @@ __global__ __launch_bounds__(256) void k_pose_lil_edges(PoseLilEdgeArgs A) {
             lil[pos] = e;
             if (edge_plane) edge_plane[pos] = i;
         }
-        base += total;
-        __syncthreads();   // s_cnt is rewritten by the next chunk
     }
     if (tid == 0) A.nlil[f] = base;
 }
@@ -454,6 +458,40 @@ int pose_launch(pslfe_ctx* ctx, int nframes, const PslPose* d_Tin, const PslPose
         PSL_STAGE_END(ctx, "pose.optimize");
     }
     PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+
+// the host form of one frame: upload, launch k_pose_optimize<LIL>, download.  who: the entry point, which has checked its arguments;
+// without LIL the LIL arguments are not used.
+template <bool LIL>
+int pose_host_form(pslfe_ctx* ctx, const char* who, const PslPose* Tcw, const PslPoseEdge* edges, int nedges, const PslPoseLilEdge* lil,
+                   int nlil, const PslCamera* cam, PslPose* Tcw_out, uint8_t* outlier, uint8_t* outlier_lil, int* ngood) {
+    PSL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    hipError_t e = hipSuccess;
+    const int32_t n32 = nedges, m32 = nlil;
+    PoseLilArgs B = {nullptr, nullptr, 0, nullptr};
+    PslPose* d_T = psl_scratch_up(ctx, Tcw, 1, st, &e);
+    const PslPoseEdge* d_edges = psl_scratch_up(ctx, nedges ? edges : nullptr, (size_t)nedges, st, &e);
+    if constexpr (LIL) B.lil = psl_scratch_up(ctx, nlil ? lil : nullptr, (size_t)nlil, st, &e);
+    const int32_t* d_n = psl_scratch_up(ctx, &n32, 1, st, &e);
+    if constexpr (LIL) B.nlil = psl_scratch_up(ctx, &m32, 1, st, &e);
+    uint8_t* d_out = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);   // outputs: not read, not written below 3 edges
+    if constexpr (LIL) B.outlier = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nlil, st, &e);
+    int32_t* d_ng = psl_scratch_up(ctx, (const int32_t*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
+    B.lstride = nlil;
+    if (int rc = pose_launch<LIL>(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr, B)) return rc;
+    int32_t ng = 0;
+    PSL_HIP(hipMemcpyAsync(Tcw_out, d_T, sizeof(PslPose), hipMemcpyDeviceToHost, st));
+    if (nedges + nlil >= 3) {
+        if (nedges) PSL_HIP(hipMemcpyAsync(outlier, d_out, (size_t)nedges, hipMemcpyDeviceToHost, st));
+        if (nlil) PSL_HIP(hipMemcpyAsync(outlier_lil, B.outlier, (size_t)nlil, hipMemcpyDeviceToHost, st));
+    }
+    PSL_HIP(hipMemcpyAsync(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    *ngood = ng;
     return PSLFE_OK;
 }
 
@@ -480,25 +518,7 @@ int pslfe_pose_optimize(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdge* e
     PSL_REQUIRE(nedges >= 0, PSLFE_E_INVALID, "%s: nedges = %d", who, nedges);
     PSL_REQUIRE(ctx && cam && Tcw && Tcw_out && ngood, PSLFE_E_INVALID, "%s: NULL argument", who);
     PSL_REQUIRE(nedges == 0 || (edges && outlier), PSLFE_E_INVALID, "%s: NULL edges or outlier bytes with nedges = %d", who, nedges);
-    PSL_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (int rc = psl_scratch_begin(ctx)) return rc;
-    hipError_t e = hipSuccess;
-    const int32_t n32 = nedges;
-    PslPose* d_T = psl_scratch_up(ctx, Tcw, 1, st, &e);
-    const PslPoseEdge* d_edges = psl_scratch_up(ctx, nedges ? edges : nullptr, (size_t)nedges, st, &e);
-    const int32_t* d_n = psl_scratch_up(ctx, &n32, 1, st, &e);
-    uint8_t* d_out = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);   // an output: not read, not written below 3 edges
-    int32_t* d_ng = psl_scratch_up(ctx, (const int32_t*)nullptr, 1, st, &e);
-    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
-    if (int rc = pose_launch<false>(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr)) return rc;
-    int32_t ng = 0;
-    PSL_HIP(hipMemcpyAsync(Tcw_out, d_T, sizeof(PslPose), hipMemcpyDeviceToHost, st));
-    if (nedges >= 3) PSL_HIP(hipMemcpyAsync(outlier, d_out, (size_t)nedges, hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipMemcpyAsync(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    *ngood = ng;
-    return PSLFE_OK;
+    return pose_host_form<false>(ctx, who, Tcw, edges, nedges, nullptr, 0, cam, Tcw_out, outlier, nullptr, ngood);
 }
 
 int pslfe_pose_optimize_lil_device(pslfe_ctx* ctx, int nframes, const PslPose* d_Tcw_in, const PslPoseEdge* d_edges, const int32_t* d_nedges,
@@ -524,32 +544,7 @@ int pslfe_pose_optimize_lil(pslfe_ctx* ctx, const PslPose* Tcw, const PslPoseEdg
     PSL_REQUIRE(ctx && cam && Tcw && Tcw_out && ngood, PSLFE_E_INVALID, "%s: NULL argument", who);
     PSL_REQUIRE(nedges == 0 || (edges && outlier), PSLFE_E_INVALID, "%s: NULL edges or outlier bytes with nedges = %d", who, nedges);
     PSL_REQUIRE(nlil == 0 || (lil && outlier_lil), PSLFE_E_INVALID, "%s: NULL LIL edges or outlier bytes with nlil = %d", who, nlil);
-    PSL_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (int rc = psl_scratch_begin(ctx)) return rc;
-    hipError_t e = hipSuccess;
-    const int32_t n32 = nedges, m32 = nlil;
-    PslPose* d_T = psl_scratch_up(ctx, Tcw, 1, st, &e);
-    const PslPoseEdge* d_edges = psl_scratch_up(ctx, nedges ? edges : nullptr, (size_t)nedges, st, &e);
-    const PslPoseLilEdge* d_lil = psl_scratch_up(ctx, nlil ? lil : nullptr, (size_t)nlil, st, &e);
-    const int32_t* d_n = psl_scratch_up(ctx, &n32, 1, st, &e);
-    const int32_t* d_m = psl_scratch_up(ctx, &m32, 1, st, &e);
-    uint8_t* d_out = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);   // outputs: not read, not written below 3 edges
-    uint8_t* d_outl = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nlil, st, &e);
-    int32_t* d_ng = psl_scratch_up(ctx, (const int32_t*)nullptr, 1, st, &e);
-    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
-    const PoseLilArgs B = {d_lil, d_m, nlil, d_outl};
-    if (int rc = pose_launch<true>(ctx, 1, d_T, d_edges, d_n, nedges, cam, d_T, d_out, d_ng, nullptr, B)) return rc;
-    int32_t ng = 0;
-    PSL_HIP(hipMemcpyAsync(Tcw_out, d_T, sizeof(PslPose), hipMemcpyDeviceToHost, st));
-    if (nedges + nlil >= 3) {
-        if (nedges) PSL_HIP(hipMemcpyAsync(outlier, d_out, (size_t)nedges, hipMemcpyDeviceToHost, st));
-        if (nlil) PSL_HIP(hipMemcpyAsync(outlier_lil, d_outl, (size_t)nlil, hipMemcpyDeviceToHost, st));
-    }
-    PSL_HIP(hipMemcpyAsync(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost, st));
-    PSL_HIP(hipStreamSynchronize(st));
-    *ngood = ng;
-    return PSLFE_OK;
+    return pose_host_form<true>(ctx, who, Tcw, edges, nedges, lil, nlil, cam, Tcw_out, outlier, outlier_lil, ngood);
 }
 
 int pslfe_pose_lil_edges_device(pslfe_ctx* ctx, int nframes, const double* d_le_l, int le_stride, const double* d_cross2d, int plane_stride,

@@ -121,8 +121,39 @@ def ref():
     print("ref", len(cases), int(out["walk_counts"].sum()), len(xs), len(nk))
 
 
+def pose_pins():
+    """pose_restatement_pins.npz: what pose_opt_cases.optimize and pose_lil_cases.optimize return on every case of their CASE_NAMES in
+    both orders (tests/test_pose_lil_cpu.py compares the restatement with it bit for bit).  Written from the two separate drivers the
+    restatement had before they became one; written again, it only pins the restatement against itself."""
+    import pose_lil_cases as lc
+    import pose_opt_cases as pc
+    out = {}
+
+    def put(key, pose, flags, ngood, info, margin):
+        out[key + "/pose"] = np.frombuffer(pose.tobytes(), np.uint8)
+        for k, f in flags.items():
+            out[f"{key}/{k}"] = np.zeros(0, np.uint8) if f is None else np.asarray(f, np.uint8)
+            out[f"{key}/{k}_none"] = np.bool_(f is None)
+        out[key + "/ngood"], out[key + "/info"], out[key + "/margin"] = np.int32(ngood), np.frombuffer(info.tobytes(), np.uint8), np.float64(margin)
+
+    for nm in pc.CASE_NAMES:
+        c = pc.case(nm)
+        for order in ("device", "edge"):
+            pose, outlier, ngood, info, margin = pc.optimize(c["Tcw"], c["edges"], c["cam"], order)
+            put(f"points/{nm}/{order}", pose, {"outlier": outlier}, ngood, info, margin)
+    for nm in lc.CASE_NAMES:
+        c = lc.case(nm)
+        for order in ("device", "edge"):
+            pose, outlier, outlier_lil, ngood, info, margin = lc.optimize(c["Tcw"], c["edges"], c["lil"], c["cam"], order)
+            put(f"lil/{nm}/{order}", pose, {"outlier": outlier, "outlier_lil": outlier_lil}, ngood, info, margin)
+    np.savez_compressed(os.path.join(HERE, "pose_restatement_pins.npz"), **out)
+    print("pose_pins", len(pc.CASE_NAMES), len(lc.CASE_NAMES), len(out))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["lines", "main", "glue"]
+    if "pose_pins" in which:
+        pose_pins()
     if "ref" in which:
         ref()
     if "lines" in which:

@@ -2,11 +2,11 @@
 add_inc/EdgeLIL.h:210-439, src/Optimizer.cc:619-694, :973-1008) on top of tests/pose_opt_cases.py, the restated set-up loop
 (:631-693) and the seeded cases of tests/test_pose_lil_cpu.py / test_pose_lil_gpu.py.
 
-The LIL part mirrors the psl_po_lil_* functions of psl-slam_amd/csrc/pose_kernels.h operation by operation and the LIL branches of
-psl-slam_amd/csrc/pslfe_pose.hip decision by decision.  A LIL edge adds its 28 terms ROW BY ROW: each of its six Jacobian rows is a
-rank-one contribution that is added to the running sum before the next row is made, so an edge is a sequence of six additions (a point
-edge is one).  order="device" runs these sequences in the device's order of the sums (LIL edge j has the edge index n + j),
-order="edge" edge by edge, points first, which is g2o's.
+_Lil mirrors the psl_po_lil_* functions of psl-slam_amd/csrc/pose_kernels.h operation by operation; it is an edge kind of
+pose_opt_cases.levenberg_rounds, which holds the rounds, iterations and trials for both kinds.  A LIL edge adds its 28 terms ROW BY
+ROW: each of its six Jacobian rows is a rank-one contribution that is added to the running sum before the next row is made, so an
+edge is a sequence of six additions (a point edge is one).  order="device" runs these sequences in the device's order of the sums
+(LIL edge j has the edge index n + j), order="edge" edge by edge, points first, which is g2o's.
 
 Two oddities of the reference are restated on purpose:
   * linearizeOplus reads segment<3>(9) for xyz2_s and xyz2_e (EdgeLIL.h:273-275): row 2 of the Jacobian is evaluated at line 2's END
@@ -25,7 +25,6 @@ LIL_DTYPE = np.dtype([("line1", "<f8", (6,)), ("line2", "<f8", (6,)), ("cross", 
 MAPLIL_DTYPE = np.dtype([("w", "<f8", (15,)), ("bad", "u1"), ("pad", "u1", (7,))])
 DELTA_LIL = float(np.float32(math.sqrt(11.07)))       # float deltaLJL = sqrt(11.07)  (src/Optimizer.cc:628)
 CHI2_LIL = np.float32(11.07)
-LANES, GROUP = pc.LANES, pc.GROUP
 MARGIN = pc.MARGIN
 
 
@@ -39,6 +38,19 @@ class _Lil:
         self.ins = [l["obs_ins"][:, 0].copy(), l["obs_ins"][:, 1].copy()]
         self.fx, self.fy, self.cx, self.cy = (float(np.float32(cam[k])) for k in ("fx", "fy", "cx", "cy"))
         self.fix_row2 = fix_row2
+        self.thr = np.full(self.m, CHI2_LIL)                                     # chi2LLIL (src/Optimizer.cc:704, :993)
+
+    # an edge kind of pc.levenberg_rounds: six additions per edge; an outlier does NOT lower the return value (nBad counts the point
+    # edges only, src/Optimizer.cc:1022)
+    steps, counted = 6, False
+    count = property(lambda self: self.m)
+
+    def chi(self, T):
+        e = self.error(T)
+        return e, self.chi2(e)
+
+    def additions(self, e, T, rho0, rho1):
+        return self.rows(e, T, rho0, rho1)
 
     def _map(self, T, X):
         r = pc._rotate(T[0], X)
@@ -117,145 +129,12 @@ class _Lil:
         return out
 
 
-def _sequences(pterms, lrows):
-    """[n][k] point terms and [m][6][k] LIL rows -> [n + m][6][k]: the additions of every edge (a point edge has one; the rest is +0,
-    which changes no bit of a sum that starts at +0)."""
-    n, m, k = len(pterms), len(lrows), pterms.shape[1] if len(pterms) else lrows.shape[2]
-    seq = np.zeros((n + m, 6, k))
-    if n:
-        seq[:n, 0] = pterms
-    if m:
-        seq[n:] = lrows
-    return seq
-
-
-def sum_device(seq, active):
-    """pc.sum_device with six additions per edge: partial sum p takes the edges p, p + 256, ... in ascending order and, of each, its
-    additions in order; then the butterfly in each group of 64 and the four group sums from left to right."""
-    nt, _, k = seq.shape
-    c = max(-(-nt // LANES), 1)
-    P = np.zeros((c * LANES, 6, k))
-    P[:nt] = np.where(active[:, None, None], seq, 0.0)
-    P = P.reshape(c, LANES, 6, k)
-    part = np.zeros((LANES, k))
-    for ci in range(c):
-        for s in range(6):
-            part = part + P[ci, :, s]
-    g = part.reshape(LANES // GROUP, GROUP, k)
-    s = GROUP // 2
-    while s >= 1:
-        g[:, :s] = g[:, :s] + g[:, s:2 * s]
-        s //= 2
-    G = g[:, 0]
-    return ((G[0] + G[1]) + G[2]) + G[3]
-
-
-def sum_edge(seq, active, n):
-    """Edge by edge in index order, of a LIL edge (index >= n) its six rows in order: g2o's order of the edges."""
-    s = np.zeros(seq.shape[2])
-    for i in np.flatnonzero(active):
-        for r in range(6 if i >= n else 1):
-            s = s + seq[i, r]
-    return s
-
-
 def optimize(Tcw, edges, lil, cam, order="device", fix_row2=False):
-    """-> (pose_out, outlier u8 [n] or None, outlier_lil u8 [m] or None, ngood, info, margin); None when nothing is written"""
-    info = np.zeros((), pc.INFO_DTYPE)
-    Tcw = np.ascontiguousarray(Tcw, pc.POSE_DTYPE).reshape(())
-    n, m = len(edges), len(lil)
-    nt = n + m
-    if nt < 3:
-        return Tcw.copy(), None, None, 0, info, math.inf
-    E, L = pc._Edges(edges, cam), _Lil(lil, cam, fix_row2)
-    red = (lambda seq, act: sum_device(seq, act)) if order == "device" else (lambda seq, act: sum_edge(seq, act, n))
-    T0 = pc.from_pose(Tcw)
-    thr = np.where(E.mono, pc.CHI2_MONO, pc.CHI2_STEREO)
-    outlier, outlier_lil = np.zeros(n, bool), np.zeros(m, bool)
-    nbad, nbad_lil, margin, T = 0, 0, math.inf, T0
-
-    def chis(Tx, robust):
-        c = E.chi2(E.error(Tx)[0])
-        cl = L.chi2(L.error(Tx))
-        r0 = E.huber(c)[0] if robust else c
-        rl = L.huber(cl)[0] if robust else cl
-        lr = np.zeros((m, 6, 1))
-        lr[:, 0, 0] = rl
-        return _sequences(r0[:, None], lr)
-
-    with np.errstate(all="ignore"):
-        for r in range(4):
-            T = T0
-            robust = r < 3
-            active = np.concatenate([~outlier, ~outlier_lil])
-            its = 0
-            if nt - nbad - nbad_lil > 0:
-                lam, ni, lm_bad = 0.0, 2.0, 0
-                for it in range(10):
-                    e, Pc = E.error(T)
-                    c = E.chi2(e)
-                    rho0, rho1 = E.huber(c) if robust else (c, np.ones(n))
-                    el = L.error(T)
-                    cl = L.chi2(el)
-                    rl0, rl1 = L.huber(cl) if robust else (cl, np.ones(m))
-                    acc = red(_sequences(E.terms(e, Pc, rho0, rho1), L.rows(el, T, rl0, rl1)), active)
-                    b = [-float(v) for v in acc[21:27]]
-                    chi = float(acc[27])
-                    ini_chi = chi
-                    if it == 0:
-                        mx = 0.0
-                        for h in (0, 6, 11, 15, 18, 20):
-                            a = abs(float(acc[h]))
-                            mx = mx if a < mx else a
-                        lam, ni, lm_bad = 1e-5 * mx, 2.0, 0
-                    rho, qmax = 0.0, 0
-                    while True:
-                        x = pc.solve6(acc, lam, b)
-                        if x is not None and not (math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < pc.THETA_MAX):
-                            x = None
-                        temp_chi, Tn = pc.DBL_MAX, T
-                        if x is not None:
-                            Tn = pc.se3_mul(pc.se3_exp(x), T)
-                            temp_chi = float(red(chis(Tn, robust), active)[0])
-                        else:
-                            x = [0.0] * 6
-                        scale = 0.0
-                        for j in range(6):
-                            scale = scale + x[j] * (lam * x[j] + b[j])
-                        scale = scale + 1e-3
-                        rho = pc._div(chi - temp_chi, scale)
-                        if rho > 0 and math.isfinite(temp_chi):
-                            t = 2.0 * rho - 1.0
-                            alpha = 1.0 - (t * t) * t
-                            alpha = (2.0 / 3.0) if (2.0 / 3.0) < alpha else alpha
-                            lam = lam * (alpha if (1.0 / 3.0) < alpha else (1.0 / 3.0))
-                            ni, chi, T = 2.0, temp_chi, Tn
-                        else:
-                            lam = lam * ni
-                            ni = ni * 2.0
-                        qmax += 1
-                        if not (rho < 0 and qmax < 10):
-                            break
-                    its += 1
-                    if qmax == 10 or rho == 0:
-                        break
-                    lm_bad = lm_bad + 1 if (ini_chi - chi) * 1e3 < ini_chi else 0
-                    if lm_bad >= 3:
-                        break
-            c = E.chi2(E.error(T)[0])
-            cl = L.chi2(L.error(T))
-            outlier = c.astype(np.float32) > thr
-            outlier_lil = cl.astype(np.float32) > CHI2_LIL                     # chi2LLIL (:704, :993)
-            if n:
-                margin = min(margin, float(np.nanmin(np.abs(c - thr.astype(np.float64)) / thr)))
-            if m:
-                margin = min(margin, float(np.nanmin(np.abs(cl - float(CHI2_LIL)) / float(CHI2_LIL))))
-            nbad, nbad_lil = int(outlier.sum()), int(outlier_lil.sum())
-            info["rounds"] = r + 1
-            info["iterations"][r] = its
-            if nt < 10:
-                break
-    return pc.to_pose(T), outlier.astype(np.uint8), outlier_lil.astype(np.uint8), nt - nbad, info, margin     # nBad: point edges only (:1022)
+    """The point edges, then the LIL edges (LIL edge j has the edge index n + j)
+    -> (pose_out, outlier u8 [n] or None, outlier_lil u8 [m] or None, ngood, info, margin); None when nothing is written"""
+    pose, flags, ngood, info, margin = pc.levenberg_rounds(Tcw, [pc._Edges(edges, cam), _Lil(lil, cam, fix_row2)], order)
+    outlier, outlier_lil = (None, None) if flags is None else flags
+    return pose, outlier, outlier_lil, ngood, info, margin
 
 
 # ---- the set-up loop src/Optimizer.cc:631-693 ------------------------------------------------------------------------------------------

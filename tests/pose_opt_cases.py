@@ -1,9 +1,12 @@
 """The restatement of the point edges of Optimizer::PoseOptimization (src/Optimizer.cc:239-1023 over the reference's g2o) in numpy
 float64, and the seeded cases of tests/test_pose_opt_cpu.py / test_pose_opt_gpu.py.
 
-The restatement mirrors psl-slam_amd/csrc/pose_kernels.h operation by operation (every numpy ufunc is one IEEE operation; nothing
-here goes through BLAS) and psl-slam_amd/csrc/pslfe_pose.hip decision by decision, with math.sin / math.cos.  order="device" sums
-H, b and the robust chi2 in the device's order (the header of pslfe_pose.hip); order="edge" sums them edge by edge, which is g2o's.
+The restatement mirrors the arithmetic of psl-slam_amd/csrc/pose_kernels.h operation by operation (every numpy ufunc is one IEEE
+operation; nothing here goes through BLAS) and its driver psl_po_rounds decision by decision, with math.sin / math.cos; it shares no
+text with the C++ and is what the kernel and the host loop are judged against.  levenberg_rounds is the one place where the rounds,
+iterations and trials are written here: it runs over a list of edge kinds (_Edges below; _Lil of tests/pose_lil_cases.py), and
+optimize() here and in pose_lil_cases are calls of it.  order="device" sums H, b and the robust chi2 in the device's order (the
+header of psl-slam_amd/csrc/pslfe_pose.hip); order="edge" sums them edge by edge, which is g2o's.
 Eigen and g2o cannot be built offline: parity with g2o itself is unpinned."""
 import functools
 import math
@@ -133,6 +136,18 @@ class _Edges:
         self.mono = e["ur"] < np.float32(0)
         self.fx, self.fy, self.cx, self.cy, self.bf = (float(np.float32(cam[k])) for k in ("fx", "fy", "cx", "cy", "bf"))
         self.delta = np.where(self.mono, DELTA_MONO, DELTA_STEREO)
+        self.thr = np.where(self.mono, CHI2_MONO, CHI2_STEREO)
+
+    # an edge kind of levenberg_rounds: one addition per edge; an outlier lowers the return value
+    steps, counted = 1, True
+    count = property(lambda self: self.n)
+
+    def chi(self, T):
+        ev = self.error(T)
+        return ev, self.chi2(ev[0])
+
+    def additions(self, ev, T, rho0, rho1):
+        return self.terms(ev[0], ev[1], rho0, rho1)[:, None]
 
     def error(self, T):
         """computeError of every edge: e [3][n] (e[2] = 0 for a monocular edge), Pc [3][n]."""
@@ -182,17 +197,20 @@ class _Edges:
         return out
 
 
-def sum_device(terms, active):
-    """The order of the sums of pslfe_pose.hip: 256 partial sums over i = p, p + 256, ...; a butterfly in each group of 64; the
-    four group sums from left to right.  (A partial sum is never -0, so adding +0 for an edge the device skips changes no bit.)"""
-    n, k = terms.shape
-    m = max(-(-n // LANES), 1) * LANES
-    P = np.zeros((m, k))
-    P[:n] = np.where(active[:, None], terms, 0.0)
-    P = P.reshape(-1, LANES, k)
+def sum_device(seq, active):
+    """The order of the sums of pslfe_pose.hip on seq [nt][A][k], the up to A additions of every edge (a point edge has one, a LIL
+    edge six; the rest is +0): partial sum p of 256 takes the edges p, p + 256, ... in ascending order and, of each, its additions in
+    order; a butterfly in each group of 64; the four group sums from left to right.  (A partial sum starts at +0 and is never -0,
+    so adding +0 for an edge the device skips, or for an addition an edge does not have, changes no bit.)"""
+    nt, A, k = seq.shape
+    c = max(-(-nt // LANES), 1)
+    P = np.zeros((c * LANES, A, k))
+    P[:nt] = np.where(active[:, None, None], seq, 0.0)
+    P = P.reshape(c, LANES, A, k)
     part = np.zeros((LANES, k))
-    for c in range(P.shape[0]):
-        part = part + P[c]
+    for ci in range(c):
+        for s in range(A):
+            part = part + P[ci, :, s]
     g = part.reshape(LANES // GROUP, GROUP, k)
     s = GROUP // 2
     while s >= 1:
@@ -202,11 +220,12 @@ def sum_device(terms, active):
     return ((G[0] + G[1]) + G[2]) + G[3]
 
 
-def sum_edge(terms, active):
-    """Edge by edge in index order: g2o's."""
-    s = np.zeros(terms.shape[1])
-    for row in terms[active]:
-        s = s + row
+def sum_edge(seq, active, steps=None):
+    """Edge by edge in index order, of each edge its steps[i] additions (all A without steps) in order: g2o's order of the edges."""
+    s = np.zeros(seq.shape[2])
+    for i in np.flatnonzero(active):
+        for r in range(seq.shape[1] if steps is None else steps[i]):
+            s = s + seq[i, r]
     return s
 
 
@@ -258,33 +277,56 @@ def _div(a, b):
         return float(np.float64(a) / np.float64(b))
 
 
-def optimize(Tcw, edges, cam, order="device"):
-    """-> (pose_out POSE_DTYPE record, outlier u8 [n] or None when nothing is written, ngood, info INFO_DTYPE record, margin):
-    margin = the least relative distance |chi2 - threshold| / threshold of a classification, over every round."""
-    red = sum_device if order == "device" else sum_edge
+def levenberg_rounds(Tcw, kinds, order="device"):
+    """The four rounds of PoseOptimization with their Levenberg iterations and trials over a list of edge kinds, which share one edge
+    index space in list order.  A kind has: count; steps, the additions one of its edges makes to a sum; counted, whether its outliers
+    lower the return value; thr, the float32 thresholds of its classification; chi(T) -> (what it evaluated at T, chi2 [count]);
+    huber(chi2) -> (rho, rho'); additions(evaluated, T, rho, rho') -> [count][steps][28].
+    -> (pose_out POSE_DTYPE record, [outlier u8 [count] of each kind] or None when nothing is written, ngood, info INFO_DTYPE record,
+    margin): margin = the least relative distance |chi2 - threshold| / threshold of a classification, over every round."""
     info = np.zeros((), INFO_DTYPE)
     Tcw = np.ascontiguousarray(Tcw, POSE_DTYPE).reshape(())
-    n = len(edges)
-    if n < 3:
+    nt = sum(k.count for k in kinds)
+    if nt < 3:
         return Tcw.copy(), None, 0, info, math.inf
-    E = _Edges(edges, cam)
+    steps = np.concatenate([np.full(k.count, k.steps) for k in kinds])
+    bounds = np.cumsum([0] + [k.count for k in kinds])
+
+    def red(parts):
+        """[count][<= steps][w] of each kind, the additions of its edges -> the w sums over the active edges in the chosen order"""
+        seq = np.zeros((nt, max(k.steps for k in kinds), parts[0].shape[2]))
+        for k, p, i0 in zip(kinds, parts, bounds):
+            seq[i0:i0 + k.count, :p.shape[1]] = p
+        return sum_device(seq, active) if order == "device" else sum_edge(seq, active, steps)
+
+    def system(Tx, robust):
+        parts = []
+        for k in kinds:
+            ev, c = k.chi(Tx)
+            rho0, rho1 = k.huber(c) if robust else (c, np.ones(k.count))
+            parts.append(k.additions(ev, Tx, rho0, rho1))
+        return red(parts)
+
+    def chi_of(Tx, robust):
+        parts = []
+        for k in kinds:
+            c = k.chi(Tx)[1]
+            parts.append((k.huber(c)[0] if robust else c)[:, None, None])
+        return float(red(parts)[0])
+
     T0 = from_pose(Tcw)
-    thr = np.where(E.mono, CHI2_MONO, CHI2_STEREO)
-    outlier = np.zeros(n, bool)
-    nbad, margin, T = 0, math.inf, T0
+    outlier = [np.zeros(k.count, bool) for k in kinds]
+    nbad, margin, T = [0] * len(kinds), math.inf, T0
     with np.errstate(all="ignore"):
         for r in range(4):
             T = T0
             robust = r < 3
-            active = ~outlier
+            active = np.concatenate([~o for o in outlier])
             its = 0
-            if n - nbad > 0:
+            if nt - sum(nbad) > 0:
                 lam, ni, lm_bad = 0.0, 2.0, 0
                 for it in range(10):
-                    e, Pc = E.error(T)
-                    c = E.chi2(e)
-                    rho0, rho1 = E.huber(c) if robust else (c, np.ones(n))
-                    acc = red(E.terms(e, Pc, rho0, rho1), active)
+                    acc = system(T, robust)
                     b = [-float(v) for v in acc[21:27]]
                     chi = float(acc[27])
                     ini_chi = chi
@@ -302,10 +344,7 @@ def optimize(Tcw, edges, cam, order="device"):
                         temp_chi, Tn = DBL_MAX, T
                         if x is not None:
                             Tn = se3_mul(se3_exp(x), T)
-                            e2, _ = E.error(Tn)
-                            c2 = E.chi2(e2)
-                            r0 = E.huber(c2)[0] if robust else c2
-                            temp_chi = float(red(r0[:, None], active)[0])
+                            temp_chi = chi_of(Tn, robust)
                         else:
                             x = [0.0] * 6
                         scale = 0.0
@@ -331,16 +370,24 @@ def optimize(Tcw, edges, cam, order="device"):
                     lm_bad = lm_bad + 1 if (ini_chi - chi) * 1e3 < ini_chi else 0
                     if lm_bad >= 3:
                         break
-            e, _ = E.error(T)
-            c = E.chi2(e)
-            outlier = c.astype(np.float32) > thr
-            margin = min(margin, float(np.nanmin(np.abs(c - thr.astype(np.float64)) / thr)))
-            nbad = int(outlier.sum())
+            for i, k in enumerate(kinds):
+                c = k.chi(T)[1]
+                outlier[i] = c.astype(np.float32) > k.thr
+                if k.count:
+                    margin = min(margin, float(np.nanmin(np.abs(c - k.thr.astype(np.float64)) / k.thr)))
+                nbad[i] = int(outlier[i].sum())
             info["rounds"] = r + 1
             info["iterations"][r] = its
-            if n < 10:
+            if nt < 10:
                 break
-    return to_pose(T), outlier.astype(np.uint8), n - nbad, info, margin
+    ngood = nt - sum(b for k, b in zip(kinds, nbad) if k.counted)     # nInitialCorrespondences - nBad (src/Optimizer.cc:1022)
+    return to_pose(T), [o.astype(np.uint8) for o in outlier], ngood, info, margin
+
+
+def optimize(Tcw, edges, cam, order="device"):
+    """The point edges alone -> (pose_out, outlier u8 [n] or None when nothing is written, ngood, info, margin)"""
+    pose, flags, ngood, info, margin = levenberg_rounds(Tcw, [_Edges(edges, cam)], order)
+    return pose, None if flags is None else flags[0], ngood, info, margin
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------------------

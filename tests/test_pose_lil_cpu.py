@@ -1,6 +1,7 @@
 """The restatement of the LIL edges of the pose optimisation (tests/pose_lil_cases.py) on its own, the two reference oddities made
-visible, the ABI of the new entry points, and the stand-alone host program of tools/dropin/pose_lil_main.cpp, plain and under the
-address and undefined-behaviour sanitizers.  No GPU."""
+visible, the restatement pinned against what its two separate drivers returned before they became one, the ABI of the LIL entry
+points, and the stand-alone host program of tools/dropin/pose_main.cpp on the LIL cases, plain and under the address and
+undefined-behaviour sanitizers.  No GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -23,7 +24,7 @@ ORDER_DIFFERENCE = 0.0
 
 
 def write_cases(path, names):
-    """cases.bin of tools/dropin/pose_lil_main.cpp"""
+    """cases.bin of tools/dropin/pose_main.cpp"""
     import psl_slam_amd as P
     cases = [lc.case(nm) for nm in names]
     estride, lstride = max(len(c["edges"]) for c in cases), max(len(c["lil"]) for c in cases)
@@ -81,13 +82,38 @@ def test_order_difference_is_the_documented_one():
     assert d <= ORDER_DIFFERENCE
 
 
-def test_without_lil_edges_the_restatement_is_the_point_restatement():
-    for nm in ("n10_mixed_30", "n65_mono_0"):
+def test_the_one_driver_returns_what_the_two_drivers_returned():
+    """tests/golden/pose_restatement_pins.npz holds what pose_opt_cases.optimize and pose_lil_cases.optimize returned while each had
+    its own copy of the rounds, iterations and trials (tests/golden/make_golden.py pose_pins, run on that code): pose bytes, flags,
+    return value, rounds and iterations, and the margin as a float64.  The one driver returns the same bits on every case of both
+    case sets in both orders, and without LIL edges pose_lil_cases.optimize is pose_opt_cases.optimize on every point case."""
+    pins = np.load(os.path.join(ROOT, "tests", "golden", "pose_restatement_pins.npz"))
+
+    def check(key, pose, flags, ngood, info, margin):
+        assert pose.tobytes() == pins[key + "/pose"].tobytes(), key
+        for k, f in flags.items():
+            assert (f is None) == bool(pins[f"{key}/{k}_none"]), (key, k)
+            assert f is None or (f.dtype == np.uint8 and f.tobytes() == pins[f"{key}/{k}"].tobytes()), (key, k)
+        assert ngood == int(pins[key + "/ngood"]) and info.tobytes() == pins[key + "/info"].tobytes(), key
+        assert np.float64(margin).tobytes() == pins[key + "/margin"].tobytes(), (key, margin)
+
+    checked = 0
+    for nm in pc.CASE_NAMES:
         c = pc.case(nm)
         for order in ("device", "edge"):
-            got = lc.optimize(c["Tcw"], c["edges"], np.zeros(0, lc.LIL_DTYPE), c["cam"], order)
-            ref = c["ref"][order]
-            assert got[0].tobytes() == ref[0].tobytes() and (got[1] == ref[1]).all() and got[3] == ref[2] and got[4].tobytes() == ref[3].tobytes()
+            pose, outlier, ngood, info, margin = pc.optimize(c["Tcw"], c["edges"], c["cam"], order)
+            check(f"points/{nm}/{order}", pose, {"outlier": outlier}, ngood, info, margin)
+            pose, outlier, outlier_lil, ngood, info, margin = lc.optimize(c["Tcw"], c["edges"], np.zeros(0, lc.LIL_DTYPE), c["cam"], order)
+            assert outlier_lil is None or len(outlier_lil) == 0
+            check(f"points/{nm}/{order}", pose, {"outlier": outlier}, ngood, info, margin)
+            checked += 1
+    for nm in lc.CASE_NAMES:
+        c = lc.case(nm)
+        for order in ("device", "edge"):
+            pose, outlier, outlier_lil, ngood, info, margin = lc.optimize(c["Tcw"], c["edges"], c["lil"], c["cam"], order)
+            check(f"lil/{nm}/{order}", pose, {"outlier": outlier, "outlier_lil": outlier_lil}, ngood, info, margin)
+            checked += 1
+    assert checked == 2 * (len(pc.CASE_NAMES) + len(lc.CASE_NAMES)) and len(pins.files) == 12 * len(pc.CASE_NAMES) + 16 * len(lc.CASE_NAMES)
 
 
 def test_early_return_and_one_round_rule_count_both_kinds():
@@ -171,7 +197,7 @@ def test_abi_and_dtypes():
 
 def _build_host(tmp_path, sanitize):
     exe = str(tmp_path / ("pose_lil_host_san" if sanitize else "pose_lil_host"))
-    src = os.path.join(ROOT, "tools", "dropin", "pose_lil_main.cpp")
+    src = os.path.join(ROOT, "tools", "dropin", "pose_main.cpp")
     if sanitize:
         cmd = [HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-DPSL_POSE_HOST_ONLY", "-Xarch_host",
                "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-o", exe, src]
@@ -183,7 +209,7 @@ def _build_host(tmp_path, sanitize):
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitizers"])
 def test_host_program_equals_restatement(tmp_path, sanitize):
-    """tools/dropin/pose_lil_main.cpp with -DPSL_POSE_HOST_ONLY on every case: its plain C++ loop equals the restatement in the
+    """tools/dropin/pose_main.cpp with -DPSL_POSE_HOST_ONLY on every LIL case: its plain C++ loop equals the restatement in the
     device's order bit for bit; built as a stand-alone program under -fsanitize=address,undefined the sanitizers stay silent"""
     exe = _build_host(tmp_path, sanitize)
     path, out = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")

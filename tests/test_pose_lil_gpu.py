@@ -1,7 +1,7 @@
 """GPU parity of the pose optimisation with LIL edges (psl-slam_amd/csrc/pslfe_pose.hip, k_pose_optimize<true>) with the restatement
 of tests/pose_lil_cases.py in the device's order of the sums, bit for bit: pose floats, both outlier arrays, return value, rounds and
 iterations; the host form, nlil = 0 against the point-edge entry point, a batch against single launches, the error rules, the LIL
-set-up loop and the chain glue -> LIL edges -> pose on a glue_scene frame, and the C++ consumer tools/dropin/pose_lil_main.cpp."""
+set-up loop and the chain glue -> LIL edges -> pose on a glue_scene frame, and the C++ consumer tools/dropin/pose_main.cpp on LIL cases."""
 import ctypes as C
 import os
 import subprocess
@@ -379,10 +379,10 @@ def test_chain_glue_lil_edges_pose_without_the_host():
 
 
 def test_cpp_consumer_equals_restatement(tmp_path):
-    """tools/dropin/pose_lil_main.cpp on pslfe.hpp: the batched device form, the frame-by-frame host form and its own plain C++ loop,
+    """tools/dropin/pose_main.cpp on pslfe.hpp with LIL edges (the LIL entry points): the batched device form, the frame-by-frame host form and its own plain C++ loop,
     each against the restatement in the device's order"""
-    exe = str(tmp_path / "pose_lil_main")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tools", "dropin", "pose_lil_main.cpp"),
+    exe = str(tmp_path / "pose_main")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tools", "dropin", "pose_main.cpp"),
                     "-L" + os.path.join(ROOT, "psl-slam_amd"), "-lpslfe", "-Wl,-rpath," + os.path.join(ROOT, "psl-slam_amd")],
                    check=True, capture_output=True)
     names = ["p2_l0", "p2_l1", "p2_l8", "p0_l65", "p250_l10", "p2048_l4", "p40_l512", "p100_l8_allout", "setup"]

@@ -14,7 +14,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def write_cases(path, names, cam=None):
-    """cases.bin of tools/dropin/pose_main.cpp"""
+    """cases.bin of tools/dropin/pose_main.cpp without LIL edges (lstride = 0, m = 0)"""
     import psl_slam_amd as P
     cases = [pc.case(nm) for nm in names]
     estride = max(len(c["edges"]) for c in cases)
@@ -22,11 +22,11 @@ def write_cases(path, names, cam=None):
     for k, v in (cam or pc.camera()).items():
         camrec[k] = v
     with open(path, "wb") as f:
-        np.array([len(cases), estride], np.int32).tofile(f)
+        np.array([len(cases), estride, 0], np.int32).tofile(f)
         camrec.tofile(f)
         for c in cases:
             c["Tcw"].tofile(f)
-            np.array([len(c["edges"])], np.int32).tofile(f)
+            np.array([len(c["edges"]), 0], np.int32).tofile(f)
             c["edges"].tofile(f)
     return cases
 
@@ -68,7 +68,7 @@ def test_noise_free_case_recovers_the_true_pose():
     assert ngood == 300 and not outlier.any() and info["rounds"] == 4
     E = pc._Edges(c["edges"], c["cam"])
     e, Pc = E.error(pc.from_pose(c["Ttrue"]))
-    acc = pc.sum_edge(E.terms(e, Pc, np.zeros(E.n), np.ones(E.n)), np.ones(E.n, bool))
+    acc = pc.sum_edge(E.terms(e, Pc, np.zeros(E.n), np.ones(E.n))[:, None], np.ones(E.n, bool))
     H = np.zeros((6, 6))
     H[np.triu_indices(6)] = acc[:21]
     H = H + np.triu(H, 1).T

@@ -10,8 +10,8 @@ value.  Prints one JSON line and writes it to --out.  Needs the test tree: the c
 tool and the tests optimise the same kind of frame.
 
 --lil N (default 0: the point-edge entry points, as above) adds N LIL edges per frame (tests/pose_lil_cases.py: 30 % planted
-outliers) and times pslfe_pose_optimize_lil / pslfe_pose_optimize_lil_device against the host loop of tools/dropin/pose_lil_main.cpp;
-its default --out is profiles/pose_opt_bench_lil.json.  Every device row also carries the median and the largest launch time of the
+outliers) and times pslfe_pose_optimize_lil / pslfe_pose_optimize_lil_device against the same host loop with the LIL rows in its
+case file; its default --out is profiles/pose_opt_bench_lil.json.  Every device row also carries the median and the largest launch time of the
 repetitions.  --label names the run in its JSON; --merge embeds the JSON lines of earlier runs (another build of the library
 alternated with this one, repeated runs of the same build) under "other_runs", so that one file holds a comparison and its
 run-to-run spread."""
@@ -59,14 +59,14 @@ def main():
     tmp = tmpdir.name
     exe = os.path.join(tmp, "pose_host")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DPSL_POSE_HOST_ONLY", "-o", exe,
-                    os.path.join(ROOT, "tools", "dropin", "pose_lil_main.cpp" if nlil else "pose_main.cpp")], check=True, capture_output=True)
+                    os.path.join(ROOT, "tools", "dropin", "pose_main.cpp")], check=True, capture_output=True)
 
     def down(d, a):
         P._check(P.lib().pslfe_device_download(ctx._h, P._ptr(a), C.c_void_p(d), C.c_size_t(a.nbytes)), "pslfe_device_download")
         return a
 
     res = {"tool": "bench_pose_opt", "device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None, "reps": args.reps,
-           "host_loop": f"tools/dropin/{'pose_lil_main' if nlil else 'pose_main'}.cpp -DPSL_POSE_HOST_ONLY, g++ -O2, one core",
+           "host_loop": "tools/dropin/pose_main.cpp -DPSL_POSE_HOST_ONLY, g++ -O2, one core",
            "lil_edges": nlil, "rows": []}
     if args.label:
         res["label"] = args.label
@@ -77,11 +77,11 @@ def main():
         # the host loop on one core: the 32 frames, best of reps
         path, out = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out.bin")
         with open(path, "wb") as f:
-            np.array([NSEEDS, nedges, nlil] if nlil else [NSEEDS, nedges], np.int32).tofile(f)
+            np.array([NSEEDS, nedges, nlil], np.int32).tofile(f)
             cam.tofile(f)
             for c in cases:
                 c["Tcw"].tofile(f)
-                np.array([nedges, nlil] if nlil else [nedges], np.int32).tofile(f)
+                np.array([nedges, nlil], np.int32).tofile(f)
                 c["edges"].tofile(f)
                 if nlil:
                     c["lil"].tofile(f)
