@@ -1200,6 +1200,93 @@ int pslfe_pose_lil_edges_device(pslfe_ctx* ctx, int nframes, const double* d_le_
                                 const int32_t* d_nplanes, const int32_t* d_lil_index, const PslMapLil* d_map, int nmap, PslPoseLilEdge* d_lil,
                                 int32_t* d_edge_plane, int32_t* d_nlil, int lstride);
 
+/* ---- Sim3 optimisation of loop candidates: Optimizer::OptimizeSim3 (src/Optimizer.cc:2801-2996) -------------------------------
+ * Called once per candidate by LoopClosing::ComputeSim3 (src/LoopClosing.cc:326), between pslfe_kf_search_by_sim3_poses and
+ * pslfe_kf_search_by_projection_sim3_pose.  One free 7-DoF vertex (VertexSim3Expmap), every map point vertex fixed, two edges per
+ * matched pair: e12 (EdgeSim3ProjectXYZ, obs1 - cam_map1(project(S12.map(P2c)))) and e21 (EdgeInverseSim3ProjectXYZ, obs2 -
+ * cam_map2(project(S12^-1.map(P1c)))).
+ *
+ * Parity: g2o and Eigen cannot be built offline, so this stage is "HIP == restatement", parity with g2o unpinned, as
+ * for the pose optimisation.  The restatement (tests/sim3_opt_cases.py) follows g2o in double, in the reference's order of
+ * decisions: the estimate enters as Sim3(R, t, s) with Quaterniond(R) NOT normalised (sim3.h:64-67); the Jacobians are g2o's
+ * NUMERIC ones (linearizeOplus of both edges is commented out, types_seven_dof_expmap.h:147, :169: central differences with delta =
+ * 1e-9, base_binary_edge.hpp:131-205) and are restated as such; information invSigma2 * I; Huber delta = the float root of th2
+ * widened to double (:2850), on in both calls; optimize(5); a pair leaves the graph when the plain chi2 of either of its edges
+ * exceeds (double)th2 (:2948); return 0 when fewer than 10 pairs remain (:2966; g2oS12 is then not written back); optimize(10) when a
+ * pair left, optimize(5) otherwise, from the estimate the first call left, lambda / ni / _nBad re-initialised; the final test counts
+ * nIn (:2974-2989).  Inside a call the Levenberg rules are those stated above PslPoseEdge, in seven unknowns; the update is
+ * Sim3(update) * estimate with the four branches of sim3.h:70-142 (exp is the library's psl_exp, fdlibm's, at most one ulp off
+ * glibc's); with a fixed scale update[6] = 0 and the scale keeps its bits.  A point behind a camera is not guarded in the reference
+ * and is not guarded here.  The order of the sums over the pairs is fixed by the pair index and the pair count alone
+ * (psl-slam_amd/csrc/pslfe_sim3.hip), never by the batch. */
+/* What Sim3Solver::GetEstimatedRotation / Translation / Scale hand over (src/LoopClosing.cc:320-325). */
+typedef struct PslSim3 {
+    float R[9];   /* row-major */
+    float t[3];
+    float s;
+} PslSim3;
+/* The g2o::Sim3 that comes back (LoopClosing goes on in double with it, :333-334): the quaternion as Eigen holds it. */
+typedef struct PslSim3D {
+    double q[4];  /* x y z w, not normalised */
+    double t[3];
+    double s;
+} PslSim3D;
+/* One matched pair, in the order the reference creates them (KF1 keypoint order, :2854-2933). */
+typedef struct PslSim3Pair {
+    float u1, v1;         /* pKF1->mvKeysUn[i].pt (:2897)                                             */
+    float inv_sigma2_1;   /* pKF1->mvInvLevelSigma2[kpUn1.octave] (:2904)                             */
+    float u2, v2;         /* pKF2->mvKeysUn[i2].pt (:2914)                                            */
+    float inv_sigma2_2;   /* pKF2->mvInvLevelSigma2[kpUn2.octave] (:2922)                             */
+    float P1c[3];         /* R1w*P3D1w + t1w (:2873)                                                  */
+    float P2c[3];         /* R2w*P3D2w + t2w (:2881)                                                  */
+} PslSim3Pair;
+/* What the optimisation of a candidate did: optimize() calls run (0..2), the iterations of each, and which branches of the Sim3
+ * exponential its trial steps took (bit (|sigma| >= 1e-5) * 2 + (theta >= 1e-5)); pslfe_sim3_optimize_device reports it, the one-candidate host form does not. */
+typedef struct PslSim3Info {
+    int32_t calls;
+    int32_t iterations[2];
+    int32_t exp_branches;
+} PslSim3Info;
+#ifdef __cplusplus
+static_assert(sizeof(PslSim3) == 52 && sizeof(PslSim3D) == 64 && sizeof(PslSim3Pair) == 48 && sizeof(PslSim3Info) == 16, "Sim3 PODs");
+#else
+_Static_assert(sizeof(PslSim3) == 52 && sizeof(PslSim3D) == 64 && sizeof(PslSim3Pair) == 48 && sizeof(PslSim3Info) == 16, "Sim3 PODs");
+#endif
+/* == Optimizer::OptimizeSim3 src/Optimizer.cc:2801-2996 for ncand independent candidates in one launch.  Candidate c: start
+ *    d_S12_in[c], d_npairs[c] pairs at d_pairs + c*pstride.  cam1 / cam2: host, pKF1->mK / pKF2->mK (fx, fy, cx, cy are read).
+ *    Outputs: d_bad [ncand][pstride] bytes, 1 where the reference nulls vpMatches1[idx] in either test and 0 for the other pairs of
+ *    the candidate (bytes beyond the count are not touched); d_nin[c] = the return value; d_S12_out[c] = the optimised Sim3, or
+ *    Sim3(R, t, s) of the input where the reference returns 0 before writing g2oS12 back (fewer than 10 pairs left after the first
+ *    call); d_info[c] (may be NULL).  No pair: d_nin[c] = 0, nothing is optimised.  1..9 pairs: the first call runs and flags, as
+ *    in the reference, then 0.  d_npairs[c] > pstride: d_nin[c] = PSLFE_E_CAPACITY; d_npairs[c] < 0 (an error code the set-up left
+ *    there): d_nin[c] = PSLFE_E_INVALID; neither is clamped, nothing is optimised, no byte of d_bad is written and d_S12_out[c]
+ *    is the input's Sim3.  ncand < 0, pstride < 0, a NULL array with a non-zero count: PSLFE_E_INVALID; ncand == 0: PSLFE_OK,
+ *    nothing is done.  A trial step whose rotation angle is not below 105414350 counts as a failed solve.  Asynchronous on the
+ *    context's stream. */
+int pslfe_sim3_optimize_device(pslfe_ctx* ctx, int ncand, const PslSim3* d_S12_in, const PslSim3Pair* d_pairs, const int32_t* d_npairs,
+                               int pstride, const PslCamera* cam1, const PslCamera* cam2, float th2, int fix_scale, PslSim3D* d_S12_out,
+                               uint8_t* d_bad, int32_t* d_nin, PslSim3Info* d_info);
+/* Same for one candidate, host arrays: bad has room for npairs bytes and is an output only; returns after the results have
+ * arrived. */
+int pslfe_sim3_optimize(pslfe_ctx* ctx, const PslSim3* S12, const PslSim3Pair* pairs, int npairs, const PslCamera* cam1, const PslCamera* cam2,
+                        float th2, int fix_scale, PslSim3D* S12_out, uint8_t* bad, int* nin);
+/* == The set-up loop src/Optimizer.cc:2854-2933 for ncand candidates of one current keyframe, HBM to HBM.  KF1 is slot slot1 of f1,
+ *    candidate c is slot d_slots2[c] of f2 (mvKeysUn and octaves, already resident; a slot outside f2: d_npairs[c] =
+ *    PSLFE_E_INVALID; the caller has set every slot it names: the slot numbers are in HBM, so only slot1 is checked against the
+ *    store's record, and a slot of f2 that was never set holds 0 keypoints since pslfe_frame_create and gives 0 pairs).  d_i2[c][i] (row stride f1's keypoint capacity) = pMP2->GetIndexInKeyFrame(pKF2) of vpMatches1[i], or -1 for
+ *    a NULL match.  d_mp1 / d_skip1 (n1 rows): pKF1->GetMapPointMatches(), skip != 0 for NULL or bad; d_mp2 / d_skip2
+ *    [ncand][mp2stride]: the same per candidate, indexed by the KF2 keypoint.  d_T1w, d_T2w[c]: the keyframe poses.
+ *    P3D1c = R1w*P3D1w + t1w and P3D2c are float products under the convention above PslPose (a double sum in index order, rounded
+ *    once), the value PSLFE_KF_PROJ_SIM3 uses.  inv_level_sigma2: host array of nlevels (mvInvLevelSigma2).  Rows are compacted in
+ *    i order at d_pairs + c*pstride; d_pair_kp (may be NULL) gets the i of each row; d_npairs[c] is the full count: a count above
+ *    pstride is reported, never truncated silently (the first pstride rows are written).  An index outside its array drops the
+ *    pair.  Asynchronous on the frame stores' context stream (both stores belong to one context). */
+int pslfe_sim3_pairs_from_matches_device(pslfe_frame* f1, int slot1, pslfe_frame* f2, const int32_t* d_slots2, int ncand, const int32_t* d_i2,
+                                         const PslMapPointGeom* d_mp1, const uint8_t* d_skip1, int n1, const PslMapPointGeom* d_mp2,
+                                         const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w, const PslPose* d_T2w,
+                                         const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs, int32_t* d_pair_kp,
+                                         int32_t* d_npairs, int pstride);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

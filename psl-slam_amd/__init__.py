@@ -44,6 +44,13 @@ POSELIL_DTYPE = np.dtype([("line1", "<f8", (6,)), ("line2", "<f8", (6,)), ("cros
                           ("obs_ins", "<f8", (2,))])
 MAPLIL_DTYPE = np.dtype([("w", "<f8", (15,)), ("bad", "u1"), ("pad", "u1", (7,))])
 assert POSELIL_DTYPE.itemsize == 184 and MAPLIL_DTYPE.itemsize == 128
+# Sim3 optimisation (include/pslfe.h: PslSim3, PslSim3D, PslSim3Pair, PslSim3Info)
+SIM3_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("s", "<f4")])
+SIM3D_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+SIM3PAIR_DTYPE = np.dtype([("u1", "<f4"), ("v1", "<f4"), ("inv_sigma2_1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("inv_sigma2_2", "<f4"),
+                           ("P1c", "<f4", (3,)), ("P2c", "<f4", (3,))])
+SIM3INFO_DTYPE = np.dtype([("calls", "<i4"), ("iterations", "<i4", (2,)), ("exp_branches", "<i4")])
+assert SIM3_DTYPE.itemsize == 52 and SIM3D_DTYPE.itemsize == 64 and SIM3PAIR_DTYPE.itemsize == 48 and SIM3INFO_DTYPE.itemsize == 16
 
 
 def pose(Tcw):
@@ -701,6 +708,49 @@ class Optimizer:
             ctx._h, C.c_int(nframes), C.c_void_p(d_le_l or None), C.c_int(le_stride), C.c_void_p(d_cross2d or None), C.c_int(plane_stride),
             C.c_void_p(d_nplanes or None), C.c_void_p(d_lil_index or None), C.c_void_p(d_map or None), C.c_int(nmap), C.c_void_p(d_lil or None),
             C.c_void_p(d_edge_plane or None), C.c_void_p(d_nlil or None), C.c_int(lstride)), "pslfe_pose_lil_edges_device")
+
+    @staticmethod
+    def OptimizeSim3(S12, pairs, cam1, cam2, th2, fix_scale, ctx=None):
+        """Optimizer::OptimizeSim3 src/Optimizer.cc:2801-2996 for one candidate, host arrays: S12 a SIM3_DTYPE record (what Sim3Solver
+        hands over), pairs SIM3PAIR_DTYPE[n] in KF1 keypoint order.  -> (nIn = the return value, S12_out SIM3D_DTYPE record, bad u8 [n]
+        = 1 where the reference nulls vpMatches1[idx]).  S12_out is Sim3(R, t, s) of the input where the reference returns 0 before
+        writing g2oS12 back."""
+        ctx = ctx or default_context()
+        S = np.ascontiguousarray(S12, SIM3_DTYPE).reshape(1)
+        p = np.ascontiguousarray(pairs, SIM3PAIR_DTYPE)
+        cam1 = np.ascontiguousarray(cam1, CAMERA_DTYPE).reshape(1)
+        cam2 = np.ascontiguousarray(cam2, CAMERA_DTYPE).reshape(1)
+        out = np.zeros(1, SIM3D_DTYPE)
+        bad = np.zeros(max(len(p), 1), np.uint8)
+        nin = C.c_int()
+        _check(lib().pslfe_sim3_optimize(ctx._h, _ptr(S), _ptr(p) if len(p) else None, C.c_int(len(p)), _ptr(cam1), _ptr(cam2), C.c_float(th2),
+                                         C.c_int(1 if fix_scale else 0), _ptr(out), _ptr(bad) if len(p) else None, C.byref(nin)),
+               "pslfe_sim3_optimize")
+        return nin.value, out[0], bad[:len(p)]
+
+    @staticmethod
+    def OptimizeSim3Device(ncand, d_S12_in, d_pairs, d_npairs, pstride, cam1, cam2, th2, fix_scale, d_S12_out, d_bad, d_nin, d_info=0, ctx=None):
+        """ncand independent candidates in one launch, HBM to HBM, asynchronous; all d_* are device addresses (ints; d_info may be 0).
+        d_nin[c] = PSLFE_E_CAPACITY (-4) for a count above pstride, PSLFE_E_INVALID (-1) for a negative one."""
+        ctx = ctx or default_context()
+        cam1 = np.ascontiguousarray(cam1, CAMERA_DTYPE).reshape(1)
+        cam2 = np.ascontiguousarray(cam2, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_sim3_optimize_device(
+            ctx._h, C.c_int(ncand), C.c_void_p(d_S12_in or None), C.c_void_p(d_pairs or None), C.c_void_p(d_npairs or None), C.c_int(pstride),
+            _ptr(cam1), _ptr(cam2), C.c_float(th2), C.c_int(1 if fix_scale else 0), C.c_void_p(d_S12_out or None), C.c_void_p(d_bad or None),
+            C.c_void_p(d_nin or None), C.c_void_p(d_info or None)), "pslfe_sim3_optimize_device")
+
+    @staticmethod
+    def Sim3PairsFromMatchesDevice(f1, slot1, f2, d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2, mp2stride, d_T1w, d_T2w,
+                                   inv_level_sigma2, d_pairs, d_pair_kp, d_npairs, pstride):
+        """The set-up loop :2854-2933 on the device for ncand candidates of the keyframe in slot slot1 of f1: d_i2 [ncand][f1 capacity] =
+        the KF2 keypoint of each match or -1; rows compacted in KF1 keypoint order; d_npairs[c] = the full count, also above pstride."""
+        s2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        _check(lib().pslfe_sim3_pairs_from_matches_device(
+            f1._h, C.c_int(slot1), f2._h, C.c_void_p(d_slots2 or None), C.c_int(ncand), C.c_void_p(d_i2 or None), C.c_void_p(d_mp1 or None),
+            C.c_void_p(d_skip1 or None), C.c_int(n1), C.c_void_p(d_mp2 or None), C.c_void_p(d_skip2 or None), C.c_int(mp2stride),
+            C.c_void_p(d_T1w or None), C.c_void_p(d_T2w or None), _ptr(s2), C.c_int(len(s2)), C.c_void_p(d_pairs or None),
+            C.c_void_p(d_pair_kp or None), C.c_void_p(d_npairs or None), C.c_int(pstride)), "pslfe_sim3_pairs_from_matches_device")
 
     @staticmethod
     def MapPointIndexFromMatchesDevice(frame, nframes, d_match, d_owner, d_nq, qstride, d_mp_index):

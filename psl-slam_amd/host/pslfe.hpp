@@ -1218,6 +1218,35 @@ public:
                                                    (int)invLevelSigma2.size(), d_edges, d_edgeKp, d_nedges, estride),
               "pslfe_pose_edges_from_matches_device");
     }
+    // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) src/Optimizer.cc:2801-2996: pairs = one PslSim3Pair per
+    // match that passes the set-up loop (:2854-2933), in KF1 keypoint order; S12 = what Sim3Solver hands over (src/LoopClosing.cc:
+    // 320-325); S12Out = the g2o::Sim3 that comes back, or Sim3(R, t, s) of the input where the reference returns 0 before writing
+    // g2oS12 (:2966); bad[p] = 1 where the reference nulls vpMatches1[idx]; returns nIn.  Parity with g2o itself is unpinned.
+    static int OptimizeSim3(Context& ctx, const PslSim3& S12, const std::vector<PslSim3Pair>& pairs, const PslCamera& cam1, const PslCamera& cam2,
+                            float th2, bool fixScale, PslSim3D& S12Out, std::vector<uint8_t>& bad) {
+        bad.assign(pairs.size(), 0);
+        int nin = 0;
+        check(pslfe_sim3_optimize(ctx.get(), &S12, pairs.data(), (int)pairs.size(), &cam1, &cam2, th2, fixScale ? 1 : 0, &S12Out, bad.data(), &nin),
+              "pslfe_sim3_optimize");
+        return nin;
+    }
+    // K candidates in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_sim3_optimize_device
+    static void OptimizeSim3Device(Context& ctx, int ncand, const PslSim3* d_S12In, const PslSim3Pair* d_pairs, const int32_t* d_npairs, int pstride,
+                                   const PslCamera& cam1, const PslCamera& cam2, float th2, bool fixScale, PslSim3D* d_S12Out, uint8_t* d_bad,
+                                   int32_t* d_nin, PslSim3Info* d_info = nullptr) {
+        check(pslfe_sim3_optimize_device(ctx.get(), ncand, d_S12In, d_pairs, d_npairs, pstride, &cam1, &cam2, th2, fixScale ? 1 : 0, d_S12Out, d_bad,
+                                         d_nin, d_info), "pslfe_sim3_optimize_device");
+    }
+    // the set-up loop :2854-2933 for ncand candidates of one current keyframe, HBM to HBM: pslfe_sim3_pairs_from_matches_device
+    static void Sim3PairsFromMatchesDevice(FrameGrid& f1, int slot1, FrameGrid& f2, const int32_t* d_slots2, int ncand, const int32_t* d_i2,
+                                           const PslMapPointGeom* d_mp1, const uint8_t* d_skip1, int n1, const PslMapPointGeom* d_mp2,
+                                           const uint8_t* d_skip2, int mp2Stride, const PslPose* d_T1w, const PslPose* d_T2w,
+                                           const std::vector<float>& invLevelSigma2, PslSim3Pair* d_pairs, int32_t* d_pairKp, int32_t* d_npairs,
+                                           int pstride) {
+        check(pslfe_sim3_pairs_from_matches_device(f1.get(), slot1, f2.get(), d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2, mp2Stride,
+                                                   d_T1w, d_T2w, invLevelSigma2.data(), (int)invLevelSigma2.size(), d_pairs, d_pairKp, d_npairs,
+                                                   pstride), "pslfe_sim3_pairs_from_matches_device");
+    }
 };
 
 }  // namespace pslfe

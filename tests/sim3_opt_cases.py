@@ -1,0 +1,528 @@
+"""The restatement of Optimizer::OptimizeSim3 (src/Optimizer.cc:2801-2996 over the reference's g2o) in numpy float64, and the seeded
+cases of tests/test_sim3_opt_cpu.py / test_sim3_opt_gpu.py.
+
+The restatement mirrors the arithmetic of psl-slam_amd/csrc/sim3_kernels.h operation by operation (every numpy ufunc is one IEEE
+operation; nothing here goes through BLAS) and its driver psl_s3_rounds decision by decision, with math.sin / math.cos and fdlibm's
+exp written out below (psl_exp of psl_f64math.h is fdlibm's, not glibc's); it shares no text with the C++ and is what the kernel and
+the host loop are judged against.  The Jacobians are g2o's numeric ones (central differences, delta = 1e-9), as in the reference.
+order="device" sums H, b and the robust chi2 in the device's order (the header of psl-slam_amd/csrc/pslfe_sim3.hip); order="edge"
+sums them edge by edge, which is g2o's.  Eigen and g2o cannot be built offline: parity with g2o itself is unpinned."""
+import functools
+import math
+import struct
+
+import numpy as np
+
+from pose_opt_cases import DBL_MAX, THETA_MAX, _div, _mat3mul, _quat_from_R, _quat_to_R, _rodrigues, _rotate, sum_device, sum_edge
+
+SIM3_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("s", "<f4")])
+SIM3D_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+PAIR_DTYPE = np.dtype([("u1", "<f4"), ("v1", "<f4"), ("inv_sigma2_1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("inv_sigma2_2", "<f4"),
+                       ("P1c", "<f4", (3,)), ("P2c", "<f4", (3,))])
+INFO_DTYPE = np.dtype([("calls", "<i4"), ("iterations", "<i4", (2,)), ("exp_branches", "<i4")])
+DELTA = 1e-9                      # base_binary_edge.hpp:147
+SCALAR = 1.0 / (2 * 1e-9)         # :148
+EPS = 0.00001                     # sim3.h:90
+TH2 = np.float32(10.0)            # what LoopClosing::ComputeSim3 passes (src/LoopClosing.cc:326)
+LDS_PAIRS = 1024                  # PSL_S3_LDS_PAIRS of pslfe_sim3.hip: above it the rows are read from HBM
+
+
+# ---- exp as fdlibm computes it (e_exp.c), the algorithm of psl_exp ----------------------------------------------------------------------
+def fdlibm_exp(x):
+    u = struct.unpack("<Q", struct.pack("<d", x))[0]
+    xsb = u >> 63
+    hx = (u >> 32) & 0x7FFFFFFF
+    hi = lo = 0.0
+    k = 0
+    if hx >= 0x40862E42:
+        if hx >= 0x7FF00000:
+            return x + x if (u & 0x000FFFFFFFFFFFFF) else (0.0 if xsb else x)
+        if x > 7.09782712893383973096e+02:
+            return math.inf
+        if x < -7.45133219101941108420e+02:
+            return 0.0
+    if hx > 0x3FD62E42:
+        if hx < 0x3FF0A2B2:
+            hi = x - (-6.93147180369123816490e-01 if xsb else 6.93147180369123816490e-01)
+            lo = -1.90821492927058770002e-10 if xsb else 1.90821492927058770002e-10
+            k = 1 - xsb - xsb
+        else:
+            k = int(1.44269504088896338700e+00 * x + (-0.5 if xsb else 0.5))
+            t = float(k)
+            hi = x - t * 6.93147180369123816490e-01
+            lo = t * 1.90821492927058770002e-10
+        x = hi - lo
+    elif hx < 0x3E300000:
+        return 1.0 + x
+    t = x * x
+    c = x - t * (1.66666666666666019037e-01 + t * (-2.77777777770155933842e-03 + t * (6.61375632143793436117e-05 + t * (
+        -1.65339022054652515390e-06 + t * 4.13813679705723846039e-08))))
+    if k == 0:
+        return 1.0 - ((x * c) / (c - 2.0) - x)
+    y = 1.0 - ((lo - (x * c) / (2.0 - c)) - hi)
+    return math.ldexp(y, k)
+
+
+# ---- Sim3 (sim3.h) on Python floats: (q = [x, y, z, w] not normalised, t, s) ----------------------------------------------------------
+def s3_from_rts(rec):
+    """Sim3(R, t, s) (sim3.h:64-67) of a SIM3_DTYPE record"""
+    R = [float(v) for v in np.asarray(rec["R"], np.float32).reshape(9)]
+    return _quat_from_R(R), [float(v) for v in np.asarray(rec["t"], np.float32).reshape(3)], float(np.float32(rec["s"]))
+
+
+def s3_exp(x):
+    """Sim3(update) (sim3.h:70-142) -> (Sim3, branch = (|sigma| >= eps) * 2 + (theta >= eps))"""
+    sigma = x[6]
+    theta = math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])
+    O = [0.0, -x[2], x[1], x[2], 0.0, -x[0], -x[1], x[0], 0.0]
+    s = fdlibm_exp(sigma)
+    O2 = _mat3mul(O, O)
+    eye = [1.0 if i % 4 == 0 else 0.0 for i in range(9)]
+    big_sigma, big_theta = not (abs(sigma) < EPS), not (theta < EPS)
+    if big_theta:
+        sn, cs = math.sin(theta), math.cos(theta)
+        a, b = sn / theta, (1.0 - cs) / (theta * theta)
+        R = [(eye[i] + a * O[i]) + b * O2[i] for i in range(9)]
+        if not big_sigma:
+            theta2 = theta * theta
+            C, A, B = 1.0, (1.0 - cs) / theta2, (theta - sn) / (theta2 * theta)
+        else:
+            C = (s - 1.0) / sigma
+            sa, sb = s * sn, s * cs
+            theta2, sigma2 = theta * theta, sigma * sigma
+            c = theta2 + sigma2
+            A = _div(sa * sigma + (1.0 - sb) * theta, theta * c)
+            B = _div(C - _div((sb - 1.0) * sigma + sa * theta, c), theta2)
+    else:
+        R = [(eye[i] + O[i]) + O2[i] for i in range(9)]
+        if not big_sigma:
+            C, A, B = 1.0, 1.0 / 2.0, 1.0 / 6.0
+        else:
+            C = (s - 1.0) / sigma
+            sigma2 = sigma * sigma
+            A = _div((sigma - 1.0) * s + 1.0, sigma2)
+            B = _div(((0.5 * sigma2 - sigma) + 1.0) * s, sigma2 * sigma)
+    q = _quat_from_R(R)
+    W = [(A * O[i] + B * O2[i]) + C * eye[i] for i in range(9)]
+    t = [(W[3 * i] * x[3] + W[3 * i + 1] * x[4]) + W[3 * i + 2] * x[5] for i in range(3)]
+    return (q, t, s), int(big_sigma) * 2 + int(big_theta)
+
+
+def s3_map(S, X):
+    """Sim3::map (:144) of a vector of Python floats or of numpy columns"""
+    r = _rotate(S[0], X)
+    return [S[2] * r[0] + S[1][0], S[2] * r[1] + S[1][1], S[2] * r[2] + S[1][2]]
+
+
+def s3_inverse(S):
+    q, t, s = S
+    qc = [-q[0], -q[1], -q[2], q[3]]
+    m = _div(-1.0, s)
+    return qc, _rotate(qc, [m * t[0], m * t[1], m * t[2]]), _div(1.0, s)
+
+
+def s3_mul(A, B):
+    r = _rotate(A[0], B[1])
+    a, b = A[0], B[0]
+    q = [((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1],
+         ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2],
+         ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0],
+         ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2]]
+    return q, [A[2] * r[0] + A[1][0], A[2] * r[1] + A[1][1], A[2] * r[2] + A[1][2]], A[2] * B[2]
+
+
+def s3_oplus(x, fix_scale, S):
+    """VertexSim3Expmap::oplusImpl (types_seven_dof_expmap.h:60-69) -> (Sim3, branch)"""
+    u = list(x)
+    if fix_scale:
+        u[6] = 0.0
+    d, branch = s3_exp(u)
+    return s3_mul(d, S), branch
+
+
+def s3_perturbed(S, fix_scale):
+    """the 14 perturbed estimates of a linearisation (base_binary_edge.hpp:176-198) and their inverses: [(Sp, Spi)], +delta e_d at
+    2d, -delta e_d at 2d + 1"""
+    out = []
+    for k in range(14):
+        u = [0.0] * 7
+        u[k >> 1] = -DELTA if k & 1 else DELTA
+        Sp = s3_oplus(u, fix_scale, S)[0]
+        out.append((Sp, s3_inverse(Sp)))
+    return out
+
+
+def s3_record(S):
+    r = np.zeros((), SIM3D_DTYPE)
+    r["q"], r["t"], r["s"] = S[0], S[1], S[2]
+    return r
+
+
+def s3_matrix(S):
+    """(R of the normalised quaternion, t, s) as numpy, for the tests that compare with a true Sim3"""
+    q = np.array(S[0], np.float64)
+    q = q / np.linalg.norm(q)
+    return np.array(_quat_to_R(list(q))).reshape(3, 3), np.array(S[1], np.float64), float(S[2])
+
+
+# ---- the pairs, vectorised over the pair index -------------------------------------------------------------------------------------------
+class _Pairs:
+    def __init__(self, pairs, cam1, cam2, th2):
+        p = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        self.n = len(p)
+        self.obs = [(p["u1"].astype(np.float64), p["v1"].astype(np.float64)), (p["u2"].astype(np.float64), p["v2"].astype(np.float64))]
+        self.is2 = [p["inv_sigma2_1"].astype(np.float64), p["inv_sigma2_2"].astype(np.float64)]
+        # the e12 edge maps P2c with S12, the e21 edge maps P1c with its inverse
+        self.X = [[p["P2c"][:, k].astype(np.float64) for k in range(3)], [p["P1c"][:, k].astype(np.float64) for k in range(3)]]
+        self.K = [tuple(float(np.float32(c[k])) for k in ("fx", "fy", "cx", "cy")) for c in (cam1, cam2)]
+        self.th2 = float(np.float32(th2))
+        self.delta = float(np.sqrt(np.float32(th2)))     # const float deltaHuber = sqrt(th2): the float root (src/Optimizer.cc:2850)
+
+    def error(self, side, S):
+        """computeError of one edge of every pair; S is S12 for side 0 and its inverse for side 1"""
+        P = s3_map(S, self.X[side])
+        fx, fy, cx, cy = self.K[side]
+        return [self.obs[side][0] - ((P[0] / P[2]) * fx + cx), self.obs[side][1] - ((P[1] / P[2]) * fy + cy)]
+
+    def chi2(self, side, e):
+        return e[0] * (self.is2[side] * e[0]) + e[1] * (self.is2[side] * e[1])
+
+    def huber(self, c):
+        dsqr = self.delta * self.delta
+        sq = np.sqrt(c)
+        inl = c <= dsqr
+        return np.where(inl, c, (2.0 * sq) * self.delta - dsqr), np.where(inl, 1.0, self.delta / sq)
+
+    def jacobian(self, side, pert):
+        """the numeric Jacobian of one edge of every pair: J[r][d] [n]"""
+        J = [[None] * 7, [None] * 7]
+        for d in range(7):
+            ep, em = self.error(side, pert[2 * d][side]), self.error(side, pert[2 * d + 1][side])
+            J[0][d], J[1][d] = SCALAR * (ep[0] - em[0]), SCALAR * (ep[1] - em[1])
+        return J
+
+    def terms(self, side, S, Si, pert):
+        """the 36 terms of one edge of every pair: [n][36]"""
+        e = self.error(side, Si if side else S)
+        rho0, rho1 = self.huber(self.chi2(side, e))
+        J = self.jacobian(side, pert)
+        w = rho1 * self.is2[side]
+        out = np.zeros((self.n, 36))
+        h = 0
+        for j in range(7):
+            w0, w1 = w * J[0][j], w * J[1][j]
+            for k in range(j, 7):
+                out[:, h] = w0 * J[0][k] + w1 * J[1][k]
+                h += 1
+            out[:, 28 + j] = w0 * e[0] + w1 * e[1]
+        out[:, 35] = rho0
+        return out
+
+    def plain_chi2(self, S, Si):
+        return self.chi2(0, self.error(0, S)), self.chi2(1, self.error(1, Si))
+
+
+def solve7(H, lam, b):
+    """(H + lam I) x = b by LDLt without pivoting; None when a pivot is not a finite positive number"""
+    A = [[0.0] * 7 for _ in range(7)]
+    h = 0
+    for j in range(7):
+        for k in range(j, 7):
+            A[j][k] = A[k][j] = float(H[h])
+            h += 1
+    for j in range(7):
+        A[j][j] = A[j][j] + lam
+    L = [[0.0] * 7 for _ in range(7)]
+    D = [0.0] * 7
+    ok = True
+    for j in range(7):
+        d = A[j][j]
+        for k in range(j):
+            d = d - L[j][k] * (L[j][k] * D[k])
+        if not (d > 0.0) or not (d <= DBL_MAX):
+            ok = False
+        D[j] = d
+        for i in range(j + 1, 7):
+            s = A[i][j]
+            for k in range(j):
+                s = s - L[i][k] * (L[j][k] * D[k])
+            L[i][j] = _div(s, d)
+    if not ok:
+        return None
+    y = [0.0] * 7
+    for i in range(7):
+        s = b[i]
+        for k in range(i):
+            s = s - L[i][k] * y[k]
+        y[i] = s
+    x = [0.0] * 7
+    for i in range(6, -1, -1):
+        s = _div(y[i], D[i])
+        for k in range(i + 1, 7):
+            s = s - L[k][i] * x[k]
+        x[i] = s
+    return x
+
+
+_DIAG = (0, 7, 13, 18, 22, 25, 27)     # H_jj in the 28 upper-triangle values row by row
+
+
+def optimize(S12, pairs, cam1, cam2, th2=TH2, fix_scale=False, order="device", more_iterations=None):
+    """-> (S12_out SIM3D_DTYPE record, bad u8 [n], nin, info INFO_DTYPE record, margin): margin = the least relative distance
+    |chi2 - th2| / th2 of a tested edge, over both tests."""
+    info = np.zeros((), INFO_DTYPE)
+    E = _Pairs(pairs, cam1, cam2, th2)
+    n = E.n
+    S0 = s3_from_rts(np.ascontiguousarray(S12, SIM3_DTYPE).reshape(()))
+    bad = np.zeros(n, bool)
+    state = {"margin": math.inf, "branches": 0}
+    if n <= 0:
+        return s3_record(S0), bad.astype(np.uint8), 0, info, math.inf
+    red = (lambda seq: sum_device(seq, ~bad)) if order == "device" else (lambda seq: sum_edge(seq, ~bad))
+
+    def system(S, Si):
+        pert = s3_perturbed(S, fix_scale)
+        return red(np.stack([E.terms(0, S, Si, pert), E.terms(1, S, Si, pert)], 1))
+
+    def chi_of(S, Si):
+        r = [E.huber(E.chi2(side, E.error(side, Si if side else S)))[0] for side in (0, 1)]
+        return float(red(np.stack(r, 1)[:, :, None])[0])
+
+    def run(T, iterations):
+        its = 0
+        lam, ni, lm_bad = 0.0, 2.0, 0
+        for it in range(iterations):
+            acc = system(T, s3_inverse(T))
+            b = [-float(v) for v in acc[28:35]]
+            chi = float(acc[35])
+            ini_chi = chi
+            if it == 0:
+                m = 0.0
+                for h in _DIAG:
+                    a = abs(float(acc[h]))
+                    m = m if a < m else a
+                lam, ni, lm_bad = 1e-5 * m, 2.0, 0
+            rho, qmax = 0.0, 0
+            while True:
+                x = solve7(acc, lam, b)
+                if x is not None and not (math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < THETA_MAX):
+                    x = None
+                temp_chi, Tn = DBL_MAX, T
+                if x is not None:
+                    if fix_scale:
+                        x[6] = 0.0        # oplusImpl writes into the solver's own vector (types_seven_dof_expmap.h:62-65)
+                    Tn, br = s3_oplus(x, fix_scale, T)
+                    state["branches"] |= 1 << br
+                    temp_chi = chi_of(Tn, s3_inverse(Tn))
+                else:
+                    x = [0.0] * 7
+                scale = 0.0
+                for j in range(7):
+                    scale = scale + x[j] * (lam * x[j] + b[j])
+                scale = scale + 1e-3
+                rho = _div(chi - temp_chi, scale)
+                if rho > 0 and math.isfinite(temp_chi):
+                    t = 2.0 * rho - 1.0
+                    alpha = 1.0 - (t * t) * t
+                    alpha = (2.0 / 3.0) if (2.0 / 3.0) < alpha else alpha
+                    lam = lam * (alpha if (1.0 / 3.0) < alpha else (1.0 / 3.0))
+                    ni, chi, T = 2.0, temp_chi, Tn
+                else:
+                    lam = lam * ni
+                    ni = ni * 2.0
+                qmax += 1
+                if not (rho < 0 and qmax < 10):
+                    break
+            its += 1
+            if qmax == 10 or rho == 0:
+                break
+            lm_bad = lm_bad + 1 if (ini_chi - chi) * 1e3 < ini_chi else 0
+            if lm_bad >= 3:
+                break
+        return T, its
+
+    def classify(T):
+        c12, c21 = E.plain_chi2(T, s3_inverse(T))
+        act = ~bad
+        if act.any():
+            both = np.concatenate([c12[act], c21[act]])
+            state["margin"] = min(state["margin"], float(np.nanmin(np.abs(both - E.th2) / E.th2)))
+        new = act & ((c12 > E.th2) | (c21 > E.th2))
+        bad[new] = True
+        return int(new.sum())
+
+    with np.errstate(all="ignore"):
+        T, its = run(S0, 5)
+        info["calls"], info["iterations"][0] = 1, its
+        nbad = classify(T)
+        more = (10 if nbad > 0 else 5) if more_iterations is None else more_iterations      # :2960-2964
+        if n - nbad < 10:
+            info["exp_branches"] = state["branches"]
+            return s3_record(S0), bad.astype(np.uint8), 0, info, state["margin"]
+        T, its = run(T, more)
+        info["calls"], info["iterations"][1] = 2, its
+        nbad2 = classify(T)
+    info["exp_branches"] = state["branches"]
+    return s3_record(T), bad.astype(np.uint8), n - nbad - nbad2, info, state["margin"]
+
+
+# ---- the cases -------------------------------------------------------------------------------------------------------------------------
+def cameras():
+    """two pinhole cameras (dicts of float32): 640 x 480 images"""
+    c1 = {k: np.float32(v) for k, v in (("fx", 500.0), ("fy", 500.0), ("cx", 320.0), ("cy", 240.0))}
+    c2 = {k: np.float32(v) for k, v in (("fx", 520.0), ("fy", 515.0), ("cx", 318.5), ("cy", 242.25))}
+    return c1, c2
+
+
+def sim3_rec(R, t, s):
+    r = np.zeros((), SIM3_DTYPE)
+    r["R"], r["t"], r["s"] = np.asarray(R, np.float64).reshape(9).astype(np.float32), np.asarray(t, np.float64).astype(np.float32), np.float32(s)
+    return r
+
+
+LEVEL_SCALE = np.float32(1.2) ** np.arange(8, dtype=np.float32)
+
+
+def make_case(seed, n, outliers, fix_scale, noise=True, behind=False, start=(2.0, 0.05, 0.03)):
+    """-> dict(S12 start, Strue, pairs, planted u8 [n], fix_scale).  Camera-2 points 2 to 8 m in front of camera 2, camera-1 points
+    = the true Sim3 of them held as float; observations = the projections under the true Sim3, with 0.5 px noise per level, rounded
+    to float; the start is `start` = (degrees, metres, share of the scale) off; planted outliers are 20 to 60 px off."""
+    rng = np.random.default_rng(seed)
+    cam1, cam2 = cameras()
+    Rt = _rodrigues(rng.normal(size=3) * 0.15)
+    tt = rng.normal(size=3) * 0.3
+    Strue = sim3_rec(Rt, tt, 1.1)
+    Rt, tt, st = Strue["R"].astype(np.float64).reshape(3, 3), Strue["t"].astype(np.float64), float(Strue["s"])   # the true Sim3 is the float one
+    ax = rng.normal(size=3)
+    ax /= np.linalg.norm(ax)
+    dR = _rodrigues(ax * math.radians(start[0]))
+    dt = rng.normal(size=3)
+    dt *= start[1] / np.linalg.norm(dt)
+    S12 = sim3_rec(dR @ Rt, dR @ tt + dt, st if fix_scale else st * (1.0 + start[2]))
+    fx2, fy2, cx2, cy2 = (float(cam2[k]) for k in ("fx", "fy", "cx", "cy"))
+    fx1, fy1, cx1, cy1 = (float(cam1[k]) for k in ("fx", "fy", "cx", "cy"))
+    z = rng.uniform(2.0, 8.0, n)
+    u = rng.uniform(120.0, 520.0, n)
+    v = rng.uniform(100.0, 380.0, n)
+    P2 = np.stack([(u - cx2) / fx2 * z, (v - cy2) / fy2 * z, z], 1).astype(np.float32)
+    P1 = (st * (P2.astype(np.float64) @ Rt.T) + tt).astype(np.float32)
+    A1 = st * (P2.astype(np.float64) @ Rt.T) + tt                    # S12.map(P2c)
+    A2 = ((P1.astype(np.float64) - tt) @ Rt) / st                    # S12^-1.map(P1c)
+    o1 = np.stack([A1[:, 0] / A1[:, 2] * fx1 + cx1, A1[:, 1] / A1[:, 2] * fy1 + cy1], 1)
+    o2 = np.stack([A2[:, 0] / A2[:, 2] * fx2 + cx2, A2[:, 1] / A2[:, 2] * fy2 + cy2], 1)
+    oct1, oct2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+    s1, s2 = LEVEL_SCALE[oct1], LEVEL_SCALE[oct2]
+    if noise:
+        o1 = o1 + rng.normal(size=(n, 2)) * (0.5 * s1.astype(np.float64))[:, None]
+        o2 = o2 + rng.normal(size=(n, 2)) * (0.5 * s2.astype(np.float64))[:, None]
+    planted = np.zeros(n, np.uint8)
+    k = int(round(outliers * n))
+    if k:
+        idx = rng.choice(n, k, replace=False)
+        ang = rng.uniform(0, 2 * math.pi, k)
+        mag = rng.uniform(20.0, 60.0, k)                             # at the coarsest level 20 px are still chi2 = 31 > th2
+        side = rng.random(k) < 0.5
+        off = np.stack([mag * np.cos(ang), mag * np.sin(ang)], 1)
+        o1[idx[side]] += off[side]
+        o2[idx[~side]] += off[~side]
+        planted[idx] = 1
+    p = np.zeros(n, PAIR_DTYPE)
+    p["u1"], p["v1"], p["u2"], p["v2"] = o1[:, 0], o1[:, 1], o2[:, 0], o2[:, 1]
+    p["inv_sigma2_1"], p["inv_sigma2_2"] = np.float32(1.0) / (s1 * s1), np.float32(1.0) / (s2 * s2)
+    p["P1c"], p["P2c"] = P1, P2
+    if behind and n:   # the last pair's camera-2 point maps 2 m BEHIND camera 1 under the start; its observations stay
+        Rs, ts, ss = S12["R"].astype(np.float64).reshape(3, 3), S12["t"].astype(np.float64), float(S12["s"])
+        p["P2c"][-1] = ((Rs.T @ (np.array([0.3, -0.2, -2.0]) - ts)) / ss).astype(np.float32)
+        planted[-1] = 1
+    return {"S12": S12, "Strue": Strue, "pairs": p, "planted": planted, "fix_scale": bool(fix_scale), "cam1": cam1, "cam2": cam2}
+
+
+def exact_case(n=40):
+    """Data that are exact at the start (the identity with scale 1; depths that are powers of two, pixel offsets that are dyadic):
+    chi2 = 0, b = 0, the step is 0, so rho == 0 ends the first iteration of both calls."""
+    cam1, cam2 = cameras()
+    p = np.zeros(n, PAIR_DTYPE)
+    i = np.arange(n)
+    z = np.float32(2.0) ** (1 + i % 3).astype(np.float32)
+    ku, kv = (i * 7) % 33 - 16, (i * 5) % 25 - 12
+    X = np.stack([ku * z / 64, kv * z / 64, z], 1).astype(np.float32)
+    p["P1c"], p["P2c"] = X, X
+    p["u1"], p["v1"] = ku * (500.0 / 64) + 320.0, kv * (500.0 / 64) + 240.0
+    p["u2"], p["v2"] = ku * (520.0 / 64) + 318.5, kv * (515.0 / 64) + 242.25
+    p["inv_sigma2_1"] = p["inv_sigma2_2"] = 1.0
+    S = sim3_rec(np.eye(3), np.zeros(3), 1.0)
+    return {"S12": S, "Strue": S, "pairs": p, "planted": np.zeros(n, np.uint8), "fix_scale": False, "cam1": cam1, "cam2": cam2}
+
+
+# name -> (n, outlier share, fix_scale, options of make_case)
+CASE_SPECS = {}
+for _n in (0, 1, 9, 10, 11, 64, 65, 256, 257, LDS_PAIRS, LDS_PAIRS + 1):
+    for _out in (0.0, 0.3):
+        for _fix in (True, False):
+            CASE_SPECS[f"n{_n}_{int(_out * 100)}_{'fixed' if _fix else 'free'}"] = (_n, _out, _fix, {})
+CASE_SPECS["n300_0_free_noisefree"] = (300, 0.0, False, {"noise": False})
+CASE_SPECS["n300_0_fixed_noisefree"] = (300, 0.0, True, {"noise": False})
+CASE_SPECS["n65_0_free_behind"] = (65, 0.0, False, {"behind": True})
+# one case per branch of the Sim3 exponential that the ordinary cases do not reach in a trial step (bit (|sigma| >= 1e-5) * 2 +
+# (theta >= 1e-5)): noise-free data a hair off the truth, so that the steps are that small
+CASE_SPECS["n40_0_fixed_tiny_rotation"] = (40, 0.0, True, {"noise": False, "start": (1e-4, 1e-6, 0.0)})       # branch 0
+CASE_SPECS["n40_0_free_tiny_rotation"] = (40, 0.0, False, {"noise": False, "start": (0.0, 0.0, 1e-3)})        # branch 2
+# the limit of the second call (nMoreIterations, :2960-2964) where it binds: noise-free data keep improving by more than 1e-3 of their
+# chi2 down to the rounding floor, so Terminate does not end the call first.  "limit": 5 - no pair leaves after the first call and
+# the second call runs exactly 5 iterations where 10 allowed would run more; "limit": 10 - pairs leave and the second call runs more
+# than 5 iterations where 5 allowed would stop it.  case() takes the first seed for which that holds in both orders.
+CASE_SPECS["n100_0_free_limit5"] = (100, 0.0, False, {"noise": False, "start": (6.0, 0.15, 0.08), "limit": 5})
+CASE_SPECS["n100_30_free_limit10"] = (100, 0.3, False, {"noise": False, "start": (10.0, 0.3, 0.2), "limit": 10})
+CASE_NAMES = list(CASE_SPECS) + ["exact"]
+MARGIN = 1e-6
+
+
+def run_case(c, order="device", more_iterations=None):
+    return optimize(c["S12"], c["pairs"], c["cam1"], c["cam2"], TH2, c["fix_scale"], order, more_iterations)
+
+
+def _limit_binds(c, res, limit):
+    """whether the iteration limit of the second call decides how long it runs, in both orders"""
+    for o, r in res.items():
+        if r[3]["calls"] != 2 or bool(r[1].any()) != (limit == 10):
+            return False
+        other = int(run_case(c, o, 15 - limit)[3]["iterations"][1])
+        if limit == 5 and not (r[3]["iterations"][1] == 5 and other > 5):
+            return False
+        if limit == 10 and not (r[3]["iterations"][1] > 5 and other == 5):
+            return False
+    return True
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """The case and its two references: dict(..., ref={"device": (S12_out, bad, nin, info), "edge": ...}).  A seed for which, in either
+    order, a tested chi2 lies within a relative MARGIN of th2, or for which the two orders decide differently, is rejected: the next
+    seed is taken."""
+    if name == "exact":
+        c = exact_case()
+        c["ref"] = {o: run_case(c, o)[:4] for o in ("device", "edge")}
+        return c
+    n, out, fix, opt = CASE_SPECS[name]
+    base = 1000 * (list(CASE_SPECS).index(name) + 1)
+    for seed in range(base, base + 50):
+        c = make_case(seed, n, out, fix, **{k: v for k, v in opt.items() if k != "limit"})
+        res = {o: run_case(c, o) for o in ("device", "edge")}
+        if "limit" in opt and not _limit_binds(c, res, opt["limit"]):
+            continue
+        d, e = res["device"], res["edge"]
+        same = d[2] == e[2] and (d[1] == e[1]).all() and d[3]["calls"] == e[3]["calls"]
+        if same and all(r[4] > MARGIN for r in res.values()):
+            c["seed"] = seed
+            c["ref"] = {o: r[:4] for o, r in res.items()}
+            return c
+    raise AssertionError(f"no seed for {name}")
+
+
+def sim3_doubles(rec):
+    return np.concatenate([np.asarray(rec["q"], np.float64), np.asarray(rec["t"], np.float64), [float(rec["s"])]])
+
+
+def order_difference():
+    """The largest difference of an output double between the two orders of the restatement over every case."""
+    return max(float(np.abs(sim3_doubles(case(nm)["ref"]["device"][0]) - sim3_doubles(case(nm)["ref"]["edge"][0])).max()) for nm in CASE_NAMES)

@@ -1,0 +1,239 @@
+// A C++ consumer of the Sim3 seam of psl-slam_amd/host/pslfe.hpp (pslfe::Optimizer::OptimizeSim3, the call of
+// LoopClosing::ComputeSim3 src/LoopClosing.cc:326), and the plain C++ host loop of the same restatement on one core.  Who owns what:
+// the arithmetic and the Levenberg driver psl_s3_rounds (the two optimize() calls, the removal of outlying pairs, the early return)
+// are psl-slam_amd/csrc/sim3_kernels.h; HostLoop below is the driver's `Sums` for one core and owns only the order of the sums,
+// which copies the one in the header of psl-slam_amd/csrc/pslfe_sim3.hip (a pair adds its e12 terms, then its e21 terms).  The
+// kernel instantiates the same driver with its own `Sums`.  tests/test_sim3_opt_gpu.py builds this program with g++ and compares
+// all three forms with the numpy restatement; built with -DPSL_SIM3_HOST_ONLY it needs neither the library nor a GPU
+// (tests/test_sim3_opt_cpu.py runs that build under the address and undefined-behaviour sanitizers; tools/bench_sim3_opt.py times
+// it).
+//
+// usage: sim3_main <cases.bin> <out.bin> [repeat]
+//   cases.bin: int32 K, pstride, fix_scale; float th2; PslCamera cam1, cam2; K x { PslSim3 S12; int32 n; PslSim3Pair pairs[n] }
+//              (n <= pstride)
+//   out.bin:   one section per form - "loop", then (library builds) "device" (the K candidates in one launch) and "host" (candidate
+//              by candidate through OptimizeSim3) - each K x { PslSim3D S12; int32 nin; PslSim3Info info; u8 bad[n] }; the host form
+//              reports no info (zeros)
+//   stdout:    {"candidates": K, "loop_ms": the host loop over the K candidates, best of `repeat`}
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#ifndef PSL_SIM3_HOST_ONLY
+#include "../../psl-slam_amd/host/pslfe.hpp"
+#else
+#include "../../include/pslfe.h"
+#endif
+#include "../../psl-slam_amd/csrc/sim3_kernels.h"
+
+namespace {
+
+const double kSinCosTab[444] = {
+#include "../../psl-slam_amd/csrc/psl_sincostab.inc"
+};
+
+struct Case {
+    PslSim3 S12;
+    std::vector<PslSim3Pair> pairs;
+};
+struct Result {
+    PslSim3D S12;
+    int32_t nin = 0;
+    PslSim3Info info = {0, {0, 0}, 0};
+    std::vector<uint8_t> bad;
+};
+
+PslSim3D toPod(const PslS3& S) {
+    PslSim3D o;
+    for (int i = 0; i < 4; ++i) o.q[i] = S.q[i];
+    for (int i = 0; i < 3; ++i) o.t[i] = S.t[i];
+    o.s = S.s;
+    return o;
+}
+
+// steps 2 and 3 of the order of the sums (the header of pslfe_sim3.hip) on the 256 partial sums of one value
+double reduceLanes(double* part) {
+    double G[4];
+    for (int g = 0; g < 4; ++g) {
+        double* p = part + g * PSL_POSE_GROUP;
+        for (int s = PSL_POSE_GROUP / 2; s >= 1; s >>= 1)
+            for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
+        G[g] = p[0];
+    }
+    return ((G[0] + G[1]) + G[2]) + G[3];
+}
+
+// the `Sums` of psl_s3_rounds on one core
+struct HostLoop {
+    const Case& c;
+    PslS3Cams K;
+    const int n, fixScale;
+    const double th2, delta;
+    std::vector<uint8_t> out;
+    std::vector<double> part;   // [36][256]
+    PslSim3Info info = {0, {0, 0}, 0};
+
+    HostLoop(const Case& cs, const PslCamera& cam1, const PslCamera& cam2, float th2f, int fix)
+        : c(cs), n((int)cs.pairs.size()), fixScale(fix), th2((double)th2f), delta(PSL_S3_HUBER_DELTA(th2f)), out(cs.pairs.size(), 0),
+          part((size_t)PSL_S3_NTERMS * PSL_POSE_LANES) {
+        K.fx1 = cam1.fx; K.fy1 = cam1.fy; K.cx1 = cam1.cx; K.cy1 = cam1.cy;
+        K.fx2 = cam2.fx; K.fy2 = cam2.fy; K.cx2 = cam2.cx; K.cy2 = cam2.cy;
+    }
+    const float* row(int i) const { return &c.pairs[i].u1; }
+
+    // H, b, chi2 at S: the 14 perturbed estimates once, step 1 of the order of the sums, then reduceLanes per value
+    void system(const PslS3& S, const PslS3& Si, double* acc) {
+        PslS3 pert[PSL_S3_NPERT][2];
+        for (int k = 0; k < PSL_S3_NPERT; ++k) psl_s3_perturbed(&S, k, fixScale, kSinCosTab, &pert[k][0], &pert[k][1]);
+        std::fill(part.begin(), part.end(), 0.0);
+        double a[PSL_S3_NTERMS];
+        for (int i = 0; i < n; ++i) {
+            if (out[i]) continue;
+            const int p = i % PSL_POSE_LANES;
+            for (int k = 0; k < PSL_S3_NTERMS; ++k) a[k] = part[(size_t)k * PSL_POSE_LANES + p];
+            psl_s3_edge_terms(row(i), 0, &S, &Si, pert, &K, delta, a);
+            psl_s3_edge_terms(row(i), 1, &S, &Si, pert, &K, delta, a);
+            for (int k = 0; k < PSL_S3_NTERMS; ++k) part[(size_t)k * PSL_POSE_LANES + p] = a[k];
+        }
+        for (int k = 0; k < PSL_S3_NTERMS; ++k) acc[k] = reduceLanes(&part[(size_t)k * PSL_POSE_LANES]);
+    }
+    double chi(const PslS3& S, const PslS3& Si) {
+        std::fill(part.begin(), part.begin() + PSL_POSE_LANES, 0.0);
+        for (int i = 0; i < n; ++i) {
+            if (out[i]) continue;
+            double e[2], w;
+            double& p = part[i % PSL_POSE_LANES];
+            p = p + psl_s3_edge_rho(row(i), 0, &S, &Si, &K, delta, e, &w);
+            p = p + psl_s3_edge_rho(row(i), 1, &S, &Si, &K, delta, e, &w);
+        }
+        return reduceLanes(part.data());
+    }
+    int classify(const PslS3& S, const PslS3& Si) {
+        int nbad = 0;
+        for (int i = 0; i < n; ++i) {
+            if (out[i]) continue;
+            if (psl_s3_pair_bad(row(i), &S, &Si, &K, th2)) { out[i] = 1; ++nbad; }
+        }
+        return nbad;
+    }
+    void call_done(int call, int its) {
+        info.calls = call + 1;
+        info.iterations[call] = its;
+    }
+
+    Result run() {
+        Result R;
+        PslS3 S0, S;
+        psl_s3_from_rts(c.S12.R, c.S12.t, c.S12.s, &S0);
+        int written = 0, branches = 0;
+        R.nin = psl_s3_rounds(*this, S0, n, fixScale, kSinCosTab, &S, &written, &branches);
+        info.exp_branches = branches;
+        R.S12 = toPod(S);
+        R.info = info;
+        R.bad = out;
+        return R;
+    }
+};
+
+bool writeSection(FILE* o, const std::vector<Result>& rs) {
+    for (const Result& r : rs) {
+        if (fwrite(&r.S12, sizeof(PslSim3D), 1, o) != 1 || fwrite(&r.nin, 4, 1, o) != 1 || fwrite(&r.info, sizeof(PslSim3Info), 1, o) != 1) return false;
+        if (!r.bad.empty() && fwrite(r.bad.data(), 1, r.bad.size(), o) != r.bad.size()) return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 3) { fprintf(stderr, "usage: %s cases.bin out.bin [repeat]\n", argv[0]); return 2; }
+    const int repeat = argc > 3 ? atoi(argv[3]) : 1;
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    int32_t hdr[3];
+    float th2 = 0.f;
+    PslCamera cam1, cam2;
+    if (fread(hdr, 4, 3, f) != 3 || fread(&th2, 4, 1, f) != 1 || fread(&cam1, sizeof(cam1), 1, f) != 1 || fread(&cam2, sizeof(cam2), 1, f) != 1 ||
+        hdr[0] < 0 || hdr[1] < 0) {
+        fprintf(stderr, "bad header\n");
+        return 2;
+    }
+    const int K = hdr[0], pstride = hdr[1], fixScale = hdr[2] ? 1 : 0;
+    std::vector<Case> cases(K);
+    for (Case& c : cases) {
+        int32_t n = 0;
+        if (fread(&c.S12, sizeof(PslSim3), 1, f) != 1 || fread(&n, 4, 1, f) != 1 || n < 0 || n > pstride) { fprintf(stderr, "bad case\n"); return 2; }
+        c.pairs.resize(n);
+        if (n && fread(c.pairs.data(), sizeof(PslSim3Pair), n, f) != (size_t)n) { fprintf(stderr, "short case\n"); return 2; }
+    }
+    fclose(f);
+
+    std::vector<Result> loop(K);
+    double best = -1.0;
+    for (int r = 0; r < (repeat < 1 ? 1 : repeat); ++r) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < K; ++k) loop[k] = HostLoop(cases[k], cam1, cam2, th2, fixScale).run();
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (best < 0 || ms < best) best = ms;
+    }
+    FILE* o = fopen(argv[2], "wb");
+    if (!o || !writeSection(o, loop)) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+#ifndef PSL_SIM3_HOST_ONLY
+    try {
+        pslfe::Context ctx(0);
+        std::vector<PslSim3> Sin(K);
+        std::vector<PslSim3Pair> pairs((size_t)K * pstride);
+        std::vector<int32_t> npairs(K);
+        for (int k = 0; k < K; ++k) {
+            Sin[k] = cases[k].S12;
+            npairs[k] = (int32_t)cases[k].pairs.size();
+            if (npairs[k]) memcpy(&pairs[(size_t)k * pstride], cases[k].pairs.data(), cases[k].pairs.size() * sizeof(PslSim3Pair));
+        }
+        std::vector<Result> dev(K), host(K);
+        if (K) {
+            void *dS = nullptr, *dP = nullptr, *dN = nullptr, *dO = nullptr, *dB = nullptr, *dI = nullptr, *dF = nullptr;
+            const size_t pb = pairs.size() * sizeof(PslSim3Pair), bb = (size_t)K * pstride;
+            pslfe::check(pslfe_device_alloc(ctx.get(), K * sizeof(PslSim3), &dS), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), pb ? pb : 1, &dP), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), K * 4, &dN), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), K * sizeof(PslSim3D), &dO), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), bb ? bb : 1, &dB), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), K * 4, &dI), "alloc");
+            pslfe::check(pslfe_device_alloc(ctx.get(), K * sizeof(PslSim3Info), &dF), "alloc");
+            std::vector<uint8_t> badAll(bb ? bb : 1, 0);
+            pslfe::check(pslfe_device_upload(ctx.get(), dS, Sin.data(), K * sizeof(PslSim3)), "upload");
+            if (pb) pslfe::check(pslfe_device_upload(ctx.get(), dP, pairs.data(), pb), "upload");
+            pslfe::check(pslfe_device_upload(ctx.get(), dN, npairs.data(), K * 4), "upload");
+            if (bb) pslfe::check(pslfe_device_upload(ctx.get(), dB, badAll.data(), bb), "upload");
+            pslfe::Optimizer::OptimizeSim3Device(ctx, K, (const PslSim3*)dS, (const PslSim3Pair*)dP, (const int32_t*)dN, pstride, cam1, cam2, th2,
+                                                 fixScale != 0, (PslSim3D*)dO, (uint8_t*)dB, (int32_t*)dI, (PslSim3Info*)dF);
+            ctx.synchronize();
+            std::vector<PslSim3D> Sout(K);
+            std::vector<int32_t> nin(K);
+            std::vector<PslSim3Info> info(K);
+            pslfe::check(pslfe_device_download(ctx.get(), Sout.data(), dO, K * sizeof(PslSim3D)), "download");
+            pslfe::check(pslfe_device_download(ctx.get(), nin.data(), dI, K * 4), "download");
+            pslfe::check(pslfe_device_download(ctx.get(), info.data(), dF, K * sizeof(PslSim3Info)), "download");
+            if (bb) pslfe::check(pslfe_device_download(ctx.get(), badAll.data(), dB, bb), "download");
+            for (void* p : {dS, dP, dN, dO, dB, dI, dF}) pslfe_device_free(ctx.get(), p);
+            for (int k = 0; k < K; ++k) {
+                dev[k].S12 = Sout[k]; dev[k].nin = nin[k]; dev[k].info = info[k];
+                dev[k].bad.assign(badAll.begin() + (size_t)k * pstride, badAll.begin() + (size_t)k * pstride + npairs[k]);
+                // candidate by candidate, as LoopClosing calls it
+                host[k].nin = pslfe::Optimizer::OptimizeSim3(ctx, cases[k].S12, cases[k].pairs, cam1, cam2, th2, fixScale != 0, host[k].S12, host[k].bad);
+            }
+        }
+        if (!writeSection(o, dev) || !writeSection(o, host)) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+#endif
+    if (fclose(o) != 0) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+    printf("{\"candidates\": %d, \"loop_ms\": %.6f}\n", K, best);
+    return 0;
+}
