@@ -1,0 +1,32 @@
+// Device only: steps 2 and 3 of the order of the sums (the headers of pslfe_pose.hip and pslfe_sim3.hip) on a workgroup of
+// PSL_LM_LANES threads, shared by k_pose_optimize and k_sim3_optimize.  On one core: psl_lm_reduce_lanes of lm_kernels.h.
+#ifndef PSL_LM_DEVICE_H
+#define PSL_LM_DEVICE_H
+
+#include "lm_kernels.h"
+
+// N values per thread: the butterfly inside each wave, then ((G0 + G1) + G2) + G3 of the four wave sums through LDS.  s_red holds
+// two buffers of 4 * STRIDE doubles (STRIDE >= N: the kernel's number of sums); `flip` alternates them, so one barrier per reduction
+// is enough.  Every thread calls it and gets the sums.
+template <int N, int STRIDE>
+__device__ __forceinline__ void psl_lm_reduce(double* acc, double* s_red, int& flip) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int s = PSL_LM_GROUP / 2; s >= 1; s >>= 1) v = __dadd_rn(v, __shfl_down(v, s, PSL_LM_GROUP));
+        acc[k] = v;
+    }
+    double* buf = s_red + flip * (4 * STRIDE);
+    const int lane = threadIdx.x & (PSL_LM_GROUP - 1), w = threadIdx.x / PSL_LM_GROUP;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) buf[w * STRIDE + k] = acc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = __dadd_rn(__dadd_rn(__dadd_rn(buf[k], buf[STRIDE + k]), buf[2 * STRIDE + k]), buf[3 * STRIDE + k]);
+    flip ^= 1;
+}
+
+#endif

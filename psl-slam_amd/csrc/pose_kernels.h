@@ -1,49 +1,35 @@
-// The pose optimisation (pslfe_pose.hip) as functions of one thread: the per-edge arithmetic, the 6x6 solve, the SE3 update and the
-// Levenberg driver (psl_po_rounds: the four rounds, the iterations and trials of a round, every decision g2o makes between two sums).
-// Product code.  Plain C++ text: the kernel includes it for the device and tools/dropin/pose_main.cpp for its host loop, so both run
-// the same single IEEE operations (build with -ffp-contract=off).  The driver asks its `Sums` argument for everything that is summed
-// over the edges; the order of those sums is not here but in the `Sums`.  The host loop instantiates the driver; k_pose_optimize
-// holds the same loop written out (the header of pslfe_pose.hip says why), so the two are changed together.  Restated from the
-// reference's g2o:
+// The pose optimisation (pslfe_pose.hip) as functions of one thread: the per-edge arithmetic, the SE3 update and the four rounds
+// psl_po_rounds, each one call of the Levenberg driver psl_lm_optimize<6> of lm_kernels.h (the iterations and trials of a round, the
+// 6x6 solve, every decision g2o makes between two sums).  Product code.  Plain C++ text: the kernel includes it for the device and
+// tools/dropin/pose_main.cpp for its host loop, so both run the same single IEEE operations (build with -ffp-contract=off).  The
+// rounds ask their `Problem` argument for everything that is summed over the edges; the order of those sums is not here but in the
+// `Problem`.  The host loop instantiates psl_po_rounds; k_pose_optimize holds the rounds and the driver's loop written out (the
+// header of pslfe_pose.hip says why), so they are changed together.  Restated from the reference's g2o:
 //   edge errors / Jacobians   Thirdparty/g2o/g2o/types/types_six_dof_expmap.{h,cpp} (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose)
 //   SE3Quat, exp, product     Thirdparty/g2o/g2o/types/se3quat.h, se3_ops.hpp
-//   quadratic form, Huber     Thirdparty/g2o/g2o/core/base_unary_edge.hpp, robust_kernel_impl.cpp
+//   quadratic form            Thirdparty/g2o/g2o/core/base_unary_edge.hpp
 //   the rounds                src/Optimizer.cc:696-780, :1011-1022
-//   one iteration, the loop   Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189, sparse_optimizer.cpp:354-419
 // Eigen is not in the reference tree, so where g2o hands a step to Eigen (quaternion <-> matrix, quaternion * vector, the products
 // of small matrices) the order written here is this library's: sums run in index order, left to right.  DESIGN.md §3, §5.0k.
 #ifndef PSL_POSE_KERNELS_H
 #define PSL_POSE_KERNELS_H
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define PSL_PO_HD __host__ __device__ static inline
-#else
-#define PSL_PO_HD static inline
-#endif
-#include <stdint.h>
+#include "lm_kernels.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
+
+#define PSL_PO_HD PSL_LM_HD
+#define PSL_PO_DIV(a, b) PSL_LM_DIV(a, b)
+#define PSL_PO_SQRT(a) PSL_LM_SQRT(a)
 
 #ifndef PSL_SC64_QUAL
 #define PSL_SC64_QUAL PSL_PO_HD
 #endif
 #include "psl_sincos_glibc.h"
 
-// division and square root: the correctly rounded device intrinsics, as csrc/proj_kernels.h takes them
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PSL_PO_DIV(a, b) __ddiv_rn((a), (b))
-#define PSL_PO_SQRT(a) __dsqrt_rn(a)
-#else
-#define PSL_PO_DIV(a, b) ((a) / (b))
-#define PSL_PO_SQRT(a) __builtin_sqrt(a)
-#endif
-
 #define PSL_POSE_NTERMS 28   // per edge: the 21 upper-triangle values of H row by row, the 6 of b (before the sign), the robust chi2
-#define PSL_POSE_LANES 256   // partial sums of the ordered reduction (the header of pslfe_pose.hip)
-#define PSL_POSE_GROUP 64    // partial sums of one butterfly
 
 struct PslSE3 {
     double q[4];   // x y z w
@@ -57,6 +43,7 @@ struct PslPoseCamD {
 // Huber deltas as Optimizer.cc:274-275 holds them: `const float deltaMono = sqrt(5.991)`, a double root rounded to float
 #define PSL_POSE_DELTA_MONO 2.4476518630981445   /* (float)sqrt(5.991) */
 #define PSL_POSE_DELTA_STEREO 2.7955322265625     /* (float)sqrt(7.815) */
+#define PSL_POSE_DELTA(mono) ((mono) ? PSL_POSE_DELTA_MONO : PSL_POSE_DELTA_STEREO)   // the delta of psl_lm_huber for a point edge
 
 PSL_PO_HD void psl_po_cross(const double* a, const double* b, double* o) {
     o[0] = a[1] * b[2] - a[2] * b[1];
@@ -216,18 +203,6 @@ PSL_PO_HD double psl_po_chi2(const double* e, double is2, int mono) {
     return mono ? c : c + e[2] * (is2 * e[2]);
 }
 
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-92): rho(chi2) and rho'(chi2)
-PSL_PO_HD void psl_po_huber(double chi2, int mono, double* rho0, double* rho1) {
-    const double delta = mono ? PSL_POSE_DELTA_MONO : PSL_POSE_DELTA_STEREO;
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) { *rho0 = chi2; *rho1 = 1.0; }
-    else {
-        const double sq = PSL_PO_SQRT(chi2);
-        *rho0 = (2.0 * sq) * delta - dsqr;
-        *rho1 = PSL_PO_DIV(delta, sq);
-    }
-}
-
 // linearizeOplus (types_six_dof_expmap.cpp:266-288, :335-364) and constructQuadraticForm (base_unary_edge.hpp:43-72) of one edge:
 // adds its 28 terms to acc.  w = rho' * invSigma2 weighs both H and b.
 PSL_PO_HD void psl_po_add_terms(const double* e, const double* Pc, int mono, double is2, double rho0, double rho1, const PslPoseCamD* K,
@@ -307,18 +282,6 @@ PSL_PO_HD double psl_po_lil_chi2(const double* e) {
     return c;
 }
 
-// RobustKernelHuber::robustify with the LIL delta
-PSL_PO_HD void psl_po_lil_huber(double chi2, double* rho0, double* rho1) {
-    const double delta = PSL_POSE_DELTA_LIL;
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) { *rho0 = chi2; *rho1 = 1.0; }
-    else {
-        const double sq = PSL_PO_SQRT(chi2);
-        *rho0 = (2.0 * sq) * delta - dsqr;
-        *rho1 = PSL_PO_DIV(delta, sq);
-    }
-}
-
 // a line row of _jacobianOplusXj (EdgeLIL.h:339-365) at the camera point Pc with the line (l0, l1), every entry in the header's order
 PSL_PO_HD void psl_po_lil_row_line(const double* Pc, double l0, double l1, const PslPoseCamD* K, double* J) {
     const double x = Pc[0], y = Pc[1], invz = PSL_PO_DIV(1.0, Pc[2]), invz2 = invz * invz;
@@ -383,152 +346,44 @@ PSL_PO_HD void psl_po_lil_add_terms(const double* L, const double* e, const PslS
     acc[27] = acc[27] + rho0;
 }
 
-// (H + lambda I) x = b by LDLt without pivoting; H: the 21 upper-triangle values row by row.  Returns 0 - "the solve failed" - when a
-// pivot is not a finite positive number (the matrix is then not positive definite to working precision); x is not written then.
-PSL_PO_HD int psl_po_solve6(const double* H, double lambda, const double* b, double* x) {
-    double A[6][6], L[6][6], D[6], y[6];
-    int h = 0;
-    for (int j = 0; j < 6; ++j)
-        for (int k = j; k < 6; ++k, ++h) { A[j][k] = H[h]; A[k][j] = H[h]; }
-    for (int j = 0; j < 6; ++j) A[j][j] = A[j][j] + lambda;
-    int ok = 1;
-    for (int j = 0; j < 6; ++j) {
-        double d = A[j][j];
-        for (int k = 0; k < j; ++k) d = d - L[j][k] * (L[j][k] * D[k]);
-        if (!(d > 0.0) || !(d <= 1.79769313486231570815e+308)) ok = 0;
-        D[j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double s = A[i][j];
-            for (int k = 0; k < j; ++k) s = s - L[i][k] * (L[j][k] * D[k]);
-            L[i][j] = PSL_PO_DIV(s, d);
-        }
+// The estimate of a pose `Problem` and its candidate: the vertex part of what psl_lm_optimize<6> asks for.
+struct PslPoseVertex {
+    PslSE3 T, Tn;
+    const double* sctab;   // the table of psl_sincos_glibc.h
+    PSL_LM_MEMBER void candidate(double* x) {
+        PslSE3 dT;
+        psl_po_exp(x, &dT, sctab);
+        psl_po_mul(&dT, &T, &Tn);   // oplusImpl: exp(update) * estimate
     }
-    if (!ok) return 0;
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-        y[i] = s;
-    }
-    for (int i = 5; i >= 0; --i) {
-        double s = PSL_PO_DIV(y[i], D[i]);
-        for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
-        x[i] = s;
-    }
-    return 1;
-}
-
-// The rotation angle of a step, |omega|, must lie inside the range of psl_glibc_sin / psl_glibc_cos (their table index is not
-// clamped).  A step outside it - or a NaN one - only comes from non-physical data and counts as "the solve failed".
-#define PSL_POSE_THETA_MAX 105414350.0
-PSL_PO_HD int psl_po_step_ok(const double* x) {
-    const double theta = PSL_PO_SQRT((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-    return theta < PSL_POSE_THETA_MAX;
-}
-
-// The state of OptimizationAlgorithmLevenberg between two solves of a round (optimization_algorithm_levenberg.cpp)
-struct PslPoseLM {
-    double lambda, ni;
-    int nbad;   // _nBad: iterations in a row that gained less than 1e-3 of their chi2
+    PSL_LM_MEMBER void accept() { T = Tn; }
 };
 
-// computeLambdaInit (:166-180): tau * max |H_jj|
-PSL_PO_HD double psl_po_lambda_init(const double* H) {
-    double m = 0.0;
-    int h = 0;
-    for (int j = 0; j < 6; h += 6 - j, ++j) {
-        const double a = __builtin_fabs(H[h]);
-        m = a < m ? m : a;   // std::max(fabs(h), m)
-    }
-    return 1e-5 * m;
-}
-
-// rho of one trial (:129-132): (chi - chi_new) / (sum x_j (lambda x_j + b_j) + 1e-3)
-PSL_PO_HD double psl_po_rho(double chi, double chi_new, const double* x, const double* b, double lambda) {
-    double scale = 0.0;
-    for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lambda * x[j] + b[j]);
-    scale = scale + 1e-3;
-    return PSL_PO_DIV(chi - chi_new, scale);
-}
-
-// the lambda factor of an accepted step (:135-139): 1 - (2 rho - 1)^3 clamped to [1/3, 2/3]; the cube is two products
-PSL_PO_HD double psl_po_good_scale(double rho) {
-    const double t = 2.0 * rho - 1.0;
-    double alpha = 1.0 - (t * t) * t;
-    alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;    // std::min(alpha, upper)
-    return (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);     // std::max(lower, alpha)
-}
-
-// The four rounds of PoseOptimization on one vertex, each up to ten Levenberg iterations of up to ten trials.  Sums supplies what is
-// summed over the edges (in its own, fixed order) and takes the results of a round:
-//   int round                          the round index, set here; from round 1 on an edge whose outlier byte is set is not active
-//   system(T, robust, acc)             the 28 sums (PSL_POSE_NTERMS) of the active edges at T
-//   chi(T, robust)                     the robust chi2 of the active edges at T
-//   classify(T, &nbad, &nbad_lil)      the outlier bytes of ALL edges at T and the count of either kind
+// The four rounds of PoseOptimization on one vertex, each one optimize(10) (psl_lm_optimize<6>).  Problem is a PslPoseVertex that
+// also supplies what is summed over the edges (in its own, fixed order) and takes the results of a round:
+//   int round, bool robust             set here: the round index - from round 1 on an edge whose outlier byte is set is not active -
+//                                      and whether the Huber kernel is on
+//   sums(acc)                          the 28 sums (PSL_POSE_NTERMS) of the active edges at T
+//   chi()                              the robust chi2 of the active edges at Tn
+//   classify(&nbad, &nbad_lil)         the outlier bytes of ALL edges at T and the count of either kind
 //   round_done(r, its)                 round r has run its iterations (PslPoseInfo)
-// nt: the edges of both kinds, at least 3.  sctab: the table of psl_sincos_glibc.h.  T_out: the pose of the last round; nbad_out:
-// its outlying POINT edges - nInitialCorrespondences - nBad (:1022) counts an outlying LIL edge as good.
-#define PSL_POSE_DBL_MAX 1.79769313486231570815e+308
-template <class Sums>
-PSL_PO_HD void psl_po_rounds(Sums& S, const PslSE3& T0, int nt, const double* sctab, PslSE3* T_out, int* nbad_out) {
+// nt: the edges of both kinds, at least 3.  T_out: the pose of the last round; nbad_out: its outlying POINT edges -
+// nInitialCorrespondences - nBad (:1022) counts an outlying LIL edge as good.
+template <class Problem>
+PSL_PO_HD void psl_po_rounds(Problem& P, const PslSE3& T0, int nt, PslSE3* T_out, int* nbad_out) {
     int nbad = 0, nbad_lil = 0;
-    PslSE3 T = T0;
     for (int r = 0; r < 4; ++r) {
-        S.round = r;
-        T = T0;                       // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) (:719)
-        const bool robust = r < 3;    // e->setRobustKernel(0) after round index 2 (:749)
-        int its = 0;
-        if (nt - nbad - nbad_lil > 0) {   // without an active edge g2o has no vertex to optimise and optimize() returns at once
-            PslPoseLM lm = {0.0, 2.0, 0};
-            for (int it = 0; it < 10; ++it) {
-                double acc[PSL_POSE_NTERMS];
-                S.system(T, robust, acc);
-                double b[6];
-                for (int j = 0; j < 6; ++j) b[j] = -acc[21 + j];
-                double chi = acc[27];
-                const double ini_chi = chi;
-                if (it == 0) { lm.lambda = psl_po_lambda_init(acc); lm.ni = 2.0; lm.nbad = 0; }
-                double rho = 0.0;
-                int qmax = 0;
-                do {
-                    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-                    int ok = psl_po_solve6(acc, lm.lambda, b, x);
-                    if (ok && !psl_po_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
-                        ok = 0;
-                        for (int j = 0; j < 6; ++j) x[j] = 0.0;
-                    }
-                    double temp_chi = PSL_POSE_DBL_MAX;   // a failed solve (:120)
-                    PslSE3 Tn = T;
-                    if (ok) {
-                        PslSE3 dT;
-                        psl_po_exp(x, &dT, sctab);
-                        psl_po_mul(&dT, &T, &Tn);          // oplusImpl: exp(update) * estimate
-                        temp_chi = S.chi(Tn, robust);
-                    }
-                    rho = psl_po_rho(chi, temp_chi, x, b, lm.lambda);
-                    if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_POSE_DBL_MAX) {
-                        lm.lambda = lm.lambda * psl_po_good_scale(rho);
-                        lm.ni = 2.0;
-                        chi = temp_chi;
-                        T = Tn;
-                    } else {
-                        lm.lambda = lm.lambda * lm.ni;
-                        lm.ni = lm.ni * 2.0;
-                    }
-                    ++qmax;
-                } while (rho < 0 && qmax < 10);
-                ++its;
-                if (qmax == 10 || rho == 0) break;                                    // Terminate
-                if ((ini_chi - chi) * 1e3 < ini_chi) ++lm.nbad; else lm.nbad = 0;     // the _nBad rule
-                if (lm.nbad >= 3) break;
-            }
-        }
+        P.round = r;
+        P.T = T0;                 // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) (:719)
+        P.robust = r < 3;         // e->setRobustKernel(0) after round index 2 (:749)
+        // without an active edge g2o has no vertex to optimise and optimize() returns at once
+        const int its = nt - nbad - nbad_lil > 0 ? psl_lm_optimize<6>(P, 10) : 0;
         // the plain chi2 of every edge at the round's pose, as a float, against 5.991f / 7.815f (:724-780) and of every LIL edge
         // against 11.07f (:977-1008)
-        S.classify(T, &nbad, &nbad_lil);
-        S.round_done(r, its);
+        P.classify(&nbad, &nbad_lil);
+        P.round_done(r, its);
         if (nt < 10) break;   // optimizer.edges().size() < 10: all edges, not the active ones (:1011)
     }
-    *T_out = T;
+    *T_out = P.T;
     *nbad_out = nbad;
 }
 

@@ -5,13 +5,15 @@
 //   one iteration: lambda, trials, rho, Terminate                    Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189
 //   the iteration loop of a round                                    Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419
 //   the LIL edges: set-up, error / Jacobian, classification            src/Optimizer.cc:619-694, add_inc/EdgeLIL.h:210-439, :973-1008
-// Who owns what.  pose_kernels.h holds the arithmetic of an edge, the solve and the update, which the kernel and the host loop of
-// tools/dropin/pose_main.cpp share, and the Levenberg driver psl_po_rounds (the rounds, iterations and trials with every decision
-// between two sums), which that host loop instantiates.  k_pose_optimize keeps the same loop written out in its body: instantiating
-// the driver here gave the same registers, LDS and scratch and the same per-edge and reduction code, but launches 0.6 to 1.9 % slower
-// than this form on an MI355X (profiles/pose_driver_ab.json).  A change to the driver is a change to the loop below
-// and the reverse; tests/test_pose_*_gpu.py compare both with the numpy restatement bit for bit.  The device's own: which thread
-// owns which edge, the order of the sums (psl_pose_reduce), the LDS copy of the rows, the early return, the edge set-up kernels.
+// Who owns what.  pose_kernels.h holds the arithmetic of an edge, the update and the four rounds psl_po_rounds; lm_kernels.h holds
+// the solve, the Huber kernel and the Levenberg driver psl_lm_optimize (the iterations and trials of a round with every decision
+// between two sums), which OptimizeSim3 shares.  The host loop of tools/dropin/pose_main.cpp instantiates psl_po_rounds and with it
+// psl_lm_optimize<6>.  k_pose_optimize calls the same primitives but keeps the rounds and the loop of psl_lm_optimize written out in
+// its body: instantiating the driver here gave the same registers, LDS and scratch and the same per-edge and reduction code, but
+// launches 0.6 to 1.9 % slower than this form on an MI355X (profiles/pose_driver_ab.json).  A change to
+// psl_lm_optimize or psl_po_rounds is a change to the loop below and the reverse; tests/test_pose_*_gpu.py compare both with the
+// numpy restatement bit for bit.  The device's own: which thread owns which edge, the order of the sums (its steps 2 and 3 are
+// psl_lm_reduce of lm_device.h, shared with pslfe_sim3.hip), the LDS copy of the rows, the early return, the edge set-up kernels.
 // Scope: the monocular and stereo point edges (k_pose_optimize<false>, what pslfe_pose_optimize[_device] launch) and, in
 // k_pose_optimize<true> (pslfe_pose_optimize_lil[_device]), the LIL edges (EdgeLILSE3ProjectXYZ with its fixed VertexLIL) as well.
 // The LIL edges of a frame extend its edge index space: LIL edge j has the index n + j (g2o adds them after the point edges), so
@@ -38,7 +40,7 @@
 // wave sums alternate between two LDS buffers).  The block size is fixed, so nothing depends on the launch geometry, the batch size
 // or the frame's position in the batch.  tests/pose_opt_cases.py implements the same order in numpy and reproduces the bits.
 //
-// Solve and update.  Every lane of every wave solves the 6x6 system (LDLt without pivoting, psl_po_solve6) and applies the SE3
+// Solve and update.  Every lane of every wave solves the 6x6 system (LDLt without pivoting, psl_lm_solve<6>) and applies the SE3
 // update from the reduced sums it has read from LDS.  The inputs are the same bits in every lane and every operation is a single
 // IEEE operation, so the lanes agree bit for bit and all control flow is uniform.  One lane with a broadcast would execute the
 // same number of wave instructions (a wave issues for 64 lanes whether one or all are live) and add an LDS round trip and a barrier
@@ -52,14 +54,16 @@
 
 #include "pslfe_internal.h"
 #include "match_kernels.h"
+#include "proj_kernels.h"
 #include "pose_kernels.h"
+#include "lm_device.h"
 
-#define PSL_POSE_BS PSL_POSE_LANES
+#define PSL_POSE_BS PSL_LM_LANES
 #define PSL_POSE_LDS_EDGES 2048   // 56 KB of edge rows
 
 static_assert(sizeof(PslPoseLilEdge) == PSL_POSE_LIL_DOUBLES * sizeof(double), "a LIL row is 23 doubles");
 static_assert(sizeof(PslPoseEdge) == 28 && sizeof(PslPoseInfo) == 20 && sizeof(PslPose) == 48, "pose PODs");
-static_assert(PSL_POSE_BS == 4 * PSL_POSE_GROUP, "four waves of 64");
+static_assert(PSL_POSE_BS == 4 * PSL_LM_GROUP, "four waves of 64");
 
 __device__ const double g_pose_sctab[444] = {
 #include "psl_sincostab.inc"
@@ -84,33 +88,11 @@ struct PoseLilArgs {
     uint8_t* outlier;
 };
 
-// steps 2 and 3 of the order of the sums for N values per thread; `flip` alternates the LDS buffer
-template <int N>
-__device__ __forceinline__ void psl_pose_reduce(double* acc, double* s_red, int& flip) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v = __dadd_rn(v, __shfl_down(v, s, 64));
-        acc[k] = v;
-    }
-    double* buf = s_red + flip * (4 * PSL_POSE_NTERMS);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) buf[w * PSL_POSE_NTERMS + k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        acc[k] = __dadd_rn(__dadd_rn(__dadd_rn(buf[k], buf[PSL_POSE_NTERMS + k]), buf[2 * PSL_POSE_NTERMS + k]), buf[3 * PSL_POSE_NTERMS + k]);
-    flip ^= 1;
-}
-
 extern __shared__ float s_pose_edges[];
 
 // LIL: the frames have LIL edges (B); without them B is not read and the kernel is the point-edge kernel.  n: the point edges, m: the
 // LIL edges, nt = n + m: the edges (the `< 3` and `< 10` rules and the order of the sums see one index space, points first).
+// The loops over r, it and the trials are psl_po_rounds and psl_lm_optimize<6> written out (the header says why).
 template <bool LIL>
 __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseLilArgs B) {
     __shared__ double s_red[2 * 4 * PSL_POSE_NTERMS];
@@ -177,7 +159,7 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
                     const double is2 = (double)E[7 * i + 3];
                     const double c = psl_po_chi2(e, is2, mono);
                     rho0 = c;
-                    if (robust) psl_po_huber(c, mono, &rho0, &rho1);
+                    if (robust) psl_lm_huber(c, PSL_POSE_DELTA(mono), &rho0, &rho1);
                     psl_po_add_terms(e, Pc, mono, is2, rho0, rho1, &K, acc);
                 }
                 if constexpr (LIL) {
@@ -188,28 +170,28 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
                         psl_po_lil_error(L, &T, &K, e);
                         const double c = psl_po_lil_chi2(e);
                         rho0 = c;
-                        if (robust) psl_po_lil_huber(c, &rho0, &rho1);
+                        if (robust) psl_lm_huber(c, PSL_POSE_DELTA_LIL, &rho0, &rho1);
                         psl_po_lil_add_terms(L, e, &T, rho0, rho1, &K, acc);
                     }
                 }
-                psl_pose_reduce<PSL_POSE_NTERMS>(acc, s_red, flip);
+                psl_lm_reduce<PSL_POSE_NTERMS, PSL_POSE_NTERMS>(acc, s_red, flip);
                 double b[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) b[j] = -acc[21 + j];
                 double chi = acc[27];
                 const double ini_chi = chi;
-                if (it == 0) { lambda = psl_po_lambda_init(acc); ni = 2.0; lm_bad = 0; }
+                if (it == 0) { lambda = psl_lm_lambda_init<6>(acc); ni = 2.0; lm_bad = 0; }
                 double rho = 0.0;
                 int qmax = 0;
                 do {
                     double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-                    int ok = psl_po_solve6(acc, lambda, b, x);
-                    if (ok && !psl_po_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
+                    int ok = psl_lm_solve<6>(acc, lambda, b, x);
+                    if (ok && !psl_lm_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
                         ok = 0;
 #pragma unroll
                         for (int j = 0; j < 6; ++j) x[j] = 0.0;
                     }
-                    double temp_chi = 1.79769313486231570815e+308;
+                    double temp_chi = PSL_LM_DBL_MAX;   // a failed solve (:120)
                     PslSE3 Tn = T;
                     if (ok) {
                         PslSE3 dT;
@@ -222,7 +204,7 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
                             const int mono = psl_po_error(E + 7 * i, &Tn, &K, e, Pc);
                             const double c = psl_po_chi2(e, (double)E[7 * i + 3], mono);
                             rho0 = c;
-                            if (robust) psl_po_huber(c, mono, &rho0, &rho1);
+                            if (robust) psl_lm_huber(c, PSL_POSE_DELTA(mono), &rho0, &rho1);
                             cs[0] = cs[0] + rho0;
                         }
                         if constexpr (LIL) {
@@ -232,16 +214,16 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
                                 psl_po_lil_error(Lrows + (size_t)j * PSL_POSE_LIL_DOUBLES, &Tn, &K, e);
                                 const double c = psl_po_lil_chi2(e);
                                 rho0 = c;
-                                if (robust) psl_po_lil_huber(c, &rho0, &rho1);
+                                if (robust) psl_lm_huber(c, PSL_POSE_DELTA_LIL, &rho0, &rho1);
                                 cs[0] = cs[0] + rho0;
                             }
                         }
-                        psl_pose_reduce<1>(cs, s_red, flip);
+                        psl_lm_reduce<1, PSL_POSE_NTERMS>(cs, s_red, flip);
                         temp_chi = cs[0];
                     }
-                    rho = psl_po_rho(chi, temp_chi, x, b, lambda);
-                    if (rho > 0 && __builtin_fabs(temp_chi) <= 1.79769313486231570815e+308) {
-                        lambda = lambda * psl_po_good_scale(rho);
+                    rho = psl_lm_rho<6>(chi, temp_chi, x, b, lambda);
+                    if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_LM_DBL_MAX) {
+                        lambda = lambda * psl_lm_good_scale(rho);
                         ni = 2.0;
                         chi = temp_chi;
                         T = Tn;
@@ -277,7 +259,7 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
                 cnt[1] = cnt[1] + (bad ? 1.0 : 0.0);
             }
         }
-        psl_pose_reduce<LIL ? 2 : 1>(cnt, s_red, flip);   // counts: exact in any order
+        psl_lm_reduce<LIL ? 2 : 1, PSL_POSE_NTERMS>(cnt, s_red, flip);   // counts: exact in any order
         nbad = (int)cnt[0];
         if constexpr (LIL) nbad_lil = (int)cnt[1];
         if (tid == 0 && A.info) {
@@ -292,27 +274,6 @@ __global__ __launch_bounds__(PSL_POSE_BS) void k_pose_optimize(PoseArgs A, PoseL
         for (int i = 0; i < 12; ++i) Tout[i] = P[i];
         A.ngood[f] = nt - nbad;   // nInitialCorrespondences - nBad (:1022): an outlying LIL edge still counts as good
     }
-}
-
-// Ordered compaction of one chunk of 256 items of a workgroup of 256 threads: the position of this thread's item among the kept ones
-// (base + the kept items of the threads before it: a ballot inside the wave, a scan of the four wave counts through s_cnt) and base
-// moved past the chunk.  Every thread calls it (two barriers; the second lets the next chunk rewrite s_cnt).
-__device__ __forceinline__ int psl_pose_compact(bool keep, int* s_cnt, int& base) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[w] = __popcll(bal);
-    __syncthreads();
-    int wbase = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < w) wbase += s_cnt[k];
-        total += s_cnt[k];
-    }
-    const int pos = base + wbase + before;
-    base += total;
-    __syncthreads();
-    return pos;
 }
 
 // ---- the edges of a frame from its matches ------------------------------------------------------------------------------------------
@@ -330,8 +291,8 @@ struct PoseEdgeArgs {
     int estride;
 };
 
-// one workgroup per frame: the keypoints in chunks of 256, compacted in keypoint order by a ballot inside the wave and a scan of the
-// four wave counts
+// one workgroup per frame: the keypoints in chunks of 256, compacted in keypoint order (psl_wg_compact of proj_kernels.h: a ballot
+// inside the wave and a scan of the four wave counts)
 __global__ __launch_bounds__(256) void k_pose_edges(PoseEdgeArgs A) {
     __shared__ int s_cnt[4];
     const int f = blockIdx.x, tid = threadIdx.x;
@@ -351,7 +312,9 @@ __global__ __launch_bounds__(256) void k_pose_edges(PoseEdgeArgs A) {
             m = idx[i];
             if (m < 0 || m >= A.mpstride) m = -1;
         }
-        const int pos = psl_pose_compact(m >= 0, s_cnt, base);
+        int kept;
+        const int pos = base + psl_wg_compact<256>(m >= 0, s_cnt, &kept);
+        base += kept;
         if (m >= 0 && pos < A.estride) {
             const PslKeyPoint kp = kps[i];
             const int oct = min(max(kp.octave, 0), A.nlevels - 1);
@@ -426,7 +389,9 @@ __global__ __launch_bounds__(256) void k_pose_lil_edges(PoseLilEdgeArgs A) {
             if (q < 0 || q >= A.nmap) q = -1;          // mvpMapInsecs[i] == NULL
             else if (A.map[q].bad) q = -1;             // mbBad (:634)
         }
-        const int pos = psl_pose_compact(q >= 0, s_cnt, base);
+        int kept;
+        const int pos = base + psl_wg_compact<256>(q >= 0, s_cnt, &kept);
+        base += kept;
         if (q >= 0 && pos < A.lstride) {
             PslPoseLilEdge e;
             const double* W = A.map[q].w;

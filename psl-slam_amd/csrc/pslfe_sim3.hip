@@ -1,10 +1,18 @@
 // libpslfe: Optimizer::OptimizeSim3 (src/Optimizer.cc:2801-2996, called at src/LoopClosing.cc:326) for K loop candidates in one
 // launch, and its set-up loop (:2854-2933).  Product code.
 // Reference behaviour restated (in double, in the reference's order of decisions): sim3_kernels.h names every source line.
-// Who owns what.  sim3_kernels.h holds the arithmetic of a pair, the numeric Jacobian, the 7x7 solve, the Sim3 update and the
-// Levenberg driver psl_s3_rounds; the kernel and the host loop of tools/dropin/sim3_main.cpp both instantiate that driver, each
-// with its own `Sums`.  The device's own, here: which thread owns which pair, the order of the sums (psl_s3_reduce), the LDS copy
-// of the rows, the perturbed estimates shared through LDS, the error paths, the pair set-up kernel.
+// Who owns what.  sim3_kernels.h holds the arithmetic of a pair, the numeric Jacobian, the Sim3 update and the two calls
+// psl_s3_rounds; lm_kernels.h holds the 7x7 solve, the Huber kernel and the Levenberg driver psl_lm_optimize, which the pose
+// optimisation shares.  The host loop of tools/dropin/sim3_main.cpp instantiates psl_s3_rounds and with it psl_lm_optimize<7>.
+// k_sim3_optimize calls the same primitives but keeps the two calls and the loop of psl_lm_optimize written out (sim3_rounds,
+// sim3_optimize and sim3_step below), as k_pose_optimize does: with Sim3DeviceSums as the problem of psl_lm_optimize<7> it had the
+// same VGPRs, scratch, spills, LDS and occupancy and the same count of every f64 opcode, but 254 AGPRs for 237, and launched 0.7 to
+// 1.8 % slower than this form on an MI355X, outside the parent's own spread in five of six rows (profiles/lm_core_ab.json,
+// DESIGN.md §5.0l).  This form compiles to the instructions the kernel had on its own driver.  A change to psl_lm_optimize,
+// PslS3Vertex or psl_s3_rounds is a change to those three functions and the reverse; tests/test_sim3_opt_gpu.py compares both with
+// the numpy restatement bit for bit.  The device's own, here: which thread owns which pair, the order of the sums (its
+// steps 2 and 3 are psl_lm_reduce of lm_device.h, shared with pslfe_pose.hip), the LDS copy of the rows, the perturbed estimates
+// shared through LDS, the error paths, the pair set-up kernel.
 //
 // Layout.  One workgroup of 256 threads per candidate, resident through both optimize() calls, every iteration and every trial.
 // The pair rows (12 floats) of a candidate with at most PSL_S3_LDS_PAIRS pairs are copied to LDS once (48 KB at the capacity; row
@@ -32,14 +40,16 @@
 
 #include "pslfe_internal.h"
 #include "match_kernels.h"
+#include "proj_kernels.h"
 #include "sim3_kernels.h"
+#include "lm_device.h"
 
-#define PSL_S3_BS PSL_POSE_LANES
+#define PSL_S3_BS PSL_LM_LANES
 #define PSL_S3_LDS_PAIRS 1024   // 48 KB of pair rows
 
 static_assert(sizeof(PslSim3Pair) == PSL_S3_PAIR_FLOATS * sizeof(float), "a pair row is 12 floats");
 static_assert(sizeof(PslSim3D) == sizeof(PslS3) && sizeof(PslS3) == 64, "Sim3 as 8 doubles");
-static_assert(PSL_S3_BS == 4 * PSL_POSE_GROUP, "four waves of 64");
+static_assert(PSL_S3_BS == 4 * PSL_LM_GROUP, "four waves of 64");
 
 __device__ const double g_s3_sctab[444] = {
 #include "psl_sincostab.inc"
@@ -59,36 +69,13 @@ struct Sim3Args {
     PslSim3Info* info;
 };
 
-// steps 2 and 3 of the order of the sums for N values per thread; `flip` alternates the LDS buffer
-template <int N>
-__device__ __forceinline__ void psl_s3_reduce(double* acc, double* s_red, int& flip) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v = __dadd_rn(v, __shfl_down(v, s, 64));
-        acc[k] = v;
-    }
-    double* buf = s_red + flip * (4 * PSL_S3_NTERMS);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) buf[w * PSL_S3_NTERMS + k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        acc[k] = __dadd_rn(__dadd_rn(__dadd_rn(buf[k], buf[PSL_S3_NTERMS + k]), buf[2 * PSL_S3_NTERMS + k]), buf[3 * PSL_S3_NTERMS + k]);
-    flip ^= 1;
-}
-
 // psl_s3_perturbed as a function of its own: inlined, the four branches of the exponential and the restated sin / cos and exp sit
 // in the middle of the driver's live values and the register allocator spills around them (profiles/sim3_codegen.txt)
 __device__ __noinline__ void psl_s3_perturbed_call(const PslS3* S, int k, int fix_scale, PslS3* Sp, PslS3* Spi) {
     psl_s3_perturbed(S, k, fix_scale, g_s3_sctab, Sp, Spi);
 }
 
-// the `Sums` of psl_s3_rounds on a workgroup
+// what k_sim3_optimize sums over the pairs of its candidate, on a workgroup
 struct Sim3DeviceSums {
     const float* P;       // the pair rows (LDS or HBM)
     uint8_t* out;         // the outlier bytes of the candidate
@@ -118,7 +105,7 @@ struct Sim3DeviceSums {
             psl_s3_edge_terms(row, 0, &S, &Si, s_pert, &K, delta, acc);
             psl_s3_edge_terms(row, 1, &S, &Si, s_pert, &K, delta, acc);
         }
-        psl_s3_reduce<PSL_S3_NTERMS>(acc, s_red, flip);
+        psl_lm_reduce<PSL_S3_NTERMS, PSL_S3_NTERMS>(acc, s_red, flip);
     }
     __device__ __forceinline__ double chi(const PslS3& S, const PslS3& Si) {
         double cs[1] = {0.0};
@@ -129,7 +116,7 @@ struct Sim3DeviceSums {
             cs[0] = cs[0] + psl_s3_edge_rho(row, 0, &S, &Si, &K, delta, e, &w);
             cs[0] = cs[0] + psl_s3_edge_rho(row, 1, &S, &Si, &K, delta, e, &w);
         }
-        psl_s3_reduce<1>(cs, s_red, flip);
+        psl_lm_reduce<1, PSL_S3_NTERMS>(cs, s_red, flip);
         return cs[0];
     }
     __device__ __forceinline__ int classify(const PslS3& S, const PslS3& Si) {
@@ -141,7 +128,7 @@ struct Sim3DeviceSums {
                 cnt[0] = cnt[0] + 1.0;
             }
         }
-        psl_s3_reduce<1>(cnt, s_red, flip);   // a count: exact in any order
+        psl_lm_reduce<1, PSL_S3_NTERMS>(cnt, s_red, flip);   // a count: exact in any order
         return (int)cnt[0];
     }
     __device__ __forceinline__ void call_done(int c, int its) {
@@ -151,6 +138,96 @@ struct Sim3DeviceSums {
         }
     }
 };
+
+// psl_lm_optimize<7> on a PslS3Vertex and psl_s3_rounds, written out for the kernel (the header says why).  A change to either is a
+// change to the three functions below and the reverse.
+// One trial step from the reduced sums: solves, guards the angle, applies the update as PslS3Vertex::candidate does.  Returns 1 and
+// *Sn when there is a step to evaluate.
+__device__ static inline int sim3_step(const double* acc, double lambda, const double* b, int fix_scale, const PslS3* S, double* x, PslS3* Sn,
+                                       int* branches) {
+    for (int j = 0; j < 7; ++j) x[j] = 0.0;
+    int ok = psl_lm_solve<7>(acc, lambda, b, x);
+    if (ok && !psl_lm_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
+        ok = 0;
+        for (int j = 0; j < 7; ++j) x[j] = 0.0;
+    }
+    *Sn = *S;
+    if (ok) {
+        if (fix_scale) x[6] = 0.0;
+        int br = 0;
+        psl_s3_oplus(x, fix_scale, S, g_s3_sctab, Sn, &br);
+        *branches |= 1 << br;
+    }
+    return ok;
+}
+
+// one optimize(iterations) call on the estimate *T
+__device__ static inline int sim3_optimize(Sim3DeviceSums& S, PslS3* T, int iterations, int fix_scale, int* branches) {
+    int its = 0;
+    double lambda = 0.0, ni = 2.0;
+    int lm_bad = 0;
+    for (int it = 0; it < iterations; ++it) {
+        double acc[PSL_S3_NTERMS];
+        PslS3 Ti;
+        psl_s3_inverse(T, &Ti);
+        S.system(*T, Ti, acc);
+        double b[7];
+        for (int j = 0; j < 7; ++j) b[j] = -acc[28 + j];
+        double chi = acc[35];
+        const double ini_chi = chi;
+        if (it == 0) { lambda = psl_lm_lambda_init<7>(acc); ni = 2.0; lm_bad = 0; }
+        double rho = 0.0;
+        int qmax = 0;
+        do {
+            double x[7];
+            PslS3 Tn;
+            const int ok = sim3_step(acc, lambda, b, fix_scale, T, x, &Tn, branches);
+            double temp_chi = PSL_LM_DBL_MAX;   // a failed solve (:120)
+            if (ok) {
+                PslS3 Tni;
+                psl_s3_inverse(&Tn, &Tni);
+                temp_chi = S.chi(Tn, Tni);
+            }
+            rho = psl_lm_rho<7>(chi, temp_chi, x, b, lambda);
+            if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_LM_DBL_MAX) {
+                lambda = lambda * psl_lm_good_scale(rho);
+                ni = 2.0;
+                chi = temp_chi;
+                *T = Tn;
+            } else {
+                lambda = lambda * ni;
+                ni = ni * 2.0;
+            }
+            ++qmax;
+        } while (rho < 0 && qmax < 10);
+        ++its;
+        if (qmax == 10 || rho == 0) break;                                 // Terminate
+        if ((ini_chi - chi) * 1e3 < ini_chi) ++lm_bad; else lm_bad = 0;    // the _nBad rule
+        if (lm_bad >= 3) break;
+    }
+    return its;
+}
+
+__device__ static inline int sim3_rounds(Sim3DeviceSums& S, const PslS3& S0, int npairs, int fix_scale, PslS3* S_out, int* written, int* branches) {
+    *S_out = S0;
+    *written = 0;
+    *branches = 0;
+    if (npairs <= 0) return 0;
+    PslS3 T = S0, Ti;
+    const int its0 = sim3_optimize(S, &T, 5, fix_scale, branches);
+    S.call_done(0, its0);
+    psl_s3_inverse(&T, &Ti);
+    const int nbad = S.classify(T, Ti);
+    const int more = nbad > 0 ? 10 : 5;
+    if (npairs - nbad < 10) return 0;
+    const int its1 = sim3_optimize(S, &T, more, fix_scale, branches);
+    S.call_done(1, its1);
+    psl_s3_inverse(&T, &Ti);
+    const int nbad2 = S.classify(T, Ti);
+    *S_out = T;
+    *written = 1;
+    return npairs - nbad - nbad2;
+}
 
 extern __shared__ float s_s3_pairs[];
 
@@ -197,7 +274,7 @@ __global__ __launch_bounds__(PSL_S3_BS) void k_sim3_optimize(Sim3Args A) {
     S.s_red = s_red; S.s_pert = s_pert; S.flip = 0; S.info = A.info ? A.info + c : nullptr;
     PslS3 T;
     int written = 0, branches = 0;
-    const int nin = psl_s3_rounds(S, S0, n, A.fix_scale, g_s3_sctab, &T, &written, &branches);
+    const int nin = sim3_rounds(S, S0, n, A.fix_scale, &T, &written, &branches);
     if (tid == 0) {
         PslSim3D o;
         for (int i = 0; i < 4; ++i) o.q[i] = T.q[i];
@@ -216,26 +293,6 @@ __device__ __forceinline__ float psl_s3_affine_row(const float* M, const float* 
     s = __dadd_rn(s, __dmul_rn((double)M[1], (double)X[1]));
     s = __dadd_rn(s, __dmul_rn((double)M[2], (double)X[2]));
     return (float)__dadd_rn(s, (double)t);
-}
-
-// Ordered compaction of one chunk of 256 items (psl_pose_compact of pslfe_pose.hip): a ballot inside the wave, a scan of the four
-// wave counts through s_cnt.  Every thread calls it (two barriers).
-__device__ __forceinline__ int psl_s3_compact(bool keep, int* s_cnt, int& base) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[w] = __popcll(bal);
-    __syncthreads();
-    int wbase = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < w) wbase += s_cnt[k];
-        total += s_cnt[k];
-    }
-    const int pos = base + wbase + before;
-    base += total;
-    __syncthreads();
-    return pos;
 }
 
 struct Sim3PairArgs {
@@ -260,7 +317,7 @@ struct Sim3PairArgs {
     int pstride;
 };
 
-// one workgroup per candidate: KF1's keypoints in chunks of 256, compacted in keypoint order
+// one workgroup per candidate: KF1's keypoints in chunks of 256, compacted in keypoint order (psl_wg_compact of proj_kernels.h)
 __global__ __launch_bounds__(256) void k_sim3_pairs(Sim3PairArgs A) {
     __shared__ int s_cnt[4];
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -288,7 +345,9 @@ __global__ __launch_bounds__(256) void k_sim3_pairs(Sim3PairArgs A) {
             if (j < 0 || j >= n2) j = -1;                   // an index outside its array drops the pair
             else if (A.skip1[i] || skip2[j]) j = -1;        // pMP1 NULL or bad, pMP2 bad (:2867-2869)
         }
-        const int pos = psl_s3_compact(j >= 0, s_cnt, base);
+        int kept;
+        const int pos = base + psl_wg_compact<256>(j >= 0, s_cnt, &kept);
+        base += kept;
         if (j >= 0 && pos < A.pstride) {
             const PslKeyPoint k1 = kps1[i], k2 = kps2[j];
             const float X1[3] = {A.mp1[i].x, A.mp1[i].y, A.mp1[i].z}, X2[3] = {mp2[j].x, mp2[j].y, mp2[j].z};

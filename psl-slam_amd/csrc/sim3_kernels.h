@@ -1,16 +1,16 @@
 // Optimizer::OptimizeSim3 (pslfe_sim3.hip) as functions of one thread: Sim3 and its exponential, the two projection errors of a
-// pair, g2o's numeric Jacobian, the quadratic form, the 7x7 solve and the Levenberg driver psl_s3_rounds (the two optimize() calls,
-// the removal of outlying pairs between them, the early return, the final count).  Product code.  Plain C++ text: the kernel
-// includes it for the device and tools/dropin/sim3_main.cpp for its host loop, so both run the same single IEEE operations (build
-// with -ffp-contract=off).  The driver asks its `Sums` argument for everything that is summed over the pairs; the order of those
-// sums is not here but in the `Sums`.  Restated from the reference:
+// pair, g2o's numeric Jacobian, the quadratic form, the Sim3 update and psl_s3_rounds (the two optimize() calls - each one
+// psl_lm_optimize<7> of lm_kernels.h, which holds the Levenberg loop and the 7x7 solve -, the removal of outlying pairs between
+// them, the early return, the final count).  Product code.  Plain C++ text: the kernel includes it for the device and
+// tools/dropin/sim3_main.cpp for its host loop, so both run the same single IEEE operations (build with -ffp-contract=off).
+// psl_s3_rounds asks its `Problem` argument for everything that is summed over the pairs; the order of those sums is not here but
+// in the `Problem`.  The host loop instantiates psl_s3_rounds; k_sim3_optimize holds it and the driver's loop written out (the header
+// of pslfe_sim3.hip says why), so they are changed together.  Restated from the reference:
 //   Sim3: constructors, exp, map, inverse, product   Thirdparty/g2o/g2o/types/sim3.h:59-67, :70-142, :144, :233-236, :266-272
 //   oplusImpl, the two errors                        Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h:60-69, :138-145, :160-167
 //   project                                          Thirdparty/g2o/g2o/types/se3_ops.hpp:49-55
 //   the numeric Jacobian, the quadratic form         Thirdparty/g2o/g2o/core/base_binary_edge.hpp:131-205, :55-120
-//   Huber                                            Thirdparty/g2o/g2o/core/robust_kernel_impl.cpp:78-92
 //   the calls, the classification, the return        src/Optimizer.cc:2801-2996
-//   one iteration, the loop                          Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189, sparse_optimizer.cpp:354-419
 // linearizeOplus of both edges is commented out in the reference (types_seven_dof_expmap.h:147, :169), so g2o differentiates by
 // central differences with delta = 1e-9; that is the reference's behaviour and is restated as it is.  A one-ulp difference in an
 // error becomes a 1e-5 relative difference in a Jacobian entry: the kernel, the host loop and the numpy restatement
@@ -33,11 +33,7 @@
 #endif
 
 // full unrolling keeps the small arrays below in registers on the device (indices become constants)
-#ifdef __clang__
-#define PSL_S3_UNROLL _Pragma("unroll")
-#else
-#define PSL_S3_UNROLL
-#endif
+#define PSL_S3_UNROLL PSL_LM_UNROLL
 
 // On the device the perturbed estimates of column d are read through an offset of 0 that the compiler cannot see through and that
 // depends on column d - 1 (no instruction is emitted): without it the scheduler loads all 14 estimates of an edge at once, 224 live
@@ -204,19 +200,10 @@ PSL_PO_HD void psl_s3_edge_error(const float* P, int side, const PslS3* S, const
 // chi2 = e . (invSigma2 I) e
 PSL_PO_HD double psl_s3_chi2(const double* e, double is2) { return e[0] * (is2 * e[0]) + e[1] * (is2 * e[1]); }
 
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-92) with delta = `const float deltaHuber = sqrt(th2)` (src/Optimizer.cc:2850).
-// th2 is a float and <cmath> is in scope there, so this is the FLOAT root, std::sqrt(float), widened to double by setDelta:
-// PSL_S3_HUBER_DELTA.  (For th2 = 10, what LoopClosing passes, the float root and the rounded double root are the same float.)
+// The delta of psl_lm_huber is `const float deltaHuber = sqrt(th2)` (src/Optimizer.cc:2850).  th2 is a float and <cmath> is in scope
+// there, so this is the FLOAT root, std::sqrt(float), widened to double by setDelta: PSL_S3_HUBER_DELTA.  (For th2 = 10, what
+// LoopClosing passes, the float root and the rounded double root are the same float.)
 #define PSL_S3_HUBER_DELTA(th2) ((double)__builtin_sqrtf(th2))
-PSL_PO_HD void psl_s3_huber(double chi2, double delta, double* rho0, double* rho1) {
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) { *rho0 = chi2; *rho1 = 1.0; }
-    else {
-        const double sq = PSL_PO_SQRT(chi2);
-        *rho0 = (2.0 * sq) * delta - dsqr;
-        *rho1 = PSL_PO_DIV(delta, sq);
-    }
-}
 
 // One edge of a pair at the estimate S (Si = its inverse): the error e (out), the weight w = rho' * invSigma2 that weighs both H
 // and b (out), and the edge's robust chi2 (returned).
@@ -226,7 +213,7 @@ PSL_PO_HD double psl_s3_edge_rho(const float* P, int side, const PslS3* S, const
     const double is2 = (double)P[side ? 5 : 2];
     const double c = psl_s3_chi2(e, is2);
     double rho0, rho1;
-    psl_s3_huber(c, delta, &rho0, &rho1);
+    psl_lm_huber(c, delta, &rho0, &rho1);
     *w = rho1 * is2;
     return rho0;
 }
@@ -270,168 +257,50 @@ PSL_PO_HD int psl_s3_pair_bad(const float* P, const PslS3* S, const PslS3* Si, c
     return (c12 > th2 || c21 > th2) ? 1 : 0;
 }
 
-// (H + lambda I) x = b by LDLt without pivoting in seven unknowns; H: the 28 upper-triangle values row by row.  Returns 0 - "the
-// solve failed" - when a pivot is not a finite positive number; x is not written then.  (psl_po_solve6 in seven unknowns.)
-PSL_PO_HD int psl_s3_solve7(const double* H, double lambda, const double* b, double* x) {
-    double A[7][7], L[7][7], D[7], y[7];
-    int h = 0;
-    PSL_S3_UNROLL
-    for (int j = 0; j < 7; ++j)
-        PSL_S3_UNROLL
-        for (int k = j; k < 7; ++k, ++h) { A[j][k] = H[h]; A[k][j] = H[h]; }
-    PSL_S3_UNROLL
-    for (int j = 0; j < 7; ++j) A[j][j] = A[j][j] + lambda;
-    int ok = 1;
-    PSL_S3_UNROLL
-    for (int j = 0; j < 7; ++j) {
-        double d = A[j][j];
-        PSL_S3_UNROLL
-        for (int k = 0; k < j; ++k) d = d - L[j][k] * (L[j][k] * D[k]);
-        if (!(d > 0.0) || !(d <= 1.79769313486231570815e+308)) ok = 0;
-        D[j] = d;
-        PSL_S3_UNROLL
-        for (int i = j + 1; i < 7; ++i) {
-            double s = A[i][j];
-            PSL_S3_UNROLL
-            for (int k = 0; k < j; ++k) s = s - L[i][k] * (L[j][k] * D[k]);
-            L[i][j] = PSL_PO_DIV(s, d);
-        }
-    }
-    if (!ok) return 0;
-    PSL_S3_UNROLL
-    for (int i = 0; i < 7; ++i) {
-        double s = b[i];
-        PSL_S3_UNROLL
-        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-        y[i] = s;
-    }
-    PSL_S3_UNROLL
-    for (int i = 6; i >= 0; --i) {
-        double s = PSL_PO_DIV(y[i], D[i]);
-        PSL_S3_UNROLL
-        for (int k = i + 1; k < 7; ++k) s = s - L[k][i] * x[k];
-        x[i] = s;
-    }
-    return 1;
-}
-
-// computeLambdaInit (optimization_algorithm_levenberg.cpp:166-180): tau * max |H_jj|
-PSL_PO_HD double psl_s3_lambda_init(const double* H) {
-    double m = 0.0;
-    int h = 0;
-    for (int j = 0; j < 7; h += 7 - j, ++j) {
-        const double a = __builtin_fabs(H[h]);
-        m = a < m ? m : a;
-    }
-    return 1e-5 * m;
-}
-
-// rho of one trial (:129-132)
-PSL_PO_HD double psl_s3_rho(double chi, double chi_new, const double* x, const double* b, double lambda) {
-    double scale = 0.0;
-    for (int j = 0; j < 7; ++j) scale = scale + x[j] * (lambda * x[j] + b[j]);
-    scale = scale + 1e-3;
-    return PSL_PO_DIV(chi - chi_new, scale);
-}
-
-// One trial step of an iteration from the reduced sums: solves, guards the angle, applies the update.  Returns 1 and *Sn when there
-// is a step to evaluate.  With a fixed scale oplusImpl writes 0 into the solver's own x[6] (types_seven_dof_expmap.h:62-65, the
-// const_cast), so computeScale sees it: x[6] is cleared here too.  branches: bit k set when a step took branch k of the exponential.
-PSL_PO_HD int psl_s3_step(const double* acc, double lambda, const double* b, int fix_scale, const PslS3* S, const double* tab, double* x,
-                          PslS3* Sn, int* branches) {
-    for (int j = 0; j < 7; ++j) x[j] = 0.0;
-    int ok = psl_s3_solve7(acc, lambda, b, x);
-    if (ok && !psl_po_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
-        ok = 0;
-        for (int j = 0; j < 7; ++j) x[j] = 0.0;
-    }
-    *Sn = *S;
-    if (ok) {
+// The estimate of a Sim3 `Problem` and its candidate, each used with its inverse: the vertex part of what psl_lm_optimize<7> asks for.
+struct PslS3Vertex {
+    PslS3 T, Tn;
+    int fix_scale;
+    int branches;          // bit k set when a trial step took branch k of the exponential
+    const double* sctab;   // the table of psl_sincos_glibc.h
+    // With a fixed scale oplusImpl writes 0 into the solver's own x[6] (types_seven_dof_expmap.h:62-65, the const_cast), so
+    // computeScale sees it: x[6] is cleared here too.
+    PSL_LM_MEMBER void candidate(double* x) {
         if (fix_scale) x[6] = 0.0;
         int br = 0;
-        psl_s3_oplus(x, fix_scale, S, tab, Sn, &br);
-        *branches |= 1 << br;
+        psl_s3_oplus(x, fix_scale, &T, sctab, &Tn, &br);
+        branches |= 1 << br;
     }
-    return ok;
-}
+    PSL_LM_MEMBER void accept() { T = Tn; }
+};
 
-// The two optimize() calls of OptimizeSim3 on one vertex.  Sums supplies what is summed over the pairs (in its own, fixed order):
-//   system(S, Si, acc)           the 36 sums (PSL_S3_NTERMS) of the active pairs at S (Si = S^-1); the Sums forms the 14 perturbed
-//                                estimates of the linearisation (psl_s3_perturbed) once, not per edge
-//   chi(S, Si)                   the robust chi2 of the active pairs at S
-//   classify(S, Si)              tests every ACTIVE pair at S, sets the outlier byte of an outlying one (which makes it inactive)
+// The two optimize() calls of OptimizeSim3 on one vertex.  Problem is a PslS3Vertex that also supplies what is summed over the pairs
+// (in its own, fixed order):
+//   sums(acc)                    the 36 sums (PSL_S3_NTERMS) of the active pairs at T; the Problem forms the 14 perturbed estimates
+//                                of the linearisation (psl_s3_perturbed) once, not per edge
+//   chi()                        the robust chi2 of the active pairs at Tn
+//   classify()                   tests every ACTIVE pair at T, sets the outlier byte of an outlying one (which makes it inactive)
 //                                and returns how many it set
 //   call_done(c, its)            call c has run its iterations (PslSim3Info)
-// Inside a call the Levenberg rules are those of psl_po_rounds (tau 1e-5, ten trials, rho, Terminate, the DBL_MAX trial of a failed
-// solve, the angle guard); the Huber kernel is on in both calls; the estimate carries over from the first call to the second;
-// lambda, ni and _nBad are re-initialised by each call.  Returns the return value of OptimizeSim3; *written = 0 when the reference
-// returns before writing g2oS12 back (:2966), and S_out is then S0.
-template <class Sums>
-PSL_PO_HD int psl_s3_optimize(Sums& S, PslS3* T, int iterations, int fix_scale, const double* sctab, int* branches) {
-    int its = 0;
-    double lambda = 0.0, ni = 2.0;
-    int lm_bad = 0;
-    for (int it = 0; it < iterations; ++it) {
-        double acc[PSL_S3_NTERMS];
-        PslS3 Ti;
-        psl_s3_inverse(T, &Ti);
-        S.system(*T, Ti, acc);
-        double b[7];
-        for (int j = 0; j < 7; ++j) b[j] = -acc[28 + j];
-        double chi = acc[35];
-        const double ini_chi = chi;
-        if (it == 0) { lambda = psl_s3_lambda_init(acc); ni = 2.0; lm_bad = 0; }
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            double x[7];
-            PslS3 Tn;
-            const int ok = psl_s3_step(acc, lambda, b, fix_scale, T, sctab, x, &Tn, branches);
-            double temp_chi = PSL_POSE_DBL_MAX;   // a failed solve (:120)
-            if (ok) {
-                PslS3 Tni;
-                psl_s3_inverse(&Tn, &Tni);
-                temp_chi = S.chi(Tn, Tni);
-            }
-            rho = psl_s3_rho(chi, temp_chi, x, b, lambda);
-            if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_POSE_DBL_MAX) {
-                lambda = lambda * psl_po_good_scale(rho);
-                ni = 2.0;
-                chi = temp_chi;
-                *T = Tn;
-            } else {
-                lambda = lambda * ni;
-                ni = ni * 2.0;
-            }
-            ++qmax;
-        } while (rho < 0 && qmax < 10);
-        ++its;
-        if (qmax == 10 || rho == 0) break;                                 // Terminate
-        if ((ini_chi - chi) * 1e3 < ini_chi) ++lm_bad; else lm_bad = 0;    // the _nBad rule
-        if (lm_bad >= 3) break;
-    }
-    return its;
-}
-
-template <class Sums>
-PSL_PO_HD int psl_s3_rounds(Sums& S, const PslS3& S0, int npairs, int fix_scale, const double* sctab, PslS3* S_out, int* written,
-                            int* branches) {
+// The Huber kernel is on in both calls; the estimate carries over from the first call to the second; lambda, ni and _nBad are
+// re-initialised by each call.  Returns the return value of OptimizeSim3; *written = 0 when the reference returns before writing
+// g2oS12 back (:2966), and S_out is then S0.
+template <class Problem>
+PSL_PO_HD int psl_s3_rounds(Problem& P, const PslS3& S0, int npairs, PslS3* S_out, int* written) {
     *S_out = S0;
     *written = 0;
-    *branches = 0;
+    P.branches = 0;
     if (npairs <= 0) return 0;   // no edge: nothing to optimise, nCorrespondences - nBad < 10
-    PslS3 T = S0, Ti;
-    const int its0 = psl_s3_optimize(S, &T, 5, fix_scale, sctab, branches);   // optimizer.optimize(5) (:2937)
-    S.call_done(0, its0);
-    psl_s3_inverse(&T, &Ti);
-    const int nbad = S.classify(T, Ti);                  // :2940-2958: the outlying pairs leave
+    P.T = S0;
+    const int its0 = psl_lm_optimize<7>(P, 5);           // optimizer.optimize(5) (:2937)
+    P.call_done(0, its0);
+    const int nbad = P.classify();                       // :2940-2958: the outlying pairs leave
     const int more = nbad > 0 ? 10 : 5;                  // :2960-2964
     if (npairs - nbad < 10) return 0;                    // :2966: g2oS12 is not written
-    const int its1 = psl_s3_optimize(S, &T, more, fix_scale, sctab, branches);   // :2972, from the estimate the first call left
-    S.call_done(1, its1);
-    psl_s3_inverse(&T, &Ti);
-    const int nbad2 = S.classify(T, Ti);                 // :2974-2989
-    *S_out = T;
+    const int its1 = psl_lm_optimize<7>(P, more);        // :2972, from the estimate the first call left
+    P.call_done(1, its1);
+    const int nbad2 = P.classify();                      // :2974-2989
+    *S_out = P.T;
     *written = 1;
     return npairs - nbad - nbad2;                        // nIn
 }

@@ -150,10 +150,29 @@ def pose_pins():
     print("pose_pins", len(pc.CASE_NAMES), len(lc.CASE_NAMES), len(out))
 
 
+def sim3_pins():
+    """sim3_restatement_pins.npz: what sim3_opt_cases.optimize returns on every case of its CASE_NAMES in both orders
+    (tests/test_sim3_opt_cpu.py compares the restatement with it bit for bit).  Written from the restatement while it had its own
+    copy of the iterations and trials and its own solve7; written again, it only pins the restatement against itself."""
+    import sim3_opt_cases as sc
+    out = {}
+    for nm in sc.CASE_NAMES:
+        c = sc.case(nm)
+        for order in ("device", "edge"):
+            S, bad, nin, info, margin = sc.run_case(c, order)
+            key = f"{nm}/{order}"
+            out[key + "/S12_out"], out[key + "/bad"] = np.frombuffer(S.tobytes(), np.uint8), np.asarray(bad, np.uint8)
+            out[key + "/nin"], out[key + "/info"], out[key + "/margin"] = np.int32(nin), np.frombuffer(info.tobytes(), np.uint8), np.float64(margin)
+    np.savez_compressed(os.path.join(HERE, "sim3_restatement_pins.npz"), **out)
+    print("sim3_pins", len(sc.CASE_NAMES), len(out))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["lines", "main", "glue"]
     if "pose_pins" in which:
         pose_pins()
+    if "sim3_pins" in which:
+        sim3_pins()
     if "ref" in which:
         ref()
     if "lines" in which:

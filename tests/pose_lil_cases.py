@@ -3,8 +3,8 @@ add_inc/EdgeLIL.h:210-439, src/Optimizer.cc:619-694, :973-1008) on top of tests/
 (:631-693) and the seeded cases of tests/test_pose_lil_cpu.py / test_pose_lil_gpu.py.
 
 _Lil mirrors the psl_po_lil_* functions of psl-slam_amd/csrc/pose_kernels.h operation by operation; it is an edge kind of
-pose_opt_cases.levenberg_rounds, which holds the rounds, iterations and trials for both kinds.  A LIL edge adds its 28 terms ROW BY
-ROW: each of its six Jacobian rows is a rank-one contribution that is added to the running sum before the next row is made, so an
+pose_opt_cases.levenberg_rounds, which holds the rounds for both kinds (their iterations and trials are lm_cases.levenberg).  A LIL
+edge adds its 28 terms ROW BY ROW: each of its six Jacobian rows is a rank-one contribution that is added to the running sum before the next row is made, so an
 edge is a sequence of six additions (a point edge is one).  order="device" runs these sequences in the device's order of the sums
 (LIL edge j has the edge index n + j), order="edge" edge by edge, points first, which is g2o's.
 

@@ -2,10 +2,11 @@
 float64, and the seeded cases of tests/test_pose_opt_cpu.py / test_pose_opt_gpu.py.
 
 The restatement mirrors the arithmetic of psl-slam_amd/csrc/pose_kernels.h operation by operation (every numpy ufunc is one IEEE
-operation; nothing here goes through BLAS) and its driver psl_po_rounds decision by decision, with math.sin / math.cos; it shares no
-text with the C++ and is what the kernel and the host loop are judged against.  levenberg_rounds is the one place where the rounds,
-iterations and trials are written here: it runs over a list of edge kinds (_Edges below; _Lil of tests/pose_lil_cases.py), and
-optimize() here and in pose_lil_cases are calls of it.  order="device" sums H, b and the robust chi2 in the device's order (the
+operation; nothing here goes through BLAS) and its rounds psl_po_rounds decision by decision, with math.sin / math.cos; it shares no
+text with the C++ and is what the kernel and the host loop are judged against.  levenberg_rounds is the one place where the rounds
+are written here: it runs over a list of edge kinds (_Edges below; _Lil of tests/pose_lil_cases.py), each round is one call of
+lm_cases.levenberg (the iterations and trials, shared with tests/sim3_opt_cases.py), and optimize() here and in pose_lil_cases are
+calls of it.  order="device" sums H, b and the robust chi2 in the device's order (the
 header of psl-slam_amd/csrc/pslfe_pose.hip); order="edge" sums them edge by edge, which is g2o's.
 Eigen and g2o cannot be built offline: parity with g2o itself is unpinned."""
 import functools
@@ -13,15 +14,14 @@ import math
 
 import numpy as np
 
+from lm_cases import levenberg, sum_device, sum_edge
+
 EDGE_DTYPE = np.dtype([(k, "<f4") for k in ("u", "v", "ur", "inv_sigma2", "x", "y", "z")])
 POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,))])
 INFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (4,))])
 DELTA_MONO = float(np.float32(math.sqrt(5.991)))      # const float deltaMono = sqrt(5.991)  (src/Optimizer.cc:274)
 DELTA_STEREO = float(np.float32(math.sqrt(7.815)))
 CHI2_MONO, CHI2_STEREO = np.float32(5.991), np.float32(7.815)
-DBL_MAX = 1.79769313486231570815e+308
-LANES, GROUP = 256, 64
-THETA_MAX = 105414350.0
 
 
 # ---- SE3Quat (se3quat.h) on Python floats: q = [x, y, z, w] ---------------------------------------------------------------------------
@@ -197,88 +197,8 @@ class _Edges:
         return out
 
 
-def sum_device(seq, active):
-    """The order of the sums of pslfe_pose.hip on seq [nt][A][k], the up to A additions of every edge (a point edge has one, a LIL
-    edge six; the rest is +0): partial sum p of 256 takes the edges p, p + 256, ... in ascending order and, of each, its additions in
-    order; a butterfly in each group of 64; the four group sums from left to right.  (A partial sum starts at +0 and is never -0,
-    so adding +0 for an edge the device skips, or for an addition an edge does not have, changes no bit.)"""
-    nt, A, k = seq.shape
-    c = max(-(-nt // LANES), 1)
-    P = np.zeros((c * LANES, A, k))
-    P[:nt] = np.where(active[:, None, None], seq, 0.0)
-    P = P.reshape(c, LANES, A, k)
-    part = np.zeros((LANES, k))
-    for ci in range(c):
-        for s in range(A):
-            part = part + P[ci, :, s]
-    g = part.reshape(LANES // GROUP, GROUP, k)
-    s = GROUP // 2
-    while s >= 1:
-        g[:, :s] = g[:, :s] + g[:, s:2 * s]
-        s //= 2
-    G = g[:, 0]
-    return ((G[0] + G[1]) + G[2]) + G[3]
-
-
-def sum_edge(seq, active, steps=None):
-    """Edge by edge in index order, of each edge its steps[i] additions (all A without steps) in order: g2o's order of the edges."""
-    s = np.zeros(seq.shape[2])
-    for i in np.flatnonzero(active):
-        for r in range(seq.shape[1] if steps is None else steps[i]):
-            s = s + seq[i, r]
-    return s
-
-
-def solve6(H, lam, b):
-    """(H + lam I) x = b by LDLt without pivoting; None when a pivot is not a finite positive number."""
-    A = [[0.0] * 6 for _ in range(6)]
-    h = 0
-    for j in range(6):
-        for k in range(j, 6):
-            A[j][k] = A[k][j] = float(H[h])
-            h += 1
-    for j in range(6):
-        A[j][j] = A[j][j] + lam
-    L = [[0.0] * 6 for _ in range(6)]
-    D = [0.0] * 6
-    ok = True
-    for j in range(6):
-        d = A[j][j]
-        for k in range(j):
-            d = d - L[j][k] * (L[j][k] * D[k])
-        if not (d > 0.0) or not (d <= DBL_MAX):
-            ok = False
-        D[j] = d
-        for i in range(j + 1, 6):
-            s = A[i][j]
-            for k in range(j):
-                s = s - L[i][k] * (L[j][k] * D[k])
-            L[i][j] = s / d if d != 0.0 else math.nan
-    if not ok:
-        return None
-    y = [0.0] * 6
-    for i in range(6):
-        s = b[i]
-        for k in range(i):
-            s = s - L[i][k] * y[k]
-        y[i] = s
-    x = [0.0] * 6
-    for i in range(5, -1, -1):
-        s = y[i] / D[i]
-        for k in range(i + 1, 6):
-            s = s - L[k][i] * x[k]
-        x[i] = s
-    return x
-
-
-def _div(a, b):
-    """IEEE a / b for Python floats."""
-    with np.errstate(all="ignore"):
-        return float(np.float64(a) / np.float64(b))
-
-
 def levenberg_rounds(Tcw, kinds, order="device"):
-    """The four rounds of PoseOptimization with their Levenberg iterations and trials over a list of edge kinds, which share one edge
+    """The four rounds of PoseOptimization, each one lm_cases.levenberg(problem, 10), over a list of edge kinds, which share one edge
     index space in list order.  A kind has: count; steps, the additions one of its edges makes to a sum; counted, whether its outliers
     lower the return value; thr, the float32 thresholds of its classification; chi(T) -> (what it evaluated at T, chi2 [count]);
     huber(chi2) -> (rho, rho'); additions(evaluated, T, rho, rho') -> [count][steps][28].
@@ -314,62 +234,32 @@ def levenberg_rounds(Tcw, kinds, order="device"):
             parts.append((k.huber(c)[0] if robust else c)[:, None, None])
         return float(red(parts)[0])
 
+    class Problem:
+        """the SE3 vertex and the sums of a round: the `problem` of lm_cases.levenberg"""
+        n = 6
+
+        def sums(self):
+            return system(self.T, robust)
+
+        def candidate(self, x):
+            self.Tn = se3_mul(se3_exp(x), self.T)
+
+        def chi(self):
+            return chi_of(self.Tn, robust)
+
+        def accept(self):
+            self.T = self.Tn
+
     T0 = from_pose(Tcw)
     outlier = [np.zeros(k.count, bool) for k in kinds]
-    nbad, margin, T = [0] * len(kinds), math.inf, T0
+    nbad, margin, P = [0] * len(kinds), math.inf, Problem()
     with np.errstate(all="ignore"):
         for r in range(4):
-            T = T0
+            P.T = T0
             robust = r < 3
             active = np.concatenate([~o for o in outlier])
-            its = 0
-            if nt - sum(nbad) > 0:
-                lam, ni, lm_bad = 0.0, 2.0, 0
-                for it in range(10):
-                    acc = system(T, robust)
-                    b = [-float(v) for v in acc[21:27]]
-                    chi = float(acc[27])
-                    ini_chi = chi
-                    if it == 0:
-                        m = 0.0
-                        for h in (0, 6, 11, 15, 18, 20):
-                            a = abs(float(acc[h]))
-                            m = m if a < m else a
-                        lam, ni, lm_bad = 1e-5 * m, 2.0, 0
-                    rho, qmax = 0.0, 0
-                    while True:
-                        x = solve6(acc, lam, b)
-                        if x is not None and not (math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < THETA_MAX):
-                            x = None        # a rotation angle outside the range of the device's sin / cos: as a failed solve
-                        temp_chi, Tn = DBL_MAX, T
-                        if x is not None:
-                            Tn = se3_mul(se3_exp(x), T)
-                            temp_chi = chi_of(Tn, robust)
-                        else:
-                            x = [0.0] * 6
-                        scale = 0.0
-                        for j in range(6):
-                            scale = scale + x[j] * (lam * x[j] + b[j])
-                        scale = scale + 1e-3
-                        rho = _div(chi - temp_chi, scale)
-                        if rho > 0 and math.isfinite(temp_chi):
-                            t = 2.0 * rho - 1.0
-                            alpha = 1.0 - (t * t) * t
-                            alpha = (2.0 / 3.0) if (2.0 / 3.0) < alpha else alpha
-                            lam = lam * (alpha if (1.0 / 3.0) < alpha else (1.0 / 3.0))
-                            ni, chi, T = 2.0, temp_chi, Tn
-                        else:
-                            lam = lam * ni
-                            ni = ni * 2.0
-                        qmax += 1
-                        if not (rho < 0 and qmax < 10):
-                            break
-                    its += 1
-                    if qmax == 10 or rho == 0:
-                        break
-                    lm_bad = lm_bad + 1 if (ini_chi - chi) * 1e3 < ini_chi else 0
-                    if lm_bad >= 3:
-                        break
+            its = levenberg(P, 10) if nt - sum(nbad) > 0 else 0
+            T = P.T
             for i, k in enumerate(kinds):
                 c = k.chi(T)[1]
                 outlier[i] = c.astype(np.float32) > k.thr

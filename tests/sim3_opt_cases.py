@@ -2,8 +2,8 @@
 cases of tests/test_sim3_opt_cpu.py / test_sim3_opt_gpu.py.
 
 The restatement mirrors the arithmetic of psl-slam_amd/csrc/sim3_kernels.h operation by operation (every numpy ufunc is one IEEE
-operation; nothing here goes through BLAS) and its driver psl_s3_rounds decision by decision, with math.sin / math.cos and fdlibm's
-exp written out below (psl_exp of psl_f64math.h is fdlibm's, not glibc's); it shares no text with the C++ and is what the kernel and
+operation; nothing here goes through BLAS) and its two calls psl_s3_rounds decision by decision - each call is one
+lm_cases.levenberg, shared with tests/pose_opt_cases.py -, with math.sin / math.cos and fdlibm's exp written out below (psl_exp of psl_f64math.h is fdlibm's, not glibc's); it shares no text with the C++ and is what the kernel and
 the host loop are judged against.  The Jacobians are g2o's numeric ones (central differences, delta = 1e-9), as in the reference.
 order="device" sums H, b and the robust chi2 in the device's order (the header of psl-slam_amd/csrc/pslfe_sim3.hip); order="edge"
 sums them edge by edge, which is g2o's.  Eigen and g2o cannot be built offline: parity with g2o itself is unpinned."""
@@ -13,7 +13,8 @@ import struct
 
 import numpy as np
 
-from pose_opt_cases import DBL_MAX, THETA_MAX, _div, _mat3mul, _quat_from_R, _quat_to_R, _rodrigues, _rotate, sum_device, sum_edge
+from lm_cases import _div, levenberg, sum_device, sum_edge
+from pose_opt_cases import _mat3mul, _quat_from_R, _quat_to_R, _rodrigues, _rotate
 
 SIM3_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("s", "<f4")])
 SIM3D_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
@@ -222,51 +223,6 @@ class _Pairs:
         return self.chi2(0, self.error(0, S)), self.chi2(1, self.error(1, Si))
 
 
-def solve7(H, lam, b):
-    """(H + lam I) x = b by LDLt without pivoting; None when a pivot is not a finite positive number"""
-    A = [[0.0] * 7 for _ in range(7)]
-    h = 0
-    for j in range(7):
-        for k in range(j, 7):
-            A[j][k] = A[k][j] = float(H[h])
-            h += 1
-    for j in range(7):
-        A[j][j] = A[j][j] + lam
-    L = [[0.0] * 7 for _ in range(7)]
-    D = [0.0] * 7
-    ok = True
-    for j in range(7):
-        d = A[j][j]
-        for k in range(j):
-            d = d - L[j][k] * (L[j][k] * D[k])
-        if not (d > 0.0) or not (d <= DBL_MAX):
-            ok = False
-        D[j] = d
-        for i in range(j + 1, 7):
-            s = A[i][j]
-            for k in range(j):
-                s = s - L[i][k] * (L[j][k] * D[k])
-            L[i][j] = _div(s, d)
-    if not ok:
-        return None
-    y = [0.0] * 7
-    for i in range(7):
-        s = b[i]
-        for k in range(i):
-            s = s - L[i][k] * y[k]
-        y[i] = s
-    x = [0.0] * 7
-    for i in range(6, -1, -1):
-        s = _div(y[i], D[i])
-        for k in range(i + 1, 7):
-            s = s - L[k][i] * x[k]
-        x[i] = s
-    return x
-
-
-_DIAG = (0, 7, 13, 18, 22, 25, 27)     # H_jj in the 28 upper-triangle values row by row
-
-
 def optimize(S12, pairs, cam1, cam2, th2=TH2, fix_scale=False, order="device", more_iterations=None):
     """-> (S12_out SIM3D_DTYPE record, bad u8 [n], nin, info INFO_DTYPE record, margin): margin = the least relative distance
     |chi2 - th2| / th2 of a tested edge, over both tests."""
@@ -288,58 +244,24 @@ def optimize(S12, pairs, cam1, cam2, th2=TH2, fix_scale=False, order="device", m
         r = [E.huber(E.chi2(side, E.error(side, Si if side else S)))[0] for side in (0, 1)]
         return float(red(np.stack(r, 1)[:, :, None])[0])
 
-    def run(T, iterations):
-        its = 0
-        lam, ni, lm_bad = 0.0, 2.0, 0
-        for it in range(iterations):
-            acc = system(T, s3_inverse(T))
-            b = [-float(v) for v in acc[28:35]]
-            chi = float(acc[35])
-            ini_chi = chi
-            if it == 0:
-                m = 0.0
-                for h in _DIAG:
-                    a = abs(float(acc[h]))
-                    m = m if a < m else a
-                lam, ni, lm_bad = 1e-5 * m, 2.0, 0
-            rho, qmax = 0.0, 0
-            while True:
-                x = solve7(acc, lam, b)
-                if x is not None and not (math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < THETA_MAX):
-                    x = None
-                temp_chi, Tn = DBL_MAX, T
-                if x is not None:
-                    if fix_scale:
-                        x[6] = 0.0        # oplusImpl writes into the solver's own vector (types_seven_dof_expmap.h:62-65)
-                    Tn, br = s3_oplus(x, fix_scale, T)
-                    state["branches"] |= 1 << br
-                    temp_chi = chi_of(Tn, s3_inverse(Tn))
-                else:
-                    x = [0.0] * 7
-                scale = 0.0
-                for j in range(7):
-                    scale = scale + x[j] * (lam * x[j] + b[j])
-                scale = scale + 1e-3
-                rho = _div(chi - temp_chi, scale)
-                if rho > 0 and math.isfinite(temp_chi):
-                    t = 2.0 * rho - 1.0
-                    alpha = 1.0 - (t * t) * t
-                    alpha = (2.0 / 3.0) if (2.0 / 3.0) < alpha else alpha
-                    lam = lam * (alpha if (1.0 / 3.0) < alpha else (1.0 / 3.0))
-                    ni, chi, T = 2.0, temp_chi, Tn
-                else:
-                    lam = lam * ni
-                    ni = ni * 2.0
-                qmax += 1
-                if not (rho < 0 and qmax < 10):
-                    break
-            its += 1
-            if qmax == 10 or rho == 0:
-                break
-            lm_bad = lm_bad + 1 if (ini_chi - chi) * 1e3 < ini_chi else 0
-            if lm_bad >= 3:
-                break
-        return T, its
+    class Problem:
+        """the Sim3 vertex and the sums of a call: the `problem` of lm_cases.levenberg"""
+        n = 7
+
+        def sums(self):
+            return system(self.T, s3_inverse(self.T))
+
+        def candidate(self, x):
+            if fix_scale:
+                x[6] = 0.0        # oplusImpl writes into the solver's own vector (types_seven_dof_expmap.h:62-65)
+            self.Tn, br = s3_oplus(x, fix_scale, self.T)
+            state["branches"] |= 1 << br
+
+        def chi(self):
+            return chi_of(self.Tn, s3_inverse(self.Tn))
+
+        def accept(self):
+            self.T = self.Tn
 
     def classify(T):
         c12, c21 = E.plain_chi2(T, s3_inverse(T))
@@ -352,18 +274,20 @@ def optimize(S12, pairs, cam1, cam2, th2=TH2, fix_scale=False, order="device", m
         return int(new.sum())
 
     with np.errstate(all="ignore"):
-        T, its = run(S0, 5)
+        P = Problem()
+        P.T = S0
+        its = levenberg(P, 5)
         info["calls"], info["iterations"][0] = 1, its
-        nbad = classify(T)
+        nbad = classify(P.T)
         more = (10 if nbad > 0 else 5) if more_iterations is None else more_iterations      # :2960-2964
         if n - nbad < 10:
             info["exp_branches"] = state["branches"]
             return s3_record(S0), bad.astype(np.uint8), 0, info, state["margin"]
-        T, its = run(T, more)
+        its = levenberg(P, more)
         info["calls"], info["iterations"][1] = 2, its
-        nbad2 = classify(T)
+        nbad2 = classify(P.T)
     info["exp_branches"] = state["branches"]
-    return s3_record(T), bad.astype(np.uint8), n - nbad - nbad2, info, state["margin"]
+    return s3_record(P.T), bad.astype(np.uint8), n - nbad - nbad2, info, state["margin"]
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""The restatement of Optimizer::OptimizeSim3 (tests/sim3_opt_cases.py) on its own, the ABI of the three entry points, and the
-stand-alone host program of tools/dropin/sim3_main.cpp under the address and undefined-behaviour sanitizers.  No GPU."""
+"""The restatement of Optimizer::OptimizeSim3 (tests/sim3_opt_cases.py) on its own, the restatement pinned against what it returned
+while it had its own copy of the Levenberg loop, the ABI of the three entry points, and the stand-alone host program of tools/dropin/sim3_main.cpp under the address and undefined-behaviour sanitizers.  No GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -285,6 +285,25 @@ def test_order_difference_is_the_documented_one():
     d = sc.order_difference()
     print("largest difference of an output double between the two orders:", d)
     assert d <= ORDER_DIFFERENCE
+
+
+def test_the_shared_loop_returns_what_the_written_out_loop_returned():
+    """tests/golden/sim3_restatement_pins.npz holds what sim3_opt_cases.optimize returned while the iterations, the trials and solve7
+    were written out in it (tests/golden/make_golden.py sim3_pins, run on that code): the bytes of S12_out, bad, info and of the margin
+    as a float64, and nin.  On lm_cases.levenberg it returns the same bits on every case in both orders."""
+    pins = np.load(os.path.join(ROOT, "tests", "golden", "sim3_restatement_pins.npz"))
+    checked = 0
+    for nm in sc.CASE_NAMES:
+        c = sc.case(nm)
+        for order in ("device", "edge"):
+            S, bad, nin, info, margin = sc.run_case(c, order)
+            key = f"{nm}/{order}"
+            assert S.tobytes() == pins[key + "/S12_out"].tobytes(), key
+            assert bad.dtype == np.uint8 and bad.tobytes() == pins[key + "/bad"].tobytes(), key
+            assert nin == int(pins[key + "/nin"]) and info.tobytes() == pins[key + "/info"].tobytes(), key
+            assert np.float64(margin).tobytes() == pins[key + "/margin"].tobytes(), (key, margin)
+            checked += 1
+    assert checked == 2 * len(sc.CASE_NAMES) and len(pins.files) == 10 * len(sc.CASE_NAMES)
 
 
 def test_abi_and_dtypes():

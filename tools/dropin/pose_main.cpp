@@ -1,10 +1,10 @@
 // A C++ consumer of the pose-optimisation seam of psl-slam_amd/host/pslfe.hpp (pslfe::Optimizer::PoseOptimization, the call of
 // TrackReferenceKeyFrame src/Tracking.cc:968, TrackWithMotionModel :1214 and TrackLocalMap :1331; the point edges alone or with the
 // LIL edges, PslPoseLilEdge rows), and the plain C++ host loop of the same restatement on one core.  Who owns what: the arithmetic
-// and the Levenberg driver (rounds, iterations, trials and every decision between two sums) are psl-slam_amd/csrc/pose_kernels.h;
-// HostLoop below is the driver's `Sums` for one core and owns only the order of the sums, which copies the one in the header of
-// psl-slam_amd/csrc/pslfe_pose.hip (LIL edge j has the edge index n + j and adds its six rows one after the other).  The kernel
-// shares the arithmetic and holds the driver's loop written out in its body.  tests/test_pose_opt_gpu.py and
+// and the four rounds are psl-slam_amd/csrc/pose_kernels.h, the Levenberg driver (iterations, trials and every decision between two
+// sums) and the solve psl-slam_amd/csrc/lm_kernels.h; HostLoop below is their `Problem` for one core and owns only the order of
+// the sums, which copies the one in the header of psl-slam_amd/csrc/pslfe_pose.hip (LIL edge j has the edge index n + j and adds
+// its six rows one after the other).  The kernel shares the arithmetic and holds the driver's loop written out in its body.  tests/test_pose_opt_gpu.py and
 // tests/test_pose_lil_gpu.py build this program with g++ and compare all three forms with the numpy restatement; built with
 // -DPSL_POSE_HOST_ONLY it needs neither the library nor a GPU (tests/test_pose_opt_cpu.py and tests/test_pose_lil_cpu.py run that
 // build under the address and undefined-behaviour sanitizers; tools/bench_pose_opt.py times it).
@@ -52,20 +52,8 @@ struct Result {
     std::vector<uint8_t> outlier, outlierLil;
 };
 
-// steps 2 and 3 of the order of the sums (the header of pslfe_pose.hip) on the 256 partial sums of one value
-double reduceLanes(double* part) {
-    double G[4];
-    for (int g = 0; g < 4; ++g) {
-        double* p = part + g * PSL_POSE_GROUP;
-        for (int s = PSL_POSE_GROUP / 2; s >= 1; s >>= 1)
-            for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
-        G[g] = p[0];
-    }
-    return ((G[0] + G[1]) + G[2]) + G[3];
-}
-
-// the `Sums` of psl_po_rounds on one core
-struct HostLoop {
+// the `Problem` of psl_po_rounds and psl_lm_optimize<6> on one core
+struct HostLoop : PslPoseVertex {
     const Case& c;
     PslPoseCamD K;
     const int n, m;
@@ -73,46 +61,49 @@ struct HostLoop {
     std::vector<double> part;   // [28][256]
     PslPoseInfo info = {0, {0, 0, 0, 0}};
     int round = 0;
+    bool robust = true;
 
     HostLoop(const Case& cs, const PslCamera& cam)
         : c(cs), n((int)cs.edges.size()), m((int)cs.lil.size()), out(cs.edges.size(), 0), outLil(cs.lil.size(), 0),
-          part((size_t)PSL_POSE_NTERMS * PSL_POSE_LANES) {
+          part((size_t)PSL_POSE_NTERMS * PSL_LM_LANES) {
+        sctab = kSinCosTab;
         K.fx = cam.fx; K.fy = cam.fy; K.cx = cam.cx; K.cy = cam.cy; K.bf = cam.bf;
     }
     bool active(int i) const { return round == 0 || !(i < n ? out[i] : outLil[i - n]); }
     const float* row(int i) const { return &c.edges[i].u; }
     const double* lilRow(int j) const { return c.lil[j].line1; }
 
-    // H, b, chi2 at T: step 1 of the order of the sums (the point edges, then LIL edge j at index n + j), then reduceLanes per value
-    void system(const PslSE3& T, bool robust, double* acc) {
+    // H, b, chi2 at T: step 1 of the order of the sums (the point edges, then LIL edge j at index n + j), then steps 2 and 3 per value
+    void sums(double* acc) {
         std::fill(part.begin(), part.end(), 0.0);
         double a[PSL_POSE_NTERMS];
         for (int i = 0; i < n + m; ++i) {
             if (!active(i)) continue;
-            const int p = i % PSL_POSE_LANES;
-            for (int k = 0; k < PSL_POSE_NTERMS; ++k) a[k] = part[(size_t)k * PSL_POSE_LANES + p];
+            const int p = i % PSL_LM_LANES;
+            for (int k = 0; k < PSL_POSE_NTERMS; ++k) a[k] = part[(size_t)k * PSL_LM_LANES + p];
             if (i < n) {
                 double e[3], Pc[3], rho0, rho1 = 1.0;
                 const int mono = psl_po_error(row(i), &T, &K, e, Pc);
                 const double is2 = (double)c.edges[i].inv_sigma2;
                 const double chi2 = psl_po_chi2(e, is2, mono);
                 rho0 = chi2;
-                if (robust) psl_po_huber(chi2, mono, &rho0, &rho1);
+                if (robust) psl_lm_huber(chi2, PSL_POSE_DELTA(mono), &rho0, &rho1);
                 psl_po_add_terms(e, Pc, mono, is2, rho0, rho1, &K, a);
             } else {
                 double e[6], rho0, rho1 = 1.0;
                 psl_po_lil_error(lilRow(i - n), &T, &K, e);
                 const double chi2 = psl_po_lil_chi2(e);
                 rho0 = chi2;
-                if (robust) psl_po_lil_huber(chi2, &rho0, &rho1);
+                if (robust) psl_lm_huber(chi2, PSL_POSE_DELTA_LIL, &rho0, &rho1);
                 psl_po_lil_add_terms(lilRow(i - n), e, &T, rho0, rho1, &K, a);
             }
-            for (int k = 0; k < PSL_POSE_NTERMS; ++k) part[(size_t)k * PSL_POSE_LANES + p] = a[k];
+            for (int k = 0; k < PSL_POSE_NTERMS; ++k) part[(size_t)k * PSL_LM_LANES + p] = a[k];
         }
-        for (int k = 0; k < PSL_POSE_NTERMS; ++k) acc[k] = reduceLanes(&part[(size_t)k * PSL_POSE_LANES]);
+        for (int k = 0; k < PSL_POSE_NTERMS; ++k) acc[k] = psl_lm_reduce_lanes(&part[(size_t)k * PSL_LM_LANES]);
     }
-    double chi(const PslSE3& T, bool robust) {
-        std::fill(part.begin(), part.begin() + PSL_POSE_LANES, 0.0);
+    double chi() {   // at the candidate
+        const PslSE3& T = Tn;
+        std::fill(part.begin(), part.begin() + PSL_LM_LANES, 0.0);
         for (int i = 0; i < n + m; ++i) {
             if (!active(i)) continue;
             double rho0, rho1 = 1.0;
@@ -121,19 +112,19 @@ struct HostLoop {
                 const int mono = psl_po_error(row(i), &T, &K, e, Pc);
                 const double chi2 = psl_po_chi2(e, (double)c.edges[i].inv_sigma2, mono);
                 rho0 = chi2;
-                if (robust) psl_po_huber(chi2, mono, &rho0, &rho1);
+                if (robust) psl_lm_huber(chi2, PSL_POSE_DELTA(mono), &rho0, &rho1);
             } else {
                 double e[6];
                 psl_po_lil_error(lilRow(i - n), &T, &K, e);
                 const double chi2 = psl_po_lil_chi2(e);
                 rho0 = chi2;
-                if (robust) psl_po_lil_huber(chi2, &rho0, &rho1);
+                if (robust) psl_lm_huber(chi2, PSL_POSE_DELTA_LIL, &rho0, &rho1);
             }
-            part[i % PSL_POSE_LANES] = part[i % PSL_POSE_LANES] + rho0;
+            part[i % PSL_LM_LANES] = part[i % PSL_LM_LANES] + rho0;
         }
-        return reduceLanes(part.data());
+        return psl_lm_reduce_lanes(part.data());
     }
-    void classify(const PslSE3& T, int* nbad, int* nbadLil) {
+    void classify(int* nbad, int* nbadLil) {
         *nbad = *nbadLil = 0;
         for (int i = 0; i < n; ++i) {
             double e[3], Pc[3];
@@ -160,11 +151,11 @@ struct HostLoop {
         R.outlier.assign(n, 0);
         R.outlierLil.assign(m, 0);
         if (n + m < 3) return R;
-        PslSE3 T0, T;
+        PslSE3 T0, Tout;
         int nbad = 0;
         psl_po_from_pose(c.Tcw.R, c.Tcw.t, &T0);
-        psl_po_rounds(*this, T0, n + m, kSinCosTab, &T, &nbad);
-        psl_po_to_pose(&T, R.Tcw.R, R.Tcw.t);
+        psl_po_rounds(*this, T0, n + m, &Tout, &nbad);
+        psl_po_to_pose(&Tout, R.Tcw.R, R.Tcw.t);
         R.ngood = n + m - nbad;
         R.info = info;
         R.outlier = out;

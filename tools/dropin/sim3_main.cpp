@@ -1,9 +1,10 @@
 // A C++ consumer of the Sim3 seam of psl-slam_amd/host/pslfe.hpp (pslfe::Optimizer::OptimizeSim3, the call of
 // LoopClosing::ComputeSim3 src/LoopClosing.cc:326), and the plain C++ host loop of the same restatement on one core.  Who owns what:
-// the arithmetic and the Levenberg driver psl_s3_rounds (the two optimize() calls, the removal of outlying pairs, the early return)
-// are psl-slam_amd/csrc/sim3_kernels.h; HostLoop below is the driver's `Sums` for one core and owns only the order of the sums,
-// which copies the one in the header of psl-slam_amd/csrc/pslfe_sim3.hip (a pair adds its e12 terms, then its e21 terms).  The
-// kernel instantiates the same driver with its own `Sums`.  tests/test_sim3_opt_gpu.py builds this program with g++ and compares
+// the arithmetic and psl_s3_rounds (the two optimize() calls, the removal of outlying pairs, the early return) are
+// psl-slam_amd/csrc/sim3_kernels.h, the Levenberg driver psl_lm_optimize and the solve psl-slam_amd/csrc/lm_kernels.h; HostLoop
+// below is their `Problem` for one core and owns only the order of the sums, which copies the one in the header of
+// psl-slam_amd/csrc/pslfe_sim3.hip (a pair adds its e12 terms, then its e21 terms).  The kernel shares the arithmetic and
+// holds the two calls and the driver's loop written out in its file.  tests/test_sim3_opt_gpu.py builds this program with g++ and compares
 // all three forms with the numpy restatement; built with -DPSL_SIM3_HOST_ONLY it needs neither the library nor a GPU
 // (tests/test_sim3_opt_cpu.py runs that build under the address and undefined-behaviour sanitizers; tools/bench_sim3_opt.py times
 // it).
@@ -55,64 +56,62 @@ PslSim3D toPod(const PslS3& S) {
     return o;
 }
 
-// steps 2 and 3 of the order of the sums (the header of pslfe_sim3.hip) on the 256 partial sums of one value
-double reduceLanes(double* part) {
-    double G[4];
-    for (int g = 0; g < 4; ++g) {
-        double* p = part + g * PSL_POSE_GROUP;
-        for (int s = PSL_POSE_GROUP / 2; s >= 1; s >>= 1)
-            for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
-        G[g] = p[0];
-    }
-    return ((G[0] + G[1]) + G[2]) + G[3];
-}
-
-// the `Sums` of psl_s3_rounds on one core
-struct HostLoop {
+// the `Problem` of psl_s3_rounds and psl_lm_optimize<7> on one core
+struct HostLoop : PslS3Vertex {
     const Case& c;
     PslS3Cams K;
-    const int n, fixScale;
+    const int n;
     const double th2, delta;
     std::vector<uint8_t> out;
     std::vector<double> part;   // [36][256]
     PslSim3Info info = {0, {0, 0}, 0};
 
     HostLoop(const Case& cs, const PslCamera& cam1, const PslCamera& cam2, float th2f, int fix)
-        : c(cs), n((int)cs.pairs.size()), fixScale(fix), th2((double)th2f), delta(PSL_S3_HUBER_DELTA(th2f)), out(cs.pairs.size(), 0),
-          part((size_t)PSL_S3_NTERMS * PSL_POSE_LANES) {
+        : c(cs), n((int)cs.pairs.size()), th2((double)th2f), delta(PSL_S3_HUBER_DELTA(th2f)), out(cs.pairs.size(), 0),
+          part((size_t)PSL_S3_NTERMS * PSL_LM_LANES) {
+        fix_scale = fix;
+        sctab = kSinCosTab;
         K.fx1 = cam1.fx; K.fy1 = cam1.fy; K.cx1 = cam1.cx; K.cy1 = cam1.cy;
         K.fx2 = cam2.fx; K.fy2 = cam2.fy; K.cx2 = cam2.cx; K.cy2 = cam2.cy;
     }
     const float* row(int i) const { return &c.pairs[i].u1; }
 
-    // H, b, chi2 at S: the 14 perturbed estimates once, step 1 of the order of the sums, then reduceLanes per value
-    void system(const PslS3& S, const PslS3& Si, double* acc) {
-        PslS3 pert[PSL_S3_NPERT][2];
-        for (int k = 0; k < PSL_S3_NPERT; ++k) psl_s3_perturbed(&S, k, fixScale, kSinCosTab, &pert[k][0], &pert[k][1]);
+    // H, b, chi2 at T: the 14 perturbed estimates once, step 1 of the order of the sums, then steps 2 and 3 per value
+    void sums(double* acc) {
+        const PslS3& S = T;
+        PslS3 Si, pert[PSL_S3_NPERT][2];
+        psl_s3_inverse(&S, &Si);
+        for (int k = 0; k < PSL_S3_NPERT; ++k) psl_s3_perturbed(&S, k, fix_scale, sctab, &pert[k][0], &pert[k][1]);
         std::fill(part.begin(), part.end(), 0.0);
         double a[PSL_S3_NTERMS];
         for (int i = 0; i < n; ++i) {
             if (out[i]) continue;
-            const int p = i % PSL_POSE_LANES;
-            for (int k = 0; k < PSL_S3_NTERMS; ++k) a[k] = part[(size_t)k * PSL_POSE_LANES + p];
+            const int p = i % PSL_LM_LANES;
+            for (int k = 0; k < PSL_S3_NTERMS; ++k) a[k] = part[(size_t)k * PSL_LM_LANES + p];
             psl_s3_edge_terms(row(i), 0, &S, &Si, pert, &K, delta, a);
             psl_s3_edge_terms(row(i), 1, &S, &Si, pert, &K, delta, a);
-            for (int k = 0; k < PSL_S3_NTERMS; ++k) part[(size_t)k * PSL_POSE_LANES + p] = a[k];
+            for (int k = 0; k < PSL_S3_NTERMS; ++k) part[(size_t)k * PSL_LM_LANES + p] = a[k];
         }
-        for (int k = 0; k < PSL_S3_NTERMS; ++k) acc[k] = reduceLanes(&part[(size_t)k * PSL_POSE_LANES]);
+        for (int k = 0; k < PSL_S3_NTERMS; ++k) acc[k] = psl_lm_reduce_lanes(&part[(size_t)k * PSL_LM_LANES]);
     }
-    double chi(const PslS3& S, const PslS3& Si) {
-        std::fill(part.begin(), part.begin() + PSL_POSE_LANES, 0.0);
+    double chi() {   // at the candidate
+        const PslS3& S = Tn;
+        PslS3 Si;
+        psl_s3_inverse(&S, &Si);
+        std::fill(part.begin(), part.begin() + PSL_LM_LANES, 0.0);
         for (int i = 0; i < n; ++i) {
             if (out[i]) continue;
             double e[2], w;
-            double& p = part[i % PSL_POSE_LANES];
+            double& p = part[i % PSL_LM_LANES];
             p = p + psl_s3_edge_rho(row(i), 0, &S, &Si, &K, delta, e, &w);
             p = p + psl_s3_edge_rho(row(i), 1, &S, &Si, &K, delta, e, &w);
         }
-        return reduceLanes(part.data());
+        return psl_lm_reduce_lanes(part.data());
     }
-    int classify(const PslS3& S, const PslS3& Si) {
+    int classify() {
+        const PslS3& S = T;
+        PslS3 Si;
+        psl_s3_inverse(&S, &Si);
         int nbad = 0;
         for (int i = 0; i < n; ++i) {
             if (out[i]) continue;
@@ -129,8 +128,8 @@ struct HostLoop {
         Result R;
         PslS3 S0, S;
         psl_s3_from_rts(c.S12.R, c.S12.t, c.S12.s, &S0);
-        int written = 0, branches = 0;
-        R.nin = psl_s3_rounds(*this, S0, n, fixScale, kSinCosTab, &S, &written, &branches);
+        int written = 0;
+        R.nin = psl_s3_rounds(*this, S0, n, &S, &written);
         info.exp_branches = branches;
         R.S12 = toPod(S);
         R.info = info;
