@@ -102,28 +102,55 @@ __device__ void psl_merge_two_lines(const float* l1, const float* l2, float* out
     out[2] = (float)PSL_DADD(PSL_DMUL(d2, c), xg); out[3] = (float)PSL_DADD(PSL_DMUL(d2, s), yg);
 }
 
-// One MergeLines pass (src[0..n) -> M.merged) followed by FilterShortLines(length_thr) into dst.
-// Called by all 256 threads; returns the new count (uniform).  s_i[1] accumulates the overflow flag.
-// The clustering below is the reference's serial algorithm, run by one thread; with its working set in HBM every step
-// is a dependent ~1 us access (85 % of the kernel's wave time was s_waitcnt).  For n <= PSL_MERGE_LDSN (always, at
-// 640x480) the per-line arrays it chases live in LDS: cluster code, sort order / position, length, the two BFS
-// frontiers, the sub-cluster marks.  Larger inputs use the HBM arrays (same code through flat pointers).
-// The kernel exists for two sizes of that LDS working set: 512 lines (15 KB: 8 workgroups per CU; what a 640x480 frame
-// usually has) and 1024 lines (30 KB: 5 per CU).  Both are launched; a workgroup whose frame belongs to the other one exits.
+// One MergeLines pass followed by FilterShortLines(length_thr).  Called by all 256 threads; returns the new count (uniform).
+// s_i[1] accumulates the overflow flag.  Two forms:
+//
+// psl_merge_pass_lds (n <= LN, always at 640x480): the working set of the whole pass lives in LDS - the lines (the
+// filtered output of a pass overwrites its input, so pass 2 starts where pass 1 ended), angles, lengths, sort order, the
+// cluster lists with their raw and final offsets, and the adjacency in compact form: the banded construction lists every
+// row's candidate 32-pair words (`wm`, prefix `pw`), and only those T words are kept, flattened.  Nothing on a serial or
+// single-wave path reads global memory; every such read used to be a dependent L2/HBM round trip (88 % of the kernel's
+// wave time was s_waitcnt).  Two arrays have an LDS cap and an HBM fallback through the same code: the compact adjacency
+// (T > ADJCAP words: the candidate words go to their places in the full rows of M.adj) and the final cluster lists
+// (more than CLCAP entries: M.clist, as 16-bit entries).  A frame is never truncated by an LDS cap.
+//   clustering      one wave, breadth first, lane = frontier member (see below)
+//   sub-clusters    thread = raw cluster: the raw clusters are independent, only the order of the output lists is
+//                   sequential, so every cluster is sized first (stable sort by length and the greedy walk, in the
+//                   reference's order), the sizes are prefix-summed, then the lists are written
+//   merge chains    thread = final cluster, the merged line stays in registers
+//   FilterShortLines  an ordered compaction (block scan) of those registers into the lines array
+// psl_merge_pass_hbm (n > LN, only the 1024 instance): working set in HBM, the reference's serial algorithm, literally.
+//
+// The kernel exists for two sizes of the LDS working set: 512 lines (38 KB: 4 workgroups per CU; what a 640x480 frame
+// usually has) and 1024 lines (64 KB: 2 per CU).  Both are launched; a workgroup whose frame belongs to the other one exits.
 #define PSL_MERGE_LDSN 1024
 #define PSL_MERGE_LDSN_SMALL 512
 __device__ __forceinline__ int psl_block_excl_scan256(int v, int* s_w, int* total);
 template <int LN>
 struct MergeLds {
-    int code[LN], order[LN], pos[LN], tc[LN], nx[LN], loc[LN];
+    static constexpr int ADJCAP = 2048;  // compact adjacency words kept in LDS (all 16 words of 128 rows, or 4 of each of 512)
+    static constexpr int CLCAP = 2048;   // cluster list entries kept in LDS: the n raw ones, then the final lists
+    __attribute__((aligned(16))) float lines[4 * LN];  // the current lines: input of a pass, its filtered output afterwards
+    float angles[LN];  // by index; the KeyLine responses at the end
     float length[LN];
+    uint32_t adjc[ADJCAP];  // candidate words of all rows, row after row
+    uint32_t wm[LN];        // candidate words of a sorted row (bit w): n <= 1024 -> <= 32 words
+    int coff[LN + 1], foff[LN + 1];  // offsets of the raw and of the final clusters into the list
+    uint16_t clist[CLCAP];
+    uint16_t pw[LN];  // exclusive prefix of popc(wm) over the rows (T <= 1024 * 32)
+    int16_t code[LN];
+    uint16_t order[LN], pos[LN], nx[LN];
+    union {
+        float sa[LN];  // angle by sorted position, while the bands are made
+        struct { uint16_t loc[LN], tc[LN]; };
+    };
     uint32_t bits[LN / 32];
     uint8_t clustered[LN];
-    __attribute__((aligned(16))) uint32_t row[PSL_MERGE_NMAX / 32];  // the adjacency row being scanned by the serial clustering
+    __attribute__((aligned(16))) uint32_t row[LN > PSL_MERGE_LDSN_SMALL ? PSL_MERGE_NMAX / 32 : 4];  // psl_merge_pass_hbm: the adjacency row being scanned
 };
 
-// One adjacency row HBM -> LDS with the 16-byte loads of up to 8 quads in flight: the serial scan below would otherwise
-// pay one dependent round trip per 32-pair word.
+// One adjacency row HBM -> LDS with the 16-byte loads of up to 8 quads in flight: the serial scan of psl_merge_pass_hbm
+// would otherwise pay one dependent round trip per 32-pair word.
 template <int LN>
 __device__ __forceinline__ const uint32_t* psl_merge_row(MergeLds<LN>& LD, const uint32_t* row, int words) {
     const uint4* r4 = reinterpret_cast<const uint4*>(row);
@@ -140,44 +167,55 @@ __device__ __forceinline__ const uint32_t* psl_merge_row(MergeLds<LN>& LD, const
     return LD.row;
 }
 
+// f(sorted position) for every set bit of an adjacency row, ascending.  m = the row's candidate words; r = its first
+// candidate word (compact: the candidates follow one another) or word 0 of the full row.
+template <class F>
+__device__ __forceinline__ void psl_merge_row_each(const uint32_t* r, uint32_t m, bool compact, F f) {
+    int c = 0;
+    while (m) {
+        const int w = __ffs(m) - 1;
+        m &= m - 1;
+        uint32_t v = r[compact ? c : w];
+        ++c;
+        while (v) { const int b = __ffs(v) - 1; v &= v - 1; f(w * 32 + b); }
+    }
+}
+
 template <int LN>
-__device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const float* src, float* dst, int n, float angle_threshold,
-                              float distance_threshold, float endpoint_threshold, float length_thr, int* s_i, const double* sctab) {
+__device__ int psl_merge_pass_lds(const MergeScratch& M, MergeLds<LN>& LD, int n, float angle_threshold, float distance_threshold,
+                                  float endpoint_threshold, float length_thr, int* s_i, const double* sctab) {
     const int tid = threadIdx.x, BS = 256;
+    constexpr int K = LN / 256;  // items per thread where thread = cluster
     if (n <= 0) return 0;
-    const bool small = n <= LN;
     const int words = (n + 31) >> 5;
     const int ROW = PSL_MERGE_NMAX / 32;
+    const float* src = LD.lines;
     for (int i = tid; i < n; i += BS) {
         const float dx = PSL_FSUB(src[4 * i + 2], src[4 * i]), dy = PSL_FSUB(src[4 * i + 3], src[4 * i + 1]);
-        M.angles[i] = psl_atanf(PSL_FDIV(dy, dx));  // Eigen ArrayXf::atan()
-        const float len = sqrtf(PSL_FADD(PSL_FMUL(dx, dx), PSL_FMUL(dy, dy)));
-        M.length[i] = len;
-        M.code[i] = -1;
-        if (small) { LD.length[i] = len; LD.code[i] = -1; }
+        LD.angles[i] = psl_atanf(PSL_FDIV(dy, dx));  // Eigen ArrayXf::atan()
+        LD.length[i] = sqrtf(PSL_FADD(PSL_FMUL(dx, dx), PSL_FMUL(dy, dy)));
+        LD.code[i] = -1;
     }
     __syncthreads();
     for (int i = tid; i < n; i += BS) {  // std::sort of indices by angle (stable convention H16): rank by counting
-        const float a = M.angles[i];
+        const float a = LD.angles[i];
         int r = 0;
-        for (int j = 0; j < n; ++j) { const float b = M.angles[j]; r += (b < a) || (b == a && j < i); }
-        M.pos[i] = r;
-        M.order[r] = i;
-        if (small) { LD.pos[i] = r; LD.order[r] = i; }
+        for (int j = 0; j < n; ++j) { const float b = LD.angles[j]; r += (b < a) || (b == a && j < i); }
+        LD.pos[i] = (uint16_t)r;
+        LD.order[r] = (uint16_t)i;
     }
     __syncthreads();
     const float ep_thr = PSL_FMUL(endpoint_threshold, endpoint_threshold);
-    if (small) {
-        // Adjacency over sorted positions, banded.  psl_merge_pair starts with the angle test, and the lines are sorted by
-        // angle, so for a row only the positions whose angle lies within the threshold - around the row's own angle, or
-        // across the +-pi/2 seam - can be set: three contiguous runs.  A row's candidate 32-pair words are listed in a
-        // bit mask, the (row, word) items are flattened by a prefix sum and evaluated densely; all other words are zero.
-        // (All n^2 pair tests, 97 % of them failing the angle test one lane at a time, were the kernel's main cost.)
-        float* sa = reinterpret_cast<float*>(LD.loc);  // angle by sorted position
-        int* wm = LD.tc;                               // candidate words of a row (bit w), n <= 1024 -> <= 32 words
-        int* pw = LD.nx;                               // exclusive prefix of popc(wm) over the rows
-        for (int p = tid; p < n; p += BS) sa[p] = M.angles[LD.order[p]];
-        for (int t = tid; t < n * words; t += BS) M.adj[(size_t)(t / words) * ROW + (t % words)] = 0;
+    // Adjacency over sorted positions, banded.  psl_merge_pair starts with the angle test, and the lines are sorted by
+    // angle, so for a row only the positions whose angle lies within the threshold - around the row's own angle, or
+    // across the +-pi/2 seam - can be set: three contiguous runs.  A row's candidate 32-pair words are listed in a
+    // bit mask, the (row, word) items are flattened by a prefix sum and evaluated densely; no other word is ever read.
+    // (All n^2 pair tests, 97 % of them failing the angle test one lane at a time, were the kernel's main cost.)
+    __shared__ int s_tot, s_scan[4];
+    {
+        const float* sa = LD.sa;
+        for (int p = tid; p < n; p += BS) LD.sa[p] = LD.angles[LD.order[p]];
+        if (tid == 0) s_tot = 0;
         __syncthreads();
         const float tband = angle_threshold + 1e-3f;  // superset of the exact test
         auto lower = [&](float v) { int lo = 0, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (sa[mid] < v) lo = mid + 1; else hi = mid; } return lo; };   // first p with sa[p] >= v
@@ -188,9 +226,6 @@ __device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const flo
             const uint32_t upto = b >= 31 ? 0xffffffffu : ((1u << (b + 1)) - 1u);
             return upto & ~((1u << a) - 1u);
         };
-        __shared__ int s_tot, s_scan[4];
-        if (tid == 0) s_tot = 0;
-        __syncthreads();
         for (int base = 0; base < n; base += BS) {
             const int pi = base + tid;
             uint32_t m = 0;
@@ -199,21 +234,25 @@ __device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const flo
                 m = span(lower(a - tband), upper(a + tband) - 1);
                 m |= span(lower(a + (float)PSL_PI - tband), n - 1);
                 m |= span(0, upper(a - (float)PSL_PI + tband) - 1);
-                wm[pi] = (int)m;
+                LD.wm[pi] = m;
             }
             int tot;
             const int ex = psl_block_excl_scan256(__popc(m), s_scan, &tot);
-            if (pi < n) pw[pi] = s_tot + ex;
+            if (pi < n) LD.pw[pi] = (uint16_t)(s_tot + ex);
             __syncthreads();
             if (tid == 0) s_tot += tot;
             __syncthreads();
         }
-        const int T = s_tot;
+    }
+    const int T = s_tot;
+    const bool adj_lds = T <= MergeLds<LN>::ADJCAP;  // else: the same words at their places in the full rows of M.adj
+    {
+        const uint16_t* pw = LD.pw;
         for (int k = tid; k < T; k += BS) {
             int lo = 0, hi = n;  // row = last pi with pw[pi] <= k
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (pw[mid] <= k) lo = mid + 1; else hi = mid; }
             const int pi = lo - 1;
-            uint32_t m = (uint32_t)wm[pi];
+            uint32_t m = LD.wm[pi];
             for (int r = k - pw[pi]; r > 0; --r) m &= m - 1;
             const int wj = __ffs(m) - 1;
             uint32_t bw = 0;
@@ -222,124 +261,274 @@ __device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const flo
                 const int pj = wj * 32 + b;
                 if (pj >= n || pj == pi) continue;
                 const int idxj = LD.order[pj];
-                const bool mm = pi < pj ? psl_merge_pair(src, M.angles, idxi, idxj, angle_threshold, distance_threshold, ep_thr)
-                                        : psl_merge_pair(src, M.angles, idxj, idxi, angle_threshold, distance_threshold, ep_thr);
+                const bool mm = pi < pj ? psl_merge_pair(src, LD.angles, idxi, idxj, angle_threshold, distance_threshold, ep_thr)
+                                        : psl_merge_pair(src, LD.angles, idxj, idxi, angle_threshold, distance_threshold, ep_thr);
                 bw |= (uint32_t)mm << b;
             }
-            M.adj[(size_t)pi * ROW + wj] = bw;
-        }
-    } else {
-        for (int t = tid; t < n * words; t += BS) {  // adjacency over sorted positions, one 32-pair word per step
-            const int pi = t / words, wj = t - pi * words;
-            uint32_t bw = 0;
-            const int idxi = M.order[pi];
-            for (int b = 0; b < 32; ++b) {
-                const int pj = wj * 32 + b;
-                if (pj >= n || pj == pi) continue;
-                const int idxj = M.order[pj];
-                const bool m = pi < pj ? psl_merge_pair(src, M.angles, idxi, idxj, angle_threshold, distance_threshold, ep_thr)
-                                       : psl_merge_pair(src, M.angles, idxj, idxi, angle_threshold, distance_threshold, ep_thr);
-                bw |= (uint32_t)m << b;
-            }
-            M.adj[(size_t)pi * ROW + wj] = bw;
+            if (adj_lds) LD.adjc[k] = bw; else M.adj[(size_t)pi * ROW + wj] = bw;
         }
     }
     __syncthreads();
+    // a sorted row's words for psl_merge_row_each
+    auto row_of = [&](int p) -> const uint32_t* { return adj_lds ? LD.adjc + LD.pw[p] : M.adj + (size_t)p * ROW; };
     // clustering (:159-188).  The reference walks, per cluster, a breadth-first frontier: members of `to_check` are coded and
-    // appended in list order, their still-uncoded neighbours form the next frontier (a std::set: ascending index).  Small
-    // inputs run it on one wave: lane = frontier member (or adjacency word); a neighbour k is "still uncoded" when member
-    // q is processed iff it was uncoded at the start of the round and is not itself a member at a position <= q, which
-    // makes every member independent of the others; appends are ordered compactions.  Larger inputs: serial, literally.
-    __shared__ int s_cl[3];  // ncl, total, overflow
-    if (small) {
-        if (tid < 64) {
-            const int lane = tid;
-            const unsigned long long ltm = (1ull << lane) - 1ull;
-            int* code = LD.code;
-            const int* order = LD.order;
-            const int* posv = LD.pos;
-            uint32_t* bits = LD.bits;
-            int* to_check = LD.tc;
-            int* next = LD.nx;
-            int* qpos = LD.loc;
-            for (int k = lane; k < n; k += 64) qpos[k] = 0x7fffffff;
-            if (lane == 0) M.coff[0] = 0;
+    // appended in list order, their still-uncoded neighbours form the next frontier (a std::set: ascending index).  It runs
+    // on one wave: lane = frontier member (or adjacency word); a neighbour k is "still uncoded" when member q is processed
+    // iff it was uncoded at the start of the round and is not itself a member at a position <= q, which makes every member
+    // independent of the others; appends are ordered compactions.  Every line is appended once: the n raw entries fit the list.
+    __shared__ int s_cl[2];  // ncl, nfinal under overflow
+    if (tid < 64) {
+        const int lane = tid;
+        const unsigned long long ltm = (1ull << lane) - 1ull;
+        int16_t* code = LD.code;
+        const uint16_t* order = LD.order;
+        const uint16_t* posv = LD.pos;
+        uint32_t* bits = LD.bits;
+        uint16_t* to_check = LD.tc;
+        uint16_t* next = LD.nx;
+        uint16_t* qpos = LD.loc;
+        uint16_t* clist = LD.clist;
+        for (int k = lane; k < n; k += 64) qpos[k] = 0xffff;
+        if (lane == 0) LD.coff[0] = 0;
+        __builtin_amdgcn_wave_barrier();
+        int ncl = 0, total = 0;
+        for (int i = 0; i < n; ++i) {
+            if (code[i] >= 0) continue;
+            const int new_code = ncl;
             __builtin_amdgcn_wave_barrier();
-            int ncl = 0, total = 0;
-            bool overflow = false;
-            for (int i = 0; i < n && !overflow; ++i) {
-                if (code[i] >= 0) continue;
-                const int new_code = ncl;
+            if (lane == 0) code[i] = (int16_t)new_code;
+            int ntc;
+            {   // neighbours of i in sorted-position order
+                const int p = posv[i];
+                const uint32_t m = LD.wm[p];
+                uint32_t v = 0;
+                if (lane < words && ((m >> lane) & 1u)) v = adj_lds ? LD.adjc[LD.pw[p] + __popc(m & ((1u << lane) - 1u))] : M.adj[(size_t)p * ROW + lane];
+                const int c = __popc(v);
+                int inc = c;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+                ntc = __shfl(inc, 63);
+                int o = inc - c;
+                while (v) { const int bb = __ffs(v) - 1; v &= v - 1; to_check[o++] = order[lane * 32 + bb]; }
+            }
+            if (lane == 0 && total < n) clist[total] = (uint16_t)i;
+            ++total;
+            __builtin_amdgcn_wave_barrier();
+            while (ntc > 0) {
+                if (lane < words) bits[lane] = 0;
+                for (int q = lane; q < ntc; q += 64) qpos[to_check[q]] = (uint16_t)q;
                 __builtin_amdgcn_wave_barrier();
-                if (lane == 0) code[i] = new_code;
-                int ntc;
-                {   // neighbours of i in sorted-position order
-                    uint32_t v = lane < words ? M.adj[(size_t)posv[i] * ROW + lane] : 0u;
+                for (int base = 0; base < ntc; base += 64) {
+                    const int q = base + lane;
+                    const int j = q < ntc ? to_check[q] : 0;
+                    const bool unc = q < ntc && code[j] < 0;
+                    const unsigned long long mu = __ballot(unc);
+                    const int at = total + __popcll(mu & ltm);
+                    if (unc && at < n) clist[at] = (uint16_t)j;
+                    total += __popcll(mu);
+                    if (q < ntc) {
+                        const int p = posv[j];
+                        psl_merge_row_each(row_of(p), LD.wm[p], adj_lds, [&](int pk) {
+                            const int k = order[pk];
+                            if (code[k] < 0 && !(qpos[k] <= q)) atomicOr(&bits[k >> 5], 1u << (k & 31));
+                        });
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                for (int q = lane; q < ntc; q += 64) {
+                    const int j = to_check[q];
+                    if (code[j] < 0) code[j] = (int16_t)new_code;
+                    qpos[j] = 0xffff;
+                }
+                __builtin_amdgcn_wave_barrier();
+                {   // next frontier = set bits, ascending
+                    uint32_t v = lane < words ? bits[lane] : 0u;
                     const int c = __popc(v);
                     int inc = c;
 #pragma unroll
                     for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
                     ntc = __shfl(inc, 63);
                     int o = inc - c;
-                    while (v) { const int bb = __ffs(v) - 1; v &= v - 1; to_check[o++] = order[lane * 32 + bb]; }
+                    while (v) { const int bb = __ffs(v) - 1; v &= v - 1; next[o++] = (uint16_t)(lane * 32 + bb); }
                 }
-                if (total < PSL_MERGE_CLMAX) { if (lane == 0) M.clist[total] = i; ++total; } else overflow = true;
+                uint16_t* t = to_check; to_check = next; next = t;
                 __builtin_amdgcn_wave_barrier();
-                while (ntc > 0 && !overflow) {
-                    if (lane < words) bits[lane] = 0;
-                    for (int q = lane; q < ntc; q += 64) qpos[to_check[q]] = q;
-                    __builtin_amdgcn_wave_barrier();
-                    for (int base = 0; base < ntc; base += 64) {
-                        const int q = base + lane;
-                        const int j = q < ntc ? to_check[q] : 0;
-                        const bool unc = q < ntc && code[j] < 0;
-                        const unsigned long long mu = __ballot(unc);
-                        const int at = total + __popcll(mu & ltm);
-                        if (unc && at < PSL_MERGE_CLMAX) M.clist[at] = j;
-                        total += __popcll(mu);
-                        if (total > PSL_MERGE_CLMAX) { total = PSL_MERGE_CLMAX; overflow = true; }
-                        if (q < ntc) {
-                            const uint32_t* row = M.adj + (size_t)posv[j] * ROW;
-                            for (int w = 0; w < words; ++w) {
-                                uint32_t v = row[w];
-                                while (v) {
-                                    const int bb = __ffs(v) - 1; v &= v - 1;
-                                    const int k = order[w * 32 + bb];
-                                    if (code[k] < 0 && !(qpos[k] <= q)) atomicOr(&bits[k >> 5], 1u << (k & 31));
-                                }
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    for (int q = lane; q < ntc; q += 64) {
-                        const int j = to_check[q];
-                        if (code[j] < 0) code[j] = new_code;
-                        qpos[j] = 0x7fffffff;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    {   // next frontier = set bits, ascending
-                        uint32_t v = lane < words ? bits[lane] : 0u;
-                        const int c = __popc(v);
-                        int inc = c;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
-                        ntc = __shfl(inc, 63);
-                        int o = inc - c;
-                        while (v) { const int bb = __ffs(v) - 1; v &= v - 1; next[o++] = lane * 32 + bb; }
-                    }
-                    int* t = to_check; to_check = next; next = t;
-                    __builtin_amdgcn_wave_barrier();
-                }
-                ++ncl;
-                if (lane == 0) M.coff[ncl] = total;
             }
-            if (lane == 0) { s_cl[0] = ncl; s_cl[1] = total; s_cl[2] = overflow ? 1 : 0; }
+            ++ncl;
+            if (lane == 0) LD.coff[ncl] = total < n ? total : n;
         }
-    } else if (tid == 0) {
+        if (lane == 0) { s_cl[0] = ncl; s_cl[1] = 0; }
+    }
+    __syncthreads();
+    // sub-clusters (:190-228): the final lists, appended behind the raw clusters.  Thread = raw cluster.  A cluster of at
+    // most two lines is copied.  A larger one is sorted by length, descending (stable), then the first unclustered line
+    // takes all its neighbours, marked or not, and marks them.  The adjacency is symmetric, so a line that opened a list is
+    // never marked afterwards: after the sizing walk the unmarked lines are exactly the list heads, and the writing walk
+    // needs no state of its own.
+    const int ncl = s_cl[0];
+    int nlist[K], nent[K], lbase[K], ebase[K];
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        const int c = u * BS + tid;
+        nlist[u] = 0; nent[u] = 0;
+        if (c < ncl) {
+            const int b0 = LD.coff[c], cs = LD.coff[c + 1] - b0;
+            uint16_t* cl = LD.clist + b0;
+            if (cs <= 2) { nlist[u] = 1; nent[u] = cs; }
+            else {
+                for (int a = 1; a < cs; ++a) {
+                    const uint16_t v = cl[a];
+                    const float lv = LD.length[v];
+                    int b = a - 1;
+                    while (b >= 0 && LD.length[cl[b]] < lv) { cl[b + 1] = cl[b]; --b; }
+                    cl[b + 1] = v;
+                }
+                uint8_t* clustered = LD.clustered + b0;
+                for (int q = 0; q < cs; ++q) { LD.loc[cl[q]] = (uint16_t)q; clustered[q] = 0; }
+                int nl = 0, ne = 0;
+                for (int j = 0; j < cs; ++j) {
+                    if (clustered[j]) continue;
+                    ++nl; ++ne;
+                    const int p = LD.pos[cl[j]];
+                    psl_merge_row_each(row_of(p), LD.wm[p], adj_lds, [&](int pk) { clustered[LD.loc[LD.order[pk]]] = 1; ++ne; });
+                }
+                nlist[u] = nl; nent[u] = ne;
+            }
+        }
+    }
+    int nfinal = 0, total = n;  // the final lists start behind the n raw entries
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        int t;
+        lbase[u] = nfinal + psl_block_excl_scan256(nlist[u], s_scan, &t);
+        nfinal += t;
+        ebase[u] = total + psl_block_excl_scan256(nent[u], s_scan, &t);
+        total += t;
+    }
+    // Past PSL_MERGE_CLMAX entries the reference's lists are cut as before: no entry at or behind the capacity, the list
+    // that crosses it is the last one, status bit 2.
+    const bool cl_lds = total <= MergeLds<LN>::CLCAP;
+    const bool overflow = total > PSL_MERGE_CLMAX;
+    uint16_t* fl = cl_lds ? LD.clist : reinterpret_cast<uint16_t*>(M.clist);
+    const int flcap = cl_lds ? MergeLds<LN>::CLCAP : PSL_MERGE_CLMAX;
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        const int c = u * BS + tid;
+        if (c < ncl) {
+            const int b0 = LD.coff[c], cs = LD.coff[c + 1] - b0;
+            const uint16_t* cl = LD.clist + b0;
+            int li = lbase[u], at = ebase[u];
+            auto open = [&]() { if (at <= PSL_MERGE_CLMAX) { LD.foff[li] = at; if (overflow) atomicMax(&s_cl[1], li + 1); } ++li; };
+            auto put = [&](int v) { if (at < flcap) fl[at] = (uint16_t)v; ++at; };
+            if (cs <= 2) {
+                open();
+                for (int q = 0; q < cs; ++q) put(cl[q]);
+            } else {
+                const uint8_t* clustered = LD.clustered + b0;
+                for (int j = 0; j < cs; ++j) {
+                    if (clustered[j]) continue;
+                    open();
+                    put(cl[j]);
+                    const int p = LD.pos[cl[j]];
+                    psl_merge_row_each(row_of(p), LD.wm[p], adj_lds, [&](int pk) { put(LD.order[pk]); });
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (overflow) nfinal = s_cl[1];
+    if (tid == 0) {
+        LD.foff[nfinal] = overflow ? PSL_MERGE_CLMAX : total;
+        if (overflow) s_i[1] = 1;
+    }
+    __syncthreads();
+    // merge chains (:230-262), thread = final cluster; the first line is merged with itself first.  FilterShortLines
+    // (:338-351) is an order-preserving compaction of the merged lines, from registers over the input lines.
+    const float thr2 = PSL_FMUL(length_thr, length_thr);
+    float ml[K][4];
+    bool keep[K];
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        const int c = u * BS + tid;
+        keep[u] = false;
+        ml[u][0] = ml[u][1] = ml[u][2] = ml[u][3] = 0.f;
+        if (c < nfinal) {
+            const int b0 = LD.foff[c], cs = LD.foff[c + 1] - b0;
+            if (cs > 0) {
+                const uint16_t* cl = fl + b0;
+                const int first = cl[0];
+                float nl[4] = {src[4 * first], src[4 * first + 1], src[4 * first + 2], src[4 * first + 3]};
+                for (int q = 0; q < cs; ++q) {
+                    float o[4];
+                    psl_merge_two_lines(nl, &src[4 * cl[q]], o, sctab);
+                    nl[0] = o[0]; nl[1] = o[1]; nl[2] = o[2]; nl[3] = o[3];
+                }
+                const float dx = PSL_FSUB(nl[2], nl[0]), dy = PSL_FSUB(nl[3], nl[1]);
+                keep[u] = PSL_FADD(PSL_FMUL(dx, dx), PSL_FMUL(dy, dy)) > thr2;
+                ml[u][0] = nl[0]; ml[u][1] = nl[1]; ml[u][2] = nl[2]; ml[u][3] = nl[3];
+            }
+        }
+    }
+    __syncthreads();  // every chain has read its lines
+    int out_n = 0;
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        int t;
+        const int at = out_n + psl_block_excl_scan256(keep[u] ? 1 : 0, s_scan, &t);
+        if (keep[u]) { float* d = LD.lines + 4 * at; d[0] = ml[u][0]; d[1] = ml[u][1]; d[2] = ml[u][2]; d[3] = ml[u][3]; }
+        out_n += t;
+    }
+    __syncthreads();
+    return out_n;
+}
+
+template <int LN>
+__device__ int psl_merge_pass_hbm(const MergeScratch& M, MergeLds<LN>& LD, const float* src, float* dst, int n, float angle_threshold,
+                                  float distance_threshold, float endpoint_threshold, float length_thr, int* s_i, const double* sctab) {
+    const int tid = threadIdx.x, BS = 256;
+    if (n <= 0) return 0;
+    const int words = (n + 31) >> 5;
+    const int ROW = PSL_MERGE_NMAX / 32;
+    for (int i = tid; i < n; i += BS) {
+        const float dx = PSL_FSUB(src[4 * i + 2], src[4 * i]), dy = PSL_FSUB(src[4 * i + 3], src[4 * i + 1]);
+        M.angles[i] = psl_atanf(PSL_FDIV(dy, dx));  // Eigen ArrayXf::atan()
+        M.length[i] = sqrtf(PSL_FADD(PSL_FMUL(dx, dx), PSL_FMUL(dy, dy)));
+        M.code[i] = -1;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += BS) {  // std::sort of indices by angle (stable convention H16): rank by counting
+        const float a = M.angles[i];
+        int r = 0;
+        for (int j = 0; j < n; ++j) { const float b = M.angles[j]; r += (b < a) || (b == a && j < i); }
+        M.pos[i] = r;
+        M.order[r] = i;
+    }
+    __syncthreads();
+    const float ep_thr = PSL_FMUL(endpoint_threshold, endpoint_threshold);
+    for (int t = tid; t < n * words; t += BS) {  // adjacency over sorted positions, one 32-pair word per step
+        const int pi = t / words, wj = t - pi * words;
+        uint32_t bw = 0;
+        const int idxi = M.order[pi];
+        for (int b = 0; b < 32; ++b) {
+            const int pj = wj * 32 + b;
+            if (pj >= n || pj == pi) continue;
+            const int idxj = M.order[pj];
+            const bool m = pi < pj ? psl_merge_pair(src, M.angles, idxi, idxj, angle_threshold, distance_threshold, ep_thr)
+                                   : psl_merge_pair(src, M.angles, idxj, idxi, angle_threshold, distance_threshold, ep_thr);
+            bw |= (uint32_t)m << b;
+        }
+        M.adj[(size_t)pi * ROW + wj] = bw;
+    }
+    __syncthreads();
+    int* foff = M.coff + PSL_MERGE_NMAX + 1;
+    if (tid == 0) {
+        // clustering (:159-188): per cluster a breadth-first frontier; members of `to_check` are coded and appended in list
+        // order, their still-uncoded neighbours form the next frontier (a std::set: ascending index)
         int ncl = 0, total = 0;
         int* code = M.code;
         const int* order = M.order;
         const int* posv = M.pos;
+        const float* length = M.length;
         uint32_t* bits = M.bits;
         int* to_check = M.work;
         int* next = M.work + PSL_MERGE_NMAX;
@@ -372,21 +561,11 @@ __device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const flo
             }
             M.coff[++ncl] = total;
         }
-        s_cl[0] = ncl; s_cl[1] = total; s_cl[2] = overflow ? 1 : 0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int ncl = s_cl[0], total = s_cl[1];
-        bool overflow = s_cl[2] != 0;
-        const int* order = small ? LD.order : M.order;
-        const int* posv = small ? LD.pos : M.pos;
-        const float* length = small ? LD.length : M.length;
         // sub-clusters (:190-228), appended behind the raw clusters
         const int raw_ncl = ncl;
-        int* loc = small ? LD.loc : M.work + 2 * PSL_MERGE_NMAX;
-        uint8_t* clustered = small ? LD.clustered : reinterpret_cast<uint8_t*>(M.work + 3 * PSL_MERGE_NMAX);
+        int* loc = M.work + 2 * PSL_MERGE_NMAX;
+        uint8_t* clustered = reinterpret_cast<uint8_t*>(M.work + 3 * PSL_MERGE_NMAX);
         int nfinal = 0;
-        int* foff = M.coff + PSL_MERGE_NMAX + 1;
         foff[0] = total;
         for (int c = 0; c < raw_ncl && !overflow; ++c) {
             const int cs = M.coff[c + 1] - M.coff[c];
@@ -426,7 +605,6 @@ __device__ int psl_merge_pass(const MergeScratch& M, MergeLds<LN>& LD, const flo
     }
     __syncthreads();
     const int nfinal = s_i[0];
-    const int* foff = M.coff + PSL_MERGE_NMAX + 1;
     for (int c = tid; c < nfinal; c += BS) {  // merge chains (:230-262); the first line is merged with itself first
         const int* cl = M.clist + foff[c];
         const int cs = foff[c + 1] - foff[c];
@@ -486,7 +664,7 @@ __device__ int psl_line_iterator_count(int w, int h, float fx1, float fy1, float
 // status bits: 1 = more than NMAX raw segments (truncated), 2 = cluster list overflow, 4 = more
 // than maxkl merged lines (truncated).
 template <int LN>
-__global__ __launch_bounds__(256, LN <= PSL_MERGE_LDSN_SMALL ? 8 : 5) void k_line_merge(LineParams P, MergeScratch M0, const float* __restrict__ seg, const int* __restrict__ nseg,
+__global__ __launch_bounds__(256, LN <= PSL_MERGE_LDSN_SMALL ? 4 : 2) void k_line_merge(LineParams P, MergeScratch M0, const float* __restrict__ seg, const int* __restrict__ nseg,
                                                      PslKeyLine* __restrict__ kls, double* __restrict__ lineEq, int* __restrict__ nkl,
                                                      int* __restrict__ status) {
     __shared__ int s_i[4];
@@ -508,15 +686,30 @@ __global__ __launch_bounds__(256, LN <= PSL_MERGE_LDSN_SMALL ? 8 : 5) void k_lin
     int st = 0;
     if (n > PSL_MERGE_NMAX) { n = PSL_MERGE_NMAX; st |= 1; }
     const float* src = seg + f * P.maxseg * 4;
-    for (int i = tid; i < n * 4; i += 256) M.lines0[i] = src[i];
+    // the lines of a frame stay in LDS from here to the KeyLines; only more than LN of them go through M.lines0 / M.lines1
+    bool lds = n <= LN;
+    if (lds) { for (int i = tid; i < n * 4; i += 256) LD.lines[i] = src[i]; }
+    else { for (int i = tid; i < n * 4; i += 256) M.lines0[i] = src[i]; }
     __syncthreads();
-    n = psl_merge_pass(M, LD, M.lines0, M.lines1, n, 0.05f, 5.f, 15.f, 30.f, s_i, P.sctab);
-    n = psl_merge_pass(M, LD, M.lines1, M.lines0, n, 0.03f, 3.f, 30.f, 50.f, s_i, P.sctab);
+    if (lds) {
+        n = psl_merge_pass_lds(M, LD, n, 0.05f, 5.f, 15.f, 30.f, s_i, P.sctab);
+        n = psl_merge_pass_lds(M, LD, n, 0.03f, 3.f, 30.f, 50.f, s_i, P.sctab);
+    } else if constexpr (LN > PSL_MERGE_LDSN_SMALL) {
+        n = psl_merge_pass_hbm(M, LD, M.lines0, M.lines1, n, 0.05f, 5.f, 15.f, 30.f, s_i, P.sctab);
+        lds = n <= LN;
+        if (lds) {
+            for (int i = tid; i < n * 4; i += 256) LD.lines[i] = M.lines1[i];
+            __syncthreads();
+            n = psl_merge_pass_lds(M, LD, n, 0.03f, 3.f, 30.f, 50.f, s_i, P.sctab);
+        } else {
+            n = psl_merge_pass_hbm(M, LD, M.lines1, M.lines0, n, 0.03f, 3.f, 30.f, 50.f, s_i, P.sctab);
+        }
+    }
     st |= s_i[1] << 1;
     // convertVec4fToKeyLine (:411-447)
-    const float* L = M.lines0;
+    const float* L = lds ? LD.lines : M.lines0;
+    float* resp = lds ? LD.angles : M.angles;
     PslKeyLine* out = kls + f * P.maxkl;
-    float* resp = M.angles;
     for (int i = tid; i < n; i += 256) {
         const float* l = L + 4 * i;
         PslKeyLine kl;
