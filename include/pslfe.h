@@ -217,7 +217,7 @@ int pslfe_line_debug_gradient(pslfe_line* line, int frame, int* W, int* H, doubl
 #define PSLFE_MATH_COUNT 22
 int pslfe_debug_math(pslfe_ctx* ctx, int fn, size_t n, const void* a, const void* b, void* out0, void* out1);
 /* Tap for parity tests: nfa(n, k, p) of LSD_REFINE_ADV exactly as an extraction evaluates it - the product's k_lsd_nfa_setup<phase>
- * and k_lsd_nfa_series<phase>, with run_lsd's grids, on caller-supplied trials instead of rectangles counted in an image.
+ * and k_lsd_nfa_series<phase>, with run_detect's grids, on caller-supplied trials instead of rectangles counted in an image.
  *   w, h       frame size: the geometry is prepared as an extraction of w x h frames prepares it (logNT, the tables);
  *   phase      PSLFE_NFA_FIRST (the first test: one trial per rectangle) or -1 .. 3 (five trials per rectangle; in phases -1 and 3
  *              trial t is evaluated at p / 2^(t+1));

@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256, PSL_GRAD_WAVES) void k_lsd_grad(LineParams P, 
 // counted by k_lsd_grad (one atomic per tile); the order is a counting sort over 1024 weight classes by one workgroup (the order
 // inside a class is whatever the atomics give: it only affects the schedule, never a result).
 #ifndef PSL_LSD_SUBBATCH
-#define PSL_LSD_SUBBATCH 2048   // frames whose f64 working image is resident between k_lsd_scale_tiled and k_lsd_grad (pslfe_line.hip: run_lsd)
+#define PSL_LSD_SUBBATCH 2048   // frames whose f64 working image is resident between k_lsd_scale_tiled and k_lsd_grad (pslfe_line.hip: run_grad)
 #endif
 #define PSL_ORDER_CLASSES 1024
 __global__ __launch_bounds__(1024) void k_frame_order(const int* __restrict__ weight, int nframes, int wmax, int* __restrict__ order) {

@@ -23,6 +23,10 @@
 #ifndef PSL_GROW_HELPER_FRAMES
 #define PSL_GROW_HELPER_FRAMES 64   // launches of at most this many frames run k_lsd_grow4 with helper waves (measured: tools/helper_sweep.sh)
 #endif
+// parts a launch of at least 2 * (PSL_GROW_HELPER_FRAMES + 1) frames is extracted in behind the gradient, alternately on the context's two streams
+// (run_extract).  12288 dense frames, ms per step: 1: 373.5, 2: 349.9, 3: 365.7, 4: 382.9; 2 with the auxiliary stream at the highest priority
+// 349.4, at the lowest 353.4: no priority stream (profiles/line_split_ab.log)
+constexpr unsigned PSL_LINE_PIECES = 2;
 
 // hipFuncSetAttribute acts on the function on the current device, not on an extractor object: the dynamic LDS k_lsd_grow4<3, 1> has
 // been allowed is kept per device and only ever raised (an extractor of a smaller geometry must not lower what another one relies on)
@@ -181,7 +185,7 @@ struct pslfe_line {
             lg[(size_t)lgn + j] = psl_log(pj); lg[(size_t)lgn + PSL_NFA_NP + j] = psl_log(1.0 - pj); lg[(size_t)lgn + 2 * PSL_NFA_NP + j] = psl_log10(pj);
         }
         mem.alloc(d_in, in_fstride * F, "d_in");
-        mem.alloc(d_scaled, npx * std::min<size_t>(F, PSL_LSD_SUBBATCH), "d_scaled");   // one sub-batch of the f64 working image (run_lsd)
+        mem.alloc(d_scaled, npx * std::min<size_t>(F, PSL_LSD_SUBBATCH), "d_scaled");   // one sub-batch of the f64 working image (run_grad)
         mem.alloc(d_angdeg, npx * F, "d_angdeg");
         mem.alloc(d_modgrad, npx * F, "d_modgrad");
         mem.alloc(d_trig, npx * F, "d_trig");
@@ -240,57 +244,113 @@ struct pslfe_line {
         return PSLFE_OK;
     }
 
-    int run_lsd(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
+    // Frames [f0, f0 + n) of a launch of F frames, for the launches of stream `st`: every per-frame array advanced to frame f0.  The kernels
+    // count frames from their own blockIdx, so a part needs nothing but these pointers and n; the two arrays laid out [k][F] keep the
+    // launch's stride F (ul(), uc()).  order: the part's own segment of d_order, frame indices relative to f0 (k_frame_order on the
+    // part's weights).  Parts of one launch share no buffer.
+    struct Part {
+        unsigned f0, n, F;
+        hipStream_t st;
+        float* angdeg; double* modgrad; float2* trig; float2* seedt; uint8_t* used; uint32_t* reg;
+        double* rects; int* nrect; int* weight; int* order;
+        int2* counts; int2* count0; uint16_t* ulist; int* ucount; double* vals; double2* sstate; LsdnSeries* slist; LsdnSeries* stmp; int* lcount;
+        uint8_t* keep; float* segtmp; float* seg; int* nseg;
+        MergeScratch M;
+        PslKeyLine* kls; uint8_t* ldesc; float* fdesc; double* lineEq; int* nkl; int* status; short2* dxy;
+        size_t maxseg;
+        uint16_t* ul(int k) const { return k >= 0 ? ulist + (size_t)(k & 1) * maxseg * F : nullptr; }
+        int* uc(int k) const { return k >= 0 && k < 5 ? ucount + (size_t)k * F : nullptr; }
+    };
+
+    Part part(unsigned f0, unsigned n, unsigned F, hipStream_t st) const {
+        const size_t npx = (size_t)P.W * P.H, S = (size_t)P.maxseg, K = (size_t)P.maxkl, N = PSL_MERGE_NMAX;
+        auto at = [f0](auto* base, size_t per_frame) { return base + (size_t)f0 * per_frame; };
+        Part p;
+        p.f0 = f0; p.n = n; p.F = F; p.st = st; p.maxseg = S;
+        p.angdeg = at(d_angdeg, npx); p.modgrad = at(d_modgrad, npx); p.trig = at(d_trig, npx); p.seedt = at(d_seedt, npx);
+        p.used = at(d_used, npx); p.reg = at(d_reg, npx);
+        p.rects = at(d_rects, S * PSL_LSD_RECT_F64); p.nrect = at(d_nrect, 1); p.weight = at(d_weight, 1); p.order = at(d_order, 1);
+        p.counts = at(d_counts, S * 5); p.count0 = at(d_count0, S); p.ulist = at(d_ulist, S); p.ucount = at(d_ucount, 1);
+        p.vals = at(d_vals, S * 5); p.sstate = at(d_sstate, S * 5); p.slist = at(d_slist, S * 5); p.stmp = at(d_stmp, S * 5);
+        p.lcount = at(d_lcount, PSL_NFA_NCLS + 1);
+        p.keep = at(d_keep, S); p.segtmp = at(d_segtmp, S * 4); p.seg = at(d_seg, S * 4); p.nseg = at(d_nseg, 1);
+        p.M.lines0 = at(M.lines0, N * 4); p.M.lines1 = at(M.lines1, N * 4); p.M.merged = at(M.merged, N * 4);
+        p.M.angles = at(M.angles, N); p.M.length = at(M.length, N); p.M.order = at(M.order, N); p.M.pos = at(M.pos, N);
+        p.M.adj = at(M.adj, N * (N / 32)); p.M.code = at(M.code, N); p.M.clist = at(M.clist, PSL_MERGE_CLMAX);
+        p.M.coff = at(M.coff, 2 * N + 2); p.M.work = at(M.work, 4 * N); p.M.bits = at(M.bits, N / 32); p.M.stage = at(M.stage, N);
+        p.kls = at(d_kls, K); p.ldesc = at(d_ldesc, K * 32); p.fdesc = at(d_fdesc, K * 72); p.lineEq = at(d_lineEq, K * 3);
+        p.nkl = at(d_nkl, 1); p.status = at(d_status, 1); p.dxy = at(d_dxy, (size_t)P.w * P.h);
+        return p;
+    }
+    Part whole(int nframes) const { return part(0, (unsigned)nframes, (unsigned)nframes, ctx->stream); }
+
+    // A launch of F frames runs as (profiles/r03z_switch_matrix.log, profiles/line_split_ab.log):
+    //   F <= PSL_GROW_HELPER_FRAMES (64)   k_lsd_grow4<3, 1> (<3, 0> for frames whose `used` bits do not fit in LDS): helper waves, P.singles
+    //   F >= 64                            the many-frames NFA grids
+    //   F > 64                             k_lsd_grow4<0, 0> on the frames in k_frame_order's order
+    //   F > PSL_LSD_SUBBATCH (2048)        scale / gradient in sub-batches
+    //   F >= 2 * (64 + 1) = 130            pslfe_line_extract_batch_device: everything behind the gradient in PSL_LINE_PIECES parts on two streams
+    //                                      (run_extract), each part a many-frames launch of its own
+    // LSD steps 1 + 2 (scaled image, gradient) of every frame, and the launch's memsets; on the context's stream
+    int run_grad(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
         int rc = prepare(w, h);
         if (rc) return rc;
         PSL_HIP(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         const unsigned F = (unsigned)nframes;
-        {
-            // LSD steps 1 + 2 in sub-batches of PSL_LSD_SUBBATCH frames: the f64 working image (1.57 MB per frame) only lives between the two kernels, so
-            // d_scaled holds one sub-batch (3.2 GB instead of 19 GB at 12288 frames); 2048 frames x 192 tiles still fill the chip many times over
-            PSL_HIP(hipMemsetAsync(d_used, 0, (size_t)P.W * P.H * F, st));  // the `used` map: 1 byte per scaled pixel
-            P.singles = F <= PSL_GROW_HELPER_FRAMES;
-            P.full_grad = nframes == 1;  // pslfe_line_debug_gradient reads the whole magnitude image of a single-frame call
-            const bool ordered = F > PSL_GROW_HELPER_FRAMES;   // many-frames launches: k_lsd_grow4 takes the heaviest frames first
-            if (ordered) PSL_HIP(hipMemsetAsync(d_weight, 0, (size_t)F * sizeof(int), st));
-            const unsigned tx = (P.W + 63) / 64, ty = (P.H + 15) / 16, gy = (P.H + PSL_GRAD_TH - 1) / PSL_GRAD_TH;
-            const size_t npx = (size_t)P.W * P.H;
-            for (unsigned f0 = 0; f0 < F; f0 += PSL_LSD_SUBBATCH) {
-                const unsigned n = std::min<unsigned>(PSL_LSD_SUBBATCH, F - f0);
-                const int xcd = n >= 8 ? 1 : 0;
-                const size_t po = (size_t)f0 * npx;
-                {
-                    PSL_STAGE_BEGIN(ctx, "line.lsd_scale");
-                    k_lsd_scale_tiled<<<xcd ? dim3(8, tx * ty, (n + 7) / 8) : dim3(tx, ty, n), 256, 0, st>>>(P, d_gray + (size_t)f0 * frame_stride, stride, frame_stride,
-                                                                                                             d_scaled, (int)n, xcd);
-                    PSL_STAGE_END(ctx, "line.lsd_scale");
-                }
-                {
-                    PSL_STAGE_BEGIN(ctx, "line.lsd_grad");
-                    k_lsd_grad<<<xcd ? dim3(8, tx * gy, (n + 7) / 8) : dim3(tx, gy, n), 256, 0, st>>>(P, d_scaled, d_angdeg + po, d_modgrad + po, d_trig + po, d_seedt + po,
-                                                                                                      d_used + po, ordered ? d_weight + f0 : nullptr, (int)n, xcd);
-                    PSL_STAGE_END(ctx, "line.lsd_grad");
-                }
-            }
-            if (ordered) k_frame_order<<<1, 1024, 0, st>>>(d_weight, (int)F, P.W * P.H, d_order);
-        }
+        // in sub-batches of PSL_LSD_SUBBATCH frames: the f64 working image (1.57 MB per frame) only lives between the two kernels, so
+        // d_scaled holds one sub-batch (3.2 GB instead of 19 GB at 12288 frames); 2048 frames x 192 tiles still fill the chip many times over
+        PSL_HIP(hipMemsetAsync(d_used, 0, (size_t)P.W * P.H * F, st));  // the `used` map: 1 byte per scaled pixel
+        P.singles = F <= PSL_GROW_HELPER_FRAMES;
+        P.full_grad = nframes == 1;  // pslfe_line_debug_gradient reads the whole magnitude image of a single-frame call
         P.refine = refine;
+        const bool ordered = F > PSL_GROW_HELPER_FRAMES;   // many-frames launches: k_lsd_grow4 takes the heaviest frames first
+        if (ordered) PSL_HIP(hipMemsetAsync(d_weight, 0, (size_t)F * sizeof(int), st));
+        if (refine >= 2) PSL_HIP(hipMemsetAsync(d_ucount, 0, (size_t)5 * F * sizeof(int), st));   // the undecided lists of the NFA phases (run_detect)
+        const unsigned tx = (P.W + 63) / 64, ty = (P.H + 15) / 16, gy = (P.H + PSL_GRAD_TH - 1) / PSL_GRAD_TH;
+        const size_t npx = (size_t)P.W * P.H;
+        for (unsigned f0 = 0; f0 < F; f0 += PSL_LSD_SUBBATCH) {
+            const unsigned n = std::min<unsigned>(PSL_LSD_SUBBATCH, F - f0);
+            const int xcd = n >= 8 ? 1 : 0;
+            const size_t po = (size_t)f0 * npx;
+            {
+                PSL_STAGE_BEGIN(ctx, "line.lsd_scale");
+                k_lsd_scale_tiled<<<xcd ? dim3(8, tx * ty, (n + 7) / 8) : dim3(tx, ty, n), 256, 0, st>>>(P, d_gray + (size_t)f0 * frame_stride, stride, frame_stride,
+                                                                                                         d_scaled, (int)n, xcd);
+                PSL_STAGE_END(ctx, "line.lsd_scale");
+            }
+            {
+                PSL_STAGE_BEGIN(ctx, "line.lsd_grad");
+                k_lsd_grad<<<xcd ? dim3(8, tx * gy, (n + 7) / 8) : dim3(tx, gy, n), 256, 0, st>>>(P, d_scaled, d_angdeg + po, d_modgrad + po, d_trig + po, d_seedt + po,
+                                                                                                  d_used + po, ordered ? d_weight + f0 : nullptr, (int)n, xcd);
+                PSL_STAGE_END(ctx, "line.lsd_grad");
+            }
+        }
+        PSL_HIP(hipGetLastError());
+        return PSLFE_OK;
+    }
+
+    // LSD step 3 on the frames of a part: region growing, and with LSD_REFINE_ADV the NFA validation of its rectangles -> p.seg / p.nseg
+    int run_detect(const Part& p) {
+        hipStream_t st = p.st;
+        const unsigned n = p.n;
+        int* const ngrow = refine >= 2 ? p.nrect : p.nseg;
+        const bool ordered = n > PSL_GROW_HELPER_FRAMES;   // many-frames launches: the heaviest frames of the part first
+        if (ordered) k_frame_order<<<1, 1024, 0, st>>>(p.weight, (int)n, P.W * P.H, p.order);
         {
-            PSL_STAGE_BEGIN(ctx, "line.lsd_grow");
-            // LSD_REFINE_ADV: the kernel leaves rectangles (d_rects / d_nrect) for the NFA validation below
-            if (F <= PSL_GROW_HELPER_FRAMES) {  // few workgroups per XCD: three more waves each keep that XCD's L2 warm in front of the chain (line_kernels.h)
+            PSL_STAGE_BEGIN_ON(ctx, "line.lsd_grow", st);
+            // LSD_REFINE_ADV: the kernel leaves rectangles (rects / nrect) for the NFA validation below
+            if (!ordered) {  // few workgroups per XCD: three more waves each keep that XCD's L2 warm in front of the chain (line_kernels.h)
                 const size_t ubytes = (((size_t)P.W * P.H + 31) >> 5) * 4;   // the `used` bits of the frame in LDS (24 KB at 640x480, 96 KB at 1280x960)
                 if (ubytes <= PSL_GROW_LDS_USED_MAX) {
                     PSL_HIP(psl_grow_lds_allow(ctx->device, ubytes));   // more than the default 64 KB of dynamic LDS needs the attribute
-                    k_lsd_grow4<3, 1><<<F, 256, ubytes, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F, nullptr);
+                    k_lsd_grow4<3, 1><<<n, 256, ubytes, st>>>(P, p.angdeg, p.modgrad, p.trig, p.used, p.seedt, p.reg, p.seg, ngrow, p.rects, (int)n, nullptr);
                 } else {
-                    k_lsd_grow4<3, 0><<<F, 256, 0, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F, nullptr);
+                    k_lsd_grow4<3, 0><<<n, 256, 0, st>>>(P, p.angdeg, p.modgrad, p.trig, p.used, p.seedt, p.reg, p.seg, ngrow, p.rects, (int)n, nullptr);
                 }
             } else
-                k_lsd_grow4<0, 0><<<F, 64, 0, st>>>(P, d_angdeg, d_modgrad, d_trig, d_used, d_seedt, d_reg, d_seg, refine >= 2 ? d_nrect : d_nseg, d_rects, (int)F,
-                                                 d_order);
-            PSL_STAGE_END(ctx, "line.lsd_grow");
+                k_lsd_grow4<0, 0><<<n, 64, 0, st>>>(P, p.angdeg, p.modgrad, p.trig, p.used, p.seedt, p.reg, p.seg, ngrow, p.rects, (int)n, p.order);
+            PSL_STAGE_END_ON(ctx, "line.lsd_grow", st);
             PSL_HIP(hipGetLastError());   // a refused grow launch (e.g. its dynamic LDS) must not hide behind the NFA launches
         }
         if (refine >= 2) {
@@ -300,24 +360,21 @@ struct pslfe_line {
             // with profiling on, every stage costs two event records.)
             // List k holds the rectangles still undecided after the first test (k = 0) and after phases -1 .. 2 (k = 1 .. 4): phase PH
             // walks list PH + 1 and fills list PH + 2.  Phase -1 has no pixel scan of its own: the first test's pass counts its trials.
-            const dim3 gc(F >= 64 ? PSL_NFA_COUNT_WGS : 128, F), gs(F >= 64 ? 1 : 4, F);
-            PSL_HIP(hipMemsetAsync(d_ucount, 0, (size_t)5 * F * sizeof(int), st));
-            auto ul = [&](int k) { return k >= 0 ? d_ulist + (size_t)(k & 1) * P.maxseg * F : nullptr; };
-            auto uc = [&](int k) { return k >= 0 && k < 5 ? d_ucount + (size_t)k * F : nullptr; };
+            const dim3 gc(n >= 64 ? PSL_NFA_COUNT_WGS : 128, n), gs(n >= 64 ? 1 : 4, n);
 #define PSL_NFA_COUNT(PH)                                                                                                \
     {                                                                                                                    \
-        PSL_STAGE_BEGIN(ctx, "line.nfa_count");                                                                          \
-        k_lsd_nfa_count<PH><<<gc, 256, 0, st>>>(P, d_angdeg, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_counts, d_count0); \
-        PSL_STAGE_END(ctx, "line.nfa_count");                                                                            \
+        PSL_STAGE_BEGIN_ON(ctx, "line.nfa_count", st);                                                                   \
+        k_lsd_nfa_count<PH><<<gc, 256, 0, st>>>(P, p.angdeg, p.rects, p.nrect, p.ul(PH + 1), p.uc(PH + 1), p.counts, p.count0); \
+        PSL_STAGE_END_ON(ctx, "line.nfa_count", st);                                                                     \
     }
 #define PSL_NFA_EVAL(PH)                                                                                                 \
     {                                                                                                                    \
-        PSL_STAGE_BEGIN(ctx, "line.nfa_eval");                                                                           \
-        k_lsd_nfa_setup<PH><<<F, 256, 0, st>>>(P, NT, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_counts, d_count0, d_vals, d_sstate, d_stmp, d_slist, d_lcount); \
-        k_lsd_nfa_series<PH><<<dim3(PSL_NFA_NCLS, (F + PSL_NFA_FG - 1) / PSL_NFA_FG), 256, 0, st>>>(P, NT, (int)F, d_slist, d_lcount, d_sstate); \
-        k_lsd_nfa_select<PH><<<gs, 256, 0, st>>>(P, NT.log_nt, d_rects, d_nrect, ul(PH + 1), uc(PH + 1), d_keep, d_vals, d_sstate, d_segtmp, \
-                                                 PH < 3 ? ul(PH + 2) : nullptr, uc(PH + 2));                             \
-        PSL_STAGE_END(ctx, "line.nfa_eval");                                                                             \
+        PSL_STAGE_BEGIN_ON(ctx, "line.nfa_eval", st);                                                                    \
+        k_lsd_nfa_setup<PH><<<n, 256, 0, st>>>(P, NT, p.rects, p.nrect, p.ul(PH + 1), p.uc(PH + 1), p.counts, p.count0, p.vals, p.sstate, p.stmp, p.slist, p.lcount); \
+        k_lsd_nfa_series<PH><<<dim3(PSL_NFA_NCLS, (n + PSL_NFA_FG - 1) / PSL_NFA_FG), 256, 0, st>>>(P, NT, (int)n, p.slist, p.lcount, p.sstate); \
+        k_lsd_nfa_select<PH><<<gs, 256, 0, st>>>(P, NT.log_nt, p.rects, p.nrect, p.ul(PH + 1), p.uc(PH + 1), p.keep, p.vals, p.sstate, p.segtmp, \
+                                                 PH < 3 ? p.ul(PH + 2) : nullptr, p.uc(PH + 2));                         \
+        PSL_STAGE_END_ON(ctx, "line.nfa_eval", st);                                                                      \
     }
             PSL_NFA_COUNT(PSL_NFA_FIRST)
             PSL_NFA_EVAL(PSL_NFA_FIRST)
@@ -332,42 +389,91 @@ struct pslfe_line {
             PSL_NFA_EVAL(3)
 #undef PSL_NFA_COUNT
 #undef PSL_NFA_EVAL
-            k_lsd_emit<<<F, 256, 0, st>>>(P, d_nrect, d_segtmp, d_keep, d_seg, d_nseg);
+            k_lsd_emit<<<n, 256, 0, st>>>(P, p.nrect, p.segtmp, p.keep, p.seg, p.nseg);
         }
         PSL_HIP(hipGetLastError());
+        return PSLFE_OK;
+    }
+
+    // LineSegmentDetector::detect on a launch of its own -> d_seg / d_nseg
+    int run_lsd(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
+        int rc = run_grad(d_gray, nframes, w, h, stride, frame_stride);
+        if (rc) return rc;
+        if ((rc = run_detect(whole(nframes)))) return rc;
         last_nframes = nframes;
         return PSLFE_OK;
     }
 
-    // optimizeAndMergeLines_lsd + KeyLines + top-N + line equations on the segment lists in d_seg/d_nseg
-    int run_merge(int nframes) {
+    // optimizeAndMergeLines_lsd + KeyLines + top-N + line equations on the segment lists in p.seg / p.nseg
+    int run_merge(const Part& p) {
         PSL_HIP(hipSetDevice(ctx->device));
-        PSL_STAGE_BEGIN(ctx, "line.merge");
-        k_line_merge<PSL_MERGE_LDSN_SMALL><<<nframes, 256, 0, ctx->stream>>>(P, M, d_seg, d_nseg, d_kls, d_lineEq, d_nkl, d_status);
-        k_line_merge<PSL_MERGE_LDSN><<<nframes, 256, 0, ctx->stream>>>(P, M, d_seg, d_nseg, d_kls, d_lineEq, d_nkl, d_status);
-        PSL_STAGE_END(ctx, "line.merge");
+        PSL_STAGE_BEGIN_ON(ctx, "line.merge", p.st);
+        k_line_merge<PSL_MERGE_LDSN_SMALL><<<p.n, 256, 0, p.st>>>(P, p.M, p.seg, p.nseg, p.kls, p.lineEq, p.nkl, p.status);
+        k_line_merge<PSL_MERGE_LDSN><<<p.n, 256, 0, p.st>>>(P, p.M, p.seg, p.nseg, p.kls, p.lineEq, p.nkl, p.status);
+        PSL_STAGE_END_ON(ctx, "line.merge", p.st);
         PSL_HIP(hipGetLastError());
         return PSLFE_OK;
     }
 
-    // BinaryDescriptor::compute on the keylines in d_kls/d_nkl
-    int run_lbd(const uint8_t* d_gray, int nframes, int stride, size_t frame_stride, bool want_float) {
+    // BinaryDescriptor::compute on the keylines in p.kls / p.nkl; d_gray is frame 0 of the launch
+    int run_lbd(const Part& p, const uint8_t* d_gray, int stride, size_t frame_stride, bool want_float) {
         PSL_HIP(hipSetDevice(ctx->device));
-        hipStream_t st = ctx->stream;
+        hipStream_t st = p.st;
+        const int n = (int)p.n;
         {
-            PSL_STAGE_BEGIN(ctx, "line.lbd_pre");
+            PSL_STAGE_BEGIN_ON(ctx, "line.lbd_pre", st);
             const unsigned tx = (P.w + 63) / 64, ty = (P.h + 31) / 32;
-            const int xcd = nframes >= 8 ? 1 : 0;
-            k_lbd_pre<<<xcd ? dim3(8, tx * ty, (nframes + 7) / 8) : dim3(tx, ty, nframes), 256, 0, st>>>(P, d_gray, stride, frame_stride, d_dxy, nframes, xcd);
-            PSL_STAGE_END(ctx, "line.lbd_pre");
+            const int xcd = n >= 8 ? 1 : 0;
+            k_lbd_pre<<<xcd ? dim3(8, tx * ty, (n + 7) / 8) : dim3(tx, ty, n), 256, 0, st>>>(P, d_gray + (size_t)p.f0 * frame_stride, stride, frame_stride, p.dxy, n, xcd);
+            PSL_STAGE_END_ON(ctx, "line.lbd_pre", st);
         }
         {
-            PSL_STAGE_BEGIN(ctx, "line.lbd");
+            PSL_STAGE_BEGIN_ON(ctx, "line.lbd", st);
             const int per_frame = std::min(P.maxkl, std::max(P.nfeatures, 1));
-            k_lbd<<<dim3((per_frame + 3) / 4, nframes), 256, 0, st>>>(P, d_dxy, d_kls, d_nkl, d_ldesc, want_float ? d_fdesc : nullptr);
-            PSL_STAGE_END(ctx, "line.lbd");
+            k_lbd<<<dim3((per_frame + 3) / 4, n), 256, 0, st>>>(P, p.dxy, p.kls, p.nkl, p.ldesc, want_float ? p.fdesc : nullptr);
+            PSL_STAGE_END_ON(ctx, "line.lbd", st);
         }
         PSL_HIP(hipGetLastError());
+        return PSLFE_OK;
+    }
+
+    // LSD behind the gradient, merge and LBD of the frames of one part
+    int run_part(const Part& p, const uint8_t* d_gray, int stride, size_t frame_stride) {
+        int rc = run_detect(p);
+        if (rc) return rc;
+        if ((rc = run_merge(p))) return rc;
+        return run_lbd(p, d_gray, stride, frame_stride, false);
+    }
+
+    // LINEextractor::operator() on every frame of a launch.  The frames are independent, yet each kernel behind the gradient lasts as
+    // long as its slowest frame: k_lsd_grow4<0, 0> (one wave per frame, 12288 waves on 8192 slots) holds 6.77 of 8 slots per SIMD on
+    // average, and nothing else can start while its tail drains.  So a launch of at least 2 * (PSL_GROW_HELPER_FRAMES + 1) frames runs
+    // that part of the work in PSL_LINE_PIECES parts of contiguous frames, alternately on the context's stream and on its auxiliary
+    // stream: the NFA / merge / LBD kernels of one part fill the slots the growing of the next one leaves.  Every part is a many-frames
+    // launch of its own (own k_frame_order), so a frame's result does not depend on the split.  With stage profiling on, the launch
+    // stays on one stream, so that the stage timers keep their meaning.
+    int run_extract(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
+        int rc = run_grad(d_gray, nframes, w, h, stride, frame_stride);
+        if (rc) return rc;
+        const unsigned F = (unsigned)nframes;
+        if (F < 2 * (PSL_GROW_HELPER_FRAMES + 1) || ctx->profile) {
+            if ((rc = run_part(whole(nframes), d_gray, stride, frame_stride))) return rc;
+        } else {
+            const unsigned pieces = std::min<unsigned>(PSL_LINE_PIECES, F / (PSL_GROW_HELPER_FRAMES + 1));
+            PSL_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+            PSL_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+            for (unsigned i = 0; i < pieces && !rc; ++i) {
+                const unsigned f0 = (unsigned)((size_t)F * i / pieces), f1 = (unsigned)((size_t)F * (i + 1) / pieces);
+                rc = run_part(part(f0, f1 - f0, F, i & 1 ? ctx->aux_stream : ctx->stream), d_gray, stride, frame_stride);
+            }
+            // the join, also after a failed launch: the caller's stream must not run ahead of what the auxiliary stream was given
+            const hipError_t ej = hipEventRecord(ctx->ev_join, ctx->aux_stream);
+            const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) : ej;
+            if (ew != hipSuccess) (void)hipStreamSynchronize(ctx->aux_stream);
+            if (rc) return rc;
+            PSL_HIP(ew);
+        }
+        last_nframes = nframes;
         return PSLFE_OK;
     }
 
@@ -479,7 +585,7 @@ int pslfe_line_debug_gradient(pslfe_line* line, int frame, int* W, int* H, doubl
     PSL_HIP(hipStreamSynchronize(line->ctx->stream));
     *W = line->P.W; *H = line->P.H;
     const size_t npx = (size_t)line->P.W * line->P.H;
-    if (scaled) {   // the working image is kept for one sub-batch only (run_lsd)
+    if (scaled) {   // the working image is kept for one sub-batch only (run_grad)
         PSL_REQUIRE(line->last_nframes <= PSL_LSD_SUBBATCH, PSLFE_E_STATE, "pslfe_line_debug_gradient: the scaled image is kept for launches of at most %d frames", PSL_LSD_SUBBATCH);
         PSL_HIP(hipMemcpy(scaled, line->d_scaled + frame * npx, npx * sizeof(double), hipMemcpyDeviceToHost));
     }
@@ -489,7 +595,7 @@ int pslfe_line_debug_gradient(pslfe_line* line, int frame, int* W, int* H, doubl
 }
 
 
-// nfa() on caller-supplied trials: the launches PSL_NFA_EVAL(PH) of run_lsd without the selection, on state written here instead of
+// nfa() on caller-supplied trials: the launches PSL_NFA_EVAL(PH) of run_detect without the selection, on state written here instead of
 // counted in an image.  Runs no kernel of its own.
 int pslfe_line_debug_nfa(pslfe_line* line, int w, int h, int phase, int nframes, const int32_t* nrect, int rect_cap, const double* p_lognfa,
                          const int32_t* nk, double* vals, double* tail, double* log_nt) {
@@ -534,7 +640,7 @@ int pslfe_line_debug_nfa(pslfe_line* line, int w, int h, int phase, int nframes,
     PSL_HIP(hipMemcpyAsync(phase == PSL_NFA_FIRST ? line->d_count0 : line->d_counts, cnt.data(), cnt.size() * sizeof(int2), hipMemcpyHostToDevice, st));
     uint16_t* d_ul = nullptr;
     int* d_uc = nullptr;
-    if (phase != PSL_NFA_FIRST) {   // list phase + 1 of run_lsd, at the place a launch of `nframes` frames keeps it
+    if (phase != PSL_NFA_FIRST) {   // list phase + 1 of run_detect, at the place a launch of `nframes` frames keeps it
         d_ul = line->d_ulist + (size_t)((phase + 1) & 1) * N * F;
         d_uc = line->d_ucount + (size_t)(phase + 1) * F;
         PSL_HIP(hipMemcpyAsync(d_ul, ulist.data(), ulist.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
@@ -577,10 +683,7 @@ int pslfe_line_extract_batch_device(pslfe_line* line, const uint8_t* d_gray, int
     PSL_REQUIRE(line && d_gray, PSLFE_E_INVALID, "pslfe_line_extract_batch_device: NULL argument");
     PSL_REQUIRE(nframes >= 1 && nframes <= line->max_batch, PSLFE_E_INVALID, "pslfe_line_extract_batch_device: nframes %d (max_batch %d)", nframes, line->max_batch);
     PSL_REQUIRE(stride >= w && (nframes == 1 || frame_stride >= (size_t)stride * h), PSLFE_E_INVALID, "pslfe_line_extract_batch_device: strides");
-    int rc = line->run_lsd(d_gray, nframes, w, h, stride, frame_stride);
-    if (rc) return rc;
-    if ((rc = line->run_merge(nframes))) return rc;
-    return line->run_lbd(d_gray, nframes, stride, frame_stride, false);
+    return line->run_extract(d_gray, nframes, w, h, stride, frame_stride);
 }
 
 int pslfe_line_results_device(pslfe_line* line, const PslKeyLine** d_kls, const uint8_t** d_desc, const double** d_lineEq,
@@ -663,7 +766,7 @@ int pslfe_line_optimize_and_merge(pslfe_line* line, const float* segments, int n
     // the top-N cut belongs to LINEextractor::operator(); this entry point is optimizeAndMergeLines_lsd alone
     const int keep = line->P.nfeatures;
     line->P.nfeatures = line->P.maxkl;
-    rc = line->run_merge(1);
+    rc = line->run_merge(line->whole(1));
     line->P.nfeatures = keep;
     if (rc) return rc;
     line->last_nframes = 1;
@@ -684,7 +787,7 @@ int pslfe_lbd_compute(pslfe_line* line, const uint8_t* gray, int w, int h, int s
     PSL_HIP(hipStreamSynchronize(st));
     const int keep = line->P.nfeatures;
     line->P.nfeatures = std::max(keep, nkl);
-    rc = line->run_lbd(line->d_in, 1, line->in_pitch, line->in_fstride, fdesc != nullptr);
+    rc = line->run_lbd(line->whole(1), line->d_in, line->in_pitch, line->in_fstride, fdesc != nullptr);
     line->P.nfeatures = keep;
     if (rc) return rc;
     PSL_HIP(hipMemcpyAsync(desc, line->d_ldesc, (size_t)nkl * 32, hipMemcpyDeviceToHost, st));
