@@ -415,7 +415,8 @@ int pslfe_orb_search_by_projection_map(pslfe_frame* cur, int slot, const PslProj
  *    (relocalisation) after the host has projected the keyframe's map points (skipping bad ones and those in
  *    sAlreadyFound): window search as above, but every occupied keypoint is skipped (taken[c] != 0 <=>
  *    CurrentFrame.mvpMapPoints[c] != NULL), every match occupies its keypoint, there is no stereo gate and the
- *    distance gate is ORBdist.  queries[i].angle = pKF->mvKeysUn[i].angle; `blocks` is ignored (always 1). */
+ *    distance gate is ORBdist.  queries[i].angle = pKF->mvKeysUn[i].angle; `blocks` is ignored (always 1).  With ORBdist = 256 a
+ *    query whose candidates are all at distance 256 has no match (the reference then writes mvpMapPoints[-1], :1555-1557). */
 int pslfe_orb_search_by_projection_kf(pslfe_frame* cur, int slot, const PslProjQuery* queries, const uint8_t* qdesc, int nq,
                                       const uint8_t* taken, int orb_dist, int check_orientation, int32_t* match,
                                       int32_t* assigned, int* nmatches);

@@ -319,7 +319,8 @@ int pso_search_by_projection_kf(const PsoKeyPoint* kps, const uint8_t* desc, int
             const int dist = descriptor_distance(qdesc + (size_t)i * 32, desc + (size_t)i2 * 32);
             if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
         }
-        if (bestDist <= orbDist) {
+        // ORBdist = 256 and no candidate below 256: the reference writes mvpMapPoints[-1] (:1555-1557); defined as no match
+        if (bestDist <= orbDist && bestIdx2 >= 0) {
             owner[bestIdx2] = i;
             occupied[bestIdx2] = 1;
             match[i] = bestIdx2;

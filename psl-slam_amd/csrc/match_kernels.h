@@ -239,7 +239,7 @@ struct FrameCands {
 };
 
 // Key (distance << 16 | CSR position) of candidate number j, PSL_KEY_INF if j >= T or a gate rejects it: level band,
-// window, stereo (:1405-1411), taken initially (:1401-1403), taken by an earlier query of this call (blocker != NULL).
+// window, stereo (:1405-1411), taken initially (:1401-1403), taken by an earlier query of this call (blocker != NULL), distance 256.
 // Called by all 64 lanes (shuffles inside).
 template <typename Cands>
 __device__ __forceinline__ uint32_t psl_window_key(const Cands& C, const PslProjQuery& q, const uint32_t (&qd)[8], const uint8_t* taken,
@@ -262,7 +262,9 @@ __device__ __forceinline__ uint32_t psl_window_key(const Cands& C, const PslProj
         if (blocker) ok = ok && !(blocker[i2] < qi);
         if (!no_stereo) ok = ok && !(ur > 0 && __builtin_fabsf(PSL_FSUB(q.ur, ur)) > r);
         const int dist = psl_hamming256(qd, d0, d1);
-        if (ok) key = ((uint32_t)dist << 16) | (uint32_t)p;
+        // dist < 256: every search starts from bestDist = bestDist2 = 256 and compares with a strict < (src/ORBmatcher.cc:76-78, :102,
+        // :110, :1397, :1419, :1535, :1548), so the complement of the query is never the best nor the second best
+        if (ok && dist < 256) key = ((uint32_t)dist << 16) | (uint32_t)p;
     }
     return key;
 }
