@@ -1287,6 +1287,61 @@ int pslfe_sim3_pairs_from_matches_device(pslfe_frame* f1, int slot1, pslfe_frame
                                          const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w, const PslPose* d_T2w,
                                          const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs, int32_t* d_pair_kp,
                                          int32_t* d_npairs, int pstride);
+/* The same set-up with one more output: d_sigma2 [ncand][pstride][2] (may be NULL) gets pKF1->mvLevelSigma2[kp1.octave] and
+ * pKF2->mvLevelSigma2[kp2.octave] of each row (src/Sim3Solver.cc:84-85), read from the host table level_sigma2 of nlevels entries
+ * (may be NULL when d_sigma2 is): what pslfe_sim3_solve_device needs next to the rows.  Everything else is
+ * pslfe_sim3_pairs_from_matches_device, byte for byte. */
+int pslfe_sim3_pairs_sigma2_from_matches_device(pslfe_frame* f1, int slot1, pslfe_frame* f2, const int32_t* d_slots2, int ncand,
+                                                const int32_t* d_i2, const PslMapPointGeom* d_mp1, const uint8_t* d_skip1, int n1,
+                                                const PslMapPointGeom* d_mp2, const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w,
+                                                const PslPose* d_T2w, const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs,
+                                                int32_t* d_pair_kp, int32_t* d_npairs, int pstride, const float* level_sigma2,
+                                                float* d_sigma2);
+
+/* ---- The Sim3 RANSAC of loop candidates: Sim3Solver (src/Sim3Solver.cc) ---------------------------------------------------------
+ * Step 2 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:284-345), between the set-up above and pslfe_sim3_optimize_device: for each
+ * candidate up to max_its hypotheses from three drawn pairs (Horn's closed form), each tested on every pair by two projections.
+ * The solver consumes the PslSim3Pair rows as they are (P1c, P2c; the constructor's gates are those of the set-up) plus
+ * mvLevelSigma2 of the two octaves per row.  Parity: OpenCV cannot be built offline, so this stage is "HIP == restatement", parity
+ * with OpenCV unpinned (DESIGN.md §3 lists the conventions: reduce, the Mat products, cv::eigen's Jacobi, norm, Rodrigues, the
+ * MatExpr scales, atan2 as psl_atan2).  rand() is glibc's generator; candidate c is seeded as srand(seed0 + c) at its first
+ * iteration and every iteration takes three draws (the reference shares one unseeded process-wide stream; convention H7). */
+typedef struct PslSim3SolverResult {   /* per candidate */
+    int32_t status;       /* 1 = a Sim3 was returned, 0 = the budget of this call is used up, 2 = bNoMore; PSLFE_E_CAPACITY /
+                             PSLFE_E_INVALID for a count above pstride / a negative count or state */
+    int32_t iterations;   /* mnIterations after the call */
+    int32_t ninliers;     /* nInliers of the returned hypothesis, else 0 */
+    int32_t best_inliers; /* mnBestInliers after the call */
+    PslSim3 S12;          /* mBestRotation / mBestTranslation / mBestScale (what LoopClosing.cc:320-325 reads): the returned
+                             hypothesis with status 1, zeros otherwise */
+} PslSim3SolverResult;
+#ifdef __cplusplus
+static_assert(sizeof(PslSim3SolverResult) == 68, "Sim3 solver POD");
+#else
+_Static_assert(sizeof(PslSim3SolverResult) == 68, "Sim3 solver POD");
+#endif
+/* == Sim3Solver::iterate(n_iterations, ...) for ncand independent candidates in one launch, after SetRansacParameters(prob,
+ *    min_inliers, max_its) (LoopClosing: 0.99, 20, 300).  Candidate c: d_npairs[c] rows at d_pairs + c*pstride and their sigma2 at
+ *    d_sigma2 + 2*c*pstride.  n_iterations is iterate's argument (5 in ComputeSim3; max_its or more gives find()).  d_start_it[c] /
+ *    d_best_in[c] (either may be NULL: 0) are mnIterations and mnBestInliers a former call left (PslSim3SolverResult.iterations /
+ *    .best_inliers): the call reseeds seed0 + c and skips 3 * start_it draws, so rounds of calls continue one solver exactly.
+ *    Outputs: d_res[c]; d_inliers [ncand][pstride] bytes indexed by pair row (the caller scatters them through d_pair_kp to
+ *    vbInliers[mvnIndices1[i]]): the flags of the returned hypothesis with status 1, zeros with 0 and 2, for the rows of the candidate
+ *    (bytes beyond the count are not touched).  d_npairs[c] > pstride: status = PSLFE_E_CAPACITY; d_npairs[c] < 0, d_start_it[c] < 0
+ *    or d_best_in[c] < 0: PSLFE_E_INVALID; nothing is clamped, nothing is solved, no byte of d_inliers is written, the other fields
+ *    are 0.  min_inliers < 3, max_its < 1,
+ *    n_iterations < 0, ncand < 0, pstride < 0, a NULL array with a non-zero count, prob outside (0, 1): PSLFE_E_INVALID; ncand == 0:
+ *    PSLFE_OK, nothing is done.  The iteration budget of every pair count is tabulated on the host (the host's log and pow) and
+ *    uploaded; no logarithm runs on the device.  Asynchronous on the context's stream; per-call buffers come from the scratch arena. */
+int pslfe_sim3_solve_device(pslfe_ctx* ctx, int ncand, const PslSim3Pair* d_pairs, const float* d_sigma2, const int32_t* d_npairs, int pstride,
+                            const PslCamera* cam1, const PslCamera* cam2, double prob, int min_inliers, int max_its, int fix_scale,
+                            uint32_t seed0, const int32_t* d_start_it, const int32_t* d_best_in, int n_iterations, PslSim3SolverResult* d_res,
+                            uint8_t* d_inliers);
+/* Same for one candidate, host arrays (sigma2 [npairs][2], inliers [npairs], an output only); the candidate is seeded with `seed`;
+ * returns after the results have arrived. */
+int pslfe_sim3_solve(pslfe_ctx* ctx, const PslSim3Pair* pairs, const float* sigma2, int npairs, const PslCamera* cam1, const PslCamera* cam2,
+                     double prob, int min_inliers, int max_its, int fix_scale, uint32_t seed, int start_it, int best_in, int n_iterations,
+                     PslSim3SolverResult* res, uint8_t* inliers);
 
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;

@@ -51,6 +51,9 @@ SIM3PAIR_DTYPE = np.dtype([("u1", "<f4"), ("v1", "<f4"), ("inv_sigma2_1", "<f4")
                            ("P1c", "<f4", (3,)), ("P2c", "<f4", (3,))])
 SIM3INFO_DTYPE = np.dtype([("calls", "<i4"), ("iterations", "<i4", (2,)), ("exp_branches", "<i4")])
 assert SIM3_DTYPE.itemsize == 52 and SIM3D_DTYPE.itemsize == 64 and SIM3PAIR_DTYPE.itemsize == 48 and SIM3INFO_DTYPE.itemsize == 16
+# Sim3Solver (include/pslfe.h: PslSim3SolverResult)
+SIM3SOLVERRESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("ninliers", "<i4"), ("best_inliers", "<i4"), ("S12", SIM3_DTYPE)])
+assert SIM3SOLVERRESULT_DTYPE.itemsize == 68
 
 
 def pose(Tcw):
@@ -769,6 +772,147 @@ class Optimizer:
             frame._h, C.c_int(slot0), C.c_int(nframes), C.c_void_p(d_mp_index or None), C.c_void_p(d_mp or None), C.c_int(mpstride), _ptr(s2),
             C.c_int(len(s2)), C.c_void_p(d_edges or None), C.c_void_p(d_edge_kp or None), C.c_void_p(d_nedges or None), C.c_int(estride)),
             "pslfe_pose_edges_from_matches_device")
+
+    @staticmethod
+    def Sim3PairsSigma2FromMatchesDevice(f1, slot1, f2, d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2, mp2stride, d_T1w, d_T2w,
+                                         inv_level_sigma2, level_sigma2, d_pairs, d_pair_kp, d_npairs, pstride, d_sigma2):
+        """Sim3PairsFromMatchesDevice with one more output: d_sigma2 [ncand][pstride][2] (may be 0) = mvLevelSigma2 of the two octaves of
+        each row (src/Sim3Solver.cc:84-85), what Sim3Solver needs next to the rows."""
+        s2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        l2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(l2) != len(s2):
+            raise PslfeError(f"Sim3PairsSigma2FromMatchesDevice: {len(l2)} level sigma2 for {len(s2)} inverse ones")
+        _check(lib().pslfe_sim3_pairs_sigma2_from_matches_device(
+            f1._h, C.c_int(slot1), f2._h, C.c_void_p(d_slots2 or None), C.c_int(ncand), C.c_void_p(d_i2 or None), C.c_void_p(d_mp1 or None),
+            C.c_void_p(d_skip1 or None), C.c_int(n1), C.c_void_p(d_mp2 or None), C.c_void_p(d_skip2 or None), C.c_int(mp2stride),
+            C.c_void_p(d_T1w or None), C.c_void_p(d_T2w or None), _ptr(s2), C.c_int(len(s2)), C.c_void_p(d_pairs or None),
+            C.c_void_p(d_pair_kp or None), C.c_void_p(d_npairs or None), C.c_int(pstride), _ptr(l2), C.c_void_p(d_sigma2 or None)),
+            "pslfe_sim3_pairs_sigma2_from_matches_device")
+
+
+class Sim3Solver:
+    """== ORB_SLAM2::Sim3Solver (src/Sim3Solver.cc) of one candidate, with the reference's method names.  The constructor takes what the
+    reference's constructor builds (:62-103): pairs SIM3PAIR_DTYPE[n] (the rows of the set-up loop; P1c and P2c are read), sigma2 [n][2]
+    = mvLevelSigma2 of the two octaves of each row, indices1 [n] = mvnIndices1 (row -> KF1 keypoint), n_keys1 = vpMatched12.size().
+    rand() is glibc's generator seeded with `seed` at the solver's first iteration; iterate() resumes the solver through
+    (mnIterations, mnBestInliers), so rounds of iterate(5) are one find().  Parity with OpenCV is unpinned."""
+
+    def __init__(self, pairs, sigma2, indices1, n_keys1, cam1, cam2, fix_scale, seed, ctx=None):
+        self.ctx = ctx or default_context()
+        self.pairs = np.ascontiguousarray(pairs, SIM3PAIR_DTYPE)
+        self.sigma2 = np.ascontiguousarray(sigma2, np.float32).reshape(-1, 2)
+        self.indices1 = np.ascontiguousarray(indices1, np.int32)
+        if len(self.sigma2) != len(self.pairs) or len(self.indices1) != len(self.pairs):
+            raise PslfeError("Sim3Solver: pairs, sigma2 and indices1 differ in length")
+        self.n_keys1 = int(n_keys1)
+        self.cam1 = np.ascontiguousarray(cam1, CAMERA_DTYPE).reshape(1)
+        self.cam2 = np.ascontiguousarray(cam2, CAMERA_DTYPE).reshape(1)
+        self.fix_scale, self.seed = bool(fix_scale), int(seed) & 0xffffffff
+        self.result = np.zeros((), SIM3SOLVERRESULT_DTYPE)     # of the last call
+        self.row_inliers = np.zeros(len(self.pairs), np.uint8)  # the flags of the last call by pair row
+        self._best = np.zeros((), SIM3_DTYPE)
+        self._iterations = self._best_inliers = 0
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        self.prob, self.min_inliers, self.max_its = float(probability), int(minInliers), int(maxIterations)
+        self._iterations = 0                                   # mnIterations = 0 (:137); mnBestInliers stays
+
+    def iterate(self, nIterations):
+        """-> (ok = a Sim3 was returned, bNoMore, vbInliers bool [n_keys1], nInliers); GetEstimated* hold the Sim3 when ok"""
+        n = len(self.pairs)
+        res = np.zeros(1, SIM3SOLVERRESULT_DTYPE)
+        flags = np.zeros(max(n, 1), np.uint8)
+        _check(lib().pslfe_sim3_solve(self.ctx._h, _ptr(self.pairs) if n else None, _ptr(self.sigma2) if n else None, C.c_int(n), _ptr(self.cam1),
+                                      _ptr(self.cam2), C.c_double(self.prob), C.c_int(self.min_inliers), C.c_int(self.max_its),
+                                      C.c_int(1 if self.fix_scale else 0), C.c_uint32(self.seed), C.c_int(self._iterations),
+                                      C.c_int(self._best_inliers), C.c_int(nIterations), _ptr(res), _ptr(flags) if n else None), "pslfe_sim3_solve")
+        r = res[0]
+        if r["status"] < 0:
+            _check(int(r["status"]), "pslfe_sim3_solve")
+        self.result, self.row_inliers = r, flags[:n]
+        self._iterations, self._best_inliers = int(r["iterations"]), int(r["best_inliers"])
+        ok = r["status"] == 1
+        if ok:
+            self._best = r["S12"].copy()
+        vb = np.zeros(self.n_keys1, bool)
+        if ok:
+            rows = np.flatnonzero(flags[:n])
+            vb[self.indices1[rows]] = True
+        return bool(ok), bool(r["status"] == 2), vb, int(r["ninliers"])
+
+    def find(self):
+        """-> (ok, vbInliers12, nInliers)"""
+        ok, _, vb, nin = self.iterate(self.max_its)
+        return ok, vb, nin
+
+    def GetEstimatedRotation(self):
+        return self._best["R"].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return self._best["t"].copy()
+
+    def GetEstimatedScale(self):
+        return np.float32(self._best["s"])
+
+    @staticmethod
+    def SolveDevice(ncand, d_pairs, d_sigma2, d_npairs, pstride, cam1, cam2, fix_scale, seed0, n_iterations, d_res, d_inliers, d_start_it=0,
+                    d_best_in=0, prob=0.99, min_inliers=20, max_its=300, ctx=None):
+        """Sim3Solver::iterate(n_iterations) for ncand candidates in one launch, HBM to HBM, asynchronous; all d_* are device addresses
+        (ints; d_start_it / d_best_in may be 0: a fresh solver).  d_res SIM3SOLVERRESULT_DTYPE [ncand]; d_inliers [ncand][pstride] bytes by
+        pair row.  status = PSLFE_E_CAPACITY (-4) for a count above pstride, PSLFE_E_INVALID (-1) for a negative one."""
+        ctx = ctx or default_context()
+        cam1 = np.ascontiguousarray(cam1, CAMERA_DTYPE).reshape(1)
+        cam2 = np.ascontiguousarray(cam2, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_sim3_solve_device(
+            ctx._h, C.c_int(ncand), C.c_void_p(d_pairs or None), C.c_void_p(d_sigma2 or None), C.c_void_p(d_npairs or None), C.c_int(pstride),
+            _ptr(cam1), _ptr(cam2), C.c_double(prob), C.c_int(min_inliers), C.c_int(max_its), C.c_int(1 if fix_scale else 0),
+            C.c_uint32(int(seed0) & 0xffffffff), C.c_void_p(d_start_it or None), C.c_void_p(d_best_in or None), C.c_int(n_iterations),
+            C.c_void_p(d_res or None), C.c_void_p(d_inliers or None)), "pslfe_sim3_solve_device")
+
+    @staticmethod
+    def ComputeSim3Candidates(ncand, d_pairs, d_sigma2, d_npairs, pstride, cam1, cam2, fix_scale, seed0, prob=0.99, min_inliers=20, max_its=300,
+                              per_round=5, ctx=None):
+        """The candidate loop of LoopClosing::ComputeSim3 (src/LoopClosing.cc:284-345) for ncand candidates resident in HBM: rounds of
+        iterate(5) for every candidate still in the race, one launch per round.  A generator: yields (round, c, result record, inlier
+        flags by pair row u8 [pstride]) for every candidate that returns a Sim3, in the order the reference would try them (by round,
+        then by index); the caller does what :313-340 do with it (SearchBySim3, OptimizeSim3) and stops iterating on bMatch.  bNoMore
+        discards a candidate, as does a count below 0 or above pstride; the generator ends when none is left."""
+        ctx = ctx or default_context()
+        start, best = np.zeros(ncand, np.int32), np.zeros(ncand, np.int32)
+        discarded = np.zeros(ncand, bool)
+        res, flags = np.zeros(ncand, SIM3SOLVERRESULT_DTYPE), np.zeros((ncand, max(pstride, 1)), np.uint8)
+        d_res, d_flags = ctx.device_array(res)[0], ctx.device_array(flags)[0]
+        try:
+            rnd = 0
+            while ncand > 0 and not discarded.all():
+                d_s, d_b = ctx.device_array(start)[0], ctx.device_array(best)[0]
+                try:
+                    Sim3Solver.SolveDevice(ncand, d_pairs, d_sigma2, d_npairs, pstride, cam1, cam2, fix_scale, seed0, per_round, d_res, d_flags, d_s,
+                                           d_b, prob, min_inliers, max_its, ctx=ctx)
+                    for d, a in ((d_res, res), (d_flags, flags)):
+                        _check(lib().pslfe_device_download(ctx._h, _ptr(a), C.c_void_p(d), C.c_size_t(a.nbytes)), "pslfe_device_download")
+                finally:
+                    ctx.device_free(d_s)
+                    ctx.device_free(d_b)
+                for c in range(ncand):
+                    if discarded[c]:
+                        continue
+                    st = int(res[c]["status"])
+                    if st < 0 or st == 2:
+                        discarded[c] = True
+                        start[c] = max_its                      # runs no further iteration: its start is the end of every budget
+                    if st < 0:
+                        continue
+                    if st != 2:
+                        start[c] = res[c]["iterations"]
+                    best[c] = res[c]["best_inliers"]
+                    if st == 1:
+                        yield rnd, c, res[c].copy(), flags[c, :pstride].copy()
+                rnd += 1
+        finally:
+            ctx.device_free(d_res)
+            ctx.device_free(d_flags)
 
 
 class LINEextractor:

@@ -79,6 +79,85 @@ PSL_F64_QUAL double psl_log(double x) {
     return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
 }
 
+// Division as one correctly rounded operation on the device as on the host.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PSL_F64_DIV(a, b) __ddiv_rn((a), (b))
+#else
+#define PSL_F64_DIV(a, b) ((a) / (b))
+#endif
+
+// atan(x + dx), x finite or NaN, |dx| below an ulp of x (fdlibm s_atan.c; dx = 0 is fdlibm's atan itself).  dx enters to first order,
+// dx / (1 + x^2), inside the low-order sum of the result, so it costs no rounding of its own.
+PSL_F64_QUAL double psl_atan_lo(double x, double dx) {
+    const double hi0 = 4.63647609000806093515e-01, hi1 = 7.85398163397448278999e-01, hi2 = 9.82793723247329054082e-01,
+                 hi3 = 1.57079632679489655800e+00, lo0 = 2.26987774529616870924e-17, lo1 = 3.06161699786838301793e-17,
+                 lo2 = 1.39033110312309984516e-17, lo3 = 6.12323399573676603587e-17;
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01,
+                 aT3 = -1.11111104054623557880e-01, aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02, aT8 = 4.97687799461593236017e-02,
+                 aT9 = -3.65315727442169155270e-02, aT10 = 1.62858201153657823623e-02;
+    const uint64_t u = psl_f64_bits(x);
+    const int32_t hx = (int32_t)(u >> 32);
+    const int32_t ix = hx & 0x7fffffff;
+    const double corr = dx == 0.0 ? 0.0 : PSL_F64_DIV(dx, 1.0 + x * x);
+    int id;
+    if (ix >= 0x44100000) {  // |x| >= 2^66
+        if (ix > 0x7ff00000 || (ix == 0x7ff00000 && (uint32_t)u != 0)) return x + x;  // NaN
+        return hx > 0 ? hi3 + lo3 : -hi3 - lo3;
+    }
+    if (ix < 0x3fdc0000) {  // |x| < 0.4375
+        if (ix < 0x3e200000) return x;  // |x| < 2^-29
+        id = -1;
+    } else {
+        x = __builtin_fabs(x);
+        if (ix < 0x3ff30000) {  // |x| < 1.1875
+            if (ix < 0x3fe60000) { id = 0; x = PSL_F64_DIV(2.0 * x - 1.0, 2.0 + x); }  // 7/16 <= |x| < 11/16
+            else { id = 1; x = PSL_F64_DIV(x - 1.0, x + 1.0); }
+        } else {
+            if (ix < 0x40038000) { id = 2; x = PSL_F64_DIV(x - 1.5, 1.0 + 1.5 * x); }  // |x| < 2.4375
+            else { id = 3; x = PSL_F64_DIV(-1.0, x); }
+        }
+    }
+    const double z = x * x, w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    if (id < 0) return x - (x * (s1 + s2) - corr);
+    const double hi = id == 0 ? hi0 : id == 1 ? hi1 : id == 2 ? hi2 : hi3, lo = id == 0 ? lo0 : id == 1 ? lo1 : id == 2 ? lo2 : lo3;
+    const double r = hi - (((x * (s1 + s2) - lo) - (hx < 0 ? -corr : corr)) - x);
+    return hx < 0 ? -r : r;
+}
+PSL_F64_QUAL double psl_atan(double x) { return psl_atan_lo(x, 0.0); }
+
+// atan2(y, x) for finite arguments or NaN: fdlibm e_atan2.c without its branches for an infinite argument, and with the rounding
+// error of the quotient y / x (one fma) handed to atan's low-order sum.  glibc's atan2 is the multi-precision IBM routine, whose
+// tables cannot be rebuilt offline: this one is pinned as "within 1 ulp of the host's libm" on [0, 1] x [-1, 1], the range
+// Sim3Solver::ComputeSim3 calls it on (sim3_solver_kernels.h).  fdlibm's own atan2 rounds the quotient first and lands
+// two doubles from the host's once in about 1e7 samples of that range; with the quotient's error carried none of 1.6e7 does.
+PSL_F64_QUAL double psl_atan2(double y, double x) {
+    const double tiny = 1.0e-300, pi_o_2 = 1.5707963267948965580E+00, pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
+    if (x != x || y != y) return x + y;
+    const uint64_t ux = psl_f64_bits(x), uy = psl_f64_bits(y);
+    const int32_t hx = (int32_t)(ux >> 32), hy = (int32_t)(uy >> 32);
+    const uint32_t lx = (uint32_t)ux, ly = (uint32_t)uy;
+    const int32_t ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+    if ((((uint32_t)hx - 0x3ff00000u) | lx) == 0) return psl_atan(y);  // x = 1.0
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);                 // 2 * sign(x) + sign(y)
+    if (((uint32_t)iy | ly) == 0) return m < 2 ? y : m == 2 ? pi + tiny : -pi - tiny;
+    if (((uint32_t)ix | lx) == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int32_t k = (iy - ix) >> 20;
+    double z;
+    if (k > 60) z = pi_o_2 + 0.5 * pi_lo;
+    else if (hx < 0 && k < -60) z = 0.0;
+    else {   // the quotient and its rounding error: q + dq = y / x to twice the precision
+        const double q = PSL_F64_DIV(y, x), dq = PSL_F64_DIV(__builtin_fma(-q, x, y), x);
+        z = q < 0 ? psl_atan_lo(-q, -dq) : psl_atan_lo(q, dq);
+    }
+    if (m == 0) return z;
+    if (m == 1) return -z;
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+
 // x * 2^n for results that stay normal or underflow gradually (fdlibm scalbn, the cases exp needs)
 PSL_F64_QUAL double psl_scalbn(double x, int n) {
     if (n > 1023) { x *= 8.98846567431157953865e+307; n -= 1023; if (n > 1023) { x *= 8.98846567431157953865e+307; n -= 1023; if (n > 1023) n = 1023; } }

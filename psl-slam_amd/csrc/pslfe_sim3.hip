@@ -310,11 +310,13 @@ struct Sim3PairArgs {
     const PslPose* T1w;
     const PslPose* T2w;      // [ncand]
     float inv_sigma2[PSLFE_MAX_LEVELS];
+    float sigma2[PSLFE_MAX_LEVELS];   // mvLevelSigma2, read only when sig is set
     int nlevels;
     PslSim3Pair* pairs;
     int32_t* pair_kp;
     int32_t* npairs;
     int pstride;
+    float* sig;              // [ncand][pstride][2] or NULL: mvLevelSigma2 of the two octaves of each row (src/Sim3Solver.cc:84-85)
 };
 
 // one workgroup per candidate: KF1's keypoints in chunks of 256, compacted in keypoint order (psl_wg_compact of proj_kernels.h)
@@ -360,6 +362,11 @@ __global__ __launch_bounds__(256) void k_sim3_pairs(Sim3PairArgs A) {
             }
             pairs[pos] = p;
             if (pair_kp) pair_kp[pos] = i;
+            if (A.sig) {
+                float* sg = A.sig + 2 * ((size_t)c * A.pstride + pos);
+                sg[0] = A.sigma2[min(max(k1.octave, 0), A.nlevels - 1)];
+                sg[1] = A.sigma2[min(max(k2.octave, 0), A.nlevels - 1)];
+            }
         }
     }
     if (tid == 0) A.npairs[c] = base;
@@ -382,6 +389,43 @@ int sim3_launch(pslfe_ctx* ctx, int ncand, const PslSim3* d_S12_in, const PslSim
         PSL_STAGE_BEGIN(ctx, "sim3.optimize");
         k_sim3_optimize<<<ncand, PSL_S3_BS, lds, ctx->stream>>>(A);
         PSL_STAGE_END(ctx, "sim3.optimize");
+    }
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+
+// both set-up entry points; level_sigma2 / d_sigma2 are NULL for the first
+int sim3_pairs(pslfe_frame* f1, int slot1, pslfe_frame* f2, const int32_t* d_slots2, int ncand, const int32_t* d_i2, const PslMapPointGeom* d_mp1,
+               const uint8_t* d_skip1, int n1, const PslMapPointGeom* d_mp2, const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w,
+               const PslPose* d_T2w, const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs, int32_t* d_pair_kp, int32_t* d_npairs,
+               int pstride, const float* level_sigma2, float* d_sigma2, const char* who) {
+    PSL_REQUIRE(ncand >= 0 && n1 >= 0 && mp2stride >= 0 && pstride >= 0, PSLFE_E_INVALID, "%s: ncand = %d, n1 = %d, mp2stride = %d, pstride = %d",
+                who, ncand, n1, mp2stride, pstride);
+    if (ncand == 0) return PSLFE_OK;
+    PSL_REQUIRE(f1 && f2, PSLFE_E_INVALID, "%s: NULL frame store", who);
+    PSL_REQUIRE(f1->ctx == f2->ctx, PSLFE_E_INVALID, "%s: the frame stores belong to different contexts", who);
+    PSL_REQUIRE(slot1 >= 0 && slot1 < f1->max_frames, PSLFE_E_INVALID, "%s: slot %d of %d", who, slot1, f1->max_frames);
+    PSL_REQUIRE(f1->slot_set[slot1], PSLFE_E_STATE, "%s: slot %d not set", who, slot1);
+    PSL_REQUIRE(nlevels >= 1 && nlevels <= PSLFE_MAX_LEVELS && inv_level_sigma2, PSLFE_E_INVALID, "%s: nlevels = %d (1..%d) or NULL table", who,
+                nlevels, PSLFE_MAX_LEVELS);
+    PSL_REQUIRE(d_slots2 && d_i2 && d_T1w && d_T2w && d_npairs, PSLFE_E_INVALID, "%s: NULL array", who);
+    PSL_REQUIRE(n1 == 0 || (d_mp1 && d_skip1), PSLFE_E_INVALID, "%s: NULL map points with n1 = %d", who, n1);
+    PSL_REQUIRE(mp2stride == 0 || (d_mp2 && d_skip2), PSLFE_E_INVALID, "%s: NULL map points with mp2stride = %d", who, mp2stride);
+    PSL_REQUIRE(pstride == 0 || d_pairs, PSLFE_E_INVALID, "%s: NULL pairs with pstride = %d", who, pstride);
+    PSL_REQUIRE(!d_sigma2 || level_sigma2, PSLFE_E_INVALID, "%s: NULL table of level sigma2", who);
+    pslfe_ctx* ctx = f1->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    Sim3PairArgs A;
+    A.S1 = f1->S; A.S2 = f2->S; A.slot1 = slot1; A.slots2 = d_slots2; A.max_frames2 = f2->max_frames; A.i2 = d_i2;
+    A.mp1 = d_mp1; A.skip1 = d_skip1; A.n1 = n1; A.mp2 = d_mp2; A.skip2 = d_skip2; A.mp2stride = mp2stride;
+    A.T1w = d_T1w; A.T2w = d_T2w; A.nlevels = nlevels;
+    for (int l = 0; l < PSLFE_MAX_LEVELS; ++l) A.inv_sigma2[l] = l < nlevels ? inv_level_sigma2[l] : 0.f;
+    for (int l = 0; l < PSLFE_MAX_LEVELS; ++l) A.sigma2[l] = d_sigma2 && l < nlevels ? level_sigma2[l] : 0.f;
+    A.pairs = d_pairs; A.pair_kp = d_pair_kp; A.npairs = d_npairs; A.pstride = pstride; A.sig = d_sigma2;
+    {
+        PSL_STAGE_BEGIN(ctx, "sim3.pairs");
+        k_sim3_pairs<<<ncand, 256, 0, ctx->stream>>>(A);
+        PSL_STAGE_END(ctx, "sim3.pairs");
     }
     PSL_HIP(hipGetLastError());
     return PSLFE_OK;
@@ -437,35 +481,18 @@ int pslfe_sim3_pairs_from_matches_device(pslfe_frame* f1, int slot1, pslfe_frame
                                          const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w, const PslPose* d_T2w,
                                          const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs, int32_t* d_pair_kp,
                                          int32_t* d_npairs, int pstride) {
-    static const char* who = "pslfe_sim3_pairs_from_matches_device";
-    PSL_REQUIRE(ncand >= 0 && n1 >= 0 && mp2stride >= 0 && pstride >= 0, PSLFE_E_INVALID, "%s: ncand = %d, n1 = %d, mp2stride = %d, pstride = %d",
-                who, ncand, n1, mp2stride, pstride);
-    if (ncand == 0) return PSLFE_OK;
-    PSL_REQUIRE(f1 && f2, PSLFE_E_INVALID, "%s: NULL frame store", who);
-    PSL_REQUIRE(f1->ctx == f2->ctx, PSLFE_E_INVALID, "%s: the frame stores belong to different contexts", who);
-    PSL_REQUIRE(slot1 >= 0 && slot1 < f1->max_frames, PSLFE_E_INVALID, "%s: slot %d of %d", who, slot1, f1->max_frames);
-    PSL_REQUIRE(f1->slot_set[slot1], PSLFE_E_STATE, "%s: slot %d not set", who, slot1);
-    PSL_REQUIRE(nlevels >= 1 && nlevels <= PSLFE_MAX_LEVELS && inv_level_sigma2, PSLFE_E_INVALID, "%s: nlevels = %d (1..%d) or NULL table", who,
-                nlevels, PSLFE_MAX_LEVELS);
-    PSL_REQUIRE(d_slots2 && d_i2 && d_T1w && d_T2w && d_npairs, PSLFE_E_INVALID, "%s: NULL array", who);
-    PSL_REQUIRE(n1 == 0 || (d_mp1 && d_skip1), PSLFE_E_INVALID, "%s: NULL map points with n1 = %d", who, n1);
-    PSL_REQUIRE(mp2stride == 0 || (d_mp2 && d_skip2), PSLFE_E_INVALID, "%s: NULL map points with mp2stride = %d", who, mp2stride);
-    PSL_REQUIRE(pstride == 0 || d_pairs, PSLFE_E_INVALID, "%s: NULL pairs with pstride = %d", who, pstride);
-    pslfe_ctx* ctx = f1->ctx;
-    PSL_HIP(hipSetDevice(ctx->device));
-    Sim3PairArgs A;
-    A.S1 = f1->S; A.S2 = f2->S; A.slot1 = slot1; A.slots2 = d_slots2; A.max_frames2 = f2->max_frames; A.i2 = d_i2;
-    A.mp1 = d_mp1; A.skip1 = d_skip1; A.n1 = n1; A.mp2 = d_mp2; A.skip2 = d_skip2; A.mp2stride = mp2stride;
-    A.T1w = d_T1w; A.T2w = d_T2w; A.nlevels = nlevels;
-    for (int l = 0; l < PSLFE_MAX_LEVELS; ++l) A.inv_sigma2[l] = l < nlevels ? inv_level_sigma2[l] : 0.f;
-    A.pairs = d_pairs; A.pair_kp = d_pair_kp; A.npairs = d_npairs; A.pstride = pstride;
-    {
-        PSL_STAGE_BEGIN(ctx, "sim3.pairs");
-        k_sim3_pairs<<<ncand, 256, 0, ctx->stream>>>(A);
-        PSL_STAGE_END(ctx, "sim3.pairs");
-    }
-    PSL_HIP(hipGetLastError());
-    return PSLFE_OK;
+    return sim3_pairs(f1, slot1, f2, d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2, mp2stride, d_T1w, d_T2w, inv_level_sigma2, nlevels,
+                      d_pairs, d_pair_kp, d_npairs, pstride, nullptr, nullptr, "pslfe_sim3_pairs_from_matches_device");
+}
+
+int pslfe_sim3_pairs_sigma2_from_matches_device(pslfe_frame* f1, int slot1, pslfe_frame* f2, const int32_t* d_slots2, int ncand,
+                                                const int32_t* d_i2, const PslMapPointGeom* d_mp1, const uint8_t* d_skip1, int n1,
+                                                const PslMapPointGeom* d_mp2, const uint8_t* d_skip2, int mp2stride, const PslPose* d_T1w,
+                                                const PslPose* d_T2w, const float* inv_level_sigma2, int nlevels, PslSim3Pair* d_pairs,
+                                                int32_t* d_pair_kp, int32_t* d_npairs, int pstride, const float* level_sigma2,
+                                                float* d_sigma2) {
+    return sim3_pairs(f1, slot1, f2, d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2, mp2stride, d_T1w, d_T2w, inv_level_sigma2, nlevels,
+                      d_pairs, d_pair_kp, d_npairs, pstride, level_sigma2, d_sigma2, "pslfe_sim3_pairs_sigma2_from_matches_device");
 }
 
 }  // extern "C"

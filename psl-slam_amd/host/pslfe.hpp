@@ -1247,6 +1247,139 @@ public:
                                                    d_T1w, d_T2w, invLevelSigma2.data(), (int)invLevelSigma2.size(), d_pairs, d_pairKp, d_npairs,
                                                    pstride), "pslfe_sim3_pairs_from_matches_device");
     }
+    // the same set-up with mvLevelSigma2 of both octaves of each row in d_sigma2 [ncand][pstride][2], what Sim3Solver needs next to the rows
+    static void Sim3PairsSigma2FromMatchesDevice(FrameGrid& f1, int slot1, FrameGrid& f2, const int32_t* d_slots2, int ncand, const int32_t* d_i2,
+                                                 const PslMapPointGeom* d_mp1, const uint8_t* d_skip1, int n1, const PslMapPointGeom* d_mp2,
+                                                 const uint8_t* d_skip2, int mp2Stride, const PslPose* d_T1w, const PslPose* d_T2w,
+                                                 const std::vector<float>& invLevelSigma2, const std::vector<float>& levelSigma2,
+                                                 PslSim3Pair* d_pairs, int32_t* d_pairKp, int32_t* d_npairs, int pstride, float* d_sigma2) {
+        if (levelSigma2.size() != invLevelSigma2.size()) throw Error(PSLFE_E_INVALID, "Sim3PairsSigma2FromMatchesDevice: the two level tables differ in size");
+        check(pslfe_sim3_pairs_sigma2_from_matches_device(f1.get(), slot1, f2.get(), d_slots2, ncand, d_i2, d_mp1, d_skip1, n1, d_mp2, d_skip2,
+                                                          mp2Stride, d_T1w, d_T2w, invLevelSigma2.data(), (int)invLevelSigma2.size(), d_pairs,
+                                                          d_pairKp, d_npairs, pstride, levelSigma2.data(), d_sigma2),
+              "pslfe_sim3_pairs_sigma2_from_matches_device");
+    }
+};
+
+// Sim3Solver (src/Sim3Solver.cc) of one candidate, with the reference's method names.  The constructor takes what the reference's
+// constructor builds (:62-103): the rows of the set-up loop (P1c, P2c are read), mvLevelSigma2 of the two octaves of each row,
+// mvnIndices1 (row -> KF1 keypoint) and vpMatched12.size().  rand() is glibc's generator seeded with `seed` at the solver's first
+// iteration; iterate() resumes the solver through (mnIterations, mnBestInliers), so rounds of iterate(5) are one find().
+class Sim3Solver {
+public:
+    Sim3Solver(Context& ctx, std::vector<PslSim3Pair> pairs, std::vector<float> sigma2, std::vector<int32_t> indices1, int nKeys1,
+               const PslCamera& cam1, const PslCamera& cam2, bool fixScale, uint32_t seed)
+        : ctx_(&ctx), pairs_(std::move(pairs)), sigma2_(std::move(sigma2)), indices1_(std::move(indices1)), nKeys1_(nKeys1), cam1_(cam1),
+          cam2_(cam2), fixScale_(fixScale), seed_(seed) {
+        if (sigma2_.size() != 2 * pairs_.size() || indices1_.size() != pairs_.size()) throw Error(PSLFE_E_INVALID, "Sim3Solver: array sizes differ");
+        std::memset(&res_, 0, sizeof(res_));
+        SetRansacParameters();
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        prob_ = probability; minInliers_ = minInliers; maxIts_ = maxIterations;
+        res_.iterations = 0;   // mnIterations = 0 (:137); mnBestInliers stays
+    }
+    // cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers): true when a Sim3 was returned (GetEstimated* then hold it)
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        std::vector<uint8_t> flags(pairs_.size() ? pairs_.size() : 1, 0);
+        PslSim3SolverResult r;
+        check(pslfe_sim3_solve(ctx_->get(), pairs_.data(), sigma2_.data(), (int)pairs_.size(), &cam1_, &cam2_, prob_, minInliers_, maxIts_,
+                               fixScale_ ? 1 : 0, seed_, res_.iterations, res_.best_inliers, nIterations, &r, flags.data()),
+              "pslfe_sim3_solve");
+        if (r.status < 0) throw Error(r.status, "pslfe_sim3_solve");
+        const PslSim3 kept = res_.S12;
+        res_ = r;
+        if (r.status != 1) res_.S12 = kept;   // mBestRotation / Translation / Scale as the last returned hypothesis left them
+        bNoMore = r.status == 2;
+        nInliers = r.ninliers;
+        vbInliers.assign((size_t)nKeys1_, false);
+        if (r.status == 1)
+            for (size_t i = 0; i < pairs_.size(); ++i)
+                if (flags[i] && indices1_[i] >= 0 && indices1_[i] < nKeys1_) vbInliers[(size_t)indices1_[i]] = true;
+        rowFlags_.assign(flags.begin(), flags.begin() + pairs_.size());
+        return r.status == 1;
+    }
+    bool find(std::vector<bool>& vbInliers12, int& nInliers) {
+        bool flag;
+        return iterate(maxIts_, flag, vbInliers12, nInliers);
+    }
+    const float* GetEstimatedRotation() const { return res_.S12.R; }      // 3x3 row-major
+    const float* GetEstimatedTranslation() const { return res_.S12.t; }
+    float GetEstimatedScale() const { return res_.S12.s; }
+    const PslSim3SolverResult& result() const { return res_; }            // of the last call
+    const std::vector<uint8_t>& rowInliers() const { return rowFlags_; }  // the flags of the last call by pair row
+
+    // K candidates in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_sim3_solve_device
+    static void SolveDevice(Context& ctx, int ncand, const PslSim3Pair* d_pairs, const float* d_sigma2, const int32_t* d_npairs, int pstride,
+                            const PslCamera& cam1, const PslCamera& cam2, double prob, int minInliers, int maxIts, bool fixScale, uint32_t seed0,
+                            const int32_t* d_startIt, const int32_t* d_bestIn, int nIterations, PslSim3SolverResult* d_res, uint8_t* d_inliers) {
+        check(pslfe_sim3_solve_device(ctx.get(), ncand, d_pairs, d_sigma2, d_npairs, pstride, &cam1, &cam2, prob, minInliers, maxIts,
+                                      fixScale ? 1 : 0, seed0, d_startIt, d_bestIn, nIterations, d_res, d_inliers),
+              "pslfe_sim3_solve_device");
+    }
+
+    // The candidate loop of LoopClosing::ComputeSim3 (src/LoopClosing.cc:284-345) for K candidates resident in HBM: rounds of
+    // iterate(5) for every candidate that is still in the race, one launch per round.  A candidate that returns a Sim3 is handed to
+    // `accept(round, c, result, rowInliers)` in the order the reference would try it (by round, then by index); accept does what :313-340 do
+    // (SearchBySim3, OptimizeSim3) and returns true to end the loop (bMatch).  bNoMore discards a candidate; a count below 0 or above
+    // pstride discards it at once.  Returns the accepted candidate or -1.
+    template <class Accept>
+    static int ComputeSim3Candidates(Context& ctx, int ncand, const PslSim3Pair* d_pairs, const float* d_sigma2, const int32_t* d_npairs,
+                                     int pstride, const PslCamera& cam1, const PslCamera& cam2, bool fixScale, uint32_t seed0, Accept accept,
+                                     double prob = 0.99, int minInliers = 20, int maxIts = 300, int perRound = 5) {
+        if (ncand <= 0) return -1;
+        std::vector<int32_t> startIt((size_t)ncand, 0), bestIn((size_t)ncand, 0);
+        std::vector<uint8_t> discarded((size_t)ncand, 0), flags((size_t)ncand * (pstride ? pstride : 1));
+        std::vector<PslSim3SolverResult> res((size_t)ncand);
+        void *dS = nullptr, *dB = nullptr, *dR = nullptr, *dF = nullptr;
+        auto release = [&]() { for (void* p : {dS, dB, dR, dF}) if (p) pslfe_device_free(ctx.get(), p); };
+        try {
+            check(pslfe_device_alloc(ctx.get(), (size_t)ncand * 4, &dS), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), (size_t)ncand * 4, &dB), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), (size_t)ncand * sizeof(PslSim3SolverResult), &dR), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), flags.size(), &dF), "pslfe_device_alloc");
+            int live = ncand;
+            for (int round = 0; live > 0; ++round) {
+                check(pslfe_device_upload(ctx.get(), dS, startIt.data(), (size_t)ncand * 4), "pslfe_device_upload");
+                check(pslfe_device_upload(ctx.get(), dB, bestIn.data(), (size_t)ncand * 4), "pslfe_device_upload");
+                SolveDevice(ctx, ncand, d_pairs, d_sigma2, d_npairs, pstride, cam1, cam2, prob, minInliers, maxIts, fixScale, seed0,
+                            (const int32_t*)dS, (const int32_t*)dB, perRound, (PslSim3SolverResult*)dR, (uint8_t*)dF);
+                check(pslfe_device_download(ctx.get(), res.data(), dR, (size_t)ncand * sizeof(PslSim3SolverResult)), "pslfe_device_download");
+                check(pslfe_device_download(ctx.get(), flags.data(), dF, flags.size()), "pslfe_device_download");
+                for (int c = 0; c < ncand; ++c) {
+                    if (discarded[c]) continue;
+                    const PslSim3SolverResult& r = res[c];
+                    if (r.status < 0 || r.status == 2) { discarded[c] = 1; --live; }
+                    if (r.status < 0) continue;
+                    startIt[c] = r.iterations;
+                    bestIn[c] = r.best_inliers;
+                    if (r.status == 1 && accept(round, c, r, (const uint8_t*)flags.data() + (size_t)c * pstride)) { release(); return c; }
+                }
+                // a discarded candidate runs no further iteration: its start is at the end of every budget
+                for (int c = 0; c < ncand; ++c)
+                    if (discarded[c]) startIt[c] = maxIts;
+            }
+        } catch (...) {
+            release();
+            throw;
+        }
+        release();
+        return -1;
+    }
+
+private:
+    Context* ctx_;
+    std::vector<PslSim3Pair> pairs_;
+    std::vector<float> sigma2_;
+    std::vector<int32_t> indices1_;
+    int nKeys1_;
+    PslCamera cam1_, cam2_;
+    bool fixScale_;
+    uint32_t seed_;
+    double prob_ = 0.99;
+    int minInliers_ = 6, maxIts_ = 300;
+    PslSim3SolverResult res_;
+    std::vector<uint8_t> rowFlags_;
 };
 
 }  // namespace pslfe
