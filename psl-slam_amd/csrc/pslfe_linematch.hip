@@ -161,7 +161,8 @@ __device__ int line_pick(const PslKeyLine* kls, const uint8_t* desc, const doubl
     int pick = -1;
     if (k1 != 0xffffffffu && (int)(k1 >> 16) <= PSL_LINE_TH) {
         pick = s_cand[k1 & 0xffff];
-        if (MODE == 1 && k2 != 0xffffffffu) {
+        // the reference's bestDist2 starts at 256 and moves only on dist < bestDist2 (:296-340): a candidate at 256 is never the second best
+        if (MODE == 1 && k2 != 0xffffffffu && (k2 >> 16) < 256) {
             const int l1 = kls[pick].octave, l2 = kls[s_cand[k2 & 0xffff]].octave;
             if (l1 == l2 && (float)(k1 >> 16) > PSL_FMUL(nnratio, (float)(k2 >> 16))) pick = -1;
         }

@@ -1,9 +1,11 @@
 """GPU parity (exact) of the small association routines: LSDmatcher::SearchByGeomNApearance,
 LSDmatcher::FrameBFMatch (+ lineDescriptorMAD), Map::AssociatePlanesByBoundary (live) and
-InsectLineMatch::SearchMapInsectline (dead upstream, H14)."""
+InsectLineMatch::SearchMapInsectline (dead upstream, H14): on extracted synthetic scenes and on the hand-built cases of
+tests/assoc_cases.py, whose written-down answers tests/test_assoc_cases_cpu.py holds to the oracle without a GPU."""
 import numpy as np
 import pytest
 
+import assoc_cases as AC
 import synth_frames as sf
 
 pytestmark = pytest.mark.gpu
@@ -73,6 +75,48 @@ def test_associate_planes(live):
     assert (assoc >= 0).sum() >= 1
     n, assoc = P.associate_planes(planes[:0], pts[:0], mp, 0.05, 0.999, live=live)
     assert n == 0
+
+
+# ---- the hand-built cases of tests/assoc_cases.py: the written-down answer and the oracle's, exactly ----------------------------------
+@pytest.mark.parametrize("desc_th", [0.95, 1.0, 0.05])
+def test_geom_appearance_cases(desc_th):
+    """300 last-frame lines (more than the kernel's 256 threads): 40 that share a nearest neighbour, startPointX 0.0 / -0.0, the
+    end-point gate at exactly a tenth of the image, the direction gate on both sides, a tie of the two neighbours, no map line"""
+    import psl_slam_amd as P
+    import oracle_lib
+    c = AC.geom_case()
+    n, m12, asg = P.LSDmatcher().SearchByGeomNApearance(c.kl_last, c.d_last, c.kl_cur, c.d_cur, c.has, desc_th, c.bounds)
+    en, em12, easg = c.expected(desc_th)
+    np.testing.assert_array_equal(m12, em12)
+    np.testing.assert_array_equal(asg, easg)
+    assert n == en
+    rn, rm12, rasg = oracle_lib.search_by_geom_appearance(c.kl_last, c.d_last, c.kl_cur, c.d_cur, c.has, desc_th, c.bounds)
+    assert n == rn and (m12 == rm12).all() and (asg == rasg).all()
+    n, m12, asg = P.LSDmatcher().SearchByGeomNApearance(c.kl_last, c.d_last, c.kl_cur[:1], c.d_cur[:1], c.has, desc_th, c.bounds)
+    assert n == 0 and (m12 == -1).all() and (asg == -1).all()          # one current line: no second neighbour, no match
+
+
+@pytest.mark.parametrize("case", AC.bf_cases(), ids=repr)
+def test_frame_bf_match_cases(case):
+    """n1 = 1, 2, 255, 256, 257; medians and MADs that are one of many equal values; a MAD of 0; margins on either side of the
+    threshold; two train rows"""
+    import psl_slam_amd as P
+    import oracle_lib
+    got = P.LSDmatcher(case.nnratio).FrameBFMatch(case.d1, case.d2, case.TH)
+    np.testing.assert_array_equal(got, case.expected)
+    np.testing.assert_array_equal(got, oracle_lib.frame_bf_match(case.d1, case.d2, case.nnratio, case.TH))
+
+
+@pytest.mark.parametrize("case", AC.plane_cases(), ids=repr)
+def test_associate_planes_cases(case):
+    """the signed running threshold of the live variant, flipped map planes, bad map planes, the strict angle gate at +-aTh"""
+    import psl_slam_amd as P
+    import oracle_lib
+    n, assoc = P.associate_planes(case.planes, case.points, case.map, case.dTh, case.aTh, live=case.live, map_bad=case.bad)
+    np.testing.assert_array_equal(assoc, case.expected)
+    assert n == case.nmatches
+    rn, rassoc = oracle_lib.associate_planes(case.planes, case.points, case.map, case.dTh, case.aTh, case.live, case.bad)
+    assert n == rn and (assoc == rassoc).all()
 
 
 def _line_queries(k0, rng, radius, th_cos, jitter=2.0, p_block=0.8):

@@ -567,6 +567,16 @@ def complement(fn):
                 nnratio=0.25)
 
 
+def second_at_256(nnratio=0.3):
+    """SearchByProjection(F, MapPoints) at the acceptance threshold with a second candidate at distance 256 in the best's octave:
+    bestDist2 stays 256 with level -1 (src/ORBmatcher.cc:76-78, :102-110), no ratio test, T(100) is matched although 100 > 0.3f *
+    256; next to it T(100) against T(255) (refused) and T(101) against T(256) (above TH_HIGH)."""
+    kps = keypoints([(100, 100), (101, 100), (300, 100), (301, 100), (500, 100), (501, 100), (700, 100), (701, 100)])
+    q = queries([(100, 100), (300, 100), (500, 100), (700, 100)], 5.0)
+    return Case(f"second-at-256-{nnratio}", "map", kps, [T(100), T(256), T(256), T(100), T(100), T(255), T(101), T(256)], q, [T(0)] * 4,
+                [0, 3, -1, -1], {"gated_max": 2}, nnratio=nnratio)
+
+
 # ---- the lists the tests walk --------------------------------------------------------------------------------------------------
 def host_cases():
     """every case for the host entry points, by the function it is meant for"""
@@ -578,7 +588,8 @@ def host_cases():
     cs += [pile_up("last"), pile_up("map", "equal"), pile_up("map", "alternating")]
     cs += [pile_up("last", nk=40, step=3, pad=p) for p in (1030, 2050, 3080)]
     cs += [pile_up("map", "alternating", nk=40, step=3, pad=3080)]
-    cs += [ties("last"), ties("map"), ties("kf", 64), ties("kf", 100), ties_map(5, 3, 0.5), ties_map(10, 9, 0.8), map_equalities(), complement("kf"), complement("map")]
+    cs += [ties("last"), ties("map"), ties("kf", 64), ties("kf", 100), ties_map(5, 3, 0.5), ties_map(10, 9, 0.8), map_equalities(), complement("kf"), complement("map"),
+           second_at_256()]
     cs += [capacity("last"), capacity("last", nq=2049), capacity("last", nq=3073), capacity("last", n=4095), capacity("last", reverse=True),
            capacity("map"), capacity("map", reverse=True), capacity("kf").with_opts(orb_dist=100)]
     cs += [whole_image()]
