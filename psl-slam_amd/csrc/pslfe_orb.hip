@@ -101,6 +101,10 @@ struct pslfe_orb {
         OrbParams Q;
         memset(&Q, 0, sizeof(Q));
         Q.nlevels = nlevels; Q.iniTh = std::min(std::max(iniTh, 0), 255); Q.minTh = std::min(std::max(minTh, 0), 255);
+        // The reference calls FAST(iniThFAST) and, for a cell that stays empty, FAST(minThFAST) (src/ORBextractor.cc:808-816).  With
+        // iniThFAST <= minThFAST the second call can find nothing that the first did not, so the floor below which k_fast_cells4
+        // drops a score is the smaller of the two.
+        Q.minTh = std::min(Q.minTh, Q.iniTh);
         build_gauss_q8(7, 2.0, Q.blurK);
         for (int v = 0; v < 16; ++v) Q.umax[v] = umax[v];
         size_t pyr_off = 0, blur_off = 0;

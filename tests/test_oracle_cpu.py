@@ -9,6 +9,7 @@ import pytest
 
 import oracle_lib
 import synth_frames as sf
+from orb_cases import resize_tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -81,18 +82,8 @@ def test_resize_linear_matches_numpy_restatement(oracle):
     src = sf.random_gray(640, 480, 5, "blobs")
     dst = np.zeros((400, 533), np.uint8)
     oracle.pso_resize_linear_u8(src.ctypes.data, 640, 480, dst.ctypes.data, 533, 400)
-
-    def table(ssize, dsize):
-        scale = 1.0 / (float(dsize) / ssize)
-        d = np.arange(dsize)
-        f = ((d + 0.5) * scale - 0.5).astype(np.float32)
-        s = np.floor(f).astype(np.int64)
-        f = (f - s.astype(np.float32)).astype(np.float32)
-        a1 = np.rint(f * np.float32(2048)).astype(np.int64)
-        a0 = np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int64)
-        return s, a0, a1
-    sx, a0, a1 = table(640, 533)
-    sy, b0, b1 = table(480, 400)
+    sx, a0, a1 = resize_tables(640, 533)    # the numpy restatement of the tables (tests/orb_cases.py)
+    sy, b0, b1 = resize_tables(480, 400)
     S = src.astype(np.int64)
     hor = S[:, sx] * a0 + S[:, sx + 1] * a1
     out = (((b0[:, None] * (hor[sy] >> 4)) >> 16) + ((b1[:, None] * (hor[sy + 1] >> 4)) >> 16) + 2) >> 2

@@ -39,28 +39,34 @@ def desk():
     return sf.Scene(640, 480, "desk").gray(0)
 
 
+def _assert_same_stages(gpu, orc, got, ref, nlevels, what="", frame=0):
+    """Stage by stage, frame `frame` of the extractor's last launch against the oracle's last image: pyramid levels, FAST candidates
+    per level, octree keypoints per level, blurred levels, and the final frame `got` against `ref`."""
+    for l in range(nlevels):
+        np.testing.assert_array_equal(gpu.debug_level_image(frame, l), orc.level_image(l), err_msg=f"{what} pyramid level {l}")
+    for l in range(nlevels):
+        gc, rc = gpu.debug_candidates(frame, l), orc.candidates(l)
+        assert gc.shape == rc.shape, f"{what} FAST level {l}: {len(gc)} vs {len(rc)} candidates"
+        np.testing.assert_array_equal(gc, rc, err_msg=f"{what} FAST candidates level {l}")
+    for l in range(nlevels):
+        gk = gpu.debug_level_keypoints(frame, l)
+        rk = orc.level_keypoints(l)
+        assert len(gk) == len(rk), f"{what} octree level {l}: {len(gk)} vs {len(rk)}"
+        np.testing.assert_array_equal(gk[:, 0] + 16, rk["x"].astype(np.int32), err_msg=f"{what} octree x level {l}")
+        np.testing.assert_array_equal(gk[:, 1] + 16, rk["y"].astype(np.int32), err_msg=f"{what} octree y level {l}")
+        np.testing.assert_array_equal(gk[:, 2], rk["response"].astype(np.int32), err_msg=f"{what} octree response level {l}")
+    for l in range(nlevels):
+        rb = orc.level_image(l, blurred=True)
+        if rb is not None:
+            np.testing.assert_array_equal(gpu.debug_level_image(frame, l, blurred=True), rb, err_msg=f"{what} blur level {l}")
+    _assert_same_frame(got, ref, f"{what} frame")
+
+
 def test_stages_640x480(desk):
     gpu, orc = _pair()
     got = gpu(desk)
     ref = orc(desk)
-    for l in range(8):
-        np.testing.assert_array_equal(gpu.debug_level_image(0, l), orc.level_image(l), err_msg=f"pyramid level {l}")
-    for l in range(8):
-        gc, rc = gpu.debug_candidates(0, l), orc.candidates(l)
-        assert gc.shape == rc.shape, f"FAST level {l}: {len(gc)} vs {len(rc)} candidates"
-        np.testing.assert_array_equal(gc, rc, err_msg=f"FAST candidates level {l}")
-    for l in range(8):
-        gk = gpu.debug_level_keypoints(0, l)
-        rk = orc.level_keypoints(l)
-        assert len(gk) == len(rk), f"octree level {l}: {len(gk)} vs {len(rk)}"
-        np.testing.assert_array_equal(gk[:, 0] + 16, rk["x"].astype(np.int32), err_msg=f"octree x level {l}")
-        np.testing.assert_array_equal(gk[:, 1] + 16, rk["y"].astype(np.int32), err_msg=f"octree y level {l}")
-        np.testing.assert_array_equal(gk[:, 2], rk["response"].astype(np.int32), err_msg=f"octree response level {l}")
-    for l in range(8):
-        rb = orc.level_image(l, blurred=True)
-        if rb is not None:
-            np.testing.assert_array_equal(gpu.debug_level_image(0, l, blurred=True), rb, err_msg=f"blur level {l}")
-    _assert_same_frame(got, ref, "desk frame")
+    _assert_same_stages(gpu, orc, got, ref, 8, "desk")
     assert 900 <= len(got[0]) <= gpu.max_keypoints(640, 480)
 
 
