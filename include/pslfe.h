@@ -1343,6 +1343,84 @@ int pslfe_sim3_solve(pslfe_ctx* ctx, const PslSim3Pair* pairs, const float* sigm
                      double prob, int min_inliers, int max_its, int fix_scale, uint32_t seed, int start_it, int best_in, int n_iterations,
                      PslSim3SolverResult* res, uint8_t* inliers);
 
+/* ---- The EPnP RANSAC of relocalisation candidates: PnPsolver (src/PnPsolver.cc) -------------------------------------------------------
+ * The step of Tracking::Relocalization (src/Tracking.cc:2031-2190) between SearchByBoW (:2067) and PoseOptimization (:2130): the
+ * PnPsolver constructor (:2075), SetRansacParameters (:2076) and iterate(5, ...) (:2101).  For each candidate keyframe up to
+ * mRansacMaxIts hypotheses from four drawn rows (EPnP, all in double), each tested on every row; every hypothesis with at least
+ * mRansacMinInliers inliers is refined on the best inlier set so far.  Parity: OpenCV cannot be built offline, so this stage is "HIP ==
+ * host compile of the same header == restatement", parity with OpenCV unpinned (DESIGN.md §3 lists the readings of cvMulTransposed,
+ * cvSVD, cvInvert and cvSolve).  rand() is glibc's generator; candidate c is seeded as srand(seed0 + c) at its first iteration and every
+ * iteration takes four draws (the reference shares one unseeded process-wide stream; convention H7). */
+typedef struct PslPnpRow {   /* one correspondence of the constructor's loop (src/PnPsolver.cc:78-101) */
+    float u, v;      /* mvP2D: F.mvKeysUn[i].pt (:89)                          */
+    float X, Y, Z;   /* mvP3Dw: pMP->GetWorldPos() (:92-93)                    */
+    float sigma2;    /* mvSigma2: F.mvLevelSigma2[kp.octave] (:90)             */
+} PslPnpRow;
+typedef struct PslPnpResult {   /* per candidate */
+    int32_t status;        /* bit 0: a pose was returned (Tcw valid); bit 1: bNoMore; or PSLFE_E_CAPACITY / PSLFE_E_INVALID for a count
+                              above rstride / a negative count or state */
+    int32_t iterations;    /* mnIterations after the call */
+    int32_t inliers;       /* nInliers of the returned pose, 0 without one */
+    int32_t best_inliers;  /* mnBestInliers after the call */
+    int32_t min_inliers;   /* mRansacMinInliers after the clamps of SetRansacParameters (:134-139) */
+    PslPose Tcw;           /* mRefinedTcw (:235) or mBestTcw (:253), whichever iterate() returned; zeros otherwise */
+    PslPose best_Tcw;      /* mBestTcw: state for the next call */
+} PslPnpResult;
+#ifdef __cplusplus
+static_assert(sizeof(PslPnpRow) == 24 && sizeof(PslPnpResult) == 116, "PnP solver PODs");
+#else
+_Static_assert(sizeof(PslPnpRow) == 24 && sizeof(PslPnpResult) == 116, "PnP solver PODs");
+#endif
+/* == The constructor's loop src/PnPsolver.cc:78-101 for ncand candidates of one frame, HBM to HBM: d_mp_index[c][i] (row stride: the
+ *    frame's keypoint capacity) is the row in candidate c's PslMapPointGeom array (d_mp + c*mpstride) of the map point SearchByBoW gave
+ *    keypoint i (vvpMapPointMatches[c][i]), or -1; a bad or missing point is -1, and an index outside [0, mpstride) counts as -1.  It is
+ *    the array pslfe_pose_edges_from_matches_device reads.  mvKeysUn[i].pt and the octave come from slot `slot` of `frame`;
+ *    level_sigma2: host array of nlevels (mvLevelSigma2).  The rows are written in ascending i at d_rows + c*rstride; d_row_kp (may be
+ *    NULL) gets mvKeyPointIndices.  d_nrows[c] is the full count: a count above rstride is reported, never truncated silently (the first
+ *    rstride rows are written).  ncand < 0, rstride < 0, mpstride < 0, a NULL array with a non-zero count, nlevels outside
+ *    1..PSLFE_MAX_LEVELS: PSLFE_E_INVALID; ncand == 0: PSLFE_OK.  Asynchronous on the frame's context stream. */
+int pslfe_pnp_rows_from_matches_device(pslfe_frame* frame, int slot, int ncand, const int32_t* d_mp_index, const PslMapPointGeom* d_mp,
+                                       int mpstride, const float* level_sigma2, int nlevels, PslPnpRow* d_rows, int32_t* d_row_kp,
+                                       int32_t* d_nrows, int rstride);
+/* == SetRansacParameters (:121-152) for a solver of N rows, on the host: *max_its_out = mRansacMaxIts and *min_inliers_out =
+ *    mRansacMinInliers after the clamps, the values pslfe_pnp_solve_device tabulates.  N < 0, max_its < 1, min_inliers < 0, min_set
+ *    != 4, prob outside (0, 1), a NaN epsilon or a NULL output: PSLFE_E_INVALID.  Touches no device. */
+int pslfe_pnp_ransac_parameters(double prob, int min_inliers, int max_its, int min_set, float epsilon, int N, int* max_its_out,
+                                int* min_inliers_out);
+/* == PnPsolver::iterate(n_iterations, ...) (:165-258, with Refine :260-305 and CheckInliers :308-339) for ncand independent candidates
+ *    in one launch, after SetRansacParameters(prob, min_inliers, max_its, min_set, epsilon, th2) (:121-157; Relocalization: 0.99, 10,
+ *    300, 4, 0.5, 5.991).  Candidate c: d_nrows[c] rows at d_rows + c*rstride.  cam: fx, fy, cx, cy are read and widened to double.
+ *    min_set must be 4, the only value the reference passes (PSLFE_E_INVALID otherwise).  The solver's state between calls is the
+ *    caller's: d_state_in[c] (may be NULL: a fresh solver) is the PslPnpResult a former call left (iterations, best_inliers and
+ *    best_Tcw are read; it may be d_res), and d_best_flags [ncand][rstride] (mvbBestInliers, by row) is read and written.  A call
+ *    reseeds seed0 + c and skips 4 * iterations draws, so rounds of calls continue one solver exactly, also after a returned pose.
+ *    The loop is the reference's `while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations)`: a call runs
+ *    max(mRansacMaxIts - iterations, n_iterations) iterations unless a Refine succeeds first.
+ *    Outputs: d_res[c]; d_inliers [ncand][rstride] bytes indexed by row (the caller scatters them through d_row_kp, or calls
+ *    pslfe_pnp_mp_index_from_inliers_device): the flags of the returned pose, zeros without one, for the rows of the candidate.
+ *    d_nrows[c] > rstride: status = PSLFE_E_CAPACITY; d_nrows[c] < 0 or a negative iterations / best_inliers in the state:
+ *    PSLFE_E_INVALID; nothing is clamped, nothing is solved, no byte of d_inliers or d_best_flags is written, the other fields are 0.
+ *    min_inliers < 0, max_its < 1, n_iterations < 0, ncand < 0, rstride < 0, a NULL array with a non-zero count, prob outside (0, 1), a
+ *    NaN epsilon or th2: PSLFE_E_INVALID; ncand == 0: PSLFE_OK, nothing is done.  The budget and mRansacMinInliers of every row count
+ *    are tabulated on the host (the host's log and pow) and uploaded; no logarithm runs on the device.  Asynchronous on the context's
+ *    stream; per-call buffers come from the scratch arena. */
+int pslfe_pnp_solve_device(pslfe_ctx* ctx, int ncand, const PslPnpRow* d_rows, const int32_t* d_nrows, int rstride, const PslCamera* cam,
+                           double prob, int min_inliers, int max_its, int min_set, float epsilon, float th2, uint32_t seed0,
+                           const PslPnpResult* d_state_in, uint8_t* d_best_flags, int n_iterations, PslPnpResult* d_res, uint8_t* d_inliers);
+/* Same for one candidate, host arrays: state (may be NULL) and best_flags [nrows] (read and written) are the solver's state, inliers
+ * [nrows] an output only; the candidate is seeded with `seed`; returns after the results have arrived. */
+int pslfe_pnp_solve(pslfe_ctx* ctx, const PslPnpRow* rows, int nrows, const PslCamera* cam, double prob, int min_inliers, int max_its,
+                    int min_set, float epsilon, float th2, uint32_t seed, const PslPnpResult* state, uint8_t* best_flags, int n_iterations,
+                    PslPnpResult* res, uint8_t* inliers);
+/* == src/Tracking.cc:2119-2128 for ncand candidates, HBM to HBM: keypoint j keeps its map point (d_mp_index_out[c][j] =
+ *    d_mp_index[c][j]) if it is the keypoint d_row_kp[c][r] of a row r < min(d_nrows[c], rstride) with d_inliers[c][r] set;
+ *    every other keypoint becomes -1.  kpstride: the row stride of both index arrays (the frame's keypoint capacity); a row whose
+ *    keypoint is outside [0, kpstride) is ignored.  d_mp_index_out may not alias d_mp_index.  The result feeds
+ *    pslfe_pose_edges_from_matches_device unchanged.  Negative counts or a NULL array: PSLFE_E_INVALID; ncand == 0: PSLFE_OK.
+ *    Asynchronous on the context's stream. */
+int pslfe_pnp_mp_index_from_inliers_device(pslfe_ctx* ctx, int ncand, const int32_t* d_mp_index, const int32_t* d_row_kp, const uint8_t* d_inliers,
+                                           const int32_t* d_nrows, int rstride, int kpstride, int32_t* d_mp_index_out);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

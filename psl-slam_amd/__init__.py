@@ -54,6 +54,11 @@ assert SIM3_DTYPE.itemsize == 52 and SIM3D_DTYPE.itemsize == 64 and SIM3PAIR_DTY
 # Sim3Solver (include/pslfe.h: PslSim3SolverResult)
 SIM3SOLVERRESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("ninliers", "<i4"), ("best_inliers", "<i4"), ("S12", SIM3_DTYPE)])
 assert SIM3SOLVERRESULT_DTYPE.itemsize == 68
+# PnPsolver (include/pslfe.h: PslPnpRow, PslPnpResult)
+PNPROW_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("sigma2", "<f4")])
+PNPRESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("inliers", "<i4"), ("best_inliers", "<i4"), ("min_inliers", "<i4"),
+                            ("Tcw", POSE_DTYPE), ("best_Tcw", POSE_DTYPE)])
+assert PNPROW_DTYPE.itemsize == 24 and PNPRESULT_DTYPE.itemsize == 116
 
 
 def pose(Tcw):
@@ -913,6 +918,147 @@ class Sim3Solver:
         finally:
             ctx.device_free(d_res)
             ctx.device_free(d_flags)
+
+
+class PnPsolver:
+    """== ORB_SLAM2::PnPsolver (src/PnPsolver.cc) of one relocalisation candidate, with the reference's method names.  The constructor
+    takes what the reference's constructor builds (:67-110): rows PNPROW_DTYPE[n] (mvP2D, mvP3Dw, mvSigma2), key_point_indices [n] =
+    mvKeyPointIndices (row -> keypoint of F), n_keys = vpMapPointMatches.size().  rand() is glibc's generator seeded with `seed` at the
+    solver's first iteration; iterate() resumes the solver through (mnIterations, mnBestInliers, mBestTcw, mvbBestInliers), also after a
+    returned pose.  Parity with OpenCV is unpinned."""
+
+    def __init__(self, rows, key_point_indices, n_keys, cam, seed, ctx=None):
+        self.ctx = ctx or default_context()
+        self.rows = np.ascontiguousarray(rows, PNPROW_DTYPE)
+        self.key_point_indices = np.ascontiguousarray(key_point_indices, np.int32)
+        if len(self.key_point_indices) != len(self.rows):
+            raise PslfeError("PnPsolver: rows and key_point_indices differ in length")
+        self.n_keys = int(n_keys)
+        self.cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        self.seed = int(seed) & 0xffffffff
+        self.result = np.zeros((), PNPRESULT_DTYPE)            # of the last call: the solver's state
+        self.row_inliers = np.zeros(len(self.rows), np.uint8)  # the flags of the last call by row
+        self.best_flags = np.zeros(max(len(self.rows), 1), np.uint8)   # mvbBestInliers
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4, th2=5.991):
+        self.prob, self.min_inliers, self.max_its, self.min_set = float(probability), int(minInliers), int(maxIterations), int(minSet)
+        self.epsilon, self.th2 = float(epsilon), float(th2)
+
+    @staticmethod
+    def RansacParameters(N, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4):
+        """-> (mRansacMaxIts, mRansacMinInliers) after SetRansacParameters (:134-152) for a solver of N rows; no device is touched"""
+        its, mn = C.c_int(), C.c_int()
+        _check(lib().pslfe_pnp_ransac_parameters(C.c_double(probability), C.c_int(minInliers), C.c_int(maxIterations), C.c_int(minSet),
+                                                 C.c_float(epsilon), C.c_int(N), C.byref(its), C.byref(mn)), "pslfe_pnp_ransac_parameters")
+        return its.value, mn.value
+
+    def iterate(self, nIterations):
+        """-> (Tcw POSE_DTYPE record or None, bNoMore, vbInliers bool [n_keys] (empty without a pose), nInliers)"""
+        n = len(self.rows)
+        res = np.zeros(1, PNPRESULT_DTYPE)
+        flags = np.zeros(max(n, 1), np.uint8)
+        state = np.ascontiguousarray(self.result, PNPRESULT_DTYPE).reshape(1)
+        _check(lib().pslfe_pnp_solve(self.ctx._h, _ptr(self.rows) if n else None, C.c_int(n), _ptr(self.cam), C.c_double(self.prob),
+                                     C.c_int(self.min_inliers), C.c_int(self.max_its), C.c_int(self.min_set), C.c_float(self.epsilon),
+                                     C.c_float(self.th2), C.c_uint32(self.seed), _ptr(state), _ptr(self.best_flags) if n else None,
+                                     C.c_int(nIterations), _ptr(res), _ptr(flags) if n else None), "pslfe_pnp_solve")
+        r = res[0]
+        if r["status"] < 0:
+            _check(int(r["status"]), "pslfe_pnp_solve")
+        self.result, self.row_inliers = r.copy(), flags[:n]
+        ok = bool(r["status"] & 1)
+        vb = np.zeros(self.n_keys if ok else 0, bool)
+        if ok:
+            vb[self.key_point_indices[np.flatnonzero(flags[:n])]] = True
+        return (r["Tcw"].copy() if ok else None), bool(r["status"] & 2), vb, int(r["inliers"])
+
+    def find(self):
+        """-> (Tcw or None, vbInliers, nInliers)"""
+        its, _ = PnPsolver.RansacParameters(len(self.rows), self.prob, self.min_inliers, self.max_its, self.min_set, self.epsilon)
+        T, _, vb, nin = self.iterate(its)
+        return T, vb, nin
+
+    @staticmethod
+    def RowsFromMatchesDevice(frame, slot, ncand, d_mp_index, d_mp, mpstride, level_sigma2, d_rows, d_row_kp, d_nrows, rstride):
+        """The constructor's loop :78-101 on the device for ncand candidates of the frame in `slot`: d_mp_index [ncand][frame capacity] =
+        the PslMapPointGeom row (of candidate c's array d_mp + c*mpstride) of each keypoint's match or -1; rows compacted in keypoint
+        order; d_row_kp = mvKeyPointIndices; d_nrows[c] = the full count, also above rstride."""
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        _check(lib().pslfe_pnp_rows_from_matches_device(
+            frame._h, C.c_int(slot), C.c_int(ncand), C.c_void_p(d_mp_index or None), C.c_void_p(d_mp or None), C.c_int(mpstride), _ptr(s2),
+            C.c_int(len(s2)), C.c_void_p(d_rows or None), C.c_void_p(d_row_kp or None), C.c_void_p(d_nrows or None), C.c_int(rstride)),
+            "pslfe_pnp_rows_from_matches_device")
+
+    @staticmethod
+    def SolveDevice(ncand, d_rows, d_nrows, rstride, cam, seed0, n_iterations, d_state_in, d_best_flags, d_res, d_inliers, prob=0.99,
+                    min_inliers=10, max_its=300, min_set=4, epsilon=0.5, th2=5.991, ctx=None):
+        """PnPsolver::iterate(n_iterations) for ncand candidates in one launch, HBM to HBM, asynchronous; all d_* are device addresses
+        (ints; d_state_in may be 0: fresh solvers, or d_res).  d_res PNPRESULT_DTYPE [ncand]; d_best_flags (read and written) and
+        d_inliers [ncand][rstride] bytes by row.  status = PSLFE_E_CAPACITY (-4) for a count above rstride, PSLFE_E_INVALID (-1) for a
+        negative count or state.  The defaults are Relocalization's (src/Tracking.cc:2076)."""
+        ctx = ctx or default_context()
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_pnp_solve_device(
+            ctx._h, C.c_int(ncand), C.c_void_p(d_rows or None), C.c_void_p(d_nrows or None), C.c_int(rstride), _ptr(cam), C.c_double(prob),
+            C.c_int(min_inliers), C.c_int(max_its), C.c_int(min_set), C.c_float(epsilon), C.c_float(th2), C.c_uint32(int(seed0) & 0xffffffff),
+            C.c_void_p(d_state_in or None), C.c_void_p(d_best_flags or None), C.c_int(n_iterations), C.c_void_p(d_res or None),
+            C.c_void_p(d_inliers or None)), "pslfe_pnp_solve_device")
+
+    @staticmethod
+    def MapPointIndexFromInliersDevice(ncand, d_mp_index, d_row_kp, d_inliers, d_nrows, rstride, kpstride, d_mp_index_out, ctx=None):
+        """src/Tracking.cc:2119-2128 on the device: keypoint j keeps its map point if its row is an inlier, everything else becomes -1;
+        the result feeds Optimizer.EdgesFromMatchesDevice unchanged."""
+        ctx = ctx or default_context()
+        _check(lib().pslfe_pnp_mp_index_from_inliers_device(
+            ctx._h, C.c_int(ncand), C.c_void_p(d_mp_index or None), C.c_void_p(d_row_kp or None), C.c_void_p(d_inliers or None),
+            C.c_void_p(d_nrows or None), C.c_int(rstride), C.c_int(kpstride), C.c_void_p(d_mp_index_out or None)),
+            "pslfe_pnp_mp_index_from_inliers_device")
+
+    @staticmethod
+    def RelocalizeCandidates(ncand, d_rows, d_nrows, rstride, cam, seed0, prob=0.99, min_inliers=10, max_its=300, epsilon=0.5, th2=5.991,
+                             per_round=5, max_rounds=1000, ctx=None):
+        """The candidate loop of Tracking::Relocalization (src/Tracking.cc:2088-2180) for ncand candidates resident in HBM: rounds of
+        iterate(5) for every candidate still in the race, one launch per round.  A generator: yields (round, c, result record, inlier
+        flags by row u8 [rstride]) for every candidate that returns a pose, in the order the reference would try them (by round, then
+        by index); the caller does what :2107-2172 do with it (PoseOptimization, the two SearchByProjection) and stops iterating on
+        bMatch.  bNoMore discards a candidate (its pose, if it came with one, is still yielded), as does a count below 0 or above
+        rstride; a discarded candidate is parked with a negative state, which the kernel answers without solving.  The generator ends
+        when no candidate is left, or after max_rounds rounds: a candidate whose every call returns a refined pose never says
+        bNoMore, and the reference's loop ends on it only through bMatch."""
+        ctx = ctx or default_context()
+        state, res = np.zeros(ncand, PNPRESULT_DTYPE), np.zeros(ncand, PNPRESULT_DTYPE)
+        discarded = np.zeros(ncand, bool)
+        flags = np.zeros((ncand, max(rstride, 1)), np.uint8)
+        d_res, d_flags, d_best = ctx.device_array(res)[0], ctx.device_array(flags)[0], ctx.device_array(flags)[0]
+        try:
+            rnd = 0
+            while ncand > 0 and not discarded.all() and rnd < max_rounds:
+                d_state = ctx.device_array(state)[0]
+                try:
+                    PnPsolver.SolveDevice(ncand, d_rows, d_nrows, rstride, cam, seed0, per_round, d_state, d_best, d_res, d_flags, prob,
+                                          min_inliers, max_its, 4, epsilon, th2, ctx=ctx)
+                    for d, a in ((d_res, res), (d_flags, flags)):
+                        _check(lib().pslfe_device_download(ctx._h, _ptr(a), C.c_void_p(d), C.c_size_t(a.nbytes)), "pslfe_device_download")
+                finally:
+                    ctx.device_free(d_state)
+                for c in range(ncand):
+                    if discarded[c]:
+                        continue
+                    st = int(res[c]["status"])
+                    if st < 0 or st & 2:
+                        discarded[c] = True
+                        state[c]["iterations"] = -1
+                    if st < 0:
+                        continue
+                    if not discarded[c]:
+                        state[c] = res[c]
+                    if st & 1:
+                        yield rnd, c, res[c].copy(), flags[c, :rstride].copy()
+                rnd += 1
+        finally:
+            for d in (d_res, d_flags, d_best):
+                ctx.device_free(d)
 
 
 class LINEextractor:

@@ -1382,5 +1382,123 @@ private:
     std::vector<uint8_t> rowFlags_;
 };
 
+// PnPsolver (src/PnPsolver.cc) of one relocalisation candidate, with the reference's method names.  The constructor takes what the
+// reference's constructor builds (:67-110): the rows of its loop (mvP2D, mvP3Dw, mvSigma2), mvKeyPointIndices (row -> keypoint of F)
+// and vpMapPointMatches.size().  rand() is glibc's generator seeded with `seed` at the solver's first iteration; iterate() resumes the
+// solver through (mnIterations, mnBestInliers, mBestTcw, mvbBestInliers), also after a returned pose.
+class PnPsolver {
+public:
+    PnPsolver(Context& ctx, std::vector<PslPnpRow> rows, std::vector<int32_t> keyPointIndices, int nKeys, const PslCamera& cam, uint32_t seed)
+        : ctx_(&ctx), rows_(std::move(rows)), kp_(std::move(keyPointIndices)), nKeys_(nKeys), cam_(cam), seed_(seed) {
+        if (kp_.size() != rows_.size()) throw Error(PSLFE_E_INVALID, "PnPsolver: array sizes differ");
+        std::memset(&res_, 0, sizeof(res_));
+        bestFlags_.assign(rows_.size() ? rows_.size() : 1, 0);
+        SetRansacParameters();
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f,
+                             float th2 = 5.991f) {
+        prob_ = probability; minInliers_ = minInliers; maxIts_ = maxIterations; minSet_ = minSet; epsilon_ = epsilon; th2_ = th2;
+    }
+    // cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers): true when a pose was returned (Tcw() then holds it)
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        std::vector<uint8_t> flags(rows_.size() ? rows_.size() : 1, 0);
+        PslPnpResult r;
+        check(pslfe_pnp_solve(ctx_->get(), rows_.data(), (int)rows_.size(), &cam_, prob_, minInliers_, maxIts_, minSet_, epsilon_, th2_, seed_, &res_,
+                              bestFlags_.data(), nIterations, &r, flags.data()),
+              "pslfe_pnp_solve");
+        if (r.status < 0) throw Error(r.status, "pslfe_pnp_solve");
+        res_ = r;
+        bNoMore = (r.status & 2) != 0;
+        nInliers = r.inliers;
+        vbInliers.clear();
+        if (r.status & 1) {
+            vbInliers.assign((size_t)nKeys_, false);
+            for (size_t i = 0; i < rows_.size(); ++i)
+                if (flags[i] && kp_[i] >= 0 && kp_[i] < nKeys_) vbInliers[(size_t)kp_[i]] = true;
+        }
+        rowFlags_.assign(flags.begin(), flags.begin() + rows_.size());
+        return (r.status & 1) != 0;
+    }
+    bool find(std::vector<bool>& vbInliers, int& nInliers) {
+        bool flag;
+        int its = 0, minIn = 0;   // mRansacMaxIts after the clamps
+        check(pslfe_pnp_ransac_parameters(prob_, minInliers_, maxIts_, minSet_, epsilon_, (int)rows_.size(), &its, &minIn), "pslfe_pnp_ransac_parameters");
+        return iterate(its, flag, vbInliers, nInliers);
+    }
+    const PslPose& Tcw() const { return res_.Tcw; }                       // the pose the last call returned
+    const PslPnpResult& result() const { return res_; }                   // of the last call
+    const std::vector<uint8_t>& rowInliers() const { return rowFlags_; }  // the flags of the last call by row
+
+    // K candidates in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_pnp_solve_device
+    static void SolveDevice(Context& ctx, int ncand, const PslPnpRow* d_rows, const int32_t* d_nrows, int rstride, const PslCamera& cam, double prob,
+                            int minInliers, int maxIts, int minSet, float epsilon, float th2, uint32_t seed0, const PslPnpResult* d_stateIn,
+                            uint8_t* d_bestFlags, int nIterations, PslPnpResult* d_res, uint8_t* d_inliers) {
+        check(pslfe_pnp_solve_device(ctx.get(), ncand, d_rows, d_nrows, rstride, &cam, prob, minInliers, maxIts, minSet, epsilon, th2, seed0,
+                                     d_stateIn, d_bestFlags, nIterations, d_res, d_inliers),
+              "pslfe_pnp_solve_device");
+    }
+
+    // The candidate loop of Tracking::Relocalization (src/Tracking.cc:2088-2180) for K candidates resident in HBM: rounds of iterate(5)
+    // for every candidate that is still in the race, one launch per round.  A candidate that returns a pose is handed to
+    // `accept(round, c, result, rowInliers)` in the order the reference would try it (by round, then by index); accept does what
+    // :2107-2172 do (PoseOptimization, the two SearchByProjection) and returns true to end the loop (bMatch).  bNoMore discards a
+    // candidate (:2103-2107; its pose, if it came with one, is still tried); a count below 0 or above rstride discards it at once.  A
+    // discarded candidate is parked with a negative state, which the kernel answers without solving.  A candidate whose every call
+    // returns a refined pose never says bNoMore (the reference's loop ends on it only through bMatch): the loop gives up after
+    // maxRounds rounds.  Returns the accepted candidate or -1.
+    template <class Accept>
+    static int RelocalizeCandidates(Context& ctx, int ncand, const PslPnpRow* d_rows, const int32_t* d_nrows, int rstride, const PslCamera& cam,
+                                    uint32_t seed0, Accept accept, double prob = 0.99, int minInliers = 10, int maxIts = 300,
+                                    float epsilon = 0.5f, float th2 = 5.991f, int perRound = 5, int maxRounds = 1000) {
+        if (ncand <= 0) return -1;
+        std::vector<uint8_t> discarded((size_t)ncand, 0), flags((size_t)ncand * (rstride ? rstride : 1));
+        std::vector<PslPnpResult> state((size_t)ncand), res((size_t)ncand);
+        std::memset(state.data(), 0, state.size() * sizeof(PslPnpResult));
+        void *dS = nullptr, *dB = nullptr, *dR = nullptr, *dF = nullptr;
+        auto release = [&]() { for (void* p : {dS, dB, dR, dF}) if (p) pslfe_device_free(ctx.get(), p); };
+        try {
+            check(pslfe_device_alloc(ctx.get(), state.size() * sizeof(PslPnpResult), &dS), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), state.size() * sizeof(PslPnpResult), &dR), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), flags.size(), &dB), "pslfe_device_alloc");
+            check(pslfe_device_alloc(ctx.get(), flags.size(), &dF), "pslfe_device_alloc");
+            check(pslfe_device_upload(ctx.get(), dB, flags.data(), flags.size()), "pslfe_device_upload");
+            int live = ncand;
+            for (int round = 0; live > 0 && round < maxRounds; ++round) {
+                check(pslfe_device_upload(ctx.get(), dS, state.data(), state.size() * sizeof(PslPnpResult)), "pslfe_device_upload");
+                SolveDevice(ctx, ncand, d_rows, d_nrows, rstride, cam, prob, minInliers, maxIts, 4, epsilon, th2, seed0, (const PslPnpResult*)dS,
+                            (uint8_t*)dB, perRound, (PslPnpResult*)dR, (uint8_t*)dF);
+                check(pslfe_device_download(ctx.get(), res.data(), dR, res.size() * sizeof(PslPnpResult)), "pslfe_device_download");
+                check(pslfe_device_download(ctx.get(), flags.data(), dF, flags.size()), "pslfe_device_download");
+                for (int c = 0; c < ncand; ++c) {
+                    if (discarded[c]) continue;
+                    const PslPnpResult& r = res[c];
+                    if (r.status < 0 || (r.status & 2)) { discarded[c] = 1; --live; state[c].iterations = -1; }
+                    if (r.status < 0) continue;
+                    if (!discarded[c]) state[c] = r;
+                    if ((r.status & 1) && accept(round, c, r, (const uint8_t*)flags.data() + (size_t)c * rstride)) { release(); return c; }
+                }
+            }
+        } catch (...) {
+            release();
+            throw;
+        }
+        release();
+        return -1;
+    }
+
+private:
+    Context* ctx_;
+    std::vector<PslPnpRow> rows_;
+    std::vector<int32_t> kp_;
+    int nKeys_;
+    PslCamera cam_;
+    uint32_t seed_;
+    double prob_ = 0.99;
+    int minInliers_ = 8, maxIts_ = 300, minSet_ = 4;
+    float epsilon_ = 0.4f, th2_ = 5.991f;
+    PslPnpResult res_;
+    std::vector<uint8_t> bestFlags_, rowFlags_;
+};
+
 }  // namespace pslfe
 #endif
