@@ -1441,7 +1441,12 @@ int pslfe_glue_run(pslfe_glue* g, const PslKeyLine* kls, int nlines, const float
                    int width, int height, int depth_stride, const PslCamera* cam, uint32_t seed);
 /* Same for nframes frames resident in HBM: keylines [nframes][kl_stride] (kl_stride == max_lines), counts
  * [nframes], fans [nframes][fan_stride][4], counts [nframes], depth [nframes][height][width] float; frame f is
- * seeded with seed0 + f.  (pslfe_line_results_device / pslfe_line_pair_batch_device give exactly these views.) */
+ * seeded with seed0 + f.  (pslfe_line_results_device / pslfe_line_pair_batch_device give exactly these views.)
+ * Counts that the views cannot hold are clamped, not refused (they live in HBM): frame f uses its first
+ * min(d_nkl[f], kl_stride) keylines and its first min(d_nfans[f], fan_stride) fan rows; a negative count is an empty frame.
+ * Fan-index contract: a fan row that names a line outside [0, min(d_nkl[f], kl_stride)) yields no crossing and is not counted
+ * (pslfe_glue_run refuses such a row with PSLFE_E_INVALID; this entry point cannot look at the rows).  The rows of mvLines3D /
+ * mvLineEq past a frame's count are not written by a launch, so they are never read by it either. */
 int pslfe_glue_run_batch_device(pslfe_glue* g, int nframes, const PslKeyLine* d_kls, int kl_stride, const int32_t* d_nkl,
                                 const float* d_fans, int fan_stride, const int32_t* d_nfans, const float* d_depth,
                                 int width, int height, const PslCamera* cam, uint32_t seed0);

@@ -246,8 +246,8 @@ void compute_line3d_svd(const std::vector<RPt>& pts, const std::vector<int>& idx
     }
 }
 
-// returns A, B (zero when no line)
-void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA, P3& outB) {
+// returns A, B (zero when no line); t (may be null) counts what happened, it never changes what happens
+void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA, P3& outB, PsoLineTrace* t) {
     const int np = (int)pts.size();
     const int maxIterNo = std::min(10, int(np * (np - 1) * 0.5));
     const double distThresh = 3.0;
@@ -257,11 +257,13 @@ void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA
     P3 bestA = {0, 0, 0}, bestB = {0, 0, 0};
     for (int iter = 0; iter < maxIterNo; iter++) {
         std::vector<int> inlierSet;
+        if (t) t->iterations++;
         {  // random_unique(begin, end, 2)
             size_t left = indexes.size();
             size_t begin = 0;
             for (int num = 0; num < 2; ++num) {
                 const size_t r = begin + (size_t)rng.next() % left;
+                if (t) t->rand_drawn++;
                 std::swap(indexes[begin], indexes[r]);
                 ++begin;
                 --left;
@@ -269,13 +271,21 @@ void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA
         }
         const RPt& A = pts[indexes[0]];
         const RPt& B = pts[indexes[1]];
-        if (norm(B.pos - A.pos) < 0.0000000001) continue;
+        if (norm(B.pos - A.pos) < 0.0000000001) {
+            if (t) t->degenerate++;
+            continue;
+        }
         for (int i = 0; i < np; ++i)
             if (mah_dist3d_pt_line(pts[i], A.pos, B.pos) < distThresh) inlierSet.push_back(i);
         if (inlierSet.size() > maxInlierSet.size()) {
             std::vector<P3> inlierPts(inlierSet.size());
             for (size_t ii = 0; ii < inlierSet.size(); ++ii) inlierPts[ii] = pts[inlierSet[ii]].pos;
+            if (t) t->verify_calls++;
             if (verify3d_line(inlierPts, A.pos, B.pos)) {
+                if (t) {
+                    t->verify_passes++;
+                    if (!maxInlierSet.empty()) t->replaced++;
+                }
                 maxInlierSet = inlierSet;
                 bestA = pts[indexes[0]].pos;
                 bestB = pts[indexes[1]].pos;
@@ -285,6 +295,7 @@ void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA
     }
     outA = {0, 0, 0};
     outB = {0, 0, 0};
+    if (t) t->ransac_inliers = (int32_t)maxInlierSet.size();
     if (maxInlierSet.size() >= 2) {
         P3 m = (bestA + bestB) * 0.5, d = bestB - bestA;
         while (true) {
@@ -294,6 +305,7 @@ void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA
             for (int i = 0; i < np; ++i)
                 if (mah_dist3d_pt_line(pts[i], tmp_m, tmp_m + tmp_d) < distThresh) tmpInlierSet.push_back(i);
             if (tmpInlierSet.size() > maxInlierSet.size()) {
+                if (t) t->refine_grew++;
                 maxInlierSet = tmpInlierSet;
                 m = tmp_m;
                 d = tmp_d;
@@ -310,6 +322,79 @@ void extract3dline_mahdist(const std::vector<RPt>& pts, GlibcRand& rng, P3& outA
         outA = pts[maxInlierSet[idx_end1]].pos;
         outB = pts[maxInlierSet[idx_end2]].pos;
     }
+    if (t) t->final_inliers = (int32_t)maxInlierSet.size();
+}
+
+// Frame::isLineGood over the lines of a frame; tr (may be null) receives one record per line
+void line_good(const PsoKeyLine* kls, int n, const float* depth, int cols, int rows, int dstride, const float* cam, uint32_t seed,
+               double* lines3d, float* lineEq, PsoLineTrace* tr) {
+    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    const float invfx = 1.0f / fx, invfy = 1.0f / fy;
+    GlibcRand rng(seed);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 6; ++k) lines3d[6 * i + k] = 0.0;
+        lineEq[3 * i] = lineEq[3 * i + 1] = lineEq[3 * i + 2] = -1.0f;
+    }
+    if (tr) memset(tr, 0, (size_t)n * sizeof(PsoLineTrace));
+    for (int i = 0; i < n; ++i) {
+        PsoLineTrace* t = tr ? tr + i : nullptr;
+        const float spx = kls[i].startPointX, spy = kls[i].startPointY, epx = kls[i].endPointX, epy = kls[i].endPointY;
+        const float dxf = spx - epx, dyf = spy - epy;
+        const double len = std::sqrt((double)dxf * dxf + (double)dyf * dyf);
+        const double numSmp = (double)std::min((int)len, 20);
+        if (numSmp == 0) continue;  // convention: 0/0 upstream; exit_reason stays PSO_LINE_NO_SAMPLES
+        std::vector<P3> pts3d;
+        for (int j = 0; j <= numSmp; ++j) {
+            const double w1 = 1 - j / numSmp, w2 = j / numSmp;
+            const float ax = (float)(spx * w1), ay = (float)(spy * w1), bx = (float)(epx * w2), by = (float)(epy * w2);
+            const double ptx = (double)(ax + bx), pty = (double)(ay + by);
+            if (t) t->tried++;
+            if (ptx < 0 || pty < 0 || ptx >= cols || pty >= rows) {
+                if (t) t->outside++;
+                continue;
+            }
+            int row, col;
+            if ((std::floor(ptx) == ptx) && (std::floor(pty) == pty)) {
+                col = std::max(int(ptx - 1), 0);
+                row = std::max(int(pty - 1), 0);
+                if (t) {
+                    t->int_branch++;
+                    if (int(ptx - 1) < 0 || int(pty - 1) < 0) t->clamped++;
+                }
+            } else {
+                col = int(ptx);
+                row = int(pty);
+            }
+            const float dv = depth[(size_t)row * dstride + col];
+            if (dv <= 0.01) {
+                if (t) t->holes++;
+                continue;
+            }
+            P3 p;
+            p.z = dv;
+            p.x = (col - cx) * p.z * invfx;
+            p.y = (row - cy) * p.z * invfy;
+            pts3d.push_back(p);
+        }
+        if (t) {
+            t->np = (int32_t)pts3d.size();
+            t->exit_reason = PSO_LINE_FEW_POINTS;
+        }
+        if (pts3d.size() < 5) continue;
+        std::vector<RPt> rnd(pts3d.size());
+        for (size_t j = 0; j < pts3d.size(); ++j) rnd[j] = comp_pt3d_cov(pts3d[j], (double)fx);
+        P3 A, B;
+        extract3dline_mahdist(rnd, rng, A, B, t);
+        if (t) t->exit_reason = t->ransac_inliers >= 2 ? PSO_LINE_SHORT_3D : PSO_LINE_NO_VERIFIED_SET;
+        if (norm(A - B) > 0.02) {
+            const float e0 = (float)(B.x - A.x), e1 = (float)(B.y - A.y), e2 = (float)(B.z - A.z);
+            const float magn = std::sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+            lines3d[6 * i] = A.x; lines3d[6 * i + 1] = A.y; lines3d[6 * i + 2] = A.z;
+            lines3d[6 * i + 3] = B.x; lines3d[6 * i + 4] = B.y; lines3d[6 * i + 5] = B.z;
+            lineEq[3 * i] = e0 / magn; lineEq[3 * i + 1] = e1 / magn; lineEq[3 * i + 2] = e2 / magn;
+            if (t) t->exit_reason = PSO_LINE_ACCEPTED;
+        }
+    }
 }
 
 }  // namespace
@@ -325,63 +410,28 @@ int pso_glibc_rand(uint32_t seed, int n, int32_t* out) {  // the first n values 
 // lines3d: [n][6] (start, end; zeros when the line is not good); lineEq: [n][3] (-1 when not good).  cam = fx, fy, cx, cy.
 void pso_line_good(const PsoKeyLine* kls, int n, const float* depth, int cols, int rows, int dstride, const float* cam, uint32_t seed,
                    double* lines3d, float* lineEq) {
-    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
-    const float invfx = 1.0f / fx, invfy = 1.0f / fy;
-    GlibcRand rng(seed);
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < 6; ++k) lines3d[6 * i + k] = 0.0;
-        lineEq[3 * i] = lineEq[3 * i + 1] = lineEq[3 * i + 2] = -1.0f;
-    }
-    for (int i = 0; i < n; ++i) {
-        const float spx = kls[i].startPointX, spy = kls[i].startPointY, epx = kls[i].endPointX, epy = kls[i].endPointY;
-        const float dxf = spx - epx, dyf = spy - epy;
-        const double len = std::sqrt((double)dxf * dxf + (double)dyf * dyf);
-        const double numSmp = (double)std::min((int)len, 20);
-        if (numSmp == 0) continue;  // convention: 0/0 upstream
-        std::vector<P3> pts3d;
-        for (int j = 0; j <= numSmp; ++j) {
-            const double w1 = 1 - j / numSmp, w2 = j / numSmp;
-            const float ax = (float)(spx * w1), ay = (float)(spy * w1), bx = (float)(epx * w2), by = (float)(epy * w2);
-            const double ptx = (double)(ax + bx), pty = (double)(ay + by);
-            if (ptx < 0 || pty < 0 || ptx >= cols || pty >= rows) continue;
-            int row, col;
-            if ((std::floor(ptx) == ptx) && (std::floor(pty) == pty)) {
-                col = std::max(int(ptx - 1), 0);
-                row = std::max(int(pty - 1), 0);
-            } else {
-                col = int(ptx);
-                row = int(pty);
-            }
-            const float dv = depth[(size_t)row * dstride + col];
-            if (dv <= 0.01) continue;
-            P3 p;
-            p.z = dv;
-            p.x = (col - cx) * p.z * invfx;
-            p.y = (row - cy) * p.z * invfy;
-            pts3d.push_back(p);
-        }
-        if (pts3d.size() < 5) continue;
-        std::vector<RPt> rnd(pts3d.size());
-        for (size_t j = 0; j < pts3d.size(); ++j) rnd[j] = comp_pt3d_cov(pts3d[j], (double)fx);
-        P3 A, B;
-        extract3dline_mahdist(rnd, rng, A, B);
-        if (norm(A - B) > 0.02) {
-            const float e0 = (float)(B.x - A.x), e1 = (float)(B.y - A.y), e2 = (float)(B.z - A.z);
-            const float magn = std::sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-            lines3d[6 * i] = A.x; lines3d[6 * i + 1] = A.y; lines3d[6 * i + 2] = A.z;
-            lines3d[6 * i + 3] = B.x; lines3d[6 * i + 4] = B.y; lines3d[6 * i + 5] = B.z;
-            lineEq[3 * i] = e0 / magn; lineEq[3 * i + 1] = e1 / magn; lineEq[3 * i + 2] = e2 / magn;
-        }
-    }
+    line_good(kls, n, depth, cols, rows, dstride, cam, seed, lines3d, lineEq, nullptr);
+}
+
+// The same call with one PsoLineTrace per line (psl_oracle.h): which branches of the sampler and of the RANSAC each line took.
+void pso_line_good_trace(const PsoKeyLine* kls, int n, const float* depth, int cols, int rows, int dstride, const float* cam, uint32_t seed,
+                         double* lines3d, float* lineEq, PsoLineTrace* trace) {
+    line_good(kls, n, depth, cols, rows, dstride, cam, seed, lines3d, lineEq, trace);
 }
 
 // intersection_lines_plane: for every fan row (x, y, index1, index2) whose 3-D lines pass the test of
 // Frame_shortestDistance: pair[k] = (index1, index2), xy[k] = (x, y), cross[k] = the 3-D crossing point.
-int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3d, int32_t* pair, float* xy, double* cross, int cap) {
+// A row that names a line outside [0, nlines) yields no crossing and is not counted (the reference would index out of range;
+// include/pslfe.h states the same rule for the device entry point).  reason (may be null): one PSO_FAN_* per fan row.
+int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3d, int nlines, int32_t* pair, float* xy, double* cross, int cap,
+                              int32_t* reason) {
     int k = 0;
     for (int i = 0; i < nfans; ++i) {
         const float x = fans[4 * i], y = fans[4 * i + 1];
         const int i1 = (int)fans[4 * i + 2], i2 = (int)fans[4 * i + 3];
+        if (reason) reason[i] = PSO_FAN_BAD_INDEX;
+        if (!(i1 >= 0 && i1 < nlines && i2 >= 0 && i2 < nlines)) continue;
+        if (reason) reason[i] = PSO_FAN_DET_ZERO;
         const double* L1 = lines3d + 6 * i1;
         const double* L2 = lines3d + 6 * i2;
         const P3 p1 = {L1[0], L1[1], L1[2]}, p2 = {L2[0], L2[1], L2[2]};
@@ -398,8 +448,11 @@ int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3
         const P3 mid_x = (p1 + p2) * 0.5, mid_y = (e1 + e2) * 0.5;
         const double distmid = norm(mid_x - mid_y) * 2;
         const double n1 = std::sqrt(dot(p1, p1) + dot(e1, e1)), n2 = std::sqrt(dot(p2, p2) + dot(e2, e2));
+        if (reason) reason[i] = PSO_FAN_DISTMID;
         if (!(distmid < n1 + n2)) continue;  // falls off the end upstream
+        if (reason) reason[i] = PSO_FAN_ZERO_CROSSING;
         if (!(norm(crosspoint) > 2.220446049250313e-16)) continue;
+        if (reason) reason[i] = PSO_FAN_ACCEPTED;
         if (k < cap) {
             pair[2 * k] = i1; pair[2 * k + 1] = i2;
             xy[2 * k] = x; xy[2 * k + 1] = y;
@@ -412,11 +465,15 @@ int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3
 
 // The plane loop of Frame::ExtractLSD (src/Frame.cc:505-660).  Outputs per accepted plane: plane (4 floats), normal
 // (3 doubles), line pair, 3-D and 2-D crossing points; le_l: the normalised 2-D line equations of every intersection
-// (mvle_l, pushed before the filters), [nint][6].  Returns the number of planes.
+// (mvle_l, pushed before the filters), [nint][6].  Returns the number of planes.  trace (may be null): [nint][3] =
+// (PSO_PLANE_* reason, 1 when the plane was flipped to a positive distance, the plane that made it old or -1).
 int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const double* lines3d, const int32_t* pair, const float* xy,
                           const double* cross, int nint, float* planes, double* normals, int32_t* lineNo, double* cross3d, double* cross2d,
-                          double* le_l, int cap) {
+                          double* le_l, int cap, int32_t* trace) {
     int np = 0;
+    for (int i = 0; trace && i < nint; ++i) {
+        trace[3 * i] = PSO_PLANE_NOT_GOOD; trace[3 * i + 1] = 0; trace[3 * i + 2] = -1;
+    }
     for (int i = 0; i < nint; ++i) {
         const int l1 = pair[2 * i], l2 = pair[2 * i + 1];
         for (int s = 0; s < 2; ++s) {
@@ -451,6 +508,7 @@ int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const doub
         dmax = dmax > d1 ? dmax : d1; dmax = dmax > d2 ? dmax : d2; dmax = dmax > d3 ? dmax : d3; dmax = dmax > d4 ? dmax : d4;
         dmin = dmin < d5 ? dmin : d5;
         dmax = dmax > d5 ? dmax : d5;
+        if (trace) trace[3 * i] = PSO_PLANE_SPREAD;
         if (dmax - dmin > 0.05) continue;
         const float planeDis = -(d1 + d2 + d3 + d4 + d5) / 5;
         float pl[4] = {(float)nx, (float)ny, (float)nz, planeDis};
@@ -458,6 +516,7 @@ int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const doub
         if (pl[3] < 0) {
             for (int k = 0; k < 4; ++k) pl[k] = -pl[k];
             for (int k = 0; k < 3; ++k) nn[k] = -nn[k];
+            if (trace) trace[3 * i + 1] = 1;
         }
         bool old = false;  // Frame::OldPlane
         for (int k = 0; k < np && k < cap; ++k) {
@@ -467,8 +526,10 @@ int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const doub
             if (d > 0.2 || d < -0.2) continue;
             if (angle < 0.9397 && angle > -0.9397) continue;
             old = true;
+            if (trace) trace[3 * i + 2] = k;
             break;
         }
+        if (trace) trace[3 * i] = old ? PSO_PLANE_OLD : PSO_PLANE_ACCEPTED;
         if (old) continue;
         if (np < cap) {
             for (int k = 0; k < 4; ++k) planes[4 * np + k] = pl[k];

@@ -155,10 +155,25 @@ int pso_compute_bow(const int32_t* child_begin, const int32_t* child_count, cons
 /* RGB-D line glue of the Frame constructor (glue_oracle.cpp) */
 void pso_line_good(const PsoKeyLine* kls, int n, const float* depth, int cols, int rows, int dstride, const float* cam, uint32_t seed,
                    double* lines3d, float* lineEq);
-int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3d, int32_t* pair, float* xy, double* cross, int cap);
+/* what one keyline did inside pso_line_good (pso_line_good_trace): the sampler of Frame.cc:674-716, then extract3dline_mahdist */
+typedef struct PsoLineTrace {
+    int32_t tried, outside, int_branch, clamped, holes; /* samples: all, outside the image, integer-coordinate branch, of those clamped to 0, depth <= 0.01 */
+    int32_t np;                                          /* samples that became 3-D points */
+    int32_t rand_drawn, iterations, degenerate;          /* rand() values, RANSAC iterations, pairs closer than 1e-10 */
+    int32_t verify_calls, verify_passes, replaced;       /* verify3dLine; passes that replaced a non-empty inlier set */
+    int32_t ransac_inliers, refine_grew, final_inliers;  /* set size after the RANSAC, refinement rounds that grew it, size at the end */
+    int32_t exit_reason;                                 /* PSO_LINE_* */
+} PsoLineTrace;
+enum { PSO_LINE_NO_SAMPLES = 0, PSO_LINE_FEW_POINTS = 1, PSO_LINE_NO_VERIFIED_SET = 2, PSO_LINE_SHORT_3D = 3, PSO_LINE_ACCEPTED = 4 };
+enum { PSO_FAN_BAD_INDEX = 0, PSO_FAN_DET_ZERO = 1, PSO_FAN_DISTMID = 2, PSO_FAN_ZERO_CROSSING = 3, PSO_FAN_ACCEPTED = 4 };
+enum { PSO_PLANE_NOT_GOOD = 0, PSO_PLANE_SPREAD = 1, PSO_PLANE_OLD = 2, PSO_PLANE_ACCEPTED = 3 };
+void pso_line_good_trace(const PsoKeyLine* kls, int n, const float* depth, int cols, int rows, int dstride, const float* cam, uint32_t seed,
+                         double* lines3d, float* lineEq, PsoLineTrace* trace);
+int pso_fans_to_intersections(const float* fans, int nfans, const double* lines3d, int nlines, int32_t* pair, float* xy, double* cross, int cap,
+                              int32_t* reason);
 int pso_planes_from_pairs(const PsoKeyLine* kls, const float* lineEq, const double* lines3d, const int32_t* pair, const float* xy,
                           const double* cross, int nint, float* planes, double* normals, int32_t* lineNo, double* cross3d, double* cross2d,
-                          double* le_l, int cap);
+                          double* le_l, int cap, int32_t* trace);
 int pso_glibc_rand(uint32_t seed, int n, int32_t* out);
 
 /* The sequential checkers of the device projections, the stereo constructor and the monocular initialiser.  Their PODs are the

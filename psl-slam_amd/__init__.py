@@ -1483,14 +1483,21 @@ class FrameGlue:
         _check(lib().pslfe_glue_create(self.ctx._h, C.c_int(max_lines), C.c_int(max_fans), C.c_int(max_batch), C.byref(self._h)),
                "pslfe_glue_create")
 
-    def run(self, keylines, fans, depth, cam, seed=1):
+    def run(self, keylines, fans, depth, cam, seed=1, depth_stride=None):
+        """depth: the [height][width] f32 image.  depth_stride=None copies it to tight rows; depth_stride=s passes it as it lies in
+        memory: it must then be the first `width` columns of a C-contiguous f32 buffer [height][s] (buf[:, :width]), padding included."""
         kls = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
         fans = np.ascontiguousarray(fans, np.float32).reshape(-1, 4)
-        depth = np.ascontiguousarray(depth, np.float32)
+        if depth_stride is None:
+            depth = np.ascontiguousarray(depth, np.float32)
+            depth_stride = depth.shape[1]
+        elif depth.dtype != np.float32 or depth.ndim != 2 or depth.strides != (4 * depth_stride, 4) or depth.base is None or \
+                depth.base.shape != (depth.shape[0], depth_stride) or not depth.base.flags.c_contiguous:
+            raise PslfeError(f"FrameGlue.run: depth is not the first columns of a contiguous f32 buffer with rows of {depth_stride} floats")
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
         self._n = len(kls)
         _check(lib().pslfe_glue_run(self._h, _ptr(kls), C.c_int(len(kls)), _ptr(fans), C.c_int(len(fans)), _ptr(depth),
-                                    C.c_int(depth.shape[1]), C.c_int(depth.shape[0]), C.c_int(depth.shape[1]), _ptr(cam),
+                                    C.c_int(depth.shape[1]), C.c_int(depth.shape[0]), C.c_int(depth_stride), _ptr(cam),
                                     C.c_uint32(seed)), "pslfe_glue_run")
         return self.fetch(0, self._n)
 

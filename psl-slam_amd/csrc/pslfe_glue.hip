@@ -677,7 +677,8 @@ __global__ __launch_bounds__(64, PSL_GOOD_WAVES) void k_line_good(const PslKeyLi
 
 // convertFansToKeyLines + the plane loop of ExtractLSD.  One wave per frame: phase 1 evaluates the fans in parallel and
 // compacts the crossings in fan order; phase 2 (planes) is a short serial chain through Frame::OldPlane.
-__global__ __launch_bounds__(64) void k_fans_planes(const PslKeyLine* __restrict__ kls, int kl_stride, const float* __restrict__ fans,
+__global__ __launch_bounds__(64) void k_fans_planes(const PslKeyLine* __restrict__ kls, int kl_stride, const int32_t* __restrict__ nkl,
+                                                     int nkl_single, const float* __restrict__ fans,
                                                      int fan_stride, const int32_t* __restrict__ nfans_arr, int nfans_single,
                                                      const double* __restrict__ lines3d, const float* __restrict__ lineEq,
                                                      int32_t* __restrict__ pair, float* __restrict__ xy, double* __restrict__ cross,
@@ -687,6 +688,8 @@ __global__ __launch_bounds__(64) void k_fans_planes(const PslKeyLine* __restrict
                                                      int plane_cap) {
     const int frame = blockIdx.x, lane = threadIdx.x;
     const int nf = min(nfans_arr ? nfans_arr[frame] : nfans_single, fan_stride);
+    // the rows of lines3d / lineEq that k_line_good wrote for this frame: the rows past them hold an earlier launch's values
+    const int nl = min(nkl ? nkl[frame] : nkl_single, kl_stride);
     const PslKeyLine* K = kls + (size_t)frame * kl_stride;
     const float* F = fans + (size_t)frame * fan_stride * 4;
     const double* L3 = lines3d + (size_t)frame * kl_stride * 6;
@@ -706,7 +709,7 @@ __global__ __launch_bounds__(64) void k_fans_planes(const PslKeyLine* __restrict
         if (i < nf) {
             x = F[4 * i]; y = F[4 * i + 1];
             i1 = (int)F[4 * i + 2]; i2 = (int)F[4 * i + 3];
-            if (i1 >= 0 && i1 < kl_stride && i2 >= 0 && i2 < kl_stride) {
+            if (i1 >= 0 && i1 < nl && i2 >= 0 && i2 < nl) {
                 const double* A1 = L3 + 6 * i1;
                 const double* A2 = L3 + 6 * i2;
                 const GlueP3 p1 = {A1[0], A1[1], A1[2]}, p2 = {A2[0], A2[1], A2[2]}, e1 = {A1[3], A1[4], A1[5]}, e2 = {A2[3], A2[4], A2[5]};
@@ -855,7 +858,7 @@ static int glue_run(pslfe_glue* g, int nframes, const PslKeyLine* d_kls, int kl_
     }
     {
         PSL_STAGE_BEGIN(g->ctx, "line.planes");
-        k_fans_planes<<<nframes, 64, 0, st>>>(d_kls, kl_stride, d_fans, fan_stride, d_nfans, nfans_single, g->d_lines3d, g->d_lineEq, g->d_pair,
+        k_fans_planes<<<nframes, 64, 0, st>>>(d_kls, kl_stride, d_nkl, nkl_single, d_fans, fan_stride, d_nfans, nfans_single, g->d_lines3d, g->d_lineEq, g->d_pair,
                                              g->d_xy, g->d_cross, g->d_nint, g->int_cap, g->d_planes, g->d_normals, g->d_lineNo, g->d_cross3d,
                                              g->d_cross2d, g->d_le_l, g->d_nplanes, g->plane_cap);
         PSL_STAGE_END(g->ctx, "line.planes");

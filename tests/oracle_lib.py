@@ -396,29 +396,53 @@ def frame_post_rgbd(kps, depth, cam):
     return un[:n], dep[:n], ur[:n]
 
 
-def frame_glue(keylines, fans, depth, cam, seed=1):
-    """oracle chain isLineGood -> convertFansToKeyLines -> planes, same dict as psl_slam_amd.FrameGlue.run"""
+LINETRACE_DTYPE = np.dtype([(k, "<i4") for k in ("tried", "outside", "int_branch", "clamped", "holes", "np", "rand_drawn", "iterations",
+                                                  "degenerate", "verify_calls", "verify_passes", "replaced", "ransac_inliers", "refine_grew",
+                                                  "final_inliers", "exit_reason")])
+LINE_NO_SAMPLES, LINE_FEW_POINTS, LINE_NO_VERIFIED_SET, LINE_SHORT_3D, LINE_ACCEPTED = range(5)   # PsoLineTrace.exit_reason
+FAN_BAD_INDEX, FAN_DET_ZERO, FAN_DISTMID, FAN_ZERO_CROSSING, FAN_ACCEPTED = range(5)              # per fan row
+PLANE_NOT_GOOD, PLANE_SPREAD, PLANE_OLD, PLANE_ACCEPTED = range(4)                                # per crossing
+
+
+def frame_glue(keylines, fans, depth, cam, seed=1, depth_stride=None, trace=False):
+    """oracle chain isLineGood -> convertFansToKeyLines -> planes, same dict as psl_slam_amd.FrameGlue.run (depth_stride as there:
+    depth = buf[:, :width] of a contiguous [height][depth_stride] buffer).  trace=True adds line_trace (LINETRACE_DTYPE per line),
+    fan_reason (FAN_* per fan row) and plane_trace ([crossings][3]: PLANE_*, flipped, the plane that made it old or -1)."""
     L = load()
     kls = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
     fans = np.ascontiguousarray(fans, np.float32).reshape(-1, 4)
-    depth = np.ascontiguousarray(depth, np.float32)
+    if depth_stride is None:
+        depth = np.ascontiguousarray(depth, np.float32)
+        depth_stride = depth.shape[1]
+    else:
+        assert depth.dtype == np.float32 and depth.strides == (4 * depth_stride, 4), "depth must be buf[:, :width] of a padded f32 buffer"
     K, _, _ = _cam_arrays(cam)
     n, nf = len(kls), len(fans)
     out = dict(lines3d=np.zeros((max(n, 1), 6), np.float64), lineEq=np.zeros((max(n, 1), 3), np.float32))
-    L.pso_line_good.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.pso_line_good(_p(kls), n, _p(depth), depth.shape[1], depth.shape[0], depth.shape[1], _p(K), seed, _p(out["lines3d"]), _p(out["lineEq"]))
+    good = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    args = (_p(kls), n, C.c_void_p(depth.ctypes.data), depth.shape[1], depth.shape[0], depth_stride, _p(K), seed, _p(out["lines3d"]), _p(out["lineEq"]))
+    lt = np.zeros(max(n, 1), LINETRACE_DTYPE)
+    if trace:
+        L.pso_line_good_trace.argtypes = good + [C.c_void_p]
+        L.pso_line_good_trace(*args, _p(lt))
+    else:
+        L.pso_line_good.argtypes = good
+        L.pso_line_good(*args)
     cap = max(nf, 1)
     pair, xy, cross = np.zeros((cap, 2), np.int32), np.zeros((cap, 2), np.float32), np.zeros((cap, 3), np.float64)
-    L.pso_fans_to_intersections.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    ni = L.pso_fans_to_intersections(_p(fans), nf, _p(out["lines3d"]), _p(pair), _p(xy), _p(cross), cap)
+    fr, pt = np.zeros(cap, np.int32), np.zeros((cap, 3), np.int32)
+    L.pso_fans_to_intersections.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    ni = L.pso_fans_to_intersections(_p(fans), nf, _p(out["lines3d"]), n, _p(pair), _p(xy), _p(cross), cap, _p(fr) if trace else None)
     planes, normals, lineNo = np.zeros((cap, 4), np.float32), np.zeros((cap, 3), np.float64), np.zeros((cap, 2), np.int32)
     c3, c2, le_l = np.zeros((cap, 3), np.float64), np.zeros((cap, 2), np.float64), np.zeros((cap, 6), np.float64)
-    L.pso_planes_from_pairs.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+    L.pso_planes_from_pairs.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
     npl = L.pso_planes_from_pairs(_p(kls), _p(out["lineEq"]), _p(out["lines3d"]), _p(pair), _p(xy), _p(cross), ni, _p(planes), _p(normals),
-                                  _p(lineNo), _p(c3), _p(c2), _p(le_l), cap)
+                                  _p(lineNo), _p(c3), _p(c2), _p(le_l), cap, _p(pt) if trace else None)
     out["lines3d"], out["lineEq"] = out["lines3d"][:n], out["lineEq"][:n]
     out.update(pair=pair[:ni], xy=xy[:ni], cross=cross[:ni], le_l=le_l[:ni], planes=planes[:npl], normals=normals[:npl], lineNo=lineNo[:npl],
                cross3d=c3[:npl], cross2d=c2[:npl])
+    if trace:
+        out.update(line_trace=lt[:n], fan_reason=fr[:nf], plane_trace=pt[:ni])
     return out
 
 

@@ -1,7 +1,11 @@
 """GPU parity of the RGB-D line glue (isLineGood with the 3-D RANSAC, convertFansToKeyLines, the
 plane-from-pair loop) vs the sequential CPU oracle (oracle/glue_oracle.cpp).  Device and oracle execute the same IEEE
 double statements in the same order, so every output - including the discrete ones that depend on the rand() stream - is
-compared exactly."""
+compared exactly.
+
+These tests and test_line_good_groups_gpu.py draw random segments in one room corner (glue_scene.py).  The hand-built cases with
+written-down answers - samples outside the image, the integer-coordinate clamp, a padded depth stride, the thresholds set by
+construction, fan rows past a frame's line count - are in glue_cases.py, test_glue_cases_cpu.py and test_glue_edges_gpu.py."""
 import numpy as np
 import pytest
 
