@@ -887,8 +887,9 @@ __global__ __launch_bounds__(256) void k_lbd_pre(LineParams P, const uint8_t* __
 
 // ---------------------------------------------------------------------------------------------
 // LBD (computeLBD :1027-1373): one wave per line, lane = row hID of the 63-row line support region.
-// Every float accumulation runs in the reference's order: a lane walks its row left to right, band
-// sums are taken over hID ascending by lanes 0..8, the 72-float normalisation by lane 0.
+// Every float accumulation runs in the reference's order: a lane walks its row left to right, the 72
+// band sums are taken over hID ascending with one lane per chain, and the serial additions of the
+// 72-float normalisation by lanes 0 and 1 (its products, scalings and clamp: one element per lane).
 // ---------------------------------------------------------------------------------------------
 __constant__ int c_lbd_combos[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}, {1, 2}, {1, 3}, {1, 4}, {1, 5}, {1, 6},
                                         {2, 3}, {2, 4}, {2, 5}, {2, 6}, {2, 7}, {2, 8}, {3, 4}, {3, 5}, {3, 6}, {3, 7}, {3, 8},
@@ -897,15 +898,22 @@ __constant__ int c_lbd_combos[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, 
 #ifndef PSL_LBD_WAVES
 #define PSL_LBD_WAVES 1
 #endif
+// The sample loop is bound by the address processing of its gathers (63 image rows per load instruction), and the more waves share a CU's
+// vector cache the worse it gets: measured per 12288 dense frames with these tails, 8 waves per SIMD 21.3 ms, 6: 20.4, 5: 19.5, 4: 17.6, 3: 16.4
+// (profiles/lbd_pair_tails_ab.log).  The kernel before held 5 only because its one-lane tails needed 82 VGPRs; this one needs 42, so the bound is set.
+#ifndef PSL_LBD_MAX_WAVES
+#define PSL_LBD_MAX_WAVES 3
+#endif
+__attribute__((amdgpu_waves_per_eu(1, PSL_LBD_MAX_WAVES)))
 __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const short2* __restrict__ dxyI,
                                               const PslKeyLine* __restrict__ kls, const int* __restrict__ nkl, uint8_t* __restrict__ desc,
                                               float* __restrict__ fdesc) {
-    __shared__ float s_row[4][63][8];
+    __shared__ __attribute__((aligned(16))) float s_row[4][63][8];
     __shared__ float s_des[4][72];
     const int frame = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int line = blockIdx.x * 4 + wave;
-    const bool active = line < nkl[frame];
-    const PslKeyLine kl = kls[(size_t)frame * P.maxkl + (active ? line : 0)];
+    if (line >= nkl[frame]) return;  // the kernel has no block barrier: a wave without a line holds nobody up
+    const PslKeyLine kl = kls[(size_t)frame * P.maxkl + line];
     const short2* pdxy = dxyI + (size_t)frame * P.w * P.h;
     const int NB = 9, WB = 7;
     const short realWidth = (short)P.w, imageWidth = (short)(realWidth - 1), imageHeight = (short)(P.h - 1);
@@ -916,7 +924,7 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
     float dL0, dL1;
     psl_sincosf(kl.angle, &dL1, &dL0);  // dL = (cos(direction), sin(direction)), float overloads
     const float dO0 = -dL1, dO1 = dL0;
-    if (active && lane < 63) {
+    if (lane < 63) {
         float sCorX0 = PSL_FADD(PSL_FADD(PSL_FMUL(-dL0, (float)halfWidth), PSL_FMUL(dL1, (float)halfHeight)), midX);
         float sCorY0 = PSL_FADD(PSL_FSUB(PSL_FMUL(-dL1, (float)halfWidth), PSL_FMUL(dL0, (float)halfHeight)), midY);
         for (int hh = 0; hh < lane; ++hh) { sCorX0 = PSL_FSUB(sCorX0, dL1); sCorY0 = PSL_FADD(sCorY0, dL0); }
@@ -973,58 +981,88 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
         r[0] = pL; r[1] = nL; r[2] = PSL_FMUL(pL, pL); r[3] = PSL_FMUL(nL, nL);
         r[4] = pO; r[5] = nO; r[6] = PSL_FMUL(pO, pO); r[7] = PSL_FMUL(nO, nO);
     }
-    __syncthreads();
-    if (active && lane < NB) {
-        const int b = lane;
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // pL, nL, pL2, nL2, pO, nO, pO2, nO2
-        const int h0 = max(0, WB * (b - 1)), h1 = min(WB * NB, WB * (b + 2));
-        for (int hID = h0; hID < h1; ++hID) {
-            const int own = hID / WB;
-            const float c = own == b ? P.gaussL[hID % WB + WB] : (own == b + 1 ? P.gaussL[hID % WB + 2 * WB] : P.gaussL[hID % WB]);
-            const float* r = s_row[wave][hID];
-            const float cc = PSL_FMUL(c, c);
-            acc[0] = PSL_FADD(acc[0], PSL_FMUL(c, r[0])); acc[1] = PSL_FADD(acc[1], PSL_FMUL(c, r[1]));
-            acc[2] = PSL_FADD(acc[2], PSL_FMUL(cc, r[2])); acc[3] = PSL_FADD(acc[3], PSL_FMUL(cc, r[3]));
-            acc[4] = PSL_FADD(acc[4], PSL_FMUL(c, r[4])); acc[5] = PSL_FADD(acc[5], PSL_FMUL(c, r[5]));
-            acc[6] = PSL_FADD(acc[6], PSL_FMUL(cc, r[6])); acc[7] = PSL_FADD(acc[7], PSL_FMUL(cc, r[7]));
+    // s_row[wave] and s_des[wave] belong to this wave alone: the phases below are ordered by wave barriers (LDS operations of a wave
+    // complete in order), and a wave without a line has left above.
+    __builtin_amdgcn_wave_barrier();
+    // Band sums: one lane per (band, accumulator) chain, lane = 8 * b + a, bands 0 - 7 on the 64 lanes and band 8 on lanes 0 - 7.  Row k of band
+    // b's three-band window is hID = WB * (b - 1) + k, and its coefficient is gaussL[k] (the reference's own == b / b + 1 / b - 1 cases are
+    // gaussL[hID % WB + WB / 2 * WB / 0]): uniform in k, so the unrolled loop reads it from the kernel argument.  A chain adds its rows hID ascending.
+    const int a = lane & 7;
+    const float* rw = &s_row[wave][0][0];
+    auto band_chain = [&](const int b) {
+        float acc = 0;
+        const int base = (WB * (b - 1)) * 8 + a;
+        if (b > 0) {  // band 0 has no band above it
+#pragma unroll
+            for (int k = 0; k < WB; ++k) {
+                const float c = P.gaussL[k];
+                acc = PSL_FADD(acc, PSL_FMUL((a & 2) ? PSL_FMUL(c, c) : c, rw[base + 8 * k]));
+            }
         }
+#pragma unroll
+        for (int k = WB; k < 2 * WB; ++k) {
+            const float c = P.gaussL[k];
+            acc = PSL_FADD(acc, PSL_FMUL((a & 2) ? PSL_FMUL(c, c) : c, rw[base + 8 * k]));
+        }
+        if (b < NB - 1) {  // band 8 has none below
+#pragma unroll
+            for (int k = 2 * WB; k < 3 * WB; ++k) {
+                const float c = P.gaussL[k];
+                acc = PSL_FADD(acc, PSL_FMUL((a & 2) ? PSL_FMUL(c, c) : c, rw[base + 8 * k]));
+            }
+        }
+        // accumulators (pL, nL, pL2, nL2, pO, nO, pO2, nO2) -> the band's 8 floats (mean pL, nL, pO, nO; then their standard deviations): a
+        // squared-sum lane takes the mean from the lane two below it
         const float invN = (b == 0 || b == NB - 1) ? (float)(1.0 / (WB * 2.0)) : (float)(1.0 / (WB * 3.0));
-        float* d = &s_des[wave][8 * b];
-        float temp = PSL_FMUL(acc[0], invN);
-        d[0] = temp; d[4] = sqrtf(PSL_FSUB(PSL_FMUL(acc[2], invN), PSL_FMUL(temp, temp)));
-        temp = PSL_FMUL(acc[1], invN);
-        d[1] = temp; d[5] = sqrtf(PSL_FSUB(PSL_FMUL(acc[3], invN), PSL_FMUL(temp, temp)));
-        temp = PSL_FMUL(acc[4], invN);
-        d[2] = temp; d[6] = sqrtf(PSL_FSUB(PSL_FMUL(acc[6], invN), PSL_FMUL(temp, temp)));
-        temp = PSL_FMUL(acc[5], invN);
-        d[3] = temp; d[7] = sqrtf(PSL_FSUB(PSL_FMUL(acc[7], invN), PSL_FMUL(temp, temp)));
-    }
-    __syncthreads();
-    if (active && lane == 0) {
-        float* v = s_des[wave];
-        float tempM = 0, tempS = 0;
+        const float t = PSL_FMUL(acc, invN);
+        const float m = __shfl_up(t, 2);
+        const float val = (a & 2) ? sqrtf(PSL_FSUB(t, PSL_FMUL(m, m))) : t;
+        s_des[wave][8 * b + (((a & 2) << 1) | ((a & 4) >> 1) | (a & 1))] = val;
+    };
+    band_chain(lane >> 3);
+    if (lane < 8) band_chain(NB - 1);
+    __builtin_amdgcn_wave_barrier();
+    // Normalisation, one element per lane (lanes 0 - 7 also hold elements 64 - 71).  The products are formed in parallel; only the additions run in
+    // the reference's order: lane 0 adds the 36 squares of the means (bands ascending, entries 0 - 3), lane 1 beside it those of the deviations
+    // (entries 4 - 7), lane 0 the 72 of the final sum.  The squares sit in s_row[wave], whose rows are no longer needed.
+    float* sq = &s_row[wave][0][0];
+    float v0 = s_des[wave][lane], v1 = lane < 8 ? s_des[wave][64 + lane] : 0.f;
+    sq[lane] = PSL_FMUL(v0, v0);
+    if (lane < 8) sq[64 + lane] = PSL_FMUL(v1, v1);
+    __builtin_amdgcn_wave_barrier();
+    float t = 0;
+    if (lane < 2) {
+#pragma unroll
         for (int b = 0; b < NB; ++b) {
-            const float* q = v + 8 * b;
-            tempM = PSL_FADD(tempM, PSL_FMUL(q[0], q[0])); tempM = PSL_FADD(tempM, PSL_FMUL(q[1], q[1]));
-            tempM = PSL_FADD(tempM, PSL_FMUL(q[2], q[2])); tempM = PSL_FADD(tempM, PSL_FMUL(q[3], q[3]));
-            tempS = PSL_FADD(tempS, PSL_FMUL(q[4], q[4])); tempS = PSL_FADD(tempS, PSL_FMUL(q[5], q[5]));
-            tempS = PSL_FADD(tempS, PSL_FMUL(q[6], q[6])); tempS = PSL_FADD(tempS, PSL_FMUL(q[7], q[7]));
+            const float4 q = *reinterpret_cast<const float4*>(sq + 8 * b + 4 * lane);
+            t = PSL_FADD(t, q.x); t = PSL_FADD(t, q.y); t = PSL_FADD(t, q.z); t = PSL_FADD(t, q.w);
         }
-        tempM = PSL_FDIV(1.0f, sqrtf(tempM));
-        tempS = PSL_FDIV(1.0f, sqrtf(tempS));
-        for (int b = 0; b < NB; ++b) {
-            float* q = v + 8 * b;
-            q[0] = PSL_FMUL(q[0], tempM); q[1] = PSL_FMUL(q[1], tempM); q[2] = PSL_FMUL(q[2], tempM); q[3] = PSL_FMUL(q[3], tempM);
-            q[4] = PSL_FMUL(q[4], tempS); q[5] = PSL_FMUL(q[5], tempS); q[6] = PSL_FMUL(q[6], tempS); q[7] = PSL_FMUL(q[7], tempS);
-        }
-        for (int i = 0; i < 72; ++i) if ((double)v[i] > 0.4) v[i] = (float)0.4;
-        float temp = 0;
-        for (int i = 0; i < 72; ++i) temp = PSL_FADD(temp, PSL_FMUL(v[i], v[i]));
-        temp = PSL_FDIV(1.0f, sqrtf(temp));
-        for (int i = 0; i < 72; ++i) v[i] = PSL_FMUL(v[i], temp);
+        t = PSL_FDIV(1.0f, sqrtf(t));
     }
-    __syncthreads();
-    if (!active) return;
+    const float tempM = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
+    const float tempS = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 1));
+    const float scale = (lane & 4) ? tempS : tempM;  // elements 64 - 71 have the entry lane & 7 as well
+    v0 = PSL_FMUL(v0, scale); v1 = PSL_FMUL(v1, scale);
+    if ((double)v0 > 0.4) v0 = (float)0.4;
+    if ((double)v1 > 0.4) v1 = (float)0.4;
+    __builtin_amdgcn_wave_barrier();
+    sq[lane] = PSL_FMUL(v0, v0);
+    if (lane < 8) sq[64 + lane] = PSL_FMUL(v1, v1);
+    __builtin_amdgcn_wave_barrier();
+    t = 0;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 72; i += 4) {
+            const float4 q = *reinterpret_cast<const float4*>(sq + i);
+            t = PSL_FADD(t, q.x); t = PSL_FADD(t, q.y); t = PSL_FADD(t, q.z); t = PSL_FADD(t, q.w);
+        }
+        t = PSL_FDIV(1.0f, sqrtf(t));
+    }
+    const float temp = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t)));
+    v0 = PSL_FMUL(v0, temp); v1 = PSL_FMUL(v1, temp);
+    s_des[wave][lane] = v0;
+    if (lane < 8) s_des[wave][64 + lane] = v1;
+    __builtin_amdgcn_wave_barrier();
     const size_t o = (size_t)frame * P.maxkl + line;
     if (lane < 32) {  // binaryConversion (:402-413)
         const float* f1 = &s_des[wave][8 * c_lbd_combos[lane][0]];
@@ -1034,7 +1072,10 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
         for (int i = 0; i < 8; ++i) r |= (uint32_t)(f1[i] > f2[i]) << i;
         desc[o * 32 + lane] = (uint8_t)r;
     }
-    if (fdesc) for (int i = lane; i < 72; i += 64) fdesc[o * 72 + i] = s_des[wave][i];
+    if (fdesc) {
+        fdesc[o * 72 + lane] = v0;
+        if (lane < 8) fdesc[o * 72 + 64 + lane] = v1;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1066,7 +1107,9 @@ __device__ __forceinline__ int psl_block_excl_scan256(int v, int* s_w, int* tota
 #define PSL_PAIR_WAVES 8   // 56 VGPRs instead of 58: 8 waves per SIMD instead of 7, 4.88 -> 4.37 ms per 12288 dense frames (profiles/r03z_ab_waves_misc.log; the same knob
                          // does nothing for k_lsd_grad and costs k_lbd and k_line_good their registers: left as they are)
 #endif
-__global__ __launch_bounds__(256, PSL_PAIR_WAVES) void k_lil_pair(const float* __restrict__ lines, size_t lstride, int lp, const int* __restrict__ nlines, int nlines_single,
+// The kernel for more than PSL_PAIR_LDSN lines per frame (k_lil_pair below keeps its per-line state in LDS): every thread computes line i's
+// rectangle itself, candidates go through trips of 256 with a block scan each, and the de-duplication walks the raw rows in global memory.
+__global__ __launch_bounds__(256, PSL_PAIR_WAVES) void k_lil_pair_big(const float* __restrict__ lines, size_t lstride, int lp, const int* __restrict__ nlines, int nlines_single,
                                                    float radius, float fanThr, int imgCols, int imgRows, float* __restrict__ raw,
                                                    float* __restrict__ fans, int fan_cap, int* __restrict__ nfans) {
     __shared__ int s_w[4];
@@ -1153,6 +1196,194 @@ __global__ __launch_bounds__(256, PSL_PAIR_WAVES) void k_lil_pair(const float* _
             d[0] = R[4 * r]; d[1] = R[4 * r + 1]; d[2] = R[4 * r + 2]; d[3] = R[4 * r + 3];
         }
         kept += tot;
+    }
+    if (tid == 0) nfans[frame] = kept < fan_cap ? kept : fan_cap;
+}
+
+// The same rows for up to PSL_PAIR_LDSN lines per frame, with the per-line work done once and everything between the phases in LDS:
+//   0. thread = line: the line's rotated rectangle (centre, arcAng, half sizes, sin / cos, the addWeighted offsets) and its four coordinates;
+//   1. wave = line i (i = wave, wave + 4, ...), lane = candidate line: the rectangle test of 64 end points per instruction, the start points in
+//      trips of 64, then the end points.  The few candidates that pass (4 or 5 of 340 per line on the dense scene) do not run the angle test,
+//      the intersection and its two double divisions where they stand - one or two lanes of nearly every trip would - but queue up per wave and
+//      are worked off 64 at a time, a candidate per lane; a kept candidate sets its bit in the line's mask (bit = half * LDSN + candidate: row order);
+//   2. thread = line: rows of the line = set bits; one block scan gives every line its first row;
+//   3. thread = row: line by bisection of the first rows, candidate = the set bit of that rank; the intersection is computed again (on full
+//      waves, and only for kept candidates: no coordinate has to be parked while the offsets are unknown) and the row written;
+//   4. de-duplication on the ordered keys (i << 8 | j) in LDS.  A later row of the unordered pair {i, j} can only lie among the rows of line i, as
+//      (i, j) again, or - for j > i - among the rows of line j, as (j, i): two short key ranges instead of every later row.
+// Floating point: every operation as in k_lil_pair_big, operand for operand.
+#define PSL_PAIR_LDSN 256  // the batch path sees at most maxkl lines per frame, 200 in every configuration in use
+static_assert(PSL_PAIR_LDSN % 64 == 0 && PSL_PAIR_LDSN <= 256, "k_lil_pair: thread = line in a workgroup of 256, and a line index is one byte of a key");
+
+enum { PP_CENX, PP_CENY, PP_ARC, PP_HAFW, PP_HAFH, PP_DSIN, PP_DCOS, PP_GX, PP_GY, PP_N };
+struct PslPairLds {
+    float x0[PSL_PAIR_LDSN], y0[PSL_PAIR_LDSN], x1[PSL_PAIR_LDSN], y1[PSL_PAIR_LDSN];
+    union {
+        float par[PP_N][PSL_PAIR_LDSN];  // phases 0 - 1: cenx, ceny, arcAng, hafW, hafH, dsin, dcos, gx, gy of every line
+        uint16_t key[PSL_FAN_CAP];    // phases 3 - 4
+    };
+    __attribute__((aligned(16))) uint32_t mask[PSL_PAIR_LDSN][2 * PSL_PAIR_LDSN / 32];  // [i]: bit half * PSL_PAIR_LDSN + j = candidate point (start / end of line j) kept
+    union {
+        uint32_t queue[4][128];       // phase 1, per wave: i << 16 | half << 15 | j of the candidates inside line i's rectangle
+        int off[PSL_PAIR_LDSN + 1];   // phases 2 - 4: first row of every line (off[rows] = all rows)
+    };
+    int s_w[4];
+};
+static_assert(sizeof(PslPairLds) * 5 <= 160 * 1024, "k_lil_pair: five workgroups per CU");
+
+// intersectionOfLines (:226-247) of (p0, p1)-(p2, p3) with (q0, q1)-(q2, q3)
+__device__ __forceinline__ void psl_pair_intersect(float p0, float p1, float p2, float p3, float q0, float q1, float q2, float q3, float* X, float* Y) {
+    const float A1 = PSL_FSUB(p1, p3), B1 = PSL_FSUB(p2, p0), C1 = PSL_FSUB(PSL_FMUL(p3, p0), PSL_FMUL(p1, p2));
+    const float A2 = PSL_FSUB(q1, q3), B2 = PSL_FSUB(q2, q0), C2 = PSL_FSUB(PSL_FMUL(q3, q0), PSL_FMUL(q1, q2));
+    const float D = (float)psl_det2(A1, B1, A2, B2);
+    *X = (float)(psl_det2(-C1, B1, -C2, B2) / (double)D);
+    *Y = (float)(psl_det2(A1, -C1, A2, -C2) / (double)D);
+}
+
+__global__ __launch_bounds__(256) void k_lil_pair(const float* __restrict__ lines, size_t lstride, int lp, const int* __restrict__ nlines, int nlines_single,
+                                                   float radius, float fanThr, int imgCols, int imgRows, float* __restrict__ raw,
+                                                   float* __restrict__ fans, int fan_cap, int* __restrict__ nfans) {
+    __shared__ PslPairLds S;
+    const int frame = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float* L = lines + (size_t)frame * lstride;
+    const int rows = min(nlines ? nlines[frame] : nlines_single, PSL_PAIR_LDSN);  // the host sends larger frames to k_lil_pair_big
+    float* R = raw + (size_t)frame * PSL_FAN_CAP * 4;
+    {
+        uint4* mz = reinterpret_cast<uint4*>(S.mask[tid]);
+#pragma unroll
+        for (int k = 0; k < 2 * PSL_PAIR_LDSN / 128; ++k) mz[k] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (tid < rows) {
+        const int i = tid;
+        const float p0 = L[lp * i], p1 = L[lp * i + 1], p2 = L[lp * i + 2], p3 = L[lp * i + 3];
+        const float cenx = PSL_FADD(p0, p2) / 2, ceny = PSL_FADD(p1, p3) / 2;
+        const float dy = PSL_FSUB(p3, p1), dx = PSL_FSUB(p2, p0);
+        const float degAng = psl_fast_atan2(dy, dx);
+        const float arcAng = (float)PSL_DMUL((double)(degAng / 180), PSL_PI);
+        const float length = __builtin_fabsf(psl_tanf(arcAng)) > 1 ? __builtin_fabsf(dy) : __builtin_fabsf(dx);
+        const int th = (int)PSL_FMUL(radius, 2.f), tw = (int)PSL_FADD(length, PSL_FMUL(2.f, radius));  // CvSize is integer
+        const float angle = (float)(PSL_DMUL((double)degAng, PSL_PI) / 180);
+        float dsin, dcos;
+        psl_sincosf(angle, &dsin, &dcos);
+        S.x0[i] = p0; S.y0[i] = p1; S.x1[i] = p2; S.y1[i] = p3;
+        S.par[PP_CENX][i] = cenx; S.par[PP_CENY][i] = ceny; S.par[PP_ARC][i] = arcAng;
+        S.par[PP_HAFW][i] = (float)tw / 2; S.par[PP_HAFH][i] = (float)th / 2;
+        S.par[PP_DSIN][i] = dsin; S.par[PP_DCOS][i] = dcos;
+        S.par[PP_GX][i] = (float)PSL_DSUB(PSL_DMUL(-(double)cenx, (double)dcos), PSL_DMUL((double)ceny, (double)dsin));
+        S.par[PP_GY][i] = (float)PSL_DADD(PSL_DMUL(-(double)cenx, (double)dsin), PSL_DMUL((double)ceny, (double)dcos));
+    }
+    __syncthreads();
+    const int trips = (rows + 63) >> 6;
+    uint32_t* Q = S.queue[wave];
+    int qn = 0;  // wave-uniform
+    // the angle test, the intersection and isPtInRotatedRect for up to 64 queued candidates, one per lane
+    auto work_off = [&](const int n) {
+        if (lane < n) {
+            const uint32_t e = Q[lane];
+            const int i = (int)(e >> 16), half = (int)(e >> 15 & 1u), curSer = (int)(e & 0x7fffu);
+            const float tmpa = fmodf(__builtin_fabsf(PSL_FSUB(S.par[PP_ARC][i], S.par[PP_ARC][curSer])), (float)PSL_PI);
+            if (!(tmpa < fanThr || PSL_DSUB(PSL_PI, (double)tmpa) < (double)fanThr)) {
+                float X, Y;
+                psl_pair_intersect(S.x0[i], S.y0[i], S.x1[i], S.y1[i], S.x0[curSer], S.y0[curSer], S.x1[curSer], S.y1[curSer], &X, &Y);
+                // isPtInRotatedRect (:135-149), scalar float arithmetic
+                const float cenx = S.par[PP_CENX][i], ceny = S.par[PP_CENY][i], dsin = S.par[PP_DSIN][i], dcos = S.par[PP_DCOS][i], hafW = S.par[PP_HAFW][i], hafH = S.par[PP_HAFH][i];
+                const float fx = PSL_FADD(PSL_FMUL(dcos, PSL_FSUB(X, cenx)), PSL_FMUL(dsin, PSL_FSUB(Y, ceny)));
+                const float fy = PSL_FSUB(PSL_FMUL(dsin, PSL_FSUB(X, cenx)), PSL_FMUL(dcos, PSL_FSUB(Y, ceny)));
+                if ((-hafW <= fx && fx < hafW && -hafH <= fy && fy < hafH) && (X >= 4 && X < imgCols - 4 && Y >= 4 && Y < imgRows - 4)) {
+                    const int bit = half * PSL_PAIR_LDSN + curSer;
+                    atomicOr(&S.mask[i][bit >> 5], 1u << (bit & 31));
+                }
+            }
+        }
+    };
+    for (int i = wave; i < rows; i += 4) {
+        const float hafW = S.par[PP_HAFW][i], hafH = S.par[PP_HAFH][i];
+        const float dsin = S.par[PP_DSIN][i], dcos = S.par[PP_DCOS][i], gx = S.par[PP_GX][i], gy = S.par[PP_GY][i], ndcos = -dcos;
+        for (int half = 0; half < 2; ++half) {
+            const float* PX = half ? S.x1 : S.x0;
+            const float* PY = half ? S.y1 : S.y0;
+            for (int t = 0; t < trips; ++t) {
+                const int curSer = 64 * t + lane;
+                bool in = false;
+                if (curSer < rows) {
+                    const float px = PX[curSer], py = PY[curSer];
+                    const float fposx = PSL_FADD(PSL_FADD(PSL_FMUL(px, dcos), PSL_FMUL(py, dsin)), gx);
+                    const float fposy = PSL_FADD(PSL_FADD(PSL_FMUL(px, dsin), PSL_FMUL(py, ndcos)), gy);
+                    in = -hafW <= fposx && fposx < hafW && -hafH <= fposy && fposy < hafH && curSer != i;
+                }
+                const unsigned long long m = __ballot(in);
+                if (m == 0ull) continue;
+                if (in) Q[qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint32_t)(i << 16 | half << 15 | curSer);
+                qn += __popcll(m);  // at most 63 + 64 entries
+                __builtin_amdgcn_wave_barrier();
+                if (qn >= 64) {
+                    work_off(64);
+                    const uint32_t rest = lane + 64 < qn ? Q[lane + 64] : 0u;
+                    __builtin_amdgcn_wave_barrier();
+                    Q[lane] = rest;
+                    __builtin_amdgcn_wave_barrier();
+                    qn -= 64;
+                }
+            }
+        }
+    }
+    work_off(qn);
+    __syncthreads();
+    int tot;
+    {
+        int v = 0;
+        if (tid < rows) {
+            const uint4* mw = reinterpret_cast<const uint4*>(S.mask[tid]);
+#pragma unroll
+            for (int k = 0; k < 2 * PSL_PAIR_LDSN / 128; ++k) { const uint4 w = mw[k]; v += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w); }
+        }
+        const int ofs = psl_block_excl_scan256(v, S.s_w, &tot);
+        if (tid < rows) S.off[tid] = ofs;
+        if (tid == 0) S.off[rows] = tot;
+    }
+    __syncthreads();
+    const int count = tot < PSL_FAN_CAP ? tot : PSL_FAN_CAP;  // rows beyond PSL_FAN_CAP are dropped
+    for (int r = tid; r < count; r += 256) {
+        int lo = 0, hi = rows;  // the last line whose first row is not behind r: it is the one that has row r
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (S.off[mid] <= r) lo = mid; else hi = mid; }
+        const int i = lo;
+        int rank = r - S.off[i], w = 0;
+        uint32_t bits = S.mask[i][0];
+        for (int c = __popc(bits); rank >= c; c = __popc(bits)) { rank -= c; bits = S.mask[i][++w]; }
+        for (; rank > 0; --rank) bits &= bits - 1u;
+        const int curSer = (32 * w + (__ffs(bits) - 1)) & (PSL_PAIR_LDSN - 1);
+        float X, Y;
+        psl_pair_intersect(S.x0[i], S.y0[i], S.x1[i], S.y1[i], S.x0[curSer], S.y0[curSer], S.x1[curSer], S.y1[curSer], &X, &Y);
+        *reinterpret_cast<float4*>(R + 4 * (size_t)r) = make_float4(X, Y, (float)i, (float)curSer);
+        S.key[r] = (uint16_t)(i << 8 | curSer);
+    }
+    __syncthreads();
+    // keep the LAST occurrence of every unordered (i, j) pair (:109-131), order preserved
+    float* F = fans + (size_t)frame * fan_cap * 4;
+    int kept = 0;
+    for (int base = 0; base < count; base += 256) {
+        const int r = base + tid;
+        bool flag = false;
+        if (r < count) {
+            const uint32_t k = S.key[r];
+            const int i = (int)(k >> 8), j = (int)(k & 255);
+            flag = true;
+            const int e1 = min(S.off[i + 1], count);
+            for (int q = r + 1; q < e1; ++q)
+                if (S.key[q] == k) { flag = false; break; }
+            if (flag && j > i) {
+                const uint32_t ks = (uint32_t)(j << 8 | i);
+                const int e2 = min(S.off[j + 1], count);
+                for (int q = S.off[j]; q < e2; ++q)
+                    if (S.key[q] == ks) { flag = false; break; }
+            }
+        }
+        int ktot;
+        const int ofs = psl_block_excl_scan256(flag ? 1 : 0, S.s_w, &ktot);
+        if (flag && kept + ofs < fan_cap)
+            *reinterpret_cast<float4*>(F + 4 * (size_t)(kept + ofs)) = *reinterpret_cast<const float4*>(R + 4 * (size_t)r);
+        kept += ktot;
     }
     if (tid == 0) nfans[frame] = kept < fan_cap ? kept : fan_cap;
 }

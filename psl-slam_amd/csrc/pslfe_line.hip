@@ -57,6 +57,7 @@ struct pslfe_line {
     size_t in_fstride = 0;
     int in_pitch = 0;
     int last_nframes = 0;
+    int kl_bound = 0;  // no frame's count in d_nkl exceeds this: which pairing kernel run_pair launches
 
     uint8_t* d_in = nullptr;
     double* d_scaled = nullptr;
@@ -407,6 +408,7 @@ struct pslfe_line {
     // optimizeAndMergeLines_lsd + KeyLines + top-N + line equations on the segment lists in p.seg / p.nseg
     int run_merge(const Part& p) {
         PSL_HIP(hipSetDevice(ctx->device));
+        kl_bound = std::max(kl_bound, std::min(P.maxkl, std::max(P.nfeatures, 0)));  // the top-N cut of k_line_merge
         PSL_STAGE_BEGIN_ON(ctx, "line.merge", p.st);
         k_line_merge<PSL_MERGE_LDSN_SMALL><<<p.n, 256, 0, p.st>>>(P, p.M, p.seg, p.nseg, p.kls, p.lineEq, p.nkl, p.status);
         k_line_merge<PSL_MERGE_LDSN><<<p.n, 256, 0, p.st>>>(P, p.M, p.seg, p.nseg, p.kls, p.lineEq, p.nkl, p.status);
@@ -482,8 +484,9 @@ struct pslfe_line {
         PSL_STAGE_BEGIN(ctx, "line.pair");
         // mLines = (startPointX, startPointY, endPointX, endPointY) of every keyline (src/Frame.cc:355-373):
         // these are 4 consecutive floats at offset 7 of the 17-word KeyLine record
-        k_lil_pair<<<nframes, 256, 0, ctx->stream>>>(reinterpret_cast<const float*>(d_kls) + 7, (size_t)P.maxkl * 17, 17, d_nkl, 0, radius, fanThr,
-                                                     P.w, P.h, d_rawfans, d_fans, PSL_FAN_CAP, d_nfans);
+        // up to PSL_PAIR_LDSN lines per frame the kernel keeps in LDS
+        (kl_bound <= PSL_PAIR_LDSN ? k_lil_pair : k_lil_pair_big)<<<nframes, 256, 0, ctx->stream>>>(
+            reinterpret_cast<const float*>(d_kls) + 7, (size_t)P.maxkl * 17, 17, d_nkl, 0, radius, fanThr, P.w, P.h, d_rawfans, d_fans, PSL_FAN_CAP, d_nfans);
         PSL_STAGE_END(ctx, "line.pair");
         PSL_HIP(hipGetLastError());
         return PSLFE_OK;
@@ -785,6 +788,7 @@ int pslfe_lbd_compute(pslfe_line* line, const uint8_t* gray, int w, int h, int s
     PSL_HIP(hipMemcpyAsync(line->d_kls, kls, (size_t)nkl * sizeof(PslKeyLine), hipMemcpyHostToDevice, st));
     PSL_HIP(hipMemcpyAsync(line->d_nkl, &nkl, sizeof(int), hipMemcpyHostToDevice, st));
     PSL_HIP(hipStreamSynchronize(st));
+    line->kl_bound = std::max(line->kl_bound, nkl);
     const int keep = line->P.nfeatures;
     line->P.nfeatures = std::max(keep, nkl);
     rc = line->run_lbd(line->whole(1), line->d_in, line->in_pitch, line->in_fstride, fdesc != nullptr);
@@ -824,8 +828,8 @@ int pslfe_lil_pair(pslfe_line* line, const float* lines, int nlines, float radiu
     PSL_HIP(hipStreamSynchronize(st));
     {
         PSL_STAGE_BEGIN(line->ctx, "line.pair");
-        k_lil_pair<<<1, 256, 0, st>>>(line->d_tmplines, 0, 4, nullptr, nlines, radius, fanThr, imgCols, imgRows, line->d_rawfans, line->d_fans,
-                                      PSL_FAN_CAP, line->d_nfans);
+        (nlines <= PSL_PAIR_LDSN ? k_lil_pair : k_lil_pair_big)<<<1, 256, 0, st>>>(line->d_tmplines, 0, 4, nullptr, nlines, radius, fanThr, imgCols, imgRows,
+                                                                                   line->d_rawfans, line->d_fans, PSL_FAN_CAP, line->d_nfans);
         PSL_STAGE_END(line->ctx, "line.pair");
     }
     PSL_HIP(hipGetLastError());
