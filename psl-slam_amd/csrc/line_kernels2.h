@@ -898,21 +898,43 @@ __constant__ int c_lbd_combos[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, 
 #ifndef PSL_LBD_WAVES
 #define PSL_LBD_WAVES 1
 #endif
-// The sample loop is bound by the address processing of its gathers (63 image rows per load instruction), and the more waves share a CU's
-// vector cache the worse it gets: measured per 12288 dense frames with these tails, 8 waves per SIMD 21.3 ms, 6: 20.4, 5: 19.5, 4: 17.6, 3: 16.4
-// (profiles/lbd_pair_tails_ab.log).  The kernel before held 5 only because its one-lane tails needed 82 VGPRs; this one needs 42, so the bound is set.
+// Waves per SIMD, per 12288 dense frames (profiles/lbd_layout_ab.log).  The row-major loop alone is bound by the address processing of its
+// gathers (63 image rows per load instruction for a line along the image rows), and the more waves share a CU's vector cache the worse it
+// gets: 8 waves 21.3 ms, 6: 20.4, 5: 19.5, 4: 17.6, 3: 16.4, 2: 18.3, 1: 30.8.  With the step-major path for those lines the kernel is bound
+// by instruction issue and latency instead, and every wave more hides more of it: 1: 31.1, 2: 17.7, 3: 13.9, 4: 12.2, 5: 11.4, 6: 11.1,
+// 7: 10.9, 8: 10.7 ms on its own.  In the split schedule, where it runs beside the other part's growing, 8 waves (148 KB of the CU's LDS) cost
+// what they gain: the step was fastest at 5 - 6 waves (342.5 ms at the row-major kernel's 3; 3: 339.8, 4: 338.1, 5: 337.3, 6: 336.7, 8: 341.5).
 #ifndef PSL_LBD_MAX_WAVES
-#define PSL_LBD_MAX_WAVES 3
+#define PSL_LBD_MAX_WAVES 6
 #endif
+// Lane = row is the coalesced layout only for lines that run down the image (|dL0| < |dL1|: the 63 lanes of a load are neighbours in an image
+// row).  Along a near-horizontal line the same 63 lanes sit in 63 image rows.  Such a wave (|dL0| >= |dL1|, wave-uniform) gathers step-major:
+// in chunks of PSL_LBD_T steps, (a) lane = row advances its coordinate chain as ever and leaves the chunk's pixel indices in the wave's LDS
+// scratch, (b) lane = (row within a group of 64 / T rows, step) loads them - one instruction covers T consecutive steps of 64 / T rows, a
+// few cache lines - and puts the values where the indices were, (c) lane = row accumulates its T values in step order.  Every f32 operation
+// of a row and their order are those of the row-major loop; only where a value is loaded from differs.  The scratch pitch T + 1 is odd: the
+// row-major accesses of (a) and (c) hit 32 different banks.  PSL_LBD_STEP_MAJOR 0 builds the kernel without the second path.
+#ifndef PSL_LBD_T
+#define PSL_LBD_T 16
+#endif
+#ifndef PSL_LBD_STEP_MAJOR
+#define PSL_LBD_STEP_MAJOR 1
+#endif
+static_assert(PSL_LBD_T == 8 || PSL_LBD_T == 16 || PSL_LBD_T == 32, "a chunk is 8, 16 or 32 steps");
+#define PSL_LBD_PITCH (PSL_LBD_T + 1)
 __attribute__((amdgpu_waves_per_eu(1, PSL_LBD_MAX_WAVES)))
 __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const short2* __restrict__ dxyI,
                                               const PslKeyLine* __restrict__ kls, const int* __restrict__ nkl, uint8_t* __restrict__ desc,
                                               float* __restrict__ fdesc) {
-    __shared__ __attribute__((aligned(16))) float s_row[4][63][8];
+    // per wave: the chunk scratch of the step-major path (64 rows: the last load group's fourth row is written, never read), then the 63 x 8
+    // row sums in its first 504 floats
+    __shared__ __attribute__((aligned(16))) float s_buf[4][64 * PSL_LBD_PITCH];
     __shared__ float s_des[4][72];
+    static_assert(64 * PSL_LBD_PITCH >= 63 * 8 && (64 * PSL_LBD_PITCH) % 4 == 0, "the row sums alias the scratch, 16-byte aligned per wave");
     const int frame = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int line = blockIdx.x * 4 + wave;
     if (line >= nkl[frame]) return;  // the kernel has no block barrier: a wave without a line holds nobody up
+    float (*s_row)[8] = reinterpret_cast<float (*)[8]>(s_buf[wave]);
     const PslKeyLine kl = kls[(size_t)frame * P.maxkl + line];
     const short2* pdxy = dxyI + (size_t)frame * P.w * P.h;
     const int NB = 9, WB = 7;
@@ -924,60 +946,107 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
     float dL0, dL1;
     psl_sincosf(kl.angle, &dL1, &dL0);  // dL = (cos(direction), sin(direction)), float overloads
     const float dO0 = -dL1, dO1 = dL0;
+    float sCorX = 0, sCorY = 0;
     if (lane < 63) {
         float sCorX0 = PSL_FADD(PSL_FADD(PSL_FMUL(-dL0, (float)halfWidth), PSL_FMUL(dL1, (float)halfHeight)), midX);
         float sCorY0 = PSL_FADD(PSL_FSUB(PSL_FMUL(-dL1, (float)halfWidth), PSL_FMUL(dL0, (float)halfHeight)), midY);
         for (int hh = 0; hh < lane; ++hh) { sCorX0 = PSL_FSUB(sCorX0, dL1); sCorY0 = PSL_FADD(sCorY0, dL0); }
-        float sCorX = sCorX0, sCorY = sCorY0;
-        float pL = 0, nL = 0, pO = 0, nO = 0;
-        // The gathers of a row do not depend on each other: fetch 8 samples ahead (the coordinate chain is plain
-        // float adds), then accumulate them in the reference's order.  One sample per wait made the kernel
-        // latency-bound (90 % of the wave cycles in s_waitcnt).
-        // The same values with fewer instructions per sample (the kernel is bound by vector issue, ~55 per sample before): the rounded coordinate
-        // is clamped as an int (v_med3; it is far inside the range of the reference's short), the line's length is wave-uniform (a scalar loop
-        // bound: full blocks of 8 run without a guard), and "if (g > 0) p += g; else n -= g;" is p += max(g, 0); n -= min(g, 0): adding or
-        // subtracting a zero of either sign leaves p and n - which start at +0 and only ever grow - bit for bit as they are.
-        const int len = __builtin_amdgcn_readfirstlane((int)lengthOfLSP);
-        const int iw = (int)imageWidth, ih = (int)imageHeight, rw = (int)realWidth;
-        auto fetch8 = [&](short2* g8) {
+        sCorX = sCorX0; sCorY = sCorY0;
+    }
+    float pL = 0, nL = 0, pO = 0, nO = 0;
+    // The same values with fewer instructions per sample: the rounded coordinate is clamped as an int (v_med3; it is far inside the range of
+    // the reference's short), the line's length is wave-uniform (a scalar loop bound: full blocks run without a guard), and
+    // "if (g > 0) p += g; else n -= g;" is p += max(g, 0); n -= min(g, 0): adding or subtracting a zero of either sign leaves p and n - which
+    // start at +0 and only ever grow - bit for bit as they are.
+    const int len = __builtin_amdgcn_readfirstlane((int)lengthOfLSP);
+    const int iw = (int)imageWidth, ih = (int)imageHeight, rwid = (int)realWidth;
+    const uint32_t* pix = reinterpret_cast<const uint32_t*>(pdxy);  // a short2 per pixel
+    auto next_pixel = [&]() -> uint32_t {  // the pixel under the row's coordinate; one step on
+        int t = (int)__builtin_roundf(sCorX);
+        const int xCor = t < 0 ? 0 : (t > iw ? iw : t);
+        t = (int)__builtin_roundf(sCorY);
+        const int yCor = t < 0 ? 0 : (t > ih ? ih : t);
+        sCorX = PSL_FADD(sCorX, dL0);
+        sCorY = PSL_FADD(sCorY, dL1);
+        return (uint32_t)(__mul24(yCor, rwid) + xCor);  // coordinates are clamped: reads past the line's end are harmless (24-bit multiply: a full-rate instruction)
+    };
+    auto sample = [&](const uint32_t v) {
+        const short2 g = __builtin_bit_cast(short2, v);
+        const float gx = (float)g.x, gy = (float)g.y;
+        const float gDL = PSL_FADD(PSL_FMUL(gx, dL0), PSL_FMUL(gy, dL1));
+        const float gDO = PSL_FADD(PSL_FMUL(gx, dO0), PSL_FMUL(gy, dO1));
+        pL = PSL_FADD(pL, __builtin_fmaxf(gDL, 0.0f)); nL = PSL_FSUB(nL, __builtin_fminf(gDL, 0.0f));
+        pO = PSL_FADD(pO, __builtin_fmaxf(gDO, 0.0f)); nO = PSL_FSUB(nO, __builtin_fminf(gDO, 0.0f));
+    };
+#if PSL_LBD_STEP_MAJOR
+    if (__builtin_amdgcn_readfirstlane((int)(__builtin_fabsf(dL0) >= __builtin_fabsf(dL1)))) {
+        constexpr int T = PSL_LBD_T, PITCH = PSL_LBD_PITCH, RG = 64 / T, NG = (63 + RG - 1) / RG;  // RG rows per load, NG loads per chunk
+        uint32_t* sc = reinterpret_cast<uint32_t*>(s_buf[wave]);
+        uint32_t* mine = sc + lane * PITCH;                                  // phases a and c: this row's T slots
+        const int st = lane & (T - 1), sr = lane / T;                        // phase b: this lane's step and its row within a group
+        uint32_t* put = sc + sr * PITCH + st;                                // group k: + k * RG * PITCH; row 63 of the last group is written, not read
+        const uint32_t* get = sc + (sr == RG - 1 ? sr - 1 : sr) * PITCH + st;  // ... and reads row 62's index instead (the same address as its neighbour)
+        // the three phases exchange through the wave's own LDS scratch: LDS operations of a wave complete in order, the fence keeps the
+        // compiler from moving them across
+        auto phase = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+        auto chunk = [&](const int w0, const bool guarded) {
+            if (lane < 63) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                int t = (int)__builtin_roundf(sCorX);
-                const int xCor = t < 0 ? 0 : (t > iw ? iw : t);
-                t = (int)__builtin_roundf(sCorY);
-                const int yCor = t < 0 ? 0 : (t > ih ? ih : t);
-                g8[u] = pdxy[(uint32_t)(__mul24(yCor, rw) + xCor)];  // coordinates are clamped: reads past the line's end are harmless (24-bit multiply: a full-rate instruction)
-                sCorX = PSL_FADD(sCorX, dL0);
-                sCorY = PSL_FADD(sCorY, dL1);
+                for (int u = 0; u < T; ++u) {
+                    if (guarded && w0 + u >= len) break;
+                    mine[u] = next_pixel();
+                }
             }
+            phase();
+            if (!guarded || w0 + st < len) {
+                uint32_t g[NG];
+#pragma unroll
+                for (int k = 0; k < NG; ++k) g[k] = pix[(k == NG - 1 ? get : put)[k * RG * PITCH]];  // every load of the chunk before the first wait
+#pragma unroll
+                for (int k = 0; k < NG; ++k) put[k * RG * PITCH] = g[k];
+            }
+            phase();
+            if (lane < 63) {
+#pragma unroll
+                for (int u = 0; u < T; ++u) {
+                    if (guarded && w0 + u >= len) break;
+                    sample(mine[u]);
+                }
+            }
+            phase();
         };
-        auto sample = [&](const short2 g) {
-            const float gx = (float)g.x, gy = (float)g.y;
-            const float gDL = PSL_FADD(PSL_FMUL(gx, dL0), PSL_FMUL(gy, dL1));
-            const float gDO = PSL_FADD(PSL_FMUL(gx, dO0), PSL_FMUL(gy, dO1));
-            pL = PSL_FADD(pL, __builtin_fmaxf(gDL, 0.0f)); nL = PSL_FSUB(nL, __builtin_fminf(gDL, 0.0f));
-            pO = PSL_FADD(pO, __builtin_fmaxf(gDO, 0.0f)); nO = PSL_FSUB(nO, __builtin_fminf(gDO, 0.0f));
-        };
+        int w0 = 0;
+        for (; w0 + T <= len; w0 += T) chunk(w0, false);
+        if (w0 < len) chunk(w0, true);
+    } else
+#endif
+    if (lane < 63) {
         // The gathers of a row do not depend on each other: fetch 8 samples ahead (the coordinate chain is plain
         // float adds), then accumulate them in the reference's order.  One sample per wait made the kernel
         // latency-bound (90 % of the wave cycles in s_waitcnt).
+        auto fetch8 = [&](uint32_t* g8) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) g8[u] = pix[next_pixel()];
+        };
         int w0 = 0;
         for (; w0 + 8 <= len; w0 += 8) {
-            short2 g8[8];
+            uint32_t g8[8];
             fetch8(g8);
 #pragma unroll
             for (int u = 0; u < 8; ++u) sample(g8[u]);
         }
         if (w0 < len) {
-            short2 g8[8];
+            uint32_t g8[8];
             fetch8(g8);
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 if (w0 + u < len) sample(g8[u]);
         }
+    }
+    if (lane < 63) {
         const float coef = P.gaussG[lane];
         pL = PSL_FMUL(coef, pL); nL = PSL_FMUL(coef, nL); pO = PSL_FMUL(coef, pO); nO = PSL_FMUL(coef, nO);
-        float* r = s_row[wave][lane];
+        float* r = s_row[lane];
         r[0] = pL; r[1] = nL; r[2] = PSL_FMUL(pL, pL); r[3] = PSL_FMUL(nL, nL);
         r[4] = pO; r[5] = nO; r[6] = PSL_FMUL(pO, pO); r[7] = PSL_FMUL(nO, nO);
     }
@@ -988,7 +1057,7 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
     // b's three-band window is hID = WB * (b - 1) + k, and its coefficient is gaussL[k] (the reference's own == b / b + 1 / b - 1 cases are
     // gaussL[hID % WB + WB / 2 * WB / 0]): uniform in k, so the unrolled loop reads it from the kernel argument.  A chain adds its rows hID ascending.
     const int a = lane & 7;
-    const float* rw = &s_row[wave][0][0];
+    const float* rw = &s_row[0][0];
     auto band_chain = [&](const int b) {
         float acc = 0;
         const int base = (WB * (b - 1)) * 8 + a;
@@ -1025,7 +1094,7 @@ __global__ __launch_bounds__(256, PSL_LBD_WAVES) void k_lbd(LineParams P, const 
     // Normalisation, one element per lane (lanes 0 - 7 also hold elements 64 - 71).  The products are formed in parallel; only the additions run in
     // the reference's order: lane 0 adds the 36 squares of the means (bands ascending, entries 0 - 3), lane 1 beside it those of the deviations
     // (entries 4 - 7), lane 0 the 72 of the final sum.  The squares sit in s_row[wave], whose rows are no longer needed.
-    float* sq = &s_row[wave][0][0];
+    float* sq = &s_row[0][0];
     float v0 = s_des[wave][lane], v1 = lane < 8 ? s_des[wave][64 + lane] : 0.f;
     sq[lane] = PSL_FMUL(v0, v0);
     if (lane < 8) sq[64 + lane] = PSL_FMUL(v1, v1);

@@ -432,6 +432,8 @@ struct pslfe_line {
         {
             PSL_STAGE_BEGIN_ON(ctx, "line.lbd", st);
             const int per_frame = std::min(P.maxkl, std::max(P.nfeatures, 1));
+            // plain grid: with all line blocks of a frame on one XCD (grid (8, blocks, ceil(n / 8))) the row-major kernel gained 1.1 of 16.4 ms,
+            // the kernel with the step-major path nothing (profiles/lbd_layout_ab.log)
             k_lbd<<<dim3((per_frame + 3) / 4, n), 256, 0, st>>>(P, p.dxy, p.kls, p.nkl, p.ldesc, want_float ? p.fdesc : nullptr);
             PSL_STAGE_END_ON(ctx, "line.lbd", st);
         }
