@@ -1421,6 +1421,85 @@ int pslfe_pnp_solve(pslfe_ctx* ctx, const PslPnpRow* rows, int nrows, const PslC
 int pslfe_pnp_mp_index_from_inliers_device(pslfe_ctx* ctx, int ncand, const int32_t* d_mp_index, const int32_t* d_row_kp, const uint8_t* d_inliers,
                                            const int32_t* d_nrows, int rstride, int kpstride, int32_t* d_mp_index_out);
 
+/* ---- Monocular map initialisation: Initializer (src/Initializer.cc) -----------------------------------------------------------------
+ * The step of Tracking::MonocularInitialization (src/Tracking.cc:659-760) behind SearchForInitialization (:696): the Initializer
+ * constructor (src/Initializer.cc:33-42) and Initialize (:44-121) with everything it calls: max_its sets of eight matches, a homography
+ * and a fundamental matrix from each set, both scored on every match, the winner of the ratio RH decomposed into 8 or 4 motion
+ * hypotheses, each triangulated over the winner's inliers.  Parity: "HIP == host compile of the same header == restatement", parity
+ * with OpenCV unpinned (DESIGN.md §3 lists the readings of the float SVD, the Mat products, inv, determinant and norm).  rand() is
+ * glibc's generator; pair p is seeded as srand(seed0 + p) and takes 8 * max_its draws (the reference seeds once per process with 0 and
+ * shares the stream: seed0 = 0, p = 0 is the first Initialize of a process; convention H7).
+ * Cases the reference leaves undefined:
+ *   - fewer than 8 matches: nothing is drawn or solved, status 0, nmatches the count, every other field 0 (the three indices -1);
+ *   - no model: neither search has a hypothesis with a score above 0.0 (identical keypoints give sX = inf and NaN scores): status
+ *     bit 2, nothing is reconstructed (the reference would hand an empty cv::Mat to ReconstructF);
+ *   - a NaN in vCosParallax is ordered by its bit pattern: with the sign bit set below -inf, with it clear above +inf (std::sort
+ *     is undefined there);
+ *   - a match that names a keypoint outside frame 2 (matches12[i] >= nkeys2): status PSLFE_E_INVALID for that pair.
+ *   FindFundamental sizes its vectors from the still empty vbMatchesInliers (:178); CheckFundamental resizes them (:404). */
+typedef struct PslInitResult {   /* per pair */
+    int32_t status;            /* bit 0: Initialize returned true; bit 1: the homography branch was taken (RH > 0.40, :115); bit 2: no
+                                  model; or PSLFE_E_CAPACITY / PSLFE_E_INVALID for a count above its stride / a negative count or a match
+                                  outside frame 2 */
+    int32_t nmatches;          /* mvMatches12.size() (:65) */
+    float SH, SF, RH;          /* :101, :112 */
+    int32_t best_it_h, best_it_f;   /* the iteration whose H / F won (:165, :216), -1: none */
+    int32_t inliers_h, inliers_f;   /* set flags of vbMatchesInliersH / F */
+    float H21[9], F21[9];      /* the winners, zeros without one */
+    int32_t ngood[8];          /* nGood of every CheckRT (:494-497: four; :703: eight) */
+    float parallax[8];
+    int32_t best_hypothesis;   /* ReconstructH: bestSolutionIdx (:709); ReconstructF: the hypothesis of the else-if ladder (:523-567),
+                                  -1 when the ladder is not reached */
+    float R21[9], t21[3];      /* zeros unless bit 0 */
+    int32_t ntriangulated;     /* set flags of vbTriangulated */
+} PslInitResult;
+#ifdef __cplusplus
+static_assert(sizeof(PslInitResult) == 228, "Initializer POD");
+#else
+_Static_assert(sizeof(PslInitResult) == 228, "Initializer POD");
+#endif
+/* == mvSets (src/Initializer.cc:77-97) on the host: srand(seed), then max_its sets of 8 from RandomInt(0, size - 1) on
+ *    vAvailableIndices with swap-with-back removal; sets [max_its][8].  N < 8, max_its < 0 or NULL sets: PSLFE_E_INVALID.  Touches no
+ *    device. */
+int pslfe_init_sets(uint32_t seed, int N, int max_its, int32_t* sets);
+/* == Initializer(ReferenceFrame, sigma, max_its) + Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated)
+ *    (src/Initializer.cc:33-121) for npairs independent frame pairs in one launch, HBM to HBM.  Pair p: d_nkeys1[p] keypoints of the
+ *    reference frame at d_keys1 + p * kstride * key_stride_bytes and d_nkeys2[p] of the current frame at d_keys2 + ... ; a keypoint is
+ *    two floats (mvKeysUn[i].pt.x, .y) at the start of an element of key_stride_bytes (a multiple of 4, >= 8): plain float pairs or
+ *    PslKeyPoint records.  d_matches12 + p * mstride: vMatches12, one entry per reference keypoint (-1: none).  cam: fx, fy, cx, cy
+ *    (mK, :35); sigma, max_its: the constructor's (Tracking: 1.0, 200).  minParallax = 1.0 and minTriangulated = 50 as at :116-118.
+ *    Outputs: d_res[p]; d_p3d [npairs][mstride][3] (vP3D) and d_triangulated [npairs][mstride] bytes (vbTriangulated), indexed by
+ *    reference keypoint, the first d_nkeys1[p] entries of a pair written: zeros unless Initialize returned true; d_matches12_out
+ *    (may be NULL) [npairs][mstride]: mvIniMatches after src/Tracking.cc:712-719, i.e. vMatches12 with -1 where a match was not
+ *    triangulated when Initialize returned true, vMatches12 otherwise.  Bytes beyond the counts are not touched.
+ *    d_nkeys1[p] or d_nkeys2[p] > kstride, d_nkeys1[p] > mstride: status = PSLFE_E_CAPACITY; a negative count, a match >= d_nkeys2[p]:
+ *    PSLFE_E_INVALID; nothing is clamped, nothing is solved, no output byte of that pair but its record is written (other fields 0).
+ *    npairs < 0, kstride < 0, mstride < 0, max_its < 1, a NaN sigma, a bad key_stride_bytes, a NULL array with a non-zero count:
+ *    PSLFE_E_INVALID; npairs == 0: PSLFE_OK, nothing is done.  Asynchronous on the context's stream; per-call buffers come from the
+ *    scratch arena. */
+int pslfe_init_initialize_device(pslfe_ctx* ctx, int npairs, const void* d_keys1, const int32_t* d_nkeys1, const void* d_keys2,
+                                 const int32_t* d_nkeys2, int key_stride_bytes, int kstride, const int32_t* d_matches12, int mstride,
+                                 const PslCamera* cam, float sigma, int max_its, uint32_t seed0, PslInitResult* d_res, float* d_p3d,
+                                 uint8_t* d_triangulated, int32_t* d_matches12_out);
+/* Same with the keypoints of frame slots: pair p has the reference frame in slot slot1[p] of f1 and the current frame in slot
+ * slot2[p] of f2 (host int arrays, as for pslfe_orb_search_for_initialization_device, whose d_matches12 this call takes as it is;
+ * mstride >= f1's capacity, PSLFE_E_INVALID otherwise; a slot that is not set: PSLFE_E_STATE).  Returns once the slot tables have been
+ * copied; the solver is queued on the context's stream. */
+int pslfe_init_initialize_frames_device(pslfe_frame* f1, const int32_t* slot1, pslfe_frame* f2, const int32_t* slot2, int npairs,
+                                        const int32_t* d_matches12, int mstride, const PslCamera* cam, float sigma, int max_its,
+                                        uint32_t seed0, PslInitResult* d_res, float* d_p3d, uint8_t* d_triangulated,
+                                        int32_t* d_matches12_out);
+/* One pair, host arrays: keys1 [n1][2], keys2 [n2][2] floats, matches12 [n1]; res, p3d [n1][3], triangulated [n1]; returns after the
+ * results have arrived.  A negative status of the pair is also the return value. */
+int pslfe_init_initialize(pslfe_ctx* ctx, const float* keys1, int n1, const float* keys2, int n2, const int32_t* matches12,
+                          const PslCamera* cam, float sigma, int max_its, uint32_t seed, PslInitResult* res, float* p3d,
+                          uint8_t* triangulated);
+
+/* For the tests: the order of vCosParallax and the kernel's selection alone.  cosines [n >= 1] (host) -> keys [n] (the ordered keys:
+ * ascending keys are the stated order, NaNs included), *selected = the cosine at sorted index min(50, n - 1), *parallax = its
+ * acos * 180 / CV_PI (src/Initializer.cc:898-901).  Synchronous. */
+int pslfe_init_debug_select(pslfe_ctx* ctx, const float* cosines, int n, uint32_t* keys, float* selected, float* parallax);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

@@ -59,6 +59,12 @@ PNPROW_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("X", "<f4"), ("Y", "<f4"),
 PNPRESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("inliers", "<i4"), ("best_inliers", "<i4"), ("min_inliers", "<i4"),
                             ("Tcw", POSE_DTYPE), ("best_Tcw", POSE_DTYPE)])
 assert PNPROW_DTYPE.itemsize == 24 and PNPRESULT_DTYPE.itemsize == 116
+# Initializer (include/pslfe.h: PslInitResult)
+INITRESULT_DTYPE = np.dtype([("status", "<i4"), ("nmatches", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"), ("best_it_h", "<i4"),
+                             ("best_it_f", "<i4"), ("inliers_h", "<i4"), ("inliers_f", "<i4"), ("H21", "<f4", (9,)), ("F21", "<f4", (9,)),
+                             ("ngood", "<i4", (8,)), ("parallax", "<f4", (8,)), ("best_hypothesis", "<i4"), ("R21", "<f4", (9,)),
+                             ("t21", "<f4", (3,)), ("ntriangulated", "<i4")])
+assert INITRESULT_DTYPE.itemsize == 228
 
 
 def pose(Tcw):
@@ -1059,6 +1065,85 @@ class PnPsolver:
         finally:
             for d in (d_res, d_flags, d_best):
                 ctx.device_free(d)
+
+
+class Initializer:
+    """== ORB_SLAM2::Initializer (src/Initializer.cc) of one reference frame, with the reference's method names.  The constructor takes
+    what the reference's takes from ReferenceFrame (:33-42): mvKeysUn as float32 [n1][2] (x, y) and K (a CAMERA_DTYPE record; fx, fy,
+    cx, cy are read), sigma = 1.0, iterations = 200.  rand() is glibc's generator seeded with `seed` at every Initialize (the reference
+    seeds once per process with 0: seed 0 is its first Initialize).  Parity with OpenCV is unpinned."""
+
+    def __init__(self, ReferenceKeys, K, sigma=1.0, iterations=200, seed=0, ctx=None):
+        self.ctx = ctx or default_context()
+        self.keys1 = np.ascontiguousarray(ReferenceKeys, np.float32).reshape(-1, 2)
+        self.cam = np.ascontiguousarray(K, CAMERA_DTYPE).reshape(1)
+        self.sigma, self.max_its, self.seed = float(sigma), int(iterations), int(seed) & 0xffffffff
+        self.result = np.zeros((), INITRESULT_DTYPE)   # of the last call
+
+    def Initialize(self, CurrentKeys, vMatches12):
+        """-> (bool, R21 float32 [3][3], t21 float32 [3], vP3D float32 [n1][3], vbTriangulated bool [n1]); CurrentKeys = CurrentFrame's
+        mvKeysUn as float32 [n2][2], vMatches12 int32 [n1]"""
+        keys2 = np.ascontiguousarray(CurrentKeys, np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(vMatches12, np.int32).reshape(-1)
+        n1, n2 = len(self.keys1), len(keys2)
+        if len(m) != n1:
+            raise PslfeError("Initializer: vMatches12 has one entry per reference keypoint")
+        res = np.zeros(1, INITRESULT_DTYPE)
+        p3d, tri = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8)
+        _check(lib().pslfe_init_initialize(self.ctx._h, _ptr(self.keys1) if n1 else None, C.c_int(n1), _ptr(keys2) if n2 else None, C.c_int(n2),
+                                           _ptr(m) if n1 else None, _ptr(self.cam), C.c_float(self.sigma), C.c_int(self.max_its),
+                                           C.c_uint32(self.seed), _ptr(res), _ptr(p3d) if n1 else None, _ptr(tri) if n1 else None),
+               "pslfe_init_initialize")
+        self.result = res[0].copy()
+        return (bool(res[0]["status"] & 1), res[0]["R21"].reshape(3, 3).copy(), res[0]["t21"].copy(), p3d[:n1], tri[:n1].astype(bool))
+
+    @staticmethod
+    def Sets(seed, N, iterations):
+        """mvSets (:77-97) of a pair with N matches -> int32 [iterations][8]; no device is touched"""
+        s = np.zeros((max(iterations, 1), 8), np.int32)
+        _check(lib().pslfe_init_sets(C.c_uint32(int(seed) & 0xffffffff), C.c_int(N), C.c_int(iterations), _ptr(s)), "pslfe_init_sets")
+        return s[:max(iterations, 0)]
+
+    @staticmethod
+    def DebugSelect(cosines, ctx=None):
+        """For the tests: a vCosParallax (float32 [n >= 1]) through the kernel's ordered keys and radix selection -> (keys uint32 [n],
+        the cosine at sorted index min(50, n - 1), its parallax in degrees)"""
+        ctx = ctx or default_context()
+        c = np.ascontiguousarray(cosines, np.float32).reshape(-1)
+        keys, sel, par = np.zeros(max(len(c), 1), np.uint32), np.zeros(1, np.float32), np.zeros(1, np.float32)   # arrays: a NaN keeps its bits
+        _check(lib().pslfe_init_debug_select(ctx._h, _ptr(c) if len(c) else None, C.c_int(len(c)), _ptr(keys), _ptr(sel), _ptr(par)),
+               "pslfe_init_debug_select")
+        return keys[:len(c)], sel[0], par[0]
+
+    @staticmethod
+    def InitializeDevice(npairs, d_keys1, d_nkeys1, d_keys2, d_nkeys2, key_stride_bytes, kstride, d_matches12, mstride, K, d_res, d_p3d,
+                         d_triangulated, d_matches12_out=0, sigma=1.0, iterations=200, seed0=0, ctx=None):
+        """Initialize for npairs independent frame pairs in one launch, HBM to HBM, asynchronous; all d_* are device addresses (ints).
+        d_res INITRESULT_DTYPE [npairs]; d_p3d float32 [npairs][mstride][3] and d_triangulated bytes [npairs][mstride] by reference
+        keypoint; d_matches12_out (may be 0) = mvIniMatches after src/Tracking.cc:712-719.  status = PSLFE_E_CAPACITY (-4) for a count
+        above its stride, PSLFE_E_INVALID (-1) for a negative count or a match outside frame 2."""
+        ctx = ctx or default_context()
+        cam = np.ascontiguousarray(K, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_init_initialize_device(
+            ctx._h, C.c_int(npairs), C.c_void_p(d_keys1 or None), C.c_void_p(d_nkeys1 or None), C.c_void_p(d_keys2 or None),
+            C.c_void_p(d_nkeys2 or None), C.c_int(key_stride_bytes), C.c_int(kstride), C.c_void_p(d_matches12 or None), C.c_int(mstride), _ptr(cam),
+            C.c_float(sigma), C.c_int(iterations), C.c_uint32(int(seed0) & 0xffffffff), C.c_void_p(d_res or None), C.c_void_p(d_p3d or None),
+            C.c_void_p(d_triangulated or None), C.c_void_p(d_matches12_out or None)), "pslfe_init_initialize_device")
+
+    @staticmethod
+    def InitializeFramesDevice(f1, slot1, f2, slot2, d_matches12, mstride, K, d_res, d_p3d, d_triangulated, d_matches12_out=0, sigma=1.0,
+                               iterations=200, seed0=0):
+        """The same with the keypoints of frame slots, straight behind search_for_initialization_device with its d_matches12: pair p =
+        (f1 slot slot1[p], f2 slot slot2[p]); mstride >= f1's capacity."""
+        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1)
+        s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+        if len(s1) != len(s2):
+            raise ValueError("slot1 and slot2 differ in length")
+        cam = np.ascontiguousarray(K, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_init_initialize_frames_device(
+            f1._h, _ptr(s1), f2._h, _ptr(s2), C.c_int(len(s1)), C.c_void_p(d_matches12 or None), C.c_int(mstride), _ptr(cam), C.c_float(sigma),
+            C.c_int(iterations), C.c_uint32(int(seed0) & 0xffffffff), C.c_void_p(d_res or None), C.c_void_p(d_p3d or None),
+            C.c_void_p(d_triangulated or None), C.c_void_p(d_matches12_out or None)), "pslfe_init_initialize_frames_device")
 
 
 class LINEextractor:

@@ -1500,5 +1500,72 @@ private:
     std::vector<uint8_t> bestFlags_, rowFlags_;
 };
 
+// == ORB_SLAM2::Initializer (src/Initializer.cc) of one reference frame: the constructor takes what the reference's takes from the
+// frame (:33-42): its undistorted keypoints (x, y pairs) and K; sigma = 1.0 and iterations = 200 as in include/Initializer.h.
+// rand() is glibc's generator seeded with `seed` at every Initialize (the reference seeds once per process with 0: seed 0 is its first
+// Initialize).  Parity with OpenCV is unpinned.
+class Initializer {
+public:
+    Initializer(Context& ctx, std::vector<float> referenceKeysXY, const PslCamera& K, float sigma = 1.0f, int iterations = 200, uint32_t seed = 0)
+        : ctx_(&ctx), keys1_(std::move(referenceKeysXY)), cam_(K), sigma_(sigma), maxIts_(iterations), seed_(seed) {
+        if (keys1_.size() % 2) throw Error(PSLFE_E_INVALID, "Initializer: an odd number of coordinates");
+        std::memset(&res_, 0, sizeof(res_));
+    }
+    // bool Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) (:44-121): currentKeysXY = CurrentFrame.mvKeysUn as
+    // x, y pairs; R21 [9] row-major and t21 [3]; vP3D [n1][3] flattened
+    bool Initialize(const std::vector<float>& currentKeysXY, const std::vector<int32_t>& vMatches12, float* R21, float* t21,
+                    std::vector<float>& vP3D, std::vector<bool>& vbTriangulated) {
+        const int n1 = (int)(keys1_.size() / 2), n2 = (int)(currentKeysXY.size() / 2);
+        if ((int)vMatches12.size() != n1) throw Error(PSLFE_E_INVALID, "Initializer: vMatches12 has one entry per reference keypoint");
+        std::vector<uint8_t> tri((size_t)n1 ? (size_t)n1 : 1, 0);
+        vP3D.assign(3 * (size_t)n1, 0.f);
+        check(pslfe_init_initialize(ctx_->get(), keys1_.data(), n1, currentKeysXY.data(), n2, vMatches12.data(), &cam_, sigma_, maxIts_, seed_,
+                                    &res_, vP3D.data(), tri.data()),
+              "pslfe_init_initialize");
+        vbTriangulated.assign((size_t)n1, false);
+        for (int i = 0; i < n1; ++i) vbTriangulated[(size_t)i] = tri[(size_t)i] != 0;
+        for (int k = 0; k < 9; ++k) R21[k] = res_.R21[k];
+        for (int k = 0; k < 3; ++k) t21[k] = res_.t21[k];
+        return (res_.status & 1) != 0;
+    }
+    const PslInitResult& result() const { return res_; }   // of the last call
+
+    // mvSets (:77-97) of a pair with N matches: [iterations][8]
+    static std::vector<int32_t> Sets(uint32_t seed, int N, int iterations) {
+        std::vector<int32_t> s(8 * (size_t)(iterations > 0 ? iterations : 0) + 1);
+        check(pslfe_init_sets(seed, N, iterations, s.data()), "pslfe_init_sets");
+        s.resize(8 * (size_t)iterations);
+        return s;
+    }
+    // K pairs in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_init_initialize_device
+    static void InitializeDevice(Context& ctx, int npairs, const void* d_keys1, const int32_t* d_nkeys1, const void* d_keys2, const int32_t* d_nkeys2,
+                                 int keyStrideBytes, int kstride, const int32_t* d_matches12, int mstride, const PslCamera& K, float sigma,
+                                 int iterations, uint32_t seed0, PslInitResult* d_res, float* d_p3d, uint8_t* d_triangulated,
+                                 int32_t* d_matches12Out) {
+        check(pslfe_init_initialize_device(ctx.get(), npairs, d_keys1, d_nkeys1, d_keys2, d_nkeys2, keyStrideBytes, kstride, d_matches12, mstride, &K,
+                                           sigma, iterations, seed0, d_res, d_p3d, d_triangulated, d_matches12Out),
+              "pslfe_init_initialize_device");
+    }
+    // The same with the keypoints of frame slots, straight behind ORBmatcher::SearchForInitializationDevice with its d_matches12:
+    // pair p = (f1 slot slot1[p], f2 slot slot2[p]); mstride >= f1's capacity.  pslfe_init_initialize_frames_device
+    static void InitializeFramesDevice(FrameGrid& f1, const std::vector<int32_t>& slot1, FrameGrid& f2, const std::vector<int32_t>& slot2,
+                                       const int32_t* d_matches12, int mstride, const PslCamera& K, float sigma, int iterations, uint32_t seed0,
+                                       PslInitResult* d_res, float* d_p3d, uint8_t* d_triangulated, int32_t* d_matches12Out) {
+        if (slot1.size() != slot2.size()) throw Error(PSLFE_E_INVALID, "Initializer: slot1 and slot2 differ in length");
+        check(pslfe_init_initialize_frames_device(f1.get(), slot1.data(), f2.get(), slot2.data(), (int)slot1.size(), d_matches12, mstride, &K, sigma,
+                                                  iterations, seed0, d_res, d_p3d, d_triangulated, d_matches12Out),
+              "pslfe_init_initialize_frames_device");
+    }
+
+private:
+    Context* ctx_;
+    std::vector<float> keys1_;
+    PslCamera cam_;
+    float sigma_;
+    int maxIts_;
+    uint32_t seed_;
+    PslInitResult res_;
+};
+
 }  // namespace pslfe
 #endif
