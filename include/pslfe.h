@@ -933,7 +933,8 @@ typedef struct PslLineFuseQuery {
 } PslLineFuseQuery;
 /* == the search of LSDmatcher::Fuse add_src/LSDmatcher.cpp:933-958: KeyFrame::GetLinesInArea(u1, v1, u2, v2, radius,
  *    TH = 0.998) src/KeyFrame.cc:857-891 over kls = pKF->mvKeyLines, octaves level-1 .. level, smallest distance to
- *    desc row idx, first on ties; best_dist = 256 when none.  `desc` (ndesc rows) is the matrix the caller reads rows
+ *    desc row idx, first on ties; best_idx = -1, best_dist = 256 when none - a keyline at distance 256 is none, the
+ *    reference starts from bestDist = 256 and takes dist < bestDist.  `desc` (ndesc rows) is the matrix the caller reads rows
  *    from: the reference indexes pKF->mDescriptors (the ORB matrix) with the line index at :945; a line without a row is
  *    skipped. */
 int pslfe_kf_line_fuse_best(pslfe_kf* k, const PslKeyLine* kls, int n, const uint8_t* desc, int ndesc,

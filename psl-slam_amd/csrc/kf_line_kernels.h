@@ -71,8 +71,10 @@ __device__ __forceinline__ void psl_line_fuse_row(const Src& S, int n, int ndesc
     }
     best = psl_wave_min_u32(best);
     if (lane == 0) {
-        *best_idx = best == PSL_KEY_INF ? -1 : (int)(best & 0xffffu);
-        *best_dist = best == PSL_KEY_INF ? 256 : (int)(best >> 16);
+        // bestDist starts at 256 and moves on dist < bestDist only (:933-958): a candidate at distance 256 is no candidate
+        const bool none = best >= (256u << 16);
+        *best_idx = none ? -1 : (int)(best & 0xffffu);
+        *best_dist = none ? 256 : (int)(best >> 16);
     }
 }
 

@@ -170,6 +170,41 @@ def test_line_fuse_keyframes(ns, short):
     assert (bi[np.array(ns) == 0] == -1).all() and (bd[np.array(ns) == 0] == 256).all()
 
 
+def test_line_fuse_keyframes_complement_descriptor():
+    """`dist < bestDist` from bestDist = 256 (add_src/LSDmatcher.cpp:933-958): a map line whose descriptor is the complement of every
+    candidate's leaves (-1, 256), one bit less (k, 255) - in the keyframe staged in LDS (40 keylines) and in the one read from global
+    memory (513).  Every keyline of a keyframe carries one descriptor, so whoever passes the geometric gates is at the chosen distance."""
+    import oracle_lib
+    import psl_slam_amd as P
+    from window_cases import T
+    ns = (40, 513)
+    rng = np.random.default_rng(77)
+    views = kc.views()[VIEWS3][:2]
+    cam = kc.camera()
+    kls = [lc.keylines(n, rng) for n in ns]
+    D = T(100)
+    descs = [np.tile(D, (n, 1)) for n in ns]
+    near = ~D
+    near[0] ^= 1                                               # 255 bits differ
+    ml = np.concatenate([lc.lines_onto(kls[k][:3], descs[k][:3], views[k]["Tcw"], cam, rng, flips=1)[0] for k in range(2)])
+    mld = np.stack([~D, near, D] * 2)
+    want, _, wstop, _ = lc.restate_line_project(views, ml, cam, lc.BOUNDS, lc.SCALE_LINE, TH, None)
+    kf = P.KeyFrameMatcher()
+    bi, bd, rows, stop = kf.LineFuseKeyFrames(views["Tcw"], kls, descs, ml, mld, *_args())
+    assert rows.tobytes() == want.tobytes() and (stop == wstop).all() and (stop == len(ml)).all()
+    for k in range(2):
+        rbi, rbd = oracle_lib.line_fuse_best(kls[k], descs[k], want[k], mld)
+        np.testing.assert_array_equal(bi[k], rbi, err_msg=f"keyframe {k}")
+        np.testing.assert_array_equal(bd[k], rbd, err_msg=f"keyframe {k}")
+        obi, obd = kf.LineFuse(kls[k], descs[k], want[k], mld)
+        np.testing.assert_array_equal(bi[k], obi)
+        np.testing.assert_array_equal(bd[k], obd)
+        zi, zd = oracle_lib.line_fuse_best(kls[k], descs[k], want[k], np.tile(D, (len(ml), 1)))
+        own = slice(3 * k, 3 * k + 3)                          # the lines laid onto this keyframe's keylines have candidates
+        assert (zi[own] >= 0).all() and (zd[own] == 0).all()
+        assert bi[k][own].tolist() == [-1, zi[own][1], zi[own][2]] and bd[k][own].tolist() == [256, 255, 0]
+
+
 def _tri_scene(n1, seed=41):
     rng = np.random.default_rng(seed)
     base = rng.integers(0, 256, (170, 32), dtype=np.uint8)

@@ -11,7 +11,7 @@ and the cell range of a window follow from the construction without rounding (Po
 zero; GetFeaturesInArea: cells floor((u - r) / 16) .. ceil((u + r) / 16), visited column by column, a cell in ascending index).
 
 Other searches that use the shared matcher primitives (pslfe_kf, pslfe_mono, pslfe_loop, pslfe_stereo) can take the same arrays:
-a case is just (kps, desc, uright, bounds, q, qd, taken)."""
+a case is just (kps, desc, uright, bounds, q, qd, taken); tests/kf_cases.py does so for pslfe_kf."""
 import numpy as np
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
