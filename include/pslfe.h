@@ -154,6 +154,14 @@ int pslfe_orb_debug_level_size(pslfe_orb* orb, int level, int* w, int* h);
 int pslfe_orb_debug_level_image(pslfe_orb* orb, int frame, int level, int blurred, uint8_t* out, int out_stride);
 int pslfe_orb_debug_candidates(pslfe_orb* orb, int frame, int level, int32_t* xys, int cap, int* n);
 int pslfe_orb_debug_level_keypoints(pslfe_orb* orb, int frame, int level, int32_t* xys, int cap, int* n);
+/* The way in for hand-made keypoints (tests/stereo_cases.py): after an extraction, the n host keypoints and descriptors
+ * (n x 32 bytes) replace the results and the count of frame `frame` of the last batch; the pyramid stays as extracted.  The copy
+ * is ordered on the context's stream (work queued before it reads the old arrays, work queued after it the new ones) and has
+ * completed on return.  pslfe_orb_fetch, pslfe_orb_results_device and every consumer of the handle (pslfe_frame_set_from_orb*)
+ * then see the new arrays, until the next extraction.  Nothing is checked about the keypoints themselves: the consumer's own
+ * conventions for octaves and coordinates apply.  PSLFE_E_STATE before any extraction; PSLFE_E_INVALID for a NULL argument, a
+ * frame outside the last batch or n < 0; PSLFE_E_CAPACITY for n > pslfe_orb_max_keypoints.  Nothing calls it at run time. */
+int pslfe_orb_debug_set_results(pslfe_orb* orb, int frame, const PslKeyPoint* kps, const uint8_t* desc, int n);
 
 /* ---- line extractor ---------------------------------------------------------------------------- */
 typedef struct pslfe_line pslfe_line;  /* == LINEextractor object                                  */

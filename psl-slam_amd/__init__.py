@@ -295,6 +295,15 @@ class ORBextractor:
     def debug_level_keypoints(self, frame, level):
         return self._debug_xys(lib().pslfe_orb_debug_level_keypoints, frame, level)
 
+    def debug_set_results(self, frame, kps, desc):
+        """pslfe_orb_debug_set_results: hand-made keypoints / descriptors as the results of frame `frame` of the last batch (the
+        pyramid stays as extracted); fetch() and every consumer of the handle then see them."""
+        n = len(kps)
+        k = np.zeros(max(n, 1), KEYPOINT_DTYPE)
+        d = np.zeros((max(n, 1), 32), np.uint8)
+        k[:n], d[:n] = kps, np.asarray(desc, np.uint8).reshape(n, 32)
+        _check(lib().pslfe_orb_debug_set_results(self._h, C.c_int(frame), _ptr(k), _ptr(d), C.c_int(n)), "pslfe_orb_debug_set_results")
+
     def close(self):
         if self._h:
             lib().pslfe_orb_destroy(self._h)

@@ -522,4 +522,24 @@ int pslfe_orb_debug_level_keypoints(pslfe_orb* orb, int frame, int level, int32_
     return PSLFE_OK;
 }
 
+// The way in for hand-made keypoints (tests/stereo_cases.py): frame `frame` of the last batch gets the host arrays as its results.
+int pslfe_orb_debug_set_results(pslfe_orb* orb, int frame, const PslKeyPoint* kps, const uint8_t* desc, int n) {
+    PSL_REQUIRE(orb && kps && desc, PSLFE_E_INVALID, "pslfe_orb_debug_set_results: NULL argument");
+    PSL_REQUIRE(orb->last_nframes > 0, PSLFE_E_STATE, "pslfe_orb_debug_set_results: no batch extracted yet");
+    PSL_REQUIRE(frame >= 0 && frame < orb->last_nframes, PSLFE_E_INVALID, "pslfe_orb_debug_set_results: frame %d of %d", frame, orb->last_nframes);
+    PSL_REQUIRE(n >= 0, PSLFE_E_INVALID, "pslfe_orb_debug_set_results: %d keypoints", n);
+    PSL_REQUIRE(n <= orb->P.out_cap, PSLFE_E_CAPACITY, "pslfe_orb_debug_set_results: %d keypoints, capacity %d", n, orb->P.out_cap);
+    PSL_HIP(hipSetDevice(orb->ctx->device));
+    hipStream_t st = orb->ctx->stream;
+    const size_t o = (size_t)frame * orb->P.out_cap;
+    const int cnt = n;
+    if (n > 0) {
+        PSL_HIP(hipMemcpyAsync(orb->d_kps + o, kps, (size_t)n * sizeof(PslKeyPoint), hipMemcpyHostToDevice, st));
+        PSL_HIP(hipMemcpyAsync(orb->d_desc + o * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    }
+    PSL_HIP(hipMemcpyAsync(orb->d_counts + frame, &cnt, sizeof(int), hipMemcpyHostToDevice, st));
+    PSL_HIP(hipStreamSynchronize(st));   // the host arrays and cnt may go once this returns
+    return PSLFE_OK;
+}
+
 }  // extern "C"

@@ -66,6 +66,9 @@ def test_null_arguments_return_error_codes():
     assert lib.pslfe_debug_math(None, 0, C.c_size_t(4), None, None, None, None) == -1
     assert lib.pslfe_line_debug_nfa(None, 640, 480, 0, 1, None, 1, None, None, None, None, None) == -1
     assert b"pslfe_line_debug_nfa" in lib.pslfe_last_error()
+    # the way in for hand-made keypoints
+    assert lib.pslfe_orb_debug_set_results(None, 0, pa, pa, 0) == -1
+    assert b"pslfe_orb_debug_set_results" in lib.pslfe_last_error()
     lib.pslfe_orb_destroy(None)
     lib.pslfe_frame_destroy(None)
     lib.pslfe_ctx_destroy(None)
