@@ -1509,6 +1509,67 @@ int pslfe_init_initialize(pslfe_ctx* ctx, const float* keys1, int n1, const floa
  * acos * 180 / CV_PI (src/Initializer.cc:898-901).  Synchronous. */
 int pslfe_init_debug_select(pslfe_ctx* ctx, const float* cosines, int n, uint32_t* keys, float* selected, float* parallax);
 
+/* ---- Local bundle adjustment: the point edges of Optimizer::LocalBundleAdjustment ---------------------------------------------------
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1025-1966, the call of LocalMapping::Run src/LocalMapping.cc:84) and the
+ * EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ part of LocalBundleAdjustmentAndInseclines (:1968-2534) from the optimiser's set-up on:
+ * the two rounds optimize(5) with Huber and optimize(10) without the outliers (:1642-1790, :2356-2456) over g2o's Levenberg, the
+ * Schur complement of BlockSolver<6,3> and a dense solve of the reduced camera system.  The VertexLIL vertices are not part of it.
+ * Building the lists (lLocalKeyFrames, lFixedCameras, lLocalMapPoints) and the tail (erase, SetPose, SetWorldPos) stay host code:
+ * INTEGRATION.md "LocalBundleAdjustment".  Parity: "HIP == host compile of the same header == restatement", bit for bit; parity with
+ * g2o itself is unpinned (DESIGN.md §3 lists what is pinned to g2o's text and what is this library's reading: the 3x3 inverse, the
+ * dense LDLt in place of LinearSolverEigen, the block order).  The abort flag inside optimize() is not modelled; rounds = 1 is
+ * bDoMore == false (:1645-1651).
+ * Blocks follow the caller's row order: a caller who wants g2o's index mapping passes keyframes and points in ascending mnId.
+ * Edges are given in the order the reference creates them (per map point, its observations in GetObservations() order): that
+ * order is the order of every sum. */
+typedef struct PslBaEdge {
+    int32_t point, kf;           /* rows of the problem's point and keyframe arrays */
+    float u, v, ur, inv_sigma2;  /* kpUn.pt, mvuRight (ur < 0: a monocular edge), mvInvLevelSigma2[kpUn.octave] */
+} PslBaEdge;
+typedef struct PslBaKeyFrame {
+    PslPose Tcw;                 /* GetPose() */
+    int32_t fixed;               /* mnId == 0 or a keyframe of lFixedCameras */
+} PslBaKeyFrame;
+typedef struct PslBaInfo {
+    int32_t status;              /* PSLFE_OK, PSLFE_E_CAPACITY or PSLFE_E_INVALID of this problem */
+    int32_t rounds;              /* rounds run: 0 (nothing to optimise or a refused problem), 1 or 2 */
+    int32_t iterations[2];
+    int32_t nerased;             /* set erase bytes */
+    double chi2_start, chi2_round1, chi2_end;   /* the active robust chi2 before round one, after it (under Huber) and after the last round */
+} PslBaInfo;
+#ifdef __cplusplus
+static_assert(sizeof(PslBaEdge) == 24 && sizeof(PslBaKeyFrame) == 52 && sizeof(PslBaInfo) == 48, "local BA PODs");
+#else
+_Static_assert(sizeof(PslBaEdge) == 24 && sizeof(PslBaKeyFrame) == 52 && sizeof(PslBaInfo) == 48, "local BA PODs");
+#endif
+typedef struct pslfe_ba pslfe_ba;
+/* The HBM workspaces of up to max_problems problems per launch, each of up to max_keyframes keyframes (free and fixed), max_points
+ * points and max_edges edges: per edge the Jacobian and error rows and the Hpl block, Hpp, Hll, Dinv, S (N x N doubles, N = 6 x
+ * max_keyframes), b, x, the candidate estimates and the four edge lists.  A count below 1 or a NULL argument: PSLFE_E_INVALID. */
+int pslfe_ba_create(pslfe_ctx* ctx, int max_problems, int max_keyframes, int max_points, int max_edges, pslfe_ba** out);
+void pslfe_ba_destroy(pslfe_ba* ba);
+/* == the optimisation of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1642-1790 with the vertices and edges of :1100-1640 given
+ *    as rows) for K independent problems in one launch, HBM to HBM.  Problem k has the keyframes d_kf[d_kf_off[k] .. d_kf_off[k+1]),
+ *    the points d_mp[d_mp_off[k] ..) (only x, y, z are read and written; the other fields are copied) and the edges
+ *    d_edges[d_edge_off[k] ..), whose point / kf are rows of that problem.  The offset arrays have K+1 ascending entries.  cam: fx, fy,
+ *    cx, cy, bf (host).  rounds: 2, or 1 for bDoMore == false.  Outputs, indexed as the inputs: d_kf_out (free keyframes: toCvMat of
+ *    the optimised SE3Quat, also when nothing moved them, as SetPose gets it; fixed ones: the input), d_mp_out, d_erase (one byte per
+ *    edge: vToErase, :1755, :1770), d_info[k].  d_kf_out may be d_kf and d_mp_out may be d_mp.
+ *    Per problem, in d_info[k].status, never a silent truncation: a count above the handle's caps: PSLFE_E_CAPACITY; descending or
+ *    negative offsets, an edge that names a row outside its problem, or a duplicate (point, keyframe) pair: PSLFE_E_INVALID; such a
+ *    problem leaves its outputs equal to its inputs (erase bytes 0), rounds = 0, and does not disturb its neighbours.  No free
+ *    keyframe, or no edge: PSLFE_OK with rounds = 0, outputs equal to inputs bit for bit (g2o is never called that way: the reference
+ *    always has pKF itself and its observations).
+ *    Whole call, before any device is touched: K < 0, rounds outside 1..2, K > max_problems, a NULL argument with K > 0:
+ *    PSLFE_E_INVALID; K == 0: PSLFE_OK, nothing is done.  Asynchronous on the context's stream. */
+int pslfe_ba_local_device(pslfe_ba* ba, int K, const PslBaKeyFrame* d_kf, const int32_t* d_kf_off, const PslMapPointGeom* d_mp,
+                          const int32_t* d_mp_off, const PslBaEdge* d_edges, const int32_t* d_edge_off, const PslCamera* cam, int rounds,
+                          PslBaKeyFrame* d_kf_out, PslMapPointGeom* d_mp_out, uint8_t* d_erase, PslBaInfo* d_info);
+/* One problem, host arrays; returns after the results have arrived.  Negative counts, NULL with a non-zero count, rounds outside
+ * 1..2: PSLFE_E_INVALID before any device is touched.  A negative status of the problem is also the return value. */
+int pslfe_ba_local(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const PslMapPointGeom* mp, int nmp, const PslBaEdge* edges, int nedges,
+                   const PslCamera* cam, int rounds, PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslBaInfo* info);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

@@ -65,6 +65,12 @@ INITRESULT_DTYPE = np.dtype([("status", "<i4"), ("nmatches", "<i4"), ("SH", "<f4
                              ("ngood", "<i4", (8,)), ("parallax", "<f4", (8,)), ("best_hypothesis", "<i4"), ("R21", "<f4", (9,)),
                              ("t21", "<f4", (3,)), ("ntriangulated", "<i4")])
 assert INITRESULT_DTYPE.itemsize == 228
+# local bundle adjustment (include/pslfe.h: PslBaEdge, PslBaKeyFrame, PslBaInfo)
+BAEDGE_DTYPE = np.dtype([("point", "<i4"), ("kf", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4")])
+BAKEYFRAME_DTYPE = np.dtype([("Tcw", POSE_DTYPE), ("fixed", "<i4")])
+BAINFO_DTYPE = np.dtype({"names": ["status", "rounds", "iterations", "nerased", "chi2_start", "chi2_round1", "chi2_end"],
+                         "formats": ["<i4", "<i4", ("<i4", (2,)), "<i4", "<f8", "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24, 32, 40], "itemsize": 48})
+assert BAEDGE_DTYPE.itemsize == 24 and BAKEYFRAME_DTYPE.itemsize == 52 and BAINFO_DTYPE.itemsize == 48
 
 
 def pose(Tcw):
@@ -666,10 +672,61 @@ def search_by_projection_map_device(frame, slot0, npairs, d_queries, d_qdesc, d_
         "pslfe_orb_search_by_projection_map_device")
 
 
+class BundleAdjuster:
+    """The HBM workspaces of the local bundle adjustment (pslfe_ba): up to max_problems problems per launch of up to max_keyframes
+    keyframes (free and fixed), max_points points and max_edges edges each."""
+
+    def __init__(self, max_problems, max_keyframes, max_points, max_edges, ctx=None):
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        _check(lib().pslfe_ba_create(self.ctx._h, C.c_int(max_problems), C.c_int(max_keyframes), C.c_int(max_points), C.c_int(max_edges),
+                                     C.byref(self._h)), "pslfe_ba_create")
+
+    def close(self):
+        if self._h:
+            lib().pslfe_ba_destroy.restype = None
+            lib().pslfe_ba_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Optimizer:
     """Optimizer::PoseOptimization src/Optimizer.cc:239-1023: the point edges (EdgeSE3ProjectXYZOnlyPose and
     EdgeStereoSE3ProjectXYZOnlyPose) and the LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the `lil` argument and the *Lil*
-    methods).  Parity with g2o itself is unpinned."""
+    methods); Optimizer::LocalBundleAdjustment :1025-1966, its point edges.  Parity with g2o itself is unpinned (DESIGN.md §3)."""
+
+    @staticmethod
+    def LocalBundleAdjustment(ba, kfs, mps, edges, cam, rounds=2):
+        """One problem, host arrays: kfs BAKEYFRAME_DTYPE[nkf] (lLocalKeyFrames, then lFixedCameras with fixed set), mps
+        MAPPOINT_DTYPE[nmp] (lLocalMapPoints; x, y, z are read and written), edges BAEDGE_DTYPE[ne] in the order the reference
+        creates them; rounds = 1 is bDoMore == false.  -> (kfs_out, mps_out, erase u8 [ne] = vToErase, info BAINFO_DTYPE record).
+        A refused problem (capacity, an edge outside it, a duplicate pair) raises PslfeError."""
+        k = np.ascontiguousarray(kfs, BAKEYFRAME_DTYPE).reshape(-1)
+        m = np.ascontiguousarray(mps, MAPPOINT_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(edges, BAEDGE_DTYPE).reshape(-1)
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        ko, mo, er = np.zeros(max(len(k), 1), BAKEYFRAME_DTYPE), np.zeros(max(len(m), 1), MAPPOINT_DTYPE), np.zeros(max(len(e), 1), np.uint8)
+        info = np.zeros(1, BAINFO_DTYPE)
+        _check(lib().pslfe_ba_local(ba._h, _ptr(k) if len(k) else None, C.c_int(len(k)), _ptr(m) if len(m) else None, C.c_int(len(m)),
+                                    _ptr(e) if len(e) else None, C.c_int(len(e)), _ptr(cam), C.c_int(rounds), _ptr(ko) if len(k) else None,
+                                    _ptr(mo) if len(m) else None, _ptr(er) if len(e) else None, _ptr(info)), "pslfe_ba_local")
+        return ko[:len(k)], mo[:len(m)], er[:len(e)], info[0]
+
+    @staticmethod
+    def LocalBundleAdjustmentDevice(ba, K, d_kf, d_kf_off, d_mp, d_mp_off, d_edges, d_edge_off, cam, rounds, d_kf_out, d_mp_out, d_erase, d_info):
+        """K independent problems in one launch, HBM to HBM, asynchronous; all d_* are device addresses (ints).  The offset arrays have
+        K + 1 ascending int32 entries; d_kf_out may be d_kf and d_mp_out may be d_mp; d_erase one byte per edge; d_info BAINFO_DTYPE [K]
+        with the status of each problem (-4 capacity, -1 invalid: its outputs equal its inputs)."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        _check(lib().pslfe_ba_local_device(
+            ba._h, C.c_int(K), C.c_void_p(d_kf or None), C.c_void_p(d_kf_off or None), C.c_void_p(d_mp or None), C.c_void_p(d_mp_off or None),
+            C.c_void_p(d_edges or None), C.c_void_p(d_edge_off or None), _ptr(cam), C.c_int(rounds), C.c_void_p(d_kf_out or None),
+            C.c_void_p(d_mp_out or None), C.c_void_p(d_erase or None), C.c_void_p(d_info or None)), "pslfe_ba_local_device")
 
     @staticmethod
     def PoseOptimization(Tcw, edges, cam, ctx=None, lil=None):

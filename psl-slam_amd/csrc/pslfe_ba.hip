@@ -1,0 +1,324 @@
+// libpslfe: the point edges of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1025-1966; the EdgeSE3ProjectXYZ /
+// EdgeStereoSE3ProjectXYZ part of LocalBundleAdjustmentAndInseclines :1968-2534) for K problems in one launch.  Product code.
+// Who owns what.  ba_kernels.h holds everything that is arithmetic or a decision: the edges, the quadratic form, the Schur
+// complement, the LDLt, the Levenberg loop and the two rounds, written once over an executor (its header); the host loop of
+// tools/dropin/ba_main.cpp runs the same text on one core.  This file owns the handle, the two pre-pass kernels, the executor of a
+// workgroup and the entry points.  Conventions: include/pslfe.h above pslfe_ba_local_device.
+//
+// Launches.  k_ba_check (the offsets, the counts against the handle's caps, the rows an edge names) and k_ba_lists (the four edge
+// lists by stable counting sorts, the duplicate pairs) write a status per problem; k_ba_local optimises the problems whose status
+// is PSLFE_OK and copies the others through.  All three have one workgroup per problem; a problem's result depends on nothing but
+// its own rows, so neither the batch size nor the position in the batch matters.
+//
+// k_ba_local: one resident workgroup of 256 threads per problem through both rounds, every iteration and every trial; there is no
+// launch per iteration.  The executor spreads the indices of a step over the threads (lane = edge for errors and Jacobians; thread
+// = (block, entry) walking that block's edge list in order for Hpp, Hll and S; thread = row for a column of the LDLt; thread = point
+// for the back-substitution; thread = vertex for the candidates) and ends the step with a barrier; sum256 is the ordered reduction
+// psl_lm_reduce of lm_device.h.  Control flow is uniform: every decision is taken from values all threads read back after a barrier.
+//
+// Workgroup size.  256 threads = 4 waves: the ordered reduction of lm_device.h is defined on 256 partial sums, and the result must
+// not depend on the geometry, so the size is fixed.  The workspaces do not fit LDS (160 KB per workgroup on gfx950: S alone is 259
+// KB at N = 180, the edge rows of 20 000 edges 7.5 MB), so they live in HBM / L2 (4 MB per XCD holds S, the lists and the hot edge
+// rows of one problem per resident workgroup); LDS holds the 64 bytes of the reduction and 20 bytes per thread of small arrays the
+// compiler keeps there (183 VGPRs, no scratch, 2 waves per SIMD: profiles/local_ba_codegen.txt).  The kernel is latency bound (dependent
+// double-precision chains in the LDLt and the substitutions, ~2 N + 15 barriers per trial), not occupancy bound: a single problem
+// uses one CU, and the device fills only when K reaches the CU count.  profiles/local_ba_bench.json has the first timings.
+#include <string.h>
+
+#include "pslfe_internal.h"
+#include "ba_kernels.h"
+#include "lm_device.h"
+
+#define PSL_BA_BS PSL_LM_LANES
+
+static_assert(sizeof(PslBaEdge) == 24 && sizeof(PslBaKeyFrame) == 52 && sizeof(PslBaInfo) == 48 && sizeof(PslMapPointGeom) == 32, "local BA PODs");
+static_assert(PSL_BA_BS == 4 * PSL_LM_GROUP, "four waves of 64");
+
+__device__ const double g_ba_sctab[444] = {
+#include "psl_sincostab.inc"
+};
+
+struct pslfe_ba {
+    pslfe_ctx* ctx = nullptr;
+    int max_problems = 0, ckf = 0, cmp = 0, ced = 0;
+    size_t ws_stride = 0;
+    PslDeviceBuffers bufs;
+    char* d_ws = nullptr;          // [max_problems][ws_stride]
+    int32_t* d_status = nullptr;   // [max_problems][2]: status, has work
+};
+
+struct BaArgs {
+    const PslBaKeyFrame* kf;
+    const int32_t* kf_off;
+    const PslMapPointGeom* mp;
+    const int32_t* mp_off;
+    const PslBaEdge* ed;
+    const int32_t* ed_off;
+    PslPoseCamD K;
+    int rounds, ckf, cmp, ced;
+    char* ws;
+    size_t ws_stride;
+    int32_t* status;
+    PslBaKeyFrame* kf_out;
+    PslMapPointGeom* mp_out;
+    uint8_t* erase;
+    PslBaInfo* info;
+};
+
+// the rows of problem k and, when its counts fit the caps (*code == PSLFE_OK), the views of its workspace; 0 when its offsets name
+// no rows at all
+__device__ static int ba_problem(const BaArgs& A, int k, PslBaWs* W, int* code) {
+    const int k0 = A.kf_off[k], k1 = A.kf_off[k + 1], p0 = A.mp_off[k], p1 = A.mp_off[k + 1], e0 = A.ed_off[k], e1 = A.ed_off[k + 1];
+    if (k0 < 0 || p0 < 0 || e0 < 0 || k1 < k0 || p1 < p0 || e1 < e0) { *code = PSLFE_E_INVALID; return 0; }
+    W->kf = A.kf + k0; W->mp = A.mp + p0; W->ed = A.ed + e0;
+    W->nkf = k1 - k0; W->nmp = p1 - p0; W->ne = e1 - e0;
+    W->K = A.K;
+    W->sctab = g_ba_sctab;
+    if (k1 - k0 > A.ckf || p1 - p0 > A.cmp || e1 - e0 > A.ced) { *code = PSLFE_E_CAPACITY; return 1; }
+    psl_ba_carve(A.ws + (size_t)k * A.ws_stride, A.ckf, A.cmp, A.ced, W);
+    *code = PSLFE_OK;
+    return 1;
+}
+
+// pre-pass 1: the rows.  status[2k] = the problem's code, status[2k + 1] = 1 when it has an edge and a free keyframe
+__global__ __launch_bounds__(PSL_BA_BS) void k_ba_check(BaArgs A) {
+    __shared__ int s_bad, s_free;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    PslBaWs W;
+    int code;
+    if (tid == 0) { s_bad = 0; s_free = 0; }
+    __syncthreads();
+    if (!ba_problem(A, k, &W, &code) || code != PSLFE_OK) {   // uniform
+        if (tid == 0) { A.status[2 * k] = code; A.status[2 * k + 1] = 0; }
+        return;
+    }
+    for (int e = tid; e < W.ne; e += PSL_BA_BS) {
+        const PslBaEdge ed = W.ed[e];
+        if (ed.kf < 0 || ed.kf >= W.nkf || ed.point < 0 || ed.point >= W.nmp) s_bad = 1;
+    }
+    for (int v = tid; v < W.nkf; v += PSL_BA_BS)
+        if (!W.kf[v].fixed) s_free = 1;
+    __syncthreads();
+    if (tid == 0) {
+        A.status[2 * k] = s_bad ? PSLFE_E_INVALID : PSLFE_OK;
+        A.status[2 * k + 1] = !s_bad && s_free && W.ne > 0;
+    }
+}
+
+// a stable counting sort of the edges src[0..ne) (NULL: 0, 1, 2, ...) by key into dst, as psl_ba_sort_host: the edges in chunks of
+// 256 in list order; inside a chunk an edge's place is its key's cursor plus the earlier edges of the chunk with the same key
+__device__ static void ba_sort(const PslBaWs& W, const int32_t* src, int by_point, int nkeys, int32_t* off, int32_t* dst, int* s_key) {
+    const int tid = threadIdx.x;
+    for (int k = tid; k <= nkeys; k += PSL_BA_BS) off[k] = 0;
+    __syncthreads();
+    for (int e = tid; e < W.ne; e += PSL_BA_BS) atomicAdd(&off[(by_point ? W.ed[e].point : W.ed[e].kf) + 1], 1);
+    __syncthreads();
+    if (tid == 0)
+        for (int k = 0; k < nkeys; ++k) off[k + 1] += off[k];
+    __syncthreads();
+    for (int k = tid; k < nkeys; k += PSL_BA_BS) W.cursor[k] = off[k];
+    __syncthreads();
+    for (int a0 = 0; a0 < W.ne; a0 += PSL_BA_BS) {   // uniform
+        const int a = a0 + tid;
+        const int e = a < W.ne ? (src ? src[a] : a) : -1;
+        const int key = e >= 0 ? (by_point ? W.ed[e].point : W.ed[e].kf) : -1;
+        s_key[tid] = key;
+        __syncthreads();
+        int at = 0;
+        if (e >= 0) {
+            at = W.cursor[key];
+            for (int t = 0; t < tid; ++t) at += s_key[t] == key;
+        }
+        __syncthreads();
+        if (e >= 0) {
+            dst[at] = e;
+            atomicAdd(&W.cursor[key], 1);
+        }
+        __syncthreads();
+    }
+}
+
+// pre-pass 2: the lists of a problem that passed the first and has work, and the duplicate (point, keyframe) pairs: neighbours in
+// the (point, keyframe) list
+__global__ __launch_bounds__(PSL_BA_BS) void k_ba_lists(BaArgs A) {
+    __shared__ int s_key[PSL_BA_BS];
+    __shared__ int s_dup;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (A.status[2 * k] != PSLFE_OK || !A.status[2 * k + 1]) return;   // uniform
+    PslBaWs W;
+    int code;
+    ba_problem(A, k, &W, &code);
+    if (tid == 0) s_dup = 0;
+    ba_sort(W, nullptr, 0, W.nkf, W.koff, W.klist, s_key);
+    ba_sort(W, nullptr, 1, W.nmp, W.poff, W.plist, s_key);
+    ba_sort(W, W.plist, 0, W.nkf, W.koff, W.kplist, s_key);
+    ba_sort(W, W.klist, 1, W.nmp, W.poff, W.pklist, s_key);
+    for (int a = 1 + tid; a < W.ne; a += PSL_BA_BS) {
+        const PslBaEdge x = W.ed[W.pklist[a - 1]], y = W.ed[W.pklist[a]];
+        if (x.point == y.point && x.kf == y.kf) s_dup = 1;
+    }
+    __syncthreads();
+    if (tid == 0 && s_dup) A.status[2 * k] = PSLFE_E_INVALID;
+}
+
+// the executor of ba_kernels.h on a workgroup of 256 threads
+struct BaWorkgroup {
+    double* s_red;
+    int flip;
+    template <class Fn>
+    __device__ __forceinline__ void par(int n, Fn f) {
+        for (int i = threadIdx.x; i < n; i += PSL_BA_BS) f(i);
+        __syncthreads();
+    }
+    template <class Fn>
+    __device__ __forceinline__ void one(Fn f) {
+        if (threadIdx.x == 0) f();
+        __syncthreads();
+    }
+    template <class Fn>
+    __device__ __forceinline__ double sum256(Fn f) {
+        double v[1] = {f((int)threadIdx.x)};
+        psl_lm_reduce<1, 1>(v, s_red, flip);
+        return v[0];
+    }
+    template <class V>
+    __device__ __forceinline__ V get(const V* p) {
+        const V v = *(const volatile V*)p;
+        __syncthreads();
+        return v;
+    }
+};
+
+__global__ __launch_bounds__(PSL_BA_BS) void k_ba_local(BaArgs A) {
+    __shared__ double s_red[2 * 4];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    PslBaWs W;
+    int code;
+    const int have = ba_problem(A, k, &W, &code);
+    if (have && code == PSLFE_OK) code = A.status[2 * k];   // what the pre-passes found in the rows
+    const int work = have && code == PSLFE_OK && A.status[2 * k + 1];
+    uint8_t* erase = nullptr;
+    if (have) erase = A.erase + A.ed_off[k];
+    if (!work) {   // uniform: the outputs are the inputs
+        if (have) {
+            PslBaKeyFrame* ko = A.kf_out + A.kf_off[k];
+            PslMapPointGeom* po = A.mp_out + A.mp_off[k];
+            for (int v = tid; v < W.nkf; v += PSL_BA_BS) { const PslBaKeyFrame t = W.kf[v]; ko[v] = t; }
+            for (int p = tid; p < W.nmp; p += PSL_BA_BS) { const PslMapPointGeom t = W.mp[p]; po[p] = t; }
+            for (int e = tid; e < W.ne; e += PSL_BA_BS) erase[e] = 0;
+        }
+        if (tid == 0) {
+            PslBaInfo I;
+            I.status = code; I.rounds = 0; I.iterations[0] = 0; I.iterations[1] = 0; I.nerased = 0;
+            I.chi2_start = 0.0; I.chi2_round1 = 0.0; I.chi2_end = 0.0;
+            A.info[k] = I;
+        }
+        return;
+    }
+    BaWorkgroup X = {s_red, 0};
+    psl_ba_rounds(X, W, A.rounds, A.kf_out + A.kf_off[k], A.mp_out + A.mp_off[k], erase, A.info + k);
+}
+
+extern "C" {
+
+int pslfe_ba_create(pslfe_ctx* ctx, int max_problems, int max_keyframes, int max_points, int max_edges, pslfe_ba** out) {
+    static const char* who = "pslfe_ba_create";
+    PSL_REQUIRE(ctx && out, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE(max_problems >= 1 && max_keyframes >= 1 && max_points >= 1 && max_edges >= 1, PSLFE_E_INVALID,
+                "%s: max_problems = %d, max_keyframes = %d, max_points = %d, max_edges = %d", who, max_problems, max_keyframes, max_points,
+                max_edges);
+    PSL_REQUIRE(max_keyframes <= 4096, PSLFE_E_INVALID, "%s: max_keyframes = %d (S has 36 max_keyframes^2 doubles per problem)", who, max_keyframes);
+    PSL_HIP(hipSetDevice(ctx->device));
+    pslfe_ba* b = new pslfe_ba;
+    b->ctx = ctx; b->max_problems = max_problems; b->ckf = max_keyframes; b->cmp = max_points; b->ced = max_edges;
+    PslBaWs W;
+    b->ws_stride = psl_align_up(psl_ba_carve(nullptr, max_keyframes, max_points, max_edges, &W), 256);
+    b->bufs.alloc(b->d_ws, b->ws_stride * (size_t)max_problems, "workspaces");
+    b->bufs.alloc(b->d_status, 2 * (size_t)max_problems, "status");
+    if (int rc = b->bufs.check(who)) { delete b; return rc; }
+    *out = b;
+    return PSLFE_OK;
+}
+
+void pslfe_ba_destroy(pslfe_ba* ba) {
+    if (!ba) return;
+    (void)hipSetDevice(ba->ctx->device);
+    (void)hipStreamSynchronize(ba->ctx->stream);
+    delete ba;
+}
+
+int pslfe_ba_local_device(pslfe_ba* ba, int K, const PslBaKeyFrame* d_kf, const int32_t* d_kf_off, const PslMapPointGeom* d_mp,
+                          const int32_t* d_mp_off, const PslBaEdge* d_edges, const int32_t* d_edge_off, const PslCamera* cam, int rounds,
+                          PslBaKeyFrame* d_kf_out, PslMapPointGeom* d_mp_out, uint8_t* d_erase, PslBaInfo* d_info) {
+    static const char* who = "pslfe_ba_local_device";
+    PSL_REQUIRE(K >= 0 && rounds >= 1 && rounds <= 2, PSLFE_E_INVALID, "%s: K = %d, rounds = %d (1..2)", who, K, rounds);
+    if (K == 0) return PSLFE_OK;
+    PSL_REQUIRE(ba && cam, PSLFE_E_INVALID, "%s: NULL handle or camera", who);
+    PSL_REQUIRE(K <= ba->max_problems, PSLFE_E_INVALID, "%s: K = %d above max_problems = %d", who, K, ba->max_problems);
+    PSL_REQUIRE(d_kf && d_kf_off && d_mp && d_mp_off && d_edges && d_edge_off && d_kf_out && d_mp_out && d_erase && d_info, PSLFE_E_INVALID,
+                "%s: NULL array", who);
+    pslfe_ctx* ctx = ba->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    BaArgs A;
+    A.kf = d_kf; A.kf_off = d_kf_off; A.mp = d_mp; A.mp_off = d_mp_off; A.ed = d_edges; A.ed_off = d_edge_off;
+    A.K.fx = (double)cam->fx; A.K.fy = (double)cam->fy; A.K.cx = (double)cam->cx; A.K.cy = (double)cam->cy; A.K.bf = (double)cam->bf;
+    A.rounds = rounds; A.ckf = ba->ckf; A.cmp = ba->cmp; A.ced = ba->ced;
+    A.ws = ba->d_ws; A.ws_stride = ba->ws_stride; A.status = ba->d_status;
+    A.kf_out = d_kf_out; A.mp_out = d_mp_out; A.erase = d_erase; A.info = d_info;
+    {
+        PSL_STAGE_BEGIN(ctx, "ba.check");
+        k_ba_check<<<K, PSL_BA_BS, 0, ctx->stream>>>(A);
+        PSL_STAGE_END(ctx, "ba.check");
+    }
+    {
+        PSL_STAGE_BEGIN(ctx, "ba.lists");
+        k_ba_lists<<<K, PSL_BA_BS, 0, ctx->stream>>>(A);
+        PSL_STAGE_END(ctx, "ba.lists");
+    }
+    {
+        PSL_STAGE_BEGIN(ctx, "ba.local");
+        k_ba_local<<<K, PSL_BA_BS, 0, ctx->stream>>>(A);
+        PSL_STAGE_END(ctx, "ba.local");
+    }
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+
+int pslfe_ba_local(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const PslMapPointGeom* mp, int nmp, const PslBaEdge* edges, int nedges,
+                   const PslCamera* cam, int rounds, PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslBaInfo* info) {
+    static const char* who = "pslfe_ba_local";
+    PSL_REQUIRE(nkf >= 0 && nmp >= 0 && nedges >= 0 && rounds >= 1 && rounds <= 2, PSLFE_E_INVALID,
+                "%s: nkf = %d, nmp = %d, nedges = %d, rounds = %d (1..2)", who, nkf, nmp, nedges, rounds);
+    PSL_REQUIRE(ba && cam && info, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE((nkf == 0 || (kf && kf_out)) && (nmp == 0 || (mp && mp_out)) && (nedges == 0 || (edges && erase)), PSLFE_E_INVALID,
+                "%s: NULL array with a non-zero count", who);
+    pslfe_ctx* ctx = ba->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    hipError_t e = hipSuccess;
+    const int32_t koff[2] = {0, nkf}, poff[2] = {0, nmp}, eoff[2] = {0, nedges};
+    PslBaKeyFrame* d_kf = psl_scratch_up(ctx, nkf ? kf : nullptr, (size_t)nkf, st, &e);
+    PslMapPointGeom* d_mp = psl_scratch_up(ctx, nmp ? mp : nullptr, (size_t)nmp, st, &e);
+    PslBaEdge* d_ed = psl_scratch_up(ctx, nedges ? edges : nullptr, (size_t)nedges, st, &e);
+    const int32_t* d_koff = psl_scratch_up(ctx, koff, 2, st, &e);
+    const int32_t* d_poff = psl_scratch_up(ctx, poff, 2, st, &e);
+    const int32_t* d_eoff = psl_scratch_up(ctx, eoff, 2, st, &e);
+    uint8_t* d_erase = psl_scratch_up(ctx, (const uint8_t*)nullptr, (size_t)nedges, st, &e);
+    PslBaInfo* d_info = psl_scratch_up(ctx, (const PslBaInfo*)nullptr, 1, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: scratch / upload: %s", who, hipGetErrorString(e));
+    if (int rc = pslfe_ba_local_device(ba, 1, d_kf, d_koff, d_mp, d_poff, d_ed, d_eoff, cam, rounds, d_kf, d_mp, d_erase, d_info)) return rc;
+    if (nkf) PSL_HIP(hipMemcpyAsync(kf_out, d_kf, (size_t)nkf * sizeof(PslBaKeyFrame), hipMemcpyDeviceToHost, st));
+    if (nmp) PSL_HIP(hipMemcpyAsync(mp_out, d_mp, (size_t)nmp * sizeof(PslMapPointGeom), hipMemcpyDeviceToHost, st));
+    if (nedges) PSL_HIP(hipMemcpyAsync(erase, d_erase, (size_t)nedges, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(info, d_info, sizeof(PslBaInfo), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    if (info->status < 0) {
+        pslfe_set_error("%s: the problem was refused with %d (%s)", who, info->status,
+                        info->status == PSLFE_E_CAPACITY ? "a count above the handle's caps" : "an edge outside the problem or a duplicate pair");
+        return info->status;
+    }
+    return PSLFE_OK;
+}
+
+}  // extern "C"

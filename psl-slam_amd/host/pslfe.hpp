@@ -1158,6 +1158,21 @@ private:
 // == Optimizer (include/Optimizer.h:58): PoseOptimization, src/Optimizer.cc:239-1023: the monocular and stereo point edges and the
 //    LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the overloads and methods that take PslPoseLilEdge rows).  Parity with g2o
 //    itself is unpinned.
+// The workspaces of the local bundle adjustment (pslfe_ba): up to maxProblems problems per launch of up to maxKeyframes keyframes
+// (free and fixed), maxPoints points and maxEdges edges each.  A single owner frees every buffer.
+class BundleAdjuster {
+public:
+    BundleAdjuster(Context& ctx, int maxProblems, int maxKeyframes, int maxPoints, int maxEdges) {
+        check(pslfe_ba_create(ctx.get(), maxProblems, maxKeyframes, maxPoints, maxEdges, &h_), "pslfe_ba_create");
+    }
+    ~BundleAdjuster() { pslfe_ba_destroy(h_); }
+    BundleAdjuster(const BundleAdjuster&) = delete;
+    BundleAdjuster& operator=(const BundleAdjuster&) = delete;
+    pslfe_ba* get() const { return h_; }
+private:
+    pslfe_ba* h_ = nullptr;
+};
+
 class Optimizer {
 public:
     // int Optimizer::PoseOptimization(Frame* pFrame): edges = one PslPoseEdge per non-NULL pFrame->mvpMapPoints[i] in keypoint order
@@ -1217,6 +1232,27 @@ public:
         check(pslfe_pose_edges_from_matches_device(frame.get(), slot0, nframes, d_mpIndex, d_mp, mpStride, invLevelSigma2.data(),
                                                    (int)invLevelSigma2.size(), d_edges, d_edgeKp, d_nedges, estride),
               "pslfe_pose_edges_from_matches_device");
+    }
+    // void Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) src/Optimizer.cc:1025-1966 from optimizer.initializeOptimization()
+    // (:1642) on, its point edges: kfs = lLocalKeyFrames then lFixedCameras (fixed set for those and for mnId == 0), mps =
+    // lLocalMapPoints, edges in the order the reference creates them (INTEGRATION.md "LocalBundleAdjustment").  kfs and mps come
+    // back optimised, erase[e] = 1 where the reference puts the edge's pair into vToErase.  doMore = false is bDoMore == false.
+    // A refused problem (capacity, an edge outside it, a duplicate pair) throws.  Parity with g2o itself is unpinned.
+    static PslBaInfo LocalBundleAdjustment(BundleAdjuster& ba, std::vector<PslBaKeyFrame>& kfs, std::vector<PslMapPointGeom>& mps,
+                                           const std::vector<PslBaEdge>& edges, const PslCamera& cam, std::vector<uint8_t>& erase,
+                                           bool doMore = true) {
+        erase.assign(edges.size(), 0);
+        PslBaInfo info = {};
+        check(pslfe_ba_local(ba.get(), kfs.data(), (int)kfs.size(), mps.data(), (int)mps.size(), edges.data(), (int)edges.size(), &cam,
+                             doMore ? 2 : 1, kfs.data(), mps.data(), erase.data(), &info), "pslfe_ba_local");
+        return info;
+    }
+    // K problems in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_ba_local_device
+    static void LocalBundleAdjustmentDevice(BundleAdjuster& ba, int K, const PslBaKeyFrame* d_kf, const int32_t* d_kfOff, const PslMapPointGeom* d_mp,
+                                            const int32_t* d_mpOff, const PslBaEdge* d_edges, const int32_t* d_edgeOff, const PslCamera& cam,
+                                            int rounds, PslBaKeyFrame* d_kfOut, PslMapPointGeom* d_mpOut, uint8_t* d_erase, PslBaInfo* d_info) {
+        check(pslfe_ba_local_device(ba.get(), K, d_kf, d_kfOff, d_mp, d_mpOff, d_edges, d_edgeOff, &cam, rounds, d_kfOut, d_mpOut, d_erase, d_info),
+              "pslfe_ba_local_device");
     }
     // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) src/Optimizer.cc:2801-2996: pairs = one PslSim3Pair per
     // match that passes the set-up loop (:2854-2933), in KF1 keypoint order; S12 = what Sim3Solver hands over (src/LoopClosing.cc:
