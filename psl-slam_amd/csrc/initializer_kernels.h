@@ -12,14 +12,12 @@
 //   CheckHomography, CheckFundamental            :305-468
 //   ReconstructF, ReconstructH                   :470-732
 //   Triangulate, Normalize, CheckRT, DecomposeE  :734-929
-// glibc's rand() and RandomInt are those of sim3_solver_kernels.h (psl_ss_srand, psl_ss_rand, psl_ss_random_int): included, not copied.
+// glibc's rand(), RandomInt, the draw (psl_rs_draw<8>) and the Jacobi SVD are those of ransac_kernels.h: included, not copied.
 // OpenCV is not in the reference tree: every step handed to it is this library's reading of OpenCV 3.2; parity with OpenCV is unpinned.
-//   cv::SVD::compute / SVDecomp, CV_32F   JacobiSVDImpl_<float> (psl_init_jacobi, psl_init_complete): one-sided Jacobi on the n rows
-//                                (length m) of At = A^T; with m < n the operands are swapped, so the 8x9 matrix of ComputeF21 runs on its
-//                                own 8 rows and vt is the "U" side, 9x9.  eps = 2 * FLT_EPSILON, minval = FLT_MIN, at most max(m, 30)
-//                                sweeps.  W, the dot products, c and s are doubles; a rotated element is the double expression rounded
-//                                to float, and the squares of the rounded elements are accumulated in double.  Singular values
-//                                descending with their rows.  Then every row i < n1 (n1 = the full size with FULL_UV) is divided by its
+//   cv::SVD::compute / SVDecomp, CV_32F   psl_init_jacobi, psl_init_complete: psl_rs_jacobi_svd<float> (ransac_kernels.h holds the reading)
+//                                on the n rows (length m) of At = A^T with eps = 2 * FLT_EPSILON; with m < n the operands are swapped, so
+//                                the 8x9 matrix of ComputeF21 runs on its own 8 rows and vt is the "U" side, 9x9.  Then, with minval =
+//                                FLT_MIN, every row i < n1 (n1 = the full size with FULL_UV) is divided by its
 //                                singular value; a row with sd <= minval, and every row n..n1-1, is first completed: filled with +-1/m,
 //                                the sign from (next() & 256) of RNG(0x12345678) (multiply with carry, state * 4164903690 + (state >>
 //                                32)), orthogonalised twice against the earlier rows (dot product in double of the float products,
@@ -48,7 +46,7 @@
 #include "../../include/pslfe.h"
 #include <string.h>
 
-#include "sim3_solver_kernels.h"
+#include "ransac_kernels.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -61,7 +59,7 @@
 #define PSL_INIT_PI 3.1415926535897932384626433832795
 
 #define PSL_ACOSF_HD PSL_INIT_HD
-#define PSL_ACOSF_DIV(a, b) PSL_SS_FDIV(a, b)
+#define PSL_ACOSF_DIV(a, b) PSL_RS_FDIV(a, b)
 #define PSL_ACOSF_SQRT(a) PSL_INIT_FSQRT(a)
 #include "psl_acosf.h"
 
@@ -106,34 +104,14 @@ PSL_INIT_HD int psl_init_load(const PslInitRows* R, int r, float* q) {
     return i1;
 }
 
-// ---- the draw (:82-97): eight indices, each removed by overwriting it with the back of vAvailableIndices and popping -----------------
-PSL_INIT_HD void psl_init_draw8(PslSsRand* G, int N, int* idx8) {
-    int opos[7], oval[7];
-    for (int j = 0; j < 7; ++j) { opos[j] = -1; oval[j] = 0; }
-    int size = N;
-    PSL_LM_UNROLL
-    for (int i = 0; i < 8; ++i) {
-        const int randi = psl_ss_random_int(psl_ss_rand(G), size);
-        int idx = randi, back = size - 1;
-        PSL_LM_UNROLL
-        for (int j = 0; j < 7; ++j) {   // a later write to a position wins: ascending j
-            if (opos[j] == randi) idx = oval[j];
-            if (opos[j] == size - 1) back = oval[j];
-        }
-        idx8[i] = idx;
-        if (i < 7) { opos[i] = randi; oval[i] = back; }
-        --size;
-    }
-}
-
 // ---- Normalize (:749-795), one coordinate of one frame: comp 0 = x, 1 = y.  Sequential float sums in keypoint order ------------------
 PSL_INIT_HD void psl_init_normalize(const float* keys, size_t ks, int n, int comp, float* mean, float* scale) {
     float m = 0;
     for (int i = 0; i < n; ++i) m = m + keys[ks * (size_t)i + comp];
-    m = PSL_SS_FDIV(m, (float)n);
+    m = PSL_RS_FDIV(m, (float)n);
     float dev = 0;
     for (int i = 0; i < n; ++i) dev = dev + __builtin_fabsf(keys[ks * (size_t)i + comp] - m);
-    dev = PSL_SS_FDIV(dev, (float)n);
+    dev = PSL_RS_FDIV(dev, (float)n);
     *mean = m;
     *scale = (float)PSL_PO_DIV(1.0, (double)dev);
 }
@@ -198,76 +176,16 @@ PSL_INIT_HD void psl_init_unit3(float* v) {
     for (int k = 0; k < 3; ++k) v[k] = (float)((double)v[k] * inv);
 }
 
-// ---- JacobiSVDImpl_<float> on the n rows of length m at a (row stride m), W in w, Vt (n x n; nullptr: none) ---------------------------
+// ---- cv::SVD::compute on CV_32F: psl_rs_jacobi_svd<float> with eps = 2 * FLT_EPSILON; the left side is psl_init_complete's ----------
 template <int ES>
 PSL_INIT_HD void psl_init_jacobi(float* a, int m, int n, double* w, float* v) {
-    const double eps = (double)(PSL_SS_FLT_EPSILON * 2);
-    const int max_iter = m > 30 ? m : 30;
-    for (int i = 0; i < n; ++i) {
-        double sd = 0;
-        for (int k = 0; k < m; ++k) { const double t = (double)F_(a, i * m + k); sd = sd + t * t; }
-        F_(w, i) = sd;
-        if (v)
-            for (int k = 0; k < n; ++k) F_(v, i * n + k) = k == i ? 1.f : 0.f;
-    }
-    for (int iter = 0; iter < max_iter; ++iter) {
-        bool changed = false;
-        for (int i = 0; i < n - 1; ++i)
-            for (int j = i + 1; j < n; ++j) {
-                double aa = F_(w, i), p = 0, bb = F_(w, j);
-                for (int k = 0; k < m; ++k) p = p + (double)F_(a, i * m + k) * (double)F_(a, j * m + k);
-                if (__builtin_fabs(p) <= eps * PSL_PO_SQRT(aa * bb)) continue;
-                p = p * 2;
-                const double beta = aa - bb, gamma = PSL_PO_SQRT(p * p + beta * beta);
-                double c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = PSL_PO_SQRT(PSL_PO_DIV(delta, gamma));
-                    c = PSL_PO_DIV(p, (gamma * s) * 2);
-                } else {
-                    c = PSL_PO_SQRT(PSL_PO_DIV(gamma + beta, gamma * 2));
-                    s = PSL_PO_DIV(p, (gamma * c) * 2);
-                }
-                aa = bb = 0;
-                for (int k = 0; k < m; ++k) {
-                    const double x = (double)F_(a, i * m + k), y = (double)F_(a, j * m + k);
-                    const float t0 = (float)(c * x + s * y), t1 = (float)(-s * x + c * y);
-                    F_(a, i * m + k) = t0; F_(a, j * m + k) = t1;
-                    aa = aa + (double)t0 * (double)t0; bb = bb + (double)t1 * (double)t1;
-                }
-                F_(w, i) = aa; F_(w, j) = bb;
-                changed = true;
-                if (v)
-                    for (int k = 0; k < n; ++k) {
-                        const double x = (double)F_(v, i * n + k), y = (double)F_(v, j * n + k);
-                        F_(v, i * n + k) = (float)(c * x + s * y);
-                        F_(v, j * n + k) = (float)(-s * x + c * y);
-                    }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < n; ++i) {
-        double sd = 0;
-        for (int k = 0; k < m; ++k) { const double t = (double)F_(a, i * m + k); sd = sd + t * t; }
-        F_(w, i) = PSL_PO_SQRT(sd);
-    }
-    for (int i = 0; i < n - 1; ++i) {
-        int j = i;
-        for (int k = i + 1; k < n; ++k)
-            if (F_(w, j) < F_(w, k)) j = k;
-        if (i != j) {
-            { const double t = F_(w, i); F_(w, i) = F_(w, j); F_(w, j) = t; }
-            for (int k = 0; k < m; ++k) { const float t = F_(a, i * m + k); F_(a, i * m + k) = F_(a, j * m + k); F_(a, j * m + k) = t; }
-            if (v)
-                for (int k = 0; k < n; ++k) { const float t = F_(v, i * n + k); F_(v, i * n + k) = F_(v, j * n + k); F_(v, j * n + k) = t; }
-        }
-    }
+    psl_rs_jacobi_svd<float, ES>(a, m, n, w, v, (double)(PSL_RS_FLT_EPSILON * 2));
 }
 // The left side: rows 0..n1-1 of a (n1 >= n rows of storage) divided by their singular value, completed where there is none
 template <int ES>
 PSL_INIT_HD void psl_init_complete(float* a, int m, int n, int n1, const double* w) {
     const double minval = PSL_INIT_FLT_MIN;
-    const float eps = PSL_SS_FLT_EPSILON * 2;
+    const float eps = PSL_RS_FLT_EPSILON * 2;
     unsigned long long state = 0x12345678ull;
     for (int i = 0; i < n1; ++i) {
         double sd = i < n ? F_(w, i) : 0.0;
@@ -287,7 +205,7 @@ PSL_INIT_HD void psl_init_complete(float* a, int m, int n, int n1, const double*
                         F_(a, i * m + k) = t;
                         asum = asum + __builtin_fabsf(t);
                     }
-                    asum = asum > eps * 100 ? PSL_SS_FDIV(1.f, asum) : 0.f;
+                    asum = asum > eps * 100 ? PSL_RS_FDIV(1.f, asum) : 0.f;
                     for (int k = 0; k < m; ++k) F_(a, i * m + k) = F_(a, i * m + k) * asum;
                 }
             sd = 0;
@@ -402,7 +320,7 @@ PSL_INIT_HD int psl_init_score_f(const float* F, const float* q, float invSigmaS
     const float b2 = (F[3] * u1 + F[4] * v1) + F[5];
     const float c2 = (F[6] * u1 + F[7] * v1) + F[8];
     const float num2 = (a2 * u2 + b2 * v2) + c2;
-    const float squareDist1 = PSL_SS_FDIV(num2 * num2, a2 * a2 + b2 * b2);
+    const float squareDist1 = PSL_RS_FDIV(num2 * num2, a2 * a2 + b2 * b2);
     const float chiSquare1 = squareDist1 * invSigmaSquare;
     if (chiSquare1 > th) bIn = 0;
     else *score = *score + (thScore - chiSquare1);
@@ -410,7 +328,7 @@ PSL_INIT_HD int psl_init_score_f(const float* F, const float* q, float invSigmaS
     const float b1 = (F[1] * u2 + F[4] * v2) + F[7];
     const float c1 = (F[2] * u2 + F[5] * v2) + F[8];
     const float num1 = (a1 * u1 + b1 * v1) + c1;
-    const float squareDist2 = PSL_SS_FDIV(num1 * num1, a1 * a1 + b1 * b1);
+    const float squareDist2 = PSL_RS_FDIV(num1 * num1, a1 * a1 + b1 * b1);
     const float chiSquare2 = squareDist2 * invSigmaSquare;
     if (chiSquare2 > th) bIn = 0;
     else *score = *score + (thScore - chiSquare2);
@@ -462,13 +380,13 @@ PSL_INIT_HD int psl_init_motion_h(const float* H21, const float* K, float* a, do
     psl_init_svd3<ES>(A, a, w, v, U, wf, Vt);
     const float s = (float)(psl_init_det3(U) * psl_init_det3(Vt));
     const float d1 = wf[0], d2 = wf[1], d3 = wf[2];
-    if ((double)PSL_SS_FDIV(d1, d2) < 1.00001 || (double)PSL_SS_FDIV(d2, d3) < 1.00001) return 0;
-    const float aux1 = PSL_INIT_FSQRT(PSL_SS_FDIV(d1 * d1 - d2 * d2, d1 * d1 - d3 * d3));
-    const float aux3 = PSL_INIT_FSQRT(PSL_SS_FDIV(d2 * d2 - d3 * d3, d1 * d1 - d3 * d3));
-    const float aux_stheta = PSL_SS_FDIV(PSL_INIT_FSQRT((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)), (d1 + d3) * d2);
-    const float ctheta = PSL_SS_FDIV(d2 * d2 + d1 * d3, (d1 + d3) * d2);
-    const float aux_sphi = PSL_SS_FDIV(PSL_INIT_FSQRT((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)), (d1 - d3) * d2);
-    const float cphi = PSL_SS_FDIV(d1 * d3 - d2 * d2, (d1 - d3) * d2);
+    if ((double)PSL_RS_FDIV(d1, d2) < 1.00001 || (double)PSL_RS_FDIV(d2, d3) < 1.00001) return 0;
+    const float aux1 = PSL_INIT_FSQRT(PSL_RS_FDIV(d1 * d1 - d2 * d2, d1 * d1 - d3 * d3));
+    const float aux3 = PSL_INIT_FSQRT(PSL_RS_FDIV(d2 * d2 - d3 * d3, d1 * d1 - d3 * d3));
+    const float aux_stheta = PSL_RS_FDIV(PSL_INIT_FSQRT((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)), (d1 + d3) * d2);
+    const float ctheta = PSL_RS_FDIV(d2 * d2 + d1 * d3, (d1 + d3) * d2);
+    const float aux_sphi = PSL_RS_FDIV(PSL_INIT_FSQRT((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)), (d1 - d3) * d2);
+    const float cphi = PSL_RS_FDIV(d1 * d3 - d2 * d2, (d1 - d3) * d2);
     for (int h = 0; h < 8; ++h) {
         const int i = h & 3;   // x1 = {+, +, -, -} aux1, x3 = {+, -, +, -} aux3, stheta / sphi = {+, -, -, +} aux
         const float x1 = i < 2 ? aux1 : -aux1, x3 = (i & 1) ? -aux3 : aux3;
@@ -668,12 +586,12 @@ static inline void psl_init_initialize_host(const float* k1, int n1, const float
     psl_init_normalize(k2, ks, n2, 0, &nm2.mx, &nm2.sx);
     psl_init_normalize(k2, ks, n2, 1, &nm2.my, &nm2.sy);
     const float invS2 = psl_init_inv_sigma2(sigma);
-    PslSsRand G;
-    psl_ss_srand(&G, seed);
+    PslRsRand G;
+    psl_rs_srand(&G, seed);
     float SH = 0.f, SF = 0.f, MH[18], MF[9];
     for (int it = 0; it < max_its; ++it) {
         int idx[8];
-        psl_init_draw8(&G, N, idx);
+        psl_rs_draw<8>(&G, N, idx);
         float H21[9], H12[9], F21[9], sh = 0.f, sf = 0.f;
         psl_init_hyp_h<1>(&R, idx, &nm1, &nm2, ws, wd, H21, H12);
         psl_init_hyp_f<1>(&R, idx, &nm1, &nm2, ws, wd, F21);
@@ -696,7 +614,7 @@ static inline void psl_init_initialize_host(const float* k1, int n1, const float
     if (res->best_it_h >= 0) for (int k = 0; k < 9; ++k) res->H21[k] = MH[k];
     if (res->best_it_f >= 0) for (int k = 0; k < 9; ++k) res->F21[k] = MF[k];
     if (res->best_it_h < 0 && res->best_it_f < 0) { res->status = 4; return; }
-    res->RH = PSL_SS_FDIV(SH, SH + SF);
+    res->RH = PSL_RS_FDIV(SH, SH + SF);
     const int homography = (double)res->RH > 0.40;
     if (homography) res->status |= 2;
     float K[9], Rs[72], ts[24];

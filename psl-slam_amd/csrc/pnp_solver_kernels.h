@@ -9,14 +9,13 @@
 //   the draw                                   :188-201; Thirdparty/DBoW2/DUtils/Random.cpp:47-50
 //   iterate, Refine, CheckInliers              :165-258, :260-305, :308-339
 //   compute_pose and everything under it       :375-950
-// glibc's rand() and RandomInt are those of sim3_solver_kernels.h (psl_ss_srand, psl_ss_rand, psl_ss_random_int): included, not copied.
+// glibc's rand(), RandomInt and the draw (psl_rs_draw<4>) are those of ransac_kernels.h: included, not copied.
 // OpenCV is not in the reference tree: where the solver hands a step to it (cvMulTransposed, cvSVD, cvInvert, cvSolve) the order
 // written here is this library's reading of OpenCV 3.2; parity with OpenCV is unpinned.
 //   cvMulTransposed(A, dst, 1)   A^T A: every upper-triangle entry the sequential sum over the rows of A in row order, from 0.0; the
 //                                lower triangle is copied.
-//   cvSVD                        JacobiSVDImpl_<double> (psl_pnp_jacobi): one-sided Jacobi on the n rows (length m) of At = A^T, eps =
-//                                10 * DBL_EPSILON, at most max(m, 30) sweeps, singular values descending with their vectors, the rows
-//                                normalised by 1 / w (0 where w <= DBL_MIN): the reading of oracle/glue_oracle.cpp:70-138 at any n.
+//   cvSVD                        psl_pnp_jacobi: JacobiSVDImpl_<double> as ransac_kernels.h reads it, with eps = 10 * DBL_EPSILON, then
+//                                the rows normalised by 1 / w (0 where w <= DBL_MIN): oracle/glue_oracle.cpp:70-138 at any n.
 //                                After it the rows of At are the left singular vectors (U^T) and the rows of Vt the right ones (V^T).
 //                                CV_SVD_U_T hands out U^T = At (:400, :493 read its rows); without a flag U[i][k] = At[k][i] and
 //                                V[j][k] = Vt[k][j] (:608-612: R = U V^T).
@@ -30,7 +29,9 @@
 #ifndef PSL_PNP_SOLVER_KERNELS_H
 #define PSL_PNP_SOLVER_KERNELS_H
 
-#include "sim3_solver_kernels.h"
+#include <math.h>   // the iteration budget
+
+#include "ransac_kernels.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -140,27 +141,12 @@ static inline int psl_pnp_max_iterations(double prob, int min_inliers, int max_i
     return n < 1 ? 1 : n;
 }
 
-// ---- the draw (:188-201): four indices, each removed by overwriting it with the back of vAvailableIndices and popping ---------------
-PSL_PNP_HD void psl_pnp_draw(PslSsRand* G, int N, int* idx4) {
-    int opos[3] = {-1, -1, -1}, oval[3] = {0, 0, 0};
-    int size = N;
-    for (int i = 0; i < 4; ++i) {
-        const int randi = psl_ss_random_int(psl_ss_rand(G), size);
-        int idx = randi, back = size - 1;
-        for (int j = 0; j < 3; ++j) {
-            if (opos[j] == randi) idx = oval[j];
-            if (opos[j] == size - 1) back = oval[j];
-        }
-        idx4[i] = idx;
-        if (i < 3) { opos[i] = randi; oval[i] = back; }
-        --size;
-    }
-}
-
-// ---- JacobiSVDImpl_<double> on the n rows of length m at ws[a..] (row stride m), w at ws[w..], Vt (n x n, v < 0: none) ---------------
+// ---- cvSVD: the sweeps and the sort of psl_rs_jacobi_svd<double> word for word (both are held to tests/pnp_cases.py) on the n rows of
+// length m at ws[a..], w at ws[w..], Vt at ws[v..] (v < 0: none), then the rows divided by their singular value.  Written on offsets:
+// through the template's pointers k_pnp_solve runs 0.2 to 0.5 % longer at 12288 candidates (profiles/ransac_shared_ab.json) ---------
 template <int ES>
 PSL_PNP_HD void psl_pnp_jacobi(double* ws, int a, int m, int n, int w, int v) {
-    const double eps = PSL_SS_DBL_EPSILON * 10;
+    const double eps = PSL_RS_DBL_EPSILON * 10;
     const int max_iter = m > 30 ? m : 30;
     for (int i = 0; i < n; ++i) {
         double sd = 0;
@@ -232,7 +218,7 @@ template <int ES>
 PSL_PNP_HD double psl_pnp_bksb_threshold(const double* ws, int w, int n) {
     double t = 0;
     for (int i = 0; i < n; ++i) t = t + W_(w + i);
-    return t * (PSL_SS_DBL_EPSILON * 2);
+    return t * (PSL_RS_DBL_EPSILON * 2);
 }
 
 // ---- choose_control_points (:375-409) in three steps: two sets of sums over the correspondences, then the PCA -------------------------
@@ -663,17 +649,17 @@ PSL_PNP_HD PslPnpOutcome psl_pnp_iterate(const float* rows, int N, const PslPnpC
     for (int k = 0; k < 12; ++k) T[k] = 0.f;
     if (N < min_inliers) { o.status = 2; return o; }
     PslPnpRows R = {nullptr, 0, rows, th2};
-    PslSsRand G;
+    PslRsRand G;
     if (o.iterations < max_its || n_iterations > 0) {   // a call that runs no iteration draws nothing
-        psl_ss_srand(&G, seed);
-        for (int i = 0; i < 4 * iterations; ++i) psl_ss_rand(&G);
+        psl_rs_srand(&G, seed);
+        for (int i = 0; i < 4 * iterations; ++i) psl_rs_rand(&G);
     }
     int cur = 0;
     while (o.iterations < max_its || cur < n_iterations) {
         ++cur;
         ++o.iterations;
         int idx[4];
-        psl_pnp_draw(&G, N, idx);
+        psl_rs_draw<4>(&G, N, idx);
         PslPnpSel S = {idx, nullptr, 4, 4};
         psl_pnp_compute_pose<1>(ws, &R, &S, K);
         double Rt[12];

@@ -1,9 +1,9 @@
 // libpslfe: Initializer (src/Initializer.cc), the two-view map initialisation of Tracking::MonocularInitialization
 // (src/Tracking.cc:659-760), for K independent frame pairs in one launch.  Product code.
-// Who owns what.  initializer_kernels.h holds everything a single thread computes - the draw, Normalize, the 8-point H and F with this
-// library's reading of OpenCV's float Jacobi SVD, the scores of a row, the motion hypotheses, CheckRT for one row, the decision trees -
-// and the reference's loop on one core (psl_init_initialize_host), which tools/dropin/init_main.cpp runs and tests/initializer_cases.py
-// restates in numpy.  Here: which thread computes which hypothesis and which row, the LDS copy of the matched rows, the error paths.
+// Who owns what.  initializer_kernels.h holds everything a single thread computes - Normalize, the 8-point H and F, the scores of a row,
+// the motion hypotheses, CheckRT for one row, the decision trees - and the reference's loop on one core (psl_init_initialize_host),
+// which tools/dropin/init_main.cpp runs and tests/initializer_cases.py restates in numpy; glibc's rand(), the draw and this library's
+// reading of OpenCV's Jacobi SVD are those of ransac_kernels.h, shared with the other RANSAC solvers.  Here: which thread computes which hypothesis and which row, the LDS copy of the matched rows, the error paths.
 //
 // Layout.  One workgroup of 256 threads per pair, resident through all stages.
 //   rows        the matches are compacted in keypoint order by ballot (psl_wg_compact); the frame-1 keypoint of every row goes to an
@@ -69,7 +69,7 @@ struct InitArgs {
 
 struct InitShared {
     PslInitNorm nm1, nm2;
-    PslSsRand rand;
+    PslRsRand rand;
     int idx[PSL_INIT_B][8];
     float model[PSL_INIT_B][27];   // H21 H12 F21 of the block
     float score[2][PSL_INIT_B];
@@ -230,14 +230,14 @@ __global__ __launch_bounds__(PSL_INIT_BS) void k_init_solve(InitArgs A) {
         PslInitNorm* nm = tid < 2 ? &sh.nm1 : &sh.nm2;
         psl_init_normalize(k, A.ks, n, tid & 1, (tid & 1) ? &nm->my : &nm->mx, (tid & 1) ? &nm->sy : &nm->sx);
     }
-    if (tid == 64) psl_ss_srand(&sh.rand, A.seed0 + (uint32_t)p);
+    if (tid == 64) psl_rs_srand(&sh.rand, A.seed0 + (uint32_t)p);
     const float invS2 = psl_init_inv_sigma2(A.sigma);
     float SH = 0.f, SF = 0.f;   // thread 0's
     __syncthreads();
     for (int it0 = 0; it0 < A.max_its; it0 += PSL_INIT_B) {   // uniform
         const int nb = A.max_its - it0 < PSL_INIT_B ? A.max_its - it0 : PSL_INIT_B;
         if (tid == 64)
-            for (int h = 0; h < nb; ++h) psl_init_draw8(&sh.rand, N, sh.idx[h]);
+            for (int h = 0; h < nb; ++h) psl_rs_draw<8>(&sh.rand, N, sh.idx[h]);
         __syncthreads();
         if ((tid & 7) == 0) {
             const int f = tid >> 7, h = (tid & 127) >> 3;   // waves 0-1: H, waves 2-3: F
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(PSL_INIT_BS) void k_init_solve(InitArgs A) {
         if (!have_h && !have_f) {
             o.status = 4;
         } else {
-            o.RH = PSL_SS_FDIV(SH, SH + SF);
+            o.RH = PSL_RS_FDIV(SH, SH + SF);
             hom = (double)o.RH > 0.40;
             if (hom) {
                 o.status |= 2;
@@ -396,11 +396,11 @@ extern "C" {
 int pslfe_init_sets(uint32_t seed, int N, int max_its, int32_t* sets) {
     static const char* who = "pslfe_init_sets";
     PSL_REQUIRE(N >= 8 && max_its >= 0 && sets, PSLFE_E_INVALID, "%s: N = %d, max_its = %d or NULL sets", who, N, max_its);
-    PslSsRand G;
-    psl_ss_srand(&G, seed);
+    PslRsRand G;
+    psl_rs_srand(&G, seed);
     for (int it = 0; it < max_its; ++it) {
         int idx[8];
-        psl_init_draw8(&G, N, idx);
+        psl_rs_draw<8>(&G, N, idx);
         for (int j = 0; j < 8; ++j) sets[8 * (size_t)it + j] = idx[j];
     }
     return PSLFE_OK;

@@ -1,10 +1,11 @@
 // libpslfe: PnPsolver (src/PnPsolver.cc), the EPnP RANSAC of Tracking::Relocalization (src/Tracking.cc:2075-2101), for K candidate
 // keyframes in one launch, with its set-up (the constructor's loop) and the masking of the matches by the inliers (:2119-2128).
 // Product code.
-// Who owns what.  pnp_solver_kernels.h holds everything a single thread computes - the staging of a row, the draw, EPnP in stages with
-// this library's reading of OpenCV's Jacobi SVD, the inlier test of a row - and the reference's loop on one core (psl_pnp_iterate),
-// which tools/dropin/pnp_main.cpp runs and tests/pnp_cases.py restates in numpy.  Here: which thread computes which hypothesis, which
-// sum and which row, the LDS copy of the staged rows, the error paths, and the driver in blocks.
+// Who owns what.  pnp_solver_kernels.h holds everything a single thread computes - the staging of a row, EPnP in stages, the
+// inlier test of a row - and the reference's loop on one core (psl_pnp_iterate), which tools/dropin/pnp_main.cpp runs and
+// tests/pnp_cases.py restates in numpy; glibc's rand() and the draw are those of ransac_kernels.h, shared with the other RANSAC
+// solvers, and its reading of OpenCV's Jacobi SVD is written out on the workspace's offsets (psl_pnp_jacobi).  Here: which thread
+// computes which hypothesis, which sum and which row, the LDS copy of the staged rows, the error paths, and the driver in blocks.
 //
 // The driver in blocks.  PnPsolver::iterate draws four rows, solves, counts, and - when the count reaches mRansacMinInliers - keeps the
 // hypothesis as the best on > and refines on the best inlier set; it returns at the first Refine that succeeds.  The draws never depend
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(PSL_PNP_BS) void k_pnp_solve(PnpSolveArgs A) {
     __shared__ int s_cnt[PSL_PNP_B];
     __shared__ int s_part[4];
     __shared__ float s_bestT[12];
-    __shared__ PslSsRand s_rand;
+    __shared__ PslRsRand s_rand;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = A.nrows[c];
     PslPnpResult* res = A.res + c;
@@ -185,15 +186,15 @@ __global__ __launch_bounds__(PSL_PNP_BS) void k_pnp_solve(PnpSolveArgs A) {
     int left = max_its - start_it;
     if (left < A.n_iterations) left = A.n_iterations;
     if (tid == 0 && left > 0) {   // a call that runs no iteration draws nothing
-        psl_ss_srand(&s_rand, A.seed0 + (uint32_t)c);
-        for (int i = 0; i < 4 * start_it; ++i) psl_ss_rand(&s_rand);
+        psl_rs_srand(&s_rand, A.seed0 + (uint32_t)c);
+        for (int i = 0; i < 4 * start_it; ++i) psl_rs_rand(&s_rand);
     }
     __syncthreads();
     for (;;) {   // uniform
         const int nb = left < PSL_PNP_B ? left : PSL_PNP_B;
         if (nb <= 0) break;
         if (tid == 0)
-            for (int h = 0; h < nb; ++h) psl_pnp_draw(&s_rand, n, s_idx[h]);
+            for (int h = 0; h < nb; ++h) psl_rs_draw<4>(&s_rand, n, s_idx[h]);
         __syncthreads();
         if ((tid & 15) == 0 && (tid >> 4) < nb) {
             const int h = tid >> 4;

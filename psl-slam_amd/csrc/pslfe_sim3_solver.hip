@@ -1,8 +1,9 @@
 // libpslfe: Sim3Solver (src/Sim3Solver.cc), the RANSAC of LoopClosing::ComputeSim3 (src/LoopClosing.cc:284-345), for K loop candidates
 // in one launch.  Product code.
-// Who owns what.  sim3_solver_kernels.h holds everything a single thread computes - the staging of a pair, glibc's rand() and the
-// draw, Horn's closed form with OpenCV's Jacobi (psl_ss_hypothesis), the inlier test of a pair - and the reference's loop on one core
-// (psl_ss_iterate), which tools/dropin/sim3_solver_main.cpp runs and tests/sim3_solver_cases.py restates in numpy.  Here: which thread
+// Who owns what.  sim3_solver_kernels.h holds everything a single thread computes - the staging of a pair, Horn's closed form with
+// OpenCV's eigen Jacobi (psl_ss_hypothesis), the inlier test of a pair - and the reference's loop on one core (psl_ss_iterate), which
+// tools/dropin/sim3_solver_main.cpp runs and tests/sim3_solver_cases.py restates in numpy; glibc's rand() and the draw are those of
+// ransac_kernels.h, shared with the other RANSAC solvers.  Here: which thread
 // computes which hypothesis and which pair, the LDS copy of the staged pairs, the error paths, and the driver in blocks.
 //
 // The driver in blocks.  Sim3Solver::iterate evaluates one hypothesis after the other and returns at the first iteration i whose
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(PSL_SS_BS) void k_sim3_solve(Sim3SolverArgs A) {
     __shared__ PslSsHyp s_hyp[PSL_SS_BLOCK];
     __shared__ int s_idx[PSL_SS_BLOCK][3];
     __shared__ int s_cnt[PSL_SS_BLOCK];
-    __shared__ PslSsRand s_rand;
+    __shared__ PslRsRand s_rand;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = A.npairs[c];
     PslSim3SolverResult* res = A.res + c;
@@ -119,8 +120,8 @@ __global__ __launch_bounds__(PSL_SS_BS) void k_sim3_solve(Sim3SolverArgs A) {
     const int max_its = A.tab[n - A.min_inliers];
     int it = start_it, best = best_in, budget = A.n_iterations;
     if (tid == 0 && it < max_its && budget > 0) {   // a call that runs no iteration draws nothing
-        psl_ss_srand(&s_rand, A.seed0 + (uint32_t)c);
-        for (int i = 0; i < 3 * start_it; ++i) psl_ss_rand(&s_rand);
+        psl_rs_srand(&s_rand, A.seed0 + (uint32_t)c);
+        for (int i = 0; i < 3 * start_it; ++i) psl_rs_rand(&s_rand);
     }
     __syncthreads();
     for (;;) {   // uniform
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(PSL_SS_BS) void k_sim3_solve(Sim3SolverArgs A) {
         if (PSL_SS_BLOCK < nb) nb = PSL_SS_BLOCK;
         if (nb <= 0) break;
         if (tid == 0)
-            for (int h = 0; h < nb; ++h) psl_ss_draw(&s_rand, n, s_idx[h]);
+            for (int h = 0; h < nb; ++h) psl_rs_draw<3>(&s_rand, n, s_idx[h]);
         __syncthreads();
         {
             const int h = wave * 16 + lane;

@@ -8,7 +8,7 @@
 // Restated from the reference, rounding by rounding (DESIGN.md §3 lists every convention):
 //   the thresholds, FromCameraToImage          src/Sim3Solver.cc:84-88, :405-423; include/Sim3Solver.h:78-79 (vector<size_t>)
 //   SetRansacParameters                        :114-138
-//   the draw                                   :163-177; Thirdparty/DBoW2/DUtils/Random.cpp:47-50
+//   the draw                                   :163-177: psl_rs_draw<3> of ransac_kernels.h, with glibc's rand() and RandomInt
 //   ComputeCentroid, ComputeSim3               :215-337
 //   Project, CheckInliers                      :382-403, :340-364
 //   iterate                                    :140-207
@@ -18,7 +18,8 @@
 #ifndef PSL_SIM3_SOLVER_KERNELS_H
 #define PSL_SIM3_SOLVER_KERNELS_H
 
-#include "pose_kernels.h"
+#include "pose_kernels.h"   // psl_glibc_sin, psl_glibc_cos
+#include "ransac_kernels.h"
 
 #ifndef PSL_F64_QUAL
 #define PSL_F64_QUAL PSL_PO_HD
@@ -30,15 +31,7 @@
 #endif
 
 #define PSL_SS_HD PSL_PO_HD
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PSL_SS_FDIV(a, b) __fdiv_rn((a), (b))
-#else
-#define PSL_SS_FDIV(a, b) ((a) / (b))
-#endif
-
 #define PSL_SS_STAGED_FLOATS 12     // X1[3] X2[3] p1[2] p2[2] th1 th2
-#define PSL_SS_FLT_EPSILON 1.1920928955078125e-07f
-#define PSL_SS_DBL_EPSILON 2.220446049250313e-16
 #define PSL_SS_SINCOS_RANGE 105414350.0   // psl_sincos_glibc.h
 
 struct PslSsCams {
@@ -50,55 +43,6 @@ struct PslSsHyp {
     float R[9], t[3], s;
     float T12[12], T21[12];   // row-major 3x4
 };
-
-// ---- glibc rand(): the TYPE_3 additive feedback generator, as pslfe_glue.hip restates it ---------------------------------------------
-struct PslSsRand {
-    uint32_t ring[34];
-    int k;
-};
-PSL_SS_HD void psl_ss_srand(PslSsRand* G, uint32_t seed) {
-    int32_t prev = seed == 0 ? 1 : (int32_t)seed;
-    G->ring[0] = (uint32_t)prev;
-    for (int i = 1; i < 31; ++i) {
-        const long long hi = prev / 127773, lo = prev % 127773;
-        long long word = 16807 * lo - 2836 * hi;
-        if (word < 0) word += 2147483647;
-        prev = (int32_t)word;
-        G->ring[i] = (uint32_t)prev;
-    }
-    for (int i = 31; i < 34; ++i) G->ring[i] = G->ring[i - 31];
-    for (int kk = 34; kk < 34 + 310; ++kk) G->ring[kk % 34] = G->ring[(kk - 31) % 34] + G->ring[(kk - 3) % 34];
-    G->k = 34 + 310;
-}
-PSL_SS_HD int psl_ss_rand(PslSsRand* G) {
-    const int k = G->k;
-    const uint32_t v = G->ring[(k - 31) % 34] + G->ring[(k - 3) % 34];
-    G->ring[k % 34] = v;
-    G->k = k + 1 >= 34 * 64 ? k + 1 - 34 * 63 : k + 1;   // the position matters modulo 34 alone
-    return (int)(v >> 1);
-}
-
-// DUtils::Random::RandomInt(0, d - 1): int(((double)rand() / ((double)RAND_MAX + 1.0)) * d).  rand() / 2^31 is exact and the product
-// has at most 42 significant bits, so the double expression is the integer (r * d) >> 31.
-PSL_SS_HD int psl_ss_random_int(int r, int d) { return (int)(((unsigned long long)(unsigned)r * (unsigned long long)(unsigned)d) >> 31); }
-
-// The three draws of one iteration (:163-177): an index is removed by overwriting it with the back of vAvailableIndices and popping.
-// The vector is never built: position p holds p unless one of the (at most two) earlier removals wrote to it.
-PSL_SS_HD void psl_ss_draw(PslSsRand* G, int N, int* idx3) {
-    int opos[2] = {-1, -1}, oval[2] = {0, 0};
-    int size = N;
-    for (int i = 0; i < 3; ++i) {
-        const int randi = psl_ss_random_int(psl_ss_rand(G), size);
-        int idx = randi, back = size - 1;
-        if (opos[0] == randi) idx = oval[0];
-        if (opos[1] == randi) idx = oval[1];
-        if (opos[0] == size - 1) back = oval[0];
-        if (opos[1] == size - 1) back = oval[1];
-        idx3[i] = idx;
-        if (i < 2) { opos[i] = randi; oval[i] = back; }
-        --size;
-    }
-}
 
 // ---- the iteration budget (SetRansacParameters :114-138): host arithmetic with the host's libm, tabulated per N for the device -----
 #include <math.h>
@@ -125,7 +69,7 @@ PSL_SS_HD float psl_ss_max_error(float sigma2) {
 }
 // FromCameraToImage (:405-423): invz = 1 / z in float; fx * x + cx is two float operations
 PSL_SS_HD void psl_ss_to_image(const float* X, float fx, float fy, float cx, float cy, float* p) {
-    const float invz = PSL_SS_FDIV(1.f, X[2]);
+    const float invz = PSL_RS_FDIV(1.f, X[2]);
     const float x = X[0] * invz, y = X[1] * invz;
     p[0] = fx * x + cx;
     p[1] = fy * y + cy;
@@ -213,7 +157,7 @@ PSL_SS_HD int psl_ss_jacobi4(float* A, float* W, float* V) {
             if (mv < v) { mv = v; k = indC[i]; l = i; }
         }
         const float p = A[4 * k + l];
-        if (!(__builtin_fabsf(p) > PSL_SS_FLT_EPSILON)) break;   // also ends on a NaN pivot (the reference would spin to its limit)
+        if (!(__builtin_fabsf(p) > PSL_RS_FLT_EPSILON)) break;   // also ends on a NaN pivot (the reference would spin to its limit)
         const double pd = (double)p, y = (double)(W[l] - W[k]) * 0.5;
         double td = __builtin_fabs(y) + psl_ss_hypot(pd, y);
         double sd = psl_ss_hypot(pd, td);
@@ -254,7 +198,7 @@ PSL_SS_HD int psl_ss_jacobi4(float* A, float* W, float* V) {
 PSL_SS_HD void psl_ss_rodrigues(const float* v, const double* tab, float* R) {
     double r[3] = {(double)v[0], (double)v[1], (double)v[2]};
     const double theta = PSL_PO_SQRT((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
-    if (theta < PSL_SS_DBL_EPSILON) {
+    if (theta < PSL_RS_DBL_EPSILON) {
         for (int i = 0; i < 9; ++i) R[i] = (i % 4) == 0 ? 1.f : 0.f;
         return;
     }
@@ -377,17 +321,17 @@ PSL_SS_HD PslSsOutcome psl_ss_iterate(const float* staged, int N, const PslSsCam
     PslSsOutcome o = {0, start_it, 0, best_in};
     for (int i = 0; i < N; ++i) flags[i] = 0;
     if (N < min_inliers) { o.status = 2; return o; }
-    PslSsRand G;
+    PslRsRand G;
     if (start_it < max_its && n_iterations > 0) {   // a call that runs no iteration draws nothing
-        psl_ss_srand(&G, seed);
-        for (int i = 0; i < 3 * start_it; ++i) psl_ss_rand(&G);
+        psl_rs_srand(&G, seed);
+        for (int i = 0; i < 3 * start_it; ++i) psl_rs_rand(&G);
     }
     int cur = 0;
     while (o.iterations < max_its && cur < n_iterations) {
         ++cur;
         ++o.iterations;
         int idx[3];
-        psl_ss_draw(&G, N, idx);
+        psl_rs_draw<3>(&G, N, idx);
         float P1[9], P2[9];
         psl_ss_gather(staged + 12 * idx[0], staged + 12 * idx[1], staged + 12 * idx[2], P1, P2);
         PslSsHyp h;

@@ -11,7 +11,7 @@ import math
 
 import numpy as np
 
-from sim3_solver_cases import GlibcRand, random_int, same_floats  # noqa: F401  (glibc's generator is restated once)
+from sim3_solver_cases import GlibcRand, draw, random_int, same_floats  # noqa: F401  (glibc's generator and the draw are restated once)
 
 F = np.float32
 D = np.float64
@@ -37,21 +37,9 @@ def f32(x):
 
 
 # ---- the draw (:77-97) ---------------------------------------------------------------------------------------------------------------
-def draw8(G, N):
-    """the eight draws of one set with the vector of available indices written out"""
-    avail = list(range(N))
-    out = []
-    for _ in range(8):
-        randi = random_int(G.rand(), len(avail))
-        out.append(avail[randi])
-        avail[randi] = avail[-1]
-        avail.pop()
-    return out
-
-
 def sets(seed, N, max_its):
     G = GlibcRand(seed)
-    return np.array([draw8(G, N) for _ in range(max_its)], np.int32).reshape(max_its, 8)
+    return np.array([draw(G, N, 8) for _ in range(max_its)], np.int32).reshape(max_its, 8)
 
 
 # ---- Normalize (:749-795) ------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-from sim3_solver_cases import GlibcRand, random_int, same_floats  # noqa: F401  (glibc's generator is restated once)
+from sim3_solver_cases import GlibcRand, draw, random_int, same_floats  # noqa: F401  (glibc's generator and the draw are restated once)
 
 F = np.float32
 POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,))])
@@ -64,21 +64,18 @@ def ransac_parameters(N, prob, min_inliers, max_its, min_set, epsilon):
     return max(1, min(n, max_its)), n_min
 
 
-def draw4(G, N):
-    """the four draws of one iteration with the vector of available indices written out (:188-201)"""
-    avail = list(range(N))
-    out = []
-    for _ in range(4):
-        randi = random_int(G.rand(), len(avail))
-        out.append(avail[randi])
-        avail[randi] = avail[-1]
-        avail.pop()
-    return out
-
-
 # ---- this library's reading of JacobiSVDImpl_<double> ------------------------------------------------------------------------------------
 def jacobi_rows(At, want_v):
     """At: n lists of length m, changed in place into U^T (rows normalised); -> (w descending, Vt or None)"""
+    W, Vt = jacobi_sweeps(At, want_v)
+    for i in range(len(At)):
+        s = _div(1.0, W[i]) if W[i] > DBL_MIN else 0.0
+        At[i] = [t * s for t in At[i]]
+    return W, Vt
+
+
+def jacobi_sweeps(At, want_v):
+    """jacobi_rows before its normalisation: the rows of At are left as the rotations and the sort leave them"""
     n, m = len(At), len(At[0])
     eps = DBL_EPSILON * 10
     W = []
@@ -140,9 +137,6 @@ def jacobi_rows(At, want_v):
             At[i], At[j] = At[j], At[i]
             if want_v:
                 Vt[i], Vt[j] = Vt[j], Vt[i]
-    for i in range(n):
-        s = _div(1.0, W[i]) if W[i] > DBL_MIN else 0.0
-        At[i] = [t * s for t in At[i]]
     return W, Vt
 
 
@@ -479,7 +473,7 @@ class Solver:
         while self.iterations < self.max_its or cur < n_iterations:
             cur += 1
             self.iterations += 1
-            idx = draw4(self.G, self.N)
+            idx = draw(self.G, self.N, 4)
             R, t = compute_pose(*self._corr(idx), self.cam)
             flags = check_inliers(self.rows, self.maxerr, R, t, self.cam)
             cnt = int(flags.sum())

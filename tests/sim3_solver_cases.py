@@ -144,11 +144,12 @@ def random_int(r, d):
     return int((float(r) / (2147483647.0 + 1.0)) * d)
 
 
-def draw(G, N):
-    """the three draws of one iteration with the vector of available indices written out (:163-177)"""
+def draw(G, N, k=3):
+    """the k draws of one iteration with the vector of available indices written out (Sim3Solver.cc:163-177 with k = 3,
+    PnPsolver.cc:188-201 with 4, Initializer.cc:82-97 with 8)"""
     avail = list(range(N))
     out = []
-    for _ in range(3):
+    for _ in range(k):
         randi = random_int(G.rand(), len(avail))
         out.append(avail[randi])
         avail[randi] = avail[-1]

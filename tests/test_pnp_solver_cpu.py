@@ -167,7 +167,7 @@ def test_draw_equals_swap_and_pop(host_exe, tmp_path, N):
     assert p.returncode == 0 and not p.stderr, p.stderr[-2000:]
     got = np.fromfile(out, np.int32).reshape(its, 4)
     G = pc.GlibcRand(seed)
-    want = np.array([pc.draw4(G, N) for _ in range(its)], np.int32)
+    want = np.array([pc.draw(G, N, 4) for _ in range(its)], np.int32)
     assert (got == want).all()
     assert all(len(set(r)) == 4 for r in got[:200]) and got.max() == N - 1 and got.min() == 0
 

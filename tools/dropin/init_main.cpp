@@ -81,12 +81,12 @@ int main(int argc, char** argv) {
     if (argc == 6 && !strcmp(argv[1], "--sets")) {
         const int N = atoi(argv[2]), its = atoi(argv[4]);
         if (N < 8 || its < 0) { fprintf(stderr, "bad --sets arguments\n"); return 2; }
-        PslSsRand G;
-        psl_ss_srand(&G, (uint32_t)strtoul(argv[3], nullptr, 10));
+        PslRsRand G;
+        psl_rs_srand(&G, (uint32_t)strtoul(argv[3], nullptr, 10));
         std::vector<int32_t> out(8 * (size_t)its);
         for (int i = 0; i < its; ++i) {
             int idx[8];
-            psl_init_draw8(&G, N, idx);
+            psl_rs_draw<8>(&G, N, idx);
             for (int j = 0; j < 8; ++j) out[8 * (size_t)i + j] = idx[j];
         }
         FILE* o = fopen(argv[5], "wb");

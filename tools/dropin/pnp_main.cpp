@@ -9,7 +9,7 @@
 // build under the address and undefined-behaviour sanitizers; tools/bench_pnp_solver.py times it).
 //
 // usage: pnp_main <cases.bin> <out.bin> [repeat]
-//        pnp_main --draw <N> <seed> <iterations> <out.bin>     the draws of psl_pnp_draw on one stream, int32 [iterations][4]
+//        pnp_main --draw <N> <seed> <iterations> <out.bin>     the draws of psl_rs_draw<4> on one stream, int32 [iterations][4]
 //   cases.bin: int32 K, rstride, min_set; double prob; float th2; PslCamera cam;
 //              K x { uint32 seed; int32 n, min_inliers, max_its, n_iterations, reject; float epsilon; PslPnpRow rows[n] }   (n <= rstride)
 //   out.bin:   one section per form - "loop", then (library builds) "device" (pslfe::PnPsolver::SolveDevice, one launch per candidate
@@ -115,15 +115,15 @@ bool writeSection(FILE* o, const std::vector<Result>& rs) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc == 6 && !strcmp(argv[1], "--draw")) {   // --draw N seed iterations out.bin: int32 [iterations][4], psl_pnp_draw on one stream
+    if (argc == 6 && !strcmp(argv[1], "--draw")) {   // --draw N seed iterations out.bin: int32 [iterations][4], psl_rs_draw<4> on one stream
         const int N = atoi(argv[2]), its = atoi(argv[4]);
         if (N < 4 || its < 0) { fprintf(stderr, "bad --draw arguments\n"); return 2; }
-        PslSsRand G;
-        psl_ss_srand(&G, (uint32_t)strtoul(argv[3], nullptr, 10));
+        PslRsRand G;
+        psl_rs_srand(&G, (uint32_t)strtoul(argv[3], nullptr, 10));
         std::vector<int32_t> out((size_t)its * 4 + 1);
         for (int i = 0; i < its; ++i) {
             int idx[4];
-            psl_pnp_draw(&G, N, idx);
+            psl_rs_draw<4>(&G, N, idx);
             for (int k = 0; k < 4; ++k) out[(size_t)i * 4 + k] = idx[k];
         }
         FILE* o = fopen(argv[5], "wb");
