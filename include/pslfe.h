@@ -1513,7 +1513,7 @@ int pslfe_init_debug_select(pslfe_ctx* ctx, const float* cosines, int n, uint32_
  * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1025-1966, the call of LocalMapping::Run src/LocalMapping.cc:84) and the
  * EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ part of LocalBundleAdjustmentAndInseclines (:1968-2534) from the optimiser's set-up on:
  * the two rounds optimize(5) with Huber and optimize(10) without the outliers (:1642-1790, :2356-2456) over g2o's Levenberg, the
- * Schur complement of BlockSolver<6,3> and a dense solve of the reduced camera system.  The VertexLIL vertices are not part of it.
+ * Schur complement of BlockSolver<6,3> and a dense solve of the reduced camera system.  The VertexLIL vertices are not part of these entry points (pslfe_ba_local_lil[_device] below add them).
  * Building the lists (lLocalKeyFrames, lFixedCameras, lLocalMapPoints) and the tail (erase, SetPose, SetWorldPos) stay host code:
  * INTEGRATION.md "LocalBundleAdjustment".  Parity: "HIP == host compile of the same header == restatement", bit for bit; parity with
  * g2o itself is unpinned (DESIGN.md §3 lists what is pinned to g2o's text and what is this library's reading: the 3x3 inverse, the
@@ -1569,6 +1569,49 @@ int pslfe_ba_local_device(pslfe_ba* ba, int K, const PslBaKeyFrame* d_kf, const 
  * 1..2: PSLFE_E_INVALID before any device is touched.  A negative status of the problem is also the return value. */
 int pslfe_ba_local(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const PslMapPointGeom* mp, int nmp, const PslBaEdge* edges, int nedges,
                    const PslCamera* cam, int rounds, PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslBaInfo* info);
+
+/* ---- Local bundle adjustment with the VertexLIL vertices: Optimizer::LocalBundleAdjustmentAndInseclines ------------------------------
+ * The call LocalMapping::Run makes (src/LocalMapping.cc:84; src/Optimizer.cc:1968-2534): the point edges above plus one VertexLIL per
+ * local InsectLine (:2250-2290: 15 doubles, marginalised, ids above every map point id, so the LILs follow the points) and one
+ * EdgeLILSE3ProjectXYZ per (LIL, observing keyframe) (:2295-2346, add_inc/EdgeLIL.h:210-439), created after all point edges:
+ * information 0.01 * I6 (`double invSigma = 0.01`, :1970), Huber with delta (float)sqrt(11.07), levels and erase flags by
+ * `chi2() > 11.07 || !isDepthPositive()` in double (:2401-2414, :2464-2478).  VertexLIL::oplusImpl adds FIFTEEN doubles of the update
+ * vector to a vertex that owns three (add_inc/VertexLIL.h:23-27, sparse_optimizer.cpp:425-434): segment m of an active LIL receives the
+ * step of the m-th next active LIL; past the end of the active update vector this library reads 0.0, where the reference's value is
+ * indeterminate (solver.cpp:51-57) - parity at the last four active LILs is unpinned even against a g2o build. */
+typedef struct PslBaLilEdge {
+    int32_t lil, kf;             /* rows of the problem's LIL and keyframe arrays */
+    double obs1[3];              /* pKF->mvle_l[idx].first  (src/Optimizer.cc:2305-2307) */
+    double obs2[3];              /* pKF->mvle_l[idx].second */
+    double obs_ins[2];           /* pKF->CrossPoint_2D[idx] */
+} PslBaLilEdge;
+#ifdef __cplusplus
+static_assert(sizeof(PslBaLilEdge) == 72, "local BA LIL edge");
+#else
+_Static_assert(sizeof(PslBaLilEdge) == 72, "local BA LIL edge");
+#endif
+/* pslfe_ba_create with room for up to max_lils LILs and max_lil_edges LIL edges per problem (both >= 0).  A handle from
+ * pslfe_ba_create has LIL caps of 0: a problem with a LIL row or a LIL edge is refused with PSLFE_E_CAPACITY. */
+int pslfe_ba_create_lil(pslfe_ctx* ctx, int max_problems, int max_keyframes, int max_points, int max_edges, int max_lils, int max_lil_edges,
+                        pslfe_ba** out);
+/* == pslfe_ba_local_device with the LILs of src/Optimizer.cc:2250-2533.  Problem k has also the LIL rows d_lil[d_lil_off[k] ..)
+ *    (PslMapLil: w is read and written, `bad` is copied and not read - the pML->isBad() skip is the caller's) and the LIL edges
+ *    d_lil_edges[d_lil_edge_off[k] ..) in the order the reference creates them.  Outputs: d_lil_out (the 15 doubles of every LIL,
+ *    :2526-2531; a LIL without an edge is copied; may be d_lil; it is what pslfe_pose_lil_edges_device reads as d_map), d_erase_lil
+ *    (one byte per LIL edge, :2464-2478), d_nerased_lil (may be NULL: the set bytes of d_erase_lil per problem).  d_info[k]: its chi2
+ *    values cover both kinds of edges, nerased counts point edges.  nmp == 0 is allowed.  Per problem: a LIL edge that names a row
+ *    outside the problem or a duplicate (LIL, keyframe) pair: PSLFE_E_INVALID; counts above the caps: PSLFE_E_CAPACITY; such a
+ *    problem leaves all three outputs equal to its inputs.  With every LIL count 0 the results are the bytes of
+ *    pslfe_ba_local_device.  The whole-call rules are those of pslfe_ba_local_device (every array but d_nerased_lil is required). */
+int pslfe_ba_local_lil_device(pslfe_ba* ba, int K, const PslBaKeyFrame* d_kf, const int32_t* d_kf_off, const PslMapPointGeom* d_mp,
+                              const int32_t* d_mp_off, const PslBaEdge* d_edges, const int32_t* d_edge_off, const PslMapLil* d_lil,
+                              const int32_t* d_lil_off, const PslBaLilEdge* d_lil_edges, const int32_t* d_lil_edge_off, const PslCamera* cam,
+                              int rounds, PslBaKeyFrame* d_kf_out, PslMapPointGeom* d_mp_out, uint8_t* d_erase, PslMapLil* d_lil_out,
+                              uint8_t* d_erase_lil, int32_t* d_nerased_lil, PslBaInfo* d_info);
+/* One problem, host arrays, as pslfe_ba_local. */
+int pslfe_ba_local_lil(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const PslMapPointGeom* mp, int nmp, const PslBaEdge* edges, int nedges,
+                       const PslMapLil* lil, int nlil, const PslBaLilEdge* lil_edges, int nlil_edges, const PslCamera* cam, int rounds,
+                       PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslMapLil* lil_out, uint8_t* erase_lil, PslBaInfo* info);
 
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;

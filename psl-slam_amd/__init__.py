@@ -70,6 +70,8 @@ BAEDGE_DTYPE = np.dtype([("point", "<i4"), ("kf", "<i4"), ("u", "<f4"), ("v", "<
 BAKEYFRAME_DTYPE = np.dtype([("Tcw", POSE_DTYPE), ("fixed", "<i4")])
 BAINFO_DTYPE = np.dtype({"names": ["status", "rounds", "iterations", "nerased", "chi2_start", "chi2_round1", "chi2_end"],
                          "formats": ["<i4", "<i4", ("<i4", (2,)), "<i4", "<f8", "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24, 32, 40], "itemsize": 48})
+BALILEDGE_DTYPE = np.dtype([("lil", "<i4"), ("kf", "<i4"), ("obs1", "<f8", (3,)), ("obs2", "<f8", (3,)), ("obs_ins", "<f8", (2,))])
+assert BALILEDGE_DTYPE.itemsize == 72
 assert BAEDGE_DTYPE.itemsize == 24 and BAKEYFRAME_DTYPE.itemsize == 52 and BAINFO_DTYPE.itemsize == 48
 
 
@@ -674,13 +676,18 @@ def search_by_projection_map_device(frame, slot0, npairs, d_queries, d_qdesc, d_
 
 class BundleAdjuster:
     """The HBM workspaces of the local bundle adjustment (pslfe_ba): up to max_problems problems per launch of up to max_keyframes
-    keyframes (free and fixed), max_points points and max_edges edges each."""
+    keyframes (free and fixed), max_points points and max_edges edges each; with max_lils / max_lil_edges (both given) also of that
+    many VertexLIL rows and LIL edges (pslfe_ba_create_lil), without them the LIL caps are 0."""
 
-    def __init__(self, max_problems, max_keyframes, max_points, max_edges, ctx=None):
+    def __init__(self, max_problems, max_keyframes, max_points, max_edges, max_lils=None, max_lil_edges=None, ctx=None):
         self.ctx = ctx or default_context()
         self._h = C.c_void_p()
-        _check(lib().pslfe_ba_create(self.ctx._h, C.c_int(max_problems), C.c_int(max_keyframes), C.c_int(max_points), C.c_int(max_edges),
-                                     C.byref(self._h)), "pslfe_ba_create")
+        if max_lils is None and max_lil_edges is None:
+            _check(lib().pslfe_ba_create(self.ctx._h, C.c_int(max_problems), C.c_int(max_keyframes), C.c_int(max_points), C.c_int(max_edges),
+                                         C.byref(self._h)), "pslfe_ba_create")
+        else:
+            _check(lib().pslfe_ba_create_lil(self.ctx._h, C.c_int(max_problems), C.c_int(max_keyframes), C.c_int(max_points), C.c_int(max_edges),
+                                             C.c_int(max_lils or 0), C.c_int(max_lil_edges or 0), C.byref(self._h)), "pslfe_ba_create_lil")
 
     def close(self):
         if self._h:
@@ -698,7 +705,8 @@ class BundleAdjuster:
 class Optimizer:
     """Optimizer::PoseOptimization src/Optimizer.cc:239-1023: the point edges (EdgeSE3ProjectXYZOnlyPose and
     EdgeStereoSE3ProjectXYZOnlyPose) and the LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the `lil` argument and the *Lil*
-    methods); Optimizer::LocalBundleAdjustment :1025-1966, its point edges.  Parity with g2o itself is unpinned (DESIGN.md §3)."""
+    methods); Optimizer::LocalBundleAdjustment :1025-1966, its point edges, and LocalBundleAdjustmentAndInseclines :1968-2534 with the
+    VertexLIL vertices.  Parity with g2o itself is unpinned."""
 
     @staticmethod
     def LocalBundleAdjustment(ba, kfs, mps, edges, cam, rounds=2):
@@ -727,6 +735,40 @@ class Optimizer:
             ba._h, C.c_int(K), C.c_void_p(d_kf or None), C.c_void_p(d_kf_off or None), C.c_void_p(d_mp or None), C.c_void_p(d_mp_off or None),
             C.c_void_p(d_edges or None), C.c_void_p(d_edge_off or None), _ptr(cam), C.c_int(rounds), C.c_void_p(d_kf_out or None),
             C.c_void_p(d_mp_out or None), C.c_void_p(d_erase or None), C.c_void_p(d_info or None)), "pslfe_ba_local_device")
+
+    @staticmethod
+    def LocalBundleAdjustmentAndInseclines(ba, kfs, mps, edges, lils, lil_edges, cam, rounds=2):
+        """Optimizer::LocalBundleAdjustmentAndInseclines src/Optimizer.cc:1968-2534 (the call of LocalMapping::Run), one problem, host
+        arrays: LocalBundleAdjustment's arguments plus lils MAPLIL_DTYPE[nlil] (w is read and written) and lil_edges
+        BALILEDGE_DTYPE[nle] in the order the reference creates them.  -> (kfs_out, mps_out, erase u8 [ne], lils_out, erase_lil u8
+        [nle], info).  ba needs LIL caps.  A refused problem raises PslfeError."""
+        k = np.ascontiguousarray(kfs, BAKEYFRAME_DTYPE).reshape(-1)
+        m = np.ascontiguousarray(mps, MAPPOINT_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(edges, BAEDGE_DTYPE).reshape(-1)
+        l = np.ascontiguousarray(lils, MAPLIL_DTYPE).reshape(-1)
+        f = np.ascontiguousarray(lil_edges, BALILEDGE_DTYPE).reshape(-1)
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        ko, mo, er = np.zeros(max(len(k), 1), BAKEYFRAME_DTYPE), np.zeros(max(len(m), 1), MAPPOINT_DTYPE), np.zeros(max(len(e), 1), np.uint8)
+        lo, el = np.zeros(max(len(l), 1), MAPLIL_DTYPE), np.zeros(max(len(f), 1), np.uint8)
+        info = np.zeros(1, BAINFO_DTYPE)
+        p = lambda a, n: _ptr(a) if n else None
+        _check(lib().pslfe_ba_local_lil(ba._h, p(k, len(k)), C.c_int(len(k)), p(m, len(m)), C.c_int(len(m)), p(e, len(e)), C.c_int(len(e)),
+                                        p(l, len(l)), C.c_int(len(l)), p(f, len(f)), C.c_int(len(f)), _ptr(cam), C.c_int(rounds), p(ko, len(k)),
+                                        p(mo, len(m)), p(er, len(e)), p(lo, len(l)), p(el, len(f)), _ptr(info)), "pslfe_ba_local_lil")
+        return ko[:len(k)], mo[:len(m)], er[:len(e)], lo[:len(l)], el[:len(f)], info[0]
+
+    @staticmethod
+    def LocalBundleAdjustmentAndInseclinesDevice(ba, K, d_kf, d_kf_off, d_mp, d_mp_off, d_edges, d_edge_off, d_lil, d_lil_off, d_lil_edges,
+                                                 d_lil_edge_off, cam, rounds, d_kf_out, d_mp_out, d_erase, d_lil_out, d_erase_lil, d_nerased_lil,
+                                                 d_info):
+        """K problems in one launch, HBM to HBM, asynchronous: LocalBundleAdjustmentDevice plus the LIL rows, LIL edges and their
+        offsets; d_lil_out may be d_lil and is what pose_lil_edges_device reads as its map; d_nerased_lil (int32 [K]) may be 0."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        v = lambda d: C.c_void_p(d or None)
+        _check(lib().pslfe_ba_local_lil_device(
+            ba._h, C.c_int(K), v(d_kf), v(d_kf_off), v(d_mp), v(d_mp_off), v(d_edges), v(d_edge_off), v(d_lil), v(d_lil_off), v(d_lil_edges),
+            v(d_lil_edge_off), _ptr(cam), C.c_int(rounds), v(d_kf_out), v(d_mp_out), v(d_erase), v(d_lil_out), v(d_erase_lil), v(d_nerased_lil),
+            v(d_info)), "pslfe_ba_local_lil_device")
 
     @staticmethod
     def PoseOptimization(Tcw, edges, cam, ctx=None, lil=None):

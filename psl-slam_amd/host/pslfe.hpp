@@ -1165,6 +1165,10 @@ public:
     BundleAdjuster(Context& ctx, int maxProblems, int maxKeyframes, int maxPoints, int maxEdges) {
         check(pslfe_ba_create(ctx.get(), maxProblems, maxKeyframes, maxPoints, maxEdges, &h_), "pslfe_ba_create");
     }
+    // with room for maxLils VertexLIL rows and maxLilEdges LIL edges per problem (LocalBundleAdjustmentAndInseclines)
+    BundleAdjuster(Context& ctx, int maxProblems, int maxKeyframes, int maxPoints, int maxEdges, int maxLils, int maxLilEdges) {
+        check(pslfe_ba_create_lil(ctx.get(), maxProblems, maxKeyframes, maxPoints, maxEdges, maxLils, maxLilEdges, &h_), "pslfe_ba_create_lil");
+    }
     ~BundleAdjuster() { pslfe_ba_destroy(h_); }
     BundleAdjuster(const BundleAdjuster&) = delete;
     BundleAdjuster& operator=(const BundleAdjuster&) = delete;
@@ -1253,6 +1257,33 @@ public:
                                             int rounds, PslBaKeyFrame* d_kfOut, PslMapPointGeom* d_mpOut, uint8_t* d_erase, PslBaInfo* d_info) {
         check(pslfe_ba_local_device(ba.get(), K, d_kf, d_kfOff, d_mp, d_mpOff, d_edges, d_edgeOff, &cam, rounds, d_kfOut, d_mpOut, d_erase, d_info),
               "pslfe_ba_local_device");
+    }
+    // void Optimizer::LocalBundleAdjustmentAndInseclines(pKF, pbStopFlag, pMap) src/Optimizer.cc:1968-2534, the call of LocalMapping::Run
+    // (src/LocalMapping.cc:84): LocalBundleAdjustment plus lils = one PslMapLil per local InsectLine (:2250-2290, ascending mnId for
+    // g2o's order) and lilEdges = one PslBaLilEdge per (LIL, observing keyframe that is not bad) in the order the reference creates
+    // them (:2295-2346).  lils come back with their 15 doubles (:2526-2531), eraseLil[e] = 1 where :2464-2478 flag the edge.  ba needs
+    // LIL caps.  The update of a VertexLIL follows add_inc/VertexLIL.h:23-27 under the reading of DESIGN.md §3; parity with g2o is unpinned.
+    static PslBaInfo LocalBundleAdjustmentAndInseclines(BundleAdjuster& ba, std::vector<PslBaKeyFrame>& kfs, std::vector<PslMapPointGeom>& mps,
+                                                        const std::vector<PslBaEdge>& edges, std::vector<PslMapLil>& lils,
+                                                        const std::vector<PslBaLilEdge>& lilEdges, const PslCamera& cam, std::vector<uint8_t>& erase,
+                                                        std::vector<uint8_t>& eraseLil, bool doMore = true) {
+        erase.assign(edges.size(), 0);
+        eraseLil.assign(lilEdges.size(), 0);
+        PslBaInfo info = {};
+        check(pslfe_ba_local_lil(ba.get(), kfs.data(), (int)kfs.size(), mps.data(), (int)mps.size(), edges.data(), (int)edges.size(), lils.data(),
+                                 (int)lils.size(), lilEdges.data(), (int)lilEdges.size(), &cam, doMore ? 2 : 1, kfs.data(), mps.data(), erase.data(),
+                                 lils.data(), eraseLil.data(), &info), "pslfe_ba_local_lil");
+        return info;
+    }
+    // K problems in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_ba_local_lil_device (d_nerasedLil may be NULL)
+    static void LocalBundleAdjustmentAndInseclinesDevice(BundleAdjuster& ba, int K, const PslBaKeyFrame* d_kf, const int32_t* d_kfOff,
+                                                         const PslMapPointGeom* d_mp, const int32_t* d_mpOff, const PslBaEdge* d_edges,
+                                                         const int32_t* d_edgeOff, const PslMapLil* d_lil, const int32_t* d_lilOff,
+                                                         const PslBaLilEdge* d_lilEdges, const int32_t* d_lilEdgeOff, const PslCamera& cam, int rounds,
+                                                         PslBaKeyFrame* d_kfOut, PslMapPointGeom* d_mpOut, uint8_t* d_erase, PslMapLil* d_lilOut,
+                                                         uint8_t* d_eraseLil, int32_t* d_nerasedLil, PslBaInfo* d_info) {
+        check(pslfe_ba_local_lil_device(ba.get(), K, d_kf, d_kfOff, d_mp, d_mpOff, d_edges, d_edgeOff, d_lil, d_lilOff, d_lilEdges, d_lilEdgeOff, &cam,
+                                        rounds, d_kfOut, d_mpOut, d_erase, d_lilOut, d_eraseLil, d_nerasedLil, d_info), "pslfe_ba_local_lil_device");
     }
     // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) src/Optimizer.cc:2801-2996: pairs = one PslSim3Pair per
     // match that passes the set-up loop (:2854-2933), in KF1 keypoint order; S12 = what Sim3Solver hands over (src/LoopClosing.cc:
