@@ -21,6 +21,27 @@
 
 #define PSL_LSD_NOTDEF (-1024.0f)   // angle map label for "gradient undefined" (stored as f32 degrees)
 #define PSL_SC64_QUAL __host__ __device__ static inline
+// The constants of psl_cos_sin_2pi_f32, which k_lsd_grow4 evaluates once per region start: each is formed in a scalar register pair
+// right where it is used.  Left to itself the compiler forms all fifteen at the kernel's entry, keeps them in vector registers the
+// 64-register kernel does not have, and reloads them from scratch at every region start - eleven dependent memory round trips in the
+// serial chain (k_lsd_grow4<0, 0> 123 -> 132 ms per launch of 6144 'sticks' frames).  The asm statements are volatile, so they also keep
+// their order among the kernel's other volatile asm statements (the s_waitcnt ones, the pop loop).  The definition only takes effect
+// if this is the translation unit's first inclusion of the include-guarded header: hence the #error.
+#ifdef PSL_SINCOS64_H
+#error "psl_sincos64.h was included before line_kernels.h defined PSL_SC64_K: the grower would reload the constants from scratch"
+#endif
+template <unsigned LO, unsigned HI>
+__host__ __device__ static inline double psl_sc64_here() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int lo, hi;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(lo) : "n"((int)LO));
+    asm volatile("s_mov_b32 %0, %1" : "=s"(hi) : "n"((int)HI));
+    return __hiloint2double(hi, lo);
+#else
+    return __builtin_bit_cast(double, ((unsigned long long)HI << 32) | LO);
+#endif
+}
+#define PSL_SC64_K(c) psl_sc64_here<(unsigned)(__builtin_bit_cast(unsigned long long, (double)(c)) & 0xffffffffull), (unsigned)(__builtin_bit_cast(unsigned long long, (double)(c)) >> 32)>()
 #include "psl_sincos64.h"
 #include "psl_sincos_glibc.h"
 #define PSL_F64_QUAL __host__ __device__ static inline
@@ -207,9 +228,10 @@ __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uin
 // LSD step 2 (ll_angle): 2x2 gradient, norm (f64, correctly rounded sqrt), level-line angle by the
 // f32 fastAtan2 polynomial.  The angle is stored as f32 degrees (the reference's double is exactly
 // double(deg) * DEG_TO_RADS, recomputed where it is used); NOTDEF = -1024.
-// Also tabulates, per pixel with a defined angle a = (double)deg * DEG_TO_RADS, the four values the
-// region-growing chain needs: cosf((float)a), sinf((float)a) (every pixel that joins a region) and
-// (float)cos(a), (float)sin(a) (the seed pixel), so that the serial chain contains no trigonometry.
+// Also tabulates, per pixel with a defined angle a = (double)deg * DEG_TO_RADS, what the region-growing
+// chain needs of every pixel that joins a region: cosf((float)a), sinf((float)a).  The seed's
+// (float)cos(a), (float)sin(a) are evaluated by the grower at each region start in many-frames launches
+// and tabulated here (seedt) only in launches of a few frames (lsdg_region_grow4).
 #define PSL_GRAD_TH 16  // tile height of k_lsd_grad (64 x 16 pixels per workgroup, 4 per thread)
 // squared gradient magnitude of pixel (x, y); false where the reference leaves the angle undefined by construction
 __device__ __forceinline__ bool psl_lsd_norm(const LineParams& P, const double* __restrict__ img, int x, int y, double* q) {
@@ -223,8 +245,10 @@ __device__ __forceinline__ bool psl_lsd_norm(const LineParams& P, const double* 
 }
 
 // trig[o] = (cosf, sinf) of the pixel's angle, (0, 0) where the angle is undefined: what a round of k_lsd_grow4 needs of a neighbour
-// (the angle itself only inside the margin of the decision, read from angdeg then); seedt[o] = (float)cos / sin of the double
-// angle, read once per seed.  A record is only ever read for a pixel with a defined angle or for a neighbour of one, so it is written
+// (the angle itself only inside the margin of the decision, read from angdeg then).  The seed's (float)cos / sin of the double angle
+// is tabulated (seedt[o], read once per seed) only when seedt is given, i.e. in launches of a few frames: about 2 % of the defined pixels
+// ever start a region ('sticks': ~3 000 of ~150 000 per frame), so the grower of a many-frames launch evaluates it from the angle it
+// loads anyway.  A record is only ever read for a pixel with a defined angle or for a neighbour of one, so it is written
 // only for those - about a third of the pixels (16-byte records for every pixel made this kernel HBM-write-bound, 9.4 - 11.5 ms).
 // Which pixels have a defined neighbour is known from a flag tile in LDS: 64 x 16 pixels per workgroup plus a one-pixel ring whose
 // magnitudes are recomputed.  8-byte records: a window row of the growing is 64 bytes, 1 - 2 HBM sectors instead of 2 - 3.
@@ -237,7 +261,7 @@ __device__ __forceinline__ double lsdg_fold(double ad, double theta) {
 }
 __device__ __forceinline__ bool lsdg_aligned(double ad, double theta, double prec) { return lsdg_fold(ad, theta) <= prec; }
 
-// The heavy part of a defined pixel (f64 square root, fastAtan2, two sine / cosine pairs: ~160 vector instructions) runs on the
+// The heavy part of a defined pixel (f64 square root, fastAtan2, one sine / cosine pair - two with seedt: ~130 / ~160 vector instructions) runs on the
 // COMPACTED list of the tile's defined pixels: ~15 % of the pixels have a defined angle and they are scattered, so that run in place
 // nearly every wave executed it for each of its four pixel slots with a handful of lanes active (7.7 ms per 6144 frames).  Phase A
 // (thread = 4 pixels of a column): gradient and squared magnitude, the threshold, NOTDEF angles, the flag tile, and the defined
@@ -330,9 +354,11 @@ __global__ __launch_bounds__(256, PSL_GRAD_WAVES) void k_lsd_grad(LineParams P, 
         const double ad = PSL_DMUL((double)deg, PSL_DEG2RAD);
         float sn, cs;
         psl_sincosf((float)ad, &sn, &cs);
-        float cd, sd;  // (float)cos(ad), (float)sin(ad): restricted-range evaluation, pinned exhaustively (psl_sincos64.h)
-        psl_cos_sin_2pi_f32(ad, &cd, &sd);
-        seedt[o] = make_float2(cd, sd);
+        if (seedt) {   // launches of a few frames: the seed's (float)cos(ad), (float)sin(ad), which the grower of a many-frames launch evaluates itself
+            float cd, sd;
+            psl_cos_sin_2pi_f32(ad, &cd, &sd);
+            seedt[o] = make_float2(cd, sd);
+        }
         s_deg[px] = deg;
         s_cs[px] = make_float2(cs, sn);
     }
@@ -463,7 +489,7 @@ struct LsdW {
     const double* mod;
     const float2* trig;    // (cosf, sinf) per pixel, (0, 0) = angle undefined
     uint8_t* used;         // the reference's `used` map, one byte per pixel
-    const float2* seedt;   // (float)cos, (float)sin of the double angle (seed pixels)
+    const float2* seedt;   // (float)cos, (float)sin of the double angle (seed pixels): launches of a few frames only (HELPERS), else null
     const double* sctab;
     uint32_t* ring;   // LDS mirror of reg[idx & (RING-1)]
     uint32_t* map;    // LDS [64]: window lane -> queue index + 1 (lsdg_region_grow4)
@@ -650,7 +676,7 @@ __device__ __forceinline__ int lsdg_pops2(unsigned long long& cand, unsigned lon
 // `regrow`: the refinement's second growth - its releases of the region's pixels must have completed, nothing is pending.
 // `touched`: set when the region took a pixel whose raster index lies in (seed, trip_end): only then has the seed scan to look
 // at the `used` words of its current 256-pixel trip again.
-template <int LU>
+template <int LU, int TAB>
 __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angle_out, double prec, const LsdgFast fc, LsdgPend& pd,
                                  bool regrow, int trip_end, bool& touched) {
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -668,9 +694,15 @@ __device__ int lsdg_region_grow4(const LsdW& F, int sx, int sy, double* reg_angl
         ring[0] = xy0;
         lsdg_mark<LU>(F, addr0, 1);
     }
-    float reg_deg = F.ang[addr0];       // these two loads and the first window's are in flight together
-    const float2 t0 = F.seedt[addr0];
-    float sumdx = t0.x, sumdy = t0.y;
+    float reg_deg = F.ang[addr0];       // this load (TAB: and the seed vector's) and the first window's are in flight together
+    // The seed's vector: (float)cos, (float)sin of the double angle - restricted-range evaluation, pinned exhaustively (psl_sincos64.h).
+    // Many-frames launches (TAB = 0) evaluate it here, ~50 vector and ~35 scalar instructions per region start that other waves
+    // cover, instead of a table entry per defined pixel of which 2 % were ever read.  A launch of a few frames (TAB = 1) has one
+    // chain per CU and nothing to cover them with (the drop-in consumer lost 0.17 ms per frame, profiles/grow_seed_ab.log): there
+    // k_lsd_grad still tabulates it - a table for those few frames - and the value arrives with the first window.
+    float sumdx, sumdy;
+    if (TAB) { const float2 t0 = F.seedt[addr0]; sumdx = t0.x; sumdy = t0.y; }
+    else psl_cos_sin_2pi_f32(PSL_DMUL((double)reg_deg, PSL_DEG2RAD), &sumdx, &sumdy);
     unsigned long long tch = 0ull;
     int rs_angle = 1;  // the region size reg_deg belongs to (the seed's own angle at 1)
     unsigned long long PA = pd.PA;
@@ -851,7 +883,7 @@ __device__ void lsdw_region2rect(const LsdW& F, int reg_size, double reg_angle, 
     rec->theta = theta; rec->dx = dx; rec->dy = dy;  // read by the NFA validation (LSD_REFINE_ADV) only
 }
 
-template <int LU>
+template <int LU, int TAB>
 __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double prec, LsdRect* rec, double density_th, LsdgPend& pd, int trip_end,
                            bool& touched) {
     double density = psl_lsd_density(reg_size, *rec);
@@ -885,7 +917,7 @@ __device__ int lsdw_refine(const LsdW& F, int reg_size, double reg_angle, double
     const double sum = lsdw_lane_f64(acc, 0), s_sum = lsdw_lane_f64(acc, 1);
     const double mean_angle = sum / (double)n;
     const double tau = PSL_DMUL(2.0, __dsqrt_rn(PSL_DADD(PSL_DSUB(s_sum, PSL_DMUL(PSL_DMUL(2.0, mean_angle), sum)) / (double)n, PSL_DMUL(mean_angle, mean_angle))));
-    reg_size = lsdg_region_grow4<LU>(F, x0, y0, &reg_angle, tau, lsdg_fast_setup(tau), pd, true, trip_end, touched);
+    reg_size = lsdg_region_grow4<LU, TAB>(F, x0, y0, &reg_angle, tau, lsdg_fast_setup(tau), pd, true, trip_end, touched);
     if (reg_size < 2) return 0;
     lsdw_region2rect(F, reg_size, reg_angle, prec, rec);
     density = psl_lsd_density(reg_size, *rec);
@@ -1017,7 +1049,7 @@ __device__ __forceinline__ void psl_lsd_store_segment(const LineParams& P, doubl
 // end in L2 instead of HBM (one frame: 12.9 -> 11.9 ms).  The helpers stay at most 2.5 MB in front of the seed scan, whose position
 // wave 0 publishes in LDS, so that a larger frame (1280x960: 10 MB) keeps a band in front of the scan warm instead of flushing the
 // cache (all of it at once: 25.2 ms against 24.6 ms without helpers).  No effect on results.  Not used with thousands of frames in
-// flight: no L2 to spare and no idle wave slot.  Seed vectors and magnitudes prefetched at defined pixels as well: no further gain.
+// flight: no L2 to spare and no idle wave slot.  Magnitudes prefetched at defined pixels as well: no further gain.
 template <int HELPERS, int LU>
 __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) void k_lsd_grow4(LineParams P, const float* __restrict__ angdeg, const double* __restrict__ modgrad,
                                                    const float2* __restrict__ trig, uint8_t* __restrict__ used, const float2* __restrict__ seedt, uint32_t* __restrict__ reg,
@@ -1031,7 +1063,7 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
     LsdW F;
     F.W = P.W; F.H = P.H; F.lane = lane;
     F.ang = angdeg + frame * npx; F.mod = modgrad + frame * npx; F.trig = trig + frame * npx; F.used = used + frame * npx; F.reg = reg + frame * npx;
-    F.seedt = seedt + frame * npx; F.ring = s_ring; F.term = s_term; F.sctab = P.sctab; F.map = s_map;
+    F.seedt = HELPERS ? seedt + frame * npx : nullptr; F.ring = s_ring; F.term = s_term; F.sctab = P.sctab; F.map = s_map;
     extern __shared__ uint32_t s_ubits[];   // LU: one "used" bit per scaled pixel (the launch passes 4 * words bytes)
     F.ubits = LU ? s_ubits : nullptr;
     __shared__ int s_scan_unit;  // HELPERS: the 64-pixel unit the seed scan has reached (written by wave 0, polled by the helpers)
@@ -1146,12 +1178,12 @@ __global__ __launch_bounds__(64 * (1 + HELPERS), HELPERS ? 1 : PSL_GROW_WAVES) v
                 }
                 double reg_angle;
                 bool touched = false;
-                int reg_size = lsdg_region_grow4<LU>(F, x, y, &reg_angle, P.prec, fcP, pd, false, trip_end, touched);
+                int reg_size = lsdg_region_grow4<LU, (HELPERS != 0)>(F, x, y, &reg_angle, P.prec, fcP, pd, false, trip_end, touched);
                 if (touched) { stale = true; dirty = true; }
                 if (reg_size < P.min_reg_size) continue;
                 LsdRect rec;
                 lsdw_region2rect(F, reg_size, reg_angle, P.prec, &rec);
-                const int kept = lsdw_refine<LU>(F, reg_size, reg_angle, P.prec, &rec, 0.7, pd, trip_end, touched);
+                const int kept = lsdw_refine<LU, (HELPERS != 0)>(F, reg_size, reg_angle, P.prec, &rec, 0.7, pd, trip_end, touched);
                 if (touched) { stale = true; dirty = true; }
                 if (!kept) continue;
                 if (count < P.maxseg && lane == 0) {

@@ -12,6 +12,11 @@
 #ifndef PSL_SC64_QUAL
 #define PSL_SC64_QUAL static inline
 #endif
+// PSL_SC64_K(c): how psl_cos_sin_2pi_f32 takes its constants.  The region growing (line_kernels.h) defines it so that they are
+// formed where they are used; everywhere else it is the constant itself.
+#ifndef PSL_SC64_K
+#define PSL_SC64_K(c) (c)
+#endif
 
 // cos / sin of x in [0, ~4 pi] to about 1 ulp of f64 (n <= 8: n * pio2_1 is exact)
 PSL_SC64_QUAL void psl_cos_sin_f64(double x, double* c, double* s) {
@@ -38,21 +43,21 @@ PSL_SC64_QUAL void psl_cos_sin_f64(double x, double* c, double* s) {
 }
 
 PSL_SC64_QUAL void psl_cos_sin_2pi_f32(double x, float* c, float* s) {
-    const double n = __builtin_rint(x * 6.36619772367581382433e-01);                 // x * 2/pi
-    double r = __builtin_fma(-n, 1.57079632673412561417e+00, x);                     // pio2_1: first 33 bits of pi/2
-    r = __builtin_fma(-n, 6.07710050650619224932e-11, r);                            // pio2_1t: pi/2 - pio2_1
+    const double n = __builtin_rint(x * PSL_SC64_K(6.36619772367581382433e-01));                 // x * 2/pi
+    double r = __builtin_fma(-n, PSL_SC64_K(1.57079632673412561417e+00), x);                     // pio2_1: first 33 bits of pi/2
+    r = __builtin_fma(-n, PSL_SC64_K(6.07710050650619224932e-11), r);                            // pio2_1t: pi/2 - pio2_1
     const double z = r * r;
-    double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-    ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-    ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-    ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
+    double ps = __builtin_fma(z, PSL_SC64_K(1.58969099521155010221e-10), PSL_SC64_K(-2.50507602534068634195e-08));
+    ps = __builtin_fma(z, ps, PSL_SC64_K(2.75573137070700676789e-06));
+    ps = __builtin_fma(z, ps, PSL_SC64_K(-1.98412698298579493134e-04));
+    ps = __builtin_fma(z, ps, PSL_SC64_K(8.33333333332248946124e-03));
+    ps = __builtin_fma(z, ps, PSL_SC64_K(-1.66666666666666324348e-01));
     const double sr = __builtin_fma(z * r, ps, r);
-    double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-    pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-    pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-    pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
+    double pc = __builtin_fma(z, PSL_SC64_K(-1.13596475577881948265e-11), PSL_SC64_K(2.08757232129817482790e-09));
+    pc = __builtin_fma(z, pc, PSL_SC64_K(-2.75573143513906633035e-07));
+    pc = __builtin_fma(z, pc, PSL_SC64_K(2.48015872894767294178e-05));
+    pc = __builtin_fma(z, pc, PSL_SC64_K(-1.38888888888741095749e-03));
+    pc = __builtin_fma(z, pc, PSL_SC64_K(4.16666666666666019037e-02));
     const double cr = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
     const int q = (int)n & 3;
     const double cq = (q & 1) ? sr : cr, sq = (q & 1) ? cr : sr;

@@ -64,7 +64,7 @@ struct pslfe_line {
     float* d_angdeg = nullptr;
     double* d_modgrad = nullptr;
     float2* d_trig = nullptr;     // (cosf, sinf) of the level-line angle per scaled pixel
-    float2* d_seedt = nullptr;
+    float2* d_seedt = nullptr;    // (float)cos / sin of the double angle for seeds: launches of at most PSL_GROW_HELPER_FRAMES frames only
     uint8_t* d_used = nullptr;    // LSD `used` map, one byte per scaled pixel
     uint32_t* d_reg = nullptr;
     LsdnTables NT = {};           // LSD_REFINE_ADV: log_gamma / log(p) tables of nfa() (NT.lg in HBM)
@@ -190,7 +190,7 @@ struct pslfe_line {
         mem.alloc(d_angdeg, npx * F, "d_angdeg");
         mem.alloc(d_modgrad, npx * F, "d_modgrad");
         mem.alloc(d_trig, npx * F, "d_trig");
-        mem.alloc(d_seedt, npx * F, "d_seedt");
+        mem.alloc(d_seedt, npx * std::min<size_t>(F, PSL_GROW_HELPER_FRAMES), "d_seedt");   // many-frames launches evaluate the seed vector in the grower
         mem.alloc(d_used, npx * F, "d_used");
         mem.alloc(d_reg, npx * F, "d_reg");
         mem.alloc(d_seg, (size_t)Q.maxseg * 4 * F, "d_seg");
@@ -268,7 +268,8 @@ struct pslfe_line {
         auto at = [f0](auto* base, size_t per_frame) { return base + (size_t)f0 * per_frame; };
         Part p;
         p.f0 = f0; p.n = n; p.F = F; p.st = st; p.maxseg = S;
-        p.angdeg = at(d_angdeg, npx); p.modgrad = at(d_modgrad, npx); p.trig = at(d_trig, npx); p.seedt = at(d_seedt, npx);
+        p.angdeg = at(d_angdeg, npx); p.modgrad = at(d_modgrad, npx); p.trig = at(d_trig, npx);
+        p.seedt = F <= PSL_GROW_HELPER_FRAMES ? at(d_seedt, npx) : nullptr;   // the table holds the frames of a few-frames launch only
         p.used = at(d_used, npx); p.reg = at(d_reg, npx);
         p.rects = at(d_rects, S * PSL_LSD_RECT_F64); p.nrect = at(d_nrect, 1); p.weight = at(d_weight, 1); p.order = at(d_order, 1);
         p.counts = at(d_counts, S * 5); p.count0 = at(d_count0, S); p.ulist = at(d_ulist, S); p.ucount = at(d_ucount, 1);
@@ -287,6 +288,7 @@ struct pslfe_line {
 
     // A launch of F frames runs as (profiles/r03z_switch_matrix.log, profiles/line_split_ab.log):
     //   F <= PSL_GROW_HELPER_FRAMES (64)   k_lsd_grow4<3, 1> (<3, 0> for frames whose `used` bits do not fit in LDS): helper waves, P.singles
+    //                                      and the seed vectors from k_lsd_grad's table d_seedt (larger launches: evaluated by k_lsd_grow4<0, 0>)
     //   F >= 64                            the many-frames NFA grids
     //   F > 64                             k_lsd_grow4<0, 0> on the frames in k_frame_order's order
     //   F > PSL_LSD_SUBBATCH (2048)        scale / gradient in sub-batches
@@ -322,7 +324,7 @@ struct pslfe_line {
             }
             {
                 PSL_STAGE_BEGIN(ctx, "line.lsd_grad");
-                k_lsd_grad<<<xcd ? dim3(8, tx * gy, (n + 7) / 8) : dim3(tx, gy, n), 256, 0, st>>>(P, d_scaled, d_angdeg + po, d_modgrad + po, d_trig + po, d_seedt + po,
+                k_lsd_grad<<<xcd ? dim3(8, tx * gy, (n + 7) / 8) : dim3(tx, gy, n), 256, 0, st>>>(P, d_scaled, d_angdeg + po, d_modgrad + po, d_trig + po, P.singles ? d_seedt + po : nullptr,
                                                                                                   d_used + po, ordered ? d_weight + f0 : nullptr, (int)n, xcd);
                 PSL_STAGE_END(ctx, "line.lsd_grad");
             }
@@ -341,6 +343,7 @@ struct pslfe_line {
         {
             PSL_STAGE_BEGIN_ON(ctx, "line.lsd_grow", st);
             // LSD_REFINE_ADV: the kernel leaves rectangles (rects / nrect) for the NFA validation below
+            PSL_REQUIRE(ordered || p.seedt != nullptr, PSLFE_E_INVALID, "line: a part of %u frames of a launch of %u has no seed table", n, p.F);
             if (!ordered) {  // few workgroups per XCD: three more waves each keep that XCD's L2 warm in front of the chain (line_kernels.h)
                 const size_t ubytes = (((size_t)P.W * P.H + 31) >> 5) * 4;   // the `used` bits of the frame in LDS (24 KB at 640x480, 96 KB at 1280x960)
                 if (ubytes <= PSL_GROW_LDS_USED_MAX) {
