@@ -129,7 +129,8 @@ int pslfe_ctx_create(int device, pslfe_ctx** out) {
     c->stream = c->own_stream;
     if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming) != hipSuccess) {
         pslfe_ctx_destroy(c);
         pslfe_set_error("pslfe_ctx_create: auxiliary stream / events failed");
         return PSLFE_E_HIP;
@@ -149,6 +150,7 @@ void pslfe_ctx_destroy(pslfe_ctx* ctx) {
     (void)ctx->resolve_pending();
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
+    if (ctx->ev_pre) (void)hipEventDestroy(ctx->ev_pre);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;

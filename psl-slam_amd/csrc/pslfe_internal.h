@@ -42,6 +42,7 @@ struct pslfe_ctx {
     hipStream_t stream = nullptr;  // stream in use (own or external)
     hipStream_t aux_stream = nullptr;              // second stream for independent kernels of one call (fork/join by events)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_pre = nullptr;                   // pslfe_line.hip, run_extract: behind the second part's k_lbd_pre on the context's stream
     bool profile = false;
     std::string profile_only;  // non-empty: only this stage is timed (two events per step instead of two per stage)
     std::map<std::string, StageTimer> stages;

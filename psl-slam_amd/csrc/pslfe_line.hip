@@ -27,6 +27,11 @@
 // (run_extract).  12288 dense frames, ms per step: 1: 373.5, 2: 349.9, 3: 365.7, 4: 382.9; 2 with the auxiliary stream at the highest priority
 // 349.4, at the lowest 353.4: no priority stream (profiles/line_split_ab.log)
 constexpr unsigned PSL_LINE_PIECES = 2;
+// The first of the two parts takes this share of the frames (each part at least PSL_GROW_HELPER_FRAMES + 1).  The second part's grower ends last
+// (at 188 of ~236 ms, whatever the share) and its NFA / merge / LBD launches follow it, the last 20 ms of them alone on the chip: the fewer frames
+// they cover, the sooner the join.  12288 dense frames, ms per step: 12/24: 334.0 (the parent, same session), 13/24: 333.5, 14/24: 330.4,
+// 15/24: 329.3, 16/24: 337.6 (another session, parent 335.7): 14/24, two steps in front of the cliff (profiles/line_pipeline_ab.log)
+constexpr unsigned PSL_LINE_FIRST_NUM = 7, PSL_LINE_FIRST_DEN = 12;
 
 // hipFuncSetAttribute acts on the function on the current device, not on an extractor object: the dynamic LDS k_lsd_grow4<3, 1> has
 // been allowed is kept per device and only ever raised (an extractor of a smaller geometry must not lower what another one relies on)
@@ -293,7 +298,9 @@ struct pslfe_line {
     //   F > 64                             k_lsd_grow4<0, 0> on the frames in k_frame_order's order
     //   F > PSL_LSD_SUBBATCH (2048)        scale / gradient in sub-batches
     //   F >= 2 * (64 + 1) = 130            pslfe_line_extract_batch_device: everything behind the gradient in PSL_LINE_PIECES parts on two streams
-    //                                      (run_extract), each part a many-frames launch of its own
+    //                                      (run_extract), each part a many-frames launch of its own: the first 7/12 of the frames, the second
+    //                                      the rest, each at least 65 frames (130: 65 + 65, 131: 66 + 65, 12288: 7168 + 5120); the second
+    //                                      part's k_lbd_pre on the first part's stream (profiles/line_pipeline_ab.log)
     // LSD steps 1 + 2 (scaled image, gradient) of every frame, and the launch's memsets; on the context's stream
     int run_grad(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
         int rc = prepare(w, h);
@@ -422,16 +429,29 @@ struct pslfe_line {
 
     // BinaryDescriptor::compute on the keylines in p.kls / p.nkl; d_gray is frame 0 of the launch
     int run_lbd(const Part& p, const uint8_t* d_gray, int stride, size_t frame_stride, bool want_float) {
+        const int rc = run_lbd_pre(p, d_gray, stride, frame_stride, p.st);
+        return rc ? rc : run_lbd_rows(p, want_float);
+    }
+
+    // the derivatives of the blurred image (p.dxy) of the frames of a part: they depend on the gray image alone, so stream st may be
+    // another than the part's (run_extract)
+    int run_lbd_pre(const Part& p, const uint8_t* d_gray, int stride, size_t frame_stride, hipStream_t st) {
+        PSL_HIP(hipSetDevice(ctx->device));
+        const int n = (int)p.n;
+        PSL_STAGE_BEGIN_ON(ctx, "line.lbd_pre", st);
+        const unsigned tx = (P.w + 63) / 64, ty = (P.h + 31) / 32;
+        const int xcd = n >= 8 ? 1 : 0;
+        k_lbd_pre<<<xcd ? dim3(8, tx * ty, (n + 7) / 8) : dim3(tx, ty, n), 256, 0, st>>>(P, d_gray + (size_t)p.f0 * frame_stride, stride, frame_stride, p.dxy, n, xcd);
+        PSL_STAGE_END_ON(ctx, "line.lbd_pre", st);
+        PSL_HIP(hipGetLastError());
+        return PSLFE_OK;
+    }
+
+    // the descriptor rows, from p.dxy and the keylines of the part
+    int run_lbd_rows(const Part& p, bool want_float) {
         PSL_HIP(hipSetDevice(ctx->device));
         hipStream_t st = p.st;
         const int n = (int)p.n;
-        {
-            PSL_STAGE_BEGIN_ON(ctx, "line.lbd_pre", st);
-            const unsigned tx = (P.w + 63) / 64, ty = (P.h + 31) / 32;
-            const int xcd = n >= 8 ? 1 : 0;
-            k_lbd_pre<<<xcd ? dim3(8, tx * ty, (n + 7) / 8) : dim3(tx, ty, n), 256, 0, st>>>(P, d_gray + (size_t)p.f0 * frame_stride, stride, frame_stride, p.dxy, n, xcd);
-            PSL_STAGE_END_ON(ctx, "line.lbd_pre", st);
-        }
         {
             PSL_STAGE_BEGIN_ON(ctx, "line.lbd", st);
             const int per_frame = std::min(P.maxkl, std::max(P.nfeatures, 1));
@@ -452,6 +472,19 @@ struct pslfe_line {
         return run_lbd(p, d_gray, stride, frame_stride, false);
     }
 
+    // run_part of A on its stream and of B on its own, with k_lbd_pre of B on A's stream behind A's launches (ev_pre).  The wait is only
+    // issued behind its record: a failed launch leaves no stream waiting for an event of this call that was never recorded.
+    int run_halves(const Part& A, const Part& B, const uint8_t* d_gray, int stride, size_t frame_stride) {
+        int rc = run_part(A, d_gray, stride, frame_stride);
+        if (rc) return rc;
+        if ((rc = run_lbd_pre(B, d_gray, stride, frame_stride, A.st))) return rc;
+        PSL_HIP(hipEventRecord(ctx->ev_pre, A.st));
+        if ((rc = run_detect(B))) return rc;
+        if ((rc = run_merge(B))) return rc;
+        PSL_HIP(hipStreamWaitEvent(B.st, ctx->ev_pre, 0));
+        return run_lbd_rows(B, false);
+    }
+
     // LINEextractor::operator() on every frame of a launch.  The frames are independent, yet each kernel behind the gradient lasts as
     // long as its slowest frame: k_lsd_grow4<0, 0> (one wave per frame, 12288 waves on 8192 slots) holds 6.77 of 8 slots per SIMD on
     // average, and nothing else can start while its tail drains.  So a launch of at least 2 * (PSL_GROW_HELPER_FRAMES + 1) frames runs
@@ -459,20 +492,24 @@ struct pslfe_line {
     // stream: the NFA / merge / LBD kernels of one part fill the slots the growing of the next one leaves.  Every part is a many-frames
     // launch of its own (own k_frame_order), so a frame's result does not depend on the split.  With stage profiling on, the launch
     // stays on one stream, so that the stage timers keep their meaning.
+    //   context's stream:   scale / gradient of all frames | ev_fork | A: grow, NFA, merge, k_lbd_pre, k_lbd | k_lbd_pre of B | ev_pre |      wait ev_join
+    //   auxiliary stream:                             wait ev_fork | B: grow,                  NFA, merge | wait ev_pre | k_lbd of B | ev_join
+    // The two growers start together; A's workgroups are dispatched first, so A's grower ends early (131 ms into a launch of 12288 dense
+    // frames, B's at 187) and A's chain runs in the tail of B's grower and beside the first half of B's chain (until 222); the join is
+    // at 232 (profiles/line_pipeline_ab.log).  B's chain ends the launch, so B is the smaller part (PSL_LINE_FIRST_NUM), and its
+    // k_lbd_pre, which reads nothing but the gray image, runs on the context's stream behind A's chain instead of behind B's merge.
     int run_extract(const uint8_t* d_gray, int nframes, int w, int h, int stride, size_t frame_stride) {
         int rc = run_grad(d_gray, nframes, w, h, stride, frame_stride);
         if (rc) return rc;
         const unsigned F = (unsigned)nframes;
-        if (F < 2 * (PSL_GROW_HELPER_FRAMES + 1) || ctx->profile) {
+        if (F < PSL_LINE_PIECES * (PSL_GROW_HELPER_FRAMES + 1) || ctx->profile) {
             if ((rc = run_part(whole(nframes), d_gray, stride, frame_stride))) return rc;
         } else {
-            const unsigned pieces = std::min<unsigned>(PSL_LINE_PIECES, F / (PSL_GROW_HELPER_FRAMES + 1));
+            const unsigned least = PSL_GROW_HELPER_FRAMES + 1;   // both parts are many-frames launches
+            const unsigned fB = std::min(std::max((unsigned)((size_t)F * PSL_LINE_FIRST_NUM / PSL_LINE_FIRST_DEN), least), F - least);
             PSL_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
             PSL_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-            for (unsigned i = 0; i < pieces && !rc; ++i) {
-                const unsigned f0 = (unsigned)((size_t)F * i / pieces), f1 = (unsigned)((size_t)F * (i + 1) / pieces);
-                rc = run_part(part(f0, f1 - f0, F, i & 1 ? ctx->aux_stream : ctx->stream), d_gray, stride, frame_stride);
-            }
+            rc = run_halves(part(0, fB, F, ctx->stream), part(fB, F - fB, F, ctx->aux_stream), d_gray, stride, frame_stride);
             // the join, also after a failed launch: the caller's stream must not run ahead of what the auxiliary stream was given
             const hipError_t ej = hipEventRecord(ctx->ev_join, ctx->aux_stream);
             const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) : ej;
