@@ -1613,6 +1613,70 @@ int pslfe_ba_local_lil(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const Psl
                        const PslMapLil* lil, int nlil, const PslBaLilEdge* lil_edges, int nlil_edges, const PslCamera* cam, int rounds,
                        PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslMapLil* lil_out, uint8_t* erase_lil, PslBaInfo* info);
 
+/* ---- The essential graph: Optimizer::OptimizeEssentialGraph -----------------------------------------------------------------------
+ * The call of LoopClosing::CorrectLoop (src/LoopClosing.cc, src/Optimizer.cc:2536-2799) from the vertices on: the measurements of
+ * the EdgeSim3 edges (:2607-2738), optimize(20) over g2o's Levenberg with setUserLambdaInit(1e-16) (:2549, :2741-2742), the pose
+ * recovery (:2747-2765) and the map point correction (:2768-2798, up to SetWorldPos; UpdateNormalAndDepth is
+ * pslfe_kf_update_normal_and_depth_device on d_mp_out).  Walking the pointer graph (the spanning tree, the loop edges, the
+ * covisibility lists, LoopConnections, the two Sim3 maps) stays host code: the mirrors' edge builder, INTEGRATION.md "CorrectLoop".
+ * Parity: "HIP == host compile of the same header == restatement" (tests/essential_cases.py), bit for bit; parity with g2o itself is
+ * unpinned (LinearSolverEigen is an LDLt without pivoting on row envelopes in the caller's row order, the
+ * 3x3 LU of Sim3::log and the order of every sum are this library's reading).  The global bundle adjustment CorrectLoop starts
+ * afterwards is not part of the library. */
+typedef struct PslEgKeyFrame {   /* a keyframe that is not bad, rows in ascending mnId (:2564-2599) */
+    double Scw[8];               /* vScw: q x y z w (not normalised), t, s: the CorrectedSim3 entry or Sim3(Rcw, tcw, 1.0) (:2573-2587) */
+    double Snc[8];               /* the NonCorrectedSim3 entry; read only when has_nc is set */
+    int32_t has_nc;              /* NonCorrectedSim3.find(pKF) != end() (:2646, :2662, :2689, :2720) */
+    int32_t fixed;               /* pKF == pLoopKF (:2589) */
+} PslEgKeyFrame;
+typedef struct PslEgEdge {       /* in the order the reference creates them (:2607-2738) */
+    int32_t i, j;                /* rows of the graph's keyframes: vertex 0 = i, vertex 1 = j */
+    int32_t loop;                /* 1: an edge of LoopConnections (:2607-2635), measured with vScw of both ends */
+} PslEgEdge;
+typedef struct PslEgInfo {
+    int32_t status;              /* PSLFE_OK, PSLFE_E_CAPACITY or PSLFE_E_INVALID of this graph */
+    int32_t iterations;          /* Levenberg iterations run (0 .. 20) */
+    int32_t log_branches;        /* bit k set when an evaluation of Sim3::log took branch k = (|sigma| >= 1e-5) * 2 + !(d > 1 - 1e-5) */
+    int32_t nfree;               /* free keyframes: the system has 7 nfree unknowns */
+    double chi2_start, chi2_end; /* the chi2 of all edges before the first iteration and after the last */
+    double lambda;               /* the damping when the call returned */
+} PslEgInfo;
+#ifdef __cplusplus
+static_assert(sizeof(PslEgKeyFrame) == 136 && sizeof(PslEgEdge) == 12 && sizeof(PslEgInfo) == 40, "essential graph PODs");
+#else
+_Static_assert(sizeof(PslEgKeyFrame) == 136 && sizeof(PslEgEdge) == 12 && sizeof(PslEgInfo) == 40, "essential graph PODs");
+#endif
+typedef struct pslfe_eg pslfe_eg;
+/* The HBM workspaces of up to max_graphs graphs per launch, each of up to max_keyframes keyframes, max_edges edges, max_points map
+ * points and max_envelope doubles of envelope: the lower triangle of H is stored per 7x7 block row from the lowest block column an
+ * edge gives it to the diagonal, sum over the scalar rows r of (r - 7 first_block(r) + 1) doubles (a chain: about 77 per free keyframe;
+ * a loop edge adds 49 per keyframe it spans).  A count below 1 or a NULL argument: PSLFE_E_INVALID. */
+int pslfe_eg_create(pslfe_ctx* ctx, int max_graphs, int max_keyframes, int max_edges, int max_points, int64_t max_envelope, pslfe_eg** out);
+void pslfe_eg_destroy(pslfe_eg* eg);
+/* == the optimisation, the pose recovery and the point correction of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2607-2798
+ *    with the vertices and edges given as rows) for K independent graphs in one launch, HBM to HBM.  Graph k has the keyframes
+ *    d_kf[d_kf_off[k] .. d_kf_off[k+1]), the edges d_edges[d_edge_off[k] ..) and the points d_mp[d_mp_off[k] ..) with
+ *    d_mp_ref[same index] = the keyframe row nIDr of :2775-2784 (the mnCorrectedByKF test is the caller's) or -1 for a point that
+ *    is copied unchanged (a bad one).  The offset arrays have K+1 ascending entries.  fix_scale: bFixScale.
+ *    Outputs, indexed as the inputs: d_pose_out (Tiw of :2762 for EVERY keyframe), d_S_out ([8] doubles per keyframe: the optimised
+ *    Sim3, laid out as Scw), d_mp_out (x, y, z corrected, the other fields copied; may be d_mp; it is what
+ *    pslfe_kf_update_normal_and_depth_device takes), d_info[k].
+ *    Per graph, in d_info[k].status, never a silent truncation: counts or an envelope above the handle's caps: PSLFE_E_CAPACITY;
+ *    descending or negative offsets, an edge that names a row outside its graph or has i == j, a point whose reference row is
+ *    below -1 or not a row of its graph: PSLFE_E_INVALID; such a graph gets d_S_out = its Scw and d_mp_out = its d_mp, no pose row
+ *    is written, and its neighbours are not disturbed.  Any number of keyframes may be fixed.  No free keyframe, or no edge:
+ *    PSLFE_OK with 0 iterations; the poses and points then come from the Sim3s as given.  A free keyframe without an edge gets a
+ *    zero block plus lambda and a zero step.
+ *    Whole call, before any device is touched: K < 0, K > max_graphs, a NULL argument with K > 0: PSLFE_E_INVALID; K == 0:
+ *    PSLFE_OK, nothing is done.  Asynchronous on the context's stream. */
+int pslfe_eg_optimize_device(pslfe_eg* eg, int K, const PslEgKeyFrame* d_kf, const int32_t* d_kf_off, const PslEgEdge* d_edges,
+                             const int32_t* d_edge_off, const PslMapPointGeom* d_mp, const int32_t* d_mp_ref, const int32_t* d_mp_off,
+                             int fix_scale, PslPose* d_pose_out, double* d_S_out, PslMapPointGeom* d_mp_out, PslEgInfo* d_info);
+/* One graph, host arrays; returns after the results have arrived.  Negative counts or NULL with a non-zero count: PSLFE_E_INVALID
+ * before any device is touched.  A negative status of the graph is also the return value. */
+int pslfe_eg_optimize(pslfe_eg* eg, const PslEgKeyFrame* kf, int nkf, const PslEgEdge* edges, int nedges, const PslMapPointGeom* mp,
+                      const int32_t* mp_ref, int nmp, int fix_scale, PslPose* pose_out, double* S_out, PslMapPointGeom* mp_out, PslEgInfo* info);
+
 /* ---- RGB-D line glue of the Frame constructor ------------------------------ */
 typedef struct pslfe_glue pslfe_glue;
 /* Buffers for up to max_batch frames of max_lines keylines and max_fans LIL rows each. */

@@ -73,6 +73,12 @@ BAINFO_DTYPE = np.dtype({"names": ["status", "rounds", "iterations", "nerased", 
 BALILEDGE_DTYPE = np.dtype([("lil", "<i4"), ("kf", "<i4"), ("obs1", "<f8", (3,)), ("obs2", "<f8", (3,)), ("obs_ins", "<f8", (2,))])
 assert BALILEDGE_DTYPE.itemsize == 72
 assert BAEDGE_DTYPE.itemsize == 24 and BAKEYFRAME_DTYPE.itemsize == 52 and BAINFO_DTYPE.itemsize == 48
+# essential graph (include/pslfe.h: PslEgKeyFrame, PslEgEdge, PslEgInfo)
+EGKEYFRAME_DTYPE = np.dtype([("Scw", "<f8", (8,)), ("Snc", "<f8", (8,)), ("has_nc", "<i4"), ("fixed", "<i4")])
+EGEDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("loop", "<i4")])
+EGINFO_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("log_branches", "<i4"), ("nfree", "<i4"), ("chi2_start", "<f8"),
+                         ("chi2_end", "<f8"), ("lambda", "<f8")])
+assert EGKEYFRAME_DTYPE.itemsize == 136 and EGEDGE_DTYPE.itemsize == 12 and EGINFO_DTYPE.itemsize == 40
 
 
 def pose(Tcw):
@@ -702,11 +708,104 @@ class BundleAdjuster:
             pass
 
 
+class EssentialGraph:
+    """The HBM workspaces of the essential-graph optimisation (pslfe_eg): up to max_graphs graphs per launch of up to max_keyframes
+    keyframes, max_edges edges, max_points map points and max_envelope doubles of envelope each (include/pslfe.h, pslfe_eg_create)."""
+
+    def __init__(self, max_graphs, max_keyframes, max_edges, max_points, max_envelope, ctx=None):
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        _check(lib().pslfe_eg_create(self.ctx._h, C.c_int(max_graphs), C.c_int(max_keyframes), C.c_int(max_edges), C.c_int(max_points),
+                                     C.c_int64(max_envelope), C.byref(self._h)), "pslfe_eg_create")
+
+    def close(self):
+        if self._h:
+            lib().pslfe_eg_destroy.restype = None
+            lib().pslfe_eg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Optimizer:
     """Optimizer::PoseOptimization src/Optimizer.cc:239-1023: the point edges (EdgeSE3ProjectXYZOnlyPose and
     EdgeStereoSE3ProjectXYZOnlyPose) and the LIL edges (EdgeLILSE3ProjectXYZ, :619-694, :973-1008; the `lil` argument and the *Lil*
     methods); Optimizer::LocalBundleAdjustment :1025-1966, its point edges, and LocalBundleAdjustmentAndInseclines :1968-2534 with the
     VertexLIL vertices.  Parity with g2o itself is unpinned."""
+
+    @staticmethod
+    def EssentialGraphEdges(parent, loop_edges, covisibles, loop_connections, loop_kf, cur_kf, min_feat=100):
+        """The edge rows of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2607-2738) from what the reference reads off the pointer
+        graph, as arrays over the keyframe rows (ascending mnId, bad keyframes left out, so comparing rows compares mnIds):
+        parent[i] = the row of GetParent() or -1; loop_edges[i] = the rows of GetLoopEdges() in the set's order; covisibles[i] = the
+        rows of GetCovisiblesByWeight(min_feat) in its order (bad ones left out); loop_connections = [(row i, [(row j, GetWeight(j)),
+        ...]), ...] in the order the map and its sets iterate; loop_kf / cur_kf = the rows of pLoopKF / pCurKF.
+        -> EGEDGE_DTYPE rows in the order the reference creates the edges: the LoopConnections pairs with weight >= min_feat or
+        (cur_kf, loop_kf) itself, flagged loop (they fill sInsertedEdges); then per row i its spanning-tree edge (i, parent), its loop
+        edges (i, l) with l < i, and its covisibility edges (i, n) with n < i that are neither the parent, a child, a loop edge
+        nor in sInsertedEdges."""
+        out, inserted = [], set()
+        for i, conns in loop_connections:
+            for j, w in conns:
+                if (i != cur_kf or j != loop_kf) and w < min_feat:
+                    continue
+                out.append((i, j, 1))
+                inserted.add((min(i, j), max(i, j)))
+        for i in range(len(parent)):
+            p = int(parent[i])
+            if p >= 0:
+                out.append((i, p, 0))
+            le = [int(l) for l in loop_edges[i]]
+            for l in le:
+                if l < i:
+                    out.append((i, l, 0))
+            for n in covisibles[i]:
+                n = int(n)
+                if n >= 0 and n != p and int(parent[n]) != i and n not in le and n < i:
+                    if (min(i, n), max(i, n)) in inserted:
+                        continue
+                    out.append((i, n, 0))
+        ed = np.zeros(len(out), EGEDGE_DTYPE)
+        for e, (i, j, loop) in enumerate(out):
+            ed["i"][e], ed["j"][e], ed["loop"][e] = i, j, loop
+        return ed
+
+    @staticmethod
+    def OptimizeEssentialGraph(eg, kfs, edges, mps, mp_ref, fix_scale):
+        """Optimizer::OptimizeEssentialGraph src/Optimizer.cc:2536-2799 (the call of LoopClosing::CorrectLoop), one graph, host arrays:
+        kfs EGKEYFRAME_DTYPE[nkf] (rows in ascending mnId: vScw, the NonCorrectedSim3 entry and its flag, fixed for pLoopKF), edges
+        EGEDGE_DTYPE[ne] (EssentialGraphEdges builds them), mps MAPPOINT_DTYPE[nmp] with mp_ref int32[nmp] = the row nIDr of :2775-2784
+        or -1 for a point that is copied.  -> (poses POSE_DTYPE[nkf] = Tiw of :2762, S float64 [nkf][8] = the optimised Sim3s,
+        mps_out = what SetWorldPos gets, info EGINFO_DTYPE record).  A refused graph raises PslfeError."""
+        k = np.ascontiguousarray(kfs, EGKEYFRAME_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(edges, EGEDGE_DTYPE).reshape(-1)
+        m = np.ascontiguousarray(mps, MAPPOINT_DTYPE).reshape(-1)
+        r = np.ascontiguousarray(mp_ref, np.int32).reshape(-1)
+        if len(r) != len(m):
+            raise PslfeError("OptimizeEssentialGraph: mp_ref needs one entry per map point")
+        po, So, mo = np.zeros(max(len(k), 1), POSE_DTYPE), np.zeros((max(len(k), 1), 8), np.float64), np.zeros(max(len(m), 1), MAPPOINT_DTYPE)
+        info = np.zeros(1, EGINFO_DTYPE)
+        p = lambda a, n: _ptr(a) if n else None
+        _check(lib().pslfe_eg_optimize(eg._h, p(k, len(k)), C.c_int(len(k)), p(e, len(e)), C.c_int(len(e)), p(m, len(m)), p(r, len(m)),
+                                       C.c_int(len(m)), C.c_int(1 if fix_scale else 0), p(po, len(k)), p(So, len(k)), p(mo, len(m)), _ptr(info)),
+               "pslfe_eg_optimize")
+        return po[:len(k)], So[:len(k)], mo[:len(m)], info[0]
+
+    @staticmethod
+    def OptimizeEssentialGraphDevice(eg, K, d_kf, d_kf_off, d_edges, d_edge_off, d_mp, d_mp_ref, d_mp_off, fix_scale, d_pose_out, d_S_out,
+                                     d_mp_out, d_info):
+        """K independent graphs in one launch, HBM to HBM, asynchronous; all d_* are device addresses (ints).  The offset arrays have
+        K + 1 ascending int32 entries; d_mp_out may be d_mp and is what update_normal_and_depth_device takes; d_info EGINFO_DTYPE [K]
+        with the status of each graph (-4 capacity, -1 invalid: d_S_out = its Scw, d_mp_out = its d_mp, no pose row written)."""
+        _check(lib().pslfe_eg_optimize_device(
+            eg._h, C.c_int(K), C.c_void_p(d_kf or None), C.c_void_p(d_kf_off or None), C.c_void_p(d_edges or None), C.c_void_p(d_edge_off or None),
+            C.c_void_p(d_mp or None), C.c_void_p(d_mp_ref or None), C.c_void_p(d_mp_off or None), C.c_int(1 if fix_scale else 0),
+            C.c_void_p(d_pose_out or None), C.c_void_p(d_S_out or None), C.c_void_p(d_mp_out or None), C.c_void_p(d_info or None)),
+            "pslfe_eg_optimize_device")
 
     @staticmethod
     def LocalBundleAdjustment(ba, kfs, mps, edges, cam, rounds=2):

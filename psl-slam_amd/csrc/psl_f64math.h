@@ -158,6 +158,58 @@ PSL_F64_QUAL double psl_atan2(double y, double x) {
     return (z - pi_lo) - pi;
 }
 
+// The square root as one correctly rounded operation on the device as on the host.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PSL_F64_SQRT(a) __dsqrt_rn(a)
+#else
+#define PSL_F64_SQRT(a) __builtin_sqrt(a)
+#endif
+
+// acos(x) (fdlibm e_acos.c): the rational approximation R(x^2) of (asin(x) - x) / x^3 on |x| < 0.5, the half-angle forms
+// pi - 2 asin(sqrt((1 + x) / 2)) and 2 asin(sqrt((1 - x) / 2)) beyond; |x| > 1 or a NaN gives NaN.  Sim3::log calls acos on
+// d = (trace(R) - 1) / 2 (essential_kernels.h).  glibc's acos is the multi-precision IBM routine: this one is pinned as "within
+// one ulp of the host's libm" on a grid over [-1, 1] that is dense at -1, 0 and 1 (tests/test_essential_graph_cpu.py).
+PSL_F64_QUAL double psl_acos(double x) {
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17, pi = 3.14159265358979311600e+00,
+                 pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01, pS2 = 2.01212532134862925881e-01,
+                 pS3 = -4.00555345006794114027e-02, pS4 = 7.91534994289814532176e-04, pS5 = 3.47933107596021167570e-05,
+                 qS1 = -2.40339491173441421878e+00, qS2 = 2.02094576023350569471e+00, qS3 = -6.88283971605453293030e-01,
+                 qS4 = 7.70381505559019352791e-02;
+    const uint64_t u = psl_f64_bits(x);
+    const int32_t hx = (int32_t)(u >> 32);
+    const int32_t ix = hx & 0x7fffffff;
+    if (ix >= 0x3ff00000) {  // |x| >= 1
+        if ((((uint32_t)ix - 0x3ff00000u) | (uint32_t)u) == 0) return hx > 0 ? 0.0 : pi + 2.0 * pio2_lo;
+        return psl_f64_from(0x7ff8000000000000ull);  // (x - x) / (x - x)
+    }
+    if (ix < 0x3fe00000) {  // |x| < 0.5
+        if (ix <= 0x3c600000) return pio2_hi + pio2_lo;
+        const double z = x * x;
+        const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const double r = PSL_F64_DIV(p, q);
+        return pio2_hi - (x - (pio2_lo - r * x));
+    }
+    if (hx < 0) {  // x < -0.5
+        const double z = (1.0 + x) * 0.5;
+        const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const double s = PSL_F64_SQRT(z);
+        const double r = PSL_F64_DIV(p, q);
+        const double w = r * s - pio2_lo;
+        return pi - 2.0 * (s + w);
+    }
+    const double z = (1.0 - x) * 0.5;  // x > 0.5
+    const double s = PSL_F64_SQRT(z);
+    const double df = psl_f64_from(psl_f64_bits(s) & 0xffffffff00000000ull);
+    const double c = PSL_F64_DIV(z - df * df, s + df);
+    const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const double r = PSL_F64_DIV(p, q);
+    const double w = r * s + c;
+    return 2.0 * (df + w);
+}
+
 // x * 2^n for results that stay normal or underflow gradually (fdlibm scalbn, the cases exp needs)
 PSL_F64_QUAL double psl_scalbn(double x, int n) {
     if (n > 1023) { x *= 8.98846567431157953865e+307; n -= 1023; if (n > 1023) { x *= 8.98846567431157953865e+307; n -= 1023; if (n > 1023) n = 1023; } }

@@ -1177,8 +1177,87 @@ private:
     pslfe_ba* h_ = nullptr;
 };
 
+// The workspaces of the essential-graph optimisation (pslfe_eg): up to maxGraphs graphs per launch of up to maxKeyframes keyframes,
+// maxEdges edges, maxPoints map points and maxEnvelope doubles of envelope each.  A single owner frees every buffer.
+class EssentialGraph {
+public:
+    EssentialGraph(Context& ctx, int maxGraphs, int maxKeyframes, int maxEdges, int maxPoints, int64_t maxEnvelope) {
+        check(pslfe_eg_create(ctx.get(), maxGraphs, maxKeyframes, maxEdges, maxPoints, maxEnvelope, &h_), "pslfe_eg_create");
+    }
+    ~EssentialGraph() { pslfe_eg_destroy(h_); }
+    EssentialGraph(const EssentialGraph&) = delete;
+    EssentialGraph& operator=(const EssentialGraph&) = delete;
+    pslfe_eg* get() const { return h_; }
+private:
+    pslfe_eg* h_ = nullptr;
+};
+
+// What Optimizer::OptimizeEssentialGraph reads off the pointer graph, as arrays over the keyframe rows (ascending mnId, bad keyframes
+// left out, so comparing rows compares mnIds).
+struct EssentialGraphLinks {
+    std::vector<int32_t> parent;                                  // the row of GetParent() or -1
+    std::vector<std::vector<int32_t>> loopEdges;                  // the rows of GetLoopEdges(), in the set's order
+    std::vector<std::vector<int32_t>> covisibles;                 // the rows of GetCovisiblesByWeight(100), in its order, bad ones left out
+    struct Connection { int32_t kf; std::vector<std::pair<int32_t, int>> to; };   // (row, GetWeight(row))
+    std::vector<Connection> loopConnections;                      // in the order the map and its sets iterate
+    int32_t loopKF = -1, curKF = -1;                              // the rows of pLoopKF / pCurKF
+};
+
 class Optimizer {
 public:
+    // The edge rows of Optimizer::OptimizeEssentialGraph in the order the reference creates them (src/Optimizer.cc:2607-2738): the
+    // LoopConnections pairs with weight >= minFeat or (curKF, loopKF) itself, flagged loop (they fill sInsertedEdges); then per row i its
+    // spanning-tree edge (i, parent), its loop edges (i, l) with l < i, and its covisibility edges (i, n) with n < i that are neither the
+    // parent, a child, a loop edge nor in sInsertedEdges.
+    static std::vector<PslEgEdge> EssentialGraphEdges(const EssentialGraphLinks& g, int minFeat = 100) {
+        std::vector<PslEgEdge> out;
+        std::vector<std::pair<int32_t, int32_t>> inserted;
+        auto key = [](int32_t a, int32_t b) { return std::make_pair(a < b ? a : b, a < b ? b : a); };
+        for (const auto& c : g.loopConnections)
+            for (const auto& jw : c.to) {
+                if ((c.kf != g.curKF || jw.first != g.loopKF) && jw.second < minFeat) continue;
+                out.push_back(PslEgEdge{c.kf, jw.first, 1});
+                inserted.push_back(key(c.kf, jw.first));
+            }
+        for (int32_t i = 0; i < (int32_t)g.parent.size(); ++i) {
+            const int32_t p = g.parent[i];
+            if (p >= 0) out.push_back(PslEgEdge{i, p, 0});
+            const std::vector<int32_t>& le = g.loopEdges[i];
+            for (int32_t l : le)
+                if (l < i) out.push_back(PslEgEdge{i, l, 0});
+            for (int32_t n : g.covisibles[i]) {
+                if (n < 0 || n == p || g.parent[n] == i || n >= i) continue;
+                bool skip = false;
+                for (int32_t l : le) skip = skip || l == n;
+                for (const auto& k : inserted) skip = skip || k == key(i, n);
+                if (!skip) out.push_back(PslEgEdge{i, n, 0});
+            }
+        }
+        return out;
+    }
+    // void Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+    // src/Optimizer.cc:2536-2799 from the measurements on: kfs = one row per keyframe that is not bad in ascending mnId, edges =
+    // EssentialGraphEdges, mps with mpRef[p] = the row nIDr of :2775-2784 or -1 for a point that is copied.  mps come back as
+    // SetWorldPos gets them, poses = Tiw of :2762 for SetPose, S = the optimised Sim3s ([8] doubles per keyframe).  A refused graph
+    // (capacity, an edge or a point outside it) throws.  Parity with g2o itself is unpinned.
+    static PslEgInfo OptimizeEssentialGraph(EssentialGraph& eg, const std::vector<PslEgKeyFrame>& kfs, const std::vector<PslEgEdge>& edges,
+                                            std::vector<PslMapPointGeom>& mps, const std::vector<int32_t>& mpRef, bool fixScale,
+                                            std::vector<PslPose>& poses, std::vector<double>& S) {
+        poses.resize(kfs.size());
+        S.resize(8 * kfs.size());
+        PslEgInfo info = {};
+        check(mpRef.size() == mps.size() ? PSLFE_OK : PSLFE_E_INVALID, "OptimizeEssentialGraph: mpRef needs one entry per map point");
+        check(pslfe_eg_optimize(eg.get(), kfs.data(), (int)kfs.size(), edges.data(), (int)edges.size(), mps.data(), mpRef.data(), (int)mps.size(),
+                                fixScale ? 1 : 0, poses.data(), S.data(), mps.data(), &info), "pslfe_eg_optimize");
+        return info;
+    }
+    // K graphs in one launch, HBM to HBM, asynchronous on the context's stream: pslfe_eg_optimize_device
+    static void OptimizeEssentialGraphDevice(EssentialGraph& eg, int K, const PslEgKeyFrame* d_kf, const int32_t* d_kfOff, const PslEgEdge* d_edges,
+                                             const int32_t* d_edgeOff, const PslMapPointGeom* d_mp, const int32_t* d_mpRef, const int32_t* d_mpOff,
+                                             bool fixScale, PslPose* d_poseOut, double* d_SOut, PslMapPointGeom* d_mpOut, PslEgInfo* d_info) {
+        check(pslfe_eg_optimize_device(eg.get(), K, d_kf, d_kfOff, d_edges, d_edgeOff, d_mp, d_mpRef, d_mpOff, fixScale ? 1 : 0, d_poseOut, d_SOut,
+                                       d_mpOut, d_info), "pslfe_eg_optimize_device");
+    }
     // int Optimizer::PoseOptimization(Frame* pFrame): edges = one PslPoseEdge per non-NULL pFrame->mvpMapPoints[i] in keypoint order
     // (:282-363); Tcw = pFrame->mTcw, replaced by the pose :1020 sets; outlier[e] = mvbOutlier of the edge's keypoint; returns
     // nInitialCorrespondences - nBad.  Fewer than 3 edges: returns 0, Tcw unchanged, outlier all false (:291, :696).
