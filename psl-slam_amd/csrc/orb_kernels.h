@@ -35,6 +35,7 @@ struct OrbParams {
     int nlevels, ncells, cellcap, cand_total, kp_total, out_cap, iniTh, minTh, ntiles;
     int blurK[7];
     int umax[16];
+    unsigned long long vmax;    // nibble |u|: the largest v with |u| <= umax[v] (umax[] does not increase with v)
     OrbLevelP lv[PSLFE_MAX_LEVELS];
 };
 
@@ -97,7 +98,8 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
     int spitch;
     const uint8_t* src = psl_level_ptr(P, S, level - 1, frame, &spitch);
     const int sw = P.lv[level - 1].w, sh = P.lv[level - 1].h;
-    // this thread's tables
+    // this thread's tables (indices and byte offsets are kept unsigned 32-bit throughout: a uniform base plus a 32-bit lane offset
+    // is one address operand, a sign-extended index is four more instructions per access)
     const int x4 = x0 + (tid & 15) * 4;
     int sx[4];
     short2 a[4];
@@ -105,8 +107,8 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
     for (int j = 0; j < 4; ++j) {
         int dx = x4 + j;
         dx = dx < L.w ? dx : L.w - 1;  // padding columns repeat the last pixel
-        sx[j] = xofs[dx];
-        a[j] = alpha[dx];
+        sx[j] = xofs[(uint32_t)dx];
+        a[j] = alpha[(uint32_t)dx];
         if (sx[j] + 1 >= P.lv[level - 1].w) a[j] = make_short2(2048, 0);  // clamped last column: h = p * 2048 (cv::resize)
     }
     int sy0[2], sy1[2];
@@ -114,10 +116,10 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         const int dy = min(y0 + (tid >> 4) + 16 * rr, L.h - 1);
-        const int t = yofs[dy];
+        const int t = yofs[(uint32_t)dy];
         sy0[rr] = t < 0 ? 0 : (t >= sh ? sh - 1 : t);
         sy1[rr] = t + 1 < 0 ? 0 : (t + 1 >= sh ? sh - 1 : t + 1);
-        b[rr] = beta[dy];
+        b[rr] = beta[(uint32_t)dy];
     }
     // source rectangle of this block (tables are non-decreasing)
     const int xe = min(x0 + 63, L.w - 1), ye = min(y0 + PSL_PYR_BH - 1, L.h - 1);
@@ -130,9 +132,10 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
                         ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)spitch) & 3) == 0 && cbase + ndw * 4 <= spitch;
     if (staged) {
         const uint32_t mdw = (1048576u + (uint32_t)ndw - 1u) / (uint32_t)ndw;  // k / ndw == (k * mdw) >> 20 for k < 4096
+        // k < 48 * 36, mdw <= 2^20, rows and pitches <= 4096 + 15: every product below fits the 24-bit multiplier
         for (int k = tid; k < nrows * ndw; k += 256) {
-            const int r = (int)(((uint32_t)k * mdw) >> 20), d = k - r * ndw;
-            s_tile[r * PSL_PYR_TD + d] = *reinterpret_cast<const uint32_t*>(src + (size_t)(rfirst + r) * spitch + cbase + d * 4);
+            const uint32_t r = __umul24((uint32_t)k, mdw) >> 20, d = (uint32_t)k - __umul24(r, (uint32_t)ndw);
+            s_tile[r * PSL_PYR_TD + d] = *reinterpret_cast<const uint32_t*>(src + (__umul24((uint32_t)rfirst + r, (uint32_t)spitch) + (uint32_t)cbase + d * 4));
         }
     }
     __syncthreads();
@@ -143,31 +146,43 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
 #pragma unroll
     for (int j = 0; j < 4; ++j) ofs[j] = sx[j] - cbase - 4 * d0;
     const bool fits = ofs[0] >= 0 && ofs[1] >= ofs[0] && ofs[2] >= ofs[1] && ofs[3] >= ofs[2] && ofs[3] <= 7;  // scale factors up to ~1.3
+    // The `fits` path cuts a tap pair (bytes ofs[j], ofs[j] + 1 of the three dwords u0 u1 u2) out with one v_perm, whose selector
+    // is formed here, once per thread: the middle dword u1 is the low operand (bytes 4..7 -> selector 0..3), the high operand is u0
+    // (bytes 0..3 -> 4..7) or, only for a pair that starts at byte 7, u2 (byte 8 -> 4).  With the tables of a linear resize only
+    // the last pixel gets that far, and only it carries the choice, as a flag; a thread whose pixel 2 starts at byte 7 (none has
+    // been found) takes the byte path below.
+    uint32_t psel[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)  // window byte n (0..8) has selector (n + 4) & 7; the pair is bytes ofs[j] and ofs[j] + 1
+        psel[j] = 0x0c000c00u | (((uint32_t)ofs[j] * 0x10001u + 0x50004u) & 0x70007u);
+    const bool pairs = fits && ofs[2] < 7, last3 = ofs[3] == 7;
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         const int dy = y0 + (tid >> 4) + 16 * rr;
         if (dy >= L.h) break;
-        uint8_t* dst = S.pyr + (size_t)frame * S.pyr_fstride + L.img_off + (size_t)dy * L.pitch;
+        uint8_t* dst = S.pyr + (size_t)frame * S.pyr_fstride + L.img_off;
         uint32_t packed = 0;
-        if (staged && fits) {
+        if (staged && pairs) {
             // The eight taps of a source row (4 pixels x 2 columns) lie within 12 bytes: three aligned dwords per source row
-            // instead of eight byte reads (the kernel was bound by LDS instructions), a tap pair is cut out with v_alignbyte,
-            // spread to 16-bit lanes with v_perm and weighted with one v_dot2_u32_u16.
+            // instead of eight byte reads (the kernel was bound by LDS instructions), a tap pair is cut out and spread to 16-bit
+            // lanes with one v_perm (psel[], above) and weighted with one v_dot2_u32_u16.
             const uint32_t* q0 = s_tile + (sy0[rr] - rfirst) * PSL_PYR_TD + d0;
             const uint32_t* q1 = s_tile + (sy1[rr] - rfirst) * PSL_PYR_TD + d0;
             const uint32_t u0 = q0[0], u1 = q0[1], u2 = q0[2], v0 = q1[0], v1 = q1[1], v2 = q1[2];
             const uint32_t bx = (uint32_t)(int)b[rr].x, by = (uint32_t)(int)b[rr].y;
+            uint32_t v[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool hi = ofs[j] >= 4;
-                const uint32_t t0 = __builtin_amdgcn_alignbyte(hi ? u2 : u1, hi ? u1 : u0, (uint32_t)(ofs[j] & 3));
-                const uint32_t t1 = __builtin_amdgcn_alignbyte(hi ? v2 : v1, hi ? v1 : v0, (uint32_t)(ofs[j] & 3));
                 const pyr_u16x2 cf = __builtin_bit_cast(pyr_u16x2, a[j]);
-                const uint32_t h0 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(0u, t0, 0x0c010c00u)), cf, 0u, false);
-                const uint32_t h1 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(0u, t1, 0x0c010c00u)), cf, 0u, false);
-                const uint32_t v = (((bx * (h0 >> 4)) >> 16) + ((by * (h1 >> 4)) >> 16) + 2u) >> 2;
-                packed |= (v & 0xffu) << (8 * j);
+                const uint32_t t0 = __builtin_amdgcn_perm(j == 3 && last3 ? u2 : u0, u1, psel[j]);
+                const uint32_t t1 = __builtin_amdgcn_perm(j == 3 && last3 ? v2 : v0, v1, psel[j]);
+                const uint32_t h0 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, t0), cf, 0u, false);
+                const uint32_t h1 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, t1), cf, 0u, false);
+                // bx, by <= 2048 and h >> 4 <= 32640: the 24-bit multiply gives the same product as the full one
+                v[j] = ((__umul24(bx, h0 >> 4) >> 16) + (__umul24(by, h1 >> 4) >> 16) + 2u) >> 2;
             }
+            // byte 0 of each of the four
+            packed = __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0400u) | __builtin_amdgcn_perm(v[3], v[2], 0x04000c0cu);
         } else if (staged) {
             const uint8_t* t0 = reinterpret_cast<const uint8_t*>(s_tile) + (sy0[rr] - rfirst) * (PSL_PYR_TD * 4) - cbase;
             const uint8_t* t1 = reinterpret_cast<const uint8_t*>(s_tile) + (sy1[rr] - rfirst) * (PSL_PYR_TD * 4) - cbase;
@@ -201,7 +216,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tiled(OrbParams P, FrameSrc 
                 packed |= (uint32_t)(v & 0xff) << (8 * j);
             }
         }
-        *reinterpret_cast<uint32_t*>(dst + x4) = packed;
+        *reinterpret_cast<uint32_t*>(dst + (__umul24((uint32_t)dy, (uint32_t)L.pitch) + (uint32_t)x4)) = packed;
     }
 }
 
@@ -837,9 +852,29 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
 // Orientation (IC_Angle) + rBRIEF + final KeyPoint record: one wave per keypoint.
 // Output order: levels 0..n-1 concatenated, inside a level the octree's list order (:1076-1103).
 // ---------------------------------------------------------------------------------------------
-__constant__ int8_t c_orb_pattern[1024] = {
+// the 256 x 4 sampling offsets as f32 (int8 -> f32 is exact): a lane fetches the four of a comparison with one 16-byte load
+__constant__ __attribute__((aligned(16))) float c_orb_pattern[1024] = {
 #include "orb_pattern.inc"
 };
+
+// One row operation of the data-parallel primitives: lane i receives v of the lane that CTRL names inside its row of 16.
+#define PSL_DPP_QUAD_1032 0xb1     // quad_perm [1, 0, 3, 2]: lane ^ 1
+#define PSL_DPP_QUAD_2301 0x4e     // quad_perm [2, 3, 0, 1]: lane ^ 2
+#define PSL_DPP_HALF_MIRROR 0x141  // lane i of a half row <- lane 7 - i
+#define PSL_DPP_MIRROR 0x140       // lane i of a row <- lane 15 - i
+template <int CTRL>
+__device__ __forceinline__ int psl_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+
+// Sum of v over the 64 lanes as a scalar: four row operations leave the sum of a row of 16 in each of its lanes (after the two
+// quad steps the four lanes of a quad agree, so a mirror brings in the other quads), v_readlane collects the four rows.  No LDS.
+__device__ __forceinline__ int psl_wave_sum(int v) {
+    v += psl_dpp<PSL_DPP_QUAD_1032>(v);
+    v += psl_dpp<PSL_DPP_QUAD_2301>(v);
+    v += psl_dpp<PSL_DPP_HALF_MIRROR>(v);
+    v += psl_dpp<PSL_DPP_MIRROR>(v);
+    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+           __builtin_amdgcn_readlane(v, 48);
+}
 
 #define PSL_DESC_PD 11  // LDS pitch of the descriptor patch in dwords: 37 + 3 alignment bytes -> 10, odd pitch
 #define PSL_ORI_PD 9    // LDS pitch of the orientation patch in dwords: 31 + 3 alignment bytes -> 9
@@ -848,11 +883,15 @@ __global__ __launch_bounds__(256) void k_orient_describe(OrbParams P, FrameSrc S
                                                           const int* __restrict__ lvlcnt, PslKeyPoint* __restrict__ kps,
                                                           uint8_t* __restrict__ desc, int* __restrict__ counts) {
     __shared__ uint32_t s_patch[4][37 * PSL_DESC_PD];
-    __shared__ uint32_t s_ori[4][31 * PSL_ORI_PD];
+    __shared__ uint32_t s_ori[4][32 * PSL_ORI_PD];  // 31 rows behind one that is only ever read masked
     int grp, frame;
     if (!psl_item_frame(S, &grp, &frame)) return;
     const int lane = threadIdx.x & 63;
-    const int slot = grp * 4 + (threadIdx.x >> 6);
+    // Everything up to the patch addresses is the same for the 64 lanes.  threadIdx.x >> 6 through readfirstlane tells the compiler
+    // so: the level search, P.lv[level] and the key then stay on the scalar unit (s_load from the arguments) instead of running as
+    // vector code with dependent vector loads in front of the patch loads.
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int slot = grp * 4 + wv;
     const int* lc = lvlcnt + (size_t)frame * P.nlevels;
     int level = -1, idx = slot, total = 0;
     for (int l = 0; l < P.nlevels; ++l) {
@@ -868,40 +907,54 @@ __global__ __launch_bounds__(256) void k_orient_describe(OrbParams P, FrameSrc S
     const int cx = (int)(key & 0xfff) + PSL_EDGE, cy = (int)((key >> 12) & 0xfff) + PSL_EDGE;
     int pitch;
     const uint8_t* img = psl_level_ptr(P, S, level, frame, &pitch);
+    // the lane's comparisons are j * 64 + lane (below); their offsets are asked for first and arrive behind the patches
+    float4 pt[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pt[j] = reinterpret_cast<const float4*>(c_orb_pattern)[j * 64 + lane];
 
     // One memory round trip for everything the keypoint needs: the 31 x 31 patch of the level image (orientation)
     // and the 37 x 37 patch of the blurred level (the 512 rBRIEF samples lie within radius 18.4 of the keypoint, so
     // the rotated, rounded offsets stay in [-18, 18]) are fetched with row-coalesced dword loads that are all in
     // flight together, then parked in LDS; the scattered per-lane samples come from there.
     const uint8_t* bl = blur + (size_t)frame * blur_fstride + L.blur_off;
-    uint32_t* patch = s_patch[threadIdx.x >> 6];
-    uint32_t* ori = s_ori[threadIdx.x >> 6];
+    uint32_t* patch = s_patch[wv];
+    uint32_t* ori = s_ori[wv] + PSL_ORI_PD;         // row 0 of the patch; the row in front of it is read (and masked) below
     const int pc0 = (cx - 18) & ~3, pr0 = cy - 18;  // blurred patch origin (dword-aligned column)
     const int oc0 = (cx - 15) & ~3, or0 = cy - 15;  // orientation patch origin
     const bool ori_dw = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)pitch) & 3) == 0 && oc0 + 4 * PSL_ORI_PD <= pitch;
     uint32_t pv[7], ov[5];
+    {
+        // Element k = lane + 64 t sits in row k / 11, dword k % 11.  One division for t = 0; 64 = 5 * 11 + 9, so a step of t adds 5
+        // rows and 9 dwords with at most one wrap.  Every lane loads (the row clamp keeps k >= 37 * 11 inside the level too); only
+        // the LDS writes are cut off at the patch's end.
+        int r = (int)((unsigned)lane / PSL_DESC_PD), d = lane - r * PSL_DESC_PD;
 #pragma unroll
-    for (int t = 0; t < 7; ++t) {
-        const int k = lane + 64 * t;
-        const int r = k / PSL_DESC_PD, d = k - r * PSL_DESC_PD;
-        int gy = pr0 + r;
-        gy = gy < 0 ? 0 : (gy >= L.h ? L.h - 1 : gy);  // never sampled; keeps the loads inside the level
-        const int gx = min(pc0 + d * 4, L.pitch - 4);
-        pv[t] = k < 37 * PSL_DESC_PD ? *reinterpret_cast<const uint32_t*>(bl + (size_t)gy * L.pitch + gx) : 0u;
+        for (int t = 0; t < 7; ++t) {
+            const int gy = min(max(pr0 + r, 0), L.h - 1);  // never sampled; keeps the loads inside the level
+            const int gx = min(pc0 + d * 4, L.pitch - 4);
+            pv[t] = *reinterpret_cast<const uint32_t*>(bl + (uint32_t)(gy * L.pitch + gx));
+            const bool wrap = d >= PSL_DESC_PD - 9;
+            d += wrap ? 9 - PSL_DESC_PD : 9;
+            r += wrap ? 6 : 5;
+        }
     }
     if (ori_dw) {
+        // likewise 64 = 7 * 9 + 1; the rows past the patch (t = 4 only) repeat its last row, which lies inside the level
+        int r = (int)((unsigned)lane / PSL_ORI_PD), d = lane - r * PSL_ORI_PD;
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
-            const int k = lane + 64 * t;
-            const int r = k / PSL_ORI_PD, d = k - r * PSL_ORI_PD;
-            ov[t] = k < 31 * PSL_ORI_PD ? *reinterpret_cast<const uint32_t*>(img + (size_t)(or0 + r) * pitch + oc0 + d * 4) : 0u;
+            const int rr = t == 4 ? min(r, 30) : r;
+            ov[t] = *reinterpret_cast<const uint32_t*>(img + (uint32_t)((or0 + rr) * pitch + oc0 + d * 4));
+            const bool wrap = d >= PSL_ORI_PD - 1;
+            d += wrap ? 1 - PSL_ORI_PD : 1;
+            r += wrap ? 8 : 7;
         }
     }
 #pragma unroll
-    for (int t = 0; t < 7; ++t) { const int k = lane + 64 * t; if (k < 37 * PSL_DESC_PD) patch[k] = pv[t]; }
+    for (int t = 0; t < 7; ++t) { const int k = lane + 64 * t; if (t < 6 || k < 37 * PSL_DESC_PD) patch[k] = pv[t]; }
     if (ori_dw) {
 #pragma unroll
-        for (int t = 0; t < 5; ++t) { const int k = lane + 64 * t; if (k < 31 * PSL_ORI_PD) ori[k] = ov[t]; }
+        for (int t = 0; t < 5; ++t) { const int k = lane + 64 * t; if (t < 4 || k < 31 * PSL_ORI_PD) ori[k] = ov[t]; }
     } else {  // caller's level-0 image with unaligned rows: bytes
         for (int k = lane; k < 31 * 31; k += 64) {
             const int r = k / 31, c = k - r * 31;
@@ -910,56 +963,55 @@ __global__ __launch_bounds__(256) void k_orient_describe(OrbParams P, FrameSrc S
     }
     __builtin_amdgcn_wave_barrier();
 
-    // intensity centroid over the radius-15 disc: lanes 0..30 take column u = lane-15 for v >= 0,
-    // lanes 32..62 the same column for v < 0
-    int m10 = 0, m01 = 0;
+    // Intensity centroid over the radius-15 disc.  Lanes 0..30 take column u = lane - 15 for v >= 0, lanes 32..62 the same column
+    // for v < 0; lanes 31 and 63 take nothing.  umax[] does not increase with v, so a column holds the rows |v| <= vmax(|u|)
+    // (P.vmax, a nibble per |u|), and one loop of 16 steps serves both halves: step k reads patch row 15 + k (v = k) in the lower
+    // half and row k - 1 (v = k - 16) in the upper half, both at the same immediate offset from the lane's base.  The lower half
+    // uses k <= vmax, the upper half k >= 16 - vmax, which is the complement of k <= 15 - vmax: one compare, flipped for the upper
+    // half on the scalar unit.  Step 0 of the upper half reads the row in front of the patch and is always masked.  Both sums
+    // ride in one register: sum(val) < 2^12 in the low half, sum(k * val) < 2^15 in the high half.  Integer sums: any order is exact.
+    int m10, m01;
     {
-        const int col = lane & 31;
-        if (col < 31) {
-            const int u = col - 15, au = u < 0 ? -u : u;
-            const uint8_t* c = reinterpret_cast<const uint8_t*>(ori) + 15 * (PSL_ORI_PD * 4) + (cx - oc0) + u;
-            int colsum = 0, vsum = 0;
-            if (lane < 32) {
+        const int col = lane & 31, u = col - 15, au = u < 0 ? -u : u;
+        const bool upper = lane >= 32;
+        const int vm = col < 31 ? (int)((P.vmax >> ((4 * au) & 63)) & 15) : -1;
+        const int T = upper ? 15 - vm : vm;
+        const uint8_t* c = reinterpret_cast<const uint8_t*>(ori) + (upper ? -1 : 15) * (PSL_ORI_PD * 4) + (cx - oc0) + u;
+        uint32_t acc = 0;
 #pragma unroll
-                for (int v = 0; v <= 15; ++v)
-                    if (au <= P.umax[v]) { const int val = c[v * (PSL_ORI_PD * 4)]; colsum += val; vsum += v * val; }
-            } else {
-#pragma unroll
-                for (int v = 1; v <= 15; ++v)
-                    if (au <= P.umax[v]) { const int val = c[-v * (PSL_ORI_PD * 4)]; colsum += val; vsum -= v * val; }
-            }
-            m10 = u * colsum;
-            m01 = vsum;
+        for (int k = 0; k <= 15; ++k) {
+            const uint32_t val = c[k * (PSL_ORI_PD * 4)];
+            acc += __umul24((k <= T) != upper ? val : 0u, 1u | ((uint32_t)k << 16));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { m10 += __shfl_xor(m10, o); m01 += __shfl_xor(m01, o); }
+        const int colsum = (int)(acc & 0xffffu), ksum = (int)(acc >> 16);
+        m10 = psl_wave_sum(u * colsum);
+        m01 = psl_wave_sum(upper ? ksum - 16 * colsum : ksum);
     }
     const float angle = psl_fast_atan2((float)m01, (float)m10);
 
-    // rBRIEF: lane i evaluates comparisons 4i..4i+3
+    // rBRIEF: lane i evaluates comparisons i, 64 + i, 128 + i and 192 + i, so that the 64 results of a step are a lane mask: bits
+    // 64 j .. 64 j + 63 of the descriptor as they stand, with nothing to pack across lanes.
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
     float a, b;
     psl_sincosf(PSL_FMUL(angle, factorPI), &b, &a);  // a = cos, b = sin
     const uint8_t* pb = reinterpret_cast<const uint8_t*>(patch) + 18 * (PSL_DESC_PD * 4) + (cx - pc0);
-    uint32_t nib = 0;
+    unsigned long long bits[4];
 #pragma unroll
-    for (int cmp = 0; cmp < 4; ++cmp) {
-        const int8_t* pt = &c_orb_pattern[(lane * 4 + cmp) * 4];
-        const float x0 = (float)pt[0], y0 = (float)pt[1], x1 = (float)pt[2], y1 = (float)pt[3];
+    for (int j = 0; j < 4; ++j) {
+        const float x0 = pt[j].x, y0 = pt[j].y, x1 = pt[j].z, y1 = pt[j].w;
         const int r0 = psl_cvround_f(PSL_FADD(PSL_FMUL(x0, b), PSL_FMUL(y0, a)));
         const int c0 = psl_cvround_f(PSL_FSUB(PSL_FMUL(x0, a), PSL_FMUL(y0, b)));
         const int r1 = psl_cvround_f(PSL_FADD(PSL_FMUL(x1, b), PSL_FMUL(y1, a)));
         const int c1 = psl_cvround_f(PSL_FSUB(PSL_FMUL(x1, a), PSL_FMUL(y1, b)));
-        const int t0 = pb[r0 * (PSL_DESC_PD * 4) + c0], t1 = pb[r1 * (PSL_DESC_PD * 4) + c1];
-        nib |= (uint32_t)(t0 < t1) << cmp;
+        const int t0 = pb[__mul24(r0, PSL_DESC_PD * 4) + c0], t1 = pb[__mul24(r1, PSL_DESC_PD * 4) + c1];  // |r| <= 18
+        bits[j] = __builtin_amdgcn_ballot_w64(t0 < t1);
     }
-    uint32_t v = nib << ((lane & 1) * 4);           // byte lane/2
-    v |= __shfl_xor(v, 1);
-    v <<= ((lane >> 1) & 3) * 8;                    // dword lane/8
-    v |= __shfl_xor(v, 2);
-    v |= __shfl_xor(v, 4);
     const size_t o = (size_t)frame * P.out_cap + slot;
-    if ((lane & 7) == 0) reinterpret_cast<uint32_t*>(desc + o * 32)[lane >> 3] = v;
+    if (lane == 0) {
+        uint4* dp = reinterpret_cast<uint4*>(desc + o * 32);
+        dp[0] = make_uint4((uint32_t)bits[0], (uint32_t)(bits[0] >> 32), (uint32_t)bits[1], (uint32_t)(bits[1] >> 32));
+        dp[1] = make_uint4((uint32_t)bits[2], (uint32_t)(bits[2] >> 32), (uint32_t)bits[3], (uint32_t)(bits[3] >> 32));
+    }
     if (lane < 7) {
         float f;
         const float px = (float)cx, py = (float)cy;

@@ -107,6 +107,15 @@ struct pslfe_orb {
         Q.minTh = std::min(Q.minTh, Q.iniTh);
         build_gauss_q8(7, 2.0, Q.blurK);
         for (int v = 0; v < 16; ++v) Q.umax[v] = umax[v];
+        // k_orient_describe bounds a column of the disc by the largest v with |u| <= umax[v]; umax[0] = 15 admits every |u| <= 15
+        for (int au = 0; au < 16; ++au) {
+            int vm = 0;
+            for (int v = 1; v < 16; ++v) {
+                PSL_REQUIRE(umax[v] <= umax[v - 1], PSLFE_E_STATE, "orb: umax[%d] = %d exceeds umax[%d] = %d", v, umax[v], v - 1, umax[v - 1]);
+                if (au <= umax[v]) vm = v;
+            }
+            Q.vmax |= (unsigned long long)vm << (4 * au);
+        }
         size_t pyr_off = 0, blur_off = 0;
         int cell_off = 0, cand_off = 0, kp_off = 0, tile_off = 0, cellcap = 1, max_kpcap = 0;
         for (int l = 0; l < nlevels; ++l) {
