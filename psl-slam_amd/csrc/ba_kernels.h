@@ -6,20 +6,14 @@
 // tools/dropin/ba_main.cpp for one core, so both run the same single IEEE operations (build with -ffp-contract=off; division and
 // square root are PSL_LM_DIV / PSL_LM_SQRT, sin / cos the restated tables of psl_sincos_glibc.h, no device math library).
 //
-// One text for both.  Every step is a function of (workspace, index) that writes only what the index owns, and the drivers below
-// (psl_ba_solve, psl_ba_levenberg, psl_ba_rounds) are templates over an executor `Exec`:
-//   par(n, f)      f(0) .. f(n - 1), independent of each other; all of them are done before the next step starts
-//   one(f)         f() once, done before the next step starts
-//   sum256(f)      the ordered sum of the 256 partial sums f(0) .. f(255): a butterfly in each group of 64, then ((G0 + G1) + G2) + G3
-//                  (psl_lm_reduce_lanes here, psl_lm_reduce of lm_device.h on the device)
-//   get(p)         the value at p, the same for every caller, read before anybody writes there again
-// PslBaSerial below runs them on one core; the kernel's executor spreads par over the 256 threads of a workgroup with a barrier
-// after it.  Because no step depends on how its indices are spread, the two equal each other bit for bit by construction.
+// One text for both.  Every step is a function of (workspace, index) that writes only what the index owns, and what runs the steps
+// (psl_ba_solve, PslBaProblem, psl_ba_rounds) is a template over an executor `Exec`: par / one / sum256 / get, whose contract is in
+// lm_kernels.h above psl_lm_levenberg.  PslLmSerial runs them on one core, PslLmWorkgroup of lm_device.h on the 256 threads of a
+// workgroup.  Because no step depends on how its indices are spread, the two equal each other bit for bit by construction.
 //
-// psl_lm_optimize of lm_kernels.h is written for one vertex of a compile-time size N (its arrays are acc[NH + N + 1], x[N], b[N]
-// and its solve is unrolled in N), so it cannot be instantiated here; psl_ba_levenberg is the same loop - lambda, ni, the ten
-// trials, rho, _nBad, Terminate, the failed solve - over a system in HBM.  Three places hold that loop and move together:
-// psl_lm_optimize (lm_kernels.h), psl_ba_levenberg (here), and the loops written out in k_pose_optimize / k_sim3_optimize.
+// The Levenberg loop - lambda, ni, the ten trials, rho, _nBad, Terminate, the failed solve - is the driver psl_lm_levenberg of
+// lm_kernels.h; PslBaProblem gives it the steps over a system in HBM.  The loop has three texts that are changed together: the
+// driver psl_lm_levenberg, and the two loops written out in k_pose_optimize and k_sim3_optimize.
 //
 // Restated from the reference:
 //   EdgeSE3ProjectXYZ          Thirdparty/g2o/g2o/types/types_six_dof_expmap.h:90-106 (computeError, isDepthPositive), .cpp:103-148
@@ -743,91 +737,66 @@ PSL_BA_HD double psl_ba_chi_partial(const PslBaWs& W, int p) {
     return s;
 }
 
-// One optimize(iterations) call: psl_lm_optimize over the F pose blocks and the active points.  chi_first: the chi2 of iteration 0;
-// chi_last: the current chi2 when the call returns.  Returns the iterations run.
+// The `Problem` of psl_lm_levenberg (lm_kernels.h) for one optimize() call over the F pose blocks and the active points.
 // With LIL the LIL edges are evaluated in a step of their own, and `nact` is the number of active LILs of the round.
-template <bool LIL, class Exec>
-PSL_BA_HD int psl_ba_levenberg(Exec& X, const PslBaWs& W, int F, int nact, int iterations, int robust, double* chi_first, double* chi_last) {
-    int its = 0;
-    double lambda = 0.0, ni = 2.0;
-    int nbad = 0;
-    for (int it = 0; it < iterations; ++it) {
+template <bool LIL>
+struct PslBaProblem {
+    const PslBaWs& W;
+    int F, nact, robust;
+    template <class Exec> PSL_LM_MEMBER double linearize(Exec& X, double* chi_first) {
         X.par(W.ne, [&](int e) { psl_ba_edge(W, e, W.T, W.X, robust, 1); });
         if constexpr (LIL) X.par(W.nle, [&](int e) { psl_ba_lil_edge(W, e, W.T, W.L, robust, 1); });
-        double chi = X.sum256([&](int p) { return psl_ba_chi_partial<LIL>(W, p); });
-        const double ini_chi = chi;
-        if (it == 0) *chi_first = chi;
+        const double chi = X.sum256([&](int p) { return psl_ba_chi_partial<LIL>(W, p); });
+        if (chi_first) *chi_first = chi;
         X.par(27 * F, [&](int t) { psl_ba_build_pose<LIL>(W, t); });
         X.par(9 * W.nmp, [&](int t) { psl_ba_build_point(W, t); });
         if constexpr (LIL) X.par(9 * W.nlil, [&](int t) { psl_ba_build_lil(W, t); });
-        if (it == 0) {
-            X.one([&] { W.scal[0] = psl_ba_lambda_init<LIL>(W, F); });
-            lambda = X.get(W.scal);
-            ni = 2.0;
-            nbad = 0;
-        }
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            const int ok = psl_ba_solve<LIL>(X, W, F, lambda);
-            double temp_chi = PSL_LM_DBL_MAX;   // a failed solve (:126)
-            double scale = 0.0;                 // ... has a zero step in rho
-            if (ok) {
-                X.par(W.nkf + W.nmp, [&](int v) {   // oplusImpl of every active vertex
-                    if (v < W.nkf) {
-                        const int i = W.pidx[v];
-                        if (i < 0) return;
-                        PslSE3 dT;
-                        psl_po_exp(W.xp + 6 * (size_t)i, &dT, W.sctab);
-                        psl_po_mul(&dT, &W.T[v], &W.Tn[v]);
-                    } else {
-                        const int p = v - W.nkf;
-                        if (!W.pact[p]) return;
-                        for (int j = 0; j < 3; ++j) W.Xn[3 * (size_t)p + j] = W.X[3 * (size_t)p + j] + W.xl[3 * (size_t)p + j];
-                    }
-                });
-                if constexpr (LIL) X.par(W.nlil, [&](int j) { psl_ba_lil_update(W, j, nact); });
-                X.par(W.ne, [&](int e) { psl_ba_edge(W, e, W.Tn, W.Xn, robust, 0); });
-                if constexpr (LIL) X.par(W.nle, [&](int e) { psl_ba_lil_edge(W, e, W.Tn, W.Ln, robust, 0); });
-                temp_chi = X.sum256([&](int p) { return psl_ba_chi_partial<LIL>(W, p); });
-                X.one([&] { W.scal[1] = psl_ba_scale<LIL>(W, F, lambda); });
-                scale = X.get(W.scal + 1);
-            }
-            scale = scale + 1e-3;
-            rho = PSL_LM_DIV(chi - temp_chi, scale);
-            if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_LM_DBL_MAX) {
-                lambda = lambda * psl_lm_good_scale(rho);
-                ni = 2.0;
-                chi = temp_chi;
-                if constexpr (LIL)
-                    if (ok)
-                        X.par(15 * W.nlil, [&](int t) {
-                            if (W.pact[W.nmp + t / 15]) W.L[t] = W.Ln[t];
-                        });
-                if (ok)
-                    X.par(W.nkf + W.nmp, [&](int v) {   // discardTop: the candidate becomes the estimate
-                        if (v < W.nkf) {
-                            if (W.pidx[v] >= 0) W.T[v] = W.Tn[v];
-                        } else {
-                            const int p = v - W.nkf;
-                            if (!W.pact[p]) return;
-                            for (int j = 0; j < 3; ++j) W.X[3 * (size_t)p + j] = W.Xn[3 * (size_t)p + j];
-                        }
-                    });
-            } else {
-                lambda = lambda * ni;
-                ni = ni * 2.0;
-            }
-            ++qmax;
-        } while (rho < 0 && qmax < 10);
-        ++its;
-        *chi_last = chi;
-        if (qmax == 10 || rho == 0) break;                               // Terminate
-        if ((ini_chi - chi) * 1e3 < ini_chi) ++nbad; else nbad = 0;      // the _nBad rule
-        if (nbad >= 3) break;
+        return chi;
     }
-    return its;
-}
+    template <class Exec> PSL_LM_MEMBER double lambda_init(Exec& X) {
+        X.one([&] { W.scal[0] = psl_ba_lambda_init<LIL>(W, F); });
+        return X.get(W.scal);
+    }
+    template <class Exec> PSL_LM_MEMBER int solve(Exec& X, double lambda) { return psl_ba_solve<LIL>(X, W, F, lambda); }
+    template <class Exec> PSL_LM_MEMBER double candidate(Exec& X) {
+        X.par(W.nkf + W.nmp, [&](int v) {   // oplusImpl of every active vertex
+            if (v < W.nkf) {
+                const int i = W.pidx[v];
+                if (i < 0) return;
+                PslSE3 dT;
+                psl_po_exp(W.xp + 6 * (size_t)i, &dT, W.sctab);
+                psl_po_mul(&dT, &W.T[v], &W.Tn[v]);
+            } else {
+                const int p = v - W.nkf;
+                if (!W.pact[p]) return;
+                for (int j = 0; j < 3; ++j) W.Xn[3 * (size_t)p + j] = W.X[3 * (size_t)p + j] + W.xl[3 * (size_t)p + j];
+            }
+        });
+        if constexpr (LIL) X.par(W.nlil, [&](int j) { psl_ba_lil_update(W, j, nact); });
+        X.par(W.ne, [&](int e) { psl_ba_edge(W, e, W.Tn, W.Xn, robust, 0); });
+        if constexpr (LIL) X.par(W.nle, [&](int e) { psl_ba_lil_edge(W, e, W.Tn, W.Ln, robust, 0); });
+        return X.sum256([&](int p) { return psl_ba_chi_partial<LIL>(W, p); });
+    }
+    template <class Exec> PSL_LM_MEMBER double scale(Exec& X, double lambda) {
+        X.one([&] { W.scal[1] = psl_ba_scale<LIL>(W, F, lambda); });
+        return X.get(W.scal + 1);
+    }
+    template <class Exec> PSL_LM_MEMBER void accept(Exec& X) {   // discardTop: the candidate becomes the estimate
+        if constexpr (LIL)
+            X.par(15 * W.nlil, [&](int t) {
+                if (W.pact[W.nmp + t / 15]) W.L[t] = W.Ln[t];
+            });
+        X.par(W.nkf + W.nmp, [&](int v) {
+            if (v < W.nkf) {
+                if (W.pidx[v] >= 0) W.T[v] = W.Tn[v];
+            } else {
+                const int p = v - W.nkf;
+                if (!W.pact[p]) return;
+                for (int j = 0; j < 3; ++j) W.X[3 * (size_t)p + j] = W.Xn[3 * (size_t)p + j];
+            }
+        });
+    }
+};
 
 // `bad` of edge e after a round (src/Optimizer.cc:1663, :1679, :1755, :1770): the plain chi2 of its cached _error as a double
 // against 5.991 / 7.815, or !isDepthPositive at the estimates
@@ -914,7 +883,9 @@ PSL_BA_HD void psl_ba_rounds(Exec& X, const PslBaWs& W, int rounds, PslBaKeyFram
         const int F = X.get(W.flag + 1);
         double first = 0.0, last = r ? chi_r[0] : 0.0;
         if (F > 0) {
-            its[r] = psl_ba_levenberg<LIL>(X, W, F, nact, r == 0 ? 5 : 10, robust, &first, &last);
+            PslBaProblem<LIL> P = {W, F, nact, robust};
+            double lambda;
+            its[r] = psl_lm_levenberg(X, P, r == 0 ? 5 : 10, &first, &last, &lambda);
         } else {
             X.par(W.ne, [&](int e) { psl_ba_edge(W, e, W.T, W.X, robust, 0); });
             if constexpr (LIL) X.par(W.nle, [&](int e) { psl_ba_lil_edge(W, e, W.T, W.L, robust, 0); });
@@ -1039,18 +1010,6 @@ static inline int psl_ba_lil_lists_host(const PslBaWs& W) {
     }
     return PSLFE_OK;
 }
-
-// the executor of one core
-struct PslBaSerial {
-    double* part;   // [256]
-    template <class Fn> void par(int n, Fn f) { for (int i = 0; i < n; ++i) f(i); }
-    template <class Fn> void one(Fn f) { f(); }
-    template <class Fn> double sum256(Fn f) {
-        for (int p = 0; p < PSL_LM_LANES; ++p) part[p] = f(p);
-        return psl_lm_reduce_lanes(part);
-    }
-    template <class V> V get(const V* p) { return *p; }
-};
 #endif
 
 #endif

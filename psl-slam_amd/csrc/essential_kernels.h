@@ -6,9 +6,10 @@
 // log / exp / acos those of psl_f64math.h, no device math library).  tests/essential_cases.py is the same text in Python.
 //
 // One text for both, as ba_kernels.h: every step is a function of (workspace, index) that writes only what the index owns, and
-// psl_eg_run is a template over an executor `Exec` (par / one / sum256 / get, the header of ba_kernels.h).  PslEgSerial below runs
-// the steps on one core; the kernel's executor spreads par over the 256 threads of a workgroup with a barrier after it.  No step
-// depends on how its indices are spread, so the two equal each other bit for bit by construction.
+// psl_eg_run is a template over an executor `Exec` (par / one / sum256 / get: the contract is in lm_kernels.h above
+// psl_lm_levenberg, the Levenberg driver, which PslEgProblem gives its steps).  PslLmSerial runs the steps on one core,
+// PslLmWorkgroup of lm_device.h on the 256 threads of a workgroup with a barrier after each.  No step depends on how its indices
+// are spread, so the two equal each other bit for bit by construction.
 //
 // Restated from the reference:
 //   the vertices, the measurements, the call          src/Optimizer.cc:2564-2599, :2607-2738, :2741-2742
@@ -423,72 +424,49 @@ PSL_EG_HD double psl_eg_chi_partial(const PslEgWs& W, int p) {
     return s;
 }
 
-// One optimize(iterations) call over the F free keyframes: psl_ba_levenberg's loop with lambda starting at lambda_init (g2o's
-// computeLambdaInit returns the user's value when it is positive).  Returns the iterations run.
-template <class Exec>
-PSL_EG_HD int psl_eg_levenberg(Exec& X, const PslEgWs& W, int F, int iterations, double lambda_init, double* chi_first, double* chi_last,
-                               double* lambda_out) {
-    int its = 0;
-    double lambda = 0.0, ni = 2.0;
-    int nbad = 0;
-    for (int it = 0; it < iterations; ++it) {
+// The `Problem` of psl_lm_levenberg (lm_kernels.h) for one optimize() call over the F free keyframes.  lambda0: the user's lambda
+// (g2o's computeLambdaInit returns it when it is positive).
+struct PslEgProblem {
+    const PslEgWs& W;
+    int F;
+    double lambda0;
+    template <class Exec> PSL_LM_MEMBER double linearize(Exec& X, double* chi_first) {
         X.par(15 * W.nkf, [&](int t) { psl_eg_perturb(W, t); });
         X.par(PSL_EG_EVALS * W.ne, [&](int t) { psl_eg_linearize(W, t); });
-        double chi = X.sum256([&](int p) { return psl_eg_chi_partial(W, p); });
-        const double ini_chi = chi;
-        if (it == 0) *chi_first = chi;
+        const double chi = X.sum256([&](int p) { return psl_eg_chi_partial(W, p); });
+        if (chi_first) *chi_first = chi;
         X.par(56 * F, [&](int t) { psl_eg_build_diag(W, t); });
         X.par(49 * F, [&](int t) { psl_eg_build_env(W, t); });
-        if (it == 0) { lambda = lambda_init; ni = 2.0; nbad = 0; }
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            const int ok = psl_eg_solve(X, W, F, lambda);
-            double temp_chi = PSL_LM_DBL_MAX;   // a failed solve
-            double scale = 0.0;                 // ... has a zero step in rho
-            if (ok) {
-                X.par(W.nkf, [&](int v) {       // oplusImpl of every free vertex; with a fixed scale it clears the solver's x[6]
-                    const int i = W.pidx[v];
-                    if (i < 0) return;
-                    double* x = W.x + 7 * (size_t)i;
-                    if (W.fix_scale) x[6] = 0.0;
-                    psl_s3_oplus(x, W.fix_scale, &W.S[v], W.sctab, &W.Sn[v], nullptr);
-                    psl_s3_inverse(&W.Sn[v], &W.Sni[v]);
-                });
-                X.par(W.ne, [&](int e) { psl_eg_trial_error(W, e); });
-                temp_chi = X.sum256([&](int p) { return psl_eg_chi_partial(W, p); });
-                X.one([&] {                     // computeScale: sum x_j (lambda x_j + b_j) in index order
-                    double sc = 0.0;
-                    for (int j = 0; j < 7 * F; ++j) sc = sc + W.x[j] * (lambda * W.x[j] + W.b[j]);
-                    W.scal[1] = sc;
-                });
-                scale = X.get(W.scal + 1);
-            }
-            scale = scale + 1e-3;
-            rho = PSL_LM_DIV(chi - temp_chi, scale);
-            if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_LM_DBL_MAX) {
-                lambda = lambda * psl_lm_good_scale(rho);
-                ni = 2.0;
-                chi = temp_chi;
-                if (ok)
-                    X.par(W.nkf, [&](int v) {   // discardTop: the candidate becomes the estimate
-                        if (W.pidx[v] >= 0) { W.S[v] = W.Sn[v]; W.Si[v] = W.Sni[v]; }
-                    });
-            } else {
-                lambda = lambda * ni;
-                ni = ni * 2.0;
-            }
-            ++qmax;
-        } while (rho < 0 && qmax < 10);
-        ++its;
-        *chi_last = chi;
-        if (qmax == 10 || rho == 0) break;                               // Terminate
-        if ((ini_chi - chi) * 1e3 < ini_chi) ++nbad; else nbad = 0;      // the _nBad rule
-        if (nbad >= 3) break;
+        return chi;
     }
-    *lambda_out = lambda;
-    return its;
-}
+    template <class Exec> PSL_LM_MEMBER double lambda_init(Exec&) { return lambda0; }
+    template <class Exec> PSL_LM_MEMBER int solve(Exec& X, double lambda) { return psl_eg_solve(X, W, F, lambda); }
+    template <class Exec> PSL_LM_MEMBER double candidate(Exec& X) {
+        X.par(W.nkf, [&](int v) {       // oplusImpl of every free vertex; with a fixed scale it clears the solver's x[6]
+            const int i = W.pidx[v];
+            if (i < 0) return;
+            double* x = W.x + 7 * (size_t)i;
+            if (W.fix_scale) x[6] = 0.0;
+            psl_s3_oplus(x, W.fix_scale, &W.S[v], W.sctab, &W.Sn[v], nullptr);
+            psl_s3_inverse(&W.Sn[v], &W.Sni[v]);
+        });
+        X.par(W.ne, [&](int e) { psl_eg_trial_error(W, e); });
+        return X.sum256([&](int p) { return psl_eg_chi_partial(W, p); });
+    }
+    template <class Exec> PSL_LM_MEMBER double scale(Exec& X, double lambda) {
+        X.one([&] {                     // computeScale: sum x_j (lambda x_j + b_j) in index order
+            double sc = 0.0;
+            for (int j = 0; j < 7 * F; ++j) sc = sc + W.x[j] * (lambda * W.x[j] + W.b[j]);
+            W.scal[1] = sc;
+        });
+        return X.get(W.scal + 1);
+    }
+    template <class Exec> PSL_LM_MEMBER void accept(Exec& X) {
+        X.par(W.nkf, [&](int v) {       // discardTop: the candidate becomes the estimate
+            if (W.pidx[v] >= 0) { W.S[v] = W.Sn[v]; W.Si[v] = W.Sni[v]; }
+        });
+    }
+};
 
 // Everything of one graph.  `code`: what the caller found in the offsets and the counts (PSLFE_OK, PSLFE_E_CAPACITY, or
 // PSLFE_E_INVALID with have == 0 when the offsets name no rows at all); the rows and the envelope are checked here.  A refused
@@ -590,7 +568,8 @@ PSL_EG_HD void psl_eg_run(Exec& X, const PslEgWs& W, int have, int code, size_t 
     int its = 0;
     if (F > 0 && W.ne > 0) {
         X.par(W.ne, [&](int e) { psl_eg_measure(W, e); });
-        its = psl_eg_levenberg(X, W, F, PSL_EG_ITERATIONS, PSL_EG_LAMBDA_INIT, &chi_first, &chi_last, &lambda);
+        PslEgProblem P = {W, F, PSL_EG_LAMBDA_INIT};
+        its = psl_lm_levenberg(X, P, PSL_EG_ITERATIONS, &chi_first, &chi_last, &lambda);
         X.one([&] {
             int m = 0;
             for (size_t t = 0; t < PSL_EG_EVALS * (size_t)W.ne; ++t) m |= W.bmask[t];
@@ -635,19 +614,5 @@ PSL_EG_HD void psl_eg_run(Exec& X, const PslEgWs& W, int have, int code, size_t 
         *info = I;
     });
 }
-
-#if !defined(__HIP_DEVICE_COMPILE__)
-// the executor of one core
-struct PslEgSerial {
-    double* part;   // [256]
-    template <class Fn> void par(int n, Fn f) { for (int i = 0; i < n; ++i) f(i); }
-    template <class Fn> void one(Fn f) { f(); }
-    template <class Fn> double sum256(Fn f) {
-        for (int p = 0; p < PSL_LM_LANES; ++p) part[p] = f(p);
-        return psl_lm_reduce_lanes(part);
-    }
-    template <class V> V get(const V* p) { return *p; }
-};
-#endif
 
 #endif

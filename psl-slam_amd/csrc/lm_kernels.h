@@ -1,11 +1,14 @@
-// g2o's Levenberg loop on one vertex as functions of one thread: the LDLt solve in N unknowns, lambda, rho, the Huber kernel and the
-// driver psl_lm_optimize (one optimize() call: the iterations, the trials of an iteration and every decision g2o makes between two
-// sums).  Product code, shared by the pose optimisation (pose_kernels.h, N = 6) and OptimizeSim3 (sim3_kernels.h, N = 7).  Plain C++
-// text: the kernels include it for the device and the host loops of tools/dropin/pose_main.cpp and sim3_main.cpp for one core, so
-// all run the same single IEEE operations (build with -ffp-contract=off).  The driver knows neither the vertex type nor how a sum
-// is formed: it asks its `Problem` argument for both.  Both host loops instantiate it; k_pose_optimize and k_sim3_optimize call
-// the primitives here but hold the driver's loop written out (the headers of pslfe_pose.hip and pslfe_sim3.hip say why), so the
-// three are changed together.  Restated from the reference's g2o:
+// g2o's Levenberg loop: the driver psl_lm_levenberg (one optimize() call: the iterations, the trials of an iteration and every
+// decision g2o makes between two sums) over an executor and a `Problem`, and, as functions of one thread, what one vertex needs: the
+// LDLt solve in N unknowns, lambda, rho, the Huber kernel and psl_lm_optimize, the driver on one vertex.  Product code, shared by the
+// pose optimisation (pose_kernels.h, N = 6), OptimizeSim3 (sim3_kernels.h, N = 7), the local bundle adjustment (ba_kernels.h) and
+// the essential graph (essential_kernels.h).  Plain C++ text: the kernels include it for the device and the host loops of
+// tools/dropin for one core, so all run the same single IEEE operations (build with -ffp-contract=off).  The driver knows neither
+// the vertices nor how a sum is formed or a system solved: it asks its `Problem` argument.  k_ba_local, k_eg_optimize and all five
+// host loops instantiate it; k_pose_optimize and k_sim3_optimize call the primitives here but hold the driver's loop written out
+// (instantiating it there cost 0.6 to 1.9 % per launch: profiles/pose_driver_ab.json, the headers of pslfe_pose.hip and
+// pslfe_sim3.hip).  So the loop has three texts that are changed together: the driver psl_lm_levenberg, and the two loops written
+// out in k_pose_optimize and k_sim3_optimize.  Restated from the reference's g2o:
 //   one iteration, the loop   Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189, sparse_optimizer.cpp:354-419
 //   Huber                     Thirdparty/g2o/g2o/core/robust_kernel_impl.cpp:78-92
 // tests/lm_cases.py is the same loop in numpy.  DESIGN.md §5.0k, §5.0l.
@@ -156,52 +159,56 @@ PSL_LM_HD double psl_lm_good_scale(double rho) {
     return (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);     // std::max(lower, alpha)
 }
 
-// One optimize(iterations) call of g2o on one vertex of N unknowns: up to `iterations` Levenberg iterations of up to ten trials.
-// Problem holds the estimate and a candidate for it and supplies what depends on the vertex type and on the sums:
-//   sums(acc)       the N (N + 1) / 2 values of H (upper triangle, row by row), the N of b (before the sign) and the robust chi2
-//                   of the active edges at the estimate, summed in the Problem's own, fixed order
-//   candidate(x)    forms the candidate, oplus(estimate, x).  It may edit x: what it leaves there enters rho, as g2o's computeScale
-//                   reads the solver's own vector after oplusImpl has written into it
-//   chi()           the robust chi2 of the active edges at the candidate
-//   accept()        the candidate becomes the estimate
-// lambda, ni and _nBad are initialised by each call.  A failed solve - or a step whose angle psl_lm_step_ok refuses - makes the
-// trial's chi2 DBL_MAX with a zero step in rho (:120): no candidate is formed, the trial is rejected and lambda grows.  Returns the
-// iterations run.
-template <int N, class Problem>
-PSL_LM_HD int psl_lm_optimize(Problem& P, int iterations) {
-    constexpr int NH = N * (N + 1) / 2;
+// One optimize(iterations) call of g2o: up to `iterations` Levenberg iterations of up to ten trials, with every decision g2o makes
+// between two sums and nothing else.  What is optimised, and on what it runs, are the two arguments.
+//
+// The executor `Exec` runs the steps of a Problem; this is its whole contract:
+//   par(n, f)      f(0) .. f(n - 1), independent of each other; all of them are done before the next step starts
+//   one(f)         f() once, done before the next step starts
+//   sum256(f)      the ordered sum of the 256 partial sums f(0) .. f(255): a butterfly in each group of 64, then ((G0 + G1) + G2) + G3
+//   get(p)         the value at p, the same for every caller, read before anybody writes there again
+// PslLmSerial below runs them on one core (sum256 through psl_lm_reduce_lanes); PslLmWorkgroup of lm_device.h spreads par over the
+// 256 threads of a workgroup with a barrier after it (sum256 through psl_lm_reduce).  A Problem whose steps are functions of
+// (workspace, index) that write only what the index owns does not depend on how the indices are spread, so the two executors give
+// the same bits by construction.
+//
+// The `Problem` holds the estimate and a candidate for it and supplies what differs between the optimisers, each a template over Exec:
+//   linearize(X, chi_first)   the errors and Jacobians at the estimate, the ordered sum of the robust chi2 of the active edges, then H
+//                             and b.  Returns that chi2 and, where chi_first is not NULL, also writes it there
+//   lambda_init(X)            the lambda of iteration 0 (computeLambdaInit, :166-180)
+//   solve(X, lambda)          (H + lambda I) x = b: 1 and the step x, or 0, "the solve failed"
+//   candidate(X)              oplus(estimate, x) on every vertex and the errors there.  Returns the robust chi2 at the candidate
+//   scale(X, lambda)          computeScale: sum x_j (lambda x_j + b_j) in index order, of the x that candidate left
+//   accept(X)                 the candidate becomes the estimate
+// lambda, ni and _nBad are initialised by each call.  A failed solve makes the trial's chi2 DBL_MAX with a zero step in rho (:120):
+// no candidate is formed, the trial is rejected and lambda grows.  chi_first: the chi2 of iteration 0; chi_last: the current chi2
+// when the call returns; lambda_out: the lambda then.  Returns the iterations run.
+template <class Exec, class Problem>
+PSL_LM_HD int psl_lm_levenberg(Exec& X, Problem& P, int iterations, double* chi_first, double* chi_last, double* lambda_out) {
     int its = 0;
     double lambda = 0.0, ni = 2.0;
     int nbad = 0;   // _nBad: iterations in a row that gained less than 1e-3 of their chi2
     for (int it = 0; it < iterations; ++it) {
-        double acc[NH + N + 1];
-        P.sums(acc);
-        double b[N];
-        for (int j = 0; j < N; ++j) b[j] = -acc[NH + j];
-        double chi = acc[NH + N];
+        double chi = P.linearize(X, it == 0 ? chi_first : nullptr);
         const double ini_chi = chi;
-        if (it == 0) { lambda = psl_lm_lambda_init<N>(acc); ni = 2.0; nbad = 0; }
+        if (it == 0) { lambda = P.lambda_init(X); ni = 2.0; nbad = 0; }
         double rho = 0.0;
         int qmax = 0;
         do {
-            double x[N];
-            for (int j = 0; j < N; ++j) x[j] = 0.0;
-            int ok = psl_lm_solve<N>(acc, lambda, b, x);
-            if (ok && !psl_lm_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
-                ok = 0;
-                for (int j = 0; j < N; ++j) x[j] = 0.0;
-            }
+            const int ok = P.solve(X, lambda);
             double temp_chi = PSL_LM_DBL_MAX;   // a failed solve (:120)
+            double scale = 0.0;                 // ... has a zero step in rho
             if (ok) {
-                P.candidate(x);
-                temp_chi = P.chi();
+                temp_chi = P.candidate(X);
+                scale = P.scale(X, lambda);
             }
-            rho = psl_lm_rho<N>(chi, temp_chi, x, b, lambda);
+            scale = scale + 1e-3;
+            rho = PSL_LM_DIV(chi - temp_chi, scale);   // (:129-132)
             if (rho > 0 && __builtin_fabs(temp_chi) <= PSL_LM_DBL_MAX) {
                 lambda = lambda * psl_lm_good_scale(rho);
                 ni = 2.0;
                 chi = temp_chi;
-                if (ok) P.accept();   // a failed solve has no candidate: the estimate stays (chi = inf reaches this)
+                if (ok) P.accept(X);   // a failed solve has no candidate: the estimate stays (chi = inf reaches this)
             } else {
                 lambda = lambda * ni;
                 ni = ni * 2.0;
@@ -209,11 +216,81 @@ PSL_LM_HD int psl_lm_optimize(Problem& P, int iterations) {
             ++qmax;
         } while (rho < 0 && qmax < 10);
         ++its;
+        *chi_last = chi;
         if (qmax == 10 || rho == 0) break;                               // Terminate
         if ((ini_chi - chi) * 1e3 < ini_chi) ++nbad; else nbad = 0;      // the _nBad rule
         if (nbad >= 3) break;
     }
+    *lambda_out = lambda;
     return its;
 }
+
+// psl_lm_levenberg on one vertex of N unknowns, on one core.  Problem holds the estimate and a candidate for it and supplies what
+// depends on the vertex type and on the sums:
+//   sums(acc)       the N (N + 1) / 2 values of H (upper triangle, row by row), the N of b (before the sign) and the robust chi2
+//                   of the active edges at the estimate, summed in the Problem's own, fixed order
+//   candidate(x)    forms the candidate, oplus(estimate, x).  It may edit x: what it leaves there enters rho, as g2o's computeScale
+//                   reads the solver's own vector after oplusImpl has written into it
+//   chi()           the robust chi2 of the active edges at the candidate
+//   accept()        the candidate becomes the estimate
+// A step whose angle psl_lm_step_ok refuses counts as a failed solve.  Returns the iterations run.
+template <int N, class Problem>
+PSL_LM_HD int psl_lm_optimize(Problem& P, int iterations);
+
+#if !defined(__HIP_DEVICE_COMPILE__)   // the host loops only; the device pass sees the declaration above, which psl_po_rounds and psl_s3_rounds name
+// the executor of one core
+struct PslLmSerial {
+    double* part;   // [256]; a Problem that never sums may leave it NULL
+    template <class Fn> PSL_LM_MEMBER void par(int n, Fn f) { for (int i = 0; i < n; ++i) f(i); }
+    template <class Fn> PSL_LM_MEMBER void one(Fn f) { f(); }
+    template <class Fn> PSL_LM_MEMBER double sum256(Fn f) {
+        for (int p = 0; p < PSL_LM_LANES; ++p) part[p] = f(p);
+        return psl_lm_reduce_lanes(part);
+    }
+    template <class V> PSL_LM_MEMBER V get(const V* p) { return *p; }
+};
+
+// A `Vertex` (the contract of psl_lm_optimize) as a Problem of the driver: the system of one vertex of N unknowns in registers
+template <int N, class Vertex>
+struct PslLmOneVertex {
+    static constexpr int NH = N * (N + 1) / 2;
+    Vertex& P;
+    double acc[NH + N + 1], b[N], x[N];
+    template <class Exec> PSL_LM_MEMBER double linearize(Exec&, double* chi_first) {
+        P.sums(acc);
+        for (int j = 0; j < N; ++j) b[j] = -acc[NH + j];
+        if (chi_first) *chi_first = acc[NH + N];
+        return acc[NH + N];
+    }
+    template <class Exec> PSL_LM_MEMBER double lambda_init(Exec&) { return psl_lm_lambda_init<N>(acc); }
+    template <class Exec> PSL_LM_MEMBER int solve(Exec&, double lambda) {
+        for (int j = 0; j < N; ++j) x[j] = 0.0;
+        int ok = psl_lm_solve<N>(acc, lambda, b, x);
+        if (ok && !psl_lm_step_ok(x)) {   // a rotation angle outside the range of the restated sin / cos: as a failed solve
+            ok = 0;
+            for (int j = 0; j < N; ++j) x[j] = 0.0;
+        }
+        return ok;
+    }
+    template <class Exec> PSL_LM_MEMBER double candidate(Exec&) {
+        P.candidate(x);
+        return P.chi();
+    }
+    template <class Exec> PSL_LM_MEMBER double scale(Exec&, double lambda) {
+        double s = 0.0;
+        for (int j = 0; j < N; ++j) s = s + x[j] * (lambda * x[j] + b[j]);
+        return s;
+    }
+    template <class Exec> PSL_LM_MEMBER void accept(Exec&) { P.accept(); }
+};
+
+template <int N, class Problem>
+PSL_LM_HD int psl_lm_optimize(Problem& P, int iterations) {
+    PslLmSerial X = {nullptr};
+    PslLmOneVertex<N, Problem> V = {P};
+    double chi_first, chi_last, lambda;
+    return psl_lm_levenberg(X, V, iterations, &chi_first, &chi_last, &lambda);
+}
+#endif
 
 #endif

@@ -1,9 +1,10 @@
 // libpslfe: the point edges of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1025-1966; the EdgeSE3ProjectXYZ /
 // EdgeStereoSE3ProjectXYZ part of LocalBundleAdjustmentAndInseclines :1968-2534) for K problems in one launch.  Product code.
 // Who owns what.  ba_kernels.h holds everything that is arithmetic or a decision: the edges, the quadratic form, the Schur
-// complement, the LDLt, the Levenberg loop and the two rounds, written once over an executor (its header); the host loop of
-// tools/dropin/ba_main.cpp runs the same text on one core.  This file owns the handle, the two pre-pass kernels, the executor of a
-// workgroup and the entry points.  Conventions: include/pslfe.h above pslfe_ba_local_device.
+// complement, the LDLt, the `Problem` of the Levenberg driver psl_lm_levenberg (lm_kernels.h) and the two rounds, written once over
+// an executor (the contract: lm_kernels.h); the host loop of tools/dropin/ba_main.cpp runs the same text on one core.  This file
+// owns the handle, the two pre-pass kernels and the entry points; the executor of a workgroup is PslLmWorkgroup of lm_device.h.
+// Conventions: include/pslfe.h above pslfe_ba_local_device.
 //
 // The kernels are templates over LIL, the switch of ba_kernels.h: pslfe_ba_local[_device] launch the <false> instantiations (the
 // point-only text; 183 VGPRs, scratch 0, LDS 5184 B as before), pslfe_ba_local_lil[_device] the <true> ones, which also check, list
@@ -225,34 +226,6 @@ __global__ __launch_bounds__(PSL_BA_BS) void k_ba_lists(BaArgs A) {
     if (tid == 0 && s_dup) A.status[2 * k] = PSLFE_E_INVALID;
 }
 
-// the executor of ba_kernels.h on a workgroup of 256 threads
-struct BaWorkgroup {
-    double* s_red;
-    int flip;
-    template <class Fn>
-    __device__ __forceinline__ void par(int n, Fn f) {
-        for (int i = threadIdx.x; i < n; i += PSL_BA_BS) f(i);
-        __syncthreads();
-    }
-    template <class Fn>
-    __device__ __forceinline__ void one(Fn f) {
-        if (threadIdx.x == 0) f();
-        __syncthreads();
-    }
-    template <class Fn>
-    __device__ __forceinline__ double sum256(Fn f) {
-        double v[1] = {f((int)threadIdx.x)};
-        psl_lm_reduce<1, 1>(v, s_red, flip);
-        return v[0];
-    }
-    template <class V>
-    __device__ __forceinline__ V get(const V* p) {
-        const V v = *(const volatile V*)p;
-        __syncthreads();
-        return v;
-    }
-};
-
 template <bool LIL>
 __global__ __launch_bounds__(PSL_BA_BS) void k_ba_local(BaArgs A) {
     __shared__ double s_red[2 * 4];
@@ -288,7 +261,7 @@ __global__ __launch_bounds__(PSL_BA_BS) void k_ba_local(BaArgs A) {
         }
         return;
     }
-    BaWorkgroup X = {s_red, 0};
+    PslLmWorkgroup X = {s_red, 0};
     if constexpr (LIL)
         psl_ba_rounds<true>(X, W, A.rounds, A.kf_out + A.kf_off[k], A.mp_out + A.mp_off[k], erase, A.info + k, A.lil_out + A.lil_off[k],
                             A.erase_lil + A.led_off[k], A.nerased_lil ? A.nerased_lil + k : nullptr);

@@ -1,9 +1,9 @@
 // libpslfe: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2536-2799) for K graphs in one launch.  Product code.
 // Who owns what.  essential_kernels.h holds everything that is arithmetic or a decision: the measurements, Sim3::log, the edge and
-// its numeric Jacobian, the blocks, the envelope LDLt, the Levenberg loop, the poses and the points, and the checks of the rows,
-// written once over an executor (its header); the host loop of tools/dropin/essential_main.cpp runs the same text on one core.
-// This file owns the handle, the executor of a workgroup and the entry points.  Conventions: include/pslfe.h above
-// pslfe_eg_optimize_device.
+// its numeric Jacobian, the blocks, the envelope LDLt, the `Problem` of the Levenberg driver psl_lm_levenberg (lm_kernels.h), the
+// poses and the points, and the checks of the rows, written once over an executor (the contract: lm_kernels.h); the host loop of
+// tools/dropin/essential_main.cpp runs the same text on one core.  This file owns the handle and the entry points; the executor of
+// a workgroup is PslLmWorkgroup of lm_device.h.  Conventions: include/pslfe.h above pslfe_eg_optimize_device.
 //
 // k_eg_optimize: one launch, one resident workgroup of 256 threads per graph through the lists, every iteration and every trial.
 // The executor spreads the indices of a step over the threads (thread = (keyframe, column, sign) for the perturbed estimates;
@@ -58,34 +58,6 @@ struct EgArgs {
     PslEgInfo* info;
 };
 
-// the executor of essential_kernels.h on a workgroup of 256 threads
-struct EgWorkgroup {
-    double* s_red;
-    int flip;
-    template <class Fn>
-    __device__ __forceinline__ void par(int n, Fn f) {
-        for (int i = threadIdx.x; i < n; i += PSL_EG_BS) f(i);
-        __syncthreads();
-    }
-    template <class Fn>
-    __device__ __forceinline__ void one(Fn f) {
-        if (threadIdx.x == 0) f();
-        __syncthreads();
-    }
-    template <class Fn>
-    __device__ __forceinline__ double sum256(Fn f) {
-        double v[1] = {f((int)threadIdx.x)};
-        psl_lm_reduce<1, 1>(v, s_red, flip);
-        return v[0];
-    }
-    template <class V>
-    __device__ __forceinline__ V get(const V* p) {
-        const V v = *(const volatile V*)p;
-        __syncthreads();
-        return v;
-    }
-};
-
 __global__ __launch_bounds__(PSL_EG_BS) void k_eg_optimize(EgArgs A) {
     __shared__ double s_red[2 * 4];
     const int k = blockIdx.x;
@@ -99,7 +71,7 @@ __global__ __launch_bounds__(PSL_EG_BS) void k_eg_optimize(EgArgs A) {
     W.nkf = have ? k1 - k0 : 0; W.ne = have ? e1 - e0 : 0; W.nmp = have ? p1 - p0 : 0;
     W.fix_scale = A.fix_scale;
     W.sctab = g_eg_sctab;
-    EgWorkgroup X = {s_red, 0};
+    PslLmWorkgroup X = {s_red, 0};
     psl_eg_run(X, W, have, code, A.cenv, A.pose_out + (have ? k0 : 0), A.S_out + 8 * (size_t)(have ? k0 : 0), A.mp_out + (have ? p0 : 0), A.info + k);
 }
 

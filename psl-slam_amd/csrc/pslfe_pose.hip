@@ -6,13 +6,14 @@
 //   the iteration loop of a round                                    Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419
 //   the LIL edges: set-up, error / Jacobian, classification            src/Optimizer.cc:619-694, add_inc/EdgeLIL.h:210-439, :973-1008
 // Who owns what.  pose_kernels.h holds the arithmetic of an edge, the update and the four rounds psl_po_rounds; lm_kernels.h holds
-// the solve, the Huber kernel and the Levenberg driver psl_lm_optimize (the iterations and trials of a round with every decision
-// between two sums), which OptimizeSim3 shares.  The host loop of tools/dropin/pose_main.cpp instantiates psl_po_rounds and with it
-// psl_lm_optimize<6>.  k_pose_optimize calls the same primitives but keeps the rounds and the loop of psl_lm_optimize written out in
-// its body: instantiating the driver here gave the same registers, LDS and scratch and the same per-edge and reduction code, but
-// launches 0.6 to 1.9 % slower than this form on an MI355X (profiles/pose_driver_ab.json).  A change to
-// psl_lm_optimize or psl_po_rounds is a change to the loop below and the reverse; tests/test_pose_*_gpu.py compare both with the
-// numpy restatement bit for bit.  The device's own: which thread owns which edge, the order of the sums (its steps 2 and 3 are
+// the solve, the Huber kernel and the Levenberg driver psl_lm_levenberg (the iterations and trials of a round with every decision
+// between two sums), which OptimizeSim3, the local bundle adjustment and the essential graph share.  The host loop of
+// tools/dropin/pose_main.cpp instantiates psl_po_rounds and with it psl_lm_optimize<6>, the driver on one vertex.  k_pose_optimize
+// calls the same primitives but keeps the rounds and the driver's loop written out in its body: instantiating the driver here gave
+// the same registers, LDS and scratch and the same per-edge and reduction code, but launches 0.6 to 1.9 % slower than this form on
+// an MI355X (profiles/pose_driver_ab.json).  So the loop has three texts that are changed together: the driver
+// psl_lm_levenberg, and the two loops written out here and in k_sim3_optimize; a change to psl_po_rounds is likewise a change to
+// the loop below and the reverse.  tests/test_pose_*_gpu.py compare both with the numpy restatement bit for bit.  The device's own: which thread owns which edge, the order of the sums (its steps 2 and 3 are
 // psl_lm_reduce of lm_device.h, shared with pslfe_sim3.hip), the LDS copy of the rows, the early return, the edge set-up kernels.
 // Scope: the monocular and stereo point edges (k_pose_optimize<false>, what pslfe_pose_optimize[_device] launch) and, in
 // k_pose_optimize<true> (pslfe_pose_optimize_lil[_device]), the LIL edges (EdgeLILSE3ProjectXYZ with its fixed VertexLIL) as well.

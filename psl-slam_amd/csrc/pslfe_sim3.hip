@@ -2,15 +2,17 @@
 // launch, and its set-up loop (:2854-2933).  Product code.
 // Reference behaviour restated (in double, in the reference's order of decisions): sim3_kernels.h names every source line.
 // Who owns what.  sim3_kernels.h holds the arithmetic of a pair, the numeric Jacobian, the Sim3 update and the two calls
-// psl_s3_rounds; lm_kernels.h holds the 7x7 solve, the Huber kernel and the Levenberg driver psl_lm_optimize, which the pose
-// optimisation shares.  The host loop of tools/dropin/sim3_main.cpp instantiates psl_s3_rounds and with it psl_lm_optimize<7>.
-// k_sim3_optimize calls the same primitives but keeps the two calls and the loop of psl_lm_optimize written out (sim3_rounds,
+// psl_s3_rounds; lm_kernels.h holds the 7x7 solve, the Huber kernel and the Levenberg driver psl_lm_levenberg, which the pose
+// optimisation, the local bundle adjustment and the essential graph share.  The host loop of tools/dropin/sim3_main.cpp
+// instantiates psl_s3_rounds and with it psl_lm_optimize<7>, the driver on one vertex.
+// k_sim3_optimize calls the same primitives but keeps the two calls and the driver's loop written out (sim3_rounds,
 // sim3_optimize and sim3_step below), as k_pose_optimize does: with Sim3DeviceSums as the problem of psl_lm_optimize<7> it had the
 // same VGPRs, scratch, spills, LDS and occupancy and the same count of every f64 opcode, but 254 AGPRs for 237, and launched 0.7 to
 // 1.8 % slower than this form on an MI355X, outside the parent's own spread in five of six rows (profiles/lm_core_ab.json,
-// DESIGN.md §5.0l).  This form compiles to the instructions the kernel had on its own driver.  A change to psl_lm_optimize,
-// PslS3Vertex or psl_s3_rounds is a change to those three functions and the reverse; tests/test_sim3_opt_gpu.py compares both with
-// the numpy restatement bit for bit.  The device's own, here: which thread owns which pair, the order of the sums (its
+// DESIGN.md §5.0l).  This form compiles to the instructions the kernel had on its own driver.  So the loop has three texts that
+// are changed together: the driver psl_lm_levenberg, and the two loops written out in k_pose_optimize and here; a change to
+// PslS3Vertex or psl_s3_rounds is likewise a change to those three functions and the reverse.  tests/test_sim3_opt_gpu.py compares
+// both with the numpy restatement bit for bit.  The device's own, here: which thread owns which pair, the order of the sums (its
 // steps 2 and 3 are psl_lm_reduce of lm_device.h, shared with pslfe_pose.hip), the LDS copy of the rows, the perturbed estimates
 // shared through LDS, the error paths, the pair set-up kernel.
 //

@@ -1,7 +1,7 @@
 // The sibling of ba_main.cpp for Optimizer::LocalBundleAdjustmentAndInseclines (the call LocalMapping::Run makes,
 // src/LocalMapping.cc:84): a C++ consumer of pslfe::Optimizer::LocalBundleAdjustmentAndInseclines[Device] of
 // psl-slam_amd/host/pslfe.hpp, and the plain one-core host loop of the same restatement.  Who owns what: all arithmetic and every
-// decision are psl-slam_amd/csrc/ba_kernels.h, written over an executor; the loop here is psl_ba_rounds<true> on PslBaSerial, the
+// decision are psl-slam_amd/csrc/ba_kernels.h, written over an executor; the loop here is psl_ba_rounds<true> on PslLmSerial, the
 // kernel k_ba_local<true> the same text on a workgroup.  tests/test_local_ba_lil_gpu.py builds this program with g++ and compares all
 // three forms with the restatement of tests/ba_lil_cases.py; built with -DPSL_BA_HOST_ONLY it needs neither the library nor a GPU
 // (tests/test_local_ba_lil_cpu.py runs that build under the address and undefined-behaviour sanitizers; tools/bench_local_ba.py
@@ -79,7 +79,7 @@ Result hostLoop(const Case& c, const PslCamera& cam, int rounds, const Caps& cap
     W.sctab = kSinCosTab;
     if (psl_ba_lists_host(W) != PSLFE_OK || psl_ba_lil_lists_host(W) != PSLFE_OK) return unchanged(c, PSLFE_E_INVALID);
     Result R = unchanged(c, PSLFE_OK);
-    PslBaSerial X = {W.scal + 8};
+    PslLmSerial X = {W.scal + 8};
     psl_ba_rounds<true>(X, W, rounds, R.kf.data(), R.mp.data(), R.erase.data(), &R.info, R.lil.data(), R.eraseLil.data(), &R.nerasedLil);
     return R;
 }

@@ -1,7 +1,7 @@
 // A C++ consumer of the local-bundle-adjustment seam of psl-slam_amd/host/pslfe.hpp (pslfe::Optimizer::LocalBundleAdjustment, the
 // call of LocalMapping::Run src/LocalMapping.cc:84), and the plain one-core host loop of the same restatement.  Who owns what: all
 // arithmetic and every decision are psl-slam_amd/csrc/ba_kernels.h, written over an executor; the loop here is that text on
-// PslBaSerial, the kernel k_ba_local the same text on a workgroup.  tests/test_local_ba_gpu.py builds this program with g++ and
+// PslLmSerial, the kernel k_ba_local the same text on a workgroup.  tests/test_local_ba_gpu.py builds this program with g++ and
 // compares all three forms with the numpy restatement of tests/ba_cases.py; built with -DPSL_BA_HOST_ONLY it needs neither the
 // library nor a GPU (tests/test_local_ba_cpu.py runs that build under the address and undefined-behaviour sanitizers;
 // tools/bench_local_ba.py times it).
@@ -69,7 +69,7 @@ Result hostLoop(const Case& c, const PslCamera& cam, int rounds, int ckf, int cm
     W.sctab = kSinCosTab;
     if (psl_ba_lists_host(W) != PSLFE_OK) return unchanged(c, PSLFE_E_INVALID);
     Result R = unchanged(c, PSLFE_OK);
-    PslBaSerial X = {W.scal + 8};
+    PslLmSerial X = {W.scal + 8};
     psl_ba_rounds(X, W, rounds, R.kf.data(), R.mp.data(), R.erase.data(), &R.info);
     return R;
 }

@@ -1,6 +1,6 @@
 // A C++ consumer of the essential-graph seam of psl-slam_amd/host/pslfe.hpp (pslfe::Optimizer::OptimizeEssentialGraph, the call of
 // LoopClosing::CorrectLoop), and the plain one-core host loop of the same restatement.  Who owns what: all arithmetic and every
-// decision are psl-slam_amd/csrc/essential_kernels.h, written over an executor; the loop here is that text on PslEgSerial, the kernel
+// decision are psl-slam_amd/csrc/essential_kernels.h, written over an executor; the loop here is that text on PslLmSerial, the kernel
 // k_eg_optimize the same text on a workgroup.  tests/test_essential_graph_gpu.py builds this program with g++ and compares all
 // three forms with the Python restatement of tests/essential_cases.py; built with -DPSL_EG_HOST_ONLY it needs neither the library nor
 // a GPU (tests/test_essential_graph_cpu.py runs that build under the address and undefined-behaviour sanitizers;
@@ -76,7 +76,7 @@ Result hostLoop(const Case& c, int fix_scale, int ckf, int ced, int cmp, size_t 
     W.nkf = nkf; W.ne = ne; W.nmp = nmp;
     W.fix_scale = fix_scale;
     W.sctab = kSinCosTab;
-    PslEgSerial X = {W.scal + 8};
+    PslLmSerial X = {W.scal + 8};
     psl_eg_run(X, W, 1, code, cenv, R.pose.data(), R.S.data(), R.mp.data(), &R.info);
     return R;
 }
