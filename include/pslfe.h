@@ -726,7 +726,13 @@ int pslfe_compute_bow(pslfe_vocab* v, const uint8_t* desc, int n, int levelsup, 
                       int32_t* f_nid, int32_t* bow_id, double* bow_val, int* nbow, int32_t* fv_node, int32_t* fv_start,
                       int32_t* fv_idx, int* nfv);
 /* Same for nframes frames in HBM: descriptors [nframes][stride][32], counts [nframes]; outputs [nframes][stride]
- * (bow_start / fv_start: [nframes][stride + 1]; bow_start is scratch), counts [nframes].  Asynchronous. */
+ * (bow_start / fv_start: [nframes][stride + 1]; bow_start is scratch), counts [nframes].  Asynchronous.
+ * nframes >= 1, 1 <= stride <= 4096, levelsup >= 0 and no NULL pointer, else PSLFE_E_INVALID.  The counts are read on the device
+ * only, so a count outside 0 .. stride cannot be refused here: frame f uses min(max(d_counts[f], 0), stride) features - a count
+ * above the stride is the stride, a negative count is an empty frame (nbow = nfv = 0, fv_start[0] = 0).  A frame writes
+ * n per-feature rows, nbow (bow_id, bow_val) pairs, nfv nodes, nfv + 1 starts and fv_start[nfv] indices of its own rows and
+ * nothing else: not its rows past those extents (bow_start excepted) and no row of another frame.  A feature whose leaf lies
+ * above level L - levelsup has node 0 (the reference leaves its node id unset); levelsup >= L gives node 0 for all, as there. */
 int pslfe_compute_bow_device(pslfe_vocab* v, const uint8_t* d_desc, const int32_t* d_counts, int nframes, int stride,
                              int levelsup, int32_t* d_fword, double* d_fweight, int32_t* d_fnid, int32_t* d_bow_id,
                              double* d_bow_val, int32_t* d_bow_start, int32_t* d_nbow, int32_t* d_fv_node,

@@ -121,6 +121,32 @@ def ref():
     print("ref", len(cases), int(out["walk_counts"].sum()), len(xs), len(nk))
 
 
+def bow_edge_pins():
+    """bow_edge_pins.npz: the reference's BowVector / FeatureVector accumulation (oracle/_ref/libref_dbow2.so) on the (word, weight,
+    node) streams of the bow_cases cases below: one word 4096 times, two words 2048 times each, segments across ranks 255 | 256 and
+    511 | 512, every feature stopped.  Outputs and input CRCs only; tests/test_oracle_ref_cpu.py holds the oracle to them."""
+    import ctypes as C
+    import bow_cases as bc
+    import ref_cases as T
+    db = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_dbow2.so"))
+    db.ref_bow_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
+    out = {}
+    for name in T.BOW_EDGE_CASES:
+        o = bc.oracle(name)
+        n = len(o["word"])
+        bow_id, bow_val = np.zeros(n, np.int32), np.zeros(n, np.float64)
+        fv_node, fv_start, fv_idx = np.zeros(n, np.int32), np.zeros(n + 1, np.int32), np.zeros(n, np.int32)
+        nf = C.c_int()
+        w, wt, nid = (np.ascontiguousarray(o[key]) for key in ("word", "weight", "nid"))
+        nb = db.ref_bow_accumulate(w.ctypes.data, wt.ctypes.data, nid.ctypes.data, n, bow_id.ctypes.data, bow_val.ctypes.data, fv_node.ctypes.data,
+                                   fv_start.ctypes.data, fv_idx.ctypes.data, C.byref(nf))
+        nf = nf.value
+        out.update({f"{name}_in_crc": T.crc(w, wt, nid), f"{name}_id": bow_id[:nb], f"{name}_val": bow_val[:nb], f"{name}_fv_node": fv_node[:nf],
+                    f"{name}_fv_start": fv_start[:nf + 1], f"{name}_fv_idx": fv_idx[:fv_start[nf]]})
+        print("bow_edge", name, n, nb, nf)
+    np.savez_compressed(os.path.join(HERE, "bow_edge_pins.npz"), **out)
+
+
 def pose_pins():
     """pose_restatement_pins.npz: what pose_opt_cases.optimize and pose_lil_cases.optimize return on every case of their CASE_NAMES in
     both orders (tests/test_pose_lil_cpu.py compares the restatement with it bit for bit).  Written from the two separate drivers the
@@ -175,6 +201,8 @@ if __name__ == "__main__":
         sim3_pins()
     if "ref" in which:
         ref()
+    if "bow_edge_pins" in which:
+        bow_edge_pins()
     if "lines" in which:
         lines()
     if "main" in which:

@@ -11,6 +11,8 @@ LOGNTS = [5 * (np.log10(512.0) + np.log10(384.0)) / 2 + np.log10(11.0), 5 * (np.
 NFA_EXACT = [(0, 0, 0.125), (50, 0, 0.125), (64, 64, 0.0625), (3000, 2900, 0.125), (4000, 5, 0.125)]
 # (k, L, ragged, descriptors, levelsup) of the DBoW2 cases; the vocabulary of case i is bow_vocab.make_vocab(k, L, i, ragged, 0.1)
 BOW_CASES = [(10, 3, False, 1000, 2), (6, 4, True, 700, 2), (10, 3, False, 0, 4), (3, 5, True, 1500, 4), (10, 2, False, 2000, 1), (4, 3, False, 5, 3)]
+# the bow_cases cases whose (word, weight, node) streams tests/golden/bow_edge_pins.npz holds the reference's accumulation of
+BOW_EDGE_CASES = ("one_word", "two_words", "straddle", "all_stopped_300")
 
 
 def walk_cases():

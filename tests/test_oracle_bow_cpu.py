@@ -3,39 +3,7 @@ import numpy as np
 
 import bow_vocab
 import oracle_lib
-
-
-def _ham(a, b):
-    return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
-
-
-def _py_transform(vocab, desc, levelsup):
-    children, nd, nw, nwd, L = vocab
-    bow, fv = {}, {}
-    per = []
-    for i, f in enumerate(desc):
-        node, lvl, nid = 0, 0, 0
-        while children[node]:
-            lvl += 1
-            best, bd = children[node][0], _ham(f, nd[children[node][0]])
-            for c in children[node][1:]:
-                d = _ham(f, nd[c])
-                if d < bd:
-                    best, bd = c, d
-            node = best
-            if lvl == L - levelsup:
-                nid = node
-        per.append((int(nwd[node]), float(nw[node]), nid))
-        if nw[node] > 0:
-            bow[int(nwd[node])] = bow.get(int(nwd[node]), 0.0) + float(nw[node]) if int(nwd[node]) in bow else float(nw[node])
-            fv.setdefault(nid, []).append(i)
-    norm = 0.0
-    for k in sorted(bow):
-        norm += abs(bow[k])
-    if norm > 0:
-        for k in bow:
-            bow[k] /= norm
-    return per, bow, fv
+from bow_cases import py_transform as _py_transform
 
 
 def test_compute_bow_against_plain_python():

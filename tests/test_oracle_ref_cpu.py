@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
-from ref_cases import LOGNTS, NFA_EXACT, bow_inputs, crc, log_gamma_args, nfa_args, nfa_cases, walk_cases
+from ref_cases import BOW_EDGE_CASES, LOGNTS, NFA_EXACT, bow_inputs, crc, log_gamma_args, nfa_args, nfa_cases, walk_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "ref_pins.npz")
@@ -83,3 +83,19 @@ def test_oracle_bow_accumulation_equals_the_reference_dbow2():
         assert np.array_equal(g[f"bow{case}_fv_idx"], o["fv_idx"])
         checked += len(o["bow_id"])
     assert checked > 400
+
+
+def test_oracle_bow_edge_cases_equal_the_reference_dbow2():
+    """The same on the streams of four cases of tests/bow_cases.py (tests/golden/bow_edge_pins.npz, make_golden.py bow_edge_pins): one
+    word added 4096 times - the reference's value before normalisation is the sequential sum, after it 1.0 -, two words 2048 times
+    each, segments that straddle ranks 255 | 256 and 511 | 512, and a frame of stopped words only (empty vectors, norm 0)."""
+    import bow_cases as bc
+    g = np.load(os.path.join(ROOT, "tests", "golden", "bow_edge_pins.npz"))
+    for name in BOW_EDGE_CASES:
+        o = bc.oracle(name)
+        assert crc(*(o[key] for key in ("word", "weight", "nid"))) == g[f"{name}_in_crc"], f"{name}: the case or the oracle's descent changed"
+        assert np.array_equal(g[f"{name}_id"], o["bow_id"]) and g[f"{name}_val"].tobytes() == o["bow_val"].tobytes(), name
+        assert np.array_equal(g[f"{name}_fv_node"], o["fv_node"]) and np.array_equal(g[f"{name}_fv_start"], o["fv_start"]), name
+        assert np.array_equal(g[f"{name}_fv_idx"], o["fv_idx"]), name
+    assert g["one_word_val"].tolist() == [1.0] and len(g["two_words_id"]) == 2 and len(g["straddle_id"]) == 592
+    assert len(g["all_stopped_300_id"]) == 0 and g["all_stopped_300_fv_start"].tolist() == [0]
