@@ -1619,6 +1619,59 @@ int pslfe_ba_local_lil(pslfe_ba* ba, const PslBaKeyFrame* kf, int nkf, const Psl
                        const PslMapLil* lil, int nlil, const PslBaLilEdge* lil_edges, int nlil_edges, const PslCamera* cam, int rounds,
                        PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* erase, PslMapLil* lil_out, uint8_t* erase_lil, PslBaInfo* info);
 
+/* ---- Global bundle adjustment: Optimizer::BundleAdjustment / GlobalBundleAdjustemnt ------------------------------------------------
+ * src/Optimizer.cc:37-237: the call of Tracking::CreateInitialMapMonocular (src/Tracking.cc:782, 20 iterations, robust) and of
+ * LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:650, 10 iterations, bRobust = false), from the optimiser's set-up on: one
+ * optimize(nIterations) over g2o's Levenberg with BlockSolver_6_3, no levels, no erase pass.  ONE problem spread over the whole
+ * device (the local BA gives a workgroup to each of K problems).  The arithmetic, the order of every sum and the readings of
+ * DESIGN.md §3 are those of the local BA above; parity is "HIP == host compile of the same headers == restatement", bit for bit.
+ * Rows: PslBaKeyFrame (fixed = mnId == 0, :79), PslMapPointGeom and PslBaEdge in the order the reference creates the edges
+ * (:89-173: per map point, its observations in GetObservations() order).  Bad keyframes, bad points and observations in bad
+ * keyframes are the caller's filter (:74, :92, :109), as is the choice between SetPose / SetWorldPos and mTcwGBA / mPosGBA (nLoopKF,
+ * :200-210, :224-234).  The abort flag (pbStopFlag) is not modelled. */
+typedef struct PslGbaInfo {
+    int32_t status;              /* PSLFE_OK, PSLFE_E_CAPACITY or PSLFE_E_INVALID */
+    int32_t iterations;          /* iterations run */
+    int32_t free_keyframes;      /* F: pose blocks of the system (not fixed, with an edge) */
+    int32_t included_points;     /* points with at least one edge */
+    double chi2_start, chi2_end, lambda;   /* the active (robust) chi2 of iteration 0 and at the end; the lambda then */
+} PslGbaInfo;
+#ifdef __cplusplus
+static_assert(sizeof(PslGbaInfo) == 40, "global BA POD");
+#else
+_Static_assert(sizeof(PslGbaInfo) == 40, "global BA POD");
+#endif
+typedef struct pslfe_gba pslfe_gba;
+/* The HBM workspace of one problem of up to max_keyframes keyframes (at most 4096: S has 36 max_keyframes^2 doubles, counted in
+ * size_t), max_points points and max_edges edges (at most 2^26 each: every index of a step is an int).  A count below 1, above
+ * these bounds or a NULL argument: PSLFE_E_INVALID. */
+int pslfe_gba_create(pslfe_ctx* ctx, int max_keyframes, int max_points, int max_edges, pslfe_gba** out);
+void pslfe_gba_destroy(pslfe_gba* gba);
+/* == Optimizer::BundleAdjustment (src/Optimizer.cc:49-237) on rows in HBM.  cam: fx, fy, cx, cy, bf (host).  iterations >= 1 (the
+ *    reference passes 5, 10 or 20).  robust: 1 sets Huber on every edge with THIS function's deltas, (float)sqrt(5.99) =
+ *    2.4474475383758545 for a monocular edge (:85; not the local BA's (float)sqrt(5.991)) and (float)sqrt(7.815) for a stereo
+ *    edge (:86); 0 runs without a kernel.
+ *    Outputs, indexed as the inputs: d_kf_out: EVERY keyframe gets toCvMat of its SE3Quat, the fixed ones and those without an edge
+ *    too (the reference calls SetPose or fills mTcwGBA for every keyframe, :193-210), so a fixed keyframe comes back through the
+ *    quaternion; this differs from pslfe_ba_local, which leaves fixed rows alone.  d_not_included[p] = vbNotIncludedMP (:175-183): 1
+ *    when point p has no edge.  d_mp_out: an included point gets (float) of its estimate in x, y, z; the other points and fields
+ *    keep their values; it is what pslfe_kf_update_normal_and_depth_device (:227) and ComputeSceneMedianDepth take.  d_kf_out may
+ *    be d_kf and d_mp_out may be d_mp.
+ *    info is a HOST pointer.  The call drives the Levenberg loop from the host (a decision is a small read-back, a step a launch
+ *    over the whole device on the context's stream) and returns when the outputs are written.
+ *    Never a silent truncation: a count above the handle's caps: PSLFE_E_CAPACITY; an edge that names a row outside the problem
+ *    or a duplicate (point, keyframe) pair: PSLFE_E_INVALID; both are the return value and info->status, the outputs then equal
+ *    the inputs and d_not_included is 0.  No edge, or no free keyframe with an edge: PSLFE_OK with 0 iterations; the keyframes
+ *    are still round-tripped.  Negative counts, NULL with a non-zero count (gba, cam and info always), iterations < 1, robust
+ *    outside 0..1: PSLFE_E_INVALID before any device is touched. */
+int pslfe_gba_optimize_device(pslfe_gba* gba, const PslBaKeyFrame* d_kf, int nkf, const PslMapPointGeom* d_mp, int nmp, const PslBaEdge* d_edges,
+                              int nedges, const PslCamera* cam, int iterations, int robust, PslBaKeyFrame* d_kf_out, PslMapPointGeom* d_mp_out,
+                              uint8_t* d_not_included, PslGbaInfo* info);
+/* The same on host arrays, as pslfe_ba_local. */
+int pslfe_gba_optimize(pslfe_gba* gba, const PslBaKeyFrame* kf, int nkf, const PslMapPointGeom* mp, int nmp, const PslBaEdge* edges, int nedges,
+                       const PslCamera* cam, int iterations, int robust, PslBaKeyFrame* kf_out, PslMapPointGeom* mp_out, uint8_t* not_included,
+                       PslGbaInfo* info);
+
 /* ---- The essential graph: Optimizer::OptimizeEssentialGraph -----------------------------------------------------------------------
  * The call of LoopClosing::CorrectLoop (src/LoopClosing.cc, src/Optimizer.cc:2536-2799) from the vertices on: the measurements of
  * the EdgeSim3 edges (:2607-2738), optimize(20) over g2o's Levenberg with setUserLambdaInit(1e-16) (:2549, :2741-2742), the pose

@@ -73,6 +73,10 @@ BAINFO_DTYPE = np.dtype({"names": ["status", "rounds", "iterations", "nerased", 
 BALILEDGE_DTYPE = np.dtype([("lil", "<i4"), ("kf", "<i4"), ("obs1", "<f8", (3,)), ("obs2", "<f8", (3,)), ("obs_ins", "<f8", (2,))])
 assert BALILEDGE_DTYPE.itemsize == 72
 assert BAEDGE_DTYPE.itemsize == 24 and BAKEYFRAME_DTYPE.itemsize == 52 and BAINFO_DTYPE.itemsize == 48
+# global bundle adjustment (include/pslfe.h: PslGbaInfo)
+GBAINFO_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("free_keyframes", "<i4"), ("included_points", "<i4"), ("chi2_start", "<f8"),
+                          ("chi2_end", "<f8"), ("lambda", "<f8")])
+assert GBAINFO_DTYPE.itemsize == 40
 # essential graph (include/pslfe.h: PslEgKeyFrame, PslEgEdge, PslEgInfo)
 EGKEYFRAME_DTYPE = np.dtype([("Scw", "<f8", (8,)), ("Snc", "<f8", (8,)), ("has_nc", "<i4"), ("fixed", "<i4")])
 EGEDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("loop", "<i4")])
@@ -708,6 +712,29 @@ class BundleAdjuster:
             pass
 
 
+class GlobalBundleAdjuster:
+    """The HBM workspace of the global bundle adjustment (pslfe_gba): one problem of up to max_keyframes keyframes (at most 4096),
+    max_points points and max_edges edges, spread over the whole device."""
+
+    def __init__(self, max_keyframes, max_points, max_edges, ctx=None):
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        _check(lib().pslfe_gba_create(self.ctx._h, C.c_int(max_keyframes), C.c_int(max_points), C.c_int(max_edges), C.byref(self._h)),
+               "pslfe_gba_create")
+
+    def close(self):
+        if self._h:
+            lib().pslfe_gba_destroy.restype = None
+            lib().pslfe_gba_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class EssentialGraph:
     """The HBM workspaces of the essential-graph optimisation (pslfe_eg): up to max_graphs graphs per launch of up to max_keyframes
     keyframes, max_edges edges, max_points map points and max_envelope doubles of envelope each (include/pslfe.h, pslfe_eg_create)."""
@@ -806,6 +833,51 @@ class Optimizer:
             C.c_void_p(d_mp or None), C.c_void_p(d_mp_ref or None), C.c_void_p(d_mp_off or None), C.c_int(1 if fix_scale else 0),
             C.c_void_p(d_pose_out or None), C.c_void_p(d_S_out or None), C.c_void_p(d_mp_out or None), C.c_void_p(d_info or None)),
             "pslfe_eg_optimize_device")
+
+    @staticmethod
+    def BundleAdjustment(gba, kfs, mps, edges, cam, iterations=5, robust=True):
+        """Optimizer::BundleAdjustment src/Optimizer.cc:49-237, host arrays: kfs BAKEYFRAME_DTYPE[nkf] (the keyframes that are not bad;
+        fixed = mnId == 0), mps MAPPOINT_DTYPE[nmp], edges BAEDGE_DTYPE[ne] in the order the reference creates them; robust sets Huber
+        with (float)sqrt(5.99) / (float)sqrt(7.815).  -> (kfs_out: EVERY keyframe as toCvMat of its SE3Quat, the fixed one too;
+        mps_out: a point with an edge as (float) of its estimate; not_included u8 [nmp] = vbNotIncludedMP; info GBAINFO_DTYPE record).
+        Whether the rows go to SetPose / SetWorldPos or to mTcwGBA / mPosGBA is the caller's matter.  A refused problem (capacity,
+        an edge outside it, a duplicate pair) raises PslfeError."""
+        k = np.ascontiguousarray(kfs, BAKEYFRAME_DTYPE).reshape(-1)
+        m = np.ascontiguousarray(mps, MAPPOINT_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(edges, BAEDGE_DTYPE).reshape(-1)
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        ko, mo, ni = np.zeros(max(len(k), 1), BAKEYFRAME_DTYPE), np.zeros(max(len(m), 1), MAPPOINT_DTYPE), np.zeros(max(len(m), 1), np.uint8)
+        info = np.zeros(1, GBAINFO_DTYPE)
+        p = lambda a, n: _ptr(a) if n else None
+        _check(lib().pslfe_gba_optimize(gba._h, p(k, len(k)), C.c_int(len(k)), p(m, len(m)), C.c_int(len(m)), p(e, len(e)), C.c_int(len(e)), _ptr(cam),
+                                        C.c_int(iterations), C.c_int(1 if robust else 0), p(ko, len(k)), p(mo, len(m)), p(ni, len(m)), _ptr(info)),
+               "pslfe_gba_optimize")
+        return ko[:len(k)], mo[:len(m)], ni[:len(m)], info[0]
+
+    @staticmethod
+    def BundleAdjustmentDevice(gba, d_kf, nkf, d_mp, nmp, d_edges, nedges, cam, iterations, robust, d_kf_out, d_mp_out, d_not_included):
+        """The same on rows in HBM (device addresses as ints); d_kf_out may be d_kf and d_mp_out may be d_mp, which is what
+        update_normal_and_depth_device takes next.  Returns the GBAINFO_DTYPE record when the outputs are written; a refused problem
+        does not raise: its status is in the record, its outputs equal its inputs and d_not_included is 0."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+        info = np.zeros(1, GBAINFO_DTYPE)
+        rc = lib().pslfe_gba_optimize_device(
+            gba._h, C.c_void_p(d_kf or None), C.c_int(nkf), C.c_void_p(d_mp or None), C.c_int(nmp), C.c_void_p(d_edges or None), C.c_int(nedges),
+            _ptr(cam), C.c_int(iterations), C.c_int(1 if robust else 0), C.c_void_p(d_kf_out or None), C.c_void_p(d_mp_out or None),
+            C.c_void_p(d_not_included or None), _ptr(info))
+        if rc != 0 and rc != int(info[0]["status"]):
+            _check(rc, "pslfe_gba_optimize_device")
+        return info[0]
+
+    @staticmethod
+    def GlobalBundleAdjustemnt(gba, kfs, mps, edges, cam, iterations=5, robust=True):
+        """Optimizer::GlobalBundleAdjustemnt src/Optimizer.cc:37-46 (the reference's spelling): BundleAdjustment over GetAllKeyFrames()
+        and GetAllMapPoints()."""
+        return Optimizer.BundleAdjustment(gba, kfs, mps, edges, cam, iterations, robust)
+
+    @staticmethod
+    def GlobalBundleAdjustemntDevice(gba, d_kf, nkf, d_mp, nmp, d_edges, nedges, cam, iterations, robust, d_kf_out, d_mp_out, d_not_included):
+        return Optimizer.BundleAdjustmentDevice(gba, d_kf, nkf, d_mp, nmp, d_edges, nedges, cam, iterations, robust, d_kf_out, d_mp_out, d_not_included)
 
     @staticmethod
     def LocalBundleAdjustment(ba, kfs, mps, edges, cam, rounds=2):

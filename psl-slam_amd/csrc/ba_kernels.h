@@ -63,6 +63,7 @@
 #define PSL_BA_CHI2_LIL 11.07  // src/Optimizer.cc:2406, :2469
 #define PSL_BA_CHI2_MONO 5.991
 #define PSL_BA_CHI2_STEREO 7.815
+#define PSL_GBA_DELTA_MONO 2.4474475383758545   /* thHuber2D = (float)sqrt(5.99) of Optimizer::BundleAdjustment (src/Optimizer.cc:85); its stereo delta is PSL_POSE_DELTA_STEREO */
 
 // The workspace of one problem: views into one block of HBM (host: of one allocation), carved by psl_ba_carve.
 struct PslBaWs {
@@ -241,6 +242,8 @@ PSL_BA_HD void psl_ba_jacobians(int mono, const double* Pc, const double* R, con
 
 // computeActiveErrors of edge e at the estimates (Ts, Xs): its _error and the robust chi2; with `linearize` also linearizeOplus and
 // the off-diagonal block Hpl of constructQuadraticForm, B[r][m] = (w Jp[0][r]) Jl[0][m] + (w Jp[1][r]) Jl[1][m] (+ row 2).
+// GBA = true (gba_kernels.h): the Huber deltas of Optimizer::BundleAdjustment, whose monocular one is PSL_GBA_DELTA_MONO.
+template <bool GBA = false>
 PSL_BA_HD void psl_ba_edge(const PslBaWs& W, int e, const PslSE3* Ts, const double* Xs, int robust, int linearize) {
     if (W.level[e]) return;
     const PslBaEdge ed = W.ed[e];
@@ -252,7 +255,7 @@ PSL_BA_HD void psl_ba_edge(const PslBaWs& W, int e, const PslSE3* Ts, const doub
     const double is2 = (double)ed.inv_sigma2;
     const double c = psl_po_chi2(er, is2, mono);
     double rho0 = c, rho1 = 1.0;
-    if (robust) psl_lm_huber(c, PSL_POSE_DELTA(mono), &rho0, &rho1);
+    if (robust) psl_lm_huber(c, GBA && mono ? PSL_GBA_DELTA_MONO : PSL_POSE_DELTA(mono), &rho0, &rho1);
     W.err[3 * (size_t)e] = er[0]; W.err[3 * (size_t)e + 1] = er[1]; W.err[3 * (size_t)e + 2] = er[2];
     W.rho0[e] = rho0;
     if (!linearize) return;

@@ -1177,6 +1177,21 @@ private:
     pslfe_ba* h_ = nullptr;
 };
 
+// The workspace of the global bundle adjustment (pslfe_gba): one problem of up to maxKeyframes keyframes (at most 4096), maxPoints
+// points and maxEdges edges, spread over the whole device.  A single owner frees every buffer.
+class GlobalBundleAdjuster {
+public:
+    GlobalBundleAdjuster(Context& ctx, int maxKeyframes, int maxPoints, int maxEdges) {
+        check(pslfe_gba_create(ctx.get(), maxKeyframes, maxPoints, maxEdges, &h_), "pslfe_gba_create");
+    }
+    ~GlobalBundleAdjuster() { pslfe_gba_destroy(h_); }
+    GlobalBundleAdjuster(const GlobalBundleAdjuster&) = delete;
+    GlobalBundleAdjuster& operator=(const GlobalBundleAdjuster&) = delete;
+    pslfe_gba* get() const { return h_; }
+private:
+    pslfe_gba* h_ = nullptr;
+};
+
 // The workspaces of the essential-graph optimisation (pslfe_eg): up to maxGraphs graphs per launch of up to maxKeyframes keyframes,
 // maxEdges edges, maxPoints map points and maxEnvelope doubles of envelope each.  A single owner frees every buffer.
 class EssentialGraph {
@@ -1363,6 +1378,42 @@ public:
                                                          uint8_t* d_eraseLil, int32_t* d_nerasedLil, PslBaInfo* d_info) {
         check(pslfe_ba_local_lil_device(ba.get(), K, d_kf, d_kfOff, d_mp, d_mpOff, d_edges, d_edgeOff, d_lil, d_lilOff, d_lilEdges, d_lilEdgeOff, &cam,
                                         rounds, d_kfOut, d_mpOut, d_erase, d_lilOut, d_eraseLil, d_nerasedLil, d_info), "pslfe_ba_local_lil_device");
+    }
+    // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) src/Optimizer.cc:49-237 from the
+    // optimiser's set-up on: kfs = the keyframes that are not bad (fixed = mnId == 0, :79), mps = the points that are not bad, edges
+    // in the order the reference creates them (:89-173).  EVERY keyframe comes back as toCvMat of its SE3Quat (the fixed one too,
+    // :193-210), a point with an edge as (float) of its estimate; notIncluded[p] = vbNotIncludedMP (:175-183).  Whether the rows
+    // go to SetPose / SetWorldPos or to mTcwGBA / mPosGBA (nLoopKF) is the caller's matter.  robust = true sets Huber with
+    // (float)sqrt(5.99) / (float)sqrt(7.815) (:85-86).  A refused problem throws.  Parity with g2o itself is unpinned.
+    static PslGbaInfo BundleAdjustment(GlobalBundleAdjuster& gba, std::vector<PslBaKeyFrame>& kfs, std::vector<PslMapPointGeom>& mps,
+                                       const std::vector<PslBaEdge>& edges, const PslCamera& cam, std::vector<uint8_t>& notIncluded,
+                                       int nIterations = 5, bool robust = true) {
+        notIncluded.assign(mps.size(), 0);
+        PslGbaInfo info = {};
+        check(pslfe_gba_optimize(gba.get(), kfs.data(), (int)kfs.size(), mps.data(), (int)mps.size(), edges.data(), (int)edges.size(), &cam, nIterations,
+                                 robust ? 1 : 0, kfs.data(), mps.data(), notIncluded.data(), &info), "pslfe_gba_optimize");
+        return info;
+    }
+    // the same on rows in HBM (pslfe_gba_optimize_device): returns when the outputs are written; d_kfOut may be d_kf, d_mpOut d_mp
+    static PslGbaInfo BundleAdjustmentDevice(GlobalBundleAdjuster& gba, const PslBaKeyFrame* d_kf, int nkf, const PslMapPointGeom* d_mp, int nmp,
+                                             const PslBaEdge* d_edges, int nedges, const PslCamera& cam, int nIterations, bool robust,
+                                             PslBaKeyFrame* d_kfOut, PslMapPointGeom* d_mpOut, uint8_t* d_notIncluded) {
+        PslGbaInfo info = {};
+        check(pslfe_gba_optimize_device(gba.get(), d_kf, nkf, d_mp, nmp, d_edges, nedges, &cam, nIterations, robust ? 1 : 0, d_kfOut, d_mpOut,
+                                        d_notIncluded, &info), "pslfe_gba_optimize_device");
+        return info;
+    }
+    // void Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust) src/Optimizer.cc:37-46 (the reference's
+    // spelling): BundleAdjustment over GetAllKeyFrames() and GetAllMapPoints()
+    static PslGbaInfo GlobalBundleAdjustemnt(GlobalBundleAdjuster& gba, std::vector<PslBaKeyFrame>& kfs, std::vector<PslMapPointGeom>& mps,
+                                             const std::vector<PslBaEdge>& edges, const PslCamera& cam, std::vector<uint8_t>& notIncluded,
+                                             int nIterations = 5, bool robust = true) {
+        return BundleAdjustment(gba, kfs, mps, edges, cam, notIncluded, nIterations, robust);
+    }
+    static PslGbaInfo GlobalBundleAdjustemntDevice(GlobalBundleAdjuster& gba, const PslBaKeyFrame* d_kf, int nkf, const PslMapPointGeom* d_mp, int nmp,
+                                                   const PslBaEdge* d_edges, int nedges, const PslCamera& cam, int nIterations, bool robust,
+                                                   PslBaKeyFrame* d_kfOut, PslMapPointGeom* d_mpOut, uint8_t* d_notIncluded) {
+        return BundleAdjustmentDevice(gba, d_kf, nkf, d_mp, nmp, d_edges, nedges, cam, nIterations, robust, d_kfOut, d_mpOut, d_notIncluded);
     }
     // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) src/Optimizer.cc:2801-2996: pairs = one PslSim3Pair per
     // match that passes the set-up loop (:2854-2933), in KF1 keypoint order; S12 = what Sim3Solver hands over (src/LoopClosing.cc:
