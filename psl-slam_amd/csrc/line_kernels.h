@@ -94,12 +94,17 @@ __device__ __forceinline__ int psl_reflect101i(int p, int n) {
 // inline exactly as cv::resize computes them.  A 64 x 16 tile of the working image needs <= 82 x 22
 // blurred samples, i.e. <= 88 x 28 input pixels; they are staged once in LDS (reflect-101 applied
 // while loading), row sums and column sums are formed once per sample, and the bilinear step reads
-// the blurred tile.
+// the blurred tile.  One LDS array serves all three: the staged bytes lie in its first rows, the
+// row sums take their place, and the blurred samples take the place of the row sums (19 872 bytes
+// per workgroup with the row table: 8 workgroups per CU; three arrays were 35 280 bytes and 4).
 // ---------------------------------------------------------------------------------------------
 #define PSL_LS_IC 88
 #define PSL_LS_IR 28
 #define PSL_LS_BC 82
 #define PSL_LS_BR 22
+#define PSL_LS_ST ((PSL_LS_BR + 7) / 8)       // stages of the column pass: 8 blurred rows each
+#define PSL_LS_RR (8 * (PSL_LS_ST - 1) + 14)  // rows of s_rs: the last stage reads 14 rows from row 8 (ST - 1), unclamped
+#define PSL_LS_TRIPS ((PSL_LS_IR * ((PSL_LS_BC + 3) / 4) + 255) / 256)  // work items of the row pass per thread
 __device__ __forceinline__ void psl_lsd_src(int d, int ssize, int* s, float* f, bool clamp_coef) {
     const double sc = 1. / 0.8;
     float ff = (float)((d + 0.5) * sc - 0.5);
@@ -114,9 +119,13 @@ __device__ __forceinline__ void psl_lsd_src(int d, int ssize, int* s, float* f, 
 
 __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uint8_t* __restrict__ gray, int stride, size_t fstride,
                                                           double* __restrict__ scaled, int nframes, int xcd) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[PSL_LS_IR * PSL_LS_IC + 16];
-    __shared__ double s_rs[PSL_LS_IR * PSL_LS_BC];
-    __shared__ double s_bl[PSL_LS_BR * PSL_LS_BC];
+    __shared__ __attribute__((aligned(16))) double s_rs[PSL_LS_RR * PSL_LS_BC];
+    __shared__ int s_sy0[16], s_sy1[16];  // per row of the tile: its two blurred rows (as offsets into s_rs) and its weight
+    __shared__ float s_fy[16];
+    uint8_t* const s_in = reinterpret_cast<uint8_t*>(s_rs);
+    static_assert(PSL_LS_IR * PSL_LS_IC + 16 <= sizeof(s_rs), "the staged bytes lie in s_rs");
+    static_assert(sizeof(s_rs) + sizeof(s_sy0) + sizeof(s_sy1) + sizeof(s_fy) <= 160 * 1024 / 8, "8 workgroups per CU (7 would do: 160 KB / 7)");
+    static_assert(PSL_LS_ST * PSL_LS_BC <= 256, "the column pass is one item per thread: one barrier between its reads and its writes");
     const int tid = threadIdx.x;
     int tx, ty, frame;
     if (!psl_tile_frame((P.W + 63) / 64, nframes, xcd, &tx, &ty, &frame)) return;
@@ -134,6 +143,14 @@ __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uin
     by1 = min(max(s + 1, 0), P.h - 1);
     const int nbc = bx1 - bx0 + 1, nbr = by1 - by0 + 1;  // <= 82, <= 22 for scale 0.8
     const int nic = nbc + 6, nir = nbr + 6;
+    if (tid < 16) {  // the source rows and the weight of a row of the tile: once per tile, not once per pixel
+        int sy;
+        float fy;
+        psl_lsd_src(dy0 + tid, P.h, &sy, &fy, false);
+        s_sy0[tid] = (min(max(sy, 0), P.h - 1) - by0) * PSL_LS_BC;
+        s_sy1[tid] = (min(max(sy + 1, 0), P.h - 1) - by0) * PSL_LS_BC;
+        s_fy[tid] = fy;
+    }
     if (bx0 - 3 >= 0 && bx0 - 3 + nic <= P.w && bx0 - 3 + PSL_LS_IC <= stride) {
         // no column reflection in this tile (6 of 8 tile columns): whole rows as 22 dwords (unaligned in HBM, aligned in LDS)
         for (int k = tid; k < nir * (PSL_LS_IC / 4); k += 256) {
@@ -152,51 +169,75 @@ __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uin
     __syncthreads();
     // RowFilter: s = k0*S0; s += k1*S1; ...  A thread makes 4 adjacent row sums from 10 input bytes (three aligned dwords)
     // instead of reading 7 bytes per sum (the kernel was LDS-bound); 4 rather than 8 per thread so that the <= 588 work items
-    // fill the 256 threads in 3 even trips (8 per thread: 2 trips, the second one 20 % occupied).
+    // fill the 256 threads in 3 even trips (8 per thread: 2 trips, the second one 20 % occupied; measured again at 7 waves per
+    // SIMD with each symmetric product formed once: no faster).  The row sums overwrite the staged bytes: a thread takes the
+    // dwords of all its work items into registers, and the sums are written behind a barrier.
     {
         const int ngr = (nbc + 3) >> 2;  // <= 21
         const uint32_t mgr = (1048576u + (uint32_t)ngr - 1u) / (uint32_t)ngr;
-        for (int k = tid; k < nir * ngr; k += 256) {
-            const int r = (int)(((uint32_t)k * mgr) >> 20), g = k - r * ngr;
-            const uint32_t* in32 = reinterpret_cast<const uint32_t*>(&s_in[r * PSL_LS_IC + 4 * g]);
-            const uint32_t w0 = in32[0], w1 = in32[1], w2 = in32[2];
-            double v[10];
+        uint32_t w[PSL_LS_TRIPS][3];
 #pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const uint32_t w = j < 4 ? w0 : (j < 8 ? w1 : w2);
-                v[j] = (double)((w >> (8 * (j & 3))) & 0xffu);
+        for (int t = 0; t < PSL_LS_TRIPS; ++t) {
+            const int k = tid + 256 * t;
+            if (k < nir * ngr) {
+                const int r = (int)(((uint32_t)k * mgr) >> 20), g = k - r * ngr;
+                const uint32_t* in32 = reinterpret_cast<const uint32_t*>(&s_in[r * PSL_LS_IC + 4 * g]);
+                w[t][0] = in32[0]; w[t][1] = in32[1]; w[t][2] = in32[2];
             }
+        }
+        __syncthreads();
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                if (4 * g + o < nbc) {
-                    double acc = PSL_DMUL(P.gk[0], v[o]);
+        for (int t = 0; t < PSL_LS_TRIPS; ++t) {
+            const int k = tid + 256 * t;
+            if (k < nir * ngr) {
+                const int r = (int)(((uint32_t)k * mgr) >> 20), g = k - r * ngr;
+                double v[10];
 #pragma unroll
-                    for (int j = 1; j < 7; ++j) acc = PSL_DADD(acc, PSL_DMUL(P.gk[j], v[o + j]));
-                    s_rs[r * PSL_LS_BC + 4 * g + o] = acc;
+                for (int j = 0; j < 10; ++j) v[j] = (double)((w[t][j >> 2] >> (8 * (j & 3))) & 0xffu);
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    if (4 * g + o < nbc) {
+                        double acc = PSL_DMUL(P.gk[0], v[o]);
+#pragma unroll
+                        for (int j = 1; j < 7; ++j) acc = PSL_DADD(acc, PSL_DMUL(P.gk[j], v[o + j]));
+                        s_rs[r * PSL_LS_BC + 4 * g + o] = acc;
+                    }
                 }
             }
         }
     }
     __syncthreads();
     // SymmColumnFilter: centre, then (S[k] + S[-k]) * ky[k].  A thread makes 8 vertically adjacent samples of one
-    // column from 14 row sums read once.
+    // column from 14 row sums read once.  The blurred samples take the place of the row sums they were made from: stage st
+    // reads rows 8 st .. 8 st + 13 and writes rows 8 st .. 8 st + 7, and every thread holds its samples in registers before the
+    // barrier, so no stage sees another stage's output.
     {
-        const int nst = (nbr + 7) >> 3;  // <= 3
-        for (int k = tid; k < nst * nbc; k += 256) {
-            const int st = k / nbc, c = k - st * nbc;
-            const int r0 = st * 8;
+        const int nst = (nbr + 7) >> 3;  // <= PSL_LS_ST
+        const uint32_t mbc = (1048576u + (uint32_t)nbc - 1u) / (uint32_t)nbc;
+        const int st = (int)(((uint32_t)tid * mbc) >> 20), c = tid - st * nbc;
+        const int r0 = st * 8;
+        const bool mine = tid < nst * nbc;
+        double bl[8];
+        if (mine) {
+            const double* col = &s_rs[r0 * PSL_LS_BC + c];  // rows past nir - 1 hold anything: only samples past nbr - 1 would take them
             double v[14];
 #pragma unroll
-            for (int j = 0; j < 14; ++j) v[j] = s_rs[min(r0 + j, nir - 1) * PSL_LS_BC + c];
+            for (int j = 0; j < 14; ++j) v[j] = col[j * PSL_LS_BC];
 #pragma unroll
             for (int o = 0; o < 8; ++o) {
                 if (r0 + o < nbr) {
                     double acc = PSL_DMUL(P.gk[3], v[o + 3]);
 #pragma unroll
                     for (int j = 1; j <= 3; ++j) acc = PSL_DADD(acc, PSL_DMUL(P.gk[3 + j], PSL_DADD(v[o + 3 + j], v[o + 3 - j])));
-                    s_bl[(r0 + o) * PSL_LS_BC + c] = acc;
+                    bl[o] = acc;
                 }
             }
+        }
+        __syncthreads();
+        if (mine) {
+#pragma unroll
+            for (int o = 0; o < 8; ++o)
+                if (r0 + o < nbr) s_rs[(r0 + o) * PSL_LS_BC + c] = bl[o];
         }
     }
     __syncthreads();
@@ -204,24 +245,24 @@ __global__ __launch_bounds__(256) void k_lsd_scale_tiled(LineParams P, const uin
     float fx;
     psl_lsd_src(min(dx0 + (tid & 63), P.W - 1), P.w, &sx, &fx, true);  // a thread's four pixels share the column
     const double a0 = (double)(1.f - fx), a1 = (double)fx;
+    const int cx = sx - bx0;
+    double* const tile = scaled + ((size_t)frame * P.W * P.H + (size_t)dy0 * P.W + dx0);  // uniform: the stores take 32-bit offsets
     for (int k = tid; k < 64 * 16; k += 256) {
-        const int dx = dx0 + (k & 63), dy = dy0 + (k >> 6);
-        if (dx >= P.W || dy >= P.H) continue;
-        int sy;
-        float fy;
-        psl_lsd_src(dy, P.h, &sy, &fy, false);
+        const int row = k >> 6;
+        if (dx0 + (k & 63) >= P.W || dy0 + row >= P.H) continue;
+        const float fy = s_fy[row];
         const double b0 = (double)(1.f - fy), b1 = (double)fy;
-        const int sy0 = min(max(sy, 0), P.h - 1) - by0, sy1 = min(max(sy + 1, 0), P.h - 1) - by0;
-        const int cx = sx - bx0;
+        const double* const bl0 = &s_rs[s_sy0[row] + cx];
+        const double* const bl1 = &s_rs[s_sy1[row] + cx];
         double h0, h1;
         if (sx + 1 < P.w) {
-            h0 = PSL_DADD(PSL_DMUL(s_bl[sy0 * PSL_LS_BC + cx], a0), PSL_DMUL(s_bl[sy0 * PSL_LS_BC + cx + 1], a1));
-            h1 = PSL_DADD(PSL_DMUL(s_bl[sy1 * PSL_LS_BC + cx], a0), PSL_DMUL(s_bl[sy1 * PSL_LS_BC + cx + 1], a1));
+            h0 = PSL_DADD(PSL_DMUL(bl0[0], a0), PSL_DMUL(bl0[1], a1));
+            h1 = PSL_DADD(PSL_DMUL(bl1[0], a0), PSL_DMUL(bl1[1], a1));
         } else {
-            h0 = s_bl[sy0 * PSL_LS_BC + cx];
-            h1 = s_bl[sy1 * PSL_LS_BC + cx];
+            h0 = bl0[0];
+            h1 = bl1[0];
         }
-        scaled[(size_t)frame * P.W * P.H + (size_t)dy * P.W + dx] = PSL_DADD(PSL_DMUL(h0, b0), PSL_DMUL(h1, b1));
+        tile[(uint32_t)(row * P.W + (k & 63))] = PSL_DADD(PSL_DMUL(h0, b0), PSL_DMUL(h1, b1));
     }
 }
 
