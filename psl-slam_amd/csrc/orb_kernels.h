@@ -71,6 +71,40 @@ __device__ __forceinline__ const uint8_t* psl_level_ptr(const OrbParams& P, cons
     return S.pyr + (size_t)frame * S.pyr_fstride + P.lv[level].img_off;
 }
 
+// One row operation of the data-parallel primitives: lane i receives v of the lane that CTRL names inside its row of 16.
+#define PSL_DPP_QUAD_1032 0xb1     // quad_perm [1, 0, 3, 2]: lane ^ 1
+#define PSL_DPP_QUAD_2301 0x4e     // quad_perm [2, 3, 0, 1]: lane ^ 2
+#define PSL_DPP_HALF_MIRROR 0x141  // lane i of a half row <- lane 7 - i
+#define PSL_DPP_MIRROR 0x140       // lane i of a row <- lane 15 - i
+#define PSL_DPP_ROW_SHR(n) (0x110 + (n))  // lane i of a row <- lane i - n, 0 where the row has no such lane
+template <int CTRL>
+__device__ __forceinline__ int psl_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+
+// Sum of v over the 64 lanes as a scalar: four row operations leave the sum of a row of 16 in each of its lanes (after the two
+// quad steps the four lanes of a quad agree, so a mirror brings in the other quads), v_readlane collects the four rows.  No LDS.
+__device__ __forceinline__ int psl_wave_sum(int v) {
+    v += psl_dpp<PSL_DPP_QUAD_1032>(v);
+    v += psl_dpp<PSL_DPP_QUAD_2301>(v);
+    v += psl_dpp<PSL_DPP_HALF_MIRROR>(v);
+    v += psl_dpp<PSL_DPP_MIRROR>(v);
+    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+           __builtin_amdgcn_readlane(v, 48);
+}
+
+// Inclusive prefix sum of v over the 64 lanes, and the sum of all as a scalar: four shifted adds give the prefix inside each row
+// of 16, v_readlane takes the totals of the four rows and a lane adds those of the rows before its own.  No LDS.
+__device__ __forceinline__ int psl_wave_prefix(int v, int* total) {
+    v += psl_dpp<PSL_DPP_ROW_SHR(1)>(v);
+    v += psl_dpp<PSL_DPP_ROW_SHR(2)>(v);
+    v += psl_dpp<PSL_DPP_ROW_SHR(4)>(v);
+    v += psl_dpp<PSL_DPP_ROW_SHR(8)>(v);
+    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47),
+              t3 = __builtin_amdgcn_readlane(v, 63);
+    const int lane = (int)(threadIdx.x & 63);
+    *total = t0 + t1 + t2 + t3;
+    return v + (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Pyramid: level l from level l-1, cv::resize INTER_LINEAR 8UC1 fixed point (Appendix A.3).
 // Tables (xofs, alpha, yofs, beta) are built on the host exactly as OpenCV builds them.
@@ -282,7 +316,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
                                                       int* __restrict__ cellcnt, uint32_t* __restrict__ cellcand, int cell_begin) {
     __shared__ __attribute__((aligned(16))) uint32_t s_tile32[(PSL_MAXCELL + 6) * (PSL_FAST4_TP / 4) + 4];
     __shared__ __attribute__((aligned(16))) uint32_t s_score32[(PSL_MAXCELL + 2) * (PSL_FAST4_SP / 4)];
-    __shared__ uint32_t s_rowmask[2][PSL_MAXCELL][2];  // [iniTh | minTh][row][x >> 5]: NMS survivors
+    __shared__ __attribute__((aligned(16))) uint32_t s_rowmask[2][PSL_MAXCELL][2];  // [iniTh | minTh][row][x >> 5]: NMS survivors
     __shared__ int s_rowoff[PSL_MAXCELL];
     __shared__ uint16_t s_list[PSL_MAXCELL * PSL_MAXCELL];  // y << 6 | x | polarity << 12 of pixels that pass the quick test
     __shared__ int s_nlist, s_use, s_total;
@@ -317,21 +351,35 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     const bool aligned4 = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)pitch) & 3) == 0 && iniX >= 4 && maxX + 8 <= pitch;
     const int ndw = (tw + 4) >> 2;  // <= 18
     if (aligned4) {
-        const int gx0 = (iniX - 1) & ~3;
+        // A thread keeps its dword column d and steps through the rows, 256 / ndw rows per trip: the image address is the uniform
+        // base plus a 32-bit lane offset that advances by a uniform step, and the two LDS addresses advance by constants of the
+        // trip.  tid / ndw and 256 / ndw come from one reciprocal: (n + 0.5) / ndw lies at least 0.5 / 18 from the next integer
+        // and the product is good to 128 * 2^-22.  The same trip clears the score row of the same number, dwords 0 .. ndw - 1 of
+        // the rows 0 .. ih + 1 = th - 5: the score bytes that are ever read are 3 .. iw + 4 of those rows, and (iw + 4) >> 2 < ndw.
+        // Measured with the row prefix, the compaction slots and the output pass below: 34.85 -> 32.47 ms per 12288 dense frames
+        // (profiles/orb_blur_fast_ab.log).
         const uint32_t sh = (uint32_t)((iniX - 1) & 3);
-        const uint32_t mdw = (1048576u + (uint32_t)ndw - 1u) / (uint32_t)ndw;  // k / ndw == (k * mdw) >> 20 for k < 4096
-        for (int k = tid; k < th * ndw; k += 256) {
-            const int y = (int)(((uint32_t)k * mdw) >> 20), d = k - y * ndw;
-            const uint32_t* g = reinterpret_cast<const uint32_t*>(img + (size_t)(iniY + y) * pitch + gx0) + d;
-            s_tile32[y * (PSL_FAST4_TP / 4) + d] = psl_alignbyte(g[1], g[0], sh);
+        const float inv = __builtin_amdgcn_rcpf((float)ndw);
+        const int rstep = __builtin_amdgcn_readfirstlane((int)(256.5f * inv));  // uniform: the steps below stay scalar
+        const int y0 = (int)(((float)tid + 0.5f) * inv), d = tid - (int)__umul24((uint32_t)y0, (uint32_t)ndw);
+        if (y0 < rstep) {
+            uint32_t off = __umul24((uint32_t)(iniY + y0), (uint32_t)pitch) + (uint32_t)(((iniX - 1) & ~3) + 4 * d);
+            const uint32_t ostep = __umul24((uint32_t)rstep, (uint32_t)pitch);
+            uint32_t* t = &s_tile32[__umul24((uint32_t)y0, PSL_FAST4_TP / 4) + d];
+            uint32_t* sc = &s_score32[__umul24((uint32_t)y0, PSL_FAST4_SP / 4) + d];
+            for (int y = y0; y < th; y += rstep, off += ostep, t += rstep * (PSL_FAST4_TP / 4), sc += rstep * (PSL_FAST4_SP / 4)) {
+                const uint32_t* g = reinterpret_cast<const uint32_t*>(img + off);
+                *t = psl_alignbyte(g[1], g[0], sh);
+                if (y < ih + 2) *sc = 0;
+            }
         }
     } else {
         for (int y = wave; y < th; y += 4) {
             const uint8_t* row = img + (size_t)(iniY + y) * pitch + iniX;
             for (int x = lane; x < tw; x += 64) s_tile[y * PSL_FAST4_TP + 1 + x] = row[x];
         }
+        for (int k = tid; k < (ih + 2) * (PSL_FAST4_SP / 4); k += 256) s_score32[k] = 0;
     }
-    for (int k = tid; k < (ih + 2) * (PSL_FAST4_SP / 4); k += 256) s_score32[k] = 0;
     (&s_rowmask[0][0][0])[tid] = 0;  // 2 * 64 * 2 words
     if (tid == 0) s_nlist = 0;
     __syncthreads();
@@ -341,7 +389,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     const int npass = (nitems + 255) >> 8;   // <= 4
     const uint32_t magic = (1048576u + (uint32_t)ng - 1u) / (uint32_t)ng;  // idx / ng == (idx * magic) >> 20 for idx < 4096
     const int minTh = P.minTh, iniTh = P.iniTh;
-    const unsigned long long lt = (1ull << lane) - 1ull;
     // Quick reject (exact necessary condition): an arc of 9 contains one pixel of every opposite pair, so a pixel
     // with S >= minTh has, for the 4 pairs (0,8) (2,10) (4,12) (6,14), one member > v+minTh in each pair (polarity
     // bit 0) or one member < v-minTh in each pair (polarity bit 1).
@@ -397,12 +444,15 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
         if (tot) {
             int base = 0;
             if (lane == 0) base = atomicAdd(&s_nlist, tot);
-            base = __shfl(base, 0);
+            base = __builtin_amdgcn_readfirstlane(base);  // all 64 lanes are here: lane 0's
             const uint32_t e = (uint32_t)(y << 6) | (uint32_t)(4 * g);
-            if (m4 & 1) s_list[base + __popcll(b0 & lt)] = (uint16_t)(e | ((pol & 3) << 12));
-            if (m4 & 2) s_list[base + n0 + __popcll(b1 & lt)] = (uint16_t)((e + 1) | (((pol >> 2) & 3) << 12));
-            if (m4 & 4) s_list[base + n0 + n1 + __popcll(b2 & lt)] = (uint16_t)((e + 2) | (((pol >> 4) & 3) << 12));
-            if (m4 & 8) s_list[base + n0 + n1 + n2 + __popcll(b3 & lt)] = (uint16_t)((e + 3) | (((pol >> 6) & 3) << 12));
+            // slot = first slot of the range + the ballot's bits below this lane (v_mbcnt adds them onto its last operand)
+#define PSL_SLOT(b, first) __builtin_amdgcn_mbcnt_hi((uint32_t)((b) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(b), (uint32_t)(first)))
+            if (m4 & 1) s_list[PSL_SLOT(b0, base)] = (uint16_t)(e | ((pol & 3) << 12));
+            if (m4 & 2) s_list[PSL_SLOT(b1, base + n0)] = (uint16_t)((e + 1) | (((pol >> 2) & 3) << 12));
+            if (m4 & 4) s_list[PSL_SLOT(b2, base + n0 + n1)] = (uint16_t)((e + 2) | (((pol >> 4) & 3) << 12));
+            if (m4 & 8) s_list[PSL_SLOT(b3, base + n0 + n1 + n2)] = (uint16_t)((e + 3) | (((pol >> 6) & 3) << 12));
+#undef PSL_SLOT
         }
     }
     __syncthreads();
@@ -437,30 +487,28 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells4(OrbParams P, FrameSrc S,
     if (wave == 0) {  // row counts -> raster offsets; retry at minTh only if iniTh found nothing (:812-816)
         const int c_ini = __popc(s_rowmask[0][lane][0]) + __popc(s_rowmask[0][lane][1]);
         const int c_min = __popc(s_rowmask[1][lane][0]) + __popc(s_rowmask[1][lane][1]);
-        int i_ini = c_ini, i_min = c_min;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(i_ini, o), v = __shfl_up(i_min, o);
-            if (lane >= o) { i_ini += u; i_min += v; }
-        }
-        const int t_ini = __shfl(i_ini, 63), t_min = __shfl(i_min, 63);
+        // both counts in one register (a cell has at most 64 * 64 pixels, so neither half carries), one prefix by row operations
+        // and v_readlane instead of two shuffle scans through LDS: this wave is what the other three wait for
+        int tot;
+        const int inc = psl_wave_prefix(c_ini | (c_min << 16), &tot);
+        const int i_ini = inc & 0xffff, i_min = inc >> 16, t_ini = tot & 0xffff, t_min = tot >> 16;
         const int use = t_ini > 0 ? 0 : 1;
         s_rowoff[lane] = use == 0 ? i_ini - c_ini : i_min - c_min;
         if (lane == 0) { s_use = use; s_total = use == 0 ? t_ini : t_min; }
     }
     __syncthreads();
     const int use = s_use, total = s_total;
+    // x + 3 + j wCell and y + 3 + i hCell are coordinates of the level and stay below 4096, so the two fields add without a carry
+    const uint32_t cell_xy = (uint32_t)(3 + j * L.wCell) | ((uint32_t)(3 + i * L.hCell) << 12);
+    const unsigned long long* rowmask = reinterpret_cast<const unsigned long long*>(&s_rowmask[use][0][0]);
     for (int k = tid; k < nlist; k += 256) {
         const int e = s_list[k];
         const int y = (e >> 6) & 63, x = e & 63;
-        const uint32_t w0 = s_rowmask[use][y][0], w1 = s_rowmask[use][y][1];
-        const uint32_t mine = x < 32 ? (w0 >> x) & 1 : (w1 >> (x - 32)) & 1;
-        if (mine) {
-            const int before = x < 32 ? __popc(w0 & ((1u << x) - 1u)) : __popc(w0) + __popc(w1 & ((1u << (x - 32)) - 1u));
-            const int pos = s_rowoff[y] + before;
+        const unsigned long long w = rowmask[y];  // words 0 and 1 of the row: bit x is pixel x
+        if ((w >> x) & 1ull) {
+            const int pos = s_rowoff[y] + __popcll(w & ((1ull << x) - 1ull));
             const uint32_t sc = s_score[(y + 1) * PSL_FAST4_SP + x + 4];
-            if (pos < P.cellcap)
-                out[pos] = (uint32_t)(x + 3 + j * L.wCell) | ((uint32_t)(y + 3 + i * L.hCell) << 12) | (sc << 24);
+            if (pos < P.cellcap) out[(uint32_t)pos] = (cell_xy + (uint32_t)x + ((uint32_t)y << 12)) | (sc << 24);
         }
     }
     if (tid == 0) *out_cnt = total < P.cellcap ? total : P.cellcap;
@@ -760,10 +808,27 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
     // s_in[r][c] holds pixel (x0 - 4 + c, y0 - 3 + r), c in [0, 72)
     const bool fast = x0 >= 4 && x0 + 68 <= L.w && ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)pitch) & 3) == 0;
     if (fast) {
-        for (int k = tid; k < rows * 18; k += 256) {
-            const int r = k / 18, c4 = k - r * 18;
-            const int gy = psl_reflect101(y0 + r - 3, L.h);
-            reinterpret_cast<uint32_t*>(s_in)[r * 18 + c4] = *reinterpret_cast<const uint32_t*>(img + (size_t)gy * pitch + x0 - 4 + c4 * 4);
+        // A thread keeps its column dword and steps through the rows, 14 rows of 18 dwords per trip (4 threads idle), so the one
+        // division is by a constant and outside the loop; the address is the uniform image base plus a 32-bit lane offset.
+        // Whether a row of the tile reflects is the same for the whole workgroup.  Where none does (every tile row but the
+        // level's first and last; such a tile has all 70 rows) the offset just advances by 14 rows and the five loads of a
+        // thread are issued before the first LDS store.  Measured with the column pass's seventh tap through v_dot2 and its
+        // 32-bit store offsets: 14.15 -> 12.09 ms per 12288 frames (profiles/orb_blur_fast_ab.log).
+        uint32_t* in32 = reinterpret_cast<uint32_t*>(s_in);
+        const int r0 = tid / 18, c4 = tid - r0 * 18;
+        const uint32_t col = (uint32_t)(x0 - 4 + c4 * 4), upitch = (uint32_t)pitch;
+        if (r0 < 14) {
+            if (y0 >= 3 && y0 + PSL_BLUR_TH + 3 <= L.h) {  // rows y0 - 3 .. y0 + 66 exist
+                uint32_t off = __umul24((uint32_t)(y0 + r0 - 3), upitch) + col;
+                uint32_t v[5];
+#pragma unroll
+                for (int t = 0; t < 5; ++t, off += 14u * upitch) v[t] = *reinterpret_cast<const uint32_t*>(img + off);
+#pragma unroll
+                for (int t = 0; t < 5; ++t) in32[tid + 252 * t] = v[t];  // (r0 + 14 t) * 18 + c4
+            } else {
+                for (int r = r0; r < rows; r += 14)
+                    in32[r * 18 + c4] = *reinterpret_cast<const uint32_t*>(img + (__umul24((uint32_t)psl_reflect101(y0 + r - 3, L.h), upitch) + col));
+            }
         }
     } else {
         for (int k = tid; k < rows * 72; k += 256) {
@@ -779,10 +844,15 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
     const uint32_t K0 = (uint32_t)P.blurK[0], K1 = (uint32_t)P.blurK[1], K2 = (uint32_t)P.blurK[2], K3 = (uint32_t)P.blurK[3];
     const u16x2 k0 = __builtin_bit_cast(u16x2, K0 | (K0 << 16)), k1 = __builtin_bit_cast(u16x2, K1 | (K1 << 16));
     const u16x2 k2 = __builtin_bit_cast(u16x2, K2 | (K2 << 16)), k3 = __builtin_bit_cast(u16x2, K3 | (K3 << 16));
-    for (int k = tid; k < rows * 16; k += 256) {
-        const int r = k >> 4, g = k & 15;
+    // A thread keeps its group of four columns and takes every 16th row: both LDS addresses are formed once and a trip adds a
+    // constant that the read and the write carry as their immediate offset.
+    const uint32_t* row_in = reinterpret_cast<const uint32_t*>(&s_in[(tid >> 4) * 72 + (tid & 15) * 4]);
+    uint2* row_out = reinterpret_cast<uint2*>(&s_row[(tid >> 4) * 64 + (tid & 15) * 4]);
+#pragma unroll
+    for (int t = 0; t < (PSL_BLUR_TH + 6 + 15) / 16; ++t) {
+        if ((tid >> 4) + 16 * t >= rows) break;
         // output x = x0 + 4g + j reads stream bytes (4g + j + 1) .. (4g + j + 7) of the row: three aligned dwords
-        const uint32_t* in32 = reinterpret_cast<const uint32_t*>(&s_in[r * 72 + g * 4]);
+        const uint32_t* in32 = row_in + t * (16 * 18);
         const uint32_t w0 = in32[0], w1 = in32[1], w2 = in32[2];
         // v[n] = stream byte n + 1; perm(hi, lo, sel): selector bytes 0-3 pick from lo, 4-7 from hi, 0x0c = zero
 #define PSL_PAIR(hi, lo, b0, b1) __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | (uint32_t)(b0) | ((uint32_t)(b1) << 16)))
@@ -792,39 +862,47 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
 #undef PSL_PAIR
         const u16x2 o01 = k0 * (p0 + p6) + k1 * (p1 + p5) + k2 * (p2 + p4) + k3 * p3;
         const u16x2 o23 = k0 * (p2 + p8) + k1 * (p3 + p7) + k2 * (p4 + p6) + k3 * p5;
-        *reinterpret_cast<uint2*>(&s_row[r * 64 + g * 4]) = make_uint2(__builtin_bit_cast(uint32_t, o01), __builtin_bit_cast(uint32_t, o23));
+        row_out[t * (16 * 16)] = make_uint2(__builtin_bit_cast(uint32_t, o01), __builtin_bit_cast(uint32_t, o23));
     }
     __syncthreads();
     // Column pass: a thread makes 4 adjacent pixels of 4 consecutive rows from 10 row-sum rows read once.  Two
     // vertically adjacent row sums of a pixel are paired into one register (v_perm) and meet their two
-    // coefficients in v_dot2_u32_u16; the 7th tap is a plain multiply-add.  Accumulators start at the rounding
-    // constant 2^15; min(acc, 2^24 - 1) >> 16 is saturate_cast<uchar>((acc) >> 16).
+    // coefficients in v_dot2_u32_u16.  The 7th tap (row i + 6, coefficient K0) goes the same way with a zero partner
+    // coefficient: rows 6, 7, 8 lead the pairs 6, 7, 8 and row 9 trails pair 8, so the one pair (8, 9) is all it adds.
+    // Accumulators start at the rounding constant 2^15; min(acc, 2^24 - 1) >> 16 is saturate_cast<uchar>((acc) >> 16).
     const int orows = rows - 6;
     uint8_t* dst = blur + (size_t)frame * blur_fstride + L.blur_off;
     const u16x2 c01 = __builtin_bit_cast(u16x2, K0 | (K1 << 16)), c23 = __builtin_bit_cast(u16x2, K2 | (K3 << 16));
     const u16x2 c45 = __builtin_bit_cast(u16x2, K2 | (K1 << 16));
+    const u16x2 c6 = __builtin_bit_cast(u16x2, K0), c_6 = __builtin_bit_cast(u16x2, K0 << 16);
     {
         const int g = tid & 15, oy0 = (tid >> 4) * 4;
         if (x0 + g * 4 < L.pitch && oy0 < orows) {
             uint2 q[10];
+            if (rows == PSL_BLUR_TH + 6) {  // a tile with all of its rows: oy0 + 9 <= 69, ten reads off one address
+                const uint2* col = reinterpret_cast<const uint2*>(&s_row[oy0 * 64 + g * 4]);
 #pragma unroll
-            for (int rr = 0; rr < 10; ++rr) q[rr] = *reinterpret_cast<const uint2*>(&s_row[min(oy0 + rr, rows - 1) * 64 + g * 4]);
+                for (int rr = 0; rr < 10; ++rr) q[rr] = col[rr * 16];
+            } else {
+#pragma unroll
+                for (int rr = 0; rr < 10; ++rr) q[rr] = *reinterpret_cast<const uint2*>(&s_row[min(oy0 + rr, rows - 1) * 64 + g * 4]);
+            }
             uint32_t acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int x = 0; x < 4; ++x) acc[i][x] = 1u << 15;
 #pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {  // pair of rows (rr, rr + 1)
+            for (int rr = 0; rr < 9; ++rr) {  // pair of rows (rr, rr + 1)
                 const u16x2 a0 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(q[rr + 1].x, q[rr].x, 0x05040100u));
                 const u16x2 a1 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(q[rr + 1].x, q[rr].x, 0x07060302u));
                 const u16x2 a2 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(q[rr + 1].y, q[rr].y, 0x05040100u));
                 const u16x2 a3 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(q[rr + 1].y, q[rr].y, 0x07060302u));
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {  // output row oy0 + i uses the pairs starting at i, i + 2, i + 4
+                for (int i = 0; i < 4; ++i) {  // output row oy0 + i uses the pairs starting at i, i + 2, i + 4 and row i + 6
                     const int m = rr - i;
-                    if (m == 0 || m == 2 || m == 4) {
-                        const u16x2 c = m == 0 ? c01 : (m == 2 ? c23 : c45);
+                    if (m == 0 || m == 2 || m == 4 || (m == 6 && i < 3) || (m == 5 && i == 3)) {
+                        const u16x2 c = m == 0 ? c01 : (m == 2 ? c23 : (m == 4 ? c45 : (m == 6 ? c6 : c_6)));
                         acc[i][0] = __builtin_amdgcn_udot2(a0, c, acc[i][0], false);
                         acc[i][1] = __builtin_amdgcn_udot2(a1, c, acc[i][1], false);
                         acc[i][2] = __builtin_amdgcn_udot2(a2, c, acc[i][2], false);
@@ -832,17 +910,16 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
                     }
                 }
             }
+            // the store address is the uniform base of the blurred level plus a 32-bit lane offset that advances by the pitch
+            uint32_t off = (uint32_t)(y0 + oy0) * (uint32_t)L.pitch + (uint32_t)(x0 + g * 4);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < 4; ++i, off += (uint32_t)L.pitch) {
                 if (oy0 + i >= orows) break;
-                const uint2 t = q[i + 6];  // 7th tap, coefficient K0
-                acc[i][0] += K0 * (t.x & 0xffff); acc[i][1] += K0 * (t.x >> 16);
-                acc[i][2] += K0 * (t.y & 0xffff); acc[i][3] += K0 * (t.y >> 16);
                 const uint32_t m0 = min(acc[i][0], 0xffffffu), m1 = min(acc[i][1], 0xffffffu);
                 const uint32_t m2 = min(acc[i][2], 0xffffffu), m3 = min(acc[i][3], 0xffffffu);
                 // byte 2 of each -> bytes 0..3
                 const uint32_t lo = __builtin_amdgcn_perm(m1, m0, 0x0c0c0602u), hi = __builtin_amdgcn_perm(m3, m2, 0x06020c0cu);
-                *reinterpret_cast<uint32_t*>(dst + (size_t)(y0 + oy0 + i) * L.pitch + x0 + g * 4) = lo | hi;
+                *reinterpret_cast<uint32_t*>(dst + off) = lo | hi;
             }
         }
     }
@@ -856,25 +933,6 @@ __global__ __launch_bounds__(256) void k_blur7(OrbParams P, FrameSrc S, uint8_t*
 __constant__ __attribute__((aligned(16))) float c_orb_pattern[1024] = {
 #include "orb_pattern.inc"
 };
-
-// One row operation of the data-parallel primitives: lane i receives v of the lane that CTRL names inside its row of 16.
-#define PSL_DPP_QUAD_1032 0xb1     // quad_perm [1, 0, 3, 2]: lane ^ 1
-#define PSL_DPP_QUAD_2301 0x4e     // quad_perm [2, 3, 0, 1]: lane ^ 2
-#define PSL_DPP_HALF_MIRROR 0x141  // lane i of a half row <- lane 7 - i
-#define PSL_DPP_MIRROR 0x140       // lane i of a row <- lane 15 - i
-template <int CTRL>
-__device__ __forceinline__ int psl_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
-// Sum of v over the 64 lanes as a scalar: four row operations leave the sum of a row of 16 in each of its lanes (after the two
-// quad steps the four lanes of a quad agree, so a mirror brings in the other quads), v_readlane collects the four rows.  No LDS.
-__device__ __forceinline__ int psl_wave_sum(int v) {
-    v += psl_dpp<PSL_DPP_QUAD_1032>(v);
-    v += psl_dpp<PSL_DPP_QUAD_2301>(v);
-    v += psl_dpp<PSL_DPP_HALF_MIRROR>(v);
-    v += psl_dpp<PSL_DPP_MIRROR>(v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
-}
 
 #define PSL_DESC_PD 11  // LDS pitch of the descriptor patch in dwords: 37 + 3 alignment bytes -> 10, odd pitch
 #define PSL_ORI_PD 9    // LDS pitch of the orientation patch in dwords: 31 + 3 alignment bytes -> 9
