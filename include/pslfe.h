@@ -1089,6 +1089,164 @@ int pslfe_kf_set_upkeep_sum(pslfe_kf* k, int layout);
  *    written.  Host arrays; returns after depth has arrived. */
 int pslfe_kf_scene_median_depth(pslfe_kf* k, const PslPose* Tcw, int K, const float* x, const int32_t* off, int q, float* depth);
 
+/* ---- LocalMapping::CreateNewMapPoints src/LocalMapping.cc:275-520 and CreateNewMapLines2 :522-759: the whole neighbour loop of one
+ * keyframe KF1 = mpCurrentKeyFrame against K neighbours, behind the two SearchForTriangulation matchers, in one launch chain.  The
+ * result equals K sequential iterations of the reference loop: a feature of KF1 that neighbour j gave a point (line) is, for every
+ * neighbour k > j, skipped by the search BEFORE its rotation histogram (src/ORBmatcher.cc:699-703; lines: dropped by the GetMapLine
+ * filter behind the matching, add_src/LSDmatcher.cpp:705-743).  vbMatched2 is never set (src/ORBmatcher.cc:686): two features of KF1 may
+ * take the same idx2, both are triangulated and both reported.  CheckNewKeyFrames() (:307, :555) and the abort flags are not modelled:
+ * the caller passes fewer neighbours.  The baseline gates :315-329 / :560-573 stay with the caller (pslfe_kf_scene_median_depth):
+ * `active`.  Arithmetic: the conventions above PslPose; psl-slam_amd/csrc/triangulate_kernels.h lists every step and is the text all
+ * forms run (the kernels, the host loop of tools/dropin/newpoints_main.cpp); tests/new_points_cases.py is its numpy restatement.
+ * OpenCV is not in the reference tree: parity with OpenCV itself is unpinned.  Kept as written:
+ *   - the right-image reprojection term of the SECOND keyframe uses mpCurrentKeyFrame->mbf (:474);
+ *   - bStereo2 of a line pair is read from the CURRENT keyframe's mvLineEq[idx2] (:607).  With idx2 >= NL1 the reference reads out of
+ *     range (undefined behaviour); THE LIBRARY DROPS THE PAIR with PSL_TRIL_IDX2_RANGE;
+ *   - KeyFrame::UnprojectStereo (src/KeyFrame.cc:731-747) reads mvKeys, the raw keypoints, and returns an empty Mat for z <= 0, on
+ *     which x3D.t() would throw: PSL_TRI_UNPROJECT_EMPTY;
+ *   - cos(2*atan2(mb/2, mvDepth)) are the float overloads (`using namespace std` of add_inc/LineExtractor.h:17 reaches the file).
+ * Status of a row: every `continue` of the two bodies has its own code. */
+#define PSL_TRI_CREATED 0          /* :501-517 */
+#define PSL_TRI_NO_MATCH 1         /* the search gave the query no idx2 (or the row is padding, q >= nq[k]) */
+#define PSL_TRI_TAKEN 2            /* idx1 received its point from an earlier neighbour: skipped by the search */
+#define PSL_TRI_INACTIVE 3         /* the neighbour failed the baseline gate */
+#define PSL_TRI_W_ZERO 4           /* x3D.at<float>(3) == 0 :401 */
+#define PSL_TRI_UNPROJECT_EMPTY 5  /* UnprojectStereo with z <= 0 */
+#define PSL_TRI_LOW_PARALLAX 6     /* :417 */
+#define PSL_TRI_DEPTH1 7           /* :423 */
+#define PSL_TRI_DEPTH2 8           /* :427 */
+#define PSL_TRI_REPROJ1_MONO 9     /* :443 */
+#define PSL_TRI_REPROJ1_STEREO 10  /* :454 */
+#define PSL_TRI_REPROJ2_MONO 11    /* :469 */
+#define PSL_TRI_REPROJ2_STEREO 12  /* :480 */
+#define PSL_TRI_DIST_ZERO 13       /* :490 */
+#define PSL_TRI_RATIO 14           /* :498 */
+#define PSL_TRIL_CREATED 0
+#define PSL_TRIL_NO_MATCH 1
+#define PSL_TRIL_TAKEN 2
+#define PSL_TRIL_INACTIVE 3
+#define PSL_TRIL_IDX2_RANGE 4      /* idx2 >= NL1: mvLineEq[idx2] of the current keyframe does not exist */
+#define PSL_TRIL_NO_STEREO 5       /* :639 */
+#define PSL_TRIL_DEPTH_SP1 6       /* :647 */
+#define PSL_TRIL_DEPTH_EP1 7       /* :651 */
+#define PSL_TRIL_DEPTH_SP2 8       /* :655 */
+#define PSL_TRIL_DEPTH_EP2 9       /* :659 */
+#define PSL_TRIL_REPROJ_SP1 10     /* :673 */
+#define PSL_TRIL_REPROJ_EP1 11     /* :685 */
+#define PSL_TRIL_REPROJ_SP2 12     /* :698 */
+#define PSL_TRIL_REPROJ_EP2 13     /* :709 */
+#define PSL_TRIL_DIST_ZERO 14      /* :725 */
+#define PSL_TRIL_RATIO 15          /* :733 */
+#define PSLFE_TRI_MAX_NEIGHBOURS 32
+/* mpCurrentKeyFrame: pose, fx fy cx cy, mb, mbf, ratioFactor = 1.5f*mfScaleFactor (:300), and its index in the caller's keyframe table
+ * (the `centres` of pslfe_kf_update_normal_and_depth). */
+typedef struct PslTriKeyFrame {
+    PslPose Tcw;
+    float fx, fy, cx, cy, mb, mbf, ratio_factor;
+    int32_t kf;
+} PslTriKeyFrame;
+/* One neighbour pKF2.  The line form reads active, kf, kf_first, Tcw, fx..cy alone. */
+typedef struct PslTriNeighbour {
+    int32_t active;    /* != 0: the baseline gate let it through                                              */
+    int32_t slot;      /* its slot in the frame store (mvKeysUn, mvuRight, descriptors)                      */
+    int32_t kf;        /* its index in the caller's keyframe table                                           */
+    int32_t kf_first;  /* != 0: the caller's mObservations (pointer order) iterates pKF2 before KF1          */
+    float F12[9];      /* ComputeF12(mpCurrentKeyFrame, pKF2), row-major                                     */
+    float ex, ey;      /* the epipole, src/ORBmatcher.cc:664-671                                             */
+    PslPose Tcw;
+    float fx, fy, cx, cy, mb;
+} PslTriNeighbour;
+typedef struct PslNewMapPoint {
+    float x, y, z;             /* x3D */
+    int32_t k, idx1, idx2;     /* the neighbour, the feature of KF1, the feature of the neighbour */
+} PslNewMapPoint;
+typedef struct PslNewMapLine {
+    float sp[3], ep[3];        /* the Vector6d of :737-739, as the floats it is filled from */
+    int32_t k, idx1, idx2;
+} PslNewMapLine;
+#ifdef __cplusplus
+static_assert(sizeof(PslTriKeyFrame) == 80 && sizeof(PslTriNeighbour) == 128 && sizeof(PslNewMapPoint) == 24 && sizeof(PslNewMapLine) == 36, "new-point PODs");
+#else
+_Static_assert(sizeof(PslTriKeyFrame) == 80 && sizeof(PslTriNeighbour) == 128 && sizeof(PslNewMapPoint) == 24 && sizeof(PslNewMapLine) == 36, "new-point PODs");
+#endif
+/* == CreateNewMapPoints :305-519.  Host arrays; returns after the outputs have arrived (one upload, two launches, one synchronisation).
+ *    KF1: N1 <= 4096 features: keysun1 = mvKeysUn (pt, octave are read), keys1 = mvKeys[i].pt as N1 x 2 floats, uright1 = mvuRight,
+ *    depth1 = mvDepth, taken1[i] != 0 <=> GetMapPoint(i) != NULL at the call.
+ *    Neighbour k (K <= PSLFE_TRI_MAX_NEIGHBOURS): nb[k]; its FeatureVector flattened in node order is fidx2[fidx_off[k] ..
+ *    fidx_off[k+1]) (at most 65535 entries); taken2, keys2 (x 2 floats: mvKeys[i].pt), depth2 hold its features at kp_off[k] ..
+ *    kp_off[k+1]); both offset arrays: K+1 entries ascending from 0.  Its query list, built from the state at the call as for
+ *    pslfe_kf_search_for_triangulation: rows k*nqmax .. k*nqmax + nq[k] of queries, idx1 (the feature of KF1 of the row; distinct inside
+ *    a neighbour, in [0, N1)) and qdesc (32 bytes per row); nqmax <= 4096, 0 <= nq[k] <= nqmax.  scale_factors / level_sigma2: the
+ *    nlevels (1..16) entries of mvScaleFactors / mvLevelSigma2, which the reference reads from both keyframes.
+ *    Outputs, rows k*nqmax + q, every row written: match = idx2 of the pair as neighbour k's search returns it or -1; status = PSL_TRI_*;
+ *    x3d = the triangulated point where the pair got that far, zeros otherwise (may be NULL).  nmatches[k] = the return value of
+ *    neighbour k's search (0 for an inactive one).  created_by[i] = the neighbour that gave feature i its point, or -1.  The list in
+ *    the reference's creation order (k ascending, then idx1 ascending: the order of vMatchedPairs): newp[0 .. *nnew), capacity N1;
+ *    geom (capacity N1, may be NULL) = the same rows as PslMapPointGeom with the position filled and the other fields 0.  The host
+ *    form writes all N1 rows of newp and geom: zeros behind *nnew.  The device form leaves the rows behind *d_nnew as they were.
+ *    Checks, before any device is touched: negative counts, N1 or nqmax > 4096, K > 32: PSLFE_E_INVALID; then K == 0: PSLFE_OK, nothing
+ *    written and nothing else looked at; then a NULL array or handle, nlevels outside 1..16, offsets that do not ascend from 0, nq[k]
+ *    outside [0, nqmax], an idx1 out of range or repeated inside a neighbour: PSLFE_E_INVALID; more than 65535 feature-vector entries
+ *    of one neighbour: PSLFE_E_CAPACITY; an ACTIVE neighbour's slot outside the store: PSLFE_E_INVALID, one that is not set:
+ *    PSLFE_E_STATE (the slot of an inactive neighbour is never looked at).  A
+ *    feature of the slot at or beyond kp_off[k+1] - kp_off[k] has no row in taken2 / keys2 / depth2 and is no candidate.  No output may
+ *    overlap an input or another output. */
+int pslfe_kf_create_new_map_points(pslfe_kf* k, pslfe_frame* f2, const PslTriKeyFrame* kf1, int N1, const PslKeyPoint* keysun1,
+                                   const float* keys1, const float* uright1, const float* depth1, const uint8_t* taken1,
+                                   const PslTriNeighbour* nb, int K, const int32_t* fidx2, const int32_t* fidx_off, const uint8_t* taken2,
+                                   const float* keys2, const float* depth2, const int32_t* kp_off, const PslTriQuery* queries,
+                                   const int32_t* idx1, const uint8_t* qdesc, const int32_t* nq, int nqmax, int only_stereo,
+                                   int check_orientation, const float* scale_factors, const float* level_sigma2, int nlevels,
+                                   int32_t* match, int32_t* status, float* x3d, int32_t* nmatches, int32_t* created_by,
+                                   PslNewMapPoint* newp, int32_t* nnew, PslMapPointGeom* geom);
+/* The same on device arrays: kf1, nb, fidx_off, kp_off, nq and the level tables stay host arrays, every other array is device memory;
+ * queued on the context's stream, no synchronisation.  The checks that need the contents of a device array (idx1) are the caller's.
+ * d_geom (N1 rows, 16-byte aligned; d_x3d too must not be NULL here) is written where pslfe_kf_update_normal_and_depth_device refreshes
+ * it in place: with M = N1, d_obs_off (N1 + 1 entries: 2*min(r, *nnew), so the rows behind the list have empty runs and keep their
+ * bytes), d_obs_kf (2*N1: the run (kf1->kf, nb[k].kf), the other way round when nb[k].kf_first), d_ref_kf = kf1->kf (the new point's
+ * mpRefKF is the current keyframe), d_ref_level = the octave of mvKeysUn[idx1]. */
+int pslfe_kf_create_new_map_points_device(pslfe_kf* k, pslfe_frame* f2, const PslTriKeyFrame* kf1, int N1, const PslKeyPoint* d_keysun1,
+                                          const float* d_keys1, const float* d_uright1, const float* d_depth1, const uint8_t* d_taken1,
+                                          const PslTriNeighbour* nb, int K, const int32_t* d_fidx2, const int32_t* fidx_off,
+                                          const uint8_t* d_taken2, const float* d_keys2, const float* d_depth2, const int32_t* kp_off,
+                                          const PslTriQuery* d_queries, const int32_t* d_idx1, const uint8_t* d_qdesc, const int32_t* nq,
+                                          int nqmax, int only_stereo, int check_orientation, const float* scale_factors,
+                                          const float* level_sigma2, int nlevels, int32_t* d_match, int32_t* d_status, float* d_x3d,
+                                          int32_t* d_nmatches, int32_t* d_created_by, PslNewMapPoint* d_newp, int32_t* d_nnew,
+                                          PslMapPointGeom* d_geom, int32_t* d_obs_off, int32_t* d_obs_kf, int32_t* d_ref_kf,
+                                          int32_t* d_ref_level);
+/* == CreateNewMapLines2 :554-757: pslfe_kf_line_search_for_triangulation_keyframes on (desc1, has_mapline1, desc2, off2, has_mapline2,
+ *    nnratio, TH, mutual) - its launch chain, its checks - followed on the same stream by the pair body for every row.  A pair of
+ *    neighbour k whose line of KF1 was created by a neighbour j < k is dropped with PSL_TRIL_TAKEN: that is the whole dependence between
+ *    neighbours, so one thread per line of KF1 walks k in order.  kls1 / kls2: mvKeyLines (end points and octave are read); lines3d1 /
+ *    lines3d2: mvLines3D as 6 doubles per line (camera frame); lineeq1[i] = mvLineEq[i][2] of KF1, NL1 entries; neighbour k's lines at
+ *    off2[k] .. off2[k+1].  scale_factors / level_sigma2: the POINT tables, as the reference reads mvScaleFactors / mvLevelSigma2 there.
+ *    Outputs, rows k*NL1 + i, every row written: match = the line of neighbour k or -1 (-1 for a taken pair: the reference's search
+ *    does not return it), status = PSL_TRIL_*, sp / ep (3 floats per row) = the world end points where the pair got that far;
+ *    nmatches[k] = the return value of neighbour k's search (an inactive neighbour: 0); created_by[i]; newl[0 .. *nnew) in creation
+ *    order (k ascending, then idx1 ascending), capacity NL1; geom (capacity NL1, may be NULL): sp, ep filled, the rest 0.  The host form
+ *    writes all NL1 rows of newl and geom: zeros behind *nnew; the device form leaves the rows behind *d_nnew as they were.
+ *    No output may overlap an input or another output, in either form and for points and lines alike: no aliasing is allowed.
+ *    Checks: those of the search first; NL1 > 65535 or K > 32: PSLFE_E_INVALID; K == 0: PSLFE_OK, nothing written; NL1 == 0: *nnew = 0 and
+ *    nmatches = 0; then NULL arrays, nlevels outside 1..16: PSLFE_E_INVALID. */
+int pslfe_kf_create_new_map_lines(pslfe_kf* k, const PslTriKeyFrame* kf1, int NL1, const uint8_t* desc1, const uint8_t* has_mapline1,
+                                  const PslKeyLine* kls1, const double* lines3d1, const float* lineeq1, const PslTriNeighbour* nb, int K,
+                                  const uint8_t* desc2, const int32_t* off2, const uint8_t* has_mapline2, const PslKeyLine* kls2,
+                                  const double* lines3d2, float nnratio, float TH, int mutual, const float* scale_factors,
+                                  const float* level_sigma2, int nlevels, int32_t* match, int32_t* status, float* sp, float* ep,
+                                  int32_t* nmatches, int32_t* created_by, PslNewMapLine* newl, int32_t* nnew, PslMapLineGeom* geom);
+/* The same on device arrays (kf1, nb, off2 and the level tables stay host arrays); queued on the context's stream.  d_geom (NL1 rows)
+ * and the observation runs are what pslfe_kf_line_update_average_dir_device takes with M = NL1, laid out as for the point form
+ * (d_ref_level = the octave of mvKeyLines[idx1]). */
+int pslfe_kf_create_new_map_lines_device(pslfe_kf* k, const PslTriKeyFrame* kf1, int NL1, const uint8_t* d_desc1, const uint8_t* d_has_mapline1,
+                                         const PslKeyLine* d_kls1, const double* d_lines3d1, const float* d_lineeq1, const PslTriNeighbour* nb,
+                                         int K, const uint8_t* d_desc2, const int32_t* off2, const uint8_t* d_has_mapline2,
+                                         const PslKeyLine* d_kls2, const double* d_lines3d2, float nnratio, float TH, int mutual,
+                                         const float* scale_factors, const float* level_sigma2, int nlevels, int32_t* d_match,
+                                         int32_t* d_status, float* d_sp, float* d_ep, int32_t* d_nmatches, int32_t* d_created_by,
+                                         PslNewMapLine* d_newl, int32_t* d_nnew, PslMapLineGeom* d_geom, int32_t* d_obs_off,
+                                         int32_t* d_obs_kf, int32_t* d_ref_kf, int32_t* d_ref_level);
+
 /* ---- Pose optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:239-1023), point edges and LIL edges ------------------
  * Called by TrackReferenceKeyFrame src/Tracking.cc:968, TrackWithMotionModel :1214, TrackLocalMap :1331 and, once per candidate,
  * Relocalization :2130-2161.

@@ -2136,6 +2136,18 @@ assert TRIQUERY_DTYPE.itemsize == 24 and LINEFUSEQUERY_DTYPE.itemsize == 24
 KFVIEW_DTYPE = np.dtype([("Tcw", POSE_DTYPE), ("T21", POSE_DTYPE), ("slot", "<i4")])
 assert KFVIEW_DTYPE.itemsize == 100
 KF_PROJ_FUSE, KF_PROJ_SCW, KF_PROJ_SIM3 = 0, 1, 2
+# the PODs of CreateNewMapPoints / CreateNewMapLines2 (include/pslfe.h): PslTriKeyFrame, PslTriNeighbour, PslNewMapPoint, PslNewMapLine
+TRIKEYFRAME_DTYPE = np.dtype([("Tcw", POSE_DTYPE)] + [(k, "<f4") for k in ("fx", "fy", "cx", "cy", "mb", "mbf", "ratio_factor")] + [("kf", "<i4")])
+TRINEIGHBOUR_DTYPE = np.dtype([("active", "<i4"), ("slot", "<i4"), ("kf", "<i4"), ("kf_first", "<i4"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4"),
+                               ("Tcw", POSE_DTYPE)] + [(k, "<f4") for k in ("fx", "fy", "cx", "cy", "mb")])
+NEWMAPPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("k", "<i4"), ("idx1", "<i4"), ("idx2", "<i4")])
+NEWMAPLINE_DTYPE = np.dtype([("sp", "<f4", (3,)), ("ep", "<f4", (3,)), ("k", "<i4"), ("idx1", "<i4"), ("idx2", "<i4")])
+assert (TRIKEYFRAME_DTYPE.itemsize, TRINEIGHBOUR_DTYPE.itemsize, NEWMAPPOINT_DTYPE.itemsize, NEWMAPLINE_DTYPE.itemsize) == (80, 128, 24, 36)
+TRI_MAX_NEIGHBOURS = 32
+TRI_STATUS = ("CREATED", "NO_MATCH", "TAKEN", "INACTIVE", "W_ZERO", "UNPROJECT_EMPTY", "LOW_PARALLAX", "DEPTH1", "DEPTH2", "REPROJ1_MONO",
+              "REPROJ1_STEREO", "REPROJ2_MONO", "REPROJ2_STEREO", "DIST_ZERO", "RATIO")                      # PSL_TRI_*
+TRIL_STATUS = ("CREATED", "NO_MATCH", "TAKEN", "INACTIVE", "IDX2_RANGE", "NO_STEREO", "DEPTH_SP1", "DEPTH_EP1", "DEPTH_SP2", "DEPTH_EP2",
+               "REPROJ_SP1", "REPROJ_EP1", "REPROJ_SP2", "REPROJ_EP2", "DIST_ZERO", "RATIO")                # PSL_TRIL_*
 UPKEEP_SUM_WALK, UPKEEP_SUM_TILED = 0, 1   # PSLFE_UPKEEP_SUM_*: KeyFrameMatcher.set_upkeep_sum
 
 
@@ -2430,6 +2442,153 @@ class KeyFrameMatcher:
                "pslfe_kf_line_search_for_triangulation_keyframes")
         return nm[:K], match
 
+    @staticmethod
+    def _new_points_args(kf1, keysun1, keys1, uright1, depth1, taken1, neighbours, fidx2, taken2, keys2, depth2, queries, idx1, qdesc,
+                         scale_factors, level_sigma2):
+        """the host arrays of pslfe_kf_create_new_map_points from per-neighbour lists -> a dict (kept alive by the caller)"""
+        a = {"kf1": np.ascontiguousarray(kf1, TRIKEYFRAME_DTYPE).reshape(1), "ku1": np.ascontiguousarray(keysun1, KEYPOINT_DTYPE).reshape(-1)}
+        N1 = a["N1"] = len(a["ku1"])
+        a["k1"] = np.ascontiguousarray(keys1, np.float32).reshape(N1, 2)
+        a["ur1"], a["dp1"] = np.ascontiguousarray(uright1, np.float32).reshape(N1), np.ascontiguousarray(depth1, np.float32).reshape(N1)
+        a["tk1"] = np.ascontiguousarray(taken1, np.uint8).reshape(N1)
+        a["nb"] = np.ascontiguousarray(neighbours, TRINEIGHBOUR_DTYPE).reshape(-1)
+        K = a["K"] = len(a["nb"])
+        if not all(len(x) == K for x in (fidx2, taken2, keys2, depth2, queries, idx1, qdesc)):
+            raise PslfeError(f"CreateNewMapPoints: the per-neighbour lists do not have {K} entries")
+        fl = [np.ascontiguousarray(f, np.int32).reshape(-1) for f in fidx2]
+        tl = [np.ascontiguousarray(t, np.uint8).reshape(-1) for t in taken2]
+        kl = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in keys2]
+        dl = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in depth2]
+        if any(len(t) != len(x) or len(t) != len(d) for t, x, d in zip(tl, kl, dl)):
+            raise PslfeError("CreateNewMapPoints: taken2, keys2 and depth2 of a neighbour differ in length")
+        a["foff"], a["koff"] = np.zeros(K + 1, np.int32), np.zeros(K + 1, np.int32)
+        a["foff"][1:], a["koff"][1:] = np.cumsum([len(f) for f in fl]), np.cumsum([len(t) for t in tl])
+        a["fidx"] = np.concatenate(fl + [np.zeros(0, np.int32)])
+        a["tk2"] = np.concatenate(tl + [np.zeros(0, np.uint8)])
+        a["k2"] = np.concatenate(kl + [np.zeros((0, 2), np.float32)])
+        a["dp2"] = np.concatenate(dl + [np.zeros(0, np.float32)])
+        ql = [np.ascontiguousarray(q, TRIQUERY_DTYPE).reshape(-1) for q in queries]
+        a["nq"] = np.array([len(q) for q in ql], np.int32).reshape(K)
+        nqmax = a["nqmax"] = int(a["nq"].max()) if K else 0
+        a["q"], a["i1"], a["qd"] = np.zeros((K, nqmax), TRIQUERY_DTYPE), np.zeros((K, nqmax), np.int32), np.zeros((K, nqmax, 32), np.uint8)
+        for k in range(K):
+            n = len(ql[k])
+            a["q"][k, :n], a["i1"][k, :n] = ql[k], np.asarray(idx1[k], np.int32).reshape(n)
+            a["qd"][k, :n] = np.asarray(qdesc[k], np.uint8).reshape(n, 32)
+        a["sf"], a["s2"] = np.ascontiguousarray(scale_factors, np.float32).reshape(-1), np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if len(a["sf"]) != len(a["s2"]):
+            raise PslfeError("CreateNewMapPoints: mvScaleFactors and mvLevelSigma2 differ in length")
+        return a
+
+    def CreateNewMapPoints(self, frame2, kf1, keysun1, keys1, uright1, depth1, taken1, neighbours, fidx2, taken2, keys2, depth2, queries, idx1,
+                           qdesc, scale_factors, level_sigma2, bOnlyStereo=False, checkOri=False, want_geom=True):
+        """LocalMapping::CreateNewMapPoints src/LocalMapping.cc:305-519 for KF1 against K neighbours in one call
+        (pslfe_kf_create_new_map_points).  kf1: TRIKEYFRAME_DTYPE; keysun1 (KEYPOINT_DTYPE[N1]) = mvKeysUn, keys1 [N1, 2] = mvKeys[i].pt,
+        uright1, depth1, taken1 [N1]; neighbours: TRINEIGHBOUR_DTYPE[K] (slots of frame2); per neighbour k the lists fidx2[k], taken2[k],
+        keys2[k], depth2[k] and its query list queries[k] (TRIQUERY_DTYPE), idx1[k], qdesc[k] built from the state at the call.
+        -> dict: match, status [K, nqmax], x3d [K, nqmax, 3], nmatches [K], created_by [N1], new (NEWMAPPOINT_DTYPE[nnew], creation order),
+        geom (MAPPOINT_DTYPE[nnew], position filled)."""
+        a = self._new_points_args(kf1, keysun1, keys1, uright1, depth1, taken1, neighbours, fidx2, taken2, keys2, depth2, queries, idx1, qdesc,
+                                  scale_factors, level_sigma2)
+        K, N1, nqmax = a["K"], a["N1"], a["nqmax"]
+        match, status = np.full((K, nqmax), -1, np.int32), np.full((K, nqmax), 1, np.int32)
+        x3d, nm, by = np.zeros((K, nqmax, 3), np.float32), np.zeros(max(K, 1), np.int32), np.full(max(N1, 1), -1, np.int32)
+        newp, geom, nnew = np.zeros(max(N1, 1), NEWMAPPOINT_DTYPE), np.zeros(max(N1, 1), MAPPOINT_DTYPE), C.c_int(0)
+        _check(lib().pslfe_kf_create_new_map_points(
+            self._h, frame2._h, _ptr(a["kf1"]), C.c_int(N1), _ptr(a["ku1"]), _ptr(a["k1"]), _ptr(a["ur1"]), _ptr(a["dp1"]), _ptr(a["tk1"]), _ptr(a["nb"]),
+            C.c_int(K), _ptr(a["fidx"]), _ptr(a["foff"]), _ptr(a["tk2"]), _ptr(a["k2"]), _ptr(a["dp2"]), _ptr(a["koff"]), _ptr(a["q"]), _ptr(a["i1"]),
+            _ptr(a["qd"]), _ptr(a["nq"]), C.c_int(nqmax), C.c_int(1 if bOnlyStereo else 0), C.c_int(1 if checkOri else 0), _ptr(a["sf"]), _ptr(a["s2"]),
+            C.c_int(len(a["sf"])), _ptr(match), _ptr(status), _ptr(x3d), _ptr(nm), _ptr(by), _ptr(newp), C.byref(nnew),
+            _ptr(geom) if want_geom else None), "pslfe_kf_create_new_map_points")
+        n = nnew.value
+        return {"match": match, "status": status, "x3d": x3d, "nmatches": nm[:K], "created_by": by[:N1], "new": newp[:n], "geom": geom[:n]}
+
+    def CreateNewMapPointsDevice(self, frame2, kf1, N1, d_keysun1, d_keys1, d_uright1, d_depth1, d_taken1, neighbours, d_fidx2, fidx_off, d_taken2,
+                                 d_keys2, d_depth2, kp_off, d_queries, d_idx1, d_qdesc, nq, nqmax, scale_factors, level_sigma2, d_match, d_status,
+                                 d_x3d, d_nmatches, d_created_by, d_newp, d_nnew, d_geom, d_obs_off, d_obs_kf, d_ref_kf, d_ref_level,
+                                 bOnlyStereo=False, checkOri=False):
+        """The same on device addresses (pslfe_kf_create_new_map_points_device): queued on the context's stream; d_geom and the
+        observation runs are what update_normal_and_depth_device takes with M = N1."""
+        k1, nb = np.ascontiguousarray(kf1, TRIKEYFRAME_DTYPE).reshape(1), np.ascontiguousarray(neighbours, TRINEIGHBOUR_DTYPE).reshape(-1)
+        foff, koff, nqa = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (fidx_off, kp_off, nq))
+        sf, s2 = np.ascontiguousarray(scale_factors, np.float32).reshape(-1), np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        v = lambda d: C.c_void_p(d) if d else None
+        _check(lib().pslfe_kf_create_new_map_points_device(
+            self._h, frame2._h, _ptr(k1), C.c_int(N1), v(d_keysun1), v(d_keys1), v(d_uright1), v(d_depth1), v(d_taken1), _ptr(nb), C.c_int(len(nb)),
+            v(d_fidx2), _ptr(foff), v(d_taken2), v(d_keys2), v(d_depth2), _ptr(koff), v(d_queries), v(d_idx1), v(d_qdesc), _ptr(nqa), C.c_int(nqmax),
+            C.c_int(1 if bOnlyStereo else 0), C.c_int(1 if checkOri else 0), _ptr(sf), _ptr(s2), C.c_int(len(sf)), v(d_match), v(d_status), v(d_x3d),
+            v(d_nmatches), v(d_created_by), v(d_newp), v(d_nnew), v(d_geom), v(d_obs_off), v(d_obs_kf), v(d_ref_kf), v(d_ref_level)),
+            "pslfe_kf_create_new_map_points_device")
+
+    @staticmethod
+    def _new_lines_args(kf1, ldesc1, has_mapline1, keylines1, lines3d1, lineeq1, neighbours, ldescs2, has_maplines2, keylines2, lines3d2,
+                        scale_factors, level_sigma2):
+        a = {"kf1": np.ascontiguousarray(kf1, TRIKEYFRAME_DTYPE).reshape(1), "d1": np.ascontiguousarray(ldesc1, np.uint8).reshape(-1, 32)}
+        n1 = a["n1"] = len(a["d1"])
+        a["h1"] = None if has_mapline1 is None else np.ascontiguousarray(has_mapline1, np.uint8).reshape(n1)
+        a["kl1"] = np.ascontiguousarray(keylines1, KEYLINE_DTYPE).reshape(n1)
+        a["l1"], a["eq1"] = np.ascontiguousarray(lines3d1, np.float64).reshape(n1, 6), np.ascontiguousarray(lineeq1, np.float32).reshape(n1)
+        a["nb"] = np.ascontiguousarray(neighbours, TRINEIGHBOUR_DTYPE).reshape(-1)
+        K = a["K"] = len(a["nb"])
+        if not all(len(x) == K for x in (ldescs2, keylines2, lines3d2)) or (has_maplines2 is not None and len(has_maplines2) != K):
+            raise PslfeError(f"CreateNewMapLines: the per-neighbour lists do not have {K} entries")
+        dd = [np.ascontiguousarray(x, np.uint8).reshape(-1, 32) for x in ldescs2]
+        kk = [np.ascontiguousarray(x, KEYLINE_DTYPE).reshape(-1) for x in keylines2]
+        ll = [np.ascontiguousarray(x, np.float64).reshape(-1, 6) for x in lines3d2]
+        if any(len(d) != len(k) or len(d) != len(l) for d, k, l in zip(dd, kk, ll)):
+            raise PslfeError("CreateNewMapLines: descriptors, keylines and 3-D lines of a neighbour differ in length")
+        a["off"] = np.zeros(K + 1, np.int32)
+        a["off"][1:] = np.cumsum([len(x) for x in dd])
+        a["d2"] = np.concatenate(dd + [np.zeros((0, 32), np.uint8)])
+        a["kl2"] = np.concatenate(kk + [np.zeros(0, KEYLINE_DTYPE)])
+        a["l2"] = np.concatenate(ll + [np.zeros((0, 6), np.float64)])
+        a["h2"] = None
+        if has_maplines2 is not None:
+            a["h2"] = np.concatenate([np.ascontiguousarray(x, np.uint8).reshape(-1) for x in has_maplines2] + [np.zeros(0, np.uint8)])
+            if len(a["h2"]) != a["off"][K]:
+                raise PslfeError("CreateNewMapLines: the GetMapLine bytes do not fit the neighbour lines")
+        a["sf"], a["s2"] = np.ascontiguousarray(scale_factors, np.float32).reshape(-1), np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if len(a["sf"]) != len(a["s2"]):
+            raise PslfeError("CreateNewMapLines: mvScaleFactors and mvLevelSigma2 differ in length")
+        return a
+
+    def CreateNewMapLines(self, kf1, ldesc1, has_mapline1, keylines1, lines3d1, lineeq1, neighbours, ldescs2, has_maplines2, keylines2, lines3d2,
+                          scale_factors, level_sigma2, nnratio=0.95, TH=None, mutual=True, want_geom=True):
+        """LocalMapping::CreateNewMapLines2 src/LocalMapping.cc:554-757 for KF1 against K neighbours in one call
+        (pslfe_kf_create_new_map_lines): the search of LineSearchForTriangulationKeyFrames, then the pair body.  keylines1
+        (KEYLINE_DTYPE[NL1]), lines3d1 [NL1, 6] doubles = mvLines3D, lineeq1 [NL1] = mvLineEq[i][2]; per neighbour ldescs2[k],
+        has_maplines2[k], keylines2[k], lines3d2[k]; scale_factors / level_sigma2 are the POINT tables.
+        -> dict: match, status [K, NL1], sp, ep [K, NL1, 3], nmatches [K], created_by [NL1], new (NEWMAPLINE_DTYPE[nnew]), geom."""
+        a = self._new_lines_args(kf1, ldesc1, has_mapline1, keylines1, lines3d1, lineeq1, neighbours, ldescs2, has_maplines2, keylines2, lines3d2,
+                                 scale_factors, level_sigma2)
+        K, n1 = a["K"], a["n1"]
+        match, status = np.full((K, n1), -1, np.int32), np.full((K, n1), 1, np.int32)
+        sp, ep = np.zeros((K, n1, 3), np.float32), np.zeros((K, n1, 3), np.float32)
+        nm, by = np.zeros(max(K, 1), np.int32), np.full(max(n1, 1), -1, np.int32)
+        newl, geom, nnew = np.zeros(max(n1, 1), NEWMAPLINE_DTYPE), np.zeros(max(n1, 1), MAPLINE_DTYPE), C.c_int(0)
+        _check(lib().pslfe_kf_create_new_map_lines(
+            self._h, _ptr(a["kf1"]), C.c_int(n1), _ptr(a["d1"]), _ptr(a["h1"]), _ptr(a["kl1"]), _ptr(a["l1"]), _ptr(a["eq1"]), _ptr(a["nb"]), C.c_int(K),
+            _ptr(a["d2"]), _ptr(a["off"]), _ptr(a["h2"]), _ptr(a["kl2"]), _ptr(a["l2"]), C.c_float(nnratio), C.c_float(self.TH_LOW if TH is None else TH),
+            C.c_int(1 if mutual else 0), _ptr(a["sf"]), _ptr(a["s2"]), C.c_int(len(a["sf"])), _ptr(match), _ptr(status), _ptr(sp), _ptr(ep), _ptr(nm),
+            _ptr(by), _ptr(newl), C.byref(nnew), _ptr(geom) if want_geom else None), "pslfe_kf_create_new_map_lines")
+        n = nnew.value
+        return {"match": match, "status": status, "sp": sp, "ep": ep, "nmatches": nm[:K], "created_by": by[:n1], "new": newl[:n], "geom": geom[:n]}
+
+    def CreateNewMapLinesDevice(self, kf1, NL1, d_desc1, d_has_mapline1, d_kls1, d_lines3d1, d_lineeq1, neighbours, d_desc2, off2, d_has_mapline2,
+                                d_kls2, d_lines3d2, scale_factors, level_sigma2, d_match, d_status, d_sp, d_ep, d_nmatches, d_created_by, d_newl,
+                                d_nnew, d_geom, d_obs_off, d_obs_kf, d_ref_kf, d_ref_level, nnratio=0.95, TH=None, mutual=True):
+        """The same on device addresses (pslfe_kf_create_new_map_lines_device); d_geom and the runs are what
+        line_update_average_dir_device takes with M = NL1."""
+        k1, nb = np.ascontiguousarray(kf1, TRIKEYFRAME_DTYPE).reshape(1), np.ascontiguousarray(neighbours, TRINEIGHBOUR_DTYPE).reshape(-1)
+        off = np.ascontiguousarray(off2, np.int32).reshape(-1)
+        sf, s2 = np.ascontiguousarray(scale_factors, np.float32).reshape(-1), np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        v = lambda d: C.c_void_p(d) if d else None
+        _check(lib().pslfe_kf_create_new_map_lines_device(
+            self._h, _ptr(k1), C.c_int(NL1), v(d_desc1), v(d_has_mapline1), v(d_kls1), v(d_lines3d1), v(d_lineeq1), _ptr(nb), C.c_int(len(nb)), v(d_desc2),
+            _ptr(off), v(d_has_mapline2), v(d_kls2), v(d_lines3d2), C.c_float(nnratio), C.c_float(self.TH_LOW if TH is None else TH),
+            C.c_int(1 if mutual else 0), _ptr(sf), _ptr(s2), C.c_int(len(sf)), v(d_match), v(d_status), v(d_sp), v(d_ep), v(d_nmatches), v(d_created_by),
+            v(d_newl), v(d_nnew), v(d_geom), v(d_obs_off), v(d_obs_kf), v(d_ref_kf), v(d_ref_level)), "pslfe_kf_create_new_map_lines_device")
+
     def ComputeDistinctiveDescriptors(self, desc, offsets):
         """src/MapPoint.cc:242-304 for many map points / lines at once -> best row per point (relative to its run)."""
         d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
@@ -2554,3 +2713,51 @@ def _lsd_search_for_triangulation_keyframes(self, ldesc1, ldescs2, has_mapline1,
 
 LSDmatcher.SearchForTriangulation = _lsd_search_for_triangulation
 LSDmatcher.SearchForTriangulationKeyFrames = _lsd_search_for_triangulation_keyframes
+
+
+class LocalMapping:
+    """LocalMapping::CreateNewMapPoints / CreateNewMapLines2 (src/LocalMapping.cc:275-520, :522-759) played on arrays, the way
+    Sim3Solver.ComputeSim3Candidates and PnPsolver.RelocalizeCandidates play their callers: the keyframes are dicts of the members the
+    reference reads, the map mutations (:502-517, :741-755) come back as lists."""
+
+    @staticmethod
+    def TriQueries(fvec1, fvec2, keysun1, uright1, taken1, only_stereo=False):
+        """the head of ORBmatcher::SearchForTriangulation src/ORBmatcher.cc:689-711: fvec = [(node, [features])] ascending by node.
+        -> (queries TRIQUERY_DTYPE, idx1, fidx2) in the reference's iteration order over the shared nodes."""
+        fidx2, start2 = [], {}
+        for node, feats in fvec2:
+            start2[node] = (len(fidx2), len(feats))
+            fidx2 += list(feats)
+        rows, idx1 = [], []
+        for node, feats in fvec1:
+            if node not in start2:
+                continue
+            for i in feats:
+                if taken1[i] or (only_stereo and not uright1[i] >= 0):
+                    continue
+                rows.append((start2[node][0], start2[node][1], keysun1["x"][i], keysun1["y"][i], keysun1["angle"][i], int(uright1[i] >= 0)))
+                idx1.append(i)
+        return np.array(rows, TRIQUERY_DTYPE).reshape(-1), np.array(idx1, np.int32), np.array(fidx2, np.int32)
+
+    @staticmethod
+    def CreateNewMapPoints(matcher, frame2, kf1, cur, neighbours, neigh, scale_factors, level_sigma2, checkOri=False):
+        """cur: dict(keysun, keys, uright, depth, taken, fvec, desc) of mpCurrentKeyFrame; neigh[k]: dict(keys, depth, taken, fvec) of
+        neighbour k, whose mvKeysUn / mvuRight / descriptors are slot neighbours[k]["slot"] of frame2.
+        -> (the dict of KeyFrameMatcher.CreateNewMapPoints, [(k, idx1, idx2, x3D)] in creation order = mlpRecentAddedMapPoints)."""
+        qs, i1s, fs, qds = [], [], [], []
+        for nb in neigh:
+            q, i1, f = LocalMapping.TriQueries(cur["fvec"], nb["fvec"], cur["keysun"], cur["uright"], cur["taken"])
+            qs.append(q); i1s.append(i1); fs.append(f); qds.append(np.asarray(cur["desc"], np.uint8).reshape(-1, 32)[i1])
+        r = matcher.CreateNewMapPoints(frame2, kf1, cur["keysun"], cur["keys"], cur["uright"], cur["depth"], cur["taken"], neighbours, fs,
+                                       [nb["taken"] for nb in neigh], [nb["keys"] for nb in neigh], [nb["depth"] for nb in neigh], qs, i1s, qds,
+                                       scale_factors, level_sigma2, False, checkOri)
+        return r, [(int(p["k"]), int(p["idx1"]), int(p["idx2"]), np.array([p["x"], p["y"], p["z"]], np.float32)) for p in r["new"]]
+
+    @staticmethod
+    def CreateNewMapLines(matcher, kf1, cur, neighbours, neigh, scale_factors, level_sigma2, nnratio=0.95):
+        """cur: dict(ldesc, has_mapline, keylines, lines3d, lineeq); neigh[k]: dict(ldesc, has_mapline, keylines, lines3d).
+        -> (the dict of KeyFrameMatcher.CreateNewMapLines, [(k, idx1, idx2, sp, ep)] in creation order = mlpRecentAddedMapLines)."""
+        r = matcher.CreateNewMapLines(kf1, cur["ldesc"], cur["has_mapline"], cur["keylines"], cur["lines3d"], cur["lineeq"], neighbours,
+                                      [nb["ldesc"] for nb in neigh], [nb["has_mapline"] for nb in neigh], [nb["keylines"] for nb in neigh],
+                                      [nb["lines3d"] for nb in neigh], scale_factors, level_sigma2, nnratio)
+        return r, [(int(p["k"]), int(p["idx1"]), int(p["idx2"]), p["sp"].copy(), p["ep"].copy()) for p in r["new"]]

@@ -64,6 +64,22 @@ __device__ __forceinline__ int psl_wave_sum(int v) {
     return v;
 }
 
+// exclusive scan of one int per thread over a workgroup of 256 threads; *total = the sum.  s_w: 4 ints of LDS.  Called by every thread.
+__device__ __forceinline__ int psl_block_scan_256(int v, int* s_w, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    __syncthreads();   // the previous call's reads of s_w
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    int base = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { if (w < wave) base += s_w[w]; sum += s_w[w]; }
+    *total = sum;
+    return base + incl - v;
+}
+
 // (k1, k2) <- the two smallest of {k1, k2, o1, o2}, given k1 <= k2 and o1 <= o2
 __device__ __forceinline__ void psl_merge2(uint32_t& k1, uint32_t& k2, uint32_t o1, uint32_t o2) {
     const uint32_t lo = min(k1, o1), hi = max(k1, o1);

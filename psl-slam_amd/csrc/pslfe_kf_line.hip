@@ -27,6 +27,7 @@
 #include "proj_kernels.h"
 #include "kf_project.h"
 #include "kf_line_kernels.h"
+#include "triangulate_kernels.h"
 
 #define PSL_KLP_BS 256
 #define PSL_KLF_LDS_MAX 512   // keylines of one keyframe staged in LDS (52 B each: 26 KB); more are read from global memory
@@ -247,6 +248,64 @@ __global__ __launch_bounds__(256) void k_line_tri_pairs(LineTriArgs A) {
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(A.nmatches + k, c);
 }
 
+// ---- CreateNewMapLines2 (src/LocalMapping.cc:554-757) behind the search -------------------------------------------------------------------
+// one thread per line of KF1 walks the neighbours in order: the only dependence is "this line has its map line by now"
+__global__ __launch_bounds__(256) void k_new_lines_walk(PslTriLineSet S) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < S.n1) psl_tri_line_walk(&S, i);
+}
+struct NewLinesList {
+    PslTriLineSet S;
+    int kf1;
+    int* nmatches;
+    PslNewMapLine* newl;
+    int* nnew;
+    PslMapLineGeom* geom;   // may be nullptr
+    int* obs_off;           // the four observation arrays: all or none
+    int* obs_kf;
+    int* ref_kf;
+    int* ref_level;
+};
+// the list in creation order (k ascending, idx1 ascending) and the counts; one workgroup
+__global__ __launch_bounds__(256) void k_new_lines_list(NewLinesList L) {
+    __shared__ int s_w[4];
+    const PslTriLineSet& S = L.S;
+    const int tid = threadIdx.x, n1 = S.n1;
+    const int per = (n1 + 255) / 256, i0 = tid * per, i9 = min(i0 + per, n1);
+    int nnew = 0;
+    for (int k = 0; k < S.K; ++k) {
+        int nm = 0, cnt = 0, total;
+        for (int i = i0; i < i9; ++i) { nm += S.match[(size_t)k * n1 + i] >= 0; cnt += S.created_by[i] == k; }
+        psl_block_scan_256(nm, s_w, &total);
+        if (tid == 0) L.nmatches[k] = total;
+        int pos = nnew + psl_block_scan_256(cnt, s_w, &total);
+        for (int i = i0; i < i9; ++i) {
+            if (S.created_by[i] != k) continue;
+            const size_t row = (size_t)k * n1 + i;
+            PslNewMapLine nl;
+            PslMapLineGeom g;
+            g.normal[0] = g.normal[1] = g.normal[2] = 0.0; g.min_dist = g.max_dist = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { nl.sp[c] = S.sp[3 * row + c]; nl.ep[c] = S.ep[3 * row + c]; g.sp[c] = (double)nl.sp[c]; g.ep[c] = (double)nl.ep[c]; }
+            nl.k = k; nl.idx1 = i; nl.idx2 = S.match[row];
+            L.newl[pos] = nl;
+            if (L.geom) L.geom[pos] = g;
+            if (L.obs_kf) {
+                const PslTriNeighbour* nb = S.nb + k;
+                L.obs_kf[2 * pos] = nb->kf_first ? nb->kf : L.kf1;
+                L.obs_kf[2 * pos + 1] = nb->kf_first ? L.kf1 : nb->kf;
+                L.ref_kf[pos] = L.kf1;
+                L.ref_level[pos] = S.kls1[i].octave;
+            }
+            ++pos;
+        }
+        nnew += total;
+    }
+    if (tid == 0) *L.nnew = nnew;
+    if (L.obs_off)
+        for (int r = tid; r <= n1; r += 256) L.obs_off[r] = 2 * min(r, nnew);
+}
+
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -374,14 +433,14 @@ int pslfe_kf_line_fuse_keyframes(pslfe_kf* k, const PslPose* Tcw, int K, const P
     return PSLFE_OK;
 }
 
-int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t* desc1, int n1, const uint8_t* has_mapline1, const uint8_t* desc2,
-                                                     const int32_t* off2, const uint8_t* has_mapline2, int K, float nnratio, float TH, int mutual,
-                                                     int32_t* match, int32_t* nmatches) {
-    static const char* who = "pslfe_kf_line_search_for_triangulation_keyframes";
+namespace {
+// the checks of the search, in its order; *done = 1: K == 0
+int line_tri_check(const char* who, pslfe_kf* k, const uint8_t* desc1, int n1, const uint8_t* desc2, const int32_t* off2, int K, bool outputs, int* done) {
+    *done = 0;
     PSL_REQUIRE(K >= 0 && K <= 32767 && n1 >= 0 && n1 < (1 << 20) && (double)K * (double)n1 <= (double)(INT_MAX / 4), PSLFE_E_INVALID,
                 "%s: K = %d, n1 = %d", who, K, n1);
-    if (K == 0) return PSLFE_OK;   // no neighbour: nothing to write
-    PSL_REQUIRE(nmatches && (n1 == 0 || (desc1 && match)), PSLFE_E_INVALID, "%s: NULL argument", who);
+    if (K == 0) { *done = 1; return PSLFE_OK; }   // no neighbour: nothing to write
+    PSL_REQUIRE(outputs && (n1 == 0 || desc1), PSLFE_E_INVALID, "%s: NULL argument", who);
     if (int rc = check_offsets(off2, K, "off2", who)) return rc;
     PSL_REQUIRE(off2[0] == 0, PSLFE_E_INVALID, "%s: off2[0] must be 0", who);
     for (int i = 0; i < K; ++i)
@@ -389,32 +448,43 @@ int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t*
     PSL_REQUIRE(off2[K] <= INT_MAX / 4, PSLFE_E_INVALID, "%s: %d neighbour lines", who, off2[K]);
     PSL_REQUIRE(off2[K] == 0 || desc2, PSLFE_E_INVALID, "%s: NULL neighbour descriptors", who);
     PSL_REQUIRE(k, PSLFE_E_INVALID, "%s: NULL handle", who);
-    for (int i = 0; i < K; ++i) nmatches[i] = 0;
-    if (n1 == 0) return PSLFE_OK;                        // ldesc1.rows == 0 (:715-716)
-    for (size_t i = 0; i < (size_t)K * n1; ++i) match[i] = -1;
-    const int n2all = off2[K];
-    if (n2all == 0) return PSLFE_OK;                     // every neighbour is empty
-    pslfe_ctx* ctx = k->ctx;
-    PSL_HIP(hipSetDevice(ctx->device));
+    return PSLFE_OK;
+}
+
+// The launch chain of the search, n1 > 0, inside an open scratch scope: A->match [K*n1] and A->nmatches [K] stay on the device.  The
+// descriptor and GetMapLine arrays are host arrays (uploaded) or, with on_device, device arrays.  With no neighbour line at all nothing
+// is launched: rows of -1.
+int line_tri_queue(const char* who, pslfe_ctx* ctx, const uint8_t* desc1, int n1, const uint8_t* has_mapline1, const uint8_t* desc2, const int32_t* off2,
+                   const uint8_t* has_mapline2, int K, float nnratio, float TH, int mutual, bool on_device, LineTriArgs* out) {
     hipStream_t st = ctx->stream;
-    if (int rc = psl_scratch_begin(ctx)) return rc;
+    const int n2all = off2[K];
     const size_t rows = (size_t)K * n1 + (size_t)n2all;
     hipError_t e = hipSuccess;
-    LineTriArgs A;
-    A.desc1 = psl_scratch_up(ctx, desc1, (size_t)n1 * 32, st, &e); A.n1 = n1;
-    A.desc2 = psl_scratch_up(ctx, desc2, (size_t)n2all * 32, st, &e);
-    A.off2 = psl_scratch_up(ctx, off2, (size_t)K + 1, st, &e); A.K = K;
-    A.has1 = has_mapline1 ? psl_scratch_up(ctx, has_mapline1, n1, st, &e) : nullptr;
-    A.has2 = has_mapline2 ? psl_scratch_up(ctx, has_mapline2, n2all, st, &e) : nullptr;
+    LineTriArgs& A = *out;
+    A.n1 = n1; A.K = K;
+    A.off2 = psl_scratch_up(ctx, off2, (size_t)K + 1, st, &e);
+    A.match = psl_scratch_up(ctx, (const int*)nullptr, (size_t)K * n1, st, &e);
+    A.nmatches = psl_scratch_up(ctx, (const int*)nullptr, K, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    PSL_HIP(hipMemsetAsync(A.nmatches, 0, (size_t)K * sizeof(int), st));
+    if (n2all == 0) {
+        PSL_HIP(hipMemsetAsync(A.match, 0xff, (size_t)K * n1 * sizeof(int), st));
+        return PSLFE_OK;
+    }
+    if (on_device) {
+        A.desc1 = desc1; A.desc2 = desc2; A.has1 = has_mapline1; A.has2 = has_mapline2;
+    } else {
+        A.desc1 = psl_scratch_up(ctx, desc1, (size_t)n1 * 32, st, &e);
+        A.desc2 = psl_scratch_up(ctx, desc2, (size_t)n2all * 32, st, &e);
+        A.has1 = has_mapline1 ? psl_scratch_up(ctx, has_mapline1, n1, st, &e) : nullptr;
+        A.has2 = has_mapline2 ? psl_scratch_up(ctx, has_mapline2, n2all, st, &e) : nullptr;
+    }
     A.knn_idx = psl_scratch_up(ctx, (const int*)nullptr, rows * 2, st, &e);
     A.knn_dist = psl_scratch_up(ctx, (const int*)nullptr, rows * 2, st, &e);
     A.mad = psl_scratch_up(ctx, (const float*)nullptr, rows * 2, st, &e);
     A.lm = psl_scratch_up(ctx, (const int*)nullptr, rows, st, &e);
     A.nnratio = nnratio; A.TH = TH; A.mutual = mutual != 0;
-    A.match = psl_scratch_up(ctx, (const int*)nullptr, (size_t)K * n1, st, &e);
-    A.nmatches = psl_scratch_up(ctx, (const int*)nullptr, K, st, &e);
     PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    PSL_HIP(hipMemsetAsync(A.nmatches, 0, (size_t)K * sizeof(int), st));
     int maxq = n1;
     if (A.mutual) for (int i = 0; i < K; ++i) maxq = off2[i + 1] - off2[i] > maxq ? off2[i + 1] - off2[i] : maxq;
     const int ndir = A.mutual ? 2 * K : K, dstep = A.mutual ? 1 : 2;   // without the mutual test the reverse directions are not read
@@ -426,8 +496,168 @@ int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t*
         PSL_STAGE_END(ctx, "kf.line_triangulation_set");
     }
     PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+
+// D: the device arrays of the pair body and of the list; the search's inputs as line_tri_queue takes them
+struct NewLinesDev {
+    const PslKeyLine* kls1; const double* l3d1; const float* lineeq1; const PslKeyLine* kls2; const double* l3d2;
+    int* match; int* status; float* sp; float* ep; int* nmatches; int* created_by; PslNewMapLine* newl; int* nnew; PslMapLineGeom* geom;
+    int* obs_off; int* obs_kf; int* ref_kf; int* ref_level;
+};
+int new_lines_queue(const char* who, pslfe_ctx* ctx, const PslTriKeyFrame* kf1, int NL1, const uint8_t* desc1, const uint8_t* has1,
+                    const PslTriNeighbour* nb, int K, const uint8_t* desc2, const int32_t* off2, const uint8_t* has2, float nnratio, float TH, int mutual,
+                    const float* scale_factors, const float* level_sigma2, int nlevels, bool on_device, const NewLinesDev& D) {
+    hipStream_t st = ctx->stream;
+    LineTriArgs T;
+    if (int rc = line_tri_queue(who, ctx, desc1, NL1, has1, desc2, off2, has2, K, nnratio, TH, mutual, on_device, &T)) return rc;
+    std::vector<PslTriCam> cams((size_t)K + 1);   // the set-up is host arithmetic: the same IEEE operations as in the kernels
+    for (int i = 0; i < K; ++i) psl_tri_cam_setup(&nb[i].Tcw, nb[i].fx, nb[i].fy, nb[i].cx, nb[i].cy, nb[i].mb, &cams[i]);
+    psl_tri_cam_setup(&kf1->Tcw, kf1->fx, kf1->fy, kf1->cx, kf1->cy, kf1->mb, &cams[K]);
+    hipError_t e = hipSuccess;
+    NewLinesList L;
+    PslTriLineSet& S = L.S;
+    S.cams = psl_scratch_up(ctx, cams.data(), (size_t)K + 1, st, &e);
+    S.nb = psl_scratch_up(ctx, nb, K, st, &e);
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    S.C1 = S.cams + K; S.K = K; S.n1 = NL1;
+    S.kls1 = D.kls1; S.l3d1 = D.l3d1; S.lineeq1 = D.lineeq1; S.kls2 = D.kls2; S.l3d2 = D.l3d2; S.off2 = T.off2; S.match0 = T.match;
+    for (int i = 0; i < PSL_TRI_LEVELS; ++i) { S.sf[i] = i < nlevels ? scale_factors[i] : 0.f; S.sig2[i] = i < nlevels ? level_sigma2[i] : 0.f; }
+    S.ratioFactor = kf1->ratio_factor;
+    S.match = D.match; S.status = D.status; S.sp = D.sp; S.ep = D.ep; S.created_by = D.created_by;
+    L.kf1 = kf1->kf; L.nmatches = D.nmatches; L.newl = D.newl; L.nnew = D.nnew; L.geom = D.geom;
+    L.obs_off = D.obs_off; L.obs_kf = D.obs_kf; L.ref_kf = D.ref_kf; L.ref_level = D.ref_level;
+    {
+        PSL_STAGE_BEGIN(ctx, "kf.new_lines");
+        k_new_lines_walk<<<(NL1 + 255) / 256, 256, 0, st>>>(S);
+        k_new_lines_list<<<1, 256, 0, st>>>(L);
+        PSL_STAGE_END(ctx, "kf.new_lines");
+    }
+    PSL_HIP(hipGetLastError());
+    return PSLFE_OK;
+}
+// the checks behind the search's: *done = 1 when there is nothing to queue
+int new_lines_check(const char* who, pslfe_kf* k, const PslTriKeyFrame* kf1, int NL1, const uint8_t* desc1, const PslTriNeighbour* nb, int K,
+                    const uint8_t* desc2, const int32_t* off2, const float* scale_factors, const float* level_sigma2, int nlevels, bool outputs,
+                    bool arrays, int* done) {
+    if (int rc = line_tri_check(who, k, desc1, NL1, desc2, off2, K, outputs, done)) return rc;
+    PSL_REQUIRE(NL1 <= 0xffff && K <= PSLFE_TRI_MAX_NEIGHBOURS, PSLFE_E_INVALID, "%s: NL1 = %d (max 65535), K = %d (max %d)", who, NL1, K,
+                PSLFE_TRI_MAX_NEIGHBOURS);
+    if (*done) return PSLFE_OK;
+    PSL_REQUIRE(kf1 && nb && scale_factors && level_sigma2 && arrays, PSLFE_E_INVALID, "%s: NULL argument", who);
+    PSL_REQUIRE(nlevels > 0 && nlevels <= PSL_TRI_LEVELS, PSLFE_E_INVALID, "%s: %d levels (max %d)", who, nlevels, PSL_TRI_LEVELS);
+    return PSLFE_OK;
+}
+}  // namespace
+
+int pslfe_kf_line_search_for_triangulation_keyframes(pslfe_kf* k, const uint8_t* desc1, int n1, const uint8_t* has_mapline1, const uint8_t* desc2,
+                                                     const int32_t* off2, const uint8_t* has_mapline2, int K, float nnratio, float TH, int mutual,
+                                                     int32_t* match, int32_t* nmatches) {
+    static const char* who = "pslfe_kf_line_search_for_triangulation_keyframes";
+    int done;
+    if (int rc = line_tri_check(who, k, desc1, n1, desc2, off2, K, nmatches && (n1 == 0 || match), &done)) return rc;
+    if (done) return PSLFE_OK;
+    for (int i = 0; i < K; ++i) nmatches[i] = 0;
+    if (n1 == 0) return PSLFE_OK;                        // ldesc1.rows == 0 (:715-716)
+    for (size_t i = 0; i < (size_t)K * n1; ++i) match[i] = -1;
+    if (off2[K] == 0) return PSLFE_OK;                   // every neighbour is empty
+    pslfe_ctx* ctx = k->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    LineTriArgs A;
+    if (int rc = line_tri_queue(who, ctx, desc1, n1, has_mapline1, desc2, off2, has_mapline2, K, nnratio, TH, mutual, false, &A)) return rc;
     PSL_HIP(hipMemcpyAsync(match, A.match, (size_t)K * n1 * 4, hipMemcpyDeviceToHost, st));
     PSL_HIP(hipMemcpyAsync(nmatches, A.nmatches, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipStreamSynchronize(st));
+    return PSLFE_OK;
+}
+
+int pslfe_kf_create_new_map_lines_device(pslfe_kf* k, const PslTriKeyFrame* kf1, int NL1, const uint8_t* d_desc1, const uint8_t* d_has_mapline1,
+                                         const PslKeyLine* d_kls1, const double* d_lines3d1, const float* d_lineeq1, const PslTriNeighbour* nb, int K,
+                                         const uint8_t* d_desc2, const int32_t* off2, const uint8_t* d_has_mapline2, const PslKeyLine* d_kls2,
+                                         const double* d_lines3d2, float nnratio, float TH, int mutual, const float* scale_factors,
+                                         const float* level_sigma2, int nlevels, int32_t* d_match, int32_t* d_status, float* d_sp, float* d_ep,
+                                         int32_t* d_nmatches, int32_t* d_created_by, PslNewMapLine* d_newl, int32_t* d_nnew, PslMapLineGeom* d_geom,
+                                         int32_t* d_obs_off, int32_t* d_obs_kf, int32_t* d_ref_kf, int32_t* d_ref_level) {
+    static const char* who = "pslfe_kf_create_new_map_lines_device";
+    int done;
+    const bool arrays = d_nnew && d_obs_off && (NL1 == 0 || (d_kls1 && d_lines3d1 && d_lineeq1 && d_status && d_sp && d_ep && d_created_by && d_newl &&
+                                                             d_geom && d_obs_kf && d_ref_kf && d_ref_level));
+    if (int rc = new_lines_check(who, k, kf1, NL1, d_desc1, nb, K, d_desc2, off2, scale_factors, level_sigma2, nlevels, d_nmatches && (NL1 == 0 || d_match),
+                                 arrays, &done))
+        return rc;
+    if (done) return PSLFE_OK;
+    PSL_REQUIRE(off2[K] == 0 || (d_kls2 && d_lines3d2), PSLFE_E_INVALID, "%s: NULL neighbour lines", who);
+    pslfe_ctx* ctx = k->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    if (NL1 == 0) {
+        PSL_HIP(hipMemsetAsync(d_nmatches, 0, (size_t)K * 4, ctx->stream));
+        PSL_HIP(hipMemsetAsync(d_nnew, 0, 4, ctx->stream));
+        PSL_HIP(hipMemsetAsync(d_obs_off, 0, 4, ctx->stream));
+        return PSLFE_OK;
+    }
+    const NewLinesDev D = {d_kls1, d_lines3d1, d_lineeq1, d_kls2, d_lines3d2, d_match, d_status, d_sp, d_ep, d_nmatches, d_created_by, d_newl, d_nnew,
+                           d_geom, d_obs_off, d_obs_kf, d_ref_kf, d_ref_level};
+    return new_lines_queue(who, ctx, kf1, NL1, d_desc1, d_has_mapline1, nb, K, d_desc2, off2, d_has_mapline2, nnratio, TH, mutual, scale_factors,
+                           level_sigma2, nlevels, true, D);
+}
+
+int pslfe_kf_create_new_map_lines(pslfe_kf* k, const PslTriKeyFrame* kf1, int NL1, const uint8_t* desc1, const uint8_t* has_mapline1,
+                                  const PslKeyLine* kls1, const double* lines3d1, const float* lineeq1, const PslTriNeighbour* nb, int K,
+                                  const uint8_t* desc2, const int32_t* off2, const uint8_t* has_mapline2, const PslKeyLine* kls2, const double* lines3d2,
+                                  float nnratio, float TH, int mutual, const float* scale_factors, const float* level_sigma2, int nlevels,
+                                  int32_t* match, int32_t* status, float* sp, float* ep, int32_t* nmatches, int32_t* created_by, PslNewMapLine* newl,
+                                  int32_t* nnew, PslMapLineGeom* geom) {
+    static const char* who = "pslfe_kf_create_new_map_lines";
+    int done;
+    const bool arrays = nnew && (NL1 == 0 || (kls1 && lines3d1 && lineeq1 && status && sp && ep && created_by && newl));
+    if (int rc = new_lines_check(who, k, kf1, NL1, desc1, nb, K, desc2, off2, scale_factors, level_sigma2, nlevels, nmatches && (NL1 == 0 || match), arrays,
+                                 &done))
+        return rc;
+    if (done) return PSLFE_OK;
+    PSL_REQUIRE(off2[K] == 0 || (kls2 && lines3d2), PSLFE_E_INVALID, "%s: NULL neighbour lines", who);
+    *nnew = 0;
+    for (int i = 0; i < K; ++i) nmatches[i] = 0;
+    if (NL1 == 0) return PSLFE_OK;
+    pslfe_ctx* ctx = k->ctx;
+    PSL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rc = psl_scratch_begin(ctx)) return rc;
+    hipError_t e = hipSuccess;
+    const size_t n1 = NL1, rows = (size_t)K * n1, n2 = off2[K] ? off2[K] : 1;
+    NewLinesDev D;
+    D.kls1 = psl_scratch_up(ctx, kls1, n1, st, &e);
+    D.l3d1 = psl_scratch_up(ctx, lines3d1, 6 * n1, st, &e);
+    D.lineeq1 = psl_scratch_up(ctx, lineeq1, n1, st, &e);
+    D.kls2 = psl_scratch_up(ctx, off2[K] ? kls2 : nullptr, n2, st, &e);
+    D.l3d2 = psl_scratch_up(ctx, off2[K] ? lines3d2 : nullptr, 6 * n2, st, &e);
+    D.match = psl_scratch_up(ctx, (const int*)nullptr, rows, st, &e);
+    D.status = psl_scratch_up(ctx, (const int*)nullptr, rows, st, &e);
+    D.sp = psl_scratch_up(ctx, (const float*)nullptr, rows * 3, st, &e);
+    D.ep = psl_scratch_up(ctx, (const float*)nullptr, rows * 3, st, &e);
+    D.nmatches = psl_scratch_up(ctx, (const int*)nullptr, K, st, &e);
+    D.created_by = psl_scratch_up(ctx, (const int*)nullptr, n1, st, &e);
+    D.newl = psl_scratch_up(ctx, (const PslNewMapLine*)nullptr, n1, st, &e);
+    D.nnew = psl_scratch_up(ctx, (const int*)nullptr, 1, st, &e);
+    D.geom = geom ? psl_scratch_up(ctx, (const PslMapLineGeom*)nullptr, n1, st, &e) : nullptr;
+    D.obs_off = D.obs_kf = D.ref_kf = D.ref_level = nullptr;
+    PSL_REQUIRE(e == hipSuccess, PSLFE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    PSL_HIP(hipMemsetAsync(D.newl, 0, n1 * sizeof(PslNewMapLine), st));   // the rows behind *nnew come back as zeros
+    if (geom) PSL_HIP(hipMemsetAsync(D.geom, 0, n1 * sizeof(PslMapLineGeom), st));
+    if (int rc = new_lines_queue(who, ctx, kf1, NL1, desc1, has_mapline1, nb, K, desc2, off2, has_mapline2, nnratio, TH, mutual, scale_factors,
+                                 level_sigma2, nlevels, false, D))
+        return rc;
+    PSL_HIP(hipMemcpyAsync(match, D.match, rows * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(status, D.status, rows * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(sp, D.sp, rows * 12, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(ep, D.ep, rows * 12, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(nmatches, D.nmatches, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(created_by, D.created_by, n1 * 4, hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(newl, D.newl, n1 * sizeof(PslNewMapLine), hipMemcpyDeviceToHost, st));
+    PSL_HIP(hipMemcpyAsync(nnew, D.nnew, 4, hipMemcpyDeviceToHost, st));
+    if (geom) PSL_HIP(hipMemcpyAsync(geom, D.geom, n1 * sizeof(PslMapLineGeom), hipMemcpyDeviceToHost, st));
     PSL_HIP(hipStreamSynchronize(st));
     return PSLFE_OK;
 }

@@ -1142,6 +1142,139 @@ public:
         check(pslfe_kf_scene_median_depth(h_, Tcw.data(), (int)Tcw.size(), x.data(), off.data(), q, depth.data()), "pslfe_kf_scene_median_depth");
         return depth;
     }
+    // LocalMapping::CreateNewMapPoints src/LocalMapping.cc:305-519 for mpCurrentKeyFrame against K neighbours in one call
+    // (pslfe_kf_create_new_map_points; include/pslfe.h states every array).  The arrays of neighbour k lie at fidxOff[k] / kpOff[k]; its
+    // query list at rows k*nqmax .. of queries, idx1 and qdesc.
+    struct NewPointsIn {
+        PslTriKeyFrame kf1;
+        std::vector<PslKeyPoint> keysUn1;
+        std::vector<float> keys1, uRight1, depth1;      // keys1: mvKeys[i].pt, 2 floats per feature
+        std::vector<uint8_t> taken1;
+        std::vector<PslTriNeighbour> neighbours;
+        std::vector<int32_t> fidx2, fidxOff, kpOff;
+        std::vector<uint8_t> taken2;
+        std::vector<float> keys2, depth2;
+        std::vector<PslTriQuery> queries;
+        std::vector<int32_t> idx1, nq;
+        std::vector<uint8_t> qdesc;
+        int nqmax = 0;
+        bool onlyStereo = false, checkOrientation = false;
+        std::vector<float> scaleFactors, levelSigma2;
+    };
+    struct NewPointsOut {
+        std::vector<int32_t> match, status, nmatches, createdBy;
+        std::vector<float> x3d;
+        std::vector<PslNewMapPoint> created;            // creation order: the order of mlpRecentAddedMapPoints
+        std::vector<PslMapPointGeom> geom;
+    };
+    NewPointsOut CreateNewMapPoints(FrameGrid& kf2, const NewPointsIn& in) {
+        const size_t K = in.neighbours.size(), N1 = in.keysUn1.size(), rows = K * (size_t)in.nqmax;
+        if (in.keys1.size() != 2 * N1 || in.uRight1.size() != N1 || in.depth1.size() != N1 || in.taken1.size() != N1 || in.fidxOff.size() != K + 1 ||
+            in.kpOff.size() != K + 1 || in.nq.size() != K || in.queries.size() != rows || in.idx1.size() != rows || in.qdesc.size() != rows * 32 ||
+            in.scaleFactors.size() != in.levelSigma2.size() || (size_t)in.fidxOff.back() > in.fidx2.size() || (size_t)in.kpOff.back() > in.taken2.size() ||
+            in.keys2.size() != 2 * in.taken2.size() || in.depth2.size() != in.taken2.size())
+            throw Error(PSLFE_E_INVALID, "CreateNewMapPoints: the arrays do not fit the counts");
+        NewPointsOut o;
+        o.match.assign(rows, -1); o.status.assign(rows, PSL_TRI_NO_MATCH); o.x3d.assign(rows * 3, 0.f); o.nmatches.assign(K, 0);
+        o.createdBy.assign(N1, -1); o.created.resize(N1); o.geom.resize(N1);
+        int32_t nnew = 0;
+        check(pslfe_kf_create_new_map_points(h_, kf2.get(), &in.kf1, (int)N1, in.keysUn1.data(), in.keys1.data(), in.uRight1.data(), in.depth1.data(),
+                                             in.taken1.data(), in.neighbours.data(), (int)K, in.fidx2.data(), in.fidxOff.data(), in.taken2.data(),
+                                             in.keys2.data(), in.depth2.data(), in.kpOff.data(), in.queries.data(), in.idx1.data(), in.qdesc.data(),
+                                             in.nq.data(), in.nqmax, in.onlyStereo ? 1 : 0, in.checkOrientation ? 1 : 0, in.scaleFactors.data(),
+                                             in.levelSigma2.data(), (int)in.scaleFactors.size(), o.match.data(), o.status.data(), o.x3d.data(),
+                                             o.nmatches.data(), o.createdBy.data(), o.created.data(), &nnew, o.geom.data()),
+              "pslfe_kf_create_new_map_points");
+        o.created.resize(nnew); o.geom.resize(nnew);
+        return o;
+    }
+    // The same on device arrays (pslfe_kf_create_new_map_points_device), queued on the context's stream: the per-neighbour host arrays and
+    // the level tables stay host vectors, everything else is HBM.  d_geom and the four observation arrays are what
+    // UpdateNormalAndDepthDevice takes with M = N1, so MapPoint::UpdateNormalAndDepth (:512) needs no read-back of the count.
+    struct NewPointsDevice {
+        const PslKeyPoint* d_keysUn1; const float* d_keys1; const float* d_uRight1; const float* d_depth1; const uint8_t* d_taken1;
+        const int32_t* d_fidx2; const uint8_t* d_taken2; const float* d_keys2; const float* d_depth2;
+        const PslTriQuery* d_queries; const int32_t* d_idx1; const uint8_t* d_qdesc;
+        int32_t* d_match; int32_t* d_status; float* d_x3d; int32_t* d_nmatches; int32_t* d_createdBy; PslNewMapPoint* d_created; int32_t* d_nnew;
+        PslMapPointGeom* d_geom; int32_t* d_obsOff; int32_t* d_obsKf; int32_t* d_refKf; int32_t* d_refLevel;
+    };
+    void CreateNewMapPointsDevice(FrameGrid& kf2, const PslTriKeyFrame& kf1, int N1, const std::vector<PslTriNeighbour>& neighbours,
+                                  const std::vector<int32_t>& fidxOff, const std::vector<int32_t>& kpOff, const std::vector<int32_t>& nq, int nqmax,
+                                  bool onlyStereo, bool checkOrientation, const std::vector<float>& scaleFactors,
+                                  const std::vector<float>& levelSigma2, const NewPointsDevice& d) {
+        const size_t K = neighbours.size();
+        if (fidxOff.size() != K + 1 || kpOff.size() != K + 1 || nq.size() != K || scaleFactors.size() != levelSigma2.size())
+            throw Error(PSLFE_E_INVALID, "CreateNewMapPointsDevice: the host arrays do not fit the neighbours");
+        check(pslfe_kf_create_new_map_points_device(h_, kf2.get(), &kf1, N1, d.d_keysUn1, d.d_keys1, d.d_uRight1, d.d_depth1, d.d_taken1,
+                                                    neighbours.data(), (int)K, d.d_fidx2, fidxOff.data(), d.d_taken2, d.d_keys2, d.d_depth2, kpOff.data(),
+                                                    d.d_queries, d.d_idx1, d.d_qdesc, nq.data(), nqmax, onlyStereo ? 1 : 0, checkOrientation ? 1 : 0,
+                                                    scaleFactors.data(), levelSigma2.data(), (int)scaleFactors.size(), d.d_match, d.d_status, d.d_x3d,
+                                                    d.d_nmatches, d.d_createdBy, d.d_created, d.d_nnew, d.d_geom, d.d_obsOff, d.d_obsKf, d.d_refKf,
+                                                    d.d_refLevel), "pslfe_kf_create_new_map_points_device");
+    }
+    // LocalMapping::CreateNewMapLines2 :554-757 (pslfe_kf_create_new_map_lines): the search of LineSearchForTriangulationKeyFrames, then
+    // the pair body.  Neighbour k's lines lie at off2[k] .. off2[k+1] of desc2, hasMapLine2 (may be empty), keyLines2, lines3d2.
+    struct NewLinesIn {
+        PslTriKeyFrame kf1;
+        std::vector<uint8_t> desc1, hasMapLine1;        // hasMapLine1 may be empty: none
+        std::vector<PslKeyLine> keyLines1;
+        std::vector<double> lines3d1;                   // mvLines3D, 6 per line
+        std::vector<float> lineEq1;                     // mvLineEq[i][2]
+        std::vector<PslTriNeighbour> neighbours;
+        std::vector<uint8_t> desc2, hasMapLine2;
+        std::vector<int32_t> off2;
+        std::vector<PslKeyLine> keyLines2;
+        std::vector<double> lines3d2;
+        float nnratio = 0.95f, TH = 50.f;
+        bool mutual = true;
+        std::vector<float> scaleFactors, levelSigma2;   // the POINT tables
+    };
+    struct NewLinesOut {
+        std::vector<int32_t> match, status, nmatches, createdBy;
+        std::vector<float> sp, ep;
+        std::vector<PslNewMapLine> created;
+        std::vector<PslMapLineGeom> geom;
+    };
+    NewLinesOut CreateNewMapLines(const NewLinesIn& in) {
+        const size_t K = in.neighbours.size(), n1 = in.keyLines1.size(), rows = K * n1;
+        if (in.desc1.size() != n1 * 32 || (!in.hasMapLine1.empty() && in.hasMapLine1.size() != n1) || in.lines3d1.size() != 6 * n1 || in.lineEq1.size() != n1 ||
+            in.off2.size() != K + 1 || (size_t)in.off2.back() > in.keyLines2.size() || in.desc2.size() != in.keyLines2.size() * 32 ||
+            in.lines3d2.size() != in.keyLines2.size() * 6 || (!in.hasMapLine2.empty() && in.hasMapLine2.size() != in.keyLines2.size()) ||
+            in.scaleFactors.size() != in.levelSigma2.size())
+            throw Error(PSLFE_E_INVALID, "CreateNewMapLines: the arrays do not fit the counts");
+        NewLinesOut o;
+        o.match.assign(rows, -1); o.status.assign(rows, PSL_TRIL_NO_MATCH); o.sp.assign(rows * 3, 0.f); o.ep.assign(rows * 3, 0.f);
+        o.nmatches.assign(K, 0); o.createdBy.assign(n1, -1); o.created.resize(n1); o.geom.resize(n1);
+        int32_t nnew = 0;
+        check(pslfe_kf_create_new_map_lines(h_, &in.kf1, (int)n1, in.desc1.data(), in.hasMapLine1.empty() ? nullptr : in.hasMapLine1.data(),
+                                            in.keyLines1.data(), in.lines3d1.data(), in.lineEq1.data(), in.neighbours.data(), (int)K, in.desc2.data(),
+                                            in.off2.data(), in.hasMapLine2.empty() ? nullptr : in.hasMapLine2.data(), in.keyLines2.data(),
+                                            in.lines3d2.data(), in.nnratio, in.TH, in.mutual ? 1 : 0, in.scaleFactors.data(), in.levelSigma2.data(),
+                                            (int)in.scaleFactors.size(), o.match.data(), o.status.data(), o.sp.data(), o.ep.data(), o.nmatches.data(),
+                                            o.createdBy.data(), o.created.data(), &nnew, o.geom.data()),
+              "pslfe_kf_create_new_map_lines");
+        o.created.resize(nnew); o.geom.resize(nnew);
+        return o;
+    }
+    // The same on device arrays (pslfe_kf_create_new_map_lines_device); d_geom and the runs are what LineUpdateAverageDirDevice takes with
+    // M = NL1.  d_hasMapLine1 / d_hasMapLine2 may be nullptr: none.
+    struct NewLinesDevice {
+        const uint8_t* d_desc1; const uint8_t* d_hasMapLine1; const PslKeyLine* d_keyLines1; const double* d_lines3d1; const float* d_lineEq1;
+        const uint8_t* d_desc2; const uint8_t* d_hasMapLine2; const PslKeyLine* d_keyLines2; const double* d_lines3d2;
+        int32_t* d_match; int32_t* d_status; float* d_sp; float* d_ep; int32_t* d_nmatches; int32_t* d_createdBy; PslNewMapLine* d_created;
+        int32_t* d_nnew; PslMapLineGeom* d_geom; int32_t* d_obsOff; int32_t* d_obsKf; int32_t* d_refKf; int32_t* d_refLevel;
+    };
+    void CreateNewMapLinesDevice(const PslTriKeyFrame& kf1, int NL1, const std::vector<PslTriNeighbour>& neighbours, const std::vector<int32_t>& off2,
+                                 float nnratio, float TH, bool mutual, const std::vector<float>& scaleFactors, const std::vector<float>& levelSigma2,
+                                 const NewLinesDevice& d) {
+        if (off2.size() != neighbours.size() + 1 || scaleFactors.size() != levelSigma2.size())
+            throw Error(PSLFE_E_INVALID, "CreateNewMapLinesDevice: the host arrays do not fit the neighbours");
+        check(pslfe_kf_create_new_map_lines_device(h_, &kf1, NL1, d.d_desc1, d.d_hasMapLine1, d.d_keyLines1, d.d_lines3d1, d.d_lineEq1, neighbours.data(),
+                                                   (int)neighbours.size(), d.d_desc2, off2.data(), d.d_hasMapLine2, d.d_keyLines2, d.d_lines3d2, nnratio, TH,
+                                                   mutual ? 1 : 0, scaleFactors.data(), levelSigma2.data(), (int)scaleFactors.size(), d.d_match, d.d_status,
+                                                   d.d_sp, d.d_ep, d.d_nmatches, d.d_createdBy, d.d_created, d.d_nnew, d.d_geom, d.d_obsOff, d.d_obsKf,
+                                                   d.d_refKf, d.d_refLevel), "pslfe_kf_create_new_map_lines_device");
+    }
 private:
     static void checkUpkeep(size_t n, const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKf, const std::vector<int32_t>& refKf,
                             const std::vector<int32_t>& refLevel, const std::vector<uint8_t>& skip, const char* who) {
